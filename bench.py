@@ -79,6 +79,39 @@ def pmc_traffic(kernel, pairs, io):
     return best
 
 
+DUMP_BYTES = 64 * 10 ** 6    # --dump-outputs: all .npy files together stay below this
+DUMP_SEED = 20240607         # the fixed row sample taken when a full dump would not fit
+
+
+def _as_float(a):
+    """An integer output as float32 where every value survives the round trip, else float64."""
+    f = a.astype(np.float32)
+    return f if np.array_equal(f.astype(np.float64), a.astype(np.float64)) else a.astype(np.float64)
+
+
+def dump_outputs(path, d_res, d_ops, n, res_dtype, rs):
+    """What the timed path (aim_align_device) handed back after the last timed step, as <path>/<name>.npy: one float array per
+    result field and, with CIGAR, `ops` = the ops rows with every byte outside [begin_offset, end_offset) zeroed (the rest of a row is
+    unspecified, aim_hip.h). When the whole batch would exceed DUMP_BYTES, the same seeded sample of pairs is taken for every array
+    (ascending; the `idx` field names the pairs)."""
+    import torch
+    res = np.frombuffer(d_res[: n * res_dtype.itemsize].cpu().numpy().tobytes(), dtype=res_dtype)
+    fields = {name: _as_float(res[name]) for name in res_dtype.names}
+    per_pair = sum(a.itemsize for a in fields.values()) + (2 * rs * 4 if d_ops is not None else 0)
+    k = min(n, (DUMP_BYTES - 256 * (len(fields) + 1)) // per_pair)
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    out = {name: a[rows] for name, a in fields.items()}
+    if d_ops is not None:
+        sel = torch.from_numpy(rows).to(d_ops.device)
+        ops = d_ops[: n * 2 * rs].view(n, 2 * rs).index_select(0, sel).cpu().numpy()
+        col = np.arange(2 * rs)[None, :]
+        inside = (col >= res["begin_offset"][rows][:, None]) & (col < res["end_offset"][rows][:, None])
+        out["ops"] = np.where(inside, ops, 0).astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _pinned(lib, capi, arr):
     """Copy a numpy array into pinned host memory (aim_host_alloc); returns (pointer, view)."""
     p = C.c_void_p()
@@ -169,7 +202,12 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group (RCCL) and run the final gather even at world size 1 (also AIM_BENCH_FORCE_DIST=1): "
                          "exercises the N > 1 exchange path on a single-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32/float64, at most 64 MB in all: "
+                         "a fixed seeded sample of pairs beyond that; rank 0's pairs). Same arguments, same inputs: two builds compare file by file")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -286,6 +324,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps          # HIP events on the launch stream
+    if args.dump_outputs and rank == 0:                     # (untimed; before any later launch reuses the buffers)
+        dump_outputs(args.dump_outputs, d_res, d_ops, n, res_dtype, rs)
     single_batch = None
     if nb > 1:   # the first batch alone (the round-4 figure): a sub-record, never `value`
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -38,6 +38,43 @@ def test_bench_single_gpu_line(built):
     assert d["e2e"]["packed"]["pairs_per_s"] > 0            # PCIe-inclusive leg: reported, never `value`
 
 
+def test_bench_dump_outputs(built, tmp_path):
+    """--dump-outputs: what the last timed step computed, as float .npy files that are the same from run to run with the same arguments
+    and agree with the CPU oracle. Score-only: the whole batch's {idx, score}. With CIGAR over the size bound: a seeded sample of pairs,
+    every result field plus their ops rows (bytes outside [begin_offset, end_offset) zeroed)."""
+    import numpy as np
+    from aim_amd import engine
+    from oracle import oracle
+    ms, rs = engine.launcher_sizes("wfa", 100, 0.01)
+    for n, extra in ((65536, []), (131072, ["--backtrace"])):
+        dumps = []
+        for k in range(2):
+            d = tmp_path / ("%d_%d" % (n, k))
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--pairs", str(n), "--steps", "2", "--warmup", "1",
+                                "--verify-pairs", "4096", "--no-cpu-baseline", "--no-e2e", "--no-default-io", "--dump-outputs", str(d)] + extra,
+                               capture_output=True, text=True, timeout=600, cwd=ROOT)
+            assert r.returncode == 0, r.stderr[-2000:]
+            assert _last_json(r.stdout)["steps"] == 2
+            assert sum(f.stat().st_size for f in d.iterdir()) <= 64 * 10 ** 6
+            dumps.append({f.stem: np.load(f) for f in d.glob("*.npy")})
+        a = dumps[0]
+        assert sorted(a) == (["begin_offset", "end_offset", "idx", "max_operations", "ops", "score", "status"] if extra else ["idx", "score"])
+        for name in a:
+            assert a[name].dtype in (np.float32, np.float64) and np.array_equal(a[name], dumps[1][name]), name
+        rows = a["idx"].astype(np.int64)
+        assert (len(rows) == n) if not extra else (0 < len(rows) < n and np.all(np.diff(rows) > 0))
+        req, pat, txt = engine.gen_pairs(42, 0, n, 100, 0.01, rs)
+        rows = rows[:2048]
+        ores, oops, worst = oracle.align_batch(oracle.params("wfa", ms, rs, reduce=True, backtrace=bool(extra)), req["pattern_len"][rows],
+                                               req["text_len"][rows], pat[rows], txt[rows], nthreads=4)
+        assert worst == 0 and np.array_equal(a["score"][:len(rows)], ores["score"])
+        if extra:
+            assert np.array_equal(a["begin_offset"][:len(rows)], ores["begin_offset"]) and np.array_equal(a["end_offset"][:len(rows)], ores["end_offset"])
+            for j in range(len(rows)):
+                b, e = int(ores["begin_offset"][j]), int(ores["end_offset"][j])
+                assert np.array_equal(a["ops"][j, b:e], oops[j, b:e]) and not a["ops"][j, :b].any() and not a["ops"][j, e:].any()
+
+
 def test_bench_two_ranks_control_flow(built):
     env = dict(os.environ, AIM_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
