@@ -16,7 +16,8 @@ LIB_PATH = os.environ.get("AIM_LIB") or os.path.join(_HERE, "libaim_hip.so")   #
 AIM_OK, AIM_EINVAL, AIM_ENODEV, AIM_ENOMEM, AIM_ESTATE, AIM_EALIGN = 0, -1, -2, -3, -4, -5
 ALGO_NW, ALGO_SWG, ALGO_WFA, ALGO_GENASM = 0, 1, 2, 3
 ALGO_BY_NAME = {"nw": ALGO_NW, "swg": ALGO_SWG, "wfa": ALGO_WFA, "genasm": ALGO_GENASM}
-FLAG_BACKTRACE, FLAG_REDUCE, FLAG_SWG_W16, FLAG_REQ8, FLAG_RES8 = 1, 2, 4, 8, 16
+FLAG_BACKTRACE, FLAG_REDUCE, FLAG_SWG_W16, FLAG_REQ8, FLAG_RES8, FLAG_ENDSFREE = 1, 2, 4, 8, 16, 32
+FEATURE_ENDSFREE = 1   # aim_features(): AIM_FLAG_ENDSFREE is honoured
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
 
 
@@ -25,6 +26,29 @@ class Params(C.Structure):
     _fields_ = [("algo", C.c_int32), ("match", C.c_int32), ("mismatch", C.c_int32), ("gap_o", C.c_int32),
                 ("gap_e", C.c_int32), ("gap_i", C.c_int32), ("gap_d", C.c_int32), ("max_score", C.c_int32),
                 ("read_size", C.c_int32), ("flags", C.c_uint32)]
+
+
+class EndsFreeParams(C.Structure):
+    """aim_endsfree_params_t: aim_params_t + the four free lengths of AIM_FLAG_ENDSFREE (include/aim_hip.h). The entry points
+    receive a pointer to `base` (params_ref); fields of the base read through, e.g. p.read_size."""
+    _fields_ = [("base", Params), ("pattern_begin_free", C.c_int32), ("pattern_end_free", C.c_int32),
+                ("text_begin_free", C.c_int32), ("text_end_free", C.c_int32)]
+
+    _own = ("base", "pattern_begin_free", "pattern_end_free", "text_begin_free", "text_end_free")
+
+    def __getattr__(self, name):   # only reached for names that are not fields of this structure
+        return getattr(self.base, name)
+
+    def __setattr__(self, name, value):   # fields of the base are written through: ef.flags |= FLAG_BACKTRACE reaches the library
+        if name not in self._own and hasattr(Params, name):
+            setattr(self.base, name, value)
+        else:
+            super().__setattr__(name, value)
+
+
+def params_ref(params):
+    """The `const aim_params_t *` argument for Params or EndsFreeParams (a pointer to the base of the extended struct)."""
+    return C.byref(params.base) if isinstance(params, EndsFreeParams) else C.byref(params)
 
 
 REQUEST_DTYPE = np.dtype([("pattern_len", "<i4"), ("text_len", "<i4"), ("padding", "<i4"), ("idx", "<u4")])
@@ -52,6 +76,7 @@ class BatchIO(C.Structure):
 _VP, _U32, _I32 = C.c_void_p, C.c_uint32, C.c_int32
 SYMBOLS = {
     "aim_abi_version": (C.c_int, []),
+    "aim_features": (C.c_uint32, []),
     "aim_last_error": (C.c_char_p, []),
     "aim_device_count": (C.c_int, [C.POINTER(C.c_int)]),
     "aim_set_alloc": (C.c_int, [_U32, C.POINTER(C.c_int), C.POINTER(_VP)]),

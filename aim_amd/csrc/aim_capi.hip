@@ -200,6 +200,28 @@ uint64_t stateless_budget_bytes(const aim::Knobs &kn)
     return cached[dev];
 }
 
+// AIM_FLAG_ENDSFREE: the params are the base of an aim_endsfree_params_t (aim_hip.h). Every copy this library keeps of a
+// caller's params is a whole aim_endsfree_params_t (aim_set::xparams), so the cast is valid wherever the flag is set.
+struct EndsFree { int pb = 0, pe = 0, tb = 0, te = 0; };
+inline bool is_endsfree(const aim_params_t &p) { return (p.flags & AIM_FLAG_ENDSFREE) != 0; }
+inline EndsFree ends_free(const aim_params_t &p)
+{
+    EndsFree e;
+    if (!is_endsfree(p)) return e;
+    const aim_endsfree_params_t &x = *reinterpret_cast<const aim_endsfree_params_t *>(&p);
+    e.pb = x.pattern_begin_free; e.pe = x.pattern_end_free; e.tb = x.text_begin_free; e.te = x.text_end_free;
+    return e;
+}
+// The params as this library keeps them: the extension copied only when the flag says it exists.
+inline aim_endsfree_params_t copy_params(const aim_params_t &p)
+{
+    aim_endsfree_params_t x;
+    memset(&x, 0, sizeof x);
+    if (is_endsfree(p)) x = *reinterpret_cast<const aim_endsfree_params_t *>(&p);
+    else x.base = p;
+    return x;
+}
+
 int validate_params(const aim_params_t &p)
 {
     if (p.algo != AIM_ALGO_NW && p.algo != AIM_ALGO_SWG && p.algo != AIM_ALGO_WFA && p.algo != AIM_ALGO_GENASM)
@@ -209,6 +231,7 @@ int validate_params(const aim_params_t &p)
     if ((p.flags & AIM_FLAG_REQ8) && p.read_size >= 32760)
         return fail(AIM_EINVAL, "AIM_FLAG_REQ8 carries int16 lengths: read_size must be < 32760");
     if (p.algo == AIM_ALGO_GENASM) {   // no penalties, no score cap; lengths are int32
+        if (is_endsfree(p)) return fail(AIM_EINVAL, "AIM_FLAG_ENDSFREE needs AIM_ALGO_WFA");
         if ((p.flags & AIM_FLAG_RES8) && (p.flags & AIM_FLAG_BACKTRACE))
             return fail(AIM_EINVAL, "AIM_FLAG_RES8 (idx, score results) cannot be combined with AIM_FLAG_BACKTRACE");
         if (p.read_size > (1 << 24)) return fail(AIM_EINVAL, "read_size must be <= 2^24");
@@ -223,6 +246,13 @@ int validate_params(const aim_params_t &p)
     }
     if ((p.flags & AIM_FLAG_RES8) && (p.flags & AIM_FLAG_BACKTRACE))
         return fail(AIM_EINVAL, "AIM_FLAG_RES8 (idx, score results) cannot be combined with AIM_FLAG_BACKTRACE");
+    if (is_endsfree(p)) {
+        if (p.algo != AIM_ALGO_WFA) return fail(AIM_EINVAL, "AIM_FLAG_ENDSFREE needs AIM_ALGO_WFA");
+        if (p.flags & AIM_FLAG_REDUCE) return fail(AIM_EINVAL, "AIM_FLAG_ENDSFREE cannot be combined with AIM_FLAG_REDUCE");
+        const EndsFree e = ends_free(p);
+        if (e.pb < 0 || e.pe < 0 || e.tb < 0 || e.te < 0)
+            return fail(AIM_EINVAL, "ends-free lengths must be >= 0 (got %d,%d,%d,%d)", e.pb, e.pe, e.tb, e.te);
+    }
     // the reference's lengths, WFA offsets and NW / SWG cells are int16 (WFA/DPU-WRAM/common/common.h:98-100, 174-175): what it admits
     // is < 32 767; READ_SIZE is a multiple of 8
     if (p.read_size >= 32760)
@@ -243,7 +273,11 @@ int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
         pl->scratch_total = (size_t)pl->grid * aim::kGaSlabBytes;   // slow-path columns, one slab per wavefront
         return AIM_OK;
     }
-    if (p.algo == AIM_ALGO_WFA && (mode & MODE_PACKED_IN) && !kn.force_wave && !kn.no_lane_pk && !kn.no_lane && !pl->no_lane &&
+    // Ends-free never runs on the lane kernels (their wavefront shapes are fixed at compile time for the global case); it runs on
+    // wfa_group where LDS admits the rows widened by PB + TB, else on wfa_wave.
+    const bool ef = is_endsfree(p);
+    const EndsFree efl = ends_free(p);
+    if (p.algo == AIM_ALGO_WFA && (mode & MODE_PACKED_IN) && !ef && !kn.force_wave && !kn.no_lane_pk && !kn.no_lane && !pl->no_lane &&
         aim::wfa_lane_packed_supported(p, !kn.no_lane_ext)) {
         // packed rows in; {idx, score}, compact CIGAR or result_t + ops rows out: one kernel per batch, no scratch (wfa_lane_packed.hpp)
         pl->kid = K_WFA_LANE_PK;
@@ -254,14 +288,14 @@ int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
         return AIM_OK;
     }
     if (p.algo == AIM_ALGO_WFA) {
-        const bool lane_ok = !kn.force_wave && !kn.no_lane && !pl->no_lane && aim::wfa_lane_supported(p, !kn.no_lane_ext);
+        const bool lane_ok = !ef && !kn.force_wave && !kn.no_lane && !pl->no_lane && aim::wfa_lane_supported(p, !kn.no_lane_ext);
         aim::GroupCfg gc;
         int gg = 0;
         uint32_t ggrid = 0, gchunk = n_pairs;
         size_t glds = 0, ghist = 0, ghist_pair = 0;
         const bool gpk = (mode & MODE_PACKED_IN) && !kn.no_lane_pk;   // the group kernel reads packed rows itself
         bool group_ok = !lane_ok && !kn.force_wave && !pl->no_lane && !kn.no_group &&
-                        aim::wfa_group_plan(p, n_pairs, kn, gpk, &gc, &gg, &ggrid, &glds, &ghist_pair);
+                        aim::wfa_group_plan(p, n_pairs, kn, gpk, &gc, &gg, &ggrid, &glds, &ghist_pair, efl.pb, efl.tb);
         if (group_ok && ghist_pair) {
             // BACKTRACE: every pair of a launch keeps its history region until the traceback kernel has walked it. Launches are
             // chunks of the batch whose regions fit half of the scratch bound (one chunk whenever possible).
@@ -294,7 +328,7 @@ int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
 #endif
             return AIM_OK;
         }
-        if (!lane_ok && !kn.force_wave && !kn.no_lane_pk && !kn.no_lane && !pl->no_lane && aim::wfa_lane_packed_supported(p, !kn.no_lane_ext)) {
+        if (!ef && !lane_ok && !kn.force_wave && !kn.no_lane_pk && !kn.no_lane && !pl->no_lane && aim::wfa_lane_packed_supported(p, !kn.no_lane_ext)) {
             // ASCII rows of a shape only the packed lane kernel takes (READ_SIZE other than 80 / 112: l = 150 and friends; CIGAR at
             // MAX_SCORE 6..10): pack on the device (batch_io.hpp), run the packed kernel, let the general kernel re-align the
             // non-ACGT pairs (to-do list)
@@ -337,20 +371,24 @@ int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
             pl->hist_bytes = ghist;
             pl->chunk_pairs = gchunk;
             pl->pk = gpk;
-            pl->emits_runs = bt && (mode & MODE_RUNS_OUT);
+            // (ends-free: ops rows, then cigar_rle_kernel -- the fused run output of wfa_group_tb_kernel is not used for it: one pair of
+            // a host run came back with a void first run, cause not found)
+            pl->emits_runs = bt && (mode & MODE_RUNS_OUT) && !ef;
             pl->scratch_total = pl->todo_bytes + pl->hist_bytes + fb.scratch_total;
             return AIM_OK;
         }
         pl->kid = K_WFA_WAVE;
         pl->block = 64;
         const uint64_t ms = (uint64_t)p.max_score;
-        const uint64_t full = 3 * (ms + 2) * (ms + 2) + 64;
+        // ends-free: every wavefront is up to PB + TB diagonals wider (the free lengths clamp to the pairs' lengths <= READ_SIZE)
+        const uint64_t wide = ef ? (uint64_t)std::min(efl.pb, p.read_size) + (uint64_t)std::min(efl.tb, p.read_size) : 0;
+        const uint64_t full = 3 * (ms + 2) * (ms + 2 + wide) + 64;
         uint64_t cap;
         if (bt) {
             cap = full;
         } else {   // score-only: the pool is a ring that must hold the live window (scores s-R .. s) plus the one being built
             const uint64_t R = (uint64_t)std::max(p.mismatch, p.gap_o + p.gap_e);
-            cap = std::min(full, (R + 2) * 3 * (2 * ms + 3));
+            cap = std::min(full, (R + 2) * 3 * (2 * ms + 3 + wide));
         }
         const uint64_t cap_min = bt ? 0 : cap;   // below this a score-only ring would overwrite wavefronts still in use
         pl->meta_cap = (uint32_t)(ms + 2);
@@ -358,7 +396,7 @@ int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
         {
             const uint32_t R = (uint32_t)std::max(p.mismatch, p.gap_o + p.gap_e);
             uint32_t w = 16;
-            while (w < 2 * (uint32_t)ms + 3 && w < 128) w *= 2;   // 128: keeps 16 workgroups resident per CU at l = 1000 (measured +9 % over 256)
+            while (w < 2 * (uint32_t)ms + 3 + (uint32_t)wide && w < 128) w *= 2;   // 128: keeps 16 workgroups resident per CU at l = 1000 (measured +9 % over 256)
             if (kn.wfa_slotw >= 0) w = (uint32_t)std::max(16, kn.wfa_slotw) & ~15u;
             while (w > 16 && (uint64_t)(R + 1) * 3 * w * 2 > 24 * 1024) w /= 2;
             const bool ring_ok = (uint64_t)(R + 1) * 3 * w * 2 <= 24 * 1024 && !kn.wfa_no_ring;
@@ -386,6 +424,7 @@ int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
                 uint64_t avail = budget / grid;
                 if (avail < meta_b + 4096) return fail(AIM_ENOMEM, "scratch budget too small for max_score %d", p.max_score);
                 cap = (avail - meta_b - 256) / sizeof(int16_t);
+                if (cap < wide + 1) return fail(AIM_ENOMEM, "scratch budget too small for the ends-free score-0 wavefront (%llu diagonals)", (unsigned long long)(wide + 1));
                 per = (meta_b + cap * sizeof(int16_t) + 255) & ~255ull;
             } else {
                 // Score-only: the pool is a ring and must keep its full live window (a shrunken ring silently overwrites
@@ -569,8 +608,13 @@ int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint6
     else if (pl.kid == K_DP_LANE) snprintf(extra, sizeof extra, " seq_lds=%d", (int)pl.seq_lds);
     else if (pl.kid == K_DP_REG) snprintf(extra, sizeof extra, " fb_grid=%u fb_lds=%zu", pl.fb_grid, pl.fb_lds);
     else if (pl.kid == K_DP_GROUP) snprintf(extra, sizeof extra, " lanes_per_pair=%d fb_grid=%u fb_block=%u fb_lds=%zu", aim::dp_group_lanes(p.read_size, (p.flags & AIM_FLAG_BACKTRACE) != 0, p.algo == AIM_ALGO_SWG), pl.fb_grid, pl.fb_block, pl.fb_lds);
-    return snprintf(out, cap, "%s n=%u grid=%u block=%u lds=%zu scratch=%zu budget=%llu%s", kernel_name(pl, p), n_pairs, pl.grid,
-                    pl.block, pl.lds, pl.scratch_total, (unsigned long long)budget, extra);
+    char efs[80] = "";
+    if (is_endsfree(p)) {
+        const EndsFree e = ends_free(p);
+        snprintf(efs, sizeof efs, " endsfree=%d,%d,%d,%d", e.pb, e.pe, e.tb, e.te);
+    }
+    return snprintf(out, cap, "%s n=%u grid=%u block=%u lds=%zu scratch=%zu budget=%llu%s%s", kernel_name(pl, p), n_pairs, pl.grid,
+                    pl.block, pl.lds, pl.scratch_total, (unsigned long long)budget, extra, efs);
 }
 
 int make_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, Plan *pl, uint32_t mode = 0u)
@@ -681,6 +725,10 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
     ka.runs_cap = fio ? fio->runs_cap : 0u;
     ka.cursor = fio ? fio->cursor : nullptr;
     ka.pair_base = 0;
+    {
+        const EndsFree e = ends_free(p);
+        ka.ef_pb = e.pb; ka.ef_pe = e.pe; ka.ef_tb = e.tb; ka.ef_te = e.te;
+    }
     if (kn.poison_ops >= 0 && d_ops && bt)   // debugging aid: results must not depend on what the ops rows held before (only ops[begin_offset, end_offset) is written)
         HIP_TRY(hipMemsetAsync(d_ops, kn.poison_ops & 0xff, (size_t)n_pairs * 2 * p.read_size, stream));
     switch (pl.kid) {
@@ -900,7 +948,8 @@ struct aim_device_ctx {
 
 struct aim_set {
     std::vector<aim_device_ctx> devs;
-    aim_params_t params;
+    aim_endsfree_params_t xparams;   // the params with their extension (aim_hip.h AIM_FLAG_ENDSFREE); xparams.base is what the plans read
+    const aim_params_t &params = xparams.base;
     uint32_t max_pairs = 0, max_raw = 0, max_runs = 0;
     bool configured = false;
     aim::Knobs knobs;        // AIM_* switches as read by the last aim_set_configure; launches never re-read the environment
@@ -1028,6 +1077,7 @@ int launch_on_slot(aim_set *set, aim_device_ctx &d, aim_slot &s, uint32_t mode =
 extern "C" {
 
 int aim_abi_version(void) { return AIM_ABI_VERSION; }
+uint32_t aim_features(void) { return AIM_FEATURE_ENDSFREE; }
 const char *aim_last_error(void) { return g_err; }
 
 int aim_device_count(int *count)
@@ -1178,7 +1228,7 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
             return rc;
         }
     }
-    set->params = *params;
+    set->xparams = copy_params(*params);
     set->max_pairs = max_pairs;
     set->max_raw = max_raw;
     set->max_runs = max_runs;

@@ -145,7 +145,8 @@ __device__ __forceinline__ void cigar_rle_wave(const KArgs &a, uint32_t pair, bo
     int e = r.end_offset > 2 * rs ? 2 * rs : r.end_offset;
     if (e <= b) e = b + 1;
     if (b >= 2 * rs) { b = 2 * rs - 1; e = 2 * rs; }
-    const bool walk = active && r.status == AIM_PAIR_OK;
+    // (ends-free pairs over MAX_SCORE carry an empty CIGAR, begin_offset == end_offset: no run, aim_hip.h AIM_FLAG_ENDSFREE)
+    const bool walk = active && r.status == AIM_PAIR_OK && !((a.p.flags & AIM_FLAG_ENDSFREE) && r.end_offset <= r.begin_offset);
     const uint32_t *row = reinterpret_cast<const uint32_t *>(a.ops + (uint64_t)pair * 2 * rs);
     // boundary mask of word w: bit 8j+7 set <=> byte 4w+j differs from byte 4w+j-1, restricted to positions in (b, e)
     auto boundaries = [&](int w, uint32_t cur, uint32_t prev) -> uint32_t {

@@ -18,6 +18,12 @@
 //   * per-pair descriptors (klo, khi, flags) sit in a small LDS ring, so WFA-adaptive's per-pair bounds
 //     (wfa.c:96-139) cost nothing when they do not fire.
 // Pairs with non-ACGT bytes go to the to-do list drained by wfa_wave_kernel, as in wfa_lane.hpp.
+//
+// EF (AIM_FLAG_ENDSFREE, never with REDUCE): ends-free alignment. Rows are wider by PB + TB (GroupCfg::efpb / eftb, the
+// launch's free lengths clamped to READ_SIZE; every diagonal has its own home); the score-0 wavefront spans [-pb, tb] with
+// offsets max(k, 0), extended by the group's lanes; every lane notes the smallest of its diagonals whose extended offset sits
+// on an end border, and a group_min after each row ends the pair; the end diagonal travels to the traceback kernel in the
+// TbHead, which writes the trailing free run, walks, and writes the score-0 match stroke and the leading free run.
 #pragma once
 
 #include <cstdlib>
@@ -71,21 +77,26 @@ struct GroupCfg {
     int unit;         // score unit: gcd(x, o+e, e). Only multiples of it have a wavefront (every score is a sum of penalties), so the
                       // score loop counts in units -- row s of the rings / of the history table is score s * unit -- and never
                       // visits the null wavefronts in between (x = 4, o = 6, e = 2: every second step of the reference's loop)
+    int efpb, eftb;   // EF kernels: the diagonals -efpb .. eftb of score 0 (free lengths clamped to READ_SIZE); 0 otherwise
 };
 
 enum { GF_PRESENT = 1, GF_MNULL = 2, GF_INULL = 4, GF_DNULL = 8, GF_HASI = 16, GF_HASD = 32 };
 constexpr int kGrpNull = -16384;
 
 // Per-pair history (BACKTRACE): head + one 16-byte descriptor per score + the offsets (see GroupCfg).
-struct TbHead { int32_t final_score; int32_t walk; int32_t pad[2]; };   // walk: 1 = the traceback kernel owns this pair, 0 = to-do list / not computed
+struct TbHead { int32_t final_score; int32_t walk; int32_t end_k; int32_t pad; };   // walk: 1 = the traceback kernel owns this pair, 0 = to-do list / not computed; end_k: EF's end diagonal
 struct TbRow { int16_t klo, khi, flags, pad; };   // the score's final (reduced) bounds and flags: what the traceback's range / null tests read
 static_assert(sizeof(TbHead) == 16 && sizeof(TbRow) == 8, "history layout");
 
 // Pool index of the cell of (score su in units, diagonal k): see GroupCfg. The traceback reads neighbours of cells that exist, so k may
 // lie one or two outside the row: clamped here (such a cell is never selected -- the caller's range test fails).
-template <bool MODW>
+template <bool MODW, bool EF = false>
 __device__ __forceinline__ int group_cell_index(const GroupCfg &c, int su, int k)
 {
+    if constexpr (EF) {   // row su holds the diagonals -efpb - su .. eftb + su
+        const int kc = min(max(k, -c.efpb - su), c.eftb + su);
+        return su * (su + c.efpb + c.eftb) + su + kc + c.efpb;
+    }
     if (c.wlds != c.wcap) {   // narrow rows: the row's LDS image
         const int t = max(k + c.kbias, 0);
         const int h = MODW ? t - (int)__umul24(__umul24((uint32_t)t, (uint32_t)c.wmagic) >> 16, (uint32_t)c.wlds) : (t & c.wmask);
@@ -121,7 +132,7 @@ __device__ __forceinline__ int group_min(int v)
 #else
 #define AIM_GSTAMP(i) do { } while (0)
 #endif
-template <int G, bool REDUCE, bool BT, bool MODW = false>
+template <int G, bool REDUCE, bool BT, bool MODW = false, bool EF = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MIN_WAVES))) void wfa_group_kernel(KArgs a, GroupCfg c)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -300,6 +311,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
         };
 
         const int ak = tlen - plen;
+        // EF: the pair's free lengths, clamped to its lengths (and to the launch's, which size the rows)
+        const int pb = EF ? min(min(a.ef_pb, plen), c.efpb) : 0, tb = EF ? min(min(a.ef_tb, tlen), c.eftb) : 0;
+        const int pe = EF ? min(a.ef_pe, plen) : 0, te = EF ? min(a.ef_te, tlen) : 0;
+        int hit = 0x7fffffff, end_k = ak;   // EF: smallest of my diagonals of the current row on an end border; the pair's end diagonal
+        auto on_end = [&](int k, int h) {   // end borders (plen, h >= tlen - TE), (v >= plen - PE, tlen); PE = TE = 0: also global WFA's own test
+            const int v = h - k;
+            return h >= 0 && ((v == plen && h >= tlen - te && h <= tlen) || (h == tlen && v >= plen - pe && v <= plen) ||
+                              (pe == 0 && te == 0 && k == ak && h >= tlen));
+        };
         score = 0; sm = 0; i_x = i_oe = i_e = 0;
         int final_score = -1;
         bool done = !active || bad != 0u;
@@ -316,7 +336,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
         TbRow *htab = reinterpret_cast<TbRow *>(hreg + sizeof(TbHead));
         uint2 *hpool = reinterpret_cast<uint2 *>(hreg + c.pool_off);   // cells {M, I, D, -}: ONE 8-byte store per computed cell, at its closed-form index (GroupCfg)
         const bool hnarrow = c.wlds != c.wcap;
-        if (g == 0) {
+        if (EF) {   // M[k] = max(k, 0) on [-pb, tb], extended by the group's lanes
+            klo = -pb; khi = tb;
+            for (int k = -pb + g; k <= tb; k += G) {
+                const int m0 = done ? 0 : extend(k, max(k, 0));
+                mrow_at(0)[H(k)] = (int16_t)m0;
+                if (BT && !done) hpool[group_cell_index<false, true>(c, 0, k)] = make_uint2((uint32_t)(uint16_t)m0, 0u);
+                if (on_end(k, m0)) hit = min(hit, k);
+            }
+            if (g == 0) { meta[0] = (int16_t)klo; meta[1] = (int16_t)khi; meta[2] = (int16_t)flags; }
+        } else if (g == 0) {
             const int m00 = done ? 0 : extend(0, 0);
             mrow_at(0)[H(0)] = (int16_t)m00;
             if (BT && !done) hpool[hnarrow ? H(0) : 0] = make_uint2((uint32_t)(uint16_t)m00, 0u);
@@ -327,7 +356,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
             const uint4 mm = make_uint4(0x4D4D4D4Du, 0x4D4D4D4Du, 0x4D4D4D4Du, 0x4D4D4D4Du);
             // (only the pieces that can hold a printed operation: begin_offset >= min(plen, tlen) - MAX_SCORE / e, wfa_lane.hpp)
             // (gap_e == 0: gaps cost nothing to extend and MAX_SCORE bounds no length -- the whole row is written)
-            const int p_lo = a.p.gap_e > 0 ? max(0, min(plen, tlen) - a.p.max_score / a.p.gap_e) >> 4 : 0, p_hi = min((plen + tlen + 15) >> 4, (2 * rs) / 16);
+            // (EF: begin_offset = #M + #X >= max(plen - pb - pe, tlen - tb - te) - MAX_SCORE / e: free gaps are not bounded by the score)
+            const int p_lo = a.p.gap_e > 0 ? max(0, (EF ? max(plen - pb - pe, tlen - tb - te) : min(plen, tlen)) - a.p.max_score / a.p.gap_e) >> 4 : 0, p_hi = min((plen + tlen + 15) >> 4, (2 * rs) / 16);
             for (int j = p_lo + g; j < p_hi; j += G) orow[j] = mm;
         }
         fence();
@@ -374,7 +404,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
                 if (BT && g == 0)   // final descriptor of this score (after reduction): one 8-byte store
                     *reinterpret_cast<uint2 *>(htab + score) = make_uint2((uint32_t)(uint16_t)klo | ((uint32_t)(uint16_t)khi << 16), (uint32_t)(uint16_t)flags);
                 // affine_wfa_end_reached, wfa.c:210-230
-                if ((flags & GF_PRESENT) && !(flags & GF_MNULL) && klo <= ak && khi >= ak && (int)mrow[H(ak)] >= tlen) {
+                bool reached;
+                if constexpr (EF) {
+                    // the group reduction only in a step where a lane of the wavefront hit a border: on G = 32 it is an LDS crossbar round
+                    // trip, and every step of this latency-bound loop paid it (l = 1000 e = 5 % with CIGAR: +33 % over global WFA)
+                    reached = false;
+                    if (__ballot(hit != 0x7fffffff) != 0ull) {
+                        end_k = group_min<G>(hit);
+                        reached = (flags & GF_PRESENT) && !(flags & GF_MNULL) && end_k != 0x7fffffff;
+                    }
+                } else {
+                    reached = (flags & GF_PRESENT) && !(flags & GF_MNULL) && klo <= ak && khi >= ak && (int)mrow[H(ak)] >= tlen;
+                }
+                if (reached) {
                     done = true;
                     final_score = score * U;
                 } else if ((score + 1) * U > MS) {   // wfa.c:368-376: the reference steps through the null wavefronts up to MAX_SCORE and leaves with MAX_SCORE + 1
@@ -414,6 +456,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
                 const bool i_e_null = (s_e < 0) || !(e_f & GF_PRESENT) || !(e_f & GF_HASI) || (e_f & GF_INULL);
                 const bool d_e_null = (s_e < 0) || !(e_f & GF_PRESENT) || !(e_f & GF_HASD) || (e_f & GF_DNULL);
                 const bool i_out_null = m_o_null && i_e_null, d_out_null = m_o_null && d_e_null;
+                if (EF) hit = 0x7fffffff;
                 AIM_GSTAMP(2);   // score++, source descriptors
                 if (m_sub_null && i_out_null && d_out_null) {
                     flags = 0; klo = 0; khi = -1;
@@ -431,7 +474,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
                         done = true;
                         hi_run = lo - 1;               // nothing more is computed or stored for it (its history pool is sized for admitted widths only)
                     }
-                    uint2 *hrow = hpool + (hnarrow ? score * wl : score * score + score);   // BACKTRACE: this score's row of the pool (narrow: cell of k at hrow[H(k)], else hrow[k])
+                    uint2 *hrow = hpool + (EF ? group_cell_index<false, true>(c, score, 0) : (hnarrow ? score * wl : score * score + score));   // BACKTRACE: this score's row of the pool (narrow: cell of k at hrow[H(k)], else hrow[k])
 #ifdef AIM_GROUP_COUNT_WIDTHS
                     dbg_wsum += hi - lo + 1; dbg_w32 += (hi - lo + 1) > 32; dbg_w64 += (hi - lo + 1) > 64;
 #endif
@@ -474,6 +517,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
                         // diagonal's extension depends on nothing but its own offset, so it is applied before the one store
                         const int ext = extend(k, max(del, max(sub, ins)));
                         om[hk] = (int16_t)ext;
+                        if (EF && on_end(k, ext)) hit = min(hit, k);
                         if (BT) hrow[hnarrow ? hk : k] = make_uint2((uint32_t)(uint16_t)ext | ((uint32_t)(uint16_t)ins << 16), (uint32_t)(uint16_t)del);   // I / D: -10 when absent (never selected)
                         const int dist = max(plen - (ext - k), tlen - ext);
                         part = min(part, dist);
@@ -495,6 +539,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
                 TbHead *hd = reinterpret_cast<TbHead *>(hreg);
                 hd->final_score = final_score;
                 hd->walk = bad == 0u ? 1 : 0;
+                hd->end_k = end_k;
             }
             if (bad != 0u) {
                 const uint32_t slot = atomicAdd(&todo[LANE_TODO_COUNT], 1u);
@@ -502,7 +547,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
             } else if (!BT) {
                 aim_result_t r;
                 r.max_operations = plen + tlen;
-                r.begin_offset = plen + tlen - 1;
+                r.begin_offset = plen + tlen - (EF && final_score > MS ? 0 : 1);   // (EF over the cap: empty CIGAR)
                 r.end_offset = plen + tlen;
                 r.score = final_score;
                 r.status = AIM_PAIR_OK;
@@ -548,8 +593,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
 // cycles), and the range tests of the reference then select -- a cell outside its row is read at a clamped index and never selected. Output: result_t +
 // edit operations patched into the ops row the compute kernel pre-filled with 'M' (default ABI), or aim_cigar_t + runs
 // (RUNS: the compact CIGAR; runs are collected backwards in the pair's own run scratch and copied out forwards).
-template <bool MODW, typename Sink>
-__device__ __forceinline__ int group_tb_walk(const GroupCfg &c, const TbRow *tab, const int16_t *pool, int final_score, int plen, int tlen, int X, int OE, int E, Sink &sink)
+template <bool MODW, bool EF, typename Sink>
+__device__ __forceinline__ int group_tb_walk(const GroupCfg &c, const TbRow *tab, const int16_t *pool, int final_score, int end_k, int plen, int tlen, int X, int OE, int E, Sink &sink)
 {
     enum { BT_M = 0, BT_I = 1, BT_D = 2 };
     const int ak = tlen - plen;
@@ -566,13 +611,17 @@ __device__ __forceinline__ int group_tb_walk(const GroupCfg &c, const TbRow *tab
         return r;
     };
     auto cell = [&](int s_, int which, int k_) -> int {   // which: 0 = M, 1 = I, 2 = D; index clamped into the row, selected by the caller's range test
-        return pool[4 * group_cell_index<MODW>(c, s_, k_) + which];   // cells are {M, I, D, -} int16
+        return pool[4 * group_cell_index<MODW, EF>(c, s_, k_) + which];   // cells are {M, I, D, -} int16
     };
-    int sc = final_score, k = ak;
+    int sc = final_score, k = EF ? end_k : ak;
     int offset = cell(sc, 0, k);
     bool valid = valid_loc(k, offset);
     int bt = BT_M;
     int v = offset - k, h = offset;
+    if (EF) {   // the trailing free run: the end cell sits on the bottom or the right border
+        if (v == plen) for (int i = h; i < tlen; ++i) sink.put('I');
+        else if (h == tlen) for (int i = v; i < plen; ++i) sink.put('D');
+    }
     while (v > 0 && h > 0 && sc > 0) {
         if (!valid) {
             valid = valid_loc(k, offset);
@@ -624,7 +673,11 @@ __device__ __forceinline__ int group_tb_walk(const GroupCfg &c, const TbRow *tab
     }
     if (status == AIM_PAIR_OK) {
         if (sc == 0) {
-            if (offset > 0) sink.matches(offset);
+            if (EF) {   // the score-0 match stroke from (max(-k, 0), max(k, 0)), then the leading free run
+                if (offset > max(k, 0)) sink.matches(offset - max(k, 0));
+                for (int i = 0; i < k; ++i) sink.put('I');
+                for (int i = k; i < 0; ++i) sink.put('D');
+            } else if (offset > 0) sink.matches(offset);
         } else {
             for (; v > 0; --v) sink.put('D');
             for (; h > 0; --h) sink.put('I');
@@ -633,7 +686,7 @@ __device__ __forceinline__ int group_tb_walk(const GroupCfg &c, const TbRow *tab
     return status;
 }
 
-template <bool RUNS, bool MODW>
+template <bool RUNS, bool MODW, bool EF = false>
 __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
 {
     const int lane = threadIdx.x;
@@ -656,9 +709,9 @@ __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
     int status = AIM_PAIR_OK;
     if constexpr (RUNS) {
         RunCollector<1> coll(plen + tlen - 1, reinterpret_cast<uint32_t *>(hreg + c.runs_off), c.runs_cap);
-        if (walk) status = group_tb_walk<MODW>(c, tab, pool, final_score / U, plen, tlen, X, OE, E, coll);
+        if (walk) status = group_tb_walk<MODW, EF>(c, tab, pool, final_score / U, hd.end_k, plen, tlen, X, OE, E, coll);
         coll.flush();
-        if (coll.n == 0) {   // nothing inside [0, end): edit_cigar_print still prints operations[begin_offset] = 'M'
+        if (coll.n == 0 && !(EF && !walk)) {   // (EF over the cap: an empty CIGAR, no run)   // nothing inside [0, end): edit_cigar_print still prints operations[begin_offset] = 'M'
             coll.cur_op = (uint32_t)'M'; coll.cur_len = 1u;
             coll.flush();
         }
@@ -669,8 +722,10 @@ __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
         sink.cap = 2 * rs;
         sink.pos = plen + tlen - 1;                       // edit_cigar_allocate, wfa.c:57-67
         if (walk) {
-            status = group_tb_walk<MODW>(c, tab, pool, final_score / U, plen, tlen, X, OE, E, sink);
+            status = group_tb_walk<MODW, EF>(c, tab, pool, final_score / U, hd.end_k, plen, tlen, X, OE, E, sink);
             if (status == AIM_PAIR_OK) ++sink.pos;
+        } else if (EF) {
+            sink.pos = plen + tlen;                       // over the cap: an empty CIGAR
         }
         if (active) {
             aim_result_t r;
@@ -688,9 +743,12 @@ __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
 // ---------------------------------------------------------------------------------------------------------------
 // hist_pair_bytes: bytes of ONE pair's history region (BACKTRACE; 0 otherwise) -- the caller sizes launches (chunks of pairs)
 // so that their regions fit its scratch bound. packed: the batch arrives packed (no staging rows in LDS).
+// efpb / eftb: ends-free launches (AIM_FLAG_ENDSFREE) -- the pattern-begin and text-begin free lengths; the rows widen by their sum
+// (clamped to READ_SIZE each) and every diagonal keeps its own home.
 inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const Knobs &kn, bool packed, int rows, GroupCfg *c, int *G, uint32_t *grid,
-                                size_t *lds, size_t *hist_pair_bytes)   // rows: entries per LDS ring row asked for; < 0 = the default rule
+                                size_t *lds, size_t *hist_pair_bytes, int efpb = 0, int eftb = 0)   // rows: entries per LDS ring row asked for; < 0 = the default rule
 {
+    const bool ef = (p.flags & AIM_FLAG_ENDSFREE) != 0;
     if (p.algo != AIM_ALGO_WFA) return false;
     // int16 offsets with NULL = -16384 (offset + 1 must stay above it) and 24-bit home arithmetic bound the shapes; what really decides is LDS below:
     // the packed image (READ_SIZE / 2 bytes per pair) and, without the reduction, rows of 2 * MAX_SCORE + 3 entries. (Rounds 1-3 stopped at READ_SIZE
@@ -706,8 +764,10 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
         const int u = gcd(gcd(p.mismatch, p.gap_o + p.gap_e), p.gap_e);
         c->unit = (u > 1 && !kn.group_unit1) ? u : 1;
     }
-    c->kbias = p.max_score + 1;
-    c->wcap = 2 * p.max_score + 3;
+    c->efpb = ef ? std::min(std::max(efpb, 0), p.read_size) : 0;
+    c->eftb = ef ? std::min(std::max(eftb, 0), p.read_size) : 0;
+    c->kbias = p.max_score + 1 + c->efpb;
+    c->wcap = 2 * p.max_score + 3 + c->efpb + c->eftb;
     c->ring_m = ring_m;
     c->ring_e = ring_e;
     c->np = (p.read_size + 15) / 16 + 1;
@@ -725,6 +785,7 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
         // vs 1.63; no pair of these sets outgrew the row. Rows of 64 cost 0.3-47 % of the pairs a detour, rows of 32 most.)
         int narrow = (p.flags & AIM_FLAG_REDUCE) && c->wcap >= 192 ? 128 : 0;   // without the reduction widths grow with the score
         if (rows >= 0) narrow = rows;
+        if (ef) narrow = 0;   // an ends-free row starts wide: one home per diagonal
         const bool pow2 = (narrow & (narrow - 1)) == 0;
         if (narrow >= 16 && narrow < c->wcap) {
             if (pow2) { c->wlds = narrow; c->wmask = narrow - 1; }
@@ -801,7 +862,7 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
     // one home per diagonal -- row s holds the 2s+1 diagonals a wavefront of score s can reach at most.
     {
         const uint64_t rows = (uint64_t)p.max_score / (uint64_t)c->unit + 2;
-        const uint64_t cells = c->wlds != c->wcap ? rows * (uint64_t)c->wlds : rows * rows;
+        const uint64_t cells = c->wlds != c->wcap ? rows * (uint64_t)c->wlds : rows * rows + rows * (uint64_t)(c->efpb + c->eftb);
         if (cells * 8 > (1ull << 30)) return false;
         c->pool_off = (int)(sizeof(TbHead) + (size_t)rows * sizeof(TbRow));
         c->pool_cap = (int)cells;                             // cells of 8 bytes {M, I, D, -}
@@ -820,8 +881,10 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
 // 1.21 -> 1.10 (0); but l=400 e=10 % 1.34 -> 1.73 (57 of 32 768) and l=250 e=10 % 1.59 -> 1.82 (38 of 65 536): every pair that outgrows
 // its row costs a whole general-kernel pass, so wide wavefronts keep 128. (Rows of 80: 42 pairs of cfg3 leave, 3.50 ms; tools/group_rows.py.)
 inline bool wfa_group_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs &kn, bool packed, GroupCfg *c, int *G, uint32_t *grid, size_t *lds,
-                           size_t *hist_pair_bytes)
+                           size_t *hist_pair_bytes, int efpb = 0, int eftb = 0)
 {
+    if ((p.flags & AIM_FLAG_ENDSFREE) && (p.flags & AIM_FLAG_REDUCE)) return false;
+    if (p.flags & AIM_FLAG_ENDSFREE) return wfa_group_plan_rows(p, n_pairs, kn, packed, -1, c, G, grid, lds, hist_pair_bytes, efpb, eftb);
     int rows = kn.group_wlds;
     if (rows < 0 && (p.flags & AIM_FLAG_REDUCE) && 2 * p.max_score + 3 >= 192 && 4 * p.max_score <= p.read_size) rows = 96;
     if (rows >= 16 && (rows & (rows - 1)) != 0) {   // no power of two: only the G = 16 kernels address such rows
@@ -836,8 +899,11 @@ inline bool wfa_group_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs 
 #ifdef AIM_TU_WFA_GROUP
 void wfa_group_tb_launch(const aim_params_t &p, const GroupCfg &c, uint32_t n_pairs, const KArgs &ka, hipStream_t s)
 {
-    (void)p;
     const uint32_t grid = (n_pairs + kWave - 1) / kWave;
+    if (p.flags & AIM_FLAG_ENDSFREE) {   // (ops rows only: the plan never fuses the run output of an ends-free launch, aim_capi.hip)
+        hipLaunchKernelGGL((wfa_group_tb_kernel<false, false, true>), dim3(grid), dim3(kWave), 0, s, ka, c);
+        return;
+    }
     if (c.wmagic) {
         if (ka.cig) hipLaunchKernelGGL((wfa_group_tb_kernel<true, true>), dim3(grid), dim3(kWave), 0, s, ka, c);
         else hipLaunchKernelGGL((wfa_group_tb_kernel<false, true>), dim3(grid), dim3(kWave), 0, s, ka, c);
@@ -855,6 +921,25 @@ void wfa_group_tb_launch(const aim_params_t &p, const GroupCfg &c, uint32_t n_pa
 void wfa_group_launch(const aim_params_t &p, int G, const GroupCfg &c, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s)
 {
     const bool red = p.flags & AIM_FLAG_REDUCE, bt = p.flags & AIM_FLAG_BACKTRACE;
+    if (p.flags & AIM_FLAG_ENDSFREE) {   // (never with the reduction, never with modulo rows)
+#define AIM_GRP_EF(GG)                                                                                                   \
+    do {                                                                                                                \
+        if (bt) hipLaunchKernelGGL((wfa_group_kernel<GG, false, true, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);  \
+        else hipLaunchKernelGGL((wfa_group_kernel<GG, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);    \
+    } while (0)
+        switch (G) {
+        case 1: AIM_GRP_EF(1); break;
+        case 2: AIM_GRP_EF(2); break;
+        case 4: AIM_GRP_EF(4); break;
+        case 8: AIM_GRP_EF(8); break;
+        case 16: AIM_GRP_EF(16); break;
+        case 32: AIM_GRP_EF(32); break;
+        case 64: AIM_GRP_EF(64); break;
+        default: break;
+        }
+#undef AIM_GRP_EF
+        return;
+    }
 #define AIM_GRP(GG)                                                                                                     \
     do {                                                                                                                \
         if (red && bt) hipLaunchKernelGGL((wfa_group_kernel<GG, true, true>), dim3(grid), dim3(kWave), lds, s, ka, c);  \

@@ -16,6 +16,13 @@
 // wavefront wider than a slot lives in that pool only (slower, same results).
 // Handles any MAX_SCORE / READ_SIZE / penalties; the short-read fast path is
 // wfa_lane.hpp.
+//
+// EF (AIM_FLAG_ENDSFREE, aim_hip.h): ends-free alignment.  Three changes, all
+// compiled out of the global instantiations: the score-0 wavefront spans
+// diagonals [-PB, TB] with offsets max(k, 0); after each extend the run ends as
+// soon as any diagonal's M offset sits on an end border (one wave reduction);
+// the traceback writes the trailing free run, walks, writes the score-0 match
+// stroke and then the leading free run.
 #pragma once
 
 #include "aim_device.hpp"
@@ -78,7 +85,7 @@ __device__ __forceinline__ int wf_extend_count(PtrT P, PtrT T, int v, int h, int
     return count;
 }
 
-template <bool BT, bool REDUCE, bool SEQ_LDS>
+template <bool BT, bool REDUCE, bool SEQ_LDS, bool EF = false>
 __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -150,15 +157,30 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
         int status = AIM_PAIR_OK;
         int final_score;
         const int ak = tlen - plen;   // alignment_k
+        // EF: the pair's free lengths, clamped to its lengths
+        const int pb = EF ? min(a.ef_pb, plen) : 0, pe = EF ? min(a.ef_pe, plen) : 0;
+        const int tb = EF ? min(a.ef_tb, tlen) : 0, te = EF ? min(a.ef_te, tlen) : 0;
+        const int w0 = pb + tb + 1;                       // diagonals of the score-0 wavefront
+        const bool w0_lds = ring_slots > 0 && (!EF || w0 <= slot_w);
+        const bool w0_fits = !EF || w0 <= pool_cap;       // (a BACKTRACE pool shrunk by the scratch bound may not hold it)
+        int end_k = ak;                                   // EF: the end cell's diagonal
 
         // wavefronts[0] = allocate_new_score(0,0,0,0); M[0] = 0   (wfa.c:347-348)
-        int pool_used = 1;
+        int pool_used = EF ? w0 : 1;
         WfMeta cur;
-        cur.klo = cur.khi = cur.lo = cur.hi = 0;
+        cur.klo = cur.lo = -pb;
+        cur.khi = cur.hi = tb;
         cur.off_m = 0; cur.off_i = -1; cur.off_d = -1;
-        cur.flags = WF_PRESENT | WF_INULL | WF_DNULL | (ring_slots > 0 ? WF_INLDS : 0);
+        cur.flags = WF_PRESENT | WF_INULL | WF_DNULL | (w0_lds ? WF_INLDS : 0);
         ctx.cur_score = 0;
-        if (lane == 0) {
+        if (EF) {   // M[k] = max(k, 0): (v = -k, h = 0) below the main diagonal, (v = 0, h = k) above it
+            if (w0_fits)
+                for (int i = lane; i < w0; i += kWave) {
+                    const awf_t o = (awf_t)max(i - pb, 0);
+                    pool[i] = o;
+                    if (w0_lds) slot(0, 0)[i] = o;
+                }
+        } else if (lane == 0) {
             pool[0] = 0;
             if (ring_slots > 0) slot(0, 0)[0] = 0;
         }
@@ -167,7 +189,13 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
 
         int score = 0;
         for (;;) {
+            if (EF && !w0_fits) {   // allocate_new(): "out of memory", dpu_allocator_wram.c:19-23 (the plan never admits it: a guard)
+                status = AIM_PAIR_NOMEM;
+                final_score = MS + 1;   // no score was reached: not a 0 that would read like a perfect alignment
+                break;
+            }
             const bool live = (cur.flags & WF_PRESENT) && !(cur.flags & WF_MNULL);
+            int hit_k = 0x7fffffff;   // EF: smallest diagonal whose extended M offset sits on an end border
             // ---- affine_wfa_extend, wfa.c:186-208 -------------------------------
             if (live) {
                 const bool inlds = cur.flags & WF_INLDS;
@@ -182,6 +210,14 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
                                 : wf_extend_count(gP, gT, moff - k, moff, plen, tlen, last_word);
                             if (cnt) mrow[k - cur.lo] = (awf_t)(moff + cnt);
                             if (BT && inlds) pool[cur.off_m + (k - cur.lo)] = (awf_t)(moff + cnt);   // HBM history for the traceback
+                            if (EF) {
+                                // end borders: (plen, h >= tlen - TE) and (v >= plen - PE, tlen); with PE = TE = 0 also
+                                // global WFA's own test (alignment_k, offset >= tlen), so that zero free lengths end alike
+                                const int h = moff + cnt, v = h - k;
+                                const bool end = (v == plen && h >= tlen - te && h <= tlen) || (h == tlen && v >= plen - pe && v <= plen) ||
+                                                 (pe == 0 && te == 0 && k == ak && h >= tlen);
+                                if (end) hit_k = min(hit_k, k);
+                            }
                         } else if (BT && inlds) {
                             pool[cur.off_m + (k - cur.lo)] = (awf_t)moff;
                         }
@@ -248,7 +284,12 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
             }
             // ---- affine_wfa_end_reached, wfa.c:210-230 ---------------------------
             bool done = false;
-            if ((cur.flags & WF_PRESENT) && !(cur.flags & WF_MNULL) && cur.klo <= ak && cur.khi >= ak) {
+            if (EF) {
+                if (live) {
+                    end_k = wave_min_i32(hit_k);
+                    done = end_k != 0x7fffffff;
+                }
+            } else if ((cur.flags & WF_PRESENT) && !(cur.flags & WF_MNULL) && cur.klo <= ak && cur.khi >= ak) {
                 const int off = (cur.flags & WF_INLDS) ? (int)slot(score, 0)[ak - cur.lo] : (int)pool[cur.off_m + (ak - cur.lo)];
                 done = off >= tlen;
             }
@@ -360,7 +401,7 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
         if (BT && status == AIM_PAIR_OK && final_score <= MS) {
             enum { BT_M = 0, BT_I = 1, BT_D = 2 };
             const int ops_cap = 2 * rs;
-            int sc = final_score, k = ak;
+            int sc = final_score, k = EF ? end_k : ak;
             WfMeta m0 = ctx.gmeta[sc];
             int offset = pool[m0.off_m + (k - m0.lo)];
             auto valid_loc = [&](int kk, int off) {
@@ -377,6 +418,10 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
             bool valid = valid_loc(k, offset);
             int bt = BT_M;
             int v = offset - k, h = offset;
+            if (EF) {   // the trailing free run: the end cell sits on the bottom or the right border
+                if (v == plen && h < tlen) put_run('I', tlen - h);
+                else if (h == tlen && v < plen) put_run('D', plen - v);
+            }
             while (v > 0 && h > 0 && sc > 0) {
                 if (!valid) {
                     valid = valid_loc(k, offset);
@@ -435,7 +480,12 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
             }
             if (status == AIM_PAIR_OK) {
                 if (sc == 0) {
-                    if (offset > 0) begin_offset -= offset;
+                    if (EF) {   // the score-0 match stroke from (max(-k, 0), max(k, 0)), then the leading free run
+                        const int h0 = max(k, 0);
+                        if (offset > h0) begin_offset -= offset - h0;
+                        if (k > 0) put_run('I', k);
+                        else if (k < 0) put_run('D', -k);
+                    } else if (offset > 0) begin_offset -= offset;
                 } else {
                     if (v > 0) put_run('D', v);
                     if (h > 0) put_run('I', h);
@@ -444,6 +494,7 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
             }
         }
 
+        if (EF && status == AIM_PAIR_OK && final_score > MS) begin_offset = end_offset;   // over the cap: empty CIGAR
         if (lane == 0) {
             aim_result_t r;
             r.max_operations = max_ops;
@@ -466,11 +517,20 @@ void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds,
         if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, REDV, true>), dim3(grid), dim3(kWave), lds, s, ka);       \
         else hipLaunchKernelGGL((wfa_wave_kernel<BTV, REDV, false>), dim3(grid), dim3(kWave), lds, s, ka);              \
     } while (0)
-    if (bt && red) AIM_WFW(true, true);
+#define AIM_WFW_EF(BTV)                                                                                                 \
+    do {                                                                                                                \
+        if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, true, true>), dim3(grid), dim3(kWave), lds, s, ka);  \
+        else hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka);         \
+    } while (0)
+    if (ka.p.flags & AIM_FLAG_ENDSFREE) {   // (validate_params: never with REDUCE)
+        if (bt) AIM_WFW_EF(true);
+        else AIM_WFW_EF(false);
+    } else if (bt && red) AIM_WFW(true, true);
     else if (bt) AIM_WFW(true, false);
     else if (red) AIM_WFW(false, true);
     else AIM_WFW(false, false);
 #undef AIM_WFW
+#undef AIM_WFW_EF
 }
 #else
 void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s);

@@ -12,8 +12,8 @@ import math
 import numpy as np
 
 from . import capi
-from .capi import (ALGO_BY_NAME, ALGO_NW, ALGO_SWG, ALGO_WFA, FLAG_BACKTRACE, FLAG_REDUCE, FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16,
-                   REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Params)
+from .capi import (ALGO_BY_NAME, ALGO_NW, ALGO_SWG, ALGO_WFA, FLAG_BACKTRACE, FLAG_ENDSFREE, FLAG_REDUCE, FLAG_REQ8, FLAG_RES8,
+                   FLAG_SWG_W16, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, EndsFreeParams, Params, params_ref)
 
 
 def round_up_8(x):
@@ -29,15 +29,25 @@ def launcher_sizes(algo, read_length, error, mismatch=3, gap_o=4, gap_e=1, gap=4
     return ms.value, rs.value
 
 
+def features():
+    """aim_features(): capability bits of the loaded library (capi.FEATURE_*)."""
+    return int(capi.load().aim_features())
+
+
 def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=1, gap=4, backtrace=False,
-                reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None):
+                reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None):
     """`gap` is the launchers' single NW gap cost (run-nw-pim-wram.py: -DGAP_I = -DGAP_D); `gap_i` / `gap_d` set the two macros of
-    nw.c:67-153 apart (NW/DPU-WRAM/common/common.h GAP_I, GAP_D)."""
+    nw.c:67-153 apart (NW/DPU-WRAM/common/common.h GAP_I, GAP_D). `ends_free=(PB, PE, TB, TE)`: ends-free WFA (AIM_FLAG_ENDSFREE);
+    returns an EndsFreeParams then, which every call below accepts like Params."""
     a = ALGO_BY_NAME[algo] if isinstance(algo, str) else algo
     gap_i = gap if gap_i is None else gap_i
     gap_d = gap if gap_d is None else gap_d
     flags = (FLAG_BACKTRACE if backtrace else 0) | (FLAG_REDUCE if reduce else 0) | (FLAG_SWG_W16 if swg_w16 else 0)
     flags |= (FLAG_REQ8 if req8 else 0) | (FLAG_RES8 if res8 else 0)
+    if ends_free is not None:
+        pb, pe, tb, te = (int(x) for x in ends_free)
+        return EndsFreeParams(Params(a, match, mismatch, gap_o, gap_e, gap_i, gap_d, max_score, read_size, flags | FLAG_ENDSFREE),
+                              pb, pe, tb, te)
     return Params(a, match, mismatch, gap_o, gap_e, gap_i, gap_d, max_score, read_size, flags)
 
 
@@ -57,6 +67,26 @@ def gen_pairs(seed, first_idx, n_pairs, length, error, read_size):
     capi.check(lib.aim_gen_pairs(seed, first_idx, n_pairs, length, float(error), read_size, capi.ptr(req),
                                  capi.ptr(pat), capi.ptr(txt)))
     return req, pat, txt
+
+
+def flank_pairs(seed, first_idx, req, pat, txt, flank):
+    """Ends-free inputs: `flank` seeded random A/C/G/T bases before and after every text (what a read mapper's reference window
+    around a read looks like). Rows widen by 2 * flank (rounded to a multiple of 8); the bases depend on (seed, first_idx)."""
+    n, rs = pat.shape
+    rs2 = round_up_8(rs + 2 * flank)
+    rng = np.random.default_rng([int(seed), int(first_idx), 0x666C616E6B])
+    bases = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=(n, 2 * flank))]
+    req2 = req.copy()
+    pat2 = np.zeros((n, rs2), dtype=np.uint8)
+    txt2 = np.zeros((n, rs2), dtype=np.uint8)
+    pat2[:, :rs] = pat
+    for i in range(n):
+        tl = int(req["text_len"][i])
+        txt2[i, :flank] = bases[i, :flank]
+        txt2[i, flank:flank + tl] = txt[i, :tl]
+        txt2[i, flank + tl:2 * flank + tl] = bases[i, flank:]
+    req2["text_len"] = req["text_len"] + 2 * flank
+    return req2, pat2, txt2
 
 
 def to_request8(req):
@@ -112,7 +142,7 @@ def pack_batch_native(params, req, pat, txt, threads=8):
     cap = max(1, n // 8)
     raw, rawp, rawt = np.zeros(cap, dtype=np.uint32), np.zeros((cap, rs), dtype=np.uint8), np.zeros((cap, rs), dtype=np.uint8)
     nr = C.c_uint32()
-    capi.check(lib.aim_pack_batch(C.byref(params), n, capi.ptr(req), capi.ptr(pat), capi.ptr(txt), capi.ptr(pp), capi.ptr(pt),
+    capi.check(lib.aim_pack_batch(params_ref(params), n, capi.ptr(req), capi.ptr(pat), capi.ptr(txt), capi.ptr(pp), capi.ptr(pt),
                                   capi.ptr(raw), capi.ptr(rawp), capi.ptr(rawt), cap, C.byref(nr), threads))
     k = nr.value
     return pp, pt, raw[:k].copy(), rawp[:k].copy(), rawt[:k].copy()
@@ -179,12 +209,15 @@ def cigar_of(ops_row, begin_offset, end_offset):
     return buf.raw[:n]
 
 
-def format_output(results, ops, backtrace):
-    """Output file of the reference host (host.c:339-349): 'idx, score, \\n' [+ RLE CIGAR line]."""
+def format_output(results, ops, backtrace, ends_free=False):
+    """Output file of the reference host (host.c:339-349): 'idx, score, \\n' [+ RLE CIGAR line]. ends_free: a pair with an empty
+    CIGAR (ends-free over MAX_SCORE) prints an empty CIGAR line, like `host --ends-free`."""
     out = []
     for i in range(len(results)):
         out.append(b"%d, %d, \n" % (int(results["idx"][i]), int(results["score"][i])))
-        if backtrace:
+        if backtrace and ends_free and results["end_offset"][i] <= results["begin_offset"][i]:
+            out.append(b"\n")
+        elif backtrace:
             out.append(cigar_of(ops[i], results["begin_offset"][i], results["end_offset"][i]))
     return b"".join(out)
 
@@ -216,12 +249,12 @@ class DeviceSet:
         self.close()
 
     def configure(self, params, max_pairs_per_device):
-        capi.check(self.lib.aim_set_configure(self.handle, C.byref(params), max_pairs_per_device))
+        capi.check(self.lib.aim_set_configure(self.handle, params_ref(params), max_pairs_per_device))
         self.params = params
         self.max_pairs = max_pairs_per_device
 
     def configure_slots(self, params, max_pairs_per_device, slots=2, max_raw=0, max_runs=0):
-        capi.check(self.lib.aim_set_configure_slots(self.handle, C.byref(params), max_pairs_per_device, slots, max_raw, max_runs))
+        capi.check(self.lib.aim_set_configure_slots(self.handle, params_ref(params), max_pairs_per_device, slots, max_raw, max_runs))
         self.params = params
         self.max_pairs = max_pairs_per_device
         self._inflight = {}
@@ -317,7 +350,7 @@ class DeviceSet:
         """Whole batch over all devices of the set: contiguous blocks (host.c:191-209), results in input order."""
         n = len(req)
         per = max(1, math.ceil(n / self.nr_devices))
-        if self.params is None or bytes(self.params) != bytes(params) or per > self.max_pairs:
+        if self.params is None or bytes(self.params) != bytes(params) or per > self.max_pairs:   # (EndsFreeParams: the extension too)
             self.configure(params, per)
         blocks = []
         for d in range(self.nr_devices):

@@ -4,7 +4,10 @@ seeded generator bench.py and the tests use (`aim_gen_pairs`: pattern = `length`
 ceil(length*error) sequential uniform edits; splitmix64 keyed on (seed, pair index), so any slice of a data set can be
 regenerated independently). No GPU needed.
 
-    python -m aim_amd.gen_dataset -n 40000 -l 100 -e 0.01 -o sample-l100-e1-40K [-s 42]
+    python -m aim_amd.gen_dataset -n 40000 -l 100 -e 0.01 -o sample-l100-e1-40K [-s 42] [--flank F]
+
+--flank F puts F seeded random bases before and after every text (engine.flank_pairs): inputs for ends-free alignment
+(`host --ends-free 0,0,F,F`); READ_SIZE grows by 2F.
 """
 import argparse
 import sys
@@ -12,23 +15,30 @@ import sys
 from . import engine
 
 
-def write_packed(out, seed, num_pairs, length, error, batch):
+def gen(seed, first, n, length, error, read_size, flank):
+    """engine.gen_pairs, then (flank > 0) engine.flank_pairs: rows of read_size + 2 * flank rounded to 8."""
+    req, pat, txt = engine.gen_pairs(seed, first, n, length, error, read_size)
+    return engine.flank_pairs(seed, first, req, pat, txt, flank) if flank else (req, pat, txt)
+
+
+def write_packed(out, seed, num_pairs, length, error, batch, flank=0):
     """Packed batch file (aim_amd/host/host.c, pkfile_hdr_t): 64-byte header, then per batch {n, ascii = 0, n_raw, READ_SIZE} +
     aim_request8_t[n] + packed patterns + packed texts + raw side list (indices, ASCII patterns, ASCII texts)."""
     import math
     import numpy as np
     read_size = int(math.ceil((length + length * error + 7) / 8)) * 8          # run-*-pim-*.py: READ_SIZE
+    rs_file = engine.round_up_8(read_size + 2 * flank) if flank else read_size
     batch = max(1, min(batch, max(num_pairs, 1)))
     hdr = np.zeros(64, dtype=np.uint8)
     hdr[:8] = np.frombuffer(b"AIMPK\0\0\1", dtype=np.uint8)
-    hdr[8:24] = np.array([1, read_size, 8, batch], dtype="<u4").view(np.uint8)
+    hdr[8:24] = np.array([1, rs_file, 8, batch], dtype="<u4").view(np.uint8)
     hdr[24:32] = np.array([num_pairs], dtype="<u8").view(np.uint8)
     out.write(hdr.tobytes())
     for first in range(0, num_pairs, batch):
         n = min(batch, num_pairs - first)
-        req, pat, txt = engine.gen_pairs(seed, first, n, length, error, read_size)
+        req, pat, txt = gen(seed, first, n, length, error, read_size, flank)
         pp, pt, raw, rawp, rawt = engine.pack_batch(req, pat, txt)
-        out.write(np.array([n, 0, len(raw), read_size], dtype="<u4").tobytes())
+        out.write(np.array([n, 0, len(raw), rs_file], dtype="<u4").tobytes())
         out.write(engine.to_request8(req).tobytes())
         for arr in (pp, pt, raw.astype("<u4"), rawp, rawt):
             out.write(np.ascontiguousarray(arr).tobytes())
@@ -46,16 +56,18 @@ def main(argv=None):
                     help="write a packed batch file (2 bits per base + raw side list, the format `host --packed-input` reads and "
                          "`host --pack-only` writes) instead of text; READ_SIZE by the launchers' rule for (-l, -e)")
     ap.add_argument("--batch", type=int, default=1 << 20, help="--packed: pairs per batch of the file")
+    ap.add_argument("--flank", type=int, default=0,
+                    help="F seeded random bases before and after every text (ends-free inputs); READ_SIZE grows by 2F")
     a = ap.parse_args(argv)
-    if a.num_pairs < 0 or a.length <= 0 or not (0.0 <= a.error < 1.0):
-        ap.error("need num-pairs >= 0, length > 0, 0 <= error < 1")
+    if a.num_pairs < 0 or a.length <= 0 or not (0.0 <= a.error < 1.0) or a.flank < 0:
+        ap.error("need num-pairs >= 0, length > 0, 0 <= error < 1, flank >= 0")
     # a text can outgrow the pattern by at most the number of edits; rows are 8-byte multiples like READ_SIZE
     edits = int(-(-a.length * a.error // 1))
     row = (a.length + edits + 1 + 7) // 8 * 8
     out = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
     if a.packed:
         try:
-            write_packed(out, a.seed, a.num_pairs, a.length, a.error, a.batch)
+            write_packed(out, a.seed, a.num_pairs, a.length, a.error, a.batch, a.flank)
         finally:
             if out is not sys.stdout.buffer:
                 out.close()
@@ -63,7 +75,7 @@ def main(argv=None):
     try:
         for first in range(0, a.num_pairs, a.chunk):
             n = min(a.chunk, a.num_pairs - first)
-            req, pat, txt = engine.gen_pairs(a.seed, first, n, a.length, a.error, row)
+            req, pat, txt = gen(a.seed, first, n, a.length, a.error, row, a.flank)
             out.write(engine.pairs_to_text(req, pat, txt))
     finally:
         if out is not sys.stdout.buffer:

@@ -17,6 +17,8 @@
  *     --batch B     pairs per device per launch (default 4194304)
  *     --threads T   host threads for parsing / formatting (default: all cores, max 512; two thirds parse + pack the next
  *                   batch while one third formats the previous one and one more thread writes the one before)
+ *     --ends-free PB,PE,TB,TE  (WFA) ends-free alignment: pattern begin / end and text begin / end free lengths
+ *                   (AIM_FLAG_ENDSFREE, include/aim_hip.h); the output format is unchanged
  *     --packed-input  <input> is a packed batch file (written by --pack-only or `python -m aim_amd.gen_dataset --packed`):
  *                   2 bits per base + raw side list, ready for the device; no text is parsed
  * The UPMEM dispatch (dpu_alloc/dpu_load/dpu_push_xfer/dpu_launch) is replaced
@@ -272,6 +274,7 @@ __attribute__((target("sse4.1,ssse3,bmi2"))) static int pack_seq_simd(const char
 #endif
 
 static int g_simd = 0;
+static int g_ends_free;   /* --ends-free: a pair over MAX_SCORE has an empty CIGAR and prints an empty CIGAR line */
 static inline int pack_seq(const char *seq, long len, int read_size, uint32_t *row, uint32_t row_dw)
 {
 #if defined(__x86_64__)
@@ -507,6 +510,10 @@ static void format_range(int tid, int nt, void *arg)
         o = put_int(o, (int)idx); *o++ = ','; *o++ = ' ';
         o = put_int(o, score); *o++ = ','; *o++ = ' '; *o++ = '\n';
         if (!f->backtrace) continue;
+        if (g_ends_free && (full ? j->res[i].end_offset <= j->res[i].begin_offset : j->cig[i].n_runs == 0)) {
+            *o++ = '\n';                                            /* ends-free pair over MAX_SCORE: empty CIGAR */
+            continue;
+        }
         if (full) {                                                  /* edit_cigar_print, host.c:69-89 */
             const aim_result_t *r = &j->res[i];
             const char *ops = j->ops + i * 2 * rs;
@@ -628,7 +635,7 @@ static void *pinned(size_t bytes)
  * score-only, and one lane's stages are sized for one device. Lanes share nothing but the read-only mapped input and its line
  * index; devices are dealt to lanes round-robin (more lanes than devices: several lanes -- each with its own set -- per device). */
 typedef struct {
-    aim_params_t p;
+    aim_endsfree_params_t xp;   /* xp.base: the params; the free lengths are read only with AIM_FLAG_ENDSFREE */
     int backtrace, use_req8, no_pack, full_ops, packed_input;
     uint32_t batch, slots, max_raw, runs_cap;
     const input_t *inp;
@@ -679,7 +686,7 @@ static void *lane_main(void *arg)
 {
     lane_t *L = arg;
     const cfg_t *c = L->c;
-    const aim_params_t *p = &c->p;
+    const aim_params_t *p = &c->xp.base;
     const size_t rs = (size_t)p->read_size;
     const uint32_t dw = (uint32_t)(p->read_size + 15) / 16u;
     const uint32_t batch = c->batch, slots = c->slots, gpus = L->gpus;
@@ -915,6 +922,7 @@ int main(int argc, char *argv[])
     long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
     int threads = 0;
     int pack_threads_arg = 0, fmt_threads_arg = 0;
+    int ends_free[4] = {0, 0, 0, 0};
     for (int i = 4; i < argc; ++i) {
         const char *f = argv[i];
         const char *v = (i + 1 < argc) ? argv[i + 1] : NULL;
@@ -958,6 +966,17 @@ int main(int argc, char *argv[])
         else if (!strcmp(f, "--pack-threads")) { pack_threads_arg = atoi(v); ++i; }
         else if (!strcmp(f, "--format-threads")) { fmt_threads_arg = atoi(v); ++i; }
         else if (!strcmp(f, "--out-shards")) { shards = (uint32_t)atoi(v); ++i; }
+        else if (!strcmp(f, "--ends-free")) {
+            char tail;
+            if (sscanf(v, "%d,%d,%d,%d%c", &ends_free[0], &ends_free[1], &ends_free[2], &ends_free[3], &tail) != 4 ||
+                ends_free[0] < 0 || ends_free[1] < 0 || ends_free[2] < 0 || ends_free[3] < 0) {
+                fprintf(stderr, "--ends-free PB,PE,TB,TE: four lengths >= 0\n");
+                exit(1);
+            }
+            p.flags |= AIM_FLAG_ENDSFREE;
+            g_ends_free = 1;
+            ++i;
+        }
         else { fprintf(stderr, "unknown flag %s\n", f); exit(1); }
     }
     if (shards > 64) { fprintf(stderr, "--out-shards 1..64\n"); exit(1); }
@@ -977,6 +996,7 @@ int main(int argc, char *argv[])
     const int use_req8 = p.read_size < 32760;                   /* int16 lengths */
     if (use_req8) p.flags |= AIM_FLAG_REQ8;                     /* 8-byte WFA request_t on the wire (common.h:172-177) */
     if (!backtrace) p.flags |= AIM_FLAG_RES8;                   /* score-only: {idx, score} back */
+    if ((p.flags & AIM_FLAG_ENDSFREE) && p.algo != AIM_ALGO_WFA) { fprintf(stderr, "--ends-free needs --algo wfa\n"); exit(1); }
     if (packed_input && (no_pack || pack_only)) { fprintf(stderr, "--packed-input cannot be combined with --no-pack / --pack-only\n"); exit(1); }
 #if defined(__x86_64__)
     g_simd = __builtin_cpu_supports("sse4.1") && __builtin_cpu_supports("ssse3") && __builtin_cpu_supports("bmi2");
@@ -1006,7 +1026,12 @@ int main(int argc, char *argv[])
 
     g_big_alloc = pack_only ? plain : pinned;
     printf("Allocated %d DPU(s)\n", (int)nr_dpus);
-    printf("AIM-HIP: %u MI355X device(s), kernel %s, %d host thread(s)\n", gpus, aim_kernel_name(&p), threads);
+    aim_endsfree_params_t xp;
+    memset(&xp, 0, sizeof xp);
+    xp.base = p;
+    xp.pattern_begin_free = ends_free[0]; xp.pattern_end_free = ends_free[1];
+    xp.text_begin_free = ends_free[2]; xp.text_end_free = ends_free[3];
+    printf("AIM-HIP: %u MI355X device(s), kernel %s, %d host thread(s)\n", gpus, aim_kernel_name(&xp.base), threads);
 
     uint32_t nb_reads_per_dpu = (uint32_t)ROUND_UP_MULTIPLE_8((total_nb_reads / nr_dpus));
     printf("NumReads per dpu = %u\n", nb_reads_per_dpu);
@@ -1136,7 +1161,7 @@ int main(int argc, char *argv[])
     }
     pool_stop(&idx_pool);   /* the lanes bring their own threads */
 
-    cfg.p = p; cfg.backtrace = backtrace; cfg.use_req8 = use_req8; cfg.no_pack = no_pack; cfg.full_ops = full_ops; cfg.packed_input = packed_input;
+    cfg.xp = xp; cfg.backtrace = backtrace; cfg.use_req8 = use_req8; cfg.no_pack = no_pack; cfg.full_ops = full_ops; cfg.packed_input = packed_input;
     cfg.batch = batch; cfg.slots = slots; cfg.max_raw = max_raw; cfg.runs_cap = runs_cap; cfg.inp = &inp; cfg.in_name = in; cfg.out_name = out;
 
     /* deal the input and the devices to the lanes: lane k takes the k-th contiguous run of whole batches */

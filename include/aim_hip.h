@@ -64,6 +64,7 @@ extern "C" {
 #define AIM_FLAG_RES8 0x10u
 #define AIM_SCORE_FAILED ((int32_t)0x80000000) /* aim_result8_t.score of a pair that stopped with a status (see above) */
 
+
 /* Replaces the -D macro set the launchers pass to make
  * (WFA/DPU-WRAM/run-wfa-pim-wram.py:128-131; common.h:63-89). */
 typedef struct aim_params {
@@ -78,6 +79,21 @@ typedef struct aim_params {
     int32_t read_size; /* READ_SIZE: row stride of patterns/texts, multiple of 8 */
     uint32_t flags;    /* AIM_FLAG_*                                          */
 } aim_params_t;
+
+/* AIM_FLAG_ENDSFREE (WFA only, not with AIM_FLAG_REDUCE): ends-free (semi-global) alignment.  The params are then the
+ * `base` of an aim_endsfree_params_t and every entry point taking `const aim_params_t *` also reads its four free lengths
+ * (it never reads past `base` without the flag).  Leading / trailing gaps inside the free lengths cost 0: the alignment
+ * starts at any (v = 0, h <= text_begin_free) or (v <= pattern_begin_free, h = 0) and ends at any (v = plen,
+ * h >= tlen - text_end_free) or (v >= plen - pattern_end_free, h = tlen); every other cost is WFA's.  Each free length is
+ * clamped per pair to that pair's length.  The CIGAR still covers both whole sequences: free runs print as 'I' (a text
+ * base) / 'D' (a pattern base).  A pair whose score exceeds max_score reports max_score + 1, status AIM_PAIR_OK and an
+ * empty CIGAR (begin_offset == end_offset; n_runs == 0).  With all four lengths 0 the results are global WFA's.
+ * Check aim_features() & AIM_FEATURE_ENDSFREE first: older libraries ignore unknown flags. */
+#define AIM_FLAG_ENDSFREE 0x20u
+typedef struct aim_endsfree_params {
+    aim_params_t base;
+    int32_t pattern_begin_free, pattern_end_free, text_begin_free, text_end_free;   /* each >= 0 */
+} aim_endsfree_params_t;
 
 /* Per-pair descriptor: byte-compatible with the NW/SWG request_t
  * (NW/DPU-WRAM/common/common.h:114-120).  The WFA variant of the reference
@@ -121,6 +137,9 @@ typedef struct aim_result8 {
 
 /* ---- library / device discovery ----------------------------------------- */
 int aim_abi_version(void);
+/* Capabilities added without an ABI version change: a binding tests a bit before it sets the matching flag. */
+#define AIM_FEATURE_ENDSFREE 0x1u /* AIM_FLAG_ENDSFREE is honoured */
+uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
 int aim_device_count(int *count);
