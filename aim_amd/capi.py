@@ -16,8 +16,9 @@ LIB_PATH = os.environ.get("AIM_LIB") or os.path.join(_HERE, "libaim_hip.so")   #
 AIM_OK, AIM_EINVAL, AIM_ENODEV, AIM_ENOMEM, AIM_ESTATE, AIM_EALIGN = 0, -1, -2, -3, -4, -5
 ALGO_NW, ALGO_SWG, ALGO_WFA, ALGO_GENASM = 0, 1, 2, 3
 ALGO_BY_NAME = {"nw": ALGO_NW, "swg": ALGO_SWG, "wfa": ALGO_WFA, "genasm": ALGO_GENASM}
-FLAG_BACKTRACE, FLAG_REDUCE, FLAG_SWG_W16, FLAG_REQ8, FLAG_RES8, FLAG_ENDSFREE = 1, 2, 4, 8, 16, 32
+FLAG_BACKTRACE, FLAG_REDUCE, FLAG_SWG_W16, FLAG_REQ8, FLAG_RES8, FLAG_ENDSFREE, FLAG_AFFINE2P = 1, 2, 4, 8, 16, 32, 64
 FEATURE_ENDSFREE = 1   # aim_features(): AIM_FLAG_ENDSFREE is honoured
+FEATURE_AFFINE2P = 2   # aim_features(): AIM_FLAG_AFFINE2P is honoured
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
 
 
@@ -46,9 +47,26 @@ class EndsFreeParams(C.Structure):
             super().__setattr__(name, value)
 
 
+class Affine2pParams(C.Structure):
+    """aim_affine2p_params_t: aim_params_t + the second gap piece of AIM_FLAG_AFFINE2P (include/aim_hip.h). Like EndsFreeParams,
+    the entry points receive a pointer to `base` (params_ref) and fields of the base read and write through."""
+    _fields_ = [("base", Params), ("gap_o2", C.c_int32), ("gap_e2", C.c_int32)]
+
+    _own = ("base", "gap_o2", "gap_e2")
+
+    def __getattr__(self, name):
+        return getattr(self.base, name)
+
+    def __setattr__(self, name, value):
+        if name not in self._own and hasattr(Params, name):
+            setattr(self.base, name, value)
+        else:
+            super().__setattr__(name, value)
+
+
 def params_ref(params):
-    """The `const aim_params_t *` argument for Params or EndsFreeParams (a pointer to the base of the extended struct)."""
-    return C.byref(params.base) if isinstance(params, EndsFreeParams) else C.byref(params)
+    """The `const aim_params_t *` argument for Params, EndsFreeParams or Affine2pParams (a pointer to the base of the extended struct)."""
+    return C.byref(params.base) if isinstance(params, (EndsFreeParams, Affine2pParams)) else C.byref(params)
 
 
 REQUEST_DTYPE = np.dtype([("pattern_len", "<i4"), ("text_len", "<i4"), ("padding", "<i4"), ("idx", "<u4")])

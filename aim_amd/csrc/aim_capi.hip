@@ -200,8 +200,9 @@ uint64_t stateless_budget_bytes(const aim::Knobs &kn)
     return cached[dev];
 }
 
-// AIM_FLAG_ENDSFREE: the params are the base of an aim_endsfree_params_t (aim_hip.h). Every copy this library keeps of a
-// caller's params is a whole aim_endsfree_params_t (aim_set::xparams), so the cast is valid wherever the flag is set.
+// AIM_FLAG_ENDSFREE / AIM_FLAG_AFFINE2P: the params are the base of an aim_endsfree_params_t / aim_affine2p_params_t (aim_hip.h).
+// Every copy this library keeps of a caller's params is a whole XParams (aim_set::xparams), which holds either extension, so the
+// casts are valid wherever the flags are set.
 struct EndsFree { int pb = 0, pe = 0, tb = 0, te = 0; };
 inline bool is_endsfree(const aim_params_t &p) { return (p.flags & AIM_FLAG_ENDSFREE) != 0; }
 inline EndsFree ends_free(const aim_params_t &p)
@@ -212,12 +213,28 @@ inline EndsFree ends_free(const aim_params_t &p)
     e.pb = x.pattern_begin_free; e.pe = x.pattern_end_free; e.tb = x.text_begin_free; e.te = x.text_end_free;
     return e;
 }
-// The params as this library keeps them: the extension copied only when the flag says it exists.
-inline aim_endsfree_params_t copy_params(const aim_params_t &p)
+struct Affine2p { int o2 = 0, e2 = 0; };
+inline bool is_affine2p(const aim_params_t &p) { return (p.flags & AIM_FLAG_AFFINE2P) != 0; }
+inline Affine2p affine2p(const aim_params_t &p)
 {
-    aim_endsfree_params_t x;
+    Affine2p g;
+    if (!is_affine2p(p)) return g;
+    const aim_affine2p_params_t &x = *reinterpret_cast<const aim_affine2p_params_t *>(&p);
+    g.o2 = x.gap_o2; g.e2 = x.gap_e2;
+    return g;
+}
+// The params as this library keeps them: room for either extension, and the extension copied only when a flag says it exists.
+union XParams {
+    aim_params_t base;
+    aim_endsfree_params_t ef;
+    aim_affine2p_params_t a2p;
+};
+inline XParams copy_params(const aim_params_t &p)
+{
+    XParams x;
     memset(&x, 0, sizeof x);
-    if (is_endsfree(p)) x = *reinterpret_cast<const aim_endsfree_params_t *>(&p);
+    if (is_endsfree(p)) x.ef = *reinterpret_cast<const aim_endsfree_params_t *>(&p);
+    else if (is_affine2p(p)) x.a2p = *reinterpret_cast<const aim_affine2p_params_t *>(&p);
     else x.base = p;
     return x;
 }
@@ -226,12 +243,16 @@ int validate_params(const aim_params_t &p)
 {
     if (p.algo != AIM_ALGO_NW && p.algo != AIM_ALGO_SWG && p.algo != AIM_ALGO_WFA && p.algo != AIM_ALGO_GENASM)
         return fail(AIM_EINVAL, "unknown algorithm %d", p.algo);
+    // before either extension is read: the caller's struct holds at most one of them (an aim_affine2p_params_t is shorter than
+    // an aim_endsfree_params_t)
+    if (is_endsfree(p) && is_affine2p(p)) return fail(AIM_EINVAL, "AIM_FLAG_AFFINE2P cannot be combined with AIM_FLAG_ENDSFREE");
     if (p.read_size <= 0 || (p.read_size & 7)) return fail(AIM_EINVAL, "read_size must be a positive multiple of 8 (got %d)", p.read_size);
     if (p.max_score < 0) return fail(AIM_EINVAL, "max_score must be >= 0");
     if ((p.flags & AIM_FLAG_REQ8) && p.read_size >= 32760)
         return fail(AIM_EINVAL, "AIM_FLAG_REQ8 carries int16 lengths: read_size must be < 32760");
     if (p.algo == AIM_ALGO_GENASM) {   // no penalties, no score cap; lengths are int32
         if (is_endsfree(p)) return fail(AIM_EINVAL, "AIM_FLAG_ENDSFREE needs AIM_ALGO_WFA");
+        if (is_affine2p(p)) return fail(AIM_EINVAL, "AIM_FLAG_AFFINE2P needs AIM_ALGO_WFA");
         if ((p.flags & AIM_FLAG_RES8) && (p.flags & AIM_FLAG_BACKTRACE))
             return fail(AIM_EINVAL, "AIM_FLAG_RES8 (idx, score results) cannot be combined with AIM_FLAG_BACKTRACE");
         if (p.read_size > (1 << 24)) return fail(AIM_EINVAL, "read_size must be <= 2^24");
@@ -252,6 +273,12 @@ int validate_params(const aim_params_t &p)
         const EndsFree e = ends_free(p);
         if (e.pb < 0 || e.pe < 0 || e.tb < 0 || e.te < 0)
             return fail(AIM_EINVAL, "ends-free lengths must be >= 0 (got %d,%d,%d,%d)", e.pb, e.pe, e.tb, e.te);
+    }
+    if (is_affine2p(p)) {
+        if (p.algo != AIM_ALGO_WFA) return fail(AIM_EINVAL, "AIM_FLAG_AFFINE2P needs AIM_ALGO_WFA");
+        if (p.flags & AIM_FLAG_REDUCE) return fail(AIM_EINVAL, "AIM_FLAG_AFFINE2P cannot be combined with AIM_FLAG_REDUCE");
+        const Affine2p g = affine2p(p);
+        if (g.o2 <= 0 || g.e2 <= 0) return fail(AIM_EINVAL, "affine2p penalties must be gap_o2, gap_e2 > 0 (got %d,%d)", g.o2, g.e2);
     }
     // the reference's lengths, WFA offsets and NW / SWG cells are int16 (WFA/DPU-WRAM/common/common.h:98-100, 174-175): what it admits
     // is < 32 767; READ_SIZE is a multiple of 8
@@ -275,9 +302,12 @@ int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
     }
     // Ends-free never runs on the lane kernels (their wavefront shapes are fixed at compile time for the global case); it runs on
     // wfa_group where LDS admits the rows widened by PB + TB, else on wfa_wave.
+    // Affine2p likewise: wfa_group where LDS admits the deeper rings, else wfa_wave; never a lane kernel.
     const bool ef = is_endsfree(p);
     const EndsFree efl = ends_free(p);
-    if (p.algo == AIM_ALGO_WFA && (mode & MODE_PACKED_IN) && !ef && !kn.force_wave && !kn.no_lane_pk && !kn.no_lane && !pl->no_lane &&
+    const bool a2p = is_affine2p(p);
+    const Affine2p a2 = affine2p(p);
+    if (p.algo == AIM_ALGO_WFA && (mode & MODE_PACKED_IN) && !ef && !a2p && !kn.force_wave && !kn.no_lane_pk && !kn.no_lane && !pl->no_lane &&
         aim::wfa_lane_packed_supported(p, !kn.no_lane_ext)) {
         // packed rows in; {idx, score}, compact CIGAR or result_t + ops rows out: one kernel per batch, no scratch (wfa_lane_packed.hpp)
         pl->kid = K_WFA_LANE_PK;
@@ -288,14 +318,14 @@ int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
         return AIM_OK;
     }
     if (p.algo == AIM_ALGO_WFA) {
-        const bool lane_ok = !ef && !kn.force_wave && !kn.no_lane && !pl->no_lane && aim::wfa_lane_supported(p, !kn.no_lane_ext);
+        const bool lane_ok = !ef && !a2p && !kn.force_wave && !kn.no_lane && !pl->no_lane && aim::wfa_lane_supported(p, !kn.no_lane_ext);
         aim::GroupCfg gc;
         int gg = 0;
         uint32_t ggrid = 0, gchunk = n_pairs;
         size_t glds = 0, ghist = 0, ghist_pair = 0;
         const bool gpk = (mode & MODE_PACKED_IN) && !kn.no_lane_pk;   // the group kernel reads packed rows itself
         bool group_ok = !lane_ok && !kn.force_wave && !pl->no_lane && !kn.no_group &&
-                        aim::wfa_group_plan(p, n_pairs, kn, gpk, &gc, &gg, &ggrid, &glds, &ghist_pair, efl.pb, efl.tb);
+                        aim::wfa_group_plan(p, n_pairs, kn, gpk, &gc, &gg, &ggrid, &glds, &ghist_pair, efl.pb, efl.tb, a2.o2, a2.e2);
         if (group_ok && ghist_pair) {
             // BACKTRACE: every pair of a launch keeps its history region until the traceback kernel has walked it. Launches are
             // chunks of the batch whose regions fit half of the scratch bound (one chunk whenever possible).
@@ -328,7 +358,7 @@ int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
 #endif
             return AIM_OK;
         }
-        if (!ef && !lane_ok && !kn.force_wave && !kn.no_lane_pk && !kn.no_lane && !pl->no_lane && aim::wfa_lane_packed_supported(p, !kn.no_lane_ext)) {
+        if (!ef && !a2p && !lane_ok && !kn.force_wave && !kn.no_lane_pk && !kn.no_lane && !pl->no_lane && aim::wfa_lane_packed_supported(p, !kn.no_lane_ext)) {
             // ASCII rows of a shape only the packed lane kernel takes (READ_SIZE other than 80 / 112: l = 150 and friends; CIGAR at
             // MAX_SCORE 6..10): pack on the device (batch_io.hpp), run the packed kernel, let the general kernel re-align the
             // non-ACGT pairs (to-do list)
@@ -373,7 +403,7 @@ int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
             pl->pk = gpk;
             // (ends-free: ops rows, then cigar_rle_kernel -- the fused run output of wfa_group_tb_kernel is not used for it: one pair of
             // a host run came back with a void first run, cause not found)
-            pl->emits_runs = bt && (mode & MODE_RUNS_OUT) && !ef;
+            pl->emits_runs = bt && (mode & MODE_RUNS_OUT) && !ef && !a2p;   // (affine2p: ops rows, then cigar_rle_kernel, as ends-free)
             pl->scratch_total = pl->todo_bytes + pl->hist_bytes + fb.scratch_total;
             return AIM_OK;
         }
@@ -382,34 +412,38 @@ int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
         const uint64_t ms = (uint64_t)p.max_score;
         // ends-free: every wavefront is up to PB + TB diagonals wider (the free lengths clamp to the pairs' lengths <= READ_SIZE)
         const uint64_t wide = ef ? (uint64_t)std::min(efl.pb, p.read_size) + (uint64_t)std::min(efl.tb, p.read_size) : 0;
-        const uint64_t full = 3 * (ms + 2) * (ms + 2 + wide) + 64;
+        // affine2p: five rows per wavefront (M, I1, D1, I2, D2) and a live window of max(x, o1+e1, o2+e2) + 1 scores
+        const uint64_t nc = a2p ? 5 : 3;
+        const int Rw = std::max(std::max(p.mismatch, p.gap_o + p.gap_e), a2p ? a2.o2 + a2.e2 : 0);
+        const uint64_t full = nc * (ms + 2) * (ms + 2 + wide) + 64;
         uint64_t cap;
         if (bt) {
             cap = full;
         } else {   // score-only: the pool is a ring that must hold the live window (scores s-R .. s) plus the one being built
-            const uint64_t R = (uint64_t)std::max(p.mismatch, p.gap_o + p.gap_e);
-            cap = std::min(full, (R + 2) * 3 * (2 * ms + 3 + wide));
+            const uint64_t R = (uint64_t)Rw;
+            cap = std::min(full, (R + 2) * nc * (2 * ms + 3 + wide));
         }
         const uint64_t cap_min = bt ? 0 : cap;   // below this a score-only ring would overwrite wavefronts still in use
         pl->meta_cap = (uint32_t)(ms + 2);
         // LDS ring for the live window of wavefronts: max(x, o+e)+1 slots of slot_w diagonals (M, I, D)
         {
-            const uint32_t R = (uint32_t)std::max(p.mismatch, p.gap_o + p.gap_e);
+            const uint32_t R = (uint32_t)Rw;
             uint32_t w = 16;
             while (w < 2 * (uint32_t)ms + 3 + (uint32_t)wide && w < 128) w *= 2;   // 128: keeps 16 workgroups resident per CU at l = 1000 (measured +9 % over 256)
             if (kn.wfa_slotw >= 0) w = (uint32_t)std::max(16, kn.wfa_slotw) & ~15u;
-            while (w > 16 && (uint64_t)(R + 1) * 3 * w * 2 > 24 * 1024) w /= 2;
-            const bool ring_ok = (uint64_t)(R + 1) * 3 * w * 2 <= 24 * 1024 && !kn.wfa_no_ring;
+            while (w > 16 && (uint64_t)(R + 1) * nc * w * 2 > 24 * 1024) w /= 2;
+            const bool ring_ok = (uint64_t)(R + 1) * nc * w * 2 <= 24 * 1024 && !kn.wfa_no_ring;
             pl->ring_slots = ring_ok ? R + 1 : 0;
             pl->slot_w = ring_ok ? w : 0;
         }
         const size_t seq_bytes = 2 * ((size_t)p.read_size + 8);
         pl->seq_lds = seq_bytes <= 40 * 1024;
-        const size_t ring_bytes = ((size_t)pl->ring_slots * 3 * pl->slot_w * sizeof(int16_t) + 15) & ~(size_t)15;
+        const size_t ring_bytes = ((size_t)pl->ring_slots * nc * pl->slot_w * sizeof(int16_t) + 15) & ~(size_t)15;
         pl->lds = aim::kMetaRing * sizeof(aim::WfMeta) + ring_bytes + (pl->seq_lds ? seq_bytes : 0);
         // persistent single-wave workgroups: exactly what is resident (4 waves/SIMD by VGPRs, 160 KiB LDS per CU);
         // a larger grid runs in uneven rounds
-        const uint32_t wg_per_cu = (uint32_t)std::min<size_t>(16, aim::lds_workgroups_per_cu(pl->lds));
+        // (affine2p with BACKTRACE: 142-148 VGPRs, 3 waves per SIMD)
+        const uint32_t wg_per_cu = (uint32_t)std::min<size_t>(a2p && bt ? 12 : 16, aim::lds_workgroups_per_cu(pl->lds));
         uint32_t grid = aim::resident_grid(kn, wg_per_cu);
         const uint32_t need = ((n_pairs + 7u) / 8u) * 8u;
         if (grid > need) grid = std::max(8u, need);
@@ -612,6 +646,9 @@ int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint6
     if (is_endsfree(p)) {
         const EndsFree e = ends_free(p);
         snprintf(efs, sizeof efs, " endsfree=%d,%d,%d,%d", e.pb, e.pe, e.tb, e.te);
+    } else if (is_affine2p(p)) {
+        const Affine2p g = affine2p(p);
+        snprintf(efs, sizeof efs, " affine2p=%d,%d", g.o2, g.e2);
     }
     return snprintf(out, cap, "%s n=%u grid=%u block=%u lds=%zu scratch=%zu budget=%llu%s%s", kernel_name(pl, p), n_pairs, pl.grid,
                     pl.block, pl.lds, pl.scratch_total, (unsigned long long)budget, extra, efs);
@@ -728,6 +765,8 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
     {
         const EndsFree e = ends_free(p);
         ka.ef_pb = e.pb; ka.ef_pe = e.pe; ka.ef_tb = e.tb; ka.ef_te = e.te;
+        const Affine2p g = affine2p(p);
+        ka.a2p_o2 = g.o2; ka.a2p_e2 = g.e2;
     }
     if (kn.poison_ops >= 0 && d_ops && bt)   // debugging aid: results must not depend on what the ops rows held before (only ops[begin_offset, end_offset) is written)
         HIP_TRY(hipMemsetAsync(d_ops, kn.poison_ops & 0xff, (size_t)n_pairs * 2 * p.read_size, stream));
@@ -948,7 +987,7 @@ struct aim_device_ctx {
 
 struct aim_set {
     std::vector<aim_device_ctx> devs;
-    aim_endsfree_params_t xparams;   // the params with their extension (aim_hip.h AIM_FLAG_ENDSFREE); xparams.base is what the plans read
+    XParams xparams;                 // the params with their extension (aim_hip.h AIM_FLAG_ENDSFREE / AIM_FLAG_AFFINE2P); xparams.base is what the plans read
     const aim_params_t &params = xparams.base;
     uint32_t max_pairs = 0, max_raw = 0, max_runs = 0;
     bool configured = false;
@@ -1077,7 +1116,7 @@ int launch_on_slot(aim_set *set, aim_device_ctx &d, aim_slot &s, uint32_t mode =
 extern "C" {
 
 int aim_abi_version(void) { return AIM_ABI_VERSION; }
-uint32_t aim_features(void) { return AIM_FEATURE_ENDSFREE; }
+uint32_t aim_features(void) { return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P; }
 const char *aim_last_error(void) { return g_err; }
 
 int aim_device_count(int *count)

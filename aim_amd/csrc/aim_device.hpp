@@ -44,6 +44,7 @@ struct KArgs {
     uint32_t pair_base;         // the launch covers pairs [pair_base, pair_base + n_pairs) of the batch (chunked launches): pair ids
                                 // appended to a to-do list are batch-relative
     int32_t ef_pb, ef_pe, ef_tb, ef_te;   // AIM_FLAG_ENDSFREE: pattern begin / end, text begin / end free lengths (unclamped; 0 otherwise)
+    int32_t a2p_o2, a2p_e2;               // AIM_FLAG_AFFINE2P: the second gap piece (0 otherwise)
 };
 
 // Request / result access for both wire layouts (aim_hip.h: AIM_FLAG_REQ8 / AIM_FLAG_RES8). The flag tests are wave-uniform.

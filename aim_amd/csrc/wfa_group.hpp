@@ -24,6 +24,12 @@
 // offsets max(k, 0), extended by the group's lanes; every lane notes the smallest of its diagonals whose extended offset sits
 // on an end border, and a group_min after each row ends the pair; the end diagonal travels to the traceback kernel in the
 // TbHead, which writes the trailing free run, walks, and writes the score-0 match stroke and the leading free run.
+//
+// A2P (AIM_FLAG_AFFINE2P, never with REDUCE or EF): dual-cost gap-affine. Two more components, I2 and D2, read M at s - (o2+e2)
+// and themselves at s - e2, in rings of their own (ring_e2 rows); M takes the best of X, I1, D1, I2 and D2. The M / descriptor ring
+// is max(x, o1+e1, o2+e2) + 1 rows deep, the unit is gcd(x, o1+e1, e1, o2+e2, e2), and a history cell is 16 bytes {M, I1, D1, I2, D2, -}
+// (one store). An absent piece-2 component reads as NULL, not as the -10 of an absent I1 / D1, so that a piece 2 that never
+// fires leaves every M offset as global WFA computes it. group_tb_walk_a2p tests piece 1 before piece 2 at every step.
 #pragma once
 
 #include <cstdlib>
@@ -41,6 +47,10 @@
 // register over it cost cfg3 with CIGAR 28 % (4.45 -> 5.71 ms, same box): the bound is stated instead of left to chance.
 #ifndef AIM_GROUP_MIN_WAVES
 #define AIM_GROUP_MIN_WAVES 5
+#endif
+// The A2P kernels (two more components per cell, 16-byte history cells) get their own bound: the plan caps their residency to match.
+#ifndef AIM_GROUP_A2P_MIN_WAVES
+#define AIM_GROUP_A2P_MIN_WAVES 4
 #endif
 #ifndef AIM_GROUP_MAX_PER_CU
 #define AIM_GROUP_MAX_PER_CU 20   // cap on resident single-wave workgroups per CU (5 per SIMD at <= 102 VGPRs; 24 measured worse on cfg3 with CIGAR)
@@ -78,9 +88,10 @@ struct GroupCfg {
                       // score loop counts in units -- row s of the rings / of the history table is score s * unit -- and never
                       // visits the null wavefronts in between (x = 4, o = 6, e = 2: every second step of the reference's loop)
     int efpb, eftb;   // EF kernels: the diagonals -efpb .. eftb of score 0 (free lengths clamped to READ_SIZE); 0 otherwise
+    int ring_e2;      // A2P kernels: rows of the I2 / D2 rings, a power of two > e2 (0 otherwise); history cells are 16 bytes
 };
 
-enum { GF_PRESENT = 1, GF_MNULL = 2, GF_INULL = 4, GF_DNULL = 8, GF_HASI = 16, GF_HASD = 32 };
+enum { GF_PRESENT = 1, GF_MNULL = 2, GF_INULL = 4, GF_DNULL = 8, GF_HASI = 16, GF_HASD = 32, GF_HASI2 = 64, GF_HASD2 = 128 };
 constexpr int kGrpNull = -16384;
 
 // Per-pair history (BACKTRACE): head + one 16-byte descriptor per score + the offsets (see GroupCfg).
@@ -132,8 +143,8 @@ __device__ __forceinline__ int group_min(int v)
 #else
 #define AIM_GSTAMP(i) do { } while (0)
 #endif
-template <int G, bool REDUCE, bool BT, bool MODW = false, bool EF = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MIN_WAVES))) void wfa_group_kernel(KArgs a, GroupCfg c)
+template <int G, bool REDUCE, bool BT, bool MODW = false, bool EF = false, bool A2P = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GROUP_A2P_MIN_WAVES : AIM_GROUP_MIN_WAVES))) void wfa_group_kernel(KArgs a, GroupCfg c)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     debug_poison_lds(a, smem);
@@ -153,12 +164,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
     int16_t *Mw = reinterpret_cast<int16_t *>(mine);                        // [ring_m][wlds]
     int16_t *Iw = Mw + c.ring_m * c.wlds;                                    // [ring_e][wlds]
     int16_t *Dw = Iw + c.ring_e * c.wlds;                                    // [ring_e][wlds]
-    int16_t *meta = Dw + c.ring_e * c.wlds;                                  // [ring_m][4] = klo, khi, flags, pad
-    uint32_t *packed = mine + ((c.ring_m + 2 * c.ring_e) * c.wlds * 2 + c.ring_m * 8 + 3) / 4;   // P then T, np dwords each
+    int16_t *I2w = Dw + c.ring_e * c.wlds;                                   // A2P: [ring_e2][wlds]
+    int16_t *D2w = I2w + (A2P ? c.ring_e2 : 0) * c.wlds;                     // A2P: [ring_e2][wlds]
+    int16_t *meta = A2P ? D2w + c.ring_e2 * c.wlds : Dw + c.ring_e * c.wlds; // [ring_m][4] = klo, khi, flags, pad
+    uint32_t *packed = mine + ((c.ring_m + 2 * c.ring_e + (A2P ? 2 * c.ring_e2 : 0)) * c.wlds * 2 + c.ring_m * 8 + 3) / 4;   // P then T, np dwords each
     uint32_t *pkP = packed, *pkT = packed + c.np;
 
     const int U = c.unit;                                // scores below are in units of U (GroupCfg::unit)
     const int X = a.p.mismatch / U, OE = (a.p.gap_o + a.p.gap_e) / U, E = a.p.gap_e / U, MS = a.p.max_score;
+    const int OE2 = A2P ? (a.a2p_o2 + a.a2p_e2) / U : 0, E2 = A2P ? a.a2p_e2 / U : 0;
     const int kb = c.kbias;
     uint32_t *todo = reinterpret_cast<uint32_t *>(a.scratch);
     // BACKTRACE: every wavefront is also streamed to the pair's history region in HBM (GroupCfg); wfa_group_tb_kernel walks it.
@@ -186,7 +200,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
     // pairs of a wavefront step together), so sm = score % ring_m is a running scalar and the rows of score - x,
     // score - (o+e) and score - e (the only ones ever read; all < ring_m back) are derived from it once per score step.
     // Computing the index at every use instead measured 3-5 % slower on the G <= 16 plans.
-    int score = 0, sm = 0, i_x = 0, i_oe = 0, i_e = 0;
+    int score = 0, sm = 0, i_x = 0, i_oe = 0, i_e = 0, i_oe2 = 0, i_e2 = 0;
     auto back = [&](int d) { const int i = sm - d; return i < 0 ? i + c.ring_m : i; };   // 0 <= d < ring_m
     const int wmask = c.wmask;
     const uint32_t wmagic = (uint32_t)c.wmagic;
@@ -200,6 +214,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
     auto meta_at = [&](int i) { return meta + i * 4; };
     auto islot = [&](int s) { return Iw + (s & (c.ring_e - 1)) * c.wlds; };
     auto dslot = [&](int s) { return Dw + (s & (c.ring_e - 1)) * c.wlds; };
+    auto i2slot = [&](int s) { return I2w + (s & (c.ring_e2 - 1)) * c.wlds; };
+    auto d2slot = [&](int s) { return D2w + (s & (c.ring_e2 - 1)) * c.wlds; };
     auto fence = [&]() { asm volatile("" ::: "memory"); };   // same-wave LDS traffic is ordered; compiler fence only
 
 #ifdef AIM_GROUP_STAMPS
@@ -321,6 +337,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
                               (pe == 0 && te == 0 && k == ak && h >= tlen));
         };
         score = 0; sm = 0; i_x = i_oe = i_e = 0;
+        if (A2P) i_oe2 = i_e2 = 0;
         int final_score = -1;
         bool done = !active || bad != 0u;
 #ifdef AIM_GROUP_COUNT_WIDTHS   // diagnostic builds only: wavefront width statistics into the result (max_operations = sum of widths, begin_offset = steps with width > 32, end_offset = steps with width > 64)
@@ -335,6 +352,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
         char *hreg = BT ? hist_base + (size_t)(active ? pair : 0u) * (size_t)c.hist_pair_bytes : nullptr;
         TbRow *htab = reinterpret_cast<TbRow *>(hreg + sizeof(TbHead));
         uint2 *hpool = reinterpret_cast<uint2 *>(hreg + c.pool_off);   // cells {M, I, D, -}: ONE 8-byte store per computed cell, at its closed-form index (GroupCfg)
+        uint4 *hpool4 = reinterpret_cast<uint4 *>(hreg + c.pool_off);  // A2P: cells {M, I1, D1, I2, D2, -, -, -}, one 16-byte store
         const bool hnarrow = c.wlds != c.wcap;
         if (EF) {   // M[k] = max(k, 0) on [-pb, tb], extended by the group's lanes
             klo = -pb; khi = tb;
@@ -348,7 +366,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
         } else if (g == 0) {
             const int m00 = done ? 0 : extend(0, 0);
             mrow_at(0)[H(0)] = (int16_t)m00;
-            if (BT && !done) hpool[hnarrow ? H(0) : 0] = make_uint2((uint32_t)(uint16_t)m00, 0u);
+            if (BT && !done) {
+                if (A2P) hpool4[hnarrow ? H(0) : 0] = make_uint4((uint32_t)(uint16_t)m00, 0u, 0u, 0u);
+                else hpool[hnarrow ? H(0) : 0] = make_uint2((uint32_t)(uint16_t)m00, 0u);
+            }
             meta[0] = 0; meta[1] = 0; meta[2] = (int16_t)flags;
         }
         if (BT && a.cig == nullptr && active && bad == 0u) {   // memset(cigar->operations, 'M', 2*READ_SIZE), wfa.c:465 (ops-row output only)
@@ -357,7 +378,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
             // (only the pieces that can hold a printed operation: begin_offset >= min(plen, tlen) - MAX_SCORE / e, wfa_lane.hpp)
             // (gap_e == 0: gaps cost nothing to extend and MAX_SCORE bounds no length -- the whole row is written)
             // (EF: begin_offset = #M + #X >= max(plen - pb - pe, tlen - tb - te) - MAX_SCORE / e: free gaps are not bounded by the score)
-            const int p_lo = a.p.gap_e > 0 ? max(0, (EF ? max(plen - pb - pe, tlen - tb - te) : min(plen, tlen)) - a.p.max_score / a.p.gap_e) >> 4 : 0, p_hi = min((plen + tlen + 15) >> 4, (2 * rs) / 16);
+            // (A2P: a gap base costs at least min(e1, e2))
+            const int emin = A2P ? min(a.p.gap_e, a.a2p_e2) : a.p.gap_e;
+            const int p_lo = emin > 0 ? max(0, (EF ? max(plen - pb - pe, tlen - tb - te) : min(plen, tlen)) - a.p.max_score / emin) >> 4 : 0, p_hi = min((plen + tlen + 15) >> 4, (2 * rs) / 16);
             for (int j = p_lo + g; j < p_hi; j += G) orow[j] = mm;
         }
         fence();
@@ -430,6 +453,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
             ++score;
             sm = sm + 1 == c.ring_m ? 0 : sm + 1;
             i_x = back(X); i_oe = back(OE); i_e = back(E);
+            if (A2P) { i_oe2 = back(OE2); i_e2 = back(E2); }
 #if defined(AIM_GROUP_PAD_VALU) || defined(AIM_GROUP_PAD_SALU)
             {   // diagnostic only: N independent ALU ops per score step, to tell issue-bound from stall-bound
 #ifdef AIM_GROUP_PAD_VALU
@@ -456,17 +480,37 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
                 const bool i_e_null = (s_e < 0) || !(e_f & GF_PRESENT) || !(e_f & GF_HASI) || (e_f & GF_INULL);
                 const bool d_e_null = (s_e < 0) || !(e_f & GF_PRESENT) || !(e_f & GF_HASD) || (e_f & GF_DNULL);
                 const bool i_out_null = m_o_null && i_e_null, d_out_null = m_o_null && d_e_null;
+                // A2P: piece 2's sources -- M at s - (o2+e2), I2 / D2 at s - e2
+                int o2_lo = 1, o2_hi = -1, e2_lo = 1, e2_hi = -1;
+                bool m_o2_null = true, i2_e_null = true, d2_e_null = true;
+                if constexpr (A2P) {
+                    const int s_o2 = score - OE2, s_e2 = score - E2;
+                    int o2_f = 0, e2_f = 0;
+                    if (s_o2 >= 0) { const int16_t *m = meta_at(i_oe2); o2_lo = m[0]; o2_hi = m[1]; o2_f = m[2]; }
+                    if (s_e2 >= 0) { const int16_t *m = meta_at(i_e2); e2_lo = m[0]; e2_hi = m[1]; e2_f = m[2]; }
+                    m_o2_null = (s_o2 < 0) || !(o2_f & GF_PRESENT) || (o2_f & GF_MNULL);
+                    i2_e_null = (s_e2 < 0) || !(e2_f & GF_PRESENT) || !(e2_f & GF_HASI2);
+                    d2_e_null = (s_e2 < 0) || !(e2_f & GF_PRESENT) || !(e2_f & GF_HASD2);
+                }
+                const bool i2_out_null = m_o2_null && i2_e_null, d2_out_null = m_o2_null && d2_e_null;
                 if (EF) hit = 0x7fffffff;
                 AIM_GSTAMP(2);   // score++, source descriptors
-                if (m_sub_null && i_out_null && d_out_null) {
+                if (m_sub_null && i_out_null && d_out_null && i2_out_null && d2_out_null) {
                     flags = 0; klo = 0; khi = -1;
                 } else {
                     if (m_sub_null) { sub_lo = 1; sub_hi = -1; }
                     if (m_o_null) { o_lo = 1; o_hi = -1; }
                     if (i_e_null && d_e_null) { e_lo = 1; e_hi = -1; }
-                    const int lo = min(min(sub_lo, o_lo), e_lo) - 1;
-                    const int hi = max(max(sub_hi, o_hi), e_hi) + 1;
+                    int lo = min(min(sub_lo, o_lo), e_lo) - 1;
+                    int hi = max(max(sub_hi, o_hi), e_hi) + 1;
                     flags = GF_PRESENT | (i_out_null ? GF_INULL : GF_HASI) | (d_out_null ? GF_DNULL : GF_HASD);
+                    if constexpr (A2P) {   // (a null source range 1 .. -1 widens nothing beyond k = 0, as for piece 1)
+                        if (m_o2_null) { o2_lo = 1; o2_hi = -1; }
+                        if (i2_e_null && d2_e_null) { e2_lo = 1; e2_hi = -1; }
+                        lo = min(lo, min(o2_lo, e2_lo) - 1);
+                        hi = max(hi, max(o2_hi, e2_hi) + 1);
+                        flags |= (i2_out_null ? 0 : GF_HASI2) | (d2_out_null ? 0 : GF_HASD2);
+                    }
                     klo = lo; khi = hi;
                     int hi_run = hi;                   // the cells this step computes: [lo, hi_run]
                     if (hi - lo + 1 > c.wlds - 2) {   // narrow window outgrown (never true in linear mode): the general kernel takes the pair
@@ -481,6 +525,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
                     const int16_t *r_ms = mrow_at(i_x), *r_mo = mrow_at(i_oe);   // valid rows even when the score does not exist
                     const int16_t *r_ie = islot(s_e < 0 ? 0 : s_e), *r_de = dslot(s_e < 0 ? 0 : s_e);
                     int16_t *om = mrow_at(sm), *oi = islot(score), *od = dslot(score);
+                    const int16_t *r_mo2 = mrow_at(i_oe2), *r_ie2 = A2P ? i2slot(max(score - E2, 0)) : nullptr, *r_de2 = A2P ? d2slot(max(score - E2, 0)) : nullptr;
+                    int16_t *oi2 = A2P ? i2slot(score) : nullptr, *od2 = A2P ? d2slot(score) : nullptr;
+                    uint4 *hrow4 = hpool4 + (hnarrow ? score * wl : score * score + score);   // A2P (never EF)
                     part = 0x7fffffff;
                     int trip = 0;
                     // What an ABSENT component reads as is -10 (the reference's un-computed default), what an out-of-range fetch reads as is NULL:
@@ -515,10 +562,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AIM_GROUP_MI
                         const int sub = (sub_lo <= k && k <= sub_hi) ? raw_ms + 1 : nul_s;                            // m_sub_null: range 1 .. -1 -> -10
                         // M[s][k] as the reference stores it (int16), then affine_wfa_extend (wfa.c:186-208) on that value: a
                         // diagonal's extension depends on nothing but its own offset, so it is applied before the one store
-                        const int ext = extend(k, max(del, max(sub, ins)));
+                        int best = max(del, max(sub, ins));
+                        int ins2 = kGrpNull, del2 = kGrpNull;
+                        if constexpr (A2P) {   // piece 2, fetched together with piece 1 (same round trip); absent or out of range: NULL
+                            const int raw_mo2_m1 = r_mo2[hkm], raw_ie2_m1 = r_ie2[hkm], raw_mo2_p1 = r_mo2[hkp], raw_de2_p1 = r_de2[hkp];
+                            const int ins2_g = (!m_o2_null && o2_lo <= k - 1 && k - 1 <= o2_hi) ? raw_mo2_m1 : kGrpNull;
+                            const int ins2_i = (!i2_e_null && e2_lo <= k - 1 && k - 1 <= e2_hi) ? raw_ie2_m1 : kGrpNull;
+                            ins2 = (ins2_g == kGrpNull && ins2_i == kGrpNull) ? kGrpNull : max(ins2_g, ins2_i) + 1;
+                            if (!i2_out_null) oi2[hk] = (int16_t)ins2;
+                            const int del2_g = (!m_o2_null && o2_lo <= k + 1 && k + 1 <= o2_hi) ? raw_mo2_p1 : kGrpNull;
+                            const int del2_d = (!d2_e_null && e2_lo <= k + 1 && k + 1 <= e2_hi) ? raw_de2_p1 : kGrpNull;
+                            del2 = max(del2_g, del2_d);
+                            if (!d2_out_null) od2[hk] = (int16_t)del2;
+                            best = max(best, max(ins2, del2));
+                        }
+                        const int ext = extend(k, best);
                         om[hk] = (int16_t)ext;
                         if (EF && on_end(k, ext)) hit = min(hit, k);
-                        if (BT) hrow[hnarrow ? hk : k] = make_uint2((uint32_t)(uint16_t)ext | ((uint32_t)(uint16_t)ins << 16), (uint32_t)(uint16_t)del);   // I / D: -10 when absent (never selected)
+                        if (BT && A2P)
+                            hrow4[hnarrow ? hk : k] = make_uint4((uint32_t)(uint16_t)ext | ((uint32_t)(uint16_t)ins << 16), (uint32_t)(uint16_t)del | ((uint32_t)(uint16_t)ins2 << 16),
+                                                                 (uint32_t)(uint16_t)del2, 0u);
+                        else if (BT) hrow[hnarrow ? hk : k] = make_uint2((uint32_t)(uint16_t)ext | ((uint32_t)(uint16_t)ins << 16), (uint32_t)(uint16_t)del);   // I / D: -10 when absent (never selected)
                         const int dist = max(plen - (ext - k), tlen - ext);
                         part = min(part, dist);
                         if (REDUCE) { dist0 = trip == 0 ? dist : dist0; dist1 = trip == 1 ? dist : dist1; dist2 = trip == 2 ? dist : dist2; }
@@ -686,7 +750,105 @@ __device__ __forceinline__ int group_tb_walk(const GroupCfg &c, const TbRow *tab
     return status;
 }
 
-template <bool RUNS, bool MODW, bool EF = false>
+// The A2P walk: the same steps over five components, cells {M, I1, D1, I2, D2, -, -, -} (16 bytes). At every step piece 1 is tested
+// before piece 2 and the global walk's order is kept otherwise (D ext, D open, I ext, I open, then the same for piece 2, then X): a
+// piece 2 equal to piece 1 or one that never fires gives global WFA's CIGAR byte for byte.
+template <bool MODW, typename Sink>
+__device__ __forceinline__ int group_tb_walk_a2p(const GroupCfg &c, const TbRow *tab, const int16_t *pool, int final_score, int plen, int tlen, int X, int OE, int E,
+                                                 int OE2, int E2, Sink &sink)
+{
+    enum { BT_M = 0, BT_I = 1, BT_D = 2, BT_I2 = 3, BT_D2 = 4 };
+    const int ak = tlen - plen;
+    int status = AIM_PAIR_OK;
+    auto valid_loc = [&](int kk_, int off_) {
+        const int v_ = off_ - kk_, h_ = off_;
+        return v_ > 0 && v_ <= plen && h_ > 0 && h_ <= tlen;
+    };
+    struct Row { int klo, khi, f; };
+    auto row = [&](int s_) {
+        const uint2 q = *reinterpret_cast<const uint2 *>(tab + max(s_, 0));
+        Row r;
+        r.klo = (int16_t)(q.x & 0xffffu); r.khi = (int16_t)(q.x >> 16); r.f = (int)(q.y & 0xffffu);
+        if (s_ < 0) { r.klo = 1; r.khi = -1; r.f = 0; }
+        return r;
+    };
+    auto cell = [&](int s_, int which, int k_) -> int {   // which: 0 = M, 1 = I1, 2 = D1, 3 = I2, 4 = D2
+        return pool[8 * group_cell_index<MODW>(c, max(s_, 0), k_) + which];
+    };
+    auto in_row = [](const Row &r, int k_) { return (r.f & GF_PRESENT) && r.klo <= k_ && k_ <= r.khi; };
+    int sc = final_score, k = ak;
+    int offset = cell(sc, 0, k);
+    bool valid = valid_loc(k, offset);
+    int bt = BT_M;
+    int v = offset - k, h = offset;
+    while (v > 0 && h > 0 && sc > 0) {
+        if (!valid) {
+            valid = valid_loc(k, offset);
+            if (valid) {   // add_trailing_gap, wfa_backtracing.c:48-69
+                if (k < ak) for (int i = k; i < ak; ++i) sink.put('I');
+                else if (k > ak) for (int i = ak; i < k; ++i) sink.put('D');
+            }
+        }
+        const int s_o = sc - OE, s_e = sc - E, s_x = sc - X, s_o2 = sc - OE2, s_e2 = sc - E2;
+        const Row ro = row(s_o), re = row(s_e), rx = row(s_x), ro2 = row(s_o2), re2 = row(s_e2);   // addresses depend on (sc, k) only: one round trip
+        const int v_de = cell(s_e, 2, k + 1), v_do = cell(s_o, 0, k + 1), v_ie = cell(s_e, 1, k - 1), v_io = cell(s_o, 0, k - 1), v_mx = cell(s_x, 0, k);
+        const int v_de2 = cell(s_e2, 4, k + 1), v_do2 = cell(s_o2, 0, k + 1), v_ie2 = cell(s_e2, 3, k - 1), v_io2 = cell(s_o2, 0, k - 1);
+        int del_ext = kGrpNull, del_open = kGrpNull, ins_ext = kGrpNull, ins_open = kGrpNull, misms = kGrpNull;
+        int del2_ext = kGrpNull, del2_open = kGrpNull, ins2_ext = kGrpNull, ins2_open = kGrpNull;
+        if (bt == BT_M || bt == BT_D) {
+            if (in_row(re, k + 1) && (re.f & GF_HASD)) del_ext = v_de;
+            if (in_row(ro, k + 1)) del_open = v_do;
+        }
+        if (bt == BT_M || bt == BT_I) {
+            if (in_row(re, k - 1) && (re.f & GF_HASI)) ins_ext = (int16_t)(v_ie + 1);
+            if (in_row(ro, k - 1)) ins_open = (int16_t)(v_io + 1);
+        }
+        if (bt == BT_M || bt == BT_D2) {
+            if (in_row(re2, k + 1) && (re2.f & GF_HASD2)) del2_ext = v_de2;
+            if (in_row(ro2, k + 1)) del2_open = v_do2;
+        }
+        if (bt == BT_M || bt == BT_I2) {
+            if (in_row(re2, k - 1) && (re2.f & GF_HASI2)) ins2_ext = (int16_t)(v_ie2 + 1);
+            if (in_row(ro2, k - 1)) ins2_open = (int16_t)(v_io2 + 1);
+        }
+        if (bt == BT_M && in_row(rx, k)) misms = (int16_t)(v_mx + 1);
+        const int max1 = max(max(ins_ext, ins_open), max(del_ext, del_open)), max2 = max(max(ins2_ext, ins2_open), max(del2_ext, del2_open));
+        const int max_all = max(misms, max(max1, max2));
+        if (bt == BT_M) {
+            const int num_matches = offset - max_all;
+            if (num_matches > 0) sink.matches(num_matches);
+            offset = max_all;
+            v = offset - k;
+            h = offset;
+            if (v <= 0 || h <= 0) break;
+        }
+        char op;
+        if (max_all == del_ext) { op = 'D'; sc = s_e; ++k; bt = BT_D; }
+        else if (max_all == del_open) { op = 'D'; sc = s_o; ++k; bt = BT_M; }
+        else if (max_all == ins_ext) { op = 'I'; sc = s_e; --k; offset = (int16_t)(offset - 1); bt = BT_I; }
+        else if (max_all == ins_open) { op = 'I'; sc = s_o; --k; offset = (int16_t)(offset - 1); bt = BT_M; }
+        else if (max_all == del2_ext) { op = 'D'; sc = s_e2; ++k; bt = BT_D2; }
+        else if (max_all == del2_open) { op = 'D'; sc = s_o2; ++k; bt = BT_M; }
+        else if (max_all == ins2_ext) { op = 'I'; sc = s_e2; --k; offset = (int16_t)(offset - 1); bt = BT_I2; }
+        else if (max_all == ins2_open) { op = 'I'; sc = s_o2; --k; offset = (int16_t)(offset - 1); bt = BT_M; }
+        else if (max_all == misms) { op = 'X'; sc = s_x; offset = (int16_t)(offset - 1); }
+        else { status = AIM_PAIR_WFA_NO_LINK; break; }
+        if (valid) sink.put(op);
+        v = offset - k;
+        h = offset;
+    }
+    if (status == AIM_PAIR_OK) {
+        if (sc == 0) {
+            if (offset > 0) sink.matches(offset);
+        } else {
+            for (; v > 0; --v) sink.put('D');
+            for (; h > 0; --h) sink.put('I');
+        }
+    }
+    return status;
+}
+
+template <bool RUNS, bool MODW, bool EF = false, bool A2P = false>
 __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
 {
     const int lane = threadIdx.x;
@@ -722,7 +884,10 @@ __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
         sink.cap = 2 * rs;
         sink.pos = plen + tlen - 1;                       // edit_cigar_allocate, wfa.c:57-67
         if (walk) {
-            status = group_tb_walk<MODW, EF>(c, tab, pool, final_score / U, hd.end_k, plen, tlen, X, OE, E, sink);
+            if constexpr (A2P)
+                status = group_tb_walk_a2p<MODW>(c, tab, pool, final_score / U, plen, tlen, X, OE, E, (a.a2p_o2 + a.a2p_e2) / U, a.a2p_e2 / U, sink);
+            else
+                status = group_tb_walk<MODW, EF>(c, tab, pool, final_score / U, hd.end_k, plen, tlen, X, OE, E, sink);
             if (status == AIM_PAIR_OK) ++sink.pos;
         } else if (EF) {
             sink.pos = plen + tlen;                       // over the cap: an empty CIGAR
@@ -746,22 +911,26 @@ __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
 // efpb / eftb: ends-free launches (AIM_FLAG_ENDSFREE) -- the pattern-begin and text-begin free lengths; the rows widen by their sum
 // (clamped to READ_SIZE each) and every diagonal keeps its own home.
 inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const Knobs &kn, bool packed, int rows, GroupCfg *c, int *G, uint32_t *grid,
-                                size_t *lds, size_t *hist_pair_bytes, int efpb = 0, int eftb = 0)   // rows: entries per LDS ring row asked for; < 0 = the default rule
+                                size_t *lds, size_t *hist_pair_bytes, int efpb = 0, int eftb = 0, int o2 = 0, int e2 = 0)   // rows: entries per LDS ring row asked for; < 0 = the default rule
 {
     const bool ef = (p.flags & AIM_FLAG_ENDSFREE) != 0;
+    const bool a2p = (p.flags & AIM_FLAG_AFFINE2P) != 0;   // gap_o2 / gap_e2: the extension (the caller passes them)
     if (p.algo != AIM_ALGO_WFA) return false;
     // int16 offsets with NULL = -16384 (offset + 1 must stay above it) and 24-bit home arithmetic bound the shapes; what really decides is LDS below:
     // the packed image (READ_SIZE / 2 bytes per pair) and, without the reduction, rows of 2 * MAX_SCORE + 3 entries. (Rounds 1-3 stopped at READ_SIZE
     // 2048 / MAX_SCORE 400: WFA-adaptive l = 10 000 e = 1 % then ran one pair per wavefront on wfa_wave_kernel, ~11x off cfg3's per-cell rate.)
     if (p.read_size > 16368 || p.max_score > 4000) return false;
-    const int R = p.mismatch > p.gap_o + p.gap_e ? p.mismatch : p.gap_o + p.gap_e;
-    int ring_m = 1, ring_e = 1;
+    if (a2p && (o2 <= 0 || e2 <= 0)) return false;
+    const int R = std::max(p.mismatch > p.gap_o + p.gap_e ? p.mismatch : p.gap_o + p.gap_e, a2p ? o2 + e2 : 0);
+    int ring_m = 1, ring_e = 1, ring_e2 = 0;
     ring_m = R + 1;
     while (ring_e <= p.gap_e) ring_e *= 2;
-    if (ring_m > 32 || ring_e > 16) return false;
+    if (a2p) { ring_e2 = 1; while (ring_e2 <= e2) ring_e2 *= 2; }
+    if (ring_m > 32 || ring_e > 16 || ring_e2 > 16) return false;
     {
         auto gcd = [](int a_, int b_) { while (b_) { const int t = a_ % b_; a_ = b_; b_ = t; } return a_; };
-        const int u = gcd(gcd(p.mismatch, p.gap_o + p.gap_e), p.gap_e);
+        int u = gcd(gcd(p.mismatch, p.gap_o + p.gap_e), p.gap_e);
+        if (a2p) u = gcd(gcd(u, o2 + e2), e2);
         c->unit = (u > 1 && !kn.group_unit1) ? u : 1;
     }
     c->efpb = ef ? std::min(std::max(efpb, 0), p.read_size) : 0;
@@ -770,6 +939,7 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
     c->wcap = 2 * p.max_score + 3 + c->efpb + c->eftb;
     c->ring_m = ring_m;
     c->ring_e = ring_e;
+    c->ring_e2 = ring_e2;
     c->np = (p.read_size + 15) / 16 + 1;
     // Ring rows in LDS. Every diagonal having its own home costs 2*MAX_SCORE+3 entries per row although WFA-adaptive keeps
     // the wavefront narrow (measured, tools/group_widths.py: l = 1000 e = 5 %: mean width 23, 20.6 % of the score steps wider
@@ -797,7 +967,7 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
             }
         }
     }
-    int dw = ((ring_m + 2 * ring_e) * c->wlds * 2 + ring_m * 8 + 3) / 4 + 2 * c->np;
+    int dw = ((ring_m + 2 * ring_e + 2 * ring_e2) * c->wlds * 2 + ring_m * 8 + 3) / 4 + 2 * c->np;
     dw |= 1;
     c->pair_dwords = dw;
     // LDS budget for the wavefront windows of one wavefront's pairs: 12 KiB measured best (occupancy beats lanes per
@@ -845,7 +1015,9 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
     // e = 10 % 18 -> 16 per CU 3.96 -> 3.89 ms, l = 150 e = 2 % 21 -> 20 1.174 -> 1.089 ms); the score-only variants (<= 68 VGPRs, 7
     // wavefronts per SIMD) may use 24 (cfg3 score-only 20 / 22 / 24 / 25 per CU: 3.32 / 3.25 / 3.18 / 3.67 ms), the CIGAR
     // variants are register-bound at 5 per SIMD.
-    const size_t cap_per_cu = (p.flags & AIM_FLAG_BACKTRACE) ? AIM_GROUP_MAX_PER_CU : AIM_GROUP_MAX_PER_CU + 4;   // CIGAR variants: 82-96 VGPRs (history addressing) = 5 per SIMD
+    size_t cap_per_cu = (p.flags & AIM_FLAG_BACKTRACE) ? AIM_GROUP_MAX_PER_CU : AIM_GROUP_MAX_PER_CU + 4;   // CIGAR variants: 82-96 VGPRs (history addressing) = 5 per SIMD
+    // A2P: the CIGAR variants sit at 92-104 VGPRs (their own bound, AIM_GROUP_A2P_MIN_WAVES per SIMD), the score-only ones at 79-90 (5 per SIMD)
+    if (a2p) cap_per_cu = (p.flags & AIM_FLAG_BACKTRACE) ? 4 * AIM_GROUP_A2P_MIN_WAVES : AIM_GROUP_MAX_PER_CU;
     uint32_t per_cu = (uint32_t)std::min<size_t>(cap_per_cu, lds_fit);
     if (per_cu > 16) per_cu &= ~3u;
     if (kn.group_per_cu >= 0) per_cu = (uint32_t)std::min<size_t>((size_t)std::max(1, kn.group_per_cu), lds_fit);   // residency sweeps
@@ -863,10 +1035,11 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
     {
         const uint64_t rows = (uint64_t)p.max_score / (uint64_t)c->unit + 2;
         const uint64_t cells = c->wlds != c->wcap ? rows * (uint64_t)c->wlds : rows * rows + rows * (uint64_t)(c->efpb + c->eftb);
-        if (cells * 8 > (1ull << 30)) return false;
+        const uint64_t cell_b = a2p ? 16 : 8;                 // A2P: {M, I1, D1, I2, D2, -, -, -}
+        if (cells * cell_b > (1ull << 30)) return false;
         c->pool_off = (int)(sizeof(TbHead) + (size_t)rows * sizeof(TbRow));
-        c->pool_cap = (int)cells;                             // cells of 8 bytes {M, I, D, -}
-        c->runs_off = (c->pool_off + c->pool_cap * 8 + 15) & ~15;
+        c->pool_cap = (int)cells;                             // cells of 8 bytes {M, I, D, -} (A2P: 16 bytes)
+        c->runs_off = (int)((c->pool_off + (uint64_t)c->pool_cap * cell_b + 15) & ~15ull);
         c->runs_cap = 2 * p.max_score + 16;
         c->hist_pair_bytes = (c->runs_off + c->runs_cap * 4 + 255) & ~255;
     }
@@ -881,9 +1054,11 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
 // 1.21 -> 1.10 (0); but l=400 e=10 % 1.34 -> 1.73 (57 of 32 768) and l=250 e=10 % 1.59 -> 1.82 (38 of 65 536): every pair that outgrows
 // its row costs a whole general-kernel pass, so wide wavefronts keep 128. (Rows of 80: 42 pairs of cfg3 leave, 3.50 ms; tools/group_rows.py.)
 inline bool wfa_group_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs &kn, bool packed, GroupCfg *c, int *G, uint32_t *grid, size_t *lds,
-                           size_t *hist_pair_bytes, int efpb = 0, int eftb = 0)
+                           size_t *hist_pair_bytes, int efpb = 0, int eftb = 0, int o2 = 0, int e2 = 0)
 {
     if ((p.flags & AIM_FLAG_ENDSFREE) && (p.flags & AIM_FLAG_REDUCE)) return false;
+    if ((p.flags & AIM_FLAG_AFFINE2P) && (p.flags & (AIM_FLAG_REDUCE | AIM_FLAG_ENDSFREE))) return false;
+    if (p.flags & AIM_FLAG_AFFINE2P) return wfa_group_plan_rows(p, n_pairs, kn, packed, kn.group_wlds, c, G, grid, lds, hist_pair_bytes, 0, 0, o2, e2);
     if (p.flags & AIM_FLAG_ENDSFREE) return wfa_group_plan_rows(p, n_pairs, kn, packed, -1, c, G, grid, lds, hist_pair_bytes, efpb, eftb);
     int rows = kn.group_wlds;
     if (rows < 0 && (p.flags & AIM_FLAG_REDUCE) && 2 * p.max_score + 3 >= 192 && 4 * p.max_score <= p.read_size) rows = 96;
@@ -900,6 +1075,10 @@ inline bool wfa_group_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs 
 void wfa_group_tb_launch(const aim_params_t &p, const GroupCfg &c, uint32_t n_pairs, const KArgs &ka, hipStream_t s)
 {
     const uint32_t grid = (n_pairs + kWave - 1) / kWave;
+    if (p.flags & AIM_FLAG_AFFINE2P) {   // (ops rows only, as ends-free; never modulo rows)
+        hipLaunchKernelGGL((wfa_group_tb_kernel<false, false, false, true>), dim3(grid), dim3(kWave), 0, s, ka, c);
+        return;
+    }
     if (p.flags & AIM_FLAG_ENDSFREE) {   // (ops rows only: the plan never fuses the run output of an ends-free launch, aim_capi.hip)
         hipLaunchKernelGGL((wfa_group_tb_kernel<false, false, true>), dim3(grid), dim3(kWave), 0, s, ka, c);
         return;
@@ -938,6 +1117,25 @@ void wfa_group_launch(const aim_params_t &p, int G, const GroupCfg &c, uint32_t 
         default: break;
         }
 #undef AIM_GRP_EF
+        return;
+    }
+    if (p.flags & AIM_FLAG_AFFINE2P) {   // (never with the reduction, never with modulo rows)
+#define AIM_GRP_A2P(GG)                                                                                                        \
+    do {                                                                                                                       \
+        if (bt) hipLaunchKernelGGL((wfa_group_kernel<GG, false, true, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);  \
+        else hipLaunchKernelGGL((wfa_group_kernel<GG, false, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);    \
+    } while (0)
+        switch (G) {
+        case 1: AIM_GRP_A2P(1); break;
+        case 2: AIM_GRP_A2P(2); break;
+        case 4: AIM_GRP_A2P(4); break;
+        case 8: AIM_GRP_A2P(8); break;
+        case 16: AIM_GRP_A2P(16); break;
+        case 32: AIM_GRP_A2P(32); break;
+        case 64: AIM_GRP_A2P(64); break;
+        default: break;
+        }
+#undef AIM_GRP_A2P
         return;
     }
 #define AIM_GRP(GG)                                                                                                     \

@@ -23,6 +23,13 @@
 // soon as any diagonal's M offset sits on an end border (one wave reduction);
 // the traceback writes the trailing free run, walks, writes the score-0 match
 // stroke and then the leading free run.
+//
+// A2P (AIM_FLAG_AFFINE2P, never with REDUCE or EF): dual-cost gap-affine.  Two
+// more components, I2 and D2 (M at s - (o2+e2), themselves at s - e2); M takes
+// the best of X, I1, D1, I2 and D2.  An LDS slot holds five rows, and a score's
+// pool region always holds all five (M, I1, D1, I2, D2 at off_m + comp * len),
+// so WfMeta keeps its 32 bytes and the I2 / D2 offsets are derived.  An absent
+// piece-2 component reads as NULL.  The walk tests piece 1 before piece 2.
 #pragma once
 
 #include "aim_device.hpp"
@@ -41,7 +48,7 @@ struct __attribute__((aligned(16))) WfMeta {
     int off_d;      // pool index of D[lo] (dwavefront != NULL <=> WF_HASD)
     int flags;
 };
-enum { WF_PRESENT = 1, WF_MNULL = 2, WF_INULL = 4, WF_DNULL = 8, WF_INLDS = 16, WF_HASI = 32, WF_HASD = 64 };
+enum { WF_PRESENT = 1, WF_MNULL = 2, WF_INULL = 4, WF_DNULL = 8, WF_INLDS = 16, WF_HASI = 32, WF_HASD = 64, WF_HASI2 = 128, WF_HASD2 = 256 };
 
 constexpr int kMetaRing = 64;        // scores kept in the LDS descriptor ring
 
@@ -85,9 +92,10 @@ __device__ __forceinline__ int wf_extend_count(PtrT P, PtrT T, int v, int h, int
     return count;
 }
 
-template <bool BT, bool REDUCE, bool SEQ_LDS, bool EF = false>
+template <bool BT, bool REDUCE, bool SEQ_LDS, bool EF = false, bool A2P = false>
 __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
 {
+    constexpr int NC = A2P ? 5 : 3;          // components per wavefront: M, I, D (A2P: + I2, D2)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     debug_poison_lds(a, smem);
     const int lane = threadIdx.x;
@@ -96,7 +104,7 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
     WfMeta *ring = reinterpret_cast<WfMeta *>(smem);
     awf_t *oring = reinterpret_cast<awf_t *>(smem + kMetaRing * sizeof(WfMeta));
     const int ring_slots = (int)a.ring_slots, slot_w = (int)a.slot_w;
-    uint32_t *ldsP = reinterpret_cast<uint32_t *>(smem + kMetaRing * sizeof(WfMeta) + (((size_t)ring_slots * 3 * slot_w * sizeof(awf_t) + 15) & ~(size_t)15));
+    uint32_t *ldsP = reinterpret_cast<uint32_t *>(smem + kMetaRing * sizeof(WfMeta) + (((size_t)ring_slots * NC * slot_w * sizeof(awf_t) + 15) & ~(size_t)15));
     uint32_t *ldsT = ldsP + rsw + 2;
 
     char *wscr = a.scratch + (uint64_t)blockIdx.x * a.scratch_per_wave;
@@ -109,18 +117,21 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
 
     const int X = a.p.mismatch, OE = a.p.gap_o + a.p.gap_e, E = a.p.gap_e;
     const int MS = a.p.max_score;
-    // component comp (0 M, 1 I, 2 D) of the wavefront of score sc: LDS slot or HBM pool
-    auto slot = [&](int sc, int comp) -> awf_t * { return oring + ((sc % ring_slots) * 3 + comp) * slot_w; };
+    const int OE2 = A2P ? a.a2p_o2 + a.a2p_e2 : 0, E2 = A2P ? a.a2p_e2 : 0;
+    // component comp (0 M, 1 I, 2 D; A2P: 3 I2, 4 D2) of the wavefront of score sc: LDS slot or HBM pool
+    auto slot = [&](int sc, int comp) -> awf_t * { return oring + ((sc % ring_slots) * NC + comp) * slot_w; };
     // row pointer (biased so that row[k] is diagonal k) -- computed once per score step, never per element
     auto rowp = [&](const WfMeta &m, int sc, int comp) -> const awf_t * {
-        const awf_t *b = (m.flags & WF_INLDS) ? slot(sc, comp) : pool + (comp == 0 ? m.off_m : (comp == 1 ? m.off_i : m.off_d));
+        const awf_t *b = (m.flags & WF_INLDS) ? slot(sc, comp)
+                         : A2P ? pool + m.off_m + comp * (m.hi - m.lo + 1)
+                               : pool + (comp == 0 ? m.off_m : (comp == 1 ? m.off_i : m.off_d));
         return b - m.lo;
     };
 
     // Single-wave workgroup: LDS operations of one wave execute in issue order, so data exchanged through LDS
     // needs no hardware wait, only a compiler fence.  __syncthreads() would add s_waitcnt vmcnt(0), i.e. a full
     // round trip for the history / descriptor stores still in flight -- only paid when a row lives in the HBM pool.
-    const bool meta_in_lds = max(X, OE) < kMetaRing;
+    const bool meta_in_lds = max(max(X, OE), OE2) < kMetaRing;
     auto sync = [&](bool rows_in_lds) {
         if (rows_in_lds && meta_in_lds) asm volatile("" ::: "memory");
         else __syncthreads();
@@ -311,7 +322,20 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
             const bool d_e_null = (s_e < 0) || !(me.flags & WF_PRESENT) || !(me.flags & WF_HASD) || (me.flags & WF_DNULL);
             const bool i_out_null = m_o_null && i_e_null;
             const bool d_out_null = m_o_null && d_e_null;
-            if (m_sub_null && i_out_null && d_out_null) {
+            // A2P: piece 2's sources
+            const int s_o2 = score - OE2, s_e2 = score - E2;
+            WfMeta mo2, me2;
+            mo2.flags = me2.flags = 0;
+            bool m_o2_null = true, i2_e_null = true, d2_e_null = true;
+            if constexpr (A2P) {
+                if (s_o2 >= 0) mo2 = wf_get_meta(ctx, s_o2);
+                if (s_e2 >= 0) me2 = wf_get_meta(ctx, s_e2);
+                m_o2_null = (s_o2 < 0) || !(mo2.flags & WF_PRESENT) || (mo2.flags & WF_MNULL);
+                i2_e_null = (s_e2 < 0) || !(me2.flags & WF_PRESENT) || !(me2.flags & WF_HASI2);
+                d2_e_null = (s_e2 < 0) || !(me2.flags & WF_PRESENT) || !(me2.flags & WF_HASD2);
+            }
+            const bool i2_out_null = m_o2_null && i2_e_null, d2_out_null = m_o2_null && d2_e_null;
+            if (m_sub_null && i_out_null && d_out_null && i2_out_null && d2_out_null) {
                 cur.flags = 0;   // wavefronts[score] = NULL
                 cur.klo = cur.lo = 0; cur.khi = cur.hi = -1;
                 cur.off_m = cur.off_i = cur.off_d = -1;
@@ -323,10 +347,13 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
             const int o_lo = m_o_null ? 1 : mo.klo, o_hi = m_o_null ? -1 : mo.khi;
             const bool e_none = i_e_null && d_e_null;
             const int e_lo = e_none ? 1 : me.klo, e_hi = e_none ? -1 : me.khi;
-            const int lo = min(min(sub_lo, o_lo), e_lo) - 1;
-            const int hi = max(max(sub_hi, o_hi), e_hi) + 1;
+            const int o2_lo = m_o2_null ? 1 : mo2.klo, o2_hi = m_o2_null ? -1 : mo2.khi;
+            const bool e2_none = i2_e_null && d2_e_null;
+            const int e2_lo = e2_none ? 1 : me2.klo, e2_hi = e2_none ? -1 : me2.khi;
+            const int lo = A2P ? min(min(min(sub_lo, o_lo), e_lo), min(o2_lo, e2_lo)) - 1 : min(min(sub_lo, o_lo), e_lo) - 1;
+            const int hi = A2P ? max(max(max(sub_hi, o_hi), e_hi), max(o2_hi, e2_hi)) + 1 : max(max(sub_hi, o_hi), e_hi) + 1;
             const int len = hi - lo + 1;
-            const int narr = 1 + (d_out_null ? 0 : 1) + (i_out_null ? 0 : 1);
+            const int narr = A2P ? 5 : 1 + (d_out_null ? 0 : 1) + (i_out_null ? 0 : 1);   // (A2P: all five rows, at fixed places)
             // allocate_new_score, wfa.c:143-183: an LDS slot when the wavefront fits one; an HBM pool
             // region when it does not, and always with BACKTRACE (history)
             const bool inlds = ring_slots > 0 && len <= slot_w;
@@ -351,13 +378,19 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
             cur.klo = cur.lo = lo;
             cur.khi = cur.hi = hi;
             cur.off_m = in_pool ? pool_used : -1;
-            cur.off_d = (d_out_null || !in_pool) ? -1 : pool_used + len;
-            cur.off_i = (i_out_null || !in_pool) ? -1 : pool_used + len * (d_out_null ? 1 : 2);
+            if constexpr (A2P) {
+                cur.flags |= (i2_out_null ? 0 : WF_HASI2) | (d2_out_null ? 0 : WF_HASD2);
+                cur.off_i = in_pool ? pool_used + len : -1;
+                cur.off_d = in_pool ? pool_used + 2 * len : -1;
+            } else {
+                cur.off_d = (d_out_null || !in_pool) ? -1 : pool_used + len;
+                cur.off_i = (i_out_null || !in_pool) ? -1 : pool_used + len * (d_out_null ? 1 : 2);
+            }
             if (in_pool) pool_used += len * narr;
             wf_put_meta(ctx, score, cur, lane);
             // affine_wfa_compute_offsets, wfa.c:231-266 -- one body, LDS-typed and generic call sites (see extend)
             auto compute_row = [&](const awf_t *r_mo, const awf_t *r_ie, const awf_t *r_de, const awf_t *r_ms, awf_t *om, awf_t *oi,
-                                   awf_t *od) {
+                                   awf_t *od, const awf_t *r_mo2, const awf_t *r_ie2, const awf_t *r_de2, awf_t *oi2, awf_t *od2) {
                 for (int k = lo + lane; k <= hi; k += kWave) {
                     int ins = -10;
                     if (!i_out_null) {
@@ -377,19 +410,44 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
                     }
                     int sub = -10;
                     if (!m_sub_null) sub = (sub_lo <= k && k <= sub_hi) ? (int)(awf_t)(r_ms[k] + 1) : kAwfNull;
-                    om[k - lo] = (awf_t)max(del, max(sub, ins));
+                    int best = max(del, max(sub, ins));
+                    if constexpr (A2P) {   // absent or out of range: NULL (a piece 2 that never fires changes no M offset)
+                        int ins2 = kAwfNull, del2 = kAwfNull;
+                        if (!i2_out_null) {
+                            const int g_ = (!m_o2_null && o2_lo <= k - 1 && k - 1 <= o2_hi) ? (int)r_mo2[k - 1] : kAwfNull;
+                            const int i_ = (!i2_e_null && e2_lo <= k - 1 && k - 1 <= e2_hi) ? (int)r_ie2[k - 1] : kAwfNull;
+                            ins2 = (g_ == kAwfNull && i_ == kAwfNull) ? kAwfNull : (int)(awf_t)(max(g_, i_) + 1);
+                            oi2[k - lo] = (awf_t)ins2;
+                            if (BT && inlds) pool[cur.off_m + 3 * len + (k - lo)] = (awf_t)ins2;
+                        }
+                        if (!d2_out_null) {
+                            const int g_ = (!m_o2_null && o2_lo <= k + 1 && k + 1 <= o2_hi) ? (int)r_mo2[k + 1] : kAwfNull;
+                            const int d_ = (!d2_e_null && e2_lo <= k + 1 && k + 1 <= e2_hi) ? (int)r_de2[k + 1] : kAwfNull;
+                            del2 = max(g_, d_);
+                            od2[k - lo] = (awf_t)del2;
+                            if (BT && inlds) pool[cur.off_m + 4 * len + (k - lo)] = (awf_t)del2;
+                        }
+                        best = max(best, max(ins2, del2));
+                    }
+                    om[k - lo] = (awf_t)best;
                 }
             };
             const bool all_lds = inlds && (m_o_null || (mo.flags & WF_INLDS)) && (e_none || (me.flags & WF_INLDS)) &&
-                                 (m_sub_null || (ms.flags & WF_INLDS));
+                                 (m_sub_null || (ms.flags & WF_INLDS)) &&
+                                 (!A2P || ((m_o2_null || (mo2.flags & WF_INLDS)) && (e2_none || (me2.flags & WF_INLDS))));
             if (all_lds) {
                 compute_row(slot(s_o < 0 ? 0 : s_o, 0) - mo.lo, slot(s_e < 0 ? 0 : s_e, 1) - me.lo, slot(s_e < 0 ? 0 : s_e, 2) - me.lo,
-                            slot(s_sub < 0 ? 0 : s_sub, 0) - ms.lo, slot(score, 0), slot(score, 1), slot(score, 2));
+                            slot(s_sub < 0 ? 0 : s_sub, 0) - ms.lo, slot(score, 0), slot(score, 1), slot(score, 2),
+                            A2P ? slot(s_o2 < 0 ? 0 : s_o2, 0) - mo2.lo : nullptr, A2P ? slot(s_e2 < 0 ? 0 : s_e2, 3) - me2.lo : nullptr,
+                            A2P ? slot(s_e2 < 0 ? 0 : s_e2, 4) - me2.lo : nullptr, A2P ? slot(score, 3) : nullptr, A2P ? slot(score, 4) : nullptr);
             } else {
                 compute_row(m_o_null ? nullptr : rowp(mo, s_o, 0), i_e_null ? nullptr : rowp(me, s_e, 1),
                             d_e_null ? nullptr : rowp(me, s_e, 2), m_sub_null ? nullptr : rowp(ms, s_sub, 0),
                             inlds ? slot(score, 0) : pool + cur.off_m, inlds ? slot(score, 1) : pool + cur.off_i,
-                            inlds ? slot(score, 2) : pool + cur.off_d);
+                            inlds ? slot(score, 2) : pool + cur.off_d,
+                            (!A2P || m_o2_null) ? nullptr : rowp(mo2, s_o2, 0), (!A2P || i2_e_null) ? nullptr : rowp(me2, s_e2, 3),
+                            (!A2P || d2_e_null) ? nullptr : rowp(me2, s_e2, 4), !A2P ? nullptr : inlds ? slot(score, 3) : pool + cur.off_m + 3 * len,
+                            !A2P ? nullptr : inlds ? slot(score, 4) : pool + cur.off_m + 4 * len);
             }
             sync(inlds);
         }
@@ -399,7 +457,7 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
         // Wave-uniform scalar walk; the ops row is pre-filled with 'M' so match
         // runs only move begin_offset, and gap runs are filled by all lanes.
         if (BT && status == AIM_PAIR_OK && final_score <= MS) {
-            enum { BT_M = 0, BT_I = 1, BT_D = 2 };
+            enum { BT_M = 0, BT_I = 1, BT_D = 2, BT_I2 = 3, BT_D2 = 4 };
             const int ops_cap = 2 * rs;
             int sc = final_score, k = EF ? end_k : ak;
             WfMeta m0 = ctx.gmeta[sc];
@@ -437,13 +495,13 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
                 if (s_e >= 0) me = ctx.gmeta[s_e];
                 if (s_x >= 0 && bt == BT_M) mx = ctx.gmeta[s_x];
                 int del_ext = kAwfNull, del_open = kAwfNull, ins_ext = kAwfNull, ins_open = kAwfNull, misms = kAwfNull;
-                if (bt != BT_I) {
+                if (A2P ? (bt == BT_M || bt == BT_D) : bt != BT_I) {   // (A2P: not in the piece-2 states)
                     if ((me.flags & WF_PRESENT) && !(me.flags & WF_DNULL) && me.klo <= k + 1 && k + 1 <= me.khi)
                         del_ext = pool[me.off_d + (k + 1 - me.lo)];
                     if ((mo.flags & WF_PRESENT) && mo.klo <= k + 1 && k + 1 <= mo.khi)
                         del_open = pool[mo.off_m + (k + 1 - mo.lo)];
                 }
-                if (bt != BT_D) {
+                if (A2P ? (bt == BT_M || bt == BT_I) : bt != BT_D) {
                     if ((me.flags & WF_PRESENT) && (me.flags & WF_HASI) && me.klo <= k - 1 && k - 1 <= me.khi)
                         ins_ext = (awf_t)(pool[me.off_i + (k - 1 - me.lo)] + 1);
                     if ((mo.flags & WF_PRESENT) && mo.klo <= k - 1 && k - 1 <= mo.khi)
@@ -453,9 +511,31 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
                     if ((mx.flags & WF_PRESENT) && mx.klo <= k && k <= mx.khi)
                         misms = (awf_t)(pool[mx.off_m + (k - mx.lo)] + 1);
                 }
+                int del2_ext = kAwfNull, del2_open = kAwfNull, ins2_ext = kAwfNull, ins2_open = kAwfNull;
+                if constexpr (A2P) {   // piece 2: M at s - (o2+e2), I2 / D2 at s - e2 (rows at off_m + 3 / 4 * len)
+                    const int s_o2 = sc - OE2, s_e2 = sc - E2;
+                    WfMeta mo2, me2;
+                    mo2.flags = me2.flags = 0;
+                    if (s_o2 >= 0) mo2 = ctx.gmeta[s_o2];
+                    if (s_e2 >= 0) me2 = ctx.gmeta[s_e2];
+                    const int len2 = me2.hi - me2.lo + 1;
+                    if (bt == BT_M || bt == BT_D2) {
+                        if ((me2.flags & WF_PRESENT) && (me2.flags & WF_HASD2) && me2.klo <= k + 1 && k + 1 <= me2.khi)
+                            del2_ext = pool[me2.off_m + 4 * len2 + (k + 1 - me2.lo)];
+                        if ((mo2.flags & WF_PRESENT) && mo2.klo <= k + 1 && k + 1 <= mo2.khi)
+                            del2_open = pool[mo2.off_m + (k + 1 - mo2.lo)];
+                    }
+                    if (bt == BT_M || bt == BT_I2) {
+                        if ((me2.flags & WF_PRESENT) && (me2.flags & WF_HASI2) && me2.klo <= k - 1 && k - 1 <= me2.khi)
+                            ins2_ext = (awf_t)(pool[me2.off_m + 3 * len2 + (k - 1 - me2.lo)] + 1);
+                        if ((mo2.flags & WF_PRESENT) && mo2.klo <= k - 1 && k - 1 <= mo2.khi)
+                            ins2_open = (awf_t)(pool[mo2.off_m + (k - 1 - mo2.lo)] + 1);
+                    }
+                }
                 const int max_del = max(del_ext, del_open);
                 const int max_ins = max(ins_ext, ins_open);
-                const int max_all = max(misms, max(max_ins, max_del));
+                const int max_all = A2P ? max(max(misms, max(max_ins, max_del)), max(max(del2_ext, del2_open), max(ins2_ext, ins2_open)))
+                                        : max(misms, max(max_ins, max_del));
                 if (bt == BT_M) {
                     const int num_matches = offset - max_all;
                     if (num_matches > 0) begin_offset -= num_matches;   // 'M' already in place
@@ -469,6 +549,10 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
                 else if (max_all == del_open) { op = 'D'; sc = s_o; ++k; bt = BT_M; }
                 else if (max_all == ins_ext) { op = 'I'; sc = s_e; --k; offset = (awf_t)(offset - 1); bt = BT_I; }
                 else if (max_all == ins_open) { op = 'I'; sc = s_o; --k; offset = (awf_t)(offset - 1); bt = BT_M; }
+                else if (A2P && max_all == del2_ext) { op = 'D'; sc = sc - E2; ++k; bt = BT_D2; }
+                else if (A2P && max_all == del2_open) { op = 'D'; sc = sc - OE2; ++k; bt = BT_M; }
+                else if (A2P && max_all == ins2_ext) { op = 'I'; sc = sc - E2; --k; offset = (awf_t)(offset - 1); bt = BT_I2; }
+                else if (A2P && max_all == ins2_open) { op = 'I'; sc = sc - OE2; --k; offset = (awf_t)(offset - 1); bt = BT_M; }
                 else if (max_all == misms) { op = 'X'; sc = s_x; offset = (awf_t)(offset - 1); }
                 else { status = AIM_PAIR_WFA_NO_LINK; break; }
                 if (valid) {
@@ -522,7 +606,15 @@ void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds,
         if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, true, true>), dim3(grid), dim3(kWave), lds, s, ka);  \
         else hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka);         \
     } while (0)
-    if (ka.p.flags & AIM_FLAG_ENDSFREE) {   // (validate_params: never with REDUCE)
+#define AIM_WFW_A2P(BTV)                                                                                                \
+    do {                                                                                                                \
+        if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, true, false, true>), dim3(grid), dim3(kWave), lds, s, ka);  \
+        else hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka);         \
+    } while (0)
+    if (ka.p.flags & AIM_FLAG_AFFINE2P) {   // (validate_params: never with REDUCE or ENDSFREE)
+        if (bt) AIM_WFW_A2P(true);
+        else AIM_WFW_A2P(false);
+    } else if (ka.p.flags & AIM_FLAG_ENDSFREE) {   // (validate_params: never with REDUCE)
         if (bt) AIM_WFW_EF(true);
         else AIM_WFW_EF(false);
     } else if (bt && red) AIM_WFW(true, true);
@@ -531,6 +623,7 @@ void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds,
     else AIM_WFW(false, false);
 #undef AIM_WFW
 #undef AIM_WFW_EF
+#undef AIM_WFW_A2P
 }
 #else
 void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s);

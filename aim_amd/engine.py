@@ -12,8 +12,9 @@ import math
 import numpy as np
 
 from . import capi
-from .capi import (ALGO_BY_NAME, ALGO_NW, ALGO_SWG, ALGO_WFA, FLAG_BACKTRACE, FLAG_ENDSFREE, FLAG_REDUCE, FLAG_REQ8, FLAG_RES8,
-                   FLAG_SWG_W16, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, EndsFreeParams, Params, params_ref)
+from .capi import (ALGO_BY_NAME, ALGO_NW, ALGO_SWG, ALGO_WFA, FLAG_AFFINE2P, FLAG_BACKTRACE, FLAG_ENDSFREE, FLAG_REDUCE, FLAG_REQ8,
+                   FLAG_RES8, FLAG_SWG_W16, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
+                   Params, params_ref)
 
 
 def round_up_8(x):
@@ -35,15 +36,21 @@ def features():
 
 
 def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=1, gap=4, backtrace=False,
-                reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None):
+                reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None, gap2=None):
     """`gap` is the launchers' single NW gap cost (run-nw-pim-wram.py: -DGAP_I = -DGAP_D); `gap_i` / `gap_d` set the two macros of
     nw.c:67-153 apart (NW/DPU-WRAM/common/common.h GAP_I, GAP_D). `ends_free=(PB, PE, TB, TE)`: ends-free WFA (AIM_FLAG_ENDSFREE);
-    returns an EndsFreeParams then, which every call below accepts like Params."""
+    returns an EndsFreeParams then, which every call below accepts like Params. `gap2=(O2, E2)`: dual-cost gap-affine WFA
+    (AIM_FLAG_AFFINE2P, gap_o / gap_e are piece 1); returns an Affine2pParams. The two cannot be combined."""
     a = ALGO_BY_NAME[algo] if isinstance(algo, str) else algo
     gap_i = gap if gap_i is None else gap_i
     gap_d = gap if gap_d is None else gap_d
     flags = (FLAG_BACKTRACE if backtrace else 0) | (FLAG_REDUCE if reduce else 0) | (FLAG_SWG_W16 if swg_w16 else 0)
     flags |= (FLAG_REQ8 if req8 else 0) | (FLAG_RES8 if res8 else 0)
+    if ends_free is not None and gap2 is not None:
+        raise ValueError("ends_free and gap2 cannot be combined")
+    if gap2 is not None:
+        o2, e2 = (int(x) for x in gap2)
+        return Affine2pParams(Params(a, match, mismatch, gap_o, gap_e, gap_i, gap_d, max_score, read_size, flags | FLAG_AFFINE2P), o2, e2)
     if ends_free is not None:
         pb, pe, tb, te = (int(x) for x in ends_free)
         return EndsFreeParams(Params(a, match, mismatch, gap_o, gap_e, gap_i, gap_d, max_score, read_size, flags | FLAG_ENDSFREE),
@@ -86,6 +93,38 @@ def flank_pairs(seed, first_idx, req, pat, txt, flank):
         txt2[i, flank:flank + tl] = txt[i, :tl]
         txt2[i, flank + tl:2 * flank + tl] = bases[i, flank:]
     req2["text_len"] = req["text_len"] + 2 * flank
+    return req2, pat2, txt2
+
+
+def long_indel_pairs(seed, first_idx, req, pat, txt, long_indel):
+    """Inputs for dual-cost gap-affine alignment: one seeded insertion or deletion of length in [L/2, L] (L = `long_indel`) put into
+    every text at a seeded position, after the usual edits (the structural-variant-sized indel a long read carries). Rows widen by L
+    (rounded to a multiple of 8); a deletion never empties a text. Each pair's indel depends on (seed, its pair index) only, like
+    gen_pairs' edits, so any slice of a data set -- a text file's chunks or a packed file's batches -- carries the same indels."""
+    n, rs = pat.shape
+    L = int(long_indel)
+    rs2 = round_up_8(rs + L)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    req2 = req.copy()
+    pat2 = np.zeros((n, rs2), dtype=np.uint8)
+    txt2 = np.zeros((n, rs2), dtype=np.uint8)
+    pat2[:, :rs] = pat
+    for i in range(n):
+        rng = np.random.default_rng([int(seed), int(first_idx) + i, 0x6C6F6E67])
+        length = int(rng.integers(max(1, L // 2), L + 1))
+        is_ins = bool(rng.integers(0, 2))
+        where = float(rng.random())
+        tl = int(req["text_len"][i])
+        t = txt[i, :tl]
+        if is_ins:
+            at = int(where * (tl + 1))
+            row = np.concatenate([t[:at], acgt[rng.integers(0, 4, size=length)], t[at:]])
+        else:
+            d = min(length, tl - 1)
+            at = int(where * (tl - d + 1))
+            row = np.concatenate([t[:at], t[at + d:]])
+        txt2[i, :len(row)] = row
+        req2["text_len"][i] = len(row)
     return req2, pat2, txt2
 
 

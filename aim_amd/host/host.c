@@ -19,6 +19,8 @@
  *                   batch while one third formats the previous one and one more thread writes the one before)
  *     --ends-free PB,PE,TB,TE  (WFA) ends-free alignment: pattern begin / end and text begin / end free lengths
  *                   (AIM_FLAG_ENDSFREE, include/aim_hip.h); the output format is unchanged
+ *     --gap2 O2,E2  (WFA) dual-cost gap-affine: a gap of length L costs min(gap_o + L*gap_e, O2 + L*E2)
+ *                   (AIM_FLAG_AFFINE2P, include/aim_hip.h); not with --ends-free or --reduce; the output format is unchanged
  *     --packed-input  <input> is a packed batch file (written by --pack-only or `python -m aim_amd.gen_dataset --packed`):
  *                   2 bits per base + raw side list, ready for the device; no text is parsed
  * The UPMEM dispatch (dpu_alloc/dpu_load/dpu_push_xfer/dpu_launch) is replaced
@@ -274,6 +276,8 @@ __attribute__((target("sse4.1,ssse3,bmi2"))) static int pack_seq_simd(const char
 #endif
 
 static int g_simd = 0;
+/* the params with room for either extension (include/aim_hip.h) */
+typedef union { aim_params_t base; aim_endsfree_params_t ef; aim_affine2p_params_t a2p; } xparams_t;
 static int g_ends_free;   /* --ends-free: a pair over MAX_SCORE has an empty CIGAR and prints an empty CIGAR line */
 static inline int pack_seq(const char *seq, long len, int read_size, uint32_t *row, uint32_t row_dw)
 {
@@ -635,7 +639,7 @@ static void *pinned(size_t bytes)
  * score-only, and one lane's stages are sized for one device. Lanes share nothing but the read-only mapped input and its line
  * index; devices are dealt to lanes round-robin (more lanes than devices: several lanes -- each with its own set -- per device). */
 typedef struct {
-    aim_endsfree_params_t xp;   /* xp.base: the params; the free lengths are read only with AIM_FLAG_ENDSFREE */
+    xparams_t xp;   /* xp.base: the params; the extensions are read only with AIM_FLAG_ENDSFREE / AIM_FLAG_AFFINE2P */
     int backtrace, use_req8, no_pack, full_ops, packed_input;
     uint32_t batch, slots, max_raw, runs_cap;
     const input_t *inp;
@@ -923,6 +927,7 @@ int main(int argc, char *argv[])
     int threads = 0;
     int pack_threads_arg = 0, fmt_threads_arg = 0;
     int ends_free[4] = {0, 0, 0, 0};
+    int gap2[2] = {0, 0};
     for (int i = 4; i < argc; ++i) {
         const char *f = argv[i];
         const char *v = (i + 1 < argc) ? argv[i + 1] : NULL;
@@ -977,6 +982,15 @@ int main(int argc, char *argv[])
             g_ends_free = 1;
             ++i;
         }
+        else if (!strcmp(f, "--gap2")) {
+            char tail;
+            if (sscanf(v, "%d,%d%c", &gap2[0], &gap2[1], &tail) != 2 || gap2[0] <= 0 || gap2[1] <= 0) {
+                fprintf(stderr, "--gap2 O2,E2: two penalties > 0\n");
+                exit(1);
+            }
+            p.flags |= AIM_FLAG_AFFINE2P;
+            ++i;
+        }
         else { fprintf(stderr, "unknown flag %s\n", f); exit(1); }
     }
     if (shards > 64) { fprintf(stderr, "--out-shards 1..64\n"); exit(1); }
@@ -997,6 +1011,9 @@ int main(int argc, char *argv[])
     if (use_req8) p.flags |= AIM_FLAG_REQ8;                     /* 8-byte WFA request_t on the wire (common.h:172-177) */
     if (!backtrace) p.flags |= AIM_FLAG_RES8;                   /* score-only: {idx, score} back */
     if ((p.flags & AIM_FLAG_ENDSFREE) && p.algo != AIM_ALGO_WFA) { fprintf(stderr, "--ends-free needs --algo wfa\n"); exit(1); }
+    if ((p.flags & AIM_FLAG_AFFINE2P) && p.algo != AIM_ALGO_WFA) { fprintf(stderr, "--gap2 needs --algo wfa\n"); exit(1); }
+    if ((p.flags & AIM_FLAG_AFFINE2P) && (p.flags & AIM_FLAG_ENDSFREE)) { fprintf(stderr, "--gap2 cannot be combined with --ends-free\n"); exit(1); }
+    if ((p.flags & AIM_FLAG_AFFINE2P) && (p.flags & AIM_FLAG_REDUCE)) { fprintf(stderr, "--gap2 cannot be combined with --reduce\n"); exit(1); }
     if (packed_input && (no_pack || pack_only)) { fprintf(stderr, "--packed-input cannot be combined with --no-pack / --pack-only\n"); exit(1); }
 #if defined(__x86_64__)
     g_simd = __builtin_cpu_supports("sse4.1") && __builtin_cpu_supports("ssse3") && __builtin_cpu_supports("bmi2");
@@ -1026,11 +1043,16 @@ int main(int argc, char *argv[])
 
     g_big_alloc = pack_only ? plain : pinned;
     printf("Allocated %d DPU(s)\n", (int)nr_dpus);
-    aim_endsfree_params_t xp;
+    xparams_t xp;
     memset(&xp, 0, sizeof xp);
-    xp.base = p;
-    xp.pattern_begin_free = ends_free[0]; xp.pattern_end_free = ends_free[1];
-    xp.text_begin_free = ends_free[2]; xp.text_end_free = ends_free[3];
+    if (p.flags & AIM_FLAG_AFFINE2P) {
+        xp.a2p.base = p;
+        xp.a2p.gap_o2 = gap2[0]; xp.a2p.gap_e2 = gap2[1];
+    } else {
+        xp.ef.base = p;
+        xp.ef.pattern_begin_free = ends_free[0]; xp.ef.pattern_end_free = ends_free[1];
+        xp.ef.text_begin_free = ends_free[2]; xp.ef.text_end_free = ends_free[3];
+    }
     printf("AIM-HIP: %u MI355X device(s), kernel %s, %d host thread(s)\n", gpus, aim_kernel_name(&xp.base), threads);
 
     uint32_t nb_reads_per_dpu = (uint32_t)ROUND_UP_MULTIPLE_8((total_nb_reads / nr_dpus));

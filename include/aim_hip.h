@@ -95,6 +95,20 @@ typedef struct aim_endsfree_params {
     int32_t pattern_begin_free, pattern_end_free, text_begin_free, text_end_free;   /* each >= 0 */
 } aim_endsfree_params_t;
 
+/* AIM_FLAG_AFFINE2P (WFA only; not with AIM_FLAG_REDUCE or AIM_FLAG_ENDSFREE): dual-cost (two-piece) gap-affine penalties.
+ * The params are then the `base` of an aim_affine2p_params_t and every entry point taking `const aim_params_t *` also reads
+ * gap_o2 / gap_e2 (it never reads past `base` without the flag).  A maximal run of L insertions or of L deletions costs
+ * min(gap_o + L*gap_e, gap_o2 + L*gap_e2): base.gap_o / base.gap_e are piece 1; match costs 0, mismatch costs `mismatch`.
+ * The score is the minimum cost of a global alignment; MAX_SCORE, the over-cap result and the ops-row contract are global
+ * WFA's.  A dual-affine cost never exceeds the piece-1 cost of the same alignment, so a max_score sized for piece 1 is
+ * never too small.  With (gap_o2, gap_e2) == (gap_o, gap_e), or gap_o2 + gap_e2 > max_score, the results (CIGAR bytes
+ * included) are global WFA's.  Check aim_features() & AIM_FEATURE_AFFINE2P first: older libraries ignore unknown flags. */
+#define AIM_FLAG_AFFINE2P 0x40u
+typedef struct aim_affine2p_params {
+    aim_params_t base;
+    int32_t gap_o2, gap_e2;   /* piece 2: each > 0 */
+} aim_affine2p_params_t;
+
 /* Per-pair descriptor: byte-compatible with the NW/SWG request_t
  * (NW/DPU-WRAM/common/common.h:114-120).  The WFA variant of the reference
  * uses int16 lengths (WFA/DPU-WRAM/common/common.h:172-177); a binding widens
@@ -139,6 +153,7 @@ typedef struct aim_result8 {
 int aim_abi_version(void);
 /* Capabilities added without an ABI version change: a binding tests a bit before it sets the matching flag. */
 #define AIM_FEATURE_ENDSFREE 0x1u /* AIM_FLAG_ENDSFREE is honoured */
+#define AIM_FEATURE_AFFINE2P 0x2u /* AIM_FLAG_AFFINE2P is honoured */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
