@@ -64,29 +64,32 @@ enum KernelId { K_WFA_WAVE = 0, K_WFA_LANE = 1, K_DP_LANE = 2, K_DP_WAVE = 3, K_
 // kernels of batch_io.hpp around the launch.
 enum : uint32_t { MODE_PACKED_IN = 1u, MODE_RUNS_OUT = 2u };
 
-struct Plan {
+// One kernel launch of a plan: its main kernel, or the general kernel that drains the main kernel's to-do list.
+struct Stage {
     KernelId kid;
     uint32_t grid;          // workgroups
     uint32_t block;         // threads per workgroup
     size_t lds;             // dynamic LDS bytes
-    uint64_t scratch_per_wg;
-    uint32_t pool_cap, meta_cap;
-    uint32_t ring_slots, slot_w;
-    bool seq_lds;
+    uint64_t scratch_per_wg;   // KArgs::scratch_per_wave
+    size_t scratch_at;      // where the stage's scratch starts
+    uint32_t pool_cap, meta_cap, ring_slots, slot_w;   // K_WFA_WAVE (wfa_wave_plan)
+    bool seq_lds;           // K_WFA_WAVE: both sequences staged in LDS
+    int strip_k;            // K_DP_STRIP: cells per lane
+    int seq;                // K_DP_LANE: where the pattern row lives, 0 global memory, 1 LDS image, 2 registers (dp_lane_plan)
+};
+
+struct Plan {
+    Stage main;
+    Stage fb;               // the to-do pass behind the main kernel (wfa_wave, dp_lane or dp_strip); planned iff todo_bytes != 0
+    // the scratch layout, offsets from its base
     size_t scratch_total;
-    size_t todo_bytes;      // K_WFA_LANE: to-do region in front of the fallback kernel's scratch
-    uint32_t fb_grid;       // K_WFA_LANE / K_WFA_GROUP: grid / LDS of the fallback (general) kernel
-    size_t fb_lds;
-    bool no_lane;
-    size_t hist_bytes;      // K_WFA_GROUP + BACKTRACE: history regions (one per pair of a chunk) between to-do region and fallback scratch
+    size_t todo_at, todo_bytes;   // to-do region {count @0, pair ids @16..} the main kernel fills and the fallback drains
+    size_t hist_at, hist_bytes;   // K_WFA_GROUP + BACKTRACE: history regions (one per pair of a chunk; two alternating buffers when chunked)
+    size_t flags_at, pack_p_at, pack_t_at;   // pack_first: non-ACGT flag bits, packed patterns, packed texts
     uint32_t chunk_pairs;   // K_WFA_GROUP + BACKTRACE: pairs per compute + traceback launch (their history regions fit the scratch bound)
     aim::GroupCfg gcfg;     // K_WFA_GROUP
     int group_g;
-    int strip_k;            // K_DP_STRIP: cells per lane (K_DP_GROUP: of the fallback launch; 0 = its fallback is a dp_lane.hpp kernel)
-    uint32_t fb_block;      // K_DP_GROUP: workgroup size of a dp_strip fallback
-    uint64_t fb_scratch_per_wg;   // K_DP_GROUP: ... and its slab size (the fallback's scratch starts at offset 0 like the group kernel's: they never run together)
-    bool pack_first;        // K_WFA_LANE_PK on a batch of ASCII rows: pack_rows_kernel first (scratch: to-do | flag bits | packed P | packed T | general kernel)
-    size_t pack_bytes;      // ... bytes of the flag bits + both packed arrays
+    bool pack_first;        // K_WFA_LANE_PK on a batch of ASCII rows: pack_rows_kernel first
     bool pk;                // the kernel reads the packed rows of the batch itself (no unpack pass)
     bool emits_runs;        // the kernel writes aim_cigar_t + runs itself (no ops rows, no cigar_rle_kernel)
 };
@@ -289,333 +292,259 @@ int validate_params(const aim_params_t &p)
 
 inline bool p_is_nw(const aim_params_t *p) { return p->algo == AIM_ALGO_NW; }
 
-int make_plan_inner(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, uint32_t mode, Plan *pl)
+inline size_t stage_bytes(const Stage &st) { return (size_t)(st.scratch_per_wg * st.grid); }
+
+// GenASM: one pair per wavefront; slow-path columns in one slab per wavefront
+int plan_genasm(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, Plan *pl)
 {
-    int rc = AIM_OK;
-    const bool bt = p.flags & AIM_FLAG_BACKTRACE;
-    if (p.algo == AIM_ALGO_GENASM) {
-        pl->kid = K_GENASM;
-        aim::genasm_plan(p, kn, n_pairs, &pl->grid, &pl->block, &pl->lds);
-        pl->scratch_per_wg = aim::kGaSlabBytes;
-        pl->scratch_total = (size_t)pl->grid * aim::kGaSlabBytes;   // slow-path columns, one slab per wavefront
-        return AIM_OK;
+    Stage &m = pl->main;
+    m.kid = K_GENASM;
+    aim::genasm_plan(p, kn, n_pairs, &m.grid, &m.block, &m.lds);
+    m.scratch_per_wg = aim::kGaSlabBytes;
+    pl->scratch_total = stage_bytes(m);
+    return AIM_OK;
+}
+
+int plan_wfa_wave(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, Stage *st)
+{
+    const EndsFree e = ends_free(p);
+    const Affine2p g = affine2p(p);
+    aim::WfaWavePlan w;
+    switch (aim::wfa_wave_plan(p, n_pairs, kn, budget, e.pb, e.tb, g.o2, g.e2, &w)) {
+    case aim::kWfaWaveNoPool: return fail(AIM_ENOMEM, "scratch budget too small for max_score %d", p.max_score);
+    case aim::kWfaWaveNoScore0:
+        return fail(AIM_ENOMEM, "scratch budget too small for the ends-free score-0 wavefront (%llu diagonals)", (unsigned long long)(w.wide + 1));
+    case aim::kWfaWaveNoWindow: return fail(AIM_ENOMEM, "scratch budget too small for the live window of max_score %d", p.max_score);
     }
-    // Ends-free never runs on the lane kernels (their wavefront shapes are fixed at compile time for the global case); it runs on
-    // wfa_group where LDS admits the rows widened by PB + TB, else on wfa_wave.
-    // Affine2p likewise: wfa_group where LDS admits the deeper rings, else wfa_wave; never a lane kernel.
-    const bool ef = is_endsfree(p);
-    const EndsFree efl = ends_free(p);
-    const bool a2p = is_affine2p(p);
+    st->kid = K_WFA_WAVE;
+    st->grid = w.grid;
+    st->block = 64;
+    st->lds = w.lds;
+    st->scratch_per_wg = w.scratch_per_wg;
+    st->pool_cap = w.pool_cap;
+    st->meta_cap = w.meta_cap;
+    st->ring_slots = w.ring_slots;
+    st->slot_w = w.slot_w;
+    st->seq_lds = w.seq_lds;
+    return AIM_OK;
+}
+
+// wfa_group_kernel's shape; with BACKTRACE also the chunks of the batch whose history regions fit half of the scratch bound.
+// False when LDS does not admit the shape or too few pairs would be in flight.
+bool plan_wfa_group(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, bool gpk, Plan *pl)
+{
+    const EndsFree e = ends_free(p);
     const Affine2p a2 = affine2p(p);
-    if (p.algo == AIM_ALGO_WFA && (mode & MODE_PACKED_IN) && !ef && !a2p && !kn.force_wave && !kn.no_lane_pk && !kn.no_lane && !pl->no_lane &&
-        aim::wfa_lane_packed_supported(p, !kn.no_lane_ext)) {
+    Stage &m = pl->main;
+    size_t hist_pair = 0;
+    if (!aim::wfa_group_plan(p, n_pairs, kn, gpk, &pl->gcfg, &pl->group_g, &m.grid, &m.lds, &hist_pair, e.pb, e.tb, a2.o2, a2.e2))
+        return false;
+    m.kid = K_WFA_GROUP;
+    m.block = 64;
+    pl->chunk_pairs = n_pairs;
+    if (!hist_pair) return true;
+    // BACKTRACE: every pair of a launch keeps its history region until the traceback kernel has walked it. Launches are
+    // chunks of the batch whose regions fit half of the scratch bound (one chunk whenever possible).
+    // One launch when the regions fit. (AIM_GROUP_OVERLAP=1: chunks of two grid rounds, two alternating buffers of regions, the
+    // traceback kernel of chunk c on a second stream while chunk c + 1 is computed. Measured and NOT adopted: cfg3 3.57 ->
+    // 3.79 ms, l = 100 e = 5 % 1.62 -> 1.75 ms -- several shorter compute launches lose more to ramp-up and partial rounds than
+    // the overlapped 10 % traceback gives back. Kept as a tested code path: it is also what a batch does whose regions do
+    // not fit the scratch bound.)
+    const uint64_t fit = (budget / 4) / hist_pair;          // per buffer
+    if (fit < 4096 && fit < n_pairs) return false;   // too few pairs in flight to fill the chip: the general kernel's pools are smaller
+    const uint64_t two_rounds = 2ull * m.grid * (uint64_t)(64 / pl->group_g);
+    uint64_t chunk = std::min<uint64_t>(fit, std::max<uint64_t>(two_rounds, 4096));
+    if (n_pairs <= 2 * fit && (chunk >= n_pairs || !kn.group_overlap)) chunk = n_pairs;   // one launch, one buffer of regions (half the bound)
+    else if (!kn.group_overlap) chunk = fit;                                                  // as few launches as fit, over the two buffers
+    uint32_t c = (uint32_t)chunk;
+    if (c < n_pairs) c &= ~63u;
+    const uint32_t nchunks = (n_pairs + c - 1) / c;
+    pl->chunk_pairs = c;
+    pl->hist_bytes = ((((size_t)c * hist_pair) + 255) & ~(size_t)255) * (nchunks > 1 ? 2 : 1);
+    return true;
+}
+
+// WFA: a lane kernel where it takes the shape; else wfa_group, or wfa_lane_packed behind pack_rows_kernel, with wfa_wave over their
+// to-do list; else wfa_wave alone. Ends-free and affine2p never run on the lane kernels (their wavefront shapes are fixed at compile
+// time for the global case): wfa_group where LDS admits the wider rows / deeper rings, else wfa_wave.
+int plan_wfa(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, uint32_t mode, Plan *pl)
+{
+    const bool bt = p.flags & AIM_FLAG_BACKTRACE;
+    const bool lanes = !is_endsfree(p) && !is_affine2p(p) && !kn.force_wave && !kn.no_lane;   // a lane kernel may run
+    const bool lane_pk_ok = lanes && !kn.no_lane_pk && aim::wfa_lane_packed_supported(p, !kn.no_lane_ext);
+    Stage &m = pl->main;
+    if ((mode & MODE_PACKED_IN) && lane_pk_ok) {
         // packed rows in; {idx, score}, compact CIGAR or result_t + ops rows out: one kernel per batch, no scratch (wfa_lane_packed.hpp)
-        pl->kid = K_WFA_LANE_PK;
-        aim::wfa_lane_packed_plan(p, n_pairs, kn, &pl->grid, &pl->block, &pl->lds);
+        m.kid = K_WFA_LANE_PK;
+        aim::wfa_lane_packed_plan(p, n_pairs, kn, &m.grid, &m.block, &m.lds);
         pl->scratch_total = 256;
         pl->pk = true;
         pl->emits_runs = bt && (mode & MODE_RUNS_OUT);
         return AIM_OK;
     }
-    if (p.algo == AIM_ALGO_WFA) {
-        const bool lane_ok = !ef && !a2p && !kn.force_wave && !kn.no_lane && !pl->no_lane && aim::wfa_lane_supported(p, !kn.no_lane_ext);
-        aim::GroupCfg gc;
-        int gg = 0;
-        uint32_t ggrid = 0, gchunk = n_pairs;
-        size_t glds = 0, ghist = 0, ghist_pair = 0;
-        const bool gpk = (mode & MODE_PACKED_IN) && !kn.no_lane_pk;   // the group kernel reads packed rows itself
-        bool group_ok = !lane_ok && !kn.force_wave && !pl->no_lane && !kn.no_group &&
-                        aim::wfa_group_plan(p, n_pairs, kn, gpk, &gc, &gg, &ggrid, &glds, &ghist_pair, efl.pb, efl.tb, a2.o2, a2.e2);
-        if (group_ok && ghist_pair) {
-            // BACKTRACE: every pair of a launch keeps its history region until the traceback kernel has walked it. Launches are
-            // chunks of the batch whose regions fit half of the scratch bound (one chunk whenever possible).
-            // One launch when the regions fit. (AIM_GROUP_OVERLAP=1: chunks of two grid rounds, two alternating buffers of regions, the
-            // traceback kernel of chunk c on a second stream while chunk c + 1 is computed. Measured and NOT adopted: cfg3 3.57 ->
-            // 3.79 ms, l = 100 e = 5 % 1.62 -> 1.75 ms -- several shorter compute launches lose more to ramp-up and partial rounds than
-            // the overlapped 10 % traceback gives back. Kept as a tested code path: it is also what a batch does whose regions do
-            // not fit the scratch bound.)
-            const uint64_t fit = (budget / 4) / ghist_pair;          // per buffer
-            if (fit < 4096 && fit < n_pairs) group_ok = false;   // too few pairs in flight to fill the chip: the general kernel's pools are smaller
-            else {
-                const uint64_t two_rounds = 2ull * ggrid * (uint64_t)(64 / gg);
-                uint64_t chunk = std::min<uint64_t>(fit, std::max<uint64_t>(two_rounds, 4096));
-                if (n_pairs <= 2 * fit && (chunk >= n_pairs || !kn.group_overlap)) chunk = n_pairs;   // one launch, one buffer of regions (half the bound)
-                else if (!kn.group_overlap) chunk = fit;                                                  // as few launches as fit, over the two buffers
-                gchunk = (uint32_t)chunk;
-                if (gchunk < n_pairs) gchunk &= ~63u;
-                const uint32_t nchunks = (n_pairs + gchunk - 1) / gchunk;
-                ghist = ((((size_t)gchunk * ghist_pair) + 255) & ~(size_t)255) * (nchunks > 1 ? 2 : 1);
-            }
-        }
-        if (lane_ok) {
-            // one pair per lane, everything in registers; no scratch, no second kernel (pairs with bytes outside A/C/G/T take
-            // the kernel's own raw-byte path)
-            pl->kid = K_WFA_LANE;
-            aim::wfa_lane_plan(p, n_pairs, kn, &pl->grid, &pl->block, &pl->lds);
-            pl->scratch_total = 256;   // unused; aim_scratch_bytes() keeps 0 for "invalid configuration"
+    if (lanes && aim::wfa_lane_supported(p, !kn.no_lane_ext)) {
+        // one pair per lane, everything in registers; no scratch, no second kernel (pairs with bytes outside A/C/G/T take
+        // the kernel's own raw-byte path)
+        m.kid = K_WFA_LANE;
+        aim::wfa_lane_plan(p, n_pairs, kn, &m.grid, &m.block, &m.lds);
+        m.scratch_per_wg = 256;
+        pl->scratch_total = 256;   // unused; aim_scratch_bytes() keeps 0 for "invalid configuration"
 #if AIM_LANE_STAMPS
-            pl->scratch_total += (size_t)pl->grid * 64;   // diagnostic builds park their s_memtime sums behind the first 256 bytes
+        pl->scratch_total += (size_t)m.grid * 64;   // diagnostic builds park their s_memtime sums behind the first 256 bytes
 #endif
-            return AIM_OK;
-        }
-        if (!ef && !a2p && !lane_ok && !kn.force_wave && !kn.no_lane_pk && !kn.no_lane && !pl->no_lane && aim::wfa_lane_packed_supported(p, !kn.no_lane_ext)) {
-            // ASCII rows of a shape only the packed lane kernel takes (READ_SIZE other than 80 / 112: l = 150 and friends; CIGAR at
-            // MAX_SCORE 6..10): pack on the device (batch_io.hpp), run the packed kernel, let the general kernel re-align the
-            // non-ACGT pairs (to-do list)
-            Plan fb;
-            memset(&fb, 0, sizeof fb);
-            fb.no_lane = true;
-            aim::Knobs kq = kn;
-            kq.no_group = true;
-            rc = make_plan_inner(p, std::min<uint32_t>(n_pairs, 1024u * 64u), kq, budget, 0u, &fb);
-            if (rc) return rc;
-            *pl = fb;
-            pl->fb_grid = fb.grid;
-            pl->fb_lds = fb.lds;
-            pl->kid = K_WFA_LANE_PK;
-            aim::wfa_lane_packed_plan(p, n_pairs, kn, &pl->grid, &pl->block, &pl->lds);
-            pl->pack_first = true;
-            pl->todo_bytes = aim::wfa_lane_todo_bytes(n_pairs);
-            const size_t npw = aim::packed_row_dwords(p.read_size);
-            pl->pack_bytes = ((((size_t)n_pairs + 31) / 32 * 4 + 255) & ~(size_t)255) + 2 * ((((size_t)n_pairs * npw * 4) + 64 + 255) & ~(size_t)255);
-            pl->scratch_total = pl->todo_bytes + pl->pack_bytes + fb.scratch_total;
-            return AIM_OK;
-        }
-        if (group_ok) {
-            // fast path + the general kernel in to-do mode behind it (its plan goes into *pl first)
-            Plan fb;
-            memset(&fb, 0, sizeof fb);
-            fb.no_lane = true;
-            rc = make_plan_inner(p, std::min<uint32_t>(n_pairs, 1024u * 64u), kn, budget, 0u, &fb);
-            if (rc) return rc;
-            *pl = fb;
-            pl->fb_grid = fb.grid;
-            pl->fb_lds = fb.lds;
-            pl->kid = K_WFA_GROUP;
-            pl->gcfg = gc;
-            pl->group_g = gg;
-            pl->grid = ggrid;
-            pl->block = 64;
-            pl->lds = glds;
-            pl->todo_bytes = aim::wfa_lane_todo_bytes(n_pairs);
-            pl->hist_bytes = ghist;
-            pl->chunk_pairs = gchunk;
-            pl->pk = gpk;
-            // (ends-free: ops rows, then cigar_rle_kernel -- the fused run output of wfa_group_tb_kernel is not used for it: one pair of
-            // a host run came back with a void first run, cause not found)
-            pl->emits_runs = bt && (mode & MODE_RUNS_OUT) && !ef && !a2p;   // (affine2p: ops rows, then cigar_rle_kernel, as ends-free)
-            pl->scratch_total = pl->todo_bytes + pl->hist_bytes + fb.scratch_total;
-            return AIM_OK;
-        }
-        pl->kid = K_WFA_WAVE;
-        pl->block = 64;
-        const uint64_t ms = (uint64_t)p.max_score;
-        // ends-free: every wavefront is up to PB + TB diagonals wider (the free lengths clamp to the pairs' lengths <= READ_SIZE)
-        const uint64_t wide = ef ? (uint64_t)std::min(efl.pb, p.read_size) + (uint64_t)std::min(efl.tb, p.read_size) : 0;
-        // affine2p: five rows per wavefront (M, I1, D1, I2, D2) and a live window of max(x, o1+e1, o2+e2) + 1 scores
-        const uint64_t nc = a2p ? 5 : 3;
-        const int Rw = std::max(std::max(p.mismatch, p.gap_o + p.gap_e), a2p ? a2.o2 + a2.e2 : 0);
-        const uint64_t full = nc * (ms + 2) * (ms + 2 + wide) + 64;
-        uint64_t cap;
-        if (bt) {
-            cap = full;
-        } else {   // score-only: the pool is a ring that must hold the live window (scores s-R .. s) plus the one being built
-            const uint64_t R = (uint64_t)Rw;
-            cap = std::min(full, (R + 2) * nc * (2 * ms + 3 + wide));
-        }
-        const uint64_t cap_min = bt ? 0 : cap;   // below this a score-only ring would overwrite wavefronts still in use
-        pl->meta_cap = (uint32_t)(ms + 2);
-        // LDS ring for the live window of wavefronts: max(x, o+e)+1 slots of slot_w diagonals (M, I, D)
-        {
-            const uint32_t R = (uint32_t)Rw;
-            uint32_t w = 16;
-            while (w < 2 * (uint32_t)ms + 3 + (uint32_t)wide && w < 128) w *= 2;   // 128: keeps 16 workgroups resident per CU at l = 1000 (measured +9 % over 256)
-            if (kn.wfa_slotw >= 0) w = (uint32_t)std::max(16, kn.wfa_slotw) & ~15u;
-            while (w > 16 && (uint64_t)(R + 1) * nc * w * 2 > 24 * 1024) w /= 2;
-            const bool ring_ok = (uint64_t)(R + 1) * nc * w * 2 <= 24 * 1024 && !kn.wfa_no_ring;
-            pl->ring_slots = ring_ok ? R + 1 : 0;
-            pl->slot_w = ring_ok ? w : 0;
-        }
-        const size_t seq_bytes = 2 * ((size_t)p.read_size + 8);
-        pl->seq_lds = seq_bytes <= 40 * 1024;
-        const size_t ring_bytes = ((size_t)pl->ring_slots * nc * pl->slot_w * sizeof(int16_t) + 15) & ~(size_t)15;
-        pl->lds = aim::kMetaRing * sizeof(aim::WfMeta) + ring_bytes + (pl->seq_lds ? seq_bytes : 0);
-        // persistent single-wave workgroups: exactly what is resident (4 waves/SIMD by VGPRs, 160 KiB LDS per CU);
-        // a larger grid runs in uneven rounds
-        // (affine2p with BACKTRACE: 142-148 VGPRs, 3 waves per SIMD)
-        const uint32_t wg_per_cu = (uint32_t)std::min<size_t>(a2p && bt ? 12 : 16, aim::lds_workgroups_per_cu(pl->lds));
-        uint32_t grid = aim::resident_grid(kn, wg_per_cu);
-        const uint32_t need = ((n_pairs + 7u) / 8u) * 8u;
-        if (grid > need) grid = std::max(8u, need);
-        uint64_t per = (uint64_t)pl->meta_cap * sizeof(aim::WfMeta) + cap * sizeof(int16_t);
-        per = (per + 255) & ~255ull;
-        while (grid > 2 * kn.cus && grid > 16 && per * grid > budget) grid = ((grid / 2) + 7u) & ~7u;
-        if (per * grid > budget) {
-            const uint64_t meta_b = (uint64_t)pl->meta_cap * sizeof(aim::WfMeta);
-            if (bt) {
-                // With BACKTRACE the pool is a bump arena like the DPU's (allocate_new_score, wfa.c:143-183): a smaller one
-                // is legal and a pair that outgrows it reports AIM_PAIR_NOMEM (dpu_allocator_wram.c:19-23 "out of memory").
-                uint64_t avail = budget / grid;
-                if (avail < meta_b + 4096) return fail(AIM_ENOMEM, "scratch budget too small for max_score %d", p.max_score);
-                cap = (avail - meta_b - 256) / sizeof(int16_t);
-                if (cap < wide + 1) return fail(AIM_ENOMEM, "scratch budget too small for the ends-free score-0 wavefront (%llu diagonals)", (unsigned long long)(wide + 1));
-                per = (meta_b + cap * sizeof(int16_t) + 255) & ~255ull;
-            } else {
-                // Score-only: the pool is a ring and must keep its full live window (a shrunken ring silently overwrites
-                // wavefronts score-x / score-o-e / score-e still read). Fewer workgroups instead, down to one per XCD.
-                while (grid > 8 && per * grid > budget) grid -= 8;
-                if (per * grid > budget || cap < cap_min)
-                    return fail(AIM_ENOMEM, "scratch budget too small for the live window of max_score %d", p.max_score);
-            }
-        }
-        pl->grid = grid;
-        pl->pool_cap = (uint32_t)std::min<uint64_t>(cap, 0x7fffffffu);
-        pl->scratch_per_wg = per;
-        pl->scratch_total = (size_t)(per * grid);
         return AIM_OK;
     }
-    // NW / SWG medium reads: G lanes per pair (dp_group.hpp); empty sequences and plen > 2 tlen reach nw_lane / swg_lane (READ_SIZE <= 320) or
-    // dp_strip_kernel (to-do mode) through the to-do list. [the pairs' direction-bit slabs OR, afterwards, the fallback kernel's scratch | to-do region]
-    if (aim::dp_group_supported(p, kn)) {
-        // (a budget that holds neither this plan nor its fallback is not an error: the plans below -- dp_strip / dp_lane alone -- are tried next)
-        Plan fb;
-        memset(&fb, 0, sizeof fb);
-        bool ok = true;
-        if (p.read_size <= 320) {
-            aim::Knobs kq = kn;
-            kq.dpl_seq_lds = 0;   // the to-do pass: every lane loads its own pair's rows from global memory (the listed pairs are not consecutive)
-            kq.dpl_no_reg = 0;
-            ok = aim::dp_lane_plan(p, n_pairs, budget / 2, kq, &fb.grid, &fb.block, &fb.lds, &fb.scratch_per_wg, &fb.scratch_total, &fb.seq_lds);
-            fb.strip_k = 0;
-        } else
-            ok = aim::dp_strip_plan(p, n_pairs, budget / 2, kn, &fb.grid, &fb.block, &fb.lds, &fb.scratch_per_wg, &fb.scratch_total, &fb.strip_k, &fb.pool_cap);
-        if (ok) {
-            uint32_t grid = 0;
-            size_t lds = 0;
-            uint64_t per = 0;
-            aim::dp_group_plan(p, n_pairs, kn, &grid, &lds, &per);
-            while (grid > 8 && per * grid > budget / 2) grid -= 8;
-            ok = per * grid <= budget / 2;
-            if (ok) {
-                pl->kid = K_DP_GROUP;
-                pl->block = 64;
-                pl->grid = grid;
-                pl->lds = lds;
-                pl->scratch_per_wg = per;
-                pl->fb_scratch_per_wg = fb.scratch_per_wg;
-                pl->fb_grid = fb.grid;
-                pl->fb_block = fb.block;
-                pl->fb_lds = fb.lds;
-                pl->strip_k = fb.strip_k;
-                pl->pool_cap = fb.pool_cap;
-                pl->todo_bytes = aim::wfa_lane_todo_bytes(n_pairs);
-                pl->scratch_total = ((std::max<size_t>(fb.scratch_total, (size_t)(pl->scratch_per_wg * pl->grid)) + 255) & ~(size_t)255) + pl->todo_bytes;
-                return AIM_OK;
-            }
-        }
+    const bool gpk = (mode & MODE_PACKED_IN) && !kn.no_lane_pk;   // the group kernel reads packed rows itself
+    Plan grp;
+    memset(&grp, 0, sizeof grp);
+    const bool group_ok = !kn.force_wave && !kn.no_group && plan_wfa_group(p, n_pairs, kn, budget, gpk, &grp);
+    if (!lane_pk_ok && !group_ok) {
+        int rc = plan_wfa_wave(p, n_pairs, kn, budget, &m);
+        pl->scratch_total = stage_bytes(m);
+        return rc;
     }
+    // a fast kernel, then wfa_wave over the pairs it left (its to-do list)
+    if (!lane_pk_ok) *pl = grp;
+    int rc = plan_wfa_wave(p, std::min<uint32_t>(n_pairs, 1024u * 64u), kn, budget, &pl->fb);
+    if (rc) return rc;
+    pl->todo_bytes = aim::wfa_lane_todo_bytes(n_pairs);
+    if (lane_pk_ok) {
+        // ASCII rows of a shape only the packed lane kernel takes (READ_SIZE other than 80 / 112: l = 150 and friends; CIGAR at
+        // MAX_SCORE 6..10): pack on the device (batch_io.hpp), run the packed kernel, let the general kernel re-align the
+        // non-ACGT pairs. [to-do | flag bits | packed P | packed T | general kernel]
+        m.kid = K_WFA_LANE_PK;
+        aim::wfa_lane_packed_plan(p, n_pairs, kn, &m.grid, &m.block, &m.lds);
+        pl->pack_first = true;
+        const size_t flag_b = (((size_t)n_pairs + 31) / 32 * 4 + 255) & ~(size_t)255;
+        const size_t arr_b = (((size_t)n_pairs * aim::packed_row_dwords(p.read_size) * 4) + 64 + 255) & ~(size_t)255;
+        pl->flags_at = pl->todo_bytes;
+        pl->pack_p_at = pl->flags_at + flag_b;
+        pl->pack_t_at = pl->pack_p_at + arr_b;
+        pl->fb.scratch_at = pl->pack_t_at + arr_b;
+    } else {
+        // [to-do | history regions | general kernel]
+        pl->pk = gpk;
+        // (ends-free: ops rows, then cigar_rle_kernel -- the fused run output of wfa_group_tb_kernel is not used for it: one pair of
+        // a host run came back with a void first run, cause not found; affine2p likewise)
+        pl->emits_runs = bt && (mode & MODE_RUNS_OUT) && !is_endsfree(p) && !is_affine2p(p);
+        pl->hist_at = pl->todo_bytes;
+        pl->fb.scratch_at = pl->hist_at + pl->hist_bytes;
+    }
+    pl->scratch_total = pl->fb.scratch_at + stage_bytes(pl->fb);
+    return AIM_OK;
+}
+
+// dp_lane_kernel (nw_lane / swg_lane) as a stage; todo: as the to-do pass behind another kernel
+bool plan_dp_lane(const aim_params_t &p, uint32_t n_pairs, uint64_t budget, const aim::Knobs &kn, bool todo, Stage *st)
+{
+    size_t total = 0;
+    st->kid = K_DP_LANE;
+    return aim::dp_lane_plan(p, n_pairs, budget, kn, todo, &st->grid, &st->block, &st->lds, &st->scratch_per_wg, &total, &st->seq);
+}
+
+bool plan_dp_strip(const aim_params_t &p, uint32_t n_pairs, uint64_t budget, const aim::Knobs &kn, Stage *st)
+{
+    size_t total = 0;
+    st->kid = K_DP_STRIP;
+    return aim::dp_strip_plan(p, n_pairs, budget, kn, &st->grid, &st->block, &st->lds, &st->scratch_per_wg, &total, &st->strip_k);
+}
+
+// NW / SWG medium reads: G lanes per pair (dp_group.hpp); empty sequences and plen > 2 tlen reach nw_lane / swg_lane (READ_SIZE <= 320)
+// or dp_strip_kernel (to-do mode) through the to-do list. [the pairs' direction-bit slabs OR, afterwards, the fallback kernel's scratch |
+// to-do region]. False when the budget holds neither this plan nor its fallback: not an error, the plans without dp_group are tried
+// next.
+bool plan_dp_group(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, Plan *pl)
+{
+    Plan g;
+    memset(&g, 0, sizeof g);
+    if (!(p.read_size <= 320 ? plan_dp_lane(p, n_pairs, budget / 2, kn, true, &g.fb) : plan_dp_strip(p, n_pairs, budget / 2, kn, &g.fb)))
+        return false;
+    Stage &m = g.main;
+    aim::dp_group_plan(p, n_pairs, kn, &m.grid, &m.lds, &m.scratch_per_wg);
+    while (m.grid > 8 && m.scratch_per_wg * m.grid > budget / 2) m.grid -= 8;
+    if (m.scratch_per_wg * m.grid > budget / 2) return false;
+    m.kid = K_DP_GROUP;
+    m.block = 64;
+    g.todo_bytes = aim::wfa_lane_todo_bytes(n_pairs);
+    g.todo_at = (std::max(stage_bytes(g.fb), stage_bytes(m)) + 255) & ~(size_t)255;
+    g.scratch_total = g.todo_at + g.todo_bytes;
+    *pl = g;
+    return true;
+}
+
+// NW / SWG short reads with the rows in registers (dp_reg.hpp: slab_bt bytes of direction bits per wavefront with BACKTRACE, lds bytes
+// of LDS); the pairs it cannot take (tail cells, short outliers, SWG cells that wrap) reach nw_lane / swg_lane through a to-do list.
+// [table slabs of max(grid) wavefronts, shared by both kernels | to-do region]
+int plan_dp_reg(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, uint64_t slab_bt, size_t lds, Plan *pl)
+{
+    Stage &m = pl->main, &fb = pl->fb;
+    if (!plan_dp_lane(p, n_pairs, budget / 2, kn, true, &fb)) return fail(AIM_ENOMEM, "scratch budget too small for read_size %d", p.read_size);
+    const uint64_t slab = (p.flags & AIM_FLAG_BACKTRACE) ? slab_bt : 256;
+    uint32_t per_cu = kn.nw_reg_per_cu > 0 ? (uint32_t)kn.nw_reg_per_cu : 8u;   // two wavefronts per SIMD (NW: 178 - 255 VGPRs)
+    per_cu = (uint32_t)std::min<size_t>(per_cu, aim::lds_workgroups_per_cu(lds));
+    const uint32_t n_groups = (n_pairs + 63u) / 64u;
+    uint32_t g = aim::resident_grid(kn, per_cu);
+    const uint32_t need = ((n_groups + 7u) / 8u) * 8u;
+    if (g > need) g = need < 8u ? 8u : need;
+    const uint64_t per = std::max<uint64_t>((slab + 255) & ~255ull, fb.scratch_per_wg);
+    while (g > 8 && per * g > budget / 2) g -= 8;
+    if (per * std::max(g, fb.grid) > budget) return fail(AIM_ENOMEM, "scratch budget too small for read_size %d", p.read_size);
+    m.kid = K_DP_REG;
+    m.grid = g;
+    m.block = 64;
+    m.lds = lds;
+    m.scratch_per_wg = fb.scratch_per_wg = per;
+    pl->todo_bytes = aim::wfa_lane_todo_bytes(n_pairs);
+    pl->todo_at = (size_t)(per * std::max(g, fb.grid));
+    pl->scratch_total = pl->todo_at + pl->todo_bytes;
+    return AIM_OK;
+}
+
+// NW / SWG
+int plan_dp(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, Plan *pl)
+{
+    if (aim::dp_group_supported(p, kn) && plan_dp_group(p, n_pairs, kn, budget, pl)) return AIM_OK;
     // NW / SWG long reads: one pair per workgroup of 1-12 wavefronts, row-scan, canonical table in per-workgroup HBM scratch
     // (SWG with int8 cells -- the launchers' MAX_SCORE < 127 -- wraps by design and is nobody's but the literal kernels': swg_lane_kernel, one pair per LANE with its M and I rows
     //  in LDS, takes it as far as 64 lanes' rows fit a CU's LDS (READ_SIZE <= 1 199; round 6: until then dp_wave_kernel's literal path, one lane per WORKGROUP, from READ_SIZE 321 on:
     //  6 - 13 GCUPS, profiles/r06/cliff_scan.txt))
-    bool cell8_lane = p.algo == AIM_ALGO_SWG && aim::swg_cell_bytes(p) == 1 && !kn.force_dpwave && !kn.dpw_legacy && kn.dpw_nw < 0 && kn.strip_k <= 0 &&
-                      (size_t)2 * (p.read_size + 1) * 64 <= 150 * 1024;
+    const bool cell8 = p.algo == AIM_ALGO_SWG && aim::swg_cell_bytes(p) == 1;
+    bool cell8_lane = cell8 && !kn.force_dpwave && !kn.dpw_legacy && kn.dpw_nw < 0 && kn.strip_k <= 0 && (size_t)2 * (p.read_size + 1) * 64 <= 150 * 1024;
     if (cell8_lane && p.read_size > 320) {   // (with CIGAR a lane's table is READ_SIZE^2 x 4 bytes x 64 lanes per workgroup: a budget that does not hold eight of them keeps the one-table-per-workgroup path)
-        Plan t;
-        memset(&t, 0, sizeof t);
-        cell8_lane = aim::dp_lane_plan(p, n_pairs, budget, kn, &t.grid, &t.block, &t.lds, &t.scratch_per_wg, &t.scratch_total, &t.seq_lds);
+        Stage t;
+        cell8_lane = plan_dp_lane(p, n_pairs, budget, kn, false, &t);
     }
+    Stage &m = pl->main;
     if ((p.read_size > 320 && !cell8_lane) || kn.force_dpwave) {
-        const bool cell8 = p.algo == AIM_ALGO_SWG && aim::swg_cell_bytes(p) == 1;
-        if (!kn.dpw_legacy && kn.dpw_nw < 0 && aim::dp_strip_supported(p, cell8, kn)) {
-            // column-strip pipeline (dp_strip.hpp): previous row in registers, packed int16 arithmetic, mailboxes instead of barriers
-            pl->kid = K_DP_STRIP;
-            return aim::dp_strip_plan(p, n_pairs, budget, kn, &pl->grid, &pl->block, &pl->lds, &pl->scratch_per_wg, &pl->scratch_total, &pl->strip_k, &pl->pool_cap)
-                       ? AIM_OK
-                       : fail(AIM_ENOMEM, "scratch budget (AIM_SCRATCH_GB) or LDS too small for read_size %d", p.read_size);
+        bool ok;
+        size_t total = 0;
+        if (!kn.dpw_legacy && kn.dpw_nw < 0 && aim::dp_strip_supported(p, cell8, kn))   // column-strip pipeline (dp_strip.hpp): previous row in registers, packed int16 arithmetic, mailboxes instead of barriers
+            ok = plan_dp_strip(p, n_pairs, budget, kn, &m);
+        else {
+            m.kid = K_DP_WAVE;
+            ok = aim::dp_wave_plan(p, n_pairs, budget, kn, cell8, &m.grid, &m.block, &m.lds, &m.scratch_per_wg, &total);
         }
-        pl->kid = K_DP_WAVE;
-        return aim::dp_wave_plan(p, n_pairs, budget, kn, cell8, &pl->grid, &pl->block, &pl->lds, &pl->scratch_per_wg, &pl->scratch_total)
-                   ? AIM_OK
-                   : fail(AIM_ENOMEM, "scratch budget (AIM_SCRATCH_GB) or LDS too small for read_size %d", p.read_size);
+        pl->scratch_total = stage_bytes(m);
+        return ok ? AIM_OK : fail(AIM_ENOMEM, "scratch budget (AIM_SCRATCH_GB) or LDS too small for read_size %d", p.read_size);
     }
-    // NW short reads: the row in registers (dp_reg.hpp); pairs it cannot take (tail cells: plen >= tlen + 2, short outliers) reach
-    // nw_lane_kernel through a to-do list. [table slabs of max(grid) wavefronts | to-do region]
+    const int rs = p.read_size;
     if (p.algo == AIM_ALGO_NW && !kn.no_nw_reg && !kn.force_dpwave && aim::nw_reg_supported(p)) {
-        Plan fb;
-        memset(&fb, 0, sizeof fb);
-        aim::Knobs kq = kn;
-        kq.dpl_seq_lds = p.read_size <= 124 ? 2 : 0;   // the to-do pass: every lane loads its own pair's pattern row into registers (the listed pairs are not consecutive: no staged image); READ_SIZE 128: from global memory -- never an LDS image (the plan's LDS and the launch agree)
-        kq.dpl_no_reg = 0;
-        if (!aim::dp_lane_plan(p, n_pairs, budget / 2, kq, &fb.grid, &fb.block, &fb.lds, &fb.scratch_per_wg, &fb.scratch_total, &fb.seq_lds))
-            return fail(AIM_ENOMEM, "scratch budget too small for read_size %d", p.read_size);
-        const int npk = aim::nw_reg_npk(p.read_size, bt);
-        const uint64_t slab = bt ? (uint64_t)aim::nw_reg_slab_bytes(npk, p.read_size) : 256;
-        uint32_t per_cu = npk <= 42 ? (bt ? 8u : 8u) : 8u;   // (178 - 255 VGPRs: two wavefronts per SIMD)
-        if (kn.nw_reg_per_cu > 0) per_cu = (uint32_t)kn.nw_reg_per_cu;
-        pl->lds = aim::nw_reg_lds_bytes(p);
-        per_cu = (uint32_t)std::min<size_t>(per_cu, aim::lds_workgroups_per_cu(pl->lds));
-        const uint32_t n_groups = (n_pairs + 63u) / 64u;
-        uint32_t g = aim::resident_grid(kn, per_cu);
-        const uint32_t need = ((n_groups + 7u) / 8u) * 8u;
-        if (g > need) g = need < 8u ? 8u : need;
-        const uint64_t per = std::max<uint64_t>((slab + 255) & ~255ull, fb.scratch_per_wg);
-        while (g > 8 && per * g > budget / 2) g -= 8;
-        if (per * std::max(g, fb.grid) > budget) return fail(AIM_ENOMEM, "scratch budget too small for read_size %d", p.read_size);
-        pl->kid = K_DP_REG;
-        pl->grid = g;
-        pl->block = 64;
-        pl->scratch_per_wg = per;
-        pl->fb_grid = fb.grid;
-        pl->fb_lds = fb.lds;
-        pl->todo_bytes = aim::wfa_lane_todo_bytes(n_pairs);
-        pl->scratch_total = (size_t)(per * std::max(g, fb.grid)) + pl->todo_bytes;
-        return AIM_OK;
+        const int npk = aim::nw_reg_npk(rs, (p.flags & AIM_FLAG_BACKTRACE) != 0);
+        return plan_dp_reg(p, n_pairs, kn, budget, aim::nw_reg_slab_bytes(npk, rs), aim::nw_reg_lds_bytes(p), pl);
     }
-    // SWG short reads: the M and I rows in registers (dp_reg.hpp, round 5); tail pairs, outliers and pairs whose cells wrap reach swg_lane_kernel
-    // through the same to-do list. [table slabs of max(grid) wavefronts | to-do region]
     if (p.algo == AIM_ALGO_SWG && !kn.no_swg_reg && !kn.force_dpwave && aim::swg_reg_supported(p)) {
-        Plan fb;
-        memset(&fb, 0, sizeof fb);
-        aim::Knobs kq = kn;
-        kq.dpl_seq_lds = p.read_size <= 124 ? 2 : 0;
-        kq.dpl_no_reg = 0;
-        if (!aim::dp_lane_plan(p, n_pairs, budget / 2, kq, &fb.grid, &fb.block, &fb.lds, &fb.scratch_per_wg, &fb.scratch_total, &fb.seq_lds))
-            return fail(AIM_ENOMEM, "scratch budget too small for read_size %d", p.read_size);
-        const int npk = aim::swg_reg_npk(p.read_size);
-        const uint64_t slab = bt ? (uint64_t)aim::swg_reg_slab_bytes(npk, p.read_size) : 256;
-        uint32_t per_cu = 8u;   // two wavefronts per SIMD
-        if (kn.nw_reg_per_cu > 0) per_cu = (uint32_t)kn.nw_reg_per_cu;
-        pl->lds = aim::swg_reg_lds_bytes(p, npk);
-        per_cu = (uint32_t)std::min<size_t>(per_cu, aim::lds_workgroups_per_cu(pl->lds));
-        const uint32_t n_groups = (n_pairs + 63u) / 64u;
-        uint32_t g = aim::resident_grid(kn, per_cu);
-        const uint32_t need = ((n_groups + 7u) / 8u) * 8u;
-        if (g > need) g = need < 8u ? 8u : need;
-        const uint64_t per = std::max<uint64_t>((slab + 255) & ~255ull, fb.scratch_per_wg);
-        while (g > 8 && per * g > budget / 2) g -= 8;
-        if (per * std::max(g, fb.grid) > budget) return fail(AIM_ENOMEM, "scratch budget too small for read_size %d", p.read_size);
-        pl->kid = K_DP_REG;
-        pl->grid = g;
-        pl->block = 64;
-        pl->scratch_per_wg = per;
-        pl->fb_grid = fb.grid;
-        pl->fb_lds = fb.lds;
-        pl->todo_bytes = aim::wfa_lane_todo_bytes(n_pairs);
-        pl->scratch_total = (size_t)(per * std::max(g, fb.grid)) + pl->todo_bytes;
-        return AIM_OK;
+        const int npk = aim::swg_reg_npk(rs);
+        return plan_dp_reg(p, n_pairs, kn, budget, aim::swg_reg_slab_bytes(npk, rs), aim::swg_reg_lds_bytes(p, npk), pl);
     }
     // NW / SWG short reads: one pair per lane, flat DP table in per-wave HBM scratch
-    pl->kid = K_DP_LANE;
-    return aim::dp_lane_plan(p, n_pairs, budget, kn, &pl->grid, &pl->block, &pl->lds, &pl->scratch_per_wg, &pl->scratch_total,
-                             &pl->seq_lds)
-               ? AIM_OK
-               : fail(AIM_ENOMEM, "scratch budget too small for read_size %d", p.read_size);
+    if (!plan_dp_lane(p, n_pairs, budget, kn, false, &m)) return fail(AIM_ENOMEM, "scratch budget too small for read_size %d", p.read_size);
+    pl->scratch_total = stage_bytes(m);
+    return AIM_OK;
 }
 
 const char *kernel_name(const Plan &pl, const aim_params_t &p)
 {
-    switch (pl.kid) {
+    switch (pl.main.kid) {
     case K_WFA_WAVE: return "wfa_wave_kernel";
     case K_WFA_LANE: return "wfa_lane_kernel";
     case K_WFA_LANE_PK: return "wfa_lane_packed_kernel";
@@ -634,14 +563,15 @@ const char *kernel_name(const Plan &pl, const aim_params_t &p)
 int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint64_t budget, char *out, size_t cap)
 {
     char extra[160] = "";
-    if (pl.kid == K_WFA_GROUP) snprintf(extra, sizeof extra, " G=%d hist=%zu chunk=%u fb_grid=%u packed_in=%d runs_out=%d", pl.group_g, pl.hist_bytes, pl.chunk_pairs, pl.fb_grid, (int)pl.pk, (int)pl.emits_runs);
-    else if (pl.kid == K_WFA_LANE_PK) snprintf(extra, sizeof extra, " pack_first=%d fb_grid=%u", (int)pl.pack_first, pl.fb_grid);
-    else if (pl.kid == K_DP_WAVE) snprintf(extra, sizeof extra, " wavefronts_per_pair=%u", pl.block / 64);
-    else if (pl.kid == K_DP_STRIP) snprintf(extra, sizeof extra, " wavefronts_per_pair=%u cells_per_lane=%d", pl.block / 64, pl.strip_k);
-    else if (pl.kid == K_WFA_WAVE) snprintf(extra, sizeof extra, " pool_cap=%u ring=%ux%u seq_lds=%d", pl.pool_cap, pl.ring_slots, pl.slot_w, (int)pl.seq_lds);
-    else if (pl.kid == K_DP_LANE) snprintf(extra, sizeof extra, " seq_lds=%d", (int)pl.seq_lds);
-    else if (pl.kid == K_DP_REG) snprintf(extra, sizeof extra, " fb_grid=%u fb_lds=%zu", pl.fb_grid, pl.fb_lds);
-    else if (pl.kid == K_DP_GROUP) snprintf(extra, sizeof extra, " lanes_per_pair=%d fb_grid=%u fb_block=%u fb_lds=%zu", aim::dp_group_lanes(p.read_size, (p.flags & AIM_FLAG_BACKTRACE) != 0, p.algo == AIM_ALGO_SWG), pl.fb_grid, pl.fb_block, pl.fb_lds);
+    const Stage &m = pl.main, &fb = pl.fb;
+    if (m.kid == K_WFA_GROUP) snprintf(extra, sizeof extra, " G=%d hist=%zu chunk=%u fb_grid=%u packed_in=%d runs_out=%d", pl.group_g, pl.hist_bytes, pl.chunk_pairs, fb.grid, (int)pl.pk, (int)pl.emits_runs);
+    else if (m.kid == K_WFA_LANE_PK) snprintf(extra, sizeof extra, " pack_first=%d fb_grid=%u", (int)pl.pack_first, fb.grid);
+    else if (m.kid == K_DP_WAVE) snprintf(extra, sizeof extra, " wavefronts_per_pair=%u", m.block / 64);
+    else if (m.kid == K_DP_STRIP) snprintf(extra, sizeof extra, " wavefronts_per_pair=%u cells_per_lane=%d", m.block / 64, m.strip_k);
+    else if (m.kid == K_WFA_WAVE) snprintf(extra, sizeof extra, " pool_cap=%u ring=%ux%u seq_lds=%d", m.pool_cap, m.ring_slots, m.slot_w, (int)m.seq_lds);
+    else if (m.kid == K_DP_LANE) snprintf(extra, sizeof extra, " seq_lds=%d", (int)(m.seq == 1));
+    else if (m.kid == K_DP_REG) snprintf(extra, sizeof extra, " fb_grid=%u fb_lds=%zu", fb.grid, fb.lds);
+    else if (m.kid == K_DP_GROUP) snprintf(extra, sizeof extra, " lanes_per_pair=%d fb_grid=%u fb_block=%u fb_lds=%zu", aim::dp_group_lanes(p.read_size, (p.flags & AIM_FLAG_BACKTRACE) != 0, p.algo == AIM_ALGO_SWG), fb.grid, fb.block, fb.lds);
     char efs[80] = "";
     if (is_endsfree(p)) {
         const EndsFree e = ends_free(p);
@@ -650,8 +580,8 @@ int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint6
         const Affine2p g = affine2p(p);
         snprintf(efs, sizeof efs, " affine2p=%d,%d", g.o2, g.e2);
     }
-    return snprintf(out, cap, "%s n=%u grid=%u block=%u lds=%zu scratch=%zu budget=%llu%s%s", kernel_name(pl, p), n_pairs, pl.grid,
-                    pl.block, pl.lds, pl.scratch_total, (unsigned long long)budget, extra, efs);
+    return snprintf(out, cap, "%s n=%u grid=%u block=%u lds=%zu scratch=%zu budget=%llu%s%s", kernel_name(pl, p), n_pairs, pl.main.grid,
+                    pl.main.block, pl.main.lds, pl.scratch_total, (unsigned long long)budget, extra, efs);
 }
 
 int make_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, Plan *pl, uint32_t mode = 0u)
@@ -659,7 +589,10 @@ int make_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uin
     int rc = validate_params(p);
     if (rc) return rc;
     memset(pl, 0, sizeof *pl);
-    rc = make_plan_inner(p, n_pairs, kn.cus ? kn : with_chip(kn), budget, mode, pl);
+    const aim::Knobs kc = kn.cus ? kn : with_chip(kn);
+    rc = p.algo == AIM_ALGO_GENASM ? plan_genasm(p, n_pairs, kc, pl)
+         : p.algo == AIM_ALGO_WFA  ? plan_wfa(p, n_pairs, kc, budget, mode, pl)
+                                   : plan_dp(p, n_pairs, kc, budget, pl);
     if (rc == AIM_OK && kn.plan_debug) {
         char line[384];
         describe_plan(*pl, p, n_pairs, budget, line, sizeof line);
@@ -668,9 +601,28 @@ int make_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uin
     return rc;
 }
 
-void launch_wfa_wave(bool bt, bool red, const Plan &pl, const aim::KArgs &ka, hipStream_t s)
+// KArgs of one stage: where its scratch starts, its slab and what its plan chose for wfa_wave
+aim::KArgs stage_args(aim::KArgs ka, const Stage &st, void *d_scratch)
 {
-    aim::wfa_wave_launch(bt, red, pl.seq_lds, pl.grid, pl.lds, ka, s);
+    ka.scratch = (char *)d_scratch + st.scratch_at;
+    ka.scratch_per_wave = st.scratch_per_wg;
+    ka.pool_cap = st.pool_cap;
+    ka.meta_cap = st.meta_cap;
+    ka.ring_slots = st.ring_slots;
+    ka.slot_w = st.slot_w;
+    ka.dbg_lds_bytes = (uint32_t)st.lds;
+    return ka;
+}
+
+// The kernels that run alone or as the to-do pass behind another one (ka.todo set)
+void launch_stage(const aim_params_t &p, const Stage &st, const aim::KArgs &ka, hipStream_t s)
+{
+    switch (st.kid) {
+    case K_WFA_WAVE: aim::wfa_wave_launch(p.flags & AIM_FLAG_BACKTRACE, p.flags & AIM_FLAG_REDUCE, st.seq_lds, st.grid, st.lds, ka, s); break;
+    case K_DP_LANE: aim::dp_lane_launch(p, st.seq, st.grid, st.lds, ka, s); break;
+    case K_DP_STRIP: aim::dp_strip_launch(p, st.strip_k, st.grid, st.block, st.lds, ka, s); break;
+    default: break;
+    }
 }
 
 // A second stream per device for work that only has to be ordered against ONE kernel of a launch, not against the whole stream:
@@ -728,93 +680,80 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
 {
     if (n_pairs == 0) return AIM_OK;
     const bool bt = p.flags & AIM_FLAG_BACKTRACE;
-    const bool red = p.flags & AIM_FLAG_REDUCE;
     if (pl.pk && !pl.pack_first && (!fio || !fio->packedP || !fio->packedT)) return fail(AIM_EINVAL, "plan reads packed rows but none were given");
     if (pl.emits_runs && (!fio || !fio->cig || !fio->runs || !fio->cursor)) return fail(AIM_EINVAL, "plan emits the compact CIGAR but no buffers were given");
-    const bool reads_ascii = !(pl.kid == K_WFA_LANE_PK && !pl.pack_first);   // (wfa_group reads them for its to-do pairs even on packed batches)
-    const bool writes_res = !(pl.kid == K_WFA_LANE_PK && pl.emits_runs);
+    const bool reads_ascii = !(pl.main.kid == K_WFA_LANE_PK && !pl.pack_first);   // (wfa_group reads them for its to-do pairs even on packed batches)
+    const bool writes_res = !(pl.main.kid == K_WFA_LANE_PK && pl.emits_runs);
     if (!d_req || (reads_ascii && (!d_pat || !d_txt)) || (writes_res && !d_res)) return fail(AIM_EINVAL, "null device buffer");
     if (bt && writes_res && !d_ops) return fail(AIM_EINVAL, "AIM_FLAG_BACKTRACE needs an ops buffer");
     if (scratch_bytes < pl.scratch_total || (!d_scratch && pl.scratch_total))
         return fail(AIM_EINVAL, "scratch too small: need %zu bytes, got %zu", pl.scratch_total, scratch_bytes);
-    aim::KArgs ka;
-    ka.p = p;
-    ka.n_pairs = n_pairs;
-    ka.req = static_cast<const aim_request_t *>(d_req);
-    ka.patterns = d_pat;
-    ka.texts = d_txt;
-    ka.res = static_cast<aim_result_t *>(d_res);
-    ka.ops = d_ops;
-    ka.scratch = (char *)d_scratch;
-    ka.scratch_per_wave = pl.scratch_per_wg;
-    ka.pool_cap = pl.pool_cap;
-    ka.meta_cap = pl.meta_cap;
-    ka.ring_slots = pl.ring_slots;
-    ka.slot_w = pl.slot_w;
-    ka.todo = nullptr;
-    ka.dbg_poison_lds = kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u;
-    ka.dbg_flags = (uint32_t)kn.dbg_flags;
-    ka.dbg_lds_bytes = (uint32_t)pl.lds;
-    ka.packedP = fio ? fio->packedP : nullptr;
-    ka.packedT = fio ? fio->packedT : nullptr;
-    ka.cig = fio ? fio->cig : nullptr;
-    ka.runs = fio ? fio->runs : nullptr;
-    ka.runs_cap = fio ? fio->runs_cap : 0u;
-    ka.cursor = fio ? fio->cursor : nullptr;
-    ka.pair_base = 0;
+    aim::KArgs ka0;
+    ka0.p = p;
+    ka0.n_pairs = n_pairs;
+    ka0.req = static_cast<const aim_request_t *>(d_req);
+    ka0.patterns = d_pat;
+    ka0.texts = d_txt;
+    ka0.res = static_cast<aim_result_t *>(d_res);
+    ka0.ops = d_ops;
+    ka0.todo = nullptr;
+    ka0.dbg_poison_lds = kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u;
+    ka0.dbg_flags = (uint32_t)kn.dbg_flags;
+    ka0.packedP = fio ? fio->packedP : nullptr;
+    ka0.packedT = fio ? fio->packedT : nullptr;
+    ka0.cig = fio ? fio->cig : nullptr;
+    ka0.runs = fio ? fio->runs : nullptr;
+    ka0.runs_cap = fio ? fio->runs_cap : 0u;
+    ka0.cursor = fio ? fio->cursor : nullptr;
+    ka0.pair_base = 0;
     {
         const EndsFree e = ends_free(p);
-        ka.ef_pb = e.pb; ka.ef_pe = e.pe; ka.ef_tb = e.tb; ka.ef_te = e.te;
+        ka0.ef_pb = e.pb; ka0.ef_pe = e.pe; ka0.ef_tb = e.tb; ka0.ef_te = e.te;
         const Affine2p g = affine2p(p);
-        ka.a2p_o2 = g.o2; ka.a2p_e2 = g.e2;
+        ka0.a2p_o2 = g.o2; ka0.a2p_e2 = g.e2;
     }
+    const Stage &m = pl.main;
+    aim::KArgs ka = stage_args(ka0, m, d_scratch);
+    // the fallback over the to-do list the main kernel filled: its own stage, the batch's ASCII rows
+    aim::KArgs kb = stage_args(ka0, pl.fb, d_scratch);
+    kb.todo = reinterpret_cast<const uint32_t *>((char *)d_scratch + pl.todo_at);
+    kb.packedP = kb.packedT = nullptr;
+    kb.cig = nullptr;
     if (kn.poison_ops >= 0 && d_ops && bt)   // debugging aid: results must not depend on what the ops rows held before (only ops[begin_offset, end_offset) is written)
         HIP_TRY(hipMemsetAsync(d_ops, kn.poison_ops & 0xff, (size_t)n_pairs * 2 * p.read_size, stream));
-    switch (pl.kid) {
+    if (pl.todo_bytes) HIP_TRY(hipMemsetAsync((char *)d_scratch + pl.todo_at, 0, 64, stream));   // the to-do count, zeroed per launch
+    switch (m.kid) {
     case K_WFA_WAVE:
-        launch_wfa_wave(bt, red, pl, ka, stream);
+    case K_DP_LANE:
+    case K_DP_STRIP:
+        launch_stage(p, m, ka, stream);
         break;
     case K_WFA_LANE:
-        ka.scratch_per_wave = 256;
-        aim::wfa_lane_launch(p, pl.grid, pl.block, pl.lds, ka, stream);
+        aim::wfa_lane_launch(p, m.grid, m.block, m.lds, ka, stream);
         break;
     case K_WFA_LANE_PK:
         if (pl.pack_first) {
-            // [to-do | flag bits | packed P | packed T | general kernel scratch]
-            const size_t npw = aim::packed_row_dwords(p.read_size);
-            const size_t flag_b = (((size_t)n_pairs + 31) / 32 * 4 + 255) & ~(size_t)255, arr_b = (((size_t)n_pairs * npw * 4) + 64 + 255) & ~(size_t)255;
+            // pack_rows_kernel lists the non-ACGT pairs; the packed kernel aligns the batch, wfa_wave re-aligns the listed pairs
             char *base = (char *)d_scratch;
-            uint32_t *flags_d = reinterpret_cast<uint32_t *>(base + pl.todo_bytes);
-            uint32_t *pkP = reinterpret_cast<uint32_t *>(base + pl.todo_bytes + flag_b), *pkT = reinterpret_cast<uint32_t *>(base + pl.todo_bytes + flag_b + arr_b);
-            HIP_TRY(hipMemsetAsync(base, 0, 64, stream));
-            HIP_TRY(hipMemsetAsync(flags_d, 0, flag_b, stream));
-            const uint64_t threads = (uint64_t)n_pairs * npw;
+            uint32_t *flags_d = reinterpret_cast<uint32_t *>(base + pl.flags_at);
+            uint32_t *pkP = reinterpret_cast<uint32_t *>(base + pl.pack_p_at), *pkT = reinterpret_cast<uint32_t *>(base + pl.pack_t_at);
+            HIP_TRY(hipMemsetAsync(flags_d, 0, pl.pack_p_at - pl.flags_at, stream));
+            const uint64_t threads = (uint64_t)n_pairs * aim::packed_row_dwords(p.read_size);
             hipLaunchKernelGGL(aim::pack_rows_kernel, dim3((unsigned)((threads + 255) / 256), 2), dim3(256), 0, stream, ka, pkP, pkT, flags_d,
-                               reinterpret_cast<uint32_t *>(base));
+                               reinterpret_cast<uint32_t *>(base + pl.todo_at));
             HIP_TRY(hipGetLastError());
             aim::KArgs kp = ka;
             kp.packedP = pkP;
             kp.packedT = pkT;
-            aim::wfa_lane_packed_launch(p, pl.grid, pl.lds, kp, 0u, stream);
+            aim::wfa_lane_packed_launch(p, m.grid, m.lds, kp, 0u, stream);
             HIP_TRY(hipGetLastError());
-            aim::KArgs kb = ka;
-            kb.todo = reinterpret_cast<const uint32_t *>(base);
-            kb.scratch = base + pl.todo_bytes + pl.pack_bytes;
-            kb.scratch_per_wave = pl.scratch_per_wg;
-            Plan fb = pl;
-            fb.grid = pl.fb_grid;
-            fb.lds = pl.fb_lds;
-            kb.dbg_lds_bytes = (uint32_t)fb.lds;
-            launch_wfa_wave(bt, red, fb, kb, stream);
+            launch_stage(p, pl.fb, kb, stream);
             break;
         }
-        aim::wfa_lane_packed_launch(p, pl.grid, pl.lds, ka, fio->run_slot, stream);
+        aim::wfa_lane_packed_launch(p, m.grid, m.lds, ka, fio->run_slot, stream);
         break;
     case K_WFA_GROUP: {
-        // [to-do region | history regions | general kernel scratch]: count zeroed per launch; fast kernel (+ traceback kernel
-        // with BACKTRACE) chunk by chunk; then the general kernel drains the to-do list
-        HIP_TRY(hipMemsetAsync(d_scratch, 0, 64, stream));
-        ka.scratch_per_wave = pl.todo_bytes;   // (diagnostic builds park their stamps behind the to-do region)
+        // fast kernel (+ traceback kernel with BACKTRACE) chunk by chunk; then the general kernel drains the to-do list
         const uint32_t chunk = (bt && pl.chunk_pairs) ? pl.chunk_pairs : n_pairs;
         const size_t rqb = (p.flags & AIM_FLAG_REQ8) ? sizeof(aim_request8_t) : sizeof(aim_request_t);
         const size_t rsb = (p.flags & AIM_FLAG_RES8) ? sizeof(aim_result8_t) : sizeof(aim_result_t);
@@ -840,7 +779,7 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
             const int b = (int)(ci & 1u);
             kc.n_pairs = std::min(chunk, n_pairs - first);
             kc.pair_base = first;
-            kc.scratch_per_wave = pl.todo_bytes + (overlap ? (size_t)b * buf_bytes : 0);   // where this chunk's history regions start
+            kc.scratch_per_wave = pl.hist_at + (overlap ? (size_t)b * buf_bytes : 0);   // where this chunk's history regions start (the to-do region is in front)
             kc.req = reinterpret_cast<const aim_request_t *>(static_cast<const char *>(d_req) + (size_t)first * rqb);
             if (d_pat) { kc.patterns = d_pat + (size_t)first * p.read_size; kc.texts = d_txt + (size_t)first * p.read_size; }
             if (d_res) kc.res = reinterpret_cast<aim_result_t *>(static_cast<char *>(d_res) + (size_t)first * rsb);
@@ -848,14 +787,14 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
             if (ka.packedP) { kc.packedP = ka.packedP + (size_t)first * npw; kc.packedT = ka.packedT + (size_t)first * npw; }
             if (ka.cig) kc.cig = ka.cig + first;
             // a chunk smaller than the plan's grid needs fewer workgroups (the grid stays a multiple of 8)
-            uint32_t grid = pl.grid;
+            uint32_t grid = m.grid;
             {
                 const uint32_t ppw = 64u / (uint32_t)pl.group_g;
                 const uint32_t need = ((((kc.n_pairs + ppw - 1) / ppw) + 7u) / 8u) * 8u;
                 if (grid > need) grid = need < 8u ? 8u : need;
             }
             if (overlap && ci >= 2) HIP_TRY(hipStreamWaitEvent(stream, aux->walked[b], 0));   // buffer b: its previous chunk has been walked
-            aim::wfa_group_launch(p, pl.group_g, pl.gcfg, grid, pl.lds, kc, stream);
+            aim::wfa_group_launch(p, pl.group_g, pl.gcfg, grid, m.lds, kc, stream);
             HIP_TRY(hipGetLastError());
             if (overlap) {
                 HIP_TRY(hipEventRecord(aux->computed[b], stream));
@@ -872,75 +811,32 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
             HIP_TRY(hipStreamWaitEvent(stream, aux->walked[0], 0));
             HIP_TRY(hipStreamWaitEvent(stream, aux->walked[1], 0));
         }
-        aim::KArgs kb = ka;
-        kb.packedP = kb.packedT = nullptr;
-        kb.cig = nullptr;
-        kb.todo = reinterpret_cast<const uint32_t *>(d_scratch);
-        kb.scratch = (char *)d_scratch + pl.todo_bytes + pl.hist_bytes;
-        kb.scratch_per_wave = pl.scratch_per_wg;
         if (pl.pk) {   // the general kernel reads ASCII rows: expand the to-do pairs' packed rows in place first
             hipLaunchKernelGGL(aim::unpack_todo_rows_kernel, dim3(256), dim3(256), 0, stream, ka, kb.todo, ka.packedP, ka.packedT, const_cast<char *>(d_pat), const_cast<char *>(d_txt));
             HIP_TRY(hipGetLastError());
         }
-        Plan fb = pl;
-        fb.grid = pl.fb_grid;
-        fb.lds = pl.fb_lds;
-        kb.dbg_lds_bytes = (uint32_t)fb.lds;
-        launch_wfa_wave(bt, red, fb, kb, stream);
+        launch_stage(p, pl.fb, kb, stream);
         if (pl.emits_runs) {   // the general kernel wrote result_t + ops rows for the to-do pairs: their compact CIGAR
             hipLaunchKernelGGL(aim::cigar_rle_todo_kernel, dim3(256), dim3(64), 0, stream, kb, kb.todo, ka.cig, ka.runs, ka.runs_cap, ka.cursor);
             HIP_TRY(hipGetLastError());
         }
         break;
     }
-    case K_DP_LANE:
-        aim::dp_lane_launch(p, kn, pl.grid, pl.lds, pl.seq_lds, ka, stream);
-        break;
-    case K_DP_REG: {
-        // [table slabs | to-do region]: count zeroed per launch; the register kernel; then nw_lane_kernel over the pairs it left
-        uint32_t *todo_d = reinterpret_cast<uint32_t *>((char *)d_scratch + (pl.scratch_total - pl.todo_bytes));
-        HIP_TRY(hipMemsetAsync(todo_d, 0, 64, stream));
-        ka.todo = todo_d;
-        if (p.algo == AIM_ALGO_SWG) aim::swg_reg_launch(p, pl.grid, pl.lds, ka, stream);
-        else aim::nw_reg_launch(p, pl.grid, pl.lds, ka, stream);
+    case K_DP_REG:
+    case K_DP_GROUP:
+        // the register / group kernel lists the pairs it leaves; then the literal-capable kernel over them
+        ka.todo = kb.todo;
+        if (m.kid == K_DP_GROUP) aim::dp_group_launch(p, m.grid, m.lds, ka, stream);
+        else if (p.algo == AIM_ALGO_SWG) aim::swg_reg_launch(p, m.grid, m.lds, ka, stream);
+        else aim::nw_reg_launch(p, m.grid, m.lds, ka, stream);
         HIP_TRY(hipGetLastError());
-        aim::Knobs kq = kn;
-        kq.dpl_seq_lds = p.read_size <= 124 ? 2 : 0;
-        kq.dpl_no_reg = 0;
-        ka.dbg_lds_bytes = (uint32_t)pl.fb_lds;
-        aim::dp_lane_launch(p, kq, pl.fb_grid, pl.fb_lds, false, ka, stream);
+        launch_stage(p, pl.fb, kb, stream);
         break;
-    }
-    case K_DP_GROUP: {
-        // [fallback kernel's scratch | to-do region]: count zeroed per launch; the group kernel; then the literal-capable kernel over the pairs it left
-        uint32_t *todo_d = reinterpret_cast<uint32_t *>((char *)d_scratch + (pl.scratch_total - pl.todo_bytes));
-        HIP_TRY(hipMemsetAsync(todo_d, 0, 64, stream));
-        ka.todo = todo_d;
-        aim::dp_group_launch(p, pl.grid, pl.lds, ka, stream);
-        HIP_TRY(hipGetLastError());
-        ka.dbg_lds_bytes = (uint32_t)pl.fb_lds;
-        ka.scratch_per_wave = pl.fb_scratch_per_wg;
-        if (pl.strip_k == 0) {
-            aim::Knobs kq = kn;
-            kq.dpl_seq_lds = 0;
-            kq.dpl_no_reg = 0;
-            aim::dp_lane_launch(p, kq, pl.fb_grid, pl.fb_lds, false, ka, stream);
-        } else {
-            ka.pool_cap = pl.pool_cap;
-            aim::dp_strip_launch(p, pl.strip_k, pl.fb_grid, pl.fb_block, pl.fb_lds, ka, stream);
-        }
-        break;
-    }
     case K_DP_WAVE:
-        aim::dp_wave_launch(p, p.algo == AIM_ALGO_SWG && aim::swg_cell_bytes(p) == 1, pl.grid, pl.block, pl.lds, ka, stream);
-        break;
-    case K_DP_STRIP:
-        // [slabs | lock words | pool tables of the literal path]: the locks are free at every launch
-        ka.pool_cap = pl.pool_cap;
-        aim::dp_strip_launch(p, pl.strip_k, pl.grid, pl.block, pl.lds, ka, stream);
+        aim::dp_wave_launch(p, p.algo == AIM_ALGO_SWG && aim::swg_cell_bytes(p) == 1, m.grid, m.block, m.lds, ka, stream);
         break;
     case K_GENASM:
-        aim::genasm_launch(p, kn, pl.grid, pl.lds, ka, stream);
+        aim::genasm_launch(p, m.grid, m.lds, ka, stream);
         break;
     }
     HIP_TRY(hipGetLastError());
@@ -1105,7 +1001,7 @@ int launch_on_slot(aim_set *set, aim_device_ctx &d, aim_slot &s, uint32_t mode =
     const Plan pl = plan_for_batch(set, d, s, s.n_pairs, mode);
     s.plan_last = pl;
     if (fio && pl.emits_runs) {   // slotted run buffer: pair p owns runs[3p, 3p + 3), the cursor starts behind the slots (wfa_lane_packed.hpp)
-        fio->run_slot = (pl.kid == K_WFA_LANE_PK && (uint64_t)s.n_pairs * aim::kRunSlot <= fio->runs_cap) ? aim::kRunSlot : 0u;
+        fio->run_slot = (pl.main.kid == K_WFA_LANE_PK && (uint64_t)s.n_pairs * aim::kRunSlot <= fio->runs_cap) ? aim::kRunSlot : 0u;
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)fio->cursor, (int)(s.n_pairs * fio->run_slot), 1, s.stream));
     }
     return launch(pl, set->knobs, set->params, s.n_pairs, s.d_req, s.d_pat, s.d_txt, s.d_res, s.d_ops, s.d_scratch,
@@ -1596,10 +1492,9 @@ int aim_set_fallback_pairs(aim_set_t *set, uint32_t device, uint32_t *n_fallback
     if (!s.launched) return fail(AIM_ESTATE, "device %d has not been launched", d.dev);
     *n_fallback = 0;
     const Plan &pl = s.plan_last;   // the plan the launch actually followed, not a re-plan
-    if ((pl.kid != K_WFA_GROUP && pl.kid != K_DP_REG && pl.kid != K_DP_GROUP && !pl.pack_first) || s.n_pairs == 0) return AIM_OK;   // wfa_lane_kernel has no fallback: it aligns every pair itself
+    if (!pl.todo_bytes || s.n_pairs == 0) return AIM_OK;   // no to-do list: the kernel aligns every pair itself
     HIP_TRY(hipSetDevice(d.dev));
-    const char *count_at = static_cast<const char *>(s.d_scratch) + ((pl.kid == K_DP_REG || pl.kid == K_DP_GROUP) ? pl.scratch_total - pl.todo_bytes : 0);   // the to-do count
-    HIP_TRY(hipMemcpy(n_fallback, count_at, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n_fallback, static_cast<const char *>(s.d_scratch) + pl.todo_at, sizeof(uint32_t), hipMemcpyDeviceToHost));   // the to-do count
     return AIM_OK;
 }
 

@@ -508,9 +508,10 @@ inline int swg_cell_bytes(const aim_params_t &p)
     return p.max_score < 127 ? 1 : 2;   // SWG/DPU-WRAM/common/common.h:71-75
 }
 
-// Returns false when even the smallest grid does not fit the scratch budget.
-inline bool dp_lane_plan(const aim_params_t &p, uint32_t n_pairs, uint64_t budget, const Knobs &kn, uint32_t *grid, uint32_t *block,
-                         size_t *lds, uint64_t *scratch_per_wg, size_t *scratch_total, bool *seq_lds)
+// Returns false when even the smallest grid does not fit the scratch budget. todo: the plan of a to-do pass behind another kernel.
+// *seq: where the pattern row lives -- 0 global memory, 1 LDS image, 2 registers (READ_SIZE <= 124); dp_lane_launch follows it.
+inline bool dp_lane_plan(const aim_params_t &p, uint32_t n_pairs, uint64_t budget, const Knobs &kn, bool todo, uint32_t *grid, uint32_t *block,
+                         size_t *lds, uint64_t *scratch_per_wg, size_t *scratch_total, int *seq)
 {
     const uint64_t rs = (uint64_t)p.read_size;
     // uniform-stride slab: NW (rs+8) columns (16-B units of 8 cells, +7 offset), SWG (rs+1); (rs+1) rows + slack
@@ -530,20 +531,25 @@ inline bool dp_lane_plan(const aim_params_t &p, uint32_t n_pairs, uint64_t budge
     const size_t img = (size_t)(p.read_size >> 2) * kWave * 4;   // pattern image only
     const size_t rows = p.algo == AIM_ALGO_NW ? (size_t)(p.read_size + 1) * kWave * 2
                                               : (size_t)2 * (p.read_size + 1) * kWave * swg_cell_bytes(p);   // SWG: M and I rows, CELL-typed
-    *seq_lds = img + rows <= 150 * 1024;
+    bool seq_lds = img + rows <= 150 * 1024;
     // SWG score-only does better with the pattern read from global memory and the LDS spent on residency instead (l = 100, 1 M
     // pairs, same box: image in LDS, 7 workgroups per CU 7.12 ms; no image, 8 / 10 / 11 per CU 6.66 / 6.28 / 6.30 ms). NW and the
     // CIGAR variants measure the other way (NW score-only 4.32 vs 5.24 ms, SWG CIGAR 12.5 vs 13.6 ms).
-    if (p.algo == AIM_ALGO_SWG && !(p.flags & AIM_FLAG_BACKTRACE)) *seq_lds = false;
+    if (p.algo == AIM_ALGO_SWG && !(p.flags & AIM_FLAG_BACKTRACE)) seq_lds = false;
     // READ_SIZE <= 124: no image either -- the pattern row lives in REGISTERS (dp_lane_launch, SEQ = 2), the LDS it frees is residency
     // (10 instead of 7 workgroups per CU). l = 100, 1 M pairs, same box, image in LDS / registers / global memory: NW score-only 4.30 / 3.27 /
     // 5.25 ms, NW with CIGAR 7.60 / 6.86 / 11.8, SWG score-only - / 5.89 / 6.25, SWG with CIGAR 12.7 / 11.0 / 14.5.
-    if (p.read_size <= 124 && !kn.dpl_no_reg && kn.dpl_seq_lds < 0) *seq_lds = false;
+    if (p.read_size <= 124 && !kn.dpl_no_reg && kn.dpl_seq_lds < 0) seq_lds = false;
     // experiments (AIM_DPL_SEQ_LDS): 0 = pattern from global memory, 1 = image in LDS (where it fits), 2 = registers (READ_SIZE <= 124);
     // an explicit value overrides the defaults above
-    if (kn.dpl_seq_lds == 0 || (kn.dpl_seq_lds == 2 && p.read_size <= 124)) *seq_lds = false;
-    else if (kn.dpl_seq_lds == 1) *seq_lds = img + rows <= 150 * 1024;
-    *lds = rows + (*seq_lds ? img : 0);
+    if (kn.dpl_seq_lds == 0 || (kn.dpl_seq_lds == 2 && p.read_size <= 124)) seq_lds = false;
+    else if (kn.dpl_seq_lds == 1) seq_lds = img + rows <= 150 * 1024;
+    // no image in LDS: registers when the row fits 31 dwords (preg[w0 + 1] stays inside the vector)
+    *seq = seq_lds ? 1 : (p.read_size <= 124 && !kn.dpl_no_reg && kn.dpl_seq_lds != 0) ? 2 : 0;
+    // a to-do pass: every lane loads its own pair's pattern row, into registers or from global memory -- never an LDS image (the
+    // listed pairs are not consecutive); the knobs above are not its to choose
+    if (todo) *seq = p.read_size <= 124 ? 2 : 0;
+    *lds = rows + (*seq == 1 ? img : 0);
     if (*lds > 160 * 1024) return false;
     uint32_t per_cu = (uint32_t)std::min<size_t>(12, lds_workgroups_per_cu(*lds));
     if (kn.dpl_per_cu >= 0) {   // experiments: residency sweep (also lifts the 8-per-CU start value)
@@ -563,10 +569,10 @@ inline bool dp_lane_plan(const aim_params_t &p, uint32_t n_pairs, uint64_t budge
 
 // Kernels are instantiated in ONE translation unit (tu_*.hip defines AIM_TU_DP_LANE); every other includer sees the declaration only.
 #ifdef AIM_TU_DP_LANE
-void dp_lane_launch(const aim_params_t &p, const Knobs &kn, uint32_t grid, size_t lds, bool seq_lds, const KArgs &ka, hipStream_t s)
+// seq: where the pattern row lives (dp_lane_plan)
+void dp_lane_launch(const aim_params_t &p, int seq, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s)
 {
     const bool bt = p.flags & AIM_FLAG_BACKTRACE;
-    const int seq = seq_lds ? 1 : (p.read_size <= 124 && !kn.dpl_no_reg && kn.dpl_seq_lds != 0) ? 2 : 0;   // no image in LDS: registers when the row fits 31 dwords (preg[w0 + 1] stays inside the vector)
 #define AIM_DP_LAUNCH(KERNEL)                                                                                             \
     do {                                                                                                                  \
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
@@ -589,7 +595,7 @@ void dp_lane_launch(const aim_params_t &p, const Knobs &kn, uint32_t grid, size_
 #undef AIM_DP_LAUNCH
 }
 #else
-void dp_lane_launch(const aim_params_t &p, const Knobs &kn, uint32_t grid, size_t lds, bool seq_lds, const KArgs &ka, hipStream_t s);
+void dp_lane_launch(const aim_params_t &p, int seq, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s);
 #endif
 
 }  // namespace aim

@@ -723,7 +723,7 @@ inline bool dp_strip_supported(const aim_params_t &p, bool cell8, const Knobs &k
 }
 
 inline bool dp_strip_plan(const aim_params_t &p, uint32_t n_pairs, uint64_t budget, const Knobs &kn, uint32_t *grid, uint32_t *block, size_t *lds,
-                          uint64_t *scratch_per_wg, size_t *scratch_total, int *k_out, uint32_t *pool_tables)
+                          uint64_t *scratch_per_wg, size_t *scratch_total, int *k_out)
 {
     const uint64_t rs = (uint64_t)p.read_size;
     const bool swg = p.algo == AIM_ALGO_SWG;
@@ -755,7 +755,6 @@ inline bool dp_strip_plan(const aim_params_t &p, uint32_t n_pairs, uint64_t budg
     *grid = g;
     *scratch_per_wg = per;
     *scratch_total = (size_t)(per * g);
-    *pool_tables = 0;   // (round 5's pool of literal-path tables: gone, see the kernel)
     return true;
 }
 

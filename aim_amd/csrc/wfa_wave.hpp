@@ -592,6 +592,88 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
     }
 }
 
+// What make_plan (aim_capi.hip) launches wfa_wave_kernel with, alone or over a lane / group kernel's to-do list.
+struct WfaWavePlan {
+    uint32_t grid;
+    size_t lds;
+    uint64_t scratch_per_wg;   // WfMeta array + pool of one wave
+    uint32_t pool_cap, meta_cap, ring_slots, slot_w;
+    bool seq_lds;
+    uint64_t wide;             // ends-free: diagonals every wavefront is wider by
+};
+enum { kWfaWaveOk = 0, kWfaWaveNoPool, kWfaWaveNoScore0, kWfaWaveNoWindow };   // wfa_wave_plan: what does not fit the budget
+
+// pb / tb: the ends-free begin lengths (0 without AIM_FLAG_ENDSFREE); o2 / e2: the second gap piece of AIM_FLAG_AFFINE2P.
+inline int wfa_wave_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs &kn, uint64_t budget, int pb, int tb, int o2, int e2,
+                         WfaWavePlan *w)
+{
+    const bool bt = p.flags & AIM_FLAG_BACKTRACE;
+    const bool a2p = p.flags & AIM_FLAG_AFFINE2P;
+    const uint64_t ms = (uint64_t)p.max_score;
+    // ends-free: every wavefront is up to PB + TB diagonals wider (the free lengths clamp to the pairs' lengths <= READ_SIZE)
+    const uint64_t wide = (uint64_t)std::min(pb, p.read_size) + (uint64_t)std::min(tb, p.read_size);
+    w->wide = wide;
+    // affine2p: five rows per wavefront (M, I1, D1, I2, D2) and a live window of max(x, o1+e1, o2+e2) + 1 scores
+    const uint64_t nc = a2p ? 5 : 3;
+    const int Rw = std::max(std::max(p.mismatch, p.gap_o + p.gap_e), a2p ? o2 + e2 : 0);
+    const uint64_t full = nc * (ms + 2) * (ms + 2 + wide) + 64;
+    uint64_t cap;
+    if (bt) {
+        cap = full;
+    } else {   // score-only: the pool is a ring that must hold the live window (scores s-R .. s) plus the one being built
+        const uint64_t R = (uint64_t)Rw;
+        cap = std::min(full, (R + 2) * nc * (2 * ms + 3 + wide));
+    }
+    const uint64_t cap_min = bt ? 0 : cap;   // below this a score-only ring would overwrite wavefronts still in use
+    w->meta_cap = (uint32_t)(ms + 2);
+    // LDS ring for the live window of wavefronts: max(x, o+e)+1 slots of slot_w diagonals (M, I, D)
+    {
+        const uint32_t R = (uint32_t)Rw;
+        uint32_t sw = 16;
+        while (sw < 2 * (uint32_t)ms + 3 + (uint32_t)wide && sw < 128) sw *= 2;   // 128: keeps 16 workgroups resident per CU at l = 1000 (measured +9 % over 256)
+        if (kn.wfa_slotw >= 0) sw = (uint32_t)std::max(16, kn.wfa_slotw) & ~15u;
+        while (sw > 16 && (uint64_t)(R + 1) * nc * sw * 2 > 24 * 1024) sw /= 2;
+        const bool ring_ok = (uint64_t)(R + 1) * nc * sw * 2 <= 24 * 1024 && !kn.wfa_no_ring;
+        w->ring_slots = ring_ok ? R + 1 : 0;
+        w->slot_w = ring_ok ? sw : 0;
+    }
+    const size_t seq_bytes = 2 * ((size_t)p.read_size + 8);
+    w->seq_lds = seq_bytes <= 40 * 1024;
+    const size_t ring_bytes = ((size_t)w->ring_slots * nc * w->slot_w * sizeof(int16_t) + 15) & ~(size_t)15;
+    w->lds = kMetaRing * sizeof(WfMeta) + ring_bytes + (w->seq_lds ? seq_bytes : 0);
+    // persistent single-wave workgroups: exactly what is resident (4 waves/SIMD by VGPRs, 160 KiB LDS per CU);
+    // a larger grid runs in uneven rounds
+    // (affine2p with BACKTRACE: 142-148 VGPRs, 3 waves per SIMD)
+    const uint32_t wg_per_cu = (uint32_t)std::min<size_t>(a2p && bt ? 12 : 16, lds_workgroups_per_cu(w->lds));
+    uint32_t grid = resident_grid(kn, wg_per_cu);
+    const uint32_t need = ((n_pairs + 7u) / 8u) * 8u;
+    if (grid > need) grid = std::max(8u, need);
+    uint64_t per = (uint64_t)w->meta_cap * sizeof(WfMeta) + cap * sizeof(int16_t);
+    per = (per + 255) & ~255ull;
+    while (grid > 2 * kn.cus && grid > 16 && per * grid > budget) grid = ((grid / 2) + 7u) & ~7u;
+    if (per * grid > budget) {
+        const uint64_t meta_b = (uint64_t)w->meta_cap * sizeof(WfMeta);
+        if (bt) {
+            // With BACKTRACE the pool is a bump arena like the DPU's (allocate_new_score, wfa.c:143-183): a smaller one
+            // is legal and a pair that outgrows it reports AIM_PAIR_NOMEM (dpu_allocator_wram.c:19-23 "out of memory").
+            uint64_t avail = budget / grid;
+            if (avail < meta_b + 4096) return kWfaWaveNoPool;
+            cap = (avail - meta_b - 256) / sizeof(int16_t);
+            if (cap < wide + 1) return kWfaWaveNoScore0;
+            per = (meta_b + cap * sizeof(int16_t) + 255) & ~255ull;
+        } else {
+            // Score-only: the pool is a ring and must keep its full live window (a shrunken ring silently overwrites
+            // wavefronts score-x / score-o-e / score-e still read). Fewer workgroups instead, down to one per XCD.
+            while (grid > 8 && per * grid > budget) grid -= 8;
+            if (per * grid > budget || cap < cap_min) return kWfaWaveNoWindow;
+        }
+    }
+    w->grid = grid;
+    w->pool_cap = (uint32_t)std::min<uint64_t>(cap, 0x7fffffffu);
+    w->scratch_per_wg = per;
+    return kWfaWaveOk;
+}
+
 // Kernels are instantiated in ONE translation unit (tu_*.hip defines AIM_TU_WFA_WAVE); every other includer sees the declaration only.
 #ifdef AIM_TU_WFA_WAVE
 void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s)
