@@ -17,8 +17,10 @@ AIM_OK, AIM_EINVAL, AIM_ENODEV, AIM_ENOMEM, AIM_ESTATE, AIM_EALIGN = 0, -1, -2, 
 ALGO_NW, ALGO_SWG, ALGO_WFA, ALGO_GENASM = 0, 1, 2, 3
 ALGO_BY_NAME = {"nw": ALGO_NW, "swg": ALGO_SWG, "wfa": ALGO_WFA, "genasm": ALGO_GENASM}
 FLAG_BACKTRACE, FLAG_REDUCE, FLAG_SWG_W16, FLAG_REQ8, FLAG_RES8, FLAG_ENDSFREE, FLAG_AFFINE2P = 1, 2, 4, 8, 16, 32, 64
+FLAG_LINEAR = 128      # gap-linear WFA on Params itself (gap_o = 0, gap_e per gap base)
 FEATURE_ENDSFREE = 1   # aim_features(): AIM_FLAG_ENDSFREE is honoured
 FEATURE_AFFINE2P = 2   # aim_features(): AIM_FLAG_AFFINE2P is honoured
+FEATURE_LINEAR = 4     # aim_features(): AIM_FLAG_LINEAR is honoured
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
 
 

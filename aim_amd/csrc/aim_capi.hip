@@ -226,6 +226,8 @@ inline Affine2p affine2p(const aim_params_t &p)
     g.o2 = x.gap_o2; g.e2 = x.gap_e2;
     return g;
 }
+// AIM_FLAG_LINEAR: gap-linear WFA on aim_params_t itself (no extension): gap_o = 0, gap_e is the cost of one gap base.
+inline bool is_linear(const aim_params_t &p) { return (p.flags & AIM_FLAG_LINEAR) != 0; }
 // The params as this library keeps them: room for either extension, and the extension copied only when a flag says it exists.
 union XParams {
     aim_params_t base;
@@ -249,6 +251,12 @@ int validate_params(const aim_params_t &p)
     // before either extension is read: the caller's struct holds at most one of them (an aim_affine2p_params_t is shorter than
     // an aim_endsfree_params_t)
     if (is_endsfree(p) && is_affine2p(p)) return fail(AIM_EINVAL, "AIM_FLAG_AFFINE2P cannot be combined with AIM_FLAG_ENDSFREE");
+    if (is_linear(p)) {
+        if (p.algo != AIM_ALGO_WFA) return fail(AIM_EINVAL, "AIM_FLAG_LINEAR needs AIM_ALGO_WFA");
+        if (p.flags & AIM_FLAG_REDUCE) return fail(AIM_EINVAL, "AIM_FLAG_LINEAR cannot be combined with AIM_FLAG_REDUCE");
+        if (is_endsfree(p)) return fail(AIM_EINVAL, "AIM_FLAG_LINEAR cannot be combined with AIM_FLAG_ENDSFREE");
+        if (is_affine2p(p)) return fail(AIM_EINVAL, "AIM_FLAG_LINEAR cannot be combined with AIM_FLAG_AFFINE2P");
+    }
     if (p.read_size <= 0 || (p.read_size & 7)) return fail(AIM_EINVAL, "read_size must be a positive multiple of 8 (got %d)", p.read_size);
     if (p.max_score < 0) return fail(AIM_EINVAL, "max_score must be >= 0");
     if ((p.flags & AIM_FLAG_REQ8) && p.read_size >= 32760)
@@ -264,6 +272,10 @@ int validate_params(const aim_params_t &p)
     // same admission rule as the launchers (run-wfa-pim-wram.py:41-43): m <= 0 and x, g, a > 0
     if (p.algo == AIM_ALGO_NW) {
         if (p.mismatch <= 0 || p.gap_i <= 0 || p.gap_d <= 0) return fail(AIM_EINVAL, "NW penalties must be x, g > 0");
+    } else if (is_linear(p)) {
+        if (p.match > 0 || p.mismatch <= 0 || p.gap_o != 0 || p.gap_e <= 0)
+            return fail(AIM_EINVAL, "gap-linear penalties must be m <= 0, gap_o = 0 and x, gap_e > 0 (got %d,%d,%d,%d)", p.match, p.mismatch,
+                        p.gap_o, p.gap_e);
     } else {
         if (p.match > 0 || p.mismatch <= 0 || p.gap_o <= 0 || p.gap_e <= 0)
             return fail(AIM_EINVAL, "Wrong affine gap penalties must be  m <= 0 and g, a, x > 0");
@@ -365,12 +377,12 @@ bool plan_wfa_group(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
 }
 
 // WFA: a lane kernel where it takes the shape; else wfa_group, or wfa_lane_packed behind pack_rows_kernel, with wfa_wave over their
-// to-do list; else wfa_wave alone. Ends-free and affine2p never run on the lane kernels (their wavefront shapes are fixed at compile
+// to-do list; else wfa_wave alone. Ends-free, affine2p and gap-linear never run on the lane kernels (their wavefront shapes are fixed at compile
 // time for the global case): wfa_group where LDS admits the wider rows / deeper rings, else wfa_wave.
 int plan_wfa(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, uint32_t mode, Plan *pl)
 {
     const bool bt = p.flags & AIM_FLAG_BACKTRACE;
-    const bool lanes = !is_endsfree(p) && !is_affine2p(p) && !kn.force_wave && !kn.no_lane;   // a lane kernel may run
+    const bool lanes = !is_endsfree(p) && !is_affine2p(p) && !is_linear(p) && !kn.force_wave && !kn.no_lane;   // a lane kernel may run
     const bool lane_pk_ok = lanes && !kn.no_lane_pk && aim::wfa_lane_packed_supported(p, !kn.no_lane_ext);
     Stage &m = pl->main;
     if ((mode & MODE_PACKED_IN) && lane_pk_ok) {
@@ -425,8 +437,8 @@ int plan_wfa(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint
         // [to-do | history regions | general kernel]
         pl->pk = gpk;
         // (ends-free: ops rows, then cigar_rle_kernel -- the fused run output of wfa_group_tb_kernel is not used for it: one pair of
-        // a host run came back with a void first run, cause not found; affine2p likewise)
-        pl->emits_runs = bt && (mode & MODE_RUNS_OUT) && !is_endsfree(p) && !is_affine2p(p);
+        // a host run came back with a void first run, cause not found; affine2p and gap-linear likewise)
+        pl->emits_runs = bt && (mode & MODE_RUNS_OUT) && !is_endsfree(p) && !is_affine2p(p) && !is_linear(p);
         pl->hist_at = pl->todo_bytes;
         pl->fb.scratch_at = pl->hist_at + pl->hist_bytes;
     }
@@ -579,6 +591,8 @@ int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint6
     } else if (is_affine2p(p)) {
         const Affine2p g = affine2p(p);
         snprintf(efs, sizeof efs, " affine2p=%d,%d", g.o2, g.e2);
+    } else if (is_linear(p)) {
+        snprintf(efs, sizeof efs, " linear");
     }
     return snprintf(out, cap, "%s n=%u grid=%u block=%u lds=%zu scratch=%zu budget=%llu%s%s", kernel_name(pl, p), n_pairs, pl.main.grid,
                     pl.main.block, pl.main.lds, pl.scratch_total, (unsigned long long)budget, extra, efs);
@@ -1012,7 +1026,7 @@ int launch_on_slot(aim_set *set, aim_device_ctx &d, aim_slot &s, uint32_t mode =
 extern "C" {
 
 int aim_abi_version(void) { return AIM_ABI_VERSION; }
-uint32_t aim_features(void) { return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P; }
+uint32_t aim_features(void) { return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR; }
 const char *aim_last_error(void) { return g_err; }
 
 int aim_device_count(int *count)

@@ -30,6 +30,10 @@
 // is max(x, o1+e1, o2+e2) + 1 rows deep, the unit is gcd(x, o1+e1, e1, o2+e2, e2), and a history cell is 16 bytes {M, I1, D1, I2, D2, -}
 // (one store). An absent piece-2 component reads as NULL, not as the -10 of an absent I1 / D1, so that a piece 2 that never
 // fires leaves every M offset as global WFA computes it. group_tb_walk_a2p tests piece 1 before piece 2 at every step.
+//
+// LIN (AIM_FLAG_LINEAR, never with REDUCE, EF or A2P): gap-linear. M only: M[s][k] = max(M[s-x][k] + 1, M[s-g][k-1] + 1, M[s-g][k+1]),
+// then extend; no I / D rings (GroupCfg::ring_e = 0), no I / D loads. The M / descriptor ring is max(x, g) + 1 rows, the unit gcd(x, g), a
+// history cell is the 2-byte M offset. Every NULL reads as NULL (no -10 of an absent component). group_tb_walk_lin tests D, I, X.
 #pragma once
 
 #include <cstdlib>
@@ -52,6 +56,10 @@
 #ifndef AIM_GROUP_A2P_MIN_WAVES
 #define AIM_GROUP_A2P_MIN_WAVES 4
 #endif
+// The LIN kernels (M only, 2-byte history cells) get their own bound, and the plan caps their residency to match.
+#ifndef AIM_GROUP_LIN_MIN_WAVES
+#define AIM_GROUP_LIN_MIN_WAVES 6
+#endif
 #ifndef AIM_GROUP_MAX_PER_CU
 #define AIM_GROUP_MAX_PER_CU 20   // cap on resident single-wave workgroups per CU (5 per SIMD at <= 102 VGPRs; 24 measured worse on cfg3 with CIGAR)
 #endif
@@ -62,7 +70,7 @@ struct GroupCfg {
     int kbias;        // MAX_SCORE + 1: slot index of diagonal k is k + kbias
     int wcap;         // 2*MAX_SCORE + 3 entries per ring row
     int ring_m;       // rows of the M / descriptor ring: max(x, o+e) + 1
-    int ring_e;       // power of two > e
+    int ring_e;       // power of two > e (LIN: 0, no I / D rings)
     int np;           // packed dwords per sequence (READ_SIZE/16 rounded up) + 1 pad
     int pair_dwords;  // LDS dwords per pair: window + descriptors + packed sequences (odd => conflict-free across pairs)
     int rows_per_wave;
@@ -89,6 +97,7 @@ struct GroupCfg {
                       // visits the null wavefronts in between (x = 4, o = 6, e = 2: every second step of the reference's loop)
     int efpb, eftb;   // EF kernels: the diagonals -efpb .. eftb of score 0 (free lengths clamped to READ_SIZE); 0 otherwise
     int ring_e2;      // A2P kernels: rows of the I2 / D2 rings, a power of two > e2 (0 otherwise); history cells are 16 bytes
+                      // (LIN kernels: 2 bytes, the M offset alone)
 };
 
 enum { GF_PRESENT = 1, GF_MNULL = 2, GF_INULL = 4, GF_DNULL = 8, GF_HASI = 16, GF_HASD = 32, GF_HASI2 = 64, GF_HASD2 = 128 };
@@ -143,8 +152,8 @@ __device__ __forceinline__ int group_min(int v)
 #else
 #define AIM_GSTAMP(i) do { } while (0)
 #endif
-template <int G, bool REDUCE, bool BT, bool MODW = false, bool EF = false, bool A2P = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GROUP_A2P_MIN_WAVES : AIM_GROUP_MIN_WAVES))) void wfa_group_kernel(KArgs a, GroupCfg c)
+template <int G, bool REDUCE, bool BT, bool MODW = false, bool EF = false, bool A2P = false, bool LIN = false>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GROUP_A2P_MIN_WAVES : LIN ? AIM_GROUP_LIN_MIN_WAVES : AIM_GROUP_MIN_WAVES))) void wfa_group_kernel(KArgs a, GroupCfg c)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     debug_poison_lds(a, smem);
@@ -353,6 +362,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
         TbRow *htab = reinterpret_cast<TbRow *>(hreg + sizeof(TbHead));
         uint2 *hpool = reinterpret_cast<uint2 *>(hreg + c.pool_off);   // cells {M, I, D, -}: ONE 8-byte store per computed cell, at its closed-form index (GroupCfg)
         uint4 *hpool4 = reinterpret_cast<uint4 *>(hreg + c.pool_off);  // A2P: cells {M, I1, D1, I2, D2, -, -, -}, one 16-byte store
+        int16_t *hpool2 = reinterpret_cast<int16_t *>(hreg + c.pool_off);   // LIN: cells {M}, one 2-byte store
         const bool hnarrow = c.wlds != c.wcap;
         if (EF) {   // M[k] = max(k, 0) on [-pb, tb], extended by the group's lanes
             klo = -pb; khi = tb;
@@ -368,6 +378,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
             mrow_at(0)[H(0)] = (int16_t)m00;
             if (BT && !done) {
                 if (A2P) hpool4[hnarrow ? H(0) : 0] = make_uint4((uint32_t)(uint16_t)m00, 0u, 0u, 0u);
+                else if (LIN) hpool2[hnarrow ? H(0) : 0] = (int16_t)m00;
                 else hpool[hnarrow ? H(0) : 0] = make_uint2((uint32_t)(uint16_t)m00, 0u);
             }
             meta[0] = 0; meta[1] = 0; meta[2] = (int16_t)flags;
@@ -474,11 +485,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
                 int sub_f = 0, o_f = 0, e_f = 0, sub_lo = 1, sub_hi = -1, o_lo = 1, o_hi = -1, e_lo = 1, e_hi = -1;
                 if (s_sub >= 0) { const int16_t *m = meta_at(i_x); sub_lo = m[0]; sub_hi = m[1]; sub_f = m[2]; }
                 if (s_o >= 0) { const int16_t *m = meta_at(i_oe); o_lo = m[0]; o_hi = m[1]; o_f = m[2]; }
-                if (s_e >= 0) { const int16_t *m = meta_at(i_e); e_lo = m[0]; e_hi = m[1]; e_f = m[2]; }
+                if (!LIN && s_e >= 0) { const int16_t *m = meta_at(i_e); e_lo = m[0]; e_hi = m[1]; e_f = m[2]; }
                 const bool m_sub_null = (s_sub < 0) || !(sub_f & GF_PRESENT) || (sub_f & GF_MNULL);
                 const bool m_o_null = (s_o < 0) || !(o_f & GF_PRESENT) || (o_f & GF_MNULL);
-                const bool i_e_null = (s_e < 0) || !(e_f & GF_PRESENT) || !(e_f & GF_HASI) || (e_f & GF_INULL);
-                const bool d_e_null = (s_e < 0) || !(e_f & GF_PRESENT) || !(e_f & GF_HASD) || (e_f & GF_DNULL);
+                // (LIN: no I / D components; I and D of a cell come from M at s - g, the "open" source, with o = 0)
+                const bool i_e_null = LIN || (s_e < 0) || !(e_f & GF_PRESENT) || !(e_f & GF_HASI) || (e_f & GF_INULL);
+                const bool d_e_null = LIN || (s_e < 0) || !(e_f & GF_PRESENT) || !(e_f & GF_HASD) || (e_f & GF_DNULL);
                 const bool i_out_null = m_o_null && i_e_null, d_out_null = m_o_null && d_e_null;
                 // A2P: piece 2's sources -- M at s - (o2+e2), I2 / D2 at s - e2
                 int o2_lo = 1, o2_hi = -1, e2_lo = 1, e2_hi = -1;
@@ -528,12 +540,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
                     const int16_t *r_mo2 = mrow_at(i_oe2), *r_ie2 = A2P ? i2slot(max(score - E2, 0)) : nullptr, *r_de2 = A2P ? d2slot(max(score - E2, 0)) : nullptr;
                     int16_t *oi2 = A2P ? i2slot(score) : nullptr, *od2 = A2P ? d2slot(score) : nullptr;
                     uint4 *hrow4 = hpool4 + (hnarrow ? score * wl : score * score + score);   // A2P (never EF)
+                    int16_t *hrow2 = hpool2 + (hnarrow ? score * wl : score * score + score);  // LIN (never EF)
                     part = 0x7fffffff;
                     int trip = 0;
                     // What an ABSENT component reads as is -10 (the reference's un-computed default), what an out-of-range fetch reads as is NULL:
                     // when a component is absent every fetch that feeds it is out of range (its sources are null: ranges 1 .. -1), so the
                     // "out of range" value of those fetches is made -10 once per step instead of one more select per cell and component (round 6).
-                    const int nul_i = i_out_null ? -10 : kGrpNull, nul_d = d_out_null ? -10 : kGrpNull, nul_s = m_sub_null ? -10 : kGrpNull;
+                    // (LIN: NULL throughout -- the offsets are the exact gap-linear optimum, and wfa_wave_kernel computes the same values)
+                    const int nul_i = (!LIN && i_out_null) ? -10 : kGrpNull, nul_d = (!LIN && d_out_null) ? -10 : kGrpNull, nul_s = (!LIN && m_sub_null) ? -10 : kGrpNull;
                     // homes advance with k: one conditional subtraction per step instead of a modulo per address (3 per trip)
                     // (MODW: the unsigned minimum of h and h -+ wl is the one that lies in [0, wl): two instructions, no compare + select)
                     auto wrap_up = [&](int h_) { if constexpr (MODW) return (int)min((uint32_t)h_, (uint32_t)(h_ - wl)); else return h_ & wmask; };
@@ -548,17 +562,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
                         // compiler sank two of the five loads into the blocks, i.e. back into a second round trip.)
                         AIM_GTRIP(dbg_kt);
                         const int hkm = wrap_dn(hk - 1), hkp = wrap_up(hk + 1);
-                        const int raw_mo_m1 = r_mo[hkm], raw_ie_m1 = r_ie[hkm], raw_mo_p1 = r_mo[hkp], raw_de_p1 = r_de[hkp],
+                        const int raw_mo_m1 = r_mo[hkm], raw_ie_m1 = LIN ? kGrpNull : r_ie[hkm], raw_mo_p1 = r_mo[hkp], raw_de_p1 = LIN ? kGrpNull : r_de[hkp],
                                   raw_ms = r_ms[hk];
                         const int ins_g = (!m_o_null && o_lo <= k - 1 && k - 1 <= o_hi) ? raw_mo_m1 : kGrpNull;
                         const int ins_i = (!i_e_null && e_lo <= k - 1 && k - 1 <= e_hi) ? raw_ie_m1 : kGrpNull;
                         // (offsets are <= READ_SIZE <= 16 368 or kGrpNull: the reference's int16 store of offset + 1 never wraps, so no cast is spelled out)
                         const int ins = (ins_g == kGrpNull && ins_i == kGrpNull) ? nul_i : max(ins_g, ins_i) + 1;   // i_out_null: both are NULL -> -10
-                        if (!i_out_null) oi[hk] = (int16_t)ins;
+                        if (!LIN && !i_out_null) oi[hk] = (int16_t)ins;
                         const int del_g = (!m_o_null && o_lo <= k + 1 && k + 1 <= o_hi) ? raw_mo_p1 : nul_d;
                         const int del_d = (!d_e_null && e_lo <= k + 1 && k + 1 <= e_hi) ? raw_de_p1 : nul_d;
                         const int del = max(del_g, del_d);                                                            // d_out_null: both are nul_d = -10
-                        if (!d_out_null) od[hk] = (int16_t)del;
+                        if (!LIN && !d_out_null) od[hk] = (int16_t)del;
                         const int sub = (sub_lo <= k && k <= sub_hi) ? raw_ms + 1 : nul_s;                            // m_sub_null: range 1 .. -1 -> -10
                         // M[s][k] as the reference stores it (int16), then affine_wfa_extend (wfa.c:186-208) on that value: a
                         // diagonal's extension depends on nothing but its own offset, so it is applied before the one store
@@ -582,6 +596,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
                         if (BT && A2P)
                             hrow4[hnarrow ? hk : k] = make_uint4((uint32_t)(uint16_t)ext | ((uint32_t)(uint16_t)ins << 16), (uint32_t)(uint16_t)del | ((uint32_t)(uint16_t)ins2 << 16),
                                                                  (uint32_t)(uint16_t)del2, 0u);
+                        else if (BT && LIN) hrow2[hnarrow ? hk : k] = (int16_t)ext;
                         else if (BT) hrow[hnarrow ? hk : k] = make_uint2((uint32_t)(uint16_t)ext | ((uint32_t)(uint16_t)ins << 16), (uint32_t)(uint16_t)del);   // I / D: -10 when absent (never selected)
                         const int dist = max(plen - (ext - k), tlen - ext);
                         part = min(part, dist);
@@ -848,7 +863,74 @@ __device__ __forceinline__ int group_tb_walk_a2p(const GroupCfg &c, const TbRow 
     return status;
 }
 
-template <bool RUNS, bool MODW, bool EF = false, bool A2P = false>
+// The LIN walk: M only, cells are the 2-byte M offsets. After the matches of a step it tests D (M[s-g][k+1]), then I (M[s-g][k-1] + 1),
+// then X (M[s-x][k] + 1) -- the global walk's D-before-I-before-X order with every gap an "open" from M. wfa_wave_kernel walks alike.
+template <bool MODW, typename Sink>
+__device__ __forceinline__ int group_tb_walk_lin(const GroupCfg &c, const TbRow *tab, const int16_t *pool, int final_score, int plen, int tlen, int X, int E,
+                                                 Sink &sink)
+{
+    const int ak = tlen - plen;
+    int status = AIM_PAIR_OK;
+    auto valid_loc = [&](int kk_, int off_) {
+        const int v_ = off_ - kk_, h_ = off_;
+        return v_ > 0 && v_ <= plen && h_ > 0 && h_ <= tlen;
+    };
+    struct Row { int klo, khi, f; };
+    auto row = [&](int s_) {
+        const uint2 q = *reinterpret_cast<const uint2 *>(tab + max(s_, 0));
+        Row r;
+        r.klo = (int16_t)(q.x & 0xffffu); r.khi = (int16_t)(q.x >> 16); r.f = (int)(q.y & 0xffffu);
+        if (s_ < 0) { r.klo = 1; r.khi = -1; r.f = 0; }
+        return r;
+    };
+    auto cell = [&](int s_, int k_) -> int { return pool[group_cell_index<MODW>(c, max(s_, 0), k_)]; };
+    auto in_row = [](const Row &r, int k_) { return (r.f & GF_PRESENT) && r.klo <= k_ && k_ <= r.khi; };
+    int sc = final_score, k = ak;
+    int offset = cell(sc, k);
+    bool valid = valid_loc(k, offset);
+    int v = offset - k, h = offset;
+    while (v > 0 && h > 0 && sc > 0) {
+        if (!valid) {
+            valid = valid_loc(k, offset);
+            if (valid) {   // add_trailing_gap, wfa_backtracing.c:48-69
+                if (k < ak) for (int i = k; i < ak; ++i) sink.put('I');
+                else if (k > ak) for (int i = ak; i < k; ++i) sink.put('D');
+            }
+        }
+        const int s_g = sc - E, s_x = sc - X;
+        const Row rg = row(s_g), rx = row(s_x);   // addresses depend on (sc, k) only: one round trip
+        const int v_d = cell(s_g, k + 1), v_i = cell(s_g, k - 1), v_x = cell(s_x, k);
+        const int del = in_row(rg, k + 1) ? v_d : kGrpNull;
+        const int ins = in_row(rg, k - 1) ? (int)(int16_t)(v_i + 1) : kGrpNull;
+        const int misms = in_row(rx, k) ? (int)(int16_t)(v_x + 1) : kGrpNull;
+        const int max_all = max(misms, max(ins, del));
+        const int num_matches = offset - max_all;
+        if (num_matches > 0) sink.matches(num_matches);
+        offset = max_all;
+        v = offset - k;
+        h = offset;
+        if (v <= 0 || h <= 0) break;
+        char op;
+        if (max_all == del) { op = 'D'; sc = s_g; ++k; }
+        else if (max_all == ins) { op = 'I'; sc = s_g; --k; offset = (int16_t)(offset - 1); }
+        else if (max_all == misms) { op = 'X'; sc = s_x; offset = (int16_t)(offset - 1); }
+        else { status = AIM_PAIR_WFA_NO_LINK; break; }
+        if (valid) sink.put(op);
+        v = offset - k;
+        h = offset;
+    }
+    if (status == AIM_PAIR_OK) {
+        if (sc == 0) {
+            if (offset > 0) sink.matches(offset);
+        } else {
+            for (; v > 0; --v) sink.put('D');
+            for (; h > 0; --h) sink.put('I');
+        }
+    }
+    return status;
+}
+
+template <bool RUNS, bool MODW, bool EF = false, bool A2P = false, bool LIN = false>
 __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
 {
     const int lane = threadIdx.x;
@@ -886,6 +968,8 @@ __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
         if (walk) {
             if constexpr (A2P)
                 status = group_tb_walk_a2p<MODW>(c, tab, pool, final_score / U, plen, tlen, X, OE, E, (a.a2p_o2 + a.a2p_e2) / U, a.a2p_e2 / U, sink);
+            else if constexpr (LIN)
+                status = group_tb_walk_lin<MODW>(c, tab, pool, final_score / U, plen, tlen, X, E, sink);
             else
                 status = group_tb_walk<MODW, EF>(c, tab, pool, final_score / U, hd.end_k, plen, tlen, X, OE, E, sink);
             if (status == AIM_PAIR_OK) ++sink.pos;
@@ -915,6 +999,7 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
 {
     const bool ef = (p.flags & AIM_FLAG_ENDSFREE) != 0;
     const bool a2p = (p.flags & AIM_FLAG_AFFINE2P) != 0;   // gap_o2 / gap_e2: the extension (the caller passes them)
+    const bool lin = (p.flags & AIM_FLAG_LINEAR) != 0;      // gap-linear: gap_o = 0, so o + e = g below; M ring only
     if (p.algo != AIM_ALGO_WFA) return false;
     // int16 offsets with NULL = -16384 (offset + 1 must stay above it) and 24-bit home arithmetic bound the shapes; what really decides is LDS below:
     // the packed image (READ_SIZE / 2 bytes per pair) and, without the reduction, rows of 2 * MAX_SCORE + 3 entries. (Rounds 1-3 stopped at READ_SIZE
@@ -926,6 +1011,7 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
     ring_m = R + 1;
     while (ring_e <= p.gap_e) ring_e *= 2;
     if (a2p) { ring_e2 = 1; while (ring_e2 <= e2) ring_e2 *= 2; }
+    if (lin) ring_e = 0;
     if (ring_m > 32 || ring_e > 16 || ring_e2 > 16) return false;
     {
         auto gcd = [](int a_, int b_) { while (b_) { const int t = a_ % b_; a_ = b_; b_ = t; } return a_; };
@@ -1018,6 +1104,8 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
     size_t cap_per_cu = (p.flags & AIM_FLAG_BACKTRACE) ? AIM_GROUP_MAX_PER_CU : AIM_GROUP_MAX_PER_CU + 4;   // CIGAR variants: 82-96 VGPRs (history addressing) = 5 per SIMD
     // A2P: the CIGAR variants sit at 92-104 VGPRs (their own bound, AIM_GROUP_A2P_MIN_WAVES per SIMD), the score-only ones at 79-90 (5 per SIMD)
     if (a2p) cap_per_cu = (p.flags & AIM_FLAG_BACKTRACE) ? 4 * AIM_GROUP_A2P_MIN_WAVES : AIM_GROUP_MAX_PER_CU;
+    // LIN: the score-only variants sit at 61-70 VGPRs, the CIGAR ones at 68-80: six wavefronts per SIMD (AIM_GROUP_LIN_MIN_WAVES) either way
+    if (lin) cap_per_cu = 4 * AIM_GROUP_LIN_MIN_WAVES;
     uint32_t per_cu = (uint32_t)std::min<size_t>(cap_per_cu, lds_fit);
     if (per_cu > 16) per_cu &= ~3u;
     if (kn.group_per_cu >= 0) per_cu = (uint32_t)std::min<size_t>((size_t)std::max(1, kn.group_per_cu), lds_fit);   // residency sweeps
@@ -1027,18 +1115,18 @@ inline bool wfa_group_plan_rows(const aim_params_t &p, uint32_t n_pairs, const K
     if (gr > need) gr = need < 8u ? 8u : need;
     *grid = gr;
     if (kn.plan_debug)
-        fprintf(stderr, "[aim plan] wfa_group G=%d ring_m=%d ring_e=%d wcap=%d pair_lds=%d B wg_lds=%zu B lds_fit=%zu per_cu=%u grid=%u wlds=%d unit=%d\n", g, ring_m, ring_e,
-                c->wcap, dw * 4, *lds, lds_fit, per_cu, gr, c->wlds, c->unit);
+        fprintf(stderr, "[aim plan] wfa_group G=%d ring_m=%d ring_e=%d wcap=%d pair_lds=%d B wg_lds=%zu B lds_fit=%zu per_cu=%u grid=%u wlds=%d unit=%d%s\n", g, ring_m, ring_e,
+                c->wcap, dw * 4, *lds, lds_fit, per_cu, gr, c->wlds, c->unit, lin ? " linear" : "");
     // BACKTRACE: the per-pair history region (GroupCfg). One row of the pool per score (in units): narrow rows -- the image of the LDS
     // row (wlds cells; a pair whose wavefront outgrows it leaves for the to-do list before anything of the offending score is stored);
     // one home per diagonal -- row s holds the 2s+1 diagonals a wavefront of score s can reach at most.
     {
         const uint64_t rows = (uint64_t)p.max_score / (uint64_t)c->unit + 2;
         const uint64_t cells = c->wlds != c->wcap ? rows * (uint64_t)c->wlds : rows * rows + rows * (uint64_t)(c->efpb + c->eftb);
-        const uint64_t cell_b = a2p ? 16 : 8;                 // A2P: {M, I1, D1, I2, D2, -, -, -}
+        const uint64_t cell_b = a2p ? 16 : lin ? 2 : 8;       // A2P: {M, I1, D1, I2, D2, -, -, -}; LIN: {M}
         if (cells * cell_b > (1ull << 30)) return false;
         c->pool_off = (int)(sizeof(TbHead) + (size_t)rows * sizeof(TbRow));
-        c->pool_cap = (int)cells;                             // cells of 8 bytes {M, I, D, -} (A2P: 16 bytes)
+        c->pool_cap = (int)cells;                             // cells of 8 bytes {M, I, D, -} (A2P: 16 bytes, LIN: 2)
         c->runs_off = (int)((c->pool_off + (uint64_t)c->pool_cap * cell_b + 15) & ~15ull);
         c->runs_cap = 2 * p.max_score + 16;
         c->hist_pair_bytes = (c->runs_off + c->runs_cap * 4 + 255) & ~255;
@@ -1058,6 +1146,8 @@ inline bool wfa_group_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs 
 {
     if ((p.flags & AIM_FLAG_ENDSFREE) && (p.flags & AIM_FLAG_REDUCE)) return false;
     if ((p.flags & AIM_FLAG_AFFINE2P) && (p.flags & (AIM_FLAG_REDUCE | AIM_FLAG_ENDSFREE))) return false;
+    if ((p.flags & AIM_FLAG_LINEAR) && (p.flags & (AIM_FLAG_REDUCE | AIM_FLAG_ENDSFREE | AIM_FLAG_AFFINE2P))) return false;
+    if (p.flags & AIM_FLAG_LINEAR) return wfa_group_plan_rows(p, n_pairs, kn, packed, kn.group_wlds, c, G, grid, lds, hist_pair_bytes);
     if (p.flags & AIM_FLAG_AFFINE2P) return wfa_group_plan_rows(p, n_pairs, kn, packed, kn.group_wlds, c, G, grid, lds, hist_pair_bytes, 0, 0, o2, e2);
     if (p.flags & AIM_FLAG_ENDSFREE) return wfa_group_plan_rows(p, n_pairs, kn, packed, -1, c, G, grid, lds, hist_pair_bytes, efpb, eftb);
     int rows = kn.group_wlds;
@@ -1077,6 +1167,10 @@ void wfa_group_tb_launch(const aim_params_t &p, const GroupCfg &c, uint32_t n_pa
     const uint32_t grid = (n_pairs + kWave - 1) / kWave;
     if (p.flags & AIM_FLAG_AFFINE2P) {   // (ops rows only, as ends-free; never modulo rows)
         hipLaunchKernelGGL((wfa_group_tb_kernel<false, false, false, true>), dim3(grid), dim3(kWave), 0, s, ka, c);
+        return;
+    }
+    if (p.flags & AIM_FLAG_LINEAR) {   // (ops rows only, as affine2p; never modulo rows)
+        hipLaunchKernelGGL((wfa_group_tb_kernel<false, false, false, false, true>), dim3(grid), dim3(kWave), 0, s, ka, c);
         return;
     }
     if (p.flags & AIM_FLAG_ENDSFREE) {   // (ops rows only: the plan never fuses the run output of an ends-free launch, aim_capi.hip)
@@ -1136,6 +1230,25 @@ void wfa_group_launch(const aim_params_t &p, int G, const GroupCfg &c, uint32_t 
         default: break;
         }
 #undef AIM_GRP_A2P
+        return;
+    }
+    if (p.flags & AIM_FLAG_LINEAR) {   // (never with the reduction, never with modulo rows)
+#define AIM_GRP_LIN(GG)                                                                                                              \
+    do {                                                                                                                             \
+        if (bt) hipLaunchKernelGGL((wfa_group_kernel<GG, false, true, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);  \
+        else hipLaunchKernelGGL((wfa_group_kernel<GG, false, false, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);    \
+    } while (0)
+        switch (G) {
+        case 1: AIM_GRP_LIN(1); break;
+        case 2: AIM_GRP_LIN(2); break;
+        case 4: AIM_GRP_LIN(4); break;
+        case 8: AIM_GRP_LIN(8); break;
+        case 16: AIM_GRP_LIN(16); break;
+        case 32: AIM_GRP_LIN(32); break;
+        case 64: AIM_GRP_LIN(64); break;
+        default: break;
+        }
+#undef AIM_GRP_LIN
         return;
     }
 #define AIM_GRP(GG)                                                                                                     \

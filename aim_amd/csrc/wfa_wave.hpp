@@ -30,6 +30,12 @@
 // pool region always holds all five (M, I1, D1, I2, D2 at off_m + comp * len),
 // so WfMeta keeps its 32 bytes and the I2 / D2 offsets are derived.  An absent
 // piece-2 component reads as NULL.  The walk tests piece 1 before piece 2.
+//
+// LIN (AIM_FLAG_LINEAR, never with REDUCE, EF or A2P): gap-linear.  M only:
+// M[s][k] = max(M[s-x][k] + 1, M[s-g][k-1] + 1, M[s-g][k+1]), then extend; an
+// LDS slot and a score's pool region hold the M row alone, and every NULL
+// reads as NULL.  The walk tests D, then I, then X (wfa_group.hpp's
+// group_tb_walk_lin, same CIGAR bytes).
 #pragma once
 
 #include "aim_device.hpp"
@@ -92,10 +98,10 @@ __device__ __forceinline__ int wf_extend_count(PtrT P, PtrT T, int v, int h, int
     return count;
 }
 
-template <bool BT, bool REDUCE, bool SEQ_LDS, bool EF = false, bool A2P = false>
+template <bool BT, bool REDUCE, bool SEQ_LDS, bool EF = false, bool A2P = false, bool LIN = false>
 __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
 {
-    constexpr int NC = A2P ? 5 : 3;          // components per wavefront: M, I, D (A2P: + I2, D2)
+    constexpr int NC = A2P ? 5 : LIN ? 1 : 3;   // components per wavefront: M, I, D (A2P: + I2, D2; LIN: M alone)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     debug_poison_lds(a, smem);
     const int lane = threadIdx.x;
@@ -315,11 +321,12 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
             ms.flags = mo.flags = me.flags = 0;
             if (s_sub >= 0) ms = wf_get_meta(ctx, s_sub);
             if (s_o >= 0) mo = wf_get_meta(ctx, s_o);
-            if (s_e >= 0) me = wf_get_meta(ctx, s_e);
+            if (!LIN && s_e >= 0) me = wf_get_meta(ctx, s_e);
             const bool m_sub_null = (s_sub < 0) || !(ms.flags & WF_PRESENT) || (ms.flags & WF_MNULL);
             const bool m_o_null = (s_o < 0) || !(mo.flags & WF_PRESENT) || (mo.flags & WF_MNULL);
-            const bool i_e_null = (s_e < 0) || !(me.flags & WF_PRESENT) || !(me.flags & WF_HASI) || (me.flags & WF_INULL);
-            const bool d_e_null = (s_e < 0) || !(me.flags & WF_PRESENT) || !(me.flags & WF_HASD) || (me.flags & WF_DNULL);
+            // (LIN: no I / D components; I and D of a cell come from M at s - g, the "open" source, with o = 0)
+            const bool i_e_null = LIN || (s_e < 0) || !(me.flags & WF_PRESENT) || !(me.flags & WF_HASI) || (me.flags & WF_INULL);
+            const bool d_e_null = LIN || (s_e < 0) || !(me.flags & WF_PRESENT) || !(me.flags & WF_HASD) || (me.flags & WF_DNULL);
             const bool i_out_null = m_o_null && i_e_null;
             const bool d_out_null = m_o_null && d_e_null;
             // A2P: piece 2's sources
@@ -353,7 +360,7 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
             const int lo = A2P ? min(min(min(sub_lo, o_lo), e_lo), min(o2_lo, e2_lo)) - 1 : min(min(sub_lo, o_lo), e_lo) - 1;
             const int hi = A2P ? max(max(max(sub_hi, o_hi), e_hi), max(o2_hi, e2_hi)) + 1 : max(max(sub_hi, o_hi), e_hi) + 1;
             const int len = hi - lo + 1;
-            const int narr = A2P ? 5 : 1 + (d_out_null ? 0 : 1) + (i_out_null ? 0 : 1);   // (A2P: all five rows, at fixed places)
+            const int narr = A2P ? 5 : LIN ? 1 : 1 + (d_out_null ? 0 : 1) + (i_out_null ? 0 : 1);   // (A2P: all five rows, at fixed places)
             // allocate_new_score, wfa.c:143-183: an LDS slot when the wavefront fits one; an HBM pool
             // region when it does not, and always with BACKTRACE (history)
             const bool inlds = ring_slots > 0 && len <= slot_w;
@@ -382,6 +389,8 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
                 cur.flags |= (i2_out_null ? 0 : WF_HASI2) | (d2_out_null ? 0 : WF_HASD2);
                 cur.off_i = in_pool ? pool_used + len : -1;
                 cur.off_d = in_pool ? pool_used + 2 * len : -1;
+            } else if constexpr (LIN) {
+                cur.off_i = cur.off_d = -1;
             } else {
                 cur.off_d = (d_out_null || !in_pool) ? -1 : pool_used + len;
                 cur.off_i = (i_out_null || !in_pool) ? -1 : pool_used + len * (d_out_null ? 1 : 2);
@@ -392,6 +401,14 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
             auto compute_row = [&](const awf_t *r_mo, const awf_t *r_ie, const awf_t *r_de, const awf_t *r_ms, awf_t *om, awf_t *oi,
                                    awf_t *od, const awf_t *r_mo2, const awf_t *r_ie2, const awf_t *r_de2, awf_t *oi2, awf_t *od2) {
                 for (int k = lo + lane; k <= hi; k += kWave) {
+                    if constexpr (LIN) {   // M only; out of range: NULL (wfa_group_kernel computes the same offsets)
+                        const int ins_g = (!m_o_null && o_lo <= k - 1 && k - 1 <= o_hi) ? (int)r_mo[k - 1] : kAwfNull;
+                        const int ins_l = ins_g == kAwfNull ? kAwfNull : (int)(awf_t)(ins_g + 1);
+                        const int del_l = (!m_o_null && o_lo <= k + 1 && k + 1 <= o_hi) ? (int)r_mo[k + 1] : kAwfNull;
+                        const int sub_l = (!m_sub_null && sub_lo <= k && k <= sub_hi) ? (int)(awf_t)(r_ms[k] + 1) : kAwfNull;
+                        om[k - lo] = (awf_t)max(del_l, max(sub_l, ins_l));
+                        continue;
+                    }
                     int ins = -10;
                     if (!i_out_null) {
                         const int ins_g = (!m_o_null && o_lo <= k - 1 && k - 1 <= o_hi) ? (int)r_mo[k - 1] : kAwfNull;
@@ -492,7 +509,7 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
                 WfMeta mo, me, mx;
                 mo.flags = me.flags = mx.flags = 0;
                 if (s_o >= 0) mo = ctx.gmeta[s_o];
-                if (s_e >= 0) me = ctx.gmeta[s_e];
+                if (!LIN && s_e >= 0) me = ctx.gmeta[s_e];   // (LIN: no I / D components: D, then I, then X, all from M)
                 if (s_x >= 0 && bt == BT_M) mx = ctx.gmeta[s_x];
                 int del_ext = kAwfNull, del_open = kAwfNull, ins_ext = kAwfNull, ins_open = kAwfNull, misms = kAwfNull;
                 if (A2P ? (bt == BT_M || bt == BT_D) : bt != BT_I) {   // (A2P: not in the piece-2 states)
@@ -609,12 +626,13 @@ inline int wfa_wave_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs &k
 {
     const bool bt = p.flags & AIM_FLAG_BACKTRACE;
     const bool a2p = p.flags & AIM_FLAG_AFFINE2P;
+    const bool lin = p.flags & AIM_FLAG_LINEAR;
     const uint64_t ms = (uint64_t)p.max_score;
     // ends-free: every wavefront is up to PB + TB diagonals wider (the free lengths clamp to the pairs' lengths <= READ_SIZE)
     const uint64_t wide = (uint64_t)std::min(pb, p.read_size) + (uint64_t)std::min(tb, p.read_size);
     w->wide = wide;
-    // affine2p: five rows per wavefront (M, I1, D1, I2, D2) and a live window of max(x, o1+e1, o2+e2) + 1 scores
-    const uint64_t nc = a2p ? 5 : 3;
+    // affine2p: five rows per wavefront (M, I1, D1, I2, D2) and a live window of max(x, o1+e1, o2+e2) + 1 scores; gap-linear: M alone
+    const uint64_t nc = a2p ? 5 : lin ? 1 : 3;
     const int Rw = std::max(std::max(p.mismatch, p.gap_o + p.gap_e), a2p ? o2 + e2 : 0);
     const uint64_t full = nc * (ms + 2) * (ms + 2 + wide) + 64;
     uint64_t cap;
@@ -693,9 +711,17 @@ void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds,
         if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, true, false, true>), dim3(grid), dim3(kWave), lds, s, ka);  \
         else hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka);         \
     } while (0)
+#define AIM_WFW_LIN(BTV)                                                                                                \
+    do {                                                                                                                \
+        if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, true, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka);  \
+        else hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka);         \
+    } while (0)
     if (ka.p.flags & AIM_FLAG_AFFINE2P) {   // (validate_params: never with REDUCE or ENDSFREE)
         if (bt) AIM_WFW_A2P(true);
         else AIM_WFW_A2P(false);
+    } else if (ka.p.flags & AIM_FLAG_LINEAR) {   // (validate_params: never with REDUCE, ENDSFREE or AFFINE2P)
+        if (bt) AIM_WFW_LIN(true);
+        else AIM_WFW_LIN(false);
     } else if (ka.p.flags & AIM_FLAG_ENDSFREE) {   // (validate_params: never with REDUCE)
         if (bt) AIM_WFW_EF(true);
         else AIM_WFW_EF(false);
@@ -706,6 +732,7 @@ void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds,
 #undef AIM_WFW
 #undef AIM_WFW_EF
 #undef AIM_WFW_A2P
+#undef AIM_WFW_LIN
 }
 #else
 void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s);

@@ -12,8 +12,8 @@ import math
 import numpy as np
 
 from . import capi
-from .capi import (ALGO_BY_NAME, ALGO_NW, ALGO_SWG, ALGO_WFA, FLAG_AFFINE2P, FLAG_BACKTRACE, FLAG_ENDSFREE, FLAG_REDUCE, FLAG_REQ8,
-                   FLAG_RES8, FLAG_SWG_W16, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
+from .capi import (ALGO_BY_NAME, ALGO_NW, ALGO_SWG, ALGO_WFA, FLAG_AFFINE2P, FLAG_BACKTRACE, FLAG_ENDSFREE, FLAG_LINEAR, FLAG_REDUCE,
+                   FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
                    Params, params_ref)
 
 
@@ -36,11 +36,13 @@ def features():
 
 
 def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=1, gap=4, backtrace=False,
-                reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None, gap2=None):
+                reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None, gap2=None, linear=False):
     """`gap` is the launchers' single NW gap cost (run-nw-pim-wram.py: -DGAP_I = -DGAP_D); `gap_i` / `gap_d` set the two macros of
     nw.c:67-153 apart (NW/DPU-WRAM/common/common.h GAP_I, GAP_D). `ends_free=(PB, PE, TB, TE)`: ends-free WFA (AIM_FLAG_ENDSFREE);
     returns an EndsFreeParams then, which every call below accepts like Params. `gap2=(O2, E2)`: dual-cost gap-affine WFA
-    (AIM_FLAG_AFFINE2P, gap_o / gap_e are piece 1); returns an Affine2pParams. The two cannot be combined."""
+    (AIM_FLAG_AFFINE2P, gap_o / gap_e are piece 1); returns an Affine2pParams. The two cannot be combined. `linear=True`: gap-linear
+    WFA (AIM_FLAG_LINEAR): a mismatch costs `mismatch`, every gap base `gap_e`, and gap_o is set to 0; not with ends_free, gap2 or
+    reduce."""
     a = ALGO_BY_NAME[algo] if isinstance(algo, str) else algo
     gap_i = gap if gap_i is None else gap_i
     gap_d = gap if gap_d is None else gap_d
@@ -48,6 +50,11 @@ def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=
     flags |= (FLAG_REQ8 if req8 else 0) | (FLAG_RES8 if res8 else 0)
     if ends_free is not None and gap2 is not None:
         raise ValueError("ends_free and gap2 cannot be combined")
+    if linear:
+        for name, given in (("ends_free", ends_free is not None), ("gap2", gap2 is not None), ("reduce", reduce)):
+            if given:
+                raise ValueError("linear cannot be combined with %s" % name)
+        return Params(a, match, mismatch, 0, gap_e, gap_i, gap_d, max_score, read_size, flags | FLAG_LINEAR)
     if gap2 is not None:
         o2, e2 = (int(x) for x in gap2)
         return Affine2pParams(Params(a, match, mismatch, gap_o, gap_e, gap_i, gap_d, max_score, read_size, flags | FLAG_AFFINE2P), o2, e2)

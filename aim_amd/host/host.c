@@ -21,6 +21,8 @@
  *                   (AIM_FLAG_ENDSFREE, include/aim_hip.h); the output format is unchanged
  *     --gap2 O2,E2  (WFA) dual-cost gap-affine: a gap of length L costs min(gap_o + L*gap_e, O2 + L*E2)
  *                   (AIM_FLAG_AFFINE2P, include/aim_hip.h); not with --ends-free or --reduce; the output format is unchanged
+ *     --linear      (WFA) gap-linear: a mismatch costs --mismatch, every gap base --gap-e, and gap_o is 0 (--mismatch 1 --gap-e 1:
+ *                   edit distance; AIM_FLAG_LINEAR, include/aim_hip.h); not with --gap2, --ends-free or --reduce
  *     --packed-input  <input> is a packed batch file (written by --pack-only or `python -m aim_amd.gen_dataset --packed`):
  *                   2 bits per base + raw side list, ready for the device; no text is parsed
  * The UPMEM dispatch (dpu_alloc/dpu_load/dpu_push_xfer/dpu_launch) is replaced
@@ -933,6 +935,7 @@ int main(int argc, char *argv[])
         const char *v = (i + 1 < argc) ? argv[i + 1] : NULL;
         if (!strcmp(f, "--backtrace")) p.flags |= AIM_FLAG_BACKTRACE;
         else if (!strcmp(f, "--reduce")) p.flags |= AIM_FLAG_REDUCE;
+        else if (!strcmp(f, "--linear")) p.flags |= AIM_FLAG_LINEAR;
         else if (!strcmp(f, "--swg-w16")) p.flags |= AIM_FLAG_SWG_W16;
         else if (!strcmp(f, "--no-pack")) no_pack = 1;       /* ship ASCII rows like the reference (host.c:258-268) */
         else if (!strcmp(f, "--full-ops")) full_ops = 1;     /* gather result_t + ops rows like the reference (host.c:316-326) */
@@ -1014,6 +1017,13 @@ int main(int argc, char *argv[])
     if ((p.flags & AIM_FLAG_AFFINE2P) && p.algo != AIM_ALGO_WFA) { fprintf(stderr, "--gap2 needs --algo wfa\n"); exit(1); }
     if ((p.flags & AIM_FLAG_AFFINE2P) && (p.flags & AIM_FLAG_ENDSFREE)) { fprintf(stderr, "--gap2 cannot be combined with --ends-free\n"); exit(1); }
     if ((p.flags & AIM_FLAG_AFFINE2P) && (p.flags & AIM_FLAG_REDUCE)) { fprintf(stderr, "--gap2 cannot be combined with --reduce\n"); exit(1); }
+    if (p.flags & AIM_FLAG_LINEAR) {
+        if (p.algo != AIM_ALGO_WFA) { fprintf(stderr, "--linear needs --algo wfa\n"); exit(1); }
+        if (p.flags & AIM_FLAG_AFFINE2P) { fprintf(stderr, "--linear cannot be combined with --gap2\n"); exit(1); }
+        if (p.flags & AIM_FLAG_ENDSFREE) { fprintf(stderr, "--linear cannot be combined with --ends-free\n"); exit(1); }
+        if (p.flags & AIM_FLAG_REDUCE) { fprintf(stderr, "--linear cannot be combined with --reduce\n"); exit(1); }
+        p.gap_o = 0;
+    }
     if (packed_input && (no_pack || pack_only)) { fprintf(stderr, "--packed-input cannot be combined with --no-pack / --pack-only\n"); exit(1); }
 #if defined(__x86_64__)
     g_simd = __builtin_cpu_supports("sse4.1") && __builtin_cpu_supports("ssse3") && __builtin_cpu_supports("bmi2");

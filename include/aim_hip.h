@@ -109,6 +109,13 @@ typedef struct aim_affine2p_params {
     int32_t gap_o2, gap_e2;   /* piece 2: each > 0 */
 } aim_affine2p_params_t;
 
+/* AIM_FLAG_LINEAR (WFA only; not with AIM_FLAG_REDUCE, AIM_FLAG_ENDSFREE or AIM_FLAG_AFFINE2P): gap-linear penalties, read
+ * from aim_params_t itself (no extension struct).  A match costs 0, a mismatch `mismatch` (x > 0) and every inserted or deleted
+ * base `gap_e` (g > 0); gap_o must be 0 and match <= 0.  The score is the minimum cost of a global alignment; x = g = 1 is the
+ * edit distance.  MAX_SCORE, the over-cap result and the ops-row contract are global WFA's.  Without this flag gap_o = 0 is
+ * rejected as before.  Check aim_features() & AIM_FEATURE_LINEAR first: older libraries ignore unknown flags. */
+#define AIM_FLAG_LINEAR 0x80u
+
 /* Per-pair descriptor: byte-compatible with the NW/SWG request_t
  * (NW/DPU-WRAM/common/common.h:114-120).  The WFA variant of the reference
  * uses int16 lengths (WFA/DPU-WRAM/common/common.h:172-177); a binding widens
@@ -154,6 +161,7 @@ int aim_abi_version(void);
 /* Capabilities added without an ABI version change: a binding tests a bit before it sets the matching flag. */
 #define AIM_FEATURE_ENDSFREE 0x1u /* AIM_FLAG_ENDSFREE is honoured */
 #define AIM_FEATURE_AFFINE2P 0x2u /* AIM_FLAG_AFFINE2P is honoured */
+#define AIM_FEATURE_LINEAR 0x4u   /* AIM_FLAG_LINEAR is honoured */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
