@@ -21,6 +21,8 @@ FLAG_LINEAR = 128      # gap-linear WFA on Params itself (gap_o = 0, gap_e per g
 FEATURE_ENDSFREE = 1   # aim_features(): AIM_FLAG_ENDSFREE is honoured
 FEATURE_AFFINE2P = 2   # aim_features(): AIM_FLAG_AFFINE2P is honoured
 FEATURE_LINEAR = 4     # aim_features(): AIM_FLAG_LINEAR is honoured
+FLAG_WFA_W32 = 256     # WFA with int32 wavefront offsets (AFFINE_WAVEFRONT_W32): read_size up to 2^24
+FEATURE_WFA_W32 = 8    # aim_features(): AIM_FLAG_WFA_W32 is honoured
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
 
 

@@ -228,6 +228,8 @@ inline Affine2p affine2p(const aim_params_t &p)
 }
 // AIM_FLAG_LINEAR: gap-linear WFA on aim_params_t itself (no extension): gap_o = 0, gap_e is the cost of one gap base.
 inline bool is_linear(const aim_params_t &p) { return (p.flags & AIM_FLAG_LINEAR) != 0; }
+// AIM_FLAG_WFA_W32: int32 wavefront offsets (AFFINE_WAVEFRONT_W32), wfa_wave_kernel only.
+inline bool is_w32(const aim_params_t &p) { return (p.flags & AIM_FLAG_WFA_W32) != 0; }
 // The params as this library keeps them: room for either extension, and the extension copied only when a flag says it exists.
 union XParams {
     aim_params_t base;
@@ -257,6 +259,7 @@ int validate_params(const aim_params_t &p)
         if (is_endsfree(p)) return fail(AIM_EINVAL, "AIM_FLAG_LINEAR cannot be combined with AIM_FLAG_ENDSFREE");
         if (is_affine2p(p)) return fail(AIM_EINVAL, "AIM_FLAG_LINEAR cannot be combined with AIM_FLAG_AFFINE2P");
     }
+    if (is_w32(p) && p.algo != AIM_ALGO_WFA) return fail(AIM_EINVAL, "AIM_FLAG_WFA_W32 needs AIM_ALGO_WFA");
     if (p.read_size <= 0 || (p.read_size & 7)) return fail(AIM_EINVAL, "read_size must be a positive multiple of 8 (got %d)", p.read_size);
     if (p.max_score < 0) return fail(AIM_EINVAL, "max_score must be >= 0");
     if ((p.flags & AIM_FLAG_REQ8) && p.read_size >= 32760)
@@ -294,6 +297,11 @@ int validate_params(const aim_params_t &p)
         if (p.flags & AIM_FLAG_REDUCE) return fail(AIM_EINVAL, "AIM_FLAG_AFFINE2P cannot be combined with AIM_FLAG_REDUCE");
         const Affine2p g = affine2p(p);
         if (g.o2 <= 0 || g.e2 <= 0) return fail(AIM_EINVAL, "affine2p penalties must be gap_o2, gap_e2 > 0 (got %d,%d)", g.o2, g.e2);
+    }
+    // AIM_FLAG_WFA_W32: int32 offsets (AFFINE_WAVEFRONT_W32, common.h:101-104); lengths are int32 as for GenASM
+    if (is_w32(p)) {
+        if (p.read_size > (1 << 24)) return fail(AIM_EINVAL, "read_size must be <= 2^24");
+        return AIM_OK;
     }
     // the reference's lengths, WFA offsets and NW / SWG cells are int16 (WFA/DPU-WRAM/common/common.h:98-100, 174-175): what it admits
     // is < 32 767; READ_SIZE is a multiple of 8
@@ -381,6 +389,13 @@ bool plan_wfa_group(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
 // time for the global case): wfa_group where LDS admits the wider rows / deeper rings, else wfa_wave.
 int plan_wfa(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, uint32_t mode, Plan *pl)
 {
+    if (is_w32(p)) {
+        // int32 offsets exist in wfa_wave_kernel only (wfa_group / the lane kernels keep int16 rows): it runs alone at every READ_SIZE
+        // and takes non-ACGT pairs itself, so there is no fallback stage. Below 32760 this costs speed and changes no result.
+        int rc = plan_wfa_wave(p, n_pairs, kn, budget, &pl->main);
+        pl->scratch_total = stage_bytes(pl->main);
+        return rc;
+    }
     const bool bt = p.flags & AIM_FLAG_BACKTRACE;
     const bool lanes = !is_endsfree(p) && !is_affine2p(p) && !is_linear(p) && !kn.force_wave && !kn.no_lane;   // a lane kernel may run
     const bool lane_pk_ok = lanes && !kn.no_lane_pk && aim::wfa_lane_packed_supported(p, !kn.no_lane_ext);
@@ -594,8 +609,8 @@ int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint6
     } else if (is_linear(p)) {
         snprintf(efs, sizeof efs, " linear");
     }
-    return snprintf(out, cap, "%s n=%u grid=%u block=%u lds=%zu scratch=%zu budget=%llu%s%s", kernel_name(pl, p), n_pairs, pl.main.grid,
-                    pl.main.block, pl.main.lds, pl.scratch_total, (unsigned long long)budget, extra, efs);
+    return snprintf(out, cap, "%s n=%u grid=%u block=%u lds=%zu scratch=%zu budget=%llu%s%s%s", kernel_name(pl, p), n_pairs, pl.main.grid,
+                    pl.main.block, pl.main.lds, pl.scratch_total, (unsigned long long)budget, extra, efs, is_w32(p) ? " w32" : "");
 }
 
 int make_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, Plan *pl, uint32_t mode = 0u)
@@ -1026,7 +1041,7 @@ int launch_on_slot(aim_set *set, aim_device_ctx &d, aim_slot &s, uint32_t mode =
 extern "C" {
 
 int aim_abi_version(void) { return AIM_ABI_VERSION; }
-uint32_t aim_features(void) { return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR; }
+uint32_t aim_features(void) { return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32; }
 const char *aim_last_error(void) { return g_err; }
 
 int aim_device_count(int *count)

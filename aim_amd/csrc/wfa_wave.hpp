@@ -36,14 +36,22 @@
 // LDS slot and a score's pool region hold the M row alone, and every NULL
 // reads as NULL.  The walk tests D, then I, then X (wfa_group.hpp's
 // group_tb_walk_lin, same CIGAR bytes).
+//
+// OFF (AIM_FLAG_WFA_W32): the offset type.  int16_t is the reference as built
+// (AFFINE_WAVEFRONT_W16, common.h:92-100: NULL = INT16_MIN/2, every (awf_t)
+// cast a deliberate int16 wrap); int32_t is its AFFINE_WAVEFRONT_W32 branch
+// (common.h:101-104: NULL = INT32_MIN/2), which lifts the READ_SIZE < 32760 cap.
+// The LDS ring, the HBM pool, the wrap casts, the NULL tests and the traceback
+// all take OFF; nothing else changes.
 #pragma once
 
 #include "aim_device.hpp"
 
 namespace aim {
 
-typedef int16_t awf_t;               // AFFINE_WAVEFRONT_W16, common.h:92-100
-constexpr int kAwfNull = -16384;     // AFFINE_WAVEFRONT_OFFSET_NULL = INT16_MIN/2
+// AFFINE_WAVEFRONT_OFFSET_NULL of each offset type: INT16_MIN/2 (W16, common.h:98) / INT32_MIN/2 (W32, common.h:102)
+template <typename OFF>
+constexpr int awf_null() { return sizeof(OFF) == 2 ? -16384 : INT32_MIN / 2; }
 
 // wfa_component (common.h:126-138) with pool offsets instead of pointers.
 struct __attribute__((aligned(16))) WfMeta {
@@ -61,7 +69,6 @@ constexpr int kMetaRing = 64;        // scores kept in the LDS descriptor ring
 struct WfaWaveCtx {
     WfMeta *ring;        // LDS, kMetaRing entries
     WfMeta *gmeta;       // HBM, meta_cap entries
-    awf_t *pool;         // HBM
     int cur_score;
 };
 
@@ -98,9 +105,14 @@ __device__ __forceinline__ int wf_extend_count(PtrT P, PtrT T, int v, int h, int
     return count;
 }
 
-template <bool BT, bool REDUCE, bool SEQ_LDS, bool EF = false, bool A2P = false, bool LIN = false>
+template <bool BT, bool REDUCE, bool SEQ_LDS, bool EF = false, bool A2P = false, bool LIN = false, typename OFF = int16_t>
 __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
 {
+    static_assert(sizeof(OFF) == 2 || sizeof(OFF) == 4, "offsets are int16_t or int32_t");
+    typedef OFF awf_t;
+    constexpr int kAwfNull = awf_null<OFF>();
+    // pool index sums that may pass 2^31 before they are compared with pool_cap (W32 pools can hold up to 2^31 - 1 entries)
+    typedef typename std::conditional<sizeof(OFF) == 4, int64_t, int>::type pidx_t;
     constexpr int NC = A2P ? 5 : LIN ? 1 : 3;   // components per wavefront: M, I, D (A2P: + I2, D2; LIN: M alone)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     debug_poison_lds(a, smem);
@@ -117,8 +129,7 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
     WfaWaveCtx ctx;
     ctx.ring = ring;
     ctx.gmeta = reinterpret_cast<WfMeta *>(wscr);
-    ctx.pool = reinterpret_cast<awf_t *>(wscr + (uint64_t)a.meta_cap * sizeof(WfMeta));
-    awf_t *pool = ctx.pool;
+    awf_t *pool = reinterpret_cast<awf_t *>(wscr + (uint64_t)a.meta_cap * sizeof(WfMeta));
     const int pool_cap = (int)a.pool_cap;
 
     const int X = a.p.mismatch, OE = a.p.gap_o + a.p.gap_e, E = a.p.gap_e;
@@ -365,7 +376,7 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
             // region when it does not, and always with BACKTRACE (history)
             const bool inlds = ring_slots > 0 && len <= slot_w;
             const bool in_pool = BT || !inlds;
-            if (in_pool && pool_used + len * narr > pool_cap) {
+            if (in_pool && (pidx_t)pool_used + (pidx_t)len * narr > pool_cap) {
                 if (BT) {   // allocate_new(): "out of memory" + exit(1), dpu_allocator_wram.c:19-23
                     status = AIM_PAIR_NOMEM;
                     final_score = score;
@@ -375,7 +386,7 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
                 // The plan never hands a score-only wavefront less than the live window ((R+2) * 3 * (2*MAX_SCORE+3)
                 // entries, make_plan); a wavefront that still does not fit after the wrap would run over the next
                 // workgroup's scratch, so it is reported like the DPU arena's "out of memory" instead.
-                if ((uint32_t)(len * narr) > pool_cap) {
+                if (sizeof(OFF) == 2 ? (uint32_t)(len * narr) > (uint32_t)pool_cap : (pidx_t)len * narr > pool_cap) {
                     status = AIM_PAIR_NOMEM;
                     final_score = score;
                     break;
@@ -627,6 +638,7 @@ inline int wfa_wave_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs &k
     const bool bt = p.flags & AIM_FLAG_BACKTRACE;
     const bool a2p = p.flags & AIM_FLAG_AFFINE2P;
     const bool lin = p.flags & AIM_FLAG_LINEAR;
+    const uint64_t off_b = (p.flags & AIM_FLAG_WFA_W32) ? sizeof(int32_t) : sizeof(int16_t);   // bytes per offset (AIM_FLAG_WFA_W32)
     const uint64_t ms = (uint64_t)p.max_score;
     // ends-free: every wavefront is up to PB + TB diagonals wider (the free lengths clamp to the pairs' lengths <= READ_SIZE)
     const uint64_t wide = (uint64_t)std::min(pb, p.read_size) + (uint64_t)std::min(tb, p.read_size);
@@ -650,14 +662,14 @@ inline int wfa_wave_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs &k
         uint32_t sw = 16;
         while (sw < 2 * (uint32_t)ms + 3 + (uint32_t)wide && sw < 128) sw *= 2;   // 128: keeps 16 workgroups resident per CU at l = 1000 (measured +9 % over 256)
         if (kn.wfa_slotw >= 0) sw = (uint32_t)std::max(16, kn.wfa_slotw) & ~15u;
-        while (sw > 16 && (uint64_t)(R + 1) * nc * sw * 2 > 24 * 1024) sw /= 2;
-        const bool ring_ok = (uint64_t)(R + 1) * nc * sw * 2 <= 24 * 1024 && !kn.wfa_no_ring;
+        while (sw > 16 && (uint64_t)(R + 1) * nc * sw * off_b > 24 * 1024) sw /= 2;
+        const bool ring_ok = (uint64_t)(R + 1) * nc * sw * off_b <= 24 * 1024 && !kn.wfa_no_ring;
         w->ring_slots = ring_ok ? R + 1 : 0;
         w->slot_w = ring_ok ? sw : 0;
     }
     const size_t seq_bytes = 2 * ((size_t)p.read_size + 8);
     w->seq_lds = seq_bytes <= 40 * 1024;
-    const size_t ring_bytes = ((size_t)w->ring_slots * nc * w->slot_w * sizeof(int16_t) + 15) & ~(size_t)15;
+    const size_t ring_bytes = ((size_t)w->ring_slots * nc * w->slot_w * off_b + 15) & ~(size_t)15;
     w->lds = kMetaRing * sizeof(WfMeta) + ring_bytes + (w->seq_lds ? seq_bytes : 0);
     // persistent single-wave workgroups: exactly what is resident (4 waves/SIMD by VGPRs, 160 KiB LDS per CU);
     // a larger grid runs in uneven rounds
@@ -666,7 +678,7 @@ inline int wfa_wave_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs &k
     uint32_t grid = resident_grid(kn, wg_per_cu);
     const uint32_t need = ((n_pairs + 7u) / 8u) * 8u;
     if (grid > need) grid = std::max(8u, need);
-    uint64_t per = (uint64_t)w->meta_cap * sizeof(WfMeta) + cap * sizeof(int16_t);
+    uint64_t per = (uint64_t)w->meta_cap * sizeof(WfMeta) + cap * off_b;
     per = (per + 255) & ~255ull;
     while (grid > 2 * kn.cus && grid > 16 && per * grid > budget) grid = ((grid / 2) + 7u) & ~7u;
     if (per * grid > budget) {
@@ -676,9 +688,9 @@ inline int wfa_wave_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs &k
             // is legal and a pair that outgrows it reports AIM_PAIR_NOMEM (dpu_allocator_wram.c:19-23 "out of memory").
             uint64_t avail = budget / grid;
             if (avail < meta_b + 4096) return kWfaWaveNoPool;
-            cap = (avail - meta_b - 256) / sizeof(int16_t);
+            cap = (avail - meta_b - 256) / off_b;
             if (cap < wide + 1) return kWfaWaveNoScore0;
-            per = (meta_b + cap * sizeof(int16_t) + 255) & ~255ull;
+            per = (meta_b + cap * off_b + 255) & ~255ull;
         } else {
             // Score-only: the pool is a ring and must keep its full live window (a shrunken ring silently overwrites
             // wavefronts score-x / score-o-e / score-e still read). Fewer workgroups instead, down to one per XCD.
@@ -694,27 +706,28 @@ inline int wfa_wave_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs &k
 
 // Kernels are instantiated in ONE translation unit (tu_*.hip defines AIM_TU_WFA_WAVE); every other includer sees the declaration only.
 #ifdef AIM_TU_WFA_WAVE
-void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s)
+template <typename OFF>
+void wfa_wave_launch_off(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s)
 {
 #define AIM_WFW(BTV, REDV)                                                                                              \
     do {                                                                                                                \
-        if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, REDV, true>), dim3(grid), dim3(kWave), lds, s, ka);       \
-        else hipLaunchKernelGGL((wfa_wave_kernel<BTV, REDV, false>), dim3(grid), dim3(kWave), lds, s, ka);              \
+        if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, REDV, true, false, false, false, OFF>), dim3(grid), dim3(kWave), lds, s, ka);  \
+        else hipLaunchKernelGGL((wfa_wave_kernel<BTV, REDV, false, false, false, false, OFF>), dim3(grid), dim3(kWave), lds, s, ka);         \
     } while (0)
 #define AIM_WFW_EF(BTV)                                                                                                 \
     do {                                                                                                                \
-        if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, true, true>), dim3(grid), dim3(kWave), lds, s, ka);  \
-        else hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka);         \
+        if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, true, true, false, false, OFF>), dim3(grid), dim3(kWave), lds, s, ka);  \
+        else hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, false, true, false, false, OFF>), dim3(grid), dim3(kWave), lds, s, ka);         \
     } while (0)
 #define AIM_WFW_A2P(BTV)                                                                                                \
     do {                                                                                                                \
-        if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, true, false, true>), dim3(grid), dim3(kWave), lds, s, ka);  \
-        else hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka);         \
+        if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, true, false, true, false, OFF>), dim3(grid), dim3(kWave), lds, s, ka);  \
+        else hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, false, false, true, false, OFF>), dim3(grid), dim3(kWave), lds, s, ka);         \
     } while (0)
 #define AIM_WFW_LIN(BTV)                                                                                                \
     do {                                                                                                                \
-        if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, true, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka);  \
-        else hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka);         \
+        if (seq_lds) hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, true, false, false, true, OFF>), dim3(grid), dim3(kWave), lds, s, ka);  \
+        else hipLaunchKernelGGL((wfa_wave_kernel<BTV, false, false, false, false, true, OFF>), dim3(grid), dim3(kWave), lds, s, ka);         \
     } while (0)
     if (ka.p.flags & AIM_FLAG_AFFINE2P) {   // (validate_params: never with REDUCE or ENDSFREE)
         if (bt) AIM_WFW_A2P(true);
@@ -733,6 +746,12 @@ void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds,
 #undef AIM_WFW_EF
 #undef AIM_WFW_A2P
 #undef AIM_WFW_LIN
+}
+
+void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s)
+{
+    if (ka.p.flags & AIM_FLAG_WFA_W32) wfa_wave_launch_off<int32_t>(bt, red, seq_lds, grid, lds, ka, s);
+    else wfa_wave_launch_off<int16_t>(bt, red, seq_lds, grid, lds, ka, s);
 }
 #else
 void wfa_wave_launch(bool bt, bool red, bool seq_lds, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s);

@@ -28,7 +28,8 @@ def gen(seed, first, n, length, error, read_size, flank, long_indel=0):
 
 def write_packed(out, seed, num_pairs, length, error, batch, flank=0, long_indel=0):
     """Packed batch file (aim_amd/host/host.c, pkfile_hdr_t): 64-byte header, then per batch {n, ascii = 0, n_raw, READ_SIZE} +
-    aim_request8_t[n] + packed patterns + packed texts + raw side list (indices, ASCII patterns, ASCII texts)."""
+    aim_request8_t[n] + packed patterns + packed texts + raw side list (indices, ASCII patterns, ASCII texts). From READ_SIZE 32 760 on
+    (int16 lengths no longer fit) the requests are 16-byte aim_request_t, as the host expects there."""
     import math
     import numpy as np
     read_size = int(math.ceil((length + length * error + 7) / 8)) * 8          # run-*-pim-*.py: READ_SIZE
@@ -38,9 +39,10 @@ def write_packed(out, seed, num_pairs, length, error, batch, flank=0, long_indel
     if flank:
         rs_file = engine.round_up_8(rs_file + 2 * flank)
     batch = max(1, min(batch, max(num_pairs, 1)))
+    req8 = rs_file < 32760
     hdr = np.zeros(64, dtype=np.uint8)
     hdr[:8] = np.frombuffer(b"AIMPK\0\0\1", dtype=np.uint8)
-    hdr[8:24] = np.array([1, rs_file, 8, batch], dtype="<u4").view(np.uint8)
+    hdr[8:24] = np.array([1, rs_file, 8 if req8 else 16, batch], dtype="<u4").view(np.uint8)
     hdr[24:32] = np.array([num_pairs], dtype="<u8").view(np.uint8)
     out.write(hdr.tobytes())
     for first in range(0, num_pairs, batch):
@@ -48,7 +50,7 @@ def write_packed(out, seed, num_pairs, length, error, batch, flank=0, long_indel
         req, pat, txt = gen(seed, first, n, length, error, read_size, flank, long_indel)
         pp, pt, raw, rawp, rawt = engine.pack_batch(req, pat, txt)
         out.write(np.array([n, 0, len(raw), rs_file], dtype="<u4").tobytes())
-        out.write(engine.to_request8(req).tobytes())
+        out.write((engine.to_request8(req) if req8 else req).tobytes())
         for arr in (pp, pt, raw.astype("<u4"), rawp, rawt):
             out.write(np.ascontiguousarray(arr).tobytes())
 
@@ -75,6 +77,7 @@ def main(argv=None):
     # a text can outgrow the pattern by at most the number of edits; rows are 8-byte multiples like READ_SIZE
     edits = int(-(-a.length * a.error // 1))
     row = (a.length + edits + 1 + 7) // 8 * 8
+    chunk = max(1, min(a.chunk, (256 << 20) // (2 * (row + a.long_indel + 2 * a.flank + 8))))   # long reads: ~256 MiB of rows per chunk
     out = sys.stdout.buffer if a.output == "-" else open(a.output, "wb")
     if a.packed:
         try:
@@ -84,8 +87,8 @@ def main(argv=None):
                 out.close()
         return 0
     try:
-        for first in range(0, a.num_pairs, a.chunk):
-            n = min(a.chunk, a.num_pairs - first)
+        for first in range(0, a.num_pairs, chunk):
+            n = min(chunk, a.num_pairs - first)
             req, pat, txt = gen(a.seed, first, n, a.length, a.error, row, a.flank, a.long_indel)
             out.write(engine.pairs_to_text(req, pat, txt))
     finally:

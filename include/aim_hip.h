@@ -116,6 +116,15 @@ typedef struct aim_affine2p_params {
  * rejected as before.  Check aim_features() & AIM_FEATURE_LINEAR first: older libraries ignore unknown flags. */
 #define AIM_FLAG_LINEAR 0x80u
 
+/* AIM_FLAG_WFA_W32 (WFA only): 32-bit wavefront offsets, the reference's WFA built with -DAFFINE_WAVEFRONT_W32 (offsets int32,
+ * NULL = INT32_MIN / 2) instead of its default AFFINE_WAVEFRONT_W16.  It lifts WFA's read_size < 32760 bound to read_size <= 2^24
+ * (GenASM's); AIM_FLAG_REQ8 still carries int16 lengths and keeps read_size < 32760.  It combines with AIM_FLAG_REDUCE,
+ * AIM_FLAG_ENDSFREE, AIM_FLAG_AFFINE2P, AIM_FLAG_LINEAR, AIM_FLAG_BACKTRACE and AIM_FLAG_RES8 under their own rules.  MAX_SCORE,
+ * the over-cap result, the ops-row contract, the statuses and the CIGAR bytes are unchanged.  Every batch runs on the general
+ * one-pair-per-wavefront kernel: below read_size 32760 the results equal those without the flag and the flag only costs speed.
+ * Check aim_features() & AIM_FEATURE_WFA_W32 first: older libraries ignore unknown flags. */
+#define AIM_FLAG_WFA_W32 0x100u
+
 /* Per-pair descriptor: byte-compatible with the NW/SWG request_t
  * (NW/DPU-WRAM/common/common.h:114-120).  The WFA variant of the reference
  * uses int16 lengths (WFA/DPU-WRAM/common/common.h:172-177); a binding widens
@@ -162,6 +171,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_ENDSFREE 0x1u /* AIM_FLAG_ENDSFREE is honoured */
 #define AIM_FEATURE_AFFINE2P 0x2u /* AIM_FLAG_AFFINE2P is honoured */
 #define AIM_FEATURE_LINEAR 0x4u   /* AIM_FLAG_LINEAR is honoured */
+#define AIM_FEATURE_WFA_W32 0x8u  /* AIM_FLAG_WFA_W32 is honoured */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
