@@ -23,6 +23,8 @@ FEATURE_AFFINE2P = 2   # aim_features(): AIM_FLAG_AFFINE2P is honoured
 FEATURE_LINEAR = 4     # aim_features(): AIM_FLAG_LINEAR is honoured
 FLAG_WFA_W32 = 256     # WFA with int32 wavefront offsets (AFFINE_WAVEFRONT_W32): read_size up to 2^24
 FEATURE_WFA_W32 = 8    # aim_features(): AIM_FLAG_WFA_W32 is honoured
+FLAG_WFA_BIDIR = 512   # bidirectional WFA with CIGAR: O(MAX_SCORE) scratch per workgroup (global gap-affine, BACKTRACE)
+FEATURE_WFA_BIDIR = 16 # aim_features(): AIM_FLAG_WFA_BIDIR is honoured
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
 
 

@@ -22,6 +22,7 @@
 #include "aim_hip.h"
 #include "aim_device.hpp"
 #include "wfa_wave.hpp"
+#include "wfa_bidir.hpp"
 #include "wfa_lane.hpp"
 #include "wfa_lane_packed.hpp"
 #include "wfa_group.hpp"
@@ -57,7 +58,7 @@ int fail(int code, const char *fmt, ...)
 // ---------------------------------------------------------------------------
 // launch planning
 // ---------------------------------------------------------------------------
-enum KernelId { K_WFA_WAVE = 0, K_WFA_LANE = 1, K_DP_LANE = 2, K_DP_WAVE = 3, K_WFA_GROUP = 4, K_GENASM = 5, K_WFA_LANE_PK = 6, K_DP_STRIP = 7, K_DP_REG = 8, K_DP_GROUP = 9 };
+enum KernelId { K_WFA_WAVE = 0, K_WFA_LANE = 1, K_DP_LANE = 2, K_DP_WAVE = 3, K_WFA_GROUP = 4, K_GENASM = 5, K_WFA_LANE_PK = 6, K_DP_STRIP = 7, K_DP_REG = 8, K_DP_GROUP = 9, K_WFA_BIDIR = 10 };
 
 // What a launch is asked to consume / produce besides the default ABI (ASCII rows in, result_t + ops rows out). A plan
 // honours a mode bit only when its kernel can (Plan::pk / Plan::emits_runs); otherwise the caller runs the conversion
@@ -92,6 +93,7 @@ struct Plan {
     bool pack_first;        // K_WFA_LANE_PK on a batch of ASCII rows: pack_rows_kernel first
     bool pk;                // the kernel reads the packed rows of the batch itself (no unpack pass)
     bool emits_runs;        // the kernel writes aim_cigar_t + runs itself (no ops rows, no cigar_rle_kernel)
+    int bidir_t;            // K_WFA_BIDIR: the base-case threshold T (fb is wfa_wave at MAX_SCORE min(MAX_SCORE, T), run first)
 };
 
 // The AIM_* environment variables, read HERE and nowhere else (see aim::Knobs, aim_device.hpp).
@@ -230,6 +232,8 @@ inline Affine2p affine2p(const aim_params_t &p)
 inline bool is_linear(const aim_params_t &p) { return (p.flags & AIM_FLAG_LINEAR) != 0; }
 // AIM_FLAG_WFA_W32: int32 wavefront offsets (AFFINE_WAVEFRONT_W32), wfa_wave_kernel only.
 inline bool is_w32(const aim_params_t &p) { return (p.flags & AIM_FLAG_WFA_W32) != 0; }
+// AIM_FLAG_WFA_BIDIR: bidirectional WFA with CIGAR (wfa_bidir.hpp).
+inline bool is_bidir(const aim_params_t &p) { return (p.flags & AIM_FLAG_WFA_BIDIR) != 0; }
 // The params as this library keeps them: room for either extension, and the extension copied only when a flag says it exists.
 union XParams {
     aim_params_t base;
@@ -260,6 +264,16 @@ int validate_params(const aim_params_t &p)
         if (is_affine2p(p)) return fail(AIM_EINVAL, "AIM_FLAG_LINEAR cannot be combined with AIM_FLAG_AFFINE2P");
     }
     if (is_w32(p) && p.algo != AIM_ALGO_WFA) return fail(AIM_EINVAL, "AIM_FLAG_WFA_W32 needs AIM_ALGO_WFA");
+    if (is_bidir(p)) {
+        if (p.algo != AIM_ALGO_WFA) return fail(AIM_EINVAL, "AIM_FLAG_WFA_BIDIR needs AIM_ALGO_WFA");
+        if (!(p.flags & AIM_FLAG_BACKTRACE)) return fail(AIM_EINVAL, "AIM_FLAG_WFA_BIDIR needs AIM_FLAG_BACKTRACE (score-only WFA is O(s) already)");
+        if (p.flags & AIM_FLAG_REDUCE) return fail(AIM_EINVAL, "AIM_FLAG_WFA_BIDIR cannot be combined with AIM_FLAG_REDUCE");
+        if (is_endsfree(p)) return fail(AIM_EINVAL, "AIM_FLAG_WFA_BIDIR cannot be combined with AIM_FLAG_ENDSFREE");
+        if (is_affine2p(p)) return fail(AIM_EINVAL, "AIM_FLAG_WFA_BIDIR cannot be combined with AIM_FLAG_AFFINE2P");
+        if (is_linear(p)) return fail(AIM_EINVAL, "AIM_FLAG_WFA_BIDIR cannot be combined with AIM_FLAG_LINEAR");
+        if (std::max(p.mismatch, p.gap_o + p.gap_e) + 1 > aim::kBidirMaxScope)
+            return fail(AIM_EINVAL, "AIM_FLAG_WFA_BIDIR needs max(x, o + e) < %d", aim::kBidirMaxScope);
+    }
     if (p.read_size <= 0 || (p.read_size & 7)) return fail(AIM_EINVAL, "read_size must be a positive multiple of 8 (got %d)", p.read_size);
     if (p.max_score < 0) return fail(AIM_EINVAL, "max_score must be >= 0");
     if ((p.flags & AIM_FLAG_REQ8) && p.read_size >= 32760)
@@ -387,8 +401,50 @@ bool plan_wfa_group(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &k
 // WFA: a lane kernel where it takes the shape; else wfa_group, or wfa_lane_packed behind pack_rows_kernel, with wfa_wave over their
 // to-do list; else wfa_wave alone. Ends-free, affine2p and gap-linear never run on the lane kernels (their wavefront shapes are fixed at compile
 // time for the global case): wfa_group where LDS admits the wider rows / deeper rings, else wfa_wave.
+// AIM_FLAG_WFA_BIDIR: wfa_wave_kernel at MAX_SCORE min(MAX_SCORE, T) first (every pair of score <= T gets the flag-less result and
+// bytes from it), then wfa_bidir_kernel over the pairs it left over T. The two stages run one after the other on one stream and
+// share one scratch region. Every READ_SIZE, both offset widths; no other stage.
+int plan_wfa_bidir(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, Plan *pl)
+{
+    const int T = aim::wfa_bidir_threshold(p);
+    aim_params_t p1 = p;
+    p1.flags &= ~AIM_FLAG_WFA_BIDIR;
+    p1.max_score = std::min(p.max_score, T);
+    int rc = plan_wfa_wave(p1, n_pairs, kn, budget, &pl->fb);
+    if (rc) return rc;
+    const int scope = std::max(p.mismatch, p.gap_o + p.gap_e) + 1;
+    const int kw = (int)std::min<int64_t>((int64_t)p.max_score + 2 * scope + p.gap_o + p.gap_o + p.gap_e + 8, (int64_t)p.read_size + 2);
+    Stage &m = pl->main;
+    m.kid = K_WFA_BIDIR;
+    m.block = 64;
+    m.lds = aim::wfa_bidir_lds(T);
+    m.scratch_per_wg = aim::wfa_bidir_wg_bytes(p, T, kw);
+    m.pool_cap = (uint32_t)T;
+    m.slot_w = (uint32_t)kw;
+    pl->bidir_t = T;
+    if (p.max_score <= T) {
+        // the first stage is the whole alignment: the bidirectional kernel is not launched, needs no scratch and no grid (the plan
+        // line says grid=0), and the budget is the first stage's alone
+        m.scratch_per_wg = 0;
+        m.grid = 0;
+        pl->scratch_total = stage_bytes(pl->fb);
+        return AIM_OK;
+    }
+    // persistent single-wave workgroups: what is resident by VGPRs (wfa_bidir_kernel's launch bound) and LDS
+    const uint32_t wg_per_cu = (uint32_t)std::min<size_t>(aim::kBidirPerCu, aim::lds_workgroups_per_cu(m.lds));
+    uint32_t grid = resident_grid(kn, wg_per_cu);
+    const uint32_t need = ((n_pairs + 7u) / 8u) * 8u;
+    if (grid > need) grid = std::max(8u, need);
+    while (grid > 8 && (uint64_t)m.scratch_per_wg * grid > budget) grid -= 8;
+    if ((uint64_t)m.scratch_per_wg * grid > budget) return fail(AIM_ENOMEM, "scratch budget too small for one bidirectional WFA workgroup (%llu bytes)", (unsigned long long)m.scratch_per_wg);
+    m.grid = grid;
+    pl->scratch_total = std::max(stage_bytes(m), stage_bytes(pl->fb));
+    return AIM_OK;
+}
+
 int plan_wfa(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, uint32_t mode, Plan *pl)
 {
+    if (is_bidir(p)) return plan_wfa_bidir(p, n_pairs, kn, budget, pl);
     if (is_w32(p)) {
         // int32 offsets exist in wfa_wave_kernel only (wfa_group / the lane kernels keep int16 rows): it runs alone at every READ_SIZE
         // and takes non-ACGT pairs itself, so there is no fallback stage. Below 32760 this costs speed and changes no result.
@@ -573,6 +629,7 @@ const char *kernel_name(const Plan &pl, const aim_params_t &p)
 {
     switch (pl.main.kid) {
     case K_WFA_WAVE: return "wfa_wave_kernel";
+    case K_WFA_BIDIR: return "wfa_bidir_kernel";
     case K_WFA_LANE: return "wfa_lane_kernel";
     case K_WFA_LANE_PK: return "wfa_lane_packed_kernel";
     case K_WFA_GROUP: return "wfa_group_kernel";
@@ -609,6 +666,7 @@ int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint6
     } else if (is_linear(p)) {
         snprintf(efs, sizeof efs, " linear");
     }
+    if (m.kid == K_WFA_BIDIR) snprintf(extra, sizeof extra, " bidir=%d", pl.bidir_t);
     return snprintf(out, cap, "%s n=%u grid=%u block=%u lds=%zu scratch=%zu budget=%llu%s%s%s", kernel_name(pl, p), n_pairs, pl.main.grid,
                     pl.main.block, pl.main.lds, pl.scratch_total, (unsigned long long)budget, extra, efs, is_w32(p) ? " w32" : "");
 }
@@ -867,6 +925,18 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
     case K_GENASM:
         aim::genasm_launch(p, m.grid, m.lds, ka, stream);
         break;
+    case K_WFA_BIDIR: {
+        // wfa_wave at MAX_SCORE min(MAX_SCORE, T) over the whole batch, then the bidirectional kernel over the pairs it left over T
+        aim_params_t p1 = p;
+        p1.flags &= ~AIM_FLAG_WFA_BIDIR;
+        p1.max_score = std::min(p.max_score, pl.bidir_t);
+        aim::KArgs k1 = stage_args(ka0, pl.fb, d_scratch);
+        k1.p = p1;
+        launch_stage(p1, pl.fb, k1, stream);
+        HIP_TRY(hipGetLastError());
+        if (p.max_score > pl.bidir_t) aim::wfa_bidir_launch(m.grid, m.lds, ka, stream);
+        break;
+    }
     }
     HIP_TRY(hipGetLastError());
     return AIM_OK;
@@ -1041,7 +1111,7 @@ int launch_on_slot(aim_set *set, aim_device_ctx &d, aim_slot &s, uint32_t mode =
 extern "C" {
 
 int aim_abi_version(void) { return AIM_ABI_VERSION; }
-uint32_t aim_features(void) { return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32; }
+uint32_t aim_features(void) { return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR; }
 const char *aim_last_error(void) { return g_err; }
 
 int aim_device_count(int *count)

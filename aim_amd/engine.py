@@ -13,7 +13,7 @@ import numpy as np
 
 from . import capi
 from .capi import (ALGO_BY_NAME, ALGO_NW, ALGO_SWG, ALGO_WFA, FLAG_AFFINE2P, FLAG_BACKTRACE, FLAG_ENDSFREE, FLAG_LINEAR, FLAG_REDUCE,
-                   FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16, FLAG_WFA_W32, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
+                   FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16, FLAG_WFA_BIDIR, FLAG_WFA_W32, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
                    Params, params_ref)
 
 
@@ -37,18 +37,26 @@ def features():
 
 def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=1, gap=4, backtrace=False,
                 reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None, gap2=None, linear=False,
-                w32=False):
+                w32=False, bidir=False):
     """`gap` is the launchers' single NW gap cost (run-nw-pim-wram.py: -DGAP_I = -DGAP_D); `gap_i` / `gap_d` set the two macros of
     nw.c:67-153 apart (NW/DPU-WRAM/common/common.h GAP_I, GAP_D). `ends_free=(PB, PE, TB, TE)`: ends-free WFA (AIM_FLAG_ENDSFREE);
     returns an EndsFreeParams then, which every call below accepts like Params. `gap2=(O2, E2)`: dual-cost gap-affine WFA
     (AIM_FLAG_AFFINE2P, gap_o / gap_e are piece 1); returns an Affine2pParams. The two cannot be combined. `linear=True`: gap-linear
     WFA (AIM_FLAG_LINEAR): a mismatch costs `mismatch`, every gap base `gap_e`, and gap_o is set to 0; not with ends_free, gap2 or
-    reduce. `w32=True`: WFA with 32-bit wavefront offsets (AIM_FLAG_WFA_W32), read_size up to 2^24; combines with all of the above."""
+    reduce. `w32=True`: WFA with 32-bit wavefront offsets (AIM_FLAG_WFA_W32), read_size up to 2^24; combines with all of the above.
+    `bidir=True`: bidirectional WFA (AIM_FLAG_WFA_BIDIR), CIGAR in O(MAX_SCORE) scratch; global gap-affine with backtrace only."""
     a = ALGO_BY_NAME[algo] if isinstance(algo, str) else algo
     gap_i = gap if gap_i is None else gap_i
     gap_d = gap if gap_d is None else gap_d
     flags = (FLAG_BACKTRACE if backtrace else 0) | (FLAG_REDUCE if reduce else 0) | (FLAG_SWG_W16 if swg_w16 else 0)
     flags |= (FLAG_REQ8 if req8 else 0) | (FLAG_RES8 if res8 else 0) | (FLAG_WFA_W32 if w32 else 0)
+    if bidir:
+        if not backtrace:
+            raise ValueError("bidir needs backtrace")
+        for name, given in (("reduce", reduce), ("ends_free", ends_free is not None), ("gap2", gap2 is not None), ("linear", linear)):
+            if given:
+                raise ValueError("bidir cannot be combined with %s" % name)
+        flags |= FLAG_WFA_BIDIR
     if ends_free is not None and gap2 is not None:
         raise ValueError("ends_free and gap2 cannot be combined")
     if linear:

@@ -25,6 +25,8 @@
  *                   edit distance; AIM_FLAG_LINEAR, include/aim_hip.h); not with --gap2, --ends-free or --reduce
  *     --w32         (WFA) 32-bit wavefront offsets (AIM_FLAG_WFA_W32, include/aim_hip.h): --read-size up to 2^24 instead of
  *                   < 32760; combines with the flags above; the output format is unchanged
+ *     --bidir       (WFA, with --backtrace) bidirectional WFA: the CIGAR in O(max-score) memory (AIM_FLAG_WFA_BIDIR,
+ *                   include/aim_hip.h); not with --reduce, --ends-free, --gap2 or --linear; the output format is unchanged
  *     --packed-input  <input> is a packed batch file (written by --pack-only or `python -m aim_amd.gen_dataset --packed`):
  *                   2 bits per base + raw side list, ready for the device; no text is parsed
  * The UPMEM dispatch (dpu_alloc/dpu_load/dpu_push_xfer/dpu_launch) is replaced
@@ -939,6 +941,7 @@ int main(int argc, char *argv[])
         else if (!strcmp(f, "--reduce")) p.flags |= AIM_FLAG_REDUCE;
         else if (!strcmp(f, "--linear")) p.flags |= AIM_FLAG_LINEAR;
         else if (!strcmp(f, "--w32")) p.flags |= AIM_FLAG_WFA_W32;
+        else if (!strcmp(f, "--bidir")) p.flags |= AIM_FLAG_WFA_BIDIR;
         else if (!strcmp(f, "--swg-w16")) p.flags |= AIM_FLAG_SWG_W16;
         else if (!strcmp(f, "--no-pack")) no_pack = 1;       /* ship ASCII rows like the reference (host.c:258-268) */
         else if (!strcmp(f, "--full-ops")) full_ops = 1;     /* gather result_t + ops rows like the reference (host.c:316-326) */
@@ -1028,6 +1031,14 @@ int main(int argc, char *argv[])
         p.gap_o = 0;
     }
     if ((p.flags & AIM_FLAG_WFA_W32) && p.algo != AIM_ALGO_WFA) { fprintf(stderr, "--w32 needs --algo wfa\n"); exit(1); }
+    if (p.flags & AIM_FLAG_WFA_BIDIR) {
+        if (p.algo != AIM_ALGO_WFA) { fprintf(stderr, "--bidir needs --algo wfa\n"); exit(1); }
+        if (!(p.flags & AIM_FLAG_BACKTRACE)) { fprintf(stderr, "--bidir needs --backtrace\n"); exit(1); }
+        if (p.flags & AIM_FLAG_REDUCE) { fprintf(stderr, "--bidir cannot be combined with --reduce\n"); exit(1); }
+        if (p.flags & AIM_FLAG_ENDSFREE) { fprintf(stderr, "--bidir cannot be combined with --ends-free\n"); exit(1); }
+        if (p.flags & AIM_FLAG_AFFINE2P) { fprintf(stderr, "--bidir cannot be combined with --gap2\n"); exit(1); }
+        if (p.flags & AIM_FLAG_LINEAR) { fprintf(stderr, "--bidir cannot be combined with --linear\n"); exit(1); }
+    }
     if (packed_input && (no_pack || pack_only)) { fprintf(stderr, "--packed-input cannot be combined with --no-pack / --pack-only\n"); exit(1); }
 #if defined(__x86_64__)
     g_simd = __builtin_cpu_supports("sse4.1") && __builtin_cpu_supports("ssse3") && __builtin_cpu_supports("bmi2");

@@ -124,6 +124,16 @@ typedef struct aim_affine2p_params {
  * one-pair-per-wavefront kernel: below read_size 32760 the results equal those without the flag and the flag only costs speed.
  * Check aim_features() & AIM_FEATURE_WFA_W32 first: older libraries ignore unknown flags. */
 #define AIM_FLAG_WFA_W32 0x100u
+/* AIM_FLAG_WFA_BIDIR (global gap-affine WFA with AIM_FLAG_BACKTRACE only): bidirectional WFA (Marco-Sola et al., Bioinformatics
+ * 2023), CIGAR in O(MAX_SCORE) scratch per workgroup instead of the O(MAX_SCORE^2) history, so no pair reports AIM_PAIR_NOMEM
+ * because of its score. Score and status are exactly the flag-less ones (MAX_SCORE + 1 over the cap, with the over-cap row
+ * begin_offset = end_offset - 1). The CIGAR is an optimal global alignment of the same cost in the same ops-row layout; it
+ * equals the flag-less bytes for every pair whose score is <= T, the base-case threshold the plan line prints as "bidir=T"
+ * (T >= 250). Results do not depend on the offset width, the grid, the slots or the batch size. Combines with
+ * AIM_FLAG_WFA_W32, AIM_FLAG_REQ8, packed input, compact runs and every entry point; rejected (AIM_EINVAL) with NW / SWG / GenASM,
+ * without AIM_FLAG_BACKTRACE, and with AIM_FLAG_REDUCE, AIM_FLAG_ENDSFREE, AIM_FLAG_AFFINE2P or AIM_FLAG_LINEAR (follow-ups).
+ * Check aim_features() & AIM_FEATURE_WFA_BIDIR first: older libraries ignore unknown flags. */
+#define AIM_FLAG_WFA_BIDIR 0x200u
 
 /* Per-pair descriptor: byte-compatible with the NW/SWG request_t
  * (NW/DPU-WRAM/common/common.h:114-120).  The WFA variant of the reference
@@ -172,6 +182,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_AFFINE2P 0x2u /* AIM_FLAG_AFFINE2P is honoured */
 #define AIM_FEATURE_LINEAR 0x4u   /* AIM_FLAG_LINEAR is honoured */
 #define AIM_FEATURE_WFA_W32 0x8u  /* AIM_FLAG_WFA_W32 is honoured */
+#define AIM_FEATURE_WFA_BIDIR 0x10u /* AIM_FLAG_WFA_BIDIR is honoured */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
