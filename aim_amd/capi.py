@@ -25,6 +25,9 @@ FLAG_WFA_W32 = 256     # WFA with int32 wavefront offsets (AFFINE_WAVEFRONT_W32)
 FEATURE_WFA_W32 = 8    # aim_features(): AIM_FLAG_WFA_W32 is honoured
 FLAG_WFA_BIDIR = 512   # bidirectional WFA with CIGAR: O(MAX_SCORE) scratch per workgroup (global gap-affine, BACKTRACE)
 FEATURE_WFA_BIDIR = 16 # aim_features(): AIM_FLAG_WFA_BIDIR is honoured
+FLAG_REF_TEXTS = 0x400 # texts named as (position, strand) windows of the device-resident reference (aim_set_reference)
+FEATURE_REF_TEXTS = 0x20  # aim_features(): AIM_FLAG_REF_TEXTS is honoured
+REF_MINUS_STRAND = 1 << 63   # text_pos bit 63: the reverse complement of the window
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
 
 
@@ -96,6 +99,11 @@ class BatchIO(C.Structure):
                 ("cigars", C.c_void_p), ("runs", C.c_void_p), ("runs_cap", C.c_uint32)]
 
 
+class BatchIORef(C.Structure):
+    """aim_batch_io_ref_t: aim_batch_io_t + text_pos (AIM_FLAG_REF_TEXTS); aim_set_submit receives a pointer to `base`."""
+    _fields_ = [("base", BatchIO), ("text_pos", C.c_void_p)]
+
+
 # every symbol include/aim_hip.h declares: name -> (restype, argtypes)
 _VP, _U32, _I32 = C.c_void_p, C.c_uint32, C.c_int32
 SYMBOLS = {
@@ -128,6 +136,10 @@ SYMBOLS = {
     "aim_launcher_sizes": (C.c_int, [_I32, _I32, C.c_double, _I32, _I32, _I32, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "aim_cigar_format": (C.c_int, [_VP, _I32, _I32, _VP, _I32]),
     "aim_gen_pairs": (C.c_int, [C.c_uint64, C.c_uint64, _U32, _I32, C.c_double, _I32, _VP, _VP, _VP]),
+    "aim_set_reference": (C.c_int, [_VP, _VP, C.c_uint64]),
+    "aim_set_push_ref": (C.c_int, [_VP, _U32, _U32, _VP, _VP, _VP]),
+    "aim_ref_windows_check": (C.c_int, [C.POINTER(Params), _U32, _VP, _VP, C.c_uint64, C.POINTER(_U32)]),
+    "aim_align_device_ref": (C.c_int, [C.POINTER(Params), _U32, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, C.c_size_t, _VP]),
 }
 
 _lib = None

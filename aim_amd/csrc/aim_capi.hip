@@ -234,6 +234,11 @@ inline bool is_linear(const aim_params_t &p) { return (p.flags & AIM_FLAG_LINEAR
 inline bool is_w32(const aim_params_t &p) { return (p.flags & AIM_FLAG_WFA_W32) != 0; }
 // AIM_FLAG_WFA_BIDIR: bidirectional WFA with CIGAR (wfa_bidir.hpp).
 inline bool is_bidir(const aim_params_t &p) { return (p.flags & AIM_FLAG_WFA_BIDIR) != 0; }
+// AIM_FLAG_REF_TEXTS: texts gathered from a device-resident reference (batch_io.hpp); no plan depends on it.
+inline bool is_ref(const aim_params_t &p) { return (p.flags & AIM_FLAG_REF_TEXTS) != 0; }
+// aim_align_device_ref: the gathered text rows sit behind the plan's scratch, 256-B aligned, with 256 B of tail slack
+inline size_t ref_rows_at(size_t plan_scratch) { return (plan_scratch + 255) & ~(size_t)255; }
+inline size_t ref_rows_bytes(const aim_params_t &p, uint32_t n_pairs) { return (size_t)n_pairs * (size_t)p.read_size + 256; }
 // The params as this library keeps them: room for either extension, and the extension copied only when a flag says it exists.
 union XParams {
     aim_params_t base;
@@ -667,8 +672,9 @@ int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint6
         snprintf(efs, sizeof efs, " linear");
     }
     if (m.kid == K_WFA_BIDIR) snprintf(extra, sizeof extra, " bidir=%d", pl.bidir_t);
-    return snprintf(out, cap, "%s n=%u grid=%u block=%u lds=%zu scratch=%zu budget=%llu%s%s%s", kernel_name(pl, p), n_pairs, pl.main.grid,
-                    pl.main.block, pl.main.lds, pl.scratch_total, (unsigned long long)budget, extra, efs, is_w32(p) ? " w32" : "");
+    return snprintf(out, cap, "%s n=%u grid=%u block=%u lds=%zu scratch=%zu budget=%llu%s%s%s%s", kernel_name(pl, p), n_pairs, pl.main.grid,
+                    pl.main.block, pl.main.lds, pl.scratch_total, (unsigned long long)budget, extra, efs, is_w32(p) ? " w32" : "",
+                    is_ref(p) ? " ref=1" : "");
 }
 
 int make_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, Plan *pl, uint32_t mode = 0u)
@@ -942,6 +948,22 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
     return AIM_OK;
 }
 
+// AIM_FLAG_REF_TEXTS: text rows [n_rows][READ_SIZE] of `out` gathered from the reference; row r is the window of pair idx[r]
+// (idx == nullptr: pair r). ka carries the params and the requests.
+int enqueue_gather(const aim::KArgs &ka, const uint64_t *d_tpos, const char *ref, uint64_t ref_len, const uint32_t *idx, uint32_t n_rows,
+                   char *out, hipStream_t stream)
+{
+    if (!n_rows) return AIM_OK;
+    const int rs = ka.p.read_size;
+    const bool w16 = (rs & 15) == 0;   // 16-B stores per lane where the row stride allows them, else 8-B
+    const uint64_t threads = (uint64_t)n_rows * (uint64_t)(rs / (w16 ? 16 : 8));
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (w16) hipLaunchKernelGGL(aim::gather_text_rows_kernel<4>, grid, dim3(256), 0, stream, ka, d_tpos, ref, ref_len, idx, n_rows, out);
+    else hipLaunchKernelGGL(aim::gather_text_rows_kernel<2>, grid, dim3(256), 0, stream, ka, d_tpos, ref, ref_len, idx, n_rows, out);
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -964,6 +986,9 @@ struct aim_slot {
     void *d_rawreq = nullptr, *d_rawres = nullptr;                   // raw side pass (fused packed batches): the side list as a batch of its own
     char *d_rawops = nullptr;
     aim_cigar_t *d_rawcig = nullptr;
+    uint64_t *d_tpos = nullptr;      // AIM_FLAG_REF_TEXTS: the batch's text_pos[]
+    uint32_t *d_reftodo = nullptr;   // ... packed batches on the fused lane kernel: to-do list {count @0, pair ids @16..} + flag bits
+    bool ref_pending = false;        // aim_set_push_ref: the texts are gathered at aim_set_launch
     uint32_t n_pairs = 0;
     uint32_t runs_sent = 0;  // runs of the batch in flight whose D2H copy aim_set_submit already enqueued (slotted run buffer)
     bool pushed = false, launched = false, submitted = false;
@@ -975,6 +1000,8 @@ struct aim_slot {
 struct aim_device_ctx {
     int dev = -1;
     std::vector<aim_slot> slots;
+    char *d_ref = nullptr;   // AIM_FLAG_REF_TEXTS: the reference (+ zeroed tail slack), kept across aim_set_configure
+    uint64_t ref_len = 0;
     Plan plan;               // made at configure time for max_pairs under the set's knobs and this device's budget
     uint64_t budget = 0;     // scratch bound of one slot of this device, frozen at configure time
     float h2d_ms = 0.f, kernel_ms = 0.f, d2h_ms = 0.f;   // aim_set_submit / aim_set_wait: phase times of this device's batches, summed
@@ -997,7 +1024,7 @@ inline size_t res_size(const aim_params_t &p) { return (p.flags & AIM_FLAG_RES8)
 void free_slot(aim_slot &s)
 {
     void *bufs[] = {s.d_req, s.d_pat, s.d_txt, s.d_ops, s.d_res, s.d_scratch, s.d_packP, s.d_packT, s.d_rawidx, s.d_rawP, s.d_rawT,
-                    s.d_cig, s.d_runs, s.d_cursor, s.d_rawreq, s.d_rawres, s.d_rawops, s.d_rawcig};
+                    s.d_cig, s.d_runs, s.d_cursor, s.d_rawreq, s.d_rawres, s.d_rawops, s.d_rawcig, s.d_tpos, s.d_reftodo};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (s.h_cursor) (void)hipHostFree(s.h_cursor);
@@ -1074,6 +1101,38 @@ int check_lengths(const aim_params_t &p, uint32_t n_pairs, const void *requests)
     return AIM_OK;
 }
 
+// AIM_FLAG_REF_TEXTS: every window [pos, pos + text_len) inside [0, ref_len) (bit 63 is the strand; an empty window is always
+// inside). Scanned branch-free like check_lengths; only a failing scan is repeated to name the pair.
+int check_windows(const aim_params_t &p, uint32_t n_pairs, const void *requests, const uint64_t *text_pos, uint64_t ref_len, uint32_t *bad_pair)
+{
+    const bool req8 = p.flags & AIM_FLAG_REQ8;
+    auto tlen = [&](size_t i) -> uint64_t {
+        return (uint64_t)(req8 ? static_cast<const aim_request8_t *>(requests)[i].text_len : static_cast<const aim_request_t *>(requests)[i].text_len);
+    };
+    auto bad = [&](size_t i) -> uint32_t {
+        const uint64_t pos = text_pos[i] & ~AIM_REF_MINUS_STRAND, len = tlen(i);   // (lengths are checked >= 0 already)
+        return (uint32_t)(len != 0 && (pos > ref_len || len > ref_len - pos));
+    };
+    if (!n_pairs || !any_nonzero(n_pairs, bad)) return AIM_OK;
+    for (uint32_t i = 0; i < n_pairs; ++i)
+        if (bad(i)) {
+            if (bad_pair) *bad_pair = i;
+            return fail(AIM_EINVAL, "text window of pair %u is outside the reference: pos %llu + text_len %llu > ref_len %llu", i,
+                        (unsigned long long)(text_pos[i] & ~AIM_REF_MINUS_STRAND), (unsigned long long)tlen(i), (unsigned long long)ref_len);
+        }
+    return AIM_OK;
+}
+
+// AIM_FLAG_REF_TEXTS, packed batch on the fused lane kernel: the general kernel's stage over the to-do list of windows that hold a
+// byte outside A/C/G/T (the stage pack_first plans put behind the same kernel). False when it does not fit the slot's scratch.
+bool ref_todo_stage(const aim_set *set, const aim_device_ctx &d, size_t scratch_bytes, uint32_t n_pairs, Stage *st)
+{
+    memset(st, 0, sizeof *st);
+    const aim::Knobs kc = set->knobs.cus ? set->knobs : with_chip(set->knobs);
+    if (plan_wfa_wave(set->params, std::min<uint32_t>(n_pairs, 1024u * 64u), kc, d.budget, st)) return false;
+    return stage_bytes(*st) <= scratch_bytes;
+}
+
 int status_error(uint32_t idx, int status)
 {
     return fail(AIM_EALIGN, "pair idx %u stopped with status %d (%s)", idx, status,
@@ -1111,7 +1170,10 @@ int launch_on_slot(aim_set *set, aim_device_ctx &d, aim_slot &s, uint32_t mode =
 extern "C" {
 
 int aim_abi_version(void) { return AIM_ABI_VERSION; }
-uint32_t aim_features(void) { return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR; }
+uint32_t aim_features(void)
+{
+    return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS;
+}
 const char *aim_last_error(void) { return g_err; }
 
 int aim_device_count(int *count)
@@ -1194,6 +1256,11 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
             if (params->flags & AIM_FLAG_BACKTRACE) HIP_TRY(hipMalloc((void **)&s.d_rawops, (size_t)max_raw * 2 * rs + 64));
             if (max_runs) HIP_TRY(hipMalloc((void **)&s.d_rawcig, (size_t)max_raw * sizeof(aim_cigar_t)));
         }
+        if (is_ref(*params)) {
+            HIP_TRY(hipMalloc((void **)&s.d_tpos, (size_t)max_pairs * 8));
+            if (max_raw && params->algo == AIM_ALGO_WFA)
+                HIP_TRY(hipMalloc((void **)&s.d_reftodo, 64 + (size_t)max_pairs * 4 + ((size_t)max_pairs + 31) / 32 * 4));
+        }
         if (max_runs) {
             HIP_TRY(hipMalloc((void **)&s.d_cig, (size_t)max_pairs * sizeof(aim_cigar_t)));
             HIP_TRY(hipMalloc((void **)&s.d_runs, (size_t)max_runs * 4));
@@ -1221,10 +1288,17 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
         for (int attempt = 0;; ++attempt) {
             int prc = make_plan(*params, max_pairs, kn, d.budget, &d.plan);
             if (prc) return prc;
+            size_t want = d.plan.scratch_total;
+            if (is_ref(*params) && max_raw && params->algo == AIM_ALGO_WFA) {   // room for the to-do stage of fused packed batches
+                Stage st;
+                memset(&st, 0, sizeof st);
+                if (!plan_wfa_wave(*params, std::min<uint32_t>(max_pairs, 1024u * 64u), kn.cus ? kn : with_chip(kn), d.budget, &st))
+                    want = std::max(want, stage_bytes(st));
+            }
             hipError_t e = hipSuccess;
             for (auto &s : d.slots) {
-                s.scratch_bytes = d.plan.scratch_total;
-                if (d.plan.scratch_total && (e = hipMalloc(&s.d_scratch, d.plan.scratch_total)) != hipSuccess) break;
+                s.scratch_bytes = want;
+                if (want && (e = hipMalloc(&s.d_scratch, want)) != hipSuccess) break;
             }
             if (e == hipSuccess) break;
             (void)hipGetLastError();
@@ -1234,7 +1308,7 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
             }
             if (e != hipErrorOutOfMemory || attempt >= 6 || d.budget <= ((uint64_t)1 << 28))
                 return fail(e == hipErrorOutOfMemory ? AIM_ENOMEM : AIM_ENODEV, "hipMalloc(scratch, %zu bytes) failed: %s",
-                            d.plan.scratch_total, hipGetErrorString(e));
+                            want, hipGetErrorString(e));
             d.budget /= 2;
         }
         for (auto &s : d.slots) {
@@ -1242,8 +1316,8 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
             // it (every scratch byte a launch reads must have been written by that launch). On
             // the slot's own stream and completed here: launches run on non-blocking streams that do not synchronise with
             // the null stream.
-            if (d.plan.scratch_total && kn.poison_scratch >= 0) {
-                HIP_TRY(hipMemsetAsync(s.d_scratch, kn.poison_scratch & 0xff, d.plan.scratch_total, s.stream));
+            if (s.scratch_bytes && kn.poison_scratch >= 0) {
+                HIP_TRY(hipMemsetAsync(s.d_scratch, kn.poison_scratch & 0xff, s.scratch_bytes, s.stream));
                 HIP_TRY(hipStreamSynchronize(s.stream));
             }
             s.n_pairs = 0;
@@ -1276,31 +1350,57 @@ int aim_set_configure(aim_set_t *set, const aim_params_t *params, uint32_t max_p
     return aim_set_configure_slots(set, params, max_pairs, 1, 0, 0);
 }
 
-int aim_set_push(aim_set_t *set, uint32_t device, uint32_t n_pairs, const void *requests, const char *patterns,
-                 const char *texts)
+namespace {
+// aim_set_push (texts != nullptr) and aim_set_push_ref (text_pos != nullptr)
+int push_impl(aim_set_t *set, uint32_t device, uint32_t n_pairs, const void *requests, const char *patterns, const char *texts,
+              const uint64_t *text_pos)
 {
     if (!set || device >= set->devs.size()) return fail(AIM_EINVAL, "bad device index");
     if (!set->configured) return fail(AIM_ESTATE, "aim_set_configure has not been called");
     if (n_pairs > set->max_pairs) return fail(AIM_EINVAL, "n_pairs %u exceeds configured capacity %u", n_pairs, set->max_pairs);
-    if (n_pairs && (!requests || !patterns || !texts)) return fail(AIM_EINVAL, "null host buffer");
+    if (n_pairs && (!requests || !patterns || (!texts && !text_pos))) return fail(AIM_EINVAL, "null host buffer");
     aim_device_ctx &d = set->devs[device];
     aim_slot &s = d.slots[0];
     if (s.submitted) return fail(AIM_ESTATE, "slot 0 of device %d holds a submitted batch: aim_set_wait it first", d.dev);
     const size_t rs = (size_t)set->params.read_size;
     int rc = check_lengths(set->params, n_pairs, requests);
     if (rc) return rc;
+    if (text_pos) {
+        if (!d.d_ref) return fail(AIM_ESTATE, "AIM_FLAG_REF_TEXTS: no reference on device %d (aim_set_reference)", d.dev);
+        rc = check_windows(set->params, n_pairs, requests, text_pos, d.ref_len, nullptr);
+        if (rc) return rc;
+    }
     HIP_TRY(hipSetDevice(d.dev));
     HIP_TRY(hipEventRecord(s.ev[0], s.stream));
     if (n_pairs) {
         HIP_TRY(hipMemcpyAsync(s.d_req, requests, (size_t)n_pairs * req_size(set->params), hipMemcpyHostToDevice, s.stream));
         HIP_TRY(hipMemcpyAsync(s.d_pat, patterns, (size_t)n_pairs * rs, hipMemcpyHostToDevice, s.stream));
-        HIP_TRY(hipMemcpyAsync(s.d_txt, texts, (size_t)n_pairs * rs, hipMemcpyHostToDevice, s.stream));
+        if (text_pos) HIP_TRY(hipMemcpyAsync(s.d_tpos, text_pos, (size_t)n_pairs * 8, hipMemcpyHostToDevice, s.stream));
+        else HIP_TRY(hipMemcpyAsync(s.d_txt, texts, (size_t)n_pairs * rs, hipMemcpyHostToDevice, s.stream));
     }
     HIP_TRY(hipEventRecord(s.ev[1], s.stream));
     s.n_pairs = n_pairs;
     s.pushed = true;
     s.launched = false;
+    s.ref_pending = text_pos != nullptr;
     return AIM_OK;
+}
+}  // namespace
+
+int aim_set_push(aim_set_t *set, uint32_t device, uint32_t n_pairs, const void *requests, const char *patterns,
+                 const char *texts)
+{
+    if (set && set->configured && is_ref(set->params))
+        return fail(AIM_EINVAL, "AIM_FLAG_REF_TEXTS is set: the texts are named by text_pos (aim_set_push_ref)");
+    return push_impl(set, device, n_pairs, requests, patterns, texts, nullptr);
+}
+
+int aim_set_push_ref(aim_set_t *set, uint32_t device, uint32_t n_pairs, const void *requests, const char *patterns,
+                     const uint64_t *text_pos)
+{
+    if (set && set->configured && !is_ref(set->params)) return fail(AIM_EINVAL, "aim_set_push_ref needs AIM_FLAG_REF_TEXTS");
+    if (n_pairs && !text_pos) return fail(AIM_EINVAL, "null text_pos");
+    return push_impl(set, device, n_pairs, requests, patterns, nullptr, text_pos);
 }
 
 int aim_set_launch(aim_set_t *set)
@@ -1311,6 +1411,15 @@ int aim_set_launch(aim_set_t *set)
         if (!s.pushed) return fail(AIM_ESTATE, "device %d has no pushed batch", d.dev);
         HIP_TRY(hipSetDevice(d.dev));
         HIP_TRY(hipEventRecord(s.ev[2], s.stream));
+        if (s.ref_pending && s.n_pairs) {   // AIM_FLAG_REF_TEXTS: the windows into the text rows, ahead of the plan's stages
+            aim::KArgs ka;
+            memset(&ka, 0, sizeof ka);
+            ka.p = set->params;
+            ka.n_pairs = s.n_pairs;
+            ka.req = static_cast<const aim_request_t *>(s.d_req);
+            int grc = enqueue_gather(ka, s.d_tpos, d.d_ref, d.ref_len, nullptr, s.n_pairs, s.d_txt, s.stream);
+            if (grc) return grc;
+        }
         int rc = launch_on_slot(set, d, s);
         if (rc) return rc;
         HIP_TRY(hipEventRecord(s.ev[3], s.stream));
@@ -1371,19 +1480,30 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
     const aim_params_t &p = set->params;
     const uint32_t n = io->n_pairs;
     const bool bt = p.flags & AIM_FLAG_BACKTRACE;
+    // AIM_FLAG_REF_TEXTS: io is the base of an aim_batch_io_ref_t and the texts are windows of the device's reference
+    const bool ref = is_ref(p);
+    const uint64_t *text_pos = ref ? reinterpret_cast<const aim_batch_io_ref_t *>(io)->text_pos : nullptr;
+    if (ref && (io->texts || io->packed_texts || io->raw_texts))
+        return fail(AIM_EINVAL, "AIM_FLAG_REF_TEXTS: texts, packed_texts and raw_texts must be NULL (the texts are named by text_pos)");
+    if (ref && n && !text_pos) return fail(AIM_EINVAL, "AIM_FLAG_REF_TEXTS: null text_pos");
+    if (ref && !d.d_ref) return fail(AIM_ESTATE, "AIM_FLAG_REF_TEXTS: no reference on device %d (aim_set_reference)", d.dev);
     const bool packed = io->packed_patterns || io->packed_texts;
     if (n > set->max_pairs) return fail(AIM_EINVAL, "n_pairs %u exceeds configured capacity %u", n, set->max_pairs);
     if (n && !io->requests) return fail(AIM_EINVAL, "null requests");
-    if (n && packed && (!io->packed_patterns || !io->packed_texts || !s.d_packP))
+    if (n && packed && (!io->packed_patterns || (!ref && !io->packed_texts) || !s.d_packP))
         return fail(AIM_EINVAL, "packed batch needs both packed arrays and a set configured with max_raw_pairs > 0");
-    if (n && !packed && (!io->patterns || !io->texts)) return fail(AIM_EINVAL, "null sequence rows");
+    if (n && !packed && (!io->patterns || (!ref && !io->texts))) return fail(AIM_EINVAL, "null sequence rows");
     if (packed && io->n_raw > set->max_raw) return fail(AIM_EINVAL, "n_raw %u exceeds configured capacity %u", io->n_raw, set->max_raw);
-    if (packed && io->n_raw && (!io->raw_pairs || !io->raw_patterns || !io->raw_texts)) return fail(AIM_EINVAL, "null raw side list");
+    if (packed && io->n_raw && (!io->raw_pairs || !io->raw_patterns || (!ref && !io->raw_texts))) return fail(AIM_EINVAL, "null raw side list");
     if (io->cigars && (!bt || !s.d_cig || !io->runs)) return fail(AIM_EINVAL, "compact CIGAR needs AIM_FLAG_BACKTRACE, max_runs > 0 and a run buffer");
     if (n && !io->results && !io->cigars) return fail(AIM_EINVAL, "no output buffer");
     if (io->ops && !bt) return fail(AIM_EINVAL, "ops requested without AIM_FLAG_BACKTRACE");
     int rc = check_lengths(p, n, io->requests);
     if (rc) return rc;
+    if (ref) {
+        rc = check_windows(p, n, io->requests, text_pos, d.ref_len, nullptr);
+        if (rc) return rc;
+    }
     if (packed)
         for (uint32_t j = 0; j < io->n_raw; ++j)
             if (io->raw_pairs[j] >= n) return fail(AIM_EINVAL, "raw_pairs[%u] = %u is outside the batch", j, io->raw_pairs[j]);
@@ -1394,6 +1514,7 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
     s.n_pairs = n;
     s.runs_sent = 0;
     s.pushed = s.launched = false;
+    s.ref_pending = false;
     // Everything below only enqueues work on the slot's stream. Should an enqueue fail half-way, the copies already queued
     // still reference the caller's buffers: the stream is drained before the error is returned, so that a failed submit
     // never leaves the slot (or the caller's memory) in flight.
@@ -1401,17 +1522,18 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
         HIP_TRY(hipEventRecord(s.ev[0], s.stream));
         if (n) {
             HIP_TRY(hipMemcpyAsync(s.d_req, io->requests, (size_t)n * req_size(p), hipMemcpyHostToDevice, s.stream));
+            if (ref) HIP_TRY(hipMemcpyAsync(s.d_tpos, text_pos, (size_t)n * 8, hipMemcpyHostToDevice, s.stream));
             if (packed) {
                 HIP_TRY(hipMemcpyAsync(s.d_packP, io->packed_patterns, (size_t)n * rowb, hipMemcpyHostToDevice, s.stream));
-                HIP_TRY(hipMemcpyAsync(s.d_packT, io->packed_texts, (size_t)n * rowb, hipMemcpyHostToDevice, s.stream));
+                if (!ref) HIP_TRY(hipMemcpyAsync(s.d_packT, io->packed_texts, (size_t)n * rowb, hipMemcpyHostToDevice, s.stream));
                 if (io->n_raw) {
                     HIP_TRY(hipMemcpyAsync(s.d_rawidx, io->raw_pairs, (size_t)io->n_raw * 4, hipMemcpyHostToDevice, s.stream));
                     HIP_TRY(hipMemcpyAsync(s.d_rawP, io->raw_patterns, (size_t)io->n_raw * rs, hipMemcpyHostToDevice, s.stream));
-                    HIP_TRY(hipMemcpyAsync(s.d_rawT, io->raw_texts, (size_t)io->n_raw * rs, hipMemcpyHostToDevice, s.stream));
+                    if (!ref) HIP_TRY(hipMemcpyAsync(s.d_rawT, io->raw_texts, (size_t)io->n_raw * rs, hipMemcpyHostToDevice, s.stream));
                 }
             } else {
                 HIP_TRY(hipMemcpyAsync(s.d_pat, io->patterns, (size_t)n * rs, hipMemcpyHostToDevice, s.stream));
-                HIP_TRY(hipMemcpyAsync(s.d_txt, io->texts, (size_t)n * rs, hipMemcpyHostToDevice, s.stream));
+                if (!ref) HIP_TRY(hipMemcpyAsync(s.d_txt, io->texts, (size_t)n * rs, hipMemcpyHostToDevice, s.stream));
             }
         }
         HIP_TRY(hipEventRecord(s.ev[1], s.stream));
@@ -1427,25 +1549,68 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
             // Does the alignment kernel of this configuration take the batch as it arrived and deliver what was asked for?
             // (wfa_lane_packed_kernel: packed rows in, {idx, score} or compact CIGAR out.) Then this batch is ONE kernel;
             // otherwise the conversion kernels of batch_io.hpp run around the default-ABI kernel.
-            const uint32_t mode = (packed ? MODE_PACKED_IN : 0u) | ((io->cigars && !io->results && !io->ops) ? MODE_RUNS_OUT : 0u);
-            const Plan pl = plan_for_batch(set, d, s, n, mode);
+            uint32_t mode = (packed ? MODE_PACKED_IN : 0u) | ((io->cigars && !io->results && !io->ops) ? MODE_RUNS_OUT : 0u);
+            Plan pl = plan_for_batch(set, d, s, n, mode);
+            // AIM_FLAG_REF_TEXTS: a packed batch keeps the fused packed lane kernel (its texts gathered as packed rows, the windows
+            // holding a byte outside A/C/G/T re-aligned by the general kernel over a to-do list); every other plan runs as for an
+            // ASCII batch after the gather
+            Stage ref_fb;
+            const bool ref_fused = ref && packed && pl.pk && pl.main.kid == K_WFA_LANE_PK && !pl.pack_first && s.d_reftodo &&
+                                   ref_todo_stage(set, d, s.scratch_bytes, n, &ref_fb);
+            if (ref && packed && !ref_fused && pl.pk) {
+                mode &= ~MODE_PACKED_IN;
+                pl = plan_for_batch(set, d, s, n, mode);
+            }
             const uint32_t runs_cap = std::min(io->runs_cap, set->max_runs);
             if (packed && !pl.pk) {   // expand into the reference's char[n][READ_SIZE] layout (batch_io.hpp), then run as usual
                 const uint64_t threads = (uint64_t)n * (rs / 8);
-                hipLaunchKernelGGL(aim::unpack_rows_kernel, dim3((unsigned)((threads + 255) / 256), 2), dim3(256), 0, s.stream, ka, s.d_packP,
+                const unsigned rows = ref ? 1u : 2u;   // (grid.y 0: patterns; the texts of a reference batch are gathered below)
+                hipLaunchKernelGGL(aim::unpack_rows_kernel, dim3((unsigned)((threads + 255) / 256), rows), dim3(256), 0, s.stream, ka, s.d_packP,
                                    s.d_packT, s.d_pat, s.d_txt);
                 if (io->n_raw) {
                     const uint64_t rt = (uint64_t)io->n_raw * (rs / 8);
-                    hipLaunchKernelGGL(aim::scatter_raw_rows_kernel, dim3((unsigned)((rt + 255) / 256), 2), dim3(256), 0, s.stream, p.read_size,
+                    hipLaunchKernelGGL(aim::scatter_raw_rows_kernel, dim3((unsigned)((rt + 255) / 256), rows), dim3(256), 0, s.stream, p.read_size,
                                        io->n_raw, s.d_rawidx, s.d_rawP, s.d_rawT, s.d_pat, s.d_txt);
                 }
                 HIP_TRY(hipGetLastError());
+            }
+            uint32_t *ref_todo = s.d_reftodo;
+            if (ref_fused) {
+                // packed text rows + to-do list; the side list's (non-ACGT patterns) text rows as ASCII for the raw side pass
+                uint32_t *flag_bits = ref_todo + 16 + set->max_pairs;
+                HIP_TRY(hipMemsetAsync(ref_todo, 0, 64, s.stream));
+                HIP_TRY(hipMemsetAsync(flag_bits, 0, ((size_t)n + 31) / 32 * 4, s.stream));
+                const uint64_t threads = (uint64_t)n * aim::packed_row_dwords(p.read_size);
+                hipLaunchKernelGGL(aim::gather_text_packed_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s.stream, ka, s.d_tpos,
+                                   d.d_ref, d.ref_len, s.d_packT, flag_bits, ref_todo);
+                HIP_TRY(hipGetLastError());
+                rc = enqueue_gather(ka, s.d_tpos, d.d_ref, d.ref_len, s.d_rawidx, io->n_raw, s.d_rawT, s.stream);
+                if (rc) return rc;
+            } else if (ref) {
+                rc = enqueue_gather(ka, s.d_tpos, d.d_ref, d.ref_len, nullptr, n, s.d_txt, s.stream);
+                if (rc) return rc;
             }
             FusedIo fio;
             if (pl.pk) { fio.packedP = s.d_packP; fio.packedT = s.d_packT; }
             if (pl.emits_runs) { fio.cig = s.d_cig; fio.runs = s.d_runs; fio.cursor = s.d_cursor; fio.runs_cap = runs_cap; }
             rc = launch_on_slot(set, d, s, mode, &fio);
             if (rc) return rc;
+            if (ref_fused) {
+                // the to-do windows: ASCII rows (pattern unpacked, text gathered), the general kernel over them, their compact CIGAR
+                hipLaunchKernelGGL(aim::gather_todo_rows_kernel, dim3(256), dim3(256), 0, s.stream, ka, ref_todo, s.d_tpos, d.d_ref, d.ref_len,
+                                   s.d_packP, s.d_pat, s.d_txt);
+                HIP_TRY(hipGetLastError());
+                aim::KArgs kb = stage_args(ka, ref_fb, s.d_scratch);
+                kb.patterns = s.d_pat;
+                kb.texts = s.d_txt;
+                kb.todo = ref_todo;
+                launch_stage(p, ref_fb, kb, s.stream);
+                HIP_TRY(hipGetLastError());
+                if (pl.emits_runs) {
+                    hipLaunchKernelGGL(aim::cigar_rle_todo_kernel, dim3(256), dim3(64), 0, s.stream, kb, ref_todo, s.d_cig, s.d_runs, runs_cap, s.d_cursor);
+                    HIP_TRY(hipGetLastError());
+                }
+            }
             s.runs_sent = pl.emits_runs ? n * fio.run_slot : 0u;   // 0 when the run buffer is bump-allocated: nothing is known before the kernel ran
             if (io->cigars && !pl.emits_runs) {
                 HIP_TRY(hipMemsetAsync(s.d_cursor, 0, 4, s.stream));
@@ -1610,8 +1775,53 @@ int aim_set_plan_describe(const aim_set_t *set, uint32_t device, char *out, size
 int aim_set_free(aim_set_t *set)
 {
     if (!set) return AIM_OK;
-    for (auto &d : set->devs) free_device_buffers(d);
+    for (auto &d : set->devs) {
+        free_device_buffers(d);
+        if (d.d_ref) {
+            (void)hipSetDevice(d.dev);
+            (void)hipFree(d.d_ref);
+            d.d_ref = nullptr;
+        }
+    }
     delete set;
+    return AIM_OK;
+}
+
+int aim_set_reference(aim_set_t *set, const char *seq, uint64_t len)
+{
+    if (!set || (len && !seq)) return fail(AIM_EINVAL, "bad arguments");
+    if (len > (1ull << 62)) return fail(AIM_EINVAL, "reference length %llu does not fit text_pos", (unsigned long long)len);
+    // every device's copy first; the old references are released only once all of them exist (AIM_ENOMEM keeps the old one)
+    std::vector<char *> fresh(set->devs.size(), nullptr);
+    auto drop = [&]() {
+        for (size_t i = 0; i < fresh.size(); ++i)
+            if (fresh[i]) { (void)hipSetDevice(set->devs[i].dev); (void)hipFree(fresh[i]); }
+    };
+    const size_t slack = 64;   // zeroed; the gather reads at most aim::kRefSlack bytes past the end
+    for (size_t i = 0; i < set->devs.size(); ++i) {
+        hipError_t e = hipSetDevice(set->devs[i].dev);
+        if (e == hipSuccess) e = hipMalloc((void **)&fresh[i], (size_t)len + slack);
+        if (e == hipSuccess) e = hipMemset(fresh[i] + len, 0, slack);
+        if (e == hipSuccess && len) e = hipMemcpy(fresh[i], seq, (size_t)len, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            if (e == hipErrorOutOfMemory) fresh[i] = nullptr;
+            drop();
+            return fail(e == hipErrorOutOfMemory ? AIM_ENOMEM : AIM_ENODEV, "reference of %llu bytes on device %d: %s (the previous reference stays)",
+                        (unsigned long long)len, set->devs[i].dev, hipGetErrorString(e));
+        }
+    }
+    for (size_t i = 0; i < set->devs.size(); ++i) {
+        aim_device_ctx &d = set->devs[i];
+        HIP_TRY(hipSetDevice(d.dev));
+        if (d.d_ref) {
+            for (auto &s : d.slots) HIP_TRY(hipStreamSynchronize(s.stream));   // batches in flight still read the old reference
+            HIP_TRY(hipFree(d.d_ref));
+        }
+        d.d_ref = fresh[i];
+        d.ref_len = len;
+        fresh[i] = nullptr;
+    }
     return AIM_OK;
 }
 
@@ -1633,7 +1843,54 @@ size_t aim_scratch_bytes(const aim_params_t *params, uint32_t n_pairs)
     Plan pl;
     const aim::Knobs kn = read_knobs();
     if (!params || make_plan(*params, n_pairs, kn, stateless_budget_bytes(kn), &pl)) return 0;
+    if (is_ref(*params)) return ref_rows_at(pl.scratch_total) + ref_rows_bytes(*params, n_pairs);   // + the gathered text rows
     return pl.scratch_total;
+}
+
+int aim_align_device_ref(const aim_params_t *params, uint32_t n_pairs, const void *d_requests, const char *d_patterns,
+                         const uint64_t *d_text_pos, const char *d_reference, uint64_t ref_len, void *d_results, char *d_ops,
+                         void *d_scratch, size_t scratch_bytes, void *hip_stream)
+{
+    if (!params) return fail(AIM_EINVAL, "params is NULL");
+    if (!is_ref(*params)) return fail(AIM_EINVAL, "aim_align_device_ref needs AIM_FLAG_REF_TEXTS");
+    if (n_pairs && (!d_text_pos || !d_reference || !d_requests)) return fail(AIM_EINVAL, "null device buffer");
+    int n = 0;
+    int rc = aim_device_count(&n);
+    if (rc) return rc;
+    const aim::Knobs kn = read_knobs();
+    Plan pl;
+    rc = make_plan(*params, n_pairs, kn, stateless_budget_bytes(kn), &pl);
+    if (rc) return rc;
+    const size_t at = ref_rows_at(pl.scratch_total), need = at + ref_rows_bytes(*params, n_pairs);
+    if (!d_scratch || scratch_bytes < need) return fail(AIM_EINVAL, "scratch too small: need %zu bytes, got %zu", need, scratch_bytes);
+    if (n_pairs == 0) return AIM_OK;
+    char *rows = static_cast<char *>(d_scratch) + at;
+    aim::KArgs ka;
+    memset(&ka, 0, sizeof ka);
+    ka.p = *params;
+    ka.n_pairs = n_pairs;
+    ka.req = static_cast<const aim_request_t *>(d_requests);
+    rc = enqueue_gather(ka, d_text_pos, d_reference, ref_len, nullptr, n_pairs, rows, (hipStream_t)hip_stream);
+    if (rc) return rc;
+    return launch(pl, kn, *params, n_pairs, d_requests, d_patterns, rows, d_results, d_ops, d_scratch, at, (hipStream_t)hip_stream);
+}
+
+int aim_ref_windows_check(const aim_params_t *params, uint32_t n_pairs, const void *requests, const uint64_t *text_pos, uint64_t ref_len,
+                          uint32_t *bad_pair)
+{
+    if (!params || (n_pairs && (!requests || !text_pos))) return fail(AIM_EINVAL, "bad arguments");
+    int rc = check_lengths(*params, n_pairs, requests);
+    if (rc) {
+        if (bad_pair)   // name the pair check_lengths refused
+            for (uint32_t i = 0; i < n_pairs; ++i) {
+                const bool r8 = params->flags & AIM_FLAG_REQ8;
+                const int tl = r8 ? static_cast<const aim_request8_t *>(requests)[i].text_len : static_cast<const aim_request_t *>(requests)[i].text_len;
+                const int pl = r8 ? static_cast<const aim_request8_t *>(requests)[i].pattern_len : static_cast<const aim_request_t *>(requests)[i].pattern_len;
+                if (pl < 0 || tl < 0 || pl > params->read_size || tl > params->read_size) { *bad_pair = i; break; }
+            }
+        return rc;
+    }
+    return check_windows(*params, n_pairs, requests, text_pos, ref_len, bad_pair);
 }
 
 int aim_align_device(const aim_params_t *params, uint32_t n_pairs, const void *d_requests,
@@ -1737,7 +1994,9 @@ int aim_pack_batch(const aim_params_t *params, uint32_t n_pairs, const void *req
                    uint32_t *packed_patterns, uint32_t *packed_texts, uint32_t *raw_pairs, char *raw_patterns, char *raw_texts,
                    uint32_t max_raw, uint32_t *n_raw, int threads)
 {
-    if (!params || !n_raw || (n_pairs && (!requests || !patterns || !texts || !packed_patterns || !packed_texts)))
+    // AIM_FLAG_REF_TEXTS: the texts are windows of the device's reference; only the patterns are packed (texts / packed_texts may be NULL)
+    const bool ref = params && is_ref(*params);
+    if (!params || !n_raw || (n_pairs && (!requests || !patterns || !packed_patterns || (!ref && (!texts || !packed_texts)))))
         return fail(AIM_EINVAL, "bad arguments");
     const int rs = params->read_size;
     if (rs <= 0 || (rs & 7)) return fail(AIM_EINVAL, "read_size must be a positive multiple of 8");
@@ -1754,7 +2013,7 @@ int aim_pack_batch(const aim_params_t *params, uint32_t n_pairs, const void *req
             const int pl = req8 ? static_cast<const aim_request8_t *>(requests)[i].pattern_len : static_cast<const aim_request_t *>(requests)[i].pattern_len;
             const int tl = req8 ? static_cast<const aim_request8_t *>(requests)[i].text_len : static_cast<const aim_request_t *>(requests)[i].text_len;
             const int okp = aim_pack_sequence(patterns + i * rs, pl, rs, packed_patterns + i * dw);
-            const int okt = aim_pack_sequence(texts + i * rs, tl, rs, packed_texts + i * dw);
+            const int okt = (texts && packed_texts) ? aim_pack_sequence(texts + i * rs, tl, rs, packed_texts + i * dw) : 1;
             is_raw[i] = !(okp == 1 && okt == 1);
         }
     };
@@ -1765,10 +2024,10 @@ int aim_pack_batch(const aim_params_t *params, uint32_t n_pairs, const void *req
     uint32_t n = 0;
     for (uint32_t i = 0; i < n_pairs; ++i) {
         if (!is_raw[i]) continue;
-        if (n < max_raw && raw_pairs && raw_patterns && raw_texts) {
+        if (n < max_raw && raw_pairs && raw_patterns && (raw_texts || !texts)) {
             raw_pairs[n] = i;
             memcpy(raw_patterns + (size_t)n * rs, patterns + (size_t)i * rs, (size_t)rs);
-            memcpy(raw_texts + (size_t)n * rs, texts + (size_t)i * rs, (size_t)rs);
+            if (raw_texts && texts) memcpy(raw_texts + (size_t)n * rs, texts + (size_t)i * rs, (size_t)rs);
         }
         ++n;
     }

@@ -4,10 +4,13 @@
 //     byte outside A/C/G/T, which travel as raw rows) is expanded in HBM into the reference's own layout --
 //     char[n][READ_SIZE] ASCII rows (WFA/DPU-WRAM/host/host.c:126-127, 258-268) -- so every alignment kernel runs
 //     unchanged and bit-exact.  What crosses PCIe is READ_SIZE/4 bytes per sequence instead of READ_SIZE.
+//   * gather_text_rows_kernel / gather_text_packed_kernel / gather_todo_rows_kernel (AIM_FLAG_REF_TEXTS): texts named as
+//     (position, strand) windows of a device-resident reference are gathered into the same char[n][READ_SIZE] rows (or into
+//     packed rows plus a to-do list of the windows holding a byte outside A/C/G/T, for the fused packed lane kernel).
 //   * cigar_rle_kernel: the run-length encoding edit_cigar_print does on the host (host.c:69-89) done on the device
 //     over ops[begin_offset, end_offset), so that ~3 runs per pair cross PCIe instead of 2*READ_SIZE op bytes.
 //
-// Both are pure data movement: HBM-bound, coalesced, no LDS.
+// All are pure data movement: HBM-bound, coalesced, no LDS.
 #pragma once
 
 #include "aim_device.hpp"
@@ -261,6 +264,172 @@ __global__ __launch_bounds__(256) void unpack_todo_rows_kernel(KArgs a, const ui
             w1 &= (uint32_t)(keep >> 32);
         }
         reinterpret_cast<uint2 *>((is_text ? outT : outP) + (uint64_t)pair * rs)[piece] = make_uint2(w0, w1);
+    }
+}
+
+// ---- reference windows (AIM_FLAG_REF_TEXTS) -------------------------------------------------------------------------------
+// text_pos = window start (bits 0..62) | strand << 63. Strand 0: text[i] = ref[pos + i]; strand 1: text[i] = comp(ref[pos + len - 1 - i]),
+// comp swapping A<->T, C<->G, a<->t, c<->g and keeping every other byte. Loads never leave [0, ref_len + kRefSlack): a window the
+// host check would refuse (stateless callers) reads zeros where it runs out, never outside the buffer.
+constexpr uint64_t kRefSlack = 16;                 // addressable bytes behind the reference (aim_hip.h: the row buffers' slack)
+constexpr uint64_t kRefPosMask = ~(1ull << 63);
+
+// per-byte complement of four bytes: A^T = a^t = 0x15, C^G = c^g = 0x04 (selects built from exact per-byte equality masks)
+__device__ __forceinline__ uint32_t ref_comp4(uint32_t x)
+{
+    const uint32_t u = x & 0xDFDFDFDFu;             // fold case (bit 5): only 'A' / 'a' map to 0x41, etc.
+    const uint32_t zA = ~nonzero_byte_mask(u ^ 0x41414141u), zT = ~nonzero_byte_mask(u ^ 0x54545454u);
+    const uint32_t zC = ~nonzero_byte_mask(u ^ 0x43434343u), zG = ~nonzero_byte_mask(u ^ 0x47474747u);
+    const uint32_t at = ((zA | zT) & 0x80808080u) >> 7, cg = ((zC | zG) & 0x80808080u) >> 7;   // 0x01 per selected byte
+    return x ^ (at * 0x15u) ^ (cg * 0x04u);
+}
+
+typedef uint32_t ref_u32x2 __attribute__((ext_vector_type(2), aligned(4)));
+
+// NW dwords of the reference from byte offset s (may be negative or past the end: such dwords read as zero). Aligned wide loads of
+// NW + 1 dwords, then a byte funnel (v_alignbyte) to the unaligned start.
+template <int NW>
+__device__ __forceinline__ void ref_load(const char *ref, int64_t s, uint64_t lim, uint32_t (&w)[NW])
+{
+    const int64_t a = s & ~(int64_t)3;
+    const uint32_t sh = (uint32_t)(s & 3);
+    const uint32_t *p = reinterpret_cast<const uint32_t *>(ref + a);
+    uint32_t d[NW + 1];
+    if (a >= 0 && (uint64_t)a + 4u * (NW + 1) <= lim) {
+        if constexpr (NW == 4) {
+            const pk_in_u32x4 v = *reinterpret_cast<const pk_in_u32x4 *>(p);
+            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        } else {
+            const ref_u32x2 v = *reinterpret_cast<const ref_u32x2 *>(p);
+            d[0] = v.x; d[1] = v.y;
+        }
+        d[NW] = p[NW];
+    } else {
+#pragma unroll
+        for (int k = 0; k <= NW; ++k) {
+            const int64_t ak = a + 4 * k;
+            d[k] = (ak >= 0 && (uint64_t)ak + 4u <= lim) ? p[k] : 0u;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NW; ++i) w[i] = __builtin_amdgcn_alignbyte(d[i + 1], d[i], sh);
+}
+
+// Bytes [o, o + 4 NW) of one text row: the window's bytes, zero at and past len.
+template <int NW>
+__device__ __forceinline__ void ref_piece(const char *ref, uint64_t ref_len, uint64_t tp, int len, int o, uint32_t (&w)[NW])
+{
+    const int rem = len - o;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) w[i] = 0u;
+    if (rem <= 0) return;
+    const uint64_t lim = ref_len + kRefSlack;
+    const uint64_t pos = min(tp & kRefPosMask, lim);   // (no overflow below for positions a check would refuse)
+    if (!(tp >> 63)) {
+        ref_load<NW>(ref, (int64_t)pos + o, lim, w);
+    } else {
+        // the source of bytes o .. o + 4 NW - 1 is ref[pos + len - o - 4 NW, pos + len - o), read forward, then reversed with
+        // v_perm (dword order and bytes) and complemented
+        uint32_t f[NW];
+        ref_load<NW>(ref, (int64_t)pos + len - o - 4 * NW, lim, f);
+#pragma unroll
+        for (int i = 0; i < NW; ++i) w[i] = ref_comp4(__builtin_amdgcn_perm(0u, f[NW - 1 - i], 0x00010203u));
+    }
+    if (rem < 4 * NW) {
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            const int r = rem - 4 * i;
+            w[i] &= r >= 4 ? ~0u : (r <= 0 ? 0u : ((1u << (8 * r)) - 1u));
+        }
+    }
+}
+
+// ASCII text rows: one thread writes W = 4 NW bytes of one row (16-B stores when READ_SIZE is a multiple of 16, else 8-B).
+// Row r is the window of pair idx[r] (idx == nullptr: pair r); rows [0, n_rows) of `out`.
+template <int NW>
+__global__ __launch_bounds__(256) void gather_text_rows_kernel(KArgs a, const uint64_t *text_pos, const char *ref, uint64_t ref_len, const uint32_t *idx,
+                                                               uint32_t n_rows, char *out)
+{
+    const int rs = a.p.read_size;
+    const uint32_t per_row = (uint32_t)rs / (4u * NW);
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (uint64_t)n_rows * per_row) return;
+    const uint32_t row = (uint32_t)(t / per_row), piece = (uint32_t)(t - (uint64_t)row * per_row);
+    const uint32_t pair = idx ? idx[row] : row;
+    const int len = load_request(a, pair).text_len;
+    uint32_t w[NW];
+    ref_piece<NW>(ref, ref_len, text_pos[pair], len, (int)piece * 4 * NW, w);
+    char *dst = out + (uint64_t)row * rs + (uint64_t)piece * 4 * NW;
+    if constexpr (NW == 4) *reinterpret_cast<uint4 *>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+    else *reinterpret_cast<uint2 *>(dst) = make_uint2(w[0], w[1]);
+}
+
+// Packed text rows for the fused packed lane kernel: one thread gathers 16 bases and packs them into one dword (pack_rows_kernel's
+// encoding and check); a window holding a byte outside A/C/G/T is appended once (flag bit per pair) to the to-do list
+// {count @0, pair ids @16..}, whose pairs gather_todo_rows_kernel then writes as ASCII rows for the general kernel.
+__global__ __launch_bounds__(256) void gather_text_packed_kernel(KArgs a, const uint64_t *text_pos, const char *ref, uint64_t ref_len, uint32_t *packedT,
+                                                                 uint32_t *flag_bits, uint32_t *todo)
+{
+    const int rs = a.p.read_size;
+    const uint32_t npw = packed_row_dwords(rs);
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (uint64_t)a.n_pairs * npw) return;
+    const uint32_t pair = (uint32_t)(t / npw), j = (uint32_t)(t - (uint64_t)pair * npw);
+    const int len = load_request(a, pair).text_len;
+    uint32_t w[4];
+    ref_piece<4>(ref, ref_len, text_pos[pair], len, (int)(16u * j), w);
+    uint32_t out = 0, bad = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int rem = len - (int)(16u * j + 4u * i);
+        const uint32_t mask = rem >= 4 ? ~0u : (rem <= 0 ? 0u : ((1u << (8 * rem)) - 1u));
+        const uint32_t c = (w[i] >> 1) & 0x03030303u & mask;
+        const uint32_t rec = __builtin_amdgcn_perm(0u, 0x47544341u, c) & mask;
+        bad |= rec ^ w[i];
+        out |= __builtin_amdgcn_udot4(c, 0x40100401u, 0u, false) << (8 * i);
+    }
+    packedT[t] = out;
+    if (bad) {
+        const uint32_t bit = 1u << (pair & 31u);
+        const uint32_t old = atomicOr(&flag_bits[pair >> 5], bit);
+        if (!(old & bit)) {
+            const uint32_t slot = atomicAdd(&todo[0], 1u);
+            todo[16 + slot] = pair;
+        }
+    }
+}
+
+// The to-do pairs of gather_text_packed_kernel as ASCII rows (8 bytes per thread): the pattern expanded from its packed row, the text
+// gathered from the reference.
+__global__ __launch_bounds__(256) void gather_todo_rows_kernel(KArgs a, const uint32_t *todo, const uint64_t *text_pos, const char *ref, uint64_t ref_len,
+                                                               const uint32_t *packedP, char *outP, char *outT)
+{
+    const int rs = a.p.read_size;
+    const uint32_t per_row = (uint32_t)rs / 8u;
+    const uint64_t total = (uint64_t)todo[0] * per_row * 2u;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const bool is_text = t & 1u;
+        const uint64_t u = t >> 1;
+        const uint32_t pair = todo[16 + (uint32_t)(u / per_row)], piece = (uint32_t)(u % per_row);
+        const aim_request_t rq = load_request(a, pair);
+        uint32_t w[2];
+        if (is_text) {
+            ref_piece<2>(ref, ref_len, text_pos[pair], rq.text_len, (int)piece * 8, w);
+        } else {
+            const uint32_t bits = reinterpret_cast<const uint16_t *>(packedP + (uint64_t)pair * packed_row_dwords(rs))[piece];
+            const uint32_t lo = (bits & 3u) | ((bits & 0xCu) << 6) | ((bits & 0x30u) << 12) | ((bits & 0xC0u) << 18);
+            const uint32_t hb = bits >> 8;
+            const uint32_t hi = (hb & 3u) | ((hb & 0xCu) << 6) | ((hb & 0x30u) << 12) | ((hb & 0xC0u) << 18);
+            w[0] = __builtin_amdgcn_perm(0u, 0x47544341u, lo);
+            w[1] = __builtin_amdgcn_perm(0u, 0x47544341u, hi);
+            const int rem = rq.pattern_len - (int)piece * 8;
+            if (rem < 8) {
+                const uint64_t keep = rem <= 0 ? 0ull : ((1ull << (8 * rem)) - 1ull);
+                w[0] &= (uint32_t)keep;
+                w[1] &= (uint32_t)(keep >> 32);
+            }
+        }
+        reinterpret_cast<uint2 *>((is_text ? outT : outP) + (uint64_t)pair * rs)[piece] = make_uint2(w[0], w[1]);
     }
 }
 

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import capi
 from .capi import (ALGO_BY_NAME, ALGO_NW, ALGO_SWG, ALGO_WFA, FLAG_AFFINE2P, FLAG_BACKTRACE, FLAG_ENDSFREE, FLAG_LINEAR, FLAG_REDUCE,
-                   FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16, FLAG_WFA_BIDIR, FLAG_WFA_W32, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
+                   FLAG_REF_TEXTS, FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16, FLAG_WFA_BIDIR, FLAG_WFA_W32, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
                    Params, params_ref)
 
 
@@ -37,19 +37,20 @@ def features():
 
 def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=1, gap=4, backtrace=False,
                 reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None, gap2=None, linear=False,
-                w32=False, bidir=False):
+                w32=False, bidir=False, ref_texts=False):
     """`gap` is the launchers' single NW gap cost (run-nw-pim-wram.py: -DGAP_I = -DGAP_D); `gap_i` / `gap_d` set the two macros of
     nw.c:67-153 apart (NW/DPU-WRAM/common/common.h GAP_I, GAP_D). `ends_free=(PB, PE, TB, TE)`: ends-free WFA (AIM_FLAG_ENDSFREE);
     returns an EndsFreeParams then, which every call below accepts like Params. `gap2=(O2, E2)`: dual-cost gap-affine WFA
     (AIM_FLAG_AFFINE2P, gap_o / gap_e are piece 1); returns an Affine2pParams. The two cannot be combined. `linear=True`: gap-linear
     WFA (AIM_FLAG_LINEAR): a mismatch costs `mismatch`, every gap base `gap_e`, and gap_o is set to 0; not with ends_free, gap2 or
     reduce. `w32=True`: WFA with 32-bit wavefront offsets (AIM_FLAG_WFA_W32), read_size up to 2^24; combines with all of the above.
-    `bidir=True`: bidirectional WFA (AIM_FLAG_WFA_BIDIR), CIGAR in O(MAX_SCORE) scratch; global gap-affine with backtrace only."""
+    `bidir=True`: bidirectional WFA (AIM_FLAG_WFA_BIDIR), CIGAR in O(MAX_SCORE) scratch; global gap-affine with backtrace only.
+    `ref_texts=True`: texts named as windows of the device-resident reference (AIM_FLAG_REF_TEXTS); combines with everything."""
     a = ALGO_BY_NAME[algo] if isinstance(algo, str) else algo
     gap_i = gap if gap_i is None else gap_i
     gap_d = gap if gap_d is None else gap_d
     flags = (FLAG_BACKTRACE if backtrace else 0) | (FLAG_REDUCE if reduce else 0) | (FLAG_SWG_W16 if swg_w16 else 0)
-    flags |= (FLAG_REQ8 if req8 else 0) | (FLAG_RES8 if res8 else 0) | (FLAG_WFA_W32 if w32 else 0)
+    flags |= (FLAG_REQ8 if req8 else 0) | (FLAG_RES8 if res8 else 0) | (FLAG_WFA_W32 if w32 else 0) | (FLAG_REF_TEXTS if ref_texts else 0)
     if bidir:
         if not backtrace:
             raise ValueError("bidir needs backtrace")
@@ -144,6 +145,57 @@ def long_indel_pairs(seed, first_idx, req, pat, txt, long_indel):
     return req2, pat2, txt2
 
 
+_COMP = np.arange(256, dtype=np.uint8)
+for _a, _b in (b"AT", b"CG", b"at", b"cg"):
+    _COMP[_a], _COMP[_b] = _b, _a
+
+
+def ref_window(reference, pos, length, minus):
+    """The text AIM_FLAG_REF_TEXTS names: reference[pos, pos + length), reverse-complemented on the minus strand (A<->T, C<->G,
+    a<->t, c<->g; every other byte unchanged). `reference` is a uint8 array."""
+    w = np.asarray(reference[pos:pos + length], dtype=np.uint8)
+    return _COMP[w[::-1]] if minus else w.copy()
+
+
+def ref_pairs(seed, first_idx, n_pairs, length, error, reference, read_size, minus_fraction=0.5):
+    """Seeded pairs against a reference (AIM_FLAG_REF_TEXTS): each text is a window of `length` bases at a seeded position, on the
+    minus strand with probability `minus_fraction`; its pattern is that text after ceil(length * error) seeded edits with gen_pairs'
+    model (uniform substitute / delete / insert at a uniform position; a substitution may re-draw the same base). Bytes of the
+    window other than A/C/G/T stay in the pattern. Pair i depends only on (seed, first_idx + i) and the reference.
+    Returns (requests, patterns[n][read_size], text_pos[n] uint64, texts[n][read_size]) -- the texts are the explicit rows the
+    windows name, for comparison."""
+    ref = np.frombuffer(reference, dtype=np.uint8) if isinstance(reference, (bytes, bytearray)) else np.asarray(reference, dtype=np.uint8)
+    nedits = int(math.ceil(length * error))
+    if length > len(ref):
+        raise ValueError("reference shorter than a window")
+    if length + nedits > read_size:
+        raise ValueError("read_size %d too small for length %d + %d edits" % (read_size, length, nedits))
+    acgt = b"ACGT"
+    req = np.zeros(n_pairs, dtype=REQUEST_DTYPE)
+    pat = np.zeros((n_pairs, read_size), dtype=np.uint8)
+    txt = np.zeros((n_pairs, read_size), dtype=np.uint8)
+    tpos = np.zeros(n_pairs, dtype=np.uint64)
+    for i in range(n_pairs):
+        rng = np.random.default_rng([int(seed), int(first_idx) + i, 0x726566])
+        pos = int(rng.integers(0, len(ref) - length + 1))
+        minus = bool(rng.random() < minus_fraction)
+        t = ref_window(ref, pos, length, minus)
+        p = bytearray(t.tobytes())
+        for _ in range(nedits):
+            kind, b, r = int(rng.integers(0, 3)), acgt[int(rng.integers(0, 4))], int(rng.integers(0, 1 << 32))
+            if kind == 0 and p:
+                p[r % len(p)] = b
+            elif kind == 1 and p:
+                del p[r % len(p)]
+            else:
+                p.insert(r % (len(p) + 1), b)
+        txt[i, :length] = t
+        pat[i, :len(p)] = np.frombuffer(bytes(p), dtype=np.uint8)
+        req["pattern_len"][i], req["text_len"][i], req["idx"][i] = len(p), length, int(first_idx) + i
+        tpos[i] = pos | ((1 << 63) if minus else 0)
+    return req, pat, tpos, txt
+
+
 def to_request8(req):
     """aim_request_t[] -> aim_request8_t[] (the reference's own 8-byte WFA request_t; AIM_FLAG_REQ8)."""
     out = np.zeros(len(req), dtype=REQUEST8_DTYPE)
@@ -178,8 +230,12 @@ def pack_rows(req, rows, key):
 
 
 def pack_batch(req, pat, txt):
-    """(packedP, packedT, raw_pairs, rawP, rawT) for aim_set_submit: pairs that cannot be packed go to the raw side list."""
+    """(packedP, packedT, raw_pairs, rawP, rawT) for aim_set_submit: pairs that cannot be packed go to the raw side list.
+    txt=None (AIM_FLAG_REF_TEXTS): only the patterns are packed, packedT and rawT are None and a pair is raw when its pattern is."""
     pp, okp = pack_rows(req, pat, "pattern_len")
+    if txt is None:
+        raw = np.nonzero(~okp)[0].astype(np.uint32)
+        return pp, None, raw, np.ascontiguousarray(pat[raw]), None
     pt, okt = pack_rows(req, txt, "text_len")
     raw = np.nonzero(~(okp & okt))[0].astype(np.uint32)
     return pp, pt, raw, np.ascontiguousarray(pat[raw]), np.ascontiguousarray(txt[raw])
@@ -192,15 +248,19 @@ def pack_batch_native(params, req, pat, txt, threads=8):
     dw = packed_row_dwords(rs)
     if (params.flags & FLAG_REQ8) and req.dtype != REQUEST8_DTYPE:
         req = to_request8(req)
-    req, pat, txt = np.ascontiguousarray(req), np.ascontiguousarray(pat), np.ascontiguousarray(txt)
-    pp, pt = np.zeros((n, dw), dtype=np.uint32), np.zeros((n, dw), dtype=np.uint32)
+    with_txt = txt is not None      # (None: AIM_FLAG_REF_TEXTS, only the patterns are packed; packedT and rawT come back None)
+    req, pat = np.ascontiguousarray(req), np.ascontiguousarray(pat)
+    txt = np.ascontiguousarray(txt) if with_txt else None
+    pp = np.zeros((n, dw), dtype=np.uint32)
+    pt = np.zeros((n, dw), dtype=np.uint32) if with_txt else None
     cap = max(1, n // 8)
-    raw, rawp, rawt = np.zeros(cap, dtype=np.uint32), np.zeros((cap, rs), dtype=np.uint8), np.zeros((cap, rs), dtype=np.uint8)
+    raw, rawp = np.zeros(cap, dtype=np.uint32), np.zeros((cap, rs), dtype=np.uint8)
+    rawt = np.zeros((cap, rs), dtype=np.uint8) if with_txt else None
     nr = C.c_uint32()
     capi.check(lib.aim_pack_batch(params_ref(params), n, capi.ptr(req), capi.ptr(pat), capi.ptr(txt), capi.ptr(pp), capi.ptr(pt),
                                   capi.ptr(raw), capi.ptr(rawp), capi.ptr(rawt), cap, C.byref(nr), threads))
     k = nr.value
-    return pp, pt, raw[:k].copy(), rawp[:k].copy(), rawt[:k].copy()
+    return pp, pt, raw[:k].copy(), rawp[:k].copy(), None if rawt is None else rawt[:k].copy()
 
 
 def format_output_runs(cig, runs):
@@ -314,28 +374,43 @@ class DeviceSet:
         self.max_pairs = max_pairs_per_device
         self._inflight = {}
 
-    def submit(self, device, slot, req, pat=None, txt=None, packed=None, want_ops=False, cigar_runs_cap=0):
+    def set_reference(self, seq):
+        """aim_set_reference: upload `seq` (bytes or a uint8 array, taken verbatim) to every device of the set; replaces the
+        previous reference. Batches then name their texts by text_pos (AIM_FLAG_REF_TEXTS)."""
+        arr = np.frombuffer(seq, dtype=np.uint8) if isinstance(seq, (bytes, bytearray)) else np.ascontiguousarray(seq, dtype=np.uint8)
+        capi.check(self.lib.aim_set_reference(self.handle, arr.ctypes.data if len(arr) else None, len(arr)))
+        self.ref_len = len(arr)
+
+    def submit(self, device, slot, req, pat=None, txt=None, packed=None, want_ops=False, cigar_runs_cap=0, text_pos=None):
         """aim_set_submit: ASCII rows (pat, txt) or a packed batch (pack_batch(...)); results / ops / compact CIGAR buffers
-        are allocated here and returned by wait()."""
+        are allocated here and returned by wait(). text_pos (AIM_FLAG_REF_TEXTS): the texts are windows of the reference; pass
+        pat (or packed = pack_batch(req, pat, None)) and no texts."""
         if (self.params.flags & FLAG_REQ8) and req.dtype != REQUEST8_DTYPE:
             req = to_request8(req)
         req = np.ascontiguousarray(req)
         n, rs = len(req), self.params.read_size
-        io = capi.BatchIO()
+        rio = capi.BatchIORef()
+        io = rio.base
         io.n_pairs = n
         keep = [req]
         io.requests = req.ctypes.data
+        if text_pos is not None:
+            tp = np.ascontiguousarray(text_pos, dtype=np.uint64)
+            keep.append(tp)
+            rio.text_pos = tp.ctypes.data
+        addr = lambda x: None if x is None else x.ctypes.data
         if packed is not None:
-            pp, pt, raw, rawp, rawt = [np.ascontiguousarray(x) for x in packed]
+            pp, pt, raw, rawp, rawt = [None if x is None else np.ascontiguousarray(x) for x in packed]
             keep += [pp, pt, raw, rawp, rawt]
-            io.packed_patterns, io.packed_texts = pp.ctypes.data, pt.ctypes.data
+            io.packed_patterns, io.packed_texts = addr(pp), addr(pt)
             io.n_raw = len(raw)
             if len(raw):
-                io.raw_pairs, io.raw_patterns, io.raw_texts = raw.ctypes.data, rawp.ctypes.data, rawt.ctypes.data
+                io.raw_pairs, io.raw_patterns, io.raw_texts = addr(raw), addr(rawp), addr(rawt)
         else:
-            pat, txt = np.ascontiguousarray(pat), np.ascontiguousarray(txt)
+            pat = np.ascontiguousarray(pat)
+            txt = None if txt is None else np.ascontiguousarray(txt)
             keep += [pat, txt]
-            io.patterns, io.texts = pat.ctypes.data, txt.ctypes.data
+            io.patterns, io.texts = addr(pat), addr(txt)
         out = {}
         if cigar_runs_cap:
             out["cig"] = np.zeros(n, dtype=capi.CIGAR_DTYPE)
@@ -348,7 +423,7 @@ class DeviceSet:
             out["ops"] = np.zeros((n, 2 * rs), dtype=np.uint8)
             io.ops = out["ops"].ctypes.data
         capi.check(self.lib.aim_set_submit(self.handle, device, slot, C.byref(io)))
-        self._inflight[(device, slot)] = (io, keep, out)
+        self._inflight[(device, slot)] = (rio, keep, out)
 
     def wait(self, device, slot, check=True):
         io, keep, out = self._inflight.pop((device, slot), (None, None, {}))   # nothing in flight: the library reports AIM_ESTATE
@@ -360,15 +435,21 @@ class DeviceSet:
             out["runs"] = out["runs"][: nr.value]
         return out
 
-    def push(self, device, req, pat, txt):
+    def push(self, device, req, pat, txt=None, text_pos=None):
+        """aim_set_push, or aim_set_push_ref when text_pos is given (AIM_FLAG_REF_TEXTS: the texts are windows of the reference)."""
         if (self.params.flags & FLAG_REQ8) and req.dtype != REQUEST8_DTYPE:
             req = to_request8(req)
         req = np.ascontiguousarray(req)
         pat = np.ascontiguousarray(pat)
-        txt = np.ascontiguousarray(txt)
         self._keep = getattr(self, "_keep", {})
-        self._keep[device] = (req, pat, txt)   # host buffers must outlive the async copies
-        capi.check(self.lib.aim_set_push(self.handle, device, len(req), capi.ptr(req), capi.ptr(pat), capi.ptr(txt)))
+        if text_pos is not None:
+            tp = np.ascontiguousarray(text_pos, dtype=np.uint64)
+            self._keep[device] = (req, pat, tp)   # host buffers must outlive the async copies
+            capi.check(self.lib.aim_set_push_ref(self.handle, device, len(req), capi.ptr(req), capi.ptr(pat), capi.ptr(tp)))
+        else:
+            txt = np.ascontiguousarray(txt)
+            self._keep[device] = (req, pat, txt)   # host buffers must outlive the async copies
+            capi.check(self.lib.aim_set_push(self.handle, device, len(req), capi.ptr(req), capi.ptr(pat), capi.ptr(txt)))
         self._n = getattr(self, "_n", {})
         self._n[device] = len(req)
 
@@ -401,17 +482,24 @@ class DeviceSet:
         capi.check(self.lib.aim_set_timers(self.handle, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
-    def align(self, params, req, pat, txt, check=True):
-        """Whole batch over all devices of the set: contiguous blocks (host.c:191-209), results in input order."""
+    def align(self, params, req, pat, txt, check=True, reference=None, text_pos=None):
+        """Whole batch over all devices of the set: contiguous blocks (host.c:191-209), results in input order. With text_pos
+        (params carry AIM_FLAG_REF_TEXTS) the texts are windows of `reference` (uploaded here when given, else the set's) and txt
+        is not read."""
         n = len(req)
         per = max(1, math.ceil(n / self.nr_devices))
         if self.params is None or bytes(self.params) != bytes(params) or per > self.max_pairs:   # (EndsFreeParams: the extension too)
             self.configure(params, per)
+        if reference is not None:
+            self.set_reference(reference)
         blocks = []
         for d in range(self.nr_devices):
             lo, hi = min(n, d * per), min(n, (d + 1) * per)
             blocks.append((lo, hi))
-            self.push(d, req[lo:hi], pat[lo:hi], txt[lo:hi])
+            if text_pos is not None:
+                self.push(d, req[lo:hi], pat[lo:hi], text_pos=text_pos[lo:hi])
+            else:
+                self.push(d, req[lo:hi], pat[lo:hi], txt[lo:hi])
         self.launch()
         parts = [self.pull(d, check=check) for d in range(self.nr_devices)]
         res = np.concatenate([p[0] for p in parts])
@@ -419,6 +507,8 @@ class DeviceSet:
         return res, ops
 
 
-def align(params, req, pat, txt, nr_devices=1, check=True):
+def align(params, req, pat, txt, nr_devices=1, check=True, reference=None, text_pos=None):
+    """One batch on a fresh set. reference + text_pos: the texts are windows of `reference` (params need AIM_FLAG_REF_TEXTS;
+    txt may be None)."""
     with DeviceSet(nr_devices) as s:
-        return s.align(params, req, pat, txt, check=check)
+        return s.align(params, req, pat, txt, check=check, reference=reference, text_pos=text_pos)

@@ -134,6 +134,18 @@ typedef struct aim_affine2p_params {
  * without AIM_FLAG_BACKTRACE, and with AIM_FLAG_REDUCE, AIM_FLAG_ENDSFREE, AIM_FLAG_AFFINE2P or AIM_FLAG_LINEAR (follow-ups).
  * Check aim_features() & AIM_FEATURE_WFA_BIDIR first: older libraries ignore unknown flags. */
 #define AIM_FLAG_WFA_BIDIR 0x200u
+/* AIM_FLAG_REF_TEXTS (every algorithm, combines with every other flag): the texts of a batch are windows of a reference sequence
+ * that lives on each device of the set (aim_set_reference), named per pair by a uint64_t text_pos instead of being carried as rows.
+ * Bits 0..62 of text_pos hold the window's start, bit 63 its strand: strand 0 is ref[pos, pos + text_len), strand 1 the reverse
+ * complement of that window (A<->T, C<->G, a<->t, c<->g; every other byte unchanged). text_len <= read_size as always; the
+ * request arrays are unchanged. The device gathers the windows into the char[n][READ_SIZE] text rows (zero past text_len) before
+ * any alignment kernel runs: results, statuses, ops rows and compact CIGARs equal those of the same batch sent with explicit texts.
+ * Entry points: aim_set_push_ref (aim_set_push is refused with the flag), aim_set_submit with an aim_batch_io_ref_t (texts,
+ * packed_texts and raw_texts NULL; a packed pair is raw only when its PATTERN holds a byte outside A/C/G/T) and
+ * aim_align_device_ref. aim_set_push_ref / aim_set_submit check every window with aim_ref_windows_check before anything is
+ * enqueued. Check aim_features() & AIM_FEATURE_REF_TEXTS first: older libraries ignore unknown flags. */
+#define AIM_FLAG_REF_TEXTS 0x400u
+#define AIM_REF_MINUS_STRAND (1ull << 63) /* text_pos bit 63: the reverse complement of the window */
 
 /* Per-pair descriptor: byte-compatible with the NW/SWG request_t
  * (NW/DPU-WRAM/common/common.h:114-120).  The WFA variant of the reference
@@ -183,6 +195,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_LINEAR 0x4u   /* AIM_FLAG_LINEAR is honoured */
 #define AIM_FEATURE_WFA_W32 0x8u  /* AIM_FLAG_WFA_W32 is honoured */
 #define AIM_FEATURE_WFA_BIDIR 0x10u /* AIM_FLAG_WFA_BIDIR is honoured */
+#define AIM_FEATURE_REF_TEXTS 0x20u /* AIM_FLAG_REF_TEXTS is honoured */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -232,8 +245,22 @@ int aim_set_fallback_pairs(aim_set_t *set, uint32_t device, uint32_t *n_fallback
  * (experiment / debugging knobs; none changes results) are read once per aim_set_configure and frozen in the set, so
  * this line cannot change between a configure and its launches. */
 int aim_set_plan_describe(const aim_set_t *set, uint32_t device, char *out, size_t cap);
-/* dpu_free (host.c:371) */
+/* dpu_free (host.c:371); also releases the set's reference */
 int aim_set_free(aim_set_t *set);
+
+/* ---- device-resident reference (AIM_FLAG_REF_TEXTS) ------------------------------------------------------------------
+ * Upload len bytes (taken verbatim: any byte value) to every device of the set; a second call replaces the reference. It does not
+ * count against AIM_SCRATCH_GB. AIM_ENOMEM when it does not fit a device: the previous reference then stays. Batches in flight on
+ * the set are completed before the old reference is released. */
+int aim_set_reference(aim_set_t *set, const char *seq, uint64_t len);
+/* aim_set_push of a batch whose texts are windows of the reference (needs AIM_FLAG_REF_TEXTS): text_pos[n_pairs] as above. */
+int aim_set_push_ref(aim_set_t *set, uint32_t device, uint32_t n_pairs, const void *requests, const char *patterns,
+                     const uint64_t *text_pos);
+/* Host-side window check: AIM_OK when every pair's window [pos, pos + text_len) lies inside [0, ref_len) (bit 63 is the strand,
+ * never part of the position; text_len 0 is always inside); else AIM_EINVAL naming the first bad pair, which *bad_pair (may be
+ * NULL) receives. Lengths are checked against read_size like every entry point does. */
+int aim_ref_windows_check(const aim_params_t *params, uint32_t n_pairs, const void *requests, const uint64_t *text_pos,
+                          uint64_t ref_len, uint32_t *bad_pair);
 
 /* ---- pipelined batches: packed input, compact CIGAR output, double buffering -----------------
  * The reference's host loop is strictly serial (host.c:246-330: scatter, launch, gather, print).  These entry points
@@ -277,6 +304,12 @@ typedef struct aim_batch_io {
     uint32_t runs_cap;               /* capacity of runs[], in runs */
 } aim_batch_io_t;
 
+/* AIM_FLAG_REF_TEXTS: aim_set_submit reads past `base` (only with the flag). */
+typedef struct aim_batch_io_ref {
+    aim_batch_io_t base;             /* texts, packed_texts and raw_texts must be NULL */
+    const uint64_t *text_pos;        /* [n_pairs] window start | strand << 63 */
+} aim_batch_io_ref_t;
+
 /* aim_set_configure with `slots` (1..4) buffer sets per device; max_raw_pairs bounds n_raw of a packed batch
  * (0 = packed input not used), max_runs the run buffer of a compact-CIGAR batch (0 = not used). */
 int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t max_pairs_per_device, uint32_t slots,
@@ -284,7 +317,8 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
 /* Enqueue one batch on (device, slot): H2D, [unpack], alignment kernel(s), [CIGAR run-length encoding], D2H into the
  * buffers named in *io (which must stay valid, and should be pinned -- aim_host_alloc -- for the copies to overlap).
  * Returns immediately.  A slot holds one batch at a time: aim_set_wait it before submitting to it again. */
-int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_batch_io_t *io);
+int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_batch_io_t *io /* with AIM_FLAG_REF_TEXTS: the base
+                   of an aim_batch_io_ref_t */);
 /* Block until the batch on (device, slot) is complete.  n_runs (may be NULL) receives the number of runs written.
  * Returns AIM_EALIGN like aim_set_pull when a pair stopped with a status other than AIM_PAIR_OK. */
 int aim_set_wait(aim_set_t *set, uint32_t device, uint32_t slot, uint32_t *n_runs);
@@ -292,7 +326,9 @@ int aim_set_wait(aim_set_t *set, uint32_t device, uint32_t slot, uint32_t *n_run
  * when every byte is A/C/G/T, 0 when the pair must travel raw (the row content is then unspecified). */
 int aim_pack_sequence(const char *seq, int32_t len, int32_t read_size, uint32_t *row);
 /* Whole-batch packer (host threads): ASCII rows -> packed rows + raw side list, exactly what aim_batch_io_t takes.
- * *n_raw receives the number of pairs that must travel raw; AIM_ENOMEM when it exceeds max_raw (ship the batch as ASCII). */
+ * *n_raw receives the number of pairs that must travel raw; AIM_ENOMEM when it exceeds max_raw (ship the batch as ASCII).
+ * With AIM_FLAG_REF_TEXTS texts and packed_texts may be NULL (and raw_texts is then not written): a pair is raw when its pattern
+ * holds a byte outside A/C/G/T. */
 int aim_pack_batch(const aim_params_t *params, uint32_t n_pairs, const void *requests, const char *patterns, const char *texts,
                    uint32_t *packed_patterns, uint32_t *packed_texts, uint32_t *raw_pairs, char *raw_patterns,
                    char *raw_texts, uint32_t max_raw, uint32_t *n_raw, int threads);
@@ -317,6 +353,14 @@ size_t aim_scratch_bytes(const aim_params_t *params, uint32_t n_pairs);
 int aim_align_device(const aim_params_t *params, uint32_t n_pairs, const void *d_requests,
                      const char *d_patterns, const char *d_texts, void *d_results,
                      char *d_ops, void *d_scratch, size_t scratch_bytes, void *hip_stream);
+/* AIM_FLAG_REF_TEXTS: aim_align_device with the texts gathered from d_reference (ref_len bytes, 16-byte aligned, >= 16 bytes of
+ * addressable slack after the last byte) at d_text_pos[n_pairs] (uint64_t, device memory). aim_scratch_bytes then includes the text
+ * rows: the flag-less figure rounded up to 256 B, plus n_pairs * read_size + 256 B. The caller is responsible for the windows
+ * (aim_ref_windows_check); the gather never reads outside [0, ref_len + 16), so a bad window yields an unspecified result for its
+ * pair, never a fault. */
+int aim_align_device_ref(const aim_params_t *params, uint32_t n_pairs, const void *d_requests, const char *d_patterns,
+                         const uint64_t *d_text_pos, const char *d_reference, uint64_t ref_len, void *d_results, char *d_ops,
+                         void *d_scratch, size_t scratch_bytes, void *hip_stream);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
