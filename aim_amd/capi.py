@@ -28,6 +28,8 @@ FEATURE_WFA_BIDIR = 16 # aim_features(): AIM_FLAG_WFA_BIDIR is honoured
 FLAG_REF_TEXTS = 0x400 # texts named as (position, strand) windows of the device-resident reference (aim_set_reference)
 FEATURE_REF_TEXTS = 0x20  # aim_features(): AIM_FLAG_REF_TEXTS is honoured
 REF_MINUS_STRAND = 1 << 63   # text_pos bit 63: the reverse complement of the window
+FLAG_READ_GROUPS = 0x800     # reads and their candidates: score-only pass, best candidate per read, the configured run on the winners
+FEATURE_READ_GROUPS = 0x40   # aim_features(): AIM_FLAG_READ_GROUPS is honoured
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
 
 
@@ -89,6 +91,8 @@ assert REQUEST8_DTYPE.itemsize == 8 and RESULT8_DTYPE.itemsize == 8
 CIGAR_DTYPE = np.dtype([("idx", "<u4"), ("score", "<i4"), ("run_offset", "<u4"), ("n_runs", "<u2"), ("status", "<u2")])   # aim_cigar_t
 assert CIGAR_DTYPE.itemsize == 16
 CIGAR_OVERFLOW = 0x100
+BEST_DTYPE = np.dtype([("best_pair", "<u4"), ("best_score", "<i4"), ("second_score", "<i4"), ("n_best", "<u4")])   # aim_best_t
+assert BEST_DTYPE.itemsize == 16
 
 
 class BatchIO(C.Structure):
@@ -102,6 +106,12 @@ class BatchIO(C.Structure):
 class BatchIORef(C.Structure):
     """aim_batch_io_ref_t: aim_batch_io_t + text_pos (AIM_FLAG_REF_TEXTS); aim_set_submit receives a pointer to `base`."""
     _fields_ = [("base", BatchIO), ("text_pos", C.c_void_p)]
+
+
+class BatchIOGroups(C.Structure):
+    """aim_batch_io_groups_t: laid out like BatchIORef, then the reads (AIM_FLAG_READ_GROUPS); aim_set_submit receives a pointer to
+    `base`."""
+    _fields_ = [("base", BatchIO), ("text_pos", C.c_void_p), ("n_reads", C.c_uint32), ("read_offsets", C.c_void_p), ("best", C.c_void_p)]
 
 
 # every symbol include/aim_hip.h declares: name -> (restype, argtypes)
@@ -140,6 +150,9 @@ SYMBOLS = {
     "aim_set_push_ref": (C.c_int, [_VP, _U32, _U32, _VP, _VP, _VP]),
     "aim_ref_windows_check": (C.c_int, [C.POINTER(Params), _U32, _VP, _VP, C.c_uint64, C.POINTER(_U32)]),
     "aim_align_device_ref": (C.c_int, [C.POINTER(Params), _U32, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "aim_groups_check": (C.c_int, [_U32, _U32, _VP, C.POINTER(_U32)]),
+    "aim_align_device_groups": (C.c_int, [C.POINTER(Params), _U32, _U32, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP,
+                                          C.c_size_t, _VP]),
 }
 
 _lib = None

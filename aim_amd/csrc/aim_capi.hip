@@ -32,6 +32,7 @@
 #include "dp_reg.hpp"
 #include "dp_group.hpp"
 #include "batch_io.hpp"
+#include "groups.hpp"
 #include "genasm_wave.hpp"
 
 namespace {
@@ -239,6 +240,8 @@ inline bool is_ref(const aim_params_t &p) { return (p.flags & AIM_FLAG_REF_TEXTS
 // aim_align_device_ref: the gathered text rows sit behind the plan's scratch, 256-B aligned, with 256 B of tail slack
 inline size_t ref_rows_at(size_t plan_scratch) { return (plan_scratch + 255) & ~(size_t)255; }
 inline size_t ref_rows_bytes(const aim_params_t &p, uint32_t n_pairs) { return (size_t)n_pairs * (size_t)p.read_size + 256; }
+// AIM_FLAG_READ_GROUPS: reads and their candidates (groups.hpp); the plans of its two passes never see the flag.
+inline bool is_groups(const aim_params_t &p) { return (p.flags & AIM_FLAG_READ_GROUPS) != 0; }
 // The params as this library keeps them: room for either extension, and the extension copied only when a flag says it exists.
 union XParams {
     aim_params_t base;
@@ -964,6 +967,168 @@ int enqueue_gather(const aim::KArgs &ka, const uint64_t *d_tpos, const char *ref
     return AIM_OK;
 }
 
+// ---- AIM_FLAG_READ_GROUPS -------------------------------------------------------------------------------------------------
+// Pass 1 aligns every candidate under the configured flags minus BACKTRACE, WFA_BIDIR and RES8 (result_t rows: the selection needs
+// the status); pass 2 runs the configured flags on the winners only (BACKTRACE only: without it the selected pass-1 rows are the
+// answer). Both keep the params' extension (XParams), and neither carries AIM_FLAG_READ_GROUPS.
+struct GroupsPlan {
+    XParams x1, x2;         // the two passes' params
+    Plan p1, p2;            // p2 planned iff pass2
+    bool pass2;
+    size_t plan_bytes;      // the larger of the two plans' scratch (both made for n_pairs)
+    // aim_align_device_groups: the rest of its scratch, offsets from the base (256-B aligned)
+    size_t cand_p_at, cand_t_at, res1_at, map_at, sel_at, req2_at, pat2_at, txt2_at, total;
+};
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline XParams groups_pass_params(const aim_params_t &p, uint32_t drop)
+{
+    XParams x = copy_params(p);
+    x.base.flags &= ~(AIM_FLAG_READ_GROUPS | drop);
+    return x;
+}
+
+int describe_groups(const GroupsPlan &g, uint32_t n_pairs, uint32_t n_reads, uint64_t budget, char *out, size_t cap)
+{
+    char a[384], b[384];
+    describe_plan(g.p1, g.x1.base, n_pairs, budget, a, sizeof a);
+    if (g.pass2) describe_plan(g.p2, g.x2.base, n_reads, budget, b, sizeof b);
+    else snprintf(b, sizeof b, "no second pass n=%u", n_reads);
+    return snprintf(out, cap, "%s | %s groups=1", a, b);
+}
+
+// Both passes planned for n_pairs candidates (the worst case n_reads = n_pairs for pass 2) and the stateless scratch layout:
+// [plans | candidate pattern rows | candidate text rows (REF_TEXTS) | pass-1 results | candidate -> read map | sel | pass-2 requests,
+//  pattern rows, text rows (BACKTRACE)]
+int make_groups_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, GroupsPlan *g)
+{
+    int rc = validate_params(p);
+    if (rc) return rc;
+    memset(g, 0, sizeof *g);
+    aim::Knobs quiet = kn;
+    quiet.plan_debug = false;
+    g->x1 = groups_pass_params(p, AIM_FLAG_BACKTRACE | AIM_FLAG_WFA_BIDIR | AIM_FLAG_RES8);
+    g->x2 = groups_pass_params(p, 0u);
+    g->pass2 = (p.flags & AIM_FLAG_BACKTRACE) != 0;
+    rc = make_plan(g->x1.base, n_pairs, quiet, budget, &g->p1);
+    if (rc) return rc;
+    g->plan_bytes = g->p1.scratch_total;
+    if (g->pass2) {
+        rc = make_plan(g->x2.base, n_pairs, quiet, budget, &g->p2);
+        if (rc) return rc;
+        g->plan_bytes = std::max(g->plan_bytes, g->p2.scratch_total);
+    }
+    const size_t rows = (size_t)n_pairs * (size_t)p.read_size + 256;
+    size_t at = al256(g->plan_bytes);
+    g->cand_p_at = at; at += al256(rows);
+    if (is_ref(p)) { g->cand_t_at = at; at += al256(rows); }
+    g->res1_at = at; at += al256((size_t)n_pairs * sizeof(aim_result_t));
+    g->map_at = at; at += al256((size_t)n_pairs * 4);
+    g->sel_at = at; at += al256((size_t)n_pairs * 4);
+    if (g->pass2) {
+        g->req2_at = at; at += al256((size_t)n_pairs * sizeof(aim_request_t));
+        g->pat2_at = at; at += al256(rows);
+        g->txt2_at = at; at += al256(rows);
+    }
+    g->total = at;
+    if (kn.plan_debug) {
+        char line[800];
+        describe_groups(*g, n_pairs, n_pairs, budget, line, sizeof line);
+        fprintf(stderr, "[aim plan] %s\n", line);
+    }
+    return AIM_OK;
+}
+
+// Device buffers of one groups batch (a slot's, or carved from the stateless scratch).
+struct GroupsIo {
+    uint32_t n_pairs, n_reads;
+    const void *req;             // [n_pairs]
+    const char *read_rows;       // [n_reads][READ_SIZE], or nullptr when the reads arrived packed:
+    const uint32_t *packed;      // [n_reads][ceil(READ_SIZE/16)] packed read rows ...
+    const uint32_t *raw_pairs;   // ... [n_raw] reads that travel raw, their rows in raw_rows [n_raw][READ_SIZE]
+    const char *raw_rows;
+    uint32_t n_raw;
+    uint32_t *raw_slot;          // [n_reads] scratch of the expansion
+    const uint32_t *roff;        // [n_reads + 1]
+    char *cand_p, *cand_t;       // [n_pairs][READ_SIZE]; cand_t: the candidates' text rows (given, or gathered under REF_TEXTS)
+    aim_result_t *res1;          // [n_pairs]
+    uint32_t *map, *sel;         // [n_pairs], [n_reads]
+    aim_best_t *best;            // [n_reads] or nullptr
+    void *req2;                  // [n_reads] pass-2 requests
+    char *pat2, *txt2;           // [n_reads][READ_SIZE]
+    void *res;                   // out [n_reads]
+    char *ops;                   // out [n_reads][2 READ_SIZE] (BACKTRACE)
+    void *scratch;               // the plans' region
+    size_t scratch_bytes;
+};
+
+int enqueue_rows(const aim::KArgs &ka, const char *src, uint32_t n_src, const uint32_t *idx, uint32_t n_rows, int text, char *out, hipStream_t stream)
+{
+    if (!n_rows) return AIM_OK;
+    const int rs = ka.p.read_size;
+    const bool w16 = (rs & 15) == 0;
+    const uint64_t threads = (uint64_t)n_rows * (uint64_t)(rs / (w16 ? 16 : 8));
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (w16) hipLaunchKernelGGL(aim::group_rows_kernel<4>, grid, dim3(256), 0, stream, ka, src, n_src, idx, n_rows, text, out);
+    else hipLaunchKernelGGL(aim::group_rows_kernel<2>, grid, dim3(256), 0, stream, ka, src, n_src, idx, n_rows, text, out);
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
+}
+
+// Everything after the texts are candidate rows (cand_t): expand the read rows, pass 1, select, then pass 2 or the result gather.
+// pl1 / pl2: the passes' plans for this batch (each fits io.scratch_bytes).
+int enqueue_groups(const GroupsPlan &g, const Plan &pl1, const Plan &pl2, const aim::Knobs &kn, const GroupsIo &io, hipStream_t stream,
+                   AuxStream *aux)
+{
+    const aim_params_t &p1 = g.x1.base, &p2 = g.x2.base;
+    const uint32_t n = io.n_pairs, nr = io.n_reads;
+    if (!n) return AIM_OK;
+    aim::KArgs ka;
+    memset(&ka, 0, sizeof ka);
+    ka.p = p1;
+    ka.n_pairs = n;
+    ka.req = static_cast<const aim_request_t *>(io.req);
+    hipLaunchKernelGGL(aim::group_map_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, io.roff, nr, n, io.map);
+    HIP_TRY(hipGetLastError());
+    int rc = AIM_OK;
+    if (io.read_rows) {
+        rc = enqueue_rows(ka, io.read_rows, nr, io.map, n, 0, io.cand_p, stream);
+    } else {
+        HIP_TRY(hipMemsetAsync(io.raw_slot, 0xff, (size_t)nr * 4, stream));
+        if (io.n_raw)
+            hipLaunchKernelGGL(aim::group_raw_slot_kernel, dim3((io.n_raw + 255) / 256), dim3(256), 0, stream, io.raw_pairs, io.n_raw, nr, io.raw_slot);
+        const uint64_t threads = (uint64_t)n * (uint64_t)(p1.read_size / 8);
+        hipLaunchKernelGGL(aim::group_unpack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, ka, io.packed, io.map,
+                           io.raw_slot, io.raw_rows, io.n_raw, nr, io.cand_p);
+        HIP_TRY(hipGetLastError());
+    }
+    if (rc) return rc;
+    rc = launch(pl1, kn, p1, n, io.req, io.cand_p, io.cand_t, io.res1, nullptr, io.scratch, io.scratch_bytes, stream, nullptr, aux);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(io.sel, 0, (size_t)nr * 4, stream));   // (a read the CSR check would refuse keeps a valid sel)
+    const uint32_t waves = (nr + aim::kGroupReadsPerWave - 1) / aim::kGroupReadsPerWave;
+    hipLaunchKernelGGL(aim::group_select_kernel, dim3((waves + 3) / 4), dim3(256), 0, stream, io.res1, n, io.roff, nr, io.best, io.sel);
+    HIP_TRY(hipGetLastError());
+    if (!g.pass2) {
+        hipLaunchKernelGGL(aim::group_results_kernel, dim3((nr + 255) / 256), dim3(256), 0, stream, io.res1, io.sel, nr,
+                           (int)((p2.flags & AIM_FLAG_RES8) != 0), io.res);
+        HIP_TRY(hipGetLastError());
+        return AIM_OK;
+    }
+    // the winners as a batch of their own: requests, pattern rows (already cut to pattern_len) and text rows gathered by sel
+    const uint32_t rq_dw = (uint32_t)((p2.flags & AIM_FLAG_REQ8) ? sizeof(aim_request8_t) : sizeof(aim_request_t)) / 4;
+    hipLaunchKernelGGL(aim::gather_elems_kernel, dim3((unsigned)(((uint64_t)nr * rq_dw + 255) / 256)), dim3(256), 0, stream,
+                       static_cast<const uint32_t *>(io.req), io.sel, nr, rq_dw, static_cast<uint32_t *>(io.req2));
+    HIP_TRY(hipGetLastError());
+    aim::KArgs k2 = ka;
+    k2.p = p2;
+    k2.n_pairs = nr;
+    k2.req = static_cast<const aim_request_t *>(io.req2);
+    rc = enqueue_rows(k2, io.cand_p, n, io.sel, nr, 0, io.pat2, stream);
+    if (!rc) rc = enqueue_rows(k2, io.cand_t, n, io.sel, nr, 1, io.txt2, stream);
+    if (rc) return rc;
+    return launch(pl2, kn, p2, nr, io.req2, io.pat2, io.txt2, io.res, io.ops, io.scratch, io.scratch_bytes, stream, nullptr, aux);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -989,6 +1154,15 @@ struct aim_slot {
     uint64_t *d_tpos = nullptr;      // AIM_FLAG_REF_TEXTS: the batch's text_pos[]
     uint32_t *d_reftodo = nullptr;   // ... packed batches on the fused lane kernel: to-do list {count @0, pair ids @16..} + flag bits
     bool ref_pending = false;        // aim_set_push_ref: the texts are gathered at aim_set_launch
+    // AIM_FLAG_READ_GROUPS (groups.hpp): the read-level inputs, the score-only pass's rows, the selection and the winners' batch
+    char *g_readP = nullptr;         // [max_pairs][READ_SIZE] read pattern rows as they arrive
+    uint32_t *g_roff = nullptr, *g_map = nullptr, *g_sel = nullptr, *g_rawslot = nullptr;
+    aim_result_t *g_res1 = nullptr;
+    aim_best_t *g_best = nullptr;
+    void *g_req2 = nullptr;
+    char *g_pat2 = nullptr, *g_txt2 = nullptr;
+    uint32_t n_reads = 0;            // reads of the groups batch in flight (n_pairs then counts its output rows)
+    Plan plan_last2;                 // ... the second pass's plan
     uint32_t n_pairs = 0;
     uint32_t runs_sent = 0;  // runs of the batch in flight whose D2H copy aim_set_submit already enqueued (slotted run buffer)
     bool pushed = false, launched = false, submitted = false;
@@ -1003,6 +1177,7 @@ struct aim_device_ctx {
     char *d_ref = nullptr;   // AIM_FLAG_REF_TEXTS: the reference (+ zeroed tail slack), kept across aim_set_configure
     uint64_t ref_len = 0;
     Plan plan;               // made at configure time for max_pairs under the set's knobs and this device's budget
+    Plan plan2;              // AIM_FLAG_READ_GROUPS: plan is the score-only pass's, plan2 the second pass's
     uint64_t budget = 0;     // scratch bound of one slot of this device, frozen at configure time
     float h2d_ms = 0.f, kernel_ms = 0.f, d2h_ms = 0.f;   // aim_set_submit / aim_set_wait: phase times of this device's batches, summed
 };
@@ -1024,7 +1199,8 @@ inline size_t res_size(const aim_params_t &p) { return (p.flags & AIM_FLAG_RES8)
 void free_slot(aim_slot &s)
 {
     void *bufs[] = {s.d_req, s.d_pat, s.d_txt, s.d_ops, s.d_res, s.d_scratch, s.d_packP, s.d_packT, s.d_rawidx, s.d_rawP, s.d_rawT,
-                    s.d_cig, s.d_runs, s.d_cursor, s.d_rawreq, s.d_rawres, s.d_rawops, s.d_rawcig, s.d_tpos, s.d_reftodo};
+                    s.d_cig, s.d_runs, s.d_cursor, s.d_rawreq, s.d_rawres, s.d_rawops, s.d_rawcig, s.d_tpos, s.d_reftodo,
+                    s.g_readP, s.g_roff, s.g_map, s.g_sel, s.g_rawslot, s.g_res1, s.g_best, s.g_req2, s.g_pat2, s.g_txt2};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (s.h_cursor) (void)hipHostFree(s.h_cursor);
@@ -1172,7 +1348,8 @@ extern "C" {
 int aim_abi_version(void) { return AIM_ABI_VERSION; }
 uint32_t aim_features(void)
 {
-    return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS;
+    return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
+           AIM_FEATURE_READ_GROUPS;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -1261,6 +1438,20 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
             if (max_raw && params->algo == AIM_ALGO_WFA)
                 HIP_TRY(hipMalloc((void **)&s.d_reftodo, 64 + (size_t)max_pairs * 4 + ((size_t)max_pairs + 31) / 32 * 4));
         }
+        if (is_groups(*params)) {
+            HIP_TRY(hipMalloc((void **)&s.g_readP, (size_t)max_pairs * rs + 64));
+            HIP_TRY(hipMalloc((void **)&s.g_roff, ((size_t)max_pairs + 1) * 4));
+            HIP_TRY(hipMalloc((void **)&s.g_map, (size_t)max_pairs * 4));
+            HIP_TRY(hipMalloc((void **)&s.g_sel, (size_t)max_pairs * 4));
+            if (max_raw) HIP_TRY(hipMalloc((void **)&s.g_rawslot, (size_t)max_pairs * 4));
+            HIP_TRY(hipMalloc((void **)&s.g_res1, (size_t)max_pairs * sizeof(aim_result_t)));
+            HIP_TRY(hipMalloc((void **)&s.g_best, (size_t)max_pairs * sizeof(aim_best_t)));
+            if (params->flags & AIM_FLAG_BACKTRACE) {
+                HIP_TRY(hipMalloc(&s.g_req2, (size_t)max_pairs * req_size(*params)));
+                HIP_TRY(hipMalloc((void **)&s.g_pat2, (size_t)max_pairs * rs + 64));
+                HIP_TRY(hipMalloc((void **)&s.g_txt2, (size_t)max_pairs * rs + 64));
+            }
+        }
         if (max_runs) {
             HIP_TRY(hipMalloc((void **)&s.d_cig, (size_t)max_pairs * sizeof(aim_cigar_t)));
             HIP_TRY(hipMalloc((void **)&s.d_runs, (size_t)max_runs * 4));
@@ -1286,9 +1477,19 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
             d.budget = budget_from_free(free_b / slots);
         }
         for (int attempt = 0;; ++attempt) {
-            int prc = make_plan(*params, max_pairs, kn, d.budget, &d.plan);
-            if (prc) return prc;
-            size_t want = d.plan.scratch_total;
+            size_t want = 0;
+            if (is_groups(*params)) {   // the two passes share the slot's scratch, one after the other
+                GroupsPlan g;
+                int prc = make_groups_plan(*params, max_pairs, kn, d.budget, &g);
+                if (prc) return prc;
+                d.plan = g.p1;
+                d.plan2 = g.p2;
+                want = g.plan_bytes;
+            } else {
+                int prc = make_plan(*params, max_pairs, kn, d.budget, &d.plan);
+                if (prc) return prc;
+                want = d.plan.scratch_total;
+            }
             if (is_ref(*params) && max_raw && params->algo == AIM_ALGO_WFA) {   // room for the to-do stage of fused packed batches
                 Stage st;
                 memset(&st, 0, sizeof st);
@@ -1323,6 +1524,8 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
             s.n_pairs = 0;
             s.pushed = s.launched = s.submitted = false;
             s.plan_last = d.plan;
+            s.plan_last2 = d.plan2;
+            s.n_reads = 0;
         }
         return AIM_OK;
     };
@@ -1351,12 +1554,15 @@ int aim_set_configure(aim_set_t *set, const aim_params_t *params, uint32_t max_p
 }
 
 namespace {
+const char *const kGroupsSubmitOnly = "AIM_FLAG_READ_GROUPS is set: batches go through aim_set_submit with an aim_batch_io_groups_t";
+
 // aim_set_push (texts != nullptr) and aim_set_push_ref (text_pos != nullptr)
 int push_impl(aim_set_t *set, uint32_t device, uint32_t n_pairs, const void *requests, const char *patterns, const char *texts,
               const uint64_t *text_pos)
 {
     if (!set || device >= set->devs.size()) return fail(AIM_EINVAL, "bad device index");
     if (!set->configured) return fail(AIM_ESTATE, "aim_set_configure has not been called");
+    if (is_groups(set->params)) return fail(AIM_EINVAL, kGroupsSubmitOnly);
     if (n_pairs > set->max_pairs) return fail(AIM_EINVAL, "n_pairs %u exceeds configured capacity %u", n_pairs, set->max_pairs);
     if (n_pairs && (!requests || !patterns || (!texts && !text_pos))) return fail(AIM_EINVAL, "null host buffer");
     aim_device_ctx &d = set->devs[device];
@@ -1406,6 +1612,7 @@ int aim_set_push_ref(aim_set_t *set, uint32_t device, uint32_t n_pairs, const vo
 int aim_set_launch(aim_set_t *set)
 {
     if (!set || !set->configured) return fail(AIM_ESTATE, "set is not configured");
+    if (is_groups(set->params)) return fail(AIM_EINVAL, kGroupsSubmitOnly);
     for (auto &d : set->devs) {
         aim_slot &s = d.slots[0];
         if (!s.pushed) return fail(AIM_ESTATE, "device %d has no pushed batch", d.dev);
@@ -1445,6 +1652,7 @@ int aim_set_pull(aim_set_t *set, uint32_t device, void *results, char *ops)
 {
     if (!set || device >= set->devs.size()) return fail(AIM_EINVAL, "bad device index");
     if (!set->configured) return fail(AIM_ESTATE, "aim_set_configure has not been called");
+    if (is_groups(set->params)) return fail(AIM_EINVAL, kGroupsSubmitOnly);
     aim_device_ctx &d = set->devs[device];
     aim_slot &s = d.slots[0];
     if (!s.launched) return fail(AIM_ESTATE, "device %d has not been launched", d.dev);
@@ -1469,6 +1677,186 @@ int aim_set_pull(aim_set_t *set, uint32_t device, void *results, char *ops)
     return AIM_OK;
 }
 
+namespace {
+// aim_groups_check: the CSR of a groups batch, the first bad read named
+int check_groups(uint32_t n_pairs, uint32_t n_reads, const uint32_t *roff, uint32_t *bad_read)
+{
+    auto bad = [&](uint32_t r, const char *what) {
+        if (bad_read) *bad_read = r;
+        return fail(AIM_EINVAL, "read_offsets: read %u %s", r, what);
+    };
+    if (!n_reads) return n_pairs ? fail(AIM_EINVAL, "read_offsets: %u candidates but no read", n_pairs) : AIM_OK;
+    if (!roff) return fail(AIM_EINVAL, "read_offsets is NULL");
+    if (roff[0] != 0) return bad(0, "does not start at offset 0");
+    for (uint32_t r = 0; r < n_reads; ++r) {
+        if (roff[r + 1] < roff[r]) return bad(r, "ends before it starts (offsets decrease)");
+        if (roff[r + 1] == roff[r]) return bad(r, "has no candidate");
+        if (roff[r + 1] > n_pairs) return bad(r, "runs past n_pairs");
+    }
+    if (roff[n_reads] != n_pairs) return bad(n_reads - 1, "is the last and does not end at n_pairs");
+    return AIM_OK;
+}
+
+// A plan of one pass for this batch's size under the set's frozen knobs and budget; the configure-time plan when it would need more
+// scratch than the slot holds (every kernel tolerates a grid larger than its work)
+Plan pass_plan(const aim_set *set, const aim_device_ctx &d, const aim_slot &s, const aim_params_t &pp, uint32_t n, const Plan &configured)
+{
+    Plan pl;
+    aim::Knobs quiet = set->knobs;
+    quiet.plan_debug = false;
+    if (make_plan(pp, n, quiet, d.budget, &pl) || pl.scratch_total > s.scratch_bytes) pl = configured;
+    return pl;
+}
+
+// aim_set_submit under AIM_FLAG_READ_GROUPS
+int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_io_t *io)
+{
+    const aim_params_t &p = set->params;
+    const aim_batch_io_groups_t *gio = reinterpret_cast<const aim_batch_io_groups_t *>(io);
+    const uint32_t n = io->n_pairs, nr = gio->n_reads;
+    const bool bt = p.flags & AIM_FLAG_BACKTRACE;
+    const bool ref = is_ref(p);
+    const bool packed = io->packed_patterns || io->packed_texts;
+    if (packed && (!ref || io->packed_texts))
+        return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS: packed batches need AIM_FLAG_REF_TEXTS (packed explicit texts are a follow-up)");
+    if (packed && (!s.d_packP || !s.g_rawslot)) return fail(AIM_EINVAL, "packed batch needs a set configured with max_raw_pairs > 0");
+    if (packed && io->n_raw > set->max_raw) return fail(AIM_EINVAL, "n_raw %u exceeds configured capacity %u", io->n_raw, set->max_raw);
+    if (packed && io->n_raw && (!io->raw_pairs || !io->raw_patterns)) return fail(AIM_EINVAL, "null raw side list");
+    if (!packed && io->n_raw) return fail(AIM_EINVAL, "a raw side list needs a packed batch");
+    if (ref && (io->texts || io->raw_texts)) return fail(AIM_EINVAL, "AIM_FLAG_REF_TEXTS: texts, packed_texts and raw_texts must be NULL (the texts are named by text_pos)");
+    if (ref && n && !gio->text_pos) return fail(AIM_EINVAL, "AIM_FLAG_REF_TEXTS: null text_pos");
+    if (!ref && gio->text_pos) return fail(AIM_EINVAL, "text_pos needs AIM_FLAG_REF_TEXTS");
+    if (ref && !d.d_ref) return fail(AIM_ESTATE, "AIM_FLAG_REF_TEXTS: no reference on device %d (aim_set_reference)", d.dev);
+    if (n > set->max_pairs) return fail(AIM_EINVAL, "n_pairs %u exceeds configured capacity %u", n, set->max_pairs);
+    if (n && (!io->requests || (!packed && !io->patterns) || (!ref && !io->texts))) return fail(AIM_EINVAL, "null requests or sequence rows");
+    if (io->cigars && (!bt || !s.d_cig || !io->runs)) return fail(AIM_EINVAL, "compact CIGAR needs AIM_FLAG_BACKTRACE, max_runs > 0 and a run buffer");
+    if (n && !io->results && !io->cigars && !gio->best) return fail(AIM_EINVAL, "no output buffer");
+    if (io->ops && !bt) return fail(AIM_EINVAL, "ops requested without AIM_FLAG_BACKTRACE");
+    int rc = check_groups(n, nr, gio->read_offsets, nullptr);
+    if (rc) return rc;
+    if (packed)   // the side list names reads
+        for (uint32_t j = 0; j < io->n_raw; ++j)
+            if (io->raw_pairs[j] >= nr) return fail(AIM_EINVAL, "raw_pairs[%u] = %u is outside the batch's %u reads", j, io->raw_pairs[j], nr);
+    rc = check_lengths(p, n, io->requests);
+    if (rc) return rc;
+    if (ref) {
+        rc = check_windows(p, n, io->requests, gio->text_pos, d.ref_len, nullptr);
+        if (rc) return rc;
+    }
+    const size_t rs = (size_t)p.read_size;
+    HIP_TRY(hipSetDevice(d.dev));
+    s.io = *io;
+    s.n_pairs = nr;          // aim_set_wait reads n_pairs output rows
+    s.n_reads = nr;
+    s.runs_sent = 0;
+    s.pushed = s.launched = false;
+    s.ref_pending = false;
+    GroupsPlan g;
+    memset(&g, 0, sizeof g);
+    g.x1 = groups_pass_params(p, AIM_FLAG_BACKTRACE | AIM_FLAG_WFA_BIDIR | AIM_FLAG_RES8);
+    g.x2 = groups_pass_params(p, 0u);
+    g.pass2 = bt;
+    auto enqueue = [&]() -> int {
+        HIP_TRY(hipEventRecord(s.ev[0], s.stream));
+        if (n) {
+            HIP_TRY(hipMemcpyAsync(s.d_req, io->requests, (size_t)n * req_size(p), hipMemcpyHostToDevice, s.stream));
+            HIP_TRY(hipMemcpyAsync(s.g_roff, gio->read_offsets, ((size_t)nr + 1) * 4, hipMemcpyHostToDevice, s.stream));
+            if (packed) {
+                HIP_TRY(hipMemcpyAsync(s.d_packP, io->packed_patterns, (size_t)nr * aim::packed_row_dwords(p.read_size) * 4, hipMemcpyHostToDevice, s.stream));
+                if (io->n_raw) {
+                    HIP_TRY(hipMemcpyAsync(s.d_rawidx, io->raw_pairs, (size_t)io->n_raw * 4, hipMemcpyHostToDevice, s.stream));
+                    HIP_TRY(hipMemcpyAsync(s.d_rawP, io->raw_patterns, (size_t)io->n_raw * rs, hipMemcpyHostToDevice, s.stream));
+                }
+            } else {
+                HIP_TRY(hipMemcpyAsync(s.g_readP, io->patterns, (size_t)nr * rs, hipMemcpyHostToDevice, s.stream));
+            }
+            if (ref) HIP_TRY(hipMemcpyAsync(s.d_tpos, gio->text_pos, (size_t)n * 8, hipMemcpyHostToDevice, s.stream));
+            else HIP_TRY(hipMemcpyAsync(s.d_txt, io->texts, (size_t)n * rs, hipMemcpyHostToDevice, s.stream));
+        }
+        HIP_TRY(hipEventRecord(s.ev[1], s.stream));
+        HIP_TRY(hipEventRecord(s.ev[2], s.stream));
+        if (n) {
+            if (ref) {
+                aim::KArgs ka;
+                memset(&ka, 0, sizeof ka);
+                ka.p = p;
+                ka.n_pairs = n;
+                ka.req = static_cast<const aim_request_t *>(s.d_req);
+                int grc = enqueue_gather(ka, s.d_tpos, d.d_ref, d.ref_len, nullptr, n, s.d_txt, s.stream);
+                if (grc) return grc;
+            }
+            const Plan pl1 = pass_plan(set, d, s, g.x1.base, n, d.plan);
+            const Plan pl2 = bt ? pass_plan(set, d, s, g.x2.base, nr, d.plan2) : Plan();
+            s.plan_last = pl1;
+            s.plan_last2 = pl2;
+            GroupsIo gi;
+            gi.n_pairs = n;
+            gi.n_reads = nr;
+            gi.req = s.d_req;
+            gi.read_rows = packed ? nullptr : s.g_readP;
+            gi.packed = s.d_packP;
+            gi.raw_pairs = s.d_rawidx;
+            gi.raw_rows = s.d_rawP;
+            gi.n_raw = packed ? io->n_raw : 0u;
+            gi.raw_slot = s.g_rawslot;
+            gi.roff = s.g_roff;
+            gi.cand_p = s.d_pat;
+            gi.cand_t = s.d_txt;
+            gi.res1 = s.g_res1;
+            gi.map = s.g_map;
+            gi.sel = s.g_sel;
+            gi.best = s.g_best;
+            gi.req2 = s.g_req2;
+            gi.pat2 = s.g_pat2;
+            gi.txt2 = s.g_txt2;
+            gi.res = s.d_res;
+            gi.ops = s.d_ops;
+            gi.scratch = s.d_scratch;
+            gi.scratch_bytes = s.scratch_bytes;
+            int erc = enqueue_groups(g, pl1, pl2, set->knobs, gi, s.stream, &s.aux);
+            if (erc) return erc;
+            if (io->cigars) {
+                aim::KArgs k2;
+                memset(&k2, 0, sizeof k2);
+                k2.p = g.x2.base;
+                k2.n_pairs = nr;
+                k2.req = static_cast<const aim_request_t *>(s.g_req2);
+                k2.res = static_cast<aim_result_t *>(s.d_res);
+                k2.ops = s.d_ops;
+                HIP_TRY(hipMemsetAsync(s.d_cursor, 0, 4, s.stream));
+                hipLaunchKernelGGL(aim::cigar_rle_kernel, dim3((nr + 63) / 64), dim3(64), 0, s.stream, k2, s.d_cig, s.d_runs,
+                                   std::min(io->runs_cap, set->max_runs), s.d_cursor);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        HIP_TRY(hipEventRecord(s.ev[3], s.stream));
+        HIP_TRY(hipEventRecord(s.ev[4], s.stream));
+        if (n) {
+            if (gio->best) HIP_TRY(hipMemcpyAsync(gio->best, s.g_best, (size_t)nr * sizeof(aim_best_t), hipMemcpyDeviceToHost, s.stream));
+            if (io->cigars) {
+                HIP_TRY(hipMemcpyAsync(s.h_cursor, s.d_cursor, 4, hipMemcpyDeviceToHost, s.stream));
+                HIP_TRY(hipMemcpyAsync(io->cigars, s.d_cig, (size_t)nr * sizeof(aim_cigar_t), hipMemcpyDeviceToHost, s.stream));
+            }
+            if (io->results) HIP_TRY(hipMemcpyAsync(io->results, s.d_res, (size_t)nr * res_size(p), hipMemcpyDeviceToHost, s.stream));
+            if (io->ops) HIP_TRY(hipMemcpyAsync(io->ops, s.d_ops, (size_t)nr * 2 * rs, hipMemcpyDeviceToHost, s.stream));
+        }
+        HIP_TRY(hipEventRecord(s.ev[5], s.stream));
+        return AIM_OK;
+    };
+    rc = enqueue();
+    if (rc) {   // (as aim_set_submit: nothing stays in flight on a failed submit)
+        char keep[sizeof g_err];
+        memcpy(keep, g_err, sizeof keep);
+        (void)hipStreamSynchronize(s.stream);
+        (void)hipGetLastError();
+        memcpy(g_err, keep, sizeof keep);
+        return rc;
+    }
+    s.submitted = true;
+    return AIM_OK;
+}
+}  // namespace
+
 int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_batch_io_t *io)
 {
     if (!set || device >= set->devs.size() || !io) return fail(AIM_EINVAL, "bad arguments");
@@ -1477,6 +1865,7 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
     if (slot >= d.slots.size()) return fail(AIM_EINVAL, "slot %u not configured (%zu slots)", slot, d.slots.size());
     aim_slot &s = d.slots[slot];
     if (s.submitted) return fail(AIM_ESTATE, "slot %u of device %d holds a batch: aim_set_wait it first", slot, d.dev);
+    if (is_groups(set->params)) return submit_groups(set, d, s, io);
     const aim_params_t &p = set->params;
     const uint32_t n = io->n_pairs;
     const bool bt = p.flags & AIM_FLAG_BACKTRACE;
@@ -1768,6 +2157,18 @@ int aim_set_plan_describe(const aim_set_t *set, uint32_t device, char *out, size
     if (!set->configured) return fail(AIM_ESTATE, "aim_set_configure has not been called");
     const aim_device_ctx &d = set->devs[device];
     const aim_slot &s = d.slots[0];
+    if (is_groups(set->params)) {   // the last groups batch submitted on slot 0 (before the first: the configure-time plans)
+        GroupsPlan g;
+        memset(&g, 0, sizeof g);
+        g.x1 = groups_pass_params(set->params, AIM_FLAG_BACKTRACE | AIM_FLAG_WFA_BIDIR | AIM_FLAG_RES8);
+        g.x2 = groups_pass_params(set->params, 0u);
+        g.pass2 = (set->params.flags & AIM_FLAG_BACKTRACE) != 0;
+        g.p1 = s.plan_last;
+        g.p2 = s.plan_last2;
+        const bool any = s.n_reads != 0;
+        describe_groups(g, any ? s.io.n_pairs : set->max_pairs, any ? s.n_reads : set->max_pairs, d.budget, out, cap);
+        return AIM_OK;
+    }
     describe_plan(s.plan_last, set->params, s.launched ? s.n_pairs : set->max_pairs, d.budget, out, cap);
     return AIM_OK;
 }
@@ -1842,6 +2243,12 @@ size_t aim_scratch_bytes(const aim_params_t *params, uint32_t n_pairs)
 {
     Plan pl;
     const aim::Knobs kn = read_knobs();
+    if (params && is_groups(*params)) {   // both passes' plans + the rows and arrays between them, for n_reads = n_pairs
+        GroupsPlan g;
+        aim::Knobs quiet = kn;
+        quiet.plan_debug = false;
+        return make_groups_plan(*params, n_pairs, quiet, stateless_budget_bytes(kn), &g) ? 0 : g.total;
+    }
     if (!params || make_plan(*params, n_pairs, kn, stateless_budget_bytes(kn), &pl)) return 0;
     if (is_ref(*params)) return ref_rows_at(pl.scratch_total) + ref_rows_bytes(*params, n_pairs);   // + the gathered text rows
     return pl.scratch_total;
@@ -1853,6 +2260,7 @@ int aim_align_device_ref(const aim_params_t *params, uint32_t n_pairs, const voi
 {
     if (!params) return fail(AIM_EINVAL, "params is NULL");
     if (!is_ref(*params)) return fail(AIM_EINVAL, "aim_align_device_ref needs AIM_FLAG_REF_TEXTS");
+    if (is_groups(*params)) return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS is set: use aim_align_device_groups");
     if (n_pairs && (!d_text_pos || !d_reference || !d_requests)) return fail(AIM_EINVAL, "null device buffer");
     int n = 0;
     int rc = aim_device_count(&n);
@@ -1898,6 +2306,7 @@ int aim_align_device(const aim_params_t *params, uint32_t n_pairs, const void *d
                      void *d_scratch, size_t scratch_bytes, void *hip_stream)
 {
     if (!params) return fail(AIM_EINVAL, "params is NULL");
+    if (is_groups(*params)) return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS is set: use aim_align_device_groups");
     int n = 0;
     int rc = aim_device_count(&n);
     if (rc) return rc;
@@ -1914,6 +2323,13 @@ int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, s
     if (!params || !out || cap == 0) return fail(AIM_EINVAL, "bad arguments");
     const aim::Knobs kn = read_knobs();
     const uint64_t budget = stateless_budget_bytes(kn);
+    if (is_groups(*params)) {   // n_reads = n_pairs, as aim_scratch_bytes counts it
+        GroupsPlan g;
+        int rc = make_groups_plan(*params, n_pairs, kn, budget, &g);
+        if (rc) return rc;
+        describe_groups(g, n_pairs, n_pairs, budget, out, cap);
+        return AIM_OK;
+    }
     Plan pl;
     int rc = make_plan(*params, n_pairs, kn, budget, &pl);
     if (rc) return rc;
@@ -1926,8 +2342,87 @@ const char *aim_kernel_name(const aim_params_t *params)
     Plan pl;
     aim::Knobs kn = read_knobs();
     kn.plan_debug = false;
-    if (!params || make_plan(*params, 1u << 20, kn, stateless_budget_bytes(kn), &pl)) return "";
+    if (!params) return "";
+    if (is_groups(*params)) {   // the score-only pass's kernel (the one every candidate meets)
+        const XParams x1 = groups_pass_params(*params, AIM_FLAG_BACKTRACE | AIM_FLAG_WFA_BIDIR | AIM_FLAG_RES8);
+        if (validate_params(*params) || make_plan(x1.base, 1u << 20, kn, stateless_budget_bytes(kn), &pl)) return "";
+        return kernel_name(pl, x1.base);
+    }
+    if (make_plan(*params, 1u << 20, kn, stateless_budget_bytes(kn), &pl)) return "";
     return kernel_name(pl, *params);
+}
+
+int aim_groups_check(uint32_t n_pairs, uint32_t n_reads, const uint32_t *read_offsets, uint32_t *bad_read)
+{
+    return check_groups(n_pairs, n_reads, read_offsets, bad_read);
+}
+
+int aim_align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
+                            const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
+                            const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, void *d_scratch,
+                            size_t scratch_bytes, void *hip_stream)
+{
+    if (!params) return fail(AIM_EINVAL, "params is NULL");
+    if (!is_groups(*params)) return fail(AIM_EINVAL, "aim_align_device_groups needs AIM_FLAG_READ_GROUPS");
+    const bool ref = is_ref(*params), bt = params->flags & AIM_FLAG_BACKTRACE;
+    if (n_reads > n_pairs || (n_pairs && !n_reads)) return fail(AIM_EINVAL, "n_reads %u does not fit n_pairs %u", n_reads, n_pairs);
+    if (n_pairs && (!d_requests || !d_patterns || !d_read_offsets || !d_results || (bt && !d_ops) ||
+                    (ref ? (!d_text_pos_or_null || !d_reference) : !d_texts_or_null)))
+        return fail(AIM_EINVAL, "null device buffer");
+    int n = 0;
+    int rc = aim_device_count(&n);
+    if (rc) return rc;
+    const aim::Knobs kn = read_knobs();
+    const uint64_t budget = stateless_budget_bytes(kn);
+    GroupsPlan g;
+    rc = make_groups_plan(*params, n_pairs, kn, budget, &g);
+    if (rc) return rc;
+    if (!d_scratch || scratch_bytes < g.total) return fail(AIM_EINVAL, "scratch too small: need %zu bytes, got %zu", g.total, scratch_bytes);
+    if (n_pairs == 0) return AIM_OK;
+    char *base = static_cast<char *>(d_scratch);
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    GroupsIo gi;
+    gi.n_pairs = n_pairs;
+    gi.n_reads = n_reads;
+    gi.req = d_requests;
+    gi.read_rows = d_patterns;
+    gi.packed = nullptr;
+    gi.raw_pairs = nullptr;
+    gi.raw_rows = nullptr;
+    gi.n_raw = 0;
+    gi.raw_slot = nullptr;
+    gi.roff = d_read_offsets;
+    gi.cand_p = base + g.cand_p_at;
+    gi.cand_t = ref ? base + g.cand_t_at : const_cast<char *>(d_texts_or_null);
+    gi.res1 = reinterpret_cast<aim_result_t *>(base + g.res1_at);
+    gi.map = reinterpret_cast<uint32_t *>(base + g.map_at);
+    gi.sel = reinterpret_cast<uint32_t *>(base + g.sel_at);
+    gi.best = d_best;
+    gi.req2 = bt ? base + g.req2_at : nullptr;
+    gi.pat2 = bt ? base + g.pat2_at : nullptr;
+    gi.txt2 = bt ? base + g.txt2_at : nullptr;
+    gi.res = d_results;
+    gi.ops = d_ops;
+    gi.scratch = d_scratch;
+    gi.scratch_bytes = g.plan_bytes;
+    if (ref) {
+        aim::KArgs ka;
+        memset(&ka, 0, sizeof ka);
+        ka.p = *params;
+        ka.n_pairs = n_pairs;
+        ka.req = static_cast<const aim_request_t *>(d_requests);
+        rc = enqueue_gather(ka, d_text_pos_or_null, d_reference, ref_len, nullptr, n_pairs, gi.cand_t, stream);
+        if (rc) return rc;
+    }
+    // pass 2 re-planned for the reads (smaller grids); the n_pairs plan where that would not fit the plans' region
+    Plan pl2 = g.p2;
+    if (bt) {
+        Plan q;
+        aim::Knobs quiet = kn;
+        quiet.plan_debug = false;
+        if (!make_plan(g.x2.base, n_reads, quiet, budget, &q) && q.scratch_total <= g.plan_bytes) pl2 = q;
+    }
+    return enqueue_groups(g, g.p1, pl2, kn, gi, stream, nullptr);
 }
 
 // ---------------------------------------------------------------------------

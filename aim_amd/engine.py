@@ -13,7 +13,7 @@ import numpy as np
 
 from . import capi
 from .capi import (ALGO_BY_NAME, ALGO_NW, ALGO_SWG, ALGO_WFA, FLAG_AFFINE2P, FLAG_BACKTRACE, FLAG_ENDSFREE, FLAG_LINEAR, FLAG_REDUCE,
-                   FLAG_REF_TEXTS, FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16, FLAG_WFA_BIDIR, FLAG_WFA_W32, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
+                   FLAG_READ_GROUPS, FLAG_REF_TEXTS, FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16, FLAG_WFA_BIDIR, FLAG_WFA_W32, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
                    Params, params_ref)
 
 
@@ -37,7 +37,7 @@ def features():
 
 def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=1, gap=4, backtrace=False,
                 reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None, gap2=None, linear=False,
-                w32=False, bidir=False, ref_texts=False):
+                w32=False, bidir=False, ref_texts=False, read_groups=False):
     """`gap` is the launchers' single NW gap cost (run-nw-pim-wram.py: -DGAP_I = -DGAP_D); `gap_i` / `gap_d` set the two macros of
     nw.c:67-153 apart (NW/DPU-WRAM/common/common.h GAP_I, GAP_D). `ends_free=(PB, PE, TB, TE)`: ends-free WFA (AIM_FLAG_ENDSFREE);
     returns an EndsFreeParams then, which every call below accepts like Params. `gap2=(O2, E2)`: dual-cost gap-affine WFA
@@ -45,12 +45,15 @@ def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=
     WFA (AIM_FLAG_LINEAR): a mismatch costs `mismatch`, every gap base `gap_e`, and gap_o is set to 0; not with ends_free, gap2 or
     reduce. `w32=True`: WFA with 32-bit wavefront offsets (AIM_FLAG_WFA_W32), read_size up to 2^24; combines with all of the above.
     `bidir=True`: bidirectional WFA (AIM_FLAG_WFA_BIDIR), CIGAR in O(MAX_SCORE) scratch; global gap-affine with backtrace only.
-    `ref_texts=True`: texts named as windows of the device-resident reference (AIM_FLAG_REF_TEXTS); combines with everything."""
+    `ref_texts=True`: texts named as windows of the device-resident reference (AIM_FLAG_REF_TEXTS); combines with everything.
+    `read_groups=True`: batches of reads and their candidates, best candidate per read (AIM_FLAG_READ_GROUPS); combines with
+    everything."""
     a = ALGO_BY_NAME[algo] if isinstance(algo, str) else algo
     gap_i = gap if gap_i is None else gap_i
     gap_d = gap if gap_d is None else gap_d
     flags = (FLAG_BACKTRACE if backtrace else 0) | (FLAG_REDUCE if reduce else 0) | (FLAG_SWG_W16 if swg_w16 else 0)
     flags |= (FLAG_REQ8 if req8 else 0) | (FLAG_RES8 if res8 else 0) | (FLAG_WFA_W32 if w32 else 0) | (FLAG_REF_TEXTS if ref_texts else 0)
+    flags |= FLAG_READ_GROUPS if read_groups else 0
     if bidir:
         if not backtrace:
             raise ValueError("bidir needs backtrace")
@@ -194,6 +197,63 @@ def ref_pairs(seed, first_idx, n_pairs, length, error, reference, read_size, min
         req["pattern_len"][i], req["text_len"][i], req["idx"][i] = len(p), length, int(first_idx) + i
         tpos[i] = pos | ((1 << 63) if minus else 0)
     return req, pat, tpos, txt
+
+
+def group_pairs(seed, first_read, n_reads, k, length, error, reference, read_size, minus_fraction=0.5, sizes=None, shift=8):
+    """Seeded reads with candidate windows of `reference` (AIM_FLAG_READ_GROUPS). Read r (depending only on (seed, first_read + r) and
+    the reference) is a window of `length` bases at a seeded position and strand (minus with probability `minus_fraction`) after
+    ceil(length * error) edits of ref_pairs' model. Its candidates -- k of them, or sizes[r] -- are windows of `length` bases: the
+    true window at a seeded slot; the others each either a copy of it moved by 1..`shift` bases (same strand) or a random window on
+    either strand. Every candidate's pattern is the whole read.
+    Returns (requests[n_pairs], read_rows[n_reads][read_size], read_offsets[n_reads + 1] uint32, text_pos[n_pairs] uint64,
+    texts[n_pairs][read_size], patterns[n_pairs][read_size]) -- texts and patterns are the explicit per-candidate batch."""
+    ref = np.frombuffer(reference, dtype=np.uint8) if isinstance(reference, (bytes, bytearray)) else np.asarray(reference, dtype=np.uint8)
+    nedits = int(math.ceil(length * error))
+    if length > len(ref):
+        raise ValueError("reference shorter than a window")
+    if length + nedits > read_size:
+        raise ValueError("read_size %d too small for length %d + %d edits" % (read_size, length, nedits))
+    counts = np.full(n_reads, k, dtype=np.int64) if sizes is None else np.asarray(sizes, dtype=np.int64)
+    if len(counts) != n_reads or (counts < 1).any():
+        raise ValueError("every read needs at least one candidate")
+    offsets = np.zeros(n_reads + 1, dtype=np.uint32)
+    offsets[1:] = np.cumsum(counts)
+    n = int(offsets[-1])
+    acgt = b"ACGT"
+    span = len(ref) - length + 1
+    req = np.zeros(n, dtype=REQUEST_DTYPE)
+    rows = np.zeros((n_reads, read_size), dtype=np.uint8)
+    tpos = np.zeros(n, dtype=np.uint64)
+    txt = np.zeros((n, read_size), dtype=np.uint8)
+    for r in range(n_reads):
+        rng = np.random.default_rng([int(seed), int(first_read) + r, 0x67727073])
+        pos = int(rng.integers(0, span))
+        minus = bool(rng.random() < minus_fraction)
+        p = bytearray(ref_window(ref, pos, length, minus).tobytes())
+        for _ in range(nedits):
+            kind, b, x = int(rng.integers(0, 3)), acgt[int(rng.integers(0, 4))], int(rng.integers(0, 1 << 32))
+            if kind == 0 and p:
+                p[x % len(p)] = b
+            elif kind == 1 and p:
+                del p[x % len(p)]
+            else:
+                p.insert(x % (len(p) + 1), b)
+        rows[r, :len(p)] = np.frombuffer(bytes(p), dtype=np.uint8)
+        lo, cnt = int(offsets[r]), int(counts[r])
+        true_at = int(rng.integers(0, cnt))
+        for j in range(cnt):
+            if j == true_at:
+                cp, cm = pos, minus
+            elif rng.random() < 0.5:
+                cp, cm = min(max(pos + int(rng.choice([-1, 1])) * int(rng.integers(1, shift + 1)), 0), span - 1), minus
+            else:
+                cp, cm = int(rng.integers(0, span)), bool(rng.random() < 0.5)
+            tpos[lo + j] = cp | ((1 << 63) if cm else 0)
+            txt[lo + j, :length] = ref_window(ref, cp, length, cm)
+        req["pattern_len"][lo:lo + cnt], req["text_len"][lo:lo + cnt] = len(p), length
+    req["idx"] = np.arange(n, dtype=np.uint32)
+    read_of = np.repeat(np.arange(n_reads), counts)
+    return req, rows, offsets, tpos, txt, np.ascontiguousarray(rows[read_of])
 
 
 def to_request8(req):
@@ -381,18 +441,29 @@ class DeviceSet:
         capi.check(self.lib.aim_set_reference(self.handle, arr.ctypes.data if len(arr) else None, len(arr)))
         self.ref_len = len(arr)
 
-    def submit(self, device, slot, req, pat=None, txt=None, packed=None, want_ops=False, cigar_runs_cap=0, text_pos=None):
+    def submit(self, device, slot, req, pat=None, txt=None, packed=None, want_ops=False, cigar_runs_cap=0, text_pos=None,
+               read_offsets=None):
         """aim_set_submit: ASCII rows (pat, txt) or a packed batch (pack_batch(...)); results / ops / compact CIGAR buffers
         are allocated here and returned by wait(). text_pos (AIM_FLAG_REF_TEXTS): the texts are windows of the reference; pass
-        pat (or packed = pack_batch(req, pat, None)) and no texts."""
+        pat (or packed = pack_batch(req, pat, None)) and no texts. read_offsets (AIM_FLAG_READ_GROUPS): req and the texts are per
+        candidate, pat holds one row per read; wait() returns one row per read and "best" (capi.BEST_DTYPE)."""
         if (self.params.flags & FLAG_REQ8) and req.dtype != REQUEST8_DTYPE:
             req = to_request8(req)
         req = np.ascontiguousarray(req)
         n, rs = len(req), self.params.read_size
-        rio = capi.BatchIORef()
+        rio = capi.BatchIOGroups() if read_offsets is not None else capi.BatchIORef()
         io = rio.base
+        out = {}
+        if read_offsets is not None:
+            ro = np.ascontiguousarray(read_offsets, dtype=np.uint32)
+            rio.n_reads, rio.read_offsets = len(ro) - 1, ro.ctypes.data
+            out["best"] = np.zeros(len(ro) - 1, dtype=capi.BEST_DTYPE)
+            rio.best = out["best"].ctypes.data
+            n_out = len(ro) - 1
+        else:
+            ro, n_out = None, n
         io.n_pairs = n
-        keep = [req]
+        keep = [req, ro]
         io.requests = req.ctypes.data
         if text_pos is not None:
             tp = np.ascontiguousarray(text_pos, dtype=np.uint64)
@@ -411,16 +482,15 @@ class DeviceSet:
             txt = None if txt is None else np.ascontiguousarray(txt)
             keep += [pat, txt]
             io.patterns, io.texts = addr(pat), addr(txt)
-        out = {}
         if cigar_runs_cap:
-            out["cig"] = np.zeros(n, dtype=capi.CIGAR_DTYPE)
+            out["cig"] = np.zeros(n_out, dtype=capi.CIGAR_DTYPE)
             out["runs"] = np.zeros(cigar_runs_cap, dtype=np.uint32)
             io.cigars, io.runs, io.runs_cap = out["cig"].ctypes.data, out["runs"].ctypes.data, cigar_runs_cap
         if not cigar_runs_cap or want_ops:
-            out["res"] = np.zeros(n, dtype=RESULT8_DTYPE if (self.params.flags & FLAG_RES8) else RESULT_DTYPE)
+            out["res"] = np.zeros(n_out, dtype=RESULT8_DTYPE if (self.params.flags & FLAG_RES8) else RESULT_DTYPE)
             io.results = out["res"].ctypes.data
         if want_ops:
-            out["ops"] = np.zeros((n, 2 * rs), dtype=np.uint8)
+            out["ops"] = np.zeros((n_out, 2 * rs), dtype=np.uint8)
             io.ops = out["ops"].ctypes.data
         capi.check(self.lib.aim_set_submit(self.handle, device, slot, C.byref(io)))
         self._inflight[(device, slot)] = (rio, keep, out)
@@ -473,7 +543,7 @@ class DeviceSet:
 
     def plan_describe(self, device=0):
         """The plan line of the last launch on `device` (aim_set_plan_describe)."""
-        buf = C.create_string_buffer(512)
+        buf = C.create_string_buffer(1024)
         capi.check(self.lib.aim_set_plan_describe(self.handle, device, buf, len(buf)))
         return buf.value.decode()
 

@@ -146,6 +146,19 @@ typedef struct aim_affine2p_params {
  * enqueued. Check aim_features() & AIM_FEATURE_REF_TEXTS first: older libraries ignore unknown flags. */
 #define AIM_FLAG_REF_TEXTS 0x400u
 #define AIM_REF_MINUS_STRAND (1ull << 63) /* text_pos bit 63: the reverse complement of the window */
+/* AIM_FLAG_READ_GROUPS (every algorithm, combines with every other flag under that flag's own rules): the verification stage of a
+ * read mapper. A batch holds n_reads reads and n_pairs candidates; read_offsets[n_reads + 1] (CSR, read_offsets[0] = 0,
+ * read_offsets[n_reads] = n_pairs, every read >= 1 candidate) gives read r the candidates [read_offsets[r], read_offsets[r+1]).
+ * Requests and texts (or text_pos) stay one per candidate; patterns are one row per READ, and candidate i's pattern is the first
+ * pattern_len[i] bytes of its read's row. The device aligns every candidate score-only (the configured flags minus BACKTRACE,
+ * WFA_BIDIR and RES8), picks per read the AIM_PAIR_OK candidate of lowest score (lowest batch index on a tie; a WFA pair over the cap
+ * counts with its MAX_SCORE + 1) into an aim_best_t, and runs the configured plan again on the winners only. Read r's result row,
+ * ops row [begin_offset, end_offset), compact header and runs are exactly those of candidate sel[r] -- best_pair, or
+ * read_offsets[r] when the read has no OK candidate -- run without this flag under the configured flags (its idx and status
+ * included). Entry points: aim_set_submit with an aim_batch_io_groups_t (ASCII read rows, or with AIM_FLAG_REF_TEXTS packed read rows
+ * whose raw_pairs list READ indices and raw_patterns their rows; packed explicit texts are refused) and aim_align_device_groups (ASCII); aim_set_push, aim_set_push_ref, aim_set_launch, aim_set_pull, aim_align_device and aim_align_device_ref
+ * refuse the flag. Check aim_features() & AIM_FEATURE_READ_GROUPS first: older libraries ignore unknown flags. */
+#define AIM_FLAG_READ_GROUPS 0x800u
 
 /* Per-pair descriptor: byte-compatible with the NW/SWG request_t
  * (NW/DPU-WRAM/common/common.h:114-120).  The WFA variant of the reference
@@ -196,6 +209,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_WFA_W32 0x8u  /* AIM_FLAG_WFA_W32 is honoured */
 #define AIM_FEATURE_WFA_BIDIR 0x10u /* AIM_FLAG_WFA_BIDIR is honoured */
 #define AIM_FEATURE_REF_TEXTS 0x20u /* AIM_FLAG_REF_TEXTS is honoured */
+#define AIM_FEATURE_READ_GROUPS 0x40u /* AIM_FLAG_READ_GROUPS is honoured */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -310,6 +324,32 @@ typedef struct aim_batch_io_ref {
     const uint64_t *text_pos;        /* [n_pairs] window start | strand << 63 */
 } aim_batch_io_ref_t;
 
+/* AIM_FLAG_READ_GROUPS: what each read's candidates scored in the score-only pass. second_score is the lowest score among the
+ * read's OTHER OK candidates (= best_score on a tie; INT32_MAX with fewer than two OK candidates); n_best counts the OK candidates
+ * of best_score. A read without an OK candidate: best_pair = UINT32_MAX, best_score = INT32_MAX, n_best = 0. */
+typedef struct aim_best {
+    uint32_t best_pair;              /* batch (candidate) index */
+    int32_t best_score;
+    int32_t second_score;
+    uint32_t n_best;
+} aim_best_t;
+
+/* AIM_FLAG_READ_GROUPS: aim_set_submit reads past `base` (only with the flag). The first two members are laid out exactly like
+ * aim_batch_io_ref_t. base.n_pairs, base.requests and the texts (or text_pos) are per candidate; base.patterns holds n_reads rows;
+ * base.results, ops, cigars and runs receive one row per read. Packed input only with AIM_FLAG_REF_TEXTS: packed_patterns holds n_reads
+ * rows and raw_pairs lists reads (AIM_EINVAL otherwise). */
+typedef struct aim_batch_io_groups {
+    aim_batch_io_t base;
+    const uint64_t *text_pos;        /* AIM_FLAG_REF_TEXTS: [n_pairs]; else NULL */
+    uint32_t n_reads;
+    const uint32_t *read_offsets;    /* [n_reads + 1] */
+    aim_best_t *best;                /* out: [n_reads], or NULL */
+} aim_batch_io_groups_t;
+/* Host-side CSR check: AIM_OK when read_offsets[0] == 0, the offsets never decrease, every read has a candidate and
+ * read_offsets[n_reads] == n_pairs; else AIM_EINVAL naming the first bad read, which *bad_read (may be NULL) receives (a wrong
+ * last offset names read n_reads - 1). n_reads 0 is valid only with n_pairs 0. aim_set_submit runs it before anything is enqueued. */
+int aim_groups_check(uint32_t n_pairs, uint32_t n_reads, const uint32_t *read_offsets, uint32_t *bad_read);
+
 /* aim_set_configure with `slots` (1..4) buffer sets per device; max_raw_pairs bounds n_raw of a packed batch
  * (0 = packed input not used), max_runs the run buffer of a compact-CIGAR batch (0 = not used). */
 int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t max_pairs_per_device, uint32_t slots,
@@ -361,6 +401,15 @@ int aim_align_device(const aim_params_t *params, uint32_t n_pairs, const void *d
 int aim_align_device_ref(const aim_params_t *params, uint32_t n_pairs, const void *d_requests, const char *d_patterns,
                          const uint64_t *d_text_pos, const char *d_reference, uint64_t ref_len, void *d_results, char *d_ops,
                          void *d_scratch, size_t scratch_bytes, void *hip_stream);
+/* AIM_FLAG_READ_GROUPS: the stateless form. d_patterns holds n_reads rows, d_texts_or_null n_pairs rows (NULL with
+ * AIM_FLAG_REF_TEXTS, which reads d_text_pos_or_null / d_reference / ref_len like aim_align_device_ref; otherwise those are ignored),
+ * d_read_offsets the CSR (device memory, checked by the caller: aim_groups_check). d_results / d_ops / d_best receive n_reads rows
+ * (d_ops only with AIM_FLAG_BACKTRACE; d_best may be NULL). aim_scratch_bytes(params, n_pairs) under the flag covers n_reads = n_pairs.
+ * A CSR the check would refuse yields unspecified rows, never an access outside the buffers. */
+int aim_align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
+                            const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
+                            const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, void *d_scratch,
+                            size_t scratch_bytes, void *hip_stream);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
