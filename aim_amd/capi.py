@@ -30,6 +30,8 @@ FEATURE_REF_TEXTS = 0x20  # aim_features(): AIM_FLAG_REF_TEXTS is honoured
 REF_MINUS_STRAND = 1 << 63   # text_pos bit 63: the reverse complement of the window
 FLAG_READ_GROUPS = 0x800     # reads and their candidates: score-only pass, best candidate per read, the configured run on the winners
 FEATURE_READ_GROUPS = 0x40   # aim_features(): AIM_FLAG_READ_GROUPS is honoured
+FLAG_WFA_ESCALATE = 0x1000   # WFA: a lane kernel at a low cap over the batch, the flag-less plan over the pairs it left over that cap
+FEATURE_WFA_ESCALATE = 0x80  # aim_features(): AIM_FLAG_WFA_ESCALATE is honoured
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
 
 

@@ -80,7 +80,7 @@ struct Stage {
     int seq;                // K_DP_LANE: where the pattern row lives, 0 global memory, 1 LDS image, 2 registers (dp_lane_plan)
 };
 
-struct Plan {
+struct StagePlan {
     Stage main;
     Stage fb;               // the to-do pass behind the main kernel (wfa_wave, dp_lane or dp_strip); planned iff todo_bytes != 0
     // the scratch layout, offsets from its base
@@ -95,6 +95,17 @@ struct Plan {
     bool pk;                // the kernel reads the packed rows of the batch itself (no unpack pass)
     bool emits_runs;        // the kernel writes aim_cigar_t + runs itself (no ops rows, no cigar_rle_kernel)
     int bidir_t;            // K_WFA_BIDIR: the base-case threshold T (fb is wfa_wave at MAX_SCORE min(MAX_SCORE, T), run first)
+};
+
+// A plan is one StagePlan. AIM_FLAG_WFA_ESCALATE with a cap c > 0 makes it two: the base is the lane plan at MAX_SCORE c over the whole
+// batch, s2 the flag-less full-cap plan over the list of pairs the first stage left at c + 1 (batch_io.hpp escalate_select_kernel).
+// [stage 1 | stage 2 | list {count @0, pair ids @16..} | ballot masks | workgroup counts]; scratch_total covers all of it.
+struct Plan : StagePlan {
+    bool esc;               // AIM_FLAG_WFA_ESCALATE is set (the plan line ends in escalate=<esc_c>)
+    int esc_c;              // the first stage's cap; 0: one stage, the flag-less plan
+    StagePlan s2;
+    size_t s1_scratch;      // the first stage's own scratch_total
+    size_t s2_at, list_at, mask_at, count_at;
 };
 
 // The AIM_* environment variables, read HERE and nowhere else (see aim::Knobs, aim_device.hpp).
@@ -242,6 +253,8 @@ inline size_t ref_rows_at(size_t plan_scratch) { return (plan_scratch + 255) & ~
 inline size_t ref_rows_bytes(const aim_params_t &p, uint32_t n_pairs) { return (size_t)n_pairs * (size_t)p.read_size + 256; }
 // AIM_FLAG_READ_GROUPS: reads and their candidates (groups.hpp); the plans of its two passes never see the flag.
 inline bool is_groups(const aim_params_t &p) { return (p.flags & AIM_FLAG_READ_GROUPS) != 0; }
+// AIM_FLAG_WFA_ESCALATE: a lane kernel at a low cap over the batch, the flag-less plan over the pairs it left over that cap (plan_wfa).
+inline bool is_escalate(const aim_params_t &p) { return (p.flags & AIM_FLAG_WFA_ESCALATE) != 0; }
 // The params as this library keeps them: room for either extension, and the extension copied only when a flag says it exists.
 union XParams {
     aim_params_t base;
@@ -265,6 +278,15 @@ int validate_params(const aim_params_t &p)
     // before either extension is read: the caller's struct holds at most one of them (an aim_affine2p_params_t is shorter than
     // an aim_endsfree_params_t)
     if (is_endsfree(p) && is_affine2p(p)) return fail(AIM_EINVAL, "AIM_FLAG_AFFINE2P cannot be combined with AIM_FLAG_ENDSFREE");
+    if (is_escalate(p)) {
+        if (p.algo != AIM_ALGO_WFA) return fail(AIM_EINVAL, "AIM_FLAG_WFA_ESCALATE needs AIM_ALGO_WFA");
+        if (is_endsfree(p)) return fail(AIM_EINVAL, "AIM_FLAG_WFA_ESCALATE cannot be combined with AIM_FLAG_ENDSFREE");
+        if (is_affine2p(p)) return fail(AIM_EINVAL, "AIM_FLAG_WFA_ESCALATE cannot be combined with AIM_FLAG_AFFINE2P");
+        if (is_linear(p)) return fail(AIM_EINVAL, "AIM_FLAG_WFA_ESCALATE cannot be combined with AIM_FLAG_LINEAR");
+        if (is_w32(p)) return fail(AIM_EINVAL, "AIM_FLAG_WFA_ESCALATE cannot be combined with AIM_FLAG_WFA_W32");
+        if (is_bidir(p)) return fail(AIM_EINVAL, "AIM_FLAG_WFA_ESCALATE cannot be combined with AIM_FLAG_WFA_BIDIR");
+        if (is_groups(p)) return fail(AIM_EINVAL, "AIM_FLAG_WFA_ESCALATE cannot be combined with AIM_FLAG_READ_GROUPS (a follow-up)");
+    }
     if (is_linear(p)) {
         if (p.algo != AIM_ALGO_WFA) return fail(AIM_EINVAL, "AIM_FLAG_LINEAR needs AIM_ALGO_WFA");
         if (p.flags & AIM_FLAG_REDUCE) return fail(AIM_EINVAL, "AIM_FLAG_LINEAR cannot be combined with AIM_FLAG_REDUCE");
@@ -450,7 +472,7 @@ int plan_wfa_bidir(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn
     return AIM_OK;
 }
 
-int plan_wfa(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, uint32_t mode, Plan *pl)
+int plan_wfa_flagless(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, uint32_t mode, Plan *pl)
 {
     if (is_bidir(p)) return plan_wfa_bidir(p, n_pairs, kn, budget, pl);
     if (is_w32(p)) {
@@ -522,6 +544,61 @@ int plan_wfa(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint
         pl->fb.scratch_at = pl->hist_at + pl->hist_bytes;
     }
     pl->scratch_total = pl->fb.scratch_at + stage_bytes(pl->fb);
+    return AIM_OK;
+}
+
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline bool is_lane_plan(const StagePlan &pl) { return pl.main.kid == K_WFA_LANE || pl.main.kid == K_WFA_LANE_PK; }
+
+// AIM_FLAG_WFA_ESCALATE: c is the largest cap below MAX_SCORE whose flag-less plan (same params and mode otherwise) is a lane plan. Without
+// one, or when the flag-less plan is a lane plan already, the plan is the flag-less one. Else stage 1 is that lane plan over the batch and
+// stage 2 the flag-less plan at MAX_SCORE over the list of pairs stage 1 reports at c + 1: a pair of score <= c has the same wavefronts
+// under both caps, so its stage-1 row, ops bytes included, is final. Both stages write result rows (and ops rows); the fused run output
+// is not planned under escalation (the caller runs cigar_rle_kernel over the final rows, so the run total is the flag-less one).
+int plan_wfa(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, uint32_t mode, Plan *pl)
+{
+    if (!is_escalate(p)) return plan_wfa_flagless(p, n_pairs, kn, budget, mode, pl);
+    aim_params_t q = p;
+    q.flags &= ~AIM_FLAG_WFA_ESCALATE;
+    int rc = plan_wfa_flagless(q, n_pairs, kn, budget, mode, pl);
+    if (rc) return rc;
+    pl->esc = true;
+    if (is_lane_plan(*pl)) return AIM_OK;
+    const uint32_t mode2 = mode & ~MODE_RUNS_OUT;
+    // the lane test of plan_wfa_flagless alone (no group / wave planning per candidate cap); the plan is then made once, at c
+    const bool lanes = !kn.force_wave && !kn.no_lane;
+    auto lane_at = [&](int cap) {
+        aim_params_t q1 = q;
+        q1.max_score = cap;
+        return lanes && ((!kn.no_lane_pk && aim::wfa_lane_packed_supported(q1, !kn.no_lane_ext)) || aim::wfa_lane_supported(q1, !kn.no_lane_ext));
+    };
+    int c = std::min(p.max_score - 1, 64);
+    while (c > 0 && !lane_at(c)) --c;
+    if (c <= 0) return AIM_OK;
+    Plan s1;
+    memset(&s1, 0, sizeof s1);
+    {
+        aim_params_t q1 = q;
+        q1.max_score = c;
+        if (plan_wfa_flagless(q1, n_pairs, kn, budget, mode2, &s1) != AIM_OK || !is_lane_plan(s1)) return AIM_OK;
+    }
+    // stage 2 gets the budget stage 1 leaves (their regions are laid out one behind the other)
+    const uint64_t used = al256(s1.scratch_total);
+    const uint64_t budget2 = budget > 2 * used ? budget - used : budget;
+    Plan s2;
+    memset(&s2, 0, sizeof s2);
+    rc = plan_wfa_flagless(q, n_pairs, kn, budget2, mode2, &s2);
+    if (rc) return rc;
+    *pl = s1;
+    pl->esc = true;
+    pl->esc_c = c;
+    pl->s2 = s2;
+    pl->s1_scratch = s1.scratch_total;
+    pl->s2_at = al256(s1.scratch_total);
+    pl->list_at = pl->s2_at + al256(s2.scratch_total);
+    pl->mask_at = pl->list_at + aim::wfa_lane_todo_bytes(n_pairs);
+    pl->count_at = pl->mask_at + aim::escalate_mask_bytes(n_pairs);
+    pl->scratch_total = pl->count_at + aim::escalate_count_bytes(n_pairs);
     return AIM_OK;
 }
 
@@ -633,7 +710,7 @@ int plan_dp(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint6
     return AIM_OK;
 }
 
-const char *kernel_name(const Plan &pl, const aim_params_t &p)
+const char *kernel_name(const StagePlan &pl, const aim_params_t &p)
 {
     switch (pl.main.kid) {
     case K_WFA_WAVE: return "wfa_wave_kernel";
@@ -652,7 +729,7 @@ const char *kernel_name(const Plan &pl, const aim_params_t &p)
 }
 
 // One line that identifies a plan completely: kernel, lanes / wavefronts per pair, grid, block, LDS, scratch.
-int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint64_t budget, char *out, size_t cap)
+int describe_stage_plan(const StagePlan &pl, const aim_params_t &p, uint32_t n_pairs, uint64_t budget, char *out, size_t cap)
 {
     char extra[160] = "";
     const Stage &m = pl.main, &fb = pl.fb;
@@ -680,6 +757,24 @@ int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint6
                     is_ref(p) ? " ref=1" : "");
 }
 
+// ... AIM_FLAG_WFA_ESCALATE: "<stage 1 line> | <stage 2 line> escalate=c", or the flag-less line and " escalate=0"
+int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint64_t budget, char *out, size_t cap)
+{
+    if (!pl.esc) return describe_stage_plan(pl, p, n_pairs, budget, out, cap);
+    char a[384], b[384];
+    if (!pl.esc_c) {
+        describe_stage_plan(pl, p, n_pairs, budget, a, sizeof a);
+        return snprintf(out, cap, "%s escalate=0", a);
+    }
+    aim_params_t p1 = p;
+    p1.max_score = pl.esc_c;
+    StagePlan s1 = pl;
+    s1.scratch_total = pl.s1_scratch;
+    describe_stage_plan(s1, p1, n_pairs, budget, a, sizeof a);
+    describe_stage_plan(pl.s2, p, n_pairs, budget, b, sizeof b);
+    return snprintf(out, cap, "%s | %s escalate=%d", a, b, pl.esc_c);
+}
+
 int make_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, Plan *pl, uint32_t mode = 0u)
 {
     int rc = validate_params(p);
@@ -690,7 +785,7 @@ int make_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uin
          : p.algo == AIM_ALGO_WFA  ? plan_wfa(p, n_pairs, kc, budget, mode, pl)
                                    : plan_dp(p, n_pairs, kc, budget, pl);
     if (rc == AIM_OK && kn.plan_debug) {
-        char line[384];
+        char line[800];
         describe_plan(*pl, p, n_pairs, budget, line, sizeof line);
         fprintf(stderr, "[aim plan] %s\n", line);
     }
@@ -769,13 +864,16 @@ struct FusedIo {
     uint32_t runs_cap = 0, run_slot = 0;
 };
 
-// Enqueue one alignment launch that follows plan `pl` (made for >= n_pairs pairs under the caller's knobs and budget).
-int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t n_pairs, const void *d_req,
-           const char *d_pat, const char *d_txt, void *d_res, char *d_ops, void *d_scratch, size_t scratch_bytes,
-           hipStream_t stream, const FusedIo *fio = nullptr, AuxStream *slot_aux = nullptr)
+// Enqueue one alignment launch that follows the one-stage plan `pl` (made for >= n_pairs pairs under the caller's knobs and budget).
+// list_in (AIM_FLAG_WFA_ESCALATE, second stage): the launch's pairs are those of the device-side list {count @0, pair ids @16..}, at most
+// n_pairs of them; every buffer stays the batch's. Only wfa_group (+ its traceback) and wfa_wave take one.
+int launch_one(const StagePlan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t n_pairs, const void *d_req,
+               const char *d_pat, const char *d_txt, void *d_res, char *d_ops, void *d_scratch, size_t scratch_bytes,
+               hipStream_t stream, const FusedIo *fio = nullptr, AuxStream *slot_aux = nullptr, const uint32_t *list_in = nullptr)
 {
     if (n_pairs == 0) return AIM_OK;
     const bool bt = p.flags & AIM_FLAG_BACKTRACE;
+    if (list_in && pl.main.kid != K_WFA_GROUP && pl.main.kid != K_WFA_WAVE) return fail(AIM_EINVAL, "plan takes no pair list");
     if (pl.pk && !pl.pack_first && (!fio || !fio->packedP || !fio->packedT)) return fail(AIM_EINVAL, "plan reads packed rows but none were given");
     if (pl.emits_runs && (!fio || !fio->cig || !fio->runs || !fio->cursor)) return fail(AIM_EINVAL, "plan emits the compact CIGAR but no buffers were given");
     const bool reads_ascii = !(pl.main.kid == K_WFA_LANE_PK && !pl.pack_first);   // (wfa_group reads them for its to-do pairs even on packed batches)
@@ -815,13 +913,14 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
     kb.todo = reinterpret_cast<const uint32_t *>((char *)d_scratch + pl.todo_at);
     kb.packedP = kb.packedT = nullptr;
     kb.cig = nullptr;
-    if (kn.poison_ops >= 0 && d_ops && bt)   // debugging aid: results must not depend on what the ops rows held before (only ops[begin_offset, end_offset) is written)
+    if (kn.poison_ops >= 0 && d_ops && bt && !list_in)   // (the second stage keeps the first stage's rows) debugging aid: results must not depend on what the ops rows held before (only ops[begin_offset, end_offset) is written)
         HIP_TRY(hipMemsetAsync(d_ops, kn.poison_ops & 0xff, (size_t)n_pairs * 2 * p.read_size, stream));
     if (pl.todo_bytes) HIP_TRY(hipMemsetAsync((char *)d_scratch + pl.todo_at, 0, 64, stream));   // the to-do count, zeroed per launch
     switch (m.kid) {
     case K_WFA_WAVE:
     case K_DP_LANE:
     case K_DP_STRIP:
+        if (list_in) ka.todo = list_in;
         launch_stage(p, m, ka, stream);
         break;
     case K_WFA_LANE:
@@ -876,12 +975,16 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
             kc.n_pairs = std::min(chunk, n_pairs - first);
             kc.pair_base = first;
             kc.scratch_per_wave = pl.hist_at + (overlap ? (size_t)b * buf_bytes : 0);   // where this chunk's history regions start (the to-do region is in front)
-            kc.req = reinterpret_cast<const aim_request_t *>(static_cast<const char *>(d_req) + (size_t)first * rqb);
-            if (d_pat) { kc.patterns = d_pat + (size_t)first * p.read_size; kc.texts = d_txt + (size_t)first * p.read_size; }
-            if (d_res) kc.res = reinterpret_cast<aim_result_t *>(static_cast<char *>(d_res) + (size_t)first * rsb);
-            if (d_ops) kc.ops = d_ops + (size_t)first * 2 * p.read_size;
-            if (ka.packedP) { kc.packedP = ka.packedP + (size_t)first * npw; kc.packedT = ka.packedT + (size_t)first * npw; }
-            if (ka.cig) kc.cig = ka.cig + first;
+            if (list_in) {   // positions [first, first + chunk) of the list; the arrays stay the batch's (indexed by the listed pair ids)
+                kc.todo = list_in;
+            } else {
+                kc.req = reinterpret_cast<const aim_request_t *>(static_cast<const char *>(d_req) + (size_t)first * rqb);
+                if (d_pat) { kc.patterns = d_pat + (size_t)first * p.read_size; kc.texts = d_txt + (size_t)first * p.read_size; }
+                if (d_res) kc.res = reinterpret_cast<aim_result_t *>(static_cast<char *>(d_res) + (size_t)first * rsb);
+                if (d_ops) kc.ops = d_ops + (size_t)first * 2 * p.read_size;
+                if (ka.packedP) { kc.packedP = ka.packedP + (size_t)first * npw; kc.packedT = ka.packedT + (size_t)first * npw; }
+                if (ka.cig) kc.cig = ka.cig + first;
+            }
             // a chunk smaller than the plan's grid needs fewer workgroups (the grid stays a multiple of 8)
             uint32_t grid = m.grid;
             {
@@ -890,16 +993,21 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
                 if (grid > need) grid = need < 8u ? 8u : need;
             }
             if (overlap && ci >= 2) HIP_TRY(hipStreamWaitEvent(stream, aux->walked[b], 0));   // buffer b: its previous chunk has been walked
-            aim::wfa_group_launch(p, pl.group_g, pl.gcfg, grid, m.lds, kc, stream);
+            auto tb_launch = [&](hipStream_t ts) {
+                if (list_in) aim::wfa_group_tb_todo_launch(pl.gcfg, kc.n_pairs, kc, ts);
+                else aim::wfa_group_tb_launch(p, pl.gcfg, kc.n_pairs, kc, ts);
+            };
+            if (list_in) aim::wfa_group_todo_launch(p, pl.group_g, pl.gcfg, grid, m.lds, kc, stream);
+            else aim::wfa_group_launch(p, pl.group_g, pl.gcfg, grid, m.lds, kc, stream);
             HIP_TRY(hipGetLastError());
             if (overlap) {
                 HIP_TRY(hipEventRecord(aux->computed[b], stream));
                 HIP_TRY(hipStreamWaitEvent(aux->stream, aux->computed[b], 0));
-                aim::wfa_group_tb_launch(p, pl.gcfg, kc.n_pairs, kc, aux->stream);
+                tb_launch(aux->stream);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(aux->walked[b], aux->stream));
             } else if (bt) {
-                aim::wfa_group_tb_launch(p, pl.gcfg, kc.n_pairs, kc, stream);
+                tb_launch(stream);
                 HIP_TRY(hipGetLastError());
             }
         }
@@ -951,6 +1059,53 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
     return AIM_OK;
 }
 
+// Enqueue the launches of plan `pl`. AIM_FLAG_WFA_ESCALATE with two stages: the lane plan at cap esc_c over the batch, the list of the
+// pairs it left at esc_c + 1 (ascending pair order), the full-cap plan over that list -- one stream, no host round trip.
+int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t n_pairs, const void *d_req,
+           const char *d_pat, const char *d_txt, void *d_res, char *d_ops, void *d_scratch, size_t scratch_bytes,
+           hipStream_t stream, const FusedIo *fio = nullptr, AuxStream *slot_aux = nullptr)
+{
+    // (without the flag p may be the base of an extension struct, which launch_one reads through its address: no copy of it here)
+    if (!pl.esc) return launch_one(pl, kn, p, n_pairs, d_req, d_pat, d_txt, d_res, d_ops, d_scratch, scratch_bytes, stream, fio, slot_aux);
+    if (!pl.esc_c || n_pairs == 0) {
+        aim_params_t q = p;
+        q.flags &= ~AIM_FLAG_WFA_ESCALATE;
+        return launch_one(pl, kn, q, n_pairs, d_req, d_pat, d_txt, d_res, d_ops, d_scratch, scratch_bytes, stream, fio, slot_aux);
+    }
+    if (scratch_bytes < pl.scratch_total || !d_scratch) return fail(AIM_EINVAL, "scratch too small: need %zu bytes, got %zu", pl.scratch_total, scratch_bytes);
+    if (!d_res) return fail(AIM_EINVAL, "null device buffer");
+    aim_params_t q = p, p1 = p;
+    q.flags &= ~AIM_FLAG_WFA_ESCALATE;
+    p1.flags = q.flags;
+    p1.max_score = pl.esc_c;
+    char *base = static_cast<char *>(d_scratch);
+    StagePlan s1 = pl;
+    s1.scratch_total = pl.s1_scratch;
+    int rc = launch_one(s1, kn, p1, n_pairs, d_req, d_pat, d_txt, d_res, d_ops, base, pl.s2_at, stream, fio, slot_aux);
+    if (rc) return rc;
+    uint32_t *list = reinterpret_cast<uint32_t *>(base + pl.list_at);
+    uint2 *masks = reinterpret_cast<uint2 *>(base + pl.mask_at);
+    uint32_t *counts = reinterpret_cast<uint32_t *>(base + pl.count_at);
+    const bool res8 = p.flags & AIM_FLAG_RES8;
+    const dim3 grid((n_pairs + aim::kEscTile - 1) / aim::kEscTile);
+    hipLaunchKernelGGL(aim::escalate_select_kernel, grid, dim3(256), 0, stream, static_cast<const uint32_t *>(d_res), n_pairs, res8 ? 2u : 6u,
+                       res8 ? 1u : 3u, (int32_t)(pl.esc_c + 1), masks, counts);
+    hipLaunchKernelGGL(aim::escalate_list_kernel, grid, dim3(256), 0, stream, n_pairs, masks, counts, list);
+    HIP_TRY(hipGetLastError());
+    if (pl.pk && !pl.s2.pk) {   // a packed batch whose second stage reads ASCII rows: the listed pairs' rows, expanded in place
+        aim::KArgs ku;
+        memset(&ku, 0, sizeof ku);
+        ku.p = q;
+        ku.n_pairs = n_pairs;
+        ku.req = static_cast<const aim_request_t *>(d_req);
+        if (!d_pat || !d_txt || !fio || !fio->packedP || !fio->packedT) return fail(AIM_EINVAL, "null device buffer");
+        hipLaunchKernelGGL(aim::unpack_todo_rows_kernel, dim3(256), dim3(256), 0, stream, ku, list, fio->packedP, fio->packedT, const_cast<char *>(d_pat),
+                           const_cast<char *>(d_txt));
+        HIP_TRY(hipGetLastError());
+    }
+    return launch_one(pl.s2, kn, q, n_pairs, d_req, d_pat, d_txt, d_res, d_ops, base + pl.s2_at, pl.s2.scratch_total, stream, fio, slot_aux, list);
+}
+
 // AIM_FLAG_REF_TEXTS: text rows [n_rows][READ_SIZE] of `out` gathered from the reference; row r is the window of pair idx[r]
 // (idx == nullptr: pair r). ka carries the params and the requests.
 int enqueue_gather(const aim::KArgs &ka, const uint64_t *d_tpos, const char *ref, uint64_t ref_len, const uint32_t *idx, uint32_t n_rows,
@@ -979,7 +1134,6 @@ struct GroupsPlan {
     // aim_align_device_groups: the rest of its scratch, offsets from the base (256-B aligned)
     size_t cand_p_at, cand_t_at, res1_at, map_at, sel_at, req2_at, pat2_at, txt2_at, total;
 };
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline XParams groups_pass_params(const aim_params_t &p, uint32_t drop)
 {
     XParams x = copy_params(p);
@@ -1349,7 +1503,7 @@ int aim_abi_version(void) { return AIM_ABI_VERSION; }
 uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
-           AIM_FEATURE_READ_GROUPS;
+           AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -1944,7 +2098,7 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
             // holding a byte outside A/C/G/T re-aligned by the general kernel over a to-do list); every other plan runs as for an
             // ASCII batch after the gather
             Stage ref_fb;
-            const bool ref_fused = ref && packed && pl.pk && pl.main.kid == K_WFA_LANE_PK && !pl.pack_first && s.d_reftodo &&
+            const bool ref_fused = ref && packed && pl.pk && pl.main.kid == K_WFA_LANE_PK && !pl.pack_first && s.d_reftodo && !pl.esc_c &&
                                    ref_todo_stage(set, d, s.scratch_bytes, n, &ref_fb);
             if (ref && packed && !ref_fused && pl.pk) {
                 mode &= ~MODE_PACKED_IN;

@@ -433,4 +433,69 @@ __global__ __launch_bounds__(256) void gather_todo_rows_kernel(KArgs a, const ui
     }
 }
 
+// ---- AIM_FLAG_WFA_ESCALATE: the second stage's work list --------------------------------------------------------------------
+// The first stage ran the whole batch at a low cap c on a lane kernel; the pairs it left over the cap report c + 1. Their ids go, in
+// ascending pair order, to a to-do list {count @0, pair ids @16..} that the full-cap plan drains. One pass over the results:
+// escalate_select_kernel reads each score once and keeps one ballot mask per 64 pairs plus one count per workgroup (kEscTile pairs);
+// escalate_list_kernel (same grid) turns masks and counts into list positions -- a workgroup's base is the sum of the counts before it --
+// so the list does not depend on scheduling. Plain vector stores, no atomics. The masks and counts are read 1/64th of the results' bytes.
+constexpr uint32_t kEscTile = 4096;                          // pairs per workgroup: 4 wavefronts x 16 groups of 64
+inline size_t escalate_mask_bytes(uint32_t n_pairs) { return (((size_t)n_pairs + 63) / 64 * 8 + 255) & ~(size_t)255; }
+inline size_t escalate_count_bytes(uint32_t n_pairs) { return ((((size_t)n_pairs + kEscTile - 1) / kEscTile) * 4 + 255) & ~(size_t)255; }
+
+// res: result_t rows (stride_dw 6, score_dw 3) or {idx, score} rows (2, 1)
+__global__ __launch_bounds__(256) void escalate_select_kernel(const uint32_t *res, uint32_t n_pairs, uint32_t stride_dw, uint32_t score_dw, int32_t over,
+                                                              uint2 *masks, uint32_t *counts)
+{
+    __shared__ uint32_t wave_n[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t n_groups = (n_pairs + 63u) / 64u;
+    const uint32_t g0 = blockIdx.x * (kEscTile / 64u) + wave * 16u;
+    uint32_t mine = 0;
+    for (uint32_t j = 0; j < 16u; ++j) {
+        const uint32_t g = g0 + j;
+        if (g >= n_groups) break;                            // (wave-uniform)
+        const uint32_t pair = g * 64u + lane;
+        const bool hit = pair < n_pairs && (int32_t)res[(uint64_t)pair * stride_dw + score_dw] == over;
+        const unsigned long long m = __ballot(hit);
+        mine += (uint32_t)__builtin_popcountll(m);
+        if (lane == 0) masks[g] = make_uint2((uint32_t)m, (uint32_t)(m >> 32));
+    }
+    if (lane == 0) wave_n[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+}
+
+__global__ __launch_bounds__(256) void escalate_list_kernel(uint32_t n_pairs, const uint2 *masks, const uint32_t *counts, uint32_t *todo)
+{
+    __shared__ uint32_t part[4];
+    __shared__ uint32_t goff[64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t n_groups = (n_pairs + 63u) / 64u;
+    // list positions before this workgroup: the counts of the workgroups before it
+    // (every workgroup re-reads the counts before it: B^2 / 2 dwords over a grid of B = n / 4096 workgroups -- 2 MB at 4 Mi pairs, 32 MB at
+    //  16 Mi, against the 32-128 MB of result rows the first kernel read; a batch is bounded by the device buffers long before this matters)
+    uint32_t sum = 0;
+    for (uint32_t b = threadIdx.x; b < blockIdx.x; b += 256u) sum += counts[b];
+    for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) part[wave] = sum;
+    // ... and before each of its 64 groups (wavefront 0: an exclusive scan of the groups' populations)
+    const uint32_t gt = blockIdx.x * (kEscTile / 64u) + lane;
+    uint32_t pop = 0;
+    if (wave == 0 && gt < n_groups) { const uint2 m = masks[gt]; pop = (uint32_t)(__builtin_popcount(m.x) + __builtin_popcount(m.y)); }
+    uint32_t incl = pop;
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t v = __shfl_up(incl, o); if ((int)lane >= o) incl += v; }
+    if (wave == 0) goff[lane] = incl - pop;
+    __syncthreads();
+    const uint32_t base = part[0] + part[1] + part[2] + part[3];
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) todo[0] = base + counts[blockIdx.x];   // the list's count
+    for (uint32_t j = 0; j < 16u; ++j) {
+        const uint32_t gl = wave * 16u + j, g = blockIdx.x * (kEscTile / 64u) + gl;
+        if (g >= n_groups) break;
+        const uint2 mw = masks[g];
+        const unsigned long long m = ((unsigned long long)mw.y << 32) | mw.x;
+        if ((m >> lane) & 1ull) todo[16u + base + goff[gl] + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = g * 64u + lane;
+    }
+}
+
 }  // namespace aim

@@ -152,7 +152,10 @@ __device__ __forceinline__ int group_min(int v)
 #else
 #define AIM_GSTAMP(i) do { } while (0)
 #endif
-template <int G, bool REDUCE, bool BT, bool MODW = false, bool EF = false, bool A2P = false, bool LIN = false>
+// TODO_IN (AIM_FLAG_WFA_ESCALATE, second stage): the launch's pairs are entries [pair_base, pair_base + n_pairs) of the device-side list
+// a.todo = {count @0, pair ids @16..}, cut at the list's count; every array is indexed by the listed pair id (the history regions by the
+// position inside the launch) and the rows are read straight from global memory (listed pairs are not neighbours: no staging DMA).
+template <int G, bool REDUCE, bool BT, bool MODW = false, bool EF = false, bool A2P = false, bool LIN = false, bool TODO_IN = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GROUP_A2P_MIN_WAVES : LIN ? AIM_GROUP_LIN_MIN_WAVES : AIM_GROUP_MIN_WAVES))) void wfa_group_kernel(KArgs a, GroupCfg c)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -164,7 +167,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
     // raw rows of one array, whole 16-B chunks; a whole-wavefront group (G == 64) packs straight from global memory
     // instead (one pair per ~2 ms of compute: nothing to hide, and 2*READ_SIZE bytes of LDS buy residency)
     const bool pk = a.packedP != nullptr;               // wave-uniform: the batch arrived packed (2 bits per base): no staging, no validation
-    const int rows_dw = (G >= AIM_GROUP_DIRECT_G || pk) ? 0 : ((PPW * rs + 15) / 16) * 4;
+    const int rows_dw = (G >= AIM_GROUP_DIRECT_G || pk || TODO_IN) ? 0 : ((PPW * rs + 15) / 16) * 4;
     uint32_t *rowsP = reinterpret_cast<uint32_t *>(smem);
     uint32_t *rowsT = rowsP + rows_dw;
     uint32_t *pairmem = rowsT + rows_dw + 1;
@@ -186,13 +189,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
     uint32_t *todo = reinterpret_cast<uint32_t *>(a.scratch);
     // BACKTRACE: every wavefront is also streamed to the pair's history region in HBM (GroupCfg); wfa_group_tb_kernel walks it.
     char *hist_base = BT ? a.scratch + a.scratch_per_wave : nullptr;
-    const uint32_t n_units = (a.n_pairs + PPW - 1) / PPW;
+    uint32_t n_pairs = a.n_pairs;
+    if constexpr (TODO_IN) {
+        const uint32_t listed = a.todo[LANE_TODO_COUNT];
+        n_pairs = listed > a.pair_base ? min(a.n_pairs, listed - a.pair_base) : 0u;
+    }
+    auto pair_id = [&](uint32_t pos) -> uint32_t {   // the batch's pair behind position pos of the launch
+        if constexpr (TODO_IN) return pos < n_pairs ? a.todo[LANE_TODO_LIST + a.pair_base + pos] : 0u;
+        else return pos;
+    };
+    const uint32_t n_units = (n_pairs + PPW - 1) / PPW;
     const int nchunk_total = (PPW * rs + 15) / 16;       // 16-B chunks per array per unit (the last one may run into the next row / tail slack)
 
     auto dma = [&](uint32_t unit) {
-        if (G >= AIM_GROUP_DIRECT_G || pk) return;
+        if (G >= AIM_GROUP_DIRECT_G || pk || TODO_IN) return;
         const uint32_t pair0 = unit * PPW;
-        const uint32_t rows = min((uint32_t)PPW, a.n_pairs - pair0);
+        const uint32_t rows = min((uint32_t)PPW, n_pairs - pair0);
         const int nchunks = (int)((rows * rs + 15) / 16);
         const char *gp = a.patterns + (uint64_t)pair0 * rs, *gt = a.texts + (uint64_t)pair0 * rs;
         for (int base = 0; base < nchunk_total; base += kWave) {
@@ -237,11 +249,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
     rq_next.pattern_len = rq_next.text_len = 0; rq_next.padding = 0; rq_next.idx = 0;
     if (have) {
         dma(unit);
-        if (unit * PPW + q < a.n_pairs) rq_next = load_request(a, unit * PPW + q);
+        if (unit * PPW + q < n_pairs) rq_next = load_request(a, pair_id(unit * PPW + q));
     }
     for (uint32_t it = 0; have; ++it) {
         const uint32_t pair = unit * PPW + q;
-        const bool active = pair < a.n_pairs;
+        const bool active = pair < n_pairs;
+        const uint32_t pid = pair_id(pair);   // (== pair without TODO_IN)
         __builtin_amdgcn_s_waitcnt(0);
         __syncthreads();
         const aim_request_t rq = rq_next;
@@ -253,15 +266,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
         uint32_t bad = 0;
         if (pk) {   // the wire image IS the LDS image: the group's lanes copy the ceil(READ_SIZE/16) dwords of each row
             const int npw = (rs + 15) / 16;
-            const uint32_t *gp = a.packedP + (uint64_t)pair * npw, *gt = a.packedT + (uint64_t)pair * npw;
+            const uint32_t *gp = a.packedP + (uint64_t)pid * npw, *gt = a.packedT + (uint64_t)pid * npw;
             for (int j = g; j < npw; j += G) {
                 pkP[j] = active ? __builtin_nontemporal_load(gp + j) : 0u;
                 pkT[j] = active ? __builtin_nontemporal_load(gt + j) : 0u;
             }
             if (g == 0) { pkP[c.np - 1] = 0u; pkT[c.np - 1] = 0u; }
         } else {
-            const uint32_t *rp = G >= AIM_GROUP_DIRECT_G ? reinterpret_cast<const uint32_t *>(a.patterns + (uint64_t)pair * rs) : rowsP + (q * rs) / 4;
-            const uint32_t *rt = G >= AIM_GROUP_DIRECT_G ? reinterpret_cast<const uint32_t *>(a.texts + (uint64_t)pair * rs) : rowsT + (q * rs) / 4;
+            constexpr bool direct = G >= AIM_GROUP_DIRECT_G || TODO_IN;
+            const uint32_t *rp = direct ? reinterpret_cast<const uint32_t *>(a.patterns + (uint64_t)pid * rs) : rowsP + (q * rs) / 4;
+            const uint32_t *rt = direct ? reinterpret_cast<const uint32_t *>(a.texts + (uint64_t)pid * rs) : rowsT + (q * rs) / 4;
             const int npw = (rs + 15) / 16;
             for (int j = g; j < npw; j += G) {
 #pragma unroll
@@ -272,7 +286,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int w = 4 * j + i;
-                        const uint32_t av = (4 * w < rs && (G < AIM_GROUP_DIRECT_G || active)) ? r[w] : 0u;
+                        const uint32_t av = (4 * w < rs && (!direct || active)) ? r[w] : 0u;
                         const uint32_t t = (av >> 1) & 0x03030303u;
                         const uint32_t rec = __builtin_amdgcn_perm(0u, 0x47544341u, t);
                         const int rem = len - 4 * w;
@@ -298,7 +312,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
         __syncthreads();
         if (nhave) {
             dma(nunit);
-            if (nunit * PPW + q < a.n_pairs) rq_next = load_request(a, nunit * PPW + q);
+            if (nunit * PPW + q < n_pairs) rq_next = load_request(a, pair_id(nunit * PPW + q));
         }
         __builtin_amdgcn_sched_barrier(0);
 
@@ -384,7 +398,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
             meta[0] = 0; meta[1] = 0; meta[2] = (int16_t)flags;
         }
         if (BT && a.cig == nullptr && active && bad == 0u) {   // memset(cigar->operations, 'M', 2*READ_SIZE), wfa.c:465 (ops-row output only)
-            uint4 *orow = reinterpret_cast<uint4 *>(a.ops + (uint64_t)pair * 2 * rs);
+            uint4 *orow = reinterpret_cast<uint4 *>(a.ops + (uint64_t)pid * 2 * rs);
             const uint4 mm = make_uint4(0x4D4D4D4Du, 0x4D4D4D4Du, 0x4D4D4D4Du, 0x4D4D4D4Du);
             // (only the pieces that can hold a printed operation: begin_offset >= min(plen, tlen) - MAX_SCORE / e, wfa_lane.hpp)
             // (gap_e == 0: gaps cost nothing to extend and MAX_SCORE bounds no length -- the whole row is written)
@@ -622,7 +636,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
             }
             if (bad != 0u) {
                 const uint32_t slot = atomicAdd(&todo[LANE_TODO_COUNT], 1u);
-                todo[LANE_TODO_LIST + slot] = pair + a.pair_base;
+                todo[LANE_TODO_LIST + slot] = TODO_IN ? pid : pair + a.pair_base;
             } else if (!BT) {
                 aim_result_t r;
                 r.max_operations = plen + tlen;
@@ -637,7 +651,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
 #ifdef AIM_GROUP_COUNT_TRIPS
                 r.max_operations = r.begin_offset = r.end_offset = 0;
 #endif
-                store_result(a, pair, r);
+                store_result(a, pid, r);
             }
         }
 #ifdef AIM_GROUP_COUNT_TRIPS
@@ -645,7 +659,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(A2P ? AIM_GR
             int kt = dbg_kt, et = dbg_et, st = dbg_st;
             for (int o = 32; o; o >>= 1) { kt += __shfl_xor(kt, o); et += __shfl_xor(et, o); st += __shfl_xor(st, o); }
             __builtin_amdgcn_s_waitcnt(0);   // (after the pairs' own result stores)
-            if (lane == 0 && unit * PPW < a.n_pairs && a.res != nullptr && !(a.p.flags & AIM_FLAG_RES8)) {
+            if (lane == 0 && unit * PPW < n_pairs && a.res != nullptr && !(a.p.flags & AIM_FLAG_RES8)) {
                 aim_result_t *r0 = a.res + (size_t)unit * PPW;
                 r0->max_operations = kt; r0->begin_offset = et; r0->end_offset = st;
             }
@@ -930,12 +944,19 @@ __device__ __forceinline__ int group_tb_walk_lin(const GroupCfg &c, const TbRow 
     return status;
 }
 
-template <bool RUNS, bool MODW, bool EF = false, bool A2P = false, bool LIN = false>
+template <bool RUNS, bool MODW, bool EF = false, bool A2P = false, bool LIN = false, bool TODO_IN = false>
 __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
 {
     const int lane = threadIdx.x;
     const uint32_t pair = blockIdx.x * kWave + lane;
-    const bool in_batch = pair < a.n_pairs;
+    uint32_t n_pairs = a.n_pairs;
+    if constexpr (TODO_IN) {   // (as wfa_group_kernel: positions of the list, cut at its count)
+        const uint32_t listed = a.todo[LANE_TODO_COUNT];
+        n_pairs = listed > a.pair_base ? min(a.n_pairs, listed - a.pair_base) : 0u;
+    }
+    const bool in_batch = pair < n_pairs;
+    uint32_t pid = pair;
+    if constexpr (TODO_IN) pid = in_batch ? a.todo[LANE_TODO_LIST + a.pair_base + pair] : 0u;
     const int rs = a.p.read_size;
     const int U = c.unit;                                // the history table is indexed in score units (GroupCfg::unit)
     const int X = a.p.mismatch / U, OE = (a.p.gap_o + a.p.gap_e) / U, E = a.p.gap_e / U, MS = a.p.max_score;
@@ -946,7 +967,7 @@ __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
     const int16_t *pool = reinterpret_cast<const int16_t *>(hreg + c.pool_off);
     aim_request_t rq;
     rq.pattern_len = rq.text_len = 0; rq.padding = 0; rq.idx = 0;
-    if (active) rq = load_request(a, pair);
+    if (active) rq = load_request(a, pid);
     const int plen = rq.pattern_len, tlen = rq.text_len;
     const int final_score = hd.final_score;
     const bool walk = active && final_score <= MS;      // beyond MAX_SCORE the reference returns without a backtrace (wfa.c:368-376, MRAM variant)
@@ -959,10 +980,10 @@ __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
             coll.cur_op = (uint32_t)'M'; coll.cur_len = 1u;
             coll.flush();
         }
-        store_cigar(a, pair, active, rq.idx, final_score, status, coll, 0u, lane);
+        store_cigar(a, pid, active, rq.idx, final_score, status, coll, 0u, lane);
     } else {
         OpsSink sink;
-        sink.ops = a.ops + (uint64_t)(active ? pair : 0u) * 2 * rs;
+        sink.ops = a.ops + (uint64_t)(active ? pid : 0u) * 2 * rs;
         sink.cap = 2 * rs;
         sink.pos = plen + tlen - 1;                       // edit_cigar_allocate, wfa.c:57-67
         if (walk) {
@@ -984,7 +1005,7 @@ __global__ __launch_bounds__(64) void wfa_group_tb_kernel(KArgs a, GroupCfg c)
             r.score = final_score;
             r.status = status;
             r.idx = rq.idx;
-            store_result(a, pair, r);
+            store_result(a, pid, r);
         }
     }
 }
@@ -1282,6 +1303,53 @@ void wfa_group_launch(const aim_params_t &p, int G, const GroupCfg &c, uint32_t 
 }
 #else
 void wfa_group_launch(const aim_params_t &p, int G, const GroupCfg &c, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s);
+#endif
+
+// AIM_FLAG_WFA_ESCALATE, second stage: the same kernels over the device-side list ka.todo (TODO_IN above). Global gap-affine WFA only (the
+// flag is refused with ends-free, affine2p and gap-linear); result_t / {idx, score} rows and ops rows out (no fused run output). They are
+// instantiated in a translation unit of their own (tu_wfa_group_todo.hip defines AIM_TU_WFA_GROUP_TODO).
+#ifdef AIM_TU_WFA_GROUP_TODO
+void wfa_group_tb_todo_launch(const GroupCfg &c, uint32_t n_pairs, const KArgs &ka, hipStream_t s)
+{
+    const uint32_t grid = (n_pairs + kWave - 1) / kWave;
+    if (c.wmagic) hipLaunchKernelGGL((wfa_group_tb_kernel<false, true, false, false, false, true>), dim3(grid), dim3(kWave), 0, s, ka, c);
+    else hipLaunchKernelGGL((wfa_group_tb_kernel<false, false, false, false, false, true>), dim3(grid), dim3(kWave), 0, s, ka, c);
+}
+void wfa_group_todo_launch(const aim_params_t &p, int G, const GroupCfg &c, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s)
+{
+    const bool red = p.flags & AIM_FLAG_REDUCE, bt = p.flags & AIM_FLAG_BACKTRACE;
+#define AIM_GRP_TODO(GG, MW)                                                                                                                     \
+    do {                                                                                                                                        \
+        if (red && bt) hipLaunchKernelGGL((wfa_group_kernel<GG, true, true, MW, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);  \
+        else if (red) hipLaunchKernelGGL((wfa_group_kernel<GG, true, false, MW, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);  \
+        else if (bt) hipLaunchKernelGGL((wfa_group_kernel<GG, false, true, MW, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);   \
+        else hipLaunchKernelGGL((wfa_group_kernel<GG, false, false, MW, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);          \
+    } while (0)
+    if (c.wmagic) {   // (as wfa_group_launch: modulo rows exist with the reduction at G = 16, and G = 8 when forced)
+        if (G == 8) {
+            if (bt) hipLaunchKernelGGL((wfa_group_kernel<8, true, true, true, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);
+            else hipLaunchKernelGGL((wfa_group_kernel<8, true, false, true, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);
+            return;
+        }
+        if (bt) hipLaunchKernelGGL((wfa_group_kernel<16, true, true, true, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);
+        else hipLaunchKernelGGL((wfa_group_kernel<16, true, false, true, false, false, false, true>), dim3(grid), dim3(kWave), lds, s, ka, c);
+        return;
+    }
+    switch (G) {
+    case 1: AIM_GRP_TODO(1, false); break;
+    case 2: AIM_GRP_TODO(2, false); break;
+    case 4: AIM_GRP_TODO(4, false); break;
+    case 8: AIM_GRP_TODO(8, false); break;
+    case 16: AIM_GRP_TODO(16, false); break;
+    case 32: AIM_GRP_TODO(32, false); break;
+    case 64: AIM_GRP_TODO(64, false); break;
+    default: break;
+    }
+#undef AIM_GRP_TODO
+}
+#else
+void wfa_group_tb_todo_launch(const GroupCfg &c, uint32_t n_pairs, const KArgs &ka, hipStream_t s);
+void wfa_group_todo_launch(const aim_params_t &p, int G, const GroupCfg &c, uint32_t grid, size_t lds, const KArgs &ka, hipStream_t s);
 #endif
 
 }  // namespace aim

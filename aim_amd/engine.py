@@ -13,7 +13,7 @@ import numpy as np
 
 from . import capi
 from .capi import (ALGO_BY_NAME, ALGO_NW, ALGO_SWG, ALGO_WFA, FLAG_AFFINE2P, FLAG_BACKTRACE, FLAG_ENDSFREE, FLAG_LINEAR, FLAG_REDUCE,
-                   FLAG_READ_GROUPS, FLAG_REF_TEXTS, FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16, FLAG_WFA_BIDIR, FLAG_WFA_W32, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
+                   FLAG_READ_GROUPS, FLAG_REF_TEXTS, FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16, FLAG_WFA_BIDIR, FLAG_WFA_ESCALATE, FLAG_WFA_W32, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
                    Params, params_ref)
 
 
@@ -37,7 +37,7 @@ def features():
 
 def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=1, gap=4, backtrace=False,
                 reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None, gap2=None, linear=False,
-                w32=False, bidir=False, ref_texts=False, read_groups=False):
+                w32=False, bidir=False, ref_texts=False, read_groups=False, escalate=False):
     """`gap` is the launchers' single NW gap cost (run-nw-pim-wram.py: -DGAP_I = -DGAP_D); `gap_i` / `gap_d` set the two macros of
     nw.c:67-153 apart (NW/DPU-WRAM/common/common.h GAP_I, GAP_D). `ends_free=(PB, PE, TB, TE)`: ends-free WFA (AIM_FLAG_ENDSFREE);
     returns an EndsFreeParams then, which every call below accepts like Params. `gap2=(O2, E2)`: dual-cost gap-affine WFA
@@ -47,13 +47,22 @@ def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=
     `bidir=True`: bidirectional WFA (AIM_FLAG_WFA_BIDIR), CIGAR in O(MAX_SCORE) scratch; global gap-affine with backtrace only.
     `ref_texts=True`: texts named as windows of the device-resident reference (AIM_FLAG_REF_TEXTS); combines with everything.
     `read_groups=True`: batches of reads and their candidates, best candidate per read (AIM_FLAG_READ_GROUPS); combines with
-    everything."""
+    everything. `escalate=True`: WFA on a lane kernel at a low cap, the flag-less plan over the pairs that come back over it
+    (AIM_FLAG_WFA_ESCALATE); results equal the flag-less ones; global gap-affine WFA without w32, bidir and read_groups."""
     a = ALGO_BY_NAME[algo] if isinstance(algo, str) else algo
     gap_i = gap if gap_i is None else gap_i
     gap_d = gap if gap_d is None else gap_d
     flags = (FLAG_BACKTRACE if backtrace else 0) | (FLAG_REDUCE if reduce else 0) | (FLAG_SWG_W16 if swg_w16 else 0)
     flags |= (FLAG_REQ8 if req8 else 0) | (FLAG_RES8 if res8 else 0) | (FLAG_WFA_W32 if w32 else 0) | (FLAG_REF_TEXTS if ref_texts else 0)
     flags |= FLAG_READ_GROUPS if read_groups else 0
+    if escalate:
+        if a != ALGO_WFA:
+            raise ValueError("escalate needs wfa")
+        for name, given in (("ends_free", ends_free is not None), ("gap2", gap2 is not None), ("linear", linear), ("w32", w32), ("bidir", bidir),
+                            ("read_groups", read_groups)):
+            if given:
+                raise ValueError("escalate cannot be combined with %s" % name)
+        flags |= FLAG_WFA_ESCALATE
     if bidir:
         if not backtrace:
             raise ValueError("bidir needs backtrace")
@@ -94,6 +103,23 @@ def gen_pairs(seed, first_idx, n_pairs, length, error, read_size):
     capi.check(lib.aim_gen_pairs(seed, first_idx, n_pairs, length, float(error), read_size, capi.ptr(req),
                                  capi.ptr(pat), capi.ptr(txt)))
     return req, pat, txt
+
+
+def mixed_pairs(seed, n_pairs, length, e_clean, e_tail, tail_frac, read_size):
+    """Seeded batch of mostly clean pairs with a noisy tail: pair i carries gen_pairs' edits at error e_tail when a hash of (seed, i)
+    falls under tail_frac, at e_clean otherwise (both are gen_pairs(seed, 0, n_pairs, ...) rows, so a pair depends on (seed, i) only).
+    Returns (requests, patterns, texts, is_tail)."""
+    req, pat, txt = gen_pairs(seed, 0, n_pairs, length, e_clean, read_size)
+    i = np.arange(n_pairs, dtype=np.uint64)
+    h = (i + np.uint64(int(seed) & 0xFFFFFFFF) * np.uint64(0x9E3779B1)) * np.uint64(0x9E3779B97F4A7C15)   # (wraps mod 2^64)
+    h ^= h >> np.uint64(29)
+    h *= np.uint64(0xBF58476D1CE4E5B9)
+    h ^= h >> np.uint64(32)
+    tail = (h >> np.uint64(11)).astype(np.float64) * (1.0 / (1 << 53)) < float(tail_frac)
+    if tail.any():
+        req_t, pat_t, txt_t = gen_pairs(seed, 0, n_pairs, length, e_tail, read_size)
+        req[tail], pat[tail], txt[tail] = req_t[tail], pat_t[tail], txt_t[tail]
+    return req, pat, txt, tail
 
 
 def flank_pairs(seed, first_idx, req, pat, txt, flank):

@@ -27,6 +27,8 @@
  *                   < 32760; combines with the flags above; the output format is unchanged
  *     --bidir       (WFA, with --backtrace) bidirectional WFA: the CIGAR in O(max-score) memory (AIM_FLAG_WFA_BIDIR,
  *                   include/aim_hip.h); not with --reduce, --ends-free, --gap2 or --linear; the output format is unchanged
+ *     --escalate    (WFA) a lane kernel at a low score cap over every batch, --max-score only for the pairs that come back over it
+ *                   (AIM_FLAG_WFA_ESCALATE, include/aim_hip.h); not with --ends-free, --gap2, --linear, --w32 or --bidir; same output
  *     --packed-input  <input> is a packed batch file (written by --pack-only or `python -m aim_amd.gen_dataset --packed`):
  *                   2 bits per base + raw side list, ready for the device; no text is parsed
  * The UPMEM dispatch (dpu_alloc/dpu_load/dpu_push_xfer/dpu_launch) is replaced
@@ -942,6 +944,7 @@ int main(int argc, char *argv[])
         else if (!strcmp(f, "--linear")) p.flags |= AIM_FLAG_LINEAR;
         else if (!strcmp(f, "--w32")) p.flags |= AIM_FLAG_WFA_W32;
         else if (!strcmp(f, "--bidir")) p.flags |= AIM_FLAG_WFA_BIDIR;
+        else if (!strcmp(f, "--escalate")) p.flags |= AIM_FLAG_WFA_ESCALATE;
         else if (!strcmp(f, "--swg-w16")) p.flags |= AIM_FLAG_SWG_W16;
         else if (!strcmp(f, "--no-pack")) no_pack = 1;       /* ship ASCII rows like the reference (host.c:258-268) */
         else if (!strcmp(f, "--full-ops")) full_ops = 1;     /* gather result_t + ops rows like the reference (host.c:316-326) */
@@ -1038,6 +1041,14 @@ int main(int argc, char *argv[])
         if (p.flags & AIM_FLAG_ENDSFREE) { fprintf(stderr, "--bidir cannot be combined with --ends-free\n"); exit(1); }
         if (p.flags & AIM_FLAG_AFFINE2P) { fprintf(stderr, "--bidir cannot be combined with --gap2\n"); exit(1); }
         if (p.flags & AIM_FLAG_LINEAR) { fprintf(stderr, "--bidir cannot be combined with --linear\n"); exit(1); }
+    }
+    if (p.flags & AIM_FLAG_WFA_ESCALATE) {
+        if (p.algo != AIM_ALGO_WFA) { fprintf(stderr, "--escalate needs --algo wfa\n"); exit(1); }
+        if (p.flags & AIM_FLAG_ENDSFREE) { fprintf(stderr, "--escalate cannot be combined with --ends-free\n"); exit(1); }
+        if (p.flags & AIM_FLAG_AFFINE2P) { fprintf(stderr, "--escalate cannot be combined with --gap2\n"); exit(1); }
+        if (p.flags & AIM_FLAG_LINEAR) { fprintf(stderr, "--escalate cannot be combined with --linear\n"); exit(1); }
+        if (p.flags & AIM_FLAG_WFA_W32) { fprintf(stderr, "--escalate cannot be combined with --w32\n"); exit(1); }
+        if (p.flags & AIM_FLAG_WFA_BIDIR) { fprintf(stderr, "--escalate cannot be combined with --bidir\n"); exit(1); }
     }
     if (packed_input && (no_pack || pack_only)) { fprintf(stderr, "--packed-input cannot be combined with --no-pack / --pack-only\n"); exit(1); }
 #if defined(__x86_64__)

@@ -39,6 +39,7 @@ def _parser(algo):
         ap.add_argument("-r", "--reduced", action="store_true", help="Enable WFA-Adaptive")
         ap.add_argument("--w32", action="store_true", help="WFA only: 32-bit wavefront offsets (AFFINE_WAVEFRONT_W32), for read sizes of 32 760 and more")
         ap.add_argument("--bidir", action="store_true", help="WFA with -b only: bidirectional WFA, the CIGAR in O(max score) memory")
+        ap.add_argument("--escalate", action="store_true", help="WFA only: a lane kernel at a low score cap first, the full cap for the pairs over it; same results")
     if algo == "genasm":
         ap.add_argument("-r", "--reduced", action="store_true", help="accepted and ignored")
     ap.add_argument("-t", "--nr_of_tasklets", type=int, help="accepted for compatibility; tasklets do not exist on MI355X")
@@ -77,7 +78,7 @@ def parse(algo, argv):
                 gap_o=g, gap_e=a, max_score=int(max_score), read_size=int(read_size), backtrace=args["backtrace"],
                 reduce=bool(args.get("reduced")), nr_dpus=args["nr_of_dpus"] or 1, gpus=args["gpus"],
                 swg_w16=args["mram"], dry_run=args["dry_run"], slots=args.get("slots") or 0, w32=bool(args.get("w32")),
-                bidir=bool(args.get("bidir")))
+                bidir=bool(args.get("bidir")), escalate=bool(args.get("escalate")))
 
 
 def flag_line(cfg):
@@ -113,6 +114,8 @@ def host_command(cfg):
         cmd.append("--w32")
     if cfg.get("bidir") and cfg["algo"] == "wfa":
         cmd.append("--bidir")
+    if cfg.get("escalate") and cfg["algo"] == "wfa":
+        cmd.append("--escalate")
     # batches in flight per device (host --slots). GenASM defaults to four: a pair that loses the diagonal keeps one wavefront busy long after its batch is
     # done and the next batches run under that tail (16 384 pairs of 100 kb through the CLI: 1 / 2 / 4 slots = 1.3 / 2.1 / 4.3e5 pairs/s).
     # Every slot carries its own pinned host AND device buffers (both sequence arrays + results / CIGAR): four slots are four times the pinned memory

@@ -159,6 +159,20 @@ typedef struct aim_affine2p_params {
  * whose raw_pairs list READ indices and raw_patterns their rows; packed explicit texts are refused) and aim_align_device_groups (ASCII); aim_set_push, aim_set_push_ref, aim_set_launch, aim_set_pull, aim_align_device and aim_align_device_ref
  * refuse the flag. Check aim_features() & AIM_FEATURE_READ_GROUPS first: older libraries ignore unknown flags. */
 #define AIM_FLAG_READ_GROUPS 0x800u
+/* AIM_FLAG_WFA_ESCALATE (global gap-affine WFA): a generous MAX_SCORE without losing the one-pair-per-lane kernels. The batch runs at
+ * a low cap c on a lane kernel -- c is the largest cap below MAX_SCORE whose flag-less plan is wfa_lane_kernel or wfa_lane_packed_kernel
+ * (5 or 10 today, by penalties, BACKTRACE, READ_SIZE and packed input) -- and only the pairs that come back over c are run again under
+ * the flag-less plan at MAX_SCORE, from a device-side list, on the same stream. EVERY per-pair output is exactly that of the same
+ * call without the flag: the result row, status and ops[begin_offset, end_offset); the {idx, score} row; the compact header's idx, score,
+ * n_runs and status and the pair's runs (run_offset may differ, the batch's run total does not). Results do not depend on the grid, the
+ * slots, the batch size or the AIM_DEBUG_POISON_* knobs. The plan line ends in " escalate=c": with c > 0 it is
+ * "<stage 1 line> | <stage 2 line> escalate=c"; where no lane kernel takes the shape, or the flag-less plan is a lane plan already, it
+ * is the flag-less line and " escalate=0". Combines with AIM_FLAG_REDUCE, AIM_FLAG_BACKTRACE, AIM_FLAG_REQ8, AIM_FLAG_RES8, packed
+ * input, compact runs and AIM_FLAG_REF_TEXTS on every entry point that takes them (aim_kernel_name names the first stage). Rejected
+ * (AIM_EINVAL) with NW / SWG / GenASM, with AIM_FLAG_ENDSFREE, AIM_FLAG_AFFINE2P, AIM_FLAG_LINEAR, AIM_FLAG_WFA_W32 or
+ * AIM_FLAG_WFA_BIDIR (no lane kernel takes them) and with AIM_FLAG_READ_GROUPS (a follow-up).
+ * Check aim_features() & AIM_FEATURE_WFA_ESCALATE first: older libraries ignore unknown flags. */
+#define AIM_FLAG_WFA_ESCALATE 0x1000u
 
 /* Per-pair descriptor: byte-compatible with the NW/SWG request_t
  * (NW/DPU-WRAM/common/common.h:114-120).  The WFA variant of the reference
@@ -210,6 +224,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_WFA_BIDIR 0x10u /* AIM_FLAG_WFA_BIDIR is honoured */
 #define AIM_FEATURE_REF_TEXTS 0x20u /* AIM_FLAG_REF_TEXTS is honoured */
 #define AIM_FEATURE_READ_GROUPS 0x40u /* AIM_FLAG_READ_GROUPS is honoured */
+#define AIM_FEATURE_WFA_ESCALATE 0x80u /* AIM_FLAG_WFA_ESCALATE is honoured */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
