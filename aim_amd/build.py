@@ -2,6 +2,7 @@
 
   aim_amd/libaim_hip.so   C-ABI + kernels      (hipcc --offload-arch=gfx950)
   aim_amd/host/host       the C host program   (gcc, links libaim_hip.so)
+  build/tests/lib*.so     test-only launchers  (hipcc, one per tests/csrc/*.hip; they include kernel headers, not the library)
 
 `python -m aim_amd.build` builds both; nothing is JIT-compiled at import time.
 
@@ -103,9 +104,31 @@ def build_host(force=False):
     return HOST_BIN
 
 
+def test_helper(name):
+    """Where build_test_helpers puts the launcher compiled from tests/csrc/<name>.hip."""
+    return os.path.join(ROOT, "build", "tests", "lib%s.so" % name)
+
+
+def build_test_helpers(force=False):
+    srcdir = os.path.join(ROOT, "tests", "csrc")
+    if not os.path.isdir(srcdir):
+        return []
+    out = []
+    for f in sorted(os.listdir(srcdir)):
+        if not f.endswith(".hip"):
+            continue
+        src, lib = os.path.join(srcdir, f), test_helper(f[:-4])
+        os.makedirs(os.path.dirname(lib), exist_ok=True)
+        if force or _newer(lib, _deps(src)):
+            _run([HIPCC] + HIP_FLAGS + ["-shared", "-o", lib, src])
+        out.append(lib)
+    return out
+
+
 def build_all(force=False):
     build_lib(force)
     build_host(force)
+    build_test_helpers(force)
 
 
 if __name__ == "__main__":

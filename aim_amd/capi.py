@@ -32,6 +32,9 @@ FLAG_READ_GROUPS = 0x800     # reads and their candidates: score-only pass, best
 FEATURE_READ_GROUPS = 0x40   # aim_features(): AIM_FLAG_READ_GROUPS is honoured
 FLAG_WFA_ESCALATE = 0x1000   # WFA: a lane kernel at a low cap over the batch, the flag-less plan over the pairs it left over that cap
 FEATURE_WFA_ESCALATE = 0x80  # aim_features(): AIM_FLAG_WFA_ESCALATE is honoured
+FLAG_MATE_PAIRS = 0x2000     # paired-end selection over a read-groups batch of reference windows: reads 2m and 2m + 1 are mates
+FEATURE_MATE_PAIRS = 0x100   # aim_features(): AIM_FLAG_MATE_PAIRS is honoured
+MATE_PROPER = 1              # aim_mate_t.flags: the chosen candidates are a proper combination
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
 
 
@@ -95,6 +98,9 @@ assert CIGAR_DTYPE.itemsize == 16
 CIGAR_OVERFLOW = 0x100
 BEST_DTYPE = np.dtype([("best_pair", "<u4"), ("best_score", "<i4"), ("second_score", "<i4"), ("n_best", "<u4")])   # aim_best_t
 assert BEST_DTYPE.itemsize == 16
+MATE_DTYPE = np.dtype([("best_pair", "<u4", (2,)), ("score_sum", "<i4"), ("second_sum", "<i4"), ("n_best", "<u4"), ("flags", "<u4"),
+                       ("pad", "<u4", (2,))])   # aim_mate_t
+assert MATE_DTYPE.itemsize == 32
 
 
 class BatchIO(C.Structure):
@@ -114,6 +120,13 @@ class BatchIOGroups(C.Structure):
     """aim_batch_io_groups_t: laid out like BatchIORef, then the reads (AIM_FLAG_READ_GROUPS); aim_set_submit receives a pointer to
     `base`."""
     _fields_ = [("base", BatchIO), ("text_pos", C.c_void_p), ("n_reads", C.c_uint32), ("read_offsets", C.c_void_p), ("best", C.c_void_p)]
+
+
+class BatchIOMates(C.Structure):
+    """aim_batch_io_mates_t: BatchIOGroups, then the pairing parameters and the read pairs' rows (AIM_FLAG_MATE_PAIRS); aim_set_submit
+    receives a pointer to `groups.base`."""
+    _fields_ = [("groups", BatchIOGroups), ("min_span", C.c_int64), ("max_span", C.c_int64), ("unpaired_penalty", C.c_int32),
+                ("pad", C.c_uint32), ("mates", C.c_void_p)]
 
 
 # every symbol include/aim_hip.h declares: name -> (restype, argtypes)
@@ -155,6 +168,9 @@ SYMBOLS = {
     "aim_groups_check": (C.c_int, [_U32, _U32, _VP, C.POINTER(_U32)]),
     "aim_align_device_groups": (C.c_int, [C.POINTER(Params), _U32, _U32, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP,
                                           C.c_size_t, _VP]),
+    "aim_mates_check": (C.c_int, [_U32, C.c_int64, C.c_int64, _I32]),
+    "aim_align_device_mates": (C.c_int, [C.POINTER(Params), _U32, _U32, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, C.c_int64,
+                                         C.c_int64, _I32, _VP, _VP, C.c_size_t, _VP]),
 }
 
 _lib = None
@@ -166,8 +182,9 @@ class AimError(RuntimeError):
         self.code = code
 
 
-def load():
-    """Load libaim_hip.so (built by aim_amd.build).  Fails loudly when it is missing."""
+def load(strict=True):
+    """Load libaim_hip.so (built by aim_amd.build).  Fails loudly when it is missing. strict=False accepts a library built before
+    a declared symbol existed (AIM_LIB=<an older build of this ABI>, for A/B measurements): that symbol is simply absent from it."""
     global _lib
     if _lib is not None:
         return _lib
@@ -176,6 +193,8 @@ def load():
                            "There is no CPU fallback for the alignment path." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SYMBOLS.items():
+        if not strict and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)   # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

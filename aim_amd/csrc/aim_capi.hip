@@ -33,6 +33,7 @@
 #include "dp_group.hpp"
 #include "batch_io.hpp"
 #include "groups.hpp"
+#include "mates.hpp"
 #include "genasm_wave.hpp"
 
 namespace {
@@ -253,6 +254,8 @@ inline size_t ref_rows_at(size_t plan_scratch) { return (plan_scratch + 255) & ~
 inline size_t ref_rows_bytes(const aim_params_t &p, uint32_t n_pairs) { return (size_t)n_pairs * (size_t)p.read_size + 256; }
 // AIM_FLAG_READ_GROUPS: reads and their candidates (groups.hpp); the plans of its two passes never see the flag.
 inline bool is_groups(const aim_params_t &p) { return (p.flags & AIM_FLAG_READ_GROUPS) != 0; }
+// AIM_FLAG_MATE_PAIRS: paired-end selection over a groups batch (mates.hpp); one more kernel after the independent selection.
+inline bool is_mates(const aim_params_t &p) { return (p.flags & AIM_FLAG_MATE_PAIRS) != 0; }
 // AIM_FLAG_WFA_ESCALATE: a lane kernel at a low cap over the batch, the flag-less plan over the pairs it left over that cap (plan_wfa).
 inline bool is_escalate(const aim_params_t &p) { return (p.flags & AIM_FLAG_WFA_ESCALATE) != 0; }
 // The params as this library keeps them: room for either extension, and the extension copied only when a flag says it exists.
@@ -278,6 +281,10 @@ int validate_params(const aim_params_t &p)
     // before either extension is read: the caller's struct holds at most one of them (an aim_affine2p_params_t is shorter than
     // an aim_endsfree_params_t)
     if (is_endsfree(p) && is_affine2p(p)) return fail(AIM_EINVAL, "AIM_FLAG_AFFINE2P cannot be combined with AIM_FLAG_ENDSFREE");
+    if (is_mates(p)) {   // the positions it pairs by are the windows' text_pos
+        if (!is_groups(p)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS needs AIM_FLAG_READ_GROUPS");
+        if (!is_ref(p)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS needs AIM_FLAG_REF_TEXTS");
+    }
     if (is_escalate(p)) {
         if (p.algo != AIM_ALGO_WFA) return fail(AIM_EINVAL, "AIM_FLAG_WFA_ESCALATE needs AIM_ALGO_WFA");
         if (is_endsfree(p)) return fail(AIM_EINVAL, "AIM_FLAG_WFA_ESCALATE cannot be combined with AIM_FLAG_ENDSFREE");
@@ -1130,14 +1137,16 @@ struct GroupsPlan {
     XParams x1, x2;         // the two passes' params
     Plan p1, p2;            // p2 planned iff pass2
     bool pass2;
+    bool mates;             // AIM_FLAG_MATE_PAIRS: mate_select_kernel after the independent selection
     size_t plan_bytes;      // the larger of the two plans' scratch (both made for n_pairs)
     // aim_align_device_groups: the rest of its scratch, offsets from the base (256-B aligned)
     size_t cand_p_at, cand_t_at, res1_at, map_at, sel_at, req2_at, pat2_at, txt2_at, total;
+    size_t best_at;         // aim_align_device_mates: the independent selection's rows when the caller keeps none (the last region)
 };
 inline XParams groups_pass_params(const aim_params_t &p, uint32_t drop)
 {
     XParams x = copy_params(p);
-    x.base.flags &= ~(AIM_FLAG_READ_GROUPS | drop);
+    x.base.flags &= ~(AIM_FLAG_READ_GROUPS | AIM_FLAG_MATE_PAIRS | drop);
     return x;
 }
 
@@ -1147,12 +1156,12 @@ int describe_groups(const GroupsPlan &g, uint32_t n_pairs, uint32_t n_reads, uin
     describe_plan(g.p1, g.x1.base, n_pairs, budget, a, sizeof a);
     if (g.pass2) describe_plan(g.p2, g.x2.base, n_reads, budget, b, sizeof b);
     else snprintf(b, sizeof b, "no second pass n=%u", n_reads);
-    return snprintf(out, cap, "%s | %s groups=1", a, b);
+    return snprintf(out, cap, "%s | %s groups=1%s", a, b, g.mates ? " mates=1" : "");
 }
 
 // Both passes planned for n_pairs candidates (the worst case n_reads = n_pairs for pass 2) and the stateless scratch layout:
 // [plans | candidate pattern rows | candidate text rows (REF_TEXTS) | pass-1 results | candidate -> read map | sel | pass-2 requests,
-//  pattern rows, text rows (BACKTRACE)]
+//  pattern rows, text rows (BACKTRACE) | aim_best_t rows (MATE_PAIRS)]
 int make_groups_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, GroupsPlan *g)
 {
     int rc = validate_params(p);
@@ -1163,6 +1172,7 @@ int make_groups_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &
     g->x1 = groups_pass_params(p, AIM_FLAG_BACKTRACE | AIM_FLAG_WFA_BIDIR | AIM_FLAG_RES8);
     g->x2 = groups_pass_params(p, 0u);
     g->pass2 = (p.flags & AIM_FLAG_BACKTRACE) != 0;
+    g->mates = is_mates(p);
     rc = make_plan(g->x1.base, n_pairs, quiet, budget, &g->p1);
     if (rc) return rc;
     g->plan_bytes = g->p1.scratch_total;
@@ -1183,6 +1193,7 @@ int make_groups_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &
         g->pat2_at = at; at += al256(rows);
         g->txt2_at = at; at += al256(rows);
     }
+    if (g->mates) { g->best_at = at; at += al256((size_t)n_pairs * sizeof(aim_best_t)); }
     g->total = at;
     if (kn.plan_debug) {
         char line[800];
@@ -1206,7 +1217,10 @@ struct GroupsIo {
     char *cand_p, *cand_t;       // [n_pairs][READ_SIZE]; cand_t: the candidates' text rows (given, or gathered under REF_TEXTS)
     aim_result_t *res1;          // [n_pairs]
     uint32_t *map, *sel;         // [n_pairs], [n_reads]
-    aim_best_t *best;            // [n_reads] or nullptr
+    aim_best_t *best;            // [n_reads] or nullptr (never nullptr under AIM_FLAG_MATE_PAIRS)
+    const uint64_t *tpos;        // AIM_FLAG_MATE_PAIRS: the candidates' text_pos [n_pairs] ...
+    aim::MateArgs mate;          // ... the pairing parameters (n_mates and lanes are filled in by enqueue_groups) ...
+    aim_mate_t *mates;           // ... and the read pairs' rows [n_reads / 2], or nullptr
     void *req2;                  // [n_reads] pass-2 requests
     char *pat2, *txt2;           // [n_reads][READ_SIZE]
     void *res;                   // out [n_reads]
@@ -1262,6 +1276,18 @@ int enqueue_groups(const GroupsPlan &g, const Plan &pl1, const Plan &pl2, const 
     const uint32_t waves = (nr + aim::kGroupReadsPerWave - 1) / aim::kGroupReadsPerWave;
     hipLaunchKernelGGL(aim::group_select_kernel, dim3((waves + 3) / 4), dim3(256), 0, stream, io.res1, n, io.roff, nr, io.best, io.sel);
     HIP_TRY(hipGetLastError());
+    if (g.mates && nr >= 2) {
+        // lanes per read pair: the power of two that covers an average read pair's combinations (any value gives the same rows)
+        aim::MateArgs ma = io.mate;
+        ma.n_mates = nr / 2;
+        const uint64_t k = ((uint64_t)n + nr - 1) / nr, combos = k * k;
+        ma.lanes = 1;
+        while (ma.lanes < (uint32_t)aim::kWave && ma.lanes < combos) ma.lanes <<= 1;
+        const uint64_t threads = (uint64_t)ma.n_mates * ma.lanes;
+        hipLaunchKernelGGL(aim::mate_select_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, ka, ma, io.res1, io.tpos,
+                           io.roff, io.best, io.sel, io.mates);
+        HIP_TRY(hipGetLastError());
+    }
     if (!g.pass2) {
         hipLaunchKernelGGL(aim::group_results_kernel, dim3((nr + 255) / 256), dim3(256), 0, stream, io.res1, io.sel, nr,
                            (int)((p2.flags & AIM_FLAG_RES8) != 0), io.res);
@@ -1313,6 +1339,7 @@ struct aim_slot {
     uint32_t *g_roff = nullptr, *g_map = nullptr, *g_sel = nullptr, *g_rawslot = nullptr;
     aim_result_t *g_res1 = nullptr;
     aim_best_t *g_best = nullptr;
+    aim_mate_t *g_mates = nullptr;   // AIM_FLAG_MATE_PAIRS: [max_pairs / 2]
     void *g_req2 = nullptr;
     char *g_pat2 = nullptr, *g_txt2 = nullptr;
     uint32_t n_reads = 0;            // reads of the groups batch in flight (n_pairs then counts its output rows)
@@ -1354,7 +1381,7 @@ void free_slot(aim_slot &s)
 {
     void *bufs[] = {s.d_req, s.d_pat, s.d_txt, s.d_ops, s.d_res, s.d_scratch, s.d_packP, s.d_packT, s.d_rawidx, s.d_rawP, s.d_rawT,
                     s.d_cig, s.d_runs, s.d_cursor, s.d_rawreq, s.d_rawres, s.d_rawops, s.d_rawcig, s.d_tpos, s.d_reftodo,
-                    s.g_readP, s.g_roff, s.g_map, s.g_sel, s.g_rawslot, s.g_res1, s.g_best, s.g_req2, s.g_pat2, s.g_txt2};
+                    s.g_readP, s.g_roff, s.g_map, s.g_sel, s.g_rawslot, s.g_res1, s.g_best, s.g_mates, s.g_req2, s.g_pat2, s.g_txt2};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (s.h_cursor) (void)hipHostFree(s.h_cursor);
@@ -1503,7 +1530,7 @@ int aim_abi_version(void) { return AIM_ABI_VERSION; }
 uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
-           AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE;
+           AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -1600,6 +1627,7 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
             if (max_raw) HIP_TRY(hipMalloc((void **)&s.g_rawslot, (size_t)max_pairs * 4));
             HIP_TRY(hipMalloc((void **)&s.g_res1, (size_t)max_pairs * sizeof(aim_result_t)));
             HIP_TRY(hipMalloc((void **)&s.g_best, (size_t)max_pairs * sizeof(aim_best_t)));
+            if (is_mates(*params)) HIP_TRY(hipMalloc((void **)&s.g_mates, ((size_t)max_pairs / 2 + 1) * sizeof(aim_mate_t)));
             if (params->flags & AIM_FLAG_BACKTRACE) {
                 HIP_TRY(hipMalloc(&s.g_req2, (size_t)max_pairs * req_size(*params)));
                 HIP_TRY(hipMalloc((void **)&s.g_pat2, (size_t)max_pairs * rs + 64));
@@ -1862,6 +1890,17 @@ Plan pass_plan(const aim_set *set, const aim_device_ctx &d, const aim_slot &s, c
     return pl;
 }
 
+// aim_mates_check: the read pairs and the pairing parameters of a mate-pairs batch
+int check_mates(uint32_t n_reads, int64_t min_span, int64_t max_span, int32_t unpaired_penalty)
+{
+    if (n_reads & 1u) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS: n_reads %u is odd (reads 2m and 2m + 1 are mates)", n_reads);
+    if (min_span < 0 || max_span < min_span || max_span >= ((int64_t)1 << 62))
+        return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS: bad span [%lld, %lld]: need 0 <= min_span <= max_span < 2^62", (long long)min_span,
+                    (long long)max_span);
+    if (unpaired_penalty < 0) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS: unpaired_penalty %d is negative", unpaired_penalty);
+    return AIM_OK;
+}
+
 // aim_set_submit under AIM_FLAG_READ_GROUPS
 int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_io_t *io)
 {
@@ -1871,6 +1910,8 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
     const bool bt = p.flags & AIM_FLAG_BACKTRACE;
     const bool ref = is_ref(p);
     const bool packed = io->packed_patterns || io->packed_texts;
+    // AIM_FLAG_MATE_PAIRS: io is the base of an aim_batch_io_mates_t
+    const aim_batch_io_mates_t *mio = is_mates(p) ? reinterpret_cast<const aim_batch_io_mates_t *>(io) : nullptr;
     if (packed && (!ref || io->packed_texts))
         return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS: packed batches need AIM_FLAG_REF_TEXTS (packed explicit texts are a follow-up)");
     if (packed && (!s.d_packP || !s.g_rawslot)) return fail(AIM_EINVAL, "packed batch needs a set configured with max_raw_pairs > 0");
@@ -1884,10 +1925,14 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
     if (n > set->max_pairs) return fail(AIM_EINVAL, "n_pairs %u exceeds configured capacity %u", n, set->max_pairs);
     if (n && (!io->requests || (!packed && !io->patterns) || (!ref && !io->texts))) return fail(AIM_EINVAL, "null requests or sequence rows");
     if (io->cigars && (!bt || !s.d_cig || !io->runs)) return fail(AIM_EINVAL, "compact CIGAR needs AIM_FLAG_BACKTRACE, max_runs > 0 and a run buffer");
-    if (n && !io->results && !io->cigars && !gio->best) return fail(AIM_EINVAL, "no output buffer");
+    if (n && !io->results && !io->cigars && !gio->best && !(mio && mio->mates)) return fail(AIM_EINVAL, "no output buffer");
     if (io->ops && !bt) return fail(AIM_EINVAL, "ops requested without AIM_FLAG_BACKTRACE");
     int rc = check_groups(n, nr, gio->read_offsets, nullptr);
     if (rc) return rc;
+    if (mio) {
+        rc = check_mates(nr, mio->min_span, mio->max_span, mio->unpaired_penalty);
+        if (rc) return rc;
+    }
     if (packed)   // the side list names reads
         for (uint32_t j = 0; j < io->n_raw; ++j)
             if (io->raw_pairs[j] >= nr) return fail(AIM_EINVAL, "raw_pairs[%u] = %u is outside the batch's %u reads", j, io->raw_pairs[j], nr);
@@ -1910,6 +1955,7 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
     g.x1 = groups_pass_params(p, AIM_FLAG_BACKTRACE | AIM_FLAG_WFA_BIDIR | AIM_FLAG_RES8);
     g.x2 = groups_pass_params(p, 0u);
     g.pass2 = bt;
+    g.mates = mio != nullptr;
     auto enqueue = [&]() -> int {
         HIP_TRY(hipEventRecord(s.ev[0], s.stream));
         if (n) {
@@ -1960,6 +2006,14 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
             gi.map = s.g_map;
             gi.sel = s.g_sel;
             gi.best = s.g_best;
+            gi.tpos = s.d_tpos;
+            memset(&gi.mate, 0, sizeof gi.mate);
+            if (mio) {
+                gi.mate.min_span = mio->min_span;
+                gi.mate.max_span = mio->max_span;
+                gi.mate.unpaired_penalty = mio->unpaired_penalty;
+            }
+            gi.mates = s.g_mates;
             gi.req2 = s.g_req2;
             gi.pat2 = s.g_pat2;
             gi.txt2 = s.g_txt2;
@@ -1987,6 +2041,8 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
         HIP_TRY(hipEventRecord(s.ev[4], s.stream));
         if (n) {
             if (gio->best) HIP_TRY(hipMemcpyAsync(gio->best, s.g_best, (size_t)nr * sizeof(aim_best_t), hipMemcpyDeviceToHost, s.stream));
+            if (mio && mio->mates && nr >= 2)
+                HIP_TRY(hipMemcpyAsync(mio->mates, s.g_mates, (size_t)(nr / 2) * sizeof(aim_mate_t), hipMemcpyDeviceToHost, s.stream));
             if (io->cigars) {
                 HIP_TRY(hipMemcpyAsync(s.h_cursor, s.d_cursor, 4, hipMemcpyDeviceToHost, s.stream));
                 HIP_TRY(hipMemcpyAsync(io->cigars, s.d_cig, (size_t)nr * sizeof(aim_cigar_t), hipMemcpyDeviceToHost, s.stream));
@@ -2317,6 +2373,7 @@ int aim_set_plan_describe(const aim_set_t *set, uint32_t device, char *out, size
         g.x1 = groups_pass_params(set->params, AIM_FLAG_BACKTRACE | AIM_FLAG_WFA_BIDIR | AIM_FLAG_RES8);
         g.x2 = groups_pass_params(set->params, 0u);
         g.pass2 = (set->params.flags & AIM_FLAG_BACKTRACE) != 0;
+        g.mates = is_mates(set->params);
         g.p1 = s.plan_last;
         g.p2 = s.plan_last2;
         const bool any = s.n_reads != 0;
@@ -2415,6 +2472,7 @@ int aim_align_device_ref(const aim_params_t *params, uint32_t n_pairs, const voi
     if (!params) return fail(AIM_EINVAL, "params is NULL");
     if (!is_ref(*params)) return fail(AIM_EINVAL, "aim_align_device_ref needs AIM_FLAG_REF_TEXTS");
     if (is_groups(*params)) return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS is set: use aim_align_device_groups");
+    if (is_mates(*params)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS is set: use aim_align_device_mates");
     if (n_pairs && (!d_text_pos || !d_reference || !d_requests)) return fail(AIM_EINVAL, "null device buffer");
     int n = 0;
     int rc = aim_device_count(&n);
@@ -2461,6 +2519,7 @@ int aim_align_device(const aim_params_t *params, uint32_t n_pairs, const void *d
 {
     if (!params) return fail(AIM_EINVAL, "params is NULL");
     if (is_groups(*params)) return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS is set: use aim_align_device_groups");
+    if (is_mates(*params)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS is set: use aim_align_device_mates");
     int n = 0;
     int rc = aim_device_count(&n);
     if (rc) return rc;
@@ -2511,13 +2570,18 @@ int aim_groups_check(uint32_t n_pairs, uint32_t n_reads, const uint32_t *read_of
     return check_groups(n_pairs, n_reads, read_offsets, bad_read);
 }
 
-int aim_align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
-                            const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
-                            const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, void *d_scratch,
-                            size_t scratch_bytes, void *hip_stream)
+int aim_mates_check(uint32_t n_reads, int64_t min_span, int64_t max_span, int32_t unpaired_penalty)
 {
-    if (!params) return fail(AIM_EINVAL, "params is NULL");
-    if (!is_groups(*params)) return fail(AIM_EINVAL, "aim_align_device_groups needs AIM_FLAG_READ_GROUPS");
+    return check_mates(n_reads, min_span, max_span, unpaired_penalty);
+}
+
+namespace {
+// aim_align_device_groups (mate == nullptr) and aim_align_device_mates
+int align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
+                        const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
+                        const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, const aim::MateArgs *mate,
+                        aim_mate_t *d_mates, void *d_scratch, size_t scratch_bytes, void *hip_stream)
+{
     const bool ref = is_ref(*params), bt = params->flags & AIM_FLAG_BACKTRACE;
     if (n_reads > n_pairs || (n_pairs && !n_reads)) return fail(AIM_EINVAL, "n_reads %u does not fit n_pairs %u", n_reads, n_pairs);
     if (n_pairs && (!d_requests || !d_patterns || !d_read_offsets || !d_results || (bt && !d_ops) ||
@@ -2551,7 +2615,11 @@ int aim_align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32
     gi.res1 = reinterpret_cast<aim_result_t *>(base + g.res1_at);
     gi.map = reinterpret_cast<uint32_t *>(base + g.map_at);
     gi.sel = reinterpret_cast<uint32_t *>(base + g.sel_at);
-    gi.best = d_best;
+    gi.best = d_best ? d_best : (mate ? reinterpret_cast<aim_best_t *>(base + g.best_at) : nullptr);
+    gi.tpos = d_text_pos_or_null;
+    memset(&gi.mate, 0, sizeof gi.mate);
+    if (mate) gi.mate = *mate;
+    gi.mates = d_mates;
     gi.req2 = bt ? base + g.req2_at : nullptr;
     gi.pat2 = bt ? base + g.pat2_at : nullptr;
     gi.txt2 = bt ? base + g.txt2_at : nullptr;
@@ -2577,6 +2645,41 @@ int aim_align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32
         if (!make_plan(g.x2.base, n_reads, quiet, budget, &q) && q.scratch_total <= g.plan_bytes) pl2 = q;
     }
     return enqueue_groups(g, g.p1, pl2, kn, gi, stream, nullptr);
+}
+}  // namespace
+
+int aim_align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
+                            const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
+                            const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, void *d_scratch,
+                            size_t scratch_bytes, void *hip_stream)
+{
+    if (!params) return fail(AIM_EINVAL, "params is NULL");
+    if (!is_groups(*params)) return fail(AIM_EINVAL, "aim_align_device_groups needs AIM_FLAG_READ_GROUPS");
+    if (is_mates(*params)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS is set: use aim_align_device_mates");
+    return align_device_groups(params, n_pairs, n_reads, d_requests, d_patterns, d_texts_or_null, d_text_pos_or_null, d_reference, ref_len,
+                               d_read_offsets, d_results, d_ops, d_best, nullptr, nullptr, d_scratch, scratch_bytes, hip_stream);
+}
+
+int aim_align_device_mates(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
+                           const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
+                           const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, int64_t min_span,
+                           int64_t max_span, int32_t unpaired_penalty, aim_mate_t *d_mates, void *d_scratch, size_t scratch_bytes,
+                           void *hip_stream)
+{
+    if (!params) return fail(AIM_EINVAL, "params is NULL");
+    if (!is_mates(*params)) return fail(AIM_EINVAL, "aim_align_device_mates needs AIM_FLAG_MATE_PAIRS");
+    int rc = validate_params(*params);   // (names a missing AIM_FLAG_READ_GROUPS / AIM_FLAG_REF_TEXTS)
+    if (rc) return rc;
+    if (d_texts_or_null) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS: d_texts must be NULL (the texts are named by d_text_pos)");
+    rc = check_mates(n_reads, min_span, max_span, unpaired_penalty);
+    if (rc) return rc;
+    aim::MateArgs ma;
+    memset(&ma, 0, sizeof ma);
+    ma.min_span = min_span;
+    ma.max_span = max_span;
+    ma.unpaired_penalty = unpaired_penalty;
+    return align_device_groups(params, n_pairs, n_reads, d_requests, d_patterns, nullptr, d_text_pos_or_null, d_reference, ref_len,
+                               d_read_offsets, d_results, d_ops, d_best, &ma, d_mates, d_scratch, scratch_bytes, hip_stream);
 }
 
 // ---------------------------------------------------------------------------

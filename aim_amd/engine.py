@@ -13,7 +13,7 @@ import numpy as np
 
 from . import capi
 from .capi import (ALGO_BY_NAME, ALGO_NW, ALGO_SWG, ALGO_WFA, FLAG_AFFINE2P, FLAG_BACKTRACE, FLAG_ENDSFREE, FLAG_LINEAR, FLAG_REDUCE,
-                   FLAG_READ_GROUPS, FLAG_REF_TEXTS, FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16, FLAG_WFA_BIDIR, FLAG_WFA_ESCALATE, FLAG_WFA_W32, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
+                   FLAG_MATE_PAIRS, FLAG_READ_GROUPS, FLAG_REF_TEXTS, FLAG_REQ8, FLAG_RES8, FLAG_SWG_W16, FLAG_WFA_BIDIR, FLAG_WFA_ESCALATE, FLAG_WFA_W32, REQUEST8_DTYPE, REQUEST_DTYPE, RESULT8_DTYPE, RESULT_DTYPE, Affine2pParams, EndsFreeParams,
                    Params, params_ref)
 
 
@@ -37,7 +37,7 @@ def features():
 
 def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=1, gap=4, backtrace=False,
                 reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None, gap2=None, linear=False,
-                w32=False, bidir=False, ref_texts=False, read_groups=False, escalate=False):
+                w32=False, bidir=False, ref_texts=False, read_groups=False, escalate=False, mate_pairs=False):
     """`gap` is the launchers' single NW gap cost (run-nw-pim-wram.py: -DGAP_I = -DGAP_D); `gap_i` / `gap_d` set the two macros of
     nw.c:67-153 apart (NW/DPU-WRAM/common/common.h GAP_I, GAP_D). `ends_free=(PB, PE, TB, TE)`: ends-free WFA (AIM_FLAG_ENDSFREE);
     returns an EndsFreeParams then, which every call below accepts like Params. `gap2=(O2, E2)`: dual-cost gap-affine WFA
@@ -48,13 +48,20 @@ def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=
     `ref_texts=True`: texts named as windows of the device-resident reference (AIM_FLAG_REF_TEXTS); combines with everything.
     `read_groups=True`: batches of reads and their candidates, best candidate per read (AIM_FLAG_READ_GROUPS); combines with
     everything. `escalate=True`: WFA on a lane kernel at a low cap, the flag-less plan over the pairs that come back over it
-    (AIM_FLAG_WFA_ESCALATE); results equal the flag-less ones; global gap-affine WFA without w32, bidir and read_groups."""
+    (AIM_FLAG_WFA_ESCALATE); results equal the flag-less ones; global gap-affine WFA without w32, bidir and read_groups.
+    `mate_pairs=True`: reads 2m and 2m + 1 of a read-groups batch are mates and the device picks the best consistent pair of
+    candidates (AIM_FLAG_MATE_PAIRS); needs read_groups and ref_texts."""
     a = ALGO_BY_NAME[algo] if isinstance(algo, str) else algo
     gap_i = gap if gap_i is None else gap_i
     gap_d = gap if gap_d is None else gap_d
     flags = (FLAG_BACKTRACE if backtrace else 0) | (FLAG_REDUCE if reduce else 0) | (FLAG_SWG_W16 if swg_w16 else 0)
     flags |= (FLAG_REQ8 if req8 else 0) | (FLAG_RES8 if res8 else 0) | (FLAG_WFA_W32 if w32 else 0) | (FLAG_REF_TEXTS if ref_texts else 0)
     flags |= FLAG_READ_GROUPS if read_groups else 0
+    if mate_pairs:
+        for name, given in (("read_groups", read_groups), ("ref_texts", ref_texts)):
+            if not given:
+                raise ValueError("mate_pairs needs %s" % name)
+        flags |= FLAG_MATE_PAIRS
     if escalate:
         if a != ALGO_WFA:
             raise ValueError("escalate needs wfa")
@@ -282,6 +289,106 @@ def group_pairs(seed, first_read, n_reads, k, length, error, reference, read_siz
     return req, rows, offsets, tpos, txt, np.ascontiguousarray(rows[read_of])
 
 
+MATE_TRUTH_DTYPE = np.dtype([("true", "<u4", (2,)), ("kind", "<u4")])   # mate_pairs: the true candidates of reads 2m / 2m + 1; kind below
+MATE_UNIQUE, MATE_REPEAT, MATE_DISCORDANT = 0, 1, 2
+
+
+def mate_pairs(seed, n_read_pairs, length, error, insert, k, repeat_frac, read_size=None, discordant_frac=0.05, shift=8):
+    """Seeded paired-end reads with candidate windows (AIM_FLAG_MATE_PAIRS). The reference is built here: read pair m owns a region
+    of random A/C/G/T that holds its fragment of insert +- insert // 10 bases, and a zone of planted exact repeats follows the
+    regions. The mates are the fragment's two ends in FR orientation: one read is the first `length` bases on the plus strand, the
+    other the last `length` bases on the minus strand (which of them is read 2m is seeded), each after ceil(length * error) edits
+    of ref_pairs' model. With probability `repeat_frac` one mate's window is copied verbatim into the repeat zone and the copy is a
+    candidate of that read: it scores exactly like the true window, and only the other mate tells the two apart. With probability
+    `discordant_frac` the second read is taken from the plus strand too, so the pair has no proper combination at its true windows.
+    Every read has k candidates of `length` bases in seeded order: the true window, the repeat copy if there is one, and decoys --
+    each a copy of the true window moved by 1..`shift` bases (same strand) or a random window on either strand. Read pair m depends
+    only on (seed, m) and n_read_pairs (the repeat zone's place).
+    Returns (reference uint8[], requests[n_pairs], read_rows[2 * n_read_pairs][read_size], read_offsets uint32, text_pos uint64[n_pairs],
+    texts[n_pairs][read_size], patterns[n_pairs][read_size], truth[n_read_pairs] of MATE_TRUTH_DTYPE)."""
+    nedits = int(math.ceil(length * error))
+    read_size = round_up_8(length + nedits) if read_size is None else int(read_size)
+    jitter = insert // 10
+    if insert - jitter < length:
+        raise ValueError("insert %d too small for reads of %d bases" % (insert, length))
+    if length + nedits > read_size:
+        raise ValueError("read_size %d too small for length %d + %d edits" % (read_size, length, nedits))
+    if k < 1:
+        raise ValueError("every read needs at least one candidate")
+    region = insert + jitter + 64
+    zone = n_read_pairs * region
+    ref = np.zeros(zone + n_read_pairs * length, dtype=np.uint8)
+    span = len(ref) - length + 1
+    acgt, bases = b"ACGT", np.frombuffer(b"ACGT", dtype=np.uint8)
+    n_reads, n = 2 * n_read_pairs, 2 * n_read_pairs * k
+    req = np.zeros(n, dtype=REQUEST_DTYPE)
+    rows = np.zeros((n_reads, read_size), dtype=np.uint8)
+    tpos = np.zeros(n, dtype=np.uint64)
+    truth = np.zeros(n_read_pairs, dtype=MATE_TRUTH_DTYPE)
+    plan = []
+    for m in range(n_read_pairs):           # the reference first: a window may reach into a neighbour's region or the repeat zone
+        rng = np.random.default_rng([int(seed), m, 0x6D617465])
+        ref[m * region:(m + 1) * region] = bases[rng.integers(0, 4, size=region)]
+        ref[zone + m * length:zone + (m + 1) * length] = bases[rng.integers(0, 4, size=length)]
+        frag = insert + int(rng.integers(-jitter, jitter + 1))
+        start = m * region + int(rng.integers(0, region - frag + 1))
+        u = float(rng.random())
+        kind = MATE_REPEAT if u < repeat_frac else (MATE_DISCORDANT if u < repeat_frac + discordant_frac else MATE_UNIQUE)
+        wins = [(start, False), (start + frag - length, kind != MATE_DISCORDANT)]     # (position, minus) of the plus-end / minus-end read
+        rep_of = int(rng.integers(0, 2)) if kind == MATE_REPEAT else -1
+        if rep_of >= 0:
+            ref[zone + m * length:zone + (m + 1) * length] = ref[wins[rep_of][0]:wins[rep_of][0] + length]
+        plan.append((rng, wins, rep_of, bool(rng.integers(0, 2)), kind))
+    for m, (rng, wins, rep_of, swap, kind) in enumerate(plan):
+        truth["kind"][m] = kind
+        for which in range(2):
+            r = 2 * m + (which ^ int(swap))  # swap: the minus-end read is read 2m
+            pos, minus = wins[which]
+            p = bytearray(ref_window(ref, pos, length, minus).tobytes())
+            for _ in range(nedits):
+                kd, b, x = int(rng.integers(0, 3)), acgt[int(rng.integers(0, 4))], int(rng.integers(0, 1 << 32))
+                if kd == 0 and p:
+                    p[x % len(p)] = b
+                elif kd == 1 and p:
+                    del p[x % len(p)]
+                else:
+                    p.insert(x % (len(p) + 1), b)
+            rows[r, :len(p)] = np.frombuffer(bytes(p), dtype=np.uint8)
+            cands = [(pos, minus)]
+            if which == rep_of and k >= 2:
+                cands.append((zone + m * length, minus))
+            while len(cands) < k:
+                if rng.random() < 0.5:
+                    cands.append((min(max(pos + int(rng.choice([-1, 1])) * int(rng.integers(1, shift + 1)), 0), span - 1), minus))
+                else:
+                    cands.append((int(rng.integers(0, span)), bool(rng.random() < 0.5)))
+            order = rng.permutation(k)
+            lo = r * k
+            for slot, c in enumerate(order):
+                cp, cm = cands[int(c)]
+                tpos[lo + slot] = cp | ((1 << 63) if cm else 0)
+                if c == 0:
+                    truth["true"][m, r & 1] = lo + slot
+            req["pattern_len"][lo:lo + k], req["text_len"][lo:lo + k] = len(p), length
+    req["idx"] = np.arange(n, dtype=np.uint32)
+    txt = np.zeros((n, read_size), dtype=np.uint8)
+    for c in range(n):
+        tp = int(tpos[c])
+        txt[c, :length] = ref_window(ref, tp & ((1 << 63) - 1), length, bool(tp >> 63))
+    offsets = np.arange(n_reads + 1, dtype=np.uint32) * np.uint32(k)
+    return ref, req, rows, offsets, tpos, txt, np.ascontiguousarray(np.repeat(rows, k, axis=0)), truth
+
+
+def align_device_mates(params, n_pairs, n_reads, d_requests, d_patterns, d_text_pos, d_reference, ref_len, d_read_offsets, d_results, d_ops,
+                       d_best, mates, d_mates, d_scratch, scratch_bytes, stream=None):
+    """aim_align_device_mates on device pointers (integers, e.g. torch's data_ptr(); None = NULL): the stateless form of a
+    AIM_FLAG_MATE_PAIRS batch. mates = (min_span, max_span, unpaired_penalty). Only enqueues work on `stream`."""
+    lo, hi, pen = (int(x) for x in mates)
+    capi.check(capi.load().aim_align_device_mates(params_ref(params), n_pairs, n_reads, d_requests, d_patterns, None, d_text_pos, d_reference,
+                                                  ref_len, d_read_offsets, d_results, d_ops, d_best, lo, hi, pen, d_mates, d_scratch,
+                                                  scratch_bytes, stream))
+
+
 def to_request8(req):
     """aim_request_t[] -> aim_request8_t[] (the reference's own 8-byte WFA request_t; AIM_FLAG_REQ8)."""
     out = np.zeros(len(req), dtype=REQUEST8_DTYPE)
@@ -468,16 +575,26 @@ class DeviceSet:
         self.ref_len = len(arr)
 
     def submit(self, device, slot, req, pat=None, txt=None, packed=None, want_ops=False, cigar_runs_cap=0, text_pos=None,
-               read_offsets=None):
+               read_offsets=None, mates=None):
         """aim_set_submit: ASCII rows (pat, txt) or a packed batch (pack_batch(...)); results / ops / compact CIGAR buffers
         are allocated here and returned by wait(). text_pos (AIM_FLAG_REF_TEXTS): the texts are windows of the reference; pass
         pat (or packed = pack_batch(req, pat, None)) and no texts. read_offsets (AIM_FLAG_READ_GROUPS): req and the texts are per
-        candidate, pat holds one row per read; wait() returns one row per read and "best" (capi.BEST_DTYPE)."""
+        candidate, pat holds one row per read; wait() returns one row per read and "best" (capi.BEST_DTYPE). mates = (min_span,
+        max_span, unpaired_penalty) (AIM_FLAG_MATE_PAIRS, with read_offsets and text_pos): reads 2m and 2m + 1 are mates; wait() also
+        returns "mates" (capi.MATE_DTYPE, one row per read pair) next to "best", which stays the independent selection."""
         if (self.params.flags & FLAG_REQ8) and req.dtype != REQUEST8_DTYPE:
             req = to_request8(req)
         req = np.ascontiguousarray(req)
         n, rs = len(req), self.params.read_size
-        rio = capi.BatchIOGroups() if read_offsets is not None else capi.BatchIORef()
+        if mates is not None:
+            if read_offsets is None:
+                raise ValueError("mates needs read_offsets")
+            mio = capi.BatchIOMates()
+            rio = mio.groups
+            mio.min_span, mio.max_span, mio.unpaired_penalty = (int(x) for x in mates)
+        else:
+            mio = None
+            rio = capi.BatchIOGroups() if read_offsets is not None else capi.BatchIORef()
         io = rio.base
         out = {}
         if read_offsets is not None:
@@ -486,6 +603,9 @@ class DeviceSet:
             out["best"] = np.zeros(len(ro) - 1, dtype=capi.BEST_DTYPE)
             rio.best = out["best"].ctypes.data
             n_out = len(ro) - 1
+            if mio is not None:
+                out["mates"] = np.zeros(n_out // 2, dtype=capi.MATE_DTYPE)
+                mio.mates = out["mates"].ctypes.data
         else:
             ro, n_out = None, n
         io.n_pairs = n
@@ -519,7 +639,7 @@ class DeviceSet:
             out["ops"] = np.zeros((n_out, 2 * rs), dtype=np.uint8)
             io.ops = out["ops"].ctypes.data
         capi.check(self.lib.aim_set_submit(self.handle, device, slot, C.byref(io)))
-        self._inflight[(device, slot)] = (rio, keep, out)
+        self._inflight[(device, slot)] = (rio if mio is None else mio, keep, out)
 
     def wait(self, device, slot, check=True):
         io, keep, out = self._inflight.pop((device, slot), (None, None, {}))   # nothing in flight: the library reports AIM_ESTATE

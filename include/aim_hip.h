@@ -173,6 +173,33 @@ typedef struct aim_affine2p_params {
  * AIM_FLAG_WFA_BIDIR (no lane kernel takes them) and with AIM_FLAG_READ_GROUPS (a follow-up).
  * Check aim_features() & AIM_FEATURE_WFA_ESCALATE first: older libraries ignore unknown flags. */
 #define AIM_FLAG_WFA_ESCALATE 0x1000u
+/* AIM_FLAG_MATE_PAIRS (needs AIM_FLAG_READ_GROUPS and AIM_FLAG_REF_TEXTS; combines with whatever AIM_FLAG_READ_GROUPS combines with,
+ * under those flags' own rules): paired-end candidate selection on the device. Reads 2m and 2m + 1 of a batch are mates (n_reads must
+ * be even). After the score-only pass and the independent selection of AIM_FLAG_READ_GROUPS, the device picks for every read pair the
+ * best consistent pair of candidates and falls back to the independent winners only when no consistent pair is good enough.
+ * THE SELECTION RULE (deterministic; it does not depend on the grid):
+ *   Candidate windows. Candidate c has a window [start_c, end_c) with start_c = text_pos[c] & ~AIM_REF_MINUS_STRAND and
+ *   end_c = start_c + text_len[c]. It has a strand bit, a score and a status from the score-only pass. A WFA pair over the cap counts
+ *   with MAX_SCORE + 1, as under AIM_FLAG_READ_GROUPS.
+ *   Proper combination. A combination (i, j) takes candidate i of read 2m and candidate j of read 2m+1. It is proper when all of the
+ *   following hold: both candidates are AIM_PAIR_OK; their strands differ; start_f <= start_r, with f the strand-0 candidate and r the
+ *   strand-1 candidate; min_span <= end_r - start_f <= max_span.
+ *   The spans are window coordinates. They are not refined by the CIGAR: a caller widens the bounds by the flanks of its windows.
+ *   Costs. A proper combination costs score_i + score_j. The unpaired choice costs best_a + best_b + unpaired_penalty, where best_a
+ *   and best_b are the independent AIM_FLAG_READ_GROUPS winners' scores. The unpaired choice exists only when both reads have an OK
+ *   candidate. Sums are formed in 64 bits and clamped to INT32_MAX - 1.
+ *   Choice. The proper combination of lowest cost wins, with ties broken by lowest i and then lowest j. It is taken if its cost is
+ *   at most the unpaired cost, so a tie goes to proper. Otherwise the independent winners are taken and flags = 0. If one mate has no
+ *   OK candidate, the other keeps its independent winner and score_sum = INT32_MAX.
+ *   Outputs. sel[2m] and sel[2m+1] are the chosen candidates, or read_offsets[r] when a read has none. Everything downstream is
+ *   AIM_FLAG_READ_GROUPS' contract unchanged: read r's result row, its ops row [begin_offset, end_offset), its compact header and its
+ *   runs are those of candidate sel[r] run without these flags. groups.best still reports each read's INDEPENDENT selection.
+ * The selection enumerates a read pair's combinations: its cost is O(K1 * K2) for reads of K1 and K2 candidates.
+ * Entry points: aim_set_submit with an aim_batch_io_mates_t and aim_align_device_mates; every entry point that refuses
+ * AIM_FLAG_READ_GROUPS refuses this flag too, and so does aim_align_device_groups. Without AIM_FLAG_READ_GROUPS or AIM_FLAG_REF_TEXTS
+ * the flag is AIM_EINVAL, the message naming the missing flag.
+ * Check aim_features() & AIM_FEATURE_MATE_PAIRS first: older libraries ignore unknown flags. */
+#define AIM_FLAG_MATE_PAIRS 0x2000u
 
 /* Per-pair descriptor: byte-compatible with the NW/SWG request_t
  * (NW/DPU-WRAM/common/common.h:114-120).  The WFA variant of the reference
@@ -225,6 +252,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_REF_TEXTS 0x20u /* AIM_FLAG_REF_TEXTS is honoured */
 #define AIM_FEATURE_READ_GROUPS 0x40u /* AIM_FLAG_READ_GROUPS is honoured */
 #define AIM_FEATURE_WFA_ESCALATE 0x80u /* AIM_FLAG_WFA_ESCALATE is honoured */
+#define AIM_FEATURE_MATE_PAIRS 0x100u /* AIM_FLAG_MATE_PAIRS is honoured */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -365,6 +393,29 @@ typedef struct aim_batch_io_groups {
  * last offset names read n_reads - 1). n_reads 0 is valid only with n_pairs 0. aim_set_submit runs it before anything is enqueued. */
 int aim_groups_check(uint32_t n_pairs, uint32_t n_reads, const uint32_t *read_offsets, uint32_t *bad_read);
 
+/* AIM_FLAG_MATE_PAIRS: what the device chose for read pair m (reads 2m and 2m + 1); the rule is stated at the flag. */
+#define AIM_MATE_PROPER 0x1u
+typedef struct aim_mate {          /* 32 B, one per read pair m */
+    uint32_t best_pair[2];         /* chosen candidate (batch index) of read 2m / 2m+1; UINT32_MAX: that read has no OK candidate */
+    int32_t  score_sum;            /* cost of the choice; INT32_MAX when a mate has no OK candidate */
+    int32_t  second_sum;           /* lowest cost among the OTHER proper combinations; INT32_MAX when there is none */
+    uint32_t n_best;               /* proper combinations of cost score_sum (0 when the choice is not proper) */
+    uint32_t flags;                /* AIM_MATE_PROPER */
+    uint32_t pad[2];               /* 0 */
+} aim_mate_t;
+
+/* AIM_FLAG_MATE_PAIRS: aim_set_submit reads past `groups` (only with the flag). */
+typedef struct aim_batch_io_mates {
+    aim_batch_io_groups_t groups;  /* unchanged meaning; groups.best still reports each read's INDEPENDENT selection */
+    int64_t  min_span, max_span;   /* 0 <= min_span <= max_span < 2^62 */
+    int32_t  unpaired_penalty;     /* >= 0 */
+    uint32_t pad;
+    aim_mate_t *mates;             /* out: [n_reads / 2], or NULL */
+} aim_batch_io_mates_t;
+/* Host-side check of a mate-pairs batch: AIM_OK, or AIM_EINVAL with a message for an odd n_reads, a span outside
+ * 0 <= min_span <= max_span < 2^62, or a negative penalty. aim_set_submit runs it after aim_groups_check, before anything is enqueued. */
+int aim_mates_check(uint32_t n_reads, int64_t min_span, int64_t max_span, int32_t unpaired_penalty);
+
 /* aim_set_configure with `slots` (1..4) buffer sets per device; max_raw_pairs bounds n_raw of a packed batch
  * (0 = packed input not used), max_runs the run buffer of a compact-CIGAR batch (0 = not used). */
 int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t max_pairs_per_device, uint32_t slots,
@@ -425,6 +476,14 @@ int aim_align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32
                             const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
                             const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, void *d_scratch,
                             size_t scratch_bytes, void *hip_stream);
+/* AIM_FLAG_MATE_PAIRS: aim_align_device_groups' arguments (d_texts_or_null must be NULL: the flag needs AIM_FLAG_REF_TEXTS), then the
+ * pairing parameters and d_mates[n_reads / 2] (device memory; may be NULL). n_reads must be even (aim_mates_check). d_best still
+ * receives the independent selection (may be NULL: aim_scratch_bytes under the flag includes a copy for the kernel). */
+int aim_align_device_mates(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
+                           const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
+                           const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, int64_t min_span,
+                           int64_t max_span, int32_t unpaired_penalty, aim_mate_t *d_mates, void *d_scratch, size_t scratch_bytes,
+                           void *hip_stream);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
