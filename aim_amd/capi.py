@@ -34,6 +34,9 @@ FLAG_WFA_ESCALATE = 0x1000   # WFA: a lane kernel at a low cap over the batch, t
 FEATURE_WFA_ESCALATE = 0x80  # aim_features(): AIM_FLAG_WFA_ESCALATE is honoured
 FLAG_MATE_PAIRS = 0x2000     # paired-end selection over a read-groups batch of reference windows: reads 2m and 2m + 1 are mates
 FEATURE_MATE_PAIRS = 0x100   # aim_features(): AIM_FLAG_MATE_PAIRS is honoured
+FLAG_SAM_FIELDS = 0x4000     # SAM-ready records (POS, CIGAR, NM, MD) from the final ops rows and the resident reference
+FEATURE_SAM_FIELDS = 0x200   # aim_features(): AIM_FLAG_SAM_FIELDS is honoured
+SAM_EQX, SAM_REVERSE, SAM_UNMAPPED, SAM_OVERFLOW = 0x1, 0x10, 0x4, 0x100   # sam_options; aim_sam_t.flags (SAM's own bits); aim_sam_t.status bit
 MATE_PROPER = 1              # aim_mate_t.flags: the chosen candidates are a proper combination
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
 
@@ -101,6 +104,9 @@ assert BEST_DTYPE.itemsize == 16
 MATE_DTYPE = np.dtype([("best_pair", "<u4", (2,)), ("score_sum", "<i4"), ("second_sum", "<i4"), ("n_best", "<u4"), ("flags", "<u4"),
                        ("pad", "<u4", (2,))])   # aim_mate_t
 assert MATE_DTYPE.itemsize == 32
+SAM_DTYPE = np.dtype([("idx", "<u4"), ("score", "<i4"), ("pos", "<u8"), ("ref_span", "<u4"), ("nm", "<u4"), ("cigar_offset", "<u4"),
+                      ("n_cigar", "<u4"), ("md_offset", "<u4"), ("md_len", "<u4"), ("flags", "<u2"), ("status", "<u2"), ("pad", "<u4")])   # aim_sam_t
+assert SAM_DTYPE.itemsize == 48
 
 
 class BatchIO(C.Structure):
@@ -127,6 +133,13 @@ class BatchIOMates(C.Structure):
     receives a pointer to `groups.base`."""
     _fields_ = [("groups", BatchIOGroups), ("min_span", C.c_int64), ("max_span", C.c_int64), ("unpaired_penalty", C.c_int32),
                 ("pad", C.c_uint32), ("mates", C.c_void_p)]
+
+
+class BatchIOSam(C.Structure):
+    """aim_batch_io_sam_t: BatchIOMates at offset 0 (its groups / mates members are read only under their own flags), then the record
+    buffers (AIM_FLAG_SAM_FIELDS); aim_set_submit receives a pointer to `mates.groups.base`."""
+    _fields_ = [("mates", BatchIOMates), ("sam", C.c_void_p), ("sam_cigar", C.c_void_p), ("sam_cigar_cap", C.c_uint32), ("sam_md", C.c_void_p),
+                ("sam_md_cap", C.c_uint32), ("sam_options", C.c_uint32)]
 
 
 # every symbol include/aim_hip.h declares: name -> (restype, argtypes)
@@ -171,6 +184,10 @@ SYMBOLS = {
     "aim_mates_check": (C.c_int, [_U32, C.c_int64, C.c_int64, _I32]),
     "aim_align_device_mates": (C.c_int, [C.POINTER(Params), _U32, _U32, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, C.c_int64,
                                          C.c_int64, _I32, _VP, _VP, C.c_size_t, _VP]),
+    "aim_set_sam_capacity": (C.c_int, [_VP, _U32, _U32]),
+    "aim_sam_device": (C.c_int, [C.POINTER(Params), _U32, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _U32, _VP, _VP, _U32, _VP, _U32, _VP, _VP]),
+    "aim_sam_format_cigar": (C.c_int, [_VP, _U32, _VP, _I32]),
+    "aim_sam_kernel_name": (C.c_char_p, [C.POINTER(Params)]),
 }
 
 _lib = None

@@ -34,6 +34,7 @@
 #include "batch_io.hpp"
 #include "groups.hpp"
 #include "mates.hpp"
+#include "sam_fields.hpp"
 #include "genasm_wave.hpp"
 
 namespace {
@@ -157,6 +158,7 @@ aim::Knobs read_knobs()
     k.poison_scratch = env_int("AIM_DEBUG_POISON_SCRATCH", -1);
     k.poison_ops = env_int("AIM_DEBUG_POISON_OPS", -1);
     k.poison_lds = env_int("AIM_DEBUG_POISON_LDS", -1);
+    k.sam_wave_min = env_int("AIM_SAM_WAVE_MIN", -1);
     k.plan_debug = getenv("AIM_PLAN_DEBUG") != nullptr;
     k.cus = (uint32_t)std::max(0, env_int("AIM_CHIP_CUS", 0));   // 0: ask the device (chip_cus)
     return k;
@@ -258,6 +260,9 @@ inline bool is_groups(const aim_params_t &p) { return (p.flags & AIM_FLAG_READ_G
 inline bool is_mates(const aim_params_t &p) { return (p.flags & AIM_FLAG_MATE_PAIRS) != 0; }
 // AIM_FLAG_WFA_ESCALATE: a lane kernel at a low cap over the batch, the flag-less plan over the pairs it left over that cap (plan_wfa).
 inline bool is_escalate(const aim_params_t &p) { return (p.flags & AIM_FLAG_WFA_ESCALATE) != 0; }
+// AIM_FLAG_SAM_FIELDS: SAM-ready records from the final ops rows (sam_fields.hpp); one more kernel behind the batch, no plan depends on it
+// beyond keeping the ops rows on the device (no fused run output).
+inline bool is_sam(const aim_params_t &p) { return (p.flags & AIM_FLAG_SAM_FIELDS) != 0; }
 // The params as this library keeps them: room for either extension, and the extension copied only when a flag says it exists.
 union XParams {
     aim_params_t base;
@@ -284,6 +289,13 @@ int validate_params(const aim_params_t &p)
     if (is_mates(p)) {   // the positions it pairs by are the windows' text_pos
         if (!is_groups(p)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS needs AIM_FLAG_READ_GROUPS");
         if (!is_ref(p)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS needs AIM_FLAG_REF_TEXTS");
+    }
+    if (is_sam(p)) {   // the records are on the reference's coordinates and come from the ops rows
+        if (p.flags & AIM_FLAG_RES8) return fail(AIM_EINVAL, "AIM_FLAG_SAM_FIELDS cannot be combined with AIM_FLAG_RES8");
+        if (p.algo == AIM_ALGO_GENASM)
+            return fail(AIM_EINVAL, "AIM_FLAG_SAM_FIELDS cannot be combined with AIM_ALGO_GENASM (its windowed walk is unpinned and begin_offset = 0 is another contract)");
+        if (!is_ref(p)) return fail(AIM_EINVAL, "AIM_FLAG_SAM_FIELDS needs AIM_FLAG_REF_TEXTS");
+        if (!(p.flags & AIM_FLAG_BACKTRACE)) return fail(AIM_EINVAL, "AIM_FLAG_SAM_FIELDS needs AIM_FLAG_BACKTRACE");
     }
     if (is_escalate(p)) {
         if (p.algo != AIM_ALGO_WFA) return fail(AIM_EINVAL, "AIM_FLAG_WFA_ESCALATE needs AIM_ALGO_WFA");
@@ -765,7 +777,7 @@ int describe_stage_plan(const StagePlan &pl, const aim_params_t &p, uint32_t n_p
 }
 
 // ... AIM_FLAG_WFA_ESCALATE: "<stage 1 line> | <stage 2 line> escalate=c", or the flag-less line and " escalate=0"
-int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint64_t budget, char *out, size_t cap)
+int describe_plan_stages(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint64_t budget, char *out, size_t cap)
 {
     if (!pl.esc) return describe_stage_plan(pl, p, n_pairs, budget, out, cap);
     char a[384], b[384];
@@ -780,6 +792,15 @@ int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint6
     describe_stage_plan(s1, p1, n_pairs, budget, a, sizeof a);
     describe_stage_plan(pl.s2, p, n_pairs, budget, b, sizeof b);
     return snprintf(out, cap, "%s | %s escalate=%d", a, b, pl.esc_c);
+}
+
+// ... AIM_FLAG_SAM_FIELDS: the line and " sam=1"
+int describe_plan(const Plan &pl, const aim_params_t &p, uint32_t n_pairs, uint64_t budget, char *out, size_t cap)
+{
+    if (!is_sam(p)) return describe_plan_stages(pl, p, n_pairs, budget, out, cap);
+    char a[800];
+    describe_plan_stages(pl, p, n_pairs, budget, a, sizeof a);
+    return snprintf(out, cap, "%s sam=1", a);
 }
 
 int make_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, Plan *pl, uint32_t mode = 0u)
@@ -1138,6 +1159,7 @@ struct GroupsPlan {
     Plan p1, p2;            // p2 planned iff pass2
     bool pass2;
     bool mates;             // AIM_FLAG_MATE_PAIRS: mate_select_kernel after the independent selection
+    bool sam;               // AIM_FLAG_SAM_FIELDS: the reads' records after the second pass
     size_t plan_bytes;      // the larger of the two plans' scratch (both made for n_pairs)
     // aim_align_device_groups: the rest of its scratch, offsets from the base (256-B aligned)
     size_t cand_p_at, cand_t_at, res1_at, map_at, sel_at, req2_at, pat2_at, txt2_at, total;
@@ -1146,7 +1168,7 @@ struct GroupsPlan {
 inline XParams groups_pass_params(const aim_params_t &p, uint32_t drop)
 {
     XParams x = copy_params(p);
-    x.base.flags &= ~(AIM_FLAG_READ_GROUPS | AIM_FLAG_MATE_PAIRS | drop);
+    x.base.flags &= ~(AIM_FLAG_READ_GROUPS | AIM_FLAG_MATE_PAIRS | AIM_FLAG_SAM_FIELDS | drop);
     return x;
 }
 
@@ -1156,7 +1178,7 @@ int describe_groups(const GroupsPlan &g, uint32_t n_pairs, uint32_t n_reads, uin
     describe_plan(g.p1, g.x1.base, n_pairs, budget, a, sizeof a);
     if (g.pass2) describe_plan(g.p2, g.x2.base, n_reads, budget, b, sizeof b);
     else snprintf(b, sizeof b, "no second pass n=%u", n_reads);
-    return snprintf(out, cap, "%s | %s groups=1%s", a, b, g.mates ? " mates=1" : "");
+    return snprintf(out, cap, "%s | %s groups=1%s%s", a, b, g.mates ? " mates=1" : "", g.sam ? " sam=1" : "");
 }
 
 // Both passes planned for n_pairs candidates (the worst case n_reads = n_pairs for pass 2) and the stateless scratch layout:
@@ -1173,6 +1195,7 @@ int make_groups_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &
     g->x2 = groups_pass_params(p, 0u);
     g->pass2 = (p.flags & AIM_FLAG_BACKTRACE) != 0;
     g->mates = is_mates(p);
+    g->sam = is_sam(p);
     rc = make_plan(g->x1.base, n_pairs, quiet, budget, &g->p1);
     if (rc) return rc;
     g->plan_bytes = g->p1.scratch_total;
@@ -1340,6 +1363,16 @@ struct aim_slot {
     aim_result_t *g_res1 = nullptr;
     aim_best_t *g_best = nullptr;
     aim_mate_t *g_mates = nullptr;   // AIM_FLAG_MATE_PAIRS: [max_pairs / 2]
+    // AIM_FLAG_SAM_FIELDS (aim_set_sam_capacity): records, CIGAR words, MD bytes, the two cursors and their pinned host copy
+    aim_sam_t *d_sam = nullptr;
+    uint32_t *d_samcig = nullptr, *d_samcur = nullptr, *h_samcur = nullptr;
+    char *d_sammd = nullptr;
+    uint32_t samcig_cap = 0, sammd_cap = 0;
+    // ... the SAM members of the batch in flight (sam == nullptr: none)
+    aim_sam_t *io_sam = nullptr;
+    uint32_t *io_samcig = nullptr;
+    char *io_sammd = nullptr;
+    uint32_t io_samcig_cap = 0, io_sammd_cap = 0;
     void *g_req2 = nullptr;
     char *g_pat2 = nullptr, *g_txt2 = nullptr;
     uint32_t n_reads = 0;            // reads of the groups batch in flight (n_pairs then counts its output rows)
@@ -1381,10 +1414,12 @@ void free_slot(aim_slot &s)
 {
     void *bufs[] = {s.d_req, s.d_pat, s.d_txt, s.d_ops, s.d_res, s.d_scratch, s.d_packP, s.d_packT, s.d_rawidx, s.d_rawP, s.d_rawT,
                     s.d_cig, s.d_runs, s.d_cursor, s.d_rawreq, s.d_rawres, s.d_rawops, s.d_rawcig, s.d_tpos, s.d_reftodo,
-                    s.g_readP, s.g_roff, s.g_map, s.g_sel, s.g_rawslot, s.g_res1, s.g_best, s.g_mates, s.g_req2, s.g_pat2, s.g_txt2};
+                    s.g_readP, s.g_roff, s.g_map, s.g_sel, s.g_rawslot, s.g_res1, s.g_best, s.g_mates, s.g_req2, s.g_pat2, s.g_txt2,
+                    s.d_sam, s.d_samcig, s.d_samcur, s.d_sammd};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (s.h_cursor) (void)hipHostFree(s.h_cursor);
+    if (s.h_samcur) (void)hipHostFree(s.h_samcur);
     for (auto &e : s.ev)
         if (e) (void)hipEventDestroy(e);
     if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -1522,6 +1557,82 @@ int launch_on_slot(aim_set *set, aim_device_ctx &d, aim_slot &s, uint32_t mode =
     return launch(pl, set->knobs, set->params, s.n_pairs, s.d_req, s.d_pat, s.d_txt, s.d_res, s.d_ops, s.d_scratch,
                   s.scratch_bytes, s.stream, fio, &s.aux);
 }
+
+// aim_sam_t's offsets are 32-bit. CIGAR words <= op bytes and MD bytes <= 2 per op + the digits of one final count, so both cursors stay
+// below 2^32 for every batch this admits. It depends on the row count and READ_SIZE only: checked before anything is enqueued.
+int check_sam_rows(const aim_params_t &p, uint32_t n_rows)
+{
+    if ((uint64_t)n_rows * (4ull * (uint64_t)p.read_size + 10ull) >= (1ull << 32))
+        return fail(AIM_EINVAL, "SAM records: %u rows of READ_SIZE %d exceed the 32-bit offsets of aim_sam_t (split the batch)", n_rows, p.read_size);
+    return AIM_OK;
+}
+// Which of the two kernels of sam_fields.hpp a launch takes: by READ_SIZE, AIM_SAM_WAVE_MIN overriding the measured switch
+inline bool sam_use_wave(const aim_params_t &p, const aim::Knobs &kn)
+{
+    return p.read_size >= (kn.sam_wave_min >= 0 ? kn.sam_wave_min : aim::kSamWaveMinReadSize);
+}
+
+// The SAM kernel over n_rows final rows (sam_fields.hpp), the cursors zeroed first. The caller has run check_sam_rows.
+int enqueue_sam(const aim_params_t &p, const aim::Knobs &kn, aim::SamArgs a, hipStream_t stream)
+{
+    if (!a.n_rows) return AIM_OK;
+    a.algo = p.algo;
+    a.max_score = p.max_score;
+    a.read_size = p.read_size;
+    HIP_TRY(hipMemsetAsync(a.cursors, 0, 8, stream));
+    aim::sam_fields_launch(sam_use_wave(p, kn), a, stream);
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
+}
+
+// AIM_FLAG_SAM_FIELDS on a slot: what aim_set_submit checks before anything is enqueued; *sio receives the struct (nullptr without the flag)
+int check_sam_io(const aim_set *set, const aim_slot &s, const aim_batch_io_t *io, const aim_batch_io_sam_t **sio)
+{
+    *sio = nullptr;
+    if (!is_sam(set->params)) return AIM_OK;
+    const aim_batch_io_sam_t *x = reinterpret_cast<const aim_batch_io_sam_t *>(io);
+    if (!s.d_sam) return fail(AIM_ESTATE, "AIM_FLAG_SAM_FIELDS: aim_set_sam_capacity has not been called since the set was configured");
+    if (io->n_pairs && (!x->sam || !x->sam_cigar || !x->sam_md)) return fail(AIM_EINVAL, "AIM_FLAG_SAM_FIELDS: null sam, sam_cigar or sam_md");
+    if (x->sam_options & ~AIM_SAM_EQX) return fail(AIM_EINVAL, "AIM_FLAG_SAM_FIELDS: unknown sam_options 0x%x", x->sam_options);
+    // (rows are pairs, or reads under AIM_FLAG_READ_GROUPS: never more than n_pairs)
+    if (int rc = check_sam_rows(set->params, io->n_pairs)) return rc;
+    *sio = x;
+    return AIM_OK;
+}
+
+// ... the kernel behind the batch's final rows (sel: the reads' candidates under AIM_FLAG_READ_GROUPS, else nullptr)
+int enqueue_sam_on_slot(const aim_set *set, const aim_device_ctx &d, aim_slot &s, const aim_batch_io_sam_t *sio, uint32_t n_rows, const uint32_t *sel)
+{
+    aim::SamArgs a;
+    memset(&a, 0, sizeof a);
+    a.n_rows = n_rows;
+    a.text_pos = s.d_tpos;
+    a.sel = sel;
+    a.res = static_cast<const aim_result_t *>(s.d_res);
+    a.ops = s.d_ops;
+    a.ref = d.d_ref;
+    a.ref_len = d.ref_len;
+    a.options = sio->sam_options;
+    a.sam = s.d_sam;
+    a.cigar = s.d_samcig;
+    a.cigar_cap = std::min(sio->sam_cigar_cap, s.samcig_cap);
+    a.md = s.d_sammd;
+    a.md_cap = std::min(sio->sam_md_cap, s.sammd_cap);
+    a.cursors = s.d_samcur;
+    s.io_sam = sio->sam;
+    s.io_samcig = sio->sam_cigar;
+    s.io_sammd = sio->sam_md;
+    s.io_samcig_cap = a.cigar_cap;
+    s.io_sammd_cap = a.md_cap;
+    return enqueue_sam(set->params, set->knobs, a, s.stream);
+}
+// ... and its copies back: the records and the cursors now, the words and bytes in aim_set_wait (their count is only known then)
+int enqueue_sam_d2h(aim_slot &s, uint32_t n_rows)
+{
+    HIP_TRY(hipMemcpyAsync(s.h_samcur, s.d_samcur, 8, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(hipMemcpyAsync(s.io_sam, s.d_sam, (size_t)n_rows * sizeof(aim_sam_t), hipMemcpyDeviceToHost, s.stream));
+    return AIM_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1530,7 +1641,7 @@ int aim_abi_version(void) { return AIM_ABI_VERSION; }
 uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
-           AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS;
+           AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -1737,6 +1848,8 @@ int aim_set_configure(aim_set_t *set, const aim_params_t *params, uint32_t max_p
 
 namespace {
 const char *const kGroupsSubmitOnly = "AIM_FLAG_READ_GROUPS is set: batches go through aim_set_submit with an aim_batch_io_groups_t";
+const char *const kSamStateless = "AIM_FLAG_SAM_FIELDS is set: the records come from aim_set_submit (aim_batch_io_sam_t) or, after a flag-less call, from aim_sam_device";
+const char *const kSamSubmitOnly = "AIM_FLAG_SAM_FIELDS is set: batches go through aim_set_submit with an aim_batch_io_sam_t";
 
 // aim_set_push (texts != nullptr) and aim_set_push_ref (text_pos != nullptr)
 int push_impl(aim_set_t *set, uint32_t device, uint32_t n_pairs, const void *requests, const char *patterns, const char *texts,
@@ -1745,6 +1858,7 @@ int push_impl(aim_set_t *set, uint32_t device, uint32_t n_pairs, const void *req
     if (!set || device >= set->devs.size()) return fail(AIM_EINVAL, "bad device index");
     if (!set->configured) return fail(AIM_ESTATE, "aim_set_configure has not been called");
     if (is_groups(set->params)) return fail(AIM_EINVAL, kGroupsSubmitOnly);
+    if (is_sam(set->params)) return fail(AIM_EINVAL, kSamSubmitOnly);
     if (n_pairs > set->max_pairs) return fail(AIM_EINVAL, "n_pairs %u exceeds configured capacity %u", n_pairs, set->max_pairs);
     if (n_pairs && (!requests || !patterns || (!texts && !text_pos))) return fail(AIM_EINVAL, "null host buffer");
     aim_device_ctx &d = set->devs[device];
@@ -1795,6 +1909,7 @@ int aim_set_launch(aim_set_t *set)
 {
     if (!set || !set->configured) return fail(AIM_ESTATE, "set is not configured");
     if (is_groups(set->params)) return fail(AIM_EINVAL, kGroupsSubmitOnly);
+    if (is_sam(set->params)) return fail(AIM_EINVAL, kSamSubmitOnly);
     for (auto &d : set->devs) {
         aim_slot &s = d.slots[0];
         if (!s.pushed) return fail(AIM_ESTATE, "device %d has no pushed batch", d.dev);
@@ -1835,6 +1950,7 @@ int aim_set_pull(aim_set_t *set, uint32_t device, void *results, char *ops)
     if (!set || device >= set->devs.size()) return fail(AIM_EINVAL, "bad device index");
     if (!set->configured) return fail(AIM_ESTATE, "aim_set_configure has not been called");
     if (is_groups(set->params)) return fail(AIM_EINVAL, kGroupsSubmitOnly);
+    if (is_sam(set->params)) return fail(AIM_EINVAL, kSamSubmitOnly);
     aim_device_ctx &d = set->devs[device];
     aim_slot &s = d.slots[0];
     if (!s.launched) return fail(AIM_ESTATE, "device %d has not been launched", d.dev);
@@ -1925,9 +2041,12 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
     if (n > set->max_pairs) return fail(AIM_EINVAL, "n_pairs %u exceeds configured capacity %u", n, set->max_pairs);
     if (n && (!io->requests || (!packed && !io->patterns) || (!ref && !io->texts))) return fail(AIM_EINVAL, "null requests or sequence rows");
     if (io->cigars && (!bt || !s.d_cig || !io->runs)) return fail(AIM_EINVAL, "compact CIGAR needs AIM_FLAG_BACKTRACE, max_runs > 0 and a run buffer");
-    if (n && !io->results && !io->cigars && !gio->best && !(mio && mio->mates)) return fail(AIM_EINVAL, "no output buffer");
+    const aim_batch_io_sam_t *sio = nullptr;
+    int rc = check_sam_io(set, s, io, &sio);
+    if (rc) return rc;
+    if (n && !io->results && !io->cigars && !gio->best && !(mio && mio->mates) && !sio) return fail(AIM_EINVAL, "no output buffer");
     if (io->ops && !bt) return fail(AIM_EINVAL, "ops requested without AIM_FLAG_BACKTRACE");
-    int rc = check_groups(n, nr, gio->read_offsets, nullptr);
+    rc = check_groups(n, nr, gio->read_offsets, nullptr);
     if (rc) return rc;
     if (mio) {
         rc = check_mates(nr, mio->min_span, mio->max_span, mio->unpaired_penalty);
@@ -1947,6 +2066,7 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
     s.io = *io;
     s.n_pairs = nr;          // aim_set_wait reads n_pairs output rows
     s.n_reads = nr;
+    s.io_sam = nullptr;
     s.runs_sent = 0;
     s.pushed = s.launched = false;
     s.ref_pending = false;
@@ -1956,6 +2076,7 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
     g.x2 = groups_pass_params(p, 0u);
     g.pass2 = bt;
     g.mates = mio != nullptr;
+    g.sam = is_sam(p);
     auto enqueue = [&]() -> int {
         HIP_TRY(hipEventRecord(s.ev[0], s.stream));
         if (n) {
@@ -2036,6 +2157,10 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
                                    std::min(io->runs_cap, set->max_runs), s.d_cursor);
                 HIP_TRY(hipGetLastError());
             }
+            if (sio) {   // the reads' records: row r is candidate sel[r]
+                int src = enqueue_sam_on_slot(set, d, s, sio, nr, s.g_sel);
+                if (src) return src;
+            }
         }
         HIP_TRY(hipEventRecord(s.ev[3], s.stream));
         HIP_TRY(hipEventRecord(s.ev[4], s.stream));
@@ -2049,6 +2174,10 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
             }
             if (io->results) HIP_TRY(hipMemcpyAsync(io->results, s.d_res, (size_t)nr * res_size(p), hipMemcpyDeviceToHost, s.stream));
             if (io->ops) HIP_TRY(hipMemcpyAsync(io->ops, s.d_ops, (size_t)nr * 2 * rs, hipMemcpyDeviceToHost, s.stream));
+            if (sio) {
+                int src = enqueue_sam_d2h(s, nr);
+                if (src) return src;
+            }
         }
         HIP_TRY(hipEventRecord(s.ev[5], s.stream));
         return AIM_OK;
@@ -2095,9 +2224,12 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
     if (packed && io->n_raw > set->max_raw) return fail(AIM_EINVAL, "n_raw %u exceeds configured capacity %u", io->n_raw, set->max_raw);
     if (packed && io->n_raw && (!io->raw_pairs || !io->raw_patterns || (!ref && !io->raw_texts))) return fail(AIM_EINVAL, "null raw side list");
     if (io->cigars && (!bt || !s.d_cig || !io->runs)) return fail(AIM_EINVAL, "compact CIGAR needs AIM_FLAG_BACKTRACE, max_runs > 0 and a run buffer");
-    if (n && !io->results && !io->cigars) return fail(AIM_EINVAL, "no output buffer");
+    const aim_batch_io_sam_t *sio = nullptr;
+    int rc = check_sam_io(set, s, io, &sio);
+    if (rc) return rc;
+    if (n && !io->results && !io->cigars && !sio) return fail(AIM_EINVAL, "no output buffer");
     if (io->ops && !bt) return fail(AIM_EINVAL, "ops requested without AIM_FLAG_BACKTRACE");
-    int rc = check_lengths(p, n, io->requests);
+    rc = check_lengths(p, n, io->requests);
     if (rc) return rc;
     if (ref) {
         rc = check_windows(p, n, io->requests, text_pos, d.ref_len, nullptr);
@@ -2111,6 +2243,7 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
     HIP_TRY(hipSetDevice(d.dev));
     s.io = *io;
     s.n_pairs = n;
+    s.io_sam = nullptr;
     s.runs_sent = 0;
     s.pushed = s.launched = false;
     s.ref_pending = false;
@@ -2148,7 +2281,7 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
             // Does the alignment kernel of this configuration take the batch as it arrived and deliver what was asked for?
             // (wfa_lane_packed_kernel: packed rows in, {idx, score} or compact CIGAR out.) Then this batch is ONE kernel;
             // otherwise the conversion kernels of batch_io.hpp run around the default-ABI kernel.
-            uint32_t mode = (packed ? MODE_PACKED_IN : 0u) | ((io->cigars && !io->results && !io->ops) ? MODE_RUNS_OUT : 0u);
+            uint32_t mode = (packed ? MODE_PACKED_IN : 0u) | ((io->cigars && !io->results && !io->ops && !sio) ? MODE_RUNS_OUT : 0u);   // (the SAM kernel reads ops rows)
             Plan pl = plan_for_batch(set, d, s, n, mode);
             // AIM_FLAG_REF_TEXTS: a packed batch keeps the fused packed lane kernel (its texts gathered as packed rows, the windows
             // holding a byte outside A/C/G/T re-aligned by the general kernel over a to-do list); every other plan runs as for an
@@ -2240,7 +2373,7 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
                     hipLaunchKernelGGL(aim::scatter_elems_kernel, blocks((uint64_t)nr * 4), dim3(256), 0, s.stream, (const uint32_t *)s.d_rawcig,
                                        s.d_rawidx, nr, 4u, (uint32_t *)s.d_cig);
                 }
-                if (!io->cigars || io->results || io->ops) {
+                if (!io->cigars || io->results || io->ops || sio) {
                     hipLaunchKernelGGL(aim::scatter_elems_kernel, blocks((uint64_t)nr * rs_dw), dim3(256), 0, s.stream, (const uint32_t *)s.d_rawres,
                                        s.d_rawidx, nr, rs_dw, (uint32_t *)s.d_res);
                     if (bt) {   // default output (result_t + ops rows): the side list's ops rows go home too
@@ -2251,10 +2384,18 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
                 }
                 HIP_TRY(hipGetLastError());
             }
+            if (sio) {   // the records of the final rows (the raw side pass's rows are home)
+                rc = enqueue_sam_on_slot(set, d, s, sio, n, nullptr);
+                if (rc) return rc;
+            }
         }
         HIP_TRY(hipEventRecord(s.ev[3], s.stream));
         HIP_TRY(hipEventRecord(s.ev[4], s.stream));
         if (n) {
+            if (sio) {
+                rc = enqueue_sam_d2h(s, n);
+                if (rc) return rc;
+            }
             if (io->cigars) {
                 HIP_TRY(hipMemcpyAsync(s.h_cursor, s.d_cursor, 4, hipMemcpyDeviceToHost, s.stream));
                 HIP_TRY(hipMemcpyAsync(io->cigars, s.d_cig, (size_t)n * sizeof(aim_cigar_t), hipMemcpyDeviceToHost, s.stream));
@@ -2308,6 +2449,14 @@ int aim_set_wait(aim_set_t *set, uint32_t device, uint32_t slot, uint32_t *n_run
         s.runs_sent = 0;
     }
     if (n_runs) *n_runs = runs;
+    const aim_sam_t *sam_rows = s.io_sam;
+    if (sam_rows && s.n_pairs) {   // AIM_FLAG_SAM_FIELDS: exactly the words and bytes that were written (rows that did not fit reserved theirs too)
+        const uint32_t words = std::min(s.h_samcur[0], s.io_samcig_cap), bytes = std::min(s.h_samcur[1], s.io_sammd_cap);
+        if (words) HIP_TRY(hipMemcpyAsync(s.io_samcig, s.d_samcig, (size_t)words * 4, hipMemcpyDeviceToHost, s.stream));
+        if (bytes) HIP_TRY(hipMemcpyAsync(s.io_sammd, s.d_sammd, bytes, hipMemcpyDeviceToHost, s.stream));
+        if (words || bytes) HIP_TRY(hipStreamSynchronize(s.stream));
+    }
+    s.io_sam = nullptr;
     // per DEVICE (devices run concurrently: aim_set_timers reports the slowest device, like aim_set_launch does)
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]));
@@ -2331,6 +2480,37 @@ int aim_set_wait(aim_set_t *set, uint32_t device, uint32_t slot, uint32_t *n_run
         if (any_nonzero(s.n_pairs, [r](size_t i) { return (uint32_t)r[i].status; }))
             for (uint32_t i = 0; i < s.n_pairs; ++i)
                 if (r[i].status != AIM_PAIR_OK) return status_error(r[i].idx, r[i].status);
+    } else if (sam_rows) {   // the records are the batch's only per-row output
+        if (any_nonzero(s.n_pairs, [sam_rows](size_t i) { return (uint32_t)(sam_rows[i].status & 0xffu); }))
+            for (uint32_t i = 0; i < s.n_pairs; ++i)
+                if ((sam_rows[i].status & 0xffu) != AIM_PAIR_OK) return status_error(sam_rows[i].idx, sam_rows[i].status & 0xffu);
+    }
+    return AIM_OK;
+}
+
+int aim_set_sam_capacity(aim_set_t *set, uint32_t max_cigar_words, uint32_t max_md_bytes)
+{
+    if (!set) return fail(AIM_EINVAL, "set is NULL");
+    if (!set->configured) return fail(AIM_ESTATE, "aim_set_configure_slots has not been called");
+    if (!is_sam(set->params)) return fail(AIM_EINVAL, "aim_set_sam_capacity needs a set configured with AIM_FLAG_SAM_FIELDS");
+    if (!max_cigar_words || !max_md_bytes) return fail(AIM_EINVAL, "aim_set_sam_capacity: capacities must be > 0");
+    for (auto &d : set->devs) {
+        HIP_TRY(hipSetDevice(d.dev));
+        for (auto &s : d.slots) {
+            if (s.submitted) return fail(AIM_ESTATE, "a slot of device %d holds a batch: aim_set_wait it first", d.dev);
+            void *old[] = {s.d_sam, s.d_samcig, s.d_sammd, s.d_samcur};
+            for (void *b : old)
+                if (b) (void)hipFree(b);
+            s.d_sam = nullptr; s.d_samcig = nullptr; s.d_sammd = nullptr; s.d_samcur = nullptr;
+            s.samcig_cap = s.sammd_cap = 0;
+            HIP_TRY(hipMalloc((void **)&s.d_samcig, (size_t)max_cigar_words * 4));
+            HIP_TRY(hipMalloc((void **)&s.d_sammd, (size_t)max_md_bytes));
+            HIP_TRY(hipMalloc((void **)&s.d_samcur, 64));
+            if (!s.h_samcur) HIP_TRY(hipHostMalloc((void **)&s.h_samcur, 64, hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void **)&s.d_sam, (size_t)set->max_pairs * sizeof(aim_sam_t)));   // last: a slot with d_sam is complete
+            s.samcig_cap = max_cigar_words;
+            s.sammd_cap = max_md_bytes;
+        }
     }
     return AIM_OK;
 }
@@ -2374,6 +2554,7 @@ int aim_set_plan_describe(const aim_set_t *set, uint32_t device, char *out, size
         g.x2 = groups_pass_params(set->params, 0u);
         g.pass2 = (set->params.flags & AIM_FLAG_BACKTRACE) != 0;
         g.mates = is_mates(set->params);
+        g.sam = is_sam(set->params);
         g.p1 = s.plan_last;
         g.p2 = s.plan_last2;
         const bool any = s.n_reads != 0;
@@ -2470,6 +2651,7 @@ int aim_align_device_ref(const aim_params_t *params, uint32_t n_pairs, const voi
                          void *d_scratch, size_t scratch_bytes, void *hip_stream)
 {
     if (!params) return fail(AIM_EINVAL, "params is NULL");
+    if (is_sam(*params)) return fail(AIM_EINVAL, kSamStateless);
     if (!is_ref(*params)) return fail(AIM_EINVAL, "aim_align_device_ref needs AIM_FLAG_REF_TEXTS");
     if (is_groups(*params)) return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS is set: use aim_align_device_groups");
     if (is_mates(*params)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS is set: use aim_align_device_mates");
@@ -2518,6 +2700,7 @@ int aim_align_device(const aim_params_t *params, uint32_t n_pairs, const void *d
                      void *d_scratch, size_t scratch_bytes, void *hip_stream)
 {
     if (!params) return fail(AIM_EINVAL, "params is NULL");
+    if (is_sam(*params)) return fail(AIM_EINVAL, kSamStateless);
     if (is_groups(*params)) return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS is set: use aim_align_device_groups");
     if (is_mates(*params)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS is set: use aim_align_device_mates");
     int n = 0;
@@ -2529,6 +2712,55 @@ int aim_align_device(const aim_params_t *params, uint32_t n_pairs, const void *d
     if (rc) return rc;
     return launch(pl, kn, *params, n_pairs, d_requests, d_patterns, d_texts, d_results, d_ops, d_scratch, scratch_bytes,
                   (hipStream_t)hip_stream);
+}
+
+int aim_sam_device(const aim_params_t *params, uint32_t n_rows, const void *d_requests, const uint64_t *d_text_pos,
+                   const uint32_t *d_sel_or_null, const void *d_results, const char *d_ops, const char *d_reference, uint64_t ref_len,
+                   uint32_t options, aim_sam_t *d_sam, uint32_t *d_cigar, uint32_t cigar_cap, char *d_md, uint32_t md_cap,
+                   uint32_t *d_cursors, void *hip_stream)
+{
+    if (!params) return fail(AIM_EINVAL, "params is NULL");
+    if (params->algo == AIM_ALGO_GENASM)
+        return fail(AIM_EINVAL, "aim_sam_device cannot take AIM_ALGO_GENASM rows (its windowed walk is unpinned and begin_offset = 0 is another contract)");
+    if (!(params->flags & AIM_FLAG_BACKTRACE)) return fail(AIM_EINVAL, "aim_sam_device needs AIM_FLAG_BACKTRACE (the records come from the ops rows)");
+    if (params->flags & AIM_FLAG_RES8) return fail(AIM_EINVAL, "aim_sam_device cannot be combined with AIM_FLAG_RES8");
+    if (params->read_size <= 0 || (params->read_size & 7)) return fail(AIM_EINVAL, "read_size must be a positive multiple of 8 (got %d)", params->read_size);
+    if (options & ~AIM_SAM_EQX) return fail(AIM_EINVAL, "aim_sam_device: unknown options 0x%x", options);
+    int rc = check_sam_rows(*params, n_rows);
+    if (rc) return rc;
+    if (!d_cursors) return fail(AIM_EINVAL, "null device buffer");
+    if (n_rows && (!d_requests || !d_text_pos || !d_results || !d_ops || !d_reference || !d_sam || !d_cigar || !d_md))
+        return fail(AIM_EINVAL, "null device buffer");
+    int n = 0;
+    rc = aim_device_count(&n);
+    if (rc) return rc;
+    aim::SamArgs a;
+    memset(&a, 0, sizeof a);
+    a.n_rows = n_rows;
+    a.text_pos = d_text_pos;
+    a.sel = d_sel_or_null;
+    a.res = static_cast<const aim_result_t *>(d_results);
+    a.ops = d_ops;
+    a.ref = d_reference;
+    a.ref_len = ref_len;
+    a.options = options;
+    a.sam = d_sam;
+    a.cigar = d_cigar;
+    a.cigar_cap = cigar_cap;
+    a.md = d_md;
+    a.md_cap = md_cap;
+    a.cursors = d_cursors;
+    if (!n_rows) {
+        HIP_TRY(hipMemsetAsync(d_cursors, 0, 8, (hipStream_t)hip_stream));
+        return AIM_OK;
+    }
+    return enqueue_sam(*params, read_knobs(), a, (hipStream_t)hip_stream);
+}
+
+const char *aim_sam_kernel_name(const aim_params_t *params)
+{
+    if (!params) return "";
+    return sam_use_wave(*params, read_knobs()) ? "sam_wave_kernel" : "sam_lane_kernel";
 }
 
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap)
@@ -2583,6 +2815,7 @@ int align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32_t n
                         aim_mate_t *d_mates, void *d_scratch, size_t scratch_bytes, void *hip_stream)
 {
     const bool ref = is_ref(*params), bt = params->flags & AIM_FLAG_BACKTRACE;
+    if (is_sam(*params)) return fail(AIM_EINVAL, kSamStateless);
     if (n_reads > n_pairs || (n_pairs && !n_reads)) return fail(AIM_EINVAL, "n_reads %u does not fit n_pairs %u", n_reads, n_pairs);
     if (n_pairs && (!d_requests || !d_patterns || !d_read_offsets || !d_results || (bt && !d_ops) ||
                     (ref ? (!d_text_pos_or_null || !d_reference) : !d_texts_or_null)))
@@ -2720,6 +2953,21 @@ int aim_cigar_format(const char *ops, int32_t begin_offset, int32_t end_offset, 
     n += snprintf(out + n, (size_t)(cap - n), "%d%c\n", run, last_op);
     if (n >= cap) return fail(AIM_EINVAL, "cigar buffer too small");
     return n;
+}
+
+int aim_sam_format_cigar(const uint32_t *words, uint32_t n, char *out, int32_t cap)
+{
+    if (!out || cap < 2 || (n && !words)) return fail(AIM_EINVAL, "aim_sam_format_cigar: bad arguments");
+    if (!n) { out[0] = '*'; out[1] = 0; return 1; }
+    int at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t op = words[i] & 0xfu;
+        if (op > 8u) return fail(AIM_EINVAL, "aim_sam_format_cigar: word %u holds op %u", i, op);
+        const int w = snprintf(out + at, (size_t)(cap - at), "%u%c", words[i] >> 4, "MIDNSHP=X"[op]);
+        if (w < 0 || w >= cap - at) return fail(AIM_EINVAL, "aim_sam_format_cigar: output buffer too small");
+        at += w;
+    }
+    return at;
 }
 
 int aim_pack_sequence(const char *seq, int32_t len, int32_t read_size, uint32_t *row)

@@ -119,6 +119,7 @@ struct Knobs {
     int poison_ops = -1;          // AIM_DEBUG_POISON_OPS      fill the ops rows with this byte before every launch (the kernels write ops[begin_offset, end_offset) only)
     int poison_scratch = -1;      // AIM_DEBUG_POISON_SCRATCH  fill scratch with this byte at configure
     int poison_lds = -1;          // AIM_DEBUG_POISON_LDS      fill dynamic LDS with this byte at kernel entry
+    int sam_wave_min = -1;        // AIM_SAM_WAVE_MIN    SAM records: READ_SIZE from which a row gets a whole wavefront (0 = always, large = never)
     bool plan_debug = false;      // AIM_PLAN_DEBUG=1    print the chosen plan to stderr
     // Not a knob but the one fact about the chip every plan needs: compute units of the device the plan is made for
     // (hipDeviceAttributeMultiprocessorCount, read once per device by chip_cus() in aim_capi.hip: 256 on a whole MI355X, 128 / 64 / 32

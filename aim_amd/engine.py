@@ -37,7 +37,7 @@ def features():
 
 def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=1, gap=4, backtrace=False,
                 reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None, gap2=None, linear=False,
-                w32=False, bidir=False, ref_texts=False, read_groups=False, escalate=False, mate_pairs=False):
+                w32=False, bidir=False, ref_texts=False, read_groups=False, escalate=False, mate_pairs=False, sam=False):
     """`gap` is the launchers' single NW gap cost (run-nw-pim-wram.py: -DGAP_I = -DGAP_D); `gap_i` / `gap_d` set the two macros of
     nw.c:67-153 apart (NW/DPU-WRAM/common/common.h GAP_I, GAP_D). `ends_free=(PB, PE, TB, TE)`: ends-free WFA (AIM_FLAG_ENDSFREE);
     returns an EndsFreeParams then, which every call below accepts like Params. `gap2=(O2, E2)`: dual-cost gap-affine WFA
@@ -50,7 +50,8 @@ def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=
     everything. `escalate=True`: WFA on a lane kernel at a low cap, the flag-less plan over the pairs that come back over it
     (AIM_FLAG_WFA_ESCALATE); results equal the flag-less ones; global gap-affine WFA without w32, bidir and read_groups.
     `mate_pairs=True`: reads 2m and 2m + 1 of a read-groups batch are mates and the device picks the best consistent pair of
-    candidates (AIM_FLAG_MATE_PAIRS); needs read_groups and ref_texts."""
+    candidates (AIM_FLAG_MATE_PAIRS); needs read_groups and ref_texts. `sam=True`: SAM-ready records (POS, CIGAR, NM, MD) for every
+    row of a submitted batch (AIM_FLAG_SAM_FIELDS); needs ref_texts and backtrace, not with genasm or res8."""
     a = ALGO_BY_NAME[algo] if isinstance(algo, str) else algo
     gap_i = gap if gap_i is None else gap_i
     gap_d = gap if gap_d is None else gap_d
@@ -62,6 +63,13 @@ def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=
             if not given:
                 raise ValueError("mate_pairs needs %s" % name)
         flags |= FLAG_MATE_PAIRS
+    if sam:
+        for name, given in (("ref_texts", ref_texts), ("backtrace", backtrace)):
+            if not given:
+                raise ValueError("sam needs %s" % name)
+        if a == ALGO_BY_NAME["genasm"] or res8:
+            raise ValueError("sam cannot be combined with %s" % ("res8" if res8 else "genasm"))
+        flags |= capi.FLAG_SAM_FIELDS
     if escalate:
         if a != ALGO_WFA:
             raise ValueError("escalate needs wfa")
@@ -389,6 +397,39 @@ def align_device_mates(params, n_pairs, n_reads, d_requests, d_patterns, d_text_
                                                   scratch_bytes, stream))
 
 
+def sam_device(params, n_rows, d_requests, d_text_pos, d_sel, d_results, d_ops, d_reference, ref_len, options, d_sam, d_cigar, cigar_cap,
+               d_md, md_cap, d_cursors, stream=None):
+    """aim_sam_device on device pointers (integers, e.g. torch's data_ptr(); None = NULL): SAM records of rows that already live on the
+    device, after any align_device* call with backtrace. d_sel = None: row r is candidate r. d_cursors: 2 dwords, zeroed by the call;
+    afterwards the CIGAR words and MD bytes the batch needed. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_sam_device(params_ref(params), n_rows, d_requests, d_text_pos, d_sel, d_results, d_ops, d_reference, ref_len,
+                                          options, d_sam, d_cigar, cigar_cap, d_md, md_cap, d_cursors, stream))
+
+
+def sam_kernel_name(params):
+    """aim_sam_kernel_name: "sam_lane_kernel" or "sam_wave_kernel", the record kernel a launch with these params takes right now."""
+    return capi.load().aim_sam_kernel_name(params_ref(params)).decode()
+
+
+def sam_format_cigar(words):
+    """aim_sam_format_cigar: BAM CIGAR words -> the SAM string ("*" for none)."""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    buf = C.create_string_buffer(12 * len(w) + 2)
+    n = capi.check(capi.load().aim_sam_format_cigar(w.ctypes.data if len(w) else None, len(w), buf, len(buf)))
+    return buf.raw[:n].decode()
+
+
+def sam_strings(sam, cigar, md):
+    """Per row of `sam` (capi.SAM_DTYPE) the pair (CIGAR string, MD string) from the word and byte buffers; ("*", "") for an unmapped
+    row or one marked SAM_OVERFLOW."""
+    md = np.asarray(md, dtype=np.uint8)
+    out = []
+    for r in sam:
+        co, nc, mo, ml = int(r["cigar_offset"]), int(r["n_cigar"]), int(r["md_offset"]), int(r["md_len"])
+        out.append((sam_format_cigar(cigar[co:co + nc]), md[mo:mo + ml].tobytes().decode("latin-1")))
+    return out
+
+
 def to_request8(req):
     """aim_request_t[] -> aim_request8_t[] (the reference's own 8-byte WFA request_t; AIM_FLAG_REQ8)."""
     out = np.zeros(len(req), dtype=REQUEST8_DTYPE)
@@ -567,6 +608,11 @@ class DeviceSet:
         self.max_pairs = max_pairs_per_device
         self._inflight = {}
 
+    def sam_capacity(self, max_cigar_words, max_md_bytes):
+        """aim_set_sam_capacity: the per-slot device buffers of the SAM records (after configure_slots, before the first submit
+        with sam=)."""
+        capi.check(self.lib.aim_set_sam_capacity(self.handle, int(max_cigar_words), int(max_md_bytes)))
+
     def set_reference(self, seq):
         """aim_set_reference: upload `seq` (bytes or a uint8 array, taken verbatim) to every device of the set; replaces the
         previous reference. Batches then name their texts by text_pos (AIM_FLAG_REF_TEXTS)."""
@@ -575,26 +621,29 @@ class DeviceSet:
         self.ref_len = len(arr)
 
     def submit(self, device, slot, req, pat=None, txt=None, packed=None, want_ops=False, cigar_runs_cap=0, text_pos=None,
-               read_offsets=None, mates=None):
+               read_offsets=None, mates=None, sam=None, want_res=None):
         """aim_set_submit: ASCII rows (pat, txt) or a packed batch (pack_batch(...)); results / ops / compact CIGAR buffers
         are allocated here and returned by wait(). text_pos (AIM_FLAG_REF_TEXTS): the texts are windows of the reference; pass
         pat (or packed = pack_batch(req, pat, None)) and no texts. read_offsets (AIM_FLAG_READ_GROUPS): req and the texts are per
         candidate, pat holds one row per read; wait() returns one row per read and "best" (capi.BEST_DTYPE). mates = (min_span,
         max_span, unpaired_penalty) (AIM_FLAG_MATE_PAIRS, with read_offsets and text_pos): reads 2m and 2m + 1 are mates; wait() also
-        returns "mates" (capi.MATE_DTYPE, one row per read pair) next to "best", which stays the independent selection."""
+        returns "mates" (capi.MATE_DTYPE, one row per read pair) next to "best", which stays the independent selection.
+        sam = (cigar_cap, md_cap, options) (AIM_FLAG_SAM_FIELDS): wait() also returns "sam" (capi.SAM_DTYPE, one record per output
+        row), "sam_cigar" (BAM words) and "sam_md" (bytes); want_res=False then sends no result rows back."""
         if (self.params.flags & FLAG_REQ8) and req.dtype != REQUEST8_DTYPE:
             req = to_request8(req)
         req = np.ascontiguousarray(req)
         n, rs = len(req), self.params.read_size
+        sio = capi.BatchIOSam() if (self.params.flags & capi.FLAG_SAM_FIELDS) else None
         if mates is not None:
             if read_offsets is None:
                 raise ValueError("mates needs read_offsets")
-            mio = capi.BatchIOMates()
+            mio = capi.BatchIOMates() if sio is None else sio.mates
             rio = mio.groups
             mio.min_span, mio.max_span, mio.unpaired_penalty = (int(x) for x in mates)
         else:
             mio = None
-            rio = capi.BatchIOGroups() if read_offsets is not None else capi.BatchIORef()
+            rio = sio.mates.groups if sio is not None else (capi.BatchIOGroups() if read_offsets is not None else capi.BatchIORef())
         io = rio.base
         out = {}
         if read_offsets is not None:
@@ -632,14 +681,25 @@ class DeviceSet:
             out["cig"] = np.zeros(n_out, dtype=capi.CIGAR_DTYPE)
             out["runs"] = np.zeros(cigar_runs_cap, dtype=np.uint32)
             io.cigars, io.runs, io.runs_cap = out["cig"].ctypes.data, out["runs"].ctypes.data, cigar_runs_cap
-        if not cigar_runs_cap or want_ops:
+        if sam is not None:
+            if sio is None:
+                raise ValueError("sam= needs params made with sam=True")
+            ccap, mcap, opts = (int(x) for x in sam)
+            out["sam"] = np.zeros(n_out, dtype=capi.SAM_DTYPE)
+            out["sam_cigar"] = np.zeros(max(ccap, 1), dtype=np.uint32)
+            out["sam_md"] = np.zeros(max(mcap, 1), dtype=np.uint8)
+            sio.sam, sio.sam_cigar, sio.sam_md = out["sam"].ctypes.data, out["sam_cigar"].ctypes.data, out["sam_md"].ctypes.data
+            sio.sam_cigar_cap, sio.sam_md_cap, sio.sam_options = ccap, mcap, opts
+        if want_res is None:
+            want_res = not cigar_runs_cap or want_ops
+        if want_res:
             out["res"] = np.zeros(n_out, dtype=RESULT8_DTYPE if (self.params.flags & FLAG_RES8) else RESULT_DTYPE)
             io.results = out["res"].ctypes.data
         if want_ops:
             out["ops"] = np.zeros((n_out, 2 * rs), dtype=np.uint8)
             io.ops = out["ops"].ctypes.data
         capi.check(self.lib.aim_set_submit(self.handle, device, slot, C.byref(io)))
-        self._inflight[(device, slot)] = (rio if mio is None else mio, keep, out)
+        self._inflight[(device, slot)] = (sio if sio is not None else (rio if mio is None else mio), keep, out)
 
     def wait(self, device, slot, check=True):
         io, keep, out = self._inflight.pop((device, slot), (None, None, {}))   # nothing in flight: the library reports AIM_ESTATE

@@ -200,6 +200,55 @@ typedef struct aim_affine2p_params {
  * the flag is AIM_EINVAL, the message naming the missing flag.
  * Check aim_features() & AIM_FEATURE_MATE_PAIRS first: older libraries ignore unknown flags. */
 #define AIM_FLAG_MATE_PAIRS 0x2000u
+/* AIM_FLAG_SAM_FIELDS (needs AIM_FLAG_REF_TEXTS and AIM_FLAG_BACKTRACE; not with AIM_ALGO_GENASM or AIM_FLAG_RES8): the device turns every
+ * final ops row into a SAM-ready record -- an aim_sam_t plus BAM CIGAR words and MD bytes -- in one pass over the rows and the resident
+ * reference (aim_set_submit with an aim_batch_io_sam_t; aim_sam_device is the same kernel without the flag, on rows already on a device).
+ * THE CONVENTIONS:
+ *   Ops mapping. AIM ops are 'M' (match), 'X' (mismatch), 'I' (consumes a text base) and 'D' (consumes a pattern base). The text is the
+ *   reference: AIM 'I' is SAM 'D' and AIM 'D' is SAM 'I'.
+ *   Orientation. Records are on the forward strand of the reference. A strand-0 window's ops are taken in row order, a strand-1 window's
+ *   (text_pos bit 63) in reverse order. Reference bases are read from the forward reference at their forward position: no complement, and
+ *   the read's bases are never needed ('M' / 'X' already say match / mismatch).
+ *   Terminal runs. At each end of ops[begin_offset, end_offset) every op that is not 'M' or 'X' is peeled (terminal 'I' and 'D' runs may
+ *   alternate). Peeled 'D' bases (read only) become ONE soft clip at that end; peeled 'I' bases (reference only) are dropped and move the
+ *   position. The rule is the same with and without AIM_FLAG_ENDSFREE: a record neither starts nor ends with SAM I or D.
+ *   Fields. pos is the 0-based forward position of the first reference base the remaining ops consume: the window start plus the
+ *   reference bases dropped at the row's beginning (strand 0) or at the row's END (strand 1). ref_span counts the reference bases the
+ *   remaining ops consume, nm their 'X' bases plus their inner 'I' and 'D' bases.
+ *   CIGAR. BAM words (len << 4) | op with M 0, I 1, D 2, S 4, = 7, X 8; adjacent equal ops are merged. 'M' and 'X' both give M unless
+ *   AIM_SAM_EQX is set in sam_options (then = and X).
+ *   MD. samtools' rule: a decimal match count (possibly 0) before every mismatch and before every deletion; a mismatch writes the
+ *   reference byte verbatim, a deletion '^' plus its reference bytes; a final count ends the string; read insertions and clips neither
+ *   appear nor reset the count. No terminating NUL.
+ *   Unmapped rows. A row whose status is not AIM_PAIR_OK, whose ops range is empty, which is a WFA row over the cap (score
+ *   MAX_SCORE + 1), of which nothing remains after peeling, or whose candidate is UINT32_MAX gets flags = AIM_SAM_UNMAPPED, n_cigar = 0,
+ *   md_len = 0, ref_span = 0, nm = 0 and pos = the window start (0 without a candidate).
+ *   Capacity. A row whose words or bytes do not fit gets AIM_SAM_OVERFLOW in status, n_cigar = md_len = 0 and every other field
+ *   intact; nothing of it is written. Placement in the two buffers depends on scheduling: each record carries its own offsets, and the
+ *   content they address and every other field do not depend on the grid or on the AIM_DEBUG_POISON_* knobs.
+ * Every other output of the call (result rows, ops ranges, compact headers and runs, best, mates) equals that of the same call without the
+ * flag. Combines with AIM_FLAG_READ_GROUPS / AIM_FLAG_MATE_PAIRS (rows are reads, record r follows sel[r]) and with ENDSFREE, AFFINE2P,
+ * LINEAR, WFA_W32, WFA_BIDIR, REDUCE, WFA_ESCALATE, REQ8, packed read rows and compact runs. Under the flag the ops rows stay on the
+ * device, so a plan that would fuse the run output is not used; the plan line gains " sam=1". aim_set_push_ref, aim_set_launch and
+ * aim_set_pull refuse the flag (the records need the submit struct), and so do aim_align_device, aim_align_device_ref,
+ * aim_align_device_groups and aim_align_device_mates (AIM_EINVAL: run them without the flag, then aim_sam_device over their rows).
+ * aim_plan_describe, aim_scratch_bytes and aim_kernel_name accept it and describe the plan aim_set_submit follows.
+ * Check aim_features() & AIM_FEATURE_SAM_FIELDS first: older libraries ignore unknown flags. */
+#define AIM_FLAG_SAM_FIELDS 0x4000u
+#define AIM_SAM_EQX 0x1u            /* sam_options / options: '=' and 'X' instead of 'M' */
+#define AIM_SAM_REVERSE 0x10u       /* aim_sam_t.flags: SAM's own FLAG bits */
+#define AIM_SAM_UNMAPPED 0x4u
+#define AIM_SAM_OVERFLOW 0x100u     /* aim_sam_t.status bit: the CIGAR or the MD buffer was too small for this row */
+typedef struct aim_sam {            /* 48 B per row */
+    uint32_t idx; int32_t score;    /* the row's */
+    uint64_t pos;
+    uint32_t ref_span, nm;
+    uint32_t cigar_offset, n_cigar; /* words in the CIGAR buffer */
+    uint32_t md_offset, md_len;     /* bytes in the MD buffer */
+    uint16_t flags;                 /* AIM_SAM_REVERSE | AIM_SAM_UNMAPPED */
+    uint16_t status;                /* AIM_PAIR_* | AIM_SAM_OVERFLOW */
+    uint32_t pad;                   /* 0 */
+} aim_sam_t;
 
 /* Per-pair descriptor: byte-compatible with the NW/SWG request_t
  * (NW/DPU-WRAM/common/common.h:114-120).  The WFA variant of the reference
@@ -253,6 +302,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_READ_GROUPS 0x40u /* AIM_FLAG_READ_GROUPS is honoured */
 #define AIM_FEATURE_WFA_ESCALATE 0x80u /* AIM_FLAG_WFA_ESCALATE is honoured */
 #define AIM_FEATURE_MATE_PAIRS 0x100u /* AIM_FLAG_MATE_PAIRS is honoured */
+#define AIM_FEATURE_SAM_FIELDS 0x200u /* AIM_FLAG_SAM_FIELDS is honoured; aim_sam_device and aim_sam_format_cigar exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -416,6 +466,22 @@ typedef struct aim_batch_io_mates {
  * 0 <= min_span <= max_span < 2^62, or a negative penalty. aim_set_submit runs it after aim_groups_check, before anything is enqueued. */
 int aim_mates_check(uint32_t n_reads, int64_t min_span, int64_t max_span, int32_t unpaired_penalty);
 
+/* AIM_FLAG_SAM_FIELDS: aim_set_submit reads past `mates` (only with the flag; the groups and mates members are read only under their own
+ * flags). base.results, ops and cigars may each be NULL when sam is given. aim_set_wait copies back the n records and exactly the words
+ * and bytes that were written. */
+typedef struct aim_batch_io_sam {
+    aim_batch_io_mates_t mates;    /* @0, 184 B: unchanged meaning */
+    aim_sam_t *sam;                /* out: [n_pairs], or [n_reads] under AIM_FLAG_READ_GROUPS */
+    uint32_t *sam_cigar;           /* out: BAM CIGAR words */
+    uint32_t sam_cigar_cap;        /* capacity of sam_cigar[], in words */
+    char *sam_md;                  /* out: MD bytes */
+    uint32_t sam_md_cap;           /* capacity of sam_md[], in bytes */
+    uint32_t sam_options;          /* AIM_SAM_EQX */
+} aim_batch_io_sam_t;
+/* Sizes the per-slot device buffers of the records: call after aim_set_configure_slots (a re-configure drops them). A submit with the
+ * flag before this call returns AIM_ESTATE. A batch may use less (sam_cigar_cap / sam_md_cap), never more. */
+int aim_set_sam_capacity(aim_set_t *set, uint32_t max_cigar_words, uint32_t max_md_bytes);
+
 /* aim_set_configure with `slots` (1..4) buffer sets per device; max_raw_pairs bounds n_raw of a packed batch
  * (0 = packed input not used), max_runs the run buffer of a compact-CIGAR batch (0 = not used). */
 int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t max_pairs_per_device, uint32_t slots,
@@ -484,6 +550,24 @@ int aim_align_device_mates(const aim_params_t *params, uint32_t n_pairs, uint32_
                            const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, int64_t min_span,
                            int64_t max_span, int32_t unpaired_penalty, aim_mate_t *d_mates, void *d_scratch, size_t scratch_bytes,
                            void *hip_stream);
+/* The kernel of AIM_FLAG_SAM_FIELDS on rows that already live on the device, after any aim_align_device* call with AIM_FLAG_BACKTRACE
+ * (params are that call's; the flag itself is not needed). Row r uses text_pos entry d_sel[r] -- entry r when d_sel is NULL; UINT32_MAX
+ * gives an unmapped record -- while d_results[n_rows] and d_ops[n_rows][2 * read_size] are indexed by row. d_requests (aim_request_t[] or,
+ * with AIM_FLAG_REQ8, aim_request8_t[]) is taken for symmetry with the other entry points: the records derive from the ops ranges alone.
+ * d_cursors holds 2 dwords, zeroed by the call: afterwards {CIGAR words, MD bytes} the batch needed (which may exceed the capacities).
+ * AIM_EINVAL (with a message) for AIM_ALGO_GENASM (its windowed walk is unpinned and begin_offset = 0 is another contract), without
+ * AIM_FLAG_BACKTRACE, with AIM_FLAG_RES8, and when n_rows * (4 * read_size + 10) >= 2^32 (offsets are 32-bit: split the batch; aim_set_submit applies the
+ * same bound to n_pairs before anything is enqueued). Every reference
+ * read is clamped to [0, ref_len) and every ops read to the row: rows that disagree with their lengths give an unspecified record,
+ * never a fault. The call only enqueues work on hip_stream. */
+int aim_sam_device(const aim_params_t *params, uint32_t n_rows, const void *d_requests, const uint64_t *d_text_pos,
+                   const uint32_t *d_sel_or_null, const void *d_results, const char *d_ops, const char *d_reference, uint64_t ref_len,
+                   uint32_t options, aim_sam_t *d_sam, uint32_t *d_cigar, uint32_t cigar_cap, char *d_md, uint32_t md_cap,
+                   uint32_t *d_cursors, void *hip_stream);
+/* Which of the two record kernels (sam_fields.hpp) a launch with these params takes in this process right now: "sam_lane_kernel" (one row
+ * per lane) or "sam_wave_kernel" (one row per wavefront), by read_size; the names match the rocprofv3 kernel-trace prefixes. A set freezes
+ * the choice at aim_set_configure like every other AIM_* switch. */
+const char *aim_sam_kernel_name(const aim_params_t *params);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
@@ -499,6 +583,9 @@ int aim_launcher_sizes(int32_t algo, int32_t read_length, double error, int32_t 
 /* edit_cigar_print (host.c:69-89): RLE of ops[begin,end) + '\n' into out;
  * returns bytes written or AIM_EINVAL if cap is too small. */
 int aim_cigar_format(const char *ops, int32_t begin_offset, int32_t end_offset, char *out, int32_t cap);
+/* BAM CIGAR words (aim_sam_t) as a SAM CIGAR string, NUL-terminated: "*" for n = 0. Returns the bytes written (without the NUL) or
+ * AIM_EINVAL when cap is too small or a word holds an op outside MIDNSHP=X. */
+int aim_sam_format_cigar(const uint32_t *words, uint32_t n, char *out, int32_t cap);
 /* Seeded synthetic pairs (DESIGN.md "Synthetic data"): pattern = len uniform
  * ACGT bases; text = pattern after ceil(len*error) sequential uniform
  * substitute/insert/delete edits.  Pair i depends only on (seed, first_idx+i). */
