@@ -36,6 +36,9 @@ FLAG_MATE_PAIRS = 0x2000     # paired-end selection over a read-groups batch of 
 FEATURE_MATE_PAIRS = 0x100   # aim_features(): AIM_FLAG_MATE_PAIRS is honoured
 FLAG_SAM_FIELDS = 0x4000     # SAM-ready records (POS, CIGAR, NM, MD) from the final ops rows and the resident reference
 FEATURE_SAM_FIELDS = 0x200   # aim_features(): AIM_FLAG_SAM_FIELDS is honoured
+FLAG_TOP_HITS = 0x8000       # the max_hits best candidates of every read of a read-groups batch, each a full row
+FEATURE_TOP_HITS = 0x400     # aim_features(): AIM_FLAG_TOP_HITS is honoured
+TOP_HITS_MAX = 8             # max_hits is 1..TOP_HITS_MAX
 SAM_EQX, SAM_REVERSE, SAM_UNMAPPED, SAM_OVERFLOW = 0x1, 0x10, 0x4, 0x100   # sam_options; aim_sam_t.flags (SAM's own bits); aim_sam_t.status bit
 MATE_PROPER = 1              # aim_mate_t.flags: the chosen candidates are a proper combination
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
@@ -142,6 +145,12 @@ class BatchIOSam(C.Structure):
                 ("sam_md_cap", C.c_uint32), ("sam_options", C.c_uint32)]
 
 
+class BatchIOHits(C.Structure):
+    """aim_batch_io_hits_t: BatchIOSam at offset 0 (its groups members are read, its mates and sam members ignored), then the hit rows
+    (AIM_FLAG_TOP_HITS); aim_set_submit receives a pointer to `sam.mates.groups.base`."""
+    _fields_ = [("sam", BatchIOSam), ("max_hits", C.c_uint32), ("pad", C.c_uint32), ("hit_offsets", C.c_void_p), ("hit_pair", C.c_void_p)]
+
+
 # every symbol include/aim_hip.h declares: name -> (restype, argtypes)
 _VP, _U32, _I32 = C.c_void_p, C.c_uint32, C.c_int32
 SYMBOLS = {
@@ -184,6 +193,9 @@ SYMBOLS = {
     "aim_mates_check": (C.c_int, [_U32, C.c_int64, C.c_int64, _I32]),
     "aim_align_device_mates": (C.c_int, [C.POINTER(Params), _U32, _U32, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, C.c_int64,
                                          C.c_int64, _I32, _VP, _VP, C.c_size_t, _VP]),
+    "aim_hits_offsets": (C.c_int, [_U32, _VP, _U32, _VP, C.POINTER(_U32)]),
+    "aim_align_device_hits": (C.c_int, [C.POINTER(Params), _U32, _U32, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _U32, _VP, _U32,
+                                        _VP, _VP, C.c_size_t, _VP]),
     "aim_set_sam_capacity": (C.c_int, [_VP, _U32, _U32]),
     "aim_sam_device": (C.c_int, [C.POINTER(Params), _U32, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _U32, _VP, _VP, _U32, _VP, _U32, _VP, _VP]),
     "aim_sam_format_cigar": (C.c_int, [_VP, _U32, _VP, _I32]),

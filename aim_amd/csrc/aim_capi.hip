@@ -33,6 +33,7 @@
 #include "dp_group.hpp"
 #include "batch_io.hpp"
 #include "groups.hpp"
+#include "hits.hpp"
 #include "mates.hpp"
 #include "sam_fields.hpp"
 #include "genasm_wave.hpp"
@@ -263,6 +264,8 @@ inline bool is_escalate(const aim_params_t &p) { return (p.flags & AIM_FLAG_WFA_
 // AIM_FLAG_SAM_FIELDS: SAM-ready records from the final ops rows (sam_fields.hpp); one more kernel behind the batch, no plan depends on it
 // beyond keeping the ops rows on the device (no fused run output).
 inline bool is_sam(const aim_params_t &p) { return (p.flags & AIM_FLAG_SAM_FIELDS) != 0; }
+// AIM_FLAG_TOP_HITS: the N best candidates per read (hits.hpp); the rows behind the selection are hits, not reads.
+inline bool is_hits(const aim_params_t &p) { return (p.flags & AIM_FLAG_TOP_HITS) != 0; }
 // The params as this library keeps them: room for either extension, and the extension copied only when a flag says it exists.
 union XParams {
     aim_params_t base;
@@ -289,6 +292,12 @@ int validate_params(const aim_params_t &p)
     if (is_mates(p)) {   // the positions it pairs by are the windows' text_pos
         if (!is_groups(p)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS needs AIM_FLAG_READ_GROUPS");
         if (!is_ref(p)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS needs AIM_FLAG_REF_TEXTS");
+    }
+    if (is_hits(p)) {
+        if (!is_groups(p)) return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS needs AIM_FLAG_READ_GROUPS");
+        if (is_mates(p)) return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS cannot be combined with AIM_FLAG_MATE_PAIRS (a follow-up)");
+        if (is_sam(p))
+            return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS cannot be combined with AIM_FLAG_SAM_FIELDS (a follow-up: aim_sam_device works on hit rows with d_sel = d_hit_pair)");
     }
     if (is_sam(p)) {   // the records are on the reference's coordinates and come from the ops rows
         if (p.flags & AIM_FLAG_RES8) return fail(AIM_EINVAL, "AIM_FLAG_SAM_FIELDS cannot be combined with AIM_FLAG_RES8");
@@ -1160,15 +1169,17 @@ struct GroupsPlan {
     bool pass2;
     bool mates;             // AIM_FLAG_MATE_PAIRS: mate_select_kernel after the independent selection
     bool sam;               // AIM_FLAG_SAM_FIELDS: the reads' records after the second pass
+    bool hits;              // AIM_FLAG_TOP_HITS: hit_select_kernel after the selection; the rows behind it are hits
     size_t plan_bytes;      // the larger of the two plans' scratch (both made for n_pairs)
     // aim_align_device_groups: the rest of its scratch, offsets from the base (256-B aligned)
     size_t cand_p_at, cand_t_at, res1_at, map_at, sel_at, req2_at, pat2_at, txt2_at, total;
     size_t best_at;         // aim_align_device_mates: the independent selection's rows when the caller keeps none (the last region)
+    size_t hit_at;          // aim_align_device_hits: the hit list when the caller keeps none (the last region)
 };
 inline XParams groups_pass_params(const aim_params_t &p, uint32_t drop)
 {
     XParams x = copy_params(p);
-    x.base.flags &= ~(AIM_FLAG_READ_GROUPS | AIM_FLAG_MATE_PAIRS | AIM_FLAG_SAM_FIELDS | drop);
+    x.base.flags &= ~(AIM_FLAG_READ_GROUPS | AIM_FLAG_MATE_PAIRS | AIM_FLAG_SAM_FIELDS | AIM_FLAG_TOP_HITS | drop);
     return x;
 }
 
@@ -1178,12 +1189,12 @@ int describe_groups(const GroupsPlan &g, uint32_t n_pairs, uint32_t n_reads, uin
     describe_plan(g.p1, g.x1.base, n_pairs, budget, a, sizeof a);
     if (g.pass2) describe_plan(g.p2, g.x2.base, n_reads, budget, b, sizeof b);
     else snprintf(b, sizeof b, "no second pass n=%u", n_reads);
-    return snprintf(out, cap, "%s | %s groups=1%s%s", a, b, g.mates ? " mates=1" : "", g.sam ? " sam=1" : "");
+    return snprintf(out, cap, "%s | %s groups=1%s%s%s", a, b, g.mates ? " mates=1" : "", g.sam ? " sam=1" : "", g.hits ? " hits=1" : "");
 }
 
 // Both passes planned for n_pairs candidates (the worst case n_reads = n_pairs for pass 2) and the stateless scratch layout:
 // [plans | candidate pattern rows | candidate text rows (REF_TEXTS) | pass-1 results | candidate -> read map | sel | pass-2 requests,
-//  pattern rows, text rows (BACKTRACE) | aim_best_t rows (MATE_PAIRS)]
+//  pattern rows, text rows (BACKTRACE) | aim_best_t rows (MATE_PAIRS) | hit list (TOP_HITS)]
 int make_groups_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &kn, uint64_t budget, GroupsPlan *g)
 {
     int rc = validate_params(p);
@@ -1196,6 +1207,7 @@ int make_groups_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &
     g->pass2 = (p.flags & AIM_FLAG_BACKTRACE) != 0;
     g->mates = is_mates(p);
     g->sam = is_sam(p);
+    g->hits = is_hits(p);
     rc = make_plan(g->x1.base, n_pairs, quiet, budget, &g->p1);
     if (rc) return rc;
     g->plan_bytes = g->p1.scratch_total;
@@ -1217,6 +1229,7 @@ int make_groups_plan(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs &
         g->txt2_at = at; at += al256(rows);
     }
     if (g->mates) { g->best_at = at; at += al256((size_t)n_pairs * sizeof(aim_best_t)); }
+    if (g->hits) { g->hit_at = at; at += al256((size_t)n_pairs * 4); }
     g->total = at;
     if (kn.plan_debug) {
         char line[800];
@@ -1244,10 +1257,13 @@ struct GroupsIo {
     const uint64_t *tpos;        // AIM_FLAG_MATE_PAIRS: the candidates' text_pos [n_pairs] ...
     aim::MateArgs mate;          // ... the pairing parameters (n_mates and lanes are filled in by enqueue_groups) ...
     aim_mate_t *mates;           // ... and the read pairs' rows [n_reads / 2], or nullptr
-    void *req2;                  // [n_reads] pass-2 requests
-    char *pat2, *txt2;           // [n_reads][READ_SIZE]
-    void *res;                   // out [n_reads]
-    char *ops;                   // out [n_reads][2 READ_SIZE] (BACKTRACE)
+    uint32_t n_hits, max_hits;   // AIM_FLAG_TOP_HITS: H hit rows, at most max_hits per read ...
+    const uint32_t *hoff;        // ... hit_offsets [n_reads + 1] ...
+    uint32_t *hit_pair;          // ... and the candidate of every hit row [n_hits]
+    void *req2;                  // [rows] pass-2 requests; rows = n_reads, or n_hits under AIM_FLAG_TOP_HITS (never more than n_pairs)
+    char *pat2, *txt2;           // [rows][READ_SIZE]
+    void *res;                   // out [rows]
+    char *ops;                   // out [rows][2 READ_SIZE] (BACKTRACE)
     void *scratch;               // the plans' region
     size_t scratch_bytes;
 };
@@ -1311,25 +1327,37 @@ int enqueue_groups(const GroupsPlan &g, const Plan &pl1, const Plan &pl2, const 
                            io.roff, io.best, io.sel, io.mates);
         HIP_TRY(hipGetLastError());
     }
+    // the rows behind the selection: the reads' winners, or under AIM_FLAG_TOP_HITS every read's hits in rank order
+    uint32_t rows = nr;
+    const uint32_t *row_cand = io.sel;
+    if (g.hits) {
+        rows = io.n_hits;
+        row_cand = io.hit_pair;
+        if (!rows) return AIM_OK;
+        HIP_TRY(hipMemsetAsync(io.hit_pair, 0, (size_t)rows * 4, stream));   // (rows that wrong hit_offsets leave unwritten keep a valid candidate)
+        hipLaunchKernelGGL(aim::hit_select_kernel, dim3((waves + 3) / 4), dim3(256), 0, stream, io.res1, n, io.roff, nr, io.hoff, io.max_hits,
+                           rows, io.hit_pair);
+        HIP_TRY(hipGetLastError());
+    }
     if (!g.pass2) {
-        hipLaunchKernelGGL(aim::group_results_kernel, dim3((nr + 255) / 256), dim3(256), 0, stream, io.res1, io.sel, nr,
+        hipLaunchKernelGGL(aim::group_results_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, io.res1, row_cand, rows,
                            (int)((p2.flags & AIM_FLAG_RES8) != 0), io.res);
         HIP_TRY(hipGetLastError());
         return AIM_OK;
     }
-    // the winners as a batch of their own: requests, pattern rows (already cut to pattern_len) and text rows gathered by sel
+    // the rows as a batch of their own: requests, pattern rows (already cut to pattern_len) and text rows gathered by candidate
     const uint32_t rq_dw = (uint32_t)((p2.flags & AIM_FLAG_REQ8) ? sizeof(aim_request8_t) : sizeof(aim_request_t)) / 4;
-    hipLaunchKernelGGL(aim::gather_elems_kernel, dim3((unsigned)(((uint64_t)nr * rq_dw + 255) / 256)), dim3(256), 0, stream,
-                       static_cast<const uint32_t *>(io.req), io.sel, nr, rq_dw, static_cast<uint32_t *>(io.req2));
+    hipLaunchKernelGGL(aim::gather_elems_kernel, dim3((unsigned)(((uint64_t)rows * rq_dw + 255) / 256)), dim3(256), 0, stream,
+                       static_cast<const uint32_t *>(io.req), row_cand, rows, rq_dw, static_cast<uint32_t *>(io.req2));
     HIP_TRY(hipGetLastError());
     aim::KArgs k2 = ka;
     k2.p = p2;
-    k2.n_pairs = nr;
+    k2.n_pairs = rows;
     k2.req = static_cast<const aim_request_t *>(io.req2);
-    rc = enqueue_rows(k2, io.cand_p, n, io.sel, nr, 0, io.pat2, stream);
-    if (!rc) rc = enqueue_rows(k2, io.cand_t, n, io.sel, nr, 1, io.txt2, stream);
+    rc = enqueue_rows(k2, io.cand_p, n, row_cand, rows, 0, io.pat2, stream);
+    if (!rc) rc = enqueue_rows(k2, io.cand_t, n, row_cand, rows, 1, io.txt2, stream);
     if (rc) return rc;
-    return launch(pl2, kn, p2, nr, io.req2, io.pat2, io.txt2, io.res, io.ops, io.scratch, io.scratch_bytes, stream, nullptr, aux);
+    return launch(pl2, kn, p2, rows, io.req2, io.pat2, io.txt2, io.res, io.ops, io.scratch, io.scratch_bytes, stream, nullptr, aux);
 }
 
 }  // namespace
@@ -1363,6 +1391,7 @@ struct aim_slot {
     aim_result_t *g_res1 = nullptr;
     aim_best_t *g_best = nullptr;
     aim_mate_t *g_mates = nullptr;   // AIM_FLAG_MATE_PAIRS: [max_pairs / 2]
+    uint32_t *g_hoff = nullptr, *g_hit = nullptr;   // AIM_FLAG_TOP_HITS: hit_offsets [max_pairs + 1], hit_pair [max_pairs]
     // AIM_FLAG_SAM_FIELDS (aim_set_sam_capacity): records, CIGAR words, MD bytes, the two cursors and their pinned host copy
     aim_sam_t *d_sam = nullptr;
     uint32_t *d_samcig = nullptr, *d_samcur = nullptr, *h_samcur = nullptr;
@@ -1414,7 +1443,7 @@ void free_slot(aim_slot &s)
 {
     void *bufs[] = {s.d_req, s.d_pat, s.d_txt, s.d_ops, s.d_res, s.d_scratch, s.d_packP, s.d_packT, s.d_rawidx, s.d_rawP, s.d_rawT,
                     s.d_cig, s.d_runs, s.d_cursor, s.d_rawreq, s.d_rawres, s.d_rawops, s.d_rawcig, s.d_tpos, s.d_reftodo,
-                    s.g_readP, s.g_roff, s.g_map, s.g_sel, s.g_rawslot, s.g_res1, s.g_best, s.g_mates, s.g_req2, s.g_pat2, s.g_txt2,
+                    s.g_readP, s.g_roff, s.g_map, s.g_sel, s.g_rawslot, s.g_res1, s.g_best, s.g_mates, s.g_hoff, s.g_hit, s.g_req2, s.g_pat2, s.g_txt2,
                     s.d_sam, s.d_samcig, s.d_samcur, s.d_sammd};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
@@ -1641,7 +1670,7 @@ int aim_abi_version(void) { return AIM_ABI_VERSION; }
 uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
-           AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS;
+           AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -1739,6 +1768,10 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
             HIP_TRY(hipMalloc((void **)&s.g_res1, (size_t)max_pairs * sizeof(aim_result_t)));
             HIP_TRY(hipMalloc((void **)&s.g_best, (size_t)max_pairs * sizeof(aim_best_t)));
             if (is_mates(*params)) HIP_TRY(hipMalloc((void **)&s.g_mates, ((size_t)max_pairs / 2 + 1) * sizeof(aim_mate_t)));
+            if (is_hits(*params)) {
+                HIP_TRY(hipMalloc((void **)&s.g_hoff, ((size_t)max_pairs + 1) * 4));
+                HIP_TRY(hipMalloc((void **)&s.g_hit, (size_t)max_pairs * 4));
+            }
             if (params->flags & AIM_FLAG_BACKTRACE) {
                 HIP_TRY(hipMalloc(&s.g_req2, (size_t)max_pairs * req_size(*params)));
                 HIP_TRY(hipMalloc((void **)&s.g_pat2, (size_t)max_pairs * rs + 64));
@@ -2017,6 +2050,44 @@ int check_mates(uint32_t n_reads, int64_t min_span, int64_t max_span, int32_t un
     return AIM_OK;
 }
 
+// aim_hits_offsets: the exclusive prefix sum of min(K_r, max_hits)
+int hits_offsets(uint32_t n_reads, const uint32_t *roff, uint32_t max_hits, uint32_t *hoff, uint32_t *n_hits)
+{
+    if (max_hits < 1 || max_hits > AIM_TOP_HITS_MAX)
+        return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: max_hits %u is outside 1..%d", max_hits, AIM_TOP_HITS_MAX);
+    if (!roff || !hoff) return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: null read_offsets or hit_offsets");
+    uint32_t h = 0;
+    for (uint32_t r = 0; r < n_reads; ++r) {
+        hoff[r] = h;
+        h += std::min(roff[r + 1] > roff[r] ? roff[r + 1] - roff[r] : 0u, max_hits);
+    }
+    hoff[n_reads] = h;
+    if (n_hits) *n_hits = h;
+    return AIM_OK;
+}
+
+// AIM_FLAG_TOP_HITS on a slot: the caller's hit_offsets against the CSR (already checked), before anything is enqueued; *n_hits receives H
+int check_hits_io(const aim_batch_io_hits_t *hio, uint32_t n_reads, const uint32_t *roff, uint32_t *n_hits)
+{
+    if (hio->max_hits < 1 || hio->max_hits > AIM_TOP_HITS_MAX)
+        return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: max_hits %u is outside 1..%d", hio->max_hits, AIM_TOP_HITS_MAX);
+    *n_hits = 0;
+    if (!n_reads) return AIM_OK;
+    if (!hio->hit_offsets) return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: null hit_offsets");
+    uint32_t h = 0;
+    for (uint32_t r = 0; r < n_reads; ++r) {
+        if (hio->hit_offsets[r] != h)
+            return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: hit_offsets[%u] = %u, but the hits of read %u start at row %u (aim_hits_offsets)", r,
+                        hio->hit_offsets[r], r, h);
+        h += std::min(roff[r + 1] - roff[r], hio->max_hits);
+    }
+    if (hio->hit_offsets[n_reads] != h)
+        return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: hit_offsets[%u] = %u, but the hits of read %u end at row %u (aim_hits_offsets)", n_reads,
+                    hio->hit_offsets[n_reads], n_reads - 1, h);
+    *n_hits = h;
+    return AIM_OK;
+}
+
 // aim_set_submit under AIM_FLAG_READ_GROUPS
 int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_io_t *io)
 {
@@ -2028,6 +2099,8 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
     const bool packed = io->packed_patterns || io->packed_texts;
     // AIM_FLAG_MATE_PAIRS: io is the base of an aim_batch_io_mates_t
     const aim_batch_io_mates_t *mio = is_mates(p) ? reinterpret_cast<const aim_batch_io_mates_t *>(io) : nullptr;
+    // AIM_FLAG_TOP_HITS: io is the base of an aim_batch_io_hits_t
+    const aim_batch_io_hits_t *hio = is_hits(p) ? reinterpret_cast<const aim_batch_io_hits_t *>(io) : nullptr;
     if (packed && (!ref || io->packed_texts))
         return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS: packed batches need AIM_FLAG_REF_TEXTS (packed explicit texts are a follow-up)");
     if (packed && (!s.d_packP || !s.g_rawslot)) return fail(AIM_EINVAL, "packed batch needs a set configured with max_raw_pairs > 0");
@@ -2044,12 +2117,17 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
     const aim_batch_io_sam_t *sio = nullptr;
     int rc = check_sam_io(set, s, io, &sio);
     if (rc) return rc;
-    if (n && !io->results && !io->cigars && !gio->best && !(mio && mio->mates) && !sio) return fail(AIM_EINVAL, "no output buffer");
+    if (n && !io->results && !io->cigars && !gio->best && !(mio && mio->mates) && !sio && !(hio && hio->hit_pair)) return fail(AIM_EINVAL, "no output buffer");
     if (io->ops && !bt) return fail(AIM_EINVAL, "ops requested without AIM_FLAG_BACKTRACE");
     rc = check_groups(n, nr, gio->read_offsets, nullptr);
     if (rc) return rc;
     if (mio) {
         rc = check_mates(nr, mio->min_span, mio->max_span, mio->unpaired_penalty);
+        if (rc) return rc;
+    }
+    uint32_t rows = nr;   // the batch's output rows: reads, or hits
+    if (hio) {
+        rc = check_hits_io(hio, nr, gio->read_offsets, &rows);
         if (rc) return rc;
     }
     if (packed)   // the side list names reads
@@ -2064,7 +2142,7 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
     const size_t rs = (size_t)p.read_size;
     HIP_TRY(hipSetDevice(d.dev));
     s.io = *io;
-    s.n_pairs = nr;          // aim_set_wait reads n_pairs output rows
+    s.n_pairs = rows;        // aim_set_wait reads n_pairs output rows
     s.n_reads = nr;
     s.io_sam = nullptr;
     s.runs_sent = 0;
@@ -2077,11 +2155,13 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
     g.pass2 = bt;
     g.mates = mio != nullptr;
     g.sam = is_sam(p);
+    g.hits = hio != nullptr;
     auto enqueue = [&]() -> int {
         HIP_TRY(hipEventRecord(s.ev[0], s.stream));
         if (n) {
             HIP_TRY(hipMemcpyAsync(s.d_req, io->requests, (size_t)n * req_size(p), hipMemcpyHostToDevice, s.stream));
             HIP_TRY(hipMemcpyAsync(s.g_roff, gio->read_offsets, ((size_t)nr + 1) * 4, hipMemcpyHostToDevice, s.stream));
+            if (hio) HIP_TRY(hipMemcpyAsync(s.g_hoff, hio->hit_offsets, ((size_t)nr + 1) * 4, hipMemcpyHostToDevice, s.stream));
             if (packed) {
                 HIP_TRY(hipMemcpyAsync(s.d_packP, io->packed_patterns, (size_t)nr * aim::packed_row_dwords(p.read_size) * 4, hipMemcpyHostToDevice, s.stream));
                 if (io->n_raw) {
@@ -2107,7 +2187,7 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
                 if (grc) return grc;
             }
             const Plan pl1 = pass_plan(set, d, s, g.x1.base, n, d.plan);
-            const Plan pl2 = bt ? pass_plan(set, d, s, g.x2.base, nr, d.plan2) : Plan();
+            const Plan pl2 = bt ? pass_plan(set, d, s, g.x2.base, rows, d.plan2) : Plan();
             s.plan_last = pl1;
             s.plan_last2 = pl2;
             GroupsIo gi;
@@ -2135,6 +2215,10 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
                 gi.mate.unpaired_penalty = mio->unpaired_penalty;
             }
             gi.mates = s.g_mates;
+            gi.n_hits = hio ? rows : 0u;
+            gi.max_hits = hio ? hio->max_hits : 0u;
+            gi.hoff = s.g_hoff;
+            gi.hit_pair = s.g_hit;
             gi.req2 = s.g_req2;
             gi.pat2 = s.g_pat2;
             gi.txt2 = s.g_txt2;
@@ -2148,12 +2232,12 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
                 aim::KArgs k2;
                 memset(&k2, 0, sizeof k2);
                 k2.p = g.x2.base;
-                k2.n_pairs = nr;
+                k2.n_pairs = rows;
                 k2.req = static_cast<const aim_request_t *>(s.g_req2);
                 k2.res = static_cast<aim_result_t *>(s.d_res);
                 k2.ops = s.d_ops;
                 HIP_TRY(hipMemsetAsync(s.d_cursor, 0, 4, s.stream));
-                hipLaunchKernelGGL(aim::cigar_rle_kernel, dim3((nr + 63) / 64), dim3(64), 0, s.stream, k2, s.d_cig, s.d_runs,
+                hipLaunchKernelGGL(aim::cigar_rle_kernel, dim3((rows + 63) / 64), dim3(64), 0, s.stream, k2, s.d_cig, s.d_runs,
                                    std::min(io->runs_cap, set->max_runs), s.d_cursor);
                 HIP_TRY(hipGetLastError());
             }
@@ -2170,10 +2254,11 @@ int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_
                 HIP_TRY(hipMemcpyAsync(mio->mates, s.g_mates, (size_t)(nr / 2) * sizeof(aim_mate_t), hipMemcpyDeviceToHost, s.stream));
             if (io->cigars) {
                 HIP_TRY(hipMemcpyAsync(s.h_cursor, s.d_cursor, 4, hipMemcpyDeviceToHost, s.stream));
-                HIP_TRY(hipMemcpyAsync(io->cigars, s.d_cig, (size_t)nr * sizeof(aim_cigar_t), hipMemcpyDeviceToHost, s.stream));
+                HIP_TRY(hipMemcpyAsync(io->cigars, s.d_cig, (size_t)rows * sizeof(aim_cigar_t), hipMemcpyDeviceToHost, s.stream));
             }
-            if (io->results) HIP_TRY(hipMemcpyAsync(io->results, s.d_res, (size_t)nr * res_size(p), hipMemcpyDeviceToHost, s.stream));
-            if (io->ops) HIP_TRY(hipMemcpyAsync(io->ops, s.d_ops, (size_t)nr * 2 * rs, hipMemcpyDeviceToHost, s.stream));
+            if (io->results) HIP_TRY(hipMemcpyAsync(io->results, s.d_res, (size_t)rows * res_size(p), hipMemcpyDeviceToHost, s.stream));
+            if (io->ops) HIP_TRY(hipMemcpyAsync(io->ops, s.d_ops, (size_t)rows * 2 * rs, hipMemcpyDeviceToHost, s.stream));
+            if (hio && hio->hit_pair) HIP_TRY(hipMemcpyAsync(hio->hit_pair, s.g_hit, (size_t)rows * 4, hipMemcpyDeviceToHost, s.stream));
             if (sio) {
                 int src = enqueue_sam_d2h(s, nr);
                 if (src) return src;
@@ -2555,10 +2640,11 @@ int aim_set_plan_describe(const aim_set_t *set, uint32_t device, char *out, size
         g.pass2 = (set->params.flags & AIM_FLAG_BACKTRACE) != 0;
         g.mates = is_mates(set->params);
         g.sam = is_sam(set->params);
+        g.hits = is_hits(set->params);
         g.p1 = s.plan_last;
         g.p2 = s.plan_last2;
         const bool any = s.n_reads != 0;
-        describe_groups(g, any ? s.io.n_pairs : set->max_pairs, any ? s.n_reads : set->max_pairs, d.budget, out, cap);
+        describe_groups(g, any ? s.io.n_pairs : set->max_pairs, any ? s.n_pairs : set->max_pairs, d.budget, out, cap);   // (n_pairs: the output rows)
         return AIM_OK;
     }
     describe_plan(s.plan_last, set->params, s.launched ? s.n_pairs : set->max_pairs, d.budget, out, cap);
@@ -2808,11 +2894,18 @@ int aim_mates_check(uint32_t n_reads, int64_t min_span, int64_t max_span, int32_
 }
 
 namespace {
-// aim_align_device_groups (mate == nullptr) and aim_align_device_mates
+// AIM_FLAG_TOP_HITS: the hit rows of a stateless call
+struct HitArgs {
+    uint32_t max_hits, n_hits;
+    const uint32_t *hoff;
+    uint32_t *hit_pair;      // or nullptr: the hit list lives in the scratch
+};
+
+// aim_align_device_groups (mate == nullptr, hit == nullptr), aim_align_device_mates and aim_align_device_hits
 int align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
                         const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
                         const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, const aim::MateArgs *mate,
-                        aim_mate_t *d_mates, void *d_scratch, size_t scratch_bytes, void *hip_stream)
+                        aim_mate_t *d_mates, const HitArgs *hit, void *d_scratch, size_t scratch_bytes, void *hip_stream)
 {
     const bool ref = is_ref(*params), bt = params->flags & AIM_FLAG_BACKTRACE;
     if (is_sam(*params)) return fail(AIM_EINVAL, kSamStateless);
@@ -2853,6 +2946,10 @@ int align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32_t n
     memset(&gi.mate, 0, sizeof gi.mate);
     if (mate) gi.mate = *mate;
     gi.mates = d_mates;
+    gi.n_hits = hit ? hit->n_hits : 0u;
+    gi.max_hits = hit ? hit->max_hits : 0u;
+    gi.hoff = hit ? hit->hoff : nullptr;
+    gi.hit_pair = !hit ? nullptr : hit->hit_pair ? hit->hit_pair : reinterpret_cast<uint32_t *>(base + g.hit_at);
     gi.req2 = bt ? base + g.req2_at : nullptr;
     gi.pat2 = bt ? base + g.pat2_at : nullptr;
     gi.txt2 = bt ? base + g.txt2_at : nullptr;
@@ -2869,13 +2966,13 @@ int align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32_t n
         rc = enqueue_gather(ka, d_text_pos_or_null, d_reference, ref_len, nullptr, n_pairs, gi.cand_t, stream);
         if (rc) return rc;
     }
-    // pass 2 re-planned for the reads (smaller grids); the n_pairs plan where that would not fit the plans' region
+    // pass 2 re-planned for its rows (smaller grids); the n_pairs plan where that would not fit the plans' region
     Plan pl2 = g.p2;
     if (bt) {
         Plan q;
         aim::Knobs quiet = kn;
         quiet.plan_debug = false;
-        if (!make_plan(g.x2.base, n_reads, quiet, budget, &q) && q.scratch_total <= g.plan_bytes) pl2 = q;
+        if (!make_plan(g.x2.base, hit ? hit->n_hits : n_reads, quiet, budget, &q) && q.scratch_total <= g.plan_bytes) pl2 = q;
     }
     return enqueue_groups(g, g.p1, pl2, kn, gi, stream, nullptr);
 }
@@ -2889,8 +2986,34 @@ int aim_align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32
     if (!params) return fail(AIM_EINVAL, "params is NULL");
     if (!is_groups(*params)) return fail(AIM_EINVAL, "aim_align_device_groups needs AIM_FLAG_READ_GROUPS");
     if (is_mates(*params)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS is set: use aim_align_device_mates");
+    if (is_hits(*params)) return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS is set: use aim_align_device_hits");
     return align_device_groups(params, n_pairs, n_reads, d_requests, d_patterns, d_texts_or_null, d_text_pos_or_null, d_reference, ref_len,
-                               d_read_offsets, d_results, d_ops, d_best, nullptr, nullptr, d_scratch, scratch_bytes, hip_stream);
+                               d_read_offsets, d_results, d_ops, d_best, nullptr, nullptr, nullptr, d_scratch, scratch_bytes, hip_stream);
+}
+
+int aim_hits_offsets(uint32_t n_reads, const uint32_t *read_offsets, uint32_t max_hits, uint32_t *hit_offsets, uint32_t *n_hits)
+{
+    return hits_offsets(n_reads, read_offsets, max_hits, hit_offsets, n_hits);
+}
+
+int aim_align_device_hits(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
+                          const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
+                          const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, uint32_t max_hits,
+                          const uint32_t *d_hit_offsets, uint32_t n_hits, uint32_t *d_hit_pair, void *d_scratch, size_t scratch_bytes,
+                          void *hip_stream)
+{
+    if (!params) return fail(AIM_EINVAL, "params is NULL");
+    if (!is_hits(*params)) return fail(AIM_EINVAL, "aim_align_device_hits needs AIM_FLAG_TOP_HITS");
+    int rc = validate_params(*params);   // (names a missing AIM_FLAG_READ_GROUPS, or AIM_FLAG_MATE_PAIRS / AIM_FLAG_SAM_FIELDS)
+    if (rc) return rc;
+    if (max_hits < 1 || max_hits > AIM_TOP_HITS_MAX)
+        return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: max_hits %u is outside 1..%d", max_hits, AIM_TOP_HITS_MAX);
+    if (n_hits > n_pairs || n_hits < n_reads)
+        return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: n_hits %u does not fit n_reads %u and n_pairs %u (aim_hits_offsets)", n_hits, n_reads, n_pairs);
+    if (n_pairs && !d_hit_offsets) return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: null d_hit_offsets");
+    const HitArgs ha{max_hits, n_hits, d_hit_offsets, d_hit_pair};
+    return align_device_groups(params, n_pairs, n_reads, d_requests, d_patterns, d_texts_or_null, d_text_pos_or_null, d_reference, ref_len,
+                               d_read_offsets, d_results, d_ops, d_best, nullptr, nullptr, &ha, d_scratch, scratch_bytes, hip_stream);
 }
 
 int aim_align_device_mates(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
@@ -2912,7 +3035,7 @@ int aim_align_device_mates(const aim_params_t *params, uint32_t n_pairs, uint32_
     ma.max_span = max_span;
     ma.unpaired_penalty = unpaired_penalty;
     return align_device_groups(params, n_pairs, n_reads, d_requests, d_patterns, nullptr, d_text_pos_or_null, d_reference, ref_len,
-                               d_read_offsets, d_results, d_ops, d_best, &ma, d_mates, d_scratch, scratch_bytes, hip_stream);
+                               d_read_offsets, d_results, d_ops, d_best, &ma, d_mates, nullptr, d_scratch, scratch_bytes, hip_stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -37,7 +37,7 @@ def features():
 
 def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=1, gap=4, backtrace=False,
                 reduce=False, swg_w16=False, req8=False, res8=False, gap_i=None, gap_d=None, ends_free=None, gap2=None, linear=False,
-                w32=False, bidir=False, ref_texts=False, read_groups=False, escalate=False, mate_pairs=False, sam=False):
+                w32=False, bidir=False, ref_texts=False, read_groups=False, escalate=False, mate_pairs=False, sam=False, top_hits=False):
     """`gap` is the launchers' single NW gap cost (run-nw-pim-wram.py: -DGAP_I = -DGAP_D); `gap_i` / `gap_d` set the two macros of
     nw.c:67-153 apart (NW/DPU-WRAM/common/common.h GAP_I, GAP_D). `ends_free=(PB, PE, TB, TE)`: ends-free WFA (AIM_FLAG_ENDSFREE);
     returns an EndsFreeParams then, which every call below accepts like Params. `gap2=(O2, E2)`: dual-cost gap-affine WFA
@@ -51,7 +51,9 @@ def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=
     (AIM_FLAG_WFA_ESCALATE); results equal the flag-less ones; global gap-affine WFA without w32, bidir and read_groups.
     `mate_pairs=True`: reads 2m and 2m + 1 of a read-groups batch are mates and the device picks the best consistent pair of
     candidates (AIM_FLAG_MATE_PAIRS); needs read_groups and ref_texts. `sam=True`: SAM-ready records (POS, CIGAR, NM, MD) for every
-    row of a submitted batch (AIM_FLAG_SAM_FIELDS); needs ref_texts and backtrace, not with genasm or res8."""
+    row of a submitted batch (AIM_FLAG_SAM_FIELDS); needs ref_texts and backtrace, not with genasm or res8. `top_hits=True`: the
+    max_hits best candidates of every read of a read-groups batch, each a full row (AIM_FLAG_TOP_HITS); needs read_groups, not with
+    mate_pairs or sam."""
     a = ALGO_BY_NAME[algo] if isinstance(algo, str) else algo
     gap_i = gap if gap_i is None else gap_i
     gap_d = gap if gap_d is None else gap_d
@@ -70,6 +72,13 @@ def make_params(algo, max_score, read_size, match=0, mismatch=3, gap_o=4, gap_e=
         if a == ALGO_BY_NAME["genasm"] or res8:
             raise ValueError("sam cannot be combined with %s" % ("res8" if res8 else "genasm"))
         flags |= capi.FLAG_SAM_FIELDS
+    if top_hits:
+        if not read_groups:
+            raise ValueError("top_hits needs read_groups")
+        for name, given in (("mate_pairs", mate_pairs), ("sam", sam)):
+            if given:
+                raise ValueError("top_hits cannot be combined with %s" % name)
+        flags |= capi.FLAG_TOP_HITS
     if escalate:
         if a != ALGO_WFA:
             raise ValueError("escalate needs wfa")
@@ -397,6 +406,24 @@ def align_device_mates(params, n_pairs, n_reads, d_requests, d_patterns, d_text_
                                                   scratch_bytes, stream))
 
 
+def hits_offsets(read_offsets, max_hits):
+    """aim_hits_offsets: hit_offsets[n_reads + 1] (uint32), the exclusive prefix sum of min(K_r, max_hits); H is its last entry."""
+    ro = np.ascontiguousarray(read_offsets, dtype=np.uint32)
+    ho = np.zeros(len(ro), dtype=np.uint32)
+    capi.check(capi.load().aim_hits_offsets(len(ro) - 1, capi.ptr(ro), int(max_hits), capi.ptr(ho), None))
+    return ho
+
+
+def align_device_hits(params, n_pairs, n_reads, d_requests, d_patterns, d_texts, d_text_pos, d_reference, ref_len, d_read_offsets, d_results,
+                      d_ops, d_best, max_hits, d_hit_offsets, n_hits, d_hit_pair, d_scratch, scratch_bytes, stream=None):
+    """aim_align_device_hits on device pointers (integers, e.g. torch's data_ptr(); None = NULL): the stateless form of a
+    AIM_FLAG_TOP_HITS batch. d_hit_offsets holds hits_offsets(read_offsets, max_hits) and n_hits its last entry; d_results and d_ops
+    receive n_hits rows, d_hit_pair (may be None) the rows' candidates. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_align_device_hits(params_ref(params), n_pairs, n_reads, d_requests, d_patterns, d_texts, d_text_pos, d_reference,
+                                                 ref_len, d_read_offsets, d_results, d_ops, d_best, int(max_hits), d_hit_offsets, int(n_hits),
+                                                 d_hit_pair, d_scratch, scratch_bytes, stream))
+
+
 def sam_device(params, n_rows, d_requests, d_text_pos, d_sel, d_results, d_ops, d_reference, ref_len, options, d_sam, d_cigar, cigar_cap,
                d_md, md_cap, d_cursors, stream=None):
     """aim_sam_device on device pointers (integers, e.g. torch's data_ptr(); None = NULL): SAM records of rows that already live on the
@@ -621,7 +648,7 @@ class DeviceSet:
         self.ref_len = len(arr)
 
     def submit(self, device, slot, req, pat=None, txt=None, packed=None, want_ops=False, cigar_runs_cap=0, text_pos=None,
-               read_offsets=None, mates=None, sam=None, want_res=None):
+               read_offsets=None, mates=None, sam=None, want_res=None, max_hits=None, hit_offsets=None):
         """aim_set_submit: ASCII rows (pat, txt) or a packed batch (pack_batch(...)); results / ops / compact CIGAR buffers
         are allocated here and returned by wait(). text_pos (AIM_FLAG_REF_TEXTS): the texts are windows of the reference; pass
         pat (or packed = pack_batch(req, pat, None)) and no texts. read_offsets (AIM_FLAG_READ_GROUPS): req and the texts are per
@@ -629,12 +656,20 @@ class DeviceSet:
         max_span, unpaired_penalty) (AIM_FLAG_MATE_PAIRS, with read_offsets and text_pos): reads 2m and 2m + 1 are mates; wait() also
         returns "mates" (capi.MATE_DTYPE, one row per read pair) next to "best", which stays the independent selection.
         sam = (cigar_cap, md_cap, options) (AIM_FLAG_SAM_FIELDS): wait() also returns "sam" (capi.SAM_DTYPE, one record per output
-        row), "sam_cigar" (BAM words) and "sam_md" (bytes); want_res=False then sends no result rows back."""
+        row), "sam_cigar" (BAM words) and "sam_md" (bytes); want_res=False then sends no result rows back.
+        max_hits (AIM_FLAG_TOP_HITS, with read_offsets): every read's max_hits best candidates; wait() returns one row per hit, in
+        rank order at [hit_offsets[r], hit_offsets[r + 1]), plus "hit_pair" (the rows' candidates) and "hit_offsets" -- computed here
+        by hits_offsets() unless hit_offsets is given."""
         if (self.params.flags & FLAG_REQ8) and req.dtype != REQUEST8_DTYPE:
             req = to_request8(req)
         req = np.ascontiguousarray(req)
         n, rs = len(req), self.params.read_size
-        sio = capi.BatchIOSam() if (self.params.flags & capi.FLAG_SAM_FIELDS) else None
+        hio = capi.BatchIOHits() if (self.params.flags & capi.FLAG_TOP_HITS) else None
+        if (max_hits is not None) != (hio is not None):
+            raise ValueError("max_hits= goes with params made with top_hits=True")
+        if hio is not None and read_offsets is None:
+            raise ValueError("max_hits needs read_offsets")
+        sio = hio.sam if hio is not None else (capi.BatchIOSam() if (self.params.flags & capi.FLAG_SAM_FIELDS) else None)
         if mates is not None:
             if read_offsets is None:
                 raise ValueError("mates needs read_offsets")
@@ -655,6 +690,12 @@ class DeviceSet:
             if mio is not None:
                 out["mates"] = np.zeros(n_out // 2, dtype=capi.MATE_DTYPE)
                 mio.mates = out["mates"].ctypes.data
+            if hio is not None:
+                ho = hits_offsets(ro, max_hits) if hit_offsets is None else np.ascontiguousarray(hit_offsets, dtype=np.uint32)
+                n_out = int(hits_offsets(ro, max_hits)[-1]) if len(ro) > 1 else 0     # (a wrong hit_offsets is the library's to refuse)
+                out["hit_offsets"] = ho
+                out["hit_pair"] = np.zeros(n_out, dtype=np.uint32)
+                hio.max_hits, hio.hit_offsets, hio.hit_pair = int(max_hits), ho.ctypes.data, out["hit_pair"].ctypes.data
         else:
             ro, n_out = None, n
         io.n_pairs = n
@@ -699,7 +740,7 @@ class DeviceSet:
             out["ops"] = np.zeros((n_out, 2 * rs), dtype=np.uint8)
             io.ops = out["ops"].ctypes.data
         capi.check(self.lib.aim_set_submit(self.handle, device, slot, C.byref(io)))
-        self._inflight[(device, slot)] = (sio if sio is not None else (rio if mio is None else mio), keep, out)
+        self._inflight[(device, slot)] = (hio if hio is not None else sio if sio is not None else (rio if mio is None else mio), keep, out)
 
     def wait(self, device, slot, check=True):
         io, keep, out = self._inflight.pop((device, slot), (None, None, {}))   # nothing in flight: the library reports AIM_ESTATE

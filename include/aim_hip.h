@@ -235,6 +235,27 @@ typedef struct aim_affine2p_params {
  * aim_plan_describe, aim_scratch_bytes and aim_kernel_name accept it and describe the plan aim_set_submit follows.
  * Check aim_features() & AIM_FEATURE_SAM_FIELDS first: older libraries ignore unknown flags. */
 #define AIM_FLAG_SAM_FIELDS 0x4000u
+/* AIM_FLAG_TOP_HITS (needs AIM_FLAG_READ_GROUPS; combines with whatever that flag combines with, under those flags' own rules): the
+ * max_hits best candidates of every read, each a full row -- secondary alignments, repeats, a mate-rescue list -- without sending the
+ * runners-up again as a second batch. Rows are hits, not reads, and their number is fixed by the batch's shape, so the host knows every
+ * size before it submits: nothing is compacted, scanned or counted on the device.
+ * RANKING. For read r with K_r candidates, after the score-only pass of AIM_FLAG_READ_GROUPS: the AIM_PAIR_OK candidates come first,
+ *   ordered by (score, batch index) ascending (a WFA pair over the cap counts with its MAX_SCORE + 1, as under AIM_FLAG_READ_GROUPS); the
+ *   candidates that are not OK follow, ordered by batch index. Rank 0 is therefore always sel[r] of AIM_FLAG_READ_GROUPS.
+ * ROWS. Read r gets exactly min(K_r, max_hits) hit rows, at [hit_offsets[r], hit_offsets[r + 1]) in rank order; hit_offsets is the
+ *   exclusive prefix sum of those counts (aim_hits_offsets) and H = hit_offsets[n_reads] <= n_pairs. hit_pair[h] is the candidate of
+ *   row h. Row h's result row (its idx and status included), ops range [begin_offset, end_offset), compact header and runs are exactly
+ *   those of candidate hit_pair[h] run without AIM_FLAG_READ_GROUPS and AIM_FLAG_TOP_HITS under the configured flags: the contract of
+ *   AIM_FLAG_READ_GROUPS applied per hit. Without AIM_FLAG_BACKTRACE there is no second pass and the rows are the score-only rows
+ *   (aim_result_t, or {idx, score} under AIM_FLAG_RES8). best[] is unchanged, and with max_hits = 1 every output equals that of the same
+ *   call without the flag. Nothing depends on the grid, the slots, the batch split or the AIM_DEBUG_POISON_* knobs.
+ * Entry points: aim_set_submit with an aim_batch_io_hits_t and aim_align_device_hits; every entry point that refuses
+ * AIM_FLAG_READ_GROUPS refuses this flag too, and so does aim_align_device_groups. The plan line ends in " groups=1 hits=1".
+ * AIM_EINVAL, the message naming the flag: without AIM_FLAG_READ_GROUPS, and with AIM_FLAG_MATE_PAIRS or AIM_FLAG_SAM_FIELDS (follow-ups;
+ * aim_sam_device already works on hit rows: pass d_sel = d_hit_pair and n_rows = H).
+ * Check aim_features() & AIM_FEATURE_TOP_HITS first: older libraries ignore unknown flags. */
+#define AIM_FLAG_TOP_HITS 0x8000u
+#define AIM_TOP_HITS_MAX 8          /* max_hits is 1..AIM_TOP_HITS_MAX */
 #define AIM_SAM_EQX 0x1u            /* sam_options / options: '=' and 'X' instead of 'M' */
 #define AIM_SAM_REVERSE 0x10u       /* aim_sam_t.flags: SAM's own FLAG bits */
 #define AIM_SAM_UNMAPPED 0x4u
@@ -303,6 +324,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_WFA_ESCALATE 0x80u /* AIM_FLAG_WFA_ESCALATE is honoured */
 #define AIM_FEATURE_MATE_PAIRS 0x100u /* AIM_FLAG_MATE_PAIRS is honoured */
 #define AIM_FEATURE_SAM_FIELDS 0x200u /* AIM_FLAG_SAM_FIELDS is honoured; aim_sam_device and aim_sam_format_cigar exist */
+#define AIM_FEATURE_TOP_HITS 0x400u /* AIM_FLAG_TOP_HITS is honoured; aim_hits_offsets and aim_align_device_hits exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -482,6 +504,21 @@ typedef struct aim_batch_io_sam {
  * flag before this call returns AIM_ESTATE. A batch may use less (sam_cigar_cap / sam_md_cap), never more. */
 int aim_set_sam_capacity(aim_set_t *set, uint32_t max_cigar_words, uint32_t max_md_bytes);
 
+/* AIM_FLAG_TOP_HITS: aim_set_submit reads past `sam` (only with the flag). Of `sam` the groups members are read; its mates and sam
+ * members are ignored. base.results, ops, cigars and runs receive H = hit_offsets[n_reads] rows, groups.best n_reads rows. */
+typedef struct aim_batch_io_hits {
+    aim_batch_io_sam_t sam;        /* @0, 224 B */
+    uint32_t max_hits, pad;        /* 1..AIM_TOP_HITS_MAX; 0 */
+    const uint32_t *hit_offsets;   /* in: [n_reads + 1], as aim_hits_offsets gives it */
+    uint32_t *hit_pair;            /* out: [H] candidate (batch index) of every hit row, or NULL */
+} aim_batch_io_hits_t;
+/* Host helper: hit_offsets[r] = the sum of min(K_q, max_hits) over the reads q < r, for r = 0..n_reads, K_q = read_offsets[q + 1] -
+ * read_offsets[q]; *n_hits (may be NULL) receives hit_offsets[n_reads]. AIM_EINVAL when max_hits is outside 1..AIM_TOP_HITS_MAX or a
+ * pointer is NULL. The CSR itself is aim_groups_check's business (a decreasing pair of offsets counts as an empty read here).
+ * aim_set_submit recomputes the offsets before anything is enqueued: a mismatch is AIM_EINVAL naming the first bad read. */
+int aim_hits_offsets(uint32_t n_reads, const uint32_t *read_offsets, uint32_t max_hits, uint32_t *hit_offsets /* [n_reads + 1] */,
+                     uint32_t *n_hits);
+
 /* aim_set_configure with `slots` (1..4) buffer sets per device; max_raw_pairs bounds n_raw of a packed batch
  * (0 = packed input not used), max_runs the run buffer of a compact-CIGAR batch (0 = not used). */
 int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t max_pairs_per_device, uint32_t slots,
@@ -550,6 +587,15 @@ int aim_align_device_mates(const aim_params_t *params, uint32_t n_pairs, uint32_
                            const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, int64_t min_span,
                            int64_t max_span, int32_t unpaired_penalty, aim_mate_t *d_mates, void *d_scratch, size_t scratch_bytes,
                            void *hip_stream);
+/* AIM_FLAG_TOP_HITS: aim_align_device_groups' arguments, then max_hits, d_hit_offsets[n_reads + 1] (device memory; unchecked like the
+ * CSR: a wrong one yields unspecified rows, never an access outside the buffers), n_hits = H as aim_hits_offsets gave it (<= n_pairs) and
+ * d_hit_pair[H] (device memory; may be NULL). d_results and d_ops hold H rows, d_best n_reads rows. aim_scratch_bytes under the flag is
+ * the figure without it plus the hit list: n_pairs * 4 bytes rounded up to 256 B. */
+int aim_align_device_hits(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
+                          const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
+                          const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, uint32_t max_hits,
+                          const uint32_t *d_hit_offsets, uint32_t n_hits, uint32_t *d_hit_pair, void *d_scratch, size_t scratch_bytes,
+                          void *hip_stream);
 /* The kernel of AIM_FLAG_SAM_FIELDS on rows that already live on the device, after any aim_align_device* call with AIM_FLAG_BACKTRACE
  * (params are that call's; the flag itself is not needed). Row r uses text_pos entry d_sel[r] -- entry r when d_sel is NULL; UINT32_MAX
  * gives an unmapped record -- while d_results[n_rows] and d_ops[n_rows][2 * read_size] are indexed by row. d_requests (aim_request_t[] or,
