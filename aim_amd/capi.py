@@ -39,6 +39,9 @@ FEATURE_SAM_FIELDS = 0x200   # aim_features(): AIM_FLAG_SAM_FIELDS is honoured
 FLAG_TOP_HITS = 0x8000       # the max_hits best candidates of every read of a read-groups batch, each a full row
 FEATURE_TOP_HITS = 0x400     # aim_features(): AIM_FLAG_TOP_HITS is honoured
 TOP_HITS_MAX = 8             # max_hits is 1..TOP_HITS_MAX
+FEATURE_SEED = 0x800         # aim_features(): device-side seeding (aim_index_* / aim_seed_*) exists
+SEED_MAX_CANDS, SEED_MAX_HITS, SEED_TRUNCATED, SEED_MAX_READ_SIZE = 16, 1024, 1, 4096
+SEED_MAX_REF_LEN = (1 << 32) - (1 << 25)
 SAM_EQX, SAM_REVERSE, SAM_UNMAPPED, SAM_OVERFLOW = 0x1, 0x10, 0x4, 0x100   # sam_options; aim_sam_t.flags (SAM's own bits); aim_sam_t.status bit
 MATE_PROPER = 1              # aim_mate_t.flags: the chosen candidates are a proper combination
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
@@ -110,6 +113,16 @@ assert MATE_DTYPE.itemsize == 32
 SAM_DTYPE = np.dtype([("idx", "<u4"), ("score", "<i4"), ("pos", "<u8"), ("ref_span", "<u4"), ("nm", "<u4"), ("cigar_offset", "<u4"),
                       ("n_cigar", "<u4"), ("md_offset", "<u4"), ("md_len", "<u4"), ("flags", "<u2"), ("status", "<u2"), ("pad", "<u4")])   # aim_sam_t
 assert SAM_DTYPE.itemsize == 48
+
+
+class SeedParams(C.Structure):
+    """aim_seed_params_t"""
+    _fields_ = [("k", C.c_int32), ("stride", C.c_int32), ("max_occ", C.c_int32), ("band", C.c_int32), ("flank", C.c_int32),
+                ("min_votes", C.c_int32), ("max_cands", C.c_int32), ("read_size", C.c_int32), ("idx_base", C.c_uint32), ("options", C.c_uint32)]
+
+
+SEED_DTYPE = np.dtype([("n_cands", "<u4"), ("n_hits", "<u4", (2,)), ("flags", "<u4")])   # aim_seed_t
+assert SEED_DTYPE.itemsize == 16 and C.sizeof(SeedParams) == 40
 
 
 class BatchIO(C.Structure):
@@ -200,6 +213,11 @@ SYMBOLS = {
     "aim_sam_device": (C.c_int, [C.POINTER(Params), _U32, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _U32, _VP, _VP, _U32, _VP, _U32, _VP, _VP]),
     "aim_sam_format_cigar": (C.c_int, [_VP, _U32, _VP, _I32]),
     "aim_sam_kernel_name": (C.c_char_p, [C.POINTER(Params)]),
+    "aim_index_sizes": (C.c_int, [_I32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "aim_index_build": (C.c_int, [_VP, C.c_uint64, _I32, _VP, _VP, C.POINTER(C.c_uint64), C.c_int]),
+    "aim_seed_device": (C.c_int, [C.POINTER(SeedParams), _U32, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP]),
+    "aim_seed_groups_offsets": (C.c_int, [_U32, _U32, _VP]),
+    "aim_seed_kernel_name": (C.c_char_p, []),
 }
 
 _lib = None

@@ -36,6 +36,7 @@
 #include "hits.hpp"
 #include "mates.hpp"
 #include "sam_fields.hpp"
+#include "seed.hpp"
 #include "genasm_wave.hpp"
 
 namespace {
@@ -1670,7 +1671,7 @@ int aim_abi_version(void) { return AIM_ABI_VERSION; }
 uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
-           AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS;
+           AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS | AIM_FEATURE_SEED;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -3036,6 +3037,160 @@ int aim_align_device_mates(const aim_params_t *params, uint32_t n_pairs, uint32_
     ma.unpaired_penalty = unpaired_penalty;
     return align_device_groups(params, n_pairs, n_reads, d_requests, d_patterns, nullptr, d_text_pos_or_null, d_reference, ref_len,
                                d_read_offsets, d_results, d_ops, d_best, &ma, d_mates, nullptr, d_scratch, scratch_bytes, hip_stream);
+}
+
+// ---------------------------------------------------------------------------
+// device-side seeding (AIM_FEATURE_SEED; the rule is stated in aim_hip.h, the kernel in seed.hpp)
+// ---------------------------------------------------------------------------
+extern "C++" {
+namespace {
+int check_index_args(int32_t k, uint64_t ref_len)
+{
+    if (k < 8 || k > 14) return fail(AIM_EINVAL, "seed index: k %d is outside 8..14", k);
+    if (ref_len > AIM_SEED_MAX_REF_LEN)
+        return fail(AIM_EINVAL, "seed index: ref_len %llu is above 2^32 - 2^25 (positions and diagonal keys are 32-bit)", (unsigned long long)ref_len);
+    return AIM_OK;
+}
+
+int check_seed_params(const aim_seed_params_t &sp)
+{
+    if (sp.k < 8 || sp.k > 14) return fail(AIM_EINVAL, "aim_seed_params_t: k %d is outside 8..14", sp.k);
+    if (sp.stride < 1) return fail(AIM_EINVAL, "aim_seed_params_t: stride %d must be >= 1", sp.stride);
+    if (sp.max_occ < 1) return fail(AIM_EINVAL, "aim_seed_params_t: max_occ %d must be >= 1", sp.max_occ);
+    if (sp.band < 0) return fail(AIM_EINVAL, "aim_seed_params_t: band %d must be >= 0", sp.band);
+    if (sp.flank < 0) return fail(AIM_EINVAL, "aim_seed_params_t: flank %d must be >= 0", sp.flank);
+    if (sp.min_votes < 1) return fail(AIM_EINVAL, "aim_seed_params_t: min_votes %d must be >= 1", sp.min_votes);
+    if (sp.max_cands < 1 || sp.max_cands > AIM_SEED_MAX_CANDS)
+        return fail(AIM_EINVAL, "aim_seed_params_t: max_cands %d is outside 1..%d", sp.max_cands, AIM_SEED_MAX_CANDS);
+    if (sp.read_size <= 0 || (sp.read_size & 7) || sp.read_size > AIM_SEED_MAX_READ_SIZE)
+        return fail(AIM_EINVAL, "aim_seed_params_t: read_size %d must be a positive multiple of 8, at most %d", sp.read_size, AIM_SEED_MAX_READ_SIZE);
+    if (sp.options) return fail(AIM_EINVAL, "aim_seed_params_t: unknown options 0x%x", sp.options);
+    return AIM_OK;
+}
+
+// One pass of the index build over the whole sequence for the codes [c_lo, c_hi): `visit(code, p)` for every indexed k-mer of the range,
+// p ascending. The rolling code keeps the last k bases; `good` counts how many of them in a row were upper-case A C G T.
+template <typename F>
+void index_scan(const char *seq, uint64_t len, int k, uint32_t c_lo, uint32_t c_hi, F visit)
+{
+    uint32_t code = 0, good = 0;
+    const int top = 2 * (k - 1);
+    for (uint64_t i = 0; i < len; ++i) {
+        const unsigned char c = (unsigned char)seq[i];
+        if (c == 'A' || c == 'C' || c == 'G' || c == 'T') {
+            code = (code >> 2) | ((uint32_t)((c >> 1) & 3) << top);
+            ++good;
+        } else {
+            code = 0;
+            good = 0;
+        }
+        if (good >= (uint32_t)k && code >= c_lo && code < c_hi) visit(code, (uint32_t)(i + 1 - (uint64_t)k));
+    }
+}
+}  // namespace
+}  // extern "C++"
+
+int aim_index_sizes(int32_t k, uint64_t ref_len, uint64_t *bucket_entries, uint64_t *pos_capacity)
+{
+    int rc = check_index_args(k, ref_len);
+    if (rc) return rc;
+    if (!bucket_entries || !pos_capacity) return fail(AIM_EINVAL, "seed index: NULL output pointer");
+    *bucket_entries = (1ull << (2 * k)) + 1u;
+    *pos_capacity = ref_len >= (uint64_t)k ? ref_len - (uint64_t)k + 1u : 0u;
+    return AIM_OK;
+}
+
+int aim_index_build(const char *seq, uint64_t ref_len, int32_t k, uint32_t *bucket, uint32_t *pos, uint64_t *n_pos, int threads)
+{
+    int rc = check_index_args(k, ref_len);
+    if (rc) return rc;
+    const bool any = ref_len >= (uint64_t)k;
+    if (!bucket || (ref_len && !seq) || (any && !pos)) return fail(AIM_EINVAL, "seed index: NULL seq, bucket or pos");
+    const uint64_t n_codes = 1ull << (2 * k);
+    const int T = std::max(1, std::min(threads, 64));
+    // every worker owns the codes [n_codes * t / T, n_codes * (t + 1) / T): its counts and, later, its runs of pos[] are its own
+    auto range = [&](int t) { return (uint32_t)(n_codes * (uint64_t)t / (uint64_t)T); };
+    auto run = [&](auto body) {
+        std::vector<std::thread> th;
+        for (int t = 1; t < T; ++t) th.emplace_back(body, t);
+        body(0);
+        for (auto &x : th) x.join();
+    };
+    // pass 1: counts, shifted by one so that the prefix sum below leaves bucket[c] = first entry of code c
+    run([&](int t) {
+        const uint32_t lo = range(t), hi = t + 1 == T ? (uint32_t)n_codes : range(t + 1);
+        memset(bucket + (size_t)lo + 1, 0, (size_t)(hi - lo) * sizeof(uint32_t));
+        if (any) index_scan(seq, ref_len, k, lo, hi, [&](uint32_t c, uint32_t) { ++bucket[(size_t)c + 1]; });
+    });
+    bucket[0] = 0;
+    for (uint64_t c = 0; c < n_codes; ++c) bucket[c + 1] += bucket[c];
+    const uint64_t total = bucket[n_codes];
+    // pass 2: bucket[c] is code c's cursor; afterwards it holds bucket[c + 1], and one shift restores the prefix sums
+    if (total) {
+        run([&](int t) {
+            const uint32_t lo = range(t), hi = t + 1 == T ? (uint32_t)n_codes : range(t + 1);
+            index_scan(seq, ref_len, k, lo, hi, [&](uint32_t c, uint32_t p) { pos[bucket[c]++] = p; });
+        });
+        for (uint64_t c = n_codes; c > 0; --c) bucket[c] = bucket[c - 1];
+        bucket[0] = 0;
+    }
+    if (n_pos) *n_pos = total;
+    return AIM_OK;
+}
+
+int aim_seed_groups_offsets(uint32_t n_reads, uint32_t K, uint32_t *read_offsets)
+{
+    if (K < 1 || K > AIM_SEED_MAX_CANDS) return fail(AIM_EINVAL, "aim_seed_groups_offsets: K %u is outside 1..%d", K, AIM_SEED_MAX_CANDS);
+    if (!read_offsets) return fail(AIM_EINVAL, "aim_seed_groups_offsets: NULL read_offsets");
+    if ((uint64_t)n_reads * K >= (1ull << 32)) return fail(AIM_EINVAL, "aim_seed_groups_offsets: n_reads %u * K %u does not fit 32 bits", n_reads, K);
+    for (uint64_t r = 0; r <= n_reads; ++r) read_offsets[r] = (uint32_t)(r * K);
+    return AIM_OK;
+}
+
+const char *aim_seed_kernel_name(void) { return "seed_candidates_kernel"; }
+
+int aim_seed_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads, const uint32_t *d_bucket,
+                    const uint32_t *d_pos, uint64_t ref_len, void *d_requests, uint64_t *d_text_pos, uint32_t *d_votes, aim_seed_t *d_seed,
+                    void *hip_stream)
+{
+    if (!sp) return fail(AIM_EINVAL, "aim_seed_device: sp is NULL");
+    int rc = check_seed_params(*sp);
+    if (rc) return rc;
+    if (ref_len > AIM_SEED_MAX_REF_LEN)
+        return fail(AIM_EINVAL, "aim_seed_device: ref_len %llu is above 2^32 - 2^25 (positions and diagonal keys are 32-bit)", (unsigned long long)ref_len);
+    if ((uint64_t)n_reads * (uint64_t)sp->max_cands >= (1ull << 32))
+        return fail(AIM_EINVAL, "aim_seed_device: n_reads %u * max_cands %d does not fit 32 bits (split the batch)", n_reads, sp->max_cands);
+    if (n_reads && (!d_read_len || !d_reads || !d_bucket || (!d_pos && ref_len >= (uint64_t)sp->k) || !d_requests || !d_text_pos || !d_votes || !d_seed))
+        return fail(AIM_EINVAL, "aim_seed_device: null device buffer");
+    int n = 0;
+    rc = aim_device_count(&n);
+    if (rc) return rc;
+    if (!n_reads) return AIM_OK;
+    const aim::Knobs kn = with_chip(read_knobs());
+    aim::SeedArgs a;
+    memset(&a, 0, sizeof a);
+    a.sp = *sp;
+    a.n_reads = n_reads;
+    a.read_len = d_read_len;
+    a.reads = d_reads;
+    a.bucket = d_bucket;
+    a.pos = d_pos;
+    a.ref_len = ref_len;
+    a.req = static_cast<aim_request_t *>(d_requests);
+    a.text_pos = d_text_pos;
+    a.votes = d_votes;
+    a.seed = d_seed;
+    const size_t lds = aim::seed_lds_bytes(sp->read_size);
+    a.dbg_poison_lds = kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u;
+    a.dbg_lds_bytes = (uint32_t)lds;
+    // persistent grid: what LDS lets one CU hold (at most 16 wavefronts), on every CU, capped at the reads rounded up to the multiple of 8
+    // xcd_unit needs (below 8 reads the surplus workgroups find no work and leave)
+    const uint32_t per_cu = (uint32_t)std::min<size_t>(16, aim::lds_workgroups_per_cu(lds));
+    const uint32_t grid = std::min(aim::resident_grid(kn, per_cu), (uint32_t)std::min<uint64_t>(((uint64_t)n_reads + 7u) & ~7ull, 1u << 20));
+    if (kn.plan_debug) fprintf(stderr, "[aim plan] seed_candidates_kernel grid=%u block=64 lds=%zu per_cu=%u reads=%u\n", grid, lds, per_cu, n_reads);
+    aim::seed_launch(a, grid, lds, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
 }
 
 // ---------------------------------------------------------------------------

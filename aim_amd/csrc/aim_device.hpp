@@ -73,15 +73,16 @@ __device__ __forceinline__ void store_result(const KArgs &a, uint32_t pair, cons
 
 // Debugging aid shared by all kernels: fill the workgroup's dynamic LDS with a chosen byte before anything else runs.
 // A kernel whose results depend on what LDS held at entry changes its output under this switch (tools/soak_dp_wave.py).
-__device__ __forceinline__ void debug_poison_lds(const KArgs &a, char *smem)
+__device__ __forceinline__ void debug_poison_lds(uint32_t poison, uint32_t lds_bytes, char *smem)
 {
-    if (a.dbg_poison_lds) {   // wave-uniform, false in production
-        const uint32_t w = (a.dbg_poison_lds & 0xffu) * 0x01010101u;
+    if (poison) {   // wave-uniform, false in production
+        const uint32_t w = (poison & 0xffu) * 0x01010101u;
         uint32_t *s4 = reinterpret_cast<uint32_t *>(smem);
-        for (uint32_t i = threadIdx.x; i < a.dbg_lds_bytes / 4; i += blockDim.x) s4[i] = w;
+        for (uint32_t i = threadIdx.x; i < lds_bytes / 4; i += blockDim.x) s4[i] = w;
         __syncthreads();
     }
 }
+__device__ __forceinline__ void debug_poison_lds(const KArgs &a, char *smem) { debug_poison_lds(a.dbg_poison_lds, a.dbg_lds_bytes, smem); }
 
 // Run-time knobs (the AIM_* environment variables). They are experiment / debugging switches, not configuration: every
 // one of them leaves results bit-identical. They are read in ONE place (read_knobs, aim_capi.hip) into this struct --

@@ -1,0 +1,300 @@
+// seed.hpp -- device-side seeding (aim_hip.h, AIM_FEATURE_SEED): reads and a k-mer index in, K candidate windows per read out.
+//
+//   * seed_candidates_kernel: one read per 64-lane wavefront (a workgroup is one wavefront), persistent over the reads through
+//     xcd_unit like the per-pair kernels. Everything per read lives in LDS; there is no scratch and no traffic between workgroups.
+//
+// The rule is stated in full in aim_hip.h; the phases below follow its numbering.
+//   stage    the read row, once, into LDS (dwords).
+//   hits     lanes take seeds, 64 per step. The strand-0 code is read forward from the row and the strand-1 code backward from the same
+//            bytes with the complement folded in (code ^ 2). Two bucket reads give a seed's run of positions; a wave prefix sum of the run
+//            lengths gives every lane its append position, which makes the (j, p) order of rule 3 exact.
+//   sort     an in-wave bitonic network over each strand's keys in LDS, padded with 0xFFFFFFFF (no key reaches it: ref_len <= 2^32 - 2^25).
+//   cluster  boundary flags from the neighbours and a segmented max-scan of the head positions; a cluster's votes are stored at its tail
+//            (0 elsewhere and below min_votes), so a_hi is the key there and a_lo the key `votes - 1` entries before it.
+//   rank     K rounds of "smallest remaining rank key" in the pattern of hit_select_kernel: the key (1024 - votes, strand, a_lo) is
+//            unique per cluster, round i keeps its winner in lane i, and lanes 0..K-1 then write their slots, empty ones included.
+//
+// LDS BANKS. ds_read_b32 / ds_write_b32 bank on (address / 4) % 32 within each 32-lane half. A compare-exchange stage at distance
+// j >= 32 touches consecutive dwords per half: conflict-free. At j < 32 the 32 lower partners of a half all have bit log2(j) clear and
+// would fall two to a bank; there the upper 16 lanes of each half read their UPPER partner first (address | j), so a half covers 32
+// distinct residues in each of its two reads and writes. The cluster and rank passes read consecutive entries.
+//
+// OCCUPANCY. LDS per workgroup = 8 KB of keys + 4 KB of votes + the row: 12 432 B at read_size 128, ten 1 280-B granules, so 12
+// wavefronts per CU = 3 per SIMD, LDS-bound. The register budget that keeps it so is 512 / 3 = 170; kSeedMaxVgpr = 128 leaves room for
+// a fourth wavefront should the LDS shrink. No scratch.
+#pragma once
+
+#include <climits>
+
+#include "aim_device.hpp"
+
+namespace aim {
+
+constexpr int kSeedMaxVgpr = 128;                          // the bound tests/test_seed_cpu.py checks in the code object
+constexpr uint32_t kSeedHits = AIM_SEED_MAX_HITS;          // keys per strand
+constexpr uint32_t kSeedKeyBytes = 2 * kSeedHits * 4;      // keys[2][1024]
+constexpr uint32_t kSeedVoteBytes = 2 * kSeedHits * 2;     // vt[2][1024], uint16_t
+
+struct SeedArgs {
+    aim_seed_params_t sp;
+    uint32_t n_reads;
+    const int32_t *read_len;
+    const char *reads;
+    const uint32_t *bucket, *pos;
+    uint64_t ref_len;
+    aim_request_t *req;
+    uint64_t *text_pos;
+    uint32_t *votes;
+    aim_seed_t *seed;
+    uint32_t dbg_poison_lds, dbg_lds_bytes;   // as in KArgs (AIM_DEBUG_POISON_LDS)
+};
+
+// Dynamic LDS of one workgroup: keys, votes, the row and 16 bytes past it.
+inline size_t seed_lds_bytes(int32_t read_size) { return kSeedKeyBytes + kSeedVoteBytes + (size_t)read_size + 16; }
+
+#ifdef AIM_TU_SEED   // the kernel lives in tu_seed.hip alone; aim_capi.hip sees SeedArgs and the launcher
+
+__device__ __forceinline__ uint32_t seed_scan_add(uint32_t v, int lane)   // inclusive wave prefix sum
+{
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint32_t o = __shfl_up(v, d, kWave);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint32_t seed_scan_max(uint32_t v, int lane)   // inclusive wave prefix maximum
+{
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint32_t o = __shfl_up(v, d, kWave);
+        if (lane >= d) v = max(v, o);
+    }
+    return v;
+}
+
+__device__ __forceinline__ bool seed_is_base(uint32_t c)   // upper-case A C G T
+{
+    const uint32_t d = c - 65u;
+    return d < 20u && ((0x80045u >> d) & 1u);
+}
+
+// Ascending bitonic sort of key[0, N), N a power of two >= 64, by one wavefront (see LDS BANKS above).
+__device__ __forceinline__ void seed_sort(uint32_t *key, uint32_t N, int lane)
+{
+    for (uint32_t k2 = 2; k2 <= N; k2 <<= 1) {
+        for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
+            for (uint32_t t = (uint32_t)lane; t < N / 2; t += kWave) {
+                const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u));      // the lower partner
+                const bool up = (i & k2) == 0;
+                const bool hi_first = j < 32u && (t & 16u);
+                const uint32_t a0 = hi_first ? (i | j) : i, a1 = a0 ^ j;
+                const uint32_t x = key[a0], y = key[a1];
+                const uint32_t lo_v = hi_first ? y : x, hi_v = hi_first ? x : y;
+                if ((lo_v > hi_v) == up) {
+                    key[a0] = y;
+                    key[a1] = x;
+                }
+            }
+            asm volatile("" ::: "memory");   // same-wave LDS traffic is ordered; compiler fence only
+        }
+    }
+}
+
+__device__ __forceinline__ uint64_t seed_min_u64(uint64_t v)   // wave-wide minimum, in every lane
+{
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)v, d, kWave), hi = __shfl_xor((uint32_t)(v >> 32), d, kWave);
+        const uint64_t o = ((uint64_t)hi << 32) | lo;
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(64) void seed_candidates_kernel(SeedArgs a)
+{
+    extern __shared__ __align__(16) char seed_smem[];
+    debug_poison_lds(a.dbg_poison_lds, a.dbg_lds_bytes, seed_smem);
+    const int lane = threadIdx.x;
+    uint32_t *keys = reinterpret_cast<uint32_t *>(seed_smem);                          // [2][kSeedHits]
+    uint16_t *vt = reinterpret_cast<uint16_t *>(seed_smem + kSeedKeyBytes);            // [2][kSeedHits]
+    uint32_t *row4 = reinterpret_cast<uint32_t *>(seed_smem + kSeedKeyBytes + kSeedVoteBytes);
+    const uint8_t *row = reinterpret_cast<const uint8_t *>(row4);
+    const int32_t k = a.sp.k, stride = a.sp.stride, rs = a.sp.read_size;
+    const uint32_t K = (uint32_t)a.sp.max_cands, band = (uint32_t)a.sp.band, max_occ = (uint32_t)a.sp.max_occ;
+    const uint32_t min_votes = (uint32_t)a.sp.min_votes;
+    const uint32_t n_codes = 1u << (2 * k);
+    const uint64_t pos_cap = a.ref_len >= (uint64_t)k ? a.ref_len - (uint64_t)k + 1u : 0u;
+
+    for (uint32_t it = 0;; ++it) {
+        uint32_t r;
+        if (!xcd_unit(a.n_reads, it, &r)) break;
+        const int32_t L = min(max(a.read_len[r], 0), rs);
+        asm volatile("" ::: "memory");   // the previous read's LDS reads are issued before this row lands
+        {   // stage
+            const uint32_t *g = reinterpret_cast<const uint32_t *>(a.reads + (uint64_t)r * (uint64_t)rs);
+            for (int w = lane; w < (L + 3) >> 2; w += kWave) row4[w] = g[w];
+        }
+        asm volatile("" ::: "memory");
+
+        // hits (rules 1-3)
+        const uint32_t n_seeds = L >= k ? (uint32_t)(L - k) / (uint32_t)stride + 1u : 0u;
+        uint32_t count[2] = {0u, 0u};    // hits found so far, wave-uniform; counting stops once it has passed kSeedHits
+        for (uint32_t base = 0; base < n_seeds; base += kWave) {
+            if (count[0] > kSeedHits && count[1] > kSeedHits) break;
+            const uint32_t m = base + (uint32_t)lane;
+            const bool active = m < n_seeds;
+            const int32_t j = active ? (int32_t)m * stride : 0;
+            uint32_t c0 = 0, c1 = 0;
+            bool ok0 = active, ok1 = active;
+            if (active) {
+                const uint8_t *f = row + j, *b = row + (L - 1 - j);
+                for (int i = 0; i < k; ++i) {
+                    const uint32_t x = f[i], y = b[-i];
+                    ok0 = ok0 && seed_is_base(x);
+                    ok1 = ok1 && seed_is_base(y);
+                    c0 |= ((x >> 1) & 3u) << (2 * i);
+                    c1 |= (((y >> 1) & 3u) ^ 2u) << (2 * i);
+                }
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                if (count[s] > kSeedHits) continue;              // (wave-uniform)
+                const uint32_t code = s ? c1 : c0;
+                uint32_t b0 = 0, n = 0;
+                if ((s ? ok1 : ok0) && code < n_codes) {
+                    b0 = a.bucket[code];
+                    const uint32_t b1 = a.bucket[code + 1u];
+                    n = b1 - b0;
+                    if (b1 < b0 || n > max_occ || (uint64_t)b1 > pos_cap) n = 0;
+                    n = min(n, kSeedHits + 1u);                  // past kSeedHits only "overflowed" matters: the sums below stay far from 2^32
+                }
+                const uint32_t incl = seed_scan_add(n, lane);
+                const uint32_t at = count[s] + incl - n;
+                const uint32_t bias = (uint32_t)rs - (uint32_t)j;
+                uint32_t *ks = keys + s * kSeedHits;
+                for (uint32_t q = 0; q < n && at + q < kSeedHits; ++q) ks[at + q] = a.pos[b0 + q] + bias;
+                count[s] += (uint32_t)__builtin_amdgcn_readlane((int)incl, kWave - 1);
+            }
+        }
+        const uint32_t nh[2] = {min(count[0], kSeedHits), min(count[1], kSeedHits)};
+        const uint32_t sflags = (count[0] > kSeedHits || count[1] > kSeedHits) ? AIM_SEED_TRUNCATED : 0u;
+        asm volatile("" ::: "memory");
+
+        // sort and cluster (rule 4)
+        uint32_t n_clusters = 0;         // clusters with votes >= min_votes, both strands (wave-uniform)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const uint32_t n = nh[s];
+            uint32_t *ks = keys + s * kSeedHits;
+            uint16_t *vs = vt + s * kSeedHits;
+            if (n > 1) {
+                uint32_t N = kWave;
+                while (N < n) N <<= 1;
+                for (uint32_t i = n + (uint32_t)lane; i < N; i += kWave) ks[i] = UINT_MAX;
+                asm volatile("" ::: "memory");
+                seed_sort(ks, N, lane);
+            }
+            uint32_t carry = 0;          // head position of the run that reaches into this chunk
+            for (uint32_t base = 0; base < n; base += kWave) {
+                const uint32_t i = base + (uint32_t)lane;
+                const bool active = i < n;
+                uint32_t head_at = 0, votes = 0;
+                bool tail = false;
+                if (active) {
+                    const uint32_t cur = ks[i];
+                    const bool head = i == 0 || cur - ks[i - 1] > band;
+                    tail = i + 1 == n || ks[i + 1] - cur > band;
+                    head_at = head ? i : 0u;
+                }
+                head_at = max(seed_scan_max(head_at, lane), carry);
+                carry = (uint32_t)__builtin_amdgcn_readlane((int)head_at, kWave - 1);
+                if (tail) votes = i - head_at + 1u;
+                if (votes < min_votes) votes = 0;
+                if (active) vs[i] = (uint16_t)votes;
+                n_clusters += (uint32_t)__popcll(__ballot(votes != 0));
+            }
+        }
+        asm volatile("" ::: "memory");
+
+        // rank (rule 5): round i's winner stays in lane i
+        uint32_t my_lo = 0, my_hi = 0, my_votes = 0, my_s = 0;
+        uint32_t n_cands = 0;
+        uint64_t last = 0;
+        const uint32_t rounds = min(K, n_clusters);
+        for (uint32_t round = 0; round < rounds; ++round) {
+            uint64_t best = ULLONG_MAX;
+            uint32_t best_hi = 0;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const uint32_t *ks = keys + s * kSeedHits;
+                const uint16_t *vs = vt + s * kSeedHits;
+                for (uint32_t i = (uint32_t)lane; i < nh[s]; i += kWave) {
+                    const uint32_t v = vs[i];
+                    if (!v) continue;
+                    const uint64_t key = ((uint64_t)(kSeedHits - v) << 33) | ((uint64_t)s << 32) | ks[i - v + 1u];
+                    if ((round == 0 || key > last) && key < best) {
+                        best = key;
+                        best_hi = ks[i];
+                    }
+                }
+            }
+            const uint64_t win = seed_min_u64(best);
+            // (rounds <= n_clusters and the keys are unique: every round finds one)
+            const int src = __ffsll((unsigned long long)__ballot(best == win)) - 1;
+            const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)best_hi, src);
+            if ((uint32_t)lane == round) {
+                my_lo = (uint32_t)win;
+                my_hi = hi;
+                my_votes = kSeedHits - (uint32_t)(win >> 33);
+                my_s = (uint32_t)(win >> 32) & 1u;
+            }
+            last = win;
+            ++n_cands;
+        }
+
+        // fill (rules 6-7): lanes 0..K-1 write their slots
+        if ((uint32_t)lane < K) {
+            const uint32_t slot = r * K + (uint32_t)lane;
+            aim_request_t q;
+            q.pattern_len = L;
+            q.text_len = 0;
+            q.padding = 0;
+            q.idx = a.sp.idx_base + slot;
+            uint64_t tp = 0;
+            uint32_t votes = 0;
+            if ((uint32_t)lane < n_cands) {
+                const int64_t lo = (int64_t)my_lo - (int64_t)rs - (int64_t)a.sp.flank;
+                const int64_t hi = lo + (int64_t)L + 2 * (int64_t)a.sp.flank + (int64_t)min(my_hi - my_lo, (uint32_t)rs);
+                const int64_t start = max(lo, (int64_t)0);
+                const int64_t end = max(start, min(hi, (int64_t)a.ref_len));
+                q.text_len = (int32_t)min(end - start, (int64_t)rs);
+                tp = (uint64_t)start | ((uint64_t)my_s << 63);
+                votes = my_votes;
+            }
+            a.req[slot] = q;
+            a.text_pos[slot] = tp;
+            a.votes[slot] = votes;
+        }
+        if (lane == 0) {
+            aim_seed_t sd;
+            sd.n_cands = n_cands;
+            sd.n_hits[0] = nh[0];
+            sd.n_hits[1] = nh[1];
+            sd.flags = sflags;
+            a.seed[r] = sd;
+        }
+    }
+}
+
+void seed_launch(const SeedArgs &a, uint32_t grid, size_t lds, hipStream_t s)
+{
+    hipLaunchKernelGGL(seed_candidates_kernel, dim3(grid), dim3(kWave), lds, s, a);
+}
+#else
+void seed_launch(const SeedArgs &a, uint32_t grid, size_t lds, hipStream_t s);
+#endif
+
+}  // namespace aim

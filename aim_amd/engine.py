@@ -396,6 +396,14 @@ def mate_pairs(seed, n_read_pairs, length, error, insert, k, repeat_frac, read_s
     return ref, req, rows, offsets, tpos, txt, np.ascontiguousarray(np.repeat(rows, k, axis=0)), truth
 
 
+def align_device_groups(params, n_pairs, n_reads, d_requests, d_patterns, d_texts, d_text_pos, d_reference, ref_len, d_read_offsets, d_results,
+                        d_ops, d_best, d_scratch, scratch_bytes, stream=None):
+    """aim_align_device_groups on device pointers (integers, e.g. torch's data_ptr(); None = NULL): the stateless form of a
+    AIM_FLAG_READ_GROUPS batch, e.g. on the buffers seed_candidates returned. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_align_device_groups(params_ref(params), n_pairs, n_reads, d_requests, d_patterns, d_texts, d_text_pos, d_reference,
+                                                   ref_len, d_read_offsets, d_results, d_ops, d_best, d_scratch, scratch_bytes, stream))
+
+
 def align_device_mates(params, n_pairs, n_reads, d_requests, d_patterns, d_text_pos, d_reference, ref_len, d_read_offsets, d_results, d_ops,
                        d_best, mates, d_mates, d_scratch, scratch_bytes, stream=None):
     """aim_align_device_mates on device pointers (integers, e.g. torch's data_ptr(); None = NULL): the stateless form of a
@@ -422,6 +430,92 @@ def align_device_hits(params, n_pairs, n_reads, d_requests, d_patterns, d_texts,
     capi.check(capi.load().aim_align_device_hits(params_ref(params), n_pairs, n_reads, d_requests, d_patterns, d_texts, d_text_pos, d_reference,
                                                  ref_len, d_read_offsets, d_results, d_ops, d_best, int(max_hits), d_hit_offsets, int(n_hits),
                                                  d_hit_pair, d_scratch, scratch_bytes, stream))
+
+
+def index_sizes(k, ref_len):
+    """aim_index_sizes: (bucket entries = 4^k + 1, pos capacity = ref_len - k + 1, 0 below k)."""
+    be, pc = C.c_uint64(), C.c_uint64()
+    capi.check(capi.load().aim_index_sizes(int(k), int(ref_len), C.byref(be), C.byref(pc)))
+    return be.value, pc.value
+
+
+def build_index(reference, k, threads=8):
+    """aim_index_build on the host: (bucket[4^k + 1], pos[n_pos]) as uint32 arrays for `reference` (bytes or a uint8 array). The
+    k-mer at p is reference[p, p + k), base i at bits [2i, 2i + 1] with code (ascii >> 1) & 3; only upper-case A C G T are indexed.
+    The result does not depend on `threads`."""
+    ref = np.ascontiguousarray(np.frombuffer(reference, dtype=np.uint8) if isinstance(reference, (bytes, bytearray)) else reference, dtype=np.uint8)
+    be, pc = index_sizes(k, len(ref))
+    bucket = np.zeros(be, dtype=np.uint32)
+    pos = np.zeros(max(pc, 1), dtype=np.uint32)
+    n = C.c_uint64()
+    capi.check(capi.load().aim_index_build(capi.ptr(ref), len(ref), int(k), capi.ptr(bucket), capi.ptr(pos), C.byref(n), int(threads)))
+    return bucket, pos[:n.value]
+
+
+def seed_params(k, read_size, stride=1, max_occ=16, band=8, flank=8, min_votes=2, max_cands=4, idx_base=0):
+    """aim_seed_params_t, validated like make_params: ValueError names the field that is out of bounds."""
+    bounds = (("k", k, 8, 14), ("stride", stride, 1, None), ("max_occ", max_occ, 1, None), ("band", band, 0, None), ("flank", flank, 0, None),
+              ("min_votes", min_votes, 1, None), ("max_cands", max_cands, 1, capi.SEED_MAX_CANDS), ("read_size", read_size, 8, capi.SEED_MAX_READ_SIZE))
+    for name, v, lo, hi in bounds:
+        if int(v) != v or v < lo or (hi is not None and v > hi) or v >= 1 << 31:
+            raise ValueError("%s %r is outside %d..%s" % (name, v, lo, "" if hi is None else hi))
+    if read_size % 8:
+        raise ValueError("read_size %d is not a multiple of 8" % read_size)
+    return capi.SeedParams(int(k), int(stride), int(max_occ), int(band), int(flank), int(min_votes), int(max_cands), int(read_size),
+                           int(idx_base) & 0xFFFFFFFF, 0)
+
+
+def seed_groups_offsets(n_reads, max_cands):
+    """aim_seed_groups_offsets: read_offsets[r] = r * K (uint32, n_reads + 1 entries), the CSR of the seeding kernel's slots."""
+    ro = np.zeros(n_reads + 1, dtype=np.uint32)
+    capi.check(capi.load().aim_seed_groups_offsets(int(n_reads), int(max_cands), capi.ptr(ro)))
+    return ro
+
+
+def seed_device(sp, n_reads, d_read_len, d_reads, d_bucket, d_pos, ref_len, d_requests, d_text_pos, d_votes, d_seed, stream=None):
+    """aim_seed_device on device pointers (integers, e.g. torch's data_ptr(); None = NULL). Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_seed_device(C.byref(sp), int(n_reads), d_read_len, d_reads, d_bucket, d_pos, int(ref_len), d_requests,
+                                           d_text_pos, d_votes, d_seed, stream))
+
+
+def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0"):
+    """The seeding kernel on torch device buffers. `index` is build_index's (bucket, pos) -- numpy arrays, or uint8 torch tensors
+    that already live on the device (as the "d_bucket" / "d_pos" of an earlier call); read_len is int32[n_reads], reads the ASCII
+    rows uint8[n_reads][read_size]. Returns a dict: numpy "req" (REQUEST_DTYPE), "text_pos" (uint64), "votes" (uint32) and "seed"
+    (SEED_DTYPE), each in slot order r * K + i, and the uint8 device tensors "d_req", "d_text_pos", "d_votes", "d_seed", "d_reads",
+    "d_read_len", "d_bucket", "d_pos" for chaining into align_device_groups and its siblings without a copy through the host."""
+    import torch
+    dev = torch.device(device)
+
+    def put(x, slack=0):
+        if isinstance(x, torch.Tensor):
+            return x
+        raw = np.ascontiguousarray(x).view(np.uint8).reshape(-1)
+        t = torch.zeros(max(len(raw) + slack, 16), dtype=torch.uint8, device=dev)
+        t[:len(raw)] = torch.from_numpy(raw.copy()).to(dev)
+        return t
+    rl = np.ascontiguousarray(read_len, dtype=np.int32)
+    rows = np.ascontiguousarray(reads, dtype=np.uint8)
+    n, K = len(rl), sp.max_cands
+    if rows.shape != (n, sp.read_size):
+        raise ValueError("reads must be uint8[%d][%d], got %r" % (n, sp.read_size, rows.shape))
+    d = {"d_bucket": put(index[0]), "d_pos": put(index[1]), "d_read_len": put(rl), "d_reads": put(rows, slack=64)}
+    slots = max(n * K, 1)
+    d["d_req"] = torch.zeros(slots * 16, dtype=torch.uint8, device=dev)
+    d["d_text_pos"] = torch.zeros(slots * 8, dtype=torch.uint8, device=dev)
+    d["d_votes"] = torch.zeros(slots * 4, dtype=torch.uint8, device=dev)
+    d["d_seed"] = torch.zeros(max(n, 1) * 16, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+    with torch.cuda.device(dev):
+        seed_device(sp, n, d["d_read_len"].data_ptr(), d["d_reads"].data_ptr(), d["d_bucket"].data_ptr(), d["d_pos"].data_ptr(), ref_len,
+                    d["d_req"].data_ptr(), d["d_text_pos"].data_ptr(), d["d_votes"].data_ptr(), d["d_seed"].data_ptr(),
+                    torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize(dev)
+    d["req"] = d["d_req"].cpu().numpy().view(capi.REQUEST_DTYPE)[:n * K]
+    d["text_pos"] = d["d_text_pos"].cpu().numpy().view(np.uint64)[:n * K]
+    d["votes"] = d["d_votes"].cpu().numpy().view(np.uint32)[:n * K]
+    d["seed"] = d["d_seed"].cpu().numpy().view(capi.SEED_DTYPE)[:n]
+    return d
 
 
 def sam_device(params, n_rows, d_requests, d_text_pos, d_sel, d_results, d_ops, d_reference, ref_len, options, d_sam, d_cigar, cigar_cap,

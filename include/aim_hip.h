@@ -325,6 +325,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_MATE_PAIRS 0x100u /* AIM_FLAG_MATE_PAIRS is honoured */
 #define AIM_FEATURE_SAM_FIELDS 0x200u /* AIM_FLAG_SAM_FIELDS is honoured; aim_sam_device and aim_sam_format_cigar exist */
 #define AIM_FEATURE_TOP_HITS 0x400u /* AIM_FLAG_TOP_HITS is honoured; aim_hits_offsets and aim_align_device_hits exist */
+#define AIM_FEATURE_SEED 0x800u /* device-side seeding: aim_index_sizes / aim_index_build / aim_seed_device / aim_seed_groups_offsets exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -614,6 +615,77 @@ int aim_sam_device(const aim_params_t *params, uint32_t n_rows, const void *d_re
  * per lane) or "sam_wave_kernel" (one row per wavefront), by read_size; the names match the rocprofv3 kernel-trace prefixes. A set freezes
  * the choice at aim_set_configure like every other AIM_* switch. */
 const char *aim_sam_kernel_name(const aim_params_t *params);
+
+/* ---- device-side seeding (AIM_FEATURE_SEED): candidate windows from a k-mer index -----------------------------------------
+ * The step in front of AIM_FLAG_REF_TEXTS | AIM_FLAG_READ_GROUPS: reads go in, and requests[] / text_pos[] for K candidate windows per
+ * read come out in device memory, in the fixed shape slot = r * K + i, so that aim_align_device_groups / _mates / _hits consume them
+ * without a trip through the host. Empty slots are marked, nothing is compacted, scanned or counted across reads, and the host knows
+ * every size before it launches. No flag of aim_params_t is involved.
+ * INDEX. The k-mer at reference position p is seq[p, p + k); base i of it sits at bits [2i, 2i + 1] of its code, with the packed
+ *   rows' code (ascii >> 1) & 3 (A 0, C 1, T 2, G 3). A k-mer that covers any byte other than upper-case A C G T is not indexed.
+ *   bucket[4^k + 1] is the exclusive prefix sum of the codes' counts and pos[bucket[c] .. bucket[c + 1]) holds the positions of code c
+ *   in ascending order: 4^k * 4 B + 4 B per position. Positions and diagonal keys are 32-bit: ref_len <= AIM_SEED_MAX_REF_LEN.
+ * RULE, for read r of length L = read_len[r] (0..read_size) and strand s in {0, 1}; deterministic and independent of the grid:
+ *   1. The query is the read (s = 0) or its reverse complement (s = 1). Only A C G T are complemented; any other byte stays, and a
+ *      k-mer that covers one is skipped.
+ *   2. Seeds sit at query offsets j = 0, stride, 2 * stride, ... with j + k <= L. A seed whose code has n reference positions is
+ *      skipped when n = 0 or n > max_occ; otherwise every position p, in ascending order, yields the hit key a = p + read_size - j
+ *      (uint32_t: the diagonal, biased to stay non-negative).
+ *   3. Hits are kept in (j, p) order up to AIM_SEED_MAX_HITS per strand; later ones are dropped and AIM_SEED_TRUNCATED is set.
+ *      n_hits[s] counts the kept ones.
+ *   4. The strand's keys are sorted. A cluster is a maximal run whose consecutive differences are <= band; it has votes (its
+ *      length), a_lo (its first key) and a_hi (its last).
+ *   5. The clusters of both strands with votes >= min_votes are ranked by (votes descending, strand ascending, a_lo ascending); the
+ *      first K = max_cands become the candidates, n_cands is their number.
+ *   6. Candidate i fills slot r * K + i. With lo = a_lo - read_size - flank (signed 64-bit) and
+ *      hi = lo + L + 2 * flank + min(a_hi - a_lo, read_size): start = max(lo, 0), end = max(start, min(hi, ref_len));
+ *      requests[slot] = {pattern_len L, text_len min(end - start, read_size), 0, idx_base + slot}, text_pos[slot] = start | s << 63,
+ *      votes[slot] = votes.
+ *   7. Slots from n_cands on are empty: {L, 0, 0, idx_base + slot}, text_pos 0, votes 0. An empty window is always inside the
+ *      reference; under AIM_FLAG_READ_GROUPS such a candidate scores a pure gap of L bases, and callers read n_cands.
+ * The window is on the forward reference and strand 1 sets bit 63: exactly what AIM_FLAG_REF_TEXTS reverse-complements. Flanked
+ * windows are usually aligned with AIM_FLAG_ENDSFREE (text_begin_free = text_end_free = 2 * flank).
+ * Follow-ups, not in this version: packed read rows, minimizers and spaced seeds, an index built on the device, a seeding stage inside
+ * aim_set_submit, chaining instead of voting. Check aim_features() & AIM_FEATURE_SEED first. */
+#define AIM_SEED_MAX_CANDS 16
+#define AIM_SEED_MAX_HITS 1024      /* hits kept per (read, strand) */
+#define AIM_SEED_TRUNCATED 0x1u     /* aim_seed_t.flags: a strand dropped hits beyond AIM_SEED_MAX_HITS */
+#define AIM_SEED_MAX_READ_SIZE 4096 /* the read row is staged in LDS next to the key arrays */
+#define AIM_SEED_MAX_REF_LEN 0xFE000000ull /* 2^32 - 2^25 */
+typedef struct aim_seed_params {
+    int32_t k;          /* 8..14 */
+    int32_t stride;     /* >= 1: seeds start at read offsets 0, stride, 2*stride, ... */
+    int32_t max_occ;    /* >= 1: a k-mer with more reference positions than this is skipped */
+    int32_t band;       /* >= 0: consecutive sorted diagonals at most this far apart share a cluster */
+    int32_t flank;      /* >= 0: reference bases added on each side of a cluster's window */
+    int32_t min_votes;  /* >= 1 */
+    int32_t max_cands;  /* K, 1..AIM_SEED_MAX_CANDS */
+    int32_t read_size;  /* row stride of the read rows, multiple of 8, <= AIM_SEED_MAX_READ_SIZE; also the cap on text_len */
+    uint32_t idx_base;  /* requests[r*K+i].idx = idx_base + r*K + i */
+    uint32_t options;   /* 0 */
+} aim_seed_params_t;
+typedef struct aim_seed { uint32_t n_cands, n_hits[2], flags; } aim_seed_t;   /* 16 B per read */
+/* Sizes of the index arrays, in entries: *bucket_entries = 4^k + 1, *pos_capacity = ref_len - k + 1 (0 below k). AIM_EINVAL for a k
+ * outside 8..14 or a ref_len above AIM_SEED_MAX_REF_LEN. */
+int aim_index_sizes(int32_t k, uint64_t ref_len, uint64_t *bucket_entries, uint64_t *pos_capacity);
+/* Builds the index on the host (no device is needed): a counting sort in two passes with `threads` workers (< 1 counts as 1), each of
+ * which owns a range of codes, so the result does not depend on `threads`. bucket and pos hold what aim_index_sizes reports (pos may
+ * be NULL when its capacity is 0); *n_pos (may be NULL) receives bucket[4^k], the number of positions written. */
+int aim_index_build(const char *seq, uint64_t ref_len, int32_t k, uint32_t *bucket, uint32_t *pos, uint64_t *n_pos, int threads);
+/* The seeding kernel over device buffers: ASCII read rows d_reads[n_reads][read_size] (aligned and with slack like d_patterns),
+ * d_read_len[n_reads], the index of a reference of ref_len bytes, and the outputs of the rule above: d_requests
+ * (aim_request_t[n_reads * K]), d_text_pos, d_votes (each [n_reads * K]) and d_seed[n_reads]. The call only enqueues work on
+ * hip_stream and needs no scratch: everything per read lives in LDS. A read_len outside 0..read_size is clamped; index entries that
+ * point outside the arrays aim_index_sizes describes make a seed count as absent, never a fault. AIM_EINVAL with a message naming the
+ * field for every bound of aim_seed_params_t, for ref_len, and for n_reads * K >= 2^32. */
+int aim_seed_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads,
+                    const uint32_t *d_bucket, const uint32_t *d_pos, uint64_t ref_len, void *d_requests /* aim_request_t[n_reads*K] */,
+                    uint64_t *d_text_pos, uint32_t *d_votes, aim_seed_t *d_seed, void *hip_stream);
+/* Host helper: read_offsets[r] = r * K for r = 0..n_reads, the CSR AIM_FLAG_READ_GROUPS wants for the slots above. AIM_EINVAL for a
+ * K outside 1..AIM_SEED_MAX_CANDS, a NULL pointer or n_reads * K >= 2^32. */
+int aim_seed_groups_offsets(uint32_t n_reads, uint32_t K, uint32_t *read_offsets /* [n_reads + 1] */);
+/* "seed_candidates_kernel": the rocprofv3 kernel-trace name prefix of aim_seed_device's kernel. */
+const char *aim_seed_kernel_name(void);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
