@@ -42,6 +42,7 @@ TOP_HITS_MAX = 8             # max_hits is 1..TOP_HITS_MAX
 FEATURE_SEED = 0x800         # aim_features(): device-side seeding (aim_index_* / aim_seed_*) exists
 SEED_MAX_CANDS, SEED_MAX_HITS, SEED_TRUNCATED, SEED_MAX_READ_SIZE = 16, 1024, 1, 4096
 SEED_MAX_REF_LEN = (1 << 32) - (1 << 25)
+FEATURE_INDEX_DEVICE = 0x1000   # aim_features(): aim_index_device_scratch / aim_index_build_device / aim_index_kernel_names exist
 SAM_EQX, SAM_REVERSE, SAM_UNMAPPED, SAM_OVERFLOW = 0x1, 0x10, 0x4, 0x100   # sam_options; aim_sam_t.flags (SAM's own bits); aim_sam_t.status bit
 MATE_PROPER = 1              # aim_mate_t.flags: the chosen candidates are a proper combination
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
@@ -218,6 +219,9 @@ SYMBOLS = {
     "aim_seed_device": (C.c_int, [C.POINTER(SeedParams), _U32, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP]),
     "aim_seed_groups_offsets": (C.c_int, [_U32, _U32, _VP]),
     "aim_seed_kernel_name": (C.c_char_p, []),
+    "aim_index_device_scratch": (C.c_int, [_I32, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "aim_index_build_device": (C.c_int, [_VP, C.c_uint64, _I32, _VP, _VP, _VP, C.c_uint64, _VP]),
+    "aim_index_kernel_names": (C.c_char_p, []),
 }
 
 _lib = None

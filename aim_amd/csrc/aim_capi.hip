@@ -37,6 +37,7 @@
 #include "mates.hpp"
 #include "sam_fields.hpp"
 #include "seed.hpp"
+#include "index.hpp"
 #include "genasm_wave.hpp"
 
 namespace {
@@ -1671,7 +1672,8 @@ int aim_abi_version(void) { return AIM_ABI_VERSION; }
 uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
-           AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS | AIM_FEATURE_SEED;
+           AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS | AIM_FEATURE_SEED |
+           AIM_FEATURE_INDEX_DEVICE;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -3190,6 +3192,116 @@ int aim_seed_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t
     if (kn.plan_debug) fprintf(stderr, "[aim plan] seed_candidates_kernel grid=%u block=64 lds=%zu per_cu=%u reads=%u\n", grid, lds, per_cu, n_reads);
     aim::seed_launch(a, grid, lds, (hipStream_t)hip_stream);
     HIP_TRY(hipGetLastError());
+    return AIM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the index built on the device (AIM_FEATURE_INDEX_DEVICE; the kernels and the scratch layout in index.hpp)
+// ---------------------------------------------------------------------------
+int aim_index_device_scratch(int32_t k, uint64_t ref_len, uint64_t *scratch_bytes)
+{
+    int rc = check_index_args(k, ref_len);
+    if (rc) return rc;
+    if (!scratch_bytes) return fail(AIM_EINVAL, "seed index: NULL output pointer");
+    *scratch_bytes = aim::index_layout(k, ref_len).total;
+    return AIM_OK;
+}
+
+const char *aim_index_kernel_names(void)
+{
+    return "index_code_kernel,index_scan_sums_kernel,index_scan_top_kernel,index_scan_apply_kernel,index_hist_kernel,index_scatter_kernel";
+}
+
+int aim_index_build_device(const char *d_reference, uint64_t ref_len, int32_t k, uint32_t *d_bucket, uint32_t *d_pos, void *d_scratch,
+                           uint64_t scratch_bytes, void *hip_stream)
+{
+    int rc = check_index_args(k, ref_len);
+    if (rc) return rc;
+    const aim::IndexLayout L = aim::index_layout(k, ref_len);
+    if (!d_bucket) return fail(AIM_EINVAL, "aim_index_build_device: d_bucket is NULL");
+    if (L.n) {
+        if (!d_reference) return fail(AIM_EINVAL, "aim_index_build_device: d_reference is NULL");
+        if ((uintptr_t)d_reference & 15u) return fail(AIM_EINVAL, "aim_index_build_device: d_reference is not 16-byte aligned");
+        if (!d_pos) return fail(AIM_EINVAL, "aim_index_build_device: d_pos is NULL (ref_len %llu >= k %d)", (unsigned long long)ref_len, k);
+        if (!d_scratch) return fail(AIM_EINVAL, "aim_index_build_device: d_scratch is NULL (%llu bytes are needed)", (unsigned long long)L.total);
+        if ((uintptr_t)d_scratch & 255u) return fail(AIM_EINVAL, "aim_index_build_device: d_scratch is not 256-byte aligned");
+        if (scratch_bytes < L.total)
+            return fail(AIM_EINVAL, "aim_index_build_device: scratch_bytes %llu is below the %llu aim_index_device_scratch reports",
+                        (unsigned long long)scratch_bytes, (unsigned long long)L.total);
+    }
+    int n_dev = 0;
+    rc = aim_device_count(&n_dev);
+    if (rc) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const aim::Knobs kn = with_chip(read_knobs());
+    const uint64_t n_codes = 1ull << (2 * k);
+    if (kn.plan_debug) fprintf(stderr, "[aim plan] index memset bucket bytes=%llu\n", (unsigned long long)((n_codes + 1u) * 4u));
+    HIP_TRY(hipMemsetAsync(d_bucket, 0, (size_t)(n_codes + 1u) * sizeof(uint32_t), stream));
+    if (!L.n) return AIM_OK;
+    char *scr = static_cast<char *>(d_scratch);
+    // Debugging aid, as for the alignment scratch: results must not depend on what the scratch held before.
+    if (kn.poison_scratch >= 0) HIP_TRY(hipMemsetAsync(scr, kn.poison_scratch & 0xff, (size_t)L.total, stream));
+    uint32_t *keys[2] = {reinterpret_cast<uint32_t *>(scr + L.key_a), reinterpret_cast<uint32_t *>(scr + L.key_b)};
+    uint32_t *pos_s = reinterpret_cast<uint32_t *>(scr + L.pos_s);
+    const uint32_t poison_lds = kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u;
+    // persistent grids: 8 workgroups of 256 threads per CU (index.hpp OCCUPANCY), never more than there are tiles / scan parts
+    const uint32_t resident = aim::resident_grid(kn, 8);
+    const uint32_t grid = std::min(resident, L.n_tiles);
+    auto scan = [&](uint32_t *data, uint64_t n, const char *what) {
+        aim::IndexScanArgs s;
+        memset(&s, 0, sizeof s);
+        s.data = data;
+        s.n = n;
+        s.n_parts = (uint32_t)std::min<uint64_t>(std::min(resident, aim::kIndexScanParts), (n + aim::kIndexScanBlock - 1u) / aim::kIndexScanBlock);
+        s.per_part = ((n + s.n_parts - 1u) / s.n_parts + aim::kIndexScanBlock - 1u) / aim::kIndexScanBlock * aim::kIndexScanBlock;
+        s.part = reinterpret_cast<uint32_t *>(scr + L.parts);
+        s.dbg_poison_lds = poison_lds;
+        if (kn.plan_debug) {
+            fprintf(stderr, "[aim plan] index_scan_sums_kernel grid=%u block=%d %s entries=%llu per_part=%llu\n", s.n_parts, aim::kIndexThreads, what,
+                    (unsigned long long)n, (unsigned long long)s.per_part);
+            fprintf(stderr, "[aim plan] index_scan_top_kernel grid=1 block=%d %s parts=%u\n", aim::kIndexThreads, what, s.n_parts);
+            fprintf(stderr, "[aim plan] index_scan_apply_kernel grid=%u block=%d %s entries=%llu per_part=%llu\n", s.n_parts, aim::kIndexThreads, what,
+                    (unsigned long long)n, (unsigned long long)s.per_part);
+        }
+        aim::index_launch_scan(s, stream);
+    };
+    aim::IndexArgs a;
+    memset(&a, 0, sizeof a);
+    a.ref = d_reference;
+    a.ref_len = ref_len;
+    a.k = k;
+    a.n = L.n;
+    a.n_tiles = L.n_tiles;
+    a.table = reinterpret_cast<uint32_t *>(scr + L.table);
+    a.bucket = d_bucket;
+    a.dbg_poison_lds = poison_lds;
+    a.key_out = keys[0];
+    if (kn.plan_debug)
+        fprintf(stderr, "[aim plan] index_code_kernel grid=%u block=%d k=%d positions=%llu tiles=%u\n", grid, aim::kIndexThreads, k, (unsigned long long)L.n, L.n_tiles);
+    aim::index_launch_code(a, grid, stream);
+    HIP_TRY(hipGetLastError());
+    scan(d_bucket, n_codes + 1u, "bucket");
+    HIP_TRY(hipGetLastError());
+    // pass p reads what pass p - 1 wrote; the positions alternate between d_pos and the scratch array so that the last pass lands in d_pos
+    const int passes = aim::index_passes(k);
+    for (int p = 0; p < passes; ++p) {
+        const bool last = p + 1 == passes;
+        auto pos_of = [&](int q) { return ((passes - 1 - q) & 1) ? pos_s : d_pos; };
+        a.shift = (uint32_t)(8 * p);
+        a.key_in = keys[p & 1];
+        a.key_out = last ? nullptr : keys[(p + 1) & 1];
+        a.pos_in = p ? pos_of(p - 1) : nullptr;
+        a.pos_out = pos_of(p);
+        if (kn.plan_debug) fprintf(stderr, "[aim plan] index_hist_kernel grid=%u block=%d pass=%d/%d shift=%u\n", grid, aim::kIndexThreads, p + 1, passes, a.shift);
+        aim::index_launch_hist(a, grid, stream);
+        HIP_TRY(hipGetLastError());
+        scan(a.table, (uint64_t)aim::kIndexDigits * L.n_tiles, "table");
+        HIP_TRY(hipGetLastError());
+        if (kn.plan_debug)
+            fprintf(stderr, "[aim plan] index_scatter_kernel grid=%u block=%d pass=%d/%d shift=%u keys_out=%d\n", grid, aim::kIndexThreads, p + 1, passes, a.shift, last ? 0 : 1);
+        aim::index_launch_scatter(a, grid, stream);
+        HIP_TRY(hipGetLastError());
+    }
     return AIM_OK;
 }
 

@@ -452,6 +452,47 @@ def build_index(reference, k, threads=8):
     return bucket, pos[:n.value]
 
 
+def index_device_scratch(k, ref_len):
+    """aim_index_device_scratch: bytes of device scratch build_index_device / aim_index_build_device need (0 below k)."""
+    sb = C.c_uint64()
+    capi.check(capi.load().aim_index_device_scratch(int(k), int(ref_len), C.byref(sb)))
+    return sb.value
+
+
+def index_build_device(d_reference, ref_len, k, d_bucket, d_pos, d_scratch, scratch_bytes, stream=None):
+    """aim_index_build_device on device pointers (integers, e.g. torch's data_ptr(); None = NULL). Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_index_build_device(d_reference, int(ref_len), int(k), d_bucket, d_pos, d_scratch, int(scratch_bytes), stream))
+
+
+def build_index_device(reference, k, device="cuda:0", stream=None):
+    """The index of build_index, built on the device. `reference` is bytes, a uint8 numpy array, or a uint8 torch tensor that already
+    lives on `device` with at least 16 bytes of slack behind the reference (then ref_len is its length minus 16). Returns
+    (d_bucket, d_pos, n_pos): uint8 device tensors in the form seed_candidates accepts for `index`, and bucket[4^k]. d_pos has room
+    for ref_len - k + 1 positions; the entries from n_pos on are unspecified. The scratch is allocated here and freed on return."""
+    import torch
+    dev = torch.device(device)
+    if isinstance(reference, torch.Tensor):
+        if reference.dtype != torch.uint8 or reference.device != dev or not reference.is_contiguous() or reference.numel() < 16:
+            raise ValueError("a device reference must be a contiguous uint8 tensor on %s with 16 bytes of slack" % dev)
+        d_ref, ref_len = reference.reshape(-1), reference.numel() - 16
+    else:
+        raw = np.ascontiguousarray(np.frombuffer(reference, dtype=np.uint8) if isinstance(reference, (bytes, bytearray)) else reference, dtype=np.uint8)
+        ref_len = len(raw)
+        d_ref = torch.zeros(ref_len + 16, dtype=torch.uint8, device=dev)
+        d_ref[:ref_len] = torch.from_numpy(raw.copy()).to(dev)
+    be, pc = index_sizes(k, ref_len)
+    sb = index_device_scratch(k, ref_len)
+    d_bucket = torch.empty(be * 4, dtype=torch.uint8, device=dev)
+    d_pos = torch.empty(max(pc, 1) * 4, dtype=torch.uint8, device=dev)
+    d_scr = torch.empty(max(sb, 256), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        index_build_device(d_ref.data_ptr(), ref_len, k, d_bucket.data_ptr(), d_pos.data_ptr(), d_scr.data_ptr(), sb, s.cuda_stream)
+        s.synchronize()
+    n_pos = int(d_bucket[(be - 1) * 4:].cpu().numpy().view(np.uint32)[0])
+    return d_bucket, d_pos, n_pos
+
+
 def seed_params(k, read_size, stride=1, max_occ=16, band=8, flank=8, min_votes=2, max_cands=4, idx_base=0):
     """aim_seed_params_t, validated like make_params: ValueError names the field that is out of bounds."""
     bounds = (("k", k, 8, 14), ("stride", stride, 1, None), ("max_occ", max_occ, 1, None), ("band", band, 0, None), ("flank", flank, 0, None),

@@ -326,6 +326,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_SAM_FIELDS 0x200u /* AIM_FLAG_SAM_FIELDS is honoured; aim_sam_device and aim_sam_format_cigar exist */
 #define AIM_FEATURE_TOP_HITS 0x400u /* AIM_FLAG_TOP_HITS is honoured; aim_hits_offsets and aim_align_device_hits exist */
 #define AIM_FEATURE_SEED 0x800u /* device-side seeding: aim_index_sizes / aim_index_build / aim_seed_device / aim_seed_groups_offsets exist */
+#define AIM_FEATURE_INDEX_DEVICE 0x1000u /* aim_index_device_scratch / aim_index_build_device / aim_index_kernel_names exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -645,8 +646,8 @@ const char *aim_sam_kernel_name(const aim_params_t *params);
  *      reference; under AIM_FLAG_READ_GROUPS such a candidate scores a pure gap of L bases, and callers read n_cands.
  * The window is on the forward reference and strand 1 sets bit 63: exactly what AIM_FLAG_REF_TEXTS reverse-complements. Flanked
  * windows are usually aligned with AIM_FLAG_ENDSFREE (text_begin_free = text_end_free = 2 * flank).
- * Follow-ups, not in this version: packed read rows, minimizers and spaced seeds, an index built on the device, a seeding stage inside
- * aim_set_submit, chaining instead of voting. Check aim_features() & AIM_FEATURE_SEED first. */
+ * Follow-ups, not in this version: packed read rows, minimizers and spaced seeds, a seeding stage inside aim_set_submit, chaining
+ * instead of voting. Check aim_features() & AIM_FEATURE_SEED first. */
 #define AIM_SEED_MAX_CANDS 16
 #define AIM_SEED_MAX_HITS 1024      /* hits kept per (read, strand) */
 #define AIM_SEED_TRUNCATED 0x1u     /* aim_seed_t.flags: a strand dropped hits beyond AIM_SEED_MAX_HITS */
@@ -672,6 +673,26 @@ int aim_index_sizes(int32_t k, uint64_t ref_len, uint64_t *bucket_entries, uint6
  * which owns a range of codes, so the result does not depend on `threads`. bucket and pos hold what aim_index_sizes reports (pos may
  * be NULL when its capacity is 0); *n_pos (may be NULL) receives bucket[4^k], the number of positions written. */
 int aim_index_build(const char *seq, uint64_t ref_len, int32_t k, uint32_t *bucket, uint32_t *pos, uint64_t *n_pos, int threads);
+/* ---- the same index, built on the device (AIM_FEATURE_INDEX_DEVICE) ----
+ * Bytes of device scratch aim_index_build_device needs for (k, ref_len); 0 is a legal answer (ref_len < k). With P = ref_len - k + 1
+ * positions and A(x) = x rounded up to 256:  scratch = 3 * A(4 * P) + A(1024 * ceil(P / 4096)) + 8192  -- two key arrays and one
+ * position array of a dword per position, 256 dwords of digit table per tile of 4096 positions, and the scan's 2048 part sums: about
+ * 12.25 B per position, 52 GB at AIM_SEED_MAX_REF_LEN. AIM_EINVAL as aim_index_sizes, and for a NULL scratch_bytes. */
+int aim_index_device_scratch(int32_t k, uint64_t ref_len, uint64_t *scratch_bytes);
+/* The index of aim_index_build, built on the device from ASCII reference bytes already there (d_reference as for
+ * aim_align_device_ref: 16-byte aligned, >= 16 bytes of slack). d_bucket / d_pos hold what aim_index_sizes reports. Only enqueues
+ * work on hip_stream; allocates nothing; d_scratch (256-byte aligned) may be reused once the stream has passed. Afterwards d_bucket
+ * equals aim_index_build's bucket and d_pos[0, d_bucket[4^k]) its pos, byte for byte; entries of d_pos from d_bucket[4^k] on are
+ * unspecified (the call uses all of d_pos as a sort buffer). The result does not depend on the grid, on what the scratch held, or on
+ * the order in which workgroups run: a stable radix sort of the positions by code, with the counts of bucket[] the only atomics
+ * (csrc/index.hpp). AIM_EINVAL with a message naming the cause for a k outside 8..14, a ref_len above AIM_SEED_MAX_REF_LEN, a NULL
+ * buffer that the sizes make necessary (d_bucket always; d_reference, d_pos and d_scratch from ref_len >= k), a d_reference or
+ * d_scratch that is misaligned and a scratch_bytes below aim_index_device_scratch. ref_len < k is legal: an all-zero bucket and
+ * nothing else is written. */
+int aim_index_build_device(const char *d_reference, uint64_t ref_len, int32_t k, uint32_t *d_bucket, uint32_t *d_pos,
+                           void *d_scratch, uint64_t scratch_bytes, void *hip_stream);
+/* Comma-separated rocprofv3 kernel-trace name prefixes of aim_index_build_device's kernels, in launch order. */
+const char *aim_index_kernel_names(void);
 /* The seeding kernel over device buffers: ASCII read rows d_reads[n_reads][read_size] (aligned and with slack like d_patterns),
  * d_read_len[n_reads], the index of a reference of ref_len bytes, and the outputs of the rule above: d_requests
  * (aim_request_t[n_reads * K]), d_text_pos, d_votes (each [n_reads * K]) and d_seed[n_reads]. The call only enqueues work on
