@@ -131,6 +131,9 @@ __device__ __forceinline__ void nw_reg_walk(const KArgs &a, char *smem, const in
             // direction bits came eight rows at a time): the PATTERN row is staged in LDS, in the ops row itself (row byte i at OPS(i)) -- the cursor
             // never reaches a pattern byte that is still to be read (cursor - (v - 1) = h >= 1 at every step) --, the TEXT characters of a batch's eight rows
             // come with the batch (row h needs t[h - 1] only).
+            // (READ_SIZE % 16 == 8: the last piece reaches 8 bytes past the row -- the next pair's first bases or, for a batch's last pair, the first 8 of the
+            // 16 bytes of tail slack aim_hip.h asks for behind d_patterns. The walk reads pattern bytes below plen only, so what the piece brings along never
+            // matters: tests/test_full_rows_gpu.py runs full rows at READ_SIZE 104 / 120 / 136 with noise in the slack.)
             for (int b = 0; 16 * b < rs; ++b) {
                 const aim_u32x4_u w = __builtin_nontemporal_load(reinterpret_cast<const aim_u32x4_u *>(pb) + b);
                 *reinterpret_cast<uint4 *>(&OPS(16 * b)) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -661,6 +664,7 @@ __device__ __forceinline__ void swg_reg_walk(const KArgs &a, char *smem, const i
                     sentinel -= (inD_ || inI_ || dg_) ? 1 : 0; v -= (inD_ || dg_) ? 1 : 0; h -= (inI_ || dg_) ? 1 : 0;                        \
                     layer = inD_ ? ((bq_ & 0x10u) ? 2 : 0) : inI_ ? ((bq_ & 0x100000u) ? 1 : 0) : toD_ ? 2 : toI_ ? 1 : 0; } while (0)
                 // the pattern row staged in LDS in the ops area's own layout, the text characters of a batch's rows with the batch (see nw_reg_kernel)
+                // (READ_SIZE % 16 == 8: the last piece reaches 8 bytes past the row, at most into the tail slack of aim_hip.h; see nw_reg_walk)
                 for (int b = 0; 16 * b < rs; ++b) {
                     const aim_u32x4_u w = __builtin_nontemporal_load(reinterpret_cast<const aim_u32x4_u *>(pb) + b);
                     *reinterpret_cast<uint4 *>(&OPS(16 * b)) = make_uint4(w[0], w[1], w[2], w[3]);

@@ -559,7 +559,10 @@ int aim_host_free(void *ptr);
  * memory read once per process, and a smaller bound only means fewer pairs in flight (more rounds), never an error
  * unless not even one workgroup's table fits (AIM_ENOMEM).
  * d_patterns / d_texts must be 16-byte aligned and carry >= 16 bytes of
- * addressable slack after the last row (the kernels read whole 16-byte chunks). */
+ * addressable slack after the last row (the kernels read whole 16-byte chunks).
+ * A sequence may fill its row (pattern_len, text_len <= READ_SIZE): the bytes of a row behind its length, and the slack's,
+ * are never interpreted, whatever they hold; a pair of 2 * READ_SIZE operations fills its ops row from begin_offset 0.
+ * The host arrays of aim_set_push / aim_set_submit need no slack. */
 size_t aim_scratch_bytes(const aim_params_t *params, uint32_t n_pairs);
 int aim_align_device(const aim_params_t *params, uint32_t n_pairs, const void *d_requests,
                      const char *d_patterns, const char *d_texts, void *d_results,
