@@ -9,8 +9,11 @@
 // never reach (checked at compile time), so -DREDUCE is inert exactly as in the reference.
 //
 // Data path per wavefront of 64 pairs:
-//   HBM --(LDS-DMA, 1 KiB per wave-instruction, no VGPRs; the next group's DMA is issued as soon as the
-//   image is consumed and flies under the compute)--> linear LDS image --> each lane reads ITS row with
+//   HBM --(LDS-DMA, 1 KiB per wave-instruction, no VGPRs; the next group's DMA goes out piece by piece
+//   once the image is in registers: the P side between the P pack's steps, the T side and the request
+//   thinned out over the T pack, the diagonal construction and two thirds of the score loop, so that each
+//   of a CU's 8 waves has a load about to issue in every phase; all of it older than the result store,
+//   which the loop top's counted wait leaves in flight)--> linear LDS image --> each lane reads ITS row with
 //   ds_read_b128 at compile-time offsets (row = odd number of 16-B slots: conflict-free), validates the
 //   alphabet and packs 2 bits/base with v_dot4: pattern and text become RS/16 dwords each in VGPRs.
 //   affine_wfa_extend (wfa.c:186-208) becomes bit-parallel: for diagonal k, D_k = P xor (T shifted by k
@@ -34,8 +37,17 @@
 #define AIM_LANE_FULLWAIT 0       // diagnostic: 1 = drain the whole VM queue at the loop top (round-1 behaviour) instead of the counted wait
 #endif
 #ifndef AIM_LANE_INTERLEAVE
-#define AIM_LANE_INTERLEAVE 1     // 1 = the next group's 15 LDS-DMA instructions are issued one by one BETWEEN the pack steps of the
-#endif                            // current group instead of as one burst in front of them (0 = burst, round-1 structure)
+#define AIM_LANE_INTERLEAVE 2     // where the next group's 15 LDS-DMA instructions (7 P + 7 T + 1 request at READ_SIZE 112) are issued:
+#endif                            // 0 = one burst in front of the pack (round-1 structure); 1 = one piece after every pack step, all inside the
+                                  // pack phase; 2 = P as in 1, T's pieces and the request piece thinned out over the T pack, the diagonal
+                                  // construction and the score loop (LaneSpread), so that a wave has a load about to issue in every phase.
+                                  // The CIGAR instantiation stays on 1 under 2 (measured 8-10 % slower on 2, profiles/lane_issue)
+#ifndef AIM_LANE_SPREAD_PCT
+#define AIM_LANE_SPREAD_PCT 67    // schedule 2: the share of the score loop's cells by which the last piece is out (LaneSpread; 100 / 67 / 33
+#endif                            // measured, profiles/lane_issue: later pieces land later and the loop top waits for them)
+#ifndef AIM_LANE_ASM_ROWS
+#define AIM_LANE_ASM_ROWS 1       // 1 = the loop top's LDS reads (request, P rows, T rows) are one inline-asm statement the compiler does not see
+#endif                            // (read_group): it otherwise puts s_waitcnt vmcnt(0) in front of them and undoes the counted wait (-2 %)
 #ifndef AIM_LANE_NT_STORE
 #define AIM_LANE_NT_STORE 0       // 1 = score-only result stores are nontemporal
 #endif
@@ -179,6 +191,49 @@ __device__ __forceinline__ void dma_piece(uint32_t lds_off, const char *g_lane)
     __builtin_amdgcn_sched_barrier(0);   // stays where it is written: between two pack steps
 }
 
+// Schedule 2 (AIM_LANE_INTERLEAVE == 2): where the NP + 1 pieces of the T side (NP row pieces, then the request piece) go. The
+// places a piece can go to ("slots") are counted in program order: slot j + 1 follows the T pack's step j, slot NP + 1 the diagonal
+// construction, and one slot follows every cell (score, diagonal) of the score loop. due(slot) pieces are out once that slot has
+// passed: an even hand-out that ends at the cell which closes PCT percent of the score loop.
+template <int X, int O, int E, int MAXS, int NP, int PCT>
+struct LaneSpread {
+    int cells, last;
+    constexpr LaneSpread() : cells(0), last(0)
+    {
+        constexpr WfShape<X, O, E, MAXS> SH{};
+        for (int s = 0; s <= MAXS; ++s) cells += SH.present[s] ? SH.hi[s] - SH.lo[s] + 1 : 0;
+        const int c = (cells * PCT + 99) / 100;
+        last = NP + 1 + (c < 1 ? 1 : c);
+    }
+    constexpr int due(int slot) const { return slot >= last ? NP + 1 : (slot * (NP + 1)) / last; }
+};
+
+// f(integral_constant<int, I>) for from <= I < to. Both bounds are constants wherever this is called (an unrolled loop's slot
+// number run through LaneSpread::due), so what is left is the pieces themselves: no test, no branch.
+template <typename F, int... I>
+__device__ __forceinline__ void lane_pieces(int from, int to, F &f, std::integer_sequence<int, I...>)
+{
+    ((I >= from && I < to ? f(std::integral_constant<int, I>{}) : void()), ...);
+}
+// f for every piece from `first` on: one jump on a wave-uniform counter into an unrolled run (the score loop leaves early when
+// every pair of the wave has finished; what it had not issued by then goes out here), not a test per piece.
+template <int N, typename F>
+__device__ __forceinline__ void lane_pieces_from(int first, F &f)
+{
+    static_assert(N <= 8, "one case per piece");
+    switch (first) {
+    case 0: if constexpr (0 < N) f(std::integral_constant<int, 0>{}); [[fallthrough]];
+    case 1: if constexpr (1 < N) f(std::integral_constant<int, 1>{}); [[fallthrough]];
+    case 2: if constexpr (2 < N) f(std::integral_constant<int, 2>{}); [[fallthrough]];
+    case 3: if constexpr (3 < N) f(std::integral_constant<int, 3>{}); [[fallthrough]];
+    case 4: if constexpr (4 < N) f(std::integral_constant<int, 4>{}); [[fallthrough]];
+    case 5: if constexpr (5 < N) f(std::integral_constant<int, 5>{}); [[fallthrough]];
+    case 6: if constexpr (6 < N) f(std::integral_constant<int, 6>{}); [[fallthrough]];
+    case 7: if constexpr (7 < N) f(std::integral_constant<int, 7>{}); [[fallthrough]];
+    default: break;
+    }
+}
+
 template <int RS, int NCH>
 __device__ __forceinline__ void dma_rows(uint32_t lds_off, const char *base, uint32_t pair0, uint32_t n_pairs, int lane)
 {
@@ -198,12 +253,13 @@ __device__ __forceinline__ void dma_rows(uint32_t lds_off, const char *base, uin
     }
 }
 
-// The group's 64 request descriptors, HBM -> LDS. Full groups go by LDS-DMA like the rows (one wave-instruction), so the
-// loop holds NO ordinary global load: a register-destination load would make the compiler drain the whole VM queue
-// (s_waitcnt vmcnt(0)) at its first use, and that queue also holds the previous group's result store -- waiting for a
-// store's acknowledgement (~1-2 us under load) once per group is what the "residual wait" of round 1 was. The batch's
-// last, partial group is loaded per lane and written to the same LDS slots.
-__device__ __forceinline__ void stage_requests(uint32_t lds_off, uint32_t *lds_req, const KArgs &a, uint32_t pair0, int lane)
+// The group's 64 request descriptors, HBM -> LDS, by LDS-DMA like the rows (one wave-instruction for a full group), so the
+// loop holds NO ordinary global load: a register-destination load makes the compiler put s_waitcnt vmcnt(0) in front of the
+// next write of its destination register -- on every path that reaches it, the steady-state one included -- and that queue also
+// holds the previous group's result store: waiting for a store's acknowledgement (~1-2 us under load) once per group is what
+// the "residual wait" of round 1 was. The batch's last, partial group copies its requests dword by dword (no slack behind the
+// request array is needed), into the same LDS slots.
+__device__ __forceinline__ void stage_requests(uint32_t lds_off, const KArgs &a, uint32_t pair0, int lane)
 {
     const uint32_t rqb = (a.p.flags & AIM_FLAG_REQ8) ? 8u : 16u;            // bytes per request
     const char *g = reinterpret_cast<const char *>(a.req) + (uint64_t)pair0 * rqb;
@@ -211,37 +267,91 @@ __device__ __forceinline__ void stage_requests(uint32_t lds_off, uint32_t *lds_r
         if ((uint32_t)lane * 16u < kWave * rqb)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(g + (uint64_t)lane * 16),
                                              lds_at(lds_off), 16, 0, 0);
-    } else if (pair0 + lane < a.n_pairs) {
-        const aim_request_t r = load_request(a, pair0 + lane);
-        if (rqb == 8u) {
-            lds_req[lane * 2] = (uint32_t)(uint16_t)r.pattern_len | ((uint32_t)(uint16_t)r.text_len << 16);
-            lds_req[lane * 2 + 1] = r.idx;
-        } else {
-            lds_req[lane * 4] = (uint32_t)r.pattern_len; lds_req[lane * 4 + 1] = (uint32_t)r.text_len;
-            lds_req[lane * 4 + 2] = 0u; lds_req[lane * 4 + 3] = r.idx;
+    } else {
+        const uint32_t n_dw = (a.n_pairs - pair0) * (rqb / 4u);             // <= 64 * 4
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t c = i * kWave + lane;
+            if (c < n_dw)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(g + (uint64_t)c * 4),
+                                                 lds_at(lds_off + i * kWave * 4), 4, 0, 0);
         }
     }
 }
-__device__ __forceinline__ aim_request_t read_staged_request(const uint32_t *lds_req, const KArgs &a, int lane)
+
+typedef uint32_t lane_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t lane_u32x2 __attribute__((ext_vector_type(2)));
+
+// Where a lane's staged request lies: 8 bytes {plen | tlen << 16, idx} (REQ8), or 16 bytes {plen, tlen, -, idx}. Read as one
+// 8-byte word at `lo` and one dword at `hi`, so that both layouts take the same instructions (REQ8 reads idx twice).
+struct LaneReqAddr { uint32_t lo, hi; };
+__device__ __forceinline__ LaneReqAddr staged_request_addr(uint32_t lds_req_off, const KArgs &a, int lane)
+{
+    const bool r8 = a.p.flags & AIM_FLAG_REQ8;
+    LaneReqAddr q;
+    q.lo = lds_req_off + (uint32_t)lane * (r8 ? 8u : 16u);
+    q.hi = q.lo + (r8 ? 4u : 12u);
+    return q;
+}
+__device__ __forceinline__ aim_request_t decode_staged_request(const lane_u32x2 &lo, uint32_t hi, const KArgs &a)
 {
     aim_request_t r;
-    if (a.p.flags & AIM_FLAG_REQ8) {
-        const uint2 q = *reinterpret_cast<const uint2 *>(lds_req + lane * 2);
-        r.pattern_len = (int16_t)(q.x & 0xffffu); r.text_len = (int16_t)(q.x >> 16); r.padding = 0; r.idx = q.y;
-    } else {
-        const uint4 q = *reinterpret_cast<const uint4 *>(lds_req + lane * 4);
-        r.pattern_len = (int)q.x; r.text_len = (int)q.y; r.padding = 0; r.idx = q.w;
-    }
+    r.padding = 0; r.idx = hi;
+    if (a.p.flags & AIM_FLAG_REQ8) { r.pattern_len = (int16_t)(lo.x & 0xffffu); r.text_len = (int16_t)(lo.x >> 16); }
+    else { r.pattern_len = (int)lo.x; r.text_len = (int)lo.y; }
     return r;
 }
 
-// Read this lane's row, 16 B at a time at compile-time offsets (RS/16 odd => ds_read_b128 is conflict-free).
+// The loop top's LDS reads: this lane's request and its two rows, 16 B at a time at compile-time offsets (RS/16 odd =>
+// ds_read_b128 is conflict-free), all back when this returns.
+// They are ONE inline-asm statement on purpose. The compiler knows that LDS-DMA writes LDS and orders every ds_read it emits
+// behind every LDS-DMA that may still be in flight; where paths with and without a result store meet (the loop top) it can
+// only do that with s_waitcnt vmcnt(0), which also waits for the previous group's result store -- the acknowledgement latency
+// the counted wait at the loop top exists to avoid, paid once per group (stamped: 2 050 of 10 500 ticks per group sat in front
+// of the row reads). Reads it does not see it does not guard; the kernel's own counted vmcnt wait in front of this call is what
+// orders them behind the DMA. The reads and their lgkmcnt wait share the statement (early-clobber outputs) so that no register
+// is visible to the compiler, for a copy or a spill, before its data has landed.
 template <int RS, int NP>
-__device__ __forceinline__ void load_row(const uint32_t *lds_rows, int lane, uint4 (&raw)[NP])
+__device__ __forceinline__ void read_group(const LaneReqAddr &qa, uint32_t row_addr, lane_u32x2 &q_lo, uint32_t &q_hi,
+                                           lane_u32x4 (&P)[NP], lane_u32x4 (&T)[NP])
 {
-    const uint4 *row = reinterpret_cast<const uint4 *>(lds_rows + lane * (RS / 4));
+    static_assert(NP == 5 || NP == 7, "READ_SIZE 80 or 112");
+#if AIM_LANE_ASM_ROWS
+    if constexpr (NP == 7) {
+        asm volatile("ds_read_b64 %0, %[qlo]\n\tds_read_b32 %1, %[qhi]\n\t"
+                     "ds_read_b128 %2, %[row]\n\tds_read_b128 %3, %[row] offset:16\n\tds_read_b128 %4, %[row] offset:32\n\t"
+                     "ds_read_b128 %5, %[row] offset:48\n\tds_read_b128 %6, %[row] offset:64\n\tds_read_b128 %7, %[row] offset:80\n\t"
+                     "ds_read_b128 %8, %[row] offset:96\n\t"
+                     "ds_read_b128 %9, %[row] offset:%c[tb]\n\tds_read_b128 %10, %[row] offset:%c[tb]+16\n\tds_read_b128 %11, %[row] offset:%c[tb]+32\n\t"
+                     "ds_read_b128 %12, %[row] offset:%c[tb]+48\n\tds_read_b128 %13, %[row] offset:%c[tb]+64\n\tds_read_b128 %14, %[row] offset:%c[tb]+80\n\t"
+                     "ds_read_b128 %15, %[row] offset:%c[tb]+96\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(q_lo), "=&v"(q_hi), "=&v"(P[0]), "=&v"(P[1]), "=&v"(P[2]), "=&v"(P[3]), "=&v"(P[4]), "=&v"(P[5]), "=&v"(P[6]),
+                       "=&v"(T[0]), "=&v"(T[1]), "=&v"(T[2]), "=&v"(T[3]), "=&v"(T[4]), "=&v"(T[5]), "=&v"(T[6])
+                     : [qlo] "v"(qa.lo), [qhi] "v"(qa.hi), [row] "v"(row_addr), [tb] "n"(kWave * RS)
+                     : "memory");
+    } else {
+        asm volatile("ds_read_b64 %0, %[qlo]\n\tds_read_b32 %1, %[qhi]\n\t"
+                     "ds_read_b128 %2, %[row]\n\tds_read_b128 %3, %[row] offset:16\n\tds_read_b128 %4, %[row] offset:32\n\t"
+                     "ds_read_b128 %5, %[row] offset:48\n\tds_read_b128 %6, %[row] offset:64\n\t"
+                     "ds_read_b128 %7, %[row] offset:%c[tb]\n\tds_read_b128 %8, %[row] offset:%c[tb]+16\n\tds_read_b128 %9, %[row] offset:%c[tb]+32\n\t"
+                     "ds_read_b128 %10, %[row] offset:%c[tb]+48\n\tds_read_b128 %11, %[row] offset:%c[tb]+64\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(q_lo), "=&v"(q_hi), "=&v"(P[0]), "=&v"(P[1]), "=&v"(P[2]), "=&v"(P[3]), "=&v"(P[4]),
+                       "=&v"(T[0]), "=&v"(T[1]), "=&v"(T[2]), "=&v"(T[3]), "=&v"(T[4])
+                     : [qlo] "v"(qa.lo), [qhi] "v"(qa.hi), [row] "v"(row_addr), [tb] "n"(kWave * RS)
+                     : "memory");
+    }
+#else
+    typedef const __attribute__((address_space(3))) lane_u32x4 *lds_row_t;
+    q_lo = *reinterpret_cast<const __attribute__((address_space(3))) lane_u32x2 *>((uintptr_t)qa.lo);
+    q_hi = *reinterpret_cast<const __attribute__((address_space(3))) uint32_t *>((uintptr_t)qa.hi);
 #pragma unroll
-    for (int j = 0; j < NP; ++j) raw[j] = row[j];
+    for (int j = 0; j < NP; ++j) P[j] = reinterpret_cast<lds_row_t>((uintptr_t)row_addr)[j];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) T[j] = reinterpret_cast<lds_row_t>((uintptr_t)(row_addr + kWave * RS))[j];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#endif
 }
 
 // Validate A/C/G/T over [0, len) and pack 2 bits/base: 16 bases -> one dword. `after_step(integral_constant<int, j>)` runs
@@ -252,7 +362,7 @@ __device__ __forceinline__ void load_row(const uint32_t *lds_rows, int lane, uin
 // wave-uniform) test per dword it compiled to two scalar branches per dword -- 112 per group -- and the pack phase ran at
 // less than a quarter of its issue rate.
 template <int J, bool MASKED, int NP, typename StepF>
-__device__ __forceinline__ void pack_step(const uint4 (&raw)[NP], int len, uint32_t (&out)[NP], uint32_t &bad, StepF &after_step)
+__device__ __forceinline__ void pack_step(const lane_u32x4 (&raw)[NP], int len, uint32_t (&out)[NP], uint32_t &bad, StepF &after_step)
 {
     const uint32_t a[4] = {raw[J].x, raw[J].y, raw[J].z, raw[J].w};
     uint32_t b[4];
@@ -294,7 +404,7 @@ __device__ __forceinline__ void pack_step(const uint4 (&raw)[NP], int len, uint3
 }
 // FAST: steps 0 .. NP-2 unmasked (requires len >= 16*(NP-1) for every lane of the wave), last step masked; else all masked.
 template <bool FAST, int NP, typename StepF, int... J>
-__device__ __forceinline__ uint32_t pack_row_seq(const uint4 (&raw)[NP], int len, uint32_t (&out)[NP], StepF &after_step,
+__device__ __forceinline__ uint32_t pack_row_seq(const lane_u32x4 (&raw)[NP], int len, uint32_t (&out)[NP], StepF &after_step,
                                                  std::integer_sequence<int, J...>)
 {
     uint32_t bad = 0;
@@ -302,7 +412,7 @@ __device__ __forceinline__ uint32_t pack_row_seq(const uint4 (&raw)[NP], int len
     return bad;
 }
 template <bool FAST, int NP, typename StepF>
-__device__ __forceinline__ uint32_t pack_row(const uint4 (&raw)[NP], int len, uint32_t (&out)[NP], StepF after_step)
+__device__ __forceinline__ uint32_t pack_row(const lane_u32x4 (&raw)[NP], int len, uint32_t (&out)[NP], StepF after_step)
 {
     return pack_row_seq<FAST, NP>(raw, len, out, after_step, std::make_integer_sequence<int, NP>{});
 }
@@ -313,7 +423,7 @@ enum : uint32_t { LANE_TODO_COUNT = 0, LANE_TODO_LIST = 16 };   // dword offsets
 // <=> P[16j+i] != T[16j+i+k] (the layout first_stop() scans; the packed path sets one or both bits of a pair).
 // Cold path: only run for wavefronts that hold a pair with a byte outside A/C/G/T.
 template <int NP>
-__device__ __forceinline__ void raw_diag(const uint4 (&rawP)[NP], const uint4 (&rawT)[NP], int k, uint32_t (&out)[NP])
+__device__ __forceinline__ void raw_diag(const lane_u32x4 (&rawP)[NP], const lane_u32x4 (&rawT)[NP], int k, uint32_t (&out)[NP])
 {
     uint32_t pw[4 * NP], tw[4 * NP];
 #pragma unroll
@@ -355,9 +465,11 @@ __device__ __forceinline__ void raw_diag(const uint4 (&rawP)[NP], const uint4 (&
 // computed but never read. Score-only (with CIGAR the history of a 13-wide shape does not fit the register file).
 // HIST: every computed cell (after extension) and every score's final descriptor are also written to this lane's history
 // column hist[i * kWave] (int16, lane-interleaved LDS) for wfa_backtrace_dynamic.
-template <int X, int O, int E, int MAXS, int NP, int KW, bool HIST = false>
+// on_cell() runs after every extended cell, in program order (wfa_lane_kernel's schedule 2 hands out LDS-DMA pieces there).
+struct LaneNoCell { __device__ __forceinline__ void operator()() const {} };
+template <int X, int O, int E, int MAXS, int NP, int KW, bool HIST = false, typename CellF = LaneNoCell>
 __device__ __forceinline__ int wfa_scores_dynamic(const uint32_t (&dk)[KW][NP], int plen, int tlen, int ms_run, bool reduce, bool active,
-                                                  int16_t *hist = nullptr)
+                                                  int16_t *hist = nullptr, CellF on_cell = CellF{})
 {
     constexpr WfShape<X, O, E, MAXS> SH{};
     constexpr WfHist<X, O, E, MAXS> HX{};
@@ -437,6 +549,7 @@ __device__ __forceinline__ int wfa_scores_dynamic(const uint32_t (&dk)[KW][NP], 
             }
             Mv[s][kk] = off;
             if (HIST) hist[(HX.m[s] + k - SH.lo[s]) * kWave] = (int16_t)off;
+            on_cell();
         }
         // affine_wfa_reduce_wvs (WFA-adaptive, wfa.c:69-140): only shapes that can hold >= 10 diagonals get this code
         if (SH.hi[s] - SH.lo[s] + 1 >= 10) {
@@ -500,12 +613,16 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
     constexpr int NCH = RS / 16;                // 1-KiB DMA pieces per array per group (64 rows * RS / 1024)
     constexpr int NP = RS / 16;                 // packed dwords per sequence
     constexpr int KW = SH.kmax - SH.kmin + 1;
+    // schedule 2: T's pieces and the request piece reach into the score loop. Not with CIGAR: that instantiation drains the whole
+    // VM queue at the loop top and has the backtrace behind the score loop; later pieces cost it 8-10 % (profiles/lane_issue).
+    constexpr bool SPREAD_T = AIM_LANE_INTERLEAVE == 2 && !BT;
+    constexpr int NTP = NP + 1;                           // pieces of the T side: NP of rows, then the request piece
+    // (the dynamic-bounds shape was measured with the hand-out over its whole, much longer score loop only: equal to schedule 1)
+    constexpr LaneSpread<X, O, E, MAXS, NP, DYN ? 100 : AIM_LANE_SPREAD_PCT> SP{};
     extern __shared__ __attribute__((aligned(16))) char smem[];
     debug_poison_lds(a, smem);
-    uint32_t *rowsP = reinterpret_cast<uint32_t *>(smem);
-    uint32_t *rowsT = rowsP + kWave * (RS / 4);
-    uint32_t *reqL = rowsT + kWave * (RS / 4);          // 64 request descriptors (<= 16 B each)
-    uint32_t *resL = reqL + kWave * 4;                  // 64 x aim_result_t (24 B) staged for a coalesced store (CIGAR only)
+    // [64 P rows][64 T rows][64 request descriptors (<= 16 B each)][result staging]
+    uint32_t *resL = reinterpret_cast<uint32_t *>(smem) + 2 * kWave * (RS / 4) + kWave * 4;                  // 64 x aim_result_t (24 B) staged for a coalesced store (CIGAR only)
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr_t)smem;   // LDS byte offset of the dynamic segment
     const uint32_t offP = lds0, offT = lds0 + kWave * RS, offQ = lds0 + 2 * kWave * RS;
     const int lane = threadIdx.x;
@@ -517,10 +634,12 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
     uint32_t grp;
     bool have = next_group(0, &grp);
     const bool res8 = a.p.flags & AIM_FLAG_RES8;       // wave-uniform
+    const LaneReqAddr req_addr = staged_request_addr(offQ, a, lane);
+    const uint32_t row_addr = offP + (uint32_t)lane * RS;   // this lane's P row; its T row lies kWave * RS further
     if (have) {
         dma_rows<RS, NCH>(offP, a.patterns, grp * kWave, a.n_pairs, lane);
         dma_rows<RS, NCH>(offT, a.texts, grp * kWave, a.n_pairs, lane);
-        stage_requests(offQ, reqL, a, grp * kWave, lane);
+        stage_requests(offQ, a, grp * kWave, lane);
     }
     uint32_t stores_in_flight = 0;                     // result-store instructions the previous iteration issued after its DMA
 #if AIM_LANE_STAMPS
@@ -544,23 +663,21 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
         else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         AIM_STAMP(1);                           // wait for DMA
-        const aim_request_t rq = read_staged_request(reqL, a, lane);
+        // This lane's request and both its rows into registers; once they are back, every buffer of the group is free and the
+        // next group's DMA may go into it: its HBM latency flies under the pack + compute below.
+        // (Waiting for the P rows only and letting the T reads fly under the P pack was measured worth nothing, NOTES A.1
+        // item 6, and would leave registers in flight across compiler-scheduled code.)
+        lane_u32x4 rawP[NP], rawT[NP];
+        lane_u32x2 rq_lo;
+        uint32_t rq_hi;
+        __builtin_amdgcn_sched_barrier(0);
+        read_group<RS, NP>(req_addr, row_addr, rq_lo, rq_hi, rawP, rawT);
+        __builtin_amdgcn_sched_barrier(0);
+        const aim_request_t rq = decode_staged_request(rq_lo, rq_hi, a);
         const int plen = active ? rq.pattern_len : 0, tlen = active ? rq.text_len : 0;   // lanes past the batch tail read stale LDS
-        // pull both rows into registers, then immediately start the next group's DMA into the same buffer:
-        // its HBM latency flies under the pack + compute below
-        uint4 rawP[NP], rawT[NP];
-        load_row<RS, NP>(rowsP, lane, rawP);
-        __builtin_amdgcn_sched_barrier(0);      // LDS operations return in issue order: request, P rows, then T rows
-        load_row<RS, NP>(rowsT, lane, rawT);
         uint32_t ngrp = 0;
         const bool nhave = next_group(it + 1, &ngrp);
         const bool inter = AIM_LANE_INTERLEAVE && !AIM_LANE_DIAG && nhave && (ngrp + 1u) * kWave <= a.n_pairs;   // wave-uniform
-        // A buffer may be refilled once every ds_read of it has returned. Interleaved mode refills the P buffer during the P
-        // pack and the T buffer during the T pack, so only the P rows (the NP youngest reads are T's) must be back here and
-        // the T reads fly under the P pack; burst mode needs both.
-        if (inter) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(NP) : "memory");
-        else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
         AIM_STAMP(2);                           // LDS row reads
         // The next group's DMA. Issued as ONE burst, 15 KiB from each of the CU's 8 wavefronts back-pressure the vector-memory
         // queue and the wave sits in the issue of its own glds instructions (stamped: 3 350 of 13 400 ticks per group, 220 per
@@ -569,7 +686,7 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
         if (nhave && !inter) {
             dma_rows<RS, NCH>(offP, a.patterns, ngrp * kWave, a.n_pairs, lane);
             dma_rows<RS, NCH>(offT, a.texts, ngrp * kWave, a.n_pairs, lane);
-            stage_requests(offQ, reqL, a, ngrp * kWave, lane);
+            stage_requests(offQ, a, ngrp * kWave, lane);
         }
         const char *gP_next = a.patterns + (uint64_t)ngrp * (kWave * RS) + (uint32_t)lane * 16u;
         const char *gT_next = a.texts + (uint64_t)ngrp * (kWave * RS) + (uint32_t)lane * 16u;
@@ -585,6 +702,9 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
                 r.max_operations = plen + tlen; r.begin_offset = 0; r.end_offset = 0; r.score = (int)x; r.status = 0; r.idx = rq.idx;
                 store_result(a, pair, r);
             }
+            // as production: the stores stay in flight over the loop top (without this the counted wait was vmcnt(0) and every
+            // group paid the store's acknowledgement, which overstated the store's share in the removal decomposition)
+            stores_in_flight = AIM_LANE_DIAG == 1 ? (res8 ? 1u : 2u) : 0u;
             have = nhave; grp = ngrp;
             continue;
         }
@@ -594,12 +714,21 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
         uint32_t P[NP], T[NP];
         // four instantiations of the pack phase, selected by two wave-uniform tests made ONCE per group
         uint32_t bad;
+        // piece I of the next group's T side
+        auto t_piece = [&](auto I) __attribute__((always_inline)) {
+            constexpr int i = decltype(I)::value;
+            if constexpr (i < NP) dma_piece<i>(offT, gT_next);
+            else { stage_requests(offQ, a, ngrp * kWave, lane); __builtin_amdgcn_sched_barrier(0); }
+        };
         auto pack_both = [&](auto FAST, auto INTER) __attribute__((always_inline)) {
             constexpr bool fast = decltype(FAST)::value, with_dma = decltype(INTER)::value;
             bad = pack_row<fast, NP>(rawP, plen, P, [&](auto J) { if (with_dma) dma_piece<decltype(J)::value>(offP, gP_next); });
-            if (with_dma) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }   // T rows are back
-            bad |= pack_row<fast, NP>(rawT, tlen, T, [&](auto J) { if (with_dma) dma_piece<decltype(J)::value>(offT, gT_next); });
-            if (with_dma) stage_requests(offQ, reqL, a, ngrp * kWave, lane);
+            bad |= pack_row<fast, NP>(rawT, tlen, T, [&](auto J) {
+                constexpr int j = decltype(J)::value;
+                if (with_dma && SPREAD_T) lane_pieces(SP.due(j), SP.due(j + 1), t_piece, std::make_integer_sequence<int, NTP>{});
+                else if (with_dma) dma_piece<j>(offT, gT_next);
+            });
+            if (with_dma && !SPREAD_T) stage_requests(offQ, a, ngrp * kWave, lane);
         };
         const bool fast = min_len_wave >= 16 * (NP - 1);
         if (fast && inter) pack_both(std::true_type{}, std::true_type{});
@@ -618,10 +747,28 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
                 r.max_operations = plen + tlen; r.begin_offset = 0; r.end_offset = 0; r.score = (int)x; r.status = 0; r.idx = rq.idx;
                 store_result(a, pair, r);
             }
+            stores_in_flight = res8 ? 1u : 2u;
             have = nhave; grp = ngrp;
             continue;
         }
 #endif
+        const int ak = tlen - plen;   // alignment_k
+        int Mv[MAXS + 1][KW], Iv[MAXS + 1][KW], Dv[MAXS + 1][KW];
+        int score = MAXS + 1;
+        bool done = false;
+        // Diagonals and score loop, instantiated twice: with the hand-out of the T side's remaining pieces (schedule 2, the steady
+        // state) and without (burst iterations: the batch's partial last group and each wave's last one). The choice is made once
+        // per group; a run-time test at every slot would be a scalar branch per cell.
+        auto score_phase = [&](auto SPREAD) __attribute__((always_inline)) {
+        constexpr bool spread = decltype(SPREAD)::value;
+        int slot = NP, t_out = SP.due(NP);   // the T pack has passed slots 1 .. NP; both are constants at every use once the loops are unrolled
+        auto at_slot = [&]() __attribute__((always_inline)) {
+            if constexpr (spread) {
+                ++slot;
+                lane_pieces(t_out, SP.due(slot), t_piece, std::make_integer_sequence<int, NTP>{});
+                t_out = SP.due(slot);
+            }
+        };
         // ---- mismatch bit-vectors per diagonal: bit pair v of dk[k] != 0  <=>  P[v] != T[v + k] ----
         uint32_t dk[KW][NP];
         if (__ballot(active && bad != 0u) != 0ull) {
@@ -642,14 +789,12 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
                 }
             }
         }
-        const int ak = tlen - plen;   // alignment_k
+        at_slot();                    // (the cold raw-byte construction above issues nothing: its pieces go out here)
 
         // ---- affine_wfa_compute, statically unrolled over scores and diagonals -----------------
-        int Mv[MAXS + 1][KW], Iv[MAXS + 1][KW], Dv[MAXS + 1][KW];
-        int score = MAXS + 1;
-        bool done = false;
         if constexpr (DYN) {
-            score = wfa_scores_dynamic<X, O, E, MAXS, NP, KW>(dk, plen, tlen, ms_run, (a.p.flags & AIM_FLAG_REDUCE) != 0, active);
+            score = wfa_scores_dynamic<X, O, E, MAXS, NP, KW, false, decltype(at_slot)>(dk, plen, tlen, ms_run, (a.p.flags & AIM_FLAG_REDUCE) != 0, active,
+                                                                                        nullptr, at_slot);
             done = score <= ms_run;
         } else {
 #pragma unroll
@@ -708,13 +853,20 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
                 }
                 Mv[s][kk] = off;
                 if (k == ak) { m_end = off; end_in_range = true; }
+                at_slot();
             }
             if (!done && end_in_range && m_end >= tlen && s <= ms_run) { done = true; score = s; }
             if (__ballot(!done && active) == 0ull) break;   // every pair of this wave has finished
         }
         if (!done) score = ms_run + 1;                              // wfa.c:368-376
         }
-        AIM_STAMP(5);                           // diagonals + WFA
+        // The score loop ends early when every pair of the wave has finished: what it had not issued goes out now, so that every
+        // piece is older than the result store and the loop top's counted wait stays what it is.
+        if constexpr (spread) lane_pieces_from<NTP>(t_out, t_piece);
+        };
+        if (SPREAD_T && inter) score_phase(std::true_type{});
+        else score_phase(std::false_type{});
+        AIM_STAMP(5);                           // diagonals + WFA (schedule 2: and the issue of the T side's pieces)
 
         int begin_offset = plen + tlen - 1;     // edit_cigar_allocate, wfa.c:57-67
         int status = AIM_PAIR_OK;
@@ -872,7 +1024,7 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
                 }
             }
         }
-        stores_in_flight = BT ? 0u : (res8 ? 1u : 2u);   // every iteration has at least one active lane
+        stores_in_flight = (BT || AIM_LANE_DIAG == 3) ? 0u : (res8 ? 1u : 2u);   // every iteration has at least one active lane
 #if AIM_LANE_RES_STAGE
         if (full_group) {   // wave-uniform
             typedef uint32_t aim_u32x4 __attribute__((ext_vector_type(4)));
