@@ -43,6 +43,13 @@ FEATURE_SEED = 0x800         # aim_features(): device-side seeding (aim_index_* 
 SEED_MAX_CANDS, SEED_MAX_HITS, SEED_TRUNCATED, SEED_MAX_READ_SIZE = 16, 1024, 1, 4096
 SEED_MAX_REF_LEN = (1 << 32) - (1 << 25)
 FEATURE_INDEX_DEVICE = 0x1000   # aim_features(): aim_index_device_scratch / aim_index_build_device / aim_index_kernel_names exist
+FEATURE_MINIMIZERS = 0x2000     # aim_features(): aim_index_build_minimizers / aim_index_build_device_minimizers / SEED_OPT_MINIMIZERS exist
+SEED_MAX_W = 32                 # AIM_SEED_MAX_W: the minimizer window is 1..32
+
+
+def SEED_OPT_MINIMIZERS(w):
+    """AIM_SEED_OPT_MINIMIZERS(w), for aim_seed_params_t.options."""
+    return (int(w) << 8) & 0xFFFFFFFF
 SAM_EQX, SAM_REVERSE, SAM_UNMAPPED, SAM_OVERFLOW = 0x1, 0x10, 0x4, 0x100   # sam_options; aim_sam_t.flags (SAM's own bits); aim_sam_t.status bit
 MATE_PROPER = 1              # aim_mate_t.flags: the chosen candidates are a proper combination
 PAIR_OK, PAIR_WFA_NO_LINK, PAIR_SWG_NO_OP, PAIR_NOMEM = 0, 1, 2, 3
@@ -222,6 +229,9 @@ SYMBOLS = {
     "aim_index_device_scratch": (C.c_int, [_I32, C.c_uint64, C.POINTER(C.c_uint64)]),
     "aim_index_build_device": (C.c_int, [_VP, C.c_uint64, _I32, _VP, _VP, _VP, C.c_uint64, _VP]),
     "aim_index_kernel_names": (C.c_char_p, []),
+    "aim_index_build_minimizers": (C.c_int, [_VP, C.c_uint64, _I32, _I32, _VP, _VP, C.POINTER(C.c_uint64), C.c_int]),
+    "aim_index_build_device_minimizers": (C.c_int, [_VP, C.c_uint64, _I32, _I32, _VP, _VP, _VP, C.c_uint64, _VP]),
+    "aim_minimizer_kernel_names": (C.c_char_p, []),
 }
 
 _lib = None

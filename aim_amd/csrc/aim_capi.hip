@@ -1673,7 +1673,7 @@ uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
            AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS | AIM_FEATURE_SEED |
-           AIM_FEATURE_INDEX_DEVICE;
+           AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -3066,7 +3066,17 @@ int check_seed_params(const aim_seed_params_t &sp)
         return fail(AIM_EINVAL, "aim_seed_params_t: max_cands %d is outside 1..%d", sp.max_cands, AIM_SEED_MAX_CANDS);
     if (sp.read_size <= 0 || (sp.read_size & 7) || sp.read_size > AIM_SEED_MAX_READ_SIZE)
         return fail(AIM_EINVAL, "aim_seed_params_t: read_size %d must be a positive multiple of 8, at most %d", sp.read_size, AIM_SEED_MAX_READ_SIZE);
-    if (sp.options) return fail(AIM_EINVAL, "aim_seed_params_t: unknown options 0x%x", sp.options);
+    if (sp.options) {   // AIM_SEED_OPT_MINIMIZERS(w) and nothing else
+        const uint32_t w = sp.options >> 8;
+        if ((sp.options & 0xffu) || w < 1 || w > AIM_SEED_MAX_W) return fail(AIM_EINVAL, "aim_seed_params_t: unknown options 0x%x", sp.options);
+        if (sp.stride != 1) return fail(AIM_EINVAL, "aim_seed_params_t: stride %d must be 1 with AIM_SEED_OPT_MINIMIZERS", sp.stride);
+    }
+    return AIM_OK;
+}
+
+int check_window(int32_t w)
+{
+    if (w < 1 || w > AIM_SEED_MAX_W) return fail(AIM_EINVAL, "seed index: w %d is outside 1..%d", w, AIM_SEED_MAX_W);
     return AIM_OK;
 }
 
@@ -3089,6 +3099,83 @@ void index_scan(const char *seq, uint64_t len, int k, uint32_t c_lo, uint32_t c_
         if (good >= (uint32_t)k && code >= c_lo && code < c_hi) visit(code, (uint32_t)(i + 1 - (uint64_t)k));
     }
 }
+
+// index_scan over the (w, k) minimizers alone (the rule in aim_hip.h, by its window definition): the windows slide with the scan, and a
+// monotone queue of at most w candidates -- keys strictly ascending from its front, so the front is the window's leftmost smallest --
+// names each window's minimizer. Those are ascending in p from window to window, so a position is visited once, when it first wins.
+template <typename F>
+void minimizer_scan(const char *seq, uint64_t len, int k, int w, uint32_t c_lo, uint32_t c_hi, F visit)
+{
+    if (len < (uint64_t)k) return;
+    const uint64_t n = len - (uint64_t)k + 1u, full = std::min<uint64_t>((uint64_t)w, n);   // positions; positions in a window
+    constexpr uint64_t invalid = 1ull << 32;                 // above every min_hash
+    uint64_t q_key[AIM_SEED_MAX_W], q_pos[AIM_SEED_MAX_W];   // a ring: head, size
+    uint32_t q_code[AIM_SEED_MAX_W];
+    uint32_t head = 0, size = 0, code = 0, good = 0;
+    uint64_t last = UINT64_MAX;
+    const int top = 2 * (k - 1);
+    for (uint64_t i = 0; i < len; ++i) {
+        const unsigned char c = (unsigned char)seq[i];
+        if (c == 'A' || c == 'C' || c == 'G' || c == 'T') {
+            code = (code >> 2) | ((uint32_t)((c >> 1) & 3) << top);
+            ++good;
+        } else {
+            code = 0;
+            good = 0;
+        }
+        if (i + 1 < (uint64_t)k) continue;
+        const uint64_t p = i + 1 - (uint64_t)k;              // the k-mer that ends here
+        const uint64_t key = good >= (uint32_t)k ? aim::min_hash(code) : invalid;
+        while (size && q_pos[head] + full <= p) head = (head + 1) % AIM_SEED_MAX_W, --size;   // the window is [p + 1 - full, p]: < w others remain
+        while (size && q_key[(head + size - 1) % AIM_SEED_MAX_W] > key) --size;
+        const uint32_t at = (head + size) % AIM_SEED_MAX_W;
+        q_key[at] = key, q_pos[at] = p, q_code[at] = code;
+        ++size;
+        if (p + 1 < full) continue;                          // the first window is not complete yet
+        if (q_key[head] != invalid && q_pos[head] != last) {
+            last = q_pos[head];
+            if (q_code[head] >= c_lo && q_code[head] < c_hi) visit(q_code[head], (uint32_t)last);
+        }
+    }
+}
+
+// The body of aim_index_build and aim_index_build_minimizers: a counting sort in two passes of `scan(lo, hi, visit)` per worker.
+template <typename S>
+int index_build_with(const char *seq, uint64_t ref_len, int32_t k, uint32_t *bucket, uint32_t *pos, uint64_t *n_pos, int threads, S scan)
+{
+    const bool any = ref_len >= (uint64_t)k;
+    if (!bucket || (ref_len && !seq) || (any && !pos)) return fail(AIM_EINVAL, "seed index: NULL seq, bucket or pos");
+    const uint64_t n_codes = 1ull << (2 * k);
+    const int T = std::max(1, std::min(threads, 64));
+    // every worker owns the codes [n_codes * t / T, n_codes * (t + 1) / T): its counts and, later, its runs of pos[] are its own
+    auto range = [&](int t) { return (uint32_t)(n_codes * (uint64_t)t / (uint64_t)T); };
+    auto run = [&](auto body) {
+        std::vector<std::thread> th;
+        for (int t = 1; t < T; ++t) th.emplace_back(body, t);
+        body(0);
+        for (auto &x : th) x.join();
+    };
+    // pass 1: counts, shifted by one so that the prefix sum below leaves bucket[c] = first entry of code c
+    run([&](int t) {
+        const uint32_t lo = range(t), hi = t + 1 == T ? (uint32_t)n_codes : range(t + 1);
+        memset(bucket + (size_t)lo + 1, 0, (size_t)(hi - lo) * sizeof(uint32_t));
+        if (any) scan(lo, hi, [&](uint32_t c, uint32_t) { ++bucket[(size_t)c + 1]; });
+    });
+    bucket[0] = 0;
+    for (uint64_t c = 0; c < n_codes; ++c) bucket[c + 1] += bucket[c];
+    const uint64_t total = bucket[n_codes];
+    // pass 2: bucket[c] is code c's cursor; afterwards it holds bucket[c + 1], and one shift restores the prefix sums
+    if (total) {
+        run([&](int t) {
+            const uint32_t lo = range(t), hi = t + 1 == T ? (uint32_t)n_codes : range(t + 1);
+            scan(lo, hi, [&](uint32_t c, uint32_t p) { pos[bucket[c]++] = p; });
+        });
+        for (uint64_t c = n_codes; c > 0; --c) bucket[c] = bucket[c - 1];
+        bucket[0] = 0;
+    }
+    if (n_pos) *n_pos = total;
+    return AIM_OK;
+}
 }  // namespace
 }  // extern "C++"
 
@@ -3106,38 +3193,17 @@ int aim_index_build(const char *seq, uint64_t ref_len, int32_t k, uint32_t *buck
 {
     int rc = check_index_args(k, ref_len);
     if (rc) return rc;
-    const bool any = ref_len >= (uint64_t)k;
-    if (!bucket || (ref_len && !seq) || (any && !pos)) return fail(AIM_EINVAL, "seed index: NULL seq, bucket or pos");
-    const uint64_t n_codes = 1ull << (2 * k);
-    const int T = std::max(1, std::min(threads, 64));
-    // every worker owns the codes [n_codes * t / T, n_codes * (t + 1) / T): its counts and, later, its runs of pos[] are its own
-    auto range = [&](int t) { return (uint32_t)(n_codes * (uint64_t)t / (uint64_t)T); };
-    auto run = [&](auto body) {
-        std::vector<std::thread> th;
-        for (int t = 1; t < T; ++t) th.emplace_back(body, t);
-        body(0);
-        for (auto &x : th) x.join();
-    };
-    // pass 1: counts, shifted by one so that the prefix sum below leaves bucket[c] = first entry of code c
-    run([&](int t) {
-        const uint32_t lo = range(t), hi = t + 1 == T ? (uint32_t)n_codes : range(t + 1);
-        memset(bucket + (size_t)lo + 1, 0, (size_t)(hi - lo) * sizeof(uint32_t));
-        if (any) index_scan(seq, ref_len, k, lo, hi, [&](uint32_t c, uint32_t) { ++bucket[(size_t)c + 1]; });
-    });
-    bucket[0] = 0;
-    for (uint64_t c = 0; c < n_codes; ++c) bucket[c + 1] += bucket[c];
-    const uint64_t total = bucket[n_codes];
-    // pass 2: bucket[c] is code c's cursor; afterwards it holds bucket[c + 1], and one shift restores the prefix sums
-    if (total) {
-        run([&](int t) {
-            const uint32_t lo = range(t), hi = t + 1 == T ? (uint32_t)n_codes : range(t + 1);
-            index_scan(seq, ref_len, k, lo, hi, [&](uint32_t c, uint32_t p) { pos[bucket[c]++] = p; });
-        });
-        for (uint64_t c = n_codes; c > 0; --c) bucket[c] = bucket[c - 1];
-        bucket[0] = 0;
-    }
-    if (n_pos) *n_pos = total;
-    return AIM_OK;
+    return index_build_with(seq, ref_len, k, bucket, pos, n_pos, threads,
+                            [&](uint32_t lo, uint32_t hi, auto visit) { index_scan(seq, ref_len, k, lo, hi, visit); });
+}
+
+int aim_index_build_minimizers(const char *seq, uint64_t ref_len, int32_t k, int32_t w, uint32_t *bucket, uint32_t *pos, uint64_t *n_pos, int threads)
+{
+    int rc = check_index_args(k, ref_len);
+    if (!rc) rc = check_window(w);
+    if (rc) return rc;
+    return index_build_with(seq, ref_len, k, bucket, pos, n_pos, threads,
+                            [&](uint32_t lo, uint32_t hi, auto visit) { minimizer_scan(seq, ref_len, k, w, lo, hi, visit); });
 }
 
 int aim_seed_groups_offsets(uint32_t n_reads, uint32_t K, uint32_t *read_offsets)
@@ -3182,15 +3248,21 @@ int aim_seed_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t
     a.text_pos = d_text_pos;
     a.votes = d_votes;
     a.seed = d_seed;
-    const size_t lds = aim::seed_lds_bytes(sp->read_size);
+    const bool minimizers = sp->options != 0;
+    const size_t lds = minimizers ? aim::seed_minimizer_lds_bytes(sp->read_size) : aim::seed_lds_bytes(sp->read_size);
     a.dbg_poison_lds = kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u;
     a.dbg_lds_bytes = (uint32_t)lds;
     // persistent grid: what LDS lets one CU hold (at most 16 wavefronts), on every CU, capped at the reads rounded up to the multiple of 8
     // xcd_unit needs (below 8 reads the surplus workgroups find no work and leave)
     const uint32_t per_cu = (uint32_t)std::min<size_t>(16, aim::lds_workgroups_per_cu(lds));
     const uint32_t grid = std::min(aim::resident_grid(kn, per_cu), (uint32_t)std::min<uint64_t>(((uint64_t)n_reads + 7u) & ~7ull, 1u << 20));
-    if (kn.plan_debug) fprintf(stderr, "[aim plan] seed_candidates_kernel grid=%u block=64 lds=%zu per_cu=%u reads=%u\n", grid, lds, per_cu, n_reads);
-    aim::seed_launch(a, grid, lds, (hipStream_t)hip_stream);
+    if (kn.plan_debug)
+        fprintf(stderr, "[aim plan] %s grid=%u block=64 lds=%zu per_cu=%u reads=%u\n", minimizers ? "seed_minimizer_kernel" : "seed_candidates_kernel", grid, lds,
+                per_cu, n_reads);
+    if (minimizers)
+        aim::seed_minimizer_launch(a, grid, lds, (hipStream_t)hip_stream);
+    else
+        aim::seed_launch(a, grid, lds, (hipStream_t)hip_stream);
     HIP_TRY(hipGetLastError());
     return AIM_OK;
 }
@@ -3212,8 +3284,13 @@ const char *aim_index_kernel_names(void)
     return "index_code_kernel,index_scan_sums_kernel,index_scan_top_kernel,index_scan_apply_kernel,index_hist_kernel,index_scatter_kernel";
 }
 
-int aim_index_build_device(const char *d_reference, uint64_t ref_len, int32_t k, uint32_t *d_bucket, uint32_t *d_pos, void *d_scratch,
-                           uint64_t scratch_bytes, void *hip_stream)
+const char *aim_minimizer_kernel_names(void) { return "index_minimizer_kernel,seed_minimizer_kernel"; }
+
+extern "C++" {
+namespace {
+// aim_index_build_device (w = 0: index_code_kernel) and aim_index_build_device_minimizers (w >= 1: index_minimizer_kernel in its place)
+int index_build_device(const char *d_reference, uint64_t ref_len, int32_t k, int32_t w, uint32_t *d_bucket, uint32_t *d_pos, void *d_scratch,
+                       uint64_t scratch_bytes, void *hip_stream)
 {
     int rc = check_index_args(k, ref_len);
     if (rc) return rc;
@@ -3276,9 +3353,18 @@ int aim_index_build_device(const char *d_reference, uint64_t ref_len, int32_t k,
     a.bucket = d_bucket;
     a.dbg_poison_lds = poison_lds;
     a.key_out = keys[0];
-    if (kn.plan_debug)
-        fprintf(stderr, "[aim plan] index_code_kernel grid=%u block=%d k=%d positions=%llu tiles=%u\n", grid, aim::kIndexThreads, k, (unsigned long long)L.n, L.n_tiles);
-    aim::index_launch_code(a, grid, stream);
+    a.w = w;
+    if (w) {   // 7 workgroups per CU: what its LDS allows (index.hpp)
+        const uint32_t grid_m = std::min(aim::resident_grid(kn, 7), L.n_tiles);
+        if (kn.plan_debug)
+            fprintf(stderr, "[aim plan] index_minimizer_kernel grid=%u block=%d k=%d w=%d positions=%llu tiles=%u\n", grid_m, aim::kIndexThreads, k, w,
+                    (unsigned long long)L.n, L.n_tiles);
+        aim::index_launch_minimizer(a, grid_m, stream);
+    } else {
+        if (kn.plan_debug)
+            fprintf(stderr, "[aim plan] index_code_kernel grid=%u block=%d k=%d positions=%llu tiles=%u\n", grid, aim::kIndexThreads, k, (unsigned long long)L.n, L.n_tiles);
+        aim::index_launch_code(a, grid, stream);
+    }
     HIP_TRY(hipGetLastError());
     scan(d_bucket, n_codes + 1u, "bucket");
     HIP_TRY(hipGetLastError());
@@ -3303,6 +3389,22 @@ int aim_index_build_device(const char *d_reference, uint64_t ref_len, int32_t k,
         HIP_TRY(hipGetLastError());
     }
     return AIM_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int aim_index_build_device(const char *d_reference, uint64_t ref_len, int32_t k, uint32_t *d_bucket, uint32_t *d_pos, void *d_scratch,
+                           uint64_t scratch_bytes, void *hip_stream)
+{
+    return index_build_device(d_reference, ref_len, k, 0, d_bucket, d_pos, d_scratch, scratch_bytes, hip_stream);
+}
+
+int aim_index_build_device_minimizers(const char *d_reference, uint64_t ref_len, int32_t k, int32_t w, uint32_t *d_bucket, uint32_t *d_pos,
+                                      void *d_scratch, uint64_t scratch_bytes, void *hip_stream)
+{
+    const int rc = check_window(w);
+    if (rc) return rc;
+    return index_build_device(d_reference, ref_len, k, w, d_bucket, d_pos, d_scratch, scratch_bytes, hip_stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -8,6 +8,8 @@
 //
 //   index_code_kernel       keys[p] from the reference bytes (a tile and its k - 1 bytes of halo staged in LDS), and the count of every
 //                           code into bucket[] with integer atomics -- counts only: a sum does not depend on the order of arrival.
+//   index_minimizer_kernel  aim_index_build_device_minimizers' code pass, in index_code_kernel's place: the code only for the (w, k)
+//                           minimizers of the reference, the key 4^k for every other position (described above the kernel).
 //   index_scan_*_kernel     exclusive prefix sum of a uint32 array in three launches (sums of up to kIndexScanParts contiguous parts; the
 //                           scan of those sums by one workgroup; every part rescanned from its offset). Used once over bucket[] and
 //                           once per pass over the digit table.
@@ -30,12 +32,15 @@
 // cycles per step, against 8 ballots and two global accesses per entry); a repeat-heavy tile has few leaders and no collisions. The
 // base pass reads and writes counters at stride 256 dwords per thread over consecutive digits: consecutive banks per half. The code
 // kernel reads the staged tile byte by byte: four consecutive lanes share a dword (broadcast), a half covers 8 consecutive dwords.
-// The scan kernels keep 16 wave totals in LDS and every lane reads the same ones (broadcast).
+// The scan kernels keep 16 wave totals in LDS and every lane reads the same ones (broadcast). The minimizer kernel's neighbour reads
+// hk[i - d] / hk[i + d] are consecutive dwords over the lanes at every distance d: 32 distinct banks per half.
 //
 // OCCUPANCY. 256 threads per workgroup. LDS is 4 KB (counters) or 4 112 B (tile + halo): four 1 280-B granules, so LDS allows 32
 // workgroups per CU and is never the limit. The register bounds below keep 8 workgroups (8 wavefronts per SIMD, the hardware cap) for
 // the streaming kernels; the scatter kernel holds 16 keys, 16 positions and 16 ranks per lane and is planned at 128 registers = 4
-// wavefronts per SIMD, enough to hide its two dependent global accesses per entry. No scratch memory in any of them.
+// wavefronts per SIMD, enough to hide its two dependent global accesses per entry. The minimizer kernel keeps the staged bytes of a
+// tile and its halo (4 176 B) and one key per staged position (16 632 B): 20 816 B, 17 granules, 7 workgroups per CU = 7 wavefronts per
+// SIMD, LDS-bound, with registers (64) for 8. No scratch memory in any of them.
 //
 // BYTES PER POSITION (P passes): code 1 read + 4 written; every pass reads the keys twice (histogram, scatter), the positions once from
 // pass 1 on, and writes keys (not in the last pass) and positions: 5 + 16 + 20 (P - 2) + 16 = 57 B at P = 3 and 77 B at P = 4, plus
@@ -44,6 +49,7 @@
 #pragma once
 
 #include "aim_device.hpp"
+#include "minimizer.hpp"
 
 namespace aim {
 
@@ -61,6 +67,12 @@ constexpr int kIndexScanSumsMaxVgpr = 64;
 constexpr int kIndexScanTopMaxVgpr = 64;
 constexpr int kIndexScanApplyMaxVgpr = 64;
 constexpr int kIndexScatterMaxVgpr = 128;
+constexpr int kIndexMinimizerMaxVgpr = 64;                 // (tests/test_minimizers_cpu.py)
+constexpr uint32_t kIndexMaxW = AIM_SEED_MAX_W;
+// index_minimizer_kernel stages the tile, w - 1 positions of halo on each side, k - 1 bytes behind, and up to 3 bytes in front that
+// align the first staged byte to a dword
+constexpr uint32_t kIndexMinKeys = kIndexTile + 2 * (kIndexMaxW - 1);
+constexpr uint32_t kIndexMinBytes = (kIndexMinKeys + (uint32_t)kMinMaxK - 1 + 3 + 15) / 16 * 16;
 
 inline int index_passes(int32_t k) { return (2 * k + 1 + 7) / 8; }
 
@@ -100,6 +112,7 @@ struct IndexArgs {
     uint32_t *table;                   // [256][n_tiles]
     uint32_t *bucket;
     uint32_t dbg_poison_lds;           // as in KArgs (AIM_DEBUG_POISON_LDS)
+    int32_t w;                         // index_minimizer_kernel alone: the window, 1..kIndexMaxW
 };
 
 struct IndexScanArgs {
@@ -158,6 +171,19 @@ __device__ __forceinline__ uint32_t index_count_step(uint32_t *mine, uint32_t d,
     return old + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
 }
 
+// Counts of the code pass: a run of equal codes in the wavefront (consecutive positions: poly-A, satellites) is one add of its length.
+__device__ __forceinline__ void index_count_keys(uint32_t *bucket, uint32_t key, uint32_t sentinel, int lane)
+{
+    const uint32_t prev = __shfl_up(key, 1, kWave);
+    const bool change = lane == 0 || prev != key;
+    const uint64_t chg = __ballot(change);
+    if (change && key != sentinel) {
+        const uint64_t above = lane == kWave - 1 ? 0ull : chg >> (lane + 1);
+        const uint32_t len = above ? (uint32_t)__ffsll((unsigned long long)above) : (uint32_t)(kWave - lane);
+        atomicAdd(&bucket[key], len);
+    }
+}
+
 __global__ __launch_bounds__(kIndexThreads) void index_code_kernel(IndexArgs a)
 {
     __shared__ __align__(16) uint32_t tile4[(kIndexTile + 16) / 4];
@@ -191,15 +217,80 @@ __global__ __launch_bounds__(kIndexThreads) void index_code_kernel(IndexArgs a)
             }
             const uint32_t key = ok ? code : sentinel;
             if (valid) a.key_out[i] = key;
-            // counts: a run of equal codes in the wavefront (consecutive positions: poly-A, satellites) is one add of its length
-            const uint32_t prev = __shfl_up(key, 1, kWave);
-            const bool change = lane == 0 || prev != key;
-            const uint64_t chg = __ballot(change);
-            if (change && key != sentinel) {
-                const uint64_t above = lane == kWave - 1 ? 0ull : chg >> (lane + 1);
-                const uint32_t len = above ? (uint32_t)__ffsll((unsigned long long)above) : (uint32_t)(kWave - lane);
-                atomicAdd(&a.bucket[key], len);
+            index_count_keys(a.bucket, key, sentinel, lane);
+        }
+    }
+}
+
+// The code pass of aim_index_build_device_minimizers: index_code_kernel with one more condition on a position -- it keeps its code only
+// when it is a (w, k) minimizer of the reference (the rule in aim_hip.h), and gets the sentinel 4^k otherwise. Everything behind the
+// code pass sees keys and counts as before.
+//   stage   the bytes of the positions [plo, phi) = the tile and w - 1 positions on each side, clamped to [0, n), and the k - 1 bytes
+//           behind the last one: dwords from the aligned byte below plo (the reference has 16 bytes of slack behind ref_len).
+//   keys    hk[q - plo] = min_hash(code) of every staged position, kMinInvalid where the k-mer is invalid: each key computed once per
+//           tile (the halo positions a second time by the neighbouring tile: 2 (w - 1) / kIndexTile, 1.5 % at w = 32).
+//   select  the local test: a valid position i is selected iff L + R + 1 >= min(w, n), L the run of strictly greater keys to its left,
+//           R the run of greater-or-equal keys to its right, each capped at w - 1 and at the sequence's ends. The staged range covers
+//           exactly those neighbours. The loop over the distance d ends as soon as no lane of the wavefront still extends a run.
+// LDS: 4 176 B of bytes + 16 632 B of keys, 20 816 B static with alignment, 17 granules of 1 280 B: 7 workgroups per CU (7 wavefronts per SIMD),
+// which LDS bounds; kIndexMinimizerMaxVgpr = 64 would allow 8. No scratch. BANKS: the key pass reads bytes like index_code_kernel
+// (four lanes share a dword) and writes consecutive dwords; the neighbour reads hk[li - d] / hk[li + d] are ds_read_b32 of consecutive
+// dwords over the lanes at every d: 32 distinct banks per half, conflict-free.
+// BYTES PER POSITION: 1 read + 4 written, as index_code_kernel, plus the halo's share.
+__global__ __launch_bounds__(kIndexThreads) void index_minimizer_kernel(IndexArgs a)
+{
+    __shared__ __align__(16) uint32_t tile4[kIndexMinBytes / 4];
+    __shared__ __align__(16) uint32_t hk[kIndexMinKeys];
+    debug_poison_lds(a.dbg_poison_lds, (uint32_t)sizeof tile4, reinterpret_cast<char *>(tile4));
+    debug_poison_lds(a.dbg_poison_lds, (uint32_t)sizeof hk, reinterpret_cast<char *>(hk));
+    const uint8_t *tile = reinterpret_cast<const uint8_t *>(tile4);
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    const int32_t k = a.k;
+    const uint32_t sentinel = 1u << (2 * k);
+    const uint32_t reach = min((uint32_t)a.w, kIndexMaxW) - 1u;                     // neighbours looked at on each side
+    const uint32_t need = (uint32_t)min((uint64_t)(reach + 1u), a.n);               // min(w, n)
+    for (uint32_t t = blockIdx.x; t < a.n_tiles; t += gridDim.x) {
+        const uint64_t base = (uint64_t)t * kIndexTile;
+        const uint64_t plo = base >= reach ? base - reach : 0u;                     // (base is 0 or at least kIndexTile: plo = 0 only in tile 0)
+        const uint64_t phi = min(base + kIndexTile + reach, a.n);                   // staged positions [plo, phi), phi - plo <= kIndexMinKeys
+        const uint64_t b0 = plo & ~3ull;
+        const uint32_t skew = (uint32_t)(plo - b0);                                 // staged position q's bytes start at tile + skew + (q - plo)
+        const uint32_t nk = (uint32_t)(phi - plo);
+        const uint32_t nd = (nk + skew + (uint32_t)(k - 1) + 3u) >> 2;              // <= kIndexMinBytes / 4; phi + k - 1 <= ref_len
+        __syncthreads();   // the previous tile has been read
+        const uint32_t *g = reinterpret_cast<const uint32_t *>(a.ref + b0);
+        for (uint32_t w = (uint32_t)tid; w < nd; w += kIndexThreads) tile4[w] = g[w];
+        __syncthreads();
+        for (uint32_t q = (uint32_t)tid; q < nk; q += kIndexThreads) {
+            const uint8_t *f = tile + skew + q;
+            uint32_t code = 0;
+            bool ok = true;
+            for (int j = 0; j < k; ++j) {
+                const uint32_t x = f[j];
+                ok = ok && index_is_base(x);
+                code |= ((x >> 1) & 3u) << (2 * j);
             }
+            hk[q] = ok ? min_hash(code) : kMinInvalid;
+        }
+        __syncthreads();
+        const uint32_t off = (uint32_t)(base - plo);                                // hk index of the tile's first position
+        for (int r = 0; r < kIndexSteps; ++r) {
+            const uint32_t lp = (uint32_t)(r * kIndexThreads + tid);
+            const uint64_t i = base + lp;
+            const bool valid = i < a.n;
+            const uint32_t li = off + lp;
+            const uint32_t mine = valid ? hk[li] : kMinInvalid;
+            bool left = mine != kMinInvalid, right = left;                          // the run on that side still extends
+            uint32_t span = 1;                                                      // L + R + 1
+            for (uint32_t d = 1; d <= reach; ++d) {
+                if (!__ballot(left || right)) break;
+                left = left && li >= d && hk[li - d] > mine;
+                right = right && li + d < nk && hk[li + d] >= mine;
+                span += (uint32_t)left + (uint32_t)right;
+            }
+            const uint32_t key = mine != kMinInvalid && span >= need ? min_unhash(mine) : sentinel;
+            if (valid) a.key_out[i] = key;
+            index_count_keys(a.bucket, key, sentinel, lane);
         }
     }
 }
@@ -378,6 +469,7 @@ __global__ __launch_bounds__(kIndexThreads) void index_scan_apply_kernel(IndexSc
 }
 
 void index_launch_code(const IndexArgs &a, uint32_t grid, hipStream_t s) { hipLaunchKernelGGL(index_code_kernel, dim3(grid), dim3(kIndexThreads), 0, s, a); }
+void index_launch_minimizer(const IndexArgs &a, uint32_t grid, hipStream_t s) { hipLaunchKernelGGL(index_minimizer_kernel, dim3(grid), dim3(kIndexThreads), 0, s, a); }
 void index_launch_hist(const IndexArgs &a, uint32_t grid, hipStream_t s) { hipLaunchKernelGGL(index_hist_kernel, dim3(grid), dim3(kIndexThreads), 0, s, a); }
 void index_launch_scatter(const IndexArgs &a, uint32_t grid, hipStream_t s) { hipLaunchKernelGGL(index_scatter_kernel, dim3(grid), dim3(kIndexThreads), 0, s, a); }
 void index_launch_scan(const IndexScanArgs &a, hipStream_t s)
@@ -388,6 +480,7 @@ void index_launch_scan(const IndexScanArgs &a, hipStream_t s)
 }
 #else
 void index_launch_code(const IndexArgs &a, uint32_t grid, hipStream_t s);
+void index_launch_minimizer(const IndexArgs &a, uint32_t grid, hipStream_t s);
 void index_launch_hist(const IndexArgs &a, uint32_t grid, hipStream_t s);
 void index_launch_scatter(const IndexArgs &a, uint32_t grid, hipStream_t s);
 void index_launch_scan(const IndexScanArgs &a, hipStream_t s);   // sums, top, apply

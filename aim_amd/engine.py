@@ -452,6 +452,18 @@ def build_index(reference, k, threads=8):
     return bucket, pos[:n.value]
 
 
+def index_build_minimizers(reference, k, w, threads=8):
+    """aim_index_build_minimizers on the host: build_index over the (w, k) minimizers of `reference` alone. pos holds n_pos entries,
+    about 2 / (w + 1) of the positions on random sequence; w = 1 gives build_index's arrays."""
+    ref = np.ascontiguousarray(np.frombuffer(reference, dtype=np.uint8) if isinstance(reference, (bytes, bytearray)) else reference, dtype=np.uint8)
+    be, pc = index_sizes(k, len(ref))
+    bucket = np.zeros(be, dtype=np.uint32)
+    pos = np.zeros(max(pc, 1), dtype=np.uint32)
+    n = C.c_uint64()
+    capi.check(capi.load().aim_index_build_minimizers(capi.ptr(ref), len(ref), int(k), int(w), capi.ptr(bucket), capi.ptr(pos), C.byref(n), int(threads)))
+    return bucket, pos[:n.value].copy()     # (the capacity is an upper bound: keep pos[0, n_pos) alone)
+
+
 def index_device_scratch(k, ref_len):
     """aim_index_device_scratch: bytes of device scratch build_index_device / aim_index_build_device need (0 below k)."""
     sb = C.c_uint64()
@@ -464,11 +476,18 @@ def index_build_device(d_reference, ref_len, k, d_bucket, d_pos, d_scratch, scra
     capi.check(capi.load().aim_index_build_device(d_reference, int(ref_len), int(k), d_bucket, d_pos, d_scratch, int(scratch_bytes), stream))
 
 
-def build_index_device(reference, k, device="cuda:0", stream=None):
+def index_build_device_minimizers(d_reference, ref_len, k, w, d_bucket, d_pos, d_scratch, scratch_bytes, stream=None):
+    """aim_index_build_device_minimizers on device pointers: index_build_device over the (w, k) minimizers of the reference alone."""
+    capi.check(capi.load().aim_index_build_device_minimizers(d_reference, int(ref_len), int(k), int(w), d_bucket, d_pos, d_scratch, int(scratch_bytes),
+                                                             stream))
+
+
+def build_index_device(reference, k, device="cuda:0", stream=None, w=None):
     """The index of build_index, built on the device. `reference` is bytes, a uint8 numpy array, or a uint8 torch tensor that already
     lives on `device` with at least 16 bytes of slack behind the reference (then ref_len is its length minus 16). Returns
     (d_bucket, d_pos, n_pos): uint8 device tensors in the form seed_candidates accepts for `index`, and bucket[4^k]. d_pos has room
-    for ref_len - k + 1 positions; the entries from n_pos on are unspecified. The scratch is allocated here and freed on return."""
+    for ref_len - k + 1 positions; the entries from n_pos on are unspecified. The scratch is allocated here and freed on return.
+    With a window `w` the index holds the (w, k) minimizers alone (index_build_device_minimizers)."""
     import torch
     dev = torch.device(device)
     if isinstance(reference, torch.Tensor):
@@ -487,14 +506,19 @@ def build_index_device(reference, k, device="cuda:0", stream=None):
     d_scr = torch.empty(max(sb, 256), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         s = torch.cuda.current_stream(dev) if stream is None else stream
-        index_build_device(d_ref.data_ptr(), ref_len, k, d_bucket.data_ptr(), d_pos.data_ptr(), d_scr.data_ptr(), sb, s.cuda_stream)
+        if w is None:
+            index_build_device(d_ref.data_ptr(), ref_len, k, d_bucket.data_ptr(), d_pos.data_ptr(), d_scr.data_ptr(), sb, s.cuda_stream)
+        else:
+            index_build_device_minimizers(d_ref.data_ptr(), ref_len, k, w, d_bucket.data_ptr(), d_pos.data_ptr(), d_scr.data_ptr(), sb, s.cuda_stream)
         s.synchronize()
     n_pos = int(d_bucket[(be - 1) * 4:].cpu().numpy().view(np.uint32)[0])
     return d_bucket, d_pos, n_pos
 
 
-def seed_params(k, read_size, stride=1, max_occ=16, band=8, flank=8, min_votes=2, max_cands=4, idx_base=0):
-    """aim_seed_params_t, validated like make_params: ValueError names the field that is out of bounds."""
+def seed_params(k, read_size, stride=1, max_occ=16, band=8, flank=8, min_votes=2, max_cands=4, idx_base=0, w=None):
+    """aim_seed_params_t, validated like make_params: ValueError names the field that is out of bounds. With a window `w` the seeds
+    are the query's (w, k) minimizers (options = AIM_SEED_OPT_MINIMIZERS(w)); stride must then be 1 and the index one of the same
+    (k, w)."""
     bounds = (("k", k, 8, 14), ("stride", stride, 1, None), ("max_occ", max_occ, 1, None), ("band", band, 0, None), ("flank", flank, 0, None),
               ("min_votes", min_votes, 1, None), ("max_cands", max_cands, 1, capi.SEED_MAX_CANDS), ("read_size", read_size, 8, capi.SEED_MAX_READ_SIZE))
     for name, v, lo, hi in bounds:
@@ -502,8 +526,15 @@ def seed_params(k, read_size, stride=1, max_occ=16, band=8, flank=8, min_votes=2
             raise ValueError("%s %r is outside %d..%s" % (name, v, lo, "" if hi is None else hi))
     if read_size % 8:
         raise ValueError("read_size %d is not a multiple of 8" % read_size)
+    options = 0
+    if w is not None:
+        if int(w) != w or w < 1 or w > capi.SEED_MAX_W:
+            raise ValueError("w %r is outside 1..%d" % (w, capi.SEED_MAX_W))
+        if stride != 1:
+            raise ValueError("stride %r must be 1 with minimizers (w)" % (stride,))
+        options = capi.SEED_OPT_MINIMIZERS(w)
     return capi.SeedParams(int(k), int(stride), int(max_occ), int(band), int(flank), int(min_votes), int(max_cands), int(read_size),
-                           int(idx_base) & 0xFFFFFFFF, 0)
+                           int(idx_base) & 0xFFFFFFFF, options)
 
 
 def seed_groups_offsets(n_reads, max_cands):

@@ -327,6 +327,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_TOP_HITS 0x400u /* AIM_FLAG_TOP_HITS is honoured; aim_hits_offsets and aim_align_device_hits exist */
 #define AIM_FEATURE_SEED 0x800u /* device-side seeding: aim_index_sizes / aim_index_build / aim_seed_device / aim_seed_groups_offsets exist */
 #define AIM_FEATURE_INDEX_DEVICE 0x1000u /* aim_index_device_scratch / aim_index_build_device / aim_index_kernel_names exist */
+#define AIM_FEATURE_MINIMIZERS 0x2000u /* (w, k) minimizers: aim_index_build_minimizers / aim_index_build_device_minimizers / AIM_SEED_OPT_MINIMIZERS exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -649,13 +650,35 @@ const char *aim_sam_kernel_name(const aim_params_t *params);
  *      reference; under AIM_FLAG_READ_GROUPS such a candidate scores a pure gap of L bases, and callers read n_cands.
  * The window is on the forward reference and strand 1 sets bit 63: exactly what AIM_FLAG_REF_TEXTS reverse-complements. Flanked
  * windows are usually aligned with AIM_FLAG_ENDSFREE (text_begin_free = text_end_free = 2 * flank).
- * Follow-ups, not in this version: packed read rows, minimizers and spaced seeds, a seeding stage inside aim_set_submit, chaining
- * instead of voting. Check aim_features() & AIM_FEATURE_SEED first. */
+ * MINIMIZERS (AIM_FEATURE_MINIMIZERS). With a window w the index holds, and a query looks up, only the (w, k) minimizers: the same
+ *   positions are chosen in the reference and in the query, every exact match of w + k - 1 bases shares at least one seed, and on random
+ *   sequence about 2 / (w + 1) of the positions are kept.
+ *   Order. A valid k-mer of code c has the order key h(c), in uint32_t arithmetic:
+ *       x = c;  x ^= x >> 16;  x *= 0x85ebca6b;  x ^= x >> 13;  x *= 0xc2b2ae35;  x ^= x >> 16
+ *     h is a bijection on 32 bits, so two k-mers tie only when they are the same k-mer. A k-mer that covers a byte other than
+ *     upper-case A C G T is invalid and compares greater than every valid key, 0xFFFFFFFF included.
+ *   Windows. A sequence of len bytes has n = len - k + 1 k-mer start positions. For n >= w the windows are [s, s + w) for
+ *     s = 0 .. n - w; for 0 < n < w there is the one window [0, n).
+ *   Selection. The minimizer of a window is its leftmost position of smallest key; a window whose k-mers are all invalid has none. A
+ *     position is selected when it is the minimizer of at least one window. Equivalently, a valid position i is selected iff
+ *     L + R + 1 >= min(w, n), where L counts the consecutive positions immediately left of i whose key is strictly greater (it stops at
+ *     the sequence start) and R the consecutive positions immediately right of i whose key is greater or equal (it stops at the
+ *     sequence end); both may be capped at w - 1.
+ *   Index. bucket[] / pos[] as above, except that only the selected reference positions are counted and stored; bucket[4^k] is their
+ *     number. w = 1 selects every valid k-mer: the bytes of aim_index_build.
+ *   Seeding. Only rule 2 changes: the seeds of a strand's query (the read, or its reverse complement) are its selected positions j in
+ *     ascending order, computed on the query itself, left to right; stride must be 1. max_occ, the key a = p + read_size - j, rules 3-7
+ *     are untouched. The index must have been built with the same (k, w): nothing in the arrays records w, so the library cannot check
+ *     that, and a mismatch only loses seeds.
+ * Follow-ups, not in this version: packed read rows, spaced seeds, a seeding stage inside aim_set_submit, chaining instead of voting,
+ * compacting the selected positions before the device build's sort. Check aim_features() & AIM_FEATURE_SEED first. */
 #define AIM_SEED_MAX_CANDS 16
 #define AIM_SEED_MAX_HITS 1024      /* hits kept per (read, strand) */
 #define AIM_SEED_TRUNCATED 0x1u     /* aim_seed_t.flags: a strand dropped hits beyond AIM_SEED_MAX_HITS */
 #define AIM_SEED_MAX_READ_SIZE 4096 /* the read row is staged in LDS next to the key arrays */
 #define AIM_SEED_MAX_REF_LEN 0xFE000000ull /* 2^32 - 2^25 */
+#define AIM_SEED_MAX_W 32           /* minimizer window, 1..AIM_SEED_MAX_W */
+#define AIM_SEED_OPT_MINIMIZERS(w) ((uint32_t)(w) << 8) /* aim_seed_params_t.options: seeds are the query's (w, k) minimizers */
 typedef struct aim_seed_params {
     int32_t k;          /* 8..14 */
     int32_t stride;     /* >= 1: seeds start at read offsets 0, stride, 2*stride, ... */
@@ -666,7 +689,7 @@ typedef struct aim_seed_params {
     int32_t max_cands;  /* K, 1..AIM_SEED_MAX_CANDS */
     int32_t read_size;  /* row stride of the read rows, multiple of 8, <= AIM_SEED_MAX_READ_SIZE; also the cap on text_len */
     uint32_t idx_base;  /* requests[r*K+i].idx = idx_base + r*K + i */
-    uint32_t options;   /* 0 */
+    uint32_t options;   /* 0, or AIM_SEED_OPT_MINIMIZERS(w) with stride 1; every other bit must be 0 */
 } aim_seed_params_t;
 typedef struct aim_seed { uint32_t n_cands, n_hits[2], flags; } aim_seed_t;   /* 16 B per read */
 /* Sizes of the index arrays, in entries: *bucket_entries = 4^k + 1, *pos_capacity = ref_len - k + 1 (0 below k). AIM_EINVAL for a k
@@ -676,6 +699,11 @@ int aim_index_sizes(int32_t k, uint64_t ref_len, uint64_t *bucket_entries, uint6
  * which owns a range of codes, so the result does not depend on `threads`. bucket and pos hold what aim_index_sizes reports (pos may
  * be NULL when its capacity is 0); *n_pos (may be NULL) receives bucket[4^k], the number of positions written. */
 int aim_index_build(const char *seq, uint64_t ref_len, int32_t k, uint32_t *bucket, uint32_t *pos, uint64_t *n_pos, int threads);
+/* aim_index_build over the (w, k) minimizers of seq alone (AIM_FEATURE_MINIMIZERS, the rule above): same arrays, same sizes, same
+ * meaning of threads and n_pos. pos_capacity is an upper bound -- about 2 / (w + 1) of it is used on random sequence -- and a caller
+ * may keep only pos[0, *n_pos). AIM_EINVAL as aim_index_build, and for a w outside 1..AIM_SEED_MAX_W. */
+int aim_index_build_minimizers(const char *seq, uint64_t ref_len, int32_t k, int32_t w, uint32_t *bucket, uint32_t *pos, uint64_t *n_pos,
+                               int threads);
 /* ---- the same index, built on the device (AIM_FEATURE_INDEX_DEVICE) ----
  * Bytes of device scratch aim_index_build_device needs for (k, ref_len); 0 is a legal answer (ref_len < k). With P = ref_len - k + 1
  * positions and A(x) = x rounded up to 256:  scratch = 3 * A(4 * P) + A(1024 * ceil(P / 4096)) + 8192  -- two key arrays and one
@@ -696,12 +724,23 @@ int aim_index_build_device(const char *d_reference, uint64_t ref_len, int32_t k,
                            void *d_scratch, uint64_t scratch_bytes, void *hip_stream);
 /* Comma-separated rocprofv3 kernel-trace name prefixes of aim_index_build_device's kernels, in launch order. */
 const char *aim_index_kernel_names(void);
+/* aim_index_build_minimizers on the device (AIM_FEATURE_MINIMIZERS): the contract, the scratch (aim_index_device_scratch) and the
+ * refusals of aim_index_build_device, and AIM_EINVAL with a message naming w for a w outside 1..AIM_SEED_MAX_W. Afterwards d_bucket and
+ * d_pos[0, d_bucket[4^k]) equal aim_index_build_minimizers', byte for byte. index_minimizer_kernel takes the place of
+ * index_code_kernel; the sort behind it is the same launches over all ref_len - k + 1 positions, selected or not. */
+int aim_index_build_device_minimizers(const char *d_reference, uint64_t ref_len, int32_t k, int32_t w, uint32_t *d_bucket,
+                                      uint32_t *d_pos, void *d_scratch, uint64_t scratch_bytes, void *hip_stream);
+/* "index_minimizer_kernel,seed_minimizer_kernel": comma-separated rocprofv3 kernel-trace name prefixes of the kernels
+ * AIM_FEATURE_MINIMIZERS adds, the code pass of aim_index_build_device_minimizers and aim_seed_device's kernel under
+ * AIM_SEED_OPT_MINIMIZERS. */
+const char *aim_minimizer_kernel_names(void);
 /* The seeding kernel over device buffers: ASCII read rows d_reads[n_reads][read_size] (aligned and with slack like d_patterns),
  * d_read_len[n_reads], the index of a reference of ref_len bytes, and the outputs of the rule above: d_requests
  * (aim_request_t[n_reads * K]), d_text_pos, d_votes (each [n_reads * K]) and d_seed[n_reads]. The call only enqueues work on
  * hip_stream and needs no scratch: everything per read lives in LDS. A read_len outside 0..read_size is clamped; index entries that
  * point outside the arrays aim_index_sizes describes make a seed count as absent, never a fault. AIM_EINVAL with a message naming the
- * field for every bound of aim_seed_params_t, for ref_len, and for n_reads * K >= 2^32. */
+ * field for every bound of aim_seed_params_t, for ref_len, and for n_reads * K >= 2^32. With options = AIM_SEED_OPT_MINIMIZERS(w) the
+ * kernel is seed_minimizer_kernel and d_bucket / d_pos must be a minimizer index of the same (k, w). */
 int aim_seed_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads,
                     const uint32_t *d_bucket, const uint32_t *d_pos, uint64_t ref_len, void *d_requests /* aim_request_t[n_reads*K] */,
                     uint64_t *d_text_pos, uint32_t *d_votes, aim_seed_t *d_seed, void *hip_stream);

@@ -3,6 +3,7 @@
 
   python tools/seed_rate.py --mode kernel [--reads N] [--configs 11:1,11:4,13:1,13:4] [--steps K] [--warmup W] [--out FILE.jsonl]
   python tools/seed_rate.py --mode e2e [--reads N] [--host-reads M] [--rounds R] [--out FILE.jsonl]
+  python tools/seed_rate.py --mode kernel --w 5,10,19 [--k 11,13] [--length 100|1000] [--reads N] [--rounds 5] [--out FILE.jsonl]
 
 kernel  N reads (default 1 Mi) of l = 100 with one substitution each (e = 1 %), both strands, against a 16 MiB random reference:
         seed_candidates_kernel per (k, stride) at max_occ 16, band 8, flank 8, min_votes 2, K = 4, timed with HIP events (median of
@@ -16,6 +17,10 @@ e2e     reads in, aim_best_t out, two ways, alternating for `rounds` rounds in o
         `host`    what a caller did before: seed on the host (tests/seed_model.py, the rule in numpy / Python), then send the
                   candidates through aim_align_device_groups. The host seeder is timed on --host-reads reads (default 2 048: it is
                   pure Python and takes about a millisecond per read) and its share of that path's time is reported.
+--w     (w, k) minimizers against strides: per (k, w) seed_minimizer_kernel over the minimizer index and seed_candidates_kernel over
+        the full index at stride = ceil((w + 1) / 2), which looks up the same expected number of seeds, on the same reads of --length
+        bases (rows of the next multiple of 128), alternating for `rounds` rounds of `steps` calls: time per read, hits per strand and
+        the share of reads truncated, found (n_cands > 0) and whose true position lies in one of the K windows.
 One JSON line per row (stdout, and --out)."""
 import argparse
 import ctypes as C
@@ -123,6 +128,48 @@ def kernel_rows(n, configs, steps, warmup):
     return out
 
 
+def minimizer_rows(n, ks, ws, steps, warmup, rounds):
+    import torch
+    torch.cuda.init()   # (before the library: the device buffers are torch's)
+    from aim_amd import capi, engine
+    dev = torch.device("cuda:0")
+    ref = reference()
+    rows, rl, true_pos = make_reads(ref, n)
+    stream = torch.cuda.current_stream().cuda_stream
+    names = [capi.load().aim_minimizer_kernel_names().decode().split(",")[1], capi.load().aim_seed_kernel_name().decode()]
+    out = []
+    for k in ks:
+        full = engine.build_index(ref, k, threads=16)
+        for w in ws:
+            stride = (w + 2) // 2
+            index = [engine.index_build_minimizers(ref, k, w, threads=16), full]
+            sps = [engine.seed_params(k, RS, w=w, **SEED_KW), engine.seed_params(k, RS, stride=stride, **SEED_KW)]
+            o = [engine.seed_candidates(sp, tuple(torch.from_numpy(a.view(np.uint8)).to(dev) for a in ix), len(ref), rl, rows) for sp, ix in zip(sps, index)]
+
+            def call(i):
+                engine.seed_device(sps[i], n, o[i]["d_read_len"].data_ptr(), o[i]["d_reads"].data_ptr(), o[i]["d_bucket"].data_ptr(), o[i]["d_pos"].data_ptr(),
+                                   len(ref), o[i]["d_req"].data_ptr(), o[i]["d_text_pos"].data_ptr(), o[i]["d_votes"].data_ptr(), o[i]["d_seed"].data_ptr(), stream)
+            med = [[], []]
+            for r in range(rounds):
+                for i in (0, 1):
+                    med[i].append(events_ms(torch, lambda: call(i), steps, warmup if r == 0 else 0)[0])
+            for i in (0, 1):
+                start = (o[i]["text_pos"] & np.uint64((1 << 63) - 1)).astype(np.int64).reshape(n, K)
+                tlen = o[i]["req"]["text_len"].astype(np.int64).reshape(n, K)
+                hit = ((start <= true_pos[:, None]) & (true_pos[:, None] + L <= start + tlen) & (tlen > 0)).any(axis=1)
+                ms = statistics.median(med[i])
+                out.append(dict(part="minimizers", kernel=names[i], reads=n, length=L, read_size=RS, k=k, w=w, stride=1 if i == 0 else stride, **SEED_KW,
+                                ref_len=len(ref), index_positions=len(index[i][1]), seed_ms=round(ms, 4), seed_ms_min=round(min(med[i]), 4),
+                                seed_ms_max=round(max(med[i]), 4), rounds=rounds, ns_per_read=round(ms * 1e6 / n, 2),
+                                hits_per_strand=round(float(o[i]["seed"]["n_hits"].mean()), 2),
+                                truncated_share=round(float((o[i]["seed"]["flags"] & capi.SEED_TRUNCATED != 0).mean()), 5),
+                                found=round(float((o[i]["seed"]["n_cands"] > 0).mean()), 4), true_position_in_k_windows=round(float(hit.mean()), 4)))
+                print(json.dumps(out[-1]), flush=True)
+            del o
+            torch.cuda.empty_cache()
+    return out
+
+
 def e2e_rows(n, host_n, rounds):
     import torch
     torch.cuda.init()
@@ -182,6 +229,7 @@ def e2e_rows(n, host_n, rounds):
 
 
 def main():
+    global L, RS
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["kernel", "e2e"], default="kernel")
     ap.add_argument("--reads", type=int, default=1 << 20)
@@ -190,9 +238,15 @@ def main():
     ap.add_argument("--steps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--w", default="", help="minimizer windows, e.g. 5,10,19 (kernel mode): seed_minimizer_kernel against the stride that looks up as many seeds")
+    ap.add_argument("--k", default="11,13", help="with --w: the k values")
+    ap.add_argument("--length", type=int, default=L, help="with --w: read length (rows of the next multiple of 128)")
     ap.add_argument("--out")
     a = ap.parse_args()
-    if a.mode == "kernel":
+    if a.mode == "kernel" and a.w:
+        L, RS = a.length, (a.length + 127) // 128 * 128
+        rows = minimizer_rows(a.reads, [int(x) for x in a.k.split(",")], [int(x) for x in a.w.split(",")], a.steps, a.warmup, max(a.rounds, 5))
+    elif a.mode == "kernel":
         rows = kernel_rows(a.reads, [tuple(int(x) for x in c.split(":")) for c in a.configs.split(",")], a.steps, a.warmup)
     else:
         rows = e2e_rows(a.reads, a.host_reads, a.rounds)
