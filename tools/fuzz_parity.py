@@ -23,6 +23,21 @@ def oracle_params(params, algo):
                          gap_o=params.gap_o, gap_e=params.gap_e, gap_i=params.gap_i, gap_d=params.gap_d, backtrace=bt, reduce=red, swg_cell_bytes=cellb)
 
 
+def draw_pairs(rng, n, l, e, rs, ms):
+    """(requests, patterns, texts, source): engine.gen_pairs, or with probability 0.25 tests/low_complexity.py's batch for this
+    READ_SIZE and MAX_SCORE (homopolymers, tandem repeats, two-letter sequence, runs of 'N': many equally good paths, every
+    diagonal of the band extending far). The case line names the source. A low-complexity batch takes its lengths from
+    READ_SIZE alone ((rs - 8) * 100 // 104, every fourth round rs) and its edits from its classes: the case's l and e do not
+    apply to it, which the source string says. What the callers size from l (pairs per case from max_cells / l^2, the run cap
+    from min(MAX_SCORE, l + 8), the places of their own mutations) stays valid: rs < 1.1 l + 10 in every focus, a pair within
+    MAX_SCORE has at most 2 * MAX_SCORE + 1 runs whatever its length, and a mutation behind a length lands in the padding."""
+    seed = rng.randint(1, 1 << 30)
+    if rng.random() < 0.25:
+        import low_complexity
+        return low_complexity.low_complexity_batch(rs, n, seed, ms)[:3] + ("low_complexity seed=%d (l, e do not apply)" % seed,)
+    return engine.gen_pairs(seed, 0, n, l, e, rs) + ("gen_pairs",)
+
+
 def compare(algo, params, req, pat, txt, allow_nomem=False):
     """None if bit-identical. With allow_nomem (a tiny scratch bound was forced) pairs the HIP path ended with
     AIM_PAIR_NOMEM (3: history pool overflow, the counterpart of the reference arena's 'out of memory' abort, which the
@@ -72,11 +87,11 @@ def main():
             params = engine.make_params("wfa", ms, rs, **kw)
             for k in list(os.environ):
                 if k.startswith("AIM_") and k != "AIM_LIB" and not k.startswith("AIM_DEBUG_POISON"): os.environ.pop(k)
-            req, pat, txt = engine.gen_pairs(rng.randint(1, 1 << 30), 0, n, l, e, rs)
+            req, pat, txt, src = draw_pairs(rng, n, l, e, rs, ms)
             for _ in range(rng.choice([0, 0, 1, 5])):
                 pat[rng.randrange(n), rng.randrange(max(1, l))] = ord(rng.choice("Nn*acgt"))
             kn = lib.aim_kernel_name(C.byref(params)).decode()
-            case = dict(algo="wfa", l=l, e=e, n=n, max_score=ms, read_size=rs, kernel=kn, **{k: int(v) for k, v in kw.items()})
+            case = dict(algo="wfa", l=l, e=e, n=n, max_score=ms, read_size=rs, kernel=kn, pairs=src, **{k: int(v) for k, v in kw.items()})
             try:
                 err = compare("wfa", params, req, pat, txt)
             except Exception as ex:
@@ -118,7 +133,7 @@ def main():
             if rng.random() < 0.2: env["AIM_DPL_PER_CU"] = rng.choice(["1", "3", "12"])
             if rng.random() < 0.15: env["AIM_CHIP_CUS"] = rng.choice(["1", "2"])     # a small resident grid: many groups of 64 pairs per wavefront (the queues' carry-over)
             os.environ.update(env)
-            req, pat, txt = engine.gen_pairs(rng.randint(1, 1 << 30), 0, n, l, e, rs)
+            req, pat, txt, src = draw_pairs(rng, n, l, e, rs, ms)
             if algo == "swg" and n > 8 and rng.random() < 0.4:          # unrelated texts: cells climb to MAX_SCORE + min(h, v) e, int8 cells wrap, the walk may find no operation
                 for i in range(0, n, rng.choice([2, 7, 50])):
                     k = int(req["text_len"][i])
@@ -138,7 +153,7 @@ def main():
                     txt[i, :pl] = t
                     req["text_len"][i] = pl
             kn = lib.aim_kernel_name(C.byref(params)).decode()
-            case = dict(algo=algo, l=l, e=e, n=n, max_score=ms, read_size=rs, kernel=kn, backtrace=int(bt), cost=cost, env=env)
+            case = dict(algo=algo, l=l, e=e, n=n, max_score=ms, read_size=rs, kernel=kn, backtrace=int(bt), cost=cost, env=env, pairs=src)
             try:
                 err = compare(algo, params, req, pat, txt)
             except Exception as ex:
@@ -181,7 +196,7 @@ def main():
             if rng.random() < 0.15: env["AIM_CHIP_CUS"] = rng.choice(["1", "2", "8"])     # a small resident grid: many units per wavefront (LDS slots, slabs and the window reused)
             if rng.random() < 0.1: env["AIM_SCRATCH_GB"] = rng.choice(["0.5", "2"])
             os.environ.update(env)
-            req, pat, txt = engine.gen_pairs(rng.randint(1, 1 << 30), 0, n, l, e, rs)
+            req, pat, txt, src = draw_pairs(rng, n, l, e, rs, ms)
             for _ in range(rng.choice([0, 3, 40])):                     # length outliers (contents stay what they were): tails of any size, plen > 2 tlen, empty sequences
                 i = rng.randrange(n)
                 r = rng.random()
@@ -205,7 +220,7 @@ def main():
                     txt[i, :pl] = t
                     req["text_len"][i] = pl
             kn = lib.aim_kernel_name(C.byref(params)).decode()
-            case = dict(algo=algo, l=l, e=e, n=n, max_score=ms, read_size=rs, kernel=kn, backtrace=int(bt), cost=cost, env=env)
+            case = dict(algo=algo, l=l, e=e, n=n, max_score=ms, read_size=rs, kernel=kn, backtrace=int(bt), cost=cost, env=env, pairs=src)
             try:
                 err = compare(algo, params, req, pat, txt, allow_nomem="AIM_SCRATCH_GB" in env)
             except Exception as ex:
@@ -276,11 +291,12 @@ def main():
             n = int(min(rng.choice([1, 64, 65, 1000, 5000]), max(1, a.max_cells // (l * l))))
             bt = rng.random() < 0.7
             params = engine.make_params("wfa", ms, rs, backtrace=bt, reduce=rng.random() < 0.7, req8=True, res8=not bt, **cost)
-            req, pat, txt = engine.gen_pairs(rng.randint(1, 1 << 30), 0, n, l, e, rs)
+            req, pat, txt, src = draw_pairs(rng, n, l, e, rs, ms)
             for _ in range(rng.choice([0, 0, 1, 4])):
                 pat[rng.randrange(n), rng.randrange(max(1, l))] = ord(rng.choice("Nn*"))
             op = oracle.params("wfa", ms, rs, backtrace=bt, reduce=bool(params.flags & capi.FLAG_REDUCE), mismatch=params.mismatch, gap_o=params.gap_o, gap_e=params.gap_e)
             ores, oops, _ = oracle.align_batch(op, req["pattern_len"], req["text_len"], pat, txt, nthreads=32)
+            ores["idx"] = req["idx"]      # the oracle numbers its rows 0, 1, ...; the device returns the requests' idx (gen_pairs': the same; low_complexity's start at 7000)
             err = None
             try:
                 with engine.DeviceSet(1) as st:
@@ -298,7 +314,7 @@ def main():
             cases += 1
             kernels[kn] = kernels.get(kn, 0) + 1
             if err:
-                print(json.dumps(dict(algo="wfa", l=l, e=e, n=n, max_score=ms, read_size=rs, backtrace=int(bt), cost=cost, kernel=kn, env={k: v for k, v in os.environ.items() if k.startswith("AIM_")}, ok=False)), flush=True)
+                print(json.dumps(dict(algo="wfa", l=l, e=e, n=n, max_score=ms, read_size=rs, backtrace=int(bt), cost=cost, kernel=kn, pairs=src, env={k: v for k, v in os.environ.items() if k.startswith("AIM_")}, ok=False)), flush=True)
                 print("MISMATCH:", err, flush=True)
                 return 1
             continue
@@ -346,7 +362,7 @@ def main():
         for k in ("AIM_GROUP_G", "AIM_FORCE_WAVE", "AIM_DPW_NW", "AIM_FORCE_DPWAVE", "AIM_DPL_SEQ_LDS", "AIM_DPL_PER_CU", "AIM_GROUP_PER_CU",
                   "AIM_WFA_NO_RING", "AIM_SCRATCH_GB", "AIM_STRIP_K", "AIM_DPW_LEGACY", "AIM_GROUP_WLDS", "AIM_DPL_NO_REG"): os.environ.pop(k, None)
         os.environ.update(env)
-        req, pat, txt = engine.gen_pairs(rng.randint(1, 1 << 30), 0, n, l, e, rs)
+        req, pat, txt, src = draw_pairs(rng, n, l, e, rs, ms)
         if n > 3 and rng.random() < 0.3: pat[rng.randrange(n), rng.randrange(max(1, l // 2))] = ord("N")   # non-ACGT byte
         if algo != "wfa" and l >= 1500 and rng.random() < 0.3:     # paths that shift by many diagonals half-way (a block missing from the text, other bases appended): the banded
             blk = rng.choice([l // 5, l // 3, 700, 1300])          # direction bits of dp_strip (K = 20) must notice and fill the pair again
@@ -366,7 +382,7 @@ def main():
                 pl = int(req["pattern_len"][i])
                 req["text_len"][i] = max(1, rng.choice([pl - rng.randint(1, 70), pl // 2, pl // 3, pl // 7, pl // 40, 1]))
         kn = lib.aim_kernel_name(C.byref(params)).decode()
-        case = dict(algo=algo, l=l, e=e, n=n, max_score=ms, read_size=rs, kernel=kn, env=env, **{k: (int(v) if isinstance(v, bool) else v) for k, v in kw.items()})
+        case = dict(algo=algo, l=l, e=e, n=n, max_score=ms, read_size=rs, kernel=kn, env=env, pairs=src, **{k: (int(v) if isinstance(v, bool) else v) for k, v in kw.items()})
         try:
             err = compare(algo, params, req, pat, txt, allow_nomem="AIM_SCRATCH_GB" in env)
             nomem_pairs += getattr(compare, "nomem", 0)
