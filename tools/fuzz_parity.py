@@ -116,7 +116,7 @@ def main():
                 cost = dict(mismatch=rng.randint(1, 9), gap_i=rng.choice([1, 2, 3, 4, 6, 7, 9, 30]), gap_d=rng.choice([1, 2, 3, 5, 6, 7, 9, 30]))
             if algo == "swg" and rng.random() < 0.5:                   # swg_reg_kernel on both sides of swg_reg_supported(): other costs, int16 cells, MAX_SCORE as the pseudo-infinity
                 cost = dict(mismatch=rng.randint(1, 9), gap_o=rng.choice([1, 2, 4, 6, 9, 40]), gap_e=rng.choice([1, 1, 2, 3, 5]))
-                if rng.random() < 0.1: cost["match"] = rng.choice([-2, -1, 0])
+                if rng.random() < 1 / 3: cost["match"] = rng.choice([-3, -2, -1, 0])      # a bonus: tests/test_match_bonus_gpu.py holds every SWG kernel to it
             n = rng.choice([1, 63, 64, 65, 1000, 4097, 9000])
             bt = rng.random() < 0.6
             ms = rng.randint(1, 60)
@@ -180,7 +180,7 @@ def main():
             if algo == "nw" and rng.random() < 0.4: cost = dict(mismatch=rng.randint(1, 9), gap_i=rng.choice([1, 2, 3, 4, 6, 7, 9, 30]), gap_d=rng.choice([1, 2, 3, 5, 6, 7, 9, 30]))
             if algo == "swg" and rng.random() < 0.5:
                 cost = dict(mismatch=rng.randint(1, 9), gap_o=rng.choice([1, 2, 4, 6, 9, 40]), gap_e=rng.choice([1, 1, 2, 3, 5]))
-                if rng.random() < 0.1: cost["match"] = rng.choice([-2, -1, 0])
+                if rng.random() < 1 / 3: cost["match"] = rng.choice([-3, -2, -1, 0])      # a bonus: tests/test_match_bonus_gpu.py holds every SWG kernel to it
             n = int(min(rng.choice([1, 5, 6, 7, 63, 64, 65, 500, 2000]), max(1, a.max_cells // (l * l))))
             bt = rng.random() < 0.6
             ms = rng.choice([1, 20, 60, 200, 600])
