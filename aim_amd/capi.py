@@ -45,6 +45,8 @@ SEED_MAX_REF_LEN = (1 << 32) - (1 << 25)
 FEATURE_INDEX_DEVICE = 0x1000   # aim_features(): aim_index_device_scratch / aim_index_build_device / aim_index_kernel_names exist
 FEATURE_MINIMIZERS = 0x2000     # aim_features(): aim_index_build_minimizers / aim_index_build_device_minimizers / SEED_OPT_MINIMIZERS exist
 SEED_MAX_W = 32                 # AIM_SEED_MAX_W: the minimizer window is 1..32
+FEATURE_SEED_CHAIN = 0x4000     # aim_features(): aim_seed_chain_device / aim_chain_t / aim_seed_chain_kernel_names exist
+SEED_CHAIN_LOOKBACK, SEED_CHAIN_MAX_BAND = 64, 4096
 
 
 def SEED_OPT_MINIMIZERS(w):
@@ -131,6 +133,8 @@ class SeedParams(C.Structure):
 
 SEED_DTYPE = np.dtype([("n_cands", "<u4"), ("n_hits", "<u4", (2,)), ("flags", "<u4")])   # aim_seed_t
 assert SEED_DTYPE.itemsize == 16 and C.sizeof(SeedParams) == 40
+CHAIN_DTYPE = np.dtype([("score", "<u4"), ("n_anchors", "<u2"), ("reserved", "<u2"), ("q_lo", "<u2"), ("q_hi", "<u2"), ("ref_span", "<u4")])   # aim_chain_t
+assert CHAIN_DTYPE.itemsize == 16
 
 
 class BatchIO(C.Structure):
@@ -224,6 +228,8 @@ SYMBOLS = {
     "aim_index_sizes": (C.c_int, [_I32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "aim_index_build": (C.c_int, [_VP, C.c_uint64, _I32, _VP, _VP, C.POINTER(C.c_uint64), C.c_int]),
     "aim_seed_device": (C.c_int, [C.POINTER(SeedParams), _U32, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP]),
+    "aim_seed_chain_device": (C.c_int, [C.POINTER(SeedParams), _U32, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "aim_seed_chain_kernel_names": (C.c_char_p, []),
     "aim_seed_groups_offsets": (C.c_int, [_U32, _U32, _VP]),
     "aim_seed_kernel_name": (C.c_char_p, []),
     "aim_index_device_scratch": (C.c_int, [_I32, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -37,6 +37,7 @@
 #include "mates.hpp"
 #include "sam_fields.hpp"
 #include "seed.hpp"
+#include "seed_chain.hpp"
 #include "index.hpp"
 #include "genasm_wave.hpp"
 
@@ -1673,7 +1674,7 @@ uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
            AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS | AIM_FEATURE_SEED |
-           AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS;
+           AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS | AIM_FEATURE_SEED_CHAIN;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -3217,26 +3218,32 @@ int aim_seed_groups_offsets(uint32_t n_reads, uint32_t K, uint32_t *read_offsets
 
 const char *aim_seed_kernel_name(void) { return "seed_candidates_kernel"; }
 
-int aim_seed_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads, const uint32_t *d_bucket,
-                    const uint32_t *d_pos, uint64_t ref_len, void *d_requests, uint64_t *d_text_pos, uint32_t *d_votes, aim_seed_t *d_seed,
-                    void *hip_stream)
+extern "C++" {
+namespace {
+// aim_seed_device (chain = false) and aim_seed_chain_device (chain = true: the chaining kernels, the band bound and d_chains)
+int seed_device(const char *fn, bool chain, const aim_seed_params_t *sp, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads,
+                const uint32_t *d_bucket, const uint32_t *d_pos, uint64_t ref_len, void *d_requests, uint64_t *d_text_pos, uint32_t *d_votes,
+                aim_seed_t *d_seed, aim_chain_t *d_chains, void *hip_stream)
 {
-    if (!sp) return fail(AIM_EINVAL, "aim_seed_device: sp is NULL");
+    if (!sp) return fail(AIM_EINVAL, "%s: sp is NULL", fn);
     int rc = check_seed_params(*sp);
     if (rc) return rc;
+    if (chain && sp->band > AIM_SEED_CHAIN_MAX_BAND)
+        return fail(AIM_EINVAL, "aim_seed_params_t: band %d is above %d (%s)", sp->band, AIM_SEED_CHAIN_MAX_BAND, fn);
     if (ref_len > AIM_SEED_MAX_REF_LEN)
-        return fail(AIM_EINVAL, "aim_seed_device: ref_len %llu is above 2^32 - 2^25 (positions and diagonal keys are 32-bit)", (unsigned long long)ref_len);
+        return fail(AIM_EINVAL, "%s: ref_len %llu is above 2^32 - 2^25 (positions and diagonal keys are 32-bit)", fn, (unsigned long long)ref_len);
     if ((uint64_t)n_reads * (uint64_t)sp->max_cands >= (1ull << 32))
-        return fail(AIM_EINVAL, "aim_seed_device: n_reads %u * max_cands %d does not fit 32 bits (split the batch)", n_reads, sp->max_cands);
+        return fail(AIM_EINVAL, "%s: n_reads %u * max_cands %d does not fit 32 bits (split the batch)", fn, n_reads, sp->max_cands);
     if (n_reads && (!d_read_len || !d_reads || !d_bucket || (!d_pos && ref_len >= (uint64_t)sp->k) || !d_requests || !d_text_pos || !d_votes || !d_seed))
-        return fail(AIM_EINVAL, "aim_seed_device: null device buffer");
+        return fail(AIM_EINVAL, "%s: null device buffer", fn);
     int n = 0;
     rc = aim_device_count(&n);
     if (rc) return rc;
     if (!n_reads) return AIM_OK;
     const aim::Knobs kn = with_chip(read_knobs());
-    aim::SeedArgs a;
-    memset(&a, 0, sizeof a);
+    aim::SeedChainArgs ca;
+    memset(&ca, 0, sizeof ca);
+    aim::SeedArgs &a = ca.s;
     a.sp = *sp;
     a.n_reads = n_reads;
     a.read_len = d_read_len;
@@ -3248,8 +3255,10 @@ int aim_seed_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t
     a.text_pos = d_text_pos;
     a.votes = d_votes;
     a.seed = d_seed;
+    ca.chains = d_chains;
     const bool minimizers = sp->options != 0;
-    const size_t lds = minimizers ? aim::seed_minimizer_lds_bytes(sp->read_size) : aim::seed_lds_bytes(sp->read_size);
+    const size_t lds = chain ? (minimizers ? aim::seed_chain_minimizer_lds_bytes(sp->read_size) : aim::seed_chain_lds_bytes(sp->read_size))
+                             : (minimizers ? aim::seed_minimizer_lds_bytes(sp->read_size) : aim::seed_lds_bytes(sp->read_size));
     a.dbg_poison_lds = kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u;
     a.dbg_lds_bytes = (uint32_t)lds;
     // persistent grid: what LDS lets one CU hold (at most 16 wavefronts), on every CU, capped at the reads rounded up to the multiple of 8
@@ -3257,14 +3266,37 @@ int aim_seed_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t
     const uint32_t per_cu = (uint32_t)std::min<size_t>(16, aim::lds_workgroups_per_cu(lds));
     const uint32_t grid = std::min(aim::resident_grid(kn, per_cu), (uint32_t)std::min<uint64_t>(((uint64_t)n_reads + 7u) & ~7ull, 1u << 20));
     if (kn.plan_debug)
-        fprintf(stderr, "[aim plan] %s grid=%u block=64 lds=%zu per_cu=%u reads=%u\n", minimizers ? "seed_minimizer_kernel" : "seed_candidates_kernel", grid, lds,
-                per_cu, n_reads);
-    if (minimizers)
+        fprintf(stderr, "[aim plan] %s grid=%u block=64 lds=%zu per_cu=%u reads=%u\n",
+                chain ? (minimizers ? "seed_chain_minimizer_kernel" : "seed_chain_kernel") : (minimizers ? "seed_minimizer_kernel" : "seed_candidates_kernel"),
+                grid, lds, per_cu, n_reads);
+    if (chain)
+        aim::seed_chain_launch(ca, minimizers, grid, lds, (hipStream_t)hip_stream);
+    else if (minimizers)
         aim::seed_minimizer_launch(a, grid, lds, (hipStream_t)hip_stream);
     else
         aim::seed_launch(a, grid, lds, (hipStream_t)hip_stream);
     HIP_TRY(hipGetLastError());
     return AIM_OK;
+}
+}  // namespace
+}
+
+int aim_seed_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads, const uint32_t *d_bucket,
+                    const uint32_t *d_pos, uint64_t ref_len, void *d_requests, uint64_t *d_text_pos, uint32_t *d_votes, aim_seed_t *d_seed,
+                    void *hip_stream)
+{
+    return seed_device("aim_seed_device", false, sp, n_reads, d_read_len, d_reads, d_bucket, d_pos, ref_len, d_requests, d_text_pos, d_votes, d_seed,
+                       nullptr, hip_stream);
+}
+
+const char *aim_seed_chain_kernel_names(void) { return "seed_chain_kernel,seed_chain_minimizer_kernel"; }
+
+int aim_seed_chain_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads, const uint32_t *d_bucket,
+                          const uint32_t *d_pos, uint64_t ref_len, void *d_requests, uint64_t *d_text_pos, uint32_t *d_votes, aim_seed_t *d_seed,
+                          aim_chain_t *d_chains_or_null, void *hip_stream)
+{
+    return seed_device("aim_seed_chain_device", true, sp, n_reads, d_read_len, d_reads, d_bucket, d_pos, ref_len, d_requests, d_text_pos, d_votes,
+                       d_seed, d_chains_or_null, hip_stream);
 }
 
 // ---------------------------------------------------------------------------

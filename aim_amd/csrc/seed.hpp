@@ -60,7 +60,7 @@ constexpr size_t seed_lds_bytes(int32_t read_size) { return kSeedKeyBytes + kSee
 // seed_minimizer_kernel's: one more dword per read position, the strand's order keys
 constexpr size_t seed_minimizer_lds_bytes(int32_t read_size) { return seed_lds_bytes(read_size) + 4u * (size_t)read_size; }
 
-#ifdef AIM_TU_SEED   // the kernel lives in tu_seed.hip alone; aim_capi.hip sees SeedArgs and the launcher
+#if defined(AIM_TU_SEED) || defined(AIM_TU_SEED_CHAIN)   // device code: tu_seed.hip, and tu_seed_chain.hip for what seed_chain.hpp shares
 
 __device__ __forceinline__ uint32_t seed_scan_add(uint32_t v, int lane)   // inclusive wave prefix sum
 {
@@ -256,6 +256,71 @@ __device__ __forceinline__ void seed_finish(const SeedArgs &a, uint32_t *keys, u
         a.seed[r] = sd;
     }
 }
+
+#endif
+
+#ifdef AIM_TU_SEED_CHAIN
+// The steps of the two kernels below as functions, for the kernels of seed_chain.hpp, which run them one strand at a time over (p, j)
+// anchors. The kernels below keep these steps inline, exactly as they were: their code objects do not change when seed_chain.hpp does.
+
+// stage: the read row r, once, into LDS (dwords)
+__device__ __forceinline__ void seed_stage(const SeedArgs &a, uint32_t *row4, uint32_t r, int32_t L, int lane)
+{
+    const uint32_t *g = reinterpret_cast<const uint32_t *>(a.reads + (uint64_t)r * (uint64_t)a.sp.read_size);
+    for (int w = lane; w < (L + 3) >> 2; w += kWave) row4[w] = g[w];
+}
+
+// The code of strand s's k-mer at query offset j: read forward from the row (s = 0), or backward from the same bytes with the complement
+// folded in (s = 1). *ok is cleared when it covers a byte other than upper-case A C G T.
+__device__ __forceinline__ uint32_t seed_code(const uint8_t *row, int32_t L, int32_t j, int32_t k, int s, bool *ok)
+{
+    const uint8_t *f = s ? row + (L - 1 - j) : row + j;
+    uint32_t code = 0;
+    for (int i = 0; i < k; ++i) {
+        const uint32_t x = s ? f[-i] : f[i];
+        *ok = *ok && seed_is_base(x);
+        code |= (((x >> 1) & 3u) ^ (s ? 2u : 0u)) << (2 * i);
+    }
+    return code;
+}
+
+// seed_minimizer_kernel's select for position j of the strand's order keys hk[0, n): L + R + 1 >= need = min(w, n), at most `reach`
+// reads per side. *mine_out receives hk[j] (kMinInvalid from n on).
+__device__ __forceinline__ bool seed_minimizer_selected(const uint32_t *hk, uint32_t j, uint32_t n, uint32_t reach, uint32_t need, uint32_t *mine_out)
+{
+    const uint32_t mine = j < n ? hk[j] : kMinInvalid;
+    bool left = mine != kMinInvalid, right = left;                          // the run on that side still extends
+    uint32_t span = 1;                                                      // L + R + 1
+    for (uint32_t d = 1; d <= reach; ++d) {
+        if (!__ballot(left || right)) break;
+        left = left && j >= d && hk[j - d] > mine;
+        right = right && j + d < n && hk[j + d] >= mine;
+        span += (uint32_t)left + (uint32_t)right;
+    }
+    *mine_out = mine;
+    return mine != kMinInvalid && span >= need;
+}
+
+// seed_append's lookup: the run pos[*b0, *b0 + n) of the lane's seed; n = 0 for no seed, an absent or over-frequent code and index
+// entries that point outside the arrays.
+__device__ __forceinline__ uint32_t seed_run(const SeedArgs &a, uint32_t code, bool ok, uint32_t *b0)
+{
+    const uint32_t n_codes = 1u << (2 * a.sp.k), max_occ = (uint32_t)a.sp.max_occ;
+    const uint64_t pos_cap = a.ref_len >= (uint64_t)a.sp.k ? a.ref_len - (uint64_t)a.sp.k + 1u : 0u;
+    uint32_t n = 0;
+    *b0 = 0;
+    if (ok && code < n_codes) {
+        *b0 = a.bucket[code];
+        const uint32_t b1 = a.bucket[code + 1u];
+        n = b1 - *b0;
+        if (b1 < *b0 || n > max_occ || (uint64_t)b1 > pos_cap) n = 0;
+        n = min(n, kSeedHits + 1u);                  // past kSeedHits only "overflowed" matters
+    }
+    return n;
+}
+#endif
+
+#ifdef AIM_TU_SEED   // the kernels live in tu_seed.hip alone; aim_capi.hip sees SeedArgs and the launchers
 
 __global__ __launch_bounds__(64) void seed_candidates_kernel(SeedArgs a)
 {

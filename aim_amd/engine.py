@@ -550,12 +550,26 @@ def seed_device(sp, n_reads, d_read_len, d_reads, d_bucket, d_pos, ref_len, d_re
                                            d_text_pos, d_votes, d_seed, stream))
 
 
-def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0"):
+def seed_chain_device(sp, n_reads, d_read_len, d_reads, d_bucket, d_pos, ref_len, d_requests, d_text_pos, d_votes, d_seed, d_chains=None, stream=None):
+    """aim_seed_chain_device on device pointers: seed_device with the hits chained instead of voted (band <= SEED_CHAIN_MAX_BAND);
+    d_chains (aim_chain_t per slot) may be None."""
+    capi.check(capi.load().aim_seed_chain_device(C.byref(sp), int(n_reads), d_read_len, d_reads, d_bucket, d_pos, int(ref_len), d_requests,
+                                                 d_text_pos, d_votes, d_seed, d_chains, stream))
+
+
+def seed_chain_candidates(sp, index, ref_len, read_len, reads, device="cuda:0"):
+    """seed_candidates through the chaining kernels: the same arguments and the same dict, where "votes" holds the chains' scores,
+    plus numpy "chains" (CHAIN_DTYPE, one per slot) and the device tensor "d_chains"."""
+    return seed_candidates(sp, index, ref_len, read_len, reads, device=device, chain=True)
+
+
+def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0", chain=False):
     """The seeding kernel on torch device buffers. `index` is build_index's (bucket, pos) -- numpy arrays, or uint8 torch tensors
     that already live on the device (as the "d_bucket" / "d_pos" of an earlier call); read_len is int32[n_reads], reads the ASCII
     rows uint8[n_reads][read_size]. Returns a dict: numpy "req" (REQUEST_DTYPE), "text_pos" (uint64), "votes" (uint32) and "seed"
     (SEED_DTYPE), each in slot order r * K + i, and the uint8 device tensors "d_req", "d_text_pos", "d_votes", "d_seed", "d_reads",
-    "d_read_len", "d_bucket", "d_pos" for chaining into align_device_groups and its siblings without a copy through the host."""
+    "d_read_len", "d_bucket", "d_pos" for feeding align_device_groups and its siblings without a copy through the host. chain=True
+    is seed_chain_candidates."""
     import torch
     dev = torch.device(device)
 
@@ -577,12 +591,19 @@ def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0"):
     d["d_text_pos"] = torch.zeros(slots * 8, dtype=torch.uint8, device=dev)
     d["d_votes"] = torch.zeros(slots * 4, dtype=torch.uint8, device=dev)
     d["d_seed"] = torch.zeros(max(n, 1) * 16, dtype=torch.uint8, device=dev)
+    if chain:
+        d["d_chains"] = torch.zeros(slots * 16, dtype=torch.uint8, device=dev)
     torch.cuda.synchronize(dev)
     with torch.cuda.device(dev):
-        seed_device(sp, n, d["d_read_len"].data_ptr(), d["d_reads"].data_ptr(), d["d_bucket"].data_ptr(), d["d_pos"].data_ptr(), ref_len,
-                    d["d_req"].data_ptr(), d["d_text_pos"].data_ptr(), d["d_votes"].data_ptr(), d["d_seed"].data_ptr(),
-                    torch.cuda.current_stream(dev).cuda_stream)
+        args = (sp, n, d["d_read_len"].data_ptr(), d["d_reads"].data_ptr(), d["d_bucket"].data_ptr(), d["d_pos"].data_ptr(), ref_len,
+                d["d_req"].data_ptr(), d["d_text_pos"].data_ptr(), d["d_votes"].data_ptr(), d["d_seed"].data_ptr())
+        if chain:
+            seed_chain_device(*args, d["d_chains"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            seed_device(*args, torch.cuda.current_stream(dev).cuda_stream)
     torch.cuda.synchronize(dev)
+    if chain:
+        d["chains"] = d["d_chains"].cpu().numpy().view(capi.CHAIN_DTYPE)[:n * K]
     d["req"] = d["d_req"].cpu().numpy().view(capi.REQUEST_DTYPE)[:n * K]
     d["text_pos"] = d["d_text_pos"].cpu().numpy().view(np.uint64)[:n * K]
     d["votes"] = d["d_votes"].cpu().numpy().view(np.uint32)[:n * K]

@@ -328,6 +328,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_SEED 0x800u /* device-side seeding: aim_index_sizes / aim_index_build / aim_seed_device / aim_seed_groups_offsets exist */
 #define AIM_FEATURE_INDEX_DEVICE 0x1000u /* aim_index_device_scratch / aim_index_build_device / aim_index_kernel_names exist */
 #define AIM_FEATURE_MINIMIZERS 0x2000u /* (w, k) minimizers: aim_index_build_minimizers / aim_index_build_device_minimizers / AIM_SEED_OPT_MINIMIZERS exist */
+#define AIM_FEATURE_SEED_CHAIN 0x4000u /* colinear chaining of the seed hits: aim_seed_chain_device / aim_chain_t / aim_seed_chain_kernel_names exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -670,8 +671,9 @@ const char *aim_sam_kernel_name(const aim_params_t *params);
  *     ascending order, computed on the query itself, left to right; stride must be 1. max_occ, the key a = p + read_size - j, rules 3-7
  *     are untouched. The index must have been built with the same (k, w): nothing in the arrays records w, so the library cannot check
  *     that, and a mismatch only loses seeds.
- * Follow-ups, not in this version: packed read rows, spaced seeds, a seeding stage inside aim_set_submit, chaining instead of voting,
- * compacting the selected positions before the device build's sort. Check aim_features() & AIM_FEATURE_SEED first. */
+ * Follow-ups, not in this version: packed read rows, spaced seeds, a seeding stage inside aim_set_submit, compacting the selected
+ * positions before the device build's sort; for chaining (below) also overlap filtering between chains (primary / secondary), a
+ * lookback other than 64 and MAPQ. Check aim_features() & AIM_FEATURE_SEED first. */
 #define AIM_SEED_MAX_CANDS 16
 #define AIM_SEED_MAX_HITS 1024      /* hits kept per (read, strand) */
 #define AIM_SEED_TRUNCATED 0x1u     /* aim_seed_t.flags: a strand dropped hits beyond AIM_SEED_MAX_HITS */
@@ -749,6 +751,53 @@ int aim_seed_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t
 int aim_seed_groups_offsets(uint32_t n_reads, uint32_t K, uint32_t *read_offsets /* [n_reads + 1] */);
 /* "seed_candidates_kernel": the rocprofv3 kernel-trace name prefix of aim_seed_device's kernel. */
 const char *aim_seed_kernel_name(void);
+
+/* ---- colinear chaining of the seed hits (AIM_FEATURE_SEED_CHAIN): chain-scored candidates with exact windows ----------------
+ * aim_seed_chain_device is aim_seed_device with rules 4-6 replaced: instead of sorting diagonals and cutting them into clusters by
+ * band, it chains the hits (p, j) with a gap cost, so a candidate's window follows the chain's net indel instead of its diagonal
+ * spread, and each candidate says which part of the read supports it. Rules 1-3 and 7, n_hits, AIM_SEED_TRUNCATED, the idx and slot
+ * layout, aim_seed_params_t and both seed sources (stride over the full index, or AIM_SEED_OPT_MINIMIZERS(w) over a minimizer index)
+ * are those of the seeding section above. For read r of length L and strand s, with k = aim_seed_params_t.k:
+ *   4c. Anchors. A kept hit of strand s is the pair (p, j): reference position and query offset; at most AIM_SEED_MAX_HITS per
+ *       strand, truncated in (j, p) order by rule 3. They are sorted ascending by (p, j); the pairs are distinct.
+ *       Lookback. The candidate predecessors of anchor i are the AIM_SEED_CHAIN_LOOKBACK anchors immediately before it in sorted
+ *       order (fewer at the start).
+ *       Admissible. With dp = p_i - p_j and dq = j_i - j_j (compared in 64 bits), predecessor j is admissible iff dp > 0, dq > 0 and
+ *       |dp - dq| <= band. band is 0..AIM_SEED_CHAIN_MAX_BAND here.
+ *       Score. gain = min(dp, dq, k); g = |dp - dq|; cost(0) = 0 and cost(g) = ((g * k) >> 7) + ((floor(log2 g) + 1) >> 1) otherwise;
+ *       f(i) = max(k, max over admissible j of f(j) + gain - cost). Anchor i takes a predecessor only when the best candidate score is
+ *       strictly greater than k; among equal best scores it takes the one of largest sorted index (the nearest). Otherwise i is a
+ *       root. k <= f <= AIM_SEED_MAX_HITS * 14, and no f is negative.
+ *       Chains. The predecessor links form trees, and each tree yields one chain: its end is the tree's anchor of greatest f (the
+ *       lowest sorted index on a tie) and the chain is the path from that end to the root. score = f(end), n_anchors = the path's
+ *       length, (p_lo, q_lo) = the root, p_hi = p_end + k, q_hi = j_end + k. Chains with n_anchors < min_votes are dropped.
+ *   5c. The chains of both strands are ranked by (score descending, strand ascending, p_lo ascending, q_lo ascending); the first
+ *       K = max_cands become the candidates, n_cands is their number.
+ *   6c. Candidate i fills slot r * K + i. In signed 64 bits: lo = p_lo - q_lo - flank, hi = p_hi + (L - q_hi) + flank,
+ *       start = max(lo, 0), end = max(start, min(hi, ref_len)); requests[slot] = {L, min(end - start, read_size), 0, idx_base + slot},
+ *       text_pos[slot] = start | s << 63, votes[slot] = score.
+ * aim_chain_t (optional, one per slot): score and n_anchors as above, q_lo, q_hi, and ref_span = p_hi - p_lo. [q_lo, q_hi) is the
+ * query interval the chain covers; for strand 1 the query is the read's reverse complement, so the interval of the read as given is
+ * [L - q_hi, L - q_lo). A caller clips with it, or takes it as the read interval of one part of a split read. Empty slots (rule 7)
+ * are all zero. */
+#define AIM_SEED_CHAIN_LOOKBACK 64
+#define AIM_SEED_CHAIN_MAX_BAND 4096
+typedef struct aim_chain {
+    uint32_t score;
+    uint16_t n_anchors, reserved;
+    uint16_t q_lo, q_hi;
+    uint32_t ref_span;
+} aim_chain_t;   /* 16 B per slot */
+/* aim_seed_device's arguments, checks and messages (under the name aim_seed_chain_device), AIM_EINVAL with a message naming band for
+ * a band above AIM_SEED_CHAIN_MAX_BAND, and d_chains: aim_chain_t[n_reads * K], or NULL when they are not wanted -- the other outputs
+ * do not depend on it. The kernel is seed_chain_kernel, or seed_chain_minimizer_kernel under AIM_SEED_OPT_MINIMIZERS; like
+ * aim_seed_device the call only enqueues work on hip_stream and needs no scratch. Check aim_features() & AIM_FEATURE_SEED_CHAIN. */
+int aim_seed_chain_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads,
+                          const uint32_t *d_bucket, const uint32_t *d_pos, uint64_t ref_len, void *d_requests /* aim_request_t[n_reads*K] */,
+                          uint64_t *d_text_pos, uint32_t *d_votes, aim_seed_t *d_seed, aim_chain_t *d_chains_or_null, void *hip_stream);
+/* "seed_chain_kernel,seed_chain_minimizer_kernel": comma-separated rocprofv3 kernel-trace name prefixes of aim_seed_chain_device's
+ * kernels. */
+const char *aim_seed_chain_kernel_names(void);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
