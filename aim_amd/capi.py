@@ -47,6 +47,8 @@ FEATURE_MINIMIZERS = 0x2000     # aim_features(): aim_index_build_minimizers / a
 SEED_MAX_W = 32                 # AIM_SEED_MAX_W: the minimizer window is 1..32
 FEATURE_SEED_CHAIN = 0x4000     # aim_features(): aim_seed_chain_device / aim_chain_t / aim_seed_chain_kernel_names exist
 SEED_CHAIN_LOOKBACK, SEED_CHAIN_MAX_BAND = 64, 4096
+FEATURE_SEED_CHAIN_LONG = 0x8000  # aim_features(): aim_seed_chain_long_device / aim_seed_chain_long_kernel_name exist
+SEED_LONG_MAX_READ_SIZE, SEED_LONG_MAX_HITS = 65528, 8192
 
 
 def SEED_OPT_MINIMIZERS(w):
@@ -230,6 +232,8 @@ SYMBOLS = {
     "aim_seed_device": (C.c_int, [C.POINTER(SeedParams), _U32, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP]),
     "aim_seed_chain_device": (C.c_int, [C.POINTER(SeedParams), _U32, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "aim_seed_chain_kernel_names": (C.c_char_p, []),
+    "aim_seed_chain_long_device": (C.c_int, [C.POINTER(SeedParams), _U32, _U32, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "aim_seed_chain_long_kernel_name": (C.c_char_p, []),
     "aim_seed_groups_offsets": (C.c_int, [_U32, _U32, _VP]),
     "aim_seed_kernel_name": (C.c_char_p, []),
     "aim_index_device_scratch": (C.c_int, [_I32, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -38,6 +38,7 @@
 #include "sam_fields.hpp"
 #include "seed.hpp"
 #include "seed_chain.hpp"
+#include "seed_chain_long.hpp"
 #include "index.hpp"
 #include "genasm_wave.hpp"
 
@@ -1674,7 +1675,7 @@ uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
            AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS | AIM_FEATURE_SEED |
-           AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS | AIM_FEATURE_SEED_CHAIN;
+           AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS | AIM_FEATURE_SEED_CHAIN | AIM_FEATURE_SEED_CHAIN_LONG;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -3278,6 +3279,33 @@ int seed_device(const char *fn, bool chain, const aim_seed_params_t *sp, uint32_
     HIP_TRY(hipGetLastError());
     return AIM_OK;
 }
+
+// aim_seed_chain_long_device's own parameter check: check_seed_params' bounds and messages with the long read_size bound, minimizers
+// required, and the hit cap.
+int check_seed_long_params(const aim_seed_params_t &sp, uint32_t max_hits)
+{
+    if (sp.k < 8 || sp.k > 14) return fail(AIM_EINVAL, "aim_seed_params_t: k %d is outside 8..14", sp.k);
+    if (sp.stride < 1) return fail(AIM_EINVAL, "aim_seed_params_t: stride %d must be >= 1", sp.stride);
+    if (sp.max_occ < 1) return fail(AIM_EINVAL, "aim_seed_params_t: max_occ %d must be >= 1", sp.max_occ);
+    if (sp.band < 0) return fail(AIM_EINVAL, "aim_seed_params_t: band %d must be >= 0", sp.band);
+    if (sp.flank < 0) return fail(AIM_EINVAL, "aim_seed_params_t: flank %d must be >= 0", sp.flank);
+    if (sp.min_votes < 1) return fail(AIM_EINVAL, "aim_seed_params_t: min_votes %d must be >= 1", sp.min_votes);
+    if (sp.max_cands < 1 || sp.max_cands > AIM_SEED_MAX_CANDS)
+        return fail(AIM_EINVAL, "aim_seed_params_t: max_cands %d is outside 1..%d", sp.max_cands, AIM_SEED_MAX_CANDS);
+    if (sp.read_size <= 0 || (sp.read_size & 7) || sp.read_size > AIM_SEED_LONG_MAX_READ_SIZE)
+        return fail(AIM_EINVAL, "aim_seed_params_t: read_size %d must be a positive multiple of 8, at most %d (aim_seed_chain_long_device)", sp.read_size,
+                    AIM_SEED_LONG_MAX_READ_SIZE);
+    if (!sp.options)
+        return fail(AIM_EINVAL, "aim_seed_params_t: options 0x0 must be AIM_SEED_OPT_MINIMIZERS(w) (aim_seed_chain_long_device takes minimizer seeds only)");
+    const uint32_t w = sp.options >> 8;
+    if ((sp.options & 0xffu) || w < 1 || w > AIM_SEED_MAX_W) return fail(AIM_EINVAL, "aim_seed_params_t: unknown options 0x%x", sp.options);
+    if (sp.stride != 1) return fail(AIM_EINVAL, "aim_seed_params_t: stride %d must be 1 with AIM_SEED_OPT_MINIMIZERS", sp.stride);
+    if (sp.band > AIM_SEED_CHAIN_MAX_BAND)
+        return fail(AIM_EINVAL, "aim_seed_params_t: band %d is above %d (aim_seed_chain_long_device)", sp.band, AIM_SEED_CHAIN_MAX_BAND);
+    if (max_hits < AIM_SEED_MAX_HITS || max_hits > AIM_SEED_LONG_MAX_HITS || (max_hits & (max_hits - 1u)))
+        return fail(AIM_EINVAL, "aim_seed_chain_long_device: max_hits %u must be a power of two in %d..%d", max_hits, AIM_SEED_MAX_HITS, AIM_SEED_LONG_MAX_HITS);
+    return AIM_OK;
+}
 }  // namespace
 }
 
@@ -3297,6 +3325,59 @@ int aim_seed_chain_device(const aim_seed_params_t *sp, uint32_t n_reads, const i
 {
     return seed_device("aim_seed_chain_device", true, sp, n_reads, d_read_len, d_reads, d_bucket, d_pos, ref_len, d_requests, d_text_pos, d_votes,
                        d_seed, d_chains_or_null, hip_stream);
+}
+
+const char *aim_seed_chain_long_kernel_name(void) { return "seed_chain_long_kernel"; }
+
+// aim_seed_chain_device for long reads (AIM_FEATURE_SEED_CHAIN_LONG; the kernel in seed_chain_long.hpp): seed_device()'s order of checks
+// and its grid, with the hit cap H deciding the LDS and with it the workgroups per CU.
+int aim_seed_chain_long_device(const aim_seed_params_t *sp, uint32_t max_hits, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads,
+                               const uint32_t *d_bucket, const uint32_t *d_pos, uint64_t ref_len, void *d_requests, uint64_t *d_text_pos, uint32_t *d_votes,
+                               aim_seed_t *d_seed, aim_chain_t *d_chains_or_null, void *hip_stream)
+{
+    const char *fn = "aim_seed_chain_long_device";
+    if (!sp) return fail(AIM_EINVAL, "%s: sp is NULL", fn);
+    int rc = check_seed_long_params(*sp, max_hits);
+    if (rc) return rc;
+    if (ref_len > AIM_SEED_MAX_REF_LEN)
+        return fail(AIM_EINVAL, "%s: ref_len %llu is above 2^32 - 2^25 (positions and diagonal keys are 32-bit)", fn, (unsigned long long)ref_len);
+    if ((uint64_t)n_reads * (uint64_t)sp->max_cands >= (1ull << 32))
+        return fail(AIM_EINVAL, "%s: n_reads %u * max_cands %d does not fit 32 bits (split the batch)", fn, n_reads, sp->max_cands);
+    if (n_reads && (!d_read_len || !d_reads || !d_bucket || (!d_pos && ref_len >= (uint64_t)sp->k) || !d_requests || !d_text_pos || !d_votes || !d_seed))
+        return fail(AIM_EINVAL, "%s: null device buffer", fn);
+    int n = 0;
+    rc = aim_device_count(&n);
+    if (rc) return rc;
+    if (!n_reads) return AIM_OK;
+    const aim::Knobs kn = with_chip(read_knobs());
+    aim::SeedChainLongArgs la;
+    memset(&la, 0, sizeof la);
+    aim::SeedArgs &a = la.c.s;
+    a.sp = *sp;
+    a.n_reads = n_reads;
+    a.read_len = d_read_len;
+    a.reads = d_reads;
+    a.bucket = d_bucket;
+    a.pos = d_pos;
+    a.ref_len = ref_len;
+    a.req = static_cast<aim_request_t *>(d_requests);
+    a.text_pos = d_text_pos;
+    a.votes = d_votes;
+    a.seed = d_seed;
+    la.c.chains = d_chains_or_null;
+    la.max_hits = max_hits;
+    const size_t lds = aim::seed_chain_long_lds_bytes(max_hits);
+    a.dbg_poison_lds = kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u;
+    a.dbg_lds_bytes = (uint32_t)lds;
+    // persistent grid as seed_device(): what LDS lets one CU hold, on every CU, capped at the reads rounded up to the multiple of 8
+    const uint32_t per_cu = (uint32_t)std::min<size_t>(16, aim::lds_workgroups_per_cu(lds));
+    const uint32_t grid = std::min(aim::resident_grid(kn, per_cu), (uint32_t)std::min<uint64_t>(((uint64_t)n_reads + 7u) & ~7ull, 1u << 20));
+    if (kn.plan_debug)
+        fprintf(stderr, "[aim plan] seed_chain_long_kernel grid=%u block=64 lds=%zu per_cu=%u reads=%u max_hits=%u tile=%u\n", grid, lds, per_cu, n_reads,
+                max_hits, aim::kSeedLongTile);
+    aim::seed_chain_long_launch(la, grid, lds, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -60,7 +60,7 @@ constexpr size_t seed_lds_bytes(int32_t read_size) { return kSeedKeyBytes + kSee
 // seed_minimizer_kernel's: one more dword per read position, the strand's order keys
 constexpr size_t seed_minimizer_lds_bytes(int32_t read_size) { return seed_lds_bytes(read_size) + 4u * (size_t)read_size; }
 
-#if defined(AIM_TU_SEED) || defined(AIM_TU_SEED_CHAIN)   // device code: tu_seed.hip, and tu_seed_chain.hip for what seed_chain.hpp shares
+#if defined(AIM_TU_SEED) || defined(AIM_TU_SEED_CHAIN) || defined(AIM_TU_SEED_CHAIN_LONG)   // device code: tu_seed.hip, and tu_seed_chain.hip / tu_seed_chain_long.hip for what their headers share
 
 __device__ __forceinline__ uint32_t seed_scan_add(uint32_t v, int lane)   // inclusive wave prefix sum
 {

@@ -1,0 +1,4 @@
+// tu_seed_chain_long.hip -- the translation unit that instantiates the kernel of seed_chain_long.hpp (aim_amd/build.py compiles the
+// tu_*.hip files in parallel and links them with aim_capi.hip into libaim_hip.so).
+#define AIM_TU_SEED_CHAIN_LONG 1
+#include "seed_chain_long.hpp"

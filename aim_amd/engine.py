@@ -515,12 +515,13 @@ def build_index_device(reference, k, device="cuda:0", stream=None, w=None):
     return d_bucket, d_pos, n_pos
 
 
-def seed_params(k, read_size, stride=1, max_occ=16, band=8, flank=8, min_votes=2, max_cands=4, idx_base=0, w=None):
+def seed_params(k, read_size, stride=1, max_occ=16, band=8, flank=8, min_votes=2, max_cands=4, idx_base=0, w=None, long_reads=False):
     """aim_seed_params_t, validated like make_params: ValueError names the field that is out of bounds. With a window `w` the seeds
     are the query's (w, k) minimizers (options = AIM_SEED_OPT_MINIMIZERS(w)); stride must then be 1 and the index one of the same
-    (k, w)."""
+    (k, w). long_reads=True: the parameters are for seed_chain_long_device, whose read_size goes up to SEED_LONG_MAX_READ_SIZE."""
     bounds = (("k", k, 8, 14), ("stride", stride, 1, None), ("max_occ", max_occ, 1, None), ("band", band, 0, None), ("flank", flank, 0, None),
-              ("min_votes", min_votes, 1, None), ("max_cands", max_cands, 1, capi.SEED_MAX_CANDS), ("read_size", read_size, 8, capi.SEED_MAX_READ_SIZE))
+              ("min_votes", min_votes, 1, None), ("max_cands", max_cands, 1, capi.SEED_MAX_CANDS),
+              ("read_size", read_size, 8, capi.SEED_LONG_MAX_READ_SIZE if long_reads else capi.SEED_MAX_READ_SIZE))
     for name, v, lo, hi in bounds:
         if int(v) != v or v < lo or (hi is not None and v > hi) or v >= 1 << 31:
             raise ValueError("%s %r is outside %d..%s" % (name, v, lo, "" if hi is None else hi))
@@ -563,13 +564,27 @@ def seed_chain_candidates(sp, index, ref_len, read_len, reads, device="cuda:0"):
     return seed_candidates(sp, index, ref_len, read_len, reads, device=device, chain=True)
 
 
-def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0", chain=False):
+def seed_chain_long_device(sp, max_hits, n_reads, d_read_len, d_reads, d_bucket, d_pos, ref_len, d_requests, d_text_pos, d_votes, d_seed, d_chains=None,
+                           stream=None):
+    """aim_seed_chain_long_device on device pointers: seed_chain_device over minimizer seeds with the hit cap `max_hits` (a power of two
+    in 1024..SEED_LONG_MAX_HITS) and read_size up to SEED_LONG_MAX_READ_SIZE."""
+    capi.check(capi.load().aim_seed_chain_long_device(C.byref(sp), int(max_hits), int(n_reads), d_read_len, d_reads, d_bucket, d_pos, int(ref_len),
+                                                      d_requests, d_text_pos, d_votes, d_seed, d_chains, stream))
+
+
+def seed_chain_long_candidates(sp, max_hits, index, ref_len, read_len, reads, device="cuda:0"):
+    """seed_chain_candidates through seed_chain_long_kernel: the same dict, for the parameters of seed_params(..., long_reads=True) and
+    the hit cap `max_hits`; `index` is a minimizer index of sp's (k, w)."""
+    return seed_candidates(sp, index, ref_len, read_len, reads, device=device, chain=True, max_hits=int(max_hits))
+
+
+def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0", chain=False, max_hits=None):
     """The seeding kernel on torch device buffers. `index` is build_index's (bucket, pos) -- numpy arrays, or uint8 torch tensors
     that already live on the device (as the "d_bucket" / "d_pos" of an earlier call); read_len is int32[n_reads], reads the ASCII
     rows uint8[n_reads][read_size]. Returns a dict: numpy "req" (REQUEST_DTYPE), "text_pos" (uint64), "votes" (uint32) and "seed"
     (SEED_DTYPE), each in slot order r * K + i, and the uint8 device tensors "d_req", "d_text_pos", "d_votes", "d_seed", "d_reads",
     "d_read_len", "d_bucket", "d_pos" for feeding align_device_groups and its siblings without a copy through the host. chain=True
-    is seed_chain_candidates."""
+    is seed_chain_candidates, and with max_hits seed_chain_long_candidates."""
     import torch
     dev = torch.device(device)
 
@@ -597,7 +612,9 @@ def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0", chain=
     with torch.cuda.device(dev):
         args = (sp, n, d["d_read_len"].data_ptr(), d["d_reads"].data_ptr(), d["d_bucket"].data_ptr(), d["d_pos"].data_ptr(), ref_len,
                 d["d_req"].data_ptr(), d["d_text_pos"].data_ptr(), d["d_votes"].data_ptr(), d["d_seed"].data_ptr())
-        if chain:
+        if chain and max_hits is not None:
+            seed_chain_long_device(sp, max_hits, *args[1:], d["d_chains"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        elif chain:
             seed_chain_device(*args, d["d_chains"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         else:
             seed_device(*args, torch.cuda.current_stream(dev).cuda_stream)

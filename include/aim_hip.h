@@ -329,6 +329,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_INDEX_DEVICE 0x1000u /* aim_index_device_scratch / aim_index_build_device / aim_index_kernel_names exist */
 #define AIM_FEATURE_MINIMIZERS 0x2000u /* (w, k) minimizers: aim_index_build_minimizers / aim_index_build_device_minimizers / AIM_SEED_OPT_MINIMIZERS exist */
 #define AIM_FEATURE_SEED_CHAIN 0x4000u /* colinear chaining of the seed hits: aim_seed_chain_device / aim_chain_t / aim_seed_chain_kernel_names exist */
+#define AIM_FEATURE_SEED_CHAIN_LONG 0x8000u /* chaining for long reads: aim_seed_chain_long_device / aim_seed_chain_long_kernel_name exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -673,7 +674,8 @@ const char *aim_sam_kernel_name(const aim_params_t *params);
  *     that, and a mismatch only loses seeds.
  * Follow-ups, not in this version: packed read rows, spaced seeds, a seeding stage inside aim_set_submit, compacting the selected
  * positions before the device build's sort; for chaining (below) also overlap filtering between chains (primary / secondary), a
- * lookback other than 64 and MAPQ. Check aim_features() & AIM_FEATURE_SEED first. */
+ * lookback other than 64, MAPQ, and beyond aim_seed_chain_long_device more than 8 192 anchors per strand and reads above 65 528
+ * bases. Check aim_features() & AIM_FEATURE_SEED first. */
 #define AIM_SEED_MAX_CANDS 16
 #define AIM_SEED_MAX_HITS 1024      /* hits kept per (read, strand) */
 #define AIM_SEED_TRUNCATED 0x1u     /* aim_seed_t.flags: a strand dropped hits beyond AIM_SEED_MAX_HITS */
@@ -798,6 +800,35 @@ int aim_seed_chain_device(const aim_seed_params_t *sp, uint32_t n_reads, const i
 /* "seed_chain_kernel,seed_chain_minimizer_kernel": comma-separated rocprofv3 kernel-trace name prefixes of aim_seed_chain_device's
  * kernels. */
 const char *aim_seed_chain_kernel_names(void);
+
+/* ---- chaining for long reads (AIM_FEATURE_SEED_CHAIN_LONG): the aligner's read lengths, a caller-chosen hit cap ----------------
+ * aim_seed_chain_long_device is aim_seed_chain_device -- rules 1-3, 4c-6c and 7, aim_chain_t, the slot and idx layout, d_chains or
+ * NULL -- for read rows of up to AIM_SEED_LONG_MAX_READ_SIZE bases and up to AIM_SEED_LONG_MAX_HITS anchors per strand, with exactly
+ * these differences:
+ *   Seeds. Minimizers only: options must be AIM_SEED_OPT_MINIMIZERS(w), w = 1..AIM_SEED_MAX_W, over a minimizer index of the same
+ *     (k, w); w = 1 selects every valid k-mer, which is aim_index_build's index. options = 0 is refused. stride must be 1.
+ *   Hit cap. max_hits = H takes the place of AIM_SEED_MAX_HITS in rule 3, in rule 4c and in n_hits / AIM_SEED_TRUNCATED: hits are kept
+ *     in (j, p) order up to H per strand. H is a power of two in 1024..AIM_SEED_LONG_MAX_HITS. It is part of the rule -- it decides
+ *     which hits are dropped -- and k <= f <= H * 14.
+ *   Read size. read_size is a positive multiple of 8, at most AIM_SEED_LONG_MAX_READ_SIZE: the largest multiple of 8 for which q_hi
+ *     fits aim_chain_t's uint16_t. text_len = min(end - start, read_size) as before; a read_len outside 0..read_size is clamped.
+ * Everything else is identical: band <= AIM_SEED_CHAIN_MAX_BAND, the lookback of AIM_SEED_CHAIN_LOOKBACK, gain, cost and the tie
+ * rules, the ranking by (score descending, strand, p_lo, q_lo), the windows, the empty slots, and the tolerance of index entries that
+ * point outside the arrays. So for read_size <= AIM_SEED_MAX_READ_SIZE and H = AIM_SEED_MAX_HITS every output byte equals
+ * aim_seed_chain_device's under the same AIM_SEED_OPT_MINIMIZERS(w). The result is deterministic and independent of the grid.
+ * The kernel is seed_chain_long_kernel (csrc/seed_chain_long.hpp): it walks the read in tiles from global memory, so its LDS is
+ * 14 * H bytes plus a fixed tile buffer whatever read_size is, and H decides how many reads one compute unit chains at a time
+ * (9, 5, 2, 1 for H = 1024, 2048, 4096, 8192). The call only enqueues work on hip_stream and needs no scratch.
+ * AIM_EINVAL with a message naming the field: the refusals of aim_seed_chain_device under the name aim_seed_chain_long_device, with
+ * the read_size bound above, and for a max_hits that is no power of two in 1024..AIM_SEED_LONG_MAX_HITS and for options = 0. The
+ * parameter checks come before any device query. aim_seed_device and aim_seed_chain_device keep their bounds. */
+#define AIM_SEED_LONG_MAX_READ_SIZE 65528
+#define AIM_SEED_LONG_MAX_HITS 8192
+int aim_seed_chain_long_device(const aim_seed_params_t *sp, uint32_t max_hits, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads,
+                               const uint32_t *d_bucket, const uint32_t *d_pos, uint64_t ref_len, void *d_requests /* aim_request_t[n_reads*K] */,
+                               uint64_t *d_text_pos, uint32_t *d_votes, aim_seed_t *d_seed, aim_chain_t *d_chains_or_null, void *hip_stream);
+/* "seed_chain_long_kernel": the rocprofv3 kernel-trace name prefix of aim_seed_chain_long_device's kernel. */
+const char *aim_seed_chain_long_kernel_name(void);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
