@@ -3056,7 +3056,9 @@ int check_index_args(int32_t k, uint64_t ref_len)
     return AIM_OK;
 }
 
-int check_seed_params(const aim_seed_params_t &sp)
+// The bounds every seeding entry point sets. max_read_size is AIM_SEED_MAX_READ_SIZE, or the entry point's own bound, and then `fn`
+// names that entry point in the read_size message.
+int check_seed_params(const aim_seed_params_t &sp, int32_t max_read_size = AIM_SEED_MAX_READ_SIZE, const char *fn = nullptr)
 {
     if (sp.k < 8 || sp.k > 14) return fail(AIM_EINVAL, "aim_seed_params_t: k %d is outside 8..14", sp.k);
     if (sp.stride < 1) return fail(AIM_EINVAL, "aim_seed_params_t: stride %d must be >= 1", sp.stride);
@@ -3066,8 +3068,9 @@ int check_seed_params(const aim_seed_params_t &sp)
     if (sp.min_votes < 1) return fail(AIM_EINVAL, "aim_seed_params_t: min_votes %d must be >= 1", sp.min_votes);
     if (sp.max_cands < 1 || sp.max_cands > AIM_SEED_MAX_CANDS)
         return fail(AIM_EINVAL, "aim_seed_params_t: max_cands %d is outside 1..%d", sp.max_cands, AIM_SEED_MAX_CANDS);
-    if (sp.read_size <= 0 || (sp.read_size & 7) || sp.read_size > AIM_SEED_MAX_READ_SIZE)
-        return fail(AIM_EINVAL, "aim_seed_params_t: read_size %d must be a positive multiple of 8, at most %d", sp.read_size, AIM_SEED_MAX_READ_SIZE);
+    if (sp.read_size <= 0 || (sp.read_size & 7) || sp.read_size > max_read_size)
+        return fail(AIM_EINVAL, "aim_seed_params_t: read_size %d must be a positive multiple of 8, at most %d%s%s%s", sp.read_size, max_read_size,
+                    fn ? " (" : "", fn ? fn : "", fn ? ")" : "");
     if (sp.options) {   // AIM_SEED_OPT_MINIMIZERS(w) and nothing else
         const uint32_t w = sp.options >> 8;
         if ((sp.options & 0xffu) || w < 1 || w > AIM_SEED_MAX_W) return fail(AIM_EINVAL, "aim_seed_params_t: unknown options 0x%x", sp.options);
@@ -3221,16 +3224,14 @@ const char *aim_seed_kernel_name(void) { return "seed_candidates_kernel"; }
 
 extern "C++" {
 namespace {
-// aim_seed_device (chain = false) and aim_seed_chain_device (chain = true: the chaining kernels, the band bound and d_chains)
-int seed_device(const char *fn, bool chain, const aim_seed_params_t *sp, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads,
-                const uint32_t *d_bucket, const uint32_t *d_pos, uint64_t ref_len, void *d_requests, uint64_t *d_text_pos, uint32_t *d_votes,
-                aim_seed_t *d_seed, aim_chain_t *d_chains, void *hip_stream)
+// What the seeding entry points share once their parameters are checked: the checks on ref_len, the batch size and the device pointers,
+// the device probe, the SeedArgs `a` (inside the entry point's zeroed argument struct) with the poison knobs, the persistent grid and the
+// plan line, which ends in plan_tail. launch(grid) starts `kernel`, whose workgroups take `lds` bytes each.
+template <typename Launch>
+int seed_submit(const char *fn, const char *kernel, const char *plan_tail, aim::SeedArgs &a, size_t lds, const aim_seed_params_t *sp, uint32_t n_reads,
+                const int32_t *d_read_len, const char *d_reads, const uint32_t *d_bucket, const uint32_t *d_pos, uint64_t ref_len, void *d_requests,
+                uint64_t *d_text_pos, uint32_t *d_votes, aim_seed_t *d_seed, Launch launch)
 {
-    if (!sp) return fail(AIM_EINVAL, "%s: sp is NULL", fn);
-    int rc = check_seed_params(*sp);
-    if (rc) return rc;
-    if (chain && sp->band > AIM_SEED_CHAIN_MAX_BAND)
-        return fail(AIM_EINVAL, "aim_seed_params_t: band %d is above %d (%s)", sp->band, AIM_SEED_CHAIN_MAX_BAND, fn);
     if (ref_len > AIM_SEED_MAX_REF_LEN)
         return fail(AIM_EINVAL, "%s: ref_len %llu is above 2^32 - 2^25 (positions and diagonal keys are 32-bit)", fn, (unsigned long long)ref_len);
     if ((uint64_t)n_reads * (uint64_t)sp->max_cands >= (1ull << 32))
@@ -3238,13 +3239,10 @@ int seed_device(const char *fn, bool chain, const aim_seed_params_t *sp, uint32_
     if (n_reads && (!d_read_len || !d_reads || !d_bucket || (!d_pos && ref_len >= (uint64_t)sp->k) || !d_requests || !d_text_pos || !d_votes || !d_seed))
         return fail(AIM_EINVAL, "%s: null device buffer", fn);
     int n = 0;
-    rc = aim_device_count(&n);
+    const int rc = aim_device_count(&n);
     if (rc) return rc;
     if (!n_reads) return AIM_OK;
     const aim::Knobs kn = with_chip(read_knobs());
-    aim::SeedChainArgs ca;
-    memset(&ca, 0, sizeof ca);
-    aim::SeedArgs &a = ca.s;
     a.sp = *sp;
     a.n_reads = n_reads;
     a.read_len = d_read_len;
@@ -3256,50 +3254,54 @@ int seed_device(const char *fn, bool chain, const aim_seed_params_t *sp, uint32_
     a.text_pos = d_text_pos;
     a.votes = d_votes;
     a.seed = d_seed;
-    ca.chains = d_chains;
-    const bool minimizers = sp->options != 0;
-    const size_t lds = chain ? (minimizers ? aim::seed_chain_minimizer_lds_bytes(sp->read_size) : aim::seed_chain_lds_bytes(sp->read_size))
-                             : (minimizers ? aim::seed_minimizer_lds_bytes(sp->read_size) : aim::seed_lds_bytes(sp->read_size));
     a.dbg_poison_lds = kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u;
     a.dbg_lds_bytes = (uint32_t)lds;
     // persistent grid: what LDS lets one CU hold (at most 16 wavefronts), on every CU, capped at the reads rounded up to the multiple of 8
     // xcd_unit needs (below 8 reads the surplus workgroups find no work and leave)
     const uint32_t per_cu = (uint32_t)std::min<size_t>(16, aim::lds_workgroups_per_cu(lds));
     const uint32_t grid = std::min(aim::resident_grid(kn, per_cu), (uint32_t)std::min<uint64_t>(((uint64_t)n_reads + 7u) & ~7ull, 1u << 20));
-    if (kn.plan_debug)
-        fprintf(stderr, "[aim plan] %s grid=%u block=64 lds=%zu per_cu=%u reads=%u\n",
-                chain ? (minimizers ? "seed_chain_minimizer_kernel" : "seed_chain_kernel") : (minimizers ? "seed_minimizer_kernel" : "seed_candidates_kernel"),
-                grid, lds, per_cu, n_reads);
-    if (chain)
-        aim::seed_chain_launch(ca, minimizers, grid, lds, (hipStream_t)hip_stream);
-    else if (minimizers)
-        aim::seed_minimizer_launch(a, grid, lds, (hipStream_t)hip_stream);
-    else
-        aim::seed_launch(a, grid, lds, (hipStream_t)hip_stream);
+    if (kn.plan_debug) fprintf(stderr, "[aim plan] %s grid=%u block=64 lds=%zu per_cu=%u reads=%u%s\n", kernel, grid, lds, per_cu, n_reads, plan_tail);
+    launch(grid);
     HIP_TRY(hipGetLastError());
     return AIM_OK;
 }
 
-// aim_seed_chain_long_device's own parameter check: check_seed_params' bounds and messages with the long read_size bound, minimizers
-// required, and the hit cap.
+// aim_seed_device (chain = false) and aim_seed_chain_device (chain = true: the chaining kernels, the band bound and d_chains)
+int seed_device(const char *fn, bool chain, const aim_seed_params_t *sp, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads,
+                const uint32_t *d_bucket, const uint32_t *d_pos, uint64_t ref_len, void *d_requests, uint64_t *d_text_pos, uint32_t *d_votes,
+                aim_seed_t *d_seed, aim_chain_t *d_chains, void *hip_stream)
+{
+    if (!sp) return fail(AIM_EINVAL, "%s: sp is NULL", fn);
+    const int rc = check_seed_params(*sp);
+    if (rc) return rc;
+    if (chain && sp->band > AIM_SEED_CHAIN_MAX_BAND)
+        return fail(AIM_EINVAL, "aim_seed_params_t: band %d is above %d (%s)", sp->band, AIM_SEED_CHAIN_MAX_BAND, fn);
+    aim::SeedChainArgs ca;
+    memset(&ca, 0, sizeof ca);
+    ca.chains = d_chains;
+    const bool minimizers = sp->options != 0;
+    const size_t lds = chain ? (minimizers ? aim::seed_chain_minimizer_lds_bytes(sp->read_size) : aim::seed_chain_lds_bytes(sp->read_size))
+                             : (minimizers ? aim::seed_minimizer_lds_bytes(sp->read_size) : aim::seed_lds_bytes(sp->read_size));
+    const char *kernel = chain ? (minimizers ? "seed_chain_minimizer_kernel" : "seed_chain_kernel") : (minimizers ? "seed_minimizer_kernel" : "seed_candidates_kernel");
+    return seed_submit(fn, kernel, "", ca.s, lds, sp, n_reads, d_read_len, d_reads, d_bucket, d_pos, ref_len, d_requests, d_text_pos, d_votes, d_seed,
+                       [&](uint32_t grid) {
+                           if (chain)
+                               aim::seed_chain_launch(ca, minimizers, grid, lds, (hipStream_t)hip_stream);
+                           else if (minimizers)
+                               aim::seed_minimizer_launch(ca.s, grid, lds, (hipStream_t)hip_stream);
+                           else
+                               aim::seed_launch(ca.s, grid, lds, (hipStream_t)hip_stream);
+                       });
+}
+
+// aim_seed_chain_long_device's parameter check: check_seed_params with the long read_size bound, then what is its own -- minimizers
+// required, the band bound and the hit cap.
 int check_seed_long_params(const aim_seed_params_t &sp, uint32_t max_hits)
 {
-    if (sp.k < 8 || sp.k > 14) return fail(AIM_EINVAL, "aim_seed_params_t: k %d is outside 8..14", sp.k);
-    if (sp.stride < 1) return fail(AIM_EINVAL, "aim_seed_params_t: stride %d must be >= 1", sp.stride);
-    if (sp.max_occ < 1) return fail(AIM_EINVAL, "aim_seed_params_t: max_occ %d must be >= 1", sp.max_occ);
-    if (sp.band < 0) return fail(AIM_EINVAL, "aim_seed_params_t: band %d must be >= 0", sp.band);
-    if (sp.flank < 0) return fail(AIM_EINVAL, "aim_seed_params_t: flank %d must be >= 0", sp.flank);
-    if (sp.min_votes < 1) return fail(AIM_EINVAL, "aim_seed_params_t: min_votes %d must be >= 1", sp.min_votes);
-    if (sp.max_cands < 1 || sp.max_cands > AIM_SEED_MAX_CANDS)
-        return fail(AIM_EINVAL, "aim_seed_params_t: max_cands %d is outside 1..%d", sp.max_cands, AIM_SEED_MAX_CANDS);
-    if (sp.read_size <= 0 || (sp.read_size & 7) || sp.read_size > AIM_SEED_LONG_MAX_READ_SIZE)
-        return fail(AIM_EINVAL, "aim_seed_params_t: read_size %d must be a positive multiple of 8, at most %d (aim_seed_chain_long_device)", sp.read_size,
-                    AIM_SEED_LONG_MAX_READ_SIZE);
+    const int rc = check_seed_params(sp, AIM_SEED_LONG_MAX_READ_SIZE, "aim_seed_chain_long_device");
+    if (rc) return rc;
     if (!sp.options)
         return fail(AIM_EINVAL, "aim_seed_params_t: options 0x0 must be AIM_SEED_OPT_MINIMIZERS(w) (aim_seed_chain_long_device takes minimizer seeds only)");
-    const uint32_t w = sp.options >> 8;
-    if ((sp.options & 0xffu) || w < 1 || w > AIM_SEED_MAX_W) return fail(AIM_EINVAL, "aim_seed_params_t: unknown options 0x%x", sp.options);
-    if (sp.stride != 1) return fail(AIM_EINVAL, "aim_seed_params_t: stride %d must be 1 with AIM_SEED_OPT_MINIMIZERS", sp.stride);
     if (sp.band > AIM_SEED_CHAIN_MAX_BAND)
         return fail(AIM_EINVAL, "aim_seed_params_t: band %d is above %d (aim_seed_chain_long_device)", sp.band, AIM_SEED_CHAIN_MAX_BAND);
     if (max_hits < AIM_SEED_MAX_HITS || max_hits > AIM_SEED_LONG_MAX_HITS || (max_hits & (max_hits - 1u)))
@@ -3337,47 +3339,17 @@ int aim_seed_chain_long_device(const aim_seed_params_t *sp, uint32_t max_hits, u
 {
     const char *fn = "aim_seed_chain_long_device";
     if (!sp) return fail(AIM_EINVAL, "%s: sp is NULL", fn);
-    int rc = check_seed_long_params(*sp, max_hits);
+    const int rc = check_seed_long_params(*sp, max_hits);
     if (rc) return rc;
-    if (ref_len > AIM_SEED_MAX_REF_LEN)
-        return fail(AIM_EINVAL, "%s: ref_len %llu is above 2^32 - 2^25 (positions and diagonal keys are 32-bit)", fn, (unsigned long long)ref_len);
-    if ((uint64_t)n_reads * (uint64_t)sp->max_cands >= (1ull << 32))
-        return fail(AIM_EINVAL, "%s: n_reads %u * max_cands %d does not fit 32 bits (split the batch)", fn, n_reads, sp->max_cands);
-    if (n_reads && (!d_read_len || !d_reads || !d_bucket || (!d_pos && ref_len >= (uint64_t)sp->k) || !d_requests || !d_text_pos || !d_votes || !d_seed))
-        return fail(AIM_EINVAL, "%s: null device buffer", fn);
-    int n = 0;
-    rc = aim_device_count(&n);
-    if (rc) return rc;
-    if (!n_reads) return AIM_OK;
-    const aim::Knobs kn = with_chip(read_knobs());
     aim::SeedChainLongArgs la;
     memset(&la, 0, sizeof la);
-    aim::SeedArgs &a = la.c.s;
-    a.sp = *sp;
-    a.n_reads = n_reads;
-    a.read_len = d_read_len;
-    a.reads = d_reads;
-    a.bucket = d_bucket;
-    a.pos = d_pos;
-    a.ref_len = ref_len;
-    a.req = static_cast<aim_request_t *>(d_requests);
-    a.text_pos = d_text_pos;
-    a.votes = d_votes;
-    a.seed = d_seed;
     la.c.chains = d_chains_or_null;
     la.max_hits = max_hits;
     const size_t lds = aim::seed_chain_long_lds_bytes(max_hits);
-    a.dbg_poison_lds = kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u;
-    a.dbg_lds_bytes = (uint32_t)lds;
-    // persistent grid as seed_device(): what LDS lets one CU hold, on every CU, capped at the reads rounded up to the multiple of 8
-    const uint32_t per_cu = (uint32_t)std::min<size_t>(16, aim::lds_workgroups_per_cu(lds));
-    const uint32_t grid = std::min(aim::resident_grid(kn, per_cu), (uint32_t)std::min<uint64_t>(((uint64_t)n_reads + 7u) & ~7ull, 1u << 20));
-    if (kn.plan_debug)
-        fprintf(stderr, "[aim plan] seed_chain_long_kernel grid=%u block=64 lds=%zu per_cu=%u reads=%u max_hits=%u tile=%u\n", grid, lds, per_cu, n_reads,
-                max_hits, aim::kSeedLongTile);
-    aim::seed_chain_long_launch(la, grid, lds, (hipStream_t)hip_stream);
-    HIP_TRY(hipGetLastError());
-    return AIM_OK;
+    char plan_tail[48];
+    snprintf(plan_tail, sizeof plan_tail, " max_hits=%u tile=%u", max_hits, aim::kSeedLongTile);
+    return seed_submit(fn, "seed_chain_long_kernel", plan_tail, la.c.s, lds, sp, n_reads, d_read_len, d_reads, d_bucket, d_pos, ref_len, d_requests,
+                       d_text_pos, d_votes, d_seed, [&](uint32_t grid) { aim::seed_chain_long_launch(la, grid, lds, (hipStream_t)hip_stream); });
 }
 
 // ---------------------------------------------------------------------------

@@ -7,6 +7,17 @@
 //     shares seed_append (lookup and append) and seed_finish (sort, cluster, rank, fill) with the kernel above and is described where
 //     it stands: one more LDS array, 4 B per read position, for the strand's order keys.
 //
+// SHARED STEPS. This header owns the one copy of every step the five seed kernels have in common (these two, seed_chain.hpp's two and
+// seed_chain_long.hpp's one), under AIM_SEED_DEVICE_CODE, which tu_seed.hip, tu_seed_chain.hip and tu_seed_chain_long.hip define:
+// seed_stage (the row into LDS), seed_code (a strand's k-mer code), seed_minimizer_selected (the local (w, k) selection), seed_run (the
+// index lookup with its bounds checks, the only reader of bucket[]), seed_sort (the bitonic network, on 32- or 64-bit keys) and the wave
+// scans. An append is seed_run, a prefix sum and a store loop around the kernel's own key: seed_append here, seed_chain_append and
+// seed_long_append in the chaining headers. Two kernels keep seed_code's rule in place, everything else calls the steps:
+// seed_candidates_kernel codes both strands of a seed in one fused loop (with two seed_code calls its code object leaves the recorded
+// register counts, 98 SGPRs become 97), and seed_minimizer_kernel keeps its loop inline (through the function the compiler lays the
+// select loop's blocks out differently and the kernel measured 2 % slower; profiles/seed_shared/README.md).
+// AIM_TU_SEED only says which unit defines the __global__ kernels and launchers below.
+//
 // The rule is stated in full in aim_hip.h; the phases below follow its numbering.
 //   stage    the read row, once, into LDS (dwords).
 //   hits     lanes take seeds, 64 per step. The strand-0 code is read forward from the row and the strand-1 code backward from the same
@@ -21,7 +32,9 @@
 // LDS BANKS. ds_read_b32 / ds_write_b32 bank on (address / 4) % 32 within each 32-lane half. A compare-exchange stage at distance
 // j >= 32 touches consecutive dwords per half: conflict-free. At j < 32 the 32 lower partners of a half all have bit log2(j) clear and
 // would fall two to a bank; there the upper 16 lanes of each half read their UPPER partner first (address | j), so a half covers 32
-// distinct residues in each of its two reads and writes. The cluster and rank passes read consecutive entries.
+// distinct residues in each of its two reads and writes. The cluster and rank passes read consecutive entries. The chaining kernels sort
+// 64-bit entries with the same network: ds_read_b64 / ds_write_b64 bank on the entry index modulo 32 within each 32-lane half, so the
+// reasoning holds entry for entry.
 //
 // OCCUPANCY. LDS per workgroup = 8 KB of keys + 4 KB of votes + the row: 12 432 B at read_size 128, ten 1 280-B granules, so 12
 // wavefronts per CU = 3 per SIMD, LDS-bound. The register budget that keeps it so is 512 / 3 = 170; kSeedMaxVgpr = 128 leaves room for
@@ -60,7 +73,7 @@ constexpr size_t seed_lds_bytes(int32_t read_size) { return kSeedKeyBytes + kSee
 // seed_minimizer_kernel's: one more dword per read position, the strand's order keys
 constexpr size_t seed_minimizer_lds_bytes(int32_t read_size) { return seed_lds_bytes(read_size) + 4u * (size_t)read_size; }
 
-#if defined(AIM_TU_SEED) || defined(AIM_TU_SEED_CHAIN) || defined(AIM_TU_SEED_CHAIN_LONG)   // device code: tu_seed.hip, and tu_seed_chain.hip / tu_seed_chain_long.hip for what their headers share
+#ifdef AIM_SEED_DEVICE_CODE   // device code: the three tu_seed*.hip define it. The steps below are the only copy of each, for all five seed kernels
 
 __device__ __forceinline__ uint32_t seed_scan_add(uint32_t v, int lane)   // inclusive wave prefix sum
 {
@@ -88,8 +101,9 @@ __device__ __forceinline__ bool seed_is_base(uint32_t c)   // upper-case A C G T
     return d < 20u && ((0x80045u >> d) & 1u);
 }
 
-// Ascending bitonic sort of key[0, N), N a power of two >= 64, by one wavefront (see LDS BANKS above).
-__device__ __forceinline__ void seed_sort(uint32_t *key, uint32_t N, int lane)
+// Ascending bitonic sort of key[0, N), N a power of two >= 64, by one wavefront; Key is uint32_t or uint64_t (see LDS BANKS above).
+template <typename Key>
+__device__ __forceinline__ void seed_sort(Key *key, uint32_t N, int lane)
 {
     for (uint32_t k2 = 2; k2 <= N; k2 <<= 1) {
         for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
@@ -98,8 +112,8 @@ __device__ __forceinline__ void seed_sort(uint32_t *key, uint32_t N, int lane)
                 const bool up = (i & k2) == 0;
                 const bool hi_first = j < 32u && (t & 16u);
                 const uint32_t a0 = hi_first ? (i | j) : i, a1 = a0 ^ j;
-                const uint32_t x = key[a0], y = key[a1];
-                const uint32_t lo_v = hi_first ? y : x, hi_v = hi_first ? x : y;
+                const Key x = key[a0], y = key[a1];
+                const Key lo_v = hi_first ? y : x, hi_v = hi_first ? x : y;
                 if ((lo_v > hi_v) == up) {
                     key[a0] = y;
                     key[a1] = x;
@@ -121,21 +135,73 @@ __device__ __forceinline__ uint64_t seed_min_u64(uint64_t v)   // wave-wide mini
     return v;
 }
 
-// Rules 2-3 for the 64 seeds of one step and one strand: the lane's seed (code `code` at query offset j; !ok: no seed) looks its run of
-// positions up, and a wave prefix sum of the run lengths gives every lane its append position behind the `count` hits found so far.
-// Returns the new count (wave-uniform; it stops meaning anything exact once it has passed kSeedHits).
-__device__ __forceinline__ uint32_t seed_append(const SeedArgs &a, uint32_t *ks, uint32_t count, uint32_t code, bool ok, int32_t j, int lane)
+// stage: the read row r, once, into LDS (dwords)
+__device__ __forceinline__ void seed_stage(const SeedArgs &a, uint32_t *row4, uint32_t r, int32_t L, int lane)
+{
+    const uint32_t *g = reinterpret_cast<const uint32_t *>(a.reads + (uint64_t)r * (uint64_t)a.sp.read_size);
+    for (int w = lane; w < (L + 3) >> 2; w += kWave) row4[w] = g[w];
+}
+
+// The code of strand s's k-mer at query offset j: read forward from the row (s = 0), or backward from the same bytes with the complement
+// folded in (s = 1). row[i] is the read's byte i: a kernel that holds only the bytes from a0 on passes its buffer moved back by a0.
+// *ok is cleared when the k-mer covers a byte other than upper-case A C G T.
+__device__ __forceinline__ uint32_t seed_code(const uint8_t *row, int32_t L, int32_t j, int32_t k, int s, bool *ok)
+{
+    const uint8_t *f = s ? row + (L - 1 - j) : row + j;
+    uint32_t code = 0;
+    for (int i = 0; i < k; ++i) {
+        const uint32_t x = s ? f[-i] : f[i];
+        *ok = *ok && seed_is_base(x);
+        code |= (((x >> 1) & 3u) ^ (s ? 2u : 0u)) << (2 * i);
+    }
+    return code;
+}
+
+// The local minimizer selection for position j of a strand's n order keys, hk[i] the key of position klo + i: L + R + 1 >= need =
+// min(w, n), at most `reach` = w - 1 reads per side, none of which leaves [max(j - reach, 0), min(j + reach, n - 1)]. !active: the lane
+// has no position. *mine_out receives j's key (kMinInvalid for !active).
+__device__ __forceinline__ bool seed_minimizer_selected(const uint32_t *hk, uint32_t klo, uint32_t j, bool active, uint32_t n, uint32_t reach, uint32_t need,
+                                                        uint32_t *mine_out)
+{
+    const uint32_t mine = active ? hk[j - klo] : kMinInvalid;
+    bool left = mine != kMinInvalid, right = left;                          // the run on that side still extends
+    uint32_t span = 1;                                                      // L + R + 1
+    for (uint32_t d = 1; d <= reach; ++d) {
+        if (!__ballot(left || right)) break;
+        left = left && j >= d && hk[j - d - klo] > mine;
+        right = right && j + d < n && hk[j + d - klo] >= mine;
+        span += (uint32_t)left + (uint32_t)right;
+    }
+    *mine_out = mine;
+    return mine != kMinInvalid && span >= need;
+}
+
+// The index lookup, and the only reader of bucket[]: the run pos[*b0, *b0 + n) of the lane's seed; n = 0 for no seed, an absent or
+// over-frequent code and index entries that point outside the arrays. `cap` is the strand's hit cap.
+__device__ __forceinline__ uint32_t seed_run(const SeedArgs &a, uint32_t cap, uint32_t code, bool ok, uint32_t *b0)
 {
     const uint32_t n_codes = 1u << (2 * a.sp.k), max_occ = (uint32_t)a.sp.max_occ;
     const uint64_t pos_cap = a.ref_len >= (uint64_t)a.sp.k ? a.ref_len - (uint64_t)a.sp.k + 1u : 0u;
-    uint32_t b0 = 0, n = 0;
+    uint32_t n = 0;
+    *b0 = 0;
     if (ok && code < n_codes) {
-        b0 = a.bucket[code];
+        *b0 = a.bucket[code];
         const uint32_t b1 = a.bucket[code + 1u];
-        n = b1 - b0;
-        if (b1 < b0 || n > max_occ || (uint64_t)b1 > pos_cap) n = 0;
-        n = min(n, kSeedHits + 1u);                  // past kSeedHits only "overflowed" matters: the sums below stay far from 2^32
+        n = b1 - *b0;
+        if (b1 < *b0 || n > max_occ || (uint64_t)b1 > pos_cap) n = 0;
+        n = min(n, cap + 1u);                        // past the cap only "overflowed" matters: the sums below stay far from 2^32
     }
+    return n;
+}
+
+// Rules 2-3 for the 64 seeds of one step and one strand: the lane's seed (code `code` at query offset j; !ok: no seed) looks its run of
+// positions up, and a wave prefix sum of the run lengths gives every lane its append position behind the `count` hits found so far.
+// Returns the new count (wave-uniform; it stops meaning anything exact once it has passed the cap). This is the append of the voting
+// kernels, whose key is the hit's diagonal p - j + read_size; seed_chain_append (seed_chain.hpp) is the same around another key.
+__device__ __forceinline__ uint32_t seed_append(const SeedArgs &a, uint32_t *ks, uint32_t count, uint32_t code, bool ok, int32_t j, int lane)
+{
+    uint32_t b0;
+    const uint32_t n = seed_run(a, kSeedHits, code, ok, &b0);
     const uint32_t incl = seed_scan_add(n, lane);
     const uint32_t at = count + incl - n;
     const uint32_t bias = (uint32_t)a.sp.read_size - (uint32_t)j;
@@ -259,67 +325,6 @@ __device__ __forceinline__ void seed_finish(const SeedArgs &a, uint32_t *keys, u
 
 #endif
 
-#ifdef AIM_TU_SEED_CHAIN
-// The steps of the two kernels below as functions, for the kernels of seed_chain.hpp, which run them one strand at a time over (p, j)
-// anchors. The kernels below keep these steps inline, exactly as they were: their code objects do not change when seed_chain.hpp does.
-
-// stage: the read row r, once, into LDS (dwords)
-__device__ __forceinline__ void seed_stage(const SeedArgs &a, uint32_t *row4, uint32_t r, int32_t L, int lane)
-{
-    const uint32_t *g = reinterpret_cast<const uint32_t *>(a.reads + (uint64_t)r * (uint64_t)a.sp.read_size);
-    for (int w = lane; w < (L + 3) >> 2; w += kWave) row4[w] = g[w];
-}
-
-// The code of strand s's k-mer at query offset j: read forward from the row (s = 0), or backward from the same bytes with the complement
-// folded in (s = 1). *ok is cleared when it covers a byte other than upper-case A C G T.
-__device__ __forceinline__ uint32_t seed_code(const uint8_t *row, int32_t L, int32_t j, int32_t k, int s, bool *ok)
-{
-    const uint8_t *f = s ? row + (L - 1 - j) : row + j;
-    uint32_t code = 0;
-    for (int i = 0; i < k; ++i) {
-        const uint32_t x = s ? f[-i] : f[i];
-        *ok = *ok && seed_is_base(x);
-        code |= (((x >> 1) & 3u) ^ (s ? 2u : 0u)) << (2 * i);
-    }
-    return code;
-}
-
-// seed_minimizer_kernel's select for position j of the strand's order keys hk[0, n): L + R + 1 >= need = min(w, n), at most `reach`
-// reads per side. *mine_out receives hk[j] (kMinInvalid from n on).
-__device__ __forceinline__ bool seed_minimizer_selected(const uint32_t *hk, uint32_t j, uint32_t n, uint32_t reach, uint32_t need, uint32_t *mine_out)
-{
-    const uint32_t mine = j < n ? hk[j] : kMinInvalid;
-    bool left = mine != kMinInvalid, right = left;                          // the run on that side still extends
-    uint32_t span = 1;                                                      // L + R + 1
-    for (uint32_t d = 1; d <= reach; ++d) {
-        if (!__ballot(left || right)) break;
-        left = left && j >= d && hk[j - d] > mine;
-        right = right && j + d < n && hk[j + d] >= mine;
-        span += (uint32_t)left + (uint32_t)right;
-    }
-    *mine_out = mine;
-    return mine != kMinInvalid && span >= need;
-}
-
-// seed_append's lookup: the run pos[*b0, *b0 + n) of the lane's seed; n = 0 for no seed, an absent or over-frequent code and index
-// entries that point outside the arrays.
-__device__ __forceinline__ uint32_t seed_run(const SeedArgs &a, uint32_t code, bool ok, uint32_t *b0)
-{
-    const uint32_t n_codes = 1u << (2 * a.sp.k), max_occ = (uint32_t)a.sp.max_occ;
-    const uint64_t pos_cap = a.ref_len >= (uint64_t)a.sp.k ? a.ref_len - (uint64_t)a.sp.k + 1u : 0u;
-    uint32_t n = 0;
-    *b0 = 0;
-    if (ok && code < n_codes) {
-        *b0 = a.bucket[code];
-        const uint32_t b1 = a.bucket[code + 1u];
-        n = b1 - *b0;
-        if (b1 < *b0 || n > max_occ || (uint64_t)b1 > pos_cap) n = 0;
-        n = min(n, kSeedHits + 1u);                  // past kSeedHits only "overflowed" matters
-    }
-    return n;
-}
-#endif
-
 #ifdef AIM_TU_SEED   // the kernels live in tu_seed.hip alone; aim_capi.hip sees SeedArgs and the launchers
 
 __global__ __launch_bounds__(64) void seed_candidates_kernel(SeedArgs a)
@@ -338,10 +343,7 @@ __global__ __launch_bounds__(64) void seed_candidates_kernel(SeedArgs a)
         if (!xcd_unit(a.n_reads, it, &r)) break;
         const int32_t L = min(max(a.read_len[r], 0), rs);
         asm volatile("" ::: "memory");   // the previous read's LDS reads are issued before this row lands
-        {   // stage
-            const uint32_t *g = reinterpret_cast<const uint32_t *>(a.reads + (uint64_t)r * (uint64_t)rs);
-            for (int w = lane; w < (L + 3) >> 2; w += kWave) row4[w] = g[w];
-        }
+        seed_stage(a, row4, r, L, lane);
         asm volatile("" ::: "memory");
 
         // hits (rules 1-3)
@@ -352,7 +354,7 @@ __global__ __launch_bounds__(64) void seed_candidates_kernel(SeedArgs a)
             const uint32_t m = base + (uint32_t)lane;
             const bool active = m < n_seeds;
             const int32_t j = active ? (int32_t)m * stride : 0;
-            uint32_t c0 = 0, c1 = 0;
+            uint32_t c0 = 0, c1 = 0;           // seed_code's rule for both strands at once (see SHARED STEPS)
             bool ok0 = active, ok1 = active;
             if (active) {
                 const uint8_t *f = row + j, *b = row + (L - 1 - j);
@@ -401,10 +403,7 @@ __global__ __launch_bounds__(64) void seed_minimizer_kernel(SeedArgs a)
         if (!xcd_unit(a.n_reads, it, &r)) break;
         const int32_t L = min(max(a.read_len[r], 0), rs);
         asm volatile("" ::: "memory");   // the previous read's LDS reads are issued before this row lands
-        {   // stage
-            const uint32_t *g = reinterpret_cast<const uint32_t *>(a.reads + (uint64_t)r * (uint64_t)rs);
-            for (int w = lane; w < (L + 3) >> 2; w += kWave) row4[w] = g[w];
-        }
+        seed_stage(a, row4, r, L, lane);
         asm volatile("" ::: "memory");
 
         const uint32_t n = L >= k ? (uint32_t)(L - k) + 1u : 0u;
@@ -413,7 +412,7 @@ __global__ __launch_bounds__(64) void seed_minimizer_kernel(SeedArgs a)
 #pragma unroll 1
         for (int s = 0; s < 2; ++s) {
             for (uint32_t j = (uint32_t)lane; j < n; j += kWave) {   // keys
-                const uint8_t *f = s ? row + (L - 1 - (int32_t)j) : row + j;
+                const uint8_t *f = s ? row + (L - 1 - (int32_t)j) : row + j;   // seed_code's rule, in place (see SHARED STEPS)
                 uint32_t code = 0;
                 bool ok = true;
                 for (int i = 0; i < k; ++i) {
@@ -426,16 +425,8 @@ __global__ __launch_bounds__(64) void seed_minimizer_kernel(SeedArgs a)
             asm volatile("" ::: "memory");
             for (uint32_t base = 0; base < n && count[s] <= kSeedHits; base += kWave) {   // select, hits (rules 2-3)
                 const uint32_t j = base + (uint32_t)lane;
-                const uint32_t mine = j < n ? hk[j] : kMinInvalid;
-                bool left = mine != kMinInvalid, right = left;                          // the run on that side still extends
-                uint32_t span = 1;                                                      // L + R + 1
-                for (uint32_t d = 1; d <= reach; ++d) {
-                    if (!__ballot(left || right)) break;
-                    left = left && j >= d && hk[j - d] > mine;
-                    right = right && j + d < n && hk[j + d] >= mine;
-                    span += (uint32_t)left + (uint32_t)right;
-                }
-                const bool selected = mine != kMinInvalid && span >= need;
+                uint32_t mine;
+                const bool selected = seed_minimizer_selected(hk, 0u, j, j < n, n, reach, need, &mine);
                 count[s] = seed_append(a, keys + s * kSeedHits, count[s], min_unhash(mine), selected, (int32_t)j, lane);
             }
             asm volatile("" ::: "memory");   // the next strand's keys land after this strand's reads of hk

@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 READ_SIZE = 128
 # (k, stride, w, max_occ, band, flank, min_votes, K): the rows of tests/test_seed_chain_gpu.py at read_size 128
 ROWS = [(11, 1, None, 8, 8, 8, 2, 4), (8, 1, None, 64, 48, 16, 3, 16), (14, 3, None, 1, 16, 8, 1, 8), (11, 4, None, 2, 0, 0, 1, 1),
-        (11, 1, 5, 8, 32, 8, 2, 4), (13, 1, 10, 8, 32, 8, 2, 4)]
+        (11, 1, 5, 8, 32, 8, 2, 4), (13, 1, 10, 8, 32, 8, 2, 4), (8, 1, 2, 64, 48, 16, 3, 16)]
 
 
 def _lib():

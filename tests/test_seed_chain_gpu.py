@@ -19,7 +19,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 READ_SIZE = 128
 # (k, stride, w, max_occ, band, flank, min_votes, K); w = None: the full index at that stride
 FULL = [(11, 1, None, 8, 8, 8, 2, 4), (8, 1, None, 64, 48, 16, 3, 16), (14, 3, None, 1, 16, 8, 1, 8), (11, 4, None, 2, 0, 0, 1, 1)]
-MINIMIZER = [(11, 1, 5, 8, 32, 8, 2, 4), (13, 1, 10, 8, 32, 8, 2, 4)]
+MINIMIZER = [(11, 1, 5, 8, 32, 8, 2, 4), (13, 1, 10, 8, 32, 8, 2, 4),
+             (8, 1, 2, 64, 48, 16, 3, 16)]   # minimizer strands that overflow the 1 024 kept hits (the reads from inside the tandem repeat)
 LONG = (11, 1, 10, 8, 96, 16, 2, 4)          # the long reads' row, at read_size 1 024
 LONG_SIZE, LONG_L, LONG_DEL, LONG_EDITS = 1024, 800, 60, 80
 NAMES = ("requests", "text_pos", "votes", "seed", "chains")
