@@ -49,6 +49,10 @@ FEATURE_SEED_CHAIN = 0x4000     # aim_features(): aim_seed_chain_device / aim_ch
 SEED_CHAIN_LOOKBACK, SEED_CHAIN_MAX_BAND = 64, 4096
 FEATURE_SEED_CHAIN_LONG = 0x8000  # aim_features(): aim_seed_chain_long_device / aim_seed_chain_long_kernel_name exist
 SEED_LONG_MAX_READ_SIZE, SEED_LONG_MAX_HITS = 65528, 8192
+FEATURE_CHAIN_CLASS = 0x10000     # aim_features(): aim_chain_classify_device / aim_read_mapq_device / aim_chain_class_kernel_names exist
+CHAIN_MASK_DEFAULT = 128          # AIM_CHAIN_MASK_DEFAULT: mask_q8 of minimap2's mask level 0.5
+CHAIN_PRIMARY, CHAIN_SECONDARY, CHAIN_SUPPLEMENTARY = 0x1, 0x2, 0x4            # aim_chain_class_t.flags
+MAPQ_UNMAPPED, MAPQ_SECONDARY, MAPQ_SUPPLEMENTARY, MAPQ_PROPER = 0x1, 0x2, 0x4, 0x8   # aim_read_mapq_t.flags
 
 
 def SEED_OPT_MINIMIZERS(w):
@@ -137,6 +141,9 @@ SEED_DTYPE = np.dtype([("n_cands", "<u4"), ("n_hits", "<u4", (2,)), ("flags", "<
 assert SEED_DTYPE.itemsize == 16 and C.sizeof(SeedParams) == 40
 CHAIN_DTYPE = np.dtype([("score", "<u4"), ("n_anchors", "<u2"), ("reserved", "<u2"), ("q_lo", "<u2"), ("q_hi", "<u2"), ("ref_span", "<u4")])   # aim_chain_t
 assert CHAIN_DTYPE.itemsize == 16
+CHAIN_CLASS_DTYPE = np.dtype([("sub_score", "<u4"), ("parent", "u1"), ("flags", "u1"), ("mapq", "u1"), ("n_sub", "u1")])   # aim_chain_class_t
+READ_MAPQ_DTYPE = np.dtype([("slot", "<u4"), ("mapq", "u1"), ("chain_mapq", "u1"), ("aln_mapq", "u1"), ("flags", "u1")])   # aim_read_mapq_t
+assert CHAIN_CLASS_DTYPE.itemsize == 8 and READ_MAPQ_DTYPE.itemsize == 8
 
 
 class BatchIO(C.Structure):
@@ -234,6 +241,9 @@ SYMBOLS = {
     "aim_seed_chain_kernel_names": (C.c_char_p, []),
     "aim_seed_chain_long_device": (C.c_int, [C.POINTER(SeedParams), _U32, _U32, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "aim_seed_chain_long_kernel_name": (C.c_char_p, []),
+    "aim_chain_classify_device": (C.c_int, [_U32, _U32, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "aim_read_mapq_device": (C.c_int, [_U32, _U32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    "aim_chain_class_kernel_names": (C.c_char_p, []),
     "aim_seed_groups_offsets": (C.c_int, [_U32, _U32, _VP]),
     "aim_seed_kernel_name": (C.c_char_p, []),
     "aim_index_device_scratch": (C.c_int, [_I32, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -39,6 +39,7 @@
 #include "seed.hpp"
 #include "seed_chain.hpp"
 #include "seed_chain_long.hpp"
+#include "chain_class.hpp"
 #include "index.hpp"
 #include "genasm_wave.hpp"
 
@@ -164,6 +165,7 @@ aim::Knobs read_knobs()
     k.poison_ops = env_int("AIM_DEBUG_POISON_OPS", -1);
     k.poison_lds = env_int("AIM_DEBUG_POISON_LDS", -1);
     k.sam_wave_min = env_int("AIM_SAM_WAVE_MIN", -1);
+    k.class_g = env_int("AIM_CLASS_G", -1);
     k.plan_debug = getenv("AIM_PLAN_DEBUG") != nullptr;
     k.cus = (uint32_t)std::max(0, env_int("AIM_CHIP_CUS", 0));   // 0: ask the device (chip_cus)
     return k;
@@ -1675,7 +1677,7 @@ uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
            AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS | AIM_FEATURE_SEED |
-           AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS | AIM_FEATURE_SEED_CHAIN | AIM_FEATURE_SEED_CHAIN_LONG;
+           AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS | AIM_FEATURE_SEED_CHAIN | AIM_FEATURE_SEED_CHAIN_LONG | AIM_FEATURE_CHAIN_CLASS;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -3350,6 +3352,63 @@ int aim_seed_chain_long_device(const aim_seed_params_t *sp, uint32_t max_hits, u
     snprintf(plan_tail, sizeof plan_tail, " max_hits=%u tile=%u", max_hits, aim::kSeedLongTile);
     return seed_submit(fn, "seed_chain_long_kernel", plan_tail, la.c.s, lds, sp, n_reads, d_read_len, d_reads, d_bucket, d_pos, ref_len, d_requests,
                        d_text_pos, d_votes, d_seed, [&](uint32_t grid) { aim::seed_chain_long_launch(la, grid, lds, (hipStream_t)hip_stream); });
+}
+
+// ---------------------------------------------------------------------------
+// primary / secondary chains and MAPQ (AIM_FEATURE_CHAIN_CLASS; rules 8c and 9c in aim_hip.h, the kernels in chain_class.hpp)
+// ---------------------------------------------------------------------------
+const char *aim_chain_class_kernel_names(void) { return "chain_class_kernel,read_mapq_kernel"; }
+
+int aim_chain_classify_device(uint32_t K, uint32_t read_size, uint32_t mask_q8, uint32_t n_reads, const int32_t *d_read_len, const uint64_t *d_text_pos,
+                              const aim_seed_t *d_seed, const aim_chain_t *d_chains, aim_chain_class_t *d_class, void *hip_stream)
+{
+    const char *fn = "aim_chain_classify_device";
+    if (K < 1 || K > AIM_SEED_MAX_CANDS) return fail(AIM_EINVAL, "%s: K %u is outside 1..%d", fn, K, AIM_SEED_MAX_CANDS);
+    if (mask_q8 < 1 || mask_q8 > 256) return fail(AIM_EINVAL, "%s: mask_q8 %u is outside 1..256", fn, mask_q8);
+    if (read_size == 0 || (read_size & 7u) || read_size > AIM_SEED_LONG_MAX_READ_SIZE)
+        return fail(AIM_EINVAL, "%s: read_size %u must be a positive multiple of 8, at most %d", fn, read_size, AIM_SEED_LONG_MAX_READ_SIZE);
+    if ((uint64_t)n_reads * K >= (1ull << 32)) return fail(AIM_EINVAL, "%s: n_reads %u * K %u does not fit 32 bits (split the batch)", fn, n_reads, K);
+    if (n_reads && (!d_read_len || !d_text_pos || !d_seed || !d_chains || !d_class)) return fail(AIM_EINVAL, "%s: null device buffer", fn);
+    int n = 0;
+    const int rc = aim_device_count(&n);
+    if (rc) return rc;
+    if (!n_reads) return AIM_OK;
+    const aim::Knobs kn = with_chip(read_knobs());
+    const aim::ChainClassArgs a = {K, read_size, mask_q8, n_reads, d_read_len, d_text_pos, d_seed, d_chains, d_class};
+    // lanes per read: the smallest group that holds K; AIM_CLASS_G widens it for A/B runs (the rows do not depend on it)
+    uint32_t lanes = aim::chain_class_lanes(K);
+    if ((kn.class_g == 8 || kn.class_g == 16) && (uint32_t)kn.class_g > lanes) lanes = (uint32_t)kn.class_g;
+    const uint32_t per_block = aim::kChainClassThreads / lanes;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(aim::resident_grid(kn, aim::kChainClassPerCu), ((uint64_t)n_reads + per_block - 1u) / per_block);
+    if (kn.plan_debug) fprintf(stderr, "[aim plan] chain_class_kernel grid=%u block=%d lanes=%u reads=%u K=%u mask_q8=%u\n", grid, aim::kChainClassThreads, lanes, n_reads, K, mask_q8);
+    aim::chain_class_launch(a, lanes, grid, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
+}
+
+int aim_read_mapq_device(uint32_t K, uint32_t n_reads, int32_t score_unit, const aim_best_t *d_best, const aim_mate_t *d_mates_or_null,
+                         const aim_chain_class_t *d_class, aim_read_mapq_t *d_mapq, void *hip_stream)
+{
+    const char *fn = "aim_read_mapq_device";
+    if (K < 1 || K > AIM_SEED_MAX_CANDS) return fail(AIM_EINVAL, "%s: K %u is outside 1..%d", fn, K, AIM_SEED_MAX_CANDS);
+    if ((uint64_t)n_reads * K >= (1ull << 32)) return fail(AIM_EINVAL, "%s: n_reads %u * K %u does not fit 32 bits (split the batch)", fn, n_reads, K);
+    if (score_unit < 1) return fail(AIM_EINVAL, "%s: score_unit %d must be >= 1", fn, score_unit);
+    if (d_mates_or_null && (n_reads & 1u)) return fail(AIM_EINVAL, "%s: n_reads %u is odd with d_mates (reads 2m and 2m + 1 are mates)", fn, n_reads);
+    if (n_reads && (!d_best || !d_class || !d_mapq)) return fail(AIM_EINVAL, "%s: null device buffer", fn);
+    int n = 0;
+    const int rc = aim_device_count(&n);
+    if (rc) return rc;
+    if (!n_reads) return AIM_OK;
+    const aim::Knobs kn = with_chip(read_knobs());
+    const aim::ReadMapqArgs a = {K, n_reads, score_unit, d_best, d_mates_or_null, d_class, d_mapq};
+    const uint32_t grid =
+        (uint32_t)std::min<uint64_t>(aim::resident_grid(kn, aim::kChainClassPerCu), ((uint64_t)n_reads + aim::kChainClassThreads - 1u) / aim::kChainClassThreads);
+    if (kn.plan_debug)
+        fprintf(stderr, "[aim plan] read_mapq_kernel grid=%u block=%d reads=%u K=%u score_unit=%d mates=%d\n", grid, aim::kChainClassThreads, n_reads, K, score_unit,
+                d_mates_or_null ? 1 : 0);
+    aim::read_mapq_launch(a, grid, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -121,6 +121,7 @@ struct Knobs {
     int poison_scratch = -1;      // AIM_DEBUG_POISON_SCRATCH  fill scratch with this byte at configure
     int poison_lds = -1;          // AIM_DEBUG_POISON_LDS      fill dynamic LDS with this byte at kernel entry
     int sam_wave_min = -1;        // AIM_SAM_WAVE_MIN    SAM records: READ_SIZE from which a row gets a whole wavefront (0 = always, large = never)
+    int class_g = -1;             // AIM_CLASS_G         chain_class_kernel: lanes per read, 8 or 16 where K would take fewer (A/B runs)
     bool plan_debug = false;      // AIM_PLAN_DEBUG=1    print the chosen plan to stderr
     // Not a knob but the one fact about the chip every plan needs: compute units of the device the plan is made for
     // (hipDeviceAttributeMultiprocessorCount, read once per device by chip_cus() in aim_capi.hip: 256 on a whole MI355X, 128 / 64 / 32

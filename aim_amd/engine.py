@@ -578,6 +578,37 @@ def seed_chain_long_candidates(sp, max_hits, index, ref_len, read_len, reads, de
     return seed_candidates(sp, index, ref_len, read_len, reads, device=device, chain=True, max_hits=int(max_hits))
 
 
+def chain_classify_device(K, read_size, mask_q8, n_reads, d_read_len, d_text_pos, d_seed, d_chains, d_class, stream=None):
+    """aim_chain_classify_device on device pointers (integers, e.g. torch's data_ptr(); None = NULL): rule 8c over the buffers of
+    seed_chain_device / seed_chain_long_device -> aim_chain_class_t per slot in d_class. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_chain_classify_device(int(K), int(read_size), int(mask_q8), int(n_reads), d_read_len, d_text_pos, d_seed, d_chains,
+                                                     d_class, stream))
+
+
+def read_mapq_device(K, n_reads, score_unit, d_best, d_mates, d_class, d_mapq, stream=None):
+    """aim_read_mapq_device on device pointers: rule 9c over the aim_best_t rows (and the aim_mate_t rows, or None) of
+    align_device_groups / align_device_mates and chain_classify_device's d_class -> aim_read_mapq_t per read in d_mapq."""
+    capi.check(capi.load().aim_read_mapq_device(int(K), int(n_reads), int(score_unit), d_best, d_mates, d_class, d_mapq, stream))
+
+
+def chain_classify(sp, cands, mask_q8=capi.CHAIN_MASK_DEFAULT):
+    """Classifies the candidates of seed_chain_candidates / seed_chain_long_candidates where they live: takes the aim_seed_params_t of
+    that call and the dict it returned, and adds numpy "class" (CHAIN_CLASS_DTYPE, one per slot) and the uint8 device tensor "d_class",
+    which read_mapq_device takes after the alignment. Returns the dict."""
+    import torch
+    if "d_chains" not in cands:
+        raise ValueError("chain_classify takes the dict of seed_chain_candidates or seed_chain_long_candidates: d_chains is missing")
+    dev = cands["d_chains"].device
+    n, K = len(cands["seed"]), sp.max_cands
+    cands["d_class"] = torch.zeros(max(n * K, 1) * 8, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        chain_classify_device(K, sp.read_size, mask_q8, n, cands["d_read_len"].data_ptr(), cands["d_text_pos"].data_ptr(), cands["d_seed"].data_ptr(),
+                              cands["d_chains"].data_ptr(), cands["d_class"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize(dev)
+    cands["class"] = cands["d_class"].cpu().numpy().view(capi.CHAIN_CLASS_DTYPE)[:n * K]
+    return cands
+
+
 def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0", chain=False, max_hits=None):
     """The seeding kernel on torch device buffers. `index` is build_index's (bucket, pos) -- numpy arrays, or uint8 torch tensors
     that already live on the device (as the "d_bucket" / "d_pos" of an earlier call); read_len is int32[n_reads], reads the ASCII

@@ -330,6 +330,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_MINIMIZERS 0x2000u /* (w, k) minimizers: aim_index_build_minimizers / aim_index_build_device_minimizers / AIM_SEED_OPT_MINIMIZERS exist */
 #define AIM_FEATURE_SEED_CHAIN 0x4000u /* colinear chaining of the seed hits: aim_seed_chain_device / aim_chain_t / aim_seed_chain_kernel_names exist */
 #define AIM_FEATURE_SEED_CHAIN_LONG 0x8000u /* chaining for long reads: aim_seed_chain_long_device / aim_seed_chain_long_kernel_name exist */
+#define AIM_FEATURE_CHAIN_CLASS 0x10000u /* primary / secondary chains and MAPQ: aim_chain_classify_device / aim_read_mapq_device / aim_chain_class_kernel_names exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -673,9 +674,9 @@ const char *aim_sam_kernel_name(const aim_params_t *params);
  *     are untouched. The index must have been built with the same (k, w): nothing in the arrays records w, so the library cannot check
  *     that, and a mismatch only loses seeds.
  * Follow-ups, not in this version: packed read rows, spaced seeds, a seeding stage inside aim_set_submit, compacting the selected
- * positions before the device build's sort; for chaining (below) also overlap filtering between chains (primary / secondary), a
- * lookback other than 64, MAPQ, and beyond aim_seed_chain_long_device more than 8 192 anchors per strand and reads above 65 528
- * bases. Check aim_features() & AIM_FEATURE_SEED first. */
+ * positions before the device build's sort; for chaining (below) also a lookback other than 64, and beyond
+ * aim_seed_chain_long_device more than 8 192 anchors per strand and reads above 65 528 bases. Check
+ * aim_features() & AIM_FEATURE_SEED first. */
 #define AIM_SEED_MAX_CANDS 16
 #define AIM_SEED_MAX_HITS 1024      /* hits kept per (read, strand) */
 #define AIM_SEED_TRUNCATED 0x1u     /* aim_seed_t.flags: a strand dropped hits beyond AIM_SEED_MAX_HITS */
@@ -829,6 +830,85 @@ int aim_seed_chain_long_device(const aim_seed_params_t *sp, uint32_t max_hits, u
                                uint64_t *d_text_pos, uint32_t *d_votes, aim_seed_t *d_seed, aim_chain_t *d_chains_or_null, void *hip_stream);
 /* "seed_chain_long_kernel": the rocprofv3 kernel-trace name prefix of aim_seed_chain_long_device's kernel. */
 const char *aim_seed_chain_long_kernel_name(void);
+
+/* ---- primary and secondary chains, MAPQ (AIM_FEATURE_CHAIN_CLASS): what a read's K candidates are to each other ------------------
+ * After aim_seed_chain_device or aim_seed_chain_long_device the candidates of a read are a list ranked by score. Rule 8c says which of
+ * them cover the same part of the read at another locus (secondaries: repeat copies) and which cover a part no better chain covers
+ * (primaries; beyond candidate 0 supplementary: the other part of a split or chimeric read), and gives each primary a MAPQ from the
+ * chains alone. Rule 9c, after verification, turns that and aim_best_t / aim_mate_t into one MAPQ per read. All arithmetic is signed
+ * and in at least 32 bits unless 64 is stated; both results are deterministic and independent of the grid.
+ *   8c. Classification (aim_chain_classify_device). For read r: n = min(d_seed[r].n_cands, K), L = d_read_len[r] clamped to
+ *       0..read_size (the clamp of the chain kernels), and candidate i (0 <= i < n) is slot r * K + i, in the order the chain kernel
+ *       wrote it.
+ *       Read interval. With c = d_chains[slot] and s = d_text_pos[slot] >> 63: [a_i, b_i) = [c.q_lo, c.q_hi) for s = 0 and
+ *       [L - c.q_hi, L - c.q_lo) for s = 1 -- the interval of the read as given (see aim_chain_t above). len_i = b_i - a_i.
+ *       Overlap. ov(i, j) = min(b_i, b_j) - max(a_i, a_j). i and j overlap iff ov > 0 and 256 * ov >= mask_q8 * min(len_i, len_j);
+ *       equality counts as overlap. mask_q8 is 1..256; AIM_CHAIN_MASK_DEFAULT = 128 is minimap2's mask level of 0.5. A candidate
+ *       with len <= 0 (malformed input) overlaps nothing.
+ *       Parent. Candidate 0 is primary and parent(0) = 0. For i = 1 .. n - 1 in order, parent(i) is the lowest j < i that is primary
+ *       and overlaps i; if there is none, i is primary and parent(i) = i. A secondary is never a parent.
+ *       Flags. A primary gets AIM_CHAIN_PRIMARY, a primary with i > 0 also AIM_CHAIN_SUPPLEMENTARY, every other candidate
+ *       AIM_CHAIN_SECONDARY.
+ *       Sub-score. For a primary j, n_sub is the number of i != j with parent(i) = j and sub_score the greatest c.score among them
+ *       (0 if there are none). For a secondary both are 0.
+ *       Chain MAPQ of a primary. f1 = c.score, f2 = sub_score, m = min(c.n_anchors, 10): mapq = min(60, (6 * m * (f1 - f2)) / f1) in
+ *       64 bits, integer division; 0 when f1 = 0 or f2 > f1. A secondary has mapq 0. The formula is this project's own: minimap2's
+ *       (1 - f2 / f1) factor and its penalty for few anchors, without the log factor, so that the rule is exact in integers.
+ *       Empty slots (i >= n) are 8 zero bytes.
+ *       Parents only rank higher, so the classification of the kept candidates equals what classifying every chain of the read and
+ *       keeping the first K would give. sub_score and n_sub see the kept candidates only; they are exact when n_cands < K.
+ *   9c. MAPQ of a read (aim_read_mapq_device), after aim_align_device_groups or aim_align_device_mates over the chain kernel's slots
+ *       with read_offsets[r] = r * K (aim_seed_groups_offsets), so that best_pair is a slot.
+ *       Selection. sel = d_best[r].best_pair; with d_mates and m = r / 2, sel = d_mates[m].best_pair[r & 1].
+ *       Unmapped. sel == UINT32_MAX, sel - r * K >= K (unsigned) or d_class[sel].flags == 0 (an empty slot) gives
+ *       {slot = sel, mapq = chain_mapq = aln_mapq = 0, flags = AIM_MAPQ_UNMAPPED}. No entry of d_class outside the read's own K slots
+ *       is ever read.
+ *       Chain evidence. p = r * K + d_class[sel].parent and chain_mapq = d_class[p].mapq: the ambiguity of a locus is that of its
+ *       primary, also when verification preferred the secondary. (A parent >= K, which rule 8c never writes, gives chain_mapq 0.)
+ *       Alignment evidence (b, s2, nb) = d_best[r].(best_score, second_score, n_best); with d_mates and
+ *       d_mates[m].flags & AIM_MATE_PROPER it is d_mates[m].(score_sum, second_sum, n_best) instead. aln_mapq = 0 when nb > 1, 60 when
+ *       s2 == INT32_MAX, otherwise min(60, 6 * max(s2 - b, 0) / score_unit) in 64 bits. score_unit >= 1 is the caller's cost of one
+ *       mismatch; only the difference is used, so negative scores (SWG with a match bonus) are fine.
+ *       A WFA candidate over the cap counts with MAX_SCORE + 1 (AIM_FLAG_READ_GROUPS), a lower bound of its cost: aln_mapq reaches 60
+ *       only where MAX_SCORE + 1 >= b + 10 * score_unit.
+ *       Result. mapq = min(chain_mapq, aln_mapq). For a proper pair mapq = min(aln_mapq, max(chain_mapq, the mate's chain_mapq)): a
+ *       pair is as well anchored as its better mate; a mate that is unmapped by the rule above counts as 0.
+ *       Flags. AIM_MAPQ_UNMAPPED; AIM_MAPQ_SECONDARY: the chosen candidate is a secondary chain; AIM_MAPQ_SUPPLEMENTARY: it is a
+ *       primary of index > 0; AIM_MAPQ_PROPER.
+ * Both calls only enqueue work on hip_stream, allocate nothing and need no scratch; d_class and d_mapq are 8 bytes per row and must be
+ * 4-byte aligned. AIM_EINVAL with a message under the entry point's name, before any device query: K outside 1..AIM_SEED_MAX_CANDS,
+ * mask_q8 outside 1..256, a read_size that is 0, no multiple of 8 or above AIM_SEED_LONG_MAX_READ_SIZE, n_reads * K >= 2^32,
+ * score_unit < 1, an odd n_reads with d_mates and, last of all, a NULL device buffer.
+ * Not in this version: aligning the supplementary parts of a split read, MAPQ inside aim_sam_t (a caller joins d_mapq[r] with
+ * record r), AIM_FLAG_TOP_HITS rows, the clusters of aim_seed_device (they have no read interval) and a classification stage inside
+ * aim_set_submit. */
+#define AIM_CHAIN_MASK_DEFAULT 128
+#define AIM_CHAIN_PRIMARY 0x1u
+#define AIM_CHAIN_SECONDARY 0x2u
+#define AIM_CHAIN_SUPPLEMENTARY 0x4u
+typedef struct aim_chain_class {
+    uint32_t sub_score;
+    uint8_t parent;                /* 0..K-1, index within the read */
+    uint8_t flags;                 /* AIM_CHAIN_*; 0: an empty slot */
+    uint8_t mapq;
+    uint8_t n_sub;
+} aim_chain_class_t;   /* 8 B per slot */
+int aim_chain_classify_device(uint32_t K, uint32_t read_size, uint32_t mask_q8, uint32_t n_reads, const int32_t *d_read_len,
+                              const uint64_t *d_text_pos, const aim_seed_t *d_seed, const aim_chain_t *d_chains,
+                              aim_chain_class_t *d_class /* [n_reads * K] */, void *hip_stream);
+#define AIM_MAPQ_UNMAPPED 0x1u
+#define AIM_MAPQ_SECONDARY 0x2u
+#define AIM_MAPQ_SUPPLEMENTARY 0x4u
+#define AIM_MAPQ_PROPER 0x8u
+typedef struct aim_read_mapq {
+    uint32_t slot;                 /* the chosen candidate: best_pair as rule 9c selects it */
+    uint8_t mapq, chain_mapq, aln_mapq;
+    uint8_t flags;                 /* AIM_MAPQ_* */
+} aim_read_mapq_t;     /* 8 B per read */
+int aim_read_mapq_device(uint32_t K, uint32_t n_reads, int32_t score_unit, const aim_best_t *d_best, const aim_mate_t *d_mates_or_null,
+                         const aim_chain_class_t *d_class, aim_read_mapq_t *d_mapq /* [n_reads] */, void *hip_stream);
+/* "chain_class_kernel,read_mapq_kernel": comma-separated rocprofv3 kernel-trace name prefixes of the two entry points' kernels. */
+const char *aim_chain_class_kernel_names(void);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
