@@ -87,7 +87,8 @@ typedef struct aim_params {
  * h >= tlen - text_end_free) or (v >= plen - pattern_end_free, h = tlen); every other cost is WFA's.  Each free length is
  * clamped per pair to that pair's length.  The CIGAR still covers both whole sequences: free runs print as 'I' (a text
  * base) / 'D' (a pattern base).  A pair whose score exceeds max_score reports max_score + 1, status AIM_PAIR_OK and an
- * empty CIGAR (begin_offset == end_offset; n_runs == 0).  With all four lengths 0 the results are global WFA's.
+ * empty CIGAR (begin_offset == end_offset; n_runs == 0).  With all four lengths 0 the results are global WFA's (but for
+ * that empty CIGAR of a pair over max_score, where global WFA reports a range of one byte).
  * Check aim_features() & AIM_FEATURE_ENDSFREE first: older libraries ignore unknown flags. */
 #define AIM_FLAG_ENDSFREE 0x20u
 typedef struct aim_endsfree_params {
