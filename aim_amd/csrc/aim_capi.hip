@@ -338,6 +338,15 @@ int validate_params(const aim_params_t &p)
         if (std::max(p.mismatch, p.gap_o + p.gap_e) + 1 > aim::kBidirMaxScope)
             return fail(AIM_EINVAL, "AIM_FLAG_WFA_BIDIR needs max(x, o + e) < %d", aim::kBidirMaxScope);
     }
+    // The reference's recurrence starts a cell no present source covers at -10, not NULL (wfa.c:231-266), and every WFA kernel copies that.
+    // Where (10 + k) * x < o + k * e for some gap length k -- o + e > 11 x, or e > x -- such a cell is a real offset before the gap that
+    // leads there is paid for, and the score can lie below the minimum cost. Global WFA returns that score, as the reference does; the three
+    // flags whose contract is a minimum cost are refused, whatever READ_SIZE is (short rows only make the gaps that show it rare, not absent).
+    if (p.algo == AIM_ALGO_WFA && !is_linear(p) && (is_endsfree(p) || is_affine2p(p) || is_bidir(p)) &&
+        (p.gap_o + p.gap_e > 11 * p.mismatch || p.gap_e > p.mismatch))
+        return fail(AIM_EINVAL, "%s needs gap_o + gap_e <= 11 * mismatch and gap_e <= mismatch: beyond that the reference's -10 start value makes WFA's score "
+                    "fall below the minimum cost (got x = %d, o = %d, e = %d)",
+                    is_endsfree(p) ? "AIM_FLAG_ENDSFREE" : is_affine2p(p) ? "AIM_FLAG_AFFINE2P" : "AIM_FLAG_WFA_BIDIR", p.mismatch, p.gap_o, p.gap_e);
     if (p.read_size <= 0 || (p.read_size & 7)) return fail(AIM_EINVAL, "read_size must be a positive multiple of 8 (got %d)", p.read_size);
     if (p.max_score < 0) return fail(AIM_EINVAL, "max_score must be >= 0");
     if ((p.flags & AIM_FLAG_REQ8) && p.read_size >= 32760)

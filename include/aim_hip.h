@@ -80,6 +80,14 @@ typedef struct aim_params {
     uint32_t flags;    /* AIM_FLAG_*                                          */
 } aim_params_t;
 
+/* WFA scores and the reference's -10.  The reference's recurrence (the reference's dpu/wfa.c, affine_wfa_compute_offsets) starts a cell
+ * that no present source wavefront covers at -10, not at NULL, and every WFA kernel here copies that rule byte for byte.  On a
+ * penalty set with gap_o + gap_e > 11 * mismatch or gap_e > mismatch such a cell can become a real offset before the gap that
+ * leads to it is paid for ((10 + k) * mismatch < gap_o + k * gap_e for a gap of k bases), and global WFA then returns the
+ * reference's score, which can lie below the minimum cost and below the cost of the CIGAR printed next to it (the CIGAR stays a
+ * valid alignment of the two sequences).  On every other penalty set the score is the minimum cost.  AIM_FLAG_ENDSFREE,
+ * AIM_FLAG_AFFINE2P and AIM_FLAG_WFA_BIDIR promise a minimum cost and are refused (AIM_EINVAL) on those penalty sets, whatever
+ * read_size is (for AIM_FLAG_AFFINE2P the rule reads piece 1); AIM_FLAG_LINEAR has no such start value to inherit and is not. */
 /* AIM_FLAG_ENDSFREE (WFA only, not with AIM_FLAG_REDUCE): ends-free (semi-global) alignment.  The params are then the
  * `base` of an aim_endsfree_params_t and every entry point taking `const aim_params_t *` also reads its four free lengths
  * (it never reads past `base` without the flag).  Leading / trailing gaps inside the free lengths cost 0: the alignment
@@ -88,7 +96,8 @@ typedef struct aim_params {
  * clamped per pair to that pair's length.  The CIGAR still covers both whole sequences: free runs print as 'I' (a text
  * base) / 'D' (a pattern base).  A pair whose score exceeds max_score reports max_score + 1, status AIM_PAIR_OK and an
  * empty CIGAR (begin_offset == end_offset; n_runs == 0).  With all four lengths 0 the results are global WFA's (but for
- * that empty CIGAR of a pair over max_score, where global WFA reports a range of one byte).
+ * that empty CIGAR of a pair over max_score, where global WFA reports a range of one byte).  Needs gap_o + gap_e <= 11 * mismatch
+ * and gap_e <= mismatch (above).
  * Check aim_features() & AIM_FEATURE_ENDSFREE first: older libraries ignore unknown flags. */
 #define AIM_FLAG_ENDSFREE 0x20u
 typedef struct aim_endsfree_params {
@@ -103,7 +112,8 @@ typedef struct aim_endsfree_params {
  * The score is the minimum cost of a global alignment; MAX_SCORE, the over-cap result and the ops-row contract are global
  * WFA's.  A dual-affine cost never exceeds the piece-1 cost of the same alignment, so a max_score sized for piece 1 is
  * never too small.  With (gap_o2, gap_e2) == (gap_o, gap_e), or gap_o2 + gap_e2 > max_score, the results (CIGAR bytes
- * included) are global WFA's.  Check aim_features() & AIM_FEATURE_AFFINE2P first: older libraries ignore unknown flags. */
+ * included) are global WFA's.  Needs gap_o + gap_e <= 11 * mismatch and gap_e <= mismatch (above).
+ * Check aim_features() & AIM_FEATURE_AFFINE2P first: older libraries ignore unknown flags. */
 #define AIM_FLAG_AFFINE2P 0x40u
 typedef struct aim_affine2p_params {
     aim_params_t base;
@@ -132,7 +142,10 @@ typedef struct aim_affine2p_params {
  * equals the flag-less bytes for every pair whose score is <= T, the base-case threshold the plan line prints as "bidir=T"
  * (T >= 250). Results do not depend on the offset width, the grid, the slots or the batch size. Combines with
  * AIM_FLAG_WFA_W32, AIM_FLAG_REQ8, packed input, compact runs and every entry point; rejected (AIM_EINVAL) with NW / SWG / GenASM,
- * without AIM_FLAG_BACKTRACE, and with AIM_FLAG_REDUCE, AIM_FLAG_ENDSFREE, AIM_FLAG_AFFINE2P or AIM_FLAG_LINEAR (follow-ups).
+ * without AIM_FLAG_BACKTRACE, with AIM_FLAG_REDUCE, AIM_FLAG_ENDSFREE, AIM_FLAG_AFFINE2P or AIM_FLAG_LINEAR (follow-ups), and on a
+ * penalty set with gap_o + gap_e > 11 * mismatch or gap_e > mismatch (above: its second stage has no -10).  Caveat: the flag is
+ * accepted up to max(mismatch, gap_o + gap_e) = 61, but it is verified on a GPU only up to 5; the one run at 61 ((61,50,11),
+ * read_size 1024, max_score 610) ended in an illegal memory access whose cause is not found yet ("Penalty sets").
  * Check aim_features() & AIM_FEATURE_WFA_BIDIR first: older libraries ignore unknown flags. */
 #define AIM_FLAG_WFA_BIDIR 0x200u
 /* AIM_FLAG_REF_TEXTS (every algorithm, combines with every other flag): the texts of a batch are windows of a reference sequence
