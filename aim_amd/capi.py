@@ -50,9 +50,12 @@ SEED_CHAIN_LOOKBACK, SEED_CHAIN_MAX_BAND = 64, 4096
 FEATURE_SEED_CHAIN_LONG = 0x8000  # aim_features(): aim_seed_chain_long_device / aim_seed_chain_long_kernel_name exist
 SEED_LONG_MAX_READ_SIZE, SEED_LONG_MAX_HITS = 65528, 8192
 FEATURE_CHAIN_CLASS = 0x10000     # aim_features(): aim_chain_classify_device / aim_read_mapq_device / aim_chain_class_kernel_names exist
+FEATURE_SPLIT = 0x20000           # aim_features(): aim_split_segments_device / aim_sam_device_split / aim_split_kernel_names exist
 CHAIN_MASK_DEFAULT = 128          # AIM_CHAIN_MASK_DEFAULT: mask_q8 of minimap2's mask level 0.5
 CHAIN_PRIMARY, CHAIN_SECONDARY, CHAIN_SUPPLEMENTARY = 0x1, 0x2, 0x4            # aim_chain_class_t.flags
 MAPQ_UNMAPPED, MAPQ_SECONDARY, MAPQ_SUPPLEMENTARY, MAPQ_PROPER = 0x1, 0x2, 0x4, 0x8   # aim_read_mapq_t.flags
+SEG_VALID, SEG_SUPPLEMENTARY, SEG_LEFT_OPEN, SEG_RIGHT_OPEN, SEG_LOOSE = 0x1, 0x2, 0x4, 0x8, 0x10   # aim_segment_t.flags
+SAM_SUPPLEMENTARY = 0x800         # aim_sam_t.flags, from aim_sam_device_split
 
 
 def SEED_OPT_MINIMIZERS(w):
@@ -143,6 +146,7 @@ CHAIN_DTYPE = np.dtype([("score", "<u4"), ("n_anchors", "<u2"), ("reserved", "<u
 assert CHAIN_DTYPE.itemsize == 16
 CHAIN_CLASS_DTYPE = np.dtype([("sub_score", "<u4"), ("parent", "u1"), ("flags", "u1"), ("mapq", "u1"), ("n_sub", "u1")])   # aim_chain_class_t
 READ_MAPQ_DTYPE = np.dtype([("slot", "<u4"), ("mapq", "u1"), ("chain_mapq", "u1"), ("aln_mapq", "u1"), ("flags", "u1")])   # aim_read_mapq_t
+SEGMENT_DTYPE = np.dtype([("q_begin", "<u2"), ("q_end", "<u2"), ("read_len", "<u2"), ("flags", "u1"), ("cand", "u1")])   # aim_segment_t
 assert CHAIN_CLASS_DTYPE.itemsize == 8 and READ_MAPQ_DTYPE.itemsize == 8
 
 
@@ -244,6 +248,9 @@ SYMBOLS = {
     "aim_chain_classify_device": (C.c_int, [_U32, _U32, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "aim_read_mapq_device": (C.c_int, [_U32, _U32, _I32, _VP, _VP, _VP, _VP, _VP]),
     "aim_chain_class_kernel_names": (C.c_char_p, []),
+    "aim_split_segments_device": (C.c_int, [_U32, _U32, _I32, C.c_uint64, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "aim_sam_device_split": (C.c_int, [C.POINTER(Params), _U32, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _U32, _VP, _VP, _U32, _VP, _U32, _VP, _VP, _VP]),
+    "aim_split_kernel_names": (C.c_char_p, []),
     "aim_seed_groups_offsets": (C.c_int, [_U32, _U32, _VP]),
     "aim_seed_kernel_name": (C.c_char_p, []),
     "aim_index_device_scratch": (C.c_int, [_I32, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -40,6 +40,7 @@
 #include "seed_chain.hpp"
 #include "seed_chain_long.hpp"
 #include "chain_class.hpp"
+#include "split.hpp"
 #include "index.hpp"
 #include "genasm_wave.hpp"
 
@@ -1617,14 +1618,16 @@ inline bool sam_use_wave(const aim_params_t &p, const aim::Knobs &kn)
 }
 
 // The SAM kernel over n_rows final rows (sam_fields.hpp), the cursors zeroed first. The caller has run check_sam_rows.
-int enqueue_sam(const aim_params_t &p, const aim::Knobs &kn, aim::SamArgs a, hipStream_t stream)
+// With seg the split instantiation of the same kernel (aim_sam_device_split), the segments indexed like text_pos.
+int enqueue_sam(const aim_params_t &p, const aim::Knobs &kn, aim::SamArgs a, hipStream_t stream, const aim_segment_t *seg = nullptr)
 {
     if (!a.n_rows) return AIM_OK;
     a.algo = p.algo;
     a.max_score = p.max_score;
     a.read_size = p.read_size;
     HIP_TRY(hipMemsetAsync(a.cursors, 0, 8, stream));
-    aim::sam_fields_launch(sam_use_wave(p, kn), a, stream);
+    if (seg) aim::sam_fields_split_launch(sam_use_wave(p, kn), a, seg, stream);
+    else aim::sam_fields_launch(sam_use_wave(p, kn), a, stream);
     HIP_TRY(hipGetLastError());
     return AIM_OK;
 }
@@ -1686,7 +1689,7 @@ uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
            AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS | AIM_FEATURE_SEED |
-           AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS | AIM_FEATURE_SEED_CHAIN | AIM_FEATURE_SEED_CHAIN_LONG | AIM_FEATURE_CHAIN_CLASS;
+           AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS | AIM_FEATURE_SEED_CHAIN | AIM_FEATURE_SEED_CHAIN_LONG | AIM_FEATURE_CHAIN_CLASS | AIM_FEATURE_SPLIT;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -2816,22 +2819,23 @@ int aim_align_device(const aim_params_t *params, uint32_t n_pairs, const void *d
                   (hipStream_t)hip_stream);
 }
 
-int aim_sam_device(const aim_params_t *params, uint32_t n_rows, const void *d_requests, const uint64_t *d_text_pos,
-                   const uint32_t *d_sel_or_null, const void *d_results, const char *d_ops, const char *d_reference, uint64_t ref_len,
-                   uint32_t options, aim_sam_t *d_sam, uint32_t *d_cigar, uint32_t cigar_cap, char *d_md, uint32_t md_cap,
-                   uint32_t *d_cursors, void *hip_stream)
+// aim_sam_device (split = false) and aim_sam_device_split under the name fn: the same checks in the same order, then one launch.
+static int sam_device_entry(const char *fn, bool split, const aim_params_t *params, uint32_t n_rows, const void *d_requests, const uint64_t *d_text_pos,
+                            const uint32_t *d_sel_or_null, const void *d_results, const char *d_ops, const char *d_reference, uint64_t ref_len,
+                            uint32_t options, aim_sam_t *d_sam, uint32_t *d_cigar, uint32_t cigar_cap, char *d_md, uint32_t md_cap,
+                            uint32_t *d_cursors, const aim_segment_t *d_seg, void *hip_stream)
 {
     if (!params) return fail(AIM_EINVAL, "params is NULL");
     if (params->algo == AIM_ALGO_GENASM)
-        return fail(AIM_EINVAL, "aim_sam_device cannot take AIM_ALGO_GENASM rows (its windowed walk is unpinned and begin_offset = 0 is another contract)");
-    if (!(params->flags & AIM_FLAG_BACKTRACE)) return fail(AIM_EINVAL, "aim_sam_device needs AIM_FLAG_BACKTRACE (the records come from the ops rows)");
-    if (params->flags & AIM_FLAG_RES8) return fail(AIM_EINVAL, "aim_sam_device cannot be combined with AIM_FLAG_RES8");
+        return fail(AIM_EINVAL, "%s cannot take AIM_ALGO_GENASM rows (its windowed walk is unpinned and begin_offset = 0 is another contract)", fn);
+    if (!(params->flags & AIM_FLAG_BACKTRACE)) return fail(AIM_EINVAL, "%s needs AIM_FLAG_BACKTRACE (the records come from the ops rows)", fn);
+    if (params->flags & AIM_FLAG_RES8) return fail(AIM_EINVAL, "%s cannot be combined with AIM_FLAG_RES8", fn);
     if (params->read_size <= 0 || (params->read_size & 7)) return fail(AIM_EINVAL, "read_size must be a positive multiple of 8 (got %d)", params->read_size);
-    if (options & ~AIM_SAM_EQX) return fail(AIM_EINVAL, "aim_sam_device: unknown options 0x%x", options);
+    if (options & ~AIM_SAM_EQX) return fail(AIM_EINVAL, "%s: unknown options 0x%x", fn, options);
     int rc = check_sam_rows(*params, n_rows);
     if (rc) return rc;
     if (!d_cursors) return fail(AIM_EINVAL, "null device buffer");
-    if (n_rows && (!d_requests || !d_text_pos || !d_results || !d_ops || !d_reference || !d_sam || !d_cigar || !d_md))
+    if (n_rows && (!d_requests || !d_text_pos || !d_results || !d_ops || !d_reference || !d_sam || !d_cigar || !d_md || (split && !d_seg)))
         return fail(AIM_EINVAL, "null device buffer");
     int n = 0;
     rc = aim_device_count(&n);
@@ -2856,7 +2860,25 @@ int aim_sam_device(const aim_params_t *params, uint32_t n_rows, const void *d_re
         HIP_TRY(hipMemsetAsync(d_cursors, 0, 8, (hipStream_t)hip_stream));
         return AIM_OK;
     }
-    return enqueue_sam(*params, read_knobs(), a, (hipStream_t)hip_stream);
+    return enqueue_sam(*params, read_knobs(), a, (hipStream_t)hip_stream, split ? d_seg : nullptr);
+}
+
+int aim_sam_device(const aim_params_t *params, uint32_t n_rows, const void *d_requests, const uint64_t *d_text_pos,
+                   const uint32_t *d_sel_or_null, const void *d_results, const char *d_ops, const char *d_reference, uint64_t ref_len,
+                   uint32_t options, aim_sam_t *d_sam, uint32_t *d_cigar, uint32_t cigar_cap, char *d_md, uint32_t md_cap,
+                   uint32_t *d_cursors, void *hip_stream)
+{
+    return sam_device_entry("aim_sam_device", false, params, n_rows, d_requests, d_text_pos, d_sel_or_null, d_results, d_ops, d_reference, ref_len, options, d_sam,
+                            d_cigar, cigar_cap, d_md, md_cap, d_cursors, nullptr, hip_stream);
+}
+
+int aim_sam_device_split(const aim_params_t *params, uint32_t n_rows, const void *d_requests, const uint64_t *d_text_pos,
+                         const uint32_t *d_sel_or_null, const void *d_results, const char *d_ops, const char *d_reference, uint64_t ref_len,
+                         uint32_t options, aim_sam_t *d_sam, uint32_t *d_cigar, uint32_t cigar_cap, char *d_md, uint32_t md_cap,
+                         uint32_t *d_cursors, const aim_segment_t *d_seg, void *hip_stream)
+{
+    return sam_device_entry("aim_sam_device_split", true, params, n_rows, d_requests, d_text_pos, d_sel_or_null, d_results, d_ops, d_reference, ref_len, options,
+                            d_sam, d_cigar, cigar_cap, d_md, md_cap, d_cursors, d_seg, hip_stream);
 }
 
 const char *aim_sam_kernel_name(const aim_params_t *params)
@@ -3416,6 +3438,51 @@ int aim_read_mapq_device(uint32_t K, uint32_t n_reads, int32_t score_unit, const
         fprintf(stderr, "[aim plan] read_mapq_kernel grid=%u block=%d reads=%u K=%u score_unit=%d mates=%d\n", grid, aim::kChainClassThreads, n_reads, K, score_unit,
                 d_mates_or_null ? 1 : 0);
     aim::read_mapq_launch(a, grid, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// split reads (AIM_FEATURE_SPLIT; rule 10c in aim_hip.h, the kernel in split.hpp; aim_sam_device_split stands next to aim_sam_device)
+// ---------------------------------------------------------------------------
+const char *aim_split_kernel_names(void) { return "split_segments_kernel,sam_lane_split_kernel,sam_wave_split_kernel"; }
+
+int aim_split_segments_device(uint32_t K, uint32_t read_size, int32_t flank, uint64_t ref_len, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads,
+                              const void *d_requests, const uint64_t *d_text_pos, const aim_seed_t *d_seed, const aim_chain_t *d_chains,
+                              const aim_chain_class_t *d_class, void *d_seg_requests, uint64_t *d_seg_text_pos, char *d_seg_patterns, aim_segment_t *d_seg,
+                              void *hip_stream)
+{
+    const char *fn = "aim_split_segments_device";
+    if (K < 1 || K > AIM_SEED_MAX_CANDS) return fail(AIM_EINVAL, "%s: K %u is outside 1..%d", fn, K, AIM_SEED_MAX_CANDS);
+    if (read_size == 0 || (read_size & 7u) || read_size > AIM_SEED_LONG_MAX_READ_SIZE)
+        return fail(AIM_EINVAL, "%s: read_size %u must be a positive multiple of 8, at most %d", fn, read_size, AIM_SEED_LONG_MAX_READ_SIZE);
+    if ((uint64_t)n_reads * K >= (1ull << 32)) return fail(AIM_EINVAL, "%s: n_reads %u * K %u does not fit 32 bits (split the batch)", fn, n_reads, K);
+    if (flank < 0) return fail(AIM_EINVAL, "%s: flank %d must be >= 0", fn, flank);
+    if (ref_len > AIM_SEED_MAX_REF_LEN) return fail(AIM_EINVAL, "%s: ref_len %llu is above %llu", fn, (unsigned long long)ref_len, (unsigned long long)AIM_SEED_MAX_REF_LEN);
+    if (n_reads && (!d_read_len || !d_reads || !d_requests || !d_text_pos || !d_seed || !d_chains || !d_class || !d_seg_requests || !d_seg_text_pos ||
+                    !d_seg_patterns || !d_seg))
+        return fail(AIM_EINVAL, "%s: null device buffer", fn);
+    int n = 0;
+    const int rc = aim_device_count(&n);
+    if (rc) return rc;
+    if (!n_reads) return AIM_OK;
+    const aim::Knobs kn = with_chip(read_knobs());
+    aim::SplitArgs a;
+    memset(&a, 0, sizeof a);
+    a.K = K; a.read_size = read_size; a.n_reads = n_reads; a.parts_log2 = aim::split_parts_log2(K, read_size);
+    a.flank = flank; a.ref_len = (int64_t)ref_len;
+    a.read_len = d_read_len; a.reads = d_reads; a.requests = static_cast<const aim_request_t *>(d_requests); a.text_pos = d_text_pos;
+    a.seed = d_seed; a.chains = d_chains; a.cls = d_class;
+    a.seg_requests = static_cast<aim_request_t *>(d_seg_requests); a.seg_text_pos = d_seg_text_pos; a.seg_patterns = d_seg_patterns; a.seg = d_seg;
+    // lanes per read and shares per read come from K and read_size alone; only the grid is the device's
+    const uint32_t lanes = aim::split_lanes(read_size);
+    const uint32_t per_block = aim::kSplitThreads / lanes;
+    const uint64_t items = (uint64_t)n_reads << a.parts_log2;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(aim::resident_grid(kn, aim::kSplitPerCu), (items + per_block - 1u) / per_block);
+    if (kn.plan_debug)
+        fprintf(stderr, "[aim plan] split_segments_kernel grid=%u block=%d lanes=%u parts=%u reads=%u K=%u read_size=%u\n", grid, aim::kSplitThreads, lanes,
+                1u << a.parts_log2, n_reads, K, read_size);
+    aim::split_segments_launch(a, lanes, grid, (hipStream_t)hip_stream);
     HIP_TRY(hipGetLastError());
     return AIM_OK;
 }

@@ -18,6 +18,10 @@
 //                    reference positions, MD match counts and output offsets come from wave scans with uniform carries between
 //                    tiles, and every lane reads the reference bytes of its own mismatches / deleted bases.
 // No LDS (the scans are cross-lane shuffles), plain vector stores only.
+//
+// aim_sam_device_split (AIM_FEATURE_SPLIT) is a second instantiation of both mappings, sam_lane_split_kernel and sam_wave_split_kernel:
+// the bodies below take SPLIT as a compile-time constant, and with it a row also reads its aim_segment_t, adds the rest of the read to the two soft
+// clips before anything is counted, and carries 0x800 into the record. SPLIT = false compiles to the kernels as they were.
 #pragma once
 
 #include "aim_device.hpp"
@@ -100,7 +104,8 @@ struct SamCount {
     uint32_t n_cigar, md_len, nm, ref_span, lead_ref;
     bool mapped;
 };
-__device__ __forceinline__ void sam_store_record(const SamArgs &a, uint32_t row, const SamRow &s, const SamCount &c, uint32_t coff, uint32_t moff, bool fits)
+__device__ __forceinline__ void sam_store_record(const SamArgs &a, uint32_t row, const SamRow &s, const SamCount &c, uint32_t coff, uint32_t moff, bool fits,
+                                                 uint32_t more_flags = 0u)
 {
     aim_sam_t o;
     o.idx = s.r.idx;
@@ -112,10 +117,32 @@ __device__ __forceinline__ void sam_store_record(const SamArgs &a, uint32_t row,
     o.n_cigar = (c.mapped && fits) ? c.n_cigar : 0u;
     o.md_offset = moff;
     o.md_len = (c.mapped && fits) ? c.md_len : 0u;
-    o.flags = (uint16_t)(c.mapped ? (s.rev ? 0x10u : 0u) : 0x4u);
+    o.flags = (uint16_t)(c.mapped ? ((s.rev ? 0x10u : 0u) | more_flags) : 0x4u);
     o.status = (uint16_t)(((uint32_t)s.r.status & 0xffu) | ((c.mapped && !fits) ? 0x100u : 0u));
     o.pad = 0;
     a.sam[row] = o;
+}
+
+// SPLIT: what the row's segment adds. A segment without flags turns the row into one without a candidate.
+struct SamSplit {
+    uint32_t lead, trail;   // read bases in front of / behind the segment, in the record's orientation
+    uint32_t flags;         // AIM_SAM_SUPPLEMENTARY or 0
+};
+__device__ __forceinline__ SamSplit sam_split_row(const SamArgs &a, const aim_segment_t *seg, uint32_t row, bool active, SamRow *s)
+{
+    SamSplit x = {0u, 0u, 0u};
+    if (!active) return x;
+    const uint32_t c = a.sel ? a.sel[row] : row;
+    if (c == 0xffffffffu) return x;
+    const uint2 w = reinterpret_cast<const uint2 *>(seg)[c];      // {q_begin | q_end << 16, read_len | flags << 16 | cand << 24}
+    const uint32_t flags = (w.y >> 16) & 0xffu;
+    if (!flags) { s->ws = 0; s->rev = false; s->walk = false; return x; }
+    const uint32_t before = w.x & 0xffffu, q_end = w.x >> 16, len = w.y & 0xffffu;
+    const uint32_t behind = len > q_end ? len - q_end : 0u;
+    x.lead = s->rev ? behind : before;
+    x.trail = s->rev ? before : behind;
+    x.flags = (flags & AIM_SEG_SUPPLEMENTARY) ? AIM_SAM_SUPPLEMENTARY : 0u;
+    return x;
 }
 
 __device__ __forceinline__ uint32_t sam_wave_excl_sum(uint32_t v, int lane, uint32_t *total)
@@ -194,9 +221,12 @@ __device__ __forceinline__ void sam_lane_core(const SamArgs &a, const SamRow &s,
 }
 
 // one wavefront of 64 rows; all 64 lanes must call
-__device__ __forceinline__ void sam_lane_wave(const SamArgs &a, uint32_t row, bool active, int lane)
+template <bool SPLIT>
+__device__ __forceinline__ void sam_lane_wave(const SamArgs &a, const aim_segment_t *seg, uint32_t row, bool active, int lane)
 {
-    const SamRow s = sam_row(a, row, active);
+    SamRow s = sam_row(a, row, active);
+    SamSplit x = {0u, 0u, 0u};
+    if (SPLIT) x = sam_split_row(a, seg, row, active, &s);
     const uint32_t *rowp = reinterpret_cast<const uint32_t *>(a.ops + (uint64_t)row * 2u * (uint32_t)a.read_size);
     const int n = s.walk ? s.e - s.b : 0;
     auto op_at = [&](int k) -> uint32_t {
@@ -218,7 +248,7 @@ __device__ __forceinline__ void sam_lane_wave(const SamArgs &a, uint32_t row, bo
         trail_ref += cls == 2;
         --k1;
     }
-    const uint32_t lead_clip = (uint32_t)k0 - lead_ref, trail_clip = (uint32_t)(n - k1) - trail_ref;
+    const uint32_t lead_clip = (uint32_t)k0 - lead_ref + (SPLIT ? x.lead : 0u), trail_clip = (uint32_t)(n - k1) - trail_ref + (SPLIT ? x.trail : 0u);
     SamCount c;
     c.n_cigar = 0; c.md_len = 0; c.nm = 0; c.ref_span = 0; c.lead_ref = lead_ref;
     c.mapped = k1 > k0;
@@ -234,14 +264,21 @@ __device__ __forceinline__ void sam_lane_wave(const SamArgs &a, uint32_t row, bo
     const uint64_t off_c = (uint64_t)base_c + ex_c, off_m = (uint64_t)base_m + ex_m;
     const bool fits = off_c + c.n_cigar <= a.cigar_cap && off_m + c.md_len <= a.md_cap;
     if (c.mapped && fits) sam_lane_core<true>(a, s, rowp, k0, k1, lead_clip, trail_clip, lead_ref, &c, a.cigar + off_c, a.md + off_m);
-    if (active) sam_store_record(a, row, s, c, (uint32_t)off_c, (uint32_t)off_m, fits);
+    if (active) sam_store_record(a, row, s, c, (uint32_t)off_c, (uint32_t)off_m, fits, SPLIT ? x.flags : 0u);
 }
 
 __global__ __launch_bounds__(64) void sam_lane_kernel(SamArgs a)
 {
     const int lane = threadIdx.x;
     const uint32_t row = blockIdx.x * kWave + lane;
-    sam_lane_wave(a, row, row < a.n_rows, lane);
+    sam_lane_wave<false>(a, nullptr, row, row < a.n_rows, lane);
+}
+
+__global__ __launch_bounds__(64) void sam_lane_split_kernel(SamArgs a, const aim_segment_t *seg)
+{
+    const int lane = threadIdx.x;
+    const uint32_t row = blockIdx.x * kWave + lane;
+    sam_lane_wave<true>(a, seg, row, row < a.n_rows, lane);
 }
 
 // ---- one row per wavefront ----------------------------------------------------------------------------------------------------------
@@ -414,42 +451,54 @@ __device__ __forceinline__ void sam_wave_sweep(const SamArgs &a, const SamRow &s
     }
 }
 
-// blockDim.x = 256: four rows per workgroup, one per wavefront (no LDS, no barrier)
-__global__ __launch_bounds__(256) void sam_wave_kernel(SamArgs a)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t row = blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (row >= a.n_rows) return;                           // (wave-uniform)
-    const SamRow s = sam_row(a, row, true);
-    const uint32_t *rowp = reinterpret_cast<const uint32_t *>(a.ops + (uint64_t)row * 2u * (uint32_t)a.read_size);
-    const int n = s.walk ? s.e - s.b : 0;
-    // the first and the last M / X of the walk
-    int fmin = 0x7fffffff, lneg = 0x7fffffff;              // lneg = -(last position)
-    for (int t0 = 0; t0 < n; t0 += 4 * kWave) {
-        const int k = t0 + 4 * lane;
-        const uint32_t q = sam_walk4(rowp, s, n, k);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (k + j < n && sam_class((q >> (8 * j)) & 0xffu) < 2) { fmin = min(fmin, k + j); lneg = min(lneg, -(k + j)); }
-    }
-    SamWaveState st;
-    st.first = wave_min_i32(fmin);
-    const int ln = wave_min_i32(lneg);
-    st.last = -ln;
-    st.lead_clip = st.trail_clip = 0;
-    SamCount c;
-    c.n_cigar = 0; c.md_len = 0; c.nm = 0; c.ref_span = 0; c.lead_ref = 0;
-    c.mapped = st.first != 0x7fffffff;
-    if (c.mapped) sam_wave_sweep<false>(a, s, rowp, n, lane, st, &c, nullptr, nullptr);
-    uint32_t base_c = 0, base_m = 0;
-    if (lane == 0 && c.n_cigar) base_c = atomicAdd(&a.cursors[0], c.n_cigar);
-    if (lane == 0 && c.md_len) base_m = atomicAdd(&a.cursors[1], c.md_len);
-    base_c = (uint32_t)__builtin_amdgcn_readfirstlane((int)base_c);
-    base_m = (uint32_t)__builtin_amdgcn_readfirstlane((int)base_m);
-    const bool fits = (uint64_t)base_c + c.n_cigar <= a.cigar_cap && (uint64_t)base_m + c.md_len <= a.md_cap;
-    if (c.mapped && fits) sam_wave_sweep<true>(a, s, rowp, n, lane, st, &c, a.cigar + base_c, a.md + base_m);
-    if (lane == 0) sam_store_record(a, row, s, c, base_c, base_m, fits);
-}
+// blockDim.x = 256: four rows per workgroup, one per wavefront (no LDS, no barrier). The body is a macro, not a function template like
+// sam_lane_wave: expanded inside the kernel, SPLIT = false gives sam_wave_kernel instruction for instruction as it was before there was a
+// second instantiation; inlined from a function it came out with two scalar instructions in another place.
+// Should a later compiler give the same instructions for a function template (compare the disassembly of sam_wave_kernel before and
+// after), make this a template like sam_lane_wave again.
+#define AIM_SAM_WAVE_ROWS(SPLIT, seg)                                                                                              \
+    const int lane = threadIdx.x & (kWave - 1);                                                                                    \
+    const uint32_t row = blockIdx.x * 4u + (threadIdx.x >> 6);                                                                     \
+    if (row >= a.n_rows) return; /* (wave-uniform) */                                                                              \
+    SamRow s = sam_row(a, row, true);                                                                                              \
+    SamSplit x = {0u, 0u, 0u};                                                                                                     \
+    if (SPLIT) x = sam_split_row(a, seg, row, true, &s);                                                                           \
+    const uint32_t *rowp = reinterpret_cast<const uint32_t *>(a.ops + (uint64_t)row * 2u * (uint32_t)a.read_size);                 \
+    const int n = s.walk ? s.e - s.b : 0;                                                                                          \
+    /* the first and the last M / X of the walk */                                                                                 \
+    int fmin = 0x7fffffff, lneg = 0x7fffffff; /* lneg = -(last position) */                                                        \
+    for (int t0 = 0; t0 < n; t0 += 4 * kWave) {                                                                                    \
+        const int k = t0 + 4 * lane;                                                                                               \
+        const uint32_t q = sam_walk4(rowp, s, n, k);                                                                               \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                                              \
+            if (k + j < n && sam_class((q >> (8 * j)) & 0xffu) < 2) { fmin = min(fmin, k + j); lneg = min(lneg, -(k + j)); }       \
+    }                                                                                                                              \
+    SamWaveState st;                                                                                                               \
+    st.first = wave_min_i32(fmin);                                                                                                 \
+    const int ln = wave_min_i32(lneg);                                                                                             \
+    st.last = -ln;                                                                                                                 \
+    st.lead_clip = st.trail_clip = 0;                                                                                              \
+    SamCount c;                                                                                                                    \
+    c.n_cigar = 0; c.md_len = 0; c.nm = 0; c.ref_span = 0; c.lead_ref = 0;                                                         \
+    c.mapped = st.first != 0x7fffffff;                                                                                             \
+    if (c.mapped) sam_wave_sweep<false>(a, s, rowp, n, lane, st, &c, nullptr, nullptr);                                            \
+    if (SPLIT && c.mapped) { /* the rest of the read joins the clips the sweep counted */                                          \
+        c.n_cigar += (uint32_t)(!st.lead_clip && x.lead) + (uint32_t)(!st.trail_clip && x.trail);                                  \
+        st.lead_clip += x.lead;                                                                                                    \
+        st.trail_clip += x.trail;                                                                                                  \
+    }                                                                                                                              \
+    uint32_t base_c = 0, base_m = 0;                                                                                               \
+    if (lane == 0 && c.n_cigar) base_c = atomicAdd(&a.cursors[0], c.n_cigar);                                                      \
+    if (lane == 0 && c.md_len) base_m = atomicAdd(&a.cursors[1], c.md_len);                                                        \
+    base_c = (uint32_t)__builtin_amdgcn_readfirstlane((int)base_c);                                                                \
+    base_m = (uint32_t)__builtin_amdgcn_readfirstlane((int)base_m);                                                                \
+    const bool fits = (uint64_t)base_c + c.n_cigar <= a.cigar_cap && (uint64_t)base_m + c.md_len <= a.md_cap;                      \
+    if (c.mapped && fits) sam_wave_sweep<true>(a, s, rowp, n, lane, st, &c, a.cigar + base_c, a.md + base_m);                      \
+    if (lane == 0) sam_store_record(a, row, s, c, base_c, base_m, fits, SPLIT ? x.flags : 0u);
+
+__global__ __launch_bounds__(256) void sam_wave_kernel(SamArgs a) { AIM_SAM_WAVE_ROWS(false, nullptr) }
+__global__ __launch_bounds__(256) void sam_wave_split_kernel(SamArgs a, const aim_segment_t *seg) { AIM_SAM_WAVE_ROWS(true, seg) }
+#undef AIM_SAM_WAVE_ROWS
 
 void sam_fields_launch(bool wave, const SamArgs &a, hipStream_t s)
 {
@@ -457,8 +506,16 @@ void sam_fields_launch(bool wave, const SamArgs &a, hipStream_t s)
     if (wave) hipLaunchKernelGGL(sam_wave_kernel, dim3((a.n_rows + 3u) / 4u), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(sam_lane_kernel, dim3((a.n_rows + 63u) / 64u), dim3(64), 0, s, a);
 }
+
+void sam_fields_split_launch(bool wave, const SamArgs &a, const aim_segment_t *seg, hipStream_t s)
+{
+    if (!a.n_rows) return;
+    if (wave) hipLaunchKernelGGL(sam_wave_split_kernel, dim3((a.n_rows + 3u) / 4u), dim3(256), 0, s, a, seg);
+    else hipLaunchKernelGGL(sam_lane_split_kernel, dim3((a.n_rows + 63u) / 64u), dim3(64), 0, s, a, seg);
+}
 #else
 void sam_fields_launch(bool wave, const SamArgs &a, hipStream_t s);
+void sam_fields_split_launch(bool wave, const SamArgs &a, const aim_segment_t *seg, hipStream_t s);
 #endif
 
 }  // namespace aim

@@ -609,6 +609,51 @@ def chain_classify(sp, cands, mask_q8=capi.CHAIN_MASK_DEFAULT):
     return cands
 
 
+def split_segments_device(K, read_size, flank, ref_len, n_reads, d_read_len, d_reads, d_requests, d_text_pos, d_seed, d_chains, d_class, d_seg_requests,
+                          d_seg_text_pos, d_seg_patterns, d_seg, stream=None):
+    """aim_split_segments_device on device pointers (integers, e.g. torch's data_ptr(); None = NULL): rule 10c over the buffers of
+    seed_chain_device / seed_chain_long_device and chain_classify_device -> one segment row per slot (request, text_pos, pattern row of
+    read_size bytes, aim_segment_t). `flank` is the one the chains were built with. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_split_segments_device(int(K), int(read_size), int(flank), int(ref_len), int(n_reads), d_read_len, d_reads, d_requests,
+                                                     d_text_pos, d_seed, d_chains, d_class, d_seg_requests, d_seg_text_pos, d_seg_patterns, d_seg, stream))
+
+
+def sam_device_split(params, n_rows, d_requests, d_text_pos, d_sel, d_results, d_ops, d_reference, ref_len, options, d_sam, d_cigar, cigar_cap,
+                     d_md, md_cap, d_cursors, d_seg, stream=None):
+    """aim_sam_device_split on device pointers: sam_device over aligned segment rows, with d_seg (aim_segment_t, indexed like
+    d_text_pos) adding the rest of each read to the soft clips and SAM_SUPPLEMENTARY to the flags."""
+    capi.check(capi.load().aim_sam_device_split(params_ref(params), n_rows, d_requests, d_text_pos, d_sel, d_results, d_ops, d_reference, ref_len,
+                                                options, d_sam, d_cigar, cigar_cap, d_md, md_cap, d_cursors, d_seg, stream))
+
+
+def split_segments(sp, cands, ref_len):
+    """Splits the classified candidates of chain_classify where they live: takes the aim_seed_params_t of the chaining call, the dict
+    chain_classify returned and the length of the reference the chains were built on, and adds the uint8 device tensors "d_seg_req", "d_seg_text_pos", "d_seg_patterns"
+    and "d_seg" (one row per slot, for align_device_ref and sam_device_split) and their host copies "seg_req" (REQUEST_DTYPE),
+    "seg_text_pos" (uint64), "seg_patterns" (uint8[n * K][read_size]) and "seg" (SEGMENT_DTYPE). Returns the dict."""
+    import torch
+    if "d_class" not in cands or "d_chains" not in cands:
+        raise ValueError("split_segments takes the dict of chain_classify: d_class is missing")
+    dev = cands["d_class"].device
+    n, K, rs = len(cands["seed"]), sp.max_cands, sp.read_size
+    slots = max(n * K, 1)
+    cands["d_seg_req"] = torch.zeros(slots * 16, dtype=torch.uint8, device=dev)
+    cands["d_seg_text_pos"] = torch.zeros(slots * 8, dtype=torch.uint8, device=dev)
+    cands["d_seg_patterns"] = torch.zeros(slots * rs + 64, dtype=torch.uint8, device=dev)
+    cands["d_seg"] = torch.zeros(slots * 8, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        split_segments_device(K, rs, sp.flank, int(ref_len), n, cands["d_read_len"].data_ptr(), cands["d_reads"].data_ptr(), cands["d_req"].data_ptr(),
+                              cands["d_text_pos"].data_ptr(), cands["d_seed"].data_ptr(), cands["d_chains"].data_ptr(), cands["d_class"].data_ptr(),
+                              cands["d_seg_req"].data_ptr(), cands["d_seg_text_pos"].data_ptr(), cands["d_seg_patterns"].data_ptr(), cands["d_seg"].data_ptr(),
+                              torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize(dev)
+    cands["seg_req"] = cands["d_seg_req"].cpu().numpy().view(capi.REQUEST_DTYPE)[:n * K]
+    cands["seg_text_pos"] = cands["d_seg_text_pos"].cpu().numpy().view(np.uint64)[:n * K]
+    cands["seg_patterns"] = cands["d_seg_patterns"].cpu().numpy()[:n * K * rs].reshape(n * K, rs)
+    cands["seg"] = cands["d_seg"].cpu().numpy().view(capi.SEGMENT_DTYPE)[:n * K]
+    return cands
+
+
 def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0", chain=False, max_hits=None):
     """The seeding kernel on torch device buffers. `index` is build_index's (bucket, pos) -- numpy arrays, or uint8 torch tensors
     that already live on the device (as the "d_bucket" / "d_pos" of an earlier call); read_len is int32[n_reads], reads the ASCII

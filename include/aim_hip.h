@@ -280,7 +280,7 @@ typedef struct aim_sam {            /* 48 B per row */
     uint32_t ref_span, nm;
     uint32_t cigar_offset, n_cigar; /* words in the CIGAR buffer */
     uint32_t md_offset, md_len;     /* bytes in the MD buffer */
-    uint16_t flags;                 /* AIM_SAM_REVERSE | AIM_SAM_UNMAPPED */
+    uint16_t flags;                 /* AIM_SAM_REVERSE | AIM_SAM_UNMAPPED; from aim_sam_device_split also AIM_SAM_SUPPLEMENTARY */
     uint16_t status;                /* AIM_PAIR_* | AIM_SAM_OVERFLOW */
     uint32_t pad;                   /* 0 */
 } aim_sam_t;
@@ -345,6 +345,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_SEED_CHAIN 0x4000u /* colinear chaining of the seed hits: aim_seed_chain_device / aim_chain_t / aim_seed_chain_kernel_names exist */
 #define AIM_FEATURE_SEED_CHAIN_LONG 0x8000u /* chaining for long reads: aim_seed_chain_long_device / aim_seed_chain_long_kernel_name exist */
 #define AIM_FEATURE_CHAIN_CLASS 0x10000u /* primary / secondary chains and MAPQ: aim_chain_classify_device / aim_read_mapq_device / aim_chain_class_kernel_names exist */
+#define AIM_FEATURE_SPLIT 0x20000u /* split reads: aim_split_segments_device / aim_sam_device_split / aim_split_kernel_names exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -893,8 +894,8 @@ const char *aim_seed_chain_long_kernel_name(void);
  * 4-byte aligned. AIM_EINVAL with a message under the entry point's name, before any device query: K outside 1..AIM_SEED_MAX_CANDS,
  * mask_q8 outside 1..256, a read_size that is 0, no multiple of 8 or above AIM_SEED_LONG_MAX_READ_SIZE, n_reads * K >= 2^32,
  * score_unit < 1, an odd n_reads with d_mates and, last of all, a NULL device buffer.
- * Not in this version: aligning the supplementary parts of a split read, MAPQ inside aim_sam_t (a caller joins d_mapq[r] with
- * record r), AIM_FLAG_TOP_HITS rows, the clusters of aim_seed_device (they have no read interval) and a classification stage inside
+ * Not in this version: MAPQ inside aim_sam_t (a caller joins d_mapq[r] with record r; the supplementary parts of a split read are
+ * aligned through rule 10c below), AIM_FLAG_TOP_HITS rows, the clusters of aim_seed_device (they have no read interval) and a classification stage inside
  * aim_set_submit. */
 #define AIM_CHAIN_MASK_DEFAULT 128
 #define AIM_CHAIN_PRIMARY 0x1u
@@ -923,6 +924,87 @@ int aim_read_mapq_device(uint32_t K, uint32_t n_reads, int32_t score_unit, const
                          const aim_chain_class_t *d_class, aim_read_mapq_t *d_mapq /* [n_reads] */, void *hip_stream);
 /* "chain_class_kernel,read_mapq_kernel": comma-separated rocprofv3 kernel-trace name prefixes of the two entry points' kernels. */
 const char *aim_chain_class_kernel_names(void);
+
+/* ---- split reads (AIM_FEATURE_SPLIT): one alignable segment row per primary chain, supplementary SAM records -------------------
+ * Rule 8c marks the other parts of a split or chimeric read as supplementary primaries. Rule 10c turns every primary into a row an
+ * alignment kernel takes: the part of the read that is the primary's, and the window that fits that part. aim_sam_device_split then
+ * gives each aligned segment the clips for the rest of its read and SAM's supplementary flag. The sequence is
+ *     aim_seed_chain_device | aim_seed_chain_long_device -> aim_chain_classify_device -> aim_split_segments_device ->
+ *     aim_align_device_ref over all n_reads * K segment rows (AIM_FLAG_BACKTRACE | AIM_FLAG_ENDSFREE | AIM_FLAG_REF_TEXTS, text free
+ *     ends 2 * flank) -> aim_sam_device_split,
+ * through device buffers only. Nothing is compacted or counted: segment rows keep the slot layout slot = r * K + i, and the host knows
+ * every size before it launches. Arithmetic is signed 64-bit unless stated; the result is deterministic and independent of the grid.
+ *   10c. Segments (aim_split_segments_device). For read r: n = min(d_seed[r].n_cands, K), L = d_read_len[r] clamped to 0..read_size,
+ *       and [a_i, b_i) and the strand s of candidate i are those of rule 8c. Candidate i is a primary when i < n and
+ *       d_class[slot].flags & AIM_CHAIN_PRIMARY.
+ *       Open sides. A primary i is left-open when no other primary j of the read has a_j < a_i, and right-open when none has
+ *       b_j > b_i. A read with one primary is open on both sides.
+ *       Read interval. a' = left-open ? 0 : a_i and b' = right-open ? L : b_i. An open side runs to the end of the read; an inner side
+ *       stops exactly where the chain stops, at an exact k-mer match. (Extending an inner side to the true breakpoint needs a local or
+ *       x-drop alignment, which this library does not have.) A malformed chain cannot move the interval outside the read: a' is
+ *       clamped to 0..L and b' to a'..L. A chain kernel's own chains are never clamped.
+ *       Window. In chain-query coordinates low-open = s ? right-open : left-open and high-open = s ? left-open : right-open. With
+ *       c = d_chains[slot], start = d_text_pos[slot] & ~AIM_REF_MINUS_STRAND and E = start + d_requests[slot].text_len, rule 6c's
+ *       p_lo is recovered: if start > 0, p_lo = start + c.q_lo + flank (the left clamp did not act); otherwise, if
+ *       0 < text_len < read_size and E < ref_len, p_lo = E - (L - c.q_hi) - flank - c.ref_span (the right side was not clamped, so E
+ *       is rule 6c's hi); otherwise p_lo is not recoverable: the segment gets AIM_SEG_LOOSE and both of its window bounds are the
+ *       candidate's (start, E). p_hi = p_lo + c.ref_span. seg_start = low-open ? start : min(max(p_lo, 0), ref_len);
+ *       seg_end = max(seg_start, high-open ? E : min(max(p_hi, 0), ref_len)); text_len = min(seg_end - seg_start, read_size).
+ *       An open side keeps the candidate's flank; an inner side has none, since it ends on matching bases.
+ *       Outputs for a primary. d_seg_requests[slot] = {b' - a', text_len, 0, d_requests[slot].idx};
+ *       d_seg_text_pos[slot] = seg_start | s << 63; d_seg_patterns[slot] holds read[a', b') as given (no complement:
+ *       AIM_FLAG_REF_TEXTS turns the text), then zero bytes up to read_size; d_seg[slot] = {q_begin = a', q_end = b', read_len = L,
+ *       flags, cand = i} with flags = AIM_SEG_VALID, plus AIM_SEG_SUPPLEMENTARY when i > 0, AIM_SEG_LEFT_OPEN, AIM_SEG_RIGHT_OPEN and
+ *       AIM_SEG_LOOSE as they apply.
+ *       Every other slot (a secondary, an empty slot, i >= n) is rule 7's empty slot, which every alignment kernel already takes:
+ *       request {L, 0, 0, d_requests[slot].idx}, text_pos 0, the whole read row (all read_size bytes) as pattern, and a segment record
+ *       of 8 zero bytes.
+ *       Identity. For a read with a single primary (a' = 0, b' = L, both sides open) the segment's request and text_pos equal the
+ *       chain kernel's slot byte for byte, and so does its pattern row wherever the read row is zero behind L.
+ *   aim_sam_device_split. aim_sam_device's arguments plus d_seg, indexed like d_text_pos (entry d_sel[r], or r when d_sel is NULL;
+ *       no entry is read for UINT32_MAX). Record r is exactly aim_sam_device's record for the row, with two changes.
+ *       Clips. lead = q_begin and trail = read_len - q_end for a strand-0 window, swapped for strand 1 (the record shows the read
+ *       reverse-complemented). Each is added to the soft clip at that end of the CIGAR, merged with the peeled 'D' bases into the one
+ *       S word; a clip of 0 emits no word; n_cigar grows by at most 2.
+ *       Flag. flags gains AIM_SAM_SUPPLEMENTARY when the segment has AIM_SEG_SUPPLEMENTARY.
+ *       pos, ref_span, nm and MD are untouched. A row whose segment has flags == 0 gets aim_sam_device's record for a row without a
+ *       candidate (unmapped, pos 0). Capacity, overflow, the cursors and the 2^32 bound follow aim_sam_device's rules.
+ *       Invariant. For a mapped record the CIGAR's read-consuming lengths (M, I, S, =, X) sum to read_len.
+ * aim_split_segments_device only enqueues work on hip_stream, allocates nothing and needs no scratch. d_reads and d_seg_patterns are
+ * rows of read_size bytes, aligned like d_patterns (8 bytes suffice); d_seg and d_seg_text_pos are 8-byte aligned. The kernel is
+ * split_segments_kernel (csrc/split.hpp). AIM_EINVAL with a message under the entry point's name, before any device query: the
+ * refusals of aim_chain_classify_device (K outside 1..AIM_SEED_MAX_CANDS, a read_size that is 0, no multiple of 8 or above
+ * AIM_SEED_LONG_MAX_READ_SIZE, n_reads * K >= 2^32), flank < 0, a ref_len above AIM_SEED_MAX_REF_LEN and, last of all, a NULL device
+ * buffer. aim_sam_device_split refuses what aim_sam_device refuses, and a NULL d_seg with n_rows > 0.
+ * Not in this version: extending inner sides to the breakpoint (local or x-drop alignment), a split stage inside aim_set_submit or
+ * the host CLI, the SA tag and hard clips, packed read rows, segments from the voting kernel's clusters, and MAPQ per segment (a
+ * caller joins d_class[slot].mapq). Check aim_features() & AIM_FEATURE_SPLIT first. */
+#define AIM_SEG_VALID 0x1u
+#define AIM_SEG_SUPPLEMENTARY 0x2u
+#define AIM_SEG_LEFT_OPEN 0x4u
+#define AIM_SEG_RIGHT_OPEN 0x8u
+#define AIM_SEG_LOOSE 0x10u
+#define AIM_SAM_SUPPLEMENTARY 0x800u /* aim_sam_t.flags, from aim_sam_device_split alone */
+typedef struct aim_segment {
+    uint16_t q_begin, q_end;       /* [a', b'): the segment's interval of the read as given */
+    uint16_t read_len;             /* L */
+    uint8_t flags;                 /* AIM_SEG_*; 0: no segment in this slot */
+    uint8_t cand;                  /* i, the candidate within the read */
+} aim_segment_t;       /* 8 B per slot */
+int aim_split_segments_device(uint32_t K, uint32_t read_size, int32_t flank, uint64_t ref_len, uint32_t n_reads, const int32_t *d_read_len,
+                              const char *d_reads, const void *d_requests /* aim_request_t[n_reads * K] */, const uint64_t *d_text_pos,
+                              const aim_seed_t *d_seed, const aim_chain_t *d_chains, const aim_chain_class_t *d_class,
+                              void *d_seg_requests /* aim_request_t[n_reads * K] */, uint64_t *d_seg_text_pos,
+                              char *d_seg_patterns /* [n_reads * K][read_size] */, aim_segment_t *d_seg /* [n_reads * K] */,
+                              void *hip_stream);
+int aim_sam_device_split(const aim_params_t *params, uint32_t n_rows, const void *d_requests, const uint64_t *d_text_pos,
+                         const uint32_t *d_sel_or_null, const void *d_results, const char *d_ops, const char *d_reference, uint64_t ref_len,
+                         uint32_t options, aim_sam_t *d_sam, uint32_t *d_cigar, uint32_t cigar_cap, char *d_md, uint32_t md_cap,
+                         uint32_t *d_cursors, const aim_segment_t *d_seg, void *hip_stream);
+/* "split_segments_kernel,sam_lane_split_kernel,sam_wave_split_kernel": comma-separated rocprofv3 kernel-trace name prefixes of the
+ * kernels the two entry points launch; aim_sam_device_split takes the lane or the wave kernel where aim_sam_kernel_name names
+ * aim_sam_device's. */
+const char *aim_split_kernel_names(void);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
