@@ -51,11 +51,14 @@ FEATURE_SEED_CHAIN_LONG = 0x8000  # aim_features(): aim_seed_chain_long_device /
 SEED_LONG_MAX_READ_SIZE, SEED_LONG_MAX_HITS = 65528, 8192
 FEATURE_CHAIN_CLASS = 0x10000     # aim_features(): aim_chain_classify_device / aim_read_mapq_device / aim_chain_class_kernel_names exist
 FEATURE_SPLIT = 0x20000           # aim_features(): aim_split_segments_device / aim_sam_device_split / aim_split_kernel_names exist
+FEATURE_EXTEND = 0x40000          # aim_features(): aim_extend_segments_device / aim_extend_kernel_names exist
 CHAIN_MASK_DEFAULT = 128          # AIM_CHAIN_MASK_DEFAULT: mask_q8 of minimap2's mask level 0.5
 CHAIN_PRIMARY, CHAIN_SECONDARY, CHAIN_SUPPLEMENTARY = 0x1, 0x2, 0x4            # aim_chain_class_t.flags
 MAPQ_UNMAPPED, MAPQ_SECONDARY, MAPQ_SUPPLEMENTARY, MAPQ_PROPER = 0x1, 0x2, 0x4, 0x8   # aim_read_mapq_t.flags
 SEG_VALID, SEG_SUPPLEMENTARY, SEG_LEFT_OPEN, SEG_RIGHT_OPEN, SEG_LOOSE = 0x1, 0x2, 0x4, 0x8, 0x10   # aim_segment_t.flags
 SAM_SUPPLEMENTARY = 0x800         # aim_sam_t.flags, from aim_sam_device_split
+SEG_EXT_LEFT, SEG_EXT_RIGHT = 0x20, 0x40   # aim_segment_t.flags, from aim_extend_segments_device
+EXTEND_MAX_UNIT, EXTEND_MAX_COST, EXTEND_MAX_BAND, EXTEND_MAX_EXT = 64, 4095, 31, 1024
 
 
 def SEED_OPT_MINIMIZERS(w):
@@ -148,6 +151,14 @@ CHAIN_CLASS_DTYPE = np.dtype([("sub_score", "<u4"), ("parent", "u1"), ("flags", 
 READ_MAPQ_DTYPE = np.dtype([("slot", "<u4"), ("mapq", "u1"), ("chain_mapq", "u1"), ("aln_mapq", "u1"), ("flags", "u1")])   # aim_read_mapq_t
 SEGMENT_DTYPE = np.dtype([("q_begin", "<u2"), ("q_end", "<u2"), ("read_len", "<u2"), ("flags", "u1"), ("cand", "u1")])   # aim_segment_t
 assert CHAIN_CLASS_DTYPE.itemsize == 8 and READ_MAPQ_DTYPE.itemsize == 8
+EXTEND_DTYPE = np.dtype([("dq", "<u2", (2,)), ("dr", "<u2", (2,)), ("stop", "<u2", (2,)), ("pad", "<u2", (2,)), ("score", "<i4", (2,))])   # aim_extend_t
+assert EXTEND_DTYPE.itemsize == 24
+
+
+class ExtendParams(C.Structure):
+    """aim_extend_params_t"""
+    _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_o", C.c_int32), ("gap_e", C.c_int32), ("xdrop", C.c_int32),
+                ("max_cost", C.c_int32), ("band", C.c_int32), ("max_ext", C.c_int32)]
 
 
 class BatchIO(C.Structure):
@@ -251,6 +262,8 @@ SYMBOLS = {
     "aim_split_segments_device": (C.c_int, [_U32, _U32, _I32, C.c_uint64, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "aim_sam_device_split": (C.c_int, [C.POINTER(Params), _U32, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _U32, _VP, _VP, _U32, _VP, _U32, _VP, _VP, _VP]),
     "aim_split_kernel_names": (C.c_char_p, []),
+    "aim_extend_segments_device": (C.c_int, [C.POINTER(ExtendParams), _U32, _U32, C.c_uint64, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "aim_extend_kernel_names": (C.c_char_p, []),
     "aim_seed_groups_offsets": (C.c_int, [_U32, _U32, _VP]),
     "aim_seed_kernel_name": (C.c_char_p, []),
     "aim_index_device_scratch": (C.c_int, [_I32, C.c_uint64, C.POINTER(C.c_uint64)]),

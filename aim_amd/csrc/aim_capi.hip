@@ -41,6 +41,7 @@
 #include "seed_chain_long.hpp"
 #include "chain_class.hpp"
 #include "split.hpp"
+#include "extend.hpp"
 #include "index.hpp"
 #include "genasm_wave.hpp"
 
@@ -1689,7 +1690,7 @@ uint32_t aim_features(void)
 {
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
            AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS | AIM_FEATURE_SEED |
-           AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS | AIM_FEATURE_SEED_CHAIN | AIM_FEATURE_SEED_CHAIN_LONG | AIM_FEATURE_CHAIN_CLASS | AIM_FEATURE_SPLIT;
+           AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS | AIM_FEATURE_SEED_CHAIN | AIM_FEATURE_SEED_CHAIN_LONG | AIM_FEATURE_CHAIN_CLASS | AIM_FEATURE_SPLIT | AIM_FEATURE_EXTEND;
 }
 const char *aim_last_error(void) { return g_err; }
 
@@ -3483,6 +3484,65 @@ int aim_split_segments_device(uint32_t K, uint32_t read_size, int32_t flank, uin
         fprintf(stderr, "[aim plan] split_segments_kernel grid=%u block=%d lanes=%u parts=%u reads=%u K=%u read_size=%u\n", grid, aim::kSplitThreads, lanes,
                 1u << a.parts_log2, n_reads, K, read_size);
     aim::split_segments_launch(a, lanes, grid, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// segment extension (AIM_FEATURE_EXTEND; rule 11c in aim_hip.h, the kernels in extend.hpp)
+// ---------------------------------------------------------------------------
+const char *aim_extend_kernel_names(void) { return "extend_sides_kernel,extend_apply_kernel"; }
+
+int aim_extend_segments_device(const aim_extend_params_t *p, uint32_t K, uint32_t read_size, uint64_t ref_len, uint32_t n_reads, const int32_t *d_read_len,
+                               const char *d_reads, const char *d_reference, void *d_seg_requests, uint64_t *d_seg_text_pos, char *d_seg_patterns,
+                               aim_segment_t *d_seg, aim_extend_t *d_ext, void *hip_stream)
+{
+    const char *fn = "aim_extend_segments_device";
+    if (K < 1 || K > AIM_SEED_MAX_CANDS) return fail(AIM_EINVAL, "%s: K %u is outside 1..%d", fn, K, AIM_SEED_MAX_CANDS);
+    if (read_size == 0 || (read_size & 7u) || read_size > AIM_SEED_LONG_MAX_READ_SIZE)
+        return fail(AIM_EINVAL, "%s: read_size %u must be a positive multiple of 8, at most %d", fn, read_size, AIM_SEED_LONG_MAX_READ_SIZE);
+    if ((uint64_t)n_reads * K >= (1ull << 32)) return fail(AIM_EINVAL, "%s: n_reads %u * K %u does not fit 32 bits (split the batch)", fn, n_reads, K);
+    if (!p) return fail(AIM_EINVAL, "%s: NULL parameters", fn);
+    if (p->match < 1) return fail(AIM_EINVAL, "%s: match %d must be >= 1", fn, p->match);
+    if (p->mismatch < 1) return fail(AIM_EINVAL, "%s: mismatch %d must be >= 1", fn, p->mismatch);
+    if (p->gap_o < 0) return fail(AIM_EINVAL, "%s: gap_o %d must be >= 0", fn, p->gap_o);
+    if (p->gap_e < 1) return fail(AIM_EINVAL, "%s: gap_e %d must be >= 1", fn, p->gap_e);
+    if (p->xdrop < 0) return fail(AIM_EINVAL, "%s: xdrop %d must be >= 0", fn, p->xdrop);
+    if (p->max_cost < 1 || p->max_cost > AIM_EXTEND_MAX_COST) return fail(AIM_EINVAL, "%s: max_cost %d is outside 1..%d", fn, p->max_cost, AIM_EXTEND_MAX_COST);
+    if (p->band < 1 || p->band > AIM_EXTEND_MAX_BAND) return fail(AIM_EINVAL, "%s: band %d is outside 1..%d", fn, p->band, AIM_EXTEND_MAX_BAND);
+    if (p->max_ext < 8 || p->max_ext > AIM_EXTEND_MAX_EXT) return fail(AIM_EINVAL, "%s: max_ext %d is outside 8..%d", fn, p->max_ext, AIM_EXTEND_MAX_EXT);
+    {   // (64-bit: the sums of any accepted fields fit)
+        const int64_t x2 = 2 * ((int64_t)p->match + p->mismatch), oe2 = 2 * (int64_t)p->gap_o + 2 * (int64_t)p->gap_e + p->match;
+        if (std::max(x2, oe2) > AIM_EXTEND_MAX_UNIT)
+            return fail(AIM_EINVAL, "%s: max(x', o' + e') = %lld is above %d (x' = 2 (match + mismatch), o' + e' = 2 gap_o + 2 gap_e + match)", fn,
+                        (long long)std::max(x2, oe2), AIM_EXTEND_MAX_UNIT);
+    }
+    if (ref_len > AIM_SEED_MAX_REF_LEN) return fail(AIM_EINVAL, "%s: ref_len %llu is above %llu", fn, (unsigned long long)ref_len, (unsigned long long)AIM_SEED_MAX_REF_LEN);
+    if (n_reads && (!d_read_len || !d_reads || !d_reference || !d_seg_requests || !d_seg_text_pos || !d_seg_patterns || !d_seg || !d_ext))
+        return fail(AIM_EINVAL, "%s: null device buffer", fn);
+    int n = 0;
+    const int rc = aim_device_count(&n);
+    if (rc) return rc;
+    if (!n_reads) return AIM_OK;
+    const aim::Knobs kn = with_chip(read_knobs());
+    aim::ExtendArgs a;
+    memset(&a, 0, sizeof a);
+    aim::extend_plan(*p, a);
+    a.K = K; a.read_size = read_size; a.n_reads = n_reads; a.ref_len = (int64_t)ref_len;
+    a.dbg_poison_lds = kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u;
+    a.read_len = d_read_len; a.reads = d_reads; a.ref = d_reference;
+    a.seg_requests = static_cast<aim_request_t *>(d_seg_requests); a.seg_text_pos = d_seg_text_pos; a.seg_patterns = d_seg_patterns; a.seg = d_seg;
+    a.ext = d_ext;
+    // the items of a wavefront and the LDS of a side come from the parameters alone; only the grids are the device's
+    const uint64_t slots = (uint64_t)n_reads * K;
+    const uint32_t per_cu = std::min<uint32_t>(32u, std::max<uint32_t>(1u, aim::kExtendLdsPerCu / a.lds_bytes));
+    const uint32_t grid_sides = (uint32_t)std::min<uint64_t>(aim::resident_grid(kn, per_cu), (2u * slots + 63u) / 64u);
+    const uint32_t per_block = 64u * (aim::kExtendApplyThreads / 64u);
+    const uint32_t grid_apply = (uint32_t)std::min<uint64_t>(aim::resident_grid(kn, aim::kExtendApplyPerCu), (slots + per_block - 1u) / per_block);
+    if (kn.plan_debug)
+        fprintf(stderr, "[aim plan] extend_sides_kernel grid=%u block=%d lds=%u step=%d rings=%u+2*%u reads=%u K=%u read_size=%u; extend_apply_kernel grid=%u block=%d\n",
+                grid_sides, aim::kExtendThreads, a.lds_bytes, a.g, a.dm, a.di, n_reads, K, read_size, grid_apply, aim::kExtendApplyThreads);
+    aim::extend_launch(a, grid_sides, grid_apply, (hipStream_t)hip_stream);
     HIP_TRY(hipGetLastError());
     return AIM_OK;
 }

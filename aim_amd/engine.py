@@ -654,6 +654,49 @@ def split_segments(sp, cands, ref_len):
     return cands
 
 
+def extend_params(match=1, mismatch=3, gap_o=4, gap_e=1, xdrop=20, max_cost=400, band=capi.EXTEND_MAX_BAND, max_ext=64):
+    """aim_extend_params_t (rule 11c): the score (match +a, mismatch -x, a gap of g bases -(o + g e)), the x-drop Z, the cost cap,
+    the band and the longest extension of a side. The library checks the bounds."""
+    return capi.ExtendParams(int(match), int(mismatch), int(gap_o), int(gap_e), int(xdrop), int(max_cost), int(band), int(max_ext))
+
+
+def extend_segments_device(ep, K, read_size, ref_len, n_reads, d_read_len, d_reads, d_reference, d_seg_requests, d_seg_text_pos, d_seg_patterns, d_seg,
+                           d_ext, stream=None):
+    """aim_extend_segments_device on device pointers (integers, e.g. torch's data_ptr(); None = NULL): rule 11c over the four outputs of
+    split_segments_device, which it rewrites in place where an inner side moved, and aim_extend_t per slot in d_ext. d_reference is the
+    resident reference of ref_len bytes. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_extend_segments_device(C.byref(ep) if ep is not None else None, int(K), int(read_size), int(ref_len), int(n_reads), d_read_len,
+                                                      d_reads, d_reference, d_seg_requests, d_seg_text_pos, d_seg_patterns, d_seg, d_ext, stream))
+
+
+def extend_segments(sp, split_out, ref, ep=None):
+    """Extends the inner sides of the segments of split_segments where they live: takes the aim_seed_params_t of the chaining call, the
+    dict split_segments returned, the reference the chains were built on (a numpy uint8 array, or a uint8 torch tensor on the device;
+    its length is ref_len) and aim_extend_params_t (extend_params(); None = its defaults). Updates "d_seg_req", "d_seg_text_pos", "d_seg_patterns", "d_seg"
+    and their host copies "seg_req", "seg_text_pos", "seg_patterns", "seg", and adds "d_ext" and numpy "ext" (EXTEND_DTYPE, one per
+    slot). Returns the dict."""
+    import torch
+    if "d_seg" not in split_out:
+        raise ValueError("extend_segments takes the dict of split_segments: d_seg is missing")
+    ep = extend_params() if ep is None else ep
+    dev = split_out["d_seg"].device
+    n, K, rs = len(split_out["seed"]), sp.max_cands, sp.read_size
+    d_ref = ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref, dtype=np.uint8)).to(dev)
+    ref_len = int(d_ref.numel())
+    split_out["d_ext"] = torch.zeros(max(n * K, 1) * 24, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        extend_segments_device(ep, K, rs, ref_len, n, split_out["d_read_len"].data_ptr(), split_out["d_reads"].data_ptr(), d_ref.data_ptr(),
+                               split_out["d_seg_req"].data_ptr(), split_out["d_seg_text_pos"].data_ptr(), split_out["d_seg_patterns"].data_ptr(),
+                               split_out["d_seg"].data_ptr(), split_out["d_ext"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize(dev)
+    split_out["seg_req"] = split_out["d_seg_req"].cpu().numpy().view(capi.REQUEST_DTYPE)[:n * K]
+    split_out["seg_text_pos"] = split_out["d_seg_text_pos"].cpu().numpy().view(np.uint64)[:n * K]
+    split_out["seg_patterns"] = split_out["d_seg_patterns"].cpu().numpy()[:n * K * rs].reshape(n * K, rs)
+    split_out["seg"] = split_out["d_seg"].cpu().numpy().view(capi.SEGMENT_DTYPE)[:n * K]
+    split_out["ext"] = split_out["d_ext"].cpu().numpy().view(capi.EXTEND_DTYPE)[:n * K]
+    return split_out
+
+
 def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0", chain=False, max_hits=None):
     """The seeding kernel on torch device buffers. `index` is build_index's (bucket, pos) -- numpy arrays, or uint8 torch tensors
     that already live on the device (as the "d_bucket" / "d_pos" of an earlier call); read_len is int32[n_reads], reads the ASCII

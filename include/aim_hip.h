@@ -346,6 +346,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_SEED_CHAIN_LONG 0x8000u /* chaining for long reads: aim_seed_chain_long_device / aim_seed_chain_long_kernel_name exist */
 #define AIM_FEATURE_CHAIN_CLASS 0x10000u /* primary / secondary chains and MAPQ: aim_chain_classify_device / aim_read_mapq_device / aim_chain_class_kernel_names exist */
 #define AIM_FEATURE_SPLIT 0x20000u /* split reads: aim_split_segments_device / aim_sam_device_split / aim_split_kernel_names exist */
+#define AIM_FEATURE_EXTEND 0x40000u /* segment extension: aim_extend_segments_device / aim_extend_kernel_names exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -940,8 +941,8 @@ const char *aim_chain_class_kernel_names(void);
  *       Open sides. A primary i is left-open when no other primary j of the read has a_j < a_i, and right-open when none has
  *       b_j > b_i. A read with one primary is open on both sides.
  *       Read interval. a' = left-open ? 0 : a_i and b' = right-open ? L : b_i. An open side runs to the end of the read; an inner side
- *       stops exactly where the chain stops, at an exact k-mer match. (Extending an inner side to the true breakpoint needs a local or
- *       x-drop alignment, which this library does not have.) A malformed chain cannot move the interval outside the read: a' is
+ *       stops exactly where the chain stops, at an exact k-mer match. (Extending an inner side to the true breakpoint is a stage of
+ *       its own behind this one: rule 11c, aim_extend_segments_device.) A malformed chain cannot move the interval outside the read: a' is
  *       clamped to 0..L and b' to a'..L. A chain kernel's own chains are never clamped.
  *       Window. In chain-query coordinates low-open = s ? right-open : left-open and high-open = s ? left-open : right-open. With
  *       c = d_chains[slot], start = d_text_pos[slot] & ~AIM_REF_MINUS_STRAND and E = start + d_requests[slot].text_len, rule 6c's
@@ -976,9 +977,9 @@ const char *aim_chain_class_kernel_names(void);
  * refusals of aim_chain_classify_device (K outside 1..AIM_SEED_MAX_CANDS, a read_size that is 0, no multiple of 8 or above
  * AIM_SEED_LONG_MAX_READ_SIZE, n_reads * K >= 2^32), flank < 0, a ref_len above AIM_SEED_MAX_REF_LEN and, last of all, a NULL device
  * buffer. aim_sam_device_split refuses what aim_sam_device refuses, and a NULL d_seg with n_rows > 0.
- * Not in this version: extending inner sides to the breakpoint (local or x-drop alignment), a split stage inside aim_set_submit or
- * the host CLI, the SA tag and hard clips, packed read rows, segments from the voting kernel's clusters, and MAPQ per segment (a
- * caller joins d_class[slot].mapq). Check aim_features() & AIM_FEATURE_SPLIT first. */
+ * Not in this version: a split stage inside aim_set_submit or the host CLI, the SA tag and hard clips, packed read rows, segments
+ * from the voting kernel's clusters, MAPQ per segment (a caller joins d_class[slot].mapq); overlap between neighbouring extended
+ * segments (rule 11c) is not trimmed. Check aim_features() & AIM_FEATURE_SPLIT first. */
 #define AIM_SEG_VALID 0x1u
 #define AIM_SEG_SUPPLEMENTARY 0x2u
 #define AIM_SEG_LEFT_OPEN 0x4u
@@ -1005,6 +1006,72 @@ int aim_sam_device_split(const aim_params_t *params, uint32_t n_rows, const void
  * kernels the two entry points launch; aim_sam_device_split takes the lane or the wave kernel where aim_sam_kernel_name names
  * aim_sam_device's. */
 const char *aim_split_kernel_names(void);
+
+/* ---- segment extension (AIM_FEATURE_EXTEND): the inner sides of split-read segments extended to the breakpoint ------------------
+ * Rule 10c stops an inner side at the chain's last exact k-mer, so the read bases between that k-mer and the junction are clipped in
+ * both records of a split read. aim_extend_segments_device stands between aim_split_segments_device and aim_align_device_ref: a
+ * score-only x-drop alignment moves each inner side outward, and the touched slots are rewritten in place. CIGAR and records stay
+ * with the AIM_FLAG_ENDSFREE alignment and aim_sam_device_split, which reads the new q_begin / q_end: the clips shrink by themselves
+ * and the CIGAR's read-consuming lengths still sum to read_len. Arithmetic is signed 64-bit unless stated; the result is deterministic
+ * and independent of the grid.
+ *   11c, part 1: one side. Parameters (aim_extend_params_t): match a >= 1, mismatch x >= 1, gap_o o >= 0, gap_e e >= 1, xdrop Z >= 0,
+ *       max_cost in 1..AIM_EXTEND_MAX_COST, band in 1..AIM_EXTEND_MAX_BAND, max_ext in 8..AIM_EXTEND_MAX_EXT. The transformed
+ *       penalties (Eizenga and Paten) are x' = 2 (a + x), o' = 2 o, e' = 2 e + a, and max(x', o' + e') <= AIM_EXTEND_MAX_UNIT.
+ *       Sides. q_begin, q_end are the slot's aim_segment_t, seg_start = d_seg_text_pos[slot] & ~AIM_REF_MINUS_STRAND, minus is its
+ *       bit 63, text_len = d_seg_requests[slot].text_len, L = d_read_len[r] clamped to 0..read_size. Side 0 is the read's left, side
+ *       1 its right. A side is run when the segment has AIM_SEG_VALID and not AIM_SEG_LOOSE, the side is not open, the record is
+ *       well-formed (q_begin <= q_end <= L, 0 <= text_len <= read_size, seg_start + text_len <= ref_len) and n > 0 and m > 0 below;
+ *       the outputs of every other side are zero.
+ *       Right: Q = read[q_end, min(L, q_end + max_ext)). Left: Q = reverse(read[max(0, q_begin - max_ext), q_begin)). n = |Q|.
+ *       The reference side runs up when (side is right) != minus. m = min(n + band, room, (read_size - text_len) / inner) with
+ *       room = ref_len - (seg_start + text_len) up and seg_start down, and inner the number of sides of the segment that are not
+ *       open (1 or 2; the division rounds down). Up: T = ref[seg_start + text_len, ... + m). Down: T = reverse(ref[seg_start - m,
+ *       seg_start)). T is complemented with AIM_FLAG_REF_TEXTS' table when minus. Bases match when their bytes are equal.
+ *       Cost. D(v, h) is the minimum gap-affine cost (match 0, mismatch x', a gap of g bases o' + g e'; a gap in the read next to
+ *       one in the reference opens twice) of aligning Q[0, v) with T[0, h) through cells with |h - v| <= band only; D(0, 0) = 0.
+ *       S(v, h) = (a (v + h) - D(v, h)) / 2, always an integer, is the best score of that prefix pair with match +a, mismatch -x and
+ *       a gap of g bases -(o + g e).
+ *       Stop level. For s = 0, 1, 2, ...: R(s) = max{v + h : D <= s} and B(s) = max{a (v + h) - D : D <= s}. s* is the first s with
+ *       a R(s) - s < B(s) - 2 Z, or max_cost if there is none up to max_cost. (No cell of a cost above s can score within Z of the
+ *       best any more.)
+ *       Result. The cell with D <= s* of the greatest a (v + h) - D; among equals the smallest D, then the smallest h - v; (0, 0)
+ *       when no cell is positive. dq = v, dr = h, score = S(v, h), stop = s* (stop is also written when the result is (0, 0)).
+ *   11c, part 2: apply. For a slot with a non-zero (dq, dr) on either side: q_begin -= dq[0], q_end += dq[1]; the reference bound of
+ *       the side that ran up moves up by that side's dr (seg_end), the other one down (seg_start); pattern_len = q_end - q_begin,
+ *       text_len = seg_end - seg_start (part 1's budget keeps it <= read_size), d_seg_text_pos = seg_start | minus << 63;
+ *       aim_segment_t.flags gains AIM_SEG_EXT_LEFT / AIM_SEG_EXT_RIGHT for the sides that moved; the pattern row becomes
+ *       read[q_begin, q_end) as given, read from d_reads, then zero bytes up to read_size. Every other slot keeps every byte: a
+ *       single-primary read, a secondary, an empty slot. An extended inner side gets no flank: it ends on a match.
+ *   d_ext[slot] holds both sides' (dq, dr, stop, score), zero for a side that was not run; pad is zero.
+ * aim_extend_segments_device only enqueues work on hip_stream (extend_sides_kernel, then extend_apply_kernel; csrc/extend.hpp),
+ * allocates nothing and needs no scratch. Alignment of the buffers as for aim_split_segments_device; d_ext is 8-byte aligned;
+ * d_reference holds ref_len bytes. AIM_EINVAL with a message under the entry point's name, before any device query, in this order:
+ * the K, read_size and n_reads * K refusals of aim_split_segments_device, a NULL p and each parameter bound in the order above, a
+ * ref_len above AIM_SEED_MAX_REF_LEN and, last of all, a NULL device buffer.
+ * Not in this version: a stage inside aim_set_submit or the host CLI, trimming the overlap of neighbouring extended segments, the SA
+ * tag, a band above 31, max_ext above 1024, extending open sides, Z-drop. Check aim_features() & AIM_FEATURE_EXTEND first. */
+#define AIM_SEG_EXT_LEFT 0x20u
+#define AIM_SEG_EXT_RIGHT 0x40u
+#define AIM_EXTEND_MAX_UNIT 64
+#define AIM_EXTEND_MAX_COST 4095
+#define AIM_EXTEND_MAX_BAND 31
+#define AIM_EXTEND_MAX_EXT 1024
+typedef struct aim_extend_params {
+    int32_t match, mismatch, gap_o, gap_e;   /* a, x, o, e of the score S */
+    int32_t xdrop;                           /* Z */
+    int32_t max_cost, band, max_ext;
+} aim_extend_params_t; /* 32 B */
+typedef struct aim_extend {
+    uint16_t dq[2], dr[2], stop[2], pad[2];  /* index 0: read-left side, 1: read-right side */
+    int32_t score[2];
+} aim_extend_t;        /* 24 B per slot */
+int aim_extend_segments_device(const aim_extend_params_t *p, uint32_t K, uint32_t read_size, uint64_t ref_len, uint32_t n_reads,
+                               const int32_t *d_read_len, const char *d_reads, const char *d_reference,
+                               void *d_seg_requests /* in/out */, uint64_t *d_seg_text_pos /* in/out */,
+                               char *d_seg_patterns /* in/out */, aim_segment_t *d_seg /* in/out */,
+                               aim_extend_t *d_ext /* [n_reads * K] */, void *hip_stream);
+/* "extend_sides_kernel,extend_apply_kernel": comma-separated rocprofv3 kernel-trace name prefixes of the entry point's kernels. */
+const char *aim_extend_kernel_names(void);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
