@@ -51,7 +51,7 @@ struct ReadMapqArgs {
 // Lanes per read: the smallest of 4, 8, 16 that holds K candidates.
 constexpr uint32_t chain_class_lanes(uint32_t K) { return K <= 4 ? 4u : K <= 8 ? 8u : 16u; }
 
-#ifdef AIM_TU_CHAIN_CLASS   // the kernels live in tu_chain_class.hip alone; aim_capi.hip sees the arguments and the launchers
+#ifdef AIM_TU_CHAIN_CLASS   // the kernels live in tu_chain_class.hip alone; capi_pipeline.hip sees the arguments and the launchers
 
 // Both 8-byte rows as the two dwords they are stored as: one dwordx2 store per row instead of a dword and four bytes.
 struct ClassWords {

@@ -69,7 +69,7 @@ inline void extend_plan(const aim_extend_params_t &p, ExtendArgs &a)
     a.lds_bytes = (a.dm + 2u * a.di) * 128u + a.q_cap + a.t_cap;
 }
 
-#ifdef AIM_TU_EXTEND   // the kernels live in tu_extend.hip alone; aim_capi.hip sees the arguments and the launchers
+#ifdef AIM_TU_EXTEND   // the kernels live in tu_extend.hip alone; capi_pipeline.hip sees the arguments and the launchers
 
 static_assert(sizeof(aim_extend_t) == 24 && sizeof(aim_segment_t) == 8 && sizeof(aim_request_t) == 16, "rows as rule 11c lays them out");
 

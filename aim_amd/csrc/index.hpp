@@ -123,7 +123,7 @@ struct IndexScanArgs {
     uint32_t dbg_poison_lds;
 };
 
-#ifdef AIM_TU_INDEX   // the kernels live in tu_index.hip alone; aim_capi.hip sees the argument blocks and the launchers
+#ifdef AIM_TU_INDEX   // the kernels live in tu_index.hip alone; capi_pipeline.hip sees the argument blocks and the launchers
 
 __device__ __forceinline__ uint32_t index_scan_add(uint32_t v, int lane)   // inclusive wave prefix sum
 {

@@ -1,5 +1,5 @@
 // minimizer.hpp -- the order of the (w, k) minimizer rule (aim_hip.h, AIM_FEATURE_MINIMIZERS), shared by the index kernel (index.hpp),
-// the seed kernel (seed.hpp) and the host build (aim_capi.hip).
+// the seed kernel (seed.hpp) and the host build (capi_pipeline.hip).
 //
 // A valid k-mer of code c has the order key min_hash(c), the 32-bit finaliser of MurmurHash3: a bijection on 32 bits, so two k-mers tie
 // only when they are the same k-mer, and min_unhash gives the code back -- the kernels keep one dword per position, the key, and

@@ -325,7 +325,7 @@ __device__ __forceinline__ void seed_finish(const SeedArgs &a, uint32_t *keys, u
 
 #endif
 
-#ifdef AIM_TU_SEED   // the kernels live in tu_seed.hip alone; aim_capi.hip sees SeedArgs and the launchers
+#ifdef AIM_TU_SEED   // the kernels live in tu_seed.hip alone; capi_pipeline.hip sees SeedArgs and the launchers
 
 __global__ __launch_bounds__(64) void seed_candidates_kernel(SeedArgs a)
 {

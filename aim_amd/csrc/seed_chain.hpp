@@ -214,7 +214,7 @@ __device__ __forceinline__ void seed_chain_write(const SeedChainArgs &ca, uint32
 
 #endif
 
-#ifdef AIM_TU_SEED_CHAIN   // the kernels live in tu_seed_chain.hip alone; aim_capi.hip sees SeedChainArgs and the launchers
+#ifdef AIM_TU_SEED_CHAIN   // the kernels live in tu_seed_chain.hip alone; capi_pipeline.hip sees SeedChainArgs and the launchers
 
 // seed_append with the anchor p << 12 | j in place of the diagonal key.
 __device__ __forceinline__ uint32_t seed_chain_append(const SeedArgs &a, uint64_t *ks, uint32_t count, uint32_t code, bool ok, int32_t j, int lane)

@@ -61,7 +61,7 @@ struct SeedChainLongArgs {
 constexpr size_t seed_chain_long_lds_bytes(uint32_t max_hits) { return (size_t)max_hits * 14u + kSeedLongTileBytes; }
 static_assert(seed_chain_long_lds_bytes(AIM_SEED_LONG_MAX_HITS) <= 160u * 1024u, "one workgroup fits a CU's LDS at the largest cap");
 
-#ifdef AIM_TU_SEED_CHAIN_LONG   // the kernel lives in tu_seed_chain_long.hip alone; aim_capi.hip sees the arguments and the launcher
+#ifdef AIM_TU_SEED_CHAIN_LONG   // the kernel lives in tu_seed_chain_long.hip alone; capi_pipeline.hip sees the arguments and the launcher
 
 // seed_chain_append with the cap H and the anchor p << 16 | j. Returns the new count (wave-uniform; past H only "overflowed" matters).
 __device__ __forceinline__ uint32_t seed_long_append(const SeedArgs &a, uint64_t *ks, uint32_t H, uint32_t count, uint32_t code, bool ok, uint32_t j, int lane)

@@ -60,7 +60,7 @@ inline uint32_t split_parts_log2(uint32_t K, uint32_t read_size)
     return lg;
 }
 
-#ifdef AIM_TU_SPLIT   // the kernel lives in tu_split.hip alone; aim_capi.hip sees the arguments and the launcher
+#ifdef AIM_TU_SPLIT   // the kernel lives in tu_split.hip alone; capi_pipeline.hip sees the arguments and the launcher
 
 static_assert(sizeof(aim_segment_t) == 8 && sizeof(aim_request_t) == 16 && sizeof(aim_chain_t) == 16, "rows as rule 10c lays them out");
 
