@@ -59,6 +59,9 @@ SEG_VALID, SEG_SUPPLEMENTARY, SEG_LEFT_OPEN, SEG_RIGHT_OPEN, SEG_LOOSE = 0x1, 0x
 SAM_SUPPLEMENTARY = 0x800         # aim_sam_t.flags, from aim_sam_device_split
 SEG_EXT_LEFT, SEG_EXT_RIGHT = 0x20, 0x40   # aim_segment_t.flags, from aim_extend_segments_device
 EXTEND_MAX_UNIT, EXTEND_MAX_COST, EXTEND_MAX_BAND, EXTEND_MAX_EXT = 64, 4095, 31, 1024
+FEATURE_MAPPER = 0x80000          # aim_features(): aim_map_records_device / aim_mapper_* exist
+MAP_EXTEND = 0x1                  # aim_mapper_params_t.options: run the segment extension (rule 11c)
+MAPPER_MAX_SLOTS = 4
 
 
 def SEED_OPT_MINIMIZERS(w):
@@ -159,6 +162,28 @@ class ExtendParams(C.Structure):
     """aim_extend_params_t"""
     _fields_ = [("match", C.c_int32), ("mismatch", C.c_int32), ("gap_o", C.c_int32), ("gap_e", C.c_int32), ("xdrop", C.c_int32),
                 ("max_cost", C.c_int32), ("band", C.c_int32), ("max_ext", C.c_int32)]
+
+
+MAP_RECORD_DTYPE = np.dtype([("sam", SAM_DTYPE), ("read", "<u4"), ("q_begin", "<u2"), ("q_end", "<u2"), ("mapq", "u1"), ("seg_flags", "u1"), ("rank", "u1"),
+                             ("n_records", "u1"), ("slot", "<u4")])   # aim_map_record_t
+assert MAP_RECORD_DTYPE.itemsize == 64
+
+
+class MapperParams(C.Structure):
+    """aim_mapper_params_t"""
+    _fields_ = [("seed", SeedParams), ("max_hits", C.c_uint32), ("mask_q8", C.c_uint32), ("extend", ExtendParams), ("options", C.c_uint32),
+                ("match", C.c_int32), ("mismatch", C.c_int32), ("gap_o", C.c_int32), ("gap_e", C.c_int32), ("max_score", C.c_int32),
+                ("sam_options", C.c_uint32), ("max_reads", C.c_uint32), ("slots", C.c_uint32), ("cigar_cap", C.c_uint32), ("md_cap", C.c_uint32)]
+
+
+class MapperOut(C.Structure):
+    """aim_mapper_out_t"""
+    _fields_ = [("n_reads", C.c_uint32), ("n_records", C.c_uint32), ("cigar_words", C.c_uint32), ("md_bytes", C.c_uint32),
+                ("cigar_needed", C.c_uint32), ("md_needed", C.c_uint32), ("records", C.c_void_p), ("rec_offsets", C.c_void_p),
+                ("cigar", C.c_void_p), ("md", C.c_void_p)]
+
+
+assert C.sizeof(MapperParams) == 124 and C.sizeof(MapperOut) == 56
 
 
 class BatchIO(C.Structure):
@@ -272,6 +297,14 @@ SYMBOLS = {
     "aim_index_build_minimizers": (C.c_int, [_VP, C.c_uint64, _I32, _I32, _VP, _VP, C.POINTER(C.c_uint64), C.c_int]),
     "aim_index_build_device_minimizers": (C.c_int, [_VP, C.c_uint64, _I32, _I32, _VP, _VP, _VP, C.c_uint64, _VP]),
     "aim_minimizer_kernel_names": (C.c_char_p, []),
+    "aim_map_records_scratch": (C.c_size_t, [_U32]),
+    "aim_map_records_device": (C.c_int, [_U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "aim_mapper_kernel_names": (C.c_char_p, []),
+    "aim_mapper_device_bytes": (C.c_int, [C.POINTER(MapperParams), C.c_uint64, C.POINTER(C.c_uint64)]),
+    "aim_mapper_create": (C.c_int, [C.POINTER(MapperParams), C.c_int, _VP, C.c_uint64, C.POINTER(_VP)]),
+    "aim_mapper_submit": (C.c_int, [_VP, _U32, _U32, _VP, _VP]),
+    "aim_mapper_wait": (C.c_int, [_VP, _U32, C.POINTER(MapperOut)]),
+    "aim_mapper_free": (C.c_int, [_VP]),
 }
 
 _lib = None

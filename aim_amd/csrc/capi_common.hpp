@@ -1,8 +1,12 @@
 // capi_common.hpp -- what the units of the C-ABI share: aim_capi.hip (planner, device sets, alignment entry points), capi_pipeline.hip
-// (index, seeding, classes and MAPQ, split, extension) and capi_host.hip (host-side formatters and generators). Internal, not installed.
-// Every function declared here has ONE definition, in aim_capi.hip, next to the state it owns: fail() writes the thread-local buffer
-// aim_last_error() returns, read_knobs() is the one reader of the AIM_* environment, with_chip() asks chip_cus()'s per-device cache.
+// (index, seeding, classes and MAPQ, split, extension), capi_mapper.hip (the record list and aim_mapper_t) and capi_host.hip (host-side
+// formatters and generators). Internal, not installed.
+// Every function declared here has ONE definition: in aim_capi.hip, next to the state it owns -- fail() writes the thread-local buffer
+// aim_last_error() returns, read_knobs() is the one reader of the AIM_* environment, with_chip() asks chip_cus()'s per-device cache --,
+// in capi_pipeline.hip for the parameter checks of its stages, or inline below for the refusals the pipeline's entry points share.
 #pragma once
+#include <cstdint>
+
 #include <hip/hip_runtime.h>
 
 #include "aim_hip.h"
@@ -20,6 +24,44 @@ int check_lengths(const aim_params_t &p, uint32_t n_pairs, const void *requests)
 uint32_t packed_row_dwords(int read_size);
 // AIM_FLAG_REF_TEXTS: texts gathered from a device-resident reference (batch_io.hpp); no plan depends on it.
 inline bool is_ref(const aim_params_t &p) { return (p.flags & AIM_FLAG_REF_TEXTS) != 0; }
+// What every alignment entry point refuses about its aim_params_t (aim_capi.hip: validate_params), before any device query.
+int check_align_params(const aim_params_t &p);
+// The bounds every seeding entry point sets (capi_pipeline.hip). max_read_size is AIM_SEED_MAX_READ_SIZE, or the entry point's own bound,
+// and then `fn` names that entry point in the read_size message.
+int check_seed_params(const aim_seed_params_t &sp, int32_t max_read_size = AIM_SEED_MAX_READ_SIZE, const char *fn = nullptr);
+// aim_seed_chain_device's own bound behind check_seed_params, under the name `fn`.
+int check_seed_chain_band(const aim_seed_params_t &sp, const char *fn);
+// aim_seed_chain_long_device's parameter check: check_seed_params with the long read_size bound, then what is its own.
+int check_seed_long_params(const aim_seed_params_t &sp, uint32_t max_hits);
+// aim_extend_segments_device's refusals of its aim_extend_params_t, in the header's order, under the name `fn`.
+int check_extend_params(const char *fn, const aim_extend_params_t *p);
+
+// The refusals the pipeline's entry points share: one copy of each bound and of its message; `fn` names the entry point. Each is true when
+// its bound holds and otherwise leaves its message in aim_last_error(). An entry point joins them with && in its own order -- the order its
+// violations are reported in -- and answers AIM_EINVAL when the chain breaks.
+template <typename... A>
+inline bool refuse(const char *fmt, A... a) { return fail(AIM_EINVAL, fmt, a...) == AIM_OK; }
+inline bool cands_ok(const char *fn, uint32_t K) { return (K >= 1 && K <= AIM_SEED_MAX_CANDS) || refuse("%s: K %u is outside 1..%d", fn, K, AIM_SEED_MAX_CANDS); }
+inline bool read_size_ok(const char *fn, uint32_t rs)
+{
+    return (rs && !(rs & 7u) && rs <= AIM_SEED_LONG_MAX_READ_SIZE) || refuse("%s: read_size %u must be a positive multiple of 8, at most %d", fn, rs, AIM_SEED_LONG_MAX_READ_SIZE);
+}
+// (n_reads * K candidate slots are indexed with 32 bits; `what` is the name K goes by in the entry point's arguments)
+inline bool slots_ok(const char *fn, uint32_t n_reads, uint32_t K, const char *what = "K")
+{
+    return (uint64_t)n_reads * K < (1ull << 32) || refuse("%s: n_reads %u * %s %u does not fit 32 bits (split the batch)", fn, n_reads, what, K);
+}
+// (the index and seeding entry points say why, the later stages name the bound)
+inline bool ref_len_ok(const char *fn, uint64_t ref_len, bool say_why)
+{
+    if (ref_len <= AIM_SEED_MAX_REF_LEN) return true;
+    return say_why ? refuse("%s: ref_len %llu is above 2^32 - 2^25 (positions and diagonal keys are 32-bit)", fn, (unsigned long long)ref_len)
+                   : refuse("%s: ref_len %llu is above %llu", fn, (unsigned long long)ref_len, (unsigned long long)AIM_SEED_MAX_REF_LEN);
+}
+// (an empty batch may come with NULL buffers)
+inline bool buffers_ok(const char *fn, uint32_t n_reads, bool all_set) { return !n_reads || all_set || refuse("%s: null device buffer", fn); }
+// AIM_DEBUG_POISON_LDS as the kernels take it (dbg_poison_lds): 0x100 | byte, or 0 for "leave LDS as it is"
+inline uint32_t poison_lds_word(const aim::Knobs &kn) { return kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u; }
 #pragma GCC visibility pop
 }  // namespace capi
 }  // namespace aim
@@ -31,3 +73,20 @@ inline bool is_ref(const aim_params_t &p) { return (p.flags & AIM_FLAG_REF_TEXTS
             return ::aim::capi::fail(e_ == hipErrorOutOfMemory ? AIM_ENOMEM : AIM_ENODEV, "%s failed: %s", #expr, \
                                      hipGetErrorString(e_));                                \
     } while (0)
+
+namespace aim {
+namespace capi {
+// What every batch entry point of the pipeline ends in once its arguments are checked: the device probe, nothing to do for an empty batch,
+// then launch(kn) with the knobs of the current device, and the launch's error.
+template <typename Launch>
+inline int launch_batch(uint32_t n_reads, Launch launch)
+{
+    int n = 0;
+    if (const int rc = aim_device_count(&n)) return rc;
+    if (!n_reads) return AIM_OK;
+    launch(with_chip(read_knobs()));
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
+}
+}  // namespace capi
+}  // namespace aim

@@ -1,0 +1,378 @@
+// capi_mapper.hip -- the top layer of the read-mapping pipeline (include/aim_hip.h, AIM_FEATURE_MAPPER): rule 12c's entry point
+// aim_map_records_device (kernels in mapper.hpp, the prefix sums by index.hpp's scan) and aim_mapper_t, which owns the reference, the
+// index and per-slot buffers and streams and runs the stages of capi_pipeline.hip and aim_capi.hip through their public entry points.
+// Host code only. What this unit shares with the others is in capi_common.hpp.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "capi_common.hpp"
+#include "index.hpp"
+#include "mapper.hpp"
+
+using namespace aim::capi;
+
+namespace {
+
+constexpr size_t kMapScratch = 4u * aim::kIndexScanParts;   // the scan's part sums
+
+// The message a stage's own check left, under the mapper entry point's name.
+int under(const char *fn, int rc)
+{
+    const std::string was = aim_last_error();
+    return fail(rc, "%s: %s", fn, was.c_str());
+}
+
+// The segment alignment of the mapper: global-in-the-read, free text ends of 2 * flank, CIGAR, windows of the resident reference.
+aim_endsfree_params_t align_params(const aim_mapper_params_t &p)
+{
+    aim_endsfree_params_t e;
+    memset(&e, 0, sizeof e);
+    e.base.algo = AIM_ALGO_WFA;
+    e.base.match = p.match; e.base.mismatch = p.mismatch; e.base.gap_o = p.gap_o; e.base.gap_e = p.gap_e;
+    e.base.max_score = p.max_score;
+    e.base.read_size = p.seed.read_size;
+    e.base.flags = AIM_FLAG_BACKTRACE | AIM_FLAG_ENDSFREE | AIM_FLAG_REF_TEXTS;
+    e.text_begin_free = e.text_end_free = 2 * p.seed.flank;
+    return e;
+}
+
+// Every refusal of aim_mapper_device_bytes and aim_mapper_create, in stage order; no device is asked anything.
+int check_mapper_params(const char *fn, const aim_mapper_params_t *p, uint64_t ref_len)
+{
+    if (!p) return fail(AIM_EINVAL, "%s: params is NULL", fn);
+    const aim_seed_params_t &sp = p->seed;
+    if (p->max_hits) {
+        if (check_seed_long_params(sp, p->max_hits)) return under(fn, AIM_EINVAL);
+    } else {
+        if (check_seed_params(sp, AIM_SEED_MAX_READ_SIZE, "aim_seed_chain_device") || check_seed_chain_band(sp, "aim_seed_chain_device")) return under(fn, AIM_EINVAL);
+        if (!sp.options) return fail(AIM_EINVAL, "%s: aim_seed_params_t: options 0x0 must be AIM_SEED_OPT_MINIMIZERS(w) (the mapper builds a minimizer index)", fn);
+    }
+    const uint32_t K = (uint32_t)sp.max_cands, rs = (uint32_t)sp.read_size;
+    if (p->mask_q8 < 1 || p->mask_q8 > 256) return fail(AIM_EINVAL, "%s: mask_q8 %u is outside 1..256", fn, p->mask_q8);
+    if (!(slots_ok(fn, p->max_reads, K, "max_cands") && ref_len_ok(fn, ref_len, false))) return AIM_EINVAL;
+    if (p->options & AIM_MAP_EXTEND)
+        if (const int rc = check_extend_params(fn, &p->extend)) return rc;
+    const aim_endsfree_params_t ap = align_params(*p);
+    if (check_align_params(ap.base)) return under(fn, AIM_EINVAL);
+    if (p->sam_options & ~AIM_SAM_EQX) return fail(AIM_EINVAL, "%s: unknown sam_options 0x%x", fn, p->sam_options);
+    if ((uint64_t)p->max_reads * K * (4ull * rs + 10ull) >= (1ull << 32))
+        return fail(AIM_EINVAL, "%s: max_reads %u * K %u rows of read_size %u exceed the 32-bit offsets of aim_sam_t (max_reads * K * (4 * read_size + 10) must stay below 2^32)",
+                    fn, p->max_reads, K, rs);
+    if (p->options & ~AIM_MAP_EXTEND) return fail(AIM_EINVAL, "%s: unknown options 0x%x", fn, p->options);
+    if (!p->max_reads) return fail(AIM_EINVAL, "%s: max_reads must be >= 1", fn);
+    if (p->slots < 1 || p->slots > AIM_MAPPER_MAX_SLOTS) return fail(AIM_EINVAL, "%s: slots %u is outside 1..%d", fn, p->slots, AIM_MAPPER_MAX_SLOTS);
+    return AIM_OK;
+}
+
+// The device buffers of one slot, in allocation order: `bytes` each, carved out of one allocation at multiples of 256.
+enum Buf { B_READS, B_READ_LEN, B_REQ, B_TEXT_POS, B_VOTES, B_SEED, B_CHAINS, B_CLASS, B_SEG_REQ, B_SEG_TEXT_POS, B_SEG_PATTERNS, B_SEG, B_EXT,
+           B_RESULTS, B_OPS, B_SCRATCH, B_SAM, B_CIGAR, B_MD, B_OFFSETS, B_RECORDS, B_MAP_SCRATCH, B_COUNT };
+
+struct SlotLayout {
+    uint64_t at[B_COUNT], bytes[B_COUNT], total;
+};
+
+inline uint64_t up256(uint64_t x) { return (x + 255u) & ~255ull; }
+
+SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch)
+{
+    const uint64_t N = p.max_reads, K = (uint64_t)p.seed.max_cands, rs = (uint64_t)p.seed.read_size, S = N * K;
+    SlotLayout L;
+    memset(&L, 0, sizeof L);
+    uint64_t *b = L.bytes;
+    b[B_READS] = N * rs + 64; b[B_READ_LEN] = 4 * N;
+    b[B_REQ] = 16 * S; b[B_TEXT_POS] = 8 * S; b[B_VOTES] = 4 * S; b[B_SEED] = 16 * N; b[B_CHAINS] = 16 * S; b[B_CLASS] = 8 * S;
+    b[B_SEG_REQ] = 16 * S; b[B_SEG_TEXT_POS] = 8 * S; b[B_SEG_PATTERNS] = S * rs + 64; b[B_SEG] = 8 * S;
+    b[B_EXT] = (p.options & AIM_MAP_EXTEND) ? 24 * S : 0;
+    b[B_RESULTS] = sizeof(aim_result_t) * S; b[B_OPS] = S * 2 * rs + 64; b[B_SCRATCH] = align_scratch;
+    b[B_SAM] = sizeof(aim_sam_t) * S; b[B_CIGAR] = 4ull * p.cigar_cap; b[B_MD] = p.md_cap;
+    b[B_OFFSETS] = 4 * (N + 3);          // rec_offsets[n_reads + 1], then the two cursors of the SAM kernel: one copy fetches the three dwords
+    b[B_RECORDS] = sizeof(aim_map_record_t) * S; b[B_MAP_SCRATCH] = kMapScratch;
+    uint64_t at = 0;
+    for (int i = 0; i < B_COUNT; ++i) {
+        L.at[i] = at;
+        at += up256(std::max<uint64_t>(b[i], 4));
+    }
+    L.total = at;
+    return L;
+}
+
+struct MapperSlot {
+    hipStream_t stream = nullptr;
+    char *dev = nullptr;                 // SlotLayout
+    char *h_reads = nullptr;             // pinned
+    int32_t *h_read_len = nullptr;
+    aim_map_record_t *h_records = nullptr;
+    uint32_t *h_offsets = nullptr;
+    uint32_t *h_cigar = nullptr;
+    char *h_md = nullptr;
+    uint32_t *h_head = nullptr;          // {record count, CIGAR words, MD bytes}
+    bool in_flight = false;
+    uint32_t n_reads = 0;
+};
+
+}  // namespace
+
+struct aim_mapper {
+    aim_mapper_params_t p;
+    aim_endsfree_params_t ap;
+    int device = 0;
+    uint64_t ref_len = 0;
+    char *d_ref = nullptr;
+    uint32_t *d_bucket = nullptr, *d_pos = nullptr;
+    size_t align_scratch = 0;
+    SlotLayout L;
+    MapperSlot slot[AIM_MAPPER_MAX_SLOTS];
+};
+
+namespace {
+
+template <typename T>
+T *at(const aim_mapper *m, const MapperSlot &s, Buf b) { return reinterpret_cast<T *>(s.dev + m->L.at[b]); }
+
+void release(aim_mapper *m)
+{
+    for (MapperSlot &s : m->slot) {
+        if (s.stream) (void)hipStreamSynchronize(s.stream);
+        if (s.dev) (void)hipFree(s.dev);
+        for (void *h : {(void *)s.h_reads, (void *)s.h_read_len, (void *)s.h_records, (void *)s.h_offsets, (void *)s.h_cigar, (void *)s.h_md, (void *)s.h_head})
+            if (h) (void)hipHostFree(h);
+        if (s.stream) (void)hipStreamDestroy(s.stream);
+    }
+    if (m->d_ref) (void)hipFree(m->d_ref);
+    if (m->d_bucket) (void)hipFree(m->d_bucket);
+    if (m->d_pos) (void)hipFree(m->d_pos);
+    delete m;
+}
+
+template <typename T>
+int pinned(T **p, uint64_t bytes) { HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(p), (size_t)std::max<uint64_t>(bytes, 16), hipHostMallocDefault)); return AIM_OK; }
+
+int create(aim_mapper *m, const char *seq)
+{
+    const aim_mapper_params_t &p = m->p;
+    const uint64_t N = p.max_reads, K = (uint64_t)p.seed.max_cands, rs = (uint64_t)p.seed.read_size;
+    const int32_t k = p.seed.k, w = (int32_t)(p.seed.options >> 8);
+    HIP_TRY(hipSetDevice(m->device));
+    // the reference with its 16 bytes of slack, then the minimizer index on the device; the build's scratch goes before the slots come
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_ref), (size_t)up256(m->ref_len + 16)));
+    HIP_TRY(hipMemset(m->d_ref, 0, (size_t)up256(m->ref_len + 16)));
+    if (m->ref_len) HIP_TRY(hipMemcpy(m->d_ref, seq, (size_t)m->ref_len, hipMemcpyHostToDevice));
+    uint64_t be = 0, pc = 0, isb = 0;
+    if (const int rc = aim_index_sizes(k, m->ref_len, &be, &pc)) return rc;
+    if (const int rc = aim_index_device_scratch(k, m->ref_len, &isb)) return rc;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_bucket), (size_t)(be * 4)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_pos), (size_t)std::max<uint64_t>(pc * 4, 256)));
+    void *iscr = nullptr;
+    HIP_TRY(hipMalloc(&iscr, (size_t)std::max<uint64_t>(isb, 256)));
+    int rc = aim_index_build_device_minimizers(m->d_ref, m->ref_len, k, w, m->d_bucket, m->d_pos, iscr, isb, nullptr);
+    const hipError_t e = hipDeviceSynchronize();
+    (void)hipFree(iscr);
+    if (rc) return rc;
+    HIP_TRY(e);
+    m->align_scratch = aim_scratch_bytes(&m->ap.base, (uint32_t)(N * K));
+    if (!m->align_scratch) return under("aim_mapper_create", AIM_ENOMEM);
+    m->L = slot_layout(p, m->align_scratch);
+    for (uint32_t i = 0; i < p.slots; ++i) {
+        MapperSlot &s = m->slot[i];
+        HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.dev), (size_t)m->L.total));
+        HIP_TRY(hipMemset(s.dev, 0, (size_t)m->L.total));
+        if ((rc = pinned(&s.h_reads, N * rs)) || (rc = pinned(&s.h_read_len, 4 * N)) || (rc = pinned(&s.h_records, sizeof(aim_map_record_t) * N * K)) ||
+            (rc = pinned(&s.h_offsets, 4 * (N + 1))) || (rc = pinned(&s.h_cigar, 4ull * p.cigar_cap)) || (rc = pinned(&s.h_md, p.md_cap)) || (rc = pinned(&s.h_head, 16)))
+            return rc;
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return AIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---------------------------------------------------------------------------
+// the record list (rule 12c in aim_hip.h, the kernels in mapper.hpp)
+// ---------------------------------------------------------------------------
+const char *aim_mapper_kernel_names(void) { return "map_count_kernel,map_records_kernel"; }
+
+size_t aim_map_records_scratch(uint32_t) { return kMapScratch; }
+
+int aim_map_records_device(uint32_t K, uint32_t n_reads, const aim_segment_t *d_seg, const aim_sam_t *d_sam, const aim_chain_class_t *d_class,
+                           uint32_t *d_rec_offsets, aim_map_record_t *d_records, void *d_scratch, size_t scratch_bytes, void *hip_stream)
+{
+    const char *fn = "aim_map_records_device";
+    if (!(cands_ok(fn, K) && slots_ok(fn, n_reads, K) && (d_rec_offsets || refuse("%s: d_rec_offsets is NULL", fn)) &&
+          buffers_ok(fn, n_reads, d_seg && d_sam && d_class && d_records && d_scratch) &&
+          (!(((uintptr_t)d_sam | (uintptr_t)d_records) & 15u) || refuse("%s: d_sam and d_records must be 16-byte aligned", fn)) &&
+          (!n_reads || scratch_bytes >= kMapScratch ||
+           refuse("%s: scratch_bytes %zu is below the %zu aim_map_records_scratch reports", fn, scratch_bytes, kMapScratch))))
+        return AIM_EINVAL;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    int n_dev = 0;
+    if (const int rc = aim_device_count(&n_dev)) return rc;
+    if (!n_reads) {
+        HIP_TRY(hipMemsetAsync(d_rec_offsets, 0, 4, stream));
+        return AIM_OK;
+    }
+    const aim::Knobs kn = with_chip(read_knobs());
+    // Debugging aid, as for the index scratch: results must not depend on what the scratch held before.
+    if (kn.poison_scratch >= 0) HIP_TRY(hipMemsetAsync(d_scratch, kn.poison_scratch & 0xff, kMapScratch, stream));
+    const aim::MapArgs a = {K, n_reads, d_seg, d_sam, d_class, d_rec_offsets, d_records};
+    const uint32_t lanes = aim::chain_class_lanes(K), per_block = aim::kMapThreads / lanes;
+    const uint32_t resident = aim::resident_grid(kn, aim::kMapPerCu);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(resident, ((uint64_t)n_reads + per_block - 1u) / per_block);
+    aim::IndexScanArgs s;
+    memset(&s, 0, sizeof s);
+    s.data = d_rec_offsets; s.n = (uint64_t)n_reads + 1u; s.dbg_poison_lds = poison_lds_word(kn); s.part = static_cast<uint32_t *>(d_scratch);
+    s.n_parts = (uint32_t)std::min<uint64_t>(std::min(resident, aim::kIndexScanParts), (s.n + aim::kIndexScanBlock - 1u) / aim::kIndexScanBlock);
+    s.per_part = ((s.n + s.n_parts - 1u) / s.n_parts + aim::kIndexScanBlock - 1u) / aim::kIndexScanBlock * aim::kIndexScanBlock;
+    if (kn.plan_debug)
+        fprintf(stderr, "[aim plan] map_count_kernel grid=%u block=%d lanes=%u reads=%u K=%u; scan parts=%u per_part=%llu; map_records_kernel grid=%u block=%d\n", grid,
+                aim::kMapThreads, lanes, n_reads, K, s.n_parts, (unsigned long long)s.per_part, grid, aim::kMapThreads);
+    aim::map_count_launch(a, lanes, grid, stream);
+    HIP_TRY(hipGetLastError());
+    aim::index_launch_scan(s, stream);
+    HIP_TRY(hipGetLastError());
+    aim::map_records_launch(a, lanes, grid, stream);
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// aim_mapper_t
+// ---------------------------------------------------------------------------
+int aim_mapper_device_bytes(const aim_mapper_params_t *params, uint64_t ref_len, uint64_t *bytes)
+{
+    const char *fn = "aim_mapper_device_bytes";
+    if (const int rc = check_mapper_params(fn, params, ref_len)) return rc;
+    if (!bytes) return fail(AIM_EINVAL, "%s: bytes is NULL", fn);
+    const aim_endsfree_params_t ap = align_params(*params);
+    const size_t as = aim_scratch_bytes(&ap.base, (uint32_t)((uint64_t)params->max_reads * (uint64_t)params->seed.max_cands));
+    if (!as) return under(fn, AIM_ENOMEM);
+    uint64_t be = 0, pc = 0, isb = 0;
+    if (aim_index_sizes(params->seed.k, ref_len, &be, &pc) || aim_index_device_scratch(params->seed.k, ref_len, &isb)) return under(fn, AIM_EINVAL);
+    *bytes = up256(ref_len + 16) + be * 4 + std::max<uint64_t>(pc * 4, 256) +
+             std::max<uint64_t>(std::max<uint64_t>(isb, 256), (uint64_t)params->slots * slot_layout(*params, as).total);
+    return AIM_OK;
+}
+
+int aim_mapper_create(const aim_mapper_params_t *params, int device, const char *seq, uint64_t ref_len, aim_mapper_t **mapper)
+{
+    const char *fn = "aim_mapper_create";
+    if (const int rc = check_mapper_params(fn, params, ref_len)) return rc;
+    if (!mapper) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
+    if (ref_len && !seq) return fail(AIM_EINVAL, "%s: seq is NULL", fn);
+    int n_dev = 0;
+    if (const int rc = aim_device_count(&n_dev)) return rc;
+    if (device < 0 || device >= n_dev) return fail(AIM_EINVAL, "%s: device %d is outside 0..%d", fn, device, n_dev - 1);
+    aim_mapper *m = new aim_mapper();
+    m->p = *params;
+    m->ap = align_params(*params);
+    m->device = device;
+    m->ref_len = ref_len;
+    if (const int rc = create(m, seq)) {
+        const std::string was = aim_last_error();   // (release() must not lose the message)
+        release(m);
+        return fail(rc, "%s", was.c_str());
+    }
+    *mapper = m;
+    return AIM_OK;
+}
+
+int aim_mapper_submit(aim_mapper_t *m, uint32_t slot, uint32_t n_reads, const int32_t *read_len, const char *reads)
+{
+    const char *fn = "aim_mapper_submit";
+    if (!m) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
+    if (slot >= m->p.slots) return fail(AIM_EINVAL, "%s: slot %u is outside 0..%u", fn, slot, m->p.slots - 1);
+    if (n_reads > m->p.max_reads) return fail(AIM_EINVAL, "%s: n_reads %u is above max_reads %u", fn, n_reads, m->p.max_reads);
+    if (n_reads && (!read_len || !reads)) return fail(AIM_EINVAL, "%s: NULL read_len or reads", fn);
+    MapperSlot &s = m->slot[slot];
+    if (s.in_flight) return fail(AIM_ESTATE, "%s: slot %u is in flight (aim_mapper_wait first)", fn, slot);
+    HIP_TRY(hipSetDevice(m->device));
+    s.n_reads = n_reads;
+    if (!n_reads) {                      // a valid batch with nothing to enqueue
+        s.in_flight = true;
+        return AIM_OK;
+    }
+    const aim_mapper_params_t &p = m->p;
+    const uint32_t K = (uint32_t)p.seed.max_cands, rs = (uint32_t)p.seed.read_size, rows = n_reads * K;
+    const int32_t flank = p.seed.flank;
+    hipStream_t st = s.stream;
+    memcpy(s.h_read_len, read_len, 4ull * n_reads);
+    memcpy(s.h_reads, reads, (size_t)n_reads * rs);
+    char *d_reads = at<char>(m, s, B_READS), *d_seg_pat = at<char>(m, s, B_SEG_PATTERNS), *d_ops = at<char>(m, s, B_OPS);
+    int32_t *d_rl = at<int32_t>(m, s, B_READ_LEN);
+    void *d_req = at<void>(m, s, B_REQ), *d_seg_req = at<void>(m, s, B_SEG_REQ), *d_res = at<void>(m, s, B_RESULTS);
+    uint64_t *d_tp = at<uint64_t>(m, s, B_TEXT_POS), *d_seg_tp = at<uint64_t>(m, s, B_SEG_TEXT_POS);
+    aim_seed_t *d_seed = at<aim_seed_t>(m, s, B_SEED);
+    aim_chain_t *d_chains = at<aim_chain_t>(m, s, B_CHAINS);
+    aim_chain_class_t *d_cls = at<aim_chain_class_t>(m, s, B_CLASS);
+    aim_segment_t *d_seg = at<aim_segment_t>(m, s, B_SEG);
+    aim_sam_t *d_sam = at<aim_sam_t>(m, s, B_SAM);
+    uint32_t *d_off = at<uint32_t>(m, s, B_OFFSETS), *d_cursors = d_off + n_reads + 1u;
+    HIP_TRY(hipMemcpyAsync(d_rl, s.h_read_len, 4ull * n_reads, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_reads, s.h_reads, (size_t)n_reads * rs, hipMemcpyHostToDevice, st));
+    int rc = p.max_hits ? aim_seed_chain_long_device(&p.seed, p.max_hits, n_reads, d_rl, d_reads, m->d_bucket, m->d_pos, m->ref_len, d_req, d_tp,
+                                                     at<uint32_t>(m, s, B_VOTES), d_seed, d_chains, st)
+                        : aim_seed_chain_device(&p.seed, n_reads, d_rl, d_reads, m->d_bucket, m->d_pos, m->ref_len, d_req, d_tp, at<uint32_t>(m, s, B_VOTES),
+                                                d_seed, d_chains, st);
+    if (!rc) rc = aim_chain_classify_device(K, rs, p.mask_q8, n_reads, d_rl, d_tp, d_seed, d_chains, d_cls, st);
+    if (!rc) rc = aim_split_segments_device(K, rs, flank, m->ref_len, n_reads, d_rl, d_reads, d_req, d_tp, d_seed, d_chains, d_cls, d_seg_req, d_seg_tp, d_seg_pat, d_seg, st);
+    if (!rc && (p.options & AIM_MAP_EXTEND))
+        rc = aim_extend_segments_device(&p.extend, K, rs, m->ref_len, n_reads, d_rl, d_reads, m->d_ref, d_seg_req, d_seg_tp, d_seg_pat, d_seg,
+                                        at<aim_extend_t>(m, s, B_EXT), st);
+    if (!rc) rc = aim_align_device_ref(&m->ap.base, rows, d_seg_req, d_seg_pat, d_seg_tp, m->d_ref, m->ref_len, d_res, d_ops, at<void>(m, s, B_SCRATCH), m->align_scratch, st);
+    if (!rc)
+        rc = aim_sam_device_split(&m->ap.base, rows, d_seg_req, d_seg_tp, nullptr, d_res, d_ops, m->d_ref, m->ref_len, p.sam_options, d_sam, at<uint32_t>(m, s, B_CIGAR),
+                                  p.cigar_cap, at<char>(m, s, B_MD), p.md_cap, d_cursors, d_seg, st);
+    if (!rc) rc = aim_map_records_device(K, n_reads, d_seg, d_sam, d_cls, d_off, at<aim_map_record_t>(m, s, B_RECORDS), at<void>(m, s, B_MAP_SCRATCH), kMapScratch, st);
+    if (rc) {
+        (void)hipStreamSynchronize(st);  // what was enqueued reads the pinned buffers
+        return under(fn, rc);
+    }
+    s.in_flight = true;
+    return AIM_OK;
+}
+
+int aim_mapper_wait(aim_mapper_t *m, uint32_t slot, aim_mapper_out_t *out)
+{
+    const char *fn = "aim_mapper_wait";
+    if (!m) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
+    if (slot >= m->p.slots) return fail(AIM_EINVAL, "%s: slot %u is outside 0..%u", fn, slot, m->p.slots - 1);
+    if (!out) return fail(AIM_EINVAL, "%s: out is NULL", fn);
+    MapperSlot &s = m->slot[slot];
+    if (!s.in_flight) return fail(AIM_ESTATE, "%s: nothing is in flight on slot %u", fn, slot);
+    s.in_flight = false;
+    memset(out, 0, sizeof *out);
+    out->n_reads = s.n_reads;
+    out->records = s.h_records; out->rec_offsets = s.h_offsets; out->cigar = s.h_cigar; out->md = s.h_md;
+    s.h_offsets[0] = 0;
+    if (!s.n_reads) return AIM_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    const uint32_t *d_off = at<uint32_t>(m, s, B_OFFSETS);
+    // one small copy first: rec_offsets[n_reads] and the two cursors behind it; it says how much of everything else is in use
+    HIP_TRY(hipMemcpyAsync(s.h_head, d_off + s.n_reads, 12, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    out->n_records = s.h_head[0];
+    out->cigar_needed = s.h_head[1]; out->md_needed = s.h_head[2];
+    out->cigar_words = std::min(out->cigar_needed, m->p.cigar_cap); out->md_bytes = std::min(out->md_needed, m->p.md_cap);
+    HIP_TRY(hipMemcpyAsync(s.h_records, at<char>(m, s, B_RECORDS), sizeof(aim_map_record_t) * (size_t)out->n_records, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(hipMemcpyAsync(s.h_offsets, d_off, 4ull * (s.n_reads + 1u), hipMemcpyDeviceToHost, s.stream));
+    if (out->cigar_words) HIP_TRY(hipMemcpyAsync(s.h_cigar, at<char>(m, s, B_CIGAR), 4ull * out->cigar_words, hipMemcpyDeviceToHost, s.stream));
+    if (out->md_bytes) HIP_TRY(hipMemcpyAsync(s.h_md, at<char>(m, s, B_MD), out->md_bytes, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    return AIM_OK;
+}
+
+int aim_mapper_free(aim_mapper_t *m)
+{
+    if (!m) return AIM_OK;
+    (void)hipSetDevice(m->device);
+    release(m);
+    return AIM_OK;
+}
+
+}  // extern "C"

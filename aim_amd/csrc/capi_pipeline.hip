@@ -20,47 +20,6 @@ using namespace aim::capi;
 
 namespace {
 
-// The refusals the entry points share: one copy of each bound and of its message; `fn` names the entry point. Each is true when its bound
-// holds and otherwise leaves its message in aim_last_error(). An entry point joins them with && in its own order -- the order its
-// violations are reported in -- and answers AIM_EINVAL when the chain breaks.
-template <typename... A>
-bool refuse(const char *fmt, A... a) { return fail(AIM_EINVAL, fmt, a...) == AIM_OK; }
-bool cands_ok(const char *fn, uint32_t K) { return (K >= 1 && K <= AIM_SEED_MAX_CANDS) || refuse("%s: K %u is outside 1..%d", fn, K, AIM_SEED_MAX_CANDS); }
-bool read_size_ok(const char *fn, uint32_t rs)
-{
-    return (rs && !(rs & 7u) && rs <= AIM_SEED_LONG_MAX_READ_SIZE) || refuse("%s: read_size %u must be a positive multiple of 8, at most %d", fn, rs, AIM_SEED_LONG_MAX_READ_SIZE);
-}
-// (n_reads * K candidate slots are indexed with 32 bits; `what` is the name K goes by in the entry point's arguments)
-bool slots_ok(const char *fn, uint32_t n_reads, uint32_t K, const char *what = "K")
-{
-    return (uint64_t)n_reads * K < (1ull << 32) || refuse("%s: n_reads %u * %s %u does not fit 32 bits (split the batch)", fn, n_reads, what, K);
-}
-// (the index and seeding entry points say why, the later stages name the bound)
-bool ref_len_ok(const char *fn, uint64_t ref_len, bool say_why)
-{
-    if (ref_len <= AIM_SEED_MAX_REF_LEN) return true;
-    return say_why ? refuse("%s: ref_len %llu is above 2^32 - 2^25 (positions and diagonal keys are 32-bit)", fn, (unsigned long long)ref_len)
-                   : refuse("%s: ref_len %llu is above %llu", fn, (unsigned long long)ref_len, (unsigned long long)AIM_SEED_MAX_REF_LEN);
-}
-// (an empty batch may come with NULL buffers)
-bool buffers_ok(const char *fn, uint32_t n_reads, bool all_set) { return !n_reads || all_set || refuse("%s: null device buffer", fn); }
-
-// What every batch entry point ends in once its arguments are checked: the device probe, nothing to do for an empty batch, then
-// launch(kn) with the knobs of the current device, and the launch's error.
-template <typename Launch>
-int launch_batch(uint32_t n_reads, Launch launch)
-{
-    int n = 0;
-    if (const int rc = aim_device_count(&n)) return rc;
-    if (!n_reads) return AIM_OK;
-    launch(with_chip(read_knobs()));
-    HIP_TRY(hipGetLastError());
-    return AIM_OK;
-}
-
-// AIM_DEBUG_POISON_LDS as the kernels take it (dbg_poison_lds): 0x100 | byte, or 0 for "leave LDS as it is"
-uint32_t poison_lds_word(const aim::Knobs &kn) { return kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u; }
-
 // ---------------------------------------------------------------------------
 // device-side seeding (AIM_FEATURE_SEED; the rule is stated in aim_hip.h, the kernel in seed.hpp)
 // ---------------------------------------------------------------------------
@@ -70,9 +29,10 @@ int check_index_args(int32_t k, uint64_t ref_len)
     return ref_len_ok("seed index", ref_len, true) ? AIM_OK : AIM_EINVAL;
 }
 
-// The bounds every seeding entry point sets. max_read_size is AIM_SEED_MAX_READ_SIZE, or the entry point's own bound, and then `fn`
-// names that entry point in the read_size message.
-int check_seed_params(const aim_seed_params_t &sp, int32_t max_read_size = AIM_SEED_MAX_READ_SIZE, const char *fn = nullptr)
+}  // namespace
+
+// The bounds every seeding entry point sets (declared in capi_common.hpp).
+int aim::capi::check_seed_params(const aim_seed_params_t &sp, int32_t max_read_size, const char *fn)
 {
     if (sp.k < 8 || sp.k > 14) return fail(AIM_EINVAL, "aim_seed_params_t: k %d is outside 8..14", sp.k);
     if (sp.stride < 1) return fail(AIM_EINVAL, "aim_seed_params_t: stride %d must be >= 1", sp.stride);
@@ -92,6 +52,13 @@ int check_seed_params(const aim_seed_params_t &sp, int32_t max_read_size = AIM_S
     }
     return AIM_OK;
 }
+
+int aim::capi::check_seed_chain_band(const aim_seed_params_t &sp, const char *fn)
+{
+    return sp.band > AIM_SEED_CHAIN_MAX_BAND ? fail(AIM_EINVAL, "aim_seed_params_t: band %d is above %d (%s)", sp.band, AIM_SEED_CHAIN_MAX_BAND, fn) : AIM_OK;
+}
+
+namespace {
 
 int check_window(int32_t w) { return w < 1 || w > AIM_SEED_MAX_W ? fail(AIM_EINVAL, "seed index: w %d is outside 1..%d", w, AIM_SEED_MAX_W) : AIM_OK; }
 
@@ -216,8 +183,8 @@ int seed_device(const char *fn, bool chain, const aim_seed_params_t *sp, uint32_
 {
     if (!sp) return fail(AIM_EINVAL, "%s: sp is NULL", fn);
     if (const int rc = check_seed_params(*sp)) return rc;
-    if (chain && sp->band > AIM_SEED_CHAIN_MAX_BAND)
-        return fail(AIM_EINVAL, "aim_seed_params_t: band %d is above %d (%s)", sp->band, AIM_SEED_CHAIN_MAX_BAND, fn);
+    if (chain)
+        if (const int rc = check_seed_chain_band(*sp, fn)) return rc;
     aim::SeedChainArgs ca;
     memset(&ca, 0, sizeof ca);
     ca.chains = d_chains;
@@ -236,9 +203,11 @@ int seed_device(const char *fn, bool chain, const aim_seed_params_t *sp, uint32_
                        });
 }
 
+}  // namespace
+
 // aim_seed_chain_long_device's parameter check: check_seed_params with the long read_size bound, then what is its own -- minimizers
 // required, the band bound and the hit cap.
-int check_seed_long_params(const aim_seed_params_t &sp, uint32_t max_hits)
+int aim::capi::check_seed_long_params(const aim_seed_params_t &sp, uint32_t max_hits)
 {
     if (const int rc = check_seed_params(sp, AIM_SEED_LONG_MAX_READ_SIZE, "aim_seed_chain_long_device")) return rc;
     if (!sp.options)
@@ -249,6 +218,25 @@ int check_seed_long_params(const aim_seed_params_t &sp, uint32_t max_hits)
         return fail(AIM_EINVAL, "aim_seed_chain_long_device: max_hits %u must be a power of two in %d..%d", max_hits, AIM_SEED_MAX_HITS, AIM_SEED_LONG_MAX_HITS);
     return AIM_OK;
 }
+
+int aim::capi::check_extend_params(const char *fn, const aim_extend_params_t *p)
+{
+    if (!p) return fail(AIM_EINVAL, "%s: NULL parameters", fn);
+    if (p->match < 1) return fail(AIM_EINVAL, "%s: match %d must be >= 1", fn, p->match);
+    if (p->mismatch < 1) return fail(AIM_EINVAL, "%s: mismatch %d must be >= 1", fn, p->mismatch);
+    if (p->gap_o < 0) return fail(AIM_EINVAL, "%s: gap_o %d must be >= 0", fn, p->gap_o);
+    if (p->gap_e < 1) return fail(AIM_EINVAL, "%s: gap_e %d must be >= 1", fn, p->gap_e);
+    if (p->xdrop < 0) return fail(AIM_EINVAL, "%s: xdrop %d must be >= 0", fn, p->xdrop);
+    if (p->max_cost < 1 || p->max_cost > AIM_EXTEND_MAX_COST) return fail(AIM_EINVAL, "%s: max_cost %d is outside 1..%d", fn, p->max_cost, AIM_EXTEND_MAX_COST);
+    if (p->band < 1 || p->band > AIM_EXTEND_MAX_BAND) return fail(AIM_EINVAL, "%s: band %d is outside 1..%d", fn, p->band, AIM_EXTEND_MAX_BAND);
+    if (p->max_ext < 8 || p->max_ext > AIM_EXTEND_MAX_EXT) return fail(AIM_EINVAL, "%s: max_ext %d is outside 8..%d", fn, p->max_ext, AIM_EXTEND_MAX_EXT);
+    const int64_t unit = std::max<int64_t>(2 * ((int64_t)p->match + p->mismatch), 2 * (int64_t)p->gap_o + 2 * (int64_t)p->gap_e + p->match);   // (64-bit: the sums of any accepted fields fit)
+    if (unit > AIM_EXTEND_MAX_UNIT)
+        return fail(AIM_EINVAL, "%s: max(x', o' + e') = %lld is above %d (x' = 2 (match + mismatch), o' + e' = 2 gap_o + 2 gap_e + match)", fn, (long long)unit, AIM_EXTEND_MAX_UNIT);
+    return AIM_OK;
+}
+
+namespace {
 
 // aim_index_build_device (w = 0: index_code_kernel) and aim_index_build_device_minimizers (w >= 1: index_minimizer_kernel in its place)
 int index_build_device(const char *d_reference, uint64_t ref_len, int32_t k, int32_t w, uint32_t *d_bucket, uint32_t *d_pos, void *d_scratch,
@@ -510,18 +498,7 @@ int aim_extend_segments_device(const aim_extend_params_t *p, uint32_t K, uint32_
 {
     const char *fn = "aim_extend_segments_device";
     if (!(cands_ok(fn, K) && read_size_ok(fn, read_size) && slots_ok(fn, n_reads, K))) return AIM_EINVAL;
-    if (!p) return fail(AIM_EINVAL, "%s: NULL parameters", fn);
-    if (p->match < 1) return fail(AIM_EINVAL, "%s: match %d must be >= 1", fn, p->match);
-    if (p->mismatch < 1) return fail(AIM_EINVAL, "%s: mismatch %d must be >= 1", fn, p->mismatch);
-    if (p->gap_o < 0) return fail(AIM_EINVAL, "%s: gap_o %d must be >= 0", fn, p->gap_o);
-    if (p->gap_e < 1) return fail(AIM_EINVAL, "%s: gap_e %d must be >= 1", fn, p->gap_e);
-    if (p->xdrop < 0) return fail(AIM_EINVAL, "%s: xdrop %d must be >= 0", fn, p->xdrop);
-    if (p->max_cost < 1 || p->max_cost > AIM_EXTEND_MAX_COST) return fail(AIM_EINVAL, "%s: max_cost %d is outside 1..%d", fn, p->max_cost, AIM_EXTEND_MAX_COST);
-    if (p->band < 1 || p->band > AIM_EXTEND_MAX_BAND) return fail(AIM_EINVAL, "%s: band %d is outside 1..%d", fn, p->band, AIM_EXTEND_MAX_BAND);
-    if (p->max_ext < 8 || p->max_ext > AIM_EXTEND_MAX_EXT) return fail(AIM_EINVAL, "%s: max_ext %d is outside 8..%d", fn, p->max_ext, AIM_EXTEND_MAX_EXT);
-    const int64_t unit = std::max<int64_t>(2 * ((int64_t)p->match + p->mismatch), 2 * (int64_t)p->gap_o + 2 * (int64_t)p->gap_e + p->match);   // (64-bit: the sums of any accepted fields fit)
-    if (unit > AIM_EXTEND_MAX_UNIT)
-        return fail(AIM_EINVAL, "%s: max(x', o' + e') = %lld is above %d (x' = 2 (match + mismatch), o' + e' = 2 gap_o + 2 gap_e + match)", fn, (long long)unit, AIM_EXTEND_MAX_UNIT);
+    if (const int rc = check_extend_params(fn, p)) return rc;
     if (!(ref_len_ok(fn, ref_len, false) && buffers_ok(fn, n_reads, d_read_len && d_reads && d_reference && d_seg_requests && d_seg_text_pos && d_seg_patterns && d_seg && d_ext)))
         return AIM_EINVAL;
     return launch_batch(n_reads, [&](const aim::Knobs &kn) {

@@ -697,6 +697,85 @@ def extend_segments(sp, split_out, ref, ep=None):
     return split_out
 
 
+def map_records_scratch(n_reads):
+    """aim_map_records_scratch: bytes of device scratch map_records_device needs."""
+    return int(capi.load().aim_map_records_scratch(int(n_reads)))
+
+
+def map_records_device(K, n_reads, d_seg, d_sam, d_class, d_rec_offsets, d_records, d_scratch, scratch_bytes, stream=None):
+    """aim_map_records_device on device pointers (integers, e.g. torch's data_ptr(); None = NULL): rule 12c over the aim_segment_t rows of
+    split_segments_device / extend_segments_device, the aim_sam_t rows of sam_device_split (d_sel = None) and chain_classify_device's
+    d_class -> d_rec_offsets (uint32[n_reads + 1]) and the dense aim_map_record_t list in d_records (room for n_reads * K).
+    Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_map_records_device(int(K), int(n_reads), d_seg, d_sam, d_class, d_rec_offsets, d_records, d_scratch, int(scratch_bytes), stream))
+
+
+def mapper_params(sp, max_reads, max_score, mismatch=3, gap_o=4, gap_e=1, match=0, max_hits=0, mask_q8=capi.CHAIN_MASK_DEFAULT, extend=None, sam_options=0,
+                  slots=2, cigar_cap=None, md_cap=None):
+    """aim_mapper_params_t from the seed parameters of seed_params(..., w=...) (K is sp.max_cands, read_size sp.read_size), the batch
+    size, and the WFA penalties and cap of the segment alignment. extend: extend_params() to run the segment extension (MAP_EXTEND), or
+    None. cigar_cap / md_cap default to 64 words and 256 bytes per slot row. The library checks every bound."""
+    K = int(sp.max_cands)
+    ep = extend if extend is not None else capi.ExtendParams()
+    return capi.MapperParams(sp, int(max_hits), int(mask_q8), ep, capi.MAP_EXTEND if extend is not None else 0, int(match), int(mismatch), int(gap_o),
+                             int(gap_e), int(max_score), int(sam_options), int(max_reads), int(slots),
+                             int(max_reads * K * 64 if cigar_cap is None else cigar_cap), int(max_reads * K * 256 if md_cap is None else md_cap))
+
+
+def mapper_device_bytes(mp, ref_len):
+    """aim_mapper_device_bytes: the device memory a Mapper of these parameters takes at its peak."""
+    b = C.c_uint64()
+    capi.check(capi.load().aim_mapper_device_bytes(C.byref(mp), int(ref_len), C.byref(b)))
+    return b.value
+
+
+class Mapper:
+    """aim_mapper_t: the reference, its minimizer index and per-slot buffers and streams on one device. submit(slot, read_len, reads)
+    copies a batch in and enqueues every stage; wait(slot) returns a dict of numpy views of the slot's pinned buffers -- "records"
+    (capi.MAP_RECORD_DTYPE), "rec_offsets" (uint32[n_reads + 1]), "cigar" (uint32 words) and "md" (uint8) -- which stay valid until the
+    slot's next submit, plus "cigar_needed" / "md_needed"."""
+
+    def __init__(self, mp, reference, device=0):
+        self.lib = capi.load()
+        self.params = mp
+        ref = np.ascontiguousarray(np.frombuffer(reference, dtype=np.uint8) if isinstance(reference, (bytes, bytearray)) else reference, dtype=np.uint8)
+        self.ref_len = len(ref)
+        self.handle = C.c_void_p()
+        capi.check(self.lib.aim_mapper_create(C.byref(mp), int(device), capi.ptr(ref) if len(ref) else None, len(ref), C.byref(self.handle)))
+
+    def close(self):
+        if self.handle:
+            self.lib.aim_mapper_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def submit(self, slot, read_len, reads):
+        rl = np.ascontiguousarray(read_len, dtype=np.int32)
+        rows = np.ascontiguousarray(reads, dtype=np.uint8)
+        rs = self.params.seed.read_size
+        if rows.size != len(rl) * rs:
+            raise ValueError("reads must be uint8[%d][%d], got %r" % (len(rl), rs, rows.shape))
+        capi.check(self.lib.aim_mapper_submit(self.handle, int(slot), len(rl), capi.ptr(rl) if len(rl) else None, capi.ptr(rows) if len(rl) else None))
+
+    def wait(self, slot):
+        out = capi.MapperOut()
+        capi.check(self.lib.aim_mapper_wait(self.handle, int(slot), C.byref(out)))
+
+        def view(addr, count, dtype):
+            if not count:
+                return np.zeros(0, dtype=dtype)
+            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(addr)
+            return np.frombuffer(buf, dtype=dtype)
+        return {"n_reads": out.n_reads, "records": view(out.records, out.n_records, capi.MAP_RECORD_DTYPE),
+                "rec_offsets": view(out.rec_offsets, out.n_reads + 1, np.uint32), "cigar": view(out.cigar, out.cigar_words, np.uint32),
+                "md": view(out.md, out.md_bytes, np.uint8), "cigar_needed": out.cigar_needed, "md_needed": out.md_needed}
+
+
 def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0", chain=False, max_hits=None):
     """The seeding kernel on torch device buffers. `index` is build_index's (bucket, pos) -- numpy arrays, or uint8 torch tensors
     that already live on the device (as the "d_bucket" / "d_pos" of an earlier call); read_len is int32[n_reads], reads the ASCII

@@ -1,0 +1,176 @@
+"""python -m aim_amd.map --ref REF.fa --reads READS.fq|.fa -o OUT.sam
+
+Maps single-end reads against a reference of ONE sequence with engine.Mapper (chain -> classify -> split -> [extend] -> align -> SAM
+records -> record list, all on the device) and writes SAM with aim_amd.samout. Two slots are driven alternately: while one batch is
+on the device the previous one is written. Bases are upper-cased on the way in (the index holds upper-case A C G T only). A FASTA with
+more than one sequence is refused: a contig table is a separate piece of work."""
+import argparse
+import sys
+
+import numpy as np
+
+
+def read_fasta(path):
+    """[(name, sequence bytes)] of a FASTA file; the name is the header up to the first white space."""
+    out, name, parts = [], None, []
+    with open(path, "rb") as f:
+        for line in f:
+            line = line.strip()
+            if not line:
+                continue
+            if line.startswith(b">"):
+                if name is not None:
+                    out.append((name, b"".join(parts)))
+                head = line[1:].split()
+                name, parts = (head[0].decode("latin-1") if head else ""), []
+            elif name is None:
+                raise ValueError("%s: sequence data before the first '>' line" % path)
+            else:
+                parts.append(line)
+    if name is not None:
+        out.append((name, b"".join(parts)))
+    return out
+
+
+def read_fastq(path):
+    """[(name, sequence bytes, quality string)] of a four-line-per-record FASTQ file."""
+    out = []
+    with open(path, "rb") as f:
+        lines = [l.rstrip(b"\r\n") for l in f]
+    while lines and not lines[-1]:
+        lines.pop()
+    if len(lines) % 4:
+        raise ValueError("%s: %d lines are no whole number of four-line FASTQ records" % (path, len(lines)))
+    for i in range(0, len(lines), 4):
+        h, s, p, q = lines[i:i + 4]
+        if not h.startswith(b"@") or not p.startswith(b"+"):
+            raise ValueError("%s: record %d does not start with '@' and '+' lines" % (path, i // 4))
+        if len(q) != len(s):
+            raise ValueError("%s: record %d has %d bases and %d qualities" % (path, i // 4, len(s), len(q)))
+        head = h[1:].split()
+        out.append((head[0].decode("latin-1") if head else "", s, q.decode("latin-1")))
+    return out
+
+
+def read_reads(path):
+    """FASTQ or FASTA by the file's first byte: [(name, sequence bytes, quality string or None)]."""
+    with open(path, "rb") as f:
+        first = f.read(1)
+    if first == b"@":
+        return read_fastq(path)
+    if first == b">":
+        return [(n, s, None) for n, s in read_fasta(path)]
+    if not first:
+        return []
+    raise ValueError("%s: neither FASTA ('>') nor FASTQ ('@')" % path)
+
+
+def load_reference(path):
+    """(name, upper-cased uint8 array) of a FASTA with exactly one sequence; ValueError for none or several."""
+    seqs = read_fasta(path)
+    if len(seqs) != 1:
+        raise ValueError("%s holds %d sequences: the mapper takes a reference of one sequence (a contig table is not in this version)" % (path, len(seqs)))
+    return seqs[0][0], np.frombuffer(seqs[0][1].upper(), dtype=np.uint8).copy()
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog="python -m aim_amd.map", description=__doc__.split("\n\n")[1])
+    ap.add_argument("--ref", required=True)
+    ap.add_argument("--reads", required=True)
+    ap.add_argument("-o", "--out", required=True)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--batch", type=int, default=4096, help="reads per batch (max_reads)")
+    ap.add_argument("--read-size", type=int, default=None, help="row size, a multiple of 8 (default: the longest read rounded up)")
+    ap.add_argument("-k", type=int, default=12)
+    ap.add_argument("-w", type=int, default=5, help="minimizer window")
+    ap.add_argument("--max-occ", type=int, default=16)
+    ap.add_argument("--band", type=int, default=64)
+    ap.add_argument("--flank", type=int, default=8)
+    ap.add_argument("--min-votes", type=int, default=2)
+    ap.add_argument("--max-cands", type=int, default=4, help="K")
+    ap.add_argument("--max-hits", type=int, default=None, help="0: the short-read chain kernel; else the long kernel's hit cap (default by read size)")
+    ap.add_argument("--mask-q8", type=int, default=128)
+    ap.add_argument("--extend", action="store_true", help="extend the inner sides of split segments to the breakpoint")
+    ap.add_argument("--ext-match", type=int, default=1)
+    ap.add_argument("--ext-mismatch", type=int, default=3)
+    ap.add_argument("--ext-gap-o", type=int, default=4)
+    ap.add_argument("--ext-gap-e", type=int, default=1)
+    ap.add_argument("--xdrop", type=int, default=20)
+    ap.add_argument("--ext-max-cost", type=int, default=400)
+    ap.add_argument("--ext-band", type=int, default=31)
+    ap.add_argument("--max-ext", type=int, default=64)
+    ap.add_argument("--mismatch", type=int, default=3)
+    ap.add_argument("--gap-o", type=int, default=4)
+    ap.add_argument("--gap-e", type=int, default=1)
+    ap.add_argument("--max-score", type=int, default=None, help="WFA cost cap of a segment (default: max(32, read_size / 10))")
+    ap.add_argument("--eqx", action="store_true", help="'=' and 'X' instead of 'M'")
+    ap.add_argument("--cigar-cap", type=int, default=None)
+    ap.add_argument("--md-cap", type=int, default=None)
+    return ap
+
+
+def mapper_params_from(args, read_size):
+    from . import capi, engine
+    long_reads = read_size > capi.SEED_MAX_READ_SIZE
+    max_hits = args.max_hits if args.max_hits is not None else (4096 if long_reads else 0)
+    sp = engine.seed_params(args.k, read_size, max_occ=args.max_occ, band=args.band, flank=args.flank, min_votes=args.min_votes, max_cands=args.max_cands,
+                            w=args.w, long_reads=max_hits != 0)
+    ep = engine.extend_params(args.ext_match, args.ext_mismatch, args.ext_gap_o, args.ext_gap_e, args.xdrop, args.ext_max_cost, args.ext_band,
+                              args.max_ext) if args.extend else None
+    max_score = args.max_score if args.max_score is not None else max(32, read_size // 10)
+    return engine.mapper_params(sp, args.batch, max_score, mismatch=args.mismatch, gap_o=args.gap_o, gap_e=args.gap_e, max_hits=max_hits, mask_q8=args.mask_q8,
+                                extend=ep, sam_options=capi.SAM_EQX if args.eqx else 0, slots=2, cigar_cap=args.cigar_cap, md_cap=args.md_cap)
+
+
+def main(argv=None):
+    args = parser().parse_args(argv)
+    try:
+        rname, ref = load_reference(args.ref)
+        reads = read_reads(args.reads)
+    except (OSError, ValueError) as e:
+        print("aim_amd.map: %s" % e, file=sys.stderr)
+        return 2
+    from . import engine, samout
+    longest = max([len(s) for _, s, _ in reads] + [1])
+    read_size = args.read_size if args.read_size is not None else engine.round_up_8(longest)
+    if longest > read_size:
+        print("aim_amd.map: a read of %d bases does not fit --read-size %d" % (longest, read_size), file=sys.stderr)
+        return 2
+    try:
+        mp = mapper_params_from(args, read_size)
+    except ValueError as e:
+        print("aim_amd.map: %s" % e, file=sys.stderr)
+        return 2
+    n_lines = 0
+    with open(args.out, "w") as fh, engine.Mapper(mp, ref, device=args.device) as m:
+        fh.write(samout.header(rname, len(ref), command_line=" ".join(["python -m aim_amd.map"] + list(sys.argv[1:] if argv is None else argv))))
+        pending = {}                                  # slot -> the batch in flight on it
+
+        def finish(slot):
+            nonlocal n_lines
+            names, rows, rl, quals = pending.pop(slot)
+            out = m.wait(slot)
+            if out["cigar_needed"] > mp.cigar_cap or out["md_needed"] > mp.md_cap:
+                print("aim_amd.map: a batch needed %d CIGAR words and %d MD bytes: records over --cigar-cap %d / --md-cap %d have no CIGAR" %
+                      (out["cigar_needed"], out["md_needed"], mp.cigar_cap, mp.md_cap), file=sys.stderr)
+            n_lines += samout.write(fh, out, names, rows, rl, rname, quals)
+        for b, lo in enumerate(range(0, len(reads), args.batch)):
+            part = reads[lo:lo + args.batch]
+            slot = b & 1                              # (free: its previous batch was written while the last one ran)
+            rows = np.zeros((len(part), read_size), dtype=np.uint8)
+            rl = np.zeros(len(part), dtype=np.int32)
+            for i, (_, s, _) in enumerate(part):
+                rows[i, :len(s)] = np.frombuffer(s.upper(), dtype=np.uint8)
+                rl[i] = len(s)
+            m.submit(slot, rl, rows)
+            pending[slot] = ([n for n, _, _ in part], rows, rl, [q for _, _, q in part])
+            if (slot ^ 1) in pending:                 # the older batch: written while this one runs
+                finish(slot ^ 1)
+        for slot in list(pending):                    # the last batch
+            finish(slot)
+    print("aim_amd.map: %d reads, %d SAM lines -> %s" % (len(reads), n_lines, args.out), file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,78 @@
+"""SAM text from the mapper's records (engine.Mapper.wait, rule 12c of include/aim_hip.h). Pure Python over numpy views; the one call
+into the library is the CIGAR formatter aim_sam_format_cigar.
+
+One line per record, in record order. Every line of a read carries the read's full SEQ (reverse-complemented on strand 1) with soft
+clips, as `minimap2 -Y` writes supplementary lines: there are no hard clips. Tags: NM:i, MD:Z, AS:i and, on reads with more than one
+record, SA:Z. AS is the negated alignment cost (the library's scores are penalties: 0 is a perfect match), so a greater AS is a better
+alignment. MAPQ is the record's own: the chain MAPQ of rule 8c, this project's figure."""
+import numpy as np
+
+from . import capi, engine
+
+_COMP = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+
+
+def revcomp(seq):
+    """Reverse complement of bytes: A<->T, C<->G in either case, every other byte kept."""
+    return bytes(seq).translate(_COMP)[::-1]
+
+
+def header(rname, ref_len, command_line=None, version="1"):
+    """@HD / @SQ / @PG for a reference of one sequence."""
+    pg = "@PG\tID:aim_amd\tPN:aim_amd\tVN:%s" % version
+    if command_line:
+        pg += "\tCL:" + command_line
+    return "@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:%s\tLN:%d\n%s\n" % (rname, int(ref_len), pg)
+
+
+def _cigar(rec, cigar):
+    s = rec["sam"]
+    if int(s["status"]) & capi.SAM_OVERFLOW or not int(s["n_cigar"]):
+        return "*"
+    o = int(s["cigar_offset"])
+    return engine.sam_format_cigar(cigar[o:o + int(s["n_cigar"])])
+
+
+def _sa(rname, rec, cigar):
+    s = rec["sam"]
+    return "%s,%d,%s,%s,%d,%d;" % (rname, int(s["pos"]) + 1, "-" if int(s["flags"]) & capi.SAM_REVERSE else "+", _cigar(rec, cigar), int(rec["mapq"]), int(s["nm"]))
+
+
+def record_lines(out, names, reads, read_len, rname, quals=None):
+    """The SAM lines (without newlines) of one mapper result `out` (the dict of Mapper.wait, or anything with "records", "rec_offsets",
+    "cigar" and "md"). names[r] is read r's QNAME, reads[r] its row of bases (bytes or a uint8 row), read_len[r] its length and
+    quals[r] (optional) its quality string."""
+    recs, off, cigar, md = out["records"], out["rec_offsets"], out["cigar"], np.asarray(out["md"], dtype=np.uint8)
+    lines = []
+    for r in range(len(off) - 1):
+        group = recs[int(off[r]):int(off[r + 1])]
+        L = int(read_len[r])
+        seq = bytes(reads[r][:L]) if isinstance(reads[r], (bytes, bytearray)) else np.asarray(reads[r], dtype=np.uint8)[:L].tobytes()
+        qual = quals[r] if quals is not None and quals[r] is not None else None
+        # in an SA tag the non-supplementary line comes first, then the others in rank order
+        sa_order = sorted(range(len(group)), key=lambda j: (bool(int(group[j]["sam"]["flags"]) & capi.SAM_SUPPLEMENTARY), int(group[j]["rank"])))
+        for j, rec in enumerate(group):
+            s = rec["sam"]
+            flags = int(s["flags"])
+            if flags & capi.SAM_UNMAPPED:
+                lines.append("\t".join([names[r], "4", "*", "0", "0", "*", "*", "0", "0", seq.decode("latin-1") or "*", qual or "*"]))
+                continue
+            rev = bool(flags & capi.SAM_REVERSE)
+            fields = [names[r], str(flags), rname, str(int(s["pos"]) + 1), str(int(rec["mapq"])), _cigar(rec, cigar), "*", "0", "0",
+                      (revcomp(seq) if rev else seq).decode("latin-1") or "*", (qual[::-1] if rev else qual) if qual else "*", "NM:i:%d" % int(s["nm"])]
+            if int(s["md_len"]) and not int(s["status"]) & capi.SAM_OVERFLOW:
+                o = int(s["md_offset"])
+                fields.append("MD:Z:" + md[o:o + int(s["md_len"])].tobytes().decode("latin-1"))
+            fields.append("AS:i:%d" % -int(s["score"]))
+            if len(group) > 1:
+                fields.append("SA:Z:" + "".join(_sa(rname, group[k], cigar) for k in sa_order if k != j))
+            lines.append("\t".join(fields))
+    return lines
+
+
+def write(fh, out, names, reads, read_len, rname, quals=None):
+    """record_lines, written to the text file `fh`; returns the number of lines."""
+    lines = record_lines(out, names, reads, read_len, rname, quals)
+    for line in lines:
+        fh.write(line + "\n")
+    return len(lines)

@@ -347,6 +347,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_CHAIN_CLASS 0x10000u /* primary / secondary chains and MAPQ: aim_chain_classify_device / aim_read_mapq_device / aim_chain_class_kernel_names exist */
 #define AIM_FEATURE_SPLIT 0x20000u /* split reads: aim_split_segments_device / aim_sam_device_split / aim_split_kernel_names exist */
 #define AIM_FEATURE_EXTEND 0x40000u /* segment extension: aim_extend_segments_device / aim_extend_kernel_names exist */
+#define AIM_FEATURE_MAPPER 0x80000u /* rule 12c and the mapper object: aim_map_records_device / aim_mapper_create / aim_mapper_submit / aim_mapper_wait exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -978,8 +979,8 @@ const char *aim_chain_class_kernel_names(void);
  * AIM_SEED_LONG_MAX_READ_SIZE, n_reads * K >= 2^32), flank < 0, a ref_len above AIM_SEED_MAX_REF_LEN and, last of all, a NULL device
  * buffer. aim_sam_device_split refuses what aim_sam_device refuses, and a NULL d_seg with n_rows > 0.
  * Not in this version: a split stage inside aim_set_submit or the host CLI, the SA tag and hard clips, packed read rows, segments
- * from the voting kernel's clusters, MAPQ per segment (a caller joins d_class[slot].mapq); overlap between neighbouring extended
- * segments (rule 11c) is not trimmed. Check aim_features() & AIM_FEATURE_SPLIT first. */
+ * from the voting kernel's clusters, MAPQ per segment in aim_sam_t (rule 12c's record carries d_class[slot].mapq); overlap between
+ * neighbouring extended segments (rule 11c) is not trimmed. aim_mapper_t (below) runs these stages in order. Check aim_features() & AIM_FEATURE_SPLIT first. */
 #define AIM_SEG_VALID 0x1u
 #define AIM_SEG_SUPPLEMENTARY 0x2u
 #define AIM_SEG_LEFT_OPEN 0x4u
@@ -1048,8 +1049,8 @@ const char *aim_split_kernel_names(void);
  * d_reference holds ref_len bytes. AIM_EINVAL with a message under the entry point's name, before any device query, in this order:
  * the K, read_size and n_reads * K refusals of aim_split_segments_device, a NULL p and each parameter bound in the order above, a
  * ref_len above AIM_SEED_MAX_REF_LEN and, last of all, a NULL device buffer.
- * Not in this version: a stage inside aim_set_submit or the host CLI, trimming the overlap of neighbouring extended segments, the SA
- * tag, a band above 31, max_ext above 1024, extending open sides, Z-drop. Check aim_features() & AIM_FEATURE_EXTEND first. */
+ * Not in this version: a stage inside aim_set_submit or host.c (aim_mapper_t below runs it), trimming the overlap of neighbouring
+ * extended segments, a band above 31, max_ext above 1024, extending open sides, Z-drop. Check aim_features() & AIM_FEATURE_EXTEND first. */
 #define AIM_SEG_EXT_LEFT 0x20u
 #define AIM_SEG_EXT_RIGHT 0x40u
 #define AIM_EXTEND_MAX_UNIT 64
@@ -1072,6 +1073,116 @@ int aim_extend_segments_device(const aim_extend_params_t *p, uint32_t K, uint32_
                                aim_extend_t *d_ext /* [n_reads * K] */, void *hip_stream);
 /* "extend_sides_kernel,extend_apply_kernel": comma-separated rocprofv3 kernel-trace name prefixes of the entry point's kernels. */
 const char *aim_extend_kernel_names(void);
+
+/* ---- the mapper (AIM_FEATURE_MAPPER): reads in, a dense list of SAM-ready records per read out -------------------------------
+ * The split path above ends in n_reads * K slot-shaped rows, most of them empty or secondary, without MAPQ and without a word on
+ * which rows belong to one read. Rule 12c turns them into the list a SAM writer walks, and aim_mapper_t runs the whole sequence
+ *     chain -> aim_chain_classify_device -> aim_split_segments_device -> [aim_extend_segments_device] -> aim_align_device_ref ->
+ *     aim_sam_device_split -> aim_map_records_device
+ * on buffers it owns, one stream per slot, and sends back exactly the records, their offsets and the CIGAR words and MD bytes in use.
+ *   12c. Records (aim_map_records_device). d_seg, d_sam (the rows of aim_sam_device_split with d_sel = NULL) and d_class are indexed by
+ *       slot = r * K + i. Everything is deterministic and independent of the grid and of the AIM_DEBUG_POISON_* knobs.
+ *       Mapped slot. Slot r * K + i is mapped when d_seg[slot].flags & AIM_SEG_VALID is set and d_sam[slot].flags & AIM_SAM_UNMAPPED
+ *       is not. A row with AIM_SAM_OVERFLOW in its status counts as mapped: the status says why it has no words.
+ *       Count. c_r is the number of mapped slots of read r, or 1 if there are none. d_rec_offsets[n_reads + 1] is the exclusive prefix
+ *       sum of c_r, so d_rec_offsets[n_reads] is the number of records; the records of read r are
+ *       d_records[d_rec_offsets[r], d_rec_offsets[r + 1]). There are at most n_reads * K records.
+ *       Order. The mapped slots of a read are sorted by (q_begin, i) ascending -- the order of the segments along the read as given;
+ *       rank is a slot's position in that order, and its record is d_records[d_rec_offsets[r] + rank].
+ *       Representative. The mapped slot of lowest i loses AIM_SAM_SUPPLEMENTARY if it has it, every other mapped slot gains it: a
+ *       mapped read has exactly one non-supplementary line, also when candidate 0 came back over the cap.
+ *       Record. aim_map_record_t, 64 bytes: sam is the slot's aim_sam_t verbatim except for the flag change above (cigar_offset and
+ *       md_offset still address the buffers aim_sam_device_split wrote); read = r; q_begin, q_end and seg_flags are d_seg[slot]'s;
+ *       mapq = d_class[slot].mapq; rank as above; n_records = c_r; slot = r * K + i.
+ *       MAPQ. The record's mapq is rule 8c's chain MAPQ of that primary. That is this project's own rule: it comes from the chains
+ *       alone, not from the alignment scores, and it is not minimap2's or BWA's figure.
+ *       Unmapped read. A read without a mapped slot gets one record: d_sam[r * K] with flags = AIM_SAM_UNMAPPED and pos, ref_span, nm,
+ *       n_cigar, md_len, cigar_offset and md_offset zero; idx, score, status and pad are kept; read = r, slot = r * K, n_records = 1
+ *       and q_begin, q_end, mapq, seg_flags and rank zero.
+ *   aim_map_records_device only enqueues work on hip_stream: map_count_kernel, the three launches of the index's scan over
+ *       d_rec_offsets, map_records_kernel (csrc/mapper.hpp). It allocates nothing; d_scratch holds aim_map_records_scratch(n_reads)
+ *       bytes (the scan's part sums) and may be reused once the stream has passed. Where a record lands depends on the prefix sums
+ *       alone: no atomic is involved and no workgroup waits for another. d_sam and d_records are 16-byte aligned, d_seg and d_class
+ *       8-byte, d_rec_offsets and d_scratch 4-byte. n_reads = 0 writes d_rec_offsets[0] = 0 and nothing else.
+ *       AIM_EINVAL with a message under the entry point's name, before any device query: K outside 1..AIM_SEED_MAX_CANDS,
+ *       n_reads * K >= 2^32, a NULL d_rec_offsets, a NULL device buffer with n_reads > 0, a d_sam or d_records that is not 16-byte
+ *       aligned and a scratch_bytes below aim_map_records_scratch.
+ *   aim_mapper_t. aim_mapper_params_t carries every stage's parameters: seed (options must be AIM_SEED_OPT_MINIMIZERS(w); K is
+ *       max_cands and read_size its read_size), max_hits (0: aim_seed_chain_device, which needs read_size <= AIM_SEED_MAX_READ_SIZE;
+ *       otherwise the H of aim_seed_chain_long_device), mask_q8, extend and the option bit AIM_MAP_EXTEND that runs rule 11c, the WFA
+ *       penalties and max_score of the segment alignment (the mapper sets AIM_FLAG_BACKTRACE | AIM_FLAG_ENDSFREE | AIM_FLAG_REF_TEXTS
+ *       itself, with text free ends of 2 * flank), sam_options, and the sizes: max_reads per batch, slots (1..AIM_MAPPER_MAX_SLOTS),
+ *       cigar_cap words and md_cap bytes per slot.
+ *       aim_mapper_device_bytes reports the device memory aim_mapper_create takes at its peak (the index build's scratch included,
+ *       which is released before create returns). It and aim_mapper_create refuse, with a message under their own name and before any
+ *       device query, in this order: a NULL argument; the seed parameters (aim_seed_chain_device's bounds, or
+ *       aim_seed_chain_long_device's with max_hits != 0; minimizers are required); mask_q8 outside 1..256; max_reads * K >= 2^32; a
+ *       ref_len above AIM_SEED_MAX_REF_LEN; with AIM_MAP_EXTEND the bounds of aim_extend_params_t; the alignment's parameter rules
+ *       (the penalty rule of AIM_FLAG_ENDSFREE among them); sam_options other than AIM_SAM_EQX;
+ *       max_reads * K * (4 * read_size + 10) >= 2^32; unknown option bits, max_reads = 0, slots outside 1..AIM_MAPPER_MAX_SLOTS.
+ *       aim_mapper_create(params, device, seq, ref_len, &m) uploads the reference with its 16-byte slack, builds the minimizer index
+ *       with aim_index_build_device_minimizers, allocates every per-slot device buffer and pinned host buffer once and creates one
+ *       stream per slot. aim_mapper_submit(m, slot, n_reads, read_len, reads) copies read_len[n_reads] and the ASCII rows
+ *       reads[n_reads][read_size] into the slot's pinned buffers and then only enqueues work: the copies and the stages in the order
+ *       above (rule 11c only with AIM_MAP_EXTEND). AIM_EINVAL for n_reads > max_reads or a NULL array with n_reads > 0, AIM_ESTATE for
+ *       a slot that is still in flight. aim_mapper_wait(m, slot, &out) first makes one small copy -- the record count and the two
+ *       cursors -- and then copies exactly records[n_records], rec_offsets[n_reads + 1], cigar[cigar_words] and md[md_bytes]; out's
+ *       pointers are views of the slot's pinned buffers and stay valid until the slot's next submit. AIM_ESTATE when nothing is in
+ *       flight on the slot.
+ *       Capacity. A batch that needed more than cigar_cap words or md_cap bytes still succeeds: cigar_needed / md_needed carry what
+ *       it needed, cigar_words / md_bytes what was copied (the smaller of need and capacity), and the affected records carry
+ *       AIM_SAM_OVERFLOW. n_reads = 0 is a valid batch: no records, rec_offsets = {0}.
+ *       The slots are independent: batches on different slots overlap, and a slot's result does not depend on what ran before it.
+ * aim_mapper_kernel_names: "map_count_kernel,map_records_kernel".
+ * Not in this version: a mapper stage inside aim_set_submit or host.c, more than one device per mapper, references of more than one
+ * sequence (a contig table), paired-end reads through the mapper, hard clips, trimming the overlap of neighbouring segments, packed
+ * read rows, MAPQ from alignment runner-ups. The SA tag is text and is written on the host (aim_amd/samout.py) from the records of a
+ * read. Check aim_features() & AIM_FEATURE_MAPPER first. */
+typedef struct aim_map_record {
+    aim_sam_t sam;                 /* the slot's row; flags with rule 12c's supplementary bit */
+    uint32_t read;                 /* r */
+    uint16_t q_begin, q_end;       /* the segment's interval of the read as given */
+    uint8_t mapq;                  /* the chain MAPQ of this primary (rule 8c) */
+    uint8_t seg_flags;             /* AIM_SEG_* */
+    uint8_t rank;                  /* position among the read's records */
+    uint8_t n_records;             /* c_r */
+    uint32_t slot;                 /* r * K + i */
+} aim_map_record_t;    /* 64 B per record */
+size_t aim_map_records_scratch(uint32_t n_reads);
+int aim_map_records_device(uint32_t K, uint32_t n_reads, const aim_segment_t *d_seg, const aim_sam_t *d_sam, const aim_chain_class_t *d_class,
+                           uint32_t *d_rec_offsets /* [n_reads + 1] */, aim_map_record_t *d_records /* [n_reads * K] */, void *d_scratch,
+                           size_t scratch_bytes, void *hip_stream);
+/* Comma-separated rocprofv3 kernel-trace name prefixes of the two kernels rule 12c adds. */
+const char *aim_mapper_kernel_names(void);
+#define AIM_MAP_EXTEND 0x1u        /* aim_mapper_params_t.options: run aim_extend_segments_device between split and alignment */
+#define AIM_MAPPER_MAX_SLOTS 4
+typedef struct aim_mapper_params {
+    aim_seed_params_t seed;
+    uint32_t max_hits;             /* 0: aim_seed_chain_device; otherwise the H of aim_seed_chain_long_device */
+    uint32_t mask_q8;              /* rule 8c; AIM_CHAIN_MASK_DEFAULT */
+    aim_extend_params_t extend;    /* read with AIM_MAP_EXTEND only */
+    uint32_t options;              /* AIM_MAP_EXTEND */
+    int32_t match, mismatch, gap_o, gap_e, max_score;   /* the WFA segment alignment */
+    uint32_t sam_options;          /* AIM_SAM_EQX */
+    uint32_t max_reads;            /* reads per batch */
+    uint32_t slots;                /* 1..AIM_MAPPER_MAX_SLOTS */
+    uint32_t cigar_cap, md_cap;    /* CIGAR words and MD bytes per slot */
+} aim_mapper_params_t; /* 124 B */
+typedef struct aim_mapper aim_mapper_t;
+typedef struct aim_mapper_out {
+    uint32_t n_reads, n_records;
+    uint32_t cigar_words, md_bytes;      /* copied: min(needed, capacity) */
+    uint32_t cigar_needed, md_needed;    /* what the batch needed */
+    const aim_map_record_t *records;     /* [n_records] */
+    const uint32_t *rec_offsets;         /* [n_reads + 1] */
+    const uint32_t *cigar;               /* [cigar_words] */
+    const char *md;                      /* [md_bytes] */
+} aim_mapper_out_t;
+int aim_mapper_device_bytes(const aim_mapper_params_t *params, uint64_t ref_len, uint64_t *bytes);
+int aim_mapper_create(const aim_mapper_params_t *params, int device, const char *seq, uint64_t ref_len, aim_mapper_t **mapper);
+int aim_mapper_submit(aim_mapper_t *mapper, uint32_t slot, uint32_t n_reads, const int32_t *read_len, const char *reads);
+int aim_mapper_wait(aim_mapper_t *mapper, uint32_t slot, aim_mapper_out_t *out);
+int aim_mapper_free(aim_mapper_t *mapper);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
