@@ -62,6 +62,14 @@ EXTEND_MAX_UNIT, EXTEND_MAX_COST, EXTEND_MAX_BAND, EXTEND_MAX_EXT = 64, 4095, 31
 FEATURE_MAPPER = 0x80000          # aim_features(): aim_map_records_device / aim_mapper_* exist
 MAP_EXTEND = 0x1                  # aim_mapper_params_t.options: run the segment extension (rule 11c)
 MAPPER_MAX_SLOTS = 4
+FEATURE_CONTIGS = 0x100000        # aim_features(): aim_contigs_* / aim_contig_clip_device / aim_map_records_contigs_device / aim_mapper_create_contigs exist
+CONTIG_MAX, CONTIG_NONE = 1 << 20, 0xFFFFFFFF
+SEG_CONTIG_CLIPPED = 0x80         # aim_segment_t.flags, from aim_contig_clip_device
+
+
+def CONTIG_SPACER(band):
+    """AIM_CONTIG_SPACER(band): the 'N' bases aim_mapper_create_contigs puts between two contigs."""
+    return int(band) + 64
 
 
 def SEED_OPT_MINIMIZERS(w):
@@ -305,6 +313,14 @@ SYMBOLS = {
     "aim_mapper_submit": (C.c_int, [_VP, _U32, _U32, _VP, _VP]),
     "aim_mapper_wait": (C.c_int, [_VP, _U32, C.POINTER(MapperOut)]),
     "aim_mapper_free": (C.c_int, [_VP]),
+    "aim_contigs_layout": (C.c_int, [_U32, _VP, _U32, _VP, C.POINTER(C.c_uint64)]),
+    "aim_contigs_concat": (C.c_int, [_U32, _VP, _VP, _U32, _VP]),
+    "aim_contig_clip_device": (C.c_int, [_U32, _U32, _I32, C.c_uint64, _U32, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "aim_map_records_contigs_device": (C.c_int, [_U32, _U32, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "aim_contig_kernel_names": (C.c_char_p, []),
+    "aim_mapper_device_bytes_contigs": (C.c_int, [C.POINTER(MapperParams), _U32, _VP, C.POINTER(C.c_uint64)]),
+    "aim_mapper_create_contigs": (C.c_int, [C.POINTER(MapperParams), C.c_int, _U32, _VP, _VP, C.POINTER(_VP)]),
+    "aim_mapper_contigs": (C.c_int, [_VP, C.POINTER(_U32), C.POINTER(_VP), C.POINTER(_VP)]),
 }
 
 _lib = None

@@ -1,6 +1,8 @@
 // capi_mapper.hip -- the top layer of the read-mapping pipeline (include/aim_hip.h, AIM_FEATURE_MAPPER): rule 12c's entry point
 // aim_map_records_device (kernels in mapper.hpp, the prefix sums by index.hpp's scan) and aim_mapper_t, which owns the reference, the
 // index and per-slot buffers and streams and runs the stages of capi_pipeline.hip and aim_capi.hip through their public entry points.
+// Rule 13c (AIM_FEATURE_CONTIGS) lives here too: the contig layout, aim_contig_clip_device (kernel in contig.hpp),
+// aim_map_records_contigs_device and the mapper of a reference of several sequences.
 // Host code only. What this unit shares with the others is in capi_common.hpp.
 #include <algorithm>
 #include <cstdio>
@@ -9,6 +11,7 @@
 #include <vector>
 
 #include "capi_common.hpp"
+#include "contig.hpp"
 #include "index.hpp"
 #include "mapper.hpp"
 
@@ -67,9 +70,37 @@ int check_mapper_params(const char *fn, const aim_mapper_params_t *p, uint64_t r
     return AIM_OK;
 }
 
+// Rule 13c's layout and its bounds, under the name `fn`: starts (when asked for) and ref_len.
+int contigs_layout(const char *fn, uint32_t n, const uint32_t *lens, uint32_t spacer, uint32_t *starts, uint64_t *ref_len)
+{
+    if (n < 1 || n > AIM_CONTIG_MAX) return fail(AIM_EINVAL, "%s: n_contigs %u is outside 1..%u", fn, n, AIM_CONTIG_MAX);
+    if (!lens) return fail(AIM_EINVAL, "%s: lens is NULL", fn);
+    if (spacer < 1) return fail(AIM_EINVAL, "%s: spacer %u must be >= 1", fn, spacer);
+    uint64_t at = 0;
+    for (uint32_t c = 0; c < n; ++c) {
+        if (!lens[c]) return fail(AIM_EINVAL, "%s: lens[%u] is 0 (a contig holds at least one base)", fn, c);
+        if (c) at += spacer;
+        if (at + lens[c] > AIM_SEED_MAX_REF_LEN)
+            return fail(AIM_EINVAL, "%s: contig %u ends at %llu: ref_len is above %llu", fn, c, (unsigned long long)(at + lens[c]), (unsigned long long)AIM_SEED_MAX_REF_LEN);
+        if (starts) starts[c] = (uint32_t)at;
+        at += lens[c];
+    }
+    if (ref_len) *ref_len = at;
+    return AIM_OK;
+}
+
+void contigs_concat(uint32_t n, const char *const *seqs, const uint32_t *lens, const uint32_t *starts, uint64_t ref_len, char *out)
+{
+    memset(out, 'N', (size_t)ref_len);
+    for (uint32_t c = 0; c < n; ++c) memcpy(out + starts[c], seqs[c], lens[c]);
+}
+
+// The spacer of the mapper: the band as far as any chain kernel takes one (a band outside its bounds is refused by the mapper's checks).
+uint32_t mapper_spacer(const aim_mapper_params_t &p) { return AIM_CONTIG_SPACER(std::min(std::max(p.seed.band, 0), AIM_SEED_CHAIN_MAX_BAND)); }
+
 // The device buffers of one slot, in allocation order: `bytes` each, carved out of one allocation at multiples of 256.
 enum Buf { B_READS, B_READ_LEN, B_REQ, B_TEXT_POS, B_VOTES, B_SEED, B_CHAINS, B_CLASS, B_SEG_REQ, B_SEG_TEXT_POS, B_SEG_PATTERNS, B_SEG, B_EXT,
-           B_RESULTS, B_OPS, B_SCRATCH, B_SAM, B_CIGAR, B_MD, B_OFFSETS, B_RECORDS, B_MAP_SCRATCH, B_COUNT };
+           B_RESULTS, B_OPS, B_SCRATCH, B_SAM, B_CIGAR, B_MD, B_OFFSETS, B_RECORDS, B_MAP_SCRATCH, B_CONTIG, B_COUNT };
 
 struct SlotLayout {
     uint64_t at[B_COUNT], bytes[B_COUNT], total;
@@ -77,7 +108,7 @@ struct SlotLayout {
 
 inline uint64_t up256(uint64_t x) { return (x + 255u) & ~255ull; }
 
-SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch)
+SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch, bool contigs)
 {
     const uint64_t N = p.max_reads, K = (uint64_t)p.seed.max_cands, rs = (uint64_t)p.seed.read_size, S = N * K;
     SlotLayout L;
@@ -91,9 +122,11 @@ SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch)
     b[B_SAM] = sizeof(aim_sam_t) * S; b[B_CIGAR] = 4ull * p.cigar_cap; b[B_MD] = p.md_cap;
     b[B_OFFSETS] = 4 * (N + 3);          // rec_offsets[n_reads + 1], then the two cursors of the SAM kernel: one copy fetches the three dwords
     b[B_RECORDS] = sizeof(aim_map_record_t) * S; b[B_MAP_SCRATCH] = kMapScratch;
+    b[B_CONTIG] = contigs ? 4 * S : 0;   // d_contig of rule 13c: a mapper of one sequence has none and keeps its size
     uint64_t at = 0;
     for (int i = 0; i < B_COUNT; ++i) {
         L.at[i] = at;
+        if (i == B_CONTIG && !contigs) continue;
         at += up256(std::max<uint64_t>(b[i], 4));
     }
     L.total = at;
@@ -123,6 +156,8 @@ struct aim_mapper {
     uint64_t ref_len = 0;
     char *d_ref = nullptr;
     uint32_t *d_bucket = nullptr, *d_pos = nullptr;
+    std::vector<uint32_t> starts, lens;  // rule 13c's layout; empty for a reference of one sequence
+    uint32_t *d_contig_start = nullptr, *d_contig_len = nullptr;
     size_t align_scratch = 0;
     SlotLayout L;
     MapperSlot slot[AIM_MAPPER_MAX_SLOTS];
@@ -145,6 +180,7 @@ void release(aim_mapper *m)
     if (m->d_ref) (void)hipFree(m->d_ref);
     if (m->d_bucket) (void)hipFree(m->d_bucket);
     if (m->d_pos) (void)hipFree(m->d_pos);
+    if (m->d_contig_start) (void)hipFree(m->d_contig_start);
     delete m;
 }
 
@@ -173,9 +209,15 @@ int create(aim_mapper *m, const char *seq)
     (void)hipFree(iscr);
     if (rc) return rc;
     HIP_TRY(e);
+    if (const size_t nc = m->starts.size()) {   // one allocation: starts, then lens
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->d_contig_start), 8 * nc));
+        m->d_contig_len = m->d_contig_start + nc;
+        HIP_TRY(hipMemcpy(m->d_contig_start, m->starts.data(), 4 * nc, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(m->d_contig_len, m->lens.data(), 4 * nc, hipMemcpyHostToDevice));
+    }
     m->align_scratch = aim_scratch_bytes(&m->ap.base, (uint32_t)(N * K));
     if (!m->align_scratch) return under("aim_mapper_create", AIM_ENOMEM);
-    m->L = slot_layout(p, m->align_scratch);
+    m->L = slot_layout(p, m->align_scratch, !m->starts.empty());
     for (uint32_t i = 0; i < p.slots; ++i) {
         MapperSlot &s = m->slot[i];
         HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
@@ -200,12 +242,18 @@ const char *aim_mapper_kernel_names(void) { return "map_count_kernel,map_records
 
 size_t aim_map_records_scratch(uint32_t) { return kMapScratch; }
 
-int aim_map_records_device(uint32_t K, uint32_t n_reads, const aim_segment_t *d_seg, const aim_sam_t *d_sam, const aim_chain_class_t *d_class,
-                           uint32_t *d_rec_offsets, aim_map_record_t *d_records, void *d_scratch, size_t scratch_bytes, void *hip_stream)
+}  // extern "C"
+
+namespace {
+
+// Rule 12c's three steps; with d_contig rule 13c's record kernel takes map_records_kernel's place.
+int map_records(const char *fn, bool contigs, uint32_t K, uint32_t n_reads, const aim_segment_t *d_seg, const aim_sam_t *d_sam, const aim_chain_class_t *d_class,
+                const uint32_t *d_contig, uint32_t n_contigs, const uint32_t *d_contig_start, uint32_t *d_rec_offsets, aim_map_record_t *d_records,
+                void *d_scratch, size_t scratch_bytes, void *hip_stream)
 {
-    const char *fn = "aim_map_records_device";
     if (!(cands_ok(fn, K) && slots_ok(fn, n_reads, K) && (d_rec_offsets || refuse("%s: d_rec_offsets is NULL", fn)) &&
-          buffers_ok(fn, n_reads, d_seg && d_sam && d_class && d_records && d_scratch) &&
+          (!contigs || (n_contigs >= 1 && n_contigs <= AIM_CONTIG_MAX) || refuse("%s: n_contigs %u is outside 1..%u", fn, n_contigs, AIM_CONTIG_MAX)) &&
+          buffers_ok(fn, n_reads, d_seg && d_sam && d_class && d_records && d_scratch && (!contigs || (d_contig && d_contig_start))) &&
           (!(((uintptr_t)d_sam | (uintptr_t)d_records) & 15u) || refuse("%s: d_sam and d_records must be 16-byte aligned", fn)) &&
           (!n_reads || scratch_bytes >= kMapScratch ||
            refuse("%s: scratch_bytes %zu is below the %zu aim_map_records_scratch reports", fn, scratch_bytes, kMapScratch))))
@@ -230,15 +278,129 @@ int aim_map_records_device(uint32_t K, uint32_t n_reads, const aim_segment_t *d_
     s.n_parts = (uint32_t)std::min<uint64_t>(std::min(resident, aim::kIndexScanParts), (s.n + aim::kIndexScanBlock - 1u) / aim::kIndexScanBlock);
     s.per_part = ((s.n + s.n_parts - 1u) / s.n_parts + aim::kIndexScanBlock - 1u) / aim::kIndexScanBlock * aim::kIndexScanBlock;
     if (kn.plan_debug)
-        fprintf(stderr, "[aim plan] map_count_kernel grid=%u block=%d lanes=%u reads=%u K=%u; scan parts=%u per_part=%llu; map_records_kernel grid=%u block=%d\n", grid,
-                aim::kMapThreads, lanes, n_reads, K, s.n_parts, (unsigned long long)s.per_part, grid, aim::kMapThreads);
+        fprintf(stderr, "[aim plan] map_count_kernel grid=%u block=%d lanes=%u reads=%u K=%u; scan parts=%u per_part=%llu; %s grid=%u block=%d\n", grid,
+                aim::kMapThreads, lanes, n_reads, K, s.n_parts, (unsigned long long)s.per_part, contigs ? "map_records_contig_kernel" : "map_records_kernel", grid,
+                aim::kMapThreads);
     aim::map_count_launch(a, lanes, grid, stream);
     HIP_TRY(hipGetLastError());
     aim::index_launch_scan(s, stream);
     HIP_TRY(hipGetLastError());
-    aim::map_records_launch(a, lanes, grid, stream);
+    if (contigs) aim::map_records_contig_launch(a, lanes, grid, d_contig, n_contigs, d_contig_start, stream);
+    else aim::map_records_launch(a, lanes, grid, stream);
     HIP_TRY(hipGetLastError());
     return AIM_OK;
+}
+
+// What aim_mapper_device_bytes and its contig twin report, behind their checks.
+int mapper_bytes(const char *fn, const aim_mapper_params_t *params, uint64_t ref_len, uint32_t n_contigs, uint64_t *bytes)
+{
+    if (!bytes) return fail(AIM_EINVAL, "%s: bytes is NULL", fn);
+    const aim_endsfree_params_t ap = align_params(*params);
+    const size_t as = aim_scratch_bytes(&ap.base, (uint32_t)((uint64_t)params->max_reads * (uint64_t)params->seed.max_cands));
+    if (!as) return under(fn, AIM_ENOMEM);
+    uint64_t be = 0, pc = 0, isb = 0;
+    if (aim_index_sizes(params->seed.k, ref_len, &be, &pc) || aim_index_device_scratch(params->seed.k, ref_len, &isb)) return under(fn, AIM_EINVAL);
+    *bytes = up256(ref_len + 16) + be * 4 + std::max<uint64_t>(pc * 4, 256) + 8ull * n_contigs +
+             std::max<uint64_t>(std::max<uint64_t>(isb, 256), (uint64_t)params->slots * slot_layout(*params, as, n_contigs != 0).total);
+    return AIM_OK;
+}
+
+// The device probe and the object, behind the checks of aim_mapper_create and its contig twin (which filled m's layout first).
+int mapper_make(const char *fn, aim_mapper *m, const aim_mapper_params_t *params, int device, const char *seq, uint64_t ref_len, aim_mapper_t **mapper)
+{
+    int n_dev = 0;
+    int rc = aim_device_count(&n_dev);
+    if (!rc && (device < 0 || device >= n_dev)) rc = fail(AIM_EINVAL, "%s: device %d is outside 0..%d", fn, device, n_dev - 1);
+    if (rc) {
+        delete m;
+        return rc;
+    }
+    m->p = *params;
+    m->ap = align_params(*params);
+    m->device = device;
+    m->ref_len = ref_len;
+    if ((rc = create(m, seq))) {
+        const std::string was = aim_last_error();   // (release() must not lose the message)
+        release(m);
+        return fail(rc, "%s", was.c_str());
+    }
+    *mapper = m;
+    return AIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int aim_map_records_device(uint32_t K, uint32_t n_reads, const aim_segment_t *d_seg, const aim_sam_t *d_sam, const aim_chain_class_t *d_class,
+                           uint32_t *d_rec_offsets, aim_map_record_t *d_records, void *d_scratch, size_t scratch_bytes, void *hip_stream)
+{
+    return map_records("aim_map_records_device", false, K, n_reads, d_seg, d_sam, d_class, nullptr, 0, nullptr, d_rec_offsets, d_records, d_scratch, scratch_bytes,
+                       hip_stream);
+}
+
+// ---------------------------------------------------------------------------
+// several sequences (AIM_FEATURE_CONTIGS; rule 13c in aim_hip.h, the clip kernel in contig.hpp, the record kernel in mapper.hpp)
+// ---------------------------------------------------------------------------
+const char *aim_contig_kernel_names(void) { return "contig_clip_kernel,map_records_contig_kernel"; }
+
+int aim_contigs_layout(uint32_t n_contigs, const uint32_t *lens, uint32_t spacer, uint32_t *starts, uint64_t *ref_len)
+{
+    const char *fn = "aim_contigs_layout";
+    if (const int rc = contigs_layout(fn, n_contigs, lens, spacer, nullptr, nullptr)) return rc;
+    if (!starts || !ref_len) return fail(AIM_EINVAL, "%s: %s is NULL", fn, starts ? "ref_len" : "starts");
+    return contigs_layout(fn, n_contigs, lens, spacer, starts, ref_len);
+}
+
+int aim_contigs_concat(uint32_t n_contigs, const char *const *seqs, const uint32_t *lens, uint32_t spacer, char *out)
+{
+    const char *fn = "aim_contigs_concat";
+    uint64_t ref_len = 0;
+    if (const int rc = contigs_layout(fn, n_contigs, lens, spacer, nullptr, &ref_len)) return rc;
+    if (!seqs || !out) return fail(AIM_EINVAL, "%s: %s is NULL", fn, seqs ? "out" : "seqs");
+    for (uint32_t c = 0; c < n_contigs; ++c)
+        if (!seqs[c]) return fail(AIM_EINVAL, "%s: seqs[%u] is NULL", fn, c);
+    std::vector<uint32_t> starts(n_contigs);
+    (void)contigs_layout(fn, n_contigs, lens, spacer, starts.data(), nullptr);
+    contigs_concat(n_contigs, seqs, lens, starts.data(), ref_len, out);
+    return AIM_OK;
+}
+
+int aim_contig_clip_device(uint32_t K, uint32_t read_size, int32_t flank, uint64_t ref_len, uint32_t n_contigs, const uint32_t *d_contig_start,
+                           const uint32_t *d_contig_len, uint32_t n_reads, const int32_t *d_read_len, const void *d_requests, const uint64_t *d_text_pos,
+                           const aim_chain_t *d_chains, void *d_seg_requests, uint64_t *d_seg_text_pos, aim_segment_t *d_seg, uint32_t *d_contig, void *hip_stream)
+{
+    const char *fn = "aim_contig_clip_device";
+    if (!(cands_ok(fn, K) && read_size_ok(fn, read_size) && slots_ok(fn, n_reads, K) && (flank >= 0 || refuse("%s: flank %d must be >= 0", fn, flank)) &&
+          (ref_len >= 1 || refuse("%s: ref_len must be >= 1", fn)) && ref_len_ok(fn, ref_len, false) &&
+          ((n_contigs >= 1 && n_contigs <= AIM_CONTIG_MAX) || refuse("%s: n_contigs %u is outside 1..%u", fn, n_contigs, AIM_CONTIG_MAX)) &&
+          ((d_contig_start && d_contig_len) || refuse("%s: d_contig_start or d_contig_len is NULL", fn)) &&
+          buffers_ok(fn, n_reads, d_read_len && d_requests && d_text_pos && d_chains && d_seg_requests && d_seg_text_pos && d_seg && d_contig)))
+        return AIM_EINVAL;
+    return launch_batch(n_reads, [&](const aim::Knobs &kn) {
+        aim::ContigArgs a;
+        memset(&a, 0, sizeof a);
+        a.K = K; a.read_size = read_size; a.n_slots = n_reads * K; a.n_contigs = n_contigs; a.step_log2 = aim::contig_step_log2(n_contigs);
+        a.dbg_poison_lds = poison_lds_word(kn);
+        a.flank = flank; a.ref_len = (int64_t)ref_len;
+        a.start = d_contig_start; a.len = d_contig_len;
+        a.read_len = d_read_len; a.requests = static_cast<const aim_request_t *>(d_requests); a.text_pos = d_text_pos; a.chains = d_chains;
+        a.seg_requests = static_cast<aim_request_t *>(d_seg_requests); a.seg_text_pos = d_seg_text_pos; a.seg = d_seg; a.contig = d_contig;
+        // the step comes from n_contigs alone; only the grid is the device's
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(aim::resident_grid(kn, aim::kContigPerCu), ((uint64_t)a.n_slots + aim::kContigThreads - 1u) / aim::kContigThreads);
+        if (kn.plan_debug)
+            fprintf(stderr, "[aim plan] contig_clip_kernel grid=%u block=%d contigs=%u step=%u slots=%u\n", grid, aim::kContigThreads, n_contigs, 1u << a.step_log2,
+                    a.n_slots);
+        aim::contig_clip_launch(a, grid, (hipStream_t)hip_stream);
+    });
+}
+
+int aim_map_records_contigs_device(uint32_t K, uint32_t n_reads, const aim_segment_t *d_seg, const aim_sam_t *d_sam, const aim_chain_class_t *d_class,
+                                   const uint32_t *d_contig, uint32_t n_contigs, const uint32_t *d_contig_start, uint32_t *d_rec_offsets,
+                                   aim_map_record_t *d_records, void *d_scratch, size_t scratch_bytes, void *hip_stream)
+{
+    return map_records("aim_map_records_contigs_device", true, K, n_reads, d_seg, d_sam, d_class, d_contig, n_contigs, d_contig_start, d_rec_offsets, d_records,
+                       d_scratch, scratch_bytes, hip_stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -248,15 +410,17 @@ int aim_mapper_device_bytes(const aim_mapper_params_t *params, uint64_t ref_len,
 {
     const char *fn = "aim_mapper_device_bytes";
     if (const int rc = check_mapper_params(fn, params, ref_len)) return rc;
-    if (!bytes) return fail(AIM_EINVAL, "%s: bytes is NULL", fn);
-    const aim_endsfree_params_t ap = align_params(*params);
-    const size_t as = aim_scratch_bytes(&ap.base, (uint32_t)((uint64_t)params->max_reads * (uint64_t)params->seed.max_cands));
-    if (!as) return under(fn, AIM_ENOMEM);
-    uint64_t be = 0, pc = 0, isb = 0;
-    if (aim_index_sizes(params->seed.k, ref_len, &be, &pc) || aim_index_device_scratch(params->seed.k, ref_len, &isb)) return under(fn, AIM_EINVAL);
-    *bytes = up256(ref_len + 16) + be * 4 + std::max<uint64_t>(pc * 4, 256) +
-             std::max<uint64_t>(std::max<uint64_t>(isb, 256), (uint64_t)params->slots * slot_layout(*params, as).total);
-    return AIM_OK;
+    return mapper_bytes(fn, params, ref_len, 0, bytes);
+}
+
+int aim_mapper_device_bytes_contigs(const aim_mapper_params_t *params, uint32_t n_contigs, const uint32_t *lens, uint64_t *bytes)
+{
+    const char *fn = "aim_mapper_device_bytes_contigs";
+    if (!params) return fail(AIM_EINVAL, "%s: params is NULL", fn);
+    uint64_t ref_len = 0;
+    if (const int rc = contigs_layout(fn, n_contigs, lens, mapper_spacer(*params), nullptr, &ref_len)) return rc;
+    if (const int rc = check_mapper_params(fn, params, ref_len)) return rc;
+    return mapper_bytes(fn, params, ref_len, n_contigs, bytes);
 }
 
 int aim_mapper_create(const aim_mapper_params_t *params, int device, const char *seq, uint64_t ref_len, aim_mapper_t **mapper)
@@ -265,20 +429,38 @@ int aim_mapper_create(const aim_mapper_params_t *params, int device, const char 
     if (const int rc = check_mapper_params(fn, params, ref_len)) return rc;
     if (!mapper) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
     if (ref_len && !seq) return fail(AIM_EINVAL, "%s: seq is NULL", fn);
-    int n_dev = 0;
-    if (const int rc = aim_device_count(&n_dev)) return rc;
-    if (device < 0 || device >= n_dev) return fail(AIM_EINVAL, "%s: device %d is outside 0..%d", fn, device, n_dev - 1);
+    return mapper_make(fn, new aim_mapper(), params, device, seq, ref_len, mapper);
+}
+
+int aim_mapper_create_contigs(const aim_mapper_params_t *params, int device, uint32_t n_contigs, const char *const *seqs, const uint32_t *lens, aim_mapper_t **mapper)
+{
+    const char *fn = "aim_mapper_create_contigs";
+    if (!params) return fail(AIM_EINVAL, "%s: params is NULL", fn);
+    uint64_t ref_len = 0;
+    const uint32_t spacer = mapper_spacer(*params);
+    if (const int rc = contigs_layout(fn, n_contigs, lens, spacer, nullptr, &ref_len)) return rc;
+    if (const int rc = check_mapper_params(fn, params, ref_len)) return rc;
+    if (!mapper) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
+    if (!seqs) return fail(AIM_EINVAL, "%s: seqs is NULL", fn);
+    for (uint32_t c = 0; c < n_contigs; ++c)
+        if (!seqs[c]) return fail(AIM_EINVAL, "%s: seqs[%u] is NULL", fn, c);
     aim_mapper *m = new aim_mapper();
-    m->p = *params;
-    m->ap = align_params(*params);
-    m->device = device;
-    m->ref_len = ref_len;
-    if (const int rc = create(m, seq)) {
-        const std::string was = aim_last_error();   // (release() must not lose the message)
-        release(m);
-        return fail(rc, "%s", was.c_str());
-    }
-    *mapper = m;
+    m->starts.resize(n_contigs);
+    m->lens.assign(lens, lens + n_contigs);
+    (void)contigs_layout(fn, n_contigs, lens, spacer, m->starts.data(), nullptr);
+    std::vector<char> cat((size_t)ref_len);
+    contigs_concat(n_contigs, seqs, lens, m->starts.data(), ref_len, cat.data());
+    return mapper_make(fn, m, params, device, cat.data(), ref_len, mapper);
+}
+
+int aim_mapper_contigs(const aim_mapper_t *m, uint32_t *n_contigs, const uint32_t **starts, const uint32_t **lens)
+{
+    const char *fn = "aim_mapper_contigs";
+    if (!m) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
+    if (!n_contigs || !starts || !lens) return fail(AIM_EINVAL, "%s: NULL output", fn);
+    *n_contigs = (uint32_t)m->starts.size();
+    *starts = m->starts.empty() ? nullptr : m->starts.data();
+    *lens = m->lens.empty() ? nullptr : m->lens.data();
     return AIM_OK;
 }
 
@@ -324,11 +506,19 @@ int aim_mapper_submit(aim_mapper_t *m, uint32_t slot, uint32_t n_reads, const in
     if (!rc && (p.options & AIM_MAP_EXTEND))
         rc = aim_extend_segments_device(&p.extend, K, rs, m->ref_len, n_reads, d_rl, d_reads, m->d_ref, d_seg_req, d_seg_tp, d_seg_pat, d_seg,
                                         at<aim_extend_t>(m, s, B_EXT), st);
+    const uint32_t n_contigs = (uint32_t)m->starts.size();
+    uint32_t *d_contig = at<uint32_t>(m, s, B_CONTIG);
+    if (!rc && n_contigs)
+        rc = aim_contig_clip_device(K, rs, flank, m->ref_len, n_contigs, m->d_contig_start, m->d_contig_len, n_reads, d_rl, d_req, d_tp, d_chains, d_seg_req, d_seg_tp,
+                                    d_seg, d_contig, st);
     if (!rc) rc = aim_align_device_ref(&m->ap.base, rows, d_seg_req, d_seg_pat, d_seg_tp, m->d_ref, m->ref_len, d_res, d_ops, at<void>(m, s, B_SCRATCH), m->align_scratch, st);
     if (!rc)
         rc = aim_sam_device_split(&m->ap.base, rows, d_seg_req, d_seg_tp, nullptr, d_res, d_ops, m->d_ref, m->ref_len, p.sam_options, d_sam, at<uint32_t>(m, s, B_CIGAR),
                                   p.cigar_cap, at<char>(m, s, B_MD), p.md_cap, d_cursors, d_seg, st);
-    if (!rc) rc = aim_map_records_device(K, n_reads, d_seg, d_sam, d_cls, d_off, at<aim_map_record_t>(m, s, B_RECORDS), at<void>(m, s, B_MAP_SCRATCH), kMapScratch, st);
+    if (!rc)
+        rc = n_contigs ? aim_map_records_contigs_device(K, n_reads, d_seg, d_sam, d_cls, d_contig, n_contigs, m->d_contig_start, d_off,
+                                                        at<aim_map_record_t>(m, s, B_RECORDS), at<void>(m, s, B_MAP_SCRATCH), kMapScratch, st)
+                       : aim_map_records_device(K, n_reads, d_seg, d_sam, d_cls, d_off, at<aim_map_record_t>(m, s, B_RECORDS), at<void>(m, s, B_MAP_SCRATCH), kMapScratch, st);
     if (rc) {
         (void)hipStreamSynchronize(st);  // what was enqueued reads the pinned buffers
         return under(fn, rc);

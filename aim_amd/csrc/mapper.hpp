@@ -6,6 +6,7 @@
 //     rec_offsets[n_reads] is the number of records.
 //   * map_records_kernel: per read, the mapped slots again, their rank by (q_begin, i) and the representative, and each record written
 //     at rec_offsets[r] + rank as four 16-byte stores.
+//   * map_records_contig_kernel (rule 13c) takes its place for a reference of several sequences: the slot's contig in the record.
 //
 // Both kernels give a read G = 4, 8 or 16 consecutive lanes by K, as chain_class_kernel does (chain_class_lanes), with candidate i in
 // lane i of the group; the group's bits of one wave ballot are the read's mapped slots, their population count is c_r, the lowest set
@@ -128,6 +129,75 @@ __global__ __launch_bounds__(kMapThreads) void map_records_kernel(MapArgs a, uin
     }
 }
 
+// Rule 13c's record kernel: map_records_kernel once more, with the slot's contig in the record -- a mapped record's pos becomes local to
+// contig[slot] and its pad names it, the record of an unmapped read gets AIM_CONTIG_NONE. It is a copy, not a template over one body:
+// a shared body, force-inlined into both, compiled map_records_kernel to other instructions (349 against its 357, the same 38 VGPRs),
+// and that kernel keeps its instructions. What the two share beyond map_slot is the text between the marks; a change to one belongs in the other.
+__global__ __launch_bounds__(kMapThreads) void map_records_contig_kernel(MapArgs a, uint32_t G, const uint32_t *contig, uint32_t n_contigs, const uint32_t *contig_start)
+{
+    // ---- as map_records_kernel ----
+    const uint32_t kReads = kMapThreads / G;
+    const uint32_t cand = threadIdx.x & (G - 1u);
+    const uint32_t base = (threadIdx.x & (uint32_t)(kWave - 1)) & ~(G - 1u);
+    const uint64_t n_blocks = ((uint64_t)a.n_reads + kReads - 1u) / kReads;
+    for (uint64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
+        const uint64_t r = blk * kReads + threadIdx.x / G;
+        const bool live = r < a.n_reads && cand < a.K;
+        const uint64_t slot = r * a.K + cand;
+        const MapSlot s = map_slot(a, live, slot, base, G);
+        const bool mapped = (s.mask >> cand) & 1u;
+        const uint32_t q = s.seg0 & 0xffffu;
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < a.K; ++j) {
+            const uint32_t q_j = (uint32_t)__shfl((int)q, (int)j, (int)G);
+            const bool below = mapped && (q < q_j || (q == q_j && cand < j));
+            const uint32_t bits = (uint32_t)(__ballot(below) >> base) & ((1u << G) - 1u);
+            if (cand == j) rank = (uint32_t)__popc(bits);
+        }
+        const bool unmapped_read = live && cand == 0 && !s.mask;
+        if (mapped || unmapped_read) {
+            const uint4 *row = reinterpret_cast<const uint4 *>(a.sam) + slot * 3u;
+            uint4 w0 = row[0], w1 = row[1], w2 = row[2], w3;
+            if (mapped) {
+                const uint32_t rep = (uint32_t)__ffs(s.mask) - 1u;
+                const uint32_t flags = cand == rep ? (s.fs & ~AIM_SAM_SUPPLEMENTARY) : (s.fs | AIM_SAM_SUPPLEMENTARY);
+                const uint32_t c1 = reinterpret_cast<const uint32_t *>(a.cls)[slot * 2u + 1u];
+                w2.z = flags;
+                w3.x = (uint32_t)r;
+                w3.y = s.seg0;
+                w3.z = ((c1 >> 16) & 0xffu) | ((s.seg1 >> 16) & 0xffu) << 8 | rank << 16 | (uint32_t)__popc(s.mask) << 24;
+                // ---- rule 13c: the contig-local position and the contig ----
+                const uint32_t c = contig[slot];
+                const uint64_t pos = ((uint64_t)w0.w << 32 | w0.z) - (c < n_contigs ? contig_start[c] : 0u);   // (no load outside the table)
+                w0.z = (uint32_t)pos;
+                w0.w = (uint32_t)(pos >> 32);
+                w2.w = c;                                                               // pad
+                // ---- as map_records_kernel ----
+            } else {
+                w0.z = w0.w = 0u;
+                w1 = make_uint4(0u, 0u, 0u, 0u);
+                w2.x = w2.y = 0u;
+                w2.z = AIM_SAM_UNMAPPED | (s.fs & 0xffff0000u);
+                w2.w = AIM_CONTIG_NONE;                                                 // rule 13c: pad of an unmapped read
+                w3.x = (uint32_t)r;
+                w3.y = 0u;
+                w3.z = 1u << 24;
+            }
+            w3.w = (uint32_t)slot;
+            uint4 *out = reinterpret_cast<uint4 *>(a.records) + ((uint64_t)a.rec_offsets[r] + (mapped ? rank : 0u)) * 4u;
+            out[0] = w0;
+            out[1] = w1;
+            out[2] = w2;
+            out[3] = w3;
+        }
+    }
+}
+
+void map_records_contig_launch(const MapArgs &a, uint32_t lanes, uint32_t grid, const uint32_t *contig, uint32_t n_contigs, const uint32_t *contig_start, hipStream_t s)
+{
+    hipLaunchKernelGGL(map_records_contig_kernel, dim3(grid), dim3(kMapThreads), 0, s, a, lanes, contig, n_contigs, contig_start);
+}
+
 void map_count_launch(const MapArgs &a, uint32_t lanes, uint32_t grid, hipStream_t s)
 {
     hipLaunchKernelGGL(map_count_kernel, dim3(grid), dim3(kMapThreads), 0, s, a, lanes);
@@ -138,6 +208,7 @@ void map_records_launch(const MapArgs &a, uint32_t lanes, uint32_t grid, hipStre
     hipLaunchKernelGGL(map_records_kernel, dim3(grid), dim3(kMapThreads), 0, s, a, lanes);
 }
 #else
+void map_records_contig_launch(const MapArgs &a, uint32_t lanes, uint32_t grid, const uint32_t *contig, uint32_t n_contigs, const uint32_t *contig_start, hipStream_t s);
 void map_count_launch(const MapArgs &a, uint32_t lanes, uint32_t grid, hipStream_t s);
 void map_records_launch(const MapArgs &a, uint32_t lanes, uint32_t grid, hipStream_t s);
 #endif

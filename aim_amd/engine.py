@@ -710,6 +710,55 @@ def map_records_device(K, n_reads, d_seg, d_sam, d_class, d_rec_offsets, d_recor
     capi.check(capi.load().aim_map_records_device(int(K), int(n_reads), d_seg, d_sam, d_class, d_rec_offsets, d_records, d_scratch, int(scratch_bytes), stream))
 
 
+def _contig_arrays(seqs):
+    """(uint8 arrays kept alive, lens uint32[n], a ctypes array of their addresses) for the `seqs` / `lens` arguments of rule 13c."""
+    arrs = [np.ascontiguousarray(np.frombuffer(s, dtype=np.uint8) if isinstance(s, (bytes, bytearray)) else s, dtype=np.uint8) for s in seqs]
+    lens = np.array([len(a) for a in arrs], dtype=np.uint32)
+    ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    return arrs, lens, ptrs
+
+
+def contigs_layout(lens, spacer):
+    """aim_contigs_layout: (starts uint32[n], ref_len) of contigs of these lengths with `spacer` 'N' bases between neighbours."""
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    starts = np.zeros(len(lens), dtype=np.uint32)
+    ref_len = C.c_uint64()
+    capi.check(capi.load().aim_contigs_layout(len(lens), capi.ptr(lens) if len(lens) else None, int(spacer), capi.ptr(starts) if len(lens) else None, C.byref(ref_len)))
+    return starts, ref_len.value
+
+
+def contigs_concat(seqs, spacer):
+    """aim_contigs_concat: the concatenation (uint8 array) of rule 13c's layout, 'N' in the gaps."""
+    arrs, lens, ptrs = _contig_arrays(seqs)
+    ref_len = contigs_layout(lens, spacer)[1]
+    out = np.zeros(ref_len, dtype=np.uint8)
+    capi.check(capi.load().aim_contigs_concat(len(arrs), ptrs, capi.ptr(lens), int(spacer), capi.ptr(out)))
+    return out
+
+
+def contig_clip_device(K, read_size, flank, ref_len, n_contigs, d_contig_start, d_contig_len, n_reads, d_read_len, d_requests, d_text_pos, d_chains, d_seg_requests,
+                       d_seg_text_pos, d_seg, d_contig, stream=None):
+    """aim_contig_clip_device on device pointers (integers, e.g. torch's data_ptr(); None = NULL): rule 13c's clip over the segment
+    buffers of split_segments_device / extend_segments_device, in place, from the candidates' own d_requests / d_text_pos / d_chains;
+    d_contig (uint32 per slot) receives the contig of every valid slot. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_contig_clip_device(int(K), int(read_size), int(flank), int(ref_len), int(n_contigs), d_contig_start, d_contig_len, int(n_reads), d_read_len,
+                                                  d_requests, d_text_pos, d_chains, d_seg_requests, d_seg_text_pos, d_seg, d_contig, stream))
+
+
+def map_records_contigs_device(K, n_reads, d_seg, d_sam, d_class, d_contig, n_contigs, d_contig_start, d_rec_offsets, d_records, d_scratch, scratch_bytes, stream=None):
+    """aim_map_records_contigs_device: map_records_device with contig_clip_device's d_contig -- pos local to the contig, pad = the contig."""
+    capi.check(capi.load().aim_map_records_contigs_device(int(K), int(n_reads), d_seg, d_sam, d_class, d_contig, int(n_contigs), d_contig_start, d_rec_offsets,
+                                                          d_records, d_scratch, int(scratch_bytes), stream))
+
+
+def mapper_device_bytes_contigs(mp, lens):
+    """aim_mapper_device_bytes_contigs: the device memory a Mapper.from_contigs of these parameters and contig lengths takes at its peak."""
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    b = C.c_uint64()
+    capi.check(capi.load().aim_mapper_device_bytes_contigs(C.byref(mp), len(lens), capi.ptr(lens) if len(lens) else None, C.byref(b)))
+    return b.value
+
+
 def mapper_params(sp, max_reads, max_score, mismatch=3, gap_o=4, gap_e=1, match=0, max_hits=0, mask_q8=capi.CHAIN_MASK_DEFAULT, extend=None, sam_options=0,
                   slots=2, cigar_cap=None, md_cap=None):
     """aim_mapper_params_t from the seed parameters of seed_params(..., w=...) (K is sp.max_cands, read_size sp.read_size), the batch
@@ -740,8 +789,28 @@ class Mapper:
         self.params = mp
         ref = np.ascontiguousarray(np.frombuffer(reference, dtype=np.uint8) if isinstance(reference, (bytes, bytearray)) else reference, dtype=np.uint8)
         self.ref_len = len(ref)
+        self.contigs = None
         self.handle = C.c_void_p()
         capi.check(self.lib.aim_mapper_create(C.byref(mp), int(device), capi.ptr(ref) if len(ref) else None, len(ref), C.byref(self.handle)))
+
+    @classmethod
+    def from_contigs(cls, mp, seqs, device=0):
+        """aim_mapper_create_contigs: a mapper over a reference of several sequences (rule 13c). seqs is a list of bytes or uint8 arrays,
+        one per contig. The records' pos is local to the contig in rec["sam"]["pad"]; .contigs is (starts, lens), uint32 arrays of the
+        layout inside the concatenation, and .ref_len the concatenation's length."""
+        self = cls.__new__(cls)
+        self.lib = capi.load()
+        self.params = mp
+        self.contigs = None
+        self.handle = C.c_void_p()
+        arrs, lens, ptrs = _contig_arrays(seqs)
+        capi.check(self.lib.aim_mapper_create_contigs(C.byref(mp), int(device), len(arrs), ptrs, capi.ptr(lens), C.byref(self.handle)))
+        n, st, ln = C.c_uint32(), C.c_void_p(), C.c_void_p()
+        capi.check(self.lib.aim_mapper_contigs(self.handle, C.byref(n), C.byref(st), C.byref(ln)))
+        view = lambda addr: np.frombuffer((C.c_uint32 * n.value).from_address(addr), dtype=np.uint32).copy()
+        self.contigs = (view(st.value), view(ln.value))
+        self.ref_len = int(self.contigs[0][-1]) + int(self.contigs[1][-1])
+        return self
 
     def close(self):
         if self.handle:

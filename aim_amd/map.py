@@ -1,9 +1,10 @@
 """python -m aim_amd.map --ref REF.fa --reads READS.fq|.fa -o OUT.sam
 
-Maps single-end reads against a reference of ONE sequence with engine.Mapper (chain -> classify -> split -> [extend] -> align -> SAM
+Maps single-end reads against a reference with engine.Mapper (chain -> classify -> split -> [extend] -> align -> SAM
 records -> record list, all on the device) and writes SAM with aim_amd.samout. Two slots are driven alternately: while one batch is
-on the device the previous one is written. Bases are upper-cased on the way in (the index holds upper-case A C G T only). A FASTA with
-more than one sequence is refused: a contig table is a separate piece of work."""
+on the device the previous one is written. Bases are upper-cased on the way in (the index holds upper-case A C G T only). Without
+--contigs the reference is a FASTA of ONE sequence and a FASTA with more is refused; with --contigs every sequence of the FASTA is a
+contig (rule 13c of include/aim_hip.h): one @SQ line each, and every record lies inside the sequence it names."""
 import argparse
 import sys
 
@@ -73,11 +74,23 @@ def load_reference(path):
     return seqs[0][0], np.frombuffer(seqs[0][1].upper(), dtype=np.uint8).copy()
 
 
+def load_contigs(path):
+    """(names, upper-cased uint8 arrays) of a FASTA with one sequence or more, in file order; ValueError for none or an empty one."""
+    seqs = read_fasta(path)
+    if not seqs:
+        raise ValueError("%s holds no sequence" % path)
+    for name, s in seqs:
+        if not s:
+            raise ValueError("%s: sequence '%s' is empty" % (path, name))
+    return [n for n, _ in seqs], [np.frombuffer(s.upper(), dtype=np.uint8).copy() for _, s in seqs]
+
+
 def parser():
     ap = argparse.ArgumentParser(prog="python -m aim_amd.map", description=__doc__.split("\n\n")[1])
     ap.add_argument("--ref", required=True)
     ap.add_argument("--reads", required=True)
     ap.add_argument("-o", "--out", required=True)
+    ap.add_argument("--contigs", action="store_true", help="map against every sequence of a multi-sequence FASTA (a contig table)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch", type=int, default=4096, help="reads per batch (max_reads)")
     ap.add_argument("--read-size", type=int, default=None, help="row size, a multiple of 8 (default: the longest read rounded up)")
@@ -125,10 +138,16 @@ def mapper_params_from(args, read_size):
 def main(argv=None):
     args = parser().parse_args(argv)
     try:
-        rname, ref = load_reference(args.ref)
+        if args.contigs:
+            rname, ref = load_contigs(args.ref)
+            ref_lens = [len(s) for s in ref]
+        else:
+            rname, ref = load_reference(args.ref)
+            ref_lens = len(ref)
         reads = read_reads(args.reads)
     except (OSError, ValueError) as e:
-        print("aim_amd.map: %s" % e, file=sys.stderr)
+        hint = "; --contigs maps against all of them" if not args.contigs and "contig table" in str(e) else ""
+        print("aim_amd.map: %s%s" % (e, hint), file=sys.stderr)
         return 2
     from . import engine, samout
     longest = max([len(s) for _, s, _ in reads] + [1])
@@ -142,8 +161,9 @@ def main(argv=None):
         print("aim_amd.map: %s" % e, file=sys.stderr)
         return 2
     n_lines = 0
-    with open(args.out, "w") as fh, engine.Mapper(mp, ref, device=args.device) as m:
-        fh.write(samout.header(rname, len(ref), command_line=" ".join(["python -m aim_amd.map"] + list(sys.argv[1:] if argv is None else argv))))
+    make = engine.Mapper.from_contigs if args.contigs else engine.Mapper
+    with open(args.out, "w") as fh, make(mp, ref, device=args.device) as m:
+        fh.write(samout.header(rname, ref_lens, command_line=" ".join(["python -m aim_amd.map"] + list(sys.argv[1:] if argv is None else argv))))
         pending = {}                                  # slot -> the batch in flight on it
 
         def finish(slot):

@@ -18,11 +18,13 @@ def revcomp(seq):
 
 
 def header(rname, ref_len, command_line=None, version="1"):
-    """@HD / @SQ / @PG for a reference of one sequence."""
+    """@HD / @SQ / @PG. rname and ref_len are one sequence's name and length, or two lists, one entry per contig (rule 13c): one @SQ
+    line each, in contig order."""
     pg = "@PG\tID:aim_amd\tPN:aim_amd\tVN:%s" % version
     if command_line:
         pg += "\tCL:" + command_line
-    return "@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:%s\tLN:%d\n%s\n" % (rname, int(ref_len), pg)
+    sq = [(rname, ref_len)] if isinstance(rname, str) else list(zip(rname, ref_len))
+    return "@HD\tVN:1.6\tSO:unsorted\n%s%s\n" % ("".join("@SQ\tSN:%s\tLN:%d\n" % (n, int(l)) for n, l in sq), pg)
 
 
 def _cigar(rec, cigar):
@@ -33,15 +35,21 @@ def _cigar(rec, cigar):
     return engine.sam_format_cigar(cigar[o:o + int(s["n_cigar"])])
 
 
+def _rname(rname, rec):
+    """A record's RNAME: the one name, or the name of the contig in the record's pad (Mapper.from_contigs)."""
+    return rname if isinstance(rname, str) else rname[int(rec["sam"]["pad"])]
+
+
 def _sa(rname, rec, cigar):
     s = rec["sam"]
-    return "%s,%d,%s,%s,%d,%d;" % (rname, int(s["pos"]) + 1, "-" if int(s["flags"]) & capi.SAM_REVERSE else "+", _cigar(rec, cigar), int(rec["mapq"]), int(s["nm"]))
+    return "%s,%d,%s,%s,%d,%d;" % (_rname(rname, rec), int(s["pos"]) + 1, "-" if int(s["flags"]) & capi.SAM_REVERSE else "+", _cigar(rec, cigar), int(rec["mapq"]), int(s["nm"]))
 
 
 def record_lines(out, names, reads, read_len, rname, quals=None):
     """The SAM lines (without newlines) of one mapper result `out` (the dict of Mapper.wait, or anything with "records", "rec_offsets",
     "cigar" and "md"). names[r] is read r's QNAME, reads[r] its row of bases (bytes or a uint8 row), read_len[r] its length and
-    quals[r] (optional) its quality string."""
+    quals[r] (optional) its quality string. rname is the reference's name, or the list of contig names for the records of
+    Mapper.from_contigs, whose pad says which contig pos is local to; an SA entry carries its own record's contig."""
     recs, off, cigar, md = out["records"], out["rec_offsets"], out["cigar"], np.asarray(out["md"], dtype=np.uint8)
     lines = []
     for r in range(len(off) - 1):
@@ -58,7 +66,7 @@ def record_lines(out, names, reads, read_len, rname, quals=None):
                 lines.append("\t".join([names[r], "4", "*", "0", "0", "*", "*", "0", "0", seq.decode("latin-1") or "*", qual or "*"]))
                 continue
             rev = bool(flags & capi.SAM_REVERSE)
-            fields = [names[r], str(flags), rname, str(int(s["pos"]) + 1), str(int(rec["mapq"])), _cigar(rec, cigar), "*", "0", "0",
+            fields = [names[r], str(flags), _rname(rname, rec), str(int(s["pos"]) + 1), str(int(rec["mapq"])), _cigar(rec, cigar), "*", "0", "0",
                       (revcomp(seq) if rev else seq).decode("latin-1") or "*", (qual[::-1] if rev else qual) if qual else "*", "NM:i:%d" % int(s["nm"])]
             if int(s["md_len"]) and not int(s["status"]) & capi.SAM_OVERFLOW:
                 o = int(s["md_offset"])

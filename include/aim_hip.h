@@ -348,6 +348,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_SPLIT 0x20000u /* split reads: aim_split_segments_device / aim_sam_device_split / aim_split_kernel_names exist */
 #define AIM_FEATURE_EXTEND 0x40000u /* segment extension: aim_extend_segments_device / aim_extend_kernel_names exist */
 #define AIM_FEATURE_MAPPER 0x80000u /* rule 12c and the mapper object: aim_map_records_device / aim_mapper_create / aim_mapper_submit / aim_mapper_wait exist */
+#define AIM_FEATURE_CONTIGS 0x100000u /* rule 13c, references of several sequences: aim_contigs_layout / aim_contig_clip_device / aim_map_records_contigs_device / aim_mapper_create_contigs exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -1134,8 +1135,8 @@ const char *aim_extend_kernel_names(void);
  *       AIM_SAM_OVERFLOW. n_reads = 0 is a valid batch: no records, rec_offsets = {0}.
  *       The slots are independent: batches on different slots overlap, and a slot's result does not depend on what ran before it.
  * aim_mapper_kernel_names: "map_count_kernel,map_records_kernel".
- * Not in this version: a mapper stage inside aim_set_submit or host.c, more than one device per mapper, references of more than one
- * sequence (a contig table), paired-end reads through the mapper, hard clips, trimming the overlap of neighbouring segments, packed
+ * Not in this version: a mapper stage inside aim_set_submit or host.c, more than one device per mapper, paired-end reads through the mapper
+ * (references of more than one sequence: rule 13c and aim_mapper_create_contigs below), hard clips, trimming the overlap of neighbouring segments, packed
  * read rows, MAPQ from alignment runner-ups. The SA tag is text and is written on the host (aim_amd/samout.py) from the records of a
  * read. Check aim_features() & AIM_FEATURE_MAPPER first. */
 typedef struct aim_map_record {
@@ -1183,6 +1184,80 @@ int aim_mapper_create(const aim_mapper_params_t *params, int device, const char 
 int aim_mapper_submit(aim_mapper_t *mapper, uint32_t slot, uint32_t n_reads, const int32_t *read_len, const char *reads);
 int aim_mapper_wait(aim_mapper_t *mapper, uint32_t slot, aim_mapper_out_t *out);
 int aim_mapper_free(aim_mapper_t *mapper);
+
+/* ---- references of several sequences (AIM_FEATURE_CONTIGS): contig table, edge clipping, the contig in the record ---------------
+ * The index, the chains and the alignment work on one sequence of positions. A reference of several sequences (contigs) becomes one
+ * by concatenation, and rule 13c says what the concatenation looks like, how a segment's window is kept inside the contig it belongs
+ * to, and how a record names its contig. No other stage changes.
+ *   13c. Layout (aim_contigs_layout, aim_contigs_concat; host only). Contig c of lens[c] bases starts at starts[c]: starts[0] = 0,
+ *       starts[c + 1] = starts[c] + lens[c] + spacer, and ref_len = starts[n - 1] + lens[n - 1]. The spacer bases between two
+ *       contigs are 'N': an 'N' is not A, C, G or T, so no k-mer and no minimizer spans two contigs. AIM_CONTIG_SPACER(band) =
+ *       band + 64 is the spacer aim_mapper_create_contigs uses: two anchors on either side of a true junction between neighbouring
+ *       contigs (the read continues from the end of one into the start of the next) then differ in diagonal by more than band, so
+ *       rule 4c does not link them and each side becomes a chain of its own.
+ *       AIM_EINVAL names the field or the contig: n_contigs outside 1..AIM_CONTIG_MAX, a NULL array, spacer < 1, a lens[c] of 0,
+ *       a ref_len above AIM_SEED_MAX_REF_LEN (the contig at which the sum passed it is named).
+ *       Clip (aim_contig_clip_device). Runs behind aim_split_segments_device, and behind aim_extend_segments_device where that
+ *       runs, in front of aim_align_device_ref, on every slot r * K + i whose d_seg[slot].flags has AIM_SEG_VALID:
+ *         Anchor. A is rule 10c's recovered p_lo of the candidate, from d_requests[slot], d_text_pos[slot], d_chains[slot], flank
+ *         and L = min(max(d_read_len[r], 0), read_size) -- the candidate's window, not the segment's --, clamped to
+ *         [0, ref_len - 1]. Where the segment has AIM_SEG_LOOSE, or p_lo is not recoverable, A is the segment's start.
+ *         Contig. c = max{ j : starts[j] <= A }. An anchor inside a spacer belongs to the contig in front of it.
+ *         Window. With seg_start = d_seg_text_pos[slot] without the strand bit and seg_end = seg_start + d_seg_requests[slot].text_len:
+ *         s' = max(seg_start, starts[c]) and e' = max(s', min(seg_end, starts[c] + lens[c])). If either bound moved,
+ *         d_seg_text_pos[slot] = s' | strand bit, text_len = e' - s' and d_seg[slot].flags gains AIM_SEG_CONTIG_CLIPPED; a window
+ *         wholly outside its contig ends with text_len 0. d_contig[slot] = c.
+ *         Every slot without AIM_SEG_VALID keeps every byte and gets d_contig[slot] = AIM_CONTIG_NONE; a slot that is not clipped
+ *         keeps every byte of the three segment buffers. The pattern rows, q_begin and q_end are never touched: read bases that lost
+ *         their reference come back from the alignment as a terminal read-only run, which aim_sam_device_split folds into the soft
+ *         clip, so the CIGAR's read-consuming lengths still sum to read_len and pos + ref_span stays inside the contig.
+ *         Deterministic, independent of the grid and of the AIM_DEBUG_POISON_* knobs. d_contig_start and d_contig_len are
+ *         uint32_t[n_contigs] on the device, as aim_contigs_layout gave them, and ref_len is its ref_len.
+ *         contig_clip_kernel (csrc/contig.hpp): a slot per lane; a workgroup stages every step-th start in LDS (step = the smallest
+ *         power of two with ceil(n_contigs / step) <= 1024), searches that table and finishes with at most log2(step) loads from
+ *         d_contig_start. No atomics, no scratch memory; only enqueues work on hip_stream.
+ *         AIM_EINVAL under the entry point's name, before any device query: K outside 1..AIM_SEED_MAX_CANDS, a read_size that is not
+ *         a positive multiple of 8 up to AIM_SEED_LONG_MAX_READ_SIZE, n_reads * K >= 2^32, flank < 0, ref_len 0 or above
+ *         AIM_SEED_MAX_REF_LEN, n_contigs outside 1..AIM_CONTIG_MAX, a NULL d_contig_start or d_contig_len, a NULL device buffer with
+ *         n_reads > 0.
+ *       Records (aim_map_records_contigs_device). Rule 12c exactly -- the same d_rec_offsets, ranks, representative, flags and MAPQ
+ *       -- with two changes to a mapped record: sam.pos -= starts[c] with c = d_contig[slot], so the position is contig-local, and
+ *       sam.pad = c. (A d_contig[slot] outside 0..n_contigs - 1 on a mapped slot leaves pos as it is; pad still carries it.) The one
+ *       record of an unmapped read gets sam.pad = AIM_CONTIG_NONE. map_records_contig_kernel takes map_records_kernel's place;
+ *       map_count_kernel and the scan are rule 12c's.
+ *   Mapper. aim_mapper_create_contigs(params, device, n_contigs, seqs, lens, &m) lays the contigs out with
+ *       AIM_CONTIG_SPACER(params->seed.band), concatenates them, uploads the concatenation, builds the index as aim_mapper_create
+ *       does and uploads starts and lens (8 B per contig); aim_mapper_submit then runs the clip in front of the alignment and the
+ *       contig record kernel at the end. aim_mapper_submit, aim_mapper_wait, aim_mapper_out_t and aim_mapper_params_t are unchanged,
+ *       and a mapper made by aim_mapper_create gives the bytes it always gave (pad 0, global pos).
+ *       aim_mapper_device_bytes_contigs is aim_mapper_device_bytes for such a mapper; aim_mapper_contigs returns the layout (views
+ *       that live as long as the mapper; n = 0 and NULL for a mapper of one sequence).
+ *       Refusals of the two, under their own name and before any device query: a NULL params, then the layout's bounds above, then
+ *       every check of aim_mapper_device_bytes / aim_mapper_create on the laid-out ref_len, then a NULL seqs or seqs[c].
+ * aim_contig_kernel_names: "contig_clip_kernel,map_records_contig_kernel".
+ * Not in this version: an extension (rule 11c) that stops at a contig's edge -- it may claim a few read bases against the spacer,
+ * which come back as soft clip --, chains confined to one contig inside the chain kernels, paired-end reads, a contig stage inside
+ * aim_set_submit or host.c. Check aim_features() & AIM_FEATURE_CONTIGS first. */
+#define AIM_CONTIG_MAX (1u << 20)
+#define AIM_CONTIG_NONE 0xFFFFFFFFu
+#define AIM_CONTIG_SPACER(band) ((uint32_t)(band) + 64u)
+#define AIM_SEG_CONTIG_CLIPPED 0x80u /* aim_segment_t.flags, from aim_contig_clip_device */
+int aim_contigs_layout(uint32_t n_contigs, const uint32_t *lens, uint32_t spacer, uint32_t *starts /* [n_contigs] */, uint64_t *ref_len);
+int aim_contigs_concat(uint32_t n_contigs, const char *const *seqs, const uint32_t *lens, uint32_t spacer, char *out /* [ref_len] */);
+int aim_contig_clip_device(uint32_t K, uint32_t read_size, int32_t flank, uint64_t ref_len, uint32_t n_contigs, const uint32_t *d_contig_start,
+                           const uint32_t *d_contig_len, uint32_t n_reads, const int32_t *d_read_len, const void *d_requests, const uint64_t *d_text_pos,
+                           const aim_chain_t *d_chains, void *d_seg_requests, uint64_t *d_seg_text_pos, aim_segment_t *d_seg,
+                           uint32_t *d_contig /* [n_reads * K] */, void *hip_stream);
+int aim_map_records_contigs_device(uint32_t K, uint32_t n_reads, const aim_segment_t *d_seg, const aim_sam_t *d_sam, const aim_chain_class_t *d_class,
+                                   const uint32_t *d_contig /* [n_reads * K] */, uint32_t n_contigs, const uint32_t *d_contig_start,
+                                   uint32_t *d_rec_offsets /* [n_reads + 1] */, aim_map_record_t *d_records /* [n_reads * K] */, void *d_scratch,
+                                   size_t scratch_bytes, void *hip_stream);
+/* Comma-separated rocprofv3 kernel-trace name prefixes of the two kernels rule 13c adds. */
+const char *aim_contig_kernel_names(void);
+int aim_mapper_device_bytes_contigs(const aim_mapper_params_t *params, uint32_t n_contigs, const uint32_t *lens, uint64_t *bytes);
+int aim_mapper_create_contigs(const aim_mapper_params_t *params, int device, uint32_t n_contigs, const char *const *seqs, const uint32_t *lens,
+                              aim_mapper_t **mapper);
+int aim_mapper_contigs(const aim_mapper_t *mapper, uint32_t *n_contigs, const uint32_t **starts, const uint32_t **lens);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);

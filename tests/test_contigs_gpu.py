@@ -1,0 +1,440 @@
+"""References of several sequences on the GPU. aim_contig_clip_device on synthetic slot tables against rule 13c's numpy model, every byte
+of the four buffers, for each K, batch size and contig count below, on a small and a large grid and under the poison knobs;
+aim_map_records_contigs_device on the same tables; Mapper.from_contigs end to end on the shared batch cut into three contigs
+(tests/contig_model.py) with five reads planted on the contig edges, against the stages driven by hand and against the one-sequence
+mapper on the concatenation; two slots and a reused slot; and python -m aim_amd.map --contigs."""
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+KS = (1, 4, 16)
+N_READS = (1, 65, 2100)
+N_CONTIGS = (1, 2, 3, 1024, 1025, 5000)          # 1 024 | 1 025: the sampled table's step goes from 1 to 2; 5 000: step 8
+# every contig count at 65 reads; the ends of the range at the other two sizes (one lane of work, and 33 workgroups of it)
+CONTIGS_FOR = {1: (2, 5000), 65: N_CONTIGS, 2100: (3, 1025)}
+GUARD = 64
+SEED = 21
+
+
+def run_clip(h, K, n, n_contigs, seg_flags=None, keep=False):
+    """aim_contig_clip_device over uploaded tables, 64 guard bytes of 0xEE behind each of the three segment buffers and d_contig
+    (itself prefilled with 0xEE): the four buffers as bytes, guards included."""
+    import contig_model as cg
+    from aim_amd import engine
+    lens, starts, ref_len, d, want = cg.synthetic_clip(SEED, K, n, n_contigs, seg_flags)
+    guard = np.full(GUARD, 0xEE, dtype=np.uint8)
+    up = lambda a: h.up(np.concatenate([np.ascontiguousarray(a).view(np.uint8).reshape(-1), guard]))
+    S = n * K
+    d_sr, d_stp, d_sg, d_ct = up(d["seg_req"]), up(d["seg_text_pos"]), up(d["seg"]), h.up(np.full(4 * S + GUARD, 0xEE, dtype=np.uint8))
+    d_st = h.up(starts)
+    engine.contig_clip_device(K, cg.SYN_READ_SIZE, cg.SYN_FLANK, ref_len, n_contigs, d_st, h.up(lens), n, h.up(d["read_len"]), h.up(d["req"]), h.up(d["text_pos"]),
+                              h.up(d["chains"]), d_sr, d_stp, d_sg, d_ct)
+    got = (h.down(d_sr, 16 * S + GUARD), h.down(d_stp, 8 * S + GUARD), h.down(d_sg, 8 * S + GUARD), h.down(d_ct, 4 * S + GUARD))
+    return (got, (d_sg, d_ct, d_st)) if keep else got
+
+
+def check_clip(K, n, n_contigs, got, seg_flags=None):
+    import contig_model as cg
+    want = cg.synthetic_clip(SEED, K, n, n_contigs, seg_flags)[4]
+    for name, g, w in zip(("seg_req", "seg_text_pos", "seg", "contig"), got, (want["seg_req"], want["seg_text_pos"], want["seg"], want["contig"])):
+        wb = w.view(np.uint8).reshape(-1)
+        if g[:len(wb)].tobytes() != wb.tobytes():
+            item = w.dtype.itemsize
+            bad = np.nonzero((g[:len(wb)].reshape(-1, item) != wb.reshape(-1, item)).any(axis=1))[0]
+            raise AssertionError((K, n, n_contigs, name, bad[:8].tolist(), g[:len(wb)].view(w.dtype)[bad[0]], w[bad[0]]))
+        assert (g[len(wb):] == 0xEE).all(), "written past " + name
+
+
+@pytest.mark.parametrize("K", KS)
+def test_clip_equals_model(K):
+    from test_sam_fields_gpu import Hip
+    h = Hip()
+    try:
+        for n in N_READS:
+            for nc in CONTIGS_FOR[n]:
+                check_clip(K, n, nc, run_clip(h, K, n, nc))
+                h.free()
+    finally:
+        h.free()
+
+
+KNOB_CHILD = '''
+import sys
+import numpy as np
+sys.path.insert(0, "tests")
+import test_contigs_gpu as t
+np.savez(sys.argv[1], **t.knob_batch())
+'''
+KNOB_CASES = ((4, 2100, 5000), (16, 65, 1025), (1, 2100, 3), (4, 65, 1024))
+
+
+def knob_batch():
+    from test_sam_fields_gpu import Hip
+    out = {}
+    h = Hip()
+    try:
+        for i, (K, n, nc) in enumerate(KNOB_CASES):
+            for j, g in enumerate(run_clip(h, K, n, nc)):
+                out["c%d_%d" % (i, j)] = g
+            h.free()
+    finally:
+        h.free()
+    return out
+
+
+@pytest.mark.parametrize("env", [{"AIM_CHIP_CUS": "1", "AIM_DEBUG_POISON_SCRATCH": "165", "AIM_DEBUG_POISON_OPS": "77", "AIM_DEBUG_POISON_LDS": "90"},
+                                 {"AIM_CHIP_CUS": "256", "AIM_DEBUG_POISON_LDS": "255"}], ids=["cus1-poison", "cus256-lds255"])
+def test_grid_and_poison_identical(tmp_path, env):
+    """The same bytes -- the model's -- at AIM_CHIP_CUS 1 (8 workgroups walk the 33 blocks of slots) and 256 and under the three
+    AIM_DEBUG_POISON_* knobs; the plan line names the grid, the contigs and the step."""
+    f = str(tmp_path / "k.npz")
+    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, AIM_PLAN_DEBUG="1", **env), capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    grid = 8 if env["AIM_CHIP_CUS"] == "1" else 33
+    assert "[aim plan] contig_clip_kernel grid=%d block=256 contigs=5000 step=8 slots=8400" % grid in p.stderr, p.stderr
+    assert "[aim plan] contig_clip_kernel grid=5 block=256 contigs=1025 step=2 slots=1040" in p.stderr, p.stderr
+    assert "block=256 contigs=3 step=1 slots=2100" in p.stderr and "[aim plan] contig_clip_kernel grid=2 block=256 contigs=1024 step=1 slots=260" in p.stderr, p.stderr
+    out = np.load(f)
+    for i, (K, n, nc) in enumerate(KNOB_CASES):
+        check_clip(K, n, nc, [out["c%d_%d" % (i, j)] for j in range(4)])
+
+
+@pytest.mark.parametrize("K", KS)
+def test_contig_records_equal_model(K):
+    """map_records_model's slot tables, their aim_segment_t flags driving the clip's synthetic slots, d_contig straight from the clip on
+    the device: offsets and records equal the model byte for byte; n_reads = 0 writes rec_offsets[0] alone."""
+    import contig_model as cg
+    import map_records_model as mm
+    from aim_amd import engine
+    from test_sam_fields_gpu import Hip
+    h = Hip()
+    try:
+        for n, nc in ((1, 1), (65, 3), (2100, 1025)):
+            seg, sam, cls = mm.synthetic_tables(11, K, n)
+            got, (d_sg, d_ct, d_st) = run_clip(h, K, n, nc, seg_flags=seg["flags"], keep=True)
+            check_clip(K, n, nc, got, seg_flags=seg["flags"])
+            lens, starts, ref_len, d, o = cg.synthetic_clip(SEED, K, n, nc, seg["flags"])
+            d_off = h.up(np.full(4 * (n + 1) + GUARD, 0xEE, dtype=np.uint8))
+            d_rec = h.up(np.full(64 * n * K + GUARD, 0xEE, dtype=np.uint8))
+            sb = engine.map_records_scratch(n)
+            engine.map_records_contigs_device(K, n, d_sg, h.up(sam), h.up(cls), d_ct, nc, d_st, d_off, d_rec, h.up(np.full(sb, 0xEE, dtype=np.uint8)), sb)
+            off_b, rec_b = h.down(d_off, 4 * (n + 1) + GUARD), h.down(d_rec, 64 * n * K + GUARD)
+            want_off, want = cg.records(K, n, o["seg"], sam, cls, o["contig"], starts)
+            assert off_b[:4 * (n + 1)].tobytes() == want_off.tobytes() and (off_b[4 * (n + 1):] == 0xEE).all(), (K, n)
+            total = int(want_off[n])
+            g = rec_b[:64 * total].view(mm.RECORD_DTYPE)
+            if g.tobytes() != want.tobytes():
+                bad = np.nonzero((g.view(np.uint8).reshape(total, 64) != want.view(np.uint8).reshape(total, 64)).any(axis=1))[0]
+                raise AssertionError((K, n, nc, bad[:8].tolist(), g[bad[0]], want[bad[0]]))
+            assert (rec_b[64 * total:] == 0xEE).all(), "written past the records"
+            assert (want["sam"]["pad"] == cg.NONE).any() or n == 1
+            h.free()
+        d_off = h.up(np.full(8, 0xEE, dtype=np.uint8))
+        engine.map_records_contigs_device(K, 0, None, None, None, None, 1, None, d_off, None, None, 0)
+        assert h.down(d_off, 8).tolist() == [0, 0, 0, 0, 0xEE, 0xEE, 0xEE, 0xEE]
+    finally:
+        h.free()
+
+
+# ---- the mapper end to end -----------------------------------------------------------------------------------------------------------
+def copy_out(out):
+    return {k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
+
+
+def whole_batch():
+    """The shared 73 reads followed by the five planted ones, and the three contigs."""
+    import contig_model as cg
+    import mapper_batch as mb
+    mo = cg.batch_models()
+    return mo, cg.batch_contigs(mb.batch()["ref"])[1], mo["rows"], mo["read_len"]
+
+
+def map_contigs(mp, seqs, rl, rows):
+    from aim_amd import engine
+    with engine.Mapper.from_contigs(mp, seqs) as m:
+        m.submit(0, rl, rows)
+        return copy_out(m.wait(0)), m.contigs, m.ref_len
+
+
+def hand_path(extend):
+    """test_mapper_gpu.hand_path on the concatenation, with aim_contig_clip_device between the split (or the extension) and the
+    alignment, and rule 13c's record model at the end: a dict shaped like a mapper result."""
+    import torch
+    import chain_class_model as ccm
+    import contig_model as cg
+    import mapper_batch as mb
+    from aim_amd import capi, engine
+    lib = capi.load()
+    mo, seqs, rows, rl = whole_batch()
+    ref, starts, lens = mo["concat"], mo["starts"], mo["lens"]
+    k, stride, w, max_occ, band, flank, min_votes, K = ccm.CHIMERIC_ROW
+    rs, n = ccm.CHIMERIC_SIZE, len(rl)
+    dev = torch.device("cuda:0")
+    params = engine.make_params("wfa", mb.max_score(), rs, mismatch=mb.X, gap_o=mb.O, gap_e=mb.E, backtrace=True, ref_texts=True, ends_free=(0, 0, 2 * flank, 2 * flank))
+    rows_n = n * K
+    d_ref = torch.zeros(len(ref) + 64, dtype=torch.uint8, device=dev)
+    d_ref[:len(ref)] = torch.from_numpy(ref).to(dev)
+    sp = engine.seed_params(k, rs, stride=stride, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K, w=w)
+    out = engine.split_segments(sp, engine.chain_classify(sp, engine.seed_chain_candidates(sp, engine.index_build_minimizers(ref, k, w), len(ref), rl, rows)), len(ref))
+    if extend:
+        out = engine.extend_segments(sp, out, d_ref[:len(ref)], engine.extend_params(*mb.EXTEND))
+    d_st, d_ln = torch.from_numpy(starts.view(np.int32)).to(dev), torch.from_numpy(lens.view(np.int32)).to(dev)
+    d_ct = torch.full((rows_n,), -286331154, dtype=torch.int32, device=dev)        # 0xEEEEEEEE
+    torch.cuda.synchronize()
+    engine.contig_clip_device(K, rs, flank, len(ref), len(starts), d_st.data_ptr(), d_ln.data_ptr(), n, out["d_read_len"].data_ptr(), out["d_req"].data_ptr(),
+                              out["d_text_pos"].data_ptr(), out["d_chains"].data_ptr(), out["d_seg_req"].data_ptr(), out["d_seg_text_pos"].data_ptr(),
+                              out["d_seg"].data_ptr(), d_ct.data_ptr())
+    torch.cuda.synchronize()
+    seg = out["d_seg"].cpu().numpy().view(capi.SEGMENT_DTYPE)[:rows_n]
+    contig = d_ct.cpu().numpy().view(np.uint32)
+    d_res = torch.zeros(rows_n * capi.RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    d_ops = torch.zeros(rows_n * 2 * rs + 64, dtype=torch.uint8, device=dev)
+    sb = lib.aim_scratch_bytes(capi.params_ref(params), rows_n)
+    d_scr = torch.zeros(max(sb, 16), dtype=torch.uint8, device=dev)
+    ccap, mcap = rows_n * 64, rows_n * 256
+    buf = (torch.zeros(rows_n * 48, dtype=torch.uint8, device=dev), torch.zeros(ccap * 4, dtype=torch.uint8, device=dev),
+           torch.zeros(mcap, dtype=torch.uint8, device=dev), torch.zeros(8, dtype=torch.uint8, device=dev))
+    torch.cuda.synchronize()
+    rc = lib.aim_align_device_ref(capi.params_ref(params), rows_n, out["d_seg_req"].data_ptr(), out["d_seg_patterns"].data_ptr(), out["d_seg_text_pos"].data_ptr(),
+                                  d_ref.data_ptr(), len(ref), d_res.data_ptr(), d_ops.data_ptr(), d_scr.data_ptr(), sb, None)
+    assert rc == 0, lib.aim_last_error()
+    engine.sam_device_split(params, rows_n, out["d_seg_req"].data_ptr(), out["d_seg_text_pos"].data_ptr(), None, d_res.data_ptr(), d_ops.data_ptr(), d_ref.data_ptr(),
+                            len(ref), 0, buf[0].data_ptr(), buf[1].data_ptr(), ccap, buf[2].data_ptr(), mcap, buf[3].data_ptr(), out["d_seg"].data_ptr())
+    torch.cuda.synchronize()
+    sam = buf[0].cpu().numpy().view(capi.SAM_DTYPE)
+    off, rec = cg.records(K, n, seg, sam, out["class"], contig, starts)
+    return {"records": rec, "rec_offsets": off, "cigar": buf[1].cpu().numpy().view(np.uint32), "md": buf[2].cpu().numpy()}, seg, contig
+
+
+def inside(rec, lens):
+    """pos + ref_span <= lens[pad] for every mapped record."""
+    from aim_amd import capi
+    s = rec["sam"]
+    mapped = (s["flags"] & capi.SAM_UNMAPPED) == 0
+    return mapped, s["pos"][mapped].astype(np.int64) + s["ref_span"][mapped] <= lens[s["pad"][mapped]].astype(np.int64)
+
+
+def end_to_end():
+    import chain_class_model as ccm
+    import contig_model as cg
+    import mapper_batch as mb
+    import split_model as sm
+    from aim_amd import capi, engine
+    mo, seqs, rows, rl = whole_batch()
+    K, nb, n = mo["K"], mo["n_batch"], len(rl)
+    starts, lens = mo["starts"], mo["lens"]
+    for extend in (False, True):
+        mp = mb.mapper_params(n, extend)
+        got, layout, ref_len = map_contigs(mp, seqs, rl, rows)
+        assert layout[0].tolist() == starts.tolist() and layout[1].tolist() == lens.tolist() and ref_len == mo["ref_len"]
+        # ---- the stages by hand, the clip among them, and the record model ----
+        want, seg, contig = hand_path(extend)
+        g, w = mb.canon(got), mb.canon(want)
+        assert g[1] == w[1], "rec_offsets"
+        assert g[0] == w[0], ("records", np.nonzero(np.frombuffer(g[0], dtype=np.uint8) != np.frombuffer(w[0], dtype=np.uint8))[0][:8] // 64)
+        assert g[2] == w[2] and g[3] == w[3], "CIGAR words or MD bytes"
+        # the clip on the device did what the models said it would: nothing in the shared batch, the four single-piece planted reads
+        clipped = ((seg["flags"] & cg.CLIPPED) != 0).reshape(-1, K)
+        assert not clipped[:nb].any() and clipped[[nb, nb + 1, nb + 2, nb + 3, nb + 5, nb + 6]].astype(int).tolist() == [[1, 0, 0, 0]] * 6, clipped[nb:]
+        assert extend or not clipped[nb + 4].any()
+        if not extend:
+            assert seg.tobytes() == mo["clip"]["seg"].tobytes() and contig.tobytes() == mo["clip"]["contig"].tobytes()
+        # ---- the one-sequence mapper on the concatenation: the same record bytes but for pos and pad; no record of the batch is left out ----
+        with engine.Mapper(mp, mo["concat"]) as m:
+            m.submit(0, rl, rows)
+            one = copy_out(m.wait(0))
+        assert one["rec_offsets"].tobytes() == got["rec_offsets"].tobytes()
+        rec, rec1 = got["records"], one["records"]
+        first_planted = int(got["rec_offsets"][nb])
+        a, b = rec[:first_planted].copy(), rec1[:first_planted].copy()
+        mapped = (a["sam"]["flags"] & capi.SAM_UNMAPPED) == 0
+        assert (b["sam"]["pad"] == 0).all() and (a["sam"]["pad"][~mapped] == cg.NONE).all()
+        assert (b["sam"]["pos"][mapped] - a["sam"]["pos"][mapped] == starts[a["sam"]["pad"][mapped]]).all() and (a["sam"]["pos"][~mapped] == 0).all()
+        for x in (a, b):
+            for f in ("pos", "pad", "cigar_offset", "md_offset"):    # (the two offsets depend on scheduling: the words and bytes behind them are compared below)
+                x["sam"][f] = 0
+        assert a.tobytes() == b.tobytes(), np.nonzero(a.view(np.uint8).reshape(-1, 64) != b.view(np.uint8).reshape(-1, 64))
+        o = mb.canon(one)
+        assert g[2][:first_planted] == o[2][:first_planted] and g[3][:first_planted] == o[3][:first_planted]
+        # every record of the shared batch sits on the contig, and at the place in it, that its truth says
+        b_ = mb.batch()
+        flank = ccm.CHIMERIC_ROW[5]
+        for i in np.nonzero(mapped)[0]:
+            r = int(a["read"][i])
+            if r < mb.N_CHIMERIC:
+                hf = sm.half_of(b_["halves"][r], int(a["q_begin"][i]), int(a["q_end"][i]))
+                lo, hi, slack = hf["ref_lo"], hf["ref_hi"], flank + hf["edits"]
+            else:
+                lo, hi = b_["truth"][r - mb.N_CHIMERIC][:2]
+                slack = flank + mb.UNBROKEN_EDITS
+            c, local = cg.to_concat(lo)
+            pos, span = int(rec["sam"]["pos"][i]), int(rec["sam"]["ref_span"][i])
+            assert int(rec["sam"]["pad"][i]) == c and local - slack <= pos and pos + span <= local + (hi - lo) + slack, (r, rec[i])
+        # ---- the planted reads ----
+        off = got["rec_offsets"]
+        counts = np.diff(off.astype(np.int64))[nb:]
+        assert counts.tolist() == [1, 1, 1, 1, 2, 1, 1], counts
+        words = g[2]
+        for j, (contigs, strand, beyond) in enumerate(mo["what"]):
+            grp = range(int(off[nb + j]), int(off[nb + j + 1]))
+            assert [int(rec[i]["sam"]["pad"]) for i in grp] == list(contigs), (j, [rec[i] for i in grp])
+            assert sum(int(rec[i]["sam"]["flags"]) & sm.SAM_SUPPLEMENTARY != 0 for i in grp) == len(grp) - 1
+            for i in grp:
+                s = rec[i]["sam"]
+                assert not int(s["flags"]) & sm.SAM_UNMAPPED and (int(s["flags"]) & sm.SAM_REVERSE != 0) == bool(strand)
+                if len(contigs) == 1 or not extend:         # (the extension may lean an inner side of the junction read on the spacer: the issue's note)
+                    assert bool(int(rec[i]["seg_flags"]) & cg.CLIPPED) == (len(contigs) == 1)
+                assert 0 <= int(s["pos"]) and int(s["pos"]) + int(s["ref_span"]) <= int(lens[int(s["pad"])]), rec[i]
+                assert sm.read_consumed(words[i]) == int(rl[nb + j]), (j, words[i])
+            if len(contigs) == 1:                                   # the 300 bases at the contig's edge, the others soft-clipped
+                s = rec[grp[0]]["sam"]
+                at_start = contigs[0] == 1
+                assert int(s["ref_span"]) == cg.PLANT_PIECE and int(s["pos"]) == (0 if at_start else int(lens[0]) - cg.PLANT_PIECE) and int(s["nm"]) == 0
+                clip_first = at_start                                # (the words run along the reference, whatever the read's strand)
+                assert words[grp[0]] == ([(beyond << 4) | 4, cg.PLANT_PIECE << 4] if clip_first else [cg.PLANT_PIECE << 4, (beyond << 4) | 4])
+        m_all, ok = inside(rec, lens)
+        assert ok.all(), rec[m_all][~ok]
+        # ---- and what the clip is for: the one-sequence mapper's records of the planted reads, two flags per read. bound: the record
+        # as that mapper returns it (pad 0, pos in the concatenation) breaks pos + ref_span <= lens[pad]; leaves: the aligned interval
+        # itself runs over an edge of the contig its pos lies in ----
+        bound, leaves = [], []
+        for j in range(cg.N_PLANTED):
+            grp1 = rec1[int(off[nb + j]):int(off[nb + j + 1])]
+            pos1 = grp1["sam"]["pos"].astype(np.int64)
+            end1 = pos1 + grp1["sam"]["ref_span"]
+            bound.append(int((end1 > lens[grp1["sam"]["pad"]].astype(np.int64)).any()))
+            c1 = np.searchsorted(starts, pos1, side="right") - 1
+            leaves.append(int(((end1 > starts[c1].astype(np.int64) + lens[c1]) | (pos1 >= starts[c1].astype(np.int64) + lens[c1])).any()))
+        print("ONE_SEQUENCE extend=%d %s" % (extend, json.dumps({"bound": bound, "leaves": leaves,
+                                                                  "pos_span": [(int(o["sam"]["pos"]), int(o["sam"]["ref_span"])) for o in rec1[first_planted:]]})))
+        assert leaves[5:] == [1, 1], leaves                          # one base beyond the edge: a mismatch against the spacer is the cheaper end
+
+
+PATH_CHILD = '''
+import sys
+import torch
+torch.cuda.init()   # (before the library: the hand-driven path's buffers are torch's)
+sys.path.insert(0, "tests")
+import test_contigs_gpu as t
+t.end_to_end()
+print("CONTIGS_END_TO_END_OK")
+'''
+
+
+_CHILD = {}
+
+
+def end_to_end_child():
+    """end_to_end() in a child process, once for the tests that read its output."""
+    if "p" not in _CHILD:
+        _CHILD["p"] = subprocess.run([sys.executable, "-c", PATH_CHILD], cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=300)
+    return _CHILD["p"]
+
+
+def test_end_to_end_equals_the_stages_by_hand_and_the_concatenation():
+    """Mapper.from_contigs on the 73 shared reads and the seven planted ones equals the stages by hand with the clip among them plus
+    the record model, with and without AIM_MAP_EXTEND, and equals the one-sequence mapper on the concatenation in every record byte of
+    the shared batch but pos and pad; every planted read gives the records it was planted for, inside the contig they name; and the
+    one-sequence mapper carries the two reads with one base beyond the edge out of their contig."""
+    p = end_to_end_child()
+    print(p.stdout[-3000:])
+    assert p.returncode == 0 and "CONTIGS_END_TO_END_OK" in p.stdout, p.stdout + p.stderr
+
+
+def test_one_sequence_mapper_breaks_the_bound_on_the_planted_reads():
+    """The bound every record of Mapper.from_contigs keeps, pos + ref_span <= lens[pad], put to the one-sequence mapper's records of
+    the planted reads as that mapper returns them (pad 0, pos in the concatenation): it is broken, so the planted reads do exercise
+    what rule 13c adds. Read by read, with and without the extension (measured on an MI355X):
+      24 bases in front of contig 1, both strands   pos 20 160, ref_span 300    broken: the position is the concatenation's
+      24 bases behind contig 0, both strands        pos 19 700, ref_span 300    kept: 20 000 <= lens[0] = 20 000
+      the junction read                             19 700 / 20 163 (20 160)    broken by its half on contig 1
+      one base in front of contig 1                 pos 20 159, ref_span 301    broken, and the interval itself starts in the spacer
+      one base behind contig 0                      pos 19 700, ref_span 301    broken by the one base: 20 001
+    What the 24-base reads do not do is carry an alignment over a contig's edge: 24 mismatches against the spacer's 'N' cost 72, a gap
+    of 24 costs 28, so the one-sequence mapper ends them at the edge too, and the two of them that lie on contig 0 keep the bound
+    even as it stands. The one-base reads (a mismatch 3, a gap 5) are there for that; the end-to-end test asserts them."""
+    p = end_to_end_child()
+    rows = [json.loads(l.split(" ", 2)[2]) for l in p.stdout.splitlines() if l.startswith("ONE_SEQUENCE ")]
+    assert len(rows) == 2, p.stdout + p.stderr
+    for row in rows:
+        print(row)
+        assert row["bound"] == [1, 0, 1, 0, 1, 1, 1], row
+        assert row["leaves"] == [0, 0, 0, 0, 0, 1, 1], row
+
+
+def test_two_slots_and_a_reused_slot():
+    """Batches A and B back to back on two slots equal A and B run alone; a slot used three times returns the third batch's result; a
+    mapper of one sequence next to it still gives pad 0 and global positions."""
+    import mapper_batch as mb
+    from aim_amd import engine
+    mo, seqs, rows, rl = whole_batch()
+    A, B, C3 = slice(0, 40), slice(40, 80), slice(30, 70)
+    mp = mb.mapper_params(40, True, slots=2)
+    alone = {k: mb.canon(map_contigs(mp, seqs, rl[s], rows[s])[0]) for k, s in (("A", A), ("B", B), ("C", C3))}
+    assert alone["A"] != alone["C"] and alone["B"] != alone["C"]
+    with engine.Mapper.from_contigs(mp, seqs) as m:
+        assert m.contigs[0].tolist() == mo["starts"].tolist() and m.contigs[1].tolist() == mo["lens"].tolist()
+        m.submit(0, rl[A], rows[A])
+        m.submit(1, rl[B], rows[B])
+        assert mb.canon(m.wait(0)) == alone["A"] and mb.canon(m.wait(1)) == alone["B"]
+        for s in (B, A, C3):
+            m.submit(1, rl[s], rows[s])
+            last = mb.canon(m.wait(1))
+        assert last == alone["C"]
+        m.submit(0, rl[:0], rows[:0])
+        out = m.wait(0)
+        assert out["n_reads"] == 0 and len(out["records"]) == 0 and out["rec_offsets"].tolist() == [0]
+    with engine.Mapper(mp, mo["concat"]) as m:
+        assert m.contigs is None
+        m.submit(0, rl[B], rows[B])
+        assert (m.wait(0)["records"]["sam"]["pad"] == 0).all()
+
+
+def test_command_line_with_contigs(tmp_path):
+    """python -m aim_amd.map --contigs in a child process: three @SQ lines, and the body is samout over the mapper's own records."""
+    import chain_class_model as ccm
+    import contig_model as cg
+    import mapper_batch as mb
+    from aim_amd import samout
+    mo, seqs, rows, rl = whole_batch()
+    n = len(rl)
+    k, stride, w, max_occ, band, flank, min_votes, K = ccm.CHIMERIC_ROW
+    names = ["read%d" % r for r in range(n)]
+    cnames = cg.batch_contigs(mb.batch()["ref"])[0]
+    with open(tmp_path / "ref.fa", "wb") as f:
+        for name, s in zip(cnames, seqs):
+            f.write(b">%s a contig\n" % name.encode() + b"\n".join(s.tobytes()[i:i + 70] for i in range(0, len(s), 70)) + b"\n")
+    with open(tmp_path / "reads.fq", "wb") as f:
+        for r in range(n):
+            f.write(b"@%s\n%s\n+\n%s\n" % (names[r].encode(), rows[r, :rl[r]].tobytes(), b"I" * int(rl[r])))
+    cmd = [sys.executable, "-m", "aim_amd.map", "--contigs", "--ref", str(tmp_path / "ref.fa"), "--reads", str(tmp_path / "reads.fq"), "-o", str(tmp_path / "out.sam"),
+           "--batch", "40", "--read-size", str(ccm.CHIMERIC_SIZE), "-k", str(k), "-w", str(w), "--max-occ", str(max_occ), "--band", str(band), "--flank", str(flank),
+           "--min-votes", str(min_votes), "--max-cands", str(K), "--max-score", str(mb.max_score()), "--extend"]
+    p = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout + p.stderr
+    text = open(tmp_path / "out.sam").read().splitlines()
+    head, body = [l for l in text if l.startswith("@")], [l for l in text if not l.startswith("@")]
+    assert [l[:3] for l in head] == ["@HD", "@SQ", "@SQ", "@SQ", "@PG"]
+    assert head[1:4] == ["@SQ\tSN:%s\tLN:%d" % (nm, len(s)) for nm, s in zip(cnames, seqs)]
+    upper = [np.frombuffer(s.tobytes().upper(), dtype=np.uint8) for s in seqs]     # the command line upper-cases the reference
+    want = samout.record_lines(map_contigs(mb.mapper_params(n, True), upper, rl, rows)[0], names, rows, rl, cnames, ["I" * int(x) for x in rl])
+    assert len(body) == len(want) == 2 * mb.N_CHIMERIC + mb.N_UNBROKEN + mb.N_RANDOM + cg.N_PLANTED + 1
+    assert body == want
+    # every line lies inside the sequence it names
+    ln = dict(zip(cnames, (len(s) for s in seqs)))
+    for l in body:
+        f = l.split("\t")
+        if f[2] != "*":
+            span = sum(int(x) for x, op in re.findall(r"(\d+)([MIDNSHP=X])", f[5]) if op in "MDN=X")
+            assert 1 <= int(f[3]) and int(f[3]) - 1 + span <= ln[f[2]], l
