@@ -6,8 +6,8 @@
 
 `python -m aim_amd.build` builds both; nothing is JIT-compiled at import time.
 
-The library is several translation units -- the C-ABI in aim_capi.hip (planning, device sets, the alignment entry points, the
-small batch-I/O kernels), capi_pipeline.hip (index, seeding, classes, split, extension), capi_mapper.hip (the record list and the
+The library is several translation units -- the C-ABI in aim_capi.hip (device sets, launching, the alignment entry points, the
+small batch-I/O kernels), capi_plan.hip (the launch planner: host code only), capi_pipeline.hip (index, seeding, classes, split, extension), capi_mapper.hip (the record list and the
 mapper object) and capi_host.hip (host-side helpers), and
 one tu_*.hip per kernel family, each of which instantiates the kernels of ONE header -- compiled in parallel into build/obj/ and linked
 once: a full rebuild takes as long as the slowest family instead of the sum, and editing one kernel header recompiles only

@@ -85,7 +85,7 @@ __device__ __forceinline__ void debug_poison_lds(uint32_t poison, uint32_t lds_b
 __device__ __forceinline__ void debug_poison_lds(const KArgs &a, char *smem) { debug_poison_lds(a.dbg_poison_lds, a.dbg_lds_bytes, smem); }
 
 // Run-time knobs (the AIM_* environment variables). They are experiment / debugging switches, not configuration: every
-// one of them leaves results bit-identical. They are read in ONE place (read_knobs, aim_capi.hip) into this struct --
+// one of them leaves results bit-identical. They are read in ONE place (read_knobs, capi_plan.hip) into this struct --
 // once per aim_set_configure (frozen in the set together with the plan) and once per stateless entry point -- and the
 // planners below only ever see the struct, so plan selection cannot change between a set's configure and its launches.
 struct Knobs {
@@ -124,7 +124,7 @@ struct Knobs {
     int class_g = -1;             // AIM_CLASS_G         chain_class_kernel: lanes per read, 8 or 16 where K would take fewer (A/B runs)
     bool plan_debug = false;      // AIM_PLAN_DEBUG=1    print the chosen plan to stderr
     // Not a knob but the one fact about the chip every plan needs: compute units of the device the plan is made for
-    // (hipDeviceAttributeMultiprocessorCount, read once per device by chip_cus() in aim_capi.hip: 256 on a whole MI355X, 128 / 64 / 32
+    // (hipDeviceAttributeMultiprocessorCount, read once per device by chip_cus() in capi_plan.hip: 256 on a whole MI355X, 128 / 64 / 32
     // in DPX / QPX / CPX partitions). AIM_CHIP_CUS overrides it (CPU tests plan for devices this host does not have).
     uint32_t cus = 256;
 };

@@ -14,6 +14,7 @@
 #pragma once
 
 #include "aim_device.hpp"
+#include "batch_sizes.hpp"
 
 namespace aim {
 
@@ -439,9 +440,7 @@ __global__ __launch_bounds__(256) void gather_todo_rows_kernel(KArgs a, const ui
 // escalate_select_kernel reads each score once and keeps one ballot mask per 64 pairs plus one count per workgroup (kEscTile pairs);
 // escalate_list_kernel (same grid) turns masks and counts into list positions -- a workgroup's base is the sum of the counts before it --
 // so the list does not depend on scheduling. Plain vector stores, no atomics. The masks and counts are read 1/64th of the results' bytes.
-constexpr uint32_t kEscTile = 4096;                          // pairs per workgroup: 4 wavefronts x 16 groups of 64
-inline size_t escalate_mask_bytes(uint32_t n_pairs) { return (((size_t)n_pairs + 63) / 64 * 8 + 255) & ~(size_t)255; }
-inline size_t escalate_count_bytes(uint32_t n_pairs) { return ((((size_t)n_pairs + kEscTile - 1) / kEscTile) * 4 + 255) & ~(size_t)255; }
+// (kEscTile, escalate_mask_bytes and escalate_count_bytes: batch_sizes.hpp, which the planner includes without these kernels)
 
 // res: result_t rows (stride_dw 6, score_dw 3) or {idx, score} rows (2, 1)
 __global__ __launch_bounds__(256) void escalate_select_kernel(const uint32_t *res, uint32_t n_pairs, uint32_t stride_dw, uint32_t score_dw, int32_t over,

@@ -1,9 +1,10 @@
-// capi_common.hpp -- what the units of the C-ABI share: aim_capi.hip (planner, device sets, alignment entry points), capi_pipeline.hip
-// (index, seeding, classes and MAPQ, split, extension), capi_mapper.hip (the record list and aim_mapper_t) and capi_host.hip (host-side
-// formatters and generators). Internal, not installed.
-// Every function declared here has ONE definition: in aim_capi.hip, next to the state it owns -- fail() writes the thread-local buffer
-// aim_last_error() returns, read_knobs() is the one reader of the AIM_* environment, with_chip() asks chip_cus()'s per-device cache --,
-// in capi_pipeline.hip for the parameter checks of its stages, or inline below for the refusals the pipeline's entry points share.
+// capi_common.hpp -- what the units of the C-ABI share: aim_capi.hip (device sets, launching, alignment entry points), capi_plan.hip (the
+// launch planner; its types and entry points are in plan.hpp), capi_pipeline.hip (index, seeding, classes and MAPQ, split, extension),
+// capi_mapper.hip (the record list and aim_mapper_t) and capi_host.hip (host-side formatters and generators). Internal, not installed.
+// Every function declared here has ONE definition, next to the state it owns: fail() in aim_capi.hip, where it writes the thread-local
+// buffer aim_last_error() returns; read_knobs(), the one reader of the AIM_* environment, with_chip(), which asks chip_cus()'s per-device
+// cache, and check_align_params() in capi_plan.hip; the parameter checks of the pipeline's stages in capi_pipeline.hip; the refusals the
+// pipeline's entry points share inline below.
 #pragma once
 #include <cstdint>
 
@@ -24,7 +25,7 @@ int check_lengths(const aim_params_t &p, uint32_t n_pairs, const void *requests)
 uint32_t packed_row_dwords(int read_size);
 // AIM_FLAG_REF_TEXTS: texts gathered from a device-resident reference (batch_io.hpp); no plan depends on it.
 inline bool is_ref(const aim_params_t &p) { return (p.flags & AIM_FLAG_REF_TEXTS) != 0; }
-// What every alignment entry point refuses about its aim_params_t (aim_capi.hip: validate_params), before any device query.
+// What every alignment entry point refuses about its aim_params_t (capi_plan.hip: validate_params), before any device query.
 int check_align_params(const aim_params_t &p);
 // The bounds every seeding entry point sets (capi_pipeline.hip). max_read_size is AIM_SEED_MAX_READ_SIZE, or the entry point's own bound,
 // and then `fn` names that entry point in the read_size message.

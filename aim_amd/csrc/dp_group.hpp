@@ -122,7 +122,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         rq.pattern_len = rq.text_len = 0; rq.padding = 0; rq.idx = 0;
         if (valid) rq = load_request(a, pair);
         int plen = rq.pattern_len, tlen = rq.text_len;
-        // not this kernel's: an empty sequence, aliasing beyond one row (plen > 2 tlen), lengths beyond the rows (the literal kernels report those)
+        // not this kernel's: an empty sequence, lengths beyond the rows (the literal kernels report those)
         const bool outl = valid && (plen < 1 || tlen < 1 || plen > rs || tlen > rs);   // (until round 6 also plen > 2 tlen: the last row's tail cells below take any plen now)
         {
             const unsigned long long m = __ballot(outl && g == 0), below = (1ull << lane) - 1ull;

@@ -72,7 +72,8 @@ __device__ __forceinline__ int flat_to_slab(int f, int W, int S, int plen, int t
 }
 
 // Can any int16 store of the NW recurrence wrap? All costs non-negative and every cell bounded by a gap-only path:
-// (2*READ_SIZE + 4) * max(gap_i, gap_d) + 2 * mismatch < 32000 (the bound dp_wave_exact_ok uses). If not, the reference's
+// (2*READ_SIZE + 4) * max(gap_i, gap_d) + 2 * mismatch < 32000 (dp_wave_exact_ok's bound until round 6; for costs >= 0 it now proves
+// (READ_SIZE + 4) * max(min(x, gi + gd), gi, gd) + 2 * mismatch + 2 * max(gi, gd) < 32000, this test kept the gap-only bound). If not, the reference's
 // (int16) casts on every intermediate are identities and nw_lane_kernel<.., NOWRAP = true> computes in int without them
 // (3-4 sign-extension instructions per cell); storage stays int16 either way.
 __host__ __device__ inline bool nw_lane_nowrap(const aim_params_t &p)

@@ -24,6 +24,8 @@
 //     value-comparison walk over flat indices.
 // Pairs outside these preconditions (plen > 2*tlen, possible int16 wrap, int8 cells) take a literal
 // single-lane path over a flat table in the same slab: correct for everything, slow, and rare.
+// (This list is dp_wave_kernel's. dp_strip_kernel and dp_group_kernel have no literal path: since round 6 they take plen > 2*tlen
+// themselves, and the plans keep possible int16 wrap and int8 cells away from them -- dp_strip_supported, dp_group_supported.)
 #pragma once
 
 #include <cstdlib>

@@ -1194,7 +1194,7 @@ void wfa_group_tb_launch(const aim_params_t &p, const GroupCfg &c, uint32_t n_pa
         hipLaunchKernelGGL((wfa_group_tb_kernel<false, false, false, false, true>), dim3(grid), dim3(kWave), 0, s, ka, c);
         return;
     }
-    if (p.flags & AIM_FLAG_ENDSFREE) {   // (ops rows only: the plan never fuses the run output of an ends-free launch, aim_capi.hip)
+    if (p.flags & AIM_FLAG_ENDSFREE) {   // (ops rows only: the plan never fuses the run output of an ends-free launch, capi_plan.hip)
         hipLaunchKernelGGL((wfa_group_tb_kernel<false, false, true>), dim3(grid), dim3(kWave), 0, s, ka, c);
         return;
     }

@@ -620,7 +620,7 @@ __global__ __launch_bounds__(64) void wfa_wave_kernel(KArgs a)
     }
 }
 
-// What make_plan (aim_capi.hip) launches wfa_wave_kernel with, alone or over a lane / group kernel's to-do list.
+// What make_plan (capi_plan.hip) launches wfa_wave_kernel with, alone or over a lane / group kernel's to-do list.
 struct WfaWavePlan {
     uint32_t grid;
     size_t lds;

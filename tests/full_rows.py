@@ -259,7 +259,7 @@ def feature_params(feature, rs, backtrace=True):
 ROWS = [(fam, rs) for fam, rows in TABLE.items() for rs, _ in rows]
 KERNEL_NAMES = ("wfa_wave_kernel", "wfa_bidir_kernel", "wfa_lane_kernel", "wfa_lane_packed_kernel", "wfa_group_kernel", "nw_lane_kernel",
                 "swg_lane_kernel", "nw_reg_kernel", "swg_reg_kernel", "dp_wave_kernel", "dp_strip_kernel", "dp_group_kernel",
-                "genasm_wave_kernel")      # kernel_name(), aim_capi.hip
+                "genasm_wave_kernel")      # kernel_name(), capi_plan.hip
 SEED = 20261
 
 

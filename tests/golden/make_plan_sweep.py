@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/plan_sweep.json.gz: what the planner (make_plan, aim_capi.hip) decides over a wide grid of
+"""Generate tests/golden/plan_sweep.json.gz: what the planner (make_plan, capi_plan.hip) decides over a wide grid of
 configurations, as the stateless planning entry points report it.
 
 Every row holds the params, n_pairs, the env setting, aim_plan_describe's rc and line (aim_last_error() when rc != 0) and

@@ -7,7 +7,7 @@ import re
 
 from conftest import GOLDEN, judge_abort_cases, judge_case_input, judge_cases, judge_costs
 
-# The planner's switches (aim_capi.hip read_knobs) that re-route a batch to another kernel: name, environment. AIM_DEBUG_FLAGS is
+# The planner's switches (capi_plan.hip read_knobs) that re-route a batch to another kernel: name, environment. AIM_DEBUG_FLAGS is
 # left out: it acts in diagnostic builds only. AIM_SCRATCH_GB=1 reaches int8 SWG's fallback from swg_lane to dp_wave.
 KNOBS = [
     ("default", {}),

@@ -157,9 +157,9 @@ def test_the_table_reaches_the_kernels_and_shapes_it_names(plans):
 
 
 def test_every_kernel_name_is_reached(plans):
-    """kernel_name() (aim_capi.hip) lists 13 kernels; wfa_wave and nw_lane are reached through AIM_FORCE_WAVE / AIM_NO_NW_REG,
+    """kernel_name() (capi_plan.hip) lists 13 kernels; wfa_wave and nw_lane are reached through AIM_FORCE_WAVE / AIM_NO_NW_REG,
     wfa_bidir through its flag (a feature row)."""
-    src = open(os.path.join(ROOT, "aim_amd", "csrc", "aim_capi.hip")).read()
+    src = open(os.path.join(ROOT, "aim_amd", "csrc", "capi_plan.hip")).read()
     body = src[src.index("const char *kernel_name("):]
     body = body[:body.index("\n}\n")]
     import re

@@ -1,5 +1,6 @@
 """dp_strip_shape's cost rule against the measurements it was derived from (round 6, NOTES R6.7): for every row of the committed sweeps
-(profiles/r06/strip_shape_sweep.txt: 1 024 pairs; strip_shape_sweep_few.txt: 256 / 512 pairs -- tools/strip_shape_sweep.py forces 16 / 20 / 24 / 32 cells per
+(tests/golden/strip_shape_sweep.txt: 1 024 pairs; strip_shape_sweep_few.txt: 256 / 512 pairs, copies of the files of profiles/r06 as round 6 left
+them, so that a later profiling run cannot change what this test reads -- tools/strip_shape_sweep.py forces 16 / 20 / 24 / 32 cells per
 lane on one MI355X) the shape the PLAN chooses for that READ_SIZE / batch size must be the fastest measured one or within 20 % of it. Runs on the CPU: planning is
 pure (aim_plan_describe), the numbers are fixtures."""
 import ctypes as C
@@ -14,7 +15,7 @@ CELL = re.compile(r"(\d+): dp_strip w(\d+) k(\d+) ([\d.]+) ms (\d+)")
 
 
 def _rows(name):
-    for line in open(os.path.join(ROOT, "profiles", "r06", name)):
+    for line in open(os.path.join(ROOT, "tests", "golden", name)):
         m = ROW.match(line)
         if not m:
             continue
