@@ -13,7 +13,8 @@
 //   once the image is in registers: the P side between the P pack's steps, the T side and the request
 //   thinned out over the T pack, the diagonal construction and two thirds of the score loop, so that each
 //   of a CU's 8 waves has a load about to issue in every phase; all of it older than the result store,
-//   which the loop top's counted wait leaves in flight)--> linear LDS image --> each lane reads ITS row with
+//   which the loop top's counted wait leaves in flight -- where there is one: score-only {idx, score} results collect in an
+//   LDS ring and leave eight groups at a time, in front of an iteration's DMA, AIM_LANE_RES_RING)--> linear LDS image --> each lane reads ITS row with
 //   ds_read_b128 at compile-time offsets (row = odd number of 16-B slots: conflict-free), validates the
 //   alphabet and packs 2 bits/base with v_dot4: pattern and text become RS/16 dwords each in VGPRs.
 //   affine_wfa_extend (wfa.c:186-208) becomes bit-parallel: for diagonal k, D_k = P xor (T shifted by k
@@ -25,6 +26,7 @@
 // downstream is unchanged -- no to-do list, no second kernel, no counter to reset between launches.
 #pragma once
 
+#include <cassert>
 #include <utility>
 
 #include "aim_device.hpp"
@@ -49,8 +51,20 @@
 #define AIM_LANE_ASM_ROWS 1       // 1 = the loop top's LDS reads (request, P rows, T rows) are one inline-asm statement the compiler does not see
 #endif                            // (read_group): it otherwise puts s_waitcnt vmcnt(0) in front of them and undoes the counted wait (-2 %)
 #ifndef AIM_LANE_NT_STORE
-#define AIM_LANE_NT_STORE 0       // 1 = score-only result stores are nontemporal
+#define AIM_LANE_NT_STORE 0       // 1 = score-only result stores are nontemporal (measured +1 % slower on the direct store, NOTES A.1 item 6)
 #endif
+#ifndef AIM_LANE_RES_RING
+#define AIM_LANE_RES_RING 8       // score-only {idx, score} (AIM_FLAG_RES8) results: K > 0 = the results of K full groups collect in an LDS ring
+#endif                            // (ds_write_b64 per lane and group) and leave as K / 2 global_store_dwordx4 at the top of the following iteration,
+                                  // in front of that iteration's DMA; 0 = one global_store_dwordx2 per lane and group. 0, 4 or 8 (LDS: 512 B per slot;
+                                  // K <= 10 keeps AIM_LANE_WGS_PER_CU workgroups on a CU). 8 with sc1 stores: -5.6 % (profiles/lane_store); 8 with
+                                  // plain stores or sc1 without the ring: nothing in production; 4 did not pass the stream + store floor
+#ifndef AIM_LANE_STORE_X4
+#define AIM_LANE_STORE_X4 0       // direct {idx, score} store: 1 = lane pairs exchange their results (DPP) and the even lanes store 16 B
+#endif                            // (measured: nothing, with or without sc1, profiles/lane_store)
+#ifndef AIM_LANE_STORE_SC1
+#define AIM_LANE_STORE_SC1 1      // cache policy sc1 instead of plain: 1 = on the {idx, score} stores (direct and ring), 2 = also on the default layout's two
+#endif                            // (2 measured on the default-layout row: see profiles/lane_store)
 #ifndef AIM_LANE_PACK_X2
 #define AIM_LANE_PACK_X2 0        // 1 = pack from 2 * code (no per-dword shift); off until measured and parity-checked on the GPU
 #endif
@@ -70,6 +84,8 @@
 #define AIM_LANE_WGS_PER_CU 8     // persistent single-wave workgroups per CU = resident waves at this VGPR count
                                   // (a grid larger than the residency runs in uneven rounds: 11/CU measured 15-20 % slower)
 #endif
+// slots of the result ring that kernel and plan agree on (the diagnostic builds without a result store have none)
+#define AIM_LANE_RING_SLOTS ((AIM_LANE_DIAG == 3 || AIM_LANE_DIAG == 4) ? 0 : AIM_LANE_RES_RING)
 #if AIM_LANE_STAMPS
 #define AIM_STAMP(i) do { unsigned long long t_; __builtin_amdgcn_sched_barrier(0); \
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); __builtin_amdgcn_sched_barrier(0); \
@@ -354,6 +370,60 @@ __device__ __forceinline__ void read_group(const LaneReqAddr &qa, uint32_t row_a
 #endif
 }
 
+// The score-only {idx, score} result stores, 8 B (one lane's result) and 16 B (two neighbouring results). AIM_LANE_STORE_SC1: with
+// the sc1 cache policy, which only an inline-asm statement can ask for (the s_nop covers the wait state between a store of more
+// than 64 bits and the next write of its data registers, which the compiler cannot see to here).
+__device__ __forceinline__ void lane_store8(void *dst, const lane_u32x2 &v)
+{
+#if AIM_LANE_STORE_SC1
+    asm volatile("global_store_dwordx2 %0, %1, off sc1" :: "v"(dst), "v"(v) : "memory");
+#else
+    if (AIM_LANE_NT_STORE) __builtin_nontemporal_store(v, reinterpret_cast<lane_u32x2 *>(dst)); else *reinterpret_cast<lane_u32x2 *>(dst) = v;
+#endif
+}
+__device__ __forceinline__ void lane_store16(void *dst, const lane_u32x4 &v)
+{
+#if AIM_LANE_STORE_SC1
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(dst), "v"(v) : "memory");
+#else
+    if (AIM_LANE_NT_STORE) __builtin_nontemporal_store(v, reinterpret_cast<lane_u32x4 *>(dst)); else *reinterpret_cast<lane_u32x4 *>(dst) = v;
+#endif
+}
+
+// The result ring (AIM_LANE_RES_RING = K slots of 64 x {idx, score} behind the request slots). Both of its LDS accesses are
+// inline-asm statements for read_group's reason: an LDS access the compiler emits gets s_waitcnt vmcnt(0) in front of it while
+// LDS-DMA may be in flight -- the write at the end of an iteration would drain the next group's 15 pieces once per group, a
+// read in the flush the stores in front of it. Neither touches the rows or requests the DMA writes, so no order is needed.
+__device__ __forceinline__ void ring_put(uint32_t lds_addr, uint32_t idx, uint32_t score)
+{
+    lane_u32x2 v; v.x = idx; v.y = score;
+    asm volatile("ds_write_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(lds_addr), "v"(v) : "memory");
+}
+// The first `count` slots leave as 16-B stores: lane l carries results 2 (l & 31) and 2 (l & 31) + 1 of slot 2 q + (l >> 5) in
+// store q, so one instruction covers two slots (two groups, 512 contiguous bytes each) and the LDS read is linear, 16 B per lane.
+// lds_lane = ring + 16 lane; dst_lane = the lane's 16 bytes in the group of slot (lane >> 5); step = bytes from slot s to s + 2.
+// Only full groups enter the ring, so no store reaches beyond its group's 512 bytes (the result array has no slack).
+template <int K, bool FULL>
+__device__ __forceinline__ void ring_flush(uint32_t lds_lane, char *dst_lane, uint64_t step, uint32_t count, int lane)
+{
+    static_assert(K == 4 || K == 8, "two slots per store instruction");
+    lane_u32x4 v[K / 2];
+    if constexpr (K == 8) {
+        asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]) : "v"(lds_lane) : "memory");
+    } else {
+        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:1024\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&v"(v[0]), "=&v"(v[1]) : "v"(lds_lane) : "memory");
+    }
+#pragma unroll
+    for (int q = 0; q < K / 2; ++q) {
+        if (FULL || 2u * q + ((uint32_t)lane >> 5) < count) {   // FULL: count == K, no lane is masked
+            lane_store16(dst_lane + q * step, v[q]);
+        }
+    }
+}
+
 // Validate A/C/G/T over [0, len) and pack 2 bits/base: 16 bases -> one dword. `after_step(integral_constant<int, j>)` runs
 // after the j-th 16-base step (the kernel issues one piece of the next group's DMA there).
 // MASKED = false: every byte of the step lies inside the sequence of EVERY lane (the caller proved it wave-wide), so the
@@ -621,7 +691,7 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
     constexpr LaneSpread<X, O, E, MAXS, NP, DYN ? 100 : AIM_LANE_SPREAD_PCT> SP{};
     extern __shared__ __attribute__((aligned(16))) char smem[];
     debug_poison_lds(a, smem);
-    // [64 P rows][64 T rows][64 request descriptors (<= 16 B each)][result staging]
+    // [64 P rows][64 T rows][64 request descriptors (<= 16 B each)][result staging (CIGAR) | result ring (score-only {idx, score})]
     uint32_t *resL = reinterpret_cast<uint32_t *>(smem) + 2 * kWave * (RS / 4) + kWave * 4;                  // 64 x aim_result_t (24 B) staged for a coalesced store (CIGAR only)
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr_t)smem;   // LDS byte offset of the dynamic segment
     const uint32_t offP = lds0, offT = lds0 + kWave * RS, offQ = lds0 + 2 * kWave * RS;
@@ -642,6 +712,20 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
         stage_requests(offQ, a, grp * kWave, lane);
     }
     uint32_t stores_in_flight = 0;                     // result-store instructions the previous iteration issued after its DMA
+    // Result ring (score-only, {idx, score} layout): slot s holds the results of the full group ring_grp0 + s * bpx -- a wave's
+    // groups are affine in its iteration number (xcd_unit) -- and ring_fill slots are filled. A full ring is drained at the top
+    // of the next iteration, what is left behind the loop. The batch's partial last group (the last iteration of the one wave
+    // that has it) never enters the ring. All of it is wave-uniform.
+    constexpr int RING = BT ? 0 : AIM_LANE_RING_SLOTS;
+    const uint32_t offR = offQ + kWave * 16;
+    const uint32_t bpx = gridDim.x >> 3;
+    uint32_t ring_fill = 0, ring_grp0 = 0;
+    auto ring_drain = [&](auto FULL, uint32_t count) __attribute__((always_inline)) {
+        if constexpr (RING > 0) {
+            char *dst = reinterpret_cast<char *>(a.res) + ((uint64_t)ring_grp0 + ((uint32_t)lane >> 5) * bpx) * (kWave * 8u) + ((uint32_t)lane & 31u) * 16u;
+            ring_flush<RING, decltype(FULL)::value>(offR + (uint32_t)lane * 16u, dst, (uint64_t)bpx * (2u * kWave * 8u), count, lane);
+        }
+    };
 #if AIM_LANE_STAMPS
     unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_last;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_last) :: "memory");
@@ -673,6 +757,43 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
         __builtin_amdgcn_sched_barrier(0);
         read_group<RS, NP>(req_addr, row_addr, rq_lo, rq_hi, rawP, rawT);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (RING > 0) {
+            // A full ring leaves here: the VM queue is empty (the wait above was vmcnt(0) on this path), so these stores are its
+            // oldest entries, in front of this iteration's DMA, and have the whole iteration to be acknowledged.
+            if (ring_fill == RING) {
+                ring_drain(std::true_type{}, RING);
+                ring_fill = 0;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // This group's {idx, score} results (score-only, AIM_FLAG_RES8), called with every lane on; `on` = this lane has one.
+        auto store_res8 = [&](uint32_t idx, uint32_t sc, bool on) __attribute__((always_inline)) {
+            if (RING > 0 && (grp + 1u) * kWave <= a.n_pairs) {   // wave-uniform: a full group goes into the ring, no global store
+                if (ring_fill == 0) ring_grp0 = grp;
+                ring_put(offR + ring_fill * (kWave * 8u) + (uint32_t)lane * 8u, idx, sc);
+                ++ring_fill;
+                stores_in_flight = 0;
+                return;
+            }
+            aim_result8_t *dst = reinterpret_cast<aim_result8_t *>(a.res) + pair;
+            lane_u32x2 v2; v2.x = idx; v2.y = sc;
+#if AIM_LANE_STORE_X4
+            // the odd neighbour's result into the even lane (quad_perm [1,1,3,3]); an even lane whose neighbour has none stores 8 B
+            const uint32_t nidx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)idx, 0xF5, 0xf, 0xf, false);
+            const uint32_t nsc = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)sc, 0xF5, 0xf, 0xf, false);
+            if (!(lane & 1)) {
+                if (on && pair + 1u < a.n_pairs) {
+                    lane_u32x4 v4; v4.x = idx; v4.y = sc; v4.z = nidx; v4.w = nsc;
+                    lane_store16(dst, v4);
+                } else if (on) {
+                    lane_store8(dst, v2);
+                }
+            }
+#else
+            if (on) lane_store8(dst, v2);   // ONE global_store_dwordx2 per lane (512 contiguous bytes per wavefront)
+#endif
+            stores_in_flight = 1;
+        };
         const aim_request_t rq = decode_staged_request(rq_lo, rq_hi, a);
         const int plen = active ? rq.pattern_len : 0, tlen = active ? rq.text_len : 0;   // lanes past the batch tail read stale LDS
         uint32_t ngrp = 0;
@@ -697,14 +818,19 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
             uint32_t x = 0;
 #pragma unroll
             for (int j = 0; j < NP; ++j) x ^= rawP[j].x ^ rawP[j].y ^ rawP[j].z ^ rawP[j].w ^ rawT[j].x ^ rawT[j].y ^ rawT[j].z ^ rawT[j].w;
-            if (active && (AIM_LANE_DIAG == 1 || x == 0x12345678u)) {
-                aim_result_t r;
-                r.max_operations = plen + tlen; r.begin_offset = 0; r.end_offset = 0; r.score = (int)x; r.status = 0; r.idx = rq.idx;
-                store_result(a, pair, r);
-            }
             // as production: the stores stay in flight over the loop top (without this the counted wait was vmcnt(0) and every
-            // group paid the store's acknowledgement, which overstated the store's share in the removal decomposition)
-            stores_in_flight = AIM_LANE_DIAG == 1 ? (res8 ? 1u : 2u) : 0u;
+            // group paid the store's acknowledgement, which overstated the store's share in the removal decomposition), and
+            // {idx, score} results take production's way out (store_res8: the ring, or the direct store and its variants)
+            if (AIM_LANE_DIAG == 1 && res8) {
+                store_res8(rq.idx, x, active);
+            } else {
+                if (active && (AIM_LANE_DIAG == 1 || x == 0x12345678u)) {
+                    aim_result_t r;
+                    r.max_operations = plen + tlen; r.begin_offset = 0; r.end_offset = 0; r.score = (int)x; r.status = 0; r.idx = rq.idx;
+                    store_result(a, pair, r);
+                }
+                stores_in_flight = AIM_LANE_DIAG == 1 ? 2u : 0u;
+            }
             have = nhave; grp = ngrp;
             continue;
         }
@@ -988,7 +1114,13 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
                 }
             }
         }
-        if (active) {
+        if (!BT && res8) {   // wave-uniform; score-only pairs have no status but AIM_PAIR_OK
+            bool on = active;
+#if AIM_LANE_DIAG == 3
+            on = on && score == 0x12345678;
+#endif
+            store_res8(rq.idx, (uint32_t)score, on);
+        } else if (active) {
             {
                 aim_result_t r;
                 r.max_operations = plen + tlen;
@@ -1012,19 +1144,22 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
 #endif
                 if (BT) {
                     store_result(a, pair, r);
-                } else if (res8) {     // ONE global_store_dwordx2 per lane (512 contiguous bytes per wavefront)
-                    typedef uint32_t aim_u32x2 __attribute__((ext_vector_type(2)));
-                    aim_u32x2 v2; v2.x = r.idx; v2.y = (uint32_t)r.score;
-                    aim_u32x2 *dst2 = reinterpret_cast<aim_u32x2 *>(reinterpret_cast<aim_result8_t *>(a.res) + pair);
-                    if (AIM_LANE_NT_STORE) __builtin_nontemporal_store(v2, dst2); else *dst2 = v2;
                 } else {               // TWO stores per lane: dwordx4 + dwordx2 (24-B struct, 8-B aligned)
                     uint32_t *dst = reinterpret_cast<uint32_t *>(a.res + pair);
+#if AIM_LANE_STORE_SC1 >= 2
+                    lane_u32x4 v4; v4.x = (uint32_t)r.max_operations; v4.y = (uint32_t)r.begin_offset; v4.z = (uint32_t)r.end_offset; v4.w = (uint32_t)r.score;
+                    lane_u32x2 v2; v2.x = (uint32_t)r.status; v2.y = r.idx;
+                    lane_store16(dst, v4);
+                    lane_store8(dst + 4, v2);
+#else
                     *reinterpret_cast<uint4 *>(dst) = make_uint4((uint32_t)r.max_operations, (uint32_t)r.begin_offset, (uint32_t)r.end_offset, (uint32_t)r.score);
                     *reinterpret_cast<uint2 *>(dst + 4) = make_uint2((uint32_t)r.status, r.idx);
+#endif
                 }
             }
         }
-        stores_in_flight = (BT || AIM_LANE_DIAG == 3) ? 0u : (res8 ? 1u : 2u);   // every iteration has at least one active lane
+        if (BT || AIM_LANE_DIAG == 3) stores_in_flight = 0;
+        else if (!res8) stores_in_flight = 2;   // every iteration has at least one active lane ({idx, score}: set by store_res8)
 #if AIM_LANE_RES_STAGE
         if (full_group) {   // wave-uniform
             typedef uint32_t aim_u32x4 __attribute__((ext_vector_type(4)));
@@ -1040,6 +1175,7 @@ __global__ __launch_bounds__(64, DYN ? 2 : AIM_LANE_MIN_WAVES) void wfa_lane_ker
         grp = ngrp;
         AIM_STAMP(6);                           // result store issue
     }
+    if (ring_fill) ring_drain(std::false_type{}, ring_fill);       // the groups since the last full ring (a slot may lack its partner: lanes 32 .. 63 masked)
 #if AIM_LANE_STAMPS
     if (lane == 0) {
         unsigned long long *dbg = reinterpret_cast<unsigned long long *>(a.scratch + a.scratch_per_wave) + (size_t)blockIdx.x * 8;
@@ -1091,6 +1227,11 @@ inline void wfa_lane_plan(const aim_params_t &p, uint32_t n_pairs, const Knobs &
     *grid = g;
     *block = kWave;
     *lds = (size_t)2 * kWave * p.read_size + kWave * 16 + ((p.flags & AIM_FLAG_BACKTRACE) ? kWave * sizeof(aim_result_t) : 0);
+    // the result ring of the score-only {idx, score} layout: 512 B per slot behind the request slots. It must not cost a resident
+    // workgroup (10 per CU in two rounds measured 50 % slower): 15 360 + 512 K at READ_SIZE 112 rounds to 16 granules up to K = 10
+    static_assert(AIM_LANE_RING_SLOTS == 0 || AIM_LANE_RING_SLOTS == 4 || AIM_LANE_RING_SLOTS == 8, "AIM_LANE_RES_RING: 0, 4 or 8");
+    if (!(p.flags & AIM_FLAG_BACKTRACE) && (p.flags & AIM_FLAG_RES8)) *lds += (size_t)AIM_LANE_RING_SLOTS * kWave * 8;
+    assert(lds_workgroups_per_cu(*lds) >= AIM_LANE_WGS_PER_CU);
 }
 
 // Kernels are instantiated in ONE translation unit (tu_*.hip defines AIM_TU_WFA_LANE); every other includer sees the declaration only.
