@@ -4,8 +4,8 @@
  * header).  Plain C11, no dependencies.  Every function cites the reference
  * file:line it follows (paths relative to the safaad/aim tree).
  *
- * Parity status: see aim_oracle.h ("parity unpinned" outside the recorded
- * sample-l100-e1-40K digests).
+ * Parity status: see aim_oracle.h (held to the live reference by
+ * tests/test_reference_live_cpu.py).
  */
 #define _GNU_SOURCE
 #include "aim_oracle.h"

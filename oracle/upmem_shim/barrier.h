@@ -1,0 +1,1 @@
+#include "upmem_shim.h"
