@@ -6,10 +6,11 @@
 
 `python -m aim_amd.build` builds both; nothing is JIT-compiled at import time.
 
-The library is several translation units -- the C-ABI in aim_capi.hip (device sets, launching, the alignment entry points, the
-small batch-I/O kernels), capi_plan.hip (the launch planner: host code only), capi_pipeline.hip (index, seeding, classes, split, extension), capi_mapper.hip (the record list and the
-mapper object) and capi_host.hip (host-side helpers), and
-one tu_*.hip per kernel family, each of which instantiates the kernels of ONE header -- compiled in parallel into build/obj/ and linked
+The library is several translation units -- the C-ABI in aim_capi.hip (device sets, launching, the alignment entry points),
+capi_groups.hip (the read-groups path: READ_GROUPS, MATE_PAIRS, TOP_HITS), capi_plan.hip (the launch planner), capi_pipeline.hip (index,
+seeding, classes, split, extension), capi_mapper.hip (the record list and the mapper object) and capi_host.hip (host-side helpers), all
+of them host code only, and one tu_*.hip per kernel family, each of which instantiates the kernels of ONE header (tu_groups.hip: of
+groups.hpp, hits.hpp and mates.hpp) -- compiled in parallel (MAX_JOBS at a time when it is set) into build/obj/ and linked
 once: a full rebuild takes as long as the slowest family instead of the sum, and editing one kernel header recompiles only
 the units that include it.
 
@@ -87,7 +88,7 @@ def build_lib(force=False, out=LIB, objdir=None, extra_flags=()):
         if force or _newer(obj, _deps(src)):
             jobs.append([HIPCC] + flags + ["-c", src, "-o", obj])
     if jobs:
-        workers = max(1, min(len(jobs), os.cpu_count() or 1))
+        workers = max(1, min(len(jobs), int(os.environ.get("MAX_JOBS") or os.cpu_count() or 1)))
         with concurrent.futures.ThreadPoolExecutor(workers) as ex:
             list(ex.map(_run, jobs))
     if jobs or not os.path.exists(flag_stamp):
@@ -111,6 +112,11 @@ def test_helper(name):
     return os.path.join(ROOT, "build", "tests", "lib%s.so" % name)
 
 
+# select_harness launches group_select_kernel and mate_select_kernel itself, so it instantiates them. Its source defines the guard too;
+# it is repeated here so that a copy of the helper from before groups.hpp had the guard still builds against these headers.
+HELPER_DEFINES = {"select_harness": ["-DAIM_TU_GROUPS=1"]}
+
+
 def build_test_helpers(force=False):
     srcdir = os.path.join(ROOT, "tests", "csrc")
     if not os.path.isdir(srcdir):
@@ -122,7 +128,7 @@ def build_test_helpers(force=False):
         src, lib = os.path.join(srcdir, f), test_helper(f[:-4])
         os.makedirs(os.path.dirname(lib), exist_ok=True)
         if force or _newer(lib, _deps(src)):
-            _run([HIPCC] + HIP_FLAGS + ["-shared", "-o", lib, src])
+            _run([HIPCC] + HIP_FLAGS + HELPER_DEFINES.get(f[:-4], []) + ["-shared", "-o", lib, src])
         out.append(lib)
     return out
 

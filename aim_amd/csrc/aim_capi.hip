@@ -4,9 +4,11 @@
 // dpu_push_xfer / dpu_launch (WFA/DPU-WRAM/host/host.c:186-330) is done here
 // with one HIP stream per device, HBM buffers planned per configuration, and
 // asynchronous copies.  No CPU fallback exists: every compute entry point
-// needs a HIP device.  This unit launches: device sets, slots, submits and the alignment entry points. The launch planner and the entry
-// points that only plan are in capi_plan.hip (plan.hpp), the read-mapping pipeline's entry points in capi_pipeline.hip, the host-side
-// helpers in capi_host.hip.
+// needs a HIP device.  This unit launches: device sets, slots, submits and the alignment entry points. It compiles no kernel: every
+// kernel family's tu_*.hip does, and this unit calls the launchers their headers declare. The read-groups path (AIM_FLAG_READ_GROUPS,
+// MATE_PAIRS, TOP_HITS) is in capi_groups.hip, which shares the device set's types and this unit's launch() through capi_set.hpp; the
+// launch planner and the entry points that only plan are in capi_plan.hip (plan.hpp), the read-mapping pipeline's entry points in
+// capi_pipeline.hip, the host-side helpers in capi_host.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,8 +22,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "capi_common.hpp"
-#include "plan.hpp"
+#include "capi_set.hpp"
 #include "wfa_wave.hpp"
 #include "wfa_bidir.hpp"
 #include "wfa_lane.hpp"
@@ -33,9 +34,6 @@
 #include "dp_reg.hpp"
 #include "dp_group.hpp"
 #include "batch_io.hpp"
-#include "groups.hpp"
-#include "hits.hpp"
-#include "mates.hpp"
 #include "sam_fields.hpp"
 #include "genasm_wave.hpp"
 
@@ -54,7 +52,15 @@ int aim::capi::fail(int code, const char *fmt, ...)
     return code;
 }
 
-uint32_t aim::capi::packed_row_dwords(int read_size) { return aim::packed_row_dwords(read_size); }
+int aim::capi::fail_drained(aim_slot &s, int rc)
+{
+    char keep[sizeof g_err];
+    memcpy(keep, g_err, sizeof keep);
+    (void)hipStreamSynchronize(s.stream);
+    (void)hipGetLastError();
+    memcpy(g_err, keep, sizeof keep);
+    return rc;
+}
 
 namespace {
 
@@ -82,18 +88,6 @@ void launch_stage(const aim_params_t &p, const Stage &st, const aim::KArgs &ka, 
     }
 }
 
-// A second stream per device for work that only has to be ordered against ONE kernel of a launch, not against the whole stream:
-// wfa_group's traceback kernel of chunk c runs there while chunk c + 1 is computed on the caller's stream (the traceback is a
-// latency-bound walk -- 93 % of its wavefront cycles are waits -- so it costs the compute kernel next to nothing). Events are
-// re-recorded per launch; a hipStreamWaitEvent captures the record that precedes it, so re-use across launches is safe.
-// OWNERSHIP: every slot of a device set has its own (created on first use, destroyed with the slot), so two host threads driving two
-// sets -- or two slots -- on one device never record / wait on each other's events. The stateless aim_align_device has no slot: it
-// uses one per-device instance and holds that device's mutex across its whole chunk loop.
-struct AuxStream {
-    hipStream_t stream = nullptr;
-    hipEvent_t computed[2] = {nullptr, nullptr};   // compute kernel of the chunk that uses history buffer b has finished
-    hipEvent_t walked[2] = {nullptr, nullptr};     // traceback of that chunk has finished (buffer b is free again)
-};
 int aux_stream_create(AuxStream &a)
 {
     if (a.stream) return AIM_OK;
@@ -122,14 +116,6 @@ SharedAux *shared_aux_for_current_device()
     return &table[dev];
 }
 
-// The fused batch I/O of a launch (Plan::pk / Plan::emits_runs): packed rows in, compact CIGAR out.
-struct FusedIo {
-    const uint32_t *packedP = nullptr, *packedT = nullptr;
-    aim_cigar_t *cig = nullptr;
-    uint32_t *runs = nullptr, *cursor = nullptr;
-    uint32_t runs_cap = 0, run_slot = 0;
-};
-
 // Enqueue one alignment launch that follows the one-stage plan `pl` (made for >= n_pairs pairs under the caller's knobs and budget).
 // list_in (AIM_FLAG_WFA_ESCALATE, second stage): the launch's pairs are those of the device-side list {count @0, pair ids @16..}, at most
 // n_pairs of them; every buffer stays the batch's. Only wfa_group (+ its traceback) and wfa_wave take one.
@@ -157,7 +143,7 @@ int launch_one(const StagePlan &pl, const aim::Knobs &kn, const aim_params_t &p,
     ka0.res = static_cast<aim_result_t *>(d_res);
     ka0.ops = d_ops;
     ka0.todo = nullptr;
-    ka0.dbg_poison_lds = kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u;
+    ka0.dbg_poison_lds = poison_lds_word(kn);
     ka0.dbg_flags = (uint32_t)kn.dbg_flags;
     ka0.packedP = fio ? fio->packedP : nullptr;
     ka0.packedT = fio ? fio->packedT : nullptr;
@@ -199,9 +185,7 @@ int launch_one(const StagePlan &pl, const aim::Knobs &kn, const aim_params_t &p,
             uint32_t *flags_d = reinterpret_cast<uint32_t *>(base + pl.flags_at);
             uint32_t *pkP = reinterpret_cast<uint32_t *>(base + pl.pack_p_at), *pkT = reinterpret_cast<uint32_t *>(base + pl.pack_t_at);
             HIP_TRY(hipMemsetAsync(flags_d, 0, pl.pack_p_at - pl.flags_at, stream));
-            const uint64_t threads = (uint64_t)n_pairs * aim::packed_row_dwords(p.read_size);
-            hipLaunchKernelGGL(aim::pack_rows_kernel, dim3((unsigned)((threads + 255) / 256), 2), dim3(256), 0, stream, ka, pkP, pkT, flags_d,
-                               reinterpret_cast<uint32_t *>(base + pl.todo_at));
+            aim::pack_rows_launch(ka, pkP, pkT, flags_d, reinterpret_cast<uint32_t *>(base + pl.todo_at), stream);
             HIP_TRY(hipGetLastError());
             aim::KArgs kp = ka;
             kp.packedP = pkP;
@@ -216,8 +200,7 @@ int launch_one(const StagePlan &pl, const aim::Knobs &kn, const aim_params_t &p,
     case K_WFA_GROUP: {
         // fast kernel (+ traceback kernel with BACKTRACE) chunk by chunk; then the general kernel drains the to-do list
         const uint32_t chunk = (bt && pl.chunk_pairs) ? pl.chunk_pairs : n_pairs;
-        const size_t rqb = (p.flags & AIM_FLAG_REQ8) ? sizeof(aim_request8_t) : sizeof(aim_request_t);
-        const size_t rsb = (p.flags & AIM_FLAG_RES8) ? sizeof(aim_result8_t) : sizeof(aim_result_t);
+        const size_t rqb = req_size(p), rsb = res_size(p);
         const size_t npw = aim::packed_row_dwords(p.read_size);
         const uint32_t nchunks = (n_pairs + chunk - 1) / chunk;
         const bool overlap = bt && nchunks > 1;
@@ -282,12 +265,12 @@ int launch_one(const StagePlan &pl, const aim::Knobs &kn, const aim_params_t &p,
             HIP_TRY(hipStreamWaitEvent(stream, aux->walked[1], 0));
         }
         if (pl.pk) {   // the general kernel reads ASCII rows: expand the to-do pairs' packed rows in place first
-            hipLaunchKernelGGL(aim::unpack_todo_rows_kernel, dim3(256), dim3(256), 0, stream, ka, kb.todo, ka.packedP, ka.packedT, const_cast<char *>(d_pat), const_cast<char *>(d_txt));
+            aim::unpack_todo_rows_launch(ka, kb.todo, ka.packedP, ka.packedT, const_cast<char *>(d_pat), const_cast<char *>(d_txt), stream);
             HIP_TRY(hipGetLastError());
         }
         launch_stage(p, pl.fb, kb, stream);
         if (pl.emits_runs) {   // the general kernel wrote result_t + ops rows for the to-do pairs: their compact CIGAR
-            hipLaunchKernelGGL(aim::cigar_rle_todo_kernel, dim3(256), dim3(64), 0, stream, kb, kb.todo, ka.cig, ka.runs, ka.runs_cap, ka.cursor);
+            aim::cigar_rle_todo_launch(kb, kb.todo, ka.cig, ka.runs, ka.runs_cap, ka.cursor, stream);
             HIP_TRY(hipGetLastError());
         }
         break;
@@ -327,9 +310,11 @@ int launch_one(const StagePlan &pl, const aim::Knobs &kn, const aim_params_t &p,
 
 // Enqueue the launches of plan `pl`. AIM_FLAG_WFA_ESCALATE with two stages: the lane plan at cap esc_c over the batch, the list of the
 // pairs it left at esc_c + 1 (ascending pair order), the full-cap plan over that list -- one stream, no host round trip.
-int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t n_pairs, const void *d_req,
-           const char *d_pat, const char *d_txt, void *d_res, char *d_ops, void *d_scratch, size_t scratch_bytes,
-           hipStream_t stream, const FusedIo *fio = nullptr, AuxStream *slot_aux = nullptr)
+}  // namespace
+
+int aim::capi::launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t n_pairs, const void *d_req,
+                      const char *d_pat, const char *d_txt, void *d_res, char *d_ops, void *d_scratch, size_t scratch_bytes,
+                      hipStream_t stream, const FusedIo *fio, AuxStream *slot_aux)
 {
     // (without the flag p may be the base of an extension struct, which launch_one reads through its address: no copy of it here)
     if (!pl.esc) return launch_one(pl, kn, p, n_pairs, d_req, d_pat, d_txt, d_res, d_ops, d_scratch, scratch_bytes, stream, fio, slot_aux);
@@ -353,240 +338,19 @@ int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t
     uint2 *masks = reinterpret_cast<uint2 *>(base + pl.mask_at);
     uint32_t *counts = reinterpret_cast<uint32_t *>(base + pl.count_at);
     const bool res8 = p.flags & AIM_FLAG_RES8;
-    const dim3 grid((n_pairs + aim::kEscTile - 1) / aim::kEscTile);
-    hipLaunchKernelGGL(aim::escalate_select_kernel, grid, dim3(256), 0, stream, static_cast<const uint32_t *>(d_res), n_pairs, res8 ? 2u : 6u,
-                       res8 ? 1u : 3u, (int32_t)(pl.esc_c + 1), masks, counts);
-    hipLaunchKernelGGL(aim::escalate_list_kernel, grid, dim3(256), 0, stream, n_pairs, masks, counts, list);
+    aim::escalate_list_launch(static_cast<const uint32_t *>(d_res), n_pairs, res8 ? 2u : 6u, res8 ? 1u : 3u, (int32_t)(pl.esc_c + 1), masks, counts, list,
+                              stream);
     HIP_TRY(hipGetLastError());
     if (pl.pk && !pl.s2.pk) {   // a packed batch whose second stage reads ASCII rows: the listed pairs' rows, expanded in place
-        aim::KArgs ku;
-        memset(&ku, 0, sizeof ku);
-        ku.p = q;
-        ku.n_pairs = n_pairs;
-        ku.req = static_cast<const aim_request_t *>(d_req);
         if (!d_pat || !d_txt || !fio || !fio->packedP || !fio->packedT) return fail(AIM_EINVAL, "null device buffer");
-        hipLaunchKernelGGL(aim::unpack_todo_rows_kernel, dim3(256), dim3(256), 0, stream, ku, list, fio->packedP, fio->packedT, const_cast<char *>(d_pat),
-                           const_cast<char *>(d_txt));
+        aim::unpack_todo_rows_launch(batch_args(q, n_pairs, d_req), list, fio->packedP, fio->packedT, const_cast<char *>(d_pat), const_cast<char *>(d_txt),
+                                     stream);
         HIP_TRY(hipGetLastError());
     }
     return launch_one(pl.s2, kn, q, n_pairs, d_req, d_pat, d_txt, d_res, d_ops, base + pl.s2_at, pl.s2.scratch_total, stream, fio, slot_aux, list);
 }
 
-// AIM_FLAG_REF_TEXTS: text rows [n_rows][READ_SIZE] of `out` gathered from the reference; row r is the window of pair idx[r]
-// (idx == nullptr: pair r). ka carries the params and the requests.
-int enqueue_gather(const aim::KArgs &ka, const uint64_t *d_tpos, const char *ref, uint64_t ref_len, const uint32_t *idx, uint32_t n_rows,
-                   char *out, hipStream_t stream)
-{
-    if (!n_rows) return AIM_OK;
-    const int rs = ka.p.read_size;
-    const bool w16 = (rs & 15) == 0;   // 16-B stores per lane where the row stride allows them, else 8-B
-    const uint64_t threads = (uint64_t)n_rows * (uint64_t)(rs / (w16 ? 16 : 8));
-    const dim3 grid((unsigned)((threads + 255) / 256));
-    if (w16) hipLaunchKernelGGL(aim::gather_text_rows_kernel<4>, grid, dim3(256), 0, stream, ka, d_tpos, ref, ref_len, idx, n_rows, out);
-    else hipLaunchKernelGGL(aim::gather_text_rows_kernel<2>, grid, dim3(256), 0, stream, ka, d_tpos, ref, ref_len, idx, n_rows, out);
-    HIP_TRY(hipGetLastError());
-    return AIM_OK;
-}
-
-// Device buffers of one groups batch (a slot's, or carved from the stateless scratch).
-struct GroupsIo {
-    uint32_t n_pairs, n_reads;
-    const void *req;             // [n_pairs]
-    const char *read_rows;       // [n_reads][READ_SIZE], or nullptr when the reads arrived packed:
-    const uint32_t *packed;      // [n_reads][ceil(READ_SIZE/16)] packed read rows ...
-    const uint32_t *raw_pairs;   // ... [n_raw] reads that travel raw, their rows in raw_rows [n_raw][READ_SIZE]
-    const char *raw_rows;
-    uint32_t n_raw;
-    uint32_t *raw_slot;          // [n_reads] scratch of the expansion
-    const uint32_t *roff;        // [n_reads + 1]
-    char *cand_p, *cand_t;       // [n_pairs][READ_SIZE]; cand_t: the candidates' text rows (given, or gathered under REF_TEXTS)
-    aim_result_t *res1;          // [n_pairs]
-    uint32_t *map, *sel;         // [n_pairs], [n_reads]
-    aim_best_t *best;            // [n_reads] or nullptr (never nullptr under AIM_FLAG_MATE_PAIRS)
-    const uint64_t *tpos;        // AIM_FLAG_MATE_PAIRS: the candidates' text_pos [n_pairs] ...
-    aim::MateArgs mate;          // ... the pairing parameters (n_mates and lanes are filled in by enqueue_groups) ...
-    aim_mate_t *mates;           // ... and the read pairs' rows [n_reads / 2], or nullptr
-    uint32_t n_hits, max_hits;   // AIM_FLAG_TOP_HITS: H hit rows, at most max_hits per read ...
-    const uint32_t *hoff;        // ... hit_offsets [n_reads + 1] ...
-    uint32_t *hit_pair;          // ... and the candidate of every hit row [n_hits]
-    void *req2;                  // [rows] pass-2 requests; rows = n_reads, or n_hits under AIM_FLAG_TOP_HITS (never more than n_pairs)
-    char *pat2, *txt2;           // [rows][READ_SIZE]
-    void *res;                   // out [rows]
-    char *ops;                   // out [rows][2 READ_SIZE] (BACKTRACE)
-    void *scratch;               // the plans' region
-    size_t scratch_bytes;
-};
-
-int enqueue_rows(const aim::KArgs &ka, const char *src, uint32_t n_src, const uint32_t *idx, uint32_t n_rows, int text, char *out, hipStream_t stream)
-{
-    if (!n_rows) return AIM_OK;
-    const int rs = ka.p.read_size;
-    const bool w16 = (rs & 15) == 0;
-    const uint64_t threads = (uint64_t)n_rows * (uint64_t)(rs / (w16 ? 16 : 8));
-    const dim3 grid((unsigned)((threads + 255) / 256));
-    if (w16) hipLaunchKernelGGL(aim::group_rows_kernel<4>, grid, dim3(256), 0, stream, ka, src, n_src, idx, n_rows, text, out);
-    else hipLaunchKernelGGL(aim::group_rows_kernel<2>, grid, dim3(256), 0, stream, ka, src, n_src, idx, n_rows, text, out);
-    HIP_TRY(hipGetLastError());
-    return AIM_OK;
-}
-
-// Everything after the texts are candidate rows (cand_t): expand the read rows, pass 1, select, then pass 2 or the result gather.
-// pl1 / pl2: the passes' plans for this batch (each fits io.scratch_bytes).
-int enqueue_groups(const GroupsPlan &g, const Plan &pl1, const Plan &pl2, const aim::Knobs &kn, const GroupsIo &io, hipStream_t stream,
-                   AuxStream *aux)
-{
-    const aim_params_t &p1 = g.x1.base, &p2 = g.x2.base;
-    const uint32_t n = io.n_pairs, nr = io.n_reads;
-    if (!n) return AIM_OK;
-    aim::KArgs ka;
-    memset(&ka, 0, sizeof ka);
-    ka.p = p1;
-    ka.n_pairs = n;
-    ka.req = static_cast<const aim_request_t *>(io.req);
-    hipLaunchKernelGGL(aim::group_map_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, io.roff, nr, n, io.map);
-    HIP_TRY(hipGetLastError());
-    int rc = AIM_OK;
-    if (io.read_rows) {
-        rc = enqueue_rows(ka, io.read_rows, nr, io.map, n, 0, io.cand_p, stream);
-    } else {
-        HIP_TRY(hipMemsetAsync(io.raw_slot, 0xff, (size_t)nr * 4, stream));
-        if (io.n_raw)
-            hipLaunchKernelGGL(aim::group_raw_slot_kernel, dim3((io.n_raw + 255) / 256), dim3(256), 0, stream, io.raw_pairs, io.n_raw, nr, io.raw_slot);
-        const uint64_t threads = (uint64_t)n * (uint64_t)(p1.read_size / 8);
-        hipLaunchKernelGGL(aim::group_unpack_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, ka, io.packed, io.map,
-                           io.raw_slot, io.raw_rows, io.n_raw, nr, io.cand_p);
-        HIP_TRY(hipGetLastError());
-    }
-    if (rc) return rc;
-    rc = launch(pl1, kn, p1, n, io.req, io.cand_p, io.cand_t, io.res1, nullptr, io.scratch, io.scratch_bytes, stream, nullptr, aux);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(io.sel, 0, (size_t)nr * 4, stream));   // (a read the CSR check would refuse keeps a valid sel)
-    const uint32_t waves = (nr + aim::kGroupReadsPerWave - 1) / aim::kGroupReadsPerWave;
-    hipLaunchKernelGGL(aim::group_select_kernel, dim3((waves + 3) / 4), dim3(256), 0, stream, io.res1, n, io.roff, nr, io.best, io.sel);
-    HIP_TRY(hipGetLastError());
-    if (g.mates && nr >= 2) {
-        // lanes per read pair: the power of two that covers an average read pair's combinations (any value gives the same rows)
-        aim::MateArgs ma = io.mate;
-        ma.n_mates = nr / 2;
-        const uint64_t k = ((uint64_t)n + nr - 1) / nr, combos = k * k;
-        ma.lanes = 1;
-        while (ma.lanes < (uint32_t)aim::kWave && ma.lanes < combos) ma.lanes <<= 1;
-        const uint64_t threads = (uint64_t)ma.n_mates * ma.lanes;
-        hipLaunchKernelGGL(aim::mate_select_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, ka, ma, io.res1, io.tpos,
-                           io.roff, io.best, io.sel, io.mates);
-        HIP_TRY(hipGetLastError());
-    }
-    // the rows behind the selection: the reads' winners, or under AIM_FLAG_TOP_HITS every read's hits in rank order
-    uint32_t rows = nr;
-    const uint32_t *row_cand = io.sel;
-    if (g.hits) {
-        rows = io.n_hits;
-        row_cand = io.hit_pair;
-        if (!rows) return AIM_OK;
-        HIP_TRY(hipMemsetAsync(io.hit_pair, 0, (size_t)rows * 4, stream));   // (rows that wrong hit_offsets leave unwritten keep a valid candidate)
-        hipLaunchKernelGGL(aim::hit_select_kernel, dim3((waves + 3) / 4), dim3(256), 0, stream, io.res1, n, io.roff, nr, io.hoff, io.max_hits,
-                           rows, io.hit_pair);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!g.pass2) {
-        hipLaunchKernelGGL(aim::group_results_kernel, dim3((rows + 255) / 256), dim3(256), 0, stream, io.res1, row_cand, rows,
-                           (int)((p2.flags & AIM_FLAG_RES8) != 0), io.res);
-        HIP_TRY(hipGetLastError());
-        return AIM_OK;
-    }
-    // the rows as a batch of their own: requests, pattern rows (already cut to pattern_len) and text rows gathered by candidate
-    const uint32_t rq_dw = (uint32_t)((p2.flags & AIM_FLAG_REQ8) ? sizeof(aim_request8_t) : sizeof(aim_request_t)) / 4;
-    hipLaunchKernelGGL(aim::gather_elems_kernel, dim3((unsigned)(((uint64_t)rows * rq_dw + 255) / 256)), dim3(256), 0, stream,
-                       static_cast<const uint32_t *>(io.req), row_cand, rows, rq_dw, static_cast<uint32_t *>(io.req2));
-    HIP_TRY(hipGetLastError());
-    aim::KArgs k2 = ka;
-    k2.p = p2;
-    k2.n_pairs = rows;
-    k2.req = static_cast<const aim_request_t *>(io.req2);
-    rc = enqueue_rows(k2, io.cand_p, n, row_cand, rows, 0, io.pat2, stream);
-    if (!rc) rc = enqueue_rows(k2, io.cand_t, n, row_cand, rows, 1, io.txt2, stream);
-    if (rc) return rc;
-    return launch(pl2, kn, p2, rows, io.req2, io.pat2, io.txt2, io.res, io.ops, io.scratch, io.scratch_bytes, stream, nullptr, aux);
-}
-
-}  // namespace
-
-// ---------------------------------------------------------------------------
-// device set
-// ---------------------------------------------------------------------------
-// One buffer set + stream: what a batch needs from H2D to D2H. Slot 0 also serves aim_set_push / launch / pull.
-struct aim_slot {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // h2d b/e, kernel b/e, d2h b/e
-    void *d_req = nullptr;   // aim_request_t[] or aim_request8_t[] (AIM_FLAG_REQ8)
-    char *d_pat = nullptr, *d_txt = nullptr, *d_ops = nullptr;
-    void *d_res = nullptr;   // aim_result_t[] or aim_result8_t[] (AIM_FLAG_RES8)
-    void *d_scratch = nullptr;
-    size_t scratch_bytes = 0;
-    uint32_t *d_packP = nullptr, *d_packT = nullptr;                 // packed input rows
-    uint32_t *d_rawidx = nullptr;                                    // side list of raw pairs
-    char *d_rawP = nullptr, *d_rawT = nullptr;
-    aim_cigar_t *d_cig = nullptr;                                    // compact CIGAR
-    uint32_t *d_runs = nullptr, *d_cursor = nullptr, *h_cursor = nullptr;
-    void *d_rawreq = nullptr, *d_rawres = nullptr;                   // raw side pass (fused packed batches): the side list as a batch of its own
-    char *d_rawops = nullptr;
-    aim_cigar_t *d_rawcig = nullptr;
-    uint64_t *d_tpos = nullptr;      // AIM_FLAG_REF_TEXTS: the batch's text_pos[]
-    uint32_t *d_reftodo = nullptr;   // ... packed batches on the fused lane kernel: to-do list {count @0, pair ids @16..} + flag bits
-    bool ref_pending = false;        // aim_set_push_ref: the texts are gathered at aim_set_launch
-    // AIM_FLAG_READ_GROUPS (groups.hpp): the read-level inputs, the score-only pass's rows, the selection and the winners' batch
-    char *g_readP = nullptr;         // [max_pairs][READ_SIZE] read pattern rows as they arrive
-    uint32_t *g_roff = nullptr, *g_map = nullptr, *g_sel = nullptr, *g_rawslot = nullptr;
-    aim_result_t *g_res1 = nullptr;
-    aim_best_t *g_best = nullptr;
-    aim_mate_t *g_mates = nullptr;   // AIM_FLAG_MATE_PAIRS: [max_pairs / 2]
-    uint32_t *g_hoff = nullptr, *g_hit = nullptr;   // AIM_FLAG_TOP_HITS: hit_offsets [max_pairs + 1], hit_pair [max_pairs]
-    // AIM_FLAG_SAM_FIELDS (aim_set_sam_capacity): records, CIGAR words, MD bytes, the two cursors and their pinned host copy
-    aim_sam_t *d_sam = nullptr;
-    uint32_t *d_samcig = nullptr, *d_samcur = nullptr, *h_samcur = nullptr;
-    char *d_sammd = nullptr;
-    uint32_t samcig_cap = 0, sammd_cap = 0;
-    // ... the SAM members of the batch in flight (sam == nullptr: none)
-    aim_sam_t *io_sam = nullptr;
-    uint32_t *io_samcig = nullptr;
-    char *io_sammd = nullptr;
-    uint32_t io_samcig_cap = 0, io_sammd_cap = 0;
-    void *g_req2 = nullptr;
-    char *g_pat2 = nullptr, *g_txt2 = nullptr;
-    uint32_t n_reads = 0;            // reads of the groups batch in flight (n_pairs then counts its output rows)
-    Plan plan_last2;                 // ... the second pass's plan
-    uint32_t n_pairs = 0;
-    uint32_t runs_sent = 0;  // runs of the batch in flight whose D2H copy aim_set_submit already enqueued (slotted run buffer)
-    bool pushed = false, launched = false, submitted = false;
-    AuxStream aux;           // this slot's second stream + events (chunked wfa_group launches with CIGAR); created on first use
-    Plan plan_last;          // the plan the last launch followed (the configure-time plan re-made for the pushed pair count)
-    aim_batch_io_t io;       // the batch in flight (aim_set_submit .. aim_set_wait)
-};
-
-struct aim_device_ctx {
-    int dev = -1;
-    std::vector<aim_slot> slots;
-    char *d_ref = nullptr;   // AIM_FLAG_REF_TEXTS: the reference (+ zeroed tail slack), kept across aim_set_configure
-    uint64_t ref_len = 0;
-    Plan plan;               // made at configure time for max_pairs under the set's knobs and this device's budget
-    Plan plan2;              // AIM_FLAG_READ_GROUPS: plan is the score-only pass's, plan2 the second pass's
-    uint64_t budget = 0;     // scratch bound of one slot of this device, frozen at configure time
-    float h2d_ms = 0.f, kernel_ms = 0.f, d2h_ms = 0.f;   // aim_set_submit / aim_set_wait: phase times of this device's batches, summed
-};
-
-struct aim_set {
-    std::vector<aim_device_ctx> devs;
-    XParams xparams;                 // the params with their extension (aim_hip.h AIM_FLAG_ENDSFREE / AIM_FLAG_AFFINE2P); xparams.base is what the plans read
-    const aim_params_t &params = xparams.base;
-    uint32_t max_pairs = 0, max_raw = 0, max_runs = 0;
-    bool configured = false;
-    aim::Knobs knobs;        // AIM_* switches as read by the last aim_set_configure; launches never re-read the environment
-    float h2d_ms = 0.f, kernel_ms = 0.f, d2h_ms = 0.f;
-};
-
 namespace {
-inline size_t req_size(const aim_params_t &p) { return (p.flags & AIM_FLAG_REQ8) ? sizeof(aim_request8_t) : sizeof(aim_request_t); }
-inline size_t res_size(const aim_params_t &p) { return (p.flags & AIM_FLAG_RES8) ? sizeof(aim_result8_t) : sizeof(aim_result_t); }
 
 void free_slot(aim_slot &s)
 {
@@ -671,11 +435,10 @@ int aim::capi::check_lengths(const aim_params_t &p, uint32_t n_pairs, const void
     }
     return AIM_OK;
 }
-namespace {
 
 // AIM_FLAG_REF_TEXTS: every window [pos, pos + text_len) inside [0, ref_len) (bit 63 is the strand; an empty window is always
 // inside). Scanned branch-free like check_lengths; only a failing scan is repeated to name the pair.
-int check_windows(const aim_params_t &p, uint32_t n_pairs, const void *requests, const uint64_t *text_pos, uint64_t ref_len, uint32_t *bad_pair)
+int aim::capi::check_windows(const aim_params_t &p, uint32_t n_pairs, const void *requests, const uint64_t *text_pos, uint64_t ref_len, uint32_t *bad_pair)
 {
     const bool req8 = p.flags & AIM_FLAG_REQ8;
     auto tlen = [&](size_t i) -> uint64_t {
@@ -694,6 +457,8 @@ int check_windows(const aim_params_t &p, uint32_t n_pairs, const void *requests,
         }
     return AIM_OK;
 }
+
+namespace {
 
 // AIM_FLAG_REF_TEXTS, packed batch on the fused lane kernel: the general kernel's stage over the to-do list of windows that hold a
 // byte outside A/C/G/T (the stage pack_first plans put behind the same kernel). False when it does not fit the slot's scratch.
@@ -766,9 +531,10 @@ int enqueue_sam(const aim_params_t &p, const aim::Knobs &kn, aim::SamArgs a, hip
     HIP_TRY(hipGetLastError());
     return AIM_OK;
 }
+}  // namespace
 
 // AIM_FLAG_SAM_FIELDS on a slot: what aim_set_submit checks before anything is enqueued; *sio receives the struct (nullptr without the flag)
-int check_sam_io(const aim_set *set, const aim_slot &s, const aim_batch_io_t *io, const aim_batch_io_sam_t **sio)
+int aim::capi::check_sam_io(const aim_set *set, const aim_slot &s, const aim_batch_io_t *io, const aim_batch_io_sam_t **sio)
 {
     *sio = nullptr;
     if (!is_sam(set->params)) return AIM_OK;
@@ -783,7 +549,7 @@ int check_sam_io(const aim_set *set, const aim_slot &s, const aim_batch_io_t *io
 }
 
 // ... the kernel behind the batch's final rows (sel: the reads' candidates under AIM_FLAG_READ_GROUPS, else nullptr)
-int enqueue_sam_on_slot(const aim_set *set, const aim_device_ctx &d, aim_slot &s, const aim_batch_io_sam_t *sio, uint32_t n_rows, const uint32_t *sel)
+int aim::capi::enqueue_sam_on_slot(const aim_set *set, const aim_device_ctx &d, aim_slot &s, const aim_batch_io_sam_t *sio, uint32_t n_rows, const uint32_t *sel)
 {
     aim::SamArgs a;
     memset(&a, 0, sizeof a);
@@ -809,13 +575,12 @@ int enqueue_sam_on_slot(const aim_set *set, const aim_device_ctx &d, aim_slot &s
     return enqueue_sam(set->params, set->knobs, a, s.stream);
 }
 // ... and its copies back: the records and the cursors now, the words and bytes in aim_set_wait (their count is only known then)
-int enqueue_sam_d2h(aim_slot &s, uint32_t n_rows)
+int aim::capi::enqueue_sam_d2h(aim_slot &s, uint32_t n_rows)
 {
     HIP_TRY(hipMemcpyAsync(s.h_samcur, s.d_samcur, 8, hipMemcpyDeviceToHost, s.stream));
     HIP_TRY(hipMemcpyAsync(s.io_sam, s.d_sam, (size_t)n_rows * sizeof(aim_sam_t), hipMemcpyDeviceToHost, s.stream));
     return AIM_OK;
 }
-}  // namespace
 
 
 extern "C" {
@@ -1037,7 +802,6 @@ int aim_set_configure(aim_set_t *set, const aim_params_t *params, uint32_t max_p
 
 namespace {
 const char *const kGroupsSubmitOnly = "AIM_FLAG_READ_GROUPS is set: batches go through aim_set_submit with an aim_batch_io_groups_t";
-const char *const kSamStateless = "AIM_FLAG_SAM_FIELDS is set: the records come from aim_set_submit (aim_batch_io_sam_t) or, after a flag-less call, from aim_sam_device";
 const char *const kSamSubmitOnly = "AIM_FLAG_SAM_FIELDS is set: batches go through aim_set_submit with an aim_batch_io_sam_t";
 
 // aim_set_push (texts != nullptr) and aim_set_push_ref (text_pos != nullptr)
@@ -1105,13 +869,8 @@ int aim_set_launch(aim_set_t *set)
         HIP_TRY(hipSetDevice(d.dev));
         HIP_TRY(hipEventRecord(s.ev[2], s.stream));
         if (s.ref_pending && s.n_pairs) {   // AIM_FLAG_REF_TEXTS: the windows into the text rows, ahead of the plan's stages
-            aim::KArgs ka;
-            memset(&ka, 0, sizeof ka);
-            ka.p = set->params;
-            ka.n_pairs = s.n_pairs;
-            ka.req = static_cast<const aim_request_t *>(s.d_req);
-            int grc = enqueue_gather(ka, s.d_tpos, d.d_ref, d.ref_len, nullptr, s.n_pairs, s.d_txt, s.stream);
-            if (grc) return grc;
+            aim::gather_text_rows_launch(batch_args(set->params, s.n_pairs, s.d_req), s.d_tpos, d.d_ref, d.ref_len, nullptr, s.n_pairs, s.d_txt, s.stream);
+            HIP_TRY(hipGetLastError());
         }
         int rc = launch_on_slot(set, d, s);
         if (rc) return rc;
@@ -1163,279 +922,6 @@ int aim_set_pull(aim_set_t *set, uint32_t device, void *results, char *ops)
         if (r[i].status != AIM_PAIR_OK) return status_error(r[i].idx, r[i].status);
     return AIM_OK;
 }
-
-namespace {
-// aim_groups_check: the CSR of a groups batch, the first bad read named
-int check_groups(uint32_t n_pairs, uint32_t n_reads, const uint32_t *roff, uint32_t *bad_read)
-{
-    auto bad = [&](uint32_t r, const char *what) {
-        if (bad_read) *bad_read = r;
-        return fail(AIM_EINVAL, "read_offsets: read %u %s", r, what);
-    };
-    if (!n_reads) return n_pairs ? fail(AIM_EINVAL, "read_offsets: %u candidates but no read", n_pairs) : AIM_OK;
-    if (!roff) return fail(AIM_EINVAL, "read_offsets is NULL");
-    if (roff[0] != 0) return bad(0, "does not start at offset 0");
-    for (uint32_t r = 0; r < n_reads; ++r) {
-        if (roff[r + 1] < roff[r]) return bad(r, "ends before it starts (offsets decrease)");
-        if (roff[r + 1] == roff[r]) return bad(r, "has no candidate");
-        if (roff[r + 1] > n_pairs) return bad(r, "runs past n_pairs");
-    }
-    if (roff[n_reads] != n_pairs) return bad(n_reads - 1, "is the last and does not end at n_pairs");
-    return AIM_OK;
-}
-
-// A plan of one pass for this batch's size under the set's frozen knobs and budget; the configure-time plan when it would need more
-// scratch than the slot holds (every kernel tolerates a grid larger than its work)
-Plan pass_plan(const aim_set *set, const aim_device_ctx &d, const aim_slot &s, const aim_params_t &pp, uint32_t n, const Plan &configured)
-{
-    Plan pl;
-    aim::Knobs quiet = set->knobs;
-    quiet.plan_debug = false;
-    if (make_plan(pp, n, quiet, d.budget, &pl) || pl.scratch_total > s.scratch_bytes) pl = configured;
-    return pl;
-}
-
-// aim_mates_check: the read pairs and the pairing parameters of a mate-pairs batch
-int check_mates(uint32_t n_reads, int64_t min_span, int64_t max_span, int32_t unpaired_penalty)
-{
-    if (n_reads & 1u) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS: n_reads %u is odd (reads 2m and 2m + 1 are mates)", n_reads);
-    if (min_span < 0 || max_span < min_span || max_span >= ((int64_t)1 << 62))
-        return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS: bad span [%lld, %lld]: need 0 <= min_span <= max_span < 2^62", (long long)min_span,
-                    (long long)max_span);
-    if (unpaired_penalty < 0) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS: unpaired_penalty %d is negative", unpaired_penalty);
-    return AIM_OK;
-}
-
-// aim_hits_offsets: the exclusive prefix sum of min(K_r, max_hits)
-int hits_offsets(uint32_t n_reads, const uint32_t *roff, uint32_t max_hits, uint32_t *hoff, uint32_t *n_hits)
-{
-    if (max_hits < 1 || max_hits > AIM_TOP_HITS_MAX)
-        return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: max_hits %u is outside 1..%d", max_hits, AIM_TOP_HITS_MAX);
-    if (!roff || !hoff) return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: null read_offsets or hit_offsets");
-    uint32_t h = 0;
-    for (uint32_t r = 0; r < n_reads; ++r) {
-        hoff[r] = h;
-        h += std::min(roff[r + 1] > roff[r] ? roff[r + 1] - roff[r] : 0u, max_hits);
-    }
-    hoff[n_reads] = h;
-    if (n_hits) *n_hits = h;
-    return AIM_OK;
-}
-
-// AIM_FLAG_TOP_HITS on a slot: the caller's hit_offsets against the CSR (already checked), before anything is enqueued; *n_hits receives H
-int check_hits_io(const aim_batch_io_hits_t *hio, uint32_t n_reads, const uint32_t *roff, uint32_t *n_hits)
-{
-    if (hio->max_hits < 1 || hio->max_hits > AIM_TOP_HITS_MAX)
-        return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: max_hits %u is outside 1..%d", hio->max_hits, AIM_TOP_HITS_MAX);
-    *n_hits = 0;
-    if (!n_reads) return AIM_OK;
-    if (!hio->hit_offsets) return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: null hit_offsets");
-    uint32_t h = 0;
-    for (uint32_t r = 0; r < n_reads; ++r) {
-        if (hio->hit_offsets[r] != h)
-            return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: hit_offsets[%u] = %u, but the hits of read %u start at row %u (aim_hits_offsets)", r,
-                        hio->hit_offsets[r], r, h);
-        h += std::min(roff[r + 1] - roff[r], hio->max_hits);
-    }
-    if (hio->hit_offsets[n_reads] != h)
-        return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: hit_offsets[%u] = %u, but the hits of read %u end at row %u (aim_hits_offsets)", n_reads,
-                    hio->hit_offsets[n_reads], n_reads - 1, h);
-    *n_hits = h;
-    return AIM_OK;
-}
-
-// aim_set_submit under AIM_FLAG_READ_GROUPS
-int submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const aim_batch_io_t *io)
-{
-    const aim_params_t &p = set->params;
-    const aim_batch_io_groups_t *gio = reinterpret_cast<const aim_batch_io_groups_t *>(io);
-    const uint32_t n = io->n_pairs, nr = gio->n_reads;
-    const bool bt = p.flags & AIM_FLAG_BACKTRACE;
-    const bool ref = is_ref(p);
-    const bool packed = io->packed_patterns || io->packed_texts;
-    // AIM_FLAG_MATE_PAIRS: io is the base of an aim_batch_io_mates_t
-    const aim_batch_io_mates_t *mio = is_mates(p) ? reinterpret_cast<const aim_batch_io_mates_t *>(io) : nullptr;
-    // AIM_FLAG_TOP_HITS: io is the base of an aim_batch_io_hits_t
-    const aim_batch_io_hits_t *hio = is_hits(p) ? reinterpret_cast<const aim_batch_io_hits_t *>(io) : nullptr;
-    if (packed && (!ref || io->packed_texts))
-        return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS: packed batches need AIM_FLAG_REF_TEXTS (packed explicit texts are a follow-up)");
-    if (packed && (!s.d_packP || !s.g_rawslot)) return fail(AIM_EINVAL, "packed batch needs a set configured with max_raw_pairs > 0");
-    if (packed && io->n_raw > set->max_raw) return fail(AIM_EINVAL, "n_raw %u exceeds configured capacity %u", io->n_raw, set->max_raw);
-    if (packed && io->n_raw && (!io->raw_pairs || !io->raw_patterns)) return fail(AIM_EINVAL, "null raw side list");
-    if (!packed && io->n_raw) return fail(AIM_EINVAL, "a raw side list needs a packed batch");
-    if (ref && (io->texts || io->raw_texts)) return fail(AIM_EINVAL, "AIM_FLAG_REF_TEXTS: texts, packed_texts and raw_texts must be NULL (the texts are named by text_pos)");
-    if (ref && n && !gio->text_pos) return fail(AIM_EINVAL, "AIM_FLAG_REF_TEXTS: null text_pos");
-    if (!ref && gio->text_pos) return fail(AIM_EINVAL, "text_pos needs AIM_FLAG_REF_TEXTS");
-    if (ref && !d.d_ref) return fail(AIM_ESTATE, "AIM_FLAG_REF_TEXTS: no reference on device %d (aim_set_reference)", d.dev);
-    if (n > set->max_pairs) return fail(AIM_EINVAL, "n_pairs %u exceeds configured capacity %u", n, set->max_pairs);
-    if (n && (!io->requests || (!packed && !io->patterns) || (!ref && !io->texts))) return fail(AIM_EINVAL, "null requests or sequence rows");
-    if (io->cigars && (!bt || !s.d_cig || !io->runs)) return fail(AIM_EINVAL, "compact CIGAR needs AIM_FLAG_BACKTRACE, max_runs > 0 and a run buffer");
-    const aim_batch_io_sam_t *sio = nullptr;
-    int rc = check_sam_io(set, s, io, &sio);
-    if (rc) return rc;
-    if (n && !io->results && !io->cigars && !gio->best && !(mio && mio->mates) && !sio && !(hio && hio->hit_pair)) return fail(AIM_EINVAL, "no output buffer");
-    if (io->ops && !bt) return fail(AIM_EINVAL, "ops requested without AIM_FLAG_BACKTRACE");
-    rc = check_groups(n, nr, gio->read_offsets, nullptr);
-    if (rc) return rc;
-    if (mio) {
-        rc = check_mates(nr, mio->min_span, mio->max_span, mio->unpaired_penalty);
-        if (rc) return rc;
-    }
-    uint32_t rows = nr;   // the batch's output rows: reads, or hits
-    if (hio) {
-        rc = check_hits_io(hio, nr, gio->read_offsets, &rows);
-        if (rc) return rc;
-    }
-    if (packed)   // the side list names reads
-        for (uint32_t j = 0; j < io->n_raw; ++j)
-            if (io->raw_pairs[j] >= nr) return fail(AIM_EINVAL, "raw_pairs[%u] = %u is outside the batch's %u reads", j, io->raw_pairs[j], nr);
-    rc = check_lengths(p, n, io->requests);
-    if (rc) return rc;
-    if (ref) {
-        rc = check_windows(p, n, io->requests, gio->text_pos, d.ref_len, nullptr);
-        if (rc) return rc;
-    }
-    const size_t rs = (size_t)p.read_size;
-    HIP_TRY(hipSetDevice(d.dev));
-    s.io = *io;
-    s.n_pairs = rows;        // aim_set_wait reads n_pairs output rows
-    s.n_reads = nr;
-    s.io_sam = nullptr;
-    s.runs_sent = 0;
-    s.pushed = s.launched = false;
-    s.ref_pending = false;
-    GroupsPlan g;
-    memset(&g, 0, sizeof g);
-    g.x1 = groups_pass_params(p, AIM_FLAG_BACKTRACE | AIM_FLAG_WFA_BIDIR | AIM_FLAG_RES8);
-    g.x2 = groups_pass_params(p, 0u);
-    g.pass2 = bt;
-    g.mates = mio != nullptr;
-    g.sam = is_sam(p);
-    g.hits = hio != nullptr;
-    auto enqueue = [&]() -> int {
-        HIP_TRY(hipEventRecord(s.ev[0], s.stream));
-        if (n) {
-            HIP_TRY(hipMemcpyAsync(s.d_req, io->requests, (size_t)n * req_size(p), hipMemcpyHostToDevice, s.stream));
-            HIP_TRY(hipMemcpyAsync(s.g_roff, gio->read_offsets, ((size_t)nr + 1) * 4, hipMemcpyHostToDevice, s.stream));
-            if (hio) HIP_TRY(hipMemcpyAsync(s.g_hoff, hio->hit_offsets, ((size_t)nr + 1) * 4, hipMemcpyHostToDevice, s.stream));
-            if (packed) {
-                HIP_TRY(hipMemcpyAsync(s.d_packP, io->packed_patterns, (size_t)nr * aim::packed_row_dwords(p.read_size) * 4, hipMemcpyHostToDevice, s.stream));
-                if (io->n_raw) {
-                    HIP_TRY(hipMemcpyAsync(s.d_rawidx, io->raw_pairs, (size_t)io->n_raw * 4, hipMemcpyHostToDevice, s.stream));
-                    HIP_TRY(hipMemcpyAsync(s.d_rawP, io->raw_patterns, (size_t)io->n_raw * rs, hipMemcpyHostToDevice, s.stream));
-                }
-            } else {
-                HIP_TRY(hipMemcpyAsync(s.g_readP, io->patterns, (size_t)nr * rs, hipMemcpyHostToDevice, s.stream));
-            }
-            if (ref) HIP_TRY(hipMemcpyAsync(s.d_tpos, gio->text_pos, (size_t)n * 8, hipMemcpyHostToDevice, s.stream));
-            else HIP_TRY(hipMemcpyAsync(s.d_txt, io->texts, (size_t)n * rs, hipMemcpyHostToDevice, s.stream));
-        }
-        HIP_TRY(hipEventRecord(s.ev[1], s.stream));
-        HIP_TRY(hipEventRecord(s.ev[2], s.stream));
-        if (n) {
-            if (ref) {
-                aim::KArgs ka;
-                memset(&ka, 0, sizeof ka);
-                ka.p = p;
-                ka.n_pairs = n;
-                ka.req = static_cast<const aim_request_t *>(s.d_req);
-                int grc = enqueue_gather(ka, s.d_tpos, d.d_ref, d.ref_len, nullptr, n, s.d_txt, s.stream);
-                if (grc) return grc;
-            }
-            const Plan pl1 = pass_plan(set, d, s, g.x1.base, n, d.plan);
-            const Plan pl2 = bt ? pass_plan(set, d, s, g.x2.base, rows, d.plan2) : Plan();
-            s.plan_last = pl1;
-            s.plan_last2 = pl2;
-            GroupsIo gi;
-            gi.n_pairs = n;
-            gi.n_reads = nr;
-            gi.req = s.d_req;
-            gi.read_rows = packed ? nullptr : s.g_readP;
-            gi.packed = s.d_packP;
-            gi.raw_pairs = s.d_rawidx;
-            gi.raw_rows = s.d_rawP;
-            gi.n_raw = packed ? io->n_raw : 0u;
-            gi.raw_slot = s.g_rawslot;
-            gi.roff = s.g_roff;
-            gi.cand_p = s.d_pat;
-            gi.cand_t = s.d_txt;
-            gi.res1 = s.g_res1;
-            gi.map = s.g_map;
-            gi.sel = s.g_sel;
-            gi.best = s.g_best;
-            gi.tpos = s.d_tpos;
-            memset(&gi.mate, 0, sizeof gi.mate);
-            if (mio) {
-                gi.mate.min_span = mio->min_span;
-                gi.mate.max_span = mio->max_span;
-                gi.mate.unpaired_penalty = mio->unpaired_penalty;
-            }
-            gi.mates = s.g_mates;
-            gi.n_hits = hio ? rows : 0u;
-            gi.max_hits = hio ? hio->max_hits : 0u;
-            gi.hoff = s.g_hoff;
-            gi.hit_pair = s.g_hit;
-            gi.req2 = s.g_req2;
-            gi.pat2 = s.g_pat2;
-            gi.txt2 = s.g_txt2;
-            gi.res = s.d_res;
-            gi.ops = s.d_ops;
-            gi.scratch = s.d_scratch;
-            gi.scratch_bytes = s.scratch_bytes;
-            int erc = enqueue_groups(g, pl1, pl2, set->knobs, gi, s.stream, &s.aux);
-            if (erc) return erc;
-            if (io->cigars) {
-                aim::KArgs k2;
-                memset(&k2, 0, sizeof k2);
-                k2.p = g.x2.base;
-                k2.n_pairs = rows;
-                k2.req = static_cast<const aim_request_t *>(s.g_req2);
-                k2.res = static_cast<aim_result_t *>(s.d_res);
-                k2.ops = s.d_ops;
-                HIP_TRY(hipMemsetAsync(s.d_cursor, 0, 4, s.stream));
-                hipLaunchKernelGGL(aim::cigar_rle_kernel, dim3((rows + 63) / 64), dim3(64), 0, s.stream, k2, s.d_cig, s.d_runs,
-                                   std::min(io->runs_cap, set->max_runs), s.d_cursor);
-                HIP_TRY(hipGetLastError());
-            }
-            if (sio) {   // the reads' records: row r is candidate sel[r]
-                int src = enqueue_sam_on_slot(set, d, s, sio, nr, s.g_sel);
-                if (src) return src;
-            }
-        }
-        HIP_TRY(hipEventRecord(s.ev[3], s.stream));
-        HIP_TRY(hipEventRecord(s.ev[4], s.stream));
-        if (n) {
-            if (gio->best) HIP_TRY(hipMemcpyAsync(gio->best, s.g_best, (size_t)nr * sizeof(aim_best_t), hipMemcpyDeviceToHost, s.stream));
-            if (mio && mio->mates && nr >= 2)
-                HIP_TRY(hipMemcpyAsync(mio->mates, s.g_mates, (size_t)(nr / 2) * sizeof(aim_mate_t), hipMemcpyDeviceToHost, s.stream));
-            if (io->cigars) {
-                HIP_TRY(hipMemcpyAsync(s.h_cursor, s.d_cursor, 4, hipMemcpyDeviceToHost, s.stream));
-                HIP_TRY(hipMemcpyAsync(io->cigars, s.d_cig, (size_t)rows * sizeof(aim_cigar_t), hipMemcpyDeviceToHost, s.stream));
-            }
-            if (io->results) HIP_TRY(hipMemcpyAsync(io->results, s.d_res, (size_t)rows * res_size(p), hipMemcpyDeviceToHost, s.stream));
-            if (io->ops) HIP_TRY(hipMemcpyAsync(io->ops, s.d_ops, (size_t)rows * 2 * rs, hipMemcpyDeviceToHost, s.stream));
-            if (hio && hio->hit_pair) HIP_TRY(hipMemcpyAsync(hio->hit_pair, s.g_hit, (size_t)rows * 4, hipMemcpyDeviceToHost, s.stream));
-            if (sio) {
-                int src = enqueue_sam_d2h(s, nr);
-                if (src) return src;
-            }
-        }
-        HIP_TRY(hipEventRecord(s.ev[5], s.stream));
-        return AIM_OK;
-    };
-    rc = enqueue();
-    if (rc) {   // (as aim_set_submit: nothing stays in flight on a failed submit)
-        char keep[sizeof g_err];
-        memcpy(keep, g_err, sizeof keep);
-        (void)hipStreamSynchronize(s.stream);
-        (void)hipGetLastError();
-        memcpy(g_err, keep, sizeof keep);
-        return rc;
-    }
-    s.submitted = true;
-    return AIM_OK;
-}
-}  // namespace
 
 int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_batch_io_t *io)
 {
@@ -1512,11 +998,7 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
         HIP_TRY(hipEventRecord(s.ev[1], s.stream));
         HIP_TRY(hipEventRecord(s.ev[2], s.stream));
         if (n) {
-            aim::KArgs ka;
-            memset(&ka, 0, sizeof ka);
-            ka.p = p;
-            ka.n_pairs = n;
-            ka.req = static_cast<const aim_request_t *>(s.d_req);
+            aim::KArgs ka = batch_args(p, n, s.d_req);
             ka.res = static_cast<aim_result_t *>(s.d_res);
             ka.ops = s.d_ops;
             // Does the alignment kernel of this configuration take the batch as it arrived and deliver what was asked for?
@@ -1536,15 +1018,9 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
             }
             const uint32_t runs_cap = std::min(io->runs_cap, set->max_runs);
             if (packed && !pl.pk) {   // expand into the reference's char[n][READ_SIZE] layout (batch_io.hpp), then run as usual
-                const uint64_t threads = (uint64_t)n * (rs / 8);
                 const unsigned rows = ref ? 1u : 2u;   // (grid.y 0: patterns; the texts of a reference batch are gathered below)
-                hipLaunchKernelGGL(aim::unpack_rows_kernel, dim3((unsigned)((threads + 255) / 256), rows), dim3(256), 0, s.stream, ka, s.d_packP,
-                                   s.d_packT, s.d_pat, s.d_txt);
-                if (io->n_raw) {
-                    const uint64_t rt = (uint64_t)io->n_raw * (rs / 8);
-                    hipLaunchKernelGGL(aim::scatter_raw_rows_kernel, dim3((unsigned)((rt + 255) / 256), rows), dim3(256), 0, s.stream, p.read_size,
-                                       io->n_raw, s.d_rawidx, s.d_rawP, s.d_rawT, s.d_pat, s.d_txt);
-                }
+                aim::unpack_rows_launch(ka, s.d_packP, s.d_packT, s.d_pat, s.d_txt, rows, s.stream);
+                if (io->n_raw) aim::scatter_raw_rows_launch(p.read_size, io->n_raw, s.d_rawidx, s.d_rawP, s.d_rawT, s.d_pat, s.d_txt, rows, s.stream);
                 HIP_TRY(hipGetLastError());
             }
             uint32_t *ref_todo = s.d_reftodo;
@@ -1553,15 +1029,15 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
                 uint32_t *flag_bits = ref_todo + 16 + set->max_pairs;
                 HIP_TRY(hipMemsetAsync(ref_todo, 0, 64, s.stream));
                 HIP_TRY(hipMemsetAsync(flag_bits, 0, ((size_t)n + 31) / 32 * 4, s.stream));
-                const uint64_t threads = (uint64_t)n * aim::packed_row_dwords(p.read_size);
-                hipLaunchKernelGGL(aim::gather_text_packed_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s.stream, ka, s.d_tpos,
-                                   d.d_ref, d.ref_len, s.d_packT, flag_bits, ref_todo);
+                aim::gather_text_packed_launch(ka, s.d_tpos, d.d_ref, d.ref_len, s.d_packT, flag_bits, ref_todo, s.stream);
                 HIP_TRY(hipGetLastError());
-                rc = enqueue_gather(ka, s.d_tpos, d.d_ref, d.ref_len, s.d_rawidx, io->n_raw, s.d_rawT, s.stream);
-                if (rc) return rc;
+                if (io->n_raw) {
+                    aim::gather_text_rows_launch(ka, s.d_tpos, d.d_ref, d.ref_len, s.d_rawidx, io->n_raw, s.d_rawT, s.stream);
+                    HIP_TRY(hipGetLastError());
+                }
             } else if (ref) {
-                rc = enqueue_gather(ka, s.d_tpos, d.d_ref, d.ref_len, nullptr, n, s.d_txt, s.stream);
-                if (rc) return rc;
+                aim::gather_text_rows_launch(ka, s.d_tpos, d.d_ref, d.ref_len, nullptr, n, s.d_txt, s.stream);
+                HIP_TRY(hipGetLastError());
             }
             FusedIo fio;
             if (pl.pk) { fio.packedP = s.d_packP; fio.packedT = s.d_packT; }
@@ -1570,8 +1046,7 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
             if (rc) return rc;
             if (ref_fused) {
                 // the to-do windows: ASCII rows (pattern unpacked, text gathered), the general kernel over them, their compact CIGAR
-                hipLaunchKernelGGL(aim::gather_todo_rows_kernel, dim3(256), dim3(256), 0, s.stream, ka, ref_todo, s.d_tpos, d.d_ref, d.ref_len,
-                                   s.d_packP, s.d_pat, s.d_txt);
+                aim::gather_todo_rows_launch(ka, ref_todo, s.d_tpos, d.d_ref, d.ref_len, s.d_packP, s.d_pat, s.d_txt, s.stream);
                 HIP_TRY(hipGetLastError());
                 aim::KArgs kb = stage_args(ka, ref_fb, s.d_scratch);
                 kb.patterns = s.d_pat;
@@ -1580,14 +1055,14 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
                 launch_stage(p, ref_fb, kb, s.stream);
                 HIP_TRY(hipGetLastError());
                 if (pl.emits_runs) {
-                    hipLaunchKernelGGL(aim::cigar_rle_todo_kernel, dim3(256), dim3(64), 0, s.stream, kb, ref_todo, s.d_cig, s.d_runs, runs_cap, s.d_cursor);
+                    aim::cigar_rle_todo_launch(kb, ref_todo, s.d_cig, s.d_runs, runs_cap, s.d_cursor, s.stream);
                     HIP_TRY(hipGetLastError());
                 }
             }
             s.runs_sent = pl.emits_runs ? n * fio.run_slot : 0u;   // 0 when the run buffer is bump-allocated: nothing is known before the kernel ran
             if (io->cigars && !pl.emits_runs) {
                 HIP_TRY(hipMemsetAsync(s.d_cursor, 0, 4, s.stream));
-                hipLaunchKernelGGL(aim::cigar_rle_kernel, dim3((n + 63) / 64), dim3(64), 0, s.stream, ka, s.d_cig, s.d_runs, runs_cap, s.d_cursor);
+                aim::cigar_rle_launch(ka, s.d_cig, s.d_runs, runs_cap, s.d_cursor, s.stream);
                 HIP_TRY(hipGetLastError());
             }
             if (pl.pk && io->n_raw) {
@@ -1597,9 +1072,7 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
                 // replace the void ones (with the compact CIGAR: their runs are appended to the run buffer).
                 const uint32_t nr = io->n_raw;
                 const uint32_t rq_dw = (uint32_t)req_size(p) / 4, rs_dw = (uint32_t)res_size(p) / 4;
-                auto blocks = [](uint64_t t) { return dim3((unsigned)((t + 255) / 256)); };
-                hipLaunchKernelGGL(aim::gather_elems_kernel, blocks((uint64_t)nr * rq_dw), dim3(256), 0, s.stream, (const uint32_t *)s.d_req,
-                                   s.d_rawidx, nr, rq_dw, (uint32_t *)s.d_rawreq);
+                aim::gather_elems_launch((const uint32_t *)s.d_req, s.d_rawidx, nr, rq_dw, (uint32_t *)s.d_rawreq, s.stream);
                 HIP_TRY(hipGetLastError());
                 const Plan rp = plan_for_batch(set, d, s, nr, 0u);
                 rc = launch(rp, set->knobs, p, nr, s.d_rawreq, s.d_rawP, s.d_rawT, s.d_rawres, s.d_rawops, s.d_scratch, s.scratch_bytes, s.stream, nullptr, &s.aux);
@@ -1610,17 +1083,14 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
                     kr.n_pairs = nr;
                     kr.res = static_cast<aim_result_t *>(s.d_rawres);
                     kr.ops = s.d_rawops;
-                    hipLaunchKernelGGL(aim::cigar_rle_kernel, dim3((nr + 63) / 64), dim3(64), 0, s.stream, kr, s.d_rawcig, s.d_runs, runs_cap, s.d_cursor);
-                    hipLaunchKernelGGL(aim::scatter_elems_kernel, blocks((uint64_t)nr * 4), dim3(256), 0, s.stream, (const uint32_t *)s.d_rawcig,
-                                       s.d_rawidx, nr, 4u, (uint32_t *)s.d_cig);
+                    aim::cigar_rle_launch(kr, s.d_rawcig, s.d_runs, runs_cap, s.d_cursor, s.stream);
+                    aim::scatter_elems_launch((const uint32_t *)s.d_rawcig, s.d_rawidx, nr, 4u, (uint32_t *)s.d_cig, s.stream);
                 }
                 if (!io->cigars || io->results || io->ops || sio) {
-                    hipLaunchKernelGGL(aim::scatter_elems_kernel, blocks((uint64_t)nr * rs_dw), dim3(256), 0, s.stream, (const uint32_t *)s.d_rawres,
-                                       s.d_rawidx, nr, rs_dw, (uint32_t *)s.d_res);
+                    aim::scatter_elems_launch((const uint32_t *)s.d_rawres, s.d_rawidx, nr, rs_dw, (uint32_t *)s.d_res, s.stream);
                     if (bt) {   // default output (result_t + ops rows): the side list's ops rows go home too
                         const uint32_t op_dw = (uint32_t)(2 * rs / 4);
-                        hipLaunchKernelGGL(aim::scatter_elems_kernel, blocks((uint64_t)nr * op_dw), dim3(256), 0, s.stream, (const uint32_t *)s.d_rawops,
-                                           s.d_rawidx, nr, op_dw, (uint32_t *)s.d_ops);
+                        aim::scatter_elems_launch((const uint32_t *)s.d_rawops, s.d_rawidx, nr, op_dw, (uint32_t *)s.d_ops, s.stream);
                     }
                 }
                 HIP_TRY(hipGetLastError());
@@ -1651,14 +1121,7 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
         return AIM_OK;
     };
     rc = enqueue();
-    if (rc) {
-        char keep[sizeof g_err];
-        memcpy(keep, g_err, sizeof keep);
-        (void)hipStreamSynchronize(s.stream);
-        (void)hipGetLastError();
-        memcpy(g_err, keep, sizeof keep);
-        return rc;
-    }
+    if (rc) return fail_drained(s, rc);
     s.submitted = true;
     return AIM_OK;
 }
@@ -1895,13 +1358,8 @@ int aim_align_device_ref(const aim_params_t *params, uint32_t n_pairs, const voi
     if (!d_scratch || scratch_bytes < need) return fail(AIM_EINVAL, "scratch too small: need %zu bytes, got %zu", need, scratch_bytes);
     if (n_pairs == 0) return AIM_OK;
     char *rows = static_cast<char *>(d_scratch) + at;
-    aim::KArgs ka;
-    memset(&ka, 0, sizeof ka);
-    ka.p = *params;
-    ka.n_pairs = n_pairs;
-    ka.req = static_cast<const aim_request_t *>(d_requests);
-    rc = enqueue_gather(ka, d_text_pos, d_reference, ref_len, nullptr, n_pairs, rows, (hipStream_t)hip_stream);
-    if (rc) return rc;
+    aim::gather_text_rows_launch(batch_args(*params, n_pairs, d_requests), d_text_pos, d_reference, ref_len, nullptr, n_pairs, rows, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
     return launch(pl, kn, *params, n_pairs, d_requests, d_patterns, rows, d_results, d_ops, d_scratch, at, (hipStream_t)hip_stream);
 }
 
@@ -2008,162 +1466,6 @@ const char *aim_sam_kernel_name(const aim_params_t *params)
 {
     if (!params) return "";
     return sam_use_wave(*params, read_knobs()) ? "sam_wave_kernel" : "sam_lane_kernel";
-}
-
-
-int aim_groups_check(uint32_t n_pairs, uint32_t n_reads, const uint32_t *read_offsets, uint32_t *bad_read)
-{
-    return check_groups(n_pairs, n_reads, read_offsets, bad_read);
-}
-
-int aim_mates_check(uint32_t n_reads, int64_t min_span, int64_t max_span, int32_t unpaired_penalty)
-{
-    return check_mates(n_reads, min_span, max_span, unpaired_penalty);
-}
-
-namespace {
-// AIM_FLAG_TOP_HITS: the hit rows of a stateless call
-struct HitArgs {
-    uint32_t max_hits, n_hits;
-    const uint32_t *hoff;
-    uint32_t *hit_pair;      // or nullptr: the hit list lives in the scratch
-};
-
-// aim_align_device_groups (mate == nullptr, hit == nullptr), aim_align_device_mates and aim_align_device_hits
-int align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
-                        const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
-                        const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, const aim::MateArgs *mate,
-                        aim_mate_t *d_mates, const HitArgs *hit, void *d_scratch, size_t scratch_bytes, void *hip_stream)
-{
-    const bool ref = is_ref(*params), bt = params->flags & AIM_FLAG_BACKTRACE;
-    if (is_sam(*params)) return fail(AIM_EINVAL, kSamStateless);
-    if (n_reads > n_pairs || (n_pairs && !n_reads)) return fail(AIM_EINVAL, "n_reads %u does not fit n_pairs %u", n_reads, n_pairs);
-    if (n_pairs && (!d_requests || !d_patterns || !d_read_offsets || !d_results || (bt && !d_ops) ||
-                    (ref ? (!d_text_pos_or_null || !d_reference) : !d_texts_or_null)))
-        return fail(AIM_EINVAL, "null device buffer");
-    int n = 0;
-    int rc = aim_device_count(&n);
-    if (rc) return rc;
-    const aim::Knobs kn = read_knobs();
-    const uint64_t budget = stateless_budget_bytes(kn);
-    GroupsPlan g;
-    rc = make_groups_plan(*params, n_pairs, kn, budget, &g);
-    if (rc) return rc;
-    if (!d_scratch || scratch_bytes < g.total) return fail(AIM_EINVAL, "scratch too small: need %zu bytes, got %zu", g.total, scratch_bytes);
-    if (n_pairs == 0) return AIM_OK;
-    char *base = static_cast<char *>(d_scratch);
-    const hipStream_t stream = (hipStream_t)hip_stream;
-    GroupsIo gi;
-    gi.n_pairs = n_pairs;
-    gi.n_reads = n_reads;
-    gi.req = d_requests;
-    gi.read_rows = d_patterns;
-    gi.packed = nullptr;
-    gi.raw_pairs = nullptr;
-    gi.raw_rows = nullptr;
-    gi.n_raw = 0;
-    gi.raw_slot = nullptr;
-    gi.roff = d_read_offsets;
-    gi.cand_p = base + g.cand_p_at;
-    gi.cand_t = ref ? base + g.cand_t_at : const_cast<char *>(d_texts_or_null);
-    gi.res1 = reinterpret_cast<aim_result_t *>(base + g.res1_at);
-    gi.map = reinterpret_cast<uint32_t *>(base + g.map_at);
-    gi.sel = reinterpret_cast<uint32_t *>(base + g.sel_at);
-    gi.best = d_best ? d_best : (mate ? reinterpret_cast<aim_best_t *>(base + g.best_at) : nullptr);
-    gi.tpos = d_text_pos_or_null;
-    memset(&gi.mate, 0, sizeof gi.mate);
-    if (mate) gi.mate = *mate;
-    gi.mates = d_mates;
-    gi.n_hits = hit ? hit->n_hits : 0u;
-    gi.max_hits = hit ? hit->max_hits : 0u;
-    gi.hoff = hit ? hit->hoff : nullptr;
-    gi.hit_pair = !hit ? nullptr : hit->hit_pair ? hit->hit_pair : reinterpret_cast<uint32_t *>(base + g.hit_at);
-    gi.req2 = bt ? base + g.req2_at : nullptr;
-    gi.pat2 = bt ? base + g.pat2_at : nullptr;
-    gi.txt2 = bt ? base + g.txt2_at : nullptr;
-    gi.res = d_results;
-    gi.ops = d_ops;
-    gi.scratch = d_scratch;
-    gi.scratch_bytes = g.plan_bytes;
-    if (ref) {
-        aim::KArgs ka;
-        memset(&ka, 0, sizeof ka);
-        ka.p = *params;
-        ka.n_pairs = n_pairs;
-        ka.req = static_cast<const aim_request_t *>(d_requests);
-        rc = enqueue_gather(ka, d_text_pos_or_null, d_reference, ref_len, nullptr, n_pairs, gi.cand_t, stream);
-        if (rc) return rc;
-    }
-    // pass 2 re-planned for its rows (smaller grids); the n_pairs plan where that would not fit the plans' region
-    Plan pl2 = g.p2;
-    if (bt) {
-        Plan q;
-        aim::Knobs quiet = kn;
-        quiet.plan_debug = false;
-        if (!make_plan(g.x2.base, hit ? hit->n_hits : n_reads, quiet, budget, &q) && q.scratch_total <= g.plan_bytes) pl2 = q;
-    }
-    return enqueue_groups(g, g.p1, pl2, kn, gi, stream, nullptr);
-}
-}  // namespace
-
-int aim_align_device_groups(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
-                            const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
-                            const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, void *d_scratch,
-                            size_t scratch_bytes, void *hip_stream)
-{
-    if (!params) return fail(AIM_EINVAL, "params is NULL");
-    if (!is_groups(*params)) return fail(AIM_EINVAL, "aim_align_device_groups needs AIM_FLAG_READ_GROUPS");
-    if (is_mates(*params)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS is set: use aim_align_device_mates");
-    if (is_hits(*params)) return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS is set: use aim_align_device_hits");
-    return align_device_groups(params, n_pairs, n_reads, d_requests, d_patterns, d_texts_or_null, d_text_pos_or_null, d_reference, ref_len,
-                               d_read_offsets, d_results, d_ops, d_best, nullptr, nullptr, nullptr, d_scratch, scratch_bytes, hip_stream);
-}
-
-int aim_hits_offsets(uint32_t n_reads, const uint32_t *read_offsets, uint32_t max_hits, uint32_t *hit_offsets, uint32_t *n_hits)
-{
-    return hits_offsets(n_reads, read_offsets, max_hits, hit_offsets, n_hits);
-}
-
-int aim_align_device_hits(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
-                          const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
-                          const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, uint32_t max_hits,
-                          const uint32_t *d_hit_offsets, uint32_t n_hits, uint32_t *d_hit_pair, void *d_scratch, size_t scratch_bytes,
-                          void *hip_stream)
-{
-    if (!params) return fail(AIM_EINVAL, "params is NULL");
-    if (!is_hits(*params)) return fail(AIM_EINVAL, "aim_align_device_hits needs AIM_FLAG_TOP_HITS");
-    int rc = validate_params(*params);   // (names a missing AIM_FLAG_READ_GROUPS, or AIM_FLAG_MATE_PAIRS / AIM_FLAG_SAM_FIELDS)
-    if (rc) return rc;
-    if (max_hits < 1 || max_hits > AIM_TOP_HITS_MAX)
-        return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: max_hits %u is outside 1..%d", max_hits, AIM_TOP_HITS_MAX);
-    if (n_hits > n_pairs || n_hits < n_reads)
-        return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: n_hits %u does not fit n_reads %u and n_pairs %u (aim_hits_offsets)", n_hits, n_reads, n_pairs);
-    if (n_pairs && !d_hit_offsets) return fail(AIM_EINVAL, "AIM_FLAG_TOP_HITS: null d_hit_offsets");
-    const HitArgs ha{max_hits, n_hits, d_hit_offsets, d_hit_pair};
-    return align_device_groups(params, n_pairs, n_reads, d_requests, d_patterns, d_texts_or_null, d_text_pos_or_null, d_reference, ref_len,
-                               d_read_offsets, d_results, d_ops, d_best, nullptr, nullptr, &ha, d_scratch, scratch_bytes, hip_stream);
-}
-
-int aim_align_device_mates(const aim_params_t *params, uint32_t n_pairs, uint32_t n_reads, const void *d_requests, const char *d_patterns,
-                           const char *d_texts_or_null, const uint64_t *d_text_pos_or_null, const char *d_reference, uint64_t ref_len,
-                           const uint32_t *d_read_offsets, void *d_results, char *d_ops, aim_best_t *d_best, int64_t min_span,
-                           int64_t max_span, int32_t unpaired_penalty, aim_mate_t *d_mates, void *d_scratch, size_t scratch_bytes,
-                           void *hip_stream)
-{
-    if (!params) return fail(AIM_EINVAL, "params is NULL");
-    if (!is_mates(*params)) return fail(AIM_EINVAL, "aim_align_device_mates needs AIM_FLAG_MATE_PAIRS");
-    int rc = validate_params(*params);   // (names a missing AIM_FLAG_READ_GROUPS / AIM_FLAG_REF_TEXTS)
-    if (rc) return rc;
-    if (d_texts_or_null) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS: d_texts must be NULL (the texts are named by d_text_pos)");
-    rc = check_mates(n_reads, min_span, max_span, unpaired_penalty);
-    if (rc) return rc;
-    aim::MateArgs ma;
-    memset(&ma, 0, sizeof ma);
-    ma.min_span = min_span;
-    ma.max_span = max_span;
-    ma.unpaired_penalty = unpaired_penalty;
-    return align_device_groups(params, n_pairs, n_reads, d_requests, d_patterns, nullptr, d_text_pos_or_null, d_reference, ref_len,
-                               d_read_offsets, d_results, d_ops, d_best, &ma, d_mates, nullptr, d_scratch, scratch_bytes, hip_stream);
 }
 
 }  // extern "C"

@@ -23,6 +23,44 @@ namespace aim {
 // [2*(i%16), 2*(i%16)+1] of dword i/16 of its row; a row is ceil(READ_SIZE/16) dwords.
 __host__ __device__ inline uint32_t packed_row_dwords(int read_size) { return (uint32_t)(read_size + 15) / 16u; }
 
+// ---- launchers -------------------------------------------------------------------------------------------------------
+// The kernels below are instantiated in ONE translation unit (tu_batch_io.hip defines AIM_TU_BATCH_IO); every other includer sees
+// these declarations, packed_row_dwords and the two grid rules only. A launcher owns its kernel's grid and block; the caller checks
+// hipGetLastError().
+inline dim3 blocks_256(uint64_t threads) { return dim3((unsigned)((threads + 255) / 256)); }   // one thread per element, 256 per workgroup
+// The row gathers (gather_text_rows_kernel here, group_rows_kernel in groups.hpp): a thread moves 4 nw bytes of one row -- 16-B stores
+// where the row stride READ_SIZE allows them, else 8-B.
+struct RowGather { int nw; dim3 grid; };
+inline RowGather row_gather(int read_size, uint32_t n_rows)
+{
+    const int nw = (read_size & 15) == 0 ? 4 : 2;
+    return RowGather{nw, blocks_256((uint64_t)n_rows * (uint64_t)(read_size / (4 * nw)))};
+}
+#pragma GCC visibility push(hidden)
+// grid.y = planes: 1 expands / scatters the pattern rows only (the texts of a reference batch are gathered), 2 both
+void unpack_rows_launch(const KArgs &ka, const uint32_t *packedP, const uint32_t *packedT, char *outP, char *outT, unsigned planes, hipStream_t s);
+void scatter_raw_rows_launch(int read_size, uint32_t n_raw, const uint32_t *raw_pairs, const char *rawP, const char *rawT, char *outP, char *outT,
+                             unsigned planes, hipStream_t s);
+void pack_rows_launch(const KArgs &ka, uint32_t *packedP, uint32_t *packedT, uint32_t *flag_bits, uint32_t *todo, hipStream_t s);
+void gather_elems_launch(const uint32_t *src, const uint32_t *idx, uint32_t n, uint32_t dw, uint32_t *dst, hipStream_t s);
+void scatter_elems_launch(const uint32_t *src, const uint32_t *idx, uint32_t n, uint32_t dw, uint32_t *dst, hipStream_t s);
+void cigar_rle_launch(const KArgs &ka, aim_cigar_t *hdr, uint32_t *runs, uint32_t runs_cap, uint32_t *cursor, hipStream_t s);   // pairs 0 .. ka.n_pairs - 1
+void cigar_rle_todo_launch(const KArgs &ka, const uint32_t *todo, aim_cigar_t *hdr, uint32_t *runs, uint32_t runs_cap, uint32_t *cursor, hipStream_t s);
+void unpack_todo_rows_launch(const KArgs &ka, const uint32_t *todo, const uint32_t *packedP, const uint32_t *packedT, char *outP, char *outT, hipStream_t s);
+// AIM_FLAG_REF_TEXTS: text rows [n_rows][READ_SIZE] of `out` gathered from the reference; row r is the window of pair idx[r]
+// (idx == nullptr: pair r). ka carries the params and the requests. Nothing is launched for n_rows == 0.
+void gather_text_rows_launch(const KArgs &ka, const uint64_t *text_pos, const char *ref, uint64_t ref_len, const uint32_t *idx, uint32_t n_rows, char *out,
+                             hipStream_t s);
+void gather_text_packed_launch(const KArgs &ka, const uint64_t *text_pos, const char *ref, uint64_t ref_len, uint32_t *packedT, uint32_t *flag_bits,
+                               uint32_t *todo, hipStream_t s);
+void gather_todo_rows_launch(const KArgs &ka, const uint32_t *todo, const uint64_t *text_pos, const char *ref, uint64_t ref_len, const uint32_t *packedP,
+                             char *outP, char *outT, hipStream_t s);
+// escalate_select_kernel, then escalate_list_kernel on the same grid: the pairs of `res` whose score is `over`, as the list `todo`
+void escalate_list_launch(const uint32_t *res, uint32_t n_pairs, uint32_t stride_dw, uint32_t score_dw, int32_t over, uint2 *masks, uint32_t *counts,
+                          uint32_t *todo, hipStream_t s);
+#pragma GCC visibility pop
+
+#ifdef AIM_TU_BATCH_IO
 // One thread expands 8 bases (16 packed bits -> 8 ASCII bytes); bytes at or beyond the sequence length are zero, like
 // the parser's rows.  grid.y: 0 = patterns, 1 = texts.
 __global__ __launch_bounds__(256) void unpack_rows_kernel(KArgs a, const uint32_t *packedP, const uint32_t *packedT, char *outP, char *outT)
@@ -496,5 +534,81 @@ __global__ __launch_bounds__(256) void escalate_list_kernel(uint32_t n_pairs, co
         if ((m >> lane) & 1ull) todo[16u + base + goff[gl] + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull))] = g * 64u + lane;
     }
 }
+
+// ---- the launchers declared at the top ---------------------------------------------------------------------------------------
+void unpack_rows_launch(const KArgs &ka, const uint32_t *packedP, const uint32_t *packedT, char *outP, char *outT, unsigned planes, hipStream_t s)
+{
+    const dim3 grid(blocks_256((uint64_t)ka.n_pairs * (uint64_t)(ka.p.read_size / 8)).x, planes);
+    hipLaunchKernelGGL(unpack_rows_kernel, grid, dim3(256), 0, s, ka, packedP, packedT, outP, outT);
+}
+
+void scatter_raw_rows_launch(int read_size, uint32_t n_raw, const uint32_t *raw_pairs, const char *rawP, const char *rawT, char *outP, char *outT,
+                             unsigned planes, hipStream_t s)
+{
+    const dim3 grid(blocks_256((uint64_t)n_raw * (uint64_t)(read_size / 8)).x, planes);
+    hipLaunchKernelGGL(scatter_raw_rows_kernel, grid, dim3(256), 0, s, read_size, n_raw, raw_pairs, rawP, rawT, outP, outT);
+}
+
+void pack_rows_launch(const KArgs &ka, uint32_t *packedP, uint32_t *packedT, uint32_t *flag_bits, uint32_t *todo, hipStream_t s)
+{
+    const dim3 grid(blocks_256((uint64_t)ka.n_pairs * packed_row_dwords(ka.p.read_size)).x, 2);
+    hipLaunchKernelGGL(pack_rows_kernel, grid, dim3(256), 0, s, ka, packedP, packedT, flag_bits, todo);
+}
+
+void gather_elems_launch(const uint32_t *src, const uint32_t *idx, uint32_t n, uint32_t dw, uint32_t *dst, hipStream_t s)
+{
+    hipLaunchKernelGGL(gather_elems_kernel, blocks_256((uint64_t)n * dw), dim3(256), 0, s, src, idx, n, dw, dst);
+}
+
+void scatter_elems_launch(const uint32_t *src, const uint32_t *idx, uint32_t n, uint32_t dw, uint32_t *dst, hipStream_t s)
+{
+    hipLaunchKernelGGL(scatter_elems_kernel, blocks_256((uint64_t)n * dw), dim3(256), 0, s, src, idx, n, dw, dst);
+}
+
+void cigar_rle_launch(const KArgs &ka, aim_cigar_t *hdr, uint32_t *runs, uint32_t runs_cap, uint32_t *cursor, hipStream_t s)
+{
+    hipLaunchKernelGGL(cigar_rle_kernel, dim3((ka.n_pairs + 63) / 64), dim3(64), 0, s, ka, hdr, runs, runs_cap, cursor);
+}
+
+void cigar_rle_todo_launch(const KArgs &ka, const uint32_t *todo, aim_cigar_t *hdr, uint32_t *runs, uint32_t runs_cap, uint32_t *cursor, hipStream_t s)
+{
+    hipLaunchKernelGGL(cigar_rle_todo_kernel, dim3(256), dim3(64), 0, s, ka, todo, hdr, runs, runs_cap, cursor);
+}
+
+void unpack_todo_rows_launch(const KArgs &ka, const uint32_t *todo, const uint32_t *packedP, const uint32_t *packedT, char *outP, char *outT, hipStream_t s)
+{
+    hipLaunchKernelGGL(unpack_todo_rows_kernel, dim3(256), dim3(256), 0, s, ka, todo, packedP, packedT, outP, outT);
+}
+
+void gather_text_rows_launch(const KArgs &ka, const uint64_t *text_pos, const char *ref, uint64_t ref_len, const uint32_t *idx, uint32_t n_rows, char *out,
+                             hipStream_t s)
+{
+    if (!n_rows) return;
+    const RowGather g = row_gather(ka.p.read_size, n_rows);
+    if (g.nw == 4) hipLaunchKernelGGL(gather_text_rows_kernel<4>, g.grid, dim3(256), 0, s, ka, text_pos, ref, ref_len, idx, n_rows, out);
+    else hipLaunchKernelGGL(gather_text_rows_kernel<2>, g.grid, dim3(256), 0, s, ka, text_pos, ref, ref_len, idx, n_rows, out);
+}
+
+void gather_text_packed_launch(const KArgs &ka, const uint64_t *text_pos, const char *ref, uint64_t ref_len, uint32_t *packedT, uint32_t *flag_bits,
+                               uint32_t *todo, hipStream_t s)
+{
+    hipLaunchKernelGGL(gather_text_packed_kernel, blocks_256((uint64_t)ka.n_pairs * packed_row_dwords(ka.p.read_size)), dim3(256), 0, s, ka, text_pos, ref,
+                       ref_len, packedT, flag_bits, todo);
+}
+
+void gather_todo_rows_launch(const KArgs &ka, const uint32_t *todo, const uint64_t *text_pos, const char *ref, uint64_t ref_len, const uint32_t *packedP,
+                             char *outP, char *outT, hipStream_t s)
+{
+    hipLaunchKernelGGL(gather_todo_rows_kernel, dim3(256), dim3(256), 0, s, ka, todo, text_pos, ref, ref_len, packedP, outP, outT);
+}
+
+void escalate_list_launch(const uint32_t *res, uint32_t n_pairs, uint32_t stride_dw, uint32_t score_dw, int32_t over, uint2 *masks, uint32_t *counts,
+                          uint32_t *todo, hipStream_t s)
+{
+    const dim3 grid((n_pairs + kEscTile - 1) / kEscTile);
+    hipLaunchKernelGGL(escalate_select_kernel, grid, dim3(256), 0, s, res, n_pairs, stride_dw, score_dw, over, masks, counts);
+    hipLaunchKernelGGL(escalate_list_kernel, grid, dim3(256), 0, s, n_pairs, masks, counts, todo);
+}
+#endif  // AIM_TU_BATCH_IO
 
 }  // namespace aim

@@ -1,5 +1,5 @@
 // batch_sizes.hpp -- host constants and size functions of batch_io.hpp's kernels that the launch planner (capi_plan.hip) needs too.
-// No kernel here: batch_io.hpp defines its kernels without an AIM_TU_* guard, so only aim_capi.hip may include it.
+// No kernel and no launcher here; batch_io.hpp includes it.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -1,12 +1,15 @@
-// capi_common.hpp -- what the units of the C-ABI share: aim_capi.hip (device sets, launching, alignment entry points), capi_plan.hip (the
-// launch planner; its types and entry points are in plan.hpp), capi_pipeline.hip (index, seeding, classes and MAPQ, split, extension),
-// capi_mapper.hip (the record list and aim_mapper_t) and capi_host.hip (host-side formatters and generators). Internal, not installed.
+// capi_common.hpp -- what the units of the C-ABI share: aim_capi.hip (device sets, launching, alignment entry points), capi_groups.hip
+// (the read-groups path: AIM_FLAG_READ_GROUPS, MATE_PAIRS and TOP_HITS; it shares the device set with aim_capi.hip through capi_set.hpp),
+// capi_plan.hip (the launch planner; its types and entry points are in plan.hpp), capi_pipeline.hip (index, seeding, classes and MAPQ,
+// split, extension), capi_mapper.hip (the record list and aim_mapper_t) and capi_host.hip (host-side formatters and generators). None of
+// them compiles a kernel: each kernel family's tu_*.hip does, and these units call its launchers. Internal, not installed.
 // Every function declared here has ONE definition, next to the state it owns: fail() in aim_capi.hip, where it writes the thread-local
 // buffer aim_last_error() returns; read_knobs(), the one reader of the AIM_* environment, with_chip(), which asks chip_cus()'s per-device
 // cache, and check_align_params() in capi_plan.hip; the parameter checks of the pipeline's stages in capi_pipeline.hip; the refusals the
 // pipeline's entry points share inline below.
 #pragma once
 #include <cstdint>
+#include <cstring>
 
 #include <hip/hip_runtime.h>
 
@@ -21,8 +24,6 @@ aim::Knobs read_knobs();                    // the AIM_* environment, as it is n
 aim::Knobs with_chip(aim::Knobs k);         // ... for a plan on the current device: AIM_CHIP_CUS wins, else the device's own CU count
 // Every length of a batch against READ_SIZE; AIM_EINVAL names the first pair that breaks it.
 int check_lengths(const aim_params_t &p, uint32_t n_pairs, const void *requests);
-// Dwords of a packed sequence row: aim::packed_row_dwords (batch_io.hpp) for the units that must not include its kernels.
-uint32_t packed_row_dwords(int read_size);
 // AIM_FLAG_REF_TEXTS: texts gathered from a device-resident reference (batch_io.hpp); no plan depends on it.
 inline bool is_ref(const aim_params_t &p) { return (p.flags & AIM_FLAG_REF_TEXTS) != 0; }
 // What every alignment entry point refuses about its aim_params_t (capi_plan.hip: validate_params), before any device query.
@@ -63,6 +64,16 @@ inline bool ref_len_ok(const char *fn, uint64_t ref_len, bool say_why)
 inline bool buffers_ok(const char *fn, uint32_t n_reads, bool all_set) { return !n_reads || all_set || refuse("%s: null device buffer", fn); }
 // AIM_DEBUG_POISON_LDS as the kernels take it (dbg_poison_lds): 0x100 | byte, or 0 for "leave LDS as it is"
 inline uint32_t poison_lds_word(const aim::Knobs &kn) { return kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u; }
+// The KArgs of a batch-I/O kernel: the params, the pair count and the requests; every other member zero
+inline aim::KArgs batch_args(const aim_params_t &p, uint32_t n_pairs, const void *req)
+{
+    aim::KArgs ka;
+    memset(&ka, 0, sizeof ka);
+    ka.p = p;
+    ka.n_pairs = n_pairs;
+    ka.req = static_cast<const aim_request_t *>(req);
+    return ka;
+}
 #pragma GCC visibility pop
 }  // namespace capi
 }  // namespace aim

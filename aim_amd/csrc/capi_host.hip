@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "capi_common.hpp"
+#include "batch_io.hpp"   // packed_row_dwords
 
 using namespace aim::capi;
 
@@ -78,7 +79,7 @@ int aim_sam_format_cigar(const uint32_t *words, uint32_t n, char *out, int32_t c
 int aim_pack_sequence(const char *seq, int32_t len, int32_t read_size, uint32_t *row)
 {
     if (!seq || !row || len < 0 || len > read_size) return fail(AIM_EINVAL, "bad arguments");
-    const uint32_t dw = packed_row_dwords(read_size);
+    const uint32_t dw = aim::packed_row_dwords(read_size);
     uint32_t bad = 0;
     int i = 0;
     for (uint32_t w = 0; w < dw; ++w) {
@@ -107,7 +108,7 @@ int aim_pack_batch(const aim_params_t *params, uint32_t n_pairs, const void *req
     if (rs <= 0 || (rs & 7)) return fail(AIM_EINVAL, "read_size must be a positive multiple of 8");
     int rc = check_lengths(*params, n_pairs, requests);
     if (rc) return rc;
-    const uint32_t dw = packed_row_dwords(rs);
+    const uint32_t dw = aim::packed_row_dwords(rs);
     const bool req8 = params->flags & AIM_FLAG_REQ8;
     if (threads < 1) threads = 1;
     if (threads > 256) threads = 256;

@@ -4,8 +4,7 @@
 // entry points' scratch budget per device -- and so do the three entry points that only plan: aim_scratch_bytes, aim_plan_describe
 // and aim_kernel_name. Launching, device sets and the alignment entry points are in aim_capi.hip.
 // The alignment-kernel headers below give their *_plan, *_supported and size functions; their kernels stay in the tu_*.hip units.
-// batch_io.hpp, groups.hpp, hits.hpp and mates.hpp define kernels without such a guard and belong to aim_capi.hip alone: what the
-// planner needs of them is in batch_sizes.hpp and capi::packed_row_dwords.
+// Of the batch-I/O kernels the planner needs the region sizes (batch_sizes.hpp) and packed_row_dwords (batch_io.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,7 +23,7 @@
 #include "dp_strip.hpp"
 #include "dp_reg.hpp"
 #include "dp_group.hpp"
-#include "batch_sizes.hpp"
+#include "batch_io.hpp"
 #include "genasm_wave.hpp"
 
 using namespace aim::capi;
@@ -439,7 +438,7 @@ int plan_wfa_flagless(const aim_params_t &p, uint32_t n_pairs, const aim::Knobs 
         aim::wfa_lane_packed_plan(p, n_pairs, kn, &m.grid, &m.block, &m.lds);
         pl->pack_first = true;
         const size_t flag_b = (((size_t)n_pairs + 31) / 32 * 4 + 255) & ~(size_t)255;
-        const size_t arr_b = (((size_t)n_pairs * packed_row_dwords(p.read_size) * 4) + 64 + 255) & ~(size_t)255;
+        const size_t arr_b = (((size_t)n_pairs * aim::packed_row_dwords(p.read_size) * 4) + 64 + 255) & ~(size_t)255;
         pl->flags_at = pl->todo_bytes;
         pl->pack_p_at = pl->flags_at + flag_b;
         pl->pack_t_at = pl->pack_p_at + arr_b;

@@ -14,10 +14,27 @@
 #include <climits>
 
 #include "aim_device.hpp"
-#include "batch_io.hpp"   // packed_row_dwords
+#include "batch_io.hpp"   // packed_row_dwords, blocks_256, row_gather
 
 namespace aim {
 
+constexpr uint32_t kGroupReadsPerWave = 64;
+
+// The kernels of this header, hits.hpp and mates.hpp are instantiated in ONE translation unit (tu_groups.hip defines AIM_TU_GROUPS);
+// every other includer sees the launchers' declarations and the constants host code reads. A launcher owns its kernel's grid and block;
+// the caller checks hipGetLastError().
+#pragma GCC visibility push(hidden)
+void group_map_launch(const uint32_t *roff, uint32_t n_reads, uint32_t n_pairs, uint32_t *cand_read, hipStream_t s);
+// (nothing is launched for n_rows == 0)
+void group_rows_launch(const KArgs &ka, const char *src, uint32_t n_src, const uint32_t *src_idx, uint32_t n_rows, int text, char *out, hipStream_t s);
+void group_raw_slot_launch(const uint32_t *raw_pairs, uint32_t n_raw, uint32_t n_reads, uint32_t *raw_slot, hipStream_t s);
+void group_unpack_launch(const KArgs &ka, const uint32_t *packed, const uint32_t *map, const uint32_t *raw_slot, const char *raw_rows, uint32_t n_raw,
+                         uint32_t n_reads, char *out, hipStream_t s);
+void group_select_launch(const aim_result_t *res, uint32_t n_pairs, const uint32_t *roff, uint32_t n_reads, aim_best_t *best, uint32_t *sel, hipStream_t s);
+void group_results_launch(const aim_result_t *res1, const uint32_t *sel, uint32_t n_reads, int res8, void *out, hipStream_t s);
+#pragma GCC visibility pop
+
+#ifdef AIM_TU_GROUPS
 // cand_read[c] = the read r with read_offsets[r] <= c < read_offsets[r + 1]. A CSR the host check would refuse yields some r in
 // [0, n_reads), never an access outside read_offsets[0 .. n_reads].
 __global__ __launch_bounds__(256) void group_map_kernel(const uint32_t *roff, uint32_t n_reads, uint32_t n_pairs, uint32_t *cand_read)
@@ -130,8 +147,6 @@ __device__ __forceinline__ GroupSel group_combine(const GroupSel &a, const Group
     return GroupSel{a.s, a.idx, a.cnt + b.cnt, a.s};
 }
 
-constexpr uint32_t kGroupReadsPerWave = 64;
-
 // One wave64 per kGroupReadsPerWave consecutive reads. It walks their candidates 64 at a time: each lane loads one candidate's
 // {score, status}, finds its read by a binary search inside the wave's reads, and a segmented inclusive scan (6 lane shifts) combines
 // the lanes of each read. A read that continues past a chunk is carried (wave-uniform) into the next one, so a read of any size is
@@ -208,5 +223,49 @@ __global__ __launch_bounds__(256) void group_results_kernel(const aim_result_t *
         static_cast<aim_result_t *>(out)[r] = x;
     }
 }
+
+// ---- the launchers declared at the top ---------------------------------------------------------------------------------------
+void group_map_launch(const uint32_t *roff, uint32_t n_reads, uint32_t n_pairs, uint32_t *cand_read, hipStream_t s)
+{
+    hipLaunchKernelGGL(group_map_kernel, blocks_256(n_pairs), dim3(256), 0, s, roff, n_reads, n_pairs, cand_read);
+}
+
+void group_rows_launch(const KArgs &ka, const char *src, uint32_t n_src, const uint32_t *src_idx, uint32_t n_rows, int text, char *out, hipStream_t s)
+{
+    if (!n_rows) return;
+    const RowGather g = row_gather(ka.p.read_size, n_rows);
+    if (g.nw == 4) hipLaunchKernelGGL(group_rows_kernel<4>, g.grid, dim3(256), 0, s, ka, src, n_src, src_idx, n_rows, text, out);
+    else hipLaunchKernelGGL(group_rows_kernel<2>, g.grid, dim3(256), 0, s, ka, src, n_src, src_idx, n_rows, text, out);
+}
+
+void group_raw_slot_launch(const uint32_t *raw_pairs, uint32_t n_raw, uint32_t n_reads, uint32_t *raw_slot, hipStream_t s)
+{
+    hipLaunchKernelGGL(group_raw_slot_kernel, blocks_256(n_raw), dim3(256), 0, s, raw_pairs, n_raw, n_reads, raw_slot);
+}
+
+void group_unpack_launch(const KArgs &ka, const uint32_t *packed, const uint32_t *map, const uint32_t *raw_slot, const char *raw_rows, uint32_t n_raw,
+                         uint32_t n_reads, char *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(group_unpack_kernel, blocks_256((uint64_t)ka.n_pairs * (uint64_t)(ka.p.read_size / 8)), dim3(256), 0, s, ka, packed, map, raw_slot,
+                       raw_rows, n_raw, n_reads, out);
+}
+
+// group_select_kernel and hit_select_kernel (hits.hpp): four wavefronts per workgroup, kGroupReadsPerWave reads per wavefront
+inline dim3 group_select_grid(uint32_t n_reads)
+{
+    const uint32_t waves = (n_reads + kGroupReadsPerWave - 1) / kGroupReadsPerWave;
+    return dim3((waves + 3) / 4);
+}
+
+void group_select_launch(const aim_result_t *res, uint32_t n_pairs, const uint32_t *roff, uint32_t n_reads, aim_best_t *best, uint32_t *sel, hipStream_t s)
+{
+    hipLaunchKernelGGL(group_select_kernel, group_select_grid(n_reads), dim3(256), 0, s, res, n_pairs, roff, n_reads, best, sel);
+}
+
+void group_results_launch(const aim_result_t *res1, const uint32_t *sel, uint32_t n_reads, int res8, void *out, hipStream_t s)
+{
+    hipLaunchKernelGGL(group_results_kernel, blocks_256(n_reads), dim3(256), 0, s, res1, sel, n_reads, res8, out);
+}
+#endif  // AIM_TU_GROUPS
 
 }  // namespace aim

@@ -19,6 +19,12 @@
 
 namespace aim {
 
+#pragma GCC visibility push(hidden)
+void hit_select_launch(const aim_result_t *res, uint32_t n_pairs, const uint32_t *roff, uint32_t n_reads, const uint32_t *hoff, uint32_t max_hits,
+                       uint32_t n_hits, uint32_t *hit_pair, hipStream_t s);
+#pragma GCC visibility pop
+
+#ifdef AIM_TU_GROUPS   // (groups.hpp: one unit for its kernels, these and mates.hpp's)
 // cls 0: AIM_PAIR_OK, s = the score with its sign bit flipped (int32 order as uint32 order); cls 1: any other status, s = 0.
 // cls 2 is no candidate: greater than every key a candidate has.
 struct HitKey {
@@ -119,5 +125,12 @@ __global__ __launch_bounds__(256) void hit_select_kernel(const aim_result_t *res
         last = got;
     }
 }
+
+void hit_select_launch(const aim_result_t *res, uint32_t n_pairs, const uint32_t *roff, uint32_t n_reads, const uint32_t *hoff, uint32_t max_hits,
+                       uint32_t n_hits, uint32_t *hit_pair, hipStream_t s)
+{
+    hipLaunchKernelGGL(hit_select_kernel, group_select_grid(n_reads), dim3(256), 0, s, res, n_pairs, roff, n_reads, hoff, max_hits, n_hits, hit_pair);
+}
+#endif  // AIM_TU_GROUPS
 
 }  // namespace aim

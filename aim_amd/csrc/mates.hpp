@@ -23,6 +23,13 @@ struct MateArgs {
     uint32_t lanes;         // W: lanes per read pair, a power of two in 1 .. 64 (results do not depend on it)
 };
 
+// mate_select_kernel over the n_reads / 2 read pairs of a batch of ka.n_pairs candidates; n_mates and lanes of `ma` are filled in here
+#pragma GCC visibility push(hidden)
+void mate_select_launch(const KArgs &ka, MateArgs ma, uint32_t n_reads, const aim_result_t *res, const uint64_t *tpos, const uint32_t *roff,
+                        const aim_best_t *best, uint32_t *sel, aim_mate_t *mates, hipStream_t s);
+#pragma GCC visibility pop
+
+#ifdef AIM_TU_GROUPS   // (groups.hpp: one unit for its kernels, hits.hpp's and these)
 // What a set of combinations of one read pair contributes: the lowest proper cost, its combination (lowest i, then lowest j), how many
 // proper combinations have that cost and the lowest cost among the others (INT_MAX when there is none). cnt == 0: no proper combination.
 struct MateSel {
@@ -138,5 +145,18 @@ __global__ __launch_bounds__(256) void mate_select_kernel(KArgs a, MateArgs ma, 
         out[1] = hi;
     }
 }
+
+void mate_select_launch(const KArgs &ka, MateArgs ma, uint32_t n_reads, const aim_result_t *res, const uint64_t *tpos, const uint32_t *roff,
+                        const aim_best_t *best, uint32_t *sel, aim_mate_t *mates, hipStream_t s)
+{
+    // lanes per read pair: the power of two that covers an average read pair's combinations (any value gives the same rows)
+    ma.n_mates = n_reads / 2;
+    const uint64_t k = ((uint64_t)ka.n_pairs + n_reads - 1) / n_reads, combos = k * k;
+    ma.lanes = 1;
+    while (ma.lanes < (uint32_t)kWave && ma.lanes < combos) ma.lanes <<= 1;
+    const uint64_t threads = (uint64_t)ma.n_mates * ma.lanes;
+    hipLaunchKernelGGL(mate_select_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, ka, ma, res, tpos, roff, best, sel, mates);
+}
+#endif  // AIM_TU_GROUPS
 
 }  // namespace aim

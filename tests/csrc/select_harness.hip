@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "aim_hip.h"
+#define AIM_TU_GROUPS 1   // this helper launches the kernels itself, so it instantiates them
 #include "groups.hpp"
 #include "mates.hpp"
 

@@ -113,10 +113,10 @@ def test_refusals_without_a_device():
 
 def test_refusals_in_the_library_source():
     """The messages of the refusals that need a configured set (checked on the GPU where a device exists)."""
-    src = open(os.path.join(ROOT, "aim_amd", "csrc", "aim_capi.hip")).read()
-    for msg in ("AIM_FLAG_READ_GROUPS is set: batches go through aim_set_submit with an aim_batch_io_groups_t",
-                "AIM_FLAG_READ_GROUPS: packed batches need AIM_FLAG_REF_TEXTS (packed explicit texts are a follow-up)"):
-        assert msg in src
+    src = open(os.path.join(ROOT, "aim_amd", "csrc", "aim_capi.hip")).read()        # push / launch / pull refuse a groups set here
+    groups = open(os.path.join(ROOT, "aim_amd", "csrc", "capi_groups.hip")).read()  # ... and submit_groups refuses its batches here
+    assert "AIM_FLAG_READ_GROUPS is set: batches go through aim_set_submit with an aim_batch_io_groups_t" in src
+    assert "AIM_FLAG_READ_GROUPS: packed batches need AIM_FLAG_REF_TEXTS (packed explicit texts are a follow-up)" in groups
     assert src.count("kGroupsSubmitOnly") == 4      # the definition, aim_set_push(_ref), aim_set_launch, aim_set_pull
 
 

@@ -148,7 +148,7 @@ def test_refusals_without_a_device():
 
 def test_refusals_in_the_library_source():
     """The messages of the refusal that needs a configured set (checked on the GPU where a device exists)."""
-    src = open(os.path.join(ROOT, "aim_amd", "csrc", "aim_capi.hip")).read()
+    src = open(os.path.join(ROOT, "aim_amd", "csrc", "capi_groups.hip")).read()
     for msg in ("AIM_FLAG_TOP_HITS: hit_offsets[%u] = %u, but the hits of read %u start at row %u (aim_hits_offsets)",
                 "AIM_FLAG_TOP_HITS: hit_offsets[%u] = %u, but the hits of read %u end at row %u (aim_hits_offsets)",
                 "AIM_FLAG_TOP_HITS: null hit_offsets"):
