@@ -4,11 +4,11 @@
 // dpu_push_xfer / dpu_launch (WFA/DPU-WRAM/host/host.c:186-330) is done here
 // with one HIP stream per device, HBM buffers planned per configuration, and
 // asynchronous copies.  No CPU fallback exists: every compute entry point
-// needs a HIP device.  This unit launches: device sets, slots, submits and the alignment entry points. It compiles no kernel: every
-// kernel family's tu_*.hip does, and this unit calls the launchers their headers declare. The read-groups path (AIM_FLAG_READ_GROUPS,
-// MATE_PAIRS, TOP_HITS) is in capi_groups.hip, which shares the device set's types and this unit's launch() through capi_set.hpp; the
-// launch planner and the entry points that only plan are in capi_plan.hip (plan.hpp), the read-mapping pipeline's entry points in
-// capi_pipeline.hip, the host-side helpers in capi_host.hip.
+// needs a HIP device.  This unit is the device set: its slots and their buffers, push / launch / pull, aim_set_submit as a sequence of
+// steps, aim_set_wait, the SAM entry points and the host-side checks of a batch. It compiles no kernel and launches no alignment kernel:
+// a plan becomes launches in capi_launch.hip (launch(), with aim_align_device[_ref]), reached through capi_set.hpp like the read-groups
+// path (AIM_FLAG_READ_GROUPS, MATE_PAIRS, TOP_HITS) of capi_groups.hip; the launch planner and the entry points that only plan are in
+// capi_plan.hip (plan.hpp), the read-mapping pipeline's entry points in capi_pipeline.hip, the host-side helpers in capi_host.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,25 +17,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <thread>
-#include <type_traits>
 #include <vector>
 
 #include "capi_set.hpp"
-#include "wfa_wave.hpp"
-#include "wfa_bidir.hpp"
-#include "wfa_lane.hpp"
-#include "wfa_lane_packed.hpp"
-#include "wfa_group.hpp"
-#include "dp_lane.hpp"
-#include "dp_wave.hpp"
-#include "dp_strip.hpp"
-#include "dp_reg.hpp"
-#include "dp_group.hpp"
+#include "wfa_lane_packed.hpp"   // kRunSlot
 #include "batch_io.hpp"
 #include "sam_fields.hpp"
-#include "genasm_wave.hpp"
 
 using namespace aim::capi;
 
@@ -62,306 +50,63 @@ int aim::capi::fail_drained(aim_slot &s, int rc)
     return rc;
 }
 
-namespace {
-
-// KArgs of one stage: where its scratch starts, its slab and what its plan chose for wfa_wave
-aim::KArgs stage_args(aim::KArgs ka, const Stage &st, void *d_scratch)
+void aim::capi::reset_slot(aim_slot &s, const aim_batch_io_t *io)
 {
-    ka.scratch = (char *)d_scratch + st.scratch_at;
-    ka.scratch_per_wave = st.scratch_per_wg;
-    ka.pool_cap = st.pool_cap;
-    ka.meta_cap = st.meta_cap;
-    ka.ring_slots = st.ring_slots;
-    ka.slot_w = st.slot_w;
-    ka.dbg_lds_bytes = (uint32_t)st.lds;
-    return ka;
+    s.io = *io;
+    s.io_sam = nullptr;
+    s.runs_sent = 0;
+    s.pushed = s.launched = false;
+    s.ref_pending = false;
 }
 
-// The kernels that run alone or as the to-do pass behind another one (ka.todo set)
-void launch_stage(const aim_params_t &p, const Stage &st, const aim::KArgs &ka, hipStream_t s)
+int aim::capi::enqueue_rows_d2h(const aim_params_t &p, aim_slot &s, uint32_t rows)
 {
-    switch (st.kid) {
-    case K_WFA_WAVE: aim::wfa_wave_launch(p.flags & AIM_FLAG_BACKTRACE, p.flags & AIM_FLAG_REDUCE, st.seq_lds, st.grid, st.lds, ka, s); break;
-    case K_DP_LANE: aim::dp_lane_launch(p, st.seq, st.grid, st.lds, ka, s); break;
-    case K_DP_STRIP: aim::dp_strip_launch(p, st.strip_k, st.grid, st.block, st.lds, ka, s); break;
-    default: break;
+    const aim_batch_io_t &io = s.io;
+    if (io.cigars) {
+        HIP_TRY(hipMemcpyAsync(s.h_cursor, s.d_cursor, 4, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(hipMemcpyAsync(io.cigars, s.d_cig, (size_t)rows * sizeof(aim_cigar_t), hipMemcpyDeviceToHost, s.stream));
+        // slotted run buffer (wfa_lane_packed.hpp): the first 3 n runs are the pairs' own slots, known now -- their copy
+        // overlaps the next batch instead of waiting in aim_set_wait for the cursor; only runs behind the slots follow there
+        if (s.runs_sent) HIP_TRY(hipMemcpyAsync(io.runs, s.d_runs, (size_t)s.runs_sent * 4, hipMemcpyDeviceToHost, s.stream));
     }
-}
-
-int aux_stream_create(AuxStream &a)
-{
-    if (a.stream) return AIM_OK;
-    HIP_TRY(hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(hipEventCreateWithFlags(&a.computed[i], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&a.walked[i], hipEventDisableTiming));
-    }
-    return AIM_OK;
-}
-void aux_stream_destroy(AuxStream &a)
-{
-    for (int i = 0; i < 2; ++i) {
-        if (a.computed[i]) (void)hipEventDestroy(a.computed[i]);
-        if (a.walked[i]) (void)hipEventDestroy(a.walked[i]);
-    }
-    if (a.stream) (void)hipStreamDestroy(a.stream);
-    a = AuxStream();
-}
-struct SharedAux { std::mutex mu; AuxStream aux; };
-SharedAux *shared_aux_for_current_device()
-{
-    static SharedAux table[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return nullptr; }
-    return &table[dev];
-}
-
-// Enqueue one alignment launch that follows the one-stage plan `pl` (made for >= n_pairs pairs under the caller's knobs and budget).
-// list_in (AIM_FLAG_WFA_ESCALATE, second stage): the launch's pairs are those of the device-side list {count @0, pair ids @16..}, at most
-// n_pairs of them; every buffer stays the batch's. Only wfa_group (+ its traceback) and wfa_wave take one.
-int launch_one(const StagePlan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t n_pairs, const void *d_req,
-               const char *d_pat, const char *d_txt, void *d_res, char *d_ops, void *d_scratch, size_t scratch_bytes,
-               hipStream_t stream, const FusedIo *fio = nullptr, AuxStream *slot_aux = nullptr, const uint32_t *list_in = nullptr)
-{
-    if (n_pairs == 0) return AIM_OK;
-    const bool bt = p.flags & AIM_FLAG_BACKTRACE;
-    if (list_in && pl.main.kid != K_WFA_GROUP && pl.main.kid != K_WFA_WAVE) return fail(AIM_EINVAL, "plan takes no pair list");
-    if (pl.pk && !pl.pack_first && (!fio || !fio->packedP || !fio->packedT)) return fail(AIM_EINVAL, "plan reads packed rows but none were given");
-    if (pl.emits_runs && (!fio || !fio->cig || !fio->runs || !fio->cursor)) return fail(AIM_EINVAL, "plan emits the compact CIGAR but no buffers were given");
-    const bool reads_ascii = !(pl.main.kid == K_WFA_LANE_PK && !pl.pack_first);   // (wfa_group reads them for its to-do pairs even on packed batches)
-    const bool writes_res = !(pl.main.kid == K_WFA_LANE_PK && pl.emits_runs);
-    if (!d_req || (reads_ascii && (!d_pat || !d_txt)) || (writes_res && !d_res)) return fail(AIM_EINVAL, "null device buffer");
-    if (bt && writes_res && !d_ops) return fail(AIM_EINVAL, "AIM_FLAG_BACKTRACE needs an ops buffer");
-    if (scratch_bytes < pl.scratch_total || (!d_scratch && pl.scratch_total))
-        return fail(AIM_EINVAL, "scratch too small: need %zu bytes, got %zu", pl.scratch_total, scratch_bytes);
-    aim::KArgs ka0;
-    ka0.p = p;
-    ka0.n_pairs = n_pairs;
-    ka0.req = static_cast<const aim_request_t *>(d_req);
-    ka0.patterns = d_pat;
-    ka0.texts = d_txt;
-    ka0.res = static_cast<aim_result_t *>(d_res);
-    ka0.ops = d_ops;
-    ka0.todo = nullptr;
-    ka0.dbg_poison_lds = poison_lds_word(kn);
-    ka0.dbg_flags = (uint32_t)kn.dbg_flags;
-    ka0.packedP = fio ? fio->packedP : nullptr;
-    ka0.packedT = fio ? fio->packedT : nullptr;
-    ka0.cig = fio ? fio->cig : nullptr;
-    ka0.runs = fio ? fio->runs : nullptr;
-    ka0.runs_cap = fio ? fio->runs_cap : 0u;
-    ka0.cursor = fio ? fio->cursor : nullptr;
-    ka0.pair_base = 0;
-    {
-        const EndsFree e = ends_free(p);
-        ka0.ef_pb = e.pb; ka0.ef_pe = e.pe; ka0.ef_tb = e.tb; ka0.ef_te = e.te;
-        const Affine2p g = affine2p(p);
-        ka0.a2p_o2 = g.o2; ka0.a2p_e2 = g.e2;
-    }
-    const Stage &m = pl.main;
-    aim::KArgs ka = stage_args(ka0, m, d_scratch);
-    // the fallback over the to-do list the main kernel filled: its own stage, the batch's ASCII rows
-    aim::KArgs kb = stage_args(ka0, pl.fb, d_scratch);
-    kb.todo = reinterpret_cast<const uint32_t *>((char *)d_scratch + pl.todo_at);
-    kb.packedP = kb.packedT = nullptr;
-    kb.cig = nullptr;
-    if (kn.poison_ops >= 0 && d_ops && bt && !list_in)   // (the second stage keeps the first stage's rows) debugging aid: results must not depend on what the ops rows held before (only ops[begin_offset, end_offset) is written)
-        HIP_TRY(hipMemsetAsync(d_ops, kn.poison_ops & 0xff, (size_t)n_pairs * 2 * p.read_size, stream));
-    if (pl.todo_bytes) HIP_TRY(hipMemsetAsync((char *)d_scratch + pl.todo_at, 0, 64, stream));   // the to-do count, zeroed per launch
-    switch (m.kid) {
-    case K_WFA_WAVE:
-    case K_DP_LANE:
-    case K_DP_STRIP:
-        if (list_in) ka.todo = list_in;
-        launch_stage(p, m, ka, stream);
-        break;
-    case K_WFA_LANE:
-        aim::wfa_lane_launch(p, m.grid, m.block, m.lds, ka, stream);
-        break;
-    case K_WFA_LANE_PK:
-        if (pl.pack_first) {
-            // pack_rows_kernel lists the non-ACGT pairs; the packed kernel aligns the batch, wfa_wave re-aligns the listed pairs
-            char *base = (char *)d_scratch;
-            uint32_t *flags_d = reinterpret_cast<uint32_t *>(base + pl.flags_at);
-            uint32_t *pkP = reinterpret_cast<uint32_t *>(base + pl.pack_p_at), *pkT = reinterpret_cast<uint32_t *>(base + pl.pack_t_at);
-            HIP_TRY(hipMemsetAsync(flags_d, 0, pl.pack_p_at - pl.flags_at, stream));
-            aim::pack_rows_launch(ka, pkP, pkT, flags_d, reinterpret_cast<uint32_t *>(base + pl.todo_at), stream);
-            HIP_TRY(hipGetLastError());
-            aim::KArgs kp = ka;
-            kp.packedP = pkP;
-            kp.packedT = pkT;
-            aim::wfa_lane_packed_launch(p, m.grid, m.lds, kp, 0u, stream);
-            HIP_TRY(hipGetLastError());
-            launch_stage(p, pl.fb, kb, stream);
-            break;
-        }
-        aim::wfa_lane_packed_launch(p, m.grid, m.lds, ka, fio->run_slot, stream);
-        break;
-    case K_WFA_GROUP: {
-        // fast kernel (+ traceback kernel with BACKTRACE) chunk by chunk; then the general kernel drains the to-do list
-        const uint32_t chunk = (bt && pl.chunk_pairs) ? pl.chunk_pairs : n_pairs;
-        const size_t rqb = req_size(p), rsb = res_size(p);
-        const size_t npw = aim::packed_row_dwords(p.read_size);
-        const uint32_t nchunks = (n_pairs + chunk - 1) / chunk;
-        const bool overlap = bt && nchunks > 1;
-        const size_t buf_bytes = overlap ? pl.hist_bytes / 2 : 0;     // two alternating buffers of history regions
-        AuxStream *aux = slot_aux;
-        std::unique_lock<std::mutex> shared_lock;   // stateless callers: the device's shared instance, locked until the last wait is enqueued
-        if (overlap && !aux) {
-            SharedAux *sh = shared_aux_for_current_device();
-            if (!sh) return fail(AIM_ENODEV, "no current HIP device");
-            shared_lock = std::unique_lock<std::mutex>(sh->mu);
-            aux = &sh->aux;
-        }
-        if (overlap) {
-            int arc = aux_stream_create(*aux);
-            if (arc) return arc;
-        }
-        uint32_t ci = 0;
-        for (uint32_t first = 0; first < n_pairs; first += chunk, ++ci) {
-            aim::KArgs kc = ka;
-            const int b = (int)(ci & 1u);
-            kc.n_pairs = std::min(chunk, n_pairs - first);
-            kc.pair_base = first;
-            kc.scratch_per_wave = pl.hist_at + (overlap ? (size_t)b * buf_bytes : 0);   // where this chunk's history regions start (the to-do region is in front)
-            if (list_in) {   // positions [first, first + chunk) of the list; the arrays stay the batch's (indexed by the listed pair ids)
-                kc.todo = list_in;
-            } else {
-                kc.req = reinterpret_cast<const aim_request_t *>(static_cast<const char *>(d_req) + (size_t)first * rqb);
-                if (d_pat) { kc.patterns = d_pat + (size_t)first * p.read_size; kc.texts = d_txt + (size_t)first * p.read_size; }
-                if (d_res) kc.res = reinterpret_cast<aim_result_t *>(static_cast<char *>(d_res) + (size_t)first * rsb);
-                if (d_ops) kc.ops = d_ops + (size_t)first * 2 * p.read_size;
-                if (ka.packedP) { kc.packedP = ka.packedP + (size_t)first * npw; kc.packedT = ka.packedT + (size_t)first * npw; }
-                if (ka.cig) kc.cig = ka.cig + first;
-            }
-            // a chunk smaller than the plan's grid needs fewer workgroups (the grid stays a multiple of 8)
-            uint32_t grid = m.grid;
-            {
-                const uint32_t ppw = 64u / (uint32_t)pl.group_g;
-                const uint32_t need = ((((kc.n_pairs + ppw - 1) / ppw) + 7u) / 8u) * 8u;
-                if (grid > need) grid = need < 8u ? 8u : need;
-            }
-            if (overlap && ci >= 2) HIP_TRY(hipStreamWaitEvent(stream, aux->walked[b], 0));   // buffer b: its previous chunk has been walked
-            auto tb_launch = [&](hipStream_t ts) {
-                if (list_in) aim::wfa_group_tb_todo_launch(pl.gcfg, kc.n_pairs, kc, ts);
-                else aim::wfa_group_tb_launch(p, pl.gcfg, kc.n_pairs, kc, ts);
-            };
-            if (list_in) aim::wfa_group_todo_launch(p, pl.group_g, pl.gcfg, grid, m.lds, kc, stream);
-            else aim::wfa_group_launch(p, pl.group_g, pl.gcfg, grid, m.lds, kc, stream);
-            HIP_TRY(hipGetLastError());
-            if (overlap) {
-                HIP_TRY(hipEventRecord(aux->computed[b], stream));
-                HIP_TRY(hipStreamWaitEvent(aux->stream, aux->computed[b], 0));
-                tb_launch(aux->stream);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(aux->walked[b], aux->stream));
-            } else if (bt) {
-                tb_launch(stream);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        if (overlap) {   // the caller's stream continues only after both buffers' tracebacks
-            HIP_TRY(hipStreamWaitEvent(stream, aux->walked[0], 0));
-            HIP_TRY(hipStreamWaitEvent(stream, aux->walked[1], 0));
-        }
-        if (pl.pk) {   // the general kernel reads ASCII rows: expand the to-do pairs' packed rows in place first
-            aim::unpack_todo_rows_launch(ka, kb.todo, ka.packedP, ka.packedT, const_cast<char *>(d_pat), const_cast<char *>(d_txt), stream);
-            HIP_TRY(hipGetLastError());
-        }
-        launch_stage(p, pl.fb, kb, stream);
-        if (pl.emits_runs) {   // the general kernel wrote result_t + ops rows for the to-do pairs: their compact CIGAR
-            aim::cigar_rle_todo_launch(kb, kb.todo, ka.cig, ka.runs, ka.runs_cap, ka.cursor, stream);
-            HIP_TRY(hipGetLastError());
-        }
-        break;
-    }
-    case K_DP_REG:
-    case K_DP_GROUP:
-        // the register / group kernel lists the pairs it leaves; then the literal-capable kernel over them
-        ka.todo = kb.todo;
-        if (m.kid == K_DP_GROUP) aim::dp_group_launch(p, m.grid, m.lds, ka, stream);
-        else if (p.algo == AIM_ALGO_SWG) aim::swg_reg_launch(p, m.grid, m.lds, ka, stream);
-        else aim::nw_reg_launch(p, m.grid, m.lds, ka, stream);
-        HIP_TRY(hipGetLastError());
-        launch_stage(p, pl.fb, kb, stream);
-        break;
-    case K_DP_WAVE:
-        aim::dp_wave_launch(p, p.algo == AIM_ALGO_SWG && aim::swg_cell_bytes(p) == 1, m.grid, m.block, m.lds, ka, stream);
-        break;
-    case K_GENASM:
-        aim::genasm_launch(p, m.grid, m.lds, ka, stream);
-        break;
-    case K_WFA_BIDIR: {
-        // wfa_wave at MAX_SCORE min(MAX_SCORE, T) over the whole batch, then the bidirectional kernel over the pairs it left over T
-        aim_params_t p1 = p;
-        p1.flags &= ~AIM_FLAG_WFA_BIDIR;
-        p1.max_score = std::min(p.max_score, pl.bidir_t);
-        aim::KArgs k1 = stage_args(ka0, pl.fb, d_scratch);
-        k1.p = p1;
-        launch_stage(p1, pl.fb, k1, stream);
-        HIP_TRY(hipGetLastError());
-        if (p.max_score > pl.bidir_t) aim::wfa_bidir_launch(m.grid, m.lds, ka, stream);
-        break;
-    }
-    }
-    HIP_TRY(hipGetLastError());
+    if (io.results) HIP_TRY(hipMemcpyAsync(io.results, s.d_res, (size_t)rows * res_size(p), hipMemcpyDeviceToHost, s.stream));
+    if (io.ops) HIP_TRY(hipMemcpyAsync(io.ops, s.d_ops, (size_t)rows * 2 * (size_t)p.read_size, hipMemcpyDeviceToHost, s.stream));
     return AIM_OK;
 }
 
-// Enqueue the launches of plan `pl`. AIM_FLAG_WFA_ESCALATE with two stages: the lane plan at cap esc_c over the batch, the list of the
-// pairs it left at esc_c + 1 (ascending pair order), the full-cap plan over that list -- one stream, no host round trip.
-}  // namespace
+namespace {
 
-int aim::capi::launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t n_pairs, const void *d_req,
-                      const char *d_pat, const char *d_txt, void *d_res, char *d_ops, void *d_scratch, size_t scratch_bytes,
-                      hipStream_t stream, const FusedIo *fio, AuxStream *slot_aux)
+// A slot's allocations: made into a typed member and recorded in one of the slot's lists, which is all that releasing them reads
+template <typename T>
+hipError_t slot_alloc(std::vector<void *> &list, T *&member, size_t bytes)
 {
-    // (without the flag p may be the base of an extension struct, which launch_one reads through its address: no copy of it here)
-    if (!pl.esc) return launch_one(pl, kn, p, n_pairs, d_req, d_pat, d_txt, d_res, d_ops, d_scratch, scratch_bytes, stream, fio, slot_aux);
-    if (!pl.esc_c || n_pairs == 0) {
-        aim_params_t q = p;
-        q.flags &= ~AIM_FLAG_WFA_ESCALATE;
-        return launch_one(pl, kn, q, n_pairs, d_req, d_pat, d_txt, d_res, d_ops, d_scratch, scratch_bytes, stream, fio, slot_aux);
-    }
-    if (scratch_bytes < pl.scratch_total || !d_scratch) return fail(AIM_EINVAL, "scratch too small: need %zu bytes, got %zu", pl.scratch_total, scratch_bytes);
-    if (!d_res) return fail(AIM_EINVAL, "null device buffer");
-    aim_params_t q = p, p1 = p;
-    q.flags &= ~AIM_FLAG_WFA_ESCALATE;
-    p1.flags = q.flags;
-    p1.max_score = pl.esc_c;
-    char *base = static_cast<char *>(d_scratch);
-    StagePlan s1 = pl;
-    s1.scratch_total = pl.s1_scratch;
-    int rc = launch_one(s1, kn, p1, n_pairs, d_req, d_pat, d_txt, d_res, d_ops, base, pl.s2_at, stream, fio, slot_aux);
-    if (rc) return rc;
-    uint32_t *list = reinterpret_cast<uint32_t *>(base + pl.list_at);
-    uint2 *masks = reinterpret_cast<uint2 *>(base + pl.mask_at);
-    uint32_t *counts = reinterpret_cast<uint32_t *>(base + pl.count_at);
-    const bool res8 = p.flags & AIM_FLAG_RES8;
-    aim::escalate_list_launch(static_cast<const uint32_t *>(d_res), n_pairs, res8 ? 2u : 6u, res8 ? 1u : 3u, (int32_t)(pl.esc_c + 1), masks, counts, list,
-                              stream);
-    HIP_TRY(hipGetLastError());
-    if (pl.pk && !pl.s2.pk) {   // a packed batch whose second stage reads ASCII rows: the listed pairs' rows, expanded in place
-        if (!d_pat || !d_txt || !fio || !fio->packedP || !fio->packedT) return fail(AIM_EINVAL, "null device buffer");
-        aim::unpack_todo_rows_launch(batch_args(q, n_pairs, d_req), list, fio->packedP, fio->packedT, const_cast<char *>(d_pat), const_cast<char *>(d_txt),
-                                     stream);
-        HIP_TRY(hipGetLastError());
-    }
-    return launch_one(pl.s2, kn, q, n_pairs, d_req, d_pat, d_txt, d_res, d_ops, base + pl.s2_at, pl.s2.scratch_total, stream, fio, slot_aux, list);
+    void *b = nullptr;
+    const hipError_t e = hipMalloc(&b, bytes);
+    if (e == hipSuccess) list.push_back(member = static_cast<T *>(b));
+    return e;
+}
+// ... and the two pinned ones
+hipError_t slot_alloc_pinned(aim_slot &s, uint32_t *&member, size_t bytes)
+{
+    const hipError_t e = hipHostMalloc((void **)&member, bytes, hipHostMallocDefault);
+    if (e == hipSuccess) s.pinned.push_back(member);
+    return e;
 }
 
-namespace {
+// The SAM buffers (aim_set_sam_capacity re-allocates them on a live slot). d_sam is what says that a slot has them.
+void free_sam_buffers(aim_slot &s)
+{
+    for (void *b : s.owned_sam) (void)hipFree(b);
+    s.owned_sam.clear();
+    s.d_sam = nullptr;
+    s.samcig_cap = s.sammd_cap = 0;
+}
 
 void free_slot(aim_slot &s)
 {
-    void *bufs[] = {s.d_req, s.d_pat, s.d_txt, s.d_ops, s.d_res, s.d_scratch, s.d_packP, s.d_packT, s.d_rawidx, s.d_rawP, s.d_rawT,
-                    s.d_cig, s.d_runs, s.d_cursor, s.d_rawreq, s.d_rawres, s.d_rawops, s.d_rawcig, s.d_tpos, s.d_reftodo,
-                    s.g_readP, s.g_roff, s.g_map, s.g_sel, s.g_rawslot, s.g_res1, s.g_best, s.g_mates, s.g_hoff, s.g_hit, s.g_req2, s.g_pat2, s.g_txt2,
-                    s.d_sam, s.d_samcig, s.d_samcur, s.d_sammd};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    if (s.h_cursor) (void)hipHostFree(s.h_cursor);
-    if (s.h_samcur) (void)hipHostFree(s.h_samcur);
+    free_sam_buffers(s);
+    for (void *b : s.owned) (void)hipFree(b);
+    for (void *b : s.pinned) (void)hipHostFree(b);
     for (auto &e : s.ev)
         if (e) (void)hipEventDestroy(e);
     if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -397,43 +142,19 @@ bool any_nonzero(size_t n, F f)
 
 // Every length of a batch against READ_SIZE (host.c:119-123) before anything is enqueued. A 4 M-pair batch is 32-64 MB of
 // requests: scanned by one thread this was 2.5 ms of every aim_set_submit -- a fifth of the host CLI's loop at 4e8 pairs/s -- so
-// large batches are scanned branch-free by a few threads and only a failing scan is repeated to name the pair.
-int aim::capi::check_lengths(const aim_params_t &p, uint32_t n_pairs, const void *requests)
+// large batches are scanned branch-free by a few threads (any_nonzero) and only a failing scan is repeated to name the pair.
+int aim::capi::check_lengths(const aim_params_t &p, uint32_t n_pairs, const void *requests, uint32_t *bad_pair)
 {
-    const int rs = p.read_size;
-    const bool req8 = p.flags & AIM_FLAG_REQ8;
-    auto bad_in = [&](size_t lo, size_t hi) -> uint32_t {
-        uint32_t bad = 0;
-        if (req8) {
-            const aim_request8_t *r = static_cast<const aim_request8_t *>(requests);
-            for (size_t i = lo; i < hi; ++i) bad |= (uint32_t)((r[i].pattern_len < 0) | (r[i].text_len < 0) | (r[i].pattern_len > rs) | (r[i].text_len > rs));
-        } else {
-            const aim_request_t *r = static_cast<const aim_request_t *>(requests);
-            for (size_t i = lo; i < hi; ++i) bad |= (uint32_t)((r[i].pattern_len < 0) | (r[i].text_len < 0) | (r[i].pattern_len > rs) | (r[i].text_len > rs));
-        }
-        return bad;
+    auto scan = [&](auto *r) -> int {   // (r: the requests in their own type, aim_request_t or aim_request8_t)
+        const int rs = p.read_size;
+        auto bad = [r, rs](size_t i) { return (uint32_t)((r[i].pattern_len < 0) | (r[i].text_len < 0) | (r[i].pattern_len > rs) | (r[i].text_len > rs)); };
+        if (!any_nonzero(n_pairs, bad)) return AIM_OK;
+        uint32_t i = 0;
+        while (!bad(i)) ++i;
+        if (bad_pair) *bad_pair = i;
+        return fail(AIM_EINVAL, "READ LENGTH less than length of the input reads (pair %u)", i);  // host.c:119-123
     };
-    uint32_t bad = 0;
-    const unsigned nt = n_pairs >= (1u << 19) ? 8u : 1u;
-    if (nt == 1) bad = bad_in(0, n_pairs);
-    else {
-        uint32_t part[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < nt; ++t) th.emplace_back([&, t] { part[t] = bad_in((size_t)n_pairs * t / nt, (size_t)n_pairs * (t + 1) / nt); });
-        part[0] = bad_in(0, (size_t)n_pairs / nt);
-        for (auto &x : th) x.join();
-        for (unsigned t = 0; t < nt; ++t) bad |= part[t];
-    }
-    if (!bad) return AIM_OK;
-    for (uint32_t i = 0; i < n_pairs; ++i) {
-        const int pl = req8 ? static_cast<const aim_request8_t *>(requests)[i].pattern_len
-                            : static_cast<const aim_request_t *>(requests)[i].pattern_len;
-        const int tl = req8 ? static_cast<const aim_request8_t *>(requests)[i].text_len
-                            : static_cast<const aim_request_t *>(requests)[i].text_len;
-        if (pl < 0 || tl < 0 || pl > rs || tl > rs)
-            return fail(AIM_EINVAL, "READ LENGTH less than length of the input reads (pair %u)", i);  // host.c:119-123
-    }
-    return AIM_OK;
+    return (p.flags & AIM_FLAG_REQ8) ? scan(static_cast<const aim_request8_t *>(requests)) : scan(static_cast<const aim_request_t *>(requests));
 }
 
 // AIM_FLAG_REF_TEXTS: every window [pos, pos + text_len) inside [0, ref_len) (bit 63 is the strand; an empty window is always
@@ -491,6 +212,15 @@ Plan plan_for_batch(aim_set *set, aim_device_ctx &d, aim_slot &s, uint32_t n_pai
     return pl;
 }
 
+// The slot's batch as a launch takes it: n_pairs pairs in the slot's own buffers
+LaunchIo slot_launch_io(const aim_slot &s)
+{
+    LaunchIo io;
+    io.n_pairs = s.n_pairs; io.req = s.d_req; io.pat = s.d_pat; io.txt = s.d_txt;
+    io.res = s.d_res; io.ops = s.d_ops; io.scratch = s.d_scratch; io.scratch_bytes = s.scratch_bytes;
+    return io;
+}
+
 int launch_on_slot(aim_set *set, aim_device_ctx &d, aim_slot &s, uint32_t mode = 0u, FusedIo *fio = nullptr)
 {
     const Plan pl = plan_for_batch(set, d, s, s.n_pairs, mode);
@@ -499,8 +229,7 @@ int launch_on_slot(aim_set *set, aim_device_ctx &d, aim_slot &s, uint32_t mode =
         fio->run_slot = (pl.main.kid == K_WFA_LANE_PK && (uint64_t)s.n_pairs * aim::kRunSlot <= fio->runs_cap) ? aim::kRunSlot : 0u;
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)fio->cursor, (int)(s.n_pairs * fio->run_slot), 1, s.stream));
     }
-    return launch(pl, set->knobs, set->params, s.n_pairs, s.d_req, s.d_pat, s.d_txt, s.d_res, s.d_ops, s.d_scratch,
-                  s.scratch_bytes, s.stream, fio, &s.aux);
+    return launch(pl, set->knobs, set->params, slot_launch_io(s), s.stream, fio, &s.aux);
 }
 
 // aim_sam_t's offsets are 32-bit. CIGAR words <= op bytes and MD bytes <= 2 per op + the digits of one final count, so both cursors stay
@@ -583,6 +312,200 @@ int aim::capi::enqueue_sam_d2h(aim_slot &s, uint32_t n_rows)
 }
 
 
+namespace {
+
+// What the steps of one aim_set_submit share: the batch as check_submit_io read it, then what choose_plan decided for it
+struct Batch {
+    uint32_t n = 0;
+    bool ref = false, packed = false;             // AIM_FLAG_REF_TEXTS; packed rows in
+    const uint64_t *text_pos = nullptr;           // ref: io is the base of an aim_batch_io_ref_t and the texts are windows of the device's reference
+    const aim_batch_io_sam_t *sio = nullptr;      // AIM_FLAG_SAM_FIELDS: io is the base of one
+    uint32_t mode = 0;
+    Plan pl;
+    uint32_t runs_cap = 0;
+    bool ref_fused = false;                       // a packed REF_TEXTS batch that keeps the fused packed lane kernel ...
+    Stage ref_fb;                                 // ... and the general kernel's stage over its to-do windows
+};
+
+// Every refusal of a batch, before anything is enqueued
+int check_submit_io(const aim_set *set, const aim_device_ctx &d, const aim_slot &s, const aim_batch_io_t *io, Batch *b)
+{
+    const aim_params_t &p = set->params;
+    const uint32_t n = b->n = io->n_pairs;
+    const bool bt = p.flags & AIM_FLAG_BACKTRACE;
+    const bool ref = b->ref = is_ref(p);
+    const uint64_t *text_pos = b->text_pos = ref ? reinterpret_cast<const aim_batch_io_ref_t *>(io)->text_pos : nullptr;
+    if (ref && (io->texts || io->packed_texts || io->raw_texts))
+        return fail(AIM_EINVAL, "AIM_FLAG_REF_TEXTS: texts, packed_texts and raw_texts must be NULL (the texts are named by text_pos)");
+    if (ref && n && !text_pos) return fail(AIM_EINVAL, "AIM_FLAG_REF_TEXTS: null text_pos");
+    if (ref && !d.d_ref) return fail(AIM_ESTATE, "AIM_FLAG_REF_TEXTS: no reference on device %d (aim_set_reference)", d.dev);
+    const bool packed = b->packed = io->packed_patterns || io->packed_texts;
+    if (n > set->max_pairs) return fail(AIM_EINVAL, "n_pairs %u exceeds configured capacity %u", n, set->max_pairs);
+    if (n && !io->requests) return fail(AIM_EINVAL, "null requests");
+    if (n && packed && (!io->packed_patterns || (!ref && !io->packed_texts) || !s.d_packP))
+        return fail(AIM_EINVAL, "packed batch needs both packed arrays and a set configured with max_raw_pairs > 0");
+    if (n && !packed && (!io->patterns || (!ref && !io->texts))) return fail(AIM_EINVAL, "null sequence rows");
+    if (packed && io->n_raw > set->max_raw) return fail(AIM_EINVAL, "n_raw %u exceeds configured capacity %u", io->n_raw, set->max_raw);
+    if (packed && io->n_raw && (!io->raw_pairs || !io->raw_patterns || (!ref && !io->raw_texts))) return fail(AIM_EINVAL, "null raw side list");
+    if (io->cigars && (!bt || !s.d_cig || !io->runs)) return fail(AIM_EINVAL, "compact CIGAR needs AIM_FLAG_BACKTRACE, max_runs > 0 and a run buffer");
+    if (int rc = check_sam_io(set, s, io, &b->sio)) return rc;
+    if (n && !io->results && !io->cigars && !b->sio) return fail(AIM_EINVAL, "no output buffer");
+    if (io->ops && !bt) return fail(AIM_EINVAL, "ops requested without AIM_FLAG_BACKTRACE");
+    if (int rc = check_lengths(p, n, io->requests)) return rc;
+    if (ref)
+        if (int rc = check_windows(p, n, io->requests, text_pos, d.ref_len, nullptr)) return rc;
+    if (packed)
+        for (uint32_t j = 0; j < io->n_raw; ++j)
+            if (io->raw_pairs[j] >= n) return fail(AIM_EINVAL, "raw_pairs[%u] = %u is outside the batch", j, io->raw_pairs[j]);
+    return AIM_OK;
+}
+
+// Does the alignment kernel of this configuration take the batch as it arrived and deliver what was asked for?
+// (wfa_lane_packed_kernel: packed rows in, {idx, score} or compact CIGAR out.) Then this batch is ONE kernel;
+// otherwise the conversion kernels of batch_io.hpp run around the default-ABI kernel.
+void choose_plan(aim_set *set, aim_device_ctx &d, aim_slot &s, Batch &b)
+{
+    const aim_batch_io_t &io = s.io;
+    b.runs_cap = std::min(io.runs_cap, set->max_runs);
+    b.mode = (b.packed ? MODE_PACKED_IN : 0u) | ((io.cigars && !io.results && !io.ops && !b.sio) ? MODE_RUNS_OUT : 0u);   // (the SAM kernel reads ops rows)
+    b.pl = plan_for_batch(set, d, s, b.n, b.mode);
+    // AIM_FLAG_REF_TEXTS: a packed batch keeps the fused packed lane kernel (its texts gathered as packed rows, the windows
+    // holding a byte outside A/C/G/T re-aligned by the general kernel over a to-do list); every other plan runs as for an
+    // ASCII batch after the gather
+    b.ref_fused = b.ref && b.packed && b.pl.pk && b.pl.main.kid == K_WFA_LANE_PK && !b.pl.pack_first && s.d_reftodo && !b.pl.esc_c &&
+                  ref_todo_stage(set, d, s.scratch_bytes, b.n, &b.ref_fb);
+    if (b.ref && b.packed && !b.ref_fused && b.pl.pk) {
+        b.mode &= ~MODE_PACKED_IN;
+        b.pl = plan_for_batch(set, d, s, b.n, b.mode);
+    }
+}
+
+// The KArgs of the batch-I/O kernels around the slot's alignment: the batch's requests and its result and ops rows
+aim::KArgs slot_args(const aim_params_t &p, const aim_slot &s)
+{
+    aim::KArgs ka = batch_args(p, s.n_pairs, s.d_req);
+    ka.res = static_cast<aim_result_t *>(s.d_res);
+    ka.ops = s.d_ops;
+    return ka;
+}
+
+// The H2D copies of a batch
+int enqueue_inputs(const aim_params_t &p, aim_slot &s, const Batch &b)
+{
+    const aim_batch_io_t &io = s.io;
+    const size_t n = b.n, rs = (size_t)p.read_size, rowb = (size_t)aim::packed_row_dwords(p.read_size) * 4;
+    HIP_TRY(hipMemcpyAsync(s.d_req, io.requests, n * req_size(p), hipMemcpyHostToDevice, s.stream));
+    if (b.ref) HIP_TRY(hipMemcpyAsync(s.d_tpos, b.text_pos, n * 8, hipMemcpyHostToDevice, s.stream));
+    if (!b.packed) {
+        HIP_TRY(hipMemcpyAsync(s.d_pat, io.patterns, n * rs, hipMemcpyHostToDevice, s.stream));
+        if (!b.ref) HIP_TRY(hipMemcpyAsync(s.d_txt, io.texts, n * rs, hipMemcpyHostToDevice, s.stream));
+        return AIM_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(s.d_packP, io.packed_patterns, n * rowb, hipMemcpyHostToDevice, s.stream));
+    if (!b.ref) HIP_TRY(hipMemcpyAsync(s.d_packT, io.packed_texts, n * rowb, hipMemcpyHostToDevice, s.stream));
+    if (io.n_raw) {
+        HIP_TRY(hipMemcpyAsync(s.d_rawidx, io.raw_pairs, (size_t)io.n_raw * 4, hipMemcpyHostToDevice, s.stream));
+        HIP_TRY(hipMemcpyAsync(s.d_rawP, io.raw_patterns, (size_t)io.n_raw * rs, hipMemcpyHostToDevice, s.stream));
+        if (!b.ref) HIP_TRY(hipMemcpyAsync(s.d_rawT, io.raw_texts, (size_t)io.n_raw * rs, hipMemcpyHostToDevice, s.stream));
+    }
+    return AIM_OK;
+}
+
+// The rows as the plan's kernel reads them: packed rows expanded where it reads ASCII, REF_TEXTS windows gathered
+int enqueue_text_rows(const aim_set *set, const aim_device_ctx &d, aim_slot &s, const Batch &b)
+{
+    const aim_batch_io_t &io = s.io;
+    const aim::KArgs ka = slot_args(set->params, s);
+    if (b.packed && !b.pl.pk) {   // expand into the reference's char[n][READ_SIZE] layout (batch_io.hpp), then run as usual
+        const unsigned rows = b.ref ? 1u : 2u;   // (grid.y 0: patterns; the texts of a reference batch are gathered below)
+        aim::unpack_rows_launch(ka, s.d_packP, s.d_packT, s.d_pat, s.d_txt, rows, s.stream);
+        if (io.n_raw) aim::scatter_raw_rows_launch(set->params.read_size, io.n_raw, s.d_rawidx, s.d_rawP, s.d_rawT, s.d_pat, s.d_txt, rows, s.stream);
+        HIP_TRY(hipGetLastError());
+    }
+    if (b.ref_fused) {
+        // packed text rows + to-do list; the side list's (non-ACGT patterns) text rows as ASCII for the raw side pass
+        uint32_t *flag_bits = s.d_reftodo + 16 + set->max_pairs;
+        HIP_TRY(hipMemsetAsync(s.d_reftodo, 0, 64, s.stream));
+        HIP_TRY(hipMemsetAsync(flag_bits, 0, ((size_t)b.n + 31) / 32 * 4, s.stream));
+        aim::gather_text_packed_launch(ka, s.d_tpos, d.d_ref, d.ref_len, s.d_packT, flag_bits, s.d_reftodo, s.stream);
+        HIP_TRY(hipGetLastError());
+        if (io.n_raw) {
+            aim::gather_text_rows_launch(ka, s.d_tpos, d.d_ref, d.ref_len, s.d_rawidx, io.n_raw, s.d_rawT, s.stream);
+            HIP_TRY(hipGetLastError());
+        }
+    } else if (b.ref) {
+        aim::gather_text_rows_launch(ka, s.d_tpos, d.d_ref, d.ref_len, nullptr, b.n, s.d_txt, s.stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return AIM_OK;
+}
+
+// The plan's launches over the slot's batch, then what completes its rows: the to-do windows of a fused REF_TEXTS batch, and the
+// compact CIGAR as a pass of its own when the plan's kernel does not emit runs
+int enqueue_alignment(aim_set *set, aim_device_ctx &d, aim_slot &s, const Batch &b)
+{
+    const aim_params_t &p = set->params;
+    const aim::KArgs ka = slot_args(p, s);
+    FusedIo fio;
+    if (b.pl.pk) { fio.packedP = s.d_packP; fio.packedT = s.d_packT; }
+    if (b.pl.emits_runs) { fio.cig = s.d_cig; fio.runs = s.d_runs; fio.cursor = s.d_cursor; fio.runs_cap = b.runs_cap; }
+    if (int rc = launch_on_slot(set, d, s, b.mode, &fio)) return rc;
+    if (b.ref_fused) {
+        // the to-do windows: ASCII rows (pattern unpacked, text gathered), the general kernel over them, their compact CIGAR
+        aim::gather_todo_rows_launch(ka, s.d_reftodo, s.d_tpos, d.d_ref, d.ref_len, s.d_packP, s.d_pat, s.d_txt, s.stream);
+        HIP_TRY(hipGetLastError());
+        if (int rc = launch_todo_stage(p, b.ref_fb, slot_launch_io(s), s.d_reftodo, s.stream)) return rc;
+        if (b.pl.emits_runs) {
+            aim::cigar_rle_todo_launch(ka, s.d_reftodo, s.d_cig, s.d_runs, b.runs_cap, s.d_cursor, s.stream);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    s.runs_sent = b.pl.emits_runs ? b.n * fio.run_slot : 0u;   // 0 when the run buffer is bump-allocated: nothing is known before the kernel ran
+    if (s.io.cigars && !b.pl.emits_runs) {
+        HIP_TRY(hipMemsetAsync(s.d_cursor, 0, 4, s.stream));
+        aim::cigar_rle_launch(ka, s.d_cig, s.d_runs, b.runs_cap, s.d_cursor, s.stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return AIM_OK;
+}
+
+// Raw side pass: the pairs of the side list hold a byte outside A/C/G/T (the reference compares raw bytes,
+// host.c:126-127); what the packed kernel computed for them is void. They are aligned as a batch of their own by
+// the ASCII kernels -- requests gathered, the side list's rows are its patterns / texts -- and their results
+// replace the void ones (with the compact CIGAR: their runs are appended to the run buffer).
+int enqueue_raw_side_pass(aim_set *set, aim_device_ctx &d, aim_slot &s, const Batch &b)
+{
+    const aim_params_t &p = set->params;
+    const aim_batch_io_t &io = s.io;
+    const uint32_t nr = io.n_raw;
+    if (!b.pl.pk || !nr) return AIM_OK;
+    const uint32_t rq_dw = (uint32_t)req_size(p) / 4, rs_dw = (uint32_t)res_size(p) / 4;
+    aim::gather_elems_launch((const uint32_t *)s.d_req, s.d_rawidx, nr, rq_dw, (uint32_t *)s.d_rawreq, s.stream);
+    HIP_TRY(hipGetLastError());
+    LaunchIo raw;
+    raw.n_pairs = nr; raw.req = s.d_rawreq; raw.pat = s.d_rawP; raw.txt = s.d_rawT;
+    raw.res = s.d_rawres; raw.ops = s.d_rawops; raw.scratch = s.d_scratch; raw.scratch_bytes = s.scratch_bytes;
+    if (int rc = launch(plan_for_batch(set, d, s, nr, 0u), set->knobs, p, raw, s.stream, nullptr, &s.aux)) return rc;
+    // (both outputs may be asked for at once -- aim_cigar_t + runs AND result_t [+ ops rows]: each gets its own scatter)
+    if (io.cigars) {
+        aim::KArgs kr = slot_args(p, s);
+        kr.n_pairs = nr;
+        kr.res = static_cast<aim_result_t *>(s.d_rawres);
+        kr.ops = s.d_rawops;
+        aim::cigar_rle_launch(kr, s.d_rawcig, s.d_runs, b.runs_cap, s.d_cursor, s.stream);
+        aim::scatter_elems_launch((const uint32_t *)s.d_rawcig, s.d_rawidx, nr, 4u, (uint32_t *)s.d_cig, s.stream);
+    }
+    if (!io.cigars || io.results || io.ops || b.sio) {
+        aim::scatter_elems_launch((const uint32_t *)s.d_rawres, s.d_rawidx, nr, rs_dw, (uint32_t *)s.d_res, s.stream);
+        if (p.flags & AIM_FLAG_BACKTRACE)   // default output (result_t + ops rows): the side list's ops rows go home too
+            aim::scatter_elems_launch((const uint32_t *)s.d_rawops, s.d_rawidx, nr, (uint32_t)(2 * p.read_size / 4), (uint32_t *)s.d_ops, s.stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return AIM_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int aim_abi_version(void) { return AIM_ABI_VERSION; }
@@ -659,51 +582,51 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
         HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
         for (auto &e : s.ev) HIP_TRY(hipEventCreate(&e));
         // the MRAM plan of host.c:215-241, in HBM (+64 B tail slack on the sequence arrays)
-        HIP_TRY(hipMalloc(&s.d_req, (size_t)max_pairs * req_size(*params)));
-        HIP_TRY(hipMalloc(&s.d_res, (size_t)max_pairs * res_size(*params)));
-        HIP_TRY(hipMalloc((void **)&s.d_pat, (size_t)max_pairs * rs + 64));
-        HIP_TRY(hipMalloc((void **)&s.d_txt, (size_t)max_pairs * rs + 64));
-        if (params->flags & AIM_FLAG_BACKTRACE) HIP_TRY(hipMalloc((void **)&s.d_ops, (size_t)max_pairs * 2 * rs + 64));
+        HIP_TRY(slot_alloc(s.owned, s.d_req, (size_t)max_pairs * req_size(*params)));
+        HIP_TRY(slot_alloc(s.owned, s.d_res, (size_t)max_pairs * res_size(*params)));
+        HIP_TRY(slot_alloc(s.owned, s.d_pat, (size_t)max_pairs * rs + 64));
+        HIP_TRY(slot_alloc(s.owned, s.d_txt, (size_t)max_pairs * rs + 64));
+        if (params->flags & AIM_FLAG_BACKTRACE) HIP_TRY(slot_alloc(s.owned, s.d_ops, (size_t)max_pairs * 2 * rs + 64));
         if (max_raw) {
-            HIP_TRY(hipMalloc((void **)&s.d_packP, (size_t)max_pairs * rowdw * 4 + 64));
-            HIP_TRY(hipMalloc((void **)&s.d_packT, (size_t)max_pairs * rowdw * 4 + 64));
-            HIP_TRY(hipMalloc((void **)&s.d_rawidx, (size_t)max_raw * 4));
-            HIP_TRY(hipMalloc((void **)&s.d_rawP, (size_t)max_raw * rs + 64));   // (+64 B: the raw side pass hands them to the ASCII kernels as patterns / texts, aim_hip.h tail slack)
-            HIP_TRY(hipMalloc((void **)&s.d_rawT, (size_t)max_raw * rs + 64));
-            HIP_TRY(hipMalloc(&s.d_rawreq, (size_t)max_raw * req_size(*params)));
-            HIP_TRY(hipMalloc(&s.d_rawres, (size_t)max_raw * res_size(*params)));
-            if (params->flags & AIM_FLAG_BACKTRACE) HIP_TRY(hipMalloc((void **)&s.d_rawops, (size_t)max_raw * 2 * rs + 64));
-            if (max_runs) HIP_TRY(hipMalloc((void **)&s.d_rawcig, (size_t)max_raw * sizeof(aim_cigar_t)));
+            HIP_TRY(slot_alloc(s.owned, s.d_packP, (size_t)max_pairs * rowdw * 4 + 64));
+            HIP_TRY(slot_alloc(s.owned, s.d_packT, (size_t)max_pairs * rowdw * 4 + 64));
+            HIP_TRY(slot_alloc(s.owned, s.d_rawidx, (size_t)max_raw * 4));
+            HIP_TRY(slot_alloc(s.owned, s.d_rawP, (size_t)max_raw * rs + 64));   // (+64 B: the raw side pass hands them to the ASCII kernels as patterns / texts, aim_hip.h tail slack)
+            HIP_TRY(slot_alloc(s.owned, s.d_rawT, (size_t)max_raw * rs + 64));
+            HIP_TRY(slot_alloc(s.owned, s.d_rawreq, (size_t)max_raw * req_size(*params)));
+            HIP_TRY(slot_alloc(s.owned, s.d_rawres, (size_t)max_raw * res_size(*params)));
+            if (params->flags & AIM_FLAG_BACKTRACE) HIP_TRY(slot_alloc(s.owned, s.d_rawops, (size_t)max_raw * 2 * rs + 64));
+            if (max_runs) HIP_TRY(slot_alloc(s.owned, s.d_rawcig, (size_t)max_raw * sizeof(aim_cigar_t)));
         }
         if (is_ref(*params)) {
-            HIP_TRY(hipMalloc((void **)&s.d_tpos, (size_t)max_pairs * 8));
+            HIP_TRY(slot_alloc(s.owned, s.d_tpos, (size_t)max_pairs * 8));
             if (max_raw && params->algo == AIM_ALGO_WFA)
-                HIP_TRY(hipMalloc((void **)&s.d_reftodo, 64 + (size_t)max_pairs * 4 + ((size_t)max_pairs + 31) / 32 * 4));
+                HIP_TRY(slot_alloc(s.owned, s.d_reftodo, 64 + (size_t)max_pairs * 4 + ((size_t)max_pairs + 31) / 32 * 4));
         }
         if (is_groups(*params)) {
-            HIP_TRY(hipMalloc((void **)&s.g_readP, (size_t)max_pairs * rs + 64));
-            HIP_TRY(hipMalloc((void **)&s.g_roff, ((size_t)max_pairs + 1) * 4));
-            HIP_TRY(hipMalloc((void **)&s.g_map, (size_t)max_pairs * 4));
-            HIP_TRY(hipMalloc((void **)&s.g_sel, (size_t)max_pairs * 4));
-            if (max_raw) HIP_TRY(hipMalloc((void **)&s.g_rawslot, (size_t)max_pairs * 4));
-            HIP_TRY(hipMalloc((void **)&s.g_res1, (size_t)max_pairs * sizeof(aim_result_t)));
-            HIP_TRY(hipMalloc((void **)&s.g_best, (size_t)max_pairs * sizeof(aim_best_t)));
-            if (is_mates(*params)) HIP_TRY(hipMalloc((void **)&s.g_mates, ((size_t)max_pairs / 2 + 1) * sizeof(aim_mate_t)));
+            HIP_TRY(slot_alloc(s.owned, s.g_readP, (size_t)max_pairs * rs + 64));
+            HIP_TRY(slot_alloc(s.owned, s.g_roff, ((size_t)max_pairs + 1) * 4));
+            HIP_TRY(slot_alloc(s.owned, s.g_map, (size_t)max_pairs * 4));
+            HIP_TRY(slot_alloc(s.owned, s.g_sel, (size_t)max_pairs * 4));
+            if (max_raw) HIP_TRY(slot_alloc(s.owned, s.g_rawslot, (size_t)max_pairs * 4));
+            HIP_TRY(slot_alloc(s.owned, s.g_res1, (size_t)max_pairs * sizeof(aim_result_t)));
+            HIP_TRY(slot_alloc(s.owned, s.g_best, (size_t)max_pairs * sizeof(aim_best_t)));
+            if (is_mates(*params)) HIP_TRY(slot_alloc(s.owned, s.g_mates, ((size_t)max_pairs / 2 + 1) * sizeof(aim_mate_t)));
             if (is_hits(*params)) {
-                HIP_TRY(hipMalloc((void **)&s.g_hoff, ((size_t)max_pairs + 1) * 4));
-                HIP_TRY(hipMalloc((void **)&s.g_hit, (size_t)max_pairs * 4));
+                HIP_TRY(slot_alloc(s.owned, s.g_hoff, ((size_t)max_pairs + 1) * 4));
+                HIP_TRY(slot_alloc(s.owned, s.g_hit, (size_t)max_pairs * 4));
             }
             if (params->flags & AIM_FLAG_BACKTRACE) {
-                HIP_TRY(hipMalloc(&s.g_req2, (size_t)max_pairs * req_size(*params)));
-                HIP_TRY(hipMalloc((void **)&s.g_pat2, (size_t)max_pairs * rs + 64));
-                HIP_TRY(hipMalloc((void **)&s.g_txt2, (size_t)max_pairs * rs + 64));
+                HIP_TRY(slot_alloc(s.owned, s.g_req2, (size_t)max_pairs * req_size(*params)));
+                HIP_TRY(slot_alloc(s.owned, s.g_pat2, (size_t)max_pairs * rs + 64));
+                HIP_TRY(slot_alloc(s.owned, s.g_txt2, (size_t)max_pairs * rs + 64));
             }
         }
         if (max_runs) {
-            HIP_TRY(hipMalloc((void **)&s.d_cig, (size_t)max_pairs * sizeof(aim_cigar_t)));
-            HIP_TRY(hipMalloc((void **)&s.d_runs, (size_t)max_runs * 4));
-            HIP_TRY(hipMalloc((void **)&s.d_cursor, 64));
-            HIP_TRY(hipHostMalloc((void **)&s.h_cursor, 64, hipHostMallocDefault));
+            HIP_TRY(slot_alloc(s.owned, s.d_cig, (size_t)max_pairs * sizeof(aim_cigar_t)));
+            HIP_TRY(slot_alloc(s.owned, s.d_runs, (size_t)max_runs * 4));
+            HIP_TRY(slot_alloc(s.owned, s.d_cursor, 64));
+            HIP_TRY(slot_alloc_pinned(s, s.h_cursor, 64));
         }
         return AIM_OK;
     };
@@ -746,12 +669,12 @@ int aim_set_configure_slots(aim_set_t *set, const aim_params_t *params, uint32_t
             hipError_t e = hipSuccess;
             for (auto &s : d.slots) {
                 s.scratch_bytes = want;
-                if (want && (e = hipMalloc(&s.d_scratch, want)) != hipSuccess) break;
+                if (want && (e = slot_alloc(s.owned, s.d_scratch, want)) != hipSuccess) break;
             }
             if (e == hipSuccess) break;
             (void)hipGetLastError();
             for (auto &s : d.slots) {
-                if (s.d_scratch) (void)hipFree(s.d_scratch);
+                if (s.d_scratch) { (void)hipFree(s.d_scratch); s.owned.pop_back(); }   // (the scratch is the last the slot recorded)
                 s.d_scratch = nullptr;
             }
             if (e != hipErrorOutOfMemory || attempt >= 6 || d.budget <= ((uint64_t)1 << 28))
@@ -932,196 +855,33 @@ int aim_set_submit(aim_set_t *set, uint32_t device, uint32_t slot, const aim_bat
     aim_slot &s = d.slots[slot];
     if (s.submitted) return fail(AIM_ESTATE, "slot %u of device %d holds a batch: aim_set_wait it first", slot, d.dev);
     if (is_groups(set->params)) return submit_groups(set, d, s, io);
-    const aim_params_t &p = set->params;
-    const uint32_t n = io->n_pairs;
-    const bool bt = p.flags & AIM_FLAG_BACKTRACE;
-    // AIM_FLAG_REF_TEXTS: io is the base of an aim_batch_io_ref_t and the texts are windows of the device's reference
-    const bool ref = is_ref(p);
-    const uint64_t *text_pos = ref ? reinterpret_cast<const aim_batch_io_ref_t *>(io)->text_pos : nullptr;
-    if (ref && (io->texts || io->packed_texts || io->raw_texts))
-        return fail(AIM_EINVAL, "AIM_FLAG_REF_TEXTS: texts, packed_texts and raw_texts must be NULL (the texts are named by text_pos)");
-    if (ref && n && !text_pos) return fail(AIM_EINVAL, "AIM_FLAG_REF_TEXTS: null text_pos");
-    if (ref && !d.d_ref) return fail(AIM_ESTATE, "AIM_FLAG_REF_TEXTS: no reference on device %d (aim_set_reference)", d.dev);
-    const bool packed = io->packed_patterns || io->packed_texts;
-    if (n > set->max_pairs) return fail(AIM_EINVAL, "n_pairs %u exceeds configured capacity %u", n, set->max_pairs);
-    if (n && !io->requests) return fail(AIM_EINVAL, "null requests");
-    if (n && packed && (!io->packed_patterns || (!ref && !io->packed_texts) || !s.d_packP))
-        return fail(AIM_EINVAL, "packed batch needs both packed arrays and a set configured with max_raw_pairs > 0");
-    if (n && !packed && (!io->patterns || (!ref && !io->texts))) return fail(AIM_EINVAL, "null sequence rows");
-    if (packed && io->n_raw > set->max_raw) return fail(AIM_EINVAL, "n_raw %u exceeds configured capacity %u", io->n_raw, set->max_raw);
-    if (packed && io->n_raw && (!io->raw_pairs || !io->raw_patterns || (!ref && !io->raw_texts))) return fail(AIM_EINVAL, "null raw side list");
-    if (io->cigars && (!bt || !s.d_cig || !io->runs)) return fail(AIM_EINVAL, "compact CIGAR needs AIM_FLAG_BACKTRACE, max_runs > 0 and a run buffer");
-    const aim_batch_io_sam_t *sio = nullptr;
-    int rc = check_sam_io(set, s, io, &sio);
-    if (rc) return rc;
-    if (n && !io->results && !io->cigars && !sio) return fail(AIM_EINVAL, "no output buffer");
-    if (io->ops && !bt) return fail(AIM_EINVAL, "ops requested without AIM_FLAG_BACKTRACE");
-    rc = check_lengths(p, n, io->requests);
-    if (rc) return rc;
-    if (ref) {
-        rc = check_windows(p, n, io->requests, text_pos, d.ref_len, nullptr);
-        if (rc) return rc;
-    }
-    if (packed)
-        for (uint32_t j = 0; j < io->n_raw; ++j)
-            if (io->raw_pairs[j] >= n) return fail(AIM_EINVAL, "raw_pairs[%u] = %u is outside the batch", j, io->raw_pairs[j]);
-    const size_t rs = (size_t)p.read_size;
-    const size_t rowb = (size_t)aim::packed_row_dwords(p.read_size) * 4;
+    Batch b;
+    if (int rc = check_submit_io(set, d, s, io, &b)) return rc;
     HIP_TRY(hipSetDevice(d.dev));
-    s.io = *io;
-    s.n_pairs = n;
-    s.io_sam = nullptr;
-    s.runs_sent = 0;
-    s.pushed = s.launched = false;
-    s.ref_pending = false;
+    reset_slot(s, io);
+    s.n_pairs = b.n;
     // Everything below only enqueues work on the slot's stream. Should an enqueue fail half-way, the copies already queued
     // still reference the caller's buffers: the stream is drained before the error is returned, so that a failed submit
     // never leaves the slot (or the caller's memory) in flight.
     auto enqueue = [&]() -> int {
+        int rc = AIM_OK;
         HIP_TRY(hipEventRecord(s.ev[0], s.stream));
-        if (n) {
-            HIP_TRY(hipMemcpyAsync(s.d_req, io->requests, (size_t)n * req_size(p), hipMemcpyHostToDevice, s.stream));
-            if (ref) HIP_TRY(hipMemcpyAsync(s.d_tpos, text_pos, (size_t)n * 8, hipMemcpyHostToDevice, s.stream));
-            if (packed) {
-                HIP_TRY(hipMemcpyAsync(s.d_packP, io->packed_patterns, (size_t)n * rowb, hipMemcpyHostToDevice, s.stream));
-                if (!ref) HIP_TRY(hipMemcpyAsync(s.d_packT, io->packed_texts, (size_t)n * rowb, hipMemcpyHostToDevice, s.stream));
-                if (io->n_raw) {
-                    HIP_TRY(hipMemcpyAsync(s.d_rawidx, io->raw_pairs, (size_t)io->n_raw * 4, hipMemcpyHostToDevice, s.stream));
-                    HIP_TRY(hipMemcpyAsync(s.d_rawP, io->raw_patterns, (size_t)io->n_raw * rs, hipMemcpyHostToDevice, s.stream));
-                    if (!ref) HIP_TRY(hipMemcpyAsync(s.d_rawT, io->raw_texts, (size_t)io->n_raw * rs, hipMemcpyHostToDevice, s.stream));
-                }
-            } else {
-                HIP_TRY(hipMemcpyAsync(s.d_pat, io->patterns, (size_t)n * rs, hipMemcpyHostToDevice, s.stream));
-                if (!ref) HIP_TRY(hipMemcpyAsync(s.d_txt, io->texts, (size_t)n * rs, hipMemcpyHostToDevice, s.stream));
-            }
-        }
+        if (b.n && (rc = enqueue_inputs(set->params, s, b))) return rc;
         HIP_TRY(hipEventRecord(s.ev[1], s.stream));
         HIP_TRY(hipEventRecord(s.ev[2], s.stream));
-        if (n) {
-            aim::KArgs ka = batch_args(p, n, s.d_req);
-            ka.res = static_cast<aim_result_t *>(s.d_res);
-            ka.ops = s.d_ops;
-            // Does the alignment kernel of this configuration take the batch as it arrived and deliver what was asked for?
-            // (wfa_lane_packed_kernel: packed rows in, {idx, score} or compact CIGAR out.) Then this batch is ONE kernel;
-            // otherwise the conversion kernels of batch_io.hpp run around the default-ABI kernel.
-            uint32_t mode = (packed ? MODE_PACKED_IN : 0u) | ((io->cigars && !io->results && !io->ops && !sio) ? MODE_RUNS_OUT : 0u);   // (the SAM kernel reads ops rows)
-            Plan pl = plan_for_batch(set, d, s, n, mode);
-            // AIM_FLAG_REF_TEXTS: a packed batch keeps the fused packed lane kernel (its texts gathered as packed rows, the windows
-            // holding a byte outside A/C/G/T re-aligned by the general kernel over a to-do list); every other plan runs as for an
-            // ASCII batch after the gather
-            Stage ref_fb;
-            const bool ref_fused = ref && packed && pl.pk && pl.main.kid == K_WFA_LANE_PK && !pl.pack_first && s.d_reftodo && !pl.esc_c &&
-                                   ref_todo_stage(set, d, s.scratch_bytes, n, &ref_fb);
-            if (ref && packed && !ref_fused && pl.pk) {
-                mode &= ~MODE_PACKED_IN;
-                pl = plan_for_batch(set, d, s, n, mode);
-            }
-            const uint32_t runs_cap = std::min(io->runs_cap, set->max_runs);
-            if (packed && !pl.pk) {   // expand into the reference's char[n][READ_SIZE] layout (batch_io.hpp), then run as usual
-                const unsigned rows = ref ? 1u : 2u;   // (grid.y 0: patterns; the texts of a reference batch are gathered below)
-                aim::unpack_rows_launch(ka, s.d_packP, s.d_packT, s.d_pat, s.d_txt, rows, s.stream);
-                if (io->n_raw) aim::scatter_raw_rows_launch(p.read_size, io->n_raw, s.d_rawidx, s.d_rawP, s.d_rawT, s.d_pat, s.d_txt, rows, s.stream);
-                HIP_TRY(hipGetLastError());
-            }
-            uint32_t *ref_todo = s.d_reftodo;
-            if (ref_fused) {
-                // packed text rows + to-do list; the side list's (non-ACGT patterns) text rows as ASCII for the raw side pass
-                uint32_t *flag_bits = ref_todo + 16 + set->max_pairs;
-                HIP_TRY(hipMemsetAsync(ref_todo, 0, 64, s.stream));
-                HIP_TRY(hipMemsetAsync(flag_bits, 0, ((size_t)n + 31) / 32 * 4, s.stream));
-                aim::gather_text_packed_launch(ka, s.d_tpos, d.d_ref, d.ref_len, s.d_packT, flag_bits, ref_todo, s.stream);
-                HIP_TRY(hipGetLastError());
-                if (io->n_raw) {
-                    aim::gather_text_rows_launch(ka, s.d_tpos, d.d_ref, d.ref_len, s.d_rawidx, io->n_raw, s.d_rawT, s.stream);
-                    HIP_TRY(hipGetLastError());
-                }
-            } else if (ref) {
-                aim::gather_text_rows_launch(ka, s.d_tpos, d.d_ref, d.ref_len, nullptr, n, s.d_txt, s.stream);
-                HIP_TRY(hipGetLastError());
-            }
-            FusedIo fio;
-            if (pl.pk) { fio.packedP = s.d_packP; fio.packedT = s.d_packT; }
-            if (pl.emits_runs) { fio.cig = s.d_cig; fio.runs = s.d_runs; fio.cursor = s.d_cursor; fio.runs_cap = runs_cap; }
-            rc = launch_on_slot(set, d, s, mode, &fio);
-            if (rc) return rc;
-            if (ref_fused) {
-                // the to-do windows: ASCII rows (pattern unpacked, text gathered), the general kernel over them, their compact CIGAR
-                aim::gather_todo_rows_launch(ka, ref_todo, s.d_tpos, d.d_ref, d.ref_len, s.d_packP, s.d_pat, s.d_txt, s.stream);
-                HIP_TRY(hipGetLastError());
-                aim::KArgs kb = stage_args(ka, ref_fb, s.d_scratch);
-                kb.patterns = s.d_pat;
-                kb.texts = s.d_txt;
-                kb.todo = ref_todo;
-                launch_stage(p, ref_fb, kb, s.stream);
-                HIP_TRY(hipGetLastError());
-                if (pl.emits_runs) {
-                    aim::cigar_rle_todo_launch(kb, ref_todo, s.d_cig, s.d_runs, runs_cap, s.d_cursor, s.stream);
-                    HIP_TRY(hipGetLastError());
-                }
-            }
-            s.runs_sent = pl.emits_runs ? n * fio.run_slot : 0u;   // 0 when the run buffer is bump-allocated: nothing is known before the kernel ran
-            if (io->cigars && !pl.emits_runs) {
-                HIP_TRY(hipMemsetAsync(s.d_cursor, 0, 4, s.stream));
-                aim::cigar_rle_launch(ka, s.d_cig, s.d_runs, runs_cap, s.d_cursor, s.stream);
-                HIP_TRY(hipGetLastError());
-            }
-            if (pl.pk && io->n_raw) {
-                // Raw side pass: the pairs of the side list hold a byte outside A/C/G/T (the reference compares raw bytes,
-                // host.c:126-127); what the packed kernel computed for them is void. They are aligned as a batch of their own by
-                // the ASCII kernels -- requests gathered, the side list's rows are its patterns / texts -- and their results
-                // replace the void ones (with the compact CIGAR: their runs are appended to the run buffer).
-                const uint32_t nr = io->n_raw;
-                const uint32_t rq_dw = (uint32_t)req_size(p) / 4, rs_dw = (uint32_t)res_size(p) / 4;
-                aim::gather_elems_launch((const uint32_t *)s.d_req, s.d_rawidx, nr, rq_dw, (uint32_t *)s.d_rawreq, s.stream);
-                HIP_TRY(hipGetLastError());
-                const Plan rp = plan_for_batch(set, d, s, nr, 0u);
-                rc = launch(rp, set->knobs, p, nr, s.d_rawreq, s.d_rawP, s.d_rawT, s.d_rawres, s.d_rawops, s.d_scratch, s.scratch_bytes, s.stream, nullptr, &s.aux);
-                if (rc) return rc;
-                // (both outputs may be asked for at once -- aim_cigar_t + runs AND result_t [+ ops rows]: each gets its own scatter)
-                if (io->cigars) {
-                    aim::KArgs kr = ka;
-                    kr.n_pairs = nr;
-                    kr.res = static_cast<aim_result_t *>(s.d_rawres);
-                    kr.ops = s.d_rawops;
-                    aim::cigar_rle_launch(kr, s.d_rawcig, s.d_runs, runs_cap, s.d_cursor, s.stream);
-                    aim::scatter_elems_launch((const uint32_t *)s.d_rawcig, s.d_rawidx, nr, 4u, (uint32_t *)s.d_cig, s.stream);
-                }
-                if (!io->cigars || io->results || io->ops || sio) {
-                    aim::scatter_elems_launch((const uint32_t *)s.d_rawres, s.d_rawidx, nr, rs_dw, (uint32_t *)s.d_res, s.stream);
-                    if (bt) {   // default output (result_t + ops rows): the side list's ops rows go home too
-                        const uint32_t op_dw = (uint32_t)(2 * rs / 4);
-                        aim::scatter_elems_launch((const uint32_t *)s.d_rawops, s.d_rawidx, nr, op_dw, (uint32_t *)s.d_ops, s.stream);
-                    }
-                }
-                HIP_TRY(hipGetLastError());
-            }
-            if (sio) {   // the records of the final rows (the raw side pass's rows are home)
-                rc = enqueue_sam_on_slot(set, d, s, sio, n, nullptr);
-                if (rc) return rc;
-            }
-        }
+        if (b.n) choose_plan(set, d, s, b);
+        if (b.n && (rc = enqueue_text_rows(set, d, s, b))) return rc;
+        if (b.n && (rc = enqueue_alignment(set, d, s, b))) return rc;
+        if (b.n && (rc = enqueue_raw_side_pass(set, d, s, b))) return rc;
+        if (b.n && b.sio && (rc = enqueue_sam_on_slot(set, d, s, b.sio, b.n, nullptr))) return rc;   // the records of the final rows (the raw side pass's rows are home)
         HIP_TRY(hipEventRecord(s.ev[3], s.stream));
         HIP_TRY(hipEventRecord(s.ev[4], s.stream));
-        if (n) {
-            if (sio) {
-                rc = enqueue_sam_d2h(s, n);
-                if (rc) return rc;
-            }
-            if (io->cigars) {
-                HIP_TRY(hipMemcpyAsync(s.h_cursor, s.d_cursor, 4, hipMemcpyDeviceToHost, s.stream));
-                HIP_TRY(hipMemcpyAsync(io->cigars, s.d_cig, (size_t)n * sizeof(aim_cigar_t), hipMemcpyDeviceToHost, s.stream));
-                // slotted run buffer (wfa_lane_packed.hpp): the first 3 n runs are the pairs' own slots, known now -- their copy
-                // overlaps the next batch instead of waiting in aim_set_wait for the cursor; only runs behind the slots follow there
-                if (s.runs_sent) HIP_TRY(hipMemcpyAsync(io->runs, s.d_runs, (size_t)s.runs_sent * 4, hipMemcpyDeviceToHost, s.stream));
-            }
-            if (io->results) HIP_TRY(hipMemcpyAsync(io->results, s.d_res, (size_t)n * res_size(p), hipMemcpyDeviceToHost, s.stream));
-            if (io->ops) HIP_TRY(hipMemcpyAsync(io->ops, s.d_ops, (size_t)n * 2 * rs, hipMemcpyDeviceToHost, s.stream));
-        }
+        if (b.n && b.sio && (rc = enqueue_sam_d2h(s, b.n))) return rc;
+        if (b.n && (rc = enqueue_rows_d2h(set->params, s, b.n))) return rc;
         HIP_TRY(hipEventRecord(s.ev[5], s.stream));
         return AIM_OK;
     };
-    rc = enqueue();
-    if (rc) return fail_drained(s, rc);
+    if (int rc = enqueue()) return fail_drained(s, rc);
     s.submitted = true;
     return AIM_OK;
 }
@@ -1202,16 +962,12 @@ int aim_set_sam_capacity(aim_set_t *set, uint32_t max_cigar_words, uint32_t max_
         HIP_TRY(hipSetDevice(d.dev));
         for (auto &s : d.slots) {
             if (s.submitted) return fail(AIM_ESTATE, "a slot of device %d holds a batch: aim_set_wait it first", d.dev);
-            void *old[] = {s.d_sam, s.d_samcig, s.d_sammd, s.d_samcur};
-            for (void *b : old)
-                if (b) (void)hipFree(b);
-            s.d_sam = nullptr; s.d_samcig = nullptr; s.d_sammd = nullptr; s.d_samcur = nullptr;
-            s.samcig_cap = s.sammd_cap = 0;
-            HIP_TRY(hipMalloc((void **)&s.d_samcig, (size_t)max_cigar_words * 4));
-            HIP_TRY(hipMalloc((void **)&s.d_sammd, (size_t)max_md_bytes));
-            HIP_TRY(hipMalloc((void **)&s.d_samcur, 64));
-            if (!s.h_samcur) HIP_TRY(hipHostMalloc((void **)&s.h_samcur, 64, hipHostMallocDefault));
-            HIP_TRY(hipMalloc((void **)&s.d_sam, (size_t)set->max_pairs * sizeof(aim_sam_t)));   // last: a slot with d_sam is complete
+            free_sam_buffers(s);
+            HIP_TRY(slot_alloc(s.owned_sam, s.d_samcig, (size_t)max_cigar_words * 4));
+            HIP_TRY(slot_alloc(s.owned_sam, s.d_sammd, (size_t)max_md_bytes));
+            HIP_TRY(slot_alloc(s.owned_sam, s.d_samcur, 64));
+            if (!s.h_samcur) HIP_TRY(slot_alloc_pinned(s, s.h_samcur, 64));
+            HIP_TRY(slot_alloc(s.owned_sam, s.d_sam, (size_t)set->max_pairs * sizeof(aim_sam_t)));   // last: a slot with d_sam is complete
             s.samcig_cap = max_cigar_words;
             s.sammd_cap = max_md_bytes;
         }
@@ -1337,67 +1093,12 @@ int aim_host_free(void *ptr)
 }
 
 
-int aim_align_device_ref(const aim_params_t *params, uint32_t n_pairs, const void *d_requests, const char *d_patterns,
-                         const uint64_t *d_text_pos, const char *d_reference, uint64_t ref_len, void *d_results, char *d_ops,
-                         void *d_scratch, size_t scratch_bytes, void *hip_stream)
-{
-    if (!params) return fail(AIM_EINVAL, "params is NULL");
-    if (is_sam(*params)) return fail(AIM_EINVAL, kSamStateless);
-    if (!is_ref(*params)) return fail(AIM_EINVAL, "aim_align_device_ref needs AIM_FLAG_REF_TEXTS");
-    if (is_groups(*params)) return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS is set: use aim_align_device_groups");
-    if (is_mates(*params)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS is set: use aim_align_device_mates");
-    if (n_pairs && (!d_text_pos || !d_reference || !d_requests)) return fail(AIM_EINVAL, "null device buffer");
-    int n = 0;
-    int rc = aim_device_count(&n);
-    if (rc) return rc;
-    const aim::Knobs kn = read_knobs();
-    Plan pl;
-    rc = make_plan(*params, n_pairs, kn, stateless_budget_bytes(kn), &pl);
-    if (rc) return rc;
-    const size_t at = ref_rows_at(pl.scratch_total), need = at + ref_rows_bytes(*params, n_pairs);
-    if (!d_scratch || scratch_bytes < need) return fail(AIM_EINVAL, "scratch too small: need %zu bytes, got %zu", need, scratch_bytes);
-    if (n_pairs == 0) return AIM_OK;
-    char *rows = static_cast<char *>(d_scratch) + at;
-    aim::gather_text_rows_launch(batch_args(*params, n_pairs, d_requests), d_text_pos, d_reference, ref_len, nullptr, n_pairs, rows, (hipStream_t)hip_stream);
-    HIP_TRY(hipGetLastError());
-    return launch(pl, kn, *params, n_pairs, d_requests, d_patterns, rows, d_results, d_ops, d_scratch, at, (hipStream_t)hip_stream);
-}
-
 int aim_ref_windows_check(const aim_params_t *params, uint32_t n_pairs, const void *requests, const uint64_t *text_pos, uint64_t ref_len,
                           uint32_t *bad_pair)
 {
     if (!params || (n_pairs && (!requests || !text_pos))) return fail(AIM_EINVAL, "bad arguments");
-    int rc = check_lengths(*params, n_pairs, requests);
-    if (rc) {
-        if (bad_pair)   // name the pair check_lengths refused
-            for (uint32_t i = 0; i < n_pairs; ++i) {
-                const bool r8 = params->flags & AIM_FLAG_REQ8;
-                const int tl = r8 ? static_cast<const aim_request8_t *>(requests)[i].text_len : static_cast<const aim_request_t *>(requests)[i].text_len;
-                const int pl = r8 ? static_cast<const aim_request8_t *>(requests)[i].pattern_len : static_cast<const aim_request_t *>(requests)[i].pattern_len;
-                if (pl < 0 || tl < 0 || pl > params->read_size || tl > params->read_size) { *bad_pair = i; break; }
-            }
-        return rc;
-    }
+    if (int rc = check_lengths(*params, n_pairs, requests, bad_pair)) return rc;
     return check_windows(*params, n_pairs, requests, text_pos, ref_len, bad_pair);
-}
-
-int aim_align_device(const aim_params_t *params, uint32_t n_pairs, const void *d_requests,
-                     const char *d_patterns, const char *d_texts, void *d_results, char *d_ops,
-                     void *d_scratch, size_t scratch_bytes, void *hip_stream)
-{
-    if (!params) return fail(AIM_EINVAL, "params is NULL");
-    if (is_sam(*params)) return fail(AIM_EINVAL, kSamStateless);
-    if (is_groups(*params)) return fail(AIM_EINVAL, "AIM_FLAG_READ_GROUPS is set: use aim_align_device_groups");
-    if (is_mates(*params)) return fail(AIM_EINVAL, "AIM_FLAG_MATE_PAIRS is set: use aim_align_device_mates");
-    int n = 0;
-    int rc = aim_device_count(&n);
-    if (rc) return rc;
-    const aim::Knobs kn = read_knobs();
-    Plan pl;
-    rc = make_plan(*params, n_pairs, kn, stateless_budget_bytes(kn), &pl);
-    if (rc) return rc;
-    return launch(pl, kn, *params, n_pairs, d_requests, d_patterns, d_texts, d_results, d_ops, d_scratch, scratch_bytes,
-                  (hipStream_t)hip_stream);
 }
 
 // aim_sam_device (split = false) and aim_sam_device_split under the name fn: the same checks in the same order, then one launch.

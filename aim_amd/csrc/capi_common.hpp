@@ -1,5 +1,6 @@
-// capi_common.hpp -- what the units of the C-ABI share: aim_capi.hip (device sets, launching, alignment entry points), capi_groups.hip
-// (the read-groups path: AIM_FLAG_READ_GROUPS, MATE_PAIRS and TOP_HITS; it shares the device set with aim_capi.hip through capi_set.hpp),
+// capi_common.hpp -- what the units of the C-ABI share: aim_capi.hip (device sets, slots, submit and wait), capi_launch.hip (a plan into
+// launches, and the stateless alignment entry points), capi_groups.hip (the read-groups path: AIM_FLAG_READ_GROUPS, MATE_PAIRS and
+// TOP_HITS) -- these three share the device set and launch() through capi_set.hpp --,
 // capi_plan.hip (the launch planner; its types and entry points are in plan.hpp), capi_pipeline.hip (index, seeding, classes and MAPQ,
 // split, extension), capi_mapper.hip (the record list and aim_mapper_t) and capi_host.hip (host-side formatters and generators). None of
 // them compiles a kernel: each kernel family's tu_*.hip does, and these units call its launchers. Internal, not installed.
@@ -22,8 +23,8 @@ namespace capi {
 int fail(int code, const char *fmt, ...);   // sets aim_last_error() for the calling thread and returns `code`
 aim::Knobs read_knobs();                    // the AIM_* environment, as it is now
 aim::Knobs with_chip(aim::Knobs k);         // ... for a plan on the current device: AIM_CHIP_CUS wins, else the device's own CU count
-// Every length of a batch against READ_SIZE; AIM_EINVAL names the first pair that breaks it.
-int check_lengths(const aim_params_t &p, uint32_t n_pairs, const void *requests);
+// Every length of a batch against READ_SIZE; AIM_EINVAL names the first pair that breaks it (and *bad_pair receives it).
+int check_lengths(const aim_params_t &p, uint32_t n_pairs, const void *requests, uint32_t *bad_pair = nullptr);
 // AIM_FLAG_REF_TEXTS: texts gathered from a device-resident reference (batch_io.hpp); no plan depends on it.
 inline bool is_ref(const aim_params_t &p) { return (p.flags & AIM_FLAG_REF_TEXTS) != 0; }
 // What every alignment entry point refuses about its aim_params_t (capi_plan.hip: validate_params), before any device query.

@@ -1,7 +1,8 @@
 // capi_groups.hip -- the read-groups path of the C-ABI (include/aim_hip.h): AIM_FLAG_READ_GROUPS, AIM_FLAG_MATE_PAIRS and
 // AIM_FLAG_TOP_HITS. A groups batch on a slot (submit_groups, which aim_set_submit hands such a batch to), the stateless entry points
 // and the host-side checks of their inputs. Host code only: the kernels are launched through groups.hpp, hits.hpp, mates.hpp and
-// batch_io.hpp, the two alignment passes through launch() of aim_capi.hip (capi_set.hpp).
+// batch_io.hpp, the two alignment passes through launch() of capi_launch.hip; that and what a groups batch shares with aim_set_submit
+// of aim_capi.hip (the slot's reset, the copies of its output rows, the checks) are declared in capi_set.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -66,7 +67,10 @@ int enqueue_groups(const GroupsPlan &g, const Plan &pl1, const Plan &pl2, const 
         aim::group_unpack_launch(ka, io.packed, io.map, io.raw_slot, io.raw_rows, io.n_raw, nr, io.cand_p, stream);
         HIP_TRY(hipGetLastError());
     }
-    int rc = launch(pl1, kn, p1, n, io.req, io.cand_p, io.cand_t, io.res1, nullptr, io.scratch, io.scratch_bytes, stream, nullptr, aux);
+    LaunchIo pass;   // pass 1: every candidate, score rows only
+    pass.n_pairs = n; pass.req = io.req; pass.pat = io.cand_p; pass.txt = io.cand_t;
+    pass.res = io.res1; pass.scratch = io.scratch; pass.scratch_bytes = io.scratch_bytes;
+    int rc = launch(pl1, kn, p1, pass, stream, nullptr, aux);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(io.sel, 0, (size_t)nr * 4, stream));   // (a read the CSR check would refuse keeps a valid sel)
     aim::group_select_launch(io.res1, n, io.roff, nr, io.best, io.sel, stream);
@@ -102,7 +106,9 @@ int enqueue_groups(const GroupsPlan &g, const Plan &pl1, const Plan &pl2, const 
     HIP_TRY(hipGetLastError());
     aim::group_rows_launch(k2, io.cand_t, n, row_cand, rows, 1, io.txt2, stream);
     HIP_TRY(hipGetLastError());
-    return launch(pl2, kn, p2, rows, io.req2, io.pat2, io.txt2, io.res, io.ops, io.scratch, io.scratch_bytes, stream, nullptr, aux);
+    pass.n_pairs = rows; pass.req = io.req2; pass.pat = io.pat2; pass.txt = io.txt2;   // pass 2: the rows behind the selection
+    pass.res = io.res; pass.ops = io.ops;
+    return launch(pl2, kn, p2, pass, stream, nullptr, aux);
 }
 
 // aim_groups_check: the CSR of a groups batch, the first bad read named
@@ -239,13 +245,9 @@ int aim::capi::submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const
     }
     const size_t rs = (size_t)p.read_size;
     HIP_TRY(hipSetDevice(d.dev));
-    s.io = *io;
+    reset_slot(s, io);
     s.n_pairs = rows;        // aim_set_wait reads n_pairs output rows
     s.n_reads = nr;
-    s.io_sam = nullptr;
-    s.runs_sent = 0;
-    s.pushed = s.launched = false;
-    s.ref_pending = false;
     GroupsPlan g;
     memset(&g, 0, sizeof g);
     g.x1 = groups_pass_params(p, AIM_FLAG_BACKTRACE | AIM_FLAG_WFA_BIDIR | AIM_FLAG_RES8);
@@ -344,12 +346,7 @@ int aim::capi::submit_groups(aim_set *set, aim_device_ctx &d, aim_slot &s, const
             if (gio->best) HIP_TRY(hipMemcpyAsync(gio->best, s.g_best, (size_t)nr * sizeof(aim_best_t), hipMemcpyDeviceToHost, s.stream));
             if (mio && mio->mates && nr >= 2)
                 HIP_TRY(hipMemcpyAsync(mio->mates, s.g_mates, (size_t)(nr / 2) * sizeof(aim_mate_t), hipMemcpyDeviceToHost, s.stream));
-            if (io->cigars) {
-                HIP_TRY(hipMemcpyAsync(s.h_cursor, s.d_cursor, 4, hipMemcpyDeviceToHost, s.stream));
-                HIP_TRY(hipMemcpyAsync(io->cigars, s.d_cig, (size_t)rows * sizeof(aim_cigar_t), hipMemcpyDeviceToHost, s.stream));
-            }
-            if (io->results) HIP_TRY(hipMemcpyAsync(io->results, s.d_res, (size_t)rows * res_size(p), hipMemcpyDeviceToHost, s.stream));
-            if (io->ops) HIP_TRY(hipMemcpyAsync(io->ops, s.d_ops, (size_t)rows * 2 * rs, hipMemcpyDeviceToHost, s.stream));
+            if (int crc = enqueue_rows_d2h(p, s, rows)) return crc;   // (runs_sent is 0: a groups batch's runs all follow in aim_set_wait)
             if (hio && hio->hit_pair) HIP_TRY(hipMemcpyAsync(hio->hit_pair, s.g_hit, (size_t)rows * 4, hipMemcpyDeviceToHost, s.stream));
             if (sio) {
                 int src = enqueue_sam_d2h(s, nr);

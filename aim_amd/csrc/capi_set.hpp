@@ -1,6 +1,7 @@
-// capi_set.hpp -- what aim_capi.hip and capi_groups.hip share: the device set with its slots, and the functions of aim_capi.hip that a
-// groups batch goes through (the launch of a plan, the window and SAM checks, the SAM kernel on a slot). Internal, not installed. Every
-// function declared here has ONE definition: submit_groups() in capi_groups.hip, the others in aim_capi.hip.
+// capi_set.hpp -- what aim_capi.hip, capi_launch.hip and capi_groups.hip share: the device set with its slots, the launch of a plan
+// over the buffers a LaunchIo names, and the functions of aim_capi.hip that a groups batch goes through (the slot's reset and row copies,
+// the window and SAM checks, the SAM kernel on a slot). Internal, not installed. Every function declared here has ONE definition:
+// launch(), launch_todo_stage() and aux_stream_destroy() in capi_launch.hip, submit_groups() in capi_groups.hip, the others in aim_capi.hip.
 #pragma once
 #include <vector>
 
@@ -29,6 +30,17 @@ struct FusedIo {
     aim_cigar_t *cig = nullptr;
     uint32_t *runs = nullptr, *cursor = nullptr;
     uint32_t runs_cap = 0, run_slot = 0;
+};
+
+// The device buffers of the batch a launch runs over, by name (several are interchangeable by type): what a plan does not touch stays null.
+struct LaunchIo {
+    uint32_t n_pairs = 0;
+    const void *req = nullptr;
+    const char *pat = nullptr, *txt = nullptr;
+    void *res = nullptr;
+    char *ops = nullptr;
+    void *scratch = nullptr;
+    size_t scratch_bytes = 0;
 };
 }  // namespace capi
 }  // namespace aim
@@ -83,6 +95,9 @@ struct aim_slot {
     aim::capi::AuxStream aux;   // this slot's second stream + events (chunked wfa_group launches with CIGAR); created on first use
     aim::capi::Plan plan_last;  // the plan the last launch followed (the configure-time plan re-made for the pushed pair count)
     aim_batch_io_t io;       // the batch in flight (aim_set_submit .. aim_set_wait)
+    // what free_slot releases: every hipMalloc / hipHostMalloc of the slot, recorded where it is made; the SAM buffers apart, because
+    // aim_set_sam_capacity re-allocates them on a live slot
+    std::vector<void *> owned, owned_sam, pinned;
 };
 
 struct aim_device_ctx {
@@ -108,16 +123,23 @@ struct aim_set {
 
 namespace aim {
 namespace capi {
-// (the one refusal text both units use: aim_align_device[_ref] here, the stateless groups entry points in capi_groups.hip)
+// (the one refusal text two units use: aim_align_device[_ref] in capi_launch.hip, the stateless groups entry points in capi_groups.hip)
 inline constexpr const char *kSamStateless = "AIM_FLAG_SAM_FIELDS is set: the records come from aim_set_submit (aim_batch_io_sam_t) or, after a flag-less call, from aim_sam_device";
 inline size_t req_size(const aim_params_t &p) { return (p.flags & AIM_FLAG_REQ8) ? sizeof(aim_request8_t) : sizeof(aim_request_t); }
 inline size_t res_size(const aim_params_t &p) { return (p.flags & AIM_FLAG_RES8) ? sizeof(aim_result8_t) : sizeof(aim_result_t); }
 
 // Enqueue the launches of plan `pl`. AIM_FLAG_WFA_ESCALATE with two stages: the lane plan at cap esc_c over the batch, the list of the
 // pairs it left at esc_c + 1 (ascending pair order), the full-cap plan over that list -- one stream, no host round trip.
-int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, uint32_t n_pairs, const void *d_req, const char *d_pat,
-           const char *d_txt, void *d_res, char *d_ops, void *d_scratch, size_t scratch_bytes, hipStream_t stream,
-           const FusedIo *fio = nullptr, AuxStream *slot_aux = nullptr);
+int launch(const Plan &pl, const aim::Knobs &kn, const aim_params_t &p, const LaunchIo &io, hipStream_t stream, const FusedIo *fio = nullptr,
+           AuxStream *slot_aux = nullptr);
+// One Stage (a general kernel) over the device-side list `todo` {count @0, pair ids @16..} of the batch io, whose ASCII rows are io.pat / io.txt
+int launch_todo_stage(const aim_params_t &p, const Stage &st, const LaunchIo &io, const uint32_t *todo, hipStream_t stream);
+void aux_stream_destroy(AuxStream &a);
+// What every submit does to its slot before it enqueues: the batch becomes the slot's, nothing of an earlier one is left (n_pairs and
+// n_reads are the caller's)
+void reset_slot(aim_slot &s, const aim_batch_io_t *io);
+// ... and the copies back of the batch's `rows` output rows: compact CIGAR with its cursor (and the runs known by now), results, ops rows
+int enqueue_rows_d2h(const aim_params_t &p, aim_slot &s, uint32_t rows);
 // What a failed submit ends in: nothing of it stays in flight on the slot's stream, and aim_last_error() keeps the enqueue's message.
 int fail_drained(aim_slot &s, int rc);
 int check_windows(const aim_params_t &p, uint32_t n_pairs, const void *requests, const uint64_t *text_pos, uint64_t ref_len, uint32_t *bad_pair);

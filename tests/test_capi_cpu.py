@@ -58,6 +58,50 @@ def test_no_device_means_loud_failure(built):
     assert rc == capi.AIM_ENODEV
 
 
+@pytest.mark.parametrize("req8", [False, True])
+def test_ref_windows_check_names_the_pair_of_a_bad_length(built, req8):
+    """aim_ref_windows_check checks the lengths first and then the windows: *bad_pair names the first pair that breaks either, and the
+    message is that check's own. Bad lengths at pair 0, at a middle pair and at the last pair, of every kind (negative, over READ_SIZE,
+    pattern or text), with and without REQ8; a bad window behind good lengths still names its own pair."""
+    import numpy as np
+    from aim_amd import capi, engine
+    lib = capi.load()
+    rs, n, ref_len = 112, 9, 1000
+    p = engine.make_params("wfa", 5, rs, ref_texts=True, req8=req8)
+
+    def check(plen, tlen, tpos):
+        req = np.zeros(n, dtype=capi.REQUEST_DTYPE)
+        req["pattern_len"], req["text_len"], req["idx"] = plen, tlen, np.arange(n)
+        if req8:
+            req = engine.to_request8(req)
+        tpos = np.ascontiguousarray(tpos, dtype=np.uint64)
+        bad = C.c_uint32(0xFFFFFFFF)
+        rc = lib.aim_ref_windows_check(capi.params_ref(p), n, capi.ptr(req), capi.ptr(tpos), ref_len, C.byref(bad))
+        return rc, bad.value, lib.aim_last_error().decode()
+
+    good_len, good_pos = np.full(n, 100), np.arange(n) * 100                  # windows [100 i, 100 i + 100): the last ends at 900
+    assert check(good_len, good_len, good_pos)[:2] == (capi.AIM_OK, 0xFFFFFFFF)
+    for pair in (0, n // 2, n - 1):
+        for field, value in (("p", rs + 1), ("t", rs + 1), ("p", -1), ("t", -1)):
+            plen, tlen = good_len.copy(), good_len.copy()
+            (plen if field == "p" else tlen)[pair] = value
+            rc, bad, msg = check(plen, tlen, good_pos)
+            assert (rc, bad) == (capi.AIM_EINVAL, pair), (pair, field, value)
+            assert msg == "READ LENGTH less than length of the input reads (pair %d)" % pair
+    # the first of several is named; a bad length in front of a bad window wins, a bad window in front of a bad length does not
+    plen = good_len.copy(); plen[[2, 5]] = rs + 8
+    assert check(plen, good_len, good_pos)[1] == 2
+    pos = good_pos.copy(); pos[1] = ref_len - 99                              # 901 + 100 > 1000
+    rc, bad, msg = check(plen, good_len, pos)
+    assert (rc, bad) == (capi.AIM_EINVAL, 2) and msg.startswith("READ LENGTH")
+    # good lengths everywhere: the window check names its own pair, in its own words
+    for pair in (0, n // 2, n - 1):
+        pos = good_pos.copy(); pos[pair] = ref_len - 99
+        rc, bad, msg = check(good_len, good_len, pos)
+        assert (rc, bad) == (capi.AIM_EINVAL, pair)
+        assert msg.startswith("text window of pair %d is outside the reference" % pair)
+
+
 def test_product_never_references_the_oracle():
     """The product path must not import, link or execute anything under oracle/."""
     for base, _, files in os.walk(os.path.join(ROOT, "aim_amd")):

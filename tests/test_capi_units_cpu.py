@@ -15,7 +15,8 @@ def _code(path):
 
 def test_no_capi_unit_compiles_or_launches_a_kernel():
     units = [os.path.join(CSRC, "aim_capi.hip")] + sorted(glob.glob(os.path.join(CSRC, "capi_*.hip")))
-    assert len(units) >= 6, units            # aim_capi, capi_groups, capi_host, capi_mapper, capi_pipeline, capi_plan
+    assert len(units) >= 7, units            # aim_capi, capi_groups, capi_host, capi_launch, capi_mapper, capi_pipeline, capi_plan
+    assert "capi_launch.hip" in [os.path.basename(u) for u in units]
     for u in units:
         code = _code(u)
         for word in ("__global__", "hipLaunchKernelGGL", "<<<"):
