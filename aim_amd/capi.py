@@ -65,6 +65,9 @@ MAPPER_MAX_SLOTS = 4
 FEATURE_CONTIGS = 0x100000        # aim_features(): aim_contigs_* / aim_contig_clip_device / aim_map_records_contigs_device / aim_mapper_create_contigs exist
 CONTIG_MAX, CONTIG_NONE = 1 << 20, 0xFFFFFFFF
 SEG_CONTIG_CLIPPED = 0x80         # aim_segment_t.flags, from aim_contig_clip_device
+FEATURE_PAIRED = 0x200000         # aim_features(): aim_pair_rescue_rows_device / aim_pair_select_device / aim_map_mates_device / aim_mapper_set_pairing exist
+PAIR_RESCUE = 0x1                 # aim_map_pair_params_t.options: try the mate rescue
+PAIR_PROPER, PAIR_RESCUE_TRIED_A, PAIR_RESCUE_TRIED_B, PAIR_RESCUED_A, PAIR_RESCUED_B = 0x1, 0x2, 0x4, 0x8, 0x10   # aim_map_pair_t.flags
 
 
 def CONTIG_SPACER(band):
@@ -194,6 +197,23 @@ class MapperOut(C.Structure):
 assert C.sizeof(MapperParams) == 124 and C.sizeof(MapperOut) == 56
 
 
+class MapPairParams(C.Structure):
+    """aim_map_pair_params_t"""
+    _fields_ = [("min_span", C.c_int64), ("max_span", C.c_int64), ("unpaired_penalty", C.c_int32), ("options", C.c_uint32), ("rescue_size", C.c_uint32),
+                ("rescue_cigar_cap", C.c_uint32), ("rescue_md_cap", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class MapperPairsOut(C.Structure):
+    """aim_mapper_pairs_out_t"""
+    _fields_ = [("n_pairs", C.c_uint32), ("n_records", C.c_uint32), ("rescue_cigar_words", C.c_uint32), ("rescue_md_bytes", C.c_uint32),
+                ("rescue_cigar_needed", C.c_uint32), ("rescue_md_needed", C.c_uint32), ("mates", C.c_void_p), ("pairs", C.c_void_p)]
+
+
+MAP_PAIR_DTYPE = np.dtype([("slot", "<u4", (2,)), ("score_sum", "<i4"), ("second_sum", "<i4"), ("n_best", "<u4"), ("flags", "<u4"), ("span", "<i8")])   # aim_map_pair_t
+MAP_MATE_DTYPE = np.dtype([("mate_pos", "<u8"), ("tlen", "<i4"), ("mate_contig", "<u4")])   # aim_map_mate_t
+assert C.sizeof(MapPairParams) == 40 and C.sizeof(MapperPairsOut) == 40 and MAP_PAIR_DTYPE.itemsize == 32 and MAP_MATE_DTYPE.itemsize == 16
+
+
 class BatchIO(C.Structure):
     """aim_batch_io_t"""
     _fields_ = [("n_pairs", C.c_uint32), ("requests", C.c_void_p), ("patterns", C.c_void_p), ("texts", C.c_void_p),
@@ -321,6 +341,13 @@ SYMBOLS = {
     "aim_mapper_device_bytes_contigs": (C.c_int, [C.POINTER(MapperParams), _U32, _VP, C.POINTER(C.c_uint64)]),
     "aim_mapper_create_contigs": (C.c_int, [C.POINTER(MapperParams), C.c_int, _U32, _VP, _VP, C.POINTER(_VP)]),
     "aim_mapper_contigs": (C.c_int, [_VP, C.POINTER(_U32), C.POINTER(_VP), C.POINTER(_VP)]),
+    "aim_pair_rescue_rows_device": (C.c_int, [C.POINTER(MapPairParams), _U32, _U32, C.c_uint64, _U32, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "aim_pair_select_device": (C.c_int, [C.POINTER(MapPairParams), _U32, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _VP]),
+    "aim_map_mates_device": (C.c_int, [_U32, _U32, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP]),
+    "aim_pair_kernel_names": (C.c_char_p, []),
+    "aim_mapper_pairing_device_bytes": (C.c_int, [C.POINTER(MapperParams), C.POINTER(MapPairParams), C.POINTER(C.c_uint64)]),
+    "aim_mapper_set_pairing": (C.c_int, [_VP, C.POINTER(MapPairParams)]),
+    "aim_mapper_pairs": (C.c_int, [_VP, _U32, C.POINTER(MapperPairsOut)]),
 }
 
 _lib = None

@@ -2,7 +2,8 @@
 // launches, and the stateless alignment entry points), capi_groups.hip (the read-groups path: AIM_FLAG_READ_GROUPS, MATE_PAIRS and
 // TOP_HITS) -- these three share the device set and launch() through capi_set.hpp --,
 // capi_plan.hip (the launch planner; its types and entry points are in plan.hpp), capi_pipeline.hip (index, seeding, classes and MAPQ,
-// split, extension), capi_mapper.hip (the record list and aim_mapper_t) and capi_host.hip (host-side formatters and generators). None of
+// split, extension), capi_mapper.hip (the record list and aim_mapper_t), capi_pair.hip (rule 14c's stateless entry points) and capi_host.hip (host-side formatters and
+// generators). None of
 // them compiles a kernel: each kernel family's tu_*.hip does, and these units call its launchers. Internal, not installed.
 // Every function declared here has ONE definition, next to the state it owns: fail() in aim_capi.hip, where it writes the thread-local
 // buffer aim_last_error() returns; read_knobs(), the one reader of the AIM_* environment, with_chip(), which asks chip_cus()'s per-device
@@ -38,6 +39,9 @@ int check_seed_chain_band(const aim_seed_params_t &sp, const char *fn);
 int check_seed_long_params(const aim_seed_params_t &sp, uint32_t max_hits);
 // aim_extend_segments_device's refusals of its aim_extend_params_t, in the header's order, under the name `fn`.
 int check_extend_params(const char *fn, const aim_extend_params_t *p);
+// Rule 14c's refusals of its aim_map_pair_params_t against K, read_size and n_reads, in the header's order, under the name `fn`
+// (capi_pair.hip). The rescue_size bounds are checked with AIM_PAIR_RESCUE, or always when `rescue_always`.
+int check_pair_params(const char *fn, const aim_map_pair_params_t *pp, uint32_t K, uint32_t read_size, uint32_t n_reads, bool rescue_always);
 
 // The refusals the pipeline's entry points share: one copy of each bound and of its message; `fn` names the entry point. Each is true when
 // its bound holds and otherwise leaves its message in aim_last_error(). An entry point joins them with && in its own order -- the order its

@@ -42,6 +42,34 @@ aim_endsfree_params_t align_params(const aim_mapper_params_t &p)
     return e;
 }
 
+// Rule 14c's rescue alignment: the segment alignment at read_size = rescue_size, with the whole window free at either end.
+aim_endsfree_params_t rescue_params(const aim_mapper_params_t &p, const aim_map_pair_params_t &pp)
+{
+    aim_endsfree_params_t e = align_params(p);
+    e.base.read_size = (int32_t)pp.rescue_size;
+    e.text_begin_free = e.text_end_free = (int32_t)pp.rescue_size;
+    return e;
+}
+
+// Every refusal of aim_mapper_pairing_device_bytes and aim_mapper_set_pairing behind the NULL checks; no device is asked anything.
+int check_pairing(const char *fn, const aim_mapper_params_t &p, const aim_map_pair_params_t *pp)
+{
+    if (const int rc = check_pair_params(fn, pp, (uint32_t)p.seed.max_cands, (uint32_t)p.seed.read_size, 0, false)) return rc;
+    if ((uint64_t)p.max_reads * ((uint64_t)p.seed.max_cands + 1u) >= (1ull << 32))
+        return fail(AIM_EINVAL, "%s: max_reads %u * (K %d + 1) does not fit 32 bits", fn, p.max_reads, p.seed.max_cands);
+    if (pp->options & AIM_PAIR_RESCUE) {
+        if (pp->rescue_size > (uint32_t)INT32_MAX) return fail(AIM_EINVAL, "%s: rescue_size %u is above INT32_MAX", fn, pp->rescue_size);
+        const aim_endsfree_params_t rap = rescue_params(p, *pp);
+        if (check_align_params(rap.base)) return under(fn, AIM_EINVAL);
+        if ((uint64_t)p.max_reads * (4ull * pp->rescue_size + 10ull) >= (1ull << 32))
+            return fail(AIM_EINVAL, "%s: max_reads %u rows of rescue_size %u exceed the 32-bit offsets of aim_sam_t (max_reads * (4 * rescue_size + 10) must stay below 2^32)",
+                        fn, p.max_reads, pp->rescue_size);
+    }
+    if ((uint64_t)p.cigar_cap + pp->rescue_cigar_cap >= (1ull << 32) || (uint64_t)p.md_cap + pp->rescue_md_cap >= (1ull << 32))
+        return fail(AIM_EINVAL, "%s: cigar_cap + rescue_cigar_cap and md_cap + rescue_md_cap must stay below 2^32", fn);
+    return AIM_OK;
+}
+
 // Every refusal of aim_mapper_device_bytes and aim_mapper_create, in stage order; no device is asked anything.
 int check_mapper_params(const char *fn, const aim_mapper_params_t *p, uint64_t ref_len)
 {
@@ -100,7 +128,9 @@ uint32_t mapper_spacer(const aim_mapper_params_t &p) { return AIM_CONTIG_SPACER(
 
 // The device buffers of one slot, in allocation order: `bytes` each, carved out of one allocation at multiples of 256.
 enum Buf { B_READS, B_READ_LEN, B_REQ, B_TEXT_POS, B_VOTES, B_SEED, B_CHAINS, B_CLASS, B_SEG_REQ, B_SEG_TEXT_POS, B_SEG_PATTERNS, B_SEG, B_EXT,
-           B_RESULTS, B_OPS, B_SCRATCH, B_SAM, B_CIGAR, B_MD, B_OFFSETS, B_RECORDS, B_MAP_SCRATCH, B_CONTIG, B_COUNT };
+           B_RESULTS, B_OPS, B_SCRATCH, B_SAM, B_CIGAR, B_MD, B_OFFSETS, B_RECORDS, B_MAP_SCRATCH, B_CONTIG,
+           // rule 14c, after aim_mapper_set_pairing alone (the B_RES_* only with AIM_PAIR_RESCUE): a mapper without it keeps its layout
+           B_PAIRS, B_MATES, B_RES_CURSORS, B_RES_REQ, B_RES_TEXT_POS, B_RES_PATTERNS, B_RES_RESULTS, B_RES_OPS, B_RES_SCRATCH, B_RES_SAM, B_COUNT };
 
 struct SlotLayout {
     uint64_t at[B_COUNT], bytes[B_COUNT], total;
@@ -108,7 +138,7 @@ struct SlotLayout {
 
 inline uint64_t up256(uint64_t x) { return (x + 255u) & ~255ull; }
 
-SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch, bool contigs)
+SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch, bool contigs, const aim_map_pair_params_t *pp = nullptr, size_t rescue_scratch = 0)
 {
     const uint64_t N = p.max_reads, K = (uint64_t)p.seed.max_cands, rs = (uint64_t)p.seed.read_size, S = N * K;
     SlotLayout L;
@@ -123,10 +153,19 @@ SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch, bool 
     b[B_OFFSETS] = 4 * (N + 3);          // rec_offsets[n_reads + 1], then the two cursors of the SAM kernel: one copy fetches the three dwords
     b[B_RECORDS] = sizeof(aim_map_record_t) * S; b[B_MAP_SCRATCH] = kMapScratch;
     b[B_CONTIG] = contigs ? 4 * S : 0;   // d_contig of rule 13c: a mapper of one sequence has none and keeps its size
+    if (pp) {                            // rule 14c: the rescue regions behind the main ones, and the buffers of the new stages
+        b[B_CIGAR] += 4ull * pp->rescue_cigar_cap; b[B_MD] += pp->rescue_md_cap;
+        b[B_PAIRS] = sizeof(aim_map_pair_t) * ((N + 1) / 2); b[B_MATES] = sizeof(aim_map_mate_t) * S; b[B_RES_CURSORS] = 8;
+        if (pp->options & AIM_PAIR_RESCUE) {
+            const uint64_t rz = pp->rescue_size;
+            b[B_RES_REQ] = 16 * N; b[B_RES_TEXT_POS] = 8 * N; b[B_RES_PATTERNS] = N * rz + 64; b[B_RES_RESULTS] = sizeof(aim_result_t) * N;
+            b[B_RES_OPS] = N * 2 * rz + 64; b[B_RES_SCRATCH] = rescue_scratch; b[B_RES_SAM] = sizeof(aim_sam_t) * N;
+        }
+    }
     uint64_t at = 0;
     for (int i = 0; i < B_COUNT; ++i) {
         L.at[i] = at;
-        if (i == B_CONTIG && !contigs) continue;
+        if (i >= B_CONTIG && !b[i]) continue;   // the buffers of rules 13c and 14c exist only where the rule runs
         at += up256(std::max<uint64_t>(b[i], 4));
     }
     L.total = at;
@@ -145,6 +184,12 @@ struct MapperSlot {
     uint32_t *h_head = nullptr;          // {record count, CIGAR words, MD bytes}
     bool in_flight = false;
     uint32_t n_reads = 0;
+    // rule 14c (aim_mapper_set_pairing): the views of aim_mapper_pairs and what the last wait found
+    aim_map_mate_t *h_mates = nullptr;   // pinned
+    aim_map_pair_t *h_pairs = nullptr;
+    uint32_t *h_res_head = nullptr;      // {rescue CIGAR words, rescue MD bytes}
+    bool waited = false;
+    aim_mapper_pairs_out_t po = {};
 };
 
 }  // namespace
@@ -161,6 +206,10 @@ struct aim_mapper {
     size_t align_scratch = 0;
     SlotLayout L;
     MapperSlot slot[AIM_MAPPER_MAX_SLOTS];
+    bool paired = false;                 // rule 14c: aim_mapper_set_pairing was called
+    aim_map_pair_params_t pp = {};
+    aim_endsfree_params_t rap = {};      // the rescue alignment
+    size_t rescue_scratch = 0;
 };
 
 namespace {
@@ -173,7 +222,8 @@ void release(aim_mapper *m)
     for (MapperSlot &s : m->slot) {
         if (s.stream) (void)hipStreamSynchronize(s.stream);
         if (s.dev) (void)hipFree(s.dev);
-        for (void *h : {(void *)s.h_reads, (void *)s.h_read_len, (void *)s.h_records, (void *)s.h_offsets, (void *)s.h_cigar, (void *)s.h_md, (void *)s.h_head})
+        for (void *h : {(void *)s.h_reads, (void *)s.h_read_len, (void *)s.h_records, (void *)s.h_offsets, (void *)s.h_cigar, (void *)s.h_md, (void *)s.h_head,
+                        (void *)s.h_mates, (void *)s.h_pairs, (void *)s.h_res_head})
             if (h) (void)hipHostFree(h);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
@@ -289,6 +339,38 @@ int map_records(const char *fn, bool contigs, uint32_t K, uint32_t n_reads, cons
     else aim::map_records_launch(a, lanes, grid, stream);
     HIP_TRY(hipGetLastError());
     return AIM_OK;
+}
+
+// Rule 14c's stages between aim_sam_device_split and the record kernel, on the slot's buffers: the rescue rows, their alignment and
+// their records behind the main CIGAR / MD regions (the three with AIM_PAIR_RESCUE alone), then select / apply.
+int submit_pairing(aim_mapper *m, MapperSlot &s, uint32_t n_reads, hipStream_t st)
+{
+    const aim_mapper_params_t &p = m->p;
+    const aim_map_pair_params_t &pp = m->pp;
+    const uint32_t K = (uint32_t)p.seed.max_cands, rs = (uint32_t)p.seed.read_size, n_contigs = (uint32_t)m->starts.size();
+    const bool rescue = (pp.options & AIM_PAIR_RESCUE) != 0;
+    int32_t *d_rl = at<int32_t>(m, s, B_READ_LEN);
+    aim_segment_t *d_seg = at<aim_segment_t>(m, s, B_SEG);
+    aim_sam_t *d_sam = at<aim_sam_t>(m, s, B_SAM), *d_res_sam = rescue ? at<aim_sam_t>(m, s, B_RES_SAM) : nullptr;
+    uint32_t *d_contig = n_contigs ? at<uint32_t>(m, s, B_CONTIG) : nullptr, *d_res_cursors = at<uint32_t>(m, s, B_RES_CURSORS);
+    int rc = AIM_OK;
+    if (rescue) {
+        void *d_req = at<void>(m, s, B_RES_REQ), *d_res = at<void>(m, s, B_RES_RESULTS);
+        uint64_t *d_tp = at<uint64_t>(m, s, B_RES_TEXT_POS);
+        char *d_pat = at<char>(m, s, B_RES_PATTERNS), *d_ops = at<char>(m, s, B_RES_OPS);
+        rc = aim_pair_rescue_rows_device(&pp, K, rs, m->ref_len, n_contigs, m->d_contig_start, m->d_contig_len, n_reads, d_rl, at<char>(m, s, B_READS), d_seg, d_sam,
+                                         d_contig, d_req, d_tp, d_pat, st);
+        if (!rc) rc = aim_align_device_ref(&m->rap.base, n_reads, d_req, d_pat, d_tp, m->d_ref, m->ref_len, d_res, d_ops, at<void>(m, s, B_RES_SCRATCH), m->rescue_scratch, st);
+        if (!rc)
+            rc = aim_sam_device(&m->rap.base, n_reads, d_req, d_tp, nullptr, d_res, d_ops, m->d_ref, m->ref_len, p.sam_options, d_res_sam,
+                                at<uint32_t>(m, s, B_CIGAR) + p.cigar_cap, pp.rescue_cigar_cap, at<char>(m, s, B_MD) + p.md_cap, pp.rescue_md_cap, d_res_cursors, st);
+    } else {
+        HIP_TRY(hipMemsetAsync(d_res_cursors, 0, 8, st));
+    }
+    if (!rc)
+        rc = aim_pair_select_device(&pp, K, rs, n_reads, d_rl, d_seg, d_sam, at<aim_chain_class_t>(m, s, B_CLASS), d_contig, d_res_sam, p.cigar_cap, p.md_cap,
+                                    at<aim_map_pair_t>(m, s, B_PAIRS), st);
+    return rc;
 }
 
 // What aim_mapper_device_bytes and its contig twin report, behind their checks.
@@ -471,10 +553,12 @@ int aim_mapper_submit(aim_mapper_t *m, uint32_t slot, uint32_t n_reads, const in
     if (slot >= m->p.slots) return fail(AIM_EINVAL, "%s: slot %u is outside 0..%u", fn, slot, m->p.slots - 1);
     if (n_reads > m->p.max_reads) return fail(AIM_EINVAL, "%s: n_reads %u is above max_reads %u", fn, n_reads, m->p.max_reads);
     if (n_reads && (!read_len || !reads)) return fail(AIM_EINVAL, "%s: NULL read_len or reads", fn);
+    if (m->paired && (n_reads & 1u)) return fail(AIM_EINVAL, "%s: n_reads %u is odd (after aim_mapper_set_pairing reads 2m and 2m + 1 are mates)", fn, n_reads);
     MapperSlot &s = m->slot[slot];
     if (s.in_flight) return fail(AIM_ESTATE, "%s: slot %u is in flight (aim_mapper_wait first)", fn, slot);
     HIP_TRY(hipSetDevice(m->device));
     s.n_reads = n_reads;
+    s.waited = false;                    // the views of aim_mapper_pairs end here
     if (!n_reads) {                      // a valid batch with nothing to enqueue
         s.in_flight = true;
         return AIM_OK;
@@ -515,10 +599,14 @@ int aim_mapper_submit(aim_mapper_t *m, uint32_t slot, uint32_t n_reads, const in
     if (!rc)
         rc = aim_sam_device_split(&m->ap.base, rows, d_seg_req, d_seg_tp, nullptr, d_res, d_ops, m->d_ref, m->ref_len, p.sam_options, d_sam, at<uint32_t>(m, s, B_CIGAR),
                                   p.cigar_cap, at<char>(m, s, B_MD), p.md_cap, d_cursors, d_seg, st);
+    if (!rc && m->paired) rc = submit_pairing(m, s, n_reads, st);   // rule 14c in front of the record kernel: rescue, select / apply
     if (!rc)
         rc = n_contigs ? aim_map_records_contigs_device(K, n_reads, d_seg, d_sam, d_cls, d_contig, n_contigs, m->d_contig_start, d_off,
                                                         at<aim_map_record_t>(m, s, B_RECORDS), at<void>(m, s, B_MAP_SCRATCH), kMapScratch, st)
                        : aim_map_records_device(K, n_reads, d_seg, d_sam, d_cls, d_off, at<aim_map_record_t>(m, s, B_RECORDS), at<void>(m, s, B_MAP_SCRATCH), kMapScratch, st);
+    if (!rc && m->paired)                // ... and behind it: the mate fields
+        rc = aim_map_mates_device(K, n_reads, at<aim_map_pair_t>(m, s, B_PAIRS), d_seg, d_sam, n_contigs ? d_contig : nullptr, n_contigs, m->d_contig_start, d_off,
+                                  at<aim_map_record_t>(m, s, B_RECORDS), at<aim_map_mate_t>(m, s, B_MATES), st);
     if (rc) {
         (void)hipStreamSynchronize(st);  // what was enqueued reads the pinned buffers
         return under(fn, rc);
@@ -536,6 +624,9 @@ int aim_mapper_wait(aim_mapper_t *m, uint32_t slot, aim_mapper_out_t *out)
     MapperSlot &s = m->slot[slot];
     if (!s.in_flight) return fail(AIM_ESTATE, "%s: nothing is in flight on slot %u", fn, slot);
     s.in_flight = false;
+    s.waited = true;
+    memset(&s.po, 0, sizeof s.po);
+    s.po.mates = s.h_mates; s.po.pairs = s.h_pairs;
     memset(out, 0, sizeof *out);
     out->n_reads = s.n_reads;
     out->records = s.h_records; out->rec_offsets = s.h_offsets; out->cigar = s.h_cigar; out->md = s.h_md;
@@ -545,6 +636,7 @@ int aim_mapper_wait(aim_mapper_t *m, uint32_t slot, aim_mapper_out_t *out)
     const uint32_t *d_off = at<uint32_t>(m, s, B_OFFSETS);
     // one small copy first: rec_offsets[n_reads] and the two cursors behind it; it says how much of everything else is in use
     HIP_TRY(hipMemcpyAsync(s.h_head, d_off + s.n_reads, 12, hipMemcpyDeviceToHost, s.stream));
+    if (m->paired) HIP_TRY(hipMemcpyAsync(s.h_res_head, at<char>(m, s, B_RES_CURSORS), 8, hipMemcpyDeviceToHost, s.stream));   // the rescue regions' own cursor pair
     HIP_TRY(hipStreamSynchronize(s.stream));
     out->n_records = s.h_head[0];
     out->cigar_needed = s.h_head[1]; out->md_needed = s.h_head[2];
@@ -553,7 +645,111 @@ int aim_mapper_wait(aim_mapper_t *m, uint32_t slot, aim_mapper_out_t *out)
     HIP_TRY(hipMemcpyAsync(s.h_offsets, d_off, 4ull * (s.n_reads + 1u), hipMemcpyDeviceToHost, s.stream));
     if (out->cigar_words) HIP_TRY(hipMemcpyAsync(s.h_cigar, at<char>(m, s, B_CIGAR), 4ull * out->cigar_words, hipMemcpyDeviceToHost, s.stream));
     if (out->md_bytes) HIP_TRY(hipMemcpyAsync(s.h_md, at<char>(m, s, B_MD), out->md_bytes, hipMemcpyDeviceToHost, s.stream));
+    if (m->paired) {                     // rule 14c: the second range of either buffer, the mate fields and the pairs
+        aim_mapper_pairs_out_t &po = s.po;
+        po.n_pairs = s.n_reads / 2u; po.n_records = out->n_records;
+        po.rescue_cigar_needed = s.h_res_head[0]; po.rescue_md_needed = s.h_res_head[1];
+        po.rescue_cigar_words = std::min(po.rescue_cigar_needed, m->pp.rescue_cigar_cap); po.rescue_md_bytes = std::min(po.rescue_md_needed, m->pp.rescue_md_cap);
+        if (po.rescue_cigar_words)
+            HIP_TRY(hipMemcpyAsync(s.h_cigar + m->p.cigar_cap, at<uint32_t>(m, s, B_CIGAR) + m->p.cigar_cap, 4ull * po.rescue_cigar_words, hipMemcpyDeviceToHost, s.stream));
+        if (po.rescue_md_bytes) HIP_TRY(hipMemcpyAsync(s.h_md + m->p.md_cap, at<char>(m, s, B_MD) + m->p.md_cap, po.rescue_md_bytes, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(hipMemcpyAsync(s.h_mates, at<char>(m, s, B_MATES), sizeof(aim_map_mate_t) * (size_t)po.n_records, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(hipMemcpyAsync(s.h_pairs, at<char>(m, s, B_PAIRS), sizeof(aim_map_pair_t) * (size_t)po.n_pairs, hipMemcpyDeviceToHost, s.stream));
+    }
     HIP_TRY(hipStreamSynchronize(s.stream));
+    return AIM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// paired-end reads (AIM_FEATURE_PAIRED; rule 14c in aim_hip.h, the kernels in pair.hpp, the stateless entry points in capi_pair.hip)
+// ---------------------------------------------------------------------------
+int aim_mapper_pairing_device_bytes(const aim_mapper_params_t *params, const aim_map_pair_params_t *pp, uint64_t *bytes)
+{
+    const char *fn = "aim_mapper_pairing_device_bytes";
+    if (const int rc = check_mapper_params(fn, params, 0)) return rc;
+    if (const int rc = check_pairing(fn, *params, pp)) return rc;
+    if (!bytes) return fail(AIM_EINVAL, "%s: bytes is NULL", fn);
+    const aim_endsfree_params_t ap = align_params(*params), rap = rescue_params(*params, *pp);
+    const size_t as = aim_scratch_bytes(&ap.base, (uint32_t)((uint64_t)params->max_reads * (uint64_t)params->seed.max_cands));
+    const size_t rsb = (pp->options & AIM_PAIR_RESCUE) ? aim_scratch_bytes(&rap.base, params->max_reads) : 0;
+    if (!as || ((pp->options & AIM_PAIR_RESCUE) && !rsb)) return under(fn, AIM_ENOMEM);
+    // (the difference is the same for either kind of mapper)
+    *bytes = (uint64_t)params->slots * (slot_layout(*params, as, false, pp, rsb).total - slot_layout(*params, as, false).total);
+    return AIM_OK;
+}
+
+int aim_mapper_set_pairing(aim_mapper_t *m, const aim_map_pair_params_t *pp)
+{
+    const char *fn = "aim_mapper_set_pairing";
+    if (!m) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
+    if (const int rc = check_pairing(fn, m->p, pp)) return rc;
+    if (m->paired) return fail(AIM_ESTATE, "%s: pairing is already set", fn);
+    for (uint32_t i = 0; i < m->p.slots; ++i)
+        if (m->slot[i].in_flight) return fail(AIM_ESTATE, "%s: slot %u is in flight (aim_mapper_wait first)", fn, i);
+    HIP_TRY(hipSetDevice(m->device));
+    const aim_mapper_params_t &p = m->p;
+    const uint64_t N = p.max_reads, K = (uint64_t)p.seed.max_cands;
+    const aim_endsfree_params_t rap = rescue_params(p, *pp);
+    size_t rsb = 0;
+    if (pp->options & AIM_PAIR_RESCUE) {
+        rsb = aim_scratch_bytes(&rap.base, p.max_reads);
+        if (!rsb) return under(fn, AIM_ENOMEM);
+    }
+    const SlotLayout L = slot_layout(p, m->align_scratch, !m->starts.empty(), pp, rsb);
+    // Each slot moves to buffers of the new layout; nothing is in flight and no slot keeps state between batches. The new buffers come
+    // first, so a failure leaves the mapper as it was.
+    char *dev[AIM_MAPPER_MAX_SLOTS] = {};
+    void *host[AIM_MAPPER_MAX_SLOTS][5] = {};
+    int rc = AIM_OK;
+    auto make = [&]() -> int {
+        for (uint32_t i = 0; i < p.slots; ++i) {
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dev[i]), (size_t)L.total));
+            HIP_TRY(hipMemset(dev[i], 0, (size_t)L.total));
+            const uint64_t sizes[5] = {4ull * ((uint64_t)p.cigar_cap + pp->rescue_cigar_cap), (uint64_t)p.md_cap + pp->rescue_md_cap, sizeof(aim_map_mate_t) * N * K,
+                                       sizeof(aim_map_pair_t) * ((N + 1) / 2), 16};
+            for (int j = 0; j < 5; ++j)
+                if (const int r = pinned(&host[i][j], sizes[j])) return r;
+        }
+        HIP_TRY(hipDeviceSynchronize());
+        return AIM_OK;
+    };
+    if ((rc = make())) {
+        const std::string was = aim_last_error();
+        for (uint32_t i = 0; i < p.slots; ++i) {
+            if (dev[i]) (void)hipFree(dev[i]);
+            for (void *h : host[i])
+                if (h) (void)hipHostFree(h);
+        }
+        return fail(rc, "%s: %s", fn, was.c_str());
+    }
+    for (uint32_t i = 0; i < p.slots; ++i) {
+        MapperSlot &s = m->slot[i];
+        (void)hipFree(s.dev);
+        (void)hipHostFree(s.h_cigar);
+        (void)hipHostFree(s.h_md);
+        s.dev = dev[i];
+        s.h_cigar = static_cast<uint32_t *>(host[i][0]); s.h_md = static_cast<char *>(host[i][1]);
+        s.h_mates = static_cast<aim_map_mate_t *>(host[i][2]); s.h_pairs = static_cast<aim_map_pair_t *>(host[i][3]); s.h_res_head = static_cast<uint32_t *>(host[i][4]);
+        s.waited = false;
+    }
+    m->L = L;
+    m->pp = *pp;
+    m->rap = rap;
+    m->rescue_scratch = rsb;
+    m->paired = true;
+    return AIM_OK;
+}
+
+int aim_mapper_pairs(aim_mapper_t *m, uint32_t slot, aim_mapper_pairs_out_t *out)
+{
+    const char *fn = "aim_mapper_pairs";
+    if (!m) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
+    if (slot >= m->p.slots) return fail(AIM_EINVAL, "%s: slot %u is outside 0..%u", fn, slot, m->p.slots - 1);
+    if (!out) return fail(AIM_EINVAL, "%s: out is NULL", fn);
+    if (!m->paired) return fail(AIM_ESTATE, "%s: aim_mapper_set_pairing was not called", fn);
+    const MapperSlot &s = m->slot[slot];
+    if (s.in_flight || !s.waited) return fail(AIM_ESTATE, "%s: slot %u has no batch waited for (aim_mapper_wait first)", fn, slot);
+    *out = s.po;
     return AIM_OK;
 }
 

@@ -759,6 +759,43 @@ def mapper_device_bytes_contigs(mp, lens):
     return b.value
 
 
+def pair_params(min_span, max_span, unpaired_penalty=0, rescue=True, rescue_size=0, rescue_cigar_cap=0, rescue_md_cap=0):
+    """aim_map_pair_params_t (rule 14c): the span bounds in aligned coordinates, the penalty of the unpaired choice, and -- with rescue --
+    the read_size of the rescue alignment (a multiple of 8, at least max_span - min_span + read_size) and the mapper's rescue regions."""
+    return capi.MapPairParams(int(min_span), int(max_span), int(unpaired_penalty), capi.PAIR_RESCUE if rescue else 0, int(rescue_size), int(rescue_cigar_cap),
+                              int(rescue_md_cap), 0)
+
+
+def pair_rescue_rows_device(pp, K, read_size, ref_len, n_reads, d_read_len, d_reads, d_seg, d_sam, d_res_requests, d_res_text_pos, d_res_patterns, d_contig=None,
+                            n_contigs=0, d_contig_start=None, d_contig_len=None, stream=None):
+    """aim_pair_rescue_rows_device on device pointers (integers, e.g. torch's data_ptr(); None = NULL): rule 14c's rescue row per read --
+    aim_request_t, text_pos and the pattern row at stride pp.rescue_size -- from the slot arrays behind sam_device_split. d_contig (with
+    the contig table) for a reference of several sequences. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_pair_rescue_rows_device(C.byref(pp), int(K), int(read_size), int(ref_len), int(n_contigs), d_contig_start, d_contig_len, int(n_reads),
+                                                       d_read_len, d_reads, d_seg, d_sam, d_contig, d_res_requests, d_res_text_pos, d_res_patterns, stream))
+
+
+def pair_select_device(pp, K, read_size, n_reads, d_read_len, d_seg, d_sam, d_class, d_res_sam, cigar_base, md_base, d_pairs, d_contig=None, stream=None):
+    """aim_pair_select_device: rule 14c's choice per read pair -> d_pairs (capi.MAP_PAIR_DTYPE per pair), and apply: a chosen rescue row
+    (d_res_sam, the sam_device records of the rescue rows) folded into d_seg / d_sam / d_class / d_contig in place. Only enqueues work."""
+    capi.check(capi.load().aim_pair_select_device(C.byref(pp), int(K), int(read_size), int(n_reads), d_read_len, d_seg, d_sam, d_class, d_contig, d_res_sam,
+                                                  int(cigar_base), int(md_base), d_pairs, stream))
+
+
+def map_mates_device(K, n_reads, d_pairs, d_seg, d_sam, d_rec_offsets, d_records, d_mates, d_contig=None, n_contigs=0, d_contig_start=None, stream=None):
+    """aim_map_mates_device, behind map_records_device / map_records_contigs_device: the paired flag bits into d_records and one
+    capi.MAP_MATE_DTYPE per record into d_mates (room for n_reads * K). Only enqueues work."""
+    capi.check(capi.load().aim_map_mates_device(int(K), int(n_reads), d_pairs, d_seg, d_sam, d_contig, int(n_contigs), d_contig_start, d_rec_offsets, d_records,
+                                                d_mates, stream))
+
+
+def mapper_pairing_device_bytes(mp, pp):
+    """aim_mapper_pairing_device_bytes: the device memory Mapper.set_pairing adds, over all slots."""
+    b = C.c_uint64()
+    capi.check(capi.load().aim_mapper_pairing_device_bytes(C.byref(mp), C.byref(pp), C.byref(b)))
+    return b.value
+
+
 def mapper_params(sp, max_reads, max_score, mismatch=3, gap_o=4, gap_e=1, match=0, max_hits=0, mask_q8=capi.CHAIN_MASK_DEFAULT, extend=None, sam_options=0,
                   slots=2, cigar_cap=None, md_cap=None):
     """aim_mapper_params_t from the seed parameters of seed_params(..., w=...) (K is sp.max_cands, read_size sp.read_size), the batch
@@ -778,11 +815,25 @@ def mapper_device_bytes(mp, ref_len):
     return b.value
 
 
+def _view(addr, count, dtype):
+    """A numpy view of `count` items of `dtype` at a host address (an empty array for none)."""
+    if not count:
+        return np.zeros(0, dtype=dtype)
+    buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(addr)
+    return np.frombuffer(buf, dtype=dtype)
+
+
 class Mapper:
     """aim_mapper_t: the reference, its minimizer index and per-slot buffers and streams on one device. submit(slot, read_len, reads)
     copies a batch in and enqueues every stage; wait(slot) returns a dict of numpy views of the slot's pinned buffers -- "records"
     (capi.MAP_RECORD_DTYPE), "rec_offsets" (uint32[n_reads + 1]), "cigar" (uint32 words) and "md" (uint8) -- which stay valid until the
-    slot's next submit, plus "cigar_needed" / "md_needed"."""
+    slot's next submit, plus "cigar_needed" / "md_needed". After set_pairing(pp) (rule 14c) reads 2m and 2m + 1 are mates: wait's dict
+    gains what pairs(slot) returns, and where a rescue wrote something "cigar" / "md" reach to the end of the rescue region (which starts
+    at cigar_cap / md_cap), so that a rescued record's cigar_offset / md_offset index them like any other. Such a widened view spans the
+    gap between the main range's end (cigar_needed / md_needed, at most the capacity) and the region's start: that gap is never copied
+    and holds whatever the pinned buffer held -- index the arrays by a record's offsets, do not hash or compare them whole. "rescue_cigar"
+    and "rescue_md" are the rescue ranges alone, as views of their own."""
+    pairing = None
 
     def __init__(self, mp, reference, device=0):
         self.lib = capi.load()
@@ -823,6 +874,20 @@ class Mapper:
     def __exit__(self, *exc):
         self.close()
 
+    def set_pairing(self, pp):
+        """aim_mapper_set_pairing: once, while no slot is in flight."""
+        capi.check(self.lib.aim_mapper_set_pairing(self.handle, C.byref(pp)))
+        self.pairing = pp
+
+    def pairs(self, slot):
+        """aim_mapper_pairs after wait(slot): "mates" (capi.MAP_MATE_DTYPE per record), "pairs" (capi.MAP_PAIR_DTYPE per read pair) and the
+        rescue regions' "rescue_cigar_words" / "rescue_md_bytes" (copied) and "rescue_cigar_needed" / "rescue_md_needed"."""
+        po = capi.MapperPairsOut()
+        capi.check(self.lib.aim_mapper_pairs(self.handle, int(slot), C.byref(po)))
+        return {"mates": _view(po.mates, po.n_records, capi.MAP_MATE_DTYPE), "pairs": _view(po.pairs, po.n_pairs, capi.MAP_PAIR_DTYPE),
+                "rescue_cigar_words": po.rescue_cigar_words, "rescue_md_bytes": po.rescue_md_bytes, "rescue_cigar_needed": po.rescue_cigar_needed,
+                "rescue_md_needed": po.rescue_md_needed}
+
     def submit(self, slot, read_len, reads):
         rl = np.ascontiguousarray(read_len, dtype=np.int32)
         rows = np.ascontiguousarray(reads, dtype=np.uint8)
@@ -834,15 +899,19 @@ class Mapper:
     def wait(self, slot):
         out = capi.MapperOut()
         capi.check(self.lib.aim_mapper_wait(self.handle, int(slot), C.byref(out)))
-
-        def view(addr, count, dtype):
-            if not count:
-                return np.zeros(0, dtype=dtype)
-            buf = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(addr)
-            return np.frombuffer(buf, dtype=dtype)
-        return {"n_reads": out.n_reads, "records": view(out.records, out.n_records, capi.MAP_RECORD_DTYPE),
-                "rec_offsets": view(out.rec_offsets, out.n_reads + 1, np.uint32), "cigar": view(out.cigar, out.cigar_words, np.uint32),
-                "md": view(out.md, out.md_bytes, np.uint8), "cigar_needed": out.cigar_needed, "md_needed": out.md_needed}
+        view = _view
+        res = {"n_reads": out.n_reads, "records": view(out.records, out.n_records, capi.MAP_RECORD_DTYPE),
+               "rec_offsets": view(out.rec_offsets, out.n_reads + 1, np.uint32), "cigar": view(out.cigar, out.cigar_words, np.uint32),
+               "md": view(out.md, out.md_bytes, np.uint8), "cigar_needed": out.cigar_needed, "md_needed": out.md_needed}
+        if self.pairing is not None:
+            res.update(self.pairs(slot))
+            if res["rescue_cigar_words"]:
+                res["cigar"] = view(out.cigar, self.params.cigar_cap + res["rescue_cigar_words"], np.uint32)
+            if res["rescue_md_bytes"]:
+                res["md"] = view(out.md, self.params.md_cap + res["rescue_md_bytes"], np.uint8)
+            res["rescue_cigar"] = res["cigar"][self.params.cigar_cap:] if res["rescue_cigar_words"] else np.zeros(0, dtype=np.uint32)
+            res["rescue_md"] = res["md"][self.params.md_cap:] if res["rescue_md_bytes"] else np.zeros(0, dtype=np.uint8)
+        return res
 
 
 def seed_candidates(sp, index, ref_len, read_len, reads, device="cuda:0", chain=False, max_hits=None):

@@ -66,6 +66,23 @@ def read_reads(path):
     raise ValueError("%s: neither FASTA ('>') nor FASTQ ('@')" % path)
 
 
+def mate_name(name):
+    """A read's name without a trailing /1 or /2."""
+    return name[:-2] if name.endswith(("/1", "/2")) else name
+
+
+def pair_reads(reads1, reads2):
+    """The two files of a paired-end run as one list, mates next to each other (reads 2m and 2m + 1), under the name they share."""
+    if len(reads1) != len(reads2):
+        raise ValueError("--reads holds %d reads and --reads2 %d" % (len(reads1), len(reads2)))
+    out = []
+    for i, (a, b) in enumerate(zip(reads1, reads2)):
+        if mate_name(a[0]) != mate_name(b[0]):
+            raise ValueError("read %d: the mates' names differ: %r and %r" % (i, a[0], b[0]))
+        out += [(mate_name(a[0]),) + tuple(a[1:]), (mate_name(b[0]),) + tuple(b[1:])]
+    return out
+
+
 def load_reference(path):
     """(name, upper-cased uint8 array) of a FASTA with exactly one sequence; ValueError for none or several."""
     seqs = read_fasta(path)
@@ -89,6 +106,12 @@ def parser():
     ap = argparse.ArgumentParser(prog="python -m aim_amd.map", description=__doc__.split("\n\n")[1])
     ap.add_argument("--ref", required=True)
     ap.add_argument("--reads", required=True)
+    ap.add_argument("--reads2", default=None, help="the second mates, read by read (paired-end: rule 14c); names agree after a trailing /1 or /2")
+    ap.add_argument("--min-span", type=int, default=0, help="paired-end: the smallest span of a proper pair, from the forward start to the reverse end")
+    ap.add_argument("--max-span", type=int, default=1000, help="paired-end: the largest span of a proper pair")
+    ap.add_argument("--unpaired-penalty", type=int, default=17, help="paired-end: what the two best single placements pay against a proper pair")
+    ap.add_argument("--rescue-size", type=int, default=None, help="paired-end: row size of the rescue alignment (default: max_span - min_span + read_size, rounded up to 8)")
+    ap.add_argument("--no-rescue", action="store_true", help="paired-end: pair what was mapped, rescue nothing")
     ap.add_argument("-o", "--out", required=True)
     ap.add_argument("--contigs", action="store_true", help="map against every sequence of a multi-sequence FASTA (a contig table)")
     ap.add_argument("--device", type=int, default=0)
@@ -145,11 +168,15 @@ def main(argv=None):
             rname, ref = load_reference(args.ref)
             ref_lens = len(ref)
         reads = read_reads(args.reads)
+        if args.reads2:
+            reads = pair_reads(reads, read_reads(args.reads2))
+            if args.batch % 2:
+                raise ValueError("--batch %d must be even with --reads2 (mates share a batch)" % args.batch)
     except (OSError, ValueError) as e:
         hint = "; --contigs maps against all of them" if not args.contigs and "contig table" in str(e) else ""
         print("aim_amd.map: %s%s" % (e, hint), file=sys.stderr)
         return 2
-    from . import engine, samout
+    from . import capi, engine, samout
     longest = max([len(s) for _, s, _ in reads] + [1])
     read_size = args.read_size if args.read_size is not None else engine.round_up_8(longest)
     if longest > read_size:
@@ -163,6 +190,15 @@ def main(argv=None):
     n_lines = 0
     make = engine.Mapper.from_contigs if args.contigs else engine.Mapper
     with open(args.out, "w") as fh, make(mp, ref, device=args.device) as m:
+        if args.reads2:
+            span = args.max_span - args.min_span + read_size
+            try:
+                m.set_pairing(engine.pair_params(args.min_span, args.max_span, args.unpaired_penalty, rescue=not args.no_rescue,
+                                                 rescue_size=args.rescue_size if args.rescue_size is not None else engine.round_up_8(max(span, read_size)),
+                                                 rescue_cigar_cap=args.batch * 64, rescue_md_cap=args.batch * 256))
+            except capi.AimError as e:
+                print("aim_amd.map: %s" % e, file=sys.stderr)
+                return 2
         fh.write(samout.header(rname, ref_lens, command_line=" ".join(["python -m aim_amd.map"] + list(sys.argv[1:] if argv is None else argv))))
         pending = {}                                  # slot -> the batch in flight on it
 

@@ -4,7 +4,12 @@ into the library is the CIGAR formatter aim_sam_format_cigar.
 One line per record, in record order. Every line of a read carries the read's full SEQ (reverse-complemented on strand 1) with soft
 clips, as `minimap2 -Y` writes supplementary lines: there are no hard clips. Tags: NM:i, MD:Z, AS:i and, on reads with more than one
 record, SA:Z. AS is the negated alignment cost (the library's scores are penalties: 0 is a perfect match), so a greater AS is a better
-alignment. MAPQ is the record's own: the chain MAPQ of rule 8c, this project's figure."""
+alignment. MAPQ is the record's own: the chain MAPQ of rule 8c, this project's figure.
+
+A result of a mapper with pairing (rule 14c: `out` carries "mates", one aim_map_mate_t per record) gives paired lines: FLAG is the
+record's own, which already holds 0x1 / 0x2 / 0x8 / 0x20 / 0x40 / 0x80; RNEXT is `=` on the record's own contig, PNEXT 1-based and TLEN
+signed, all from the mate fields; an unmapped read whose mate is mapped is written at its mate's RNAME and POS, as the SAM
+specification recommends; with both reads unmapped RNAME / RNEXT are `*` and the positions 0. SA is written as before."""
 import numpy as np
 
 from . import capi, engine
@@ -51,6 +56,8 @@ def record_lines(out, names, reads, read_len, rname, quals=None):
     quals[r] (optional) its quality string. rname is the reference's name, or the list of contig names for the records of
     Mapper.from_contigs, whose pad says which contig pos is local to; an SA entry carries its own record's contig."""
     recs, off, cigar, md = out["records"], out["rec_offsets"], out["cigar"], np.asarray(out["md"], dtype=np.uint8)
+    mates = out.get("mates") if isinstance(out, dict) else None
+    contig_name = lambda c: rname if isinstance(rname, str) else rname[int(c)]
     lines = []
     for r in range(len(off) - 1):
         group = recs[int(off[r]):int(off[r + 1])]
@@ -62,11 +69,19 @@ def record_lines(out, names, reads, read_len, rname, quals=None):
         for j, rec in enumerate(group):
             s = rec["sam"]
             flags = int(s["flags"])
+            rnext, pnext, tlen = "*", "0", "0"
+            if mates is not None:                     # rule 14c's mate fields; with an unmapped mate they are the record's own place
+                mt = mates[int(off[r]) + j]
+                if not (flags & capi.SAM_UNMAPPED and flags & 0x8):
+                    rnext, pnext, tlen = "=", str(int(mt["mate_pos"]) + 1), str(int(mt["tlen"]))
+                    if not flags & (capi.SAM_UNMAPPED | 0x8) and not isinstance(rname, str) and int(mt["mate_contig"]) != int(s["pad"]):
+                        rnext = contig_name(mt["mate_contig"])
             if flags & capi.SAM_UNMAPPED:
-                lines.append("\t".join([names[r], "4", "*", "0", "0", "*", "*", "0", "0", seq.decode("latin-1") or "*", qual or "*"]))
+                place = ["*", "0"] if mates is None or flags & 0x8 else [contig_name(mt["mate_contig"]), pnext]
+                lines.append("\t".join([names[r], str(flags) if mates is not None else "4"] + place + ["0", "*", rnext, pnext, "0", seq.decode("latin-1") or "*", qual or "*"]))
                 continue
             rev = bool(flags & capi.SAM_REVERSE)
-            fields = [names[r], str(flags), _rname(rname, rec), str(int(s["pos"]) + 1), str(int(rec["mapq"])), _cigar(rec, cigar), "*", "0", "0",
+            fields = [names[r], str(flags), _rname(rname, rec), str(int(s["pos"]) + 1), str(int(rec["mapq"])), _cigar(rec, cigar), rnext, pnext, tlen,
                       (revcomp(seq) if rev else seq).decode("latin-1") or "*", (qual[::-1] if rev else qual) if qual else "*", "NM:i:%d" % int(s["nm"])]
             if int(s["md_len"]) and not int(s["status"]) & capi.SAM_OVERFLOW:
                 o = int(s["md_offset"])

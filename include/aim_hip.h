@@ -349,6 +349,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_EXTEND 0x40000u /* segment extension: aim_extend_segments_device / aim_extend_kernel_names exist */
 #define AIM_FEATURE_MAPPER 0x80000u /* rule 12c and the mapper object: aim_map_records_device / aim_mapper_create / aim_mapper_submit / aim_mapper_wait exist */
 #define AIM_FEATURE_CONTIGS 0x100000u /* rule 13c, references of several sequences: aim_contigs_layout / aim_contig_clip_device / aim_map_records_contigs_device / aim_mapper_create_contigs exist */
+#define AIM_FEATURE_PAIRED 0x200000u /* rule 14c, paired-end reads: aim_pair_rescue_rows_device / aim_pair_select_device / aim_map_mates_device / aim_mapper_set_pairing / aim_mapper_pairs exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -1135,8 +1136,9 @@ const char *aim_extend_kernel_names(void);
  *       AIM_SAM_OVERFLOW. n_reads = 0 is a valid batch: no records, rec_offsets = {0}.
  *       The slots are independent: batches on different slots overlap, and a slot's result does not depend on what ran before it.
  * aim_mapper_kernel_names: "map_count_kernel,map_records_kernel".
- * Not in this version: a mapper stage inside aim_set_submit or host.c, more than one device per mapper, paired-end reads through the mapper
- * (references of more than one sequence: rule 13c and aim_mapper_create_contigs below), hard clips, trimming the overlap of neighbouring segments, packed
+ * Not in this version: a mapper stage inside aim_set_submit or host.c, more than one device per mapper
+ * (references of more than one sequence: rule 13c and aim_mapper_create_contigs below; paired-end reads: rule 14c and
+ * aim_mapper_set_pairing below), hard clips, trimming the overlap of neighbouring segments, packed
  * read rows, MAPQ from alignment runner-ups. The SA tag is text and is written on the host (aim_amd/samout.py) from the records of a
  * read. Check aim_features() & AIM_FEATURE_MAPPER first. */
 typedef struct aim_map_record {
@@ -1236,8 +1238,8 @@ int aim_mapper_free(aim_mapper_t *mapper);
  *       every check of aim_mapper_device_bytes / aim_mapper_create on the laid-out ref_len, then a NULL seqs or seqs[c].
  * aim_contig_kernel_names: "contig_clip_kernel,map_records_contig_kernel".
  * Not in this version: an extension (rule 11c) that stops at a contig's edge -- it may claim a few read bases against the spacer,
- * which come back as soft clip --, chains confined to one contig inside the chain kernels, paired-end reads, a contig stage inside
- * aim_set_submit or host.c. Check aim_features() & AIM_FEATURE_CONTIGS first. */
+ * which come back as soft clip --, chains confined to one contig inside the chain kernels, a contig stage inside
+ * aim_set_submit or host.c (paired-end reads: rule 14c below). Check aim_features() & AIM_FEATURE_CONTIGS first. */
 #define AIM_CONTIG_MAX (1u << 20)
 #define AIM_CONTIG_NONE 0xFFFFFFFFu
 #define AIM_CONTIG_SPACER(band) ((uint32_t)(band) + 64u)
@@ -1258,6 +1260,140 @@ int aim_mapper_device_bytes_contigs(const aim_mapper_params_t *params, uint32_t 
 int aim_mapper_create_contigs(const aim_mapper_params_t *params, int device, uint32_t n_contigs, const char *const *seqs, const uint32_t *lens,
                               aim_mapper_t **mapper);
 int aim_mapper_contigs(const aim_mapper_t *mapper, uint32_t *n_contigs, const uint32_t **starts, const uint32_t **lens);
+
+/* ---- paired-end reads (AIM_FEATURE_PAIRED): pairing from aligned coordinates, mate rescue, the mate fields of a record -----------
+ * Reads 2m and 2m + 1 of a batch are mates, so n_reads is even. Rule 14c works on the slot arrays as they stand after
+ * aim_sam_device_split -- d_seg, d_sam, d_class, d_read_len, and d_contig (NULL for one sequence) -- between that stage and the record
+ * kernel, and once more behind the record kernel. Mapped slot and representative are rule 12c's. Positions are the global ones of
+ * d_sam; the record kernel still makes them contig-local. All arithmetic is signed 64-bit; everything is deterministic and
+ * independent of the grid and of the AIM_DEBUG_POISON_* knobs.
+ *   14c. Proper combination (i, j). Slot i of read 2m and slot j of read 2m + 1 are both mapped, lie on the same contig (d_contig
+ *       equal, when given) and differ in AIM_SAM_REVERSE; with f the forward and r the reverse of the two records, pos_f <= pos_r and
+ *       min_span <= pos_r + ref_span_r - pos_f <= max_span. That figure is the combination's span. Its cost is score_i + score_j,
+ *       summed in 64 bits and clamped to INT32_MAX - 1.
+ *       Rescue rows (aim_pair_rescue_rows_device). One row per read b, with mate a = b ^ 1. The rescue is TRIED when options has
+ *       AIM_PAIR_RESCUE, read a has a mapped slot, no proper combination exists among the mapped slots of the two reads and
+ *       L = min(max(d_read_len[b], 0), read_size) > 0. The anchor A is a's representative with P = pos, S = ref_span and the bounds
+ *       [c_lo, c_hi) of its contig d_contig[A] (for one sequence, or a d_contig[A] outside the table, [0, ref_len)).
+ *         A forward: lo = max(P + min_span - L, c_lo), hi = min(P + max_span, c_hi), and the window's strand bit is set.
+ *         A reverse: with E = P + S, lo = max(E - max_span, c_lo), hi = min(E - min_span + L, c_hi), strand 0.
+ *       If hi - lo >= L the row is d_res_requests[b] = {pattern_len L, text_len hi - lo, 0, idx b} with d_res_text_pos[b] =
+ *       lo | strand bit, and the first read_size bytes of pattern row b (d_res_patterns + b * rescue_size) become read b's row; the
+ *       bytes behind them are never written and never interpreted. Otherwise, and for every read that is not tried, the row is
+ *       the EMPTY ROW {0, 0, 0, b} with text_pos 0, and its pattern row is not written. An empty row aligns to an empty ops range, so
+ *       aim_sam_device gives it AIM_SAM_UNMAPPED with pos 0 (the unmapped rule of AIM_FLAG_SAM_FIELDS): rows that were not tried
+ *       need no mark of their own. hi - lo <= max_span - min_span + read_size <= rescue_size.
+ *       The rows are aligned by aim_align_device_ref with AIM_FLAG_BACKTRACE | AIM_FLAG_ENDSFREE | AIM_FLAG_REF_TEXTS, read_size =
+ *       rescue_size, pattern free ends 0 / 0 and text free ends rescue_size / rescue_size, and aim_sam_device turns them into
+ *       d_res_sam[n_reads] with CIGAR / MD buffers of their own. No alignment kernel is added.
+ *       Choice (aim_pair_select_device). The combinations run over the mapped slots plus index K for a read's rescue row where that
+ *       row was tried and d_res_sam[b] is not AIM_SAM_UNMAPPED (AIM_SAM_OVERFLOW counts as mapped, as in rule 12c). The rescue row's
+ *       contig is its anchor's. (K, K) is excluded. The proper combination of lowest cost wins, ties going to the lowest i and then
+ *       the lowest j; n_best counts the proper combinations of that cost and second_sum is the lowest cost among the other
+ *       proper combinations (with a tie the cost itself; INT32_MAX: none), as in aim_mate_t. The unpaired cost is score(rep_a) + score(rep_b) + unpaired_penalty, clamped alike;
+ *       it exists only when both reads have a mapped slot. The proper combination is taken if there is no unpaired cost or its
+ *       cost <= the unpaired cost.
+ *       aim_map_pair_t. Taken: slot[] = the two chosen slots, 2m * K + i and (2m + 1) * K + j, so r * K + K names read r's rescue
+ *       row; score_sum, second_sum and n_best as above; span; flags has AIM_PAIR_PROPER, plus AIM_PAIR_RESCUED_A / _B where index
+ *       K was chosen for read 2m / 2m + 1. Not taken: slot[] = the representatives (UINT32_MAX: the read has no mapped slot), n_best
+ *       0, span 0, score_sum = the unpaired cost and second_sum = the best proper cost or INT32_MAX; without an unpaired cost both
+ *       are INT32_MAX. AIM_PAIR_RESCUE_TRIED_A / _B say for which read the rescue was tried, taken or not.
+ *       Apply (inside aim_pair_select_device). Where read b's rescue row is in the combination taken, it is folded into the slot
+ *       arrays in place, so rules 12c / 13c run unchanged behind it: d_sam[b * K] = d_res_sam[b] with cigar_offset += cigar_base and
+ *       md_offset += md_base; d_seg[b * K] = {0, L, L, AIM_SEG_VALID | AIM_SEG_LEFT_OPEN | AIM_SEG_RIGHT_OPEN, 0}; b's other slots
+ *       lose AIM_SEG_VALID and keep every other bit; d_contig[b * K] = the anchor's contig (when d_contig is given); the mapq byte
+ *       of d_class[b * K] becomes that of the anchor's slot. The placement a rescued read had before -- a discordant one, by the
+ *       condition for trying -- is dropped: it gives no record. Every other byte of the slot arrays stays.
+ *       Mate fields (aim_map_mates_device). Runs behind aim_map_records_device / aim_map_records_contigs_device on the same slot
+ *       arrays, one record per lane. A record of read r takes its mate's REFERENCE RECORD: the mate's chosen slot if the pair is
+ *       proper (a chosen rescue row lies in slot r * K since apply), else the mate's representative. d_records[..].sam.flags gains
+ *       0x1 always, 0x40 for even r and 0x80 for odd r, 0x8 when the mate has no mapped slot, 0x20 when the mate's reference
+ *       record has AIM_SAM_REVERSE, and 0x2 on the records of the two chosen slots of a proper pair. aim_map_mate_t[rec]:
+ *       mate_pos and mate_contig are the reference record's pos and contig, in the record's own convention (with d_contig:
+ *       pos - starts[c] and c; for one sequence the global pos and 0); tlen is +min(span, INT32_MAX) on the forward chosen record of a
+ *       proper pair, minus that on the reverse one and 0 everywhere else. With an unmapped mate, mate_pos / mate_contig are the
+ *       record's own sam.pos / sam.pad (0 for one sequence); with both reads unmapped they are 0 / AIM_CONTIG_NONE (0 / 0 for one
+ *       sequence). No other byte of a record changes.
+ *   The three entry points only enqueue work on hip_stream and allocate nothing: pair_rescue_rows_kernel, pair_select_kernel and
+ *       map_mates_kernel (csrc/pair.hpp); the first two give a read pair 4, 8 or 16 lanes by K. No LDS, no scratch memory, no atomics.
+ *       d_sam, d_res_sam, d_res_requests, d_pairs, d_records and d_mates are 16-byte aligned, d_reads, d_res_patterns, d_seg, d_class
+ *       and d_res_text_pos 8-byte. d_res_sam may be NULL without AIM_PAIR_RESCUE. n_reads = 0 enqueues nothing.
+ *       AIM_EINVAL under the entry point's name, before any device query: a NULL params; unknown option bits; an odd n_reads; K
+ *       outside 1..AIM_SEED_MAX_CANDS; n_reads * (K + 1) >= 2^32; min_span < 0, max_span < min_span or max_span >= 2^62; a negative
+ *       unpaired_penalty; a read_size that is not a positive multiple of 8 up to AIM_SEED_LONG_MAX_READ_SIZE; with AIM_PAIR_RESCUE (and
+ *       always from aim_pair_rescue_rows_device) a rescue_size that is not a multiple of 8, rescue_size < read_size or
+ *       max_span - min_span + read_size > rescue_size; ref_len 0 or above AIM_SEED_MAX_REF_LEN and, with d_contig, n_contigs outside
+ *       1..AIM_CONTIG_MAX or a NULL table; a NULL buffer with n_reads > 0; a buffer that breaks its alignment (the message names it).
+ *   Mapper. aim_mapper_set_pairing(m, &pp) switches rule 14c on for a mapper of either kind. It is legal once and only while no
+ *       slot is in flight (AIM_ESTATE otherwise); it allocates the extra per-slot buffers -- aim_mapper_pairing_device_bytes says how
+ *       much device memory that is, for all slots -- and moves each slot's CIGAR and MD buffers to ones that hold the rescue regions
+ *       behind the main ones: cigar_base = cigar_cap, md_base = md_cap, rescue_cigar_cap words and rescue_md_cap bytes, in the same
+ *       device and pinned buffers, so out->cigar[cigar_offset] and out->md[md_offset] address a rescued record like any other.
+ *       Its refusals are the ones above with K and read_size the mapper's, then the alignment's parameter rules at read_size =
+ *       rescue_size, then (cigar_cap + rescue_cigar_cap) or (md_cap + rescue_md_cap) >= 2^32.
+ *       aim_mapper_submit then refuses an odd n_reads and enqueues, behind aim_sam_device_split: the rescue rows, their alignment
+ *       and their records (the three only with AIM_PAIR_RESCUE), select / apply, the record kernel, the mate fields.
+ *       aim_mapper_wait copies the rescue regions by a cursor pair of their own, and mates[n_records] and pairs[n_reads / 2];
+ *       aim_mapper_out_t is unchanged (cigar_words / md_bytes / *_needed speak of the main regions). aim_mapper_pairs(m, slot, &po)
+ *       gives the views of the last batch waited for on the slot, valid until the slot's next submit; AIM_ESTATE without
+ *       aim_mapper_set_pairing, before the first wait and while the slot is in flight. A rescue region that was too small leaves
+ *       AIM_SAM_OVERFLOW on the rescued records and rescue_*_needed above rescue_*_words / _bytes.
+ *       A mapper on which aim_mapper_set_pairing was never called gives the bytes it always gave.
+ * aim_pair_kernel_names: "pair_rescue_rows_kernel,pair_select_kernel,map_mates_kernel".
+ * Not in this version: a pair MAPQ, insert-size estimation from the data, rescue against anchors other than the representative,
+ * keeping a rescued read's discordant placement as a secondary line, mates that overlap so far that pos_r < pos_f, pairing inside
+ * aim_set_submit or host.c, AIM_FLAG_TOP_HITS rows. Check aim_features() & AIM_FEATURE_PAIRED first. */
+#define AIM_PAIR_RESCUE 0x1u            /* aim_map_pair_params_t.options: try the mate rescue */
+#define AIM_PAIR_PROPER 0x1u            /* aim_map_pair_t.flags */
+#define AIM_PAIR_RESCUE_TRIED_A 0x2u
+#define AIM_PAIR_RESCUE_TRIED_B 0x4u
+#define AIM_PAIR_RESCUED_A 0x8u
+#define AIM_PAIR_RESCUED_B 0x10u
+typedef struct aim_map_pair_params {
+    int64_t min_span, max_span;    /* 0 <= min_span <= max_span < 2^62, in aligned coordinates */
+    int32_t unpaired_penalty;      /* >= 0 */
+    uint32_t options;              /* AIM_PAIR_RESCUE */
+    uint32_t rescue_size;          /* read_size of the rescue alignment: a multiple of 8, >= max_span - min_span + read_size */
+    uint32_t rescue_cigar_cap, rescue_md_cap;   /* the mapper's rescue regions, words and bytes per slot; the entry points ignore them */
+    uint32_t pad;                  /* 0 */
+} aim_map_pair_params_t; /* 40 B */
+typedef struct aim_map_pair {      /* 32 B, one per read pair m */
+    uint32_t slot[2];              /* the chosen slot of read 2m / 2m + 1; r * K + K: its rescue row; UINT32_MAX: no mapped slot */
+    int32_t score_sum;             /* cost of the choice; INT32_MAX when a read has no mapped slot and the choice is not proper */
+    int32_t second_sum;            /* lowest cost among the OTHER proper combinations; INT32_MAX when there is none */
+    uint32_t n_best;               /* proper combinations of cost score_sum (0 when the choice is not proper) */
+    uint32_t flags;                /* AIM_PAIR_* */
+    int64_t span;                  /* pos_r + ref_span_r - pos_f of the choice; 0 when it is not proper */
+} aim_map_pair_t;
+typedef struct aim_map_mate {      /* 16 B, one per record */
+    uint64_t mate_pos;
+    int32_t tlen;
+    uint32_t mate_contig;
+} aim_map_mate_t;
+typedef struct aim_mapper_pairs_out {
+    uint32_t n_pairs, n_records;
+    uint32_t rescue_cigar_words, rescue_md_bytes;     /* copied: min(needed, capacity); they start at cigar[cigar_cap] / md[md_cap] */
+    uint32_t rescue_cigar_needed, rescue_md_needed;
+    const aim_map_mate_t *mates;         /* [n_records], record by record */
+    const aim_map_pair_t *pairs;         /* [n_pairs] */
+} aim_mapper_pairs_out_t;
+int aim_pair_rescue_rows_device(const aim_map_pair_params_t *pp, uint32_t K, uint32_t read_size, uint64_t ref_len, uint32_t n_contigs,
+                                const uint32_t *d_contig_start, const uint32_t *d_contig_len, uint32_t n_reads, const int32_t *d_read_len,
+                                const char *d_reads, const aim_segment_t *d_seg, const aim_sam_t *d_sam, const uint32_t *d_contig_or_null,
+                                void *d_res_requests /* aim_request_t[n_reads] */, uint64_t *d_res_text_pos /* [n_reads] */,
+                                char *d_res_patterns /* [n_reads][rescue_size] */, void *hip_stream);
+int aim_pair_select_device(const aim_map_pair_params_t *pp, uint32_t K, uint32_t read_size, uint32_t n_reads, const int32_t *d_read_len,
+                           aim_segment_t *d_seg, aim_sam_t *d_sam, aim_chain_class_t *d_class, uint32_t *d_contig_or_null,
+                           const aim_sam_t *d_res_sam /* [n_reads]; may be NULL without AIM_PAIR_RESCUE */, uint32_t cigar_base, uint32_t md_base,
+                           aim_map_pair_t *d_pairs /* [n_reads / 2] */, void *hip_stream);
+int aim_map_mates_device(uint32_t K, uint32_t n_reads, const aim_map_pair_t *d_pairs, const aim_segment_t *d_seg, const aim_sam_t *d_sam,
+                         const uint32_t *d_contig_or_null, uint32_t n_contigs, const uint32_t *d_contig_start, const uint32_t *d_rec_offsets,
+                         aim_map_record_t *d_records, aim_map_mate_t *d_mates /* [n_reads * K] */, void *hip_stream);
+/* Comma-separated rocprofv3 kernel-trace name prefixes of the three kernels rule 14c adds. */
+const char *aim_pair_kernel_names(void);
+int aim_mapper_pairing_device_bytes(const aim_mapper_params_t *params, const aim_map_pair_params_t *pp, uint64_t *bytes);
+int aim_mapper_set_pairing(aim_mapper_t *mapper, const aim_map_pair_params_t *pp);
+int aim_mapper_pairs(aim_mapper_t *mapper, uint32_t slot, aim_mapper_pairs_out_t *out);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
