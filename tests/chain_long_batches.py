@@ -6,6 +6,8 @@ import re
 
 import numpy as np
 
+from gpu_buffers import cached
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_LEN = 1 << 18
 TANDEM = (100000, 300, 40)          # batch E's reference: a 300-base unit, 40 copies in tandem
@@ -20,14 +22,6 @@ CASE_F = (11, 1, 8, 128, 16, 2, 4, 4096, 4136)
 CASE_H = CASE_B[:4] + (150,) + CASE_B[5:]
 B_EDITS, B_DEL = 80, 200
 DUP = 40                            # bases of a tandem duplication in a read (batch E)
-
-_CACHE = {}
-
-
-def cached(key, make):
-    if key not in _CACHE:
-        _CACHE[key] = make()
-    return _CACHE[key]
 
 
 def tile():
@@ -44,12 +38,12 @@ def reference(tandem=False):
             at, unit, copies = TANDEM
             ref[at:at + unit * copies] = np.tile(ref[at:at + unit], copies)
         return ref
-    return cached(("ref", tandem), make)
+    return cached(("chain long ref", tandem), make)
 
 
 def model_index(k, w, tandem=False):
     import minimizer_model as mm
-    return cached(("index", k, w, tandem), lambda: mm.build_index(reference(tandem), k, w))
+    return cached(("chain long index", k, w, tandem), lambda: mm.build_index(reference(tandem), k, w))
 
 
 def draw(ref, seed, n, L, edits, read_size, deletion=0, every_del=2, starts=None, dups=0):
@@ -81,27 +75,27 @@ def draw(ref, seed, n, L, edits, read_size, deletion=0, every_del=2, starts=None
 
 def batch_b():
     """8 reads of 8 000 bases, 80 edits each, every second across a 200-base deletion, every third on the minus strand."""
-    return cached("B", lambda: draw(reference(), 1, 8, 8000, B_EDITS, CASE_B[8], deletion=B_DEL))
+    return cached("chain long B", lambda: draw(reference(), 1, 8, 8000, B_EDITS, CASE_B[8], deletion=B_DEL))
 
 
 def batch_c():
     """4 reads of 20 000 bases with 3 % edits, every second across a 500-base deletion."""
-    return cached("C", lambda: draw(reference(), 2, 4, 20000, 600, CASE_C[8], deletion=500))
+    return cached("chain long C", lambda: draw(reference(), 2, 4, 20000, 600, CASE_C[8], deletion=500))
 
 
 def batch_d1():
     """3 reads of 65 400 bases with 1 % edits, one on the minus strand."""
-    return cached("D1", lambda: draw(reference(), 3, 3, 65400, 654, CASE_D1[8]))
+    return cached("chain long D1", lambda: draw(reference(), 3, 3, 65400, 654, CASE_D1[8]))
 
 
 def batch_d2():
     """2 reads of 65 400 bases, one on each strand: at w = 10 the true strand holds more than 8 192 hits."""
-    return cached("D2", lambda: draw(reference(), 4, 2, 65400, 654, CASE_D2[8]))
+    return cached("chain long D2", lambda: draw(reference(), 4, 2, 65400, 654, CASE_D2[8]))
 
 
 def batch_d3():
     """One error-free read that fills a row of 65 528."""
-    return cached("D3", lambda: draw(reference(), 5, 1, 65528, 0, CASE_D3[8]))
+    return cached("chain long D3", lambda: draw(reference(), 5, 1, 65528, 0, CASE_D3[8]))
 
 
 def batch_e():
@@ -113,19 +107,19 @@ def batch_e():
         at, unit, copies = TANDEM
         starts = [at + int(rng.integers(0, unit * copies - 6000)) if r % 2 else int(rng.integers(0, at - 6000)) for r in range(6)]
         return draw(ref, 7, 6, 6000, 60, CASE_E[8], starts=starts, dups=5)
-    return cached("E", make)
+    return cached("chain long E", make)
 
 
 def batch_f():
     """6 reads of 4 000 bases with 2 % edits, every second across a 100-base deletion (w = 1: every valid k-mer is a seed)."""
-    return cached("F", lambda: draw(reference(), 8, 6, 4000, 80, CASE_F[8], deletion=100))
+    return cached("chain long F", lambda: draw(reference(), 8, 6, 4000, 80, CASE_F[8], deletion=100))
 
 
 def batch_h():
     """Reads of batch B's kind from the first and the last 100 reference bases."""
     span = 8000 + B_DEL
     starts = [0, 37, REF_LEN - 8000, REF_LEN - span - 41]       # (reads 1 and 3 lie across the deletion)
-    return cached("H", lambda: draw(reference(), 9, 4, 8000, B_EDITS, CASE_H[8], deletion=B_DEL, starts=starts))
+    return cached("chain long H", lambda: draw(reference(), 9, 4, 8000, B_EDITS, CASE_H[8], deletion=B_DEL, starts=starts))
 
 
 def case_g(w):
@@ -162,7 +156,7 @@ def batch_g():
                 read[T - 1] |= 0x20
             rows[r, :n_len], rl[r] = read, n_len
         return dict(rows=rows, rl=rl, strand=strand, lengths=np.array(lengths))
-    return cached("G", make)
+    return cached("chain long G", make)
 
 
 def expected(case, b, key, tandem=False, idx_base=0, detail=None):
@@ -175,7 +169,7 @@ def expected(case, b, key, tandem=False, idx_base=0, detail=None):
         out = clm.seed_chain_long(b["rows"], b["rl"], model_index(k, w, tandem), REF_LEN, k, w, max_occ, band, flank, min_votes, K, read_size, H,
                                   idx_base=idx_base, detail=d)
         return out, d
-    out, d = cached(("expected", case, key, idx_base), make)
+    out, d = cached(("chain long expected", case, key, idx_base), make)
     if detail is not None:
         detail += d
     return out

@@ -154,3 +154,33 @@ def seed_chain(reads, read_len, index, ref_len, k, stride, w, max_occ, band, fla
                 votes[slot] = score
                 ch[slot] = (score, n_anchors, 0, q_lo, q_hi, p_hi - p_lo)
     return req, tpos, votes, rows, ch
+
+
+# ---- what a strand's chains hold: counted by the tests that have to show their batches contain the cases ----------------------------
+def branching(pred):
+    """Anchors chosen as the predecessor of two or more successors."""
+    return int((np.bincount(pred[pred >= 0]) >= 2).sum()) if (pred >= 0).any() else 0
+
+
+def tied(a, f, pred, k, band):
+    """Anchors whose best candidate score is reached by more than one admissible predecessor."""
+    n_tied = 0
+    for i in np.nonzero(pred >= 0)[0]:
+        hits = 0
+        for j in range(max(0, i - LOOKBACK), i):
+            d_p, d_q = a[i][0] - a[j][0], a[i][1] - a[j][1]
+            if d_p > 0 and d_q > 0 and abs(d_p - d_q) <= band and f[j] + min(d_p, d_q, k) - int(cost(abs(d_p - d_q), k)) == f[i]:
+                hits += 1
+        n_tied += hits > 1
+    return n_tied
+
+
+def strand_stats(d, k, band, with_ties):
+    """What one strand's (anchors, f, pred) holds: branching anchors, links with g > 0, trees whose end is not their last anchor, and
+    (where asked: the count is quadratic) anchors with tied best predecessors."""
+    a, f, pred = d
+    diag = np.array([p - j for p, j in a], dtype=np.int64)
+    linked = np.nonzero(pred >= 0)[0]
+    root, depth, ends = trees(f, pred)
+    return dict(branching=branching(pred), gap_links=int((diag[linked] != diag[pred[linked]]).sum()),
+                end_not_last=sum(1 for t, e in ends.items() if e != np.nonzero(root == t)[0].max()), ties=tied(a, f, pred, k, band) if with_ties else 0)

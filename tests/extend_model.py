@@ -323,3 +323,16 @@ def directed_prefix(d, n, K):
 
 def directed_expected(p, d, K, read_size, ref):
     return extend_segments(p, K, read_size, len(ref), d["read_len"], d["reads"], ref, d["seg_req"], d["seg_tp"], d["seg_pat"], d["seg"])
+
+
+def inner_gaps(seg, halves, K):
+    """Per inner side of every valid segment: (slot, side, true cut - segment end), positive while the segment stops short of the cut."""
+    out = []
+    for slot in np.nonzero(seg["flags"] & sm.VALID)[0]:
+        sg = seg[slot]
+        hf = sm.half_of(halves[slot // K], int(sg["q_begin"]), int(sg["q_end"]))
+        if not int(sg["flags"]) & sm.LEFT_OPEN:
+            out.append((int(slot), 0, int(sg["q_begin"]) - hf["q_lo"]))
+        if not int(sg["flags"]) & sm.RIGHT_OPEN:
+            out.append((int(slot), 1, hf["q_hi"] - int(sg["q_end"])))
+    return out

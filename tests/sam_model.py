@@ -149,3 +149,20 @@ def rebuild_reference(read, words, md, strict=False):
                     rd, left = rd + 1, left - 1
     assert all(s[0] == "=" and s[1] == 0 for s in stream[si:]), stream[si:]
     return bytes(out), rd
+
+
+# ---- what the record tests share ------------------------------------------------------------------------------------------------
+def make_reference(seed, n=300000):
+    """Random A/C/G/T with a few N runs and lowercase stretches (the MD carries reference bytes verbatim)."""
+    rng = np.random.default_rng([seed, 0x73616D])
+    ref = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=n)].copy()
+    for _ in range(n // 20000):
+        at = int(rng.integers(0, n - 600))
+        ref[at:at + int(rng.integers(1, 12))] = ord("N")
+        at = int(rng.integers(0, n - 600))
+        ref[at:at + int(rng.integers(16, 300))] |= 0x20
+    return ref
+
+
+# hand-made ops rows: all-gap rows, alternating terminal runs, soft clips at both ends, a row longer than a wavefront's share
+HAND_ROWS = [b"IIIDDDII", b"DDDD", b"IDIDDMXMDIID", b"DDIMMXMII", b"MXXMIM", b"MMIIXM", b"DDDDMMMMMMMMXMMMMMDDD", b"M" * 300 + b"I" * 70 + b"XX" + b"D" * 9 + b"M" * 1100 + b"DD"]

@@ -14,6 +14,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "aim_hip.h")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from pipeline_batches import model_chains, short_reads  # noqa: E402
 
 # (k, stride, w, max_occ, band, flank, min_votes, K): the short-read rows the MAPQ tests run, at read_size 128
 SHORT_ROWS = [(11, 1, None, 8, 8, 8, 2, 4), (11, 1, 5, 8, 32, 8, 2, 4), (13, 1, 10, 8, 32, 8, 2, 4)]
@@ -283,24 +284,6 @@ def test_synthetic_best_holds_what_can_go_wrong():
         assert (ok[ok != ccm.NONE] < n * K).all() and (ok == ccm.NONE).sum() >= 10
 
 
-_CHAINS = {}
-
-
-def model_chains(key, row, rows, rl, read_size):
-    """tests/chain_model.py over seed_model's reference for one batch and parameter row, once."""
-    import chain_model as cm
-    import minimizer_model as mm
-    import seed_model as m
-    if "ref" not in _CHAINS:
-        _CHAINS["ref"] = m.make_reference()
-    if (key, row) not in _CHAINS:
-        ref = _CHAINS["ref"]
-        k, stride, w, max_occ, band, flank, min_votes, K = row
-        index = m.build_index(ref, k) if w is None else mm.build_index(ref, k, w)
-        _CHAINS[(key, row)] = cm.seed_chain(rows, rl, index, len(ref), k, stride, w, max_occ, band, flank, min_votes, K, read_size)
-    return _CHAINS[(key, row)]
-
-
 def test_chimeric_reads_have_two_primaries():
     """Each half of a chimeric read is a primary of its own, and the halves drawn around a planted copy have secondaries under a
     parent other than 0."""
@@ -326,7 +309,6 @@ def test_chimeric_reads_have_two_primaries():
 def test_chain_mapq_on_the_model_chains(row):
     """A read from inside the planted segment has three equal chains: MAPQ 0 with sub_score == score. A plain read stands alone."""
     import chain_class_model as ccm
-    import seed_model as m
     K = row[7]
     rows, rl = ccm.planted_reads()
     req, tpos, votes, seeds, chains = model_chains("planted", row, rows, rl, ccm.PLANTED_SIZE)
@@ -334,9 +316,7 @@ def test_chain_mapq_on_the_model_chains(row):
     assert (seeds["n_cands"] >= 3).all() and (cls["flags"][0::K] == ccm.PRIMARY).all() and (cls["n_sub"][0::K] >= 2).all()
     assert (cls["mapq"][0::K] == 0).all() and (cls["sub_score"][0::K] == chains["score"][0::K]).all()
     assert ((cls["flags"][1::K] == ccm.SECONDARY) & (cls["flags"][2::K] == ccm.SECONDARY)).all()
-    if "ref" not in _CHAINS:
-        _CHAINS["ref"] = m.make_reference()
-    rows, rl, _, _, plain = m.make_reads(_CHAINS["ref"], 256, 128)
+    rows, rl, _, _, plain = short_reads()
     req, tpos, votes, seeds, chains = model_chains("short", row, rows, rl, 128)
     cls = ccm.classify(K, 128, 128, rl, tpos, seeds, chains)
     print(row, "plain reads", int(plain.sum()), "chain MAPQ", sorted(set(cls["mapq"][0::K][plain].tolist())))

@@ -4,7 +4,6 @@ batch size below, across and beyond one workgroup; read_mapq_kernel on the synth
 grid of eight workgroups and on wider groups than K needs; the classification of the chain kernels' own device buffers (three
 short-read rows, the chimeric reads through both chain kernels); and the whole path chain -> classify -> align -> MAPQ."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,21 +11,16 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import child  # noqa: E402
+from gpu_buffers import Hip, cached  # noqa: E402
+from hand_stages import chain_then_classify  # noqa: E402
+from pipeline_batches import READ_SIZE, expected, reference, short_reads  # noqa: E402
 
 KS = (1, 2, 3, 4, 5, 8, 16)
 MASKS = (1, 128, 256)
 N_READS = (1, 5, 67, 4099)          # below, across and beyond one workgroup; never a multiple of the reads per wavefront
 SHORT_ROWS = [(11, 1, None, 8, 8, 8, 2, 4), (11, 1, 5, 8, 32, 8, 2, 4), (13, 1, 10, 8, 32, 8, 2, 4)]
-
-_CACHE = {}
-
-
-def cached(key, make):
-    if key not in _CACHE:
-        _CACHE[key] = make()
-    return _CACHE[key]
 
 
 def synthetic(K):
@@ -47,7 +41,7 @@ def run_classify(h, K, read_size, mask_q8, d):
     """aim_chain_classify_device over uploaded arrays, d_class prefilled with 0xEE."""
     from aim_amd import capi, engine
     n = len(d["read_len"])
-    d_cls = h.up(np.full(n * K * 8, 0xEE, dtype=np.uint8))
+    d_cls = h.filled(n * K * 8)
     engine.chain_classify_device(K, read_size, mask_q8, n, h.up(d["read_len"]), h.up(d["text_pos"]), h.up(d["seed"]), h.up(d["chains"]), d_cls)
     return h.down(d_cls, n * K * 8).view(capi.CHAIN_CLASS_DTYPE)
 
@@ -55,7 +49,7 @@ def run_classify(h, K, read_size, mask_q8, d):
 def run_mapq(h, K, score_unit, best, mates, cls):
     from aim_amd import capi, engine
     n = len(best)
-    d_out = h.up(np.full(n * 8, 0xEE, dtype=np.uint8))
+    d_out = h.filled(n * 8)
     engine.read_mapq_device(K, n, score_unit, h.up(best), None if mates is None else h.up(mates), h.up(cls), d_out)
     return h.down(d_out, n * 8).view(capi.READ_MAPQ_DTYPE)
 
@@ -68,16 +62,12 @@ def same(got, want):
 @pytest.mark.parametrize("K", KS)
 def test_classification_equals_model(K, mask_q8):
     import chain_class_model as ccm
-    from test_sam_fields_gpu import Hip
     d, want = synthetic(K), expected_class(K, mask_q8)
     assert (want["flags"] & ccm.SECONDARY).any() or K == 1
     assert (want["flags"] == 0).any() and (want["mapq"] > 0).any()
-    h = Hip()
-    try:
+    with Hip() as h:
         for n in N_READS:
             same(run_classify(h, K, ccm.SYN_READ_SIZE, mask_q8, prefix(d, n, K)), want[:n * K])
-    finally:
-        h.free()
 
 
 def mapq_batch(K, n):
@@ -95,9 +85,7 @@ def mapq_batch(K, n):
 @pytest.mark.parametrize("K", (1, 4, 16))
 def test_read_mapq_equals_model(K, score_unit, with_mates):
     import chain_class_model as ccm
-    from test_sam_fields_gpu import Hip
-    h = Hip()
-    try:
+    with Hip() as h:
         for n in (2, 300, 1000):                      # below, across and beyond one workgroup
             cls, best, mates = mapq_batch(K, n)
             want = ccm.read_mapq(K, score_unit, best, mates if with_mates else None, cls)
@@ -105,31 +93,16 @@ def test_read_mapq_equals_model(K, score_unit, with_mates):
                 assert (want["flags"] & ccm.UNMAPPED).sum() >= 20 and (want["mapq"] > 0).sum() >= 20 and len(set(want["aln_mapq"].tolist())) >= 8
                 assert with_mates == bool((want["flags"] & ccm.PROPER).any())
             same(run_mapq(h, K, score_unit, best, mates if with_mates else None, cls), want)
-    finally:
-        h.free()
-
-
-KNOB_CHILD = '''
-import sys
-import numpy as np
-sys.path.insert(0, "tests")
-import test_chain_class_gpu as t
-np.savez(sys.argv[1], **t.knob_batch())
-'''
 
 
 def knob_batch():
     import chain_class_model as ccm
-    from test_sam_fields_gpu import Hip
     out = {}
-    h = Hip()
-    try:
+    with Hip() as h:
         for K in (4, 16):
             out["class%d" % K] = run_classify(h, K, ccm.SYN_READ_SIZE, 128, synthetic(K)).view(np.uint8)
         cls, best, mates = mapq_batch(4, 4098)
         out["mapq"] = run_mapq(h, 4, 3, best, mates, cls).view(np.uint8)
-    finally:
-        h.free()
     return out
 
 
@@ -139,9 +112,7 @@ def test_grid_and_group_width_identical(tmp_path, env):
     lanes (AIM_CLASS_G)."""
     import chain_class_model as ccm
     f = str(tmp_path / "k.npz")
-    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, AIM_PLAN_DEBUG="1", **env), capture_output=True, text=True,
-                       timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    p = child.run("test_chain_class_gpu", "knob_batch", npz=f, env=dict(env, AIM_PLAN_DEBUG="1"))
     lanes = int(env.get("AIM_CLASS_G", "4"))
     grids = (8, 8) if "AIM_CHIP_CUS" in env else (-(-4099 // (256 // lanes)), -(-4098 // 256))     # eight workgroups, or one pass
     assert "[aim plan] chain_class_kernel grid=%d block=256 lanes=%d reads=4099 K=4" % (grids[0], lanes) in p.stderr, p.stderr
@@ -153,78 +124,36 @@ def test_grid_and_group_width_identical(tmp_path, env):
     assert out["mapq"].tobytes() == ccm.read_mapq(4, 3, best, mates, cls).tobytes(), env
 
 
-def chain_then_classify(case, rows, rl, read_size, max_hits=None, mask_q8=128):
-    """aim_seed_chain_device (max_hits: aim_seed_chain_long_device) and aim_chain_classify_device on the buffers it wrote, which never
-    leave the device in between. Returns (text_pos, seed rows, chains, class rows)."""
-    from test_sam_fields_gpu import Hip
-    from test_seed_chain_gpu import reference
-    from aim_amd import capi, engine
-    k, stride, w, max_occ, band, flank, min_votes, K = case
-    ref = reference()
-    sp = engine.seed_params(k, read_size, stride=stride, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K, w=w,
-                            long_reads=max_hits is not None)
-    bucket, pos = engine.build_index(ref, k, threads=4) if w is None else engine.index_build_minimizers(ref, k, w, threads=4)
-    n = len(rl)
-    h = Hip()
-    try:
-        d_rl = h.up(np.ascontiguousarray(rl, dtype=np.int32))
-        fill = lambda nbytes: h.up(np.full(nbytes, 0xEE, dtype=np.uint8))
-        d_req, d_tp, d_v, d_s, d_c, d_cls = fill(n * K * 16), fill(n * K * 8), fill(n * K * 4), fill(n * 16), fill(n * K * 16), fill(n * K * 8)
-        args = (n, d_rl, h.up(np.ascontiguousarray(rows), 64), h.up(bucket), h.up(pos), len(ref), d_req, d_tp, d_v, d_s, d_c)
-        if max_hits is None:
-            engine.seed_chain_device(sp, *args)
-        else:
-            engine.seed_chain_long_device(sp, max_hits, *args)
-        engine.chain_classify_device(K, read_size, mask_q8, n, d_rl, d_tp, d_s, d_c, d_cls)
-        return (h.down(d_tp, n * K * 8).view(np.uint64), h.down(d_s, n * 16).view(capi.SEED_DTYPE), h.down(d_c, n * K * 16).view(capi.CHAIN_DTYPE),
-                h.down(d_cls, n * K * 8).view(capi.CHAIN_CLASS_DTYPE))
-    finally:
-        h.free()
-
-
 @pytest.mark.parametrize("row", SHORT_ROWS, ids=[str(r) for r in SHORT_ROWS])
 def test_short_reads_on_the_device_chain(row):
     import chain_class_model as ccm
-    from test_seed_chain_gpu import READ_SIZE, expected, short_reads
     rows, rl = short_reads()[:2]
     req, tpos, votes, seeds, chains = expected(row, rows, rl, "short")
     K = row[7]
     want = ccm.classify(K, READ_SIZE, 128, rl, tpos, seeds, chains)
     assert (want["flags"] & ccm.SECONDARY).sum() >= 10 and (want["flags"] == 0).any()      # (reads of 100 bases have no second part)
     got = chain_then_classify(row, rows, rl, READ_SIZE)
-    assert got[0].tobytes() == tpos.tobytes() and got[1].tobytes() == seeds.tobytes() and got[2].tobytes() == chains.tobytes()
-    same(got[3], want)
+    assert got[1].tobytes() == tpos.tobytes() and got[2].tobytes() == seeds.tobytes() and got[3].tobytes() == chains.tobytes()
+    same(got[4], want)
 
 
 @pytest.mark.parametrize("max_hits", (None, 1024), ids=("seed_chain_device", "seed_chain_long_device"))
 def test_chimeric_reads_on_the_device_chain(max_hits):
     import chain_class_model as ccm
-    from test_seed_chain_gpu import expected, reference
-    rows, rl = cached("chimeric", lambda: ccm.chimeric_reads(reference()))
+    rows, rl = cached("chimeric reads", lambda: ccm.chimeric_reads(reference()))
     K = ccm.CHIMERIC_ROW[7]
     req, tpos, votes, seeds, chains = expected(ccm.CHIMERIC_ROW, rows, rl, "chimeric", read_size=ccm.CHIMERIC_SIZE)
     want = ccm.classify(K, ccm.CHIMERIC_SIZE, 128, rl, tpos, seeds, chains)
     fl = want["flags"].reshape(-1, K)
     assert (((fl & ccm.PRIMARY) != 0).sum(axis=1) >= 2).all() and (((fl & ccm.SECONDARY) != 0) & (want["parent"].reshape(-1, K) != 0)).any()
     got = chain_then_classify(ccm.CHIMERIC_ROW, rows, rl, ccm.CHIMERIC_SIZE, max_hits=max_hits)
-    assert got[0].tobytes() == tpos.tobytes() and got[1].tobytes() == seeds.tobytes() and got[2].tobytes() == chains.tobytes()
-    same(got[3], want)
-
-
-PATH_CHILD = '''
-import sys
-import torch
-torch.cuda.init()   # (before the library: the device buffers are torch's)
-sys.path.insert(0, "tests")
-import test_chain_class_gpu as t
-t.whole_path()
-print("CHAIN_CLASS_WHOLE_PATH_OK")
-'''
+    assert got[1].tobytes() == tpos.tobytes() and got[2].tobytes() == seeds.tobytes() and got[3].tobytes() == chains.tobytes()
+    same(got[4], want)
 
 
 def test_whole_path():
-    p = subprocess.run([sys.executable, "-c", PATH_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "CHAIN_CLASS_WHOLE_PATH_OK" in p.stdout, p.stdout + p.stderr
+    p = child.run("test_chain_class_gpu", "whole_path", cuda_first=True, marker="CHAIN_CLASS_WHOLE_PATH_OK")
+    assert "CHAIN_CLASS_WHOLE_PATH_OK" in p.stdout, p.stdout + p.stderr
 
 
 def whole_path():
@@ -237,7 +166,6 @@ def whole_path():
     import torch
     import chain_class_model as ccm
     import seed_model as m
-    from test_seed_chain_gpu import READ_SIZE, expected, reference, short_reads
     from aim_amd import capi, engine
     ref = reference()
     srows, srl, _, _, plain = short_reads()

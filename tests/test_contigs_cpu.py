@@ -129,7 +129,7 @@ def test_record_model():
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------------------
 def _params(**kw):
-    from test_mapper_cpu import _params as base
+    from mapper_batch import params_with as base
     return base(**kw)
 
 
@@ -187,7 +187,7 @@ def test_every_mapper_refusal_comes_back_for_contigs():
     """Behind the contig bounds, every check of aim_mapper_device_bytes / aim_mapper_create on the laid-out ref_len, under the new
     names; then the arguments of the two entry points."""
     from aim_amd import capi, engine
-    from test_mapper_cpu import REFUSALS
+    from mapper_batch import REFUSALS
     lib = _lib()
     lens = _u32([9000, 1, 500])
     b, h = C.c_uint64(), C.c_void_p()
@@ -262,7 +262,7 @@ def test_contig_kernels_code_objects():
 # ---- samout --------------------------------------------------------------------------------------------------------------------------
 def _two_contig_records():
     from aim_amd import capi
-    from test_mapper_cpu import _record
+    from mapper_batch import record as _record
     M, S = 0, 4
     w = lambda n, op: (n << 4) | op
     cigar, md = [], []

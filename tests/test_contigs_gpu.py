@@ -16,6 +16,9 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import child  # noqa: E402
+import hand_stages as hs  # noqa: E402
+from gpu_buffers import Hip, copy_out, put  # noqa: E402
 
 KS = (1, 4, 16)
 N_READS = (1, 65, 2100)
@@ -35,7 +38,7 @@ def run_clip(h, K, n, n_contigs, seg_flags=None, keep=False):
     guard = np.full(GUARD, 0xEE, dtype=np.uint8)
     up = lambda a: h.up(np.concatenate([np.ascontiguousarray(a).view(np.uint8).reshape(-1), guard]))
     S = n * K
-    d_sr, d_stp, d_sg, d_ct = up(d["seg_req"]), up(d["seg_text_pos"]), up(d["seg"]), h.up(np.full(4 * S + GUARD, 0xEE, dtype=np.uint8))
+    d_sr, d_stp, d_sg, d_ct = up(d["seg_req"]), up(d["seg_text_pos"]), up(d["seg"]), h.filled(4 * S + GUARD)
     d_st = h.up(starts)
     engine.contig_clip_device(K, cg.SYN_READ_SIZE, cg.SYN_FLANK, ref_len, n_contigs, d_st, h.up(lens), n, h.up(d["read_len"]), h.up(d["req"]), h.up(d["text_pos"]),
                               h.up(d["chains"]), d_sr, d_stp, d_sg, d_ct)
@@ -57,38 +60,23 @@ def check_clip(K, n, n_contigs, got, seg_flags=None):
 
 @pytest.mark.parametrize("K", KS)
 def test_clip_equals_model(K):
-    from test_sam_fields_gpu import Hip
-    h = Hip()
-    try:
+    with Hip() as h:
         for n in N_READS:
             for nc in CONTIGS_FOR[n]:
                 check_clip(K, n, nc, run_clip(h, K, n, nc))
                 h.free()
-    finally:
-        h.free()
 
 
-KNOB_CHILD = '''
-import sys
-import numpy as np
-sys.path.insert(0, "tests")
-import test_contigs_gpu as t
-np.savez(sys.argv[1], **t.knob_batch())
-'''
 KNOB_CASES = ((4, 2100, 5000), (16, 65, 1025), (1, 2100, 3), (4, 65, 1024))
 
 
 def knob_batch():
-    from test_sam_fields_gpu import Hip
     out = {}
-    h = Hip()
-    try:
+    with Hip() as h:
         for i, (K, n, nc) in enumerate(KNOB_CASES):
             for j, g in enumerate(run_clip(h, K, n, nc)):
                 out["c%d_%d" % (i, j)] = g
             h.free()
-    finally:
-        h.free()
     return out
 
 
@@ -98,9 +86,7 @@ def test_grid_and_poison_identical(tmp_path, env):
     """The same bytes -- the model's -- at AIM_CHIP_CUS 1 (8 workgroups walk the 33 blocks of slots) and 256 and under the three
     AIM_DEBUG_POISON_* knobs; the plan line names the grid, the contigs and the step."""
     f = str(tmp_path / "k.npz")
-    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, AIM_PLAN_DEBUG="1", **env), capture_output=True, text=True,
-                       timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    p = child.run("test_contigs_gpu", "knob_batch", npz=f, env=dict(env, AIM_PLAN_DEBUG="1"))
     grid = 8 if env["AIM_CHIP_CUS"] == "1" else 33
     assert "[aim plan] contig_clip_kernel grid=%d block=256 contigs=5000 step=8 slots=8400" % grid in p.stderr, p.stderr
     assert "[aim plan] contig_clip_kernel grid=5 block=256 contigs=1025 step=2 slots=1040" in p.stderr, p.stderr
@@ -117,18 +103,15 @@ def test_contig_records_equal_model(K):
     import contig_model as cg
     import map_records_model as mm
     from aim_amd import engine
-    from test_sam_fields_gpu import Hip
-    h = Hip()
-    try:
+    with Hip() as h:
         for n, nc in ((1, 1), (65, 3), (2100, 1025)):
             seg, sam, cls = mm.synthetic_tables(11, K, n)
             got, (d_sg, d_ct, d_st) = run_clip(h, K, n, nc, seg_flags=seg["flags"], keep=True)
             check_clip(K, n, nc, got, seg_flags=seg["flags"])
             lens, starts, ref_len, d, o = cg.synthetic_clip(SEED, K, n, nc, seg["flags"])
-            d_off = h.up(np.full(4 * (n + 1) + GUARD, 0xEE, dtype=np.uint8))
-            d_rec = h.up(np.full(64 * n * K + GUARD, 0xEE, dtype=np.uint8))
+            d_off, d_rec = h.filled(4 * (n + 1) + GUARD), h.filled(64 * n * K + GUARD)
             sb = engine.map_records_scratch(n)
-            engine.map_records_contigs_device(K, n, d_sg, h.up(sam), h.up(cls), d_ct, nc, d_st, d_off, d_rec, h.up(np.full(sb, 0xEE, dtype=np.uint8)), sb)
+            engine.map_records_contigs_device(K, n, d_sg, h.up(sam), h.up(cls), d_ct, nc, d_st, d_off, d_rec, h.filled(sb), sb)
             off_b, rec_b = h.down(d_off, 4 * (n + 1) + GUARD), h.down(d_rec, 64 * n * K + GUARD)
             want_off, want = cg.records(K, n, o["seg"], sam, cls, o["contig"], starts)
             assert off_b[:4 * (n + 1)].tobytes() == want_off.tobytes() and (off_b[4 * (n + 1):] == 0xEE).all(), (K, n)
@@ -140,18 +123,12 @@ def test_contig_records_equal_model(K):
             assert (rec_b[64 * total:] == 0xEE).all(), "written past the records"
             assert (want["sam"]["pad"] == cg.NONE).any() or n == 1
             h.free()
-        d_off = h.up(np.full(8, 0xEE, dtype=np.uint8))
+        d_off = h.filled(8)
         engine.map_records_contigs_device(K, 0, None, None, None, None, 1, None, d_off, None, None, 0)
         assert h.down(d_off, 8).tolist() == [0, 0, 0, 0, 0xEE, 0xEE, 0xEE, 0xEE]
-    finally:
-        h.free()
 
 
 # ---- the mapper end to end -----------------------------------------------------------------------------------------------------------
-def copy_out(out):
-    return {k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
-
-
 def whole_batch():
     """The shared 73 reads followed by the five planted ones, and the three contigs."""
     import contig_model as cg
@@ -168,53 +145,27 @@ def map_contigs(mp, seqs, rl, rows):
 
 
 def hand_path(extend):
-    """test_mapper_gpu.hand_path on the concatenation, with aim_contig_clip_device between the split (or the extension) and the
+    """hand_stages.single_end on the concatenation, with aim_contig_clip_device between the split (or the extension) and the
     alignment, and rule 13c's record model at the end: a dict shaped like a mapper result."""
-    import torch
     import chain_class_model as ccm
     import contig_model as cg
     import mapper_batch as mb
     from aim_amd import capi, engine
-    lib = capi.load()
     mo, seqs, rows, rl = whole_batch()
     ref, starts, lens = mo["concat"], mo["starts"], mo["lens"]
     k, stride, w, max_occ, band, flank, min_votes, K = ccm.CHIMERIC_ROW
     rs, n = ccm.CHIMERIC_SIZE, len(rl)
-    dev = torch.device("cuda:0")
-    params = engine.make_params("wfa", mb.max_score(), rs, mismatch=mb.X, gap_o=mb.O, gap_e=mb.E, backtrace=True, ref_texts=True, ends_free=(0, 0, 2 * flank, 2 * flank))
+    params = hs.wfa_params(mb.max_score(), rs, mb.X, mb.O, mb.E, 2 * flank)
     rows_n = n * K
-    d_ref = torch.zeros(len(ref) + 64, dtype=torch.uint8, device=dev)
-    d_ref[:len(ref)] = torch.from_numpy(ref).to(dev)
+    d_ref = put(ref, hs.DEV, 64)
     sp = engine.seed_params(k, rs, stride=stride, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K, w=w)
-    out = engine.split_segments(sp, engine.chain_classify(sp, engine.seed_chain_candidates(sp, engine.index_build_minimizers(ref, k, w), len(ref), rl, rows)), len(ref))
-    if extend:
-        out = engine.extend_segments(sp, out, d_ref[:len(ref)], engine.extend_params(*mb.EXTEND))
-    d_st, d_ln = torch.from_numpy(starts.view(np.int32)).to(dev), torch.from_numpy(lens.view(np.int32)).to(dev)
-    d_ct = torch.full((rows_n,), -286331154, dtype=torch.int32, device=dev)        # 0xEEEEEEEE
-    torch.cuda.synchronize()
-    engine.contig_clip_device(K, rs, flank, len(ref), len(starts), d_st.data_ptr(), d_ln.data_ptr(), n, out["d_read_len"].data_ptr(), out["d_req"].data_ptr(),
-                              out["d_text_pos"].data_ptr(), out["d_chains"].data_ptr(), out["d_seg_req"].data_ptr(), out["d_seg_text_pos"].data_ptr(),
-                              out["d_seg"].data_ptr(), d_ct.data_ptr())
-    torch.cuda.synchronize()
+    out = hs.segment_rows(sp, ref, rl, rows, extend=(d_ref, engine.extend_params(*mb.EXTEND)) if extend else None)
+    d_ct = hs.clip_contigs(out, K, rs, flank, len(ref), starts, lens, n)[0]
     seg = out["d_seg"].cpu().numpy().view(capi.SEGMENT_DTYPE)[:rows_n]
     contig = d_ct.cpu().numpy().view(np.uint32)
-    d_res = torch.zeros(rows_n * capi.RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_ops = torch.zeros(rows_n * 2 * rs + 64, dtype=torch.uint8, device=dev)
-    sb = lib.aim_scratch_bytes(capi.params_ref(params), rows_n)
-    d_scr = torch.zeros(max(sb, 16), dtype=torch.uint8, device=dev)
-    ccap, mcap = rows_n * 64, rows_n * 256
-    buf = (torch.zeros(rows_n * 48, dtype=torch.uint8, device=dev), torch.zeros(ccap * 4, dtype=torch.uint8, device=dev),
-           torch.zeros(mcap, dtype=torch.uint8, device=dev), torch.zeros(8, dtype=torch.uint8, device=dev))
-    torch.cuda.synchronize()
-    rc = lib.aim_align_device_ref(capi.params_ref(params), rows_n, out["d_seg_req"].data_ptr(), out["d_seg_patterns"].data_ptr(), out["d_seg_text_pos"].data_ptr(),
-                                  d_ref.data_ptr(), len(ref), d_res.data_ptr(), d_ops.data_ptr(), d_scr.data_ptr(), sb, None)
-    assert rc == 0, lib.aim_last_error()
-    engine.sam_device_split(params, rows_n, out["d_seg_req"].data_ptr(), out["d_seg_text_pos"].data_ptr(), None, d_res.data_ptr(), d_ops.data_ptr(), d_ref.data_ptr(),
-                            len(ref), 0, buf[0].data_ptr(), buf[1].data_ptr(), ccap, buf[2].data_ptr(), mcap, buf[3].data_ptr(), out["d_seg"].data_ptr())
-    torch.cuda.synchronize()
-    sam = buf[0].cpu().numpy().view(capi.SAM_DTYPE)
-    off, rec = cg.records(K, n, seg, sam, out["class"], contig, starts)
-    return {"records": rec, "rec_offsets": off, "cigar": buf[1].cpu().numpy().view(np.uint32), "md": buf[2].cpu().numpy()}, seg, contig
+    s = hs.segment_records(params, out, rows_n, d_ref, len(ref))[2]
+    off, rec = cg.records(K, n, seg, s["sam"], out["class"], contig, starts)
+    return {"records": rec, "rec_offsets": off, "cigar": s["cigar"], "md": s["md"]}, seg, contig
 
 
 def inside(rec, lens):
@@ -321,24 +272,13 @@ def end_to_end():
         assert leaves[5:] == [1, 1], leaves                          # one base beyond the edge: a mismatch against the spacer is the cheaper end
 
 
-PATH_CHILD = '''
-import sys
-import torch
-torch.cuda.init()   # (before the library: the hand-driven path's buffers are torch's)
-sys.path.insert(0, "tests")
-import test_contigs_gpu as t
-t.end_to_end()
-print("CONTIGS_END_TO_END_OK")
-'''
-
-
 _CHILD = {}
 
 
 def end_to_end_child():
     """end_to_end() in a child process, once for the tests that read its output."""
     if "p" not in _CHILD:
-        _CHILD["p"] = subprocess.run([sys.executable, "-c", PATH_CHILD], cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=300)
+        _CHILD["p"] = child.run("test_contigs_gpu", "end_to_end", cuda_first=True, marker="CONTIGS_END_TO_END_OK", check=False)
     return _CHILD["p"]
 
 

@@ -13,6 +13,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "aim_hip.h")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from extend_model import inner_gaps  # noqa: E402
 
 NEVER = 1 << 20                         # an x-drop no pair here can reach
 
@@ -289,7 +290,7 @@ def chimeric_model():
         import extend_model as em
         import seed_model as m
         import split_model as sm
-        from test_chain_class_cpu import model_chains
+        from pipeline_batches import model_chains
         ref = m.make_reference()
         rows, rl, halves = sm.chimeric(ref)
         k, stride, w, max_occ, band, flank, min_votes, K = ccm.CHIMERIC_ROW
@@ -299,20 +300,6 @@ def chimeric_model():
         out, ext = em.extend_segments(em.Params(*CHIM_PARAMS), K, ccm.CHIMERIC_SIZE, len(ref), rl, rows, ref, *split)
         _CHIM.update(rows=rows, rl=rl, halves=halves, ref=ref, K=K, flank=flank, split=split, ext_out=out, ext=ext)
     return _CHIM
-
-
-def inner_gaps(seg, halves, K):
-    """Per inner side of every valid segment: (slot, side, true cut - segment end), positive while the segment stops short of the cut."""
-    import split_model as sm
-    out = []
-    for slot in np.nonzero(seg["flags"] & sm.VALID)[0]:
-        sg = seg[slot]
-        hf = sm.half_of(halves[slot // K], int(sg["q_begin"]), int(sg["q_end"]))
-        if not int(sg["flags"]) & sm.LEFT_OPEN:
-            out.append((int(slot), 0, int(sg["q_begin"]) - hf["q_lo"]))
-        if not int(sg["flags"]) & sm.RIGHT_OPEN:
-            out.append((int(slot), 1, hf["q_hi"] - int(sg["q_end"])))
-    return out
 
 
 def test_chimeric_reads_recover_the_breakpoint():

@@ -4,7 +4,6 @@ penalty set, band and max_ext below, the identity on the single-primary short re
 poison knobs, and the whole path chain -> classify -> split -> extend -> align -> SAM records on the chimeric reads against the same
 path without the extension call."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,22 +11,18 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import child  # noqa: E402
+import hand_stages as hs  # noqa: E402
+from extend_model import inner_gaps  # noqa: E402
+from gpu_buffers import Hip, cached, put  # noqa: E402
+from pipeline_batches import FULL, READ_SIZE, chimeric_expected, reference, short_reads  # noqa: E402
 
 OUT = ("seg_req", "seg_text_pos", "seg_patterns", "seg", "ext")
 # (K, read_size, penalty set of extend_model.PENALTIES, band, max_ext, max_cost, batch sizes): 1, 65 and 1027 reads are below, across and
 # beyond a wavefront's 64 items and, at K = 4, a workgroup of the apply kernel; the largest batch runs at max_ext 32
 CASES = [(4, 104, 0, 31, 64, 400, (1, 65)), (1, 104, 1, 31, 8, 400, (1, 65)), (16, 104, 2, 1, 64, 400, (65,)), (4, 1024, 0, 31, 1024, 4095, (65,)),
          (16, 1024, 1, 31, 64, 70, (65,)), (1, 1024, 2, 15, 64, 400, (65,)), (4, 104, 0, 31, 32, 400, (1027,)), (16, 1024, 2, 31, 32, 400, (1027,))]
-
-_CACHE = {}
-
-
-def cached(key, make):
-    if key not in _CACHE:
-        _CACHE[key] = make()
-    return _CACHE[key]
 
 
 def case_params(case):
@@ -43,7 +38,7 @@ def directed(case):
 
     def make():
         K, rs = case[0], case[1]
-        ref = cached("ref", em.directed_reference)
+        ref = cached("directed ref", em.directed_reference)
         d = em.directed(1, max(case[6]), K, rs, ref)
         (req, tp, pat, seg), ext = em.directed_expected(case_params(case), d, K, rs, ref)
         return ref, d, (req, tp, pat, seg, ext)
@@ -59,7 +54,7 @@ def run_extend(h, p, K, read_size, ref, read_len, reads, seg_req, seg_tp, seg_pa
     ep = engine.extend_params(p.match, p.mismatch, p.gap_o, p.gap_e, p.xdrop, p.max_cost, p.band, p.max_ext)
     d_req, d_tp, d_seg = h.up(seg_req), h.up(seg_tp), h.up(seg)
     d_pat = h.up(np.concatenate([np.ascontiguousarray(seg_pat).reshape(-1), np.full(64, 0xEE, dtype=np.uint8)]))
-    d_ext = h.up(np.full(slots * 24, 0xEE, dtype=np.uint8))
+    d_ext = h.filled(slots * 24)
     engine.extend_segments_device(ep, K, read_size, len(ref), n, h.up(np.ascontiguousarray(read_len, dtype=np.int32)), h.up(reads, 64), h.up(ref, 64),
                                   d_req, d_tp, d_pat, d_seg, d_ext)
     pat = h.down(d_pat, slots * read_size + 64)
@@ -86,7 +81,6 @@ def run_directed(h, case, n):
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "K%d-rs%d-pen%d-band%d-ext%d-cost%d" % tuple(c[:6]))
 def test_directed_batch_equals_model(case):
-    from test_sam_fields_gpu import Hip
     K = case[0]
     ref, d, want = directed(case)
     ext = want[4]
@@ -94,13 +88,10 @@ def test_directed_batch_equals_model(case):
         assert (ext["dq"] != 0).any() and (ext["stop"] != 0).any() and ((ext["dq"] == 0).all(axis=1) & (want[3]["flags"] != 0)).any()
     if case[5] < 100:
         assert (ext["stop"] == case[5]).any()                       # a stop by max_cost
-    h = Hip()
-    try:
+    with Hip() as h:
         for n in case[6]:
             same(run_directed(h, case, n), want, n * K)
             h.free()
-    finally:
-        h.free()
 
 
 def test_single_primary_identity():
@@ -108,21 +99,15 @@ def test_single_primary_identity():
     four buffers and gets a zero aim_extend_t; the whole output equals the model."""
     import chain_class_model as ccm
     import extend_model as em
-    from test_sam_fields_gpu import Hip
-    from test_seed_chain_gpu import FULL, READ_SIZE, reference, short_reads
-    from test_split_gpu import chain_classify_split
     rows, rl = short_reads()[:2]
     case = FULL[0]
     K = case[7]
     ref = reference()
-    (req, tpos, seeds, chains, cls), split = chain_classify_split(case, rows, rl, READ_SIZE)
+    (req, tpos, seeds, chains, cls), split = hs.chain_classify_split(case, rows, rl, READ_SIZE)
     p = em.Params(1, 3, 4, 1, 20, 400, 31, 64)
     want, want_ext = em.extend_segments(p, K, READ_SIZE, len(ref), rl, rows, ref, *split)
-    h = Hip()
-    try:
+    with Hip() as h:
         got = run_extend(h, p, K, READ_SIZE, ref, rl, rows, *split)
-    finally:
-        h.free()
     same(got, want + (want_ext,))
     prim = (cls["flags"].reshape(-1, K) & ccm.PRIMARY) != 0
     sole = np.nonzero(prim.sum(axis=1) == 1)[0]
@@ -134,27 +119,16 @@ def test_single_primary_identity():
         assert got[4][sl].tobytes() == bytes(24 * K), r
 
 
-KNOB_CHILD = '''
-import sys
-import numpy as np
-sys.path.insert(0, "tests")
-import test_extend_gpu as t
-np.savez(sys.argv[1], **t.knob_batch())
-'''
 KNOB_CASES = (CASES[6], CASES[4])
 
 
 def knob_batch():
-    from test_sam_fields_gpu import Hip
     out = {}
-    h = Hip()
-    try:
+    with Hip() as h:
         for i, case in enumerate(KNOB_CASES):
             for name, arr in zip(OUT, run_directed(h, case, max(case[6]))):
                 out["%s_%d" % (name, i)] = arr.view(np.uint8)
             h.free()
-    finally:
-        h.free()
     return out
 
 
@@ -164,9 +138,7 @@ def test_grid_and_poison_identical(tmp_path, env):
     """The same bytes -- the model's -- at AIM_CHIP_CUS 1 (32 wavefronts walk the 129 groups of items) and 256 and under the three
     AIM_DEBUG_POISON_* knobs."""
     f = str(tmp_path / "k.npz")
-    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, AIM_PLAN_DEBUG="1", **env), capture_output=True, text=True,
-                       timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    p = child.run("test_extend_gpu", "knob_batch", npz=f, env=dict(env, AIM_PLAN_DEBUG="1"))
     grid = 32 if env["AIM_CHIP_CUS"] == "1" else 129
     apply_grid = 8 if env["AIM_CHIP_CUS"] == "1" else 17
     line = "[aim plan] extend_sides_kernel grid=%d block=64 lds=2656 step=1 rings=12+2*4 reads=1027 K=4 read_size=104; extend_apply_kernel grid=%d block=256"
@@ -179,19 +151,8 @@ def test_grid_and_poison_identical(tmp_path, env):
             assert out["%s_%d" % (name, i)].tobytes() == w.tobytes(), (name, case, env)
 
 
-PATH_CHILD = '''
-import sys
-import torch
-torch.cuda.init()   # (before the library: the device buffers are torch's)
-sys.path.insert(0, "tests")
-import test_extend_gpu as t
-t.whole_path()
-print("EXTEND_WHOLE_PATH_OK")
-'''
-
-
 def test_whole_path():
-    p = subprocess.run([sys.executable, "-c", PATH_CHILD], cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=300)
+    p = child.run("test_extend_gpu", "whole_path", cuda_first=True, marker="EXTEND_WHOLE_PATH_OK", check=False)
     print(p.stdout[-3000:])
     assert p.returncode == 0 and "EXTEND_WHOLE_PATH_OK" in p.stdout, p.stdout + p.stderr
 
@@ -228,11 +189,7 @@ def whole_path():
     import chain_class_model as ccm
     import extend_model as em
     import split_model as sm
-    from test_seed_chain_gpu import reference
-    from test_split_gpu import chimeric_expected
-    from test_extend_cpu import inner_gaps
     from aim_amd import capi, engine
-    lib = capi.load()
     ref = reference()
     rows, rl, halves, (m_req, m_tpos, m_seeds, m_chains), m_cls, m_split = chimeric_expected()
     k, stride, w, max_occ, band, flank, min_votes, K = ccm.CHIMERIC_ROW
@@ -243,37 +200,21 @@ def whole_path():
     bound = ccm.CHIMERIC_EDITS * max(x, o + e)
     max_score = bound + 16
     dev = torch.device("cuda:0")
-    params = engine.make_params("wfa", max_score, rs, mismatch=x, gap_o=o, gap_e=e, backtrace=True, ref_texts=True, ends_free=(0, 0, 2 * flank, 2 * flank))
+    params = hs.wfa_params(max_score, rs, x, o, e, 2 * flank)
     rows_n = n * K
-    d_ref = torch.zeros(len(ref) + 64, dtype=torch.uint8, device=dev)
-    d_ref[:len(ref)] = torch.from_numpy(ref).to(dev)
+    d_ref = put(ref, dev, 64)
     sp = engine.seed_params(k, rs, stride=stride, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K, w=w)
-    index = engine.index_build_minimizers(ref, k, w)
     clips = {}
     for extend in (False, True):
-        out = engine.split_segments(sp, engine.chain_classify(sp, engine.seed_chain_candidates(sp, index, len(ref), rl, rows)), len(ref))
+        out = hs.segment_rows(sp, ref, rl, rows, extend=(d_ref, engine.extend_params(*p)) if extend else None)
         if extend:
-            out = engine.extend_segments(sp, out, d_ref[:len(ref)], engine.extend_params(*p))
             got = (out["seg_req"], out["seg_text_pos"], out["seg_patterns"], out["seg"], out["ext"])
             for name, g, wnt in zip(OUT, got, want + (want_ext,)):
                 assert g.tobytes() == wnt.tobytes(), name
         seg = out["seg"]
-        d_res = torch.zeros(rows_n * capi.RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        d_ops = torch.zeros(rows_n * 2 * rs + 64, dtype=torch.uint8, device=dev)
-        sb = lib.aim_scratch_bytes(capi.params_ref(params), rows_n)
-        d_scr = torch.zeros(max(sb, 16), dtype=torch.uint8, device=dev)
-        ccap, mcap = rows_n * 64, rows_n * 256
-        buf = (torch.zeros(rows_n * 48, dtype=torch.uint8, device=dev), torch.zeros(ccap * 4, dtype=torch.uint8, device=dev),
-               torch.zeros(mcap, dtype=torch.uint8, device=dev), torch.zeros(8, dtype=torch.uint8, device=dev))
-        torch.cuda.synchronize()
-        rc = lib.aim_align_device_ref(capi.params_ref(params), rows_n, out["d_seg_req"].data_ptr(), out["d_seg_patterns"].data_ptr(), out["d_seg_text_pos"].data_ptr(),
-                                      d_ref.data_ptr(), len(ref), d_res.data_ptr(), d_ops.data_ptr(), d_scr.data_ptr(), sb, None)
-        assert rc == 0, lib.aim_last_error()
-        engine.sam_device_split(params, rows_n, out["d_seg_req"].data_ptr(), out["d_seg_text_pos"].data_ptr(), None, d_res.data_ptr(), d_ops.data_ptr(), d_ref.data_ptr(),
-                                len(ref), 0, buf[0].data_ptr(), buf[1].data_ptr(), ccap, buf[2].data_ptr(), mcap, buf[3].data_ptr(), out["d_seg"].data_ptr())
-        torch.cuda.synchronize()
-        rec, cg, cur = buf[0].cpu().numpy().view(capi.SAM_DTYPE), buf[1].cpu().numpy().view(np.uint32), buf[3].cpu().numpy().view(np.uint32)
-        assert cur[0] <= ccap and cur[1] <= mcap and not (rec["status"] & sm.SAM_OVERFLOW).any()
+        d_res, _, s = hs.segment_records(params, out, rows_n, d_ref, len(ref))
+        rec, cg, cur = s["sam"], s["cigar"], s["cur"]
+        assert cur[0] <= rows_n * 64 and cur[1] <= rows_n * 256 and not (rec["status"] & sm.SAM_OVERFLOW).any()
         res = d_res.cpu().numpy().view(capi.RESULT_DTYPE)
         words = [[int(v) for v in cg[int(r["cigar_offset"]):int(r["cigar_offset"]) + int(r["n_cigar"])]] for r in rec]
         mapped = (rec["flags"] & sm.SAM_UNMAPPED) == 0

@@ -3,8 +3,6 @@ itself pinned to tests/seed_model.build_index: the whole bucket[] and pos[:n_pos
 wavefront and the tile; k = 14 with its 1 GiB bucket and 29-bit keys; bytes that are not indexed, also across tile boundaries; one
 bucket that holds every position; any CU count and poison knob; any scratch contents; and the chain into seed_candidates."""
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -12,10 +10,12 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import child  # noqa: E402
+import pipeline_batches as pb  # noqa: E402
+from gpu_buffers import Hip  # noqa: E402
 
-T = int(re.search(r"constexpr uint32_t kIndexTile = (\d+);", open(os.path.join(ROOT, "aim_amd", "csrc", "index.hpp")).read()).group(1))
+T = pb.index_tile()
 
 _REF = {}
 
@@ -28,30 +28,11 @@ def random_ref(n, seed=2025):
     return _REF["rand"][:n]
 
 
-def model_ref():
-    if "model" not in _REF:
-        import seed_model as m
-        _REF["model"] = m.make_reference()
-    return _REF["model"]
+model_ref = pb.reference
 
 
-class Dev:
-    """Device buffers through the HIP runtime the library loaded (tests/test_sam_fields_gpu.Hip), plus raw allocations and fills."""
-
-    def __init__(self):
-        import ctypes as C
-        from test_sam_fields_gpu import Hip
-        self.C = C
-        self.h = Hip()
-        self.h.lib.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-
-    def alloc(self, nbytes, fill=None):
-        p = self.C.c_void_p()
-        assert self.h.lib.hipMalloc(self.C.byref(p), max(int(nbytes), 256)) == 0
-        self.h.bufs.append(p)
-        if fill is not None:
-            assert self.h.lib.hipMemset(p, fill, max(int(nbytes), 256)) == 0
-        return p
+class Dev(Hip):
+    """Hip with the index build on it."""
 
     def build(self, ref, k, scratch_fill=0xEE, out_fill=0xEE):
         """aim_index_build_device on `ref`: (bucket[4^k + 1], pos[pos_capacity], n_pos) as the device left them."""
@@ -60,25 +41,21 @@ class Dev:
         be, pc = engine.index_sizes(k, len(ref))
         sb = engine.index_device_scratch(k, len(ref))
         assert (sb == 0) == (pc == 0)
-        d_ref = self.h.up(ref, 16)
+        d_ref = self.up(ref, 16)
         d_bucket = self.alloc(be * 4, out_fill)
         d_pos = self.alloc(pc * 4, out_fill) if pc else None
         d_scr = self.alloc(sb, scratch_fill) if sb else None
         engine.index_build_device(d_ref, len(ref), k, d_bucket, d_pos, d_scr, sb)
-        bucket = self.h.down(d_bucket, be * 4).view(np.uint32)
-        pos = self.h.down(d_pos, pc * 4).view(np.uint32) if pc else np.zeros(0, dtype=np.uint32)
-        self.h.free()
+        bucket = self.down(d_bucket, be * 4).view(np.uint32)
+        pos = self.down(d_pos, pc * 4).view(np.uint32) if pc else np.zeros(0, dtype=np.uint32)
+        self.free()
         return bucket, pos, int(bucket[-1])
-
-    def close(self):
-        self.h.free()
 
 
 @pytest.fixture()
 def dev():
-    d = Dev()
-    yield d
-    d.close()
+    with Dev() as d:
+        yield d
 
 
 def check(dev, ref, k, **kw):
@@ -176,15 +153,6 @@ def test_scratch_is_only_scratch(dev):
     check(dev, ref, 11, scratch_fill=0xA5)
 
 
-KNOB_CHILD = '''
-import sys
-import numpy as np
-sys.path.insert(0, "tests")
-import test_index_device_gpu as t
-np.savez(sys.argv[1], **t.knob_builds())
-'''
-
-
 def knob_builds():
     d = Dev()
     out = {}
@@ -200,8 +168,7 @@ def test_grid_and_poison_identical(tmp_path, env):
     """The same bytes as the default run (and the host build) at AIM_CHIP_CUS 1 and 256 and under the three AIM_DEBUG_POISON_* knobs."""
     from aim_amd import engine
     f = str(tmp_path / "k.npz")
-    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    child.run("test_index_device_gpu", "knob_builds", npz=f, env=env)
     out = np.load(f)
     default = knob_builds()
     for k in (8, 11):
@@ -210,32 +177,20 @@ def test_grid_and_poison_identical(tmp_path, env):
             assert np.array_equal(out[key], default[key]) and np.array_equal(out[key], want), (key, env)
 
 
-CHAIN_CHILD = '''
-import sys
-import torch
-torch.cuda.init()   # (before the library: the device buffers are torch's)
-sys.path.insert(0, "tests")
-import test_index_device_gpu as t
-t.chain_on_device()
-print("INDEX_CHAIN_OK")
-'''
-
-
 def test_chain_into_seeding():
-    p = subprocess.run([sys.executable, "-c", CHAIN_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "INDEX_CHAIN_OK" in p.stdout, p.stdout + p.stderr
+    p = child.run("test_index_device_gpu", "chain_on_device", cuda_first=True, marker="INDEX_CHAIN_OK")
+    assert "INDEX_CHAIN_OK" in p.stdout, p.stdout + p.stderr
 
 
 def chain_on_device():
     """engine.build_index_device (bytes, an array and a device tensor in) and seed_candidates on the tensors it returned: every
     output array equals that of the same call with the host-built index."""
     import torch
-    import test_seed_gpu as sg
     from aim_amd import engine
-    d = sg.data()
-    ref = d["ref"]
-    k, stride, max_occ, band, flank, min_votes, K = sg.CASES[0]
-    assert k == 11
+    ref = pb.reference()
+    rows, rl = pb.short_reads()[:2]
+    k, stride, w, max_occ, band, flank, min_votes, K = pb.FULL[0]
+    assert k == 11 and w is None
     want_b, want_p = engine.build_index(ref, k, threads=4)
     dev = torch.device("cuda:0")
     d_ref = torch.zeros(len(ref) + 16, dtype=torch.uint8, device=dev)
@@ -245,9 +200,9 @@ def chain_on_device():
         assert d_bucket.dtype == torch.uint8 and d_pos.dtype == torch.uint8 and d_pos.numel() == 4 * (len(ref) - k + 1)
         assert n_pos == len(want_p) and np.array_equal(d_bucket.cpu().numpy().view(np.uint32), want_b)
         assert np.array_equal(d_pos.cpu().numpy().view(np.uint32)[:n_pos], want_p)
-    sp = engine.seed_params(k, sg.READ_SIZE, stride=stride, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K)
-    on_dev = engine.seed_candidates(sp, built[0][:2], len(ref), d["rl"], d["rows"])
-    on_host = engine.seed_candidates(sp, (want_b, want_p), len(ref), d["rl"], d["rows"])
+    sp = engine.seed_params(k, pb.READ_SIZE, stride=stride, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K)
+    on_dev = engine.seed_candidates(sp, built[0][:2], len(ref), rl, rows)
+    on_host = engine.seed_candidates(sp, (want_b, want_p), len(ref), rl, rows)
     assert (on_host["seed"]["n_cands"] > 0).any()
     for name in ("req", "text_pos", "votes", "seed"):
         assert on_dev[name].tobytes() == on_host[name].tobytes(), name

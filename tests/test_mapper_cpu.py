@@ -13,6 +13,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from mapper_batch import REFUSALS, params_with as _params, record as _record  # noqa: E402
 HEADER = os.path.join(ROOT, "include", "aim_hip.h")
 
 
@@ -83,58 +84,6 @@ def test_model_properties(K):
     assert seen["unmapped"] >= 1 and (K == 1 or (seen["multi"] > 20 and seen["ties"] > 5 and seen["moved"] > 5)), seen
 
 
-def _params(**kw):
-    """aim_mapper_params_t that every check accepts, then the overrides: seed_<field>, ext_<field> or a field of the struct itself."""
-    from aim_amd import engine
-    sp = engine.seed_params(11, 1024, max_occ=8, band=96, flank=16, min_votes=2, max_cands=4, w=10)
-    mp = engine.mapper_params(sp, 64, 76, extend=engine.extend_params(), slots=2)
-    for name, v in kw.items():
-        if name.startswith("seed_"):
-            setattr(mp.seed, name[5:], v)
-        elif name.startswith("ext_"):
-            setattr(mp.extend, name[4:], v)
-        else:
-            setattr(mp, name, v)
-    return mp
-
-
-REFUSALS = [
-    (dict(seed_k=15), "k 15 is outside 8..14"),
-    (dict(seed_options=0), "options 0x0 must be AIM_SEED_OPT_MINIMIZERS(w)"),
-    (dict(seed_options=(10 << 8) | 1), "unknown options"),
-    (dict(seed_stride=2), "stride 2 must be 1 with AIM_SEED_OPT_MINIMIZERS"),
-    (dict(seed_max_occ=0), "max_occ 0 must be >= 1"),
-    (dict(seed_band=4097), "band 4097 is above 4096"),
-    (dict(seed_flank=-1), "flank -1 must be >= 0"),
-    (dict(seed_min_votes=0), "min_votes 0 must be >= 1"),
-    (dict(seed_max_cands=17), "max_cands 17 is outside 1..16"),
-    (dict(seed_read_size=4104), "read_size 4104 must be a positive multiple of 8, at most 4096 (aim_seed_chain_device)"),
-    (dict(seed_read_size=1020), "read_size 1020 must be a positive multiple of 8"),
-    (dict(max_hits=1000), "max_hits 1000 must be a power of two in 1024..8192"),
-    (dict(max_hits=1024, seed_read_size=65536), "at most 65528 (aim_seed_chain_long_device)"),
-    (dict(max_hits=1024, seed_options=0), "takes minimizer seeds only"),
-    (dict(mask_q8=0), "mask_q8 0 is outside 1..256"),
-    (dict(mask_q8=257), "mask_q8 257 is outside 1..256"),
-    (dict(max_reads=1 << 30), "n_reads 1073741824 * max_cands 4 does not fit 32 bits"),
-    (dict(ext_match=0), "match 0 must be >= 1"),
-    (dict(ext_band=32), "band 32 is outside 1..31"),
-    (dict(ext_max_ext=7), "max_ext 7 is outside 8..1024"),
-    (dict(ext_max_cost=4096), "max_cost 4096 is outside 1..4095"),
-    (dict(ext_mismatch=40), "is above 64"),
-    (dict(gap_o=0), "penalties must be"),
-    (dict(match=1), "penalties must be"),
-    (dict(gap_e=4), "AIM_FLAG_ENDSFREE needs gap_o + gap_e <= 11 * mismatch and gap_e <= mismatch"),
-    (dict(gap_o=40), "AIM_FLAG_ENDSFREE needs gap_o + gap_e <= 11 * mismatch"),
-    (dict(max_score=-1), "max_score must be >= 0"),
-    (dict(sam_options=2), "unknown sam_options 0x2"),
-    (dict(max_reads=1 << 18), "max_reads * K * (4 * read_size + 10) must stay below 2^32"),
-    (dict(options=2), "unknown options 0x2"),
-    (dict(max_reads=0), "max_reads must be >= 1"),
-    (dict(slots=0), "slots 0 is outside 1..4"),
-    (dict(slots=5), "slots 5 is outside 1..4"),
-]
-
-
 @pytest.mark.parametrize("case", REFUSALS, ids=lambda c: "-".join("%s=%s" % kv for kv in c[0].items()))
 def test_mapper_refusals_need_no_device(case):
     """Each condition alone, from aim_mapper_device_bytes and from aim_mapper_create, under that entry point's name, before any device
@@ -203,18 +152,6 @@ def test_map_kernels_code_objects():
 
 
 # ---- samout ----------------------------------------------------------------------------------------------------------------------
-def _record(read, rank, n, flags, pos, mapq, nm, score, words, md, cigar, mdbuf, status=0):
-    from aim_amd import capi
-    rec = np.zeros(1, dtype=capi.MAP_RECORD_DTYPE)[0]
-    rec["read"], rec["rank"], rec["n_records"], rec["mapq"] = read, rank, n, mapq
-    s = rec["sam"]
-    s["flags"], s["pos"], s["nm"], s["score"], s["status"] = flags, pos, nm, score, status
-    s["cigar_offset"], s["n_cigar"], s["md_offset"], s["md_len"] = len(cigar), len(words), len(mdbuf), len(md)
-    cigar.extend(words)
-    mdbuf.extend(md.encode())
-    return rec
-
-
 def test_samout_whole_text():
     """A forward read, a reverse read, an unmapped read and a two-record read (the supplementary line first in rank order, so the SA
     tags show the non-supplementary sibling first)."""
@@ -296,7 +233,7 @@ def test_batch_premises_on_the_chain_model():
     import chain_class_model as ccm
     import mapper_batch as mb
     import split_model as sm
-    from test_seed_chain_gpu import expected, reference
+    from pipeline_batches import expected, reference
     ref = reference()
     rows, rl = mb.random_reads()
     assert (expected(ccm.CHIMERIC_ROW, rows, rl, ("mapper random", mb.RANDOM_SEED), read_size=ccm.CHIMERIC_SIZE)[3]["n_cands"] == 0).all()

@@ -14,6 +14,10 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import child  # noqa: E402
+from gpu_buffers import Hip  # noqa: E402
+from hand_stages import single_end as hand_path  # noqa: E402
+from mapper_batch import map_alone  # noqa: E402
 
 KS = (1, 4, 16)
 N_READS = (1, 65, 2100)             # one group, across a wavefront, and 2 101 scan entries: three scan parts of 1 024
@@ -29,10 +33,9 @@ def run_map_records(h, K, n, seg, sam, cls):
     """aim_map_records_device over uploaded tables; d_rec_offsets, d_records (room for n * K records and a guard) and the scratch are
     prefilled with 0xEE: (rec_offsets, the whole record buffer as bytes)."""
     from aim_amd import engine
-    d_off = h.up(np.full(4 * (n + 1) + GUARD, 0xEE, dtype=np.uint8))
-    d_rec = h.up(np.full(64 * n * K + GUARD, 0xEE, dtype=np.uint8))
+    d_off, d_rec = h.filled(4 * (n + 1) + GUARD), h.filled(64 * n * K + GUARD)
     sb = engine.map_records_scratch(n)
-    engine.map_records_device(K, n, h.up(seg), h.up(sam), h.up(cls), d_off, d_rec, h.up(np.full(sb, 0xEE, dtype=np.uint8)), sb)
+    engine.map_records_device(K, n, h.up(seg), h.up(sam), h.up(cls), d_off, d_rec, h.filled(sb), sb)
     return h.down(d_off, 4 * (n + 1) + GUARD), h.down(d_rec, 64 * n * K + GUARD)
 
 
@@ -53,44 +56,29 @@ def check_against_model(K, n, off_bytes, rec_bytes):
 @pytest.mark.parametrize("K", KS)
 def test_map_records_equal_model(K):
     import map_records_model as mm
-    from test_sam_fields_gpu import Hip
     seg, sam, cls = tables(K, 65)
     mapped = mm.mapped_slots(K, 65, seg, sam)
     assert not mapped[0].any() and mapped[1].all() and len(set(seg["q_begin"][K:2 * K].tolist())) == 1 and (sam["status"][3 * K:4 * K] & mm.SAM_OVERFLOW).all()
     assert K == 1 or (not mapped[2, 0] and mapped[2, K - 1])
-    h = Hip()
-    try:
+    with Hip() as h:
         for n in N_READS:
             check_against_model(K, n, *run_map_records(h, K, n, *tables(K, n)))
             h.free()
         from aim_amd import engine                       # an empty batch: rec_offsets[0] = 0 and nothing else
-        d_off = h.up(np.full(8, 0xEE, dtype=np.uint8))
+        d_off = h.filled(8)
         engine.map_records_device(K, 0, None, None, None, d_off, None, None, 0)
         assert h.down(d_off, 8).tolist() == [0, 0, 0, 0, 0xEE, 0xEE, 0xEE, 0xEE]
-    finally:
-        h.free()
 
 
-KNOB_CHILD = '''
-import sys
-import numpy as np
-sys.path.insert(0, "tests")
-import test_mapper_gpu as t
-np.savez(sys.argv[1], **t.knob_batch())
-'''
 KNOB_CASES = ((4, 2100), (16, 65), (1, 2100))
 
 
 def knob_batch():
-    from test_sam_fields_gpu import Hip
     out = {}
-    h = Hip()
-    try:
+    with Hip() as h:
         for i, (K, n) in enumerate(KNOB_CASES):
             out["off_%d" % i], out["rec_%d" % i] = run_map_records(h, K, n, *tables(K, n))
             h.free()
-    finally:
-        h.free()
     return out
 
 
@@ -100,9 +88,7 @@ def test_grid_and_poison_identical(tmp_path, env):
     """The same bytes -- the model's -- at AIM_CHIP_CUS 1 (8 workgroups walk the 33 blocks of reads) and 256 and under the three
     AIM_DEBUG_POISON_* knobs; the scan runs over three parts either way."""
     f = str(tmp_path / "k.npz")
-    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, AIM_PLAN_DEBUG="1", **env), capture_output=True, text=True,
-                       timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    p = child.run("test_mapper_gpu", "knob_batch", npz=f, env=dict(env, AIM_PLAN_DEBUG="1"))
     grid = 8 if env["AIM_CHIP_CUS"] == "1" else 33
     line = "[aim plan] map_count_kernel grid=%d block=256 lanes=4 reads=2100 K=4; scan parts=3 per_part=1024; map_records_kernel grid=%d block=256"
     assert line % (grid, grid) in p.stderr, p.stderr
@@ -113,59 +99,6 @@ def test_grid_and_poison_identical(tmp_path, env):
 
 
 # ---- the mapper end to end ---------------------------------------------------------------------------------------------------------
-def copy_out(out):
-    """A mapper result detached from the slot's pinned buffers."""
-    return {k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
-
-
-def map_alone(mp, ref, rl, rows):
-    from aim_amd import engine
-    with engine.Mapper(mp, ref) as m:
-        m.submit(0, rl, rows)
-        return copy_out(m.wait(0))
-
-
-def hand_path(extend):
-    """The stages one by one through the engine helpers on torch buffers, one synchronize per stage, then the record model over the
-    downloaded rows: a dict shaped like a mapper result."""
-    import torch
-    import chain_class_model as ccm
-    import map_records_model as mm
-    import mapper_batch as mb
-    from aim_amd import capi, engine
-    lib = capi.load()
-    b = mb.batch()
-    ref, rows, rl = b["ref"], b["rows"], b["read_len"]
-    k, stride, w, max_occ, band, flank, min_votes, K = ccm.CHIMERIC_ROW
-    rs, n = ccm.CHIMERIC_SIZE, len(rl)
-    dev = torch.device("cuda:0")
-    params = engine.make_params("wfa", mb.max_score(), rs, mismatch=mb.X, gap_o=mb.O, gap_e=mb.E, backtrace=True, ref_texts=True, ends_free=(0, 0, 2 * flank, 2 * flank))
-    rows_n = n * K
-    d_ref = torch.zeros(len(ref) + 64, dtype=torch.uint8, device=dev)
-    d_ref[:len(ref)] = torch.from_numpy(ref).to(dev)
-    sp = engine.seed_params(k, rs, stride=stride, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K, w=w)
-    out = engine.split_segments(sp, engine.chain_classify(sp, engine.seed_chain_candidates(sp, engine.index_build_minimizers(ref, k, w), len(ref), rl, rows)), len(ref))
-    if extend:
-        out = engine.extend_segments(sp, out, d_ref[:len(ref)], engine.extend_params(*mb.EXTEND))
-    d_res = torch.zeros(rows_n * capi.RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_ops = torch.zeros(rows_n * 2 * rs + 64, dtype=torch.uint8, device=dev)
-    sb = lib.aim_scratch_bytes(capi.params_ref(params), rows_n)
-    d_scr = torch.zeros(max(sb, 16), dtype=torch.uint8, device=dev)
-    ccap, mcap = rows_n * 64, rows_n * 256
-    buf = (torch.zeros(rows_n * 48, dtype=torch.uint8, device=dev), torch.zeros(ccap * 4, dtype=torch.uint8, device=dev),
-           torch.zeros(mcap, dtype=torch.uint8, device=dev), torch.zeros(8, dtype=torch.uint8, device=dev))
-    torch.cuda.synchronize()
-    rc = lib.aim_align_device_ref(capi.params_ref(params), rows_n, out["d_seg_req"].data_ptr(), out["d_seg_patterns"].data_ptr(), out["d_seg_text_pos"].data_ptr(),
-                                  d_ref.data_ptr(), len(ref), d_res.data_ptr(), d_ops.data_ptr(), d_scr.data_ptr(), sb, None)
-    assert rc == 0, lib.aim_last_error()
-    engine.sam_device_split(params, rows_n, out["d_seg_req"].data_ptr(), out["d_seg_text_pos"].data_ptr(), None, d_res.data_ptr(), d_ops.data_ptr(), d_ref.data_ptr(),
-                            len(ref), 0, buf[0].data_ptr(), buf[1].data_ptr(), ccap, buf[2].data_ptr(), mcap, buf[3].data_ptr(), out["d_seg"].data_ptr())
-    torch.cuda.synchronize()
-    sam = buf[0].cpu().numpy().view(capi.SAM_DTYPE)
-    off, rec = mm.map_records(K, n, out["seg"], sam, out["class"])
-    return {"records": rec, "rec_offsets": off, "cigar": buf[1].cpu().numpy().view(np.uint32), "md": buf[2].cpu().numpy()}
-
-
 def end_to_end():
     """The shared batch through aim_mapper_t, with and without AIM_MAP_EXTEND, against hand_path: the same records byte for byte apart
     from the two offsets, the same words and MD bytes behind them; two records per chimeric read, one of them supplementary, CIGARs
@@ -212,19 +145,8 @@ def end_to_end():
         print("extend", extend, "records", len(rec), "words", got["cigar_needed"], "md", got["md_needed"])
 
 
-PATH_CHILD = '''
-import sys
-import torch
-torch.cuda.init()   # (before the library: the hand-driven path's buffers are torch's)
-sys.path.insert(0, "tests")
-import test_mapper_gpu as t
-t.end_to_end()
-print("MAPPER_END_TO_END_OK")
-'''
-
-
 def test_end_to_end_equals_the_stages_by_hand():
-    p = subprocess.run([sys.executable, "-c", PATH_CHILD], cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=300)
+    p = child.run("test_mapper_gpu", "end_to_end", cuda_first=True, marker="MAPPER_END_TO_END_OK", check=False)
     print(p.stdout[-3000:])
     assert p.returncode == 0 and "MAPPER_END_TO_END_OK" in p.stdout, p.stdout + p.stderr
 

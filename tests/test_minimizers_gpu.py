@@ -4,7 +4,6 @@ its halo; references on which the halo decides; any CU count, poison knob and sc
 AIM_SEED_OPT_MINIMIZERS equals the model in every byte of requests, text_pos, votes and aim_seed_t. And the chain: device index,
 minimizer seeds, aim_align_device_groups."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,24 +11,18 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from test_index_device_gpu import Dev, T  # noqa: E402  (the device buffers and kIndexTile)
+import child  # noqa: E402
+from gpu_buffers import Hip, cached  # noqa: E402
+from pipeline_batches import index_tile  # noqa: E402
 
 READ_SIZE = 128
-_CACHE = {}
-
-
-def cached(key, make):
-    if key not in _CACHE:
-        _CACHE[key] = make()
-    return _CACHE[key]
+T = index_tile()
 
 
 def random_ref(n):
     """Seeded random A C G T; a shorter one is a prefix of a longer one."""
-    full = cached("rand", lambda: np.frombuffer(b"ACGT", dtype=np.uint8)[np.random.default_rng(4711).integers(0, 4, 2 * T + 200)])
+    full = cached("minimizer rand", lambda: np.frombuffer(b"ACGT", dtype=np.uint8)[np.random.default_rng(4711).integers(0, 4, 2 * T + 200)])
     assert n <= len(full)
     return full[:n]
 
@@ -39,23 +32,20 @@ def random_ref(n):
 def build(ref, k, w, fill=0xEE):
     """aim_index_build_device_minimizers on `ref` over outputs and scratch full of `fill`: (bucket[4^k + 1], pos[:n_pos])."""
     from aim_amd import engine
-    dev = Dev()
-    try:
+    with Hip() as h:
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         be, pc = engine.index_sizes(k, len(ref))
         sb = engine.index_device_scratch(k, len(ref))
-        d_ref = dev.h.up(ref, 16)
-        d_bucket = dev.alloc(be * 4, fill)
-        d_pos = dev.alloc(pc * 4, fill) if pc else None
-        d_scr = dev.alloc(sb, fill) if sb else None
+        d_ref = h.up(ref, 16)
+        d_bucket = h.alloc(be * 4, fill)
+        d_pos = h.alloc(pc * 4, fill) if pc else None
+        d_scr = h.alloc(sb, fill) if sb else None
         engine.index_build_device_minimizers(d_ref, len(ref), k, w, d_bucket, d_pos, d_scr, sb)
-        bucket = dev.h.down(d_bucket, be * 4).view(np.uint32)
+        bucket = h.down(d_bucket, be * 4).view(np.uint32)
         n_pos = int(bucket[-1])
         assert n_pos <= pc
-        pos = dev.h.down(d_pos, n_pos * 4).view(np.uint32) if n_pos else np.zeros(0, dtype=np.uint32)
+        pos = h.down(d_pos, n_pos * 4).view(np.uint32) if n_pos else np.zeros(0, dtype=np.uint32)
         return bucket, pos
-    finally:
-        dev.close()
 
 
 def model_bucket(ref, k, w):
@@ -178,14 +168,6 @@ def test_scratch_and_outputs_are_only_that():
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
-KNOB_CHILD = '''
-import sys
-import numpy as np
-sys.path.insert(0, "tests")
-import test_minimizers_gpu as t
-np.savez(sys.argv[1], **t.knob_batch())
-'''
-
 KNOB_ENVS = [{"AIM_CHIP_CUS": "1", "AIM_DEBUG_POISON_SCRATCH": "165", "AIM_DEBUG_POISON_OPS": "77", "AIM_DEBUG_POISON_LDS": "90"},
              {"AIM_CHIP_CUS": "256", "AIM_DEBUG_POISON_LDS": "255"}]
 KNOB_INDEX = [(8, 16), (11, 5), (8, 32)]
@@ -217,8 +199,7 @@ def test_grid_and_poison_identical(tmp_path, env):
     """The same bytes -- the host build's and the model's -- at AIM_CHIP_CUS 1 and 256 and under the three AIM_DEBUG_POISON_* knobs."""
     from aim_amd import engine
     f = str(tmp_path / "k.npz")
-    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    child.run("test_minimizers_gpu", "knob_batch", npz=f, env=env)
     out = np.load(f)
     for k, w in KNOB_INDEX:
         want_b, want_p = engine.index_build_minimizers(knob_ref(), k, w, threads=4)
@@ -237,7 +218,7 @@ def seed_data():
         ref = m.make_reference()
         rows, rl, true_pos, strand, plain = m.make_reads(ref, 192, READ_SIZE)
         return dict(ref=ref, rows=rows, rl=rl, strand=strand, plain=plain)
-    return cached("seed_data", make)
+    return cached("minimizer seed_data", make)
 
 
 def seed_case(k, w):
@@ -247,7 +228,7 @@ def seed_case(k, w):
 
 def model_index(ref_key, ref, k, w):
     import minimizer_model as mm
-    return cached(("index", ref_key, k, w), lambda: mm.build_index(ref, k, w))
+    return cached(("minimizer index", ref_key, k, w), lambda: mm.build_index(ref, k, w))
 
 
 def expected(case, ref_key="model", ref=None, rows=None, rl=None, read_size=READ_SIZE):
@@ -257,14 +238,13 @@ def expected(case, ref_key="model", ref=None, rows=None, rl=None, read_size=READ
     d = seed_data()
     ref = d["ref"] if ref is None else ref
     rows, rl = (d["rows"], d["rl"]) if rows is None else (rows, rl)
-    return cached(("expected", case, ref_key, read_size),
+    return cached(("minimizer expected", case, ref_key, read_size),
                   lambda: mm.seed(rows, rl, model_index(ref_key, ref, k, w), len(ref), k, w, max_occ, band, flank, min_votes, K, read_size))
 
 
 def run_seed(case, ref, rows, rl, read_size=READ_SIZE, options=None):
     """aim_seed_device over buffers uploaded through the HIP runtime the library loaded; the index is the library's host build for
     (k, w). options: the value to send instead of AIM_SEED_OPT_MINIMIZERS(w)."""
-    from test_sam_fields_gpu import Hip
     from aim_amd import capi, engine
     k, w, max_occ, band, flank, min_votes, K = case
     sp = engine.seed_params(k, read_size, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K, w=w)
@@ -272,17 +252,13 @@ def run_seed(case, ref, rows, rl, read_size=READ_SIZE, options=None):
         sp.options = options
     bucket, pos = engine.index_build_minimizers(ref, k, w, threads=4)
     n = len(rl)
-    h = Hip()
-    try:
+    with Hip() as h:
         d_b, d_p = h.up(bucket), h.up(pos)
         d_rl, d_rows = h.up(np.ascontiguousarray(rl, dtype=np.int32)), h.up(rows, 64)
-        d_req, d_tp = h.up(np.full(n * K * 16, 0xEE, dtype=np.uint8)), h.up(np.full(n * K * 8, 0xEE, dtype=np.uint8))
-        d_v, d_s = h.up(np.full(n * K * 4, 0xEE, dtype=np.uint8)), h.up(np.full(n * 16, 0xEE, dtype=np.uint8))
+        d_req, d_tp, d_v, d_s = h.filled(n * K * 16), h.filled(n * K * 8), h.filled(n * K * 4), h.filled(n * 16)
         engine.seed_device(sp, n, d_rl, d_rows, d_b, d_p, len(ref), d_req, d_tp, d_v, d_s)
         return (h.down(d_req, n * K * 16).view(capi.REQUEST_DTYPE), h.down(d_tp, n * K * 8).view(np.uint64),
                 h.down(d_v, n * K * 4).view(np.uint32), h.down(d_s, n * 16).view(capi.SEED_DTYPE))
-    finally:
-        h.free()
 
 
 def assert_equal(got, want):
@@ -364,20 +340,9 @@ def test_read_size_4096():
 
 # ---- the chain ------------------------------------------------------------------------------------------------------------------
 
-CHAIN_CHILD = '''
-import sys
-import torch
-torch.cuda.init()   # (before the library: the device buffers are torch's)
-sys.path.insert(0, "tests")
-import test_minimizers_gpu as t
-t.chain_on_device()
-print("MINIMIZER_CHAIN_OK")
-'''
-
-
 def test_chain_on_device():
-    p = subprocess.run([sys.executable, "-c", CHAIN_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "MINIMIZER_CHAIN_OK" in p.stdout, p.stdout + p.stderr
+    p = child.run("test_minimizers_gpu", "chain_on_device", cuda_first=True, marker="MINIMIZER_CHAIN_OK")
+    assert "MINIMIZER_CHAIN_OK" in p.stdout, p.stdout + p.stderr
 
 
 def chain_on_device():

@@ -404,7 +404,7 @@ def test_samout_paired_whole_text():
     """A proper pair on one contig, a pair on two contigs, a mapped read with an unmapped mate (written at its mate's place) and a
     pair of unmapped reads; the second read of the first pair has a supplementary record, whose line carries the same mate fields."""
     from aim_amd import capi, samout
-    from test_mapper_cpu import _record
+    from mapper_batch import record as _record
     w = lambda n, op: (n << 4) | op
     cigar, md = [], []
     recs = [_record(0, 0, 1, 0x1 | 0x2 | 0x20 | 0x40, 99, 60, 0, 0, [w(8, 0)], "8", cigar, md),

@@ -15,6 +15,9 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import child  # noqa: E402
+import hand_stages as hs  # noqa: E402
+from gpu_buffers import Hip, copy_out, put, zeros  # noqa: E402
 
 KS = (1, 4, 16)
 N_READS = (2, 130, 4100)            # one group, across wavefronts, and more read pairs than one workgroup of any K holds
@@ -36,7 +39,7 @@ def run_stages(h, K, n, t, rescue=True):
     from aim_amd import engine
     rs, rz = pm.READ_SIZE, pm.RESCUE_SIZE
     pp = engine.pair_params(pm.MIN_SPAN, pm.MAX_SPAN, 17, rescue=rescue, rescue_size=rz)
-    ee = lambda nbytes: h.up(np.full(nbytes + GUARD, 0xEE, dtype=np.uint8))
+    ee = lambda nbytes: h.filled(nbytes + GUARD)
     contigs = t["contig"] is not None
     d_rl, d_reads = h.up(t["read_len"]), h.up(t["reads"], 16)
     d_seg, d_sam, d_cls, d_res_sam = h.up(t["seg"]), h.up(t["sam"]), h.up(t["cls"]), h.up(t["res_sam"])
@@ -57,7 +60,7 @@ def run_stages(h, K, n, t, rescue=True):
         out["contig"] = h.down(d_contig, 4 * n * K)
     d_off, d_rec, d_mates = ee(4 * (n + 1)), ee(64 * n * K), ee(16 * n * K)
     sb = engine.map_records_scratch(n)
-    d_scr = h.up(np.full(sb, 0xEE, dtype=np.uint8))
+    d_scr = h.filled(sb)
     if contigs:
         engine.map_records_contigs_device(K, n, d_seg, d_sam, d_cls, d_contig, nc, d_starts, d_off, d_rec, d_scr, sb)
     else:
@@ -126,9 +129,7 @@ def check_against_model(K, n, contigs, out, rescue=True):
 @pytest.mark.parametrize("K", KS)
 def test_stages_equal_model(K, contigs):
     import pair_model as pm
-    from test_sam_fields_gpu import Hip
-    h = Hip()
-    try:
+    with Hip() as h:
         for n in N_READS:
             pairs = check_against_model(K, n, contigs, run_stages(h, K, n, tables(K, n, contigs)))
             h.free()
@@ -144,31 +145,18 @@ def test_stages_equal_model(K, contigs):
         engine.pair_rescue_rows_device(pp, K, pm.READ_SIZE, 1000, 0, None, None, None, None, None, None, None)
         engine.pair_select_device(pp, K, pm.READ_SIZE, 0, None, None, None, None, None, 0, 0, None)
         engine.map_mates_device(K, 0, None, None, None, None, None, None)
-    finally:
-        h.free()
 
 
-KNOB_CHILD = '''
-import sys
-import numpy as np
-sys.path.insert(0, "tests")
-import test_pairs_gpu as t
-np.savez(sys.argv[1], **t.knob_batch())
-'''
 KNOB_CASES = ((4, 4100, True), (16, 130, False), (1, 4100, False))
 
 
 def knob_batch():
-    from test_sam_fields_gpu import Hip
     out = {}
-    h = Hip()
-    try:
+    with Hip() as h:
         for i, (K, n, contigs) in enumerate(KNOB_CASES):
             for k, v in run_stages(h, K, n, tables(K, n, contigs)).items():
                 out["%s_%d" % (k, i)] = v
             h.free()
-    finally:
-        h.free()
     return out
 
 
@@ -178,9 +166,7 @@ def test_grid_and_poison_identical(tmp_path, env):
     """The same bytes -- the model's -- at AIM_CHIP_CUS 1 (8 workgroups walk the 33 blocks of read pairs and the 65 blocks of records)
     and 256, and under the three AIM_DEBUG_POISON_* knobs."""
     f = str(tmp_path / "k.npz")
-    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, AIM_PLAN_DEBUG="1", **env), capture_output=True, text=True,
-                       timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    p = child.run("test_pairs_gpu", "knob_batch", npz=f, env=dict(env, AIM_PLAN_DEBUG="1"))
     grid, mgrid = (8, 8) if env["AIM_CHIP_CUS"] == "1" else (33, 65)
     assert "[aim plan] pair_rescue_rows_kernel grid=%d block=256 lanes=4 reads=4100 K=4 rescue_size=512" % grid in p.stderr, p.stderr
     assert "[aim plan] pair_select_kernel grid=%d block=256 lanes=4 reads=4100 K=4 rescue=1" % grid in p.stderr, p.stderr
@@ -192,10 +178,6 @@ def test_grid_and_poison_identical(tmp_path, env):
 
 
 # ---- the mapper with pairing ---------------------------------------------------------------------------------------------------------
-def copy_out(out):
-    return {k: (np.array(v, copy=True) if isinstance(v, np.ndarray) else v) for k, v in out.items()}
-
-
 def make_mapper(mp, contigs):
     import pair_batch as pb
     from aim_amd import engine
@@ -224,7 +206,6 @@ def hand_path(contigs, rescue):
     import pair_batch as pb
     import pair_model as pm
     from aim_amd import capi, engine
-    lib = capi.load()
     b = pb.batch()
     rows, rl = b["rows"], b["read_len"]
     K, rs, rz, flank, n = pb.K, pb.READ_SIZE, pb.RESCUE_SIZE, pb.FLANK, len(b["read_len"])
@@ -236,67 +217,42 @@ def hand_path(contigs, rescue):
         lens = np.array([len(s) for s in seqs], dtype=np.uint32)
     else:
         ref = pb.reference()
-    dev = torch.device("cuda:0")
-    zeros = lambda nbytes: torch.zeros(max(nbytes, 16), dtype=torch.uint8, device=dev)
-    params = engine.make_params("wfa", pb.MAX_SCORE, rs, mismatch=pb.X, gap_o=pb.O, gap_e=pb.E, backtrace=True, ref_texts=True, ends_free=(0, 0, 2 * flank, 2 * flank))
-    rparams = engine.make_params("wfa", pb.MAX_SCORE, rz, mismatch=pb.X, gap_o=pb.O, gap_e=pb.E, backtrace=True, ref_texts=True, ends_free=(0, 0, rz, rz))
+    dev = hs.DEV
+    params = hs.wfa_params(pb.MAX_SCORE, rs, pb.X, pb.O, pb.E, 2 * flank)
+    rparams = hs.wfa_params(pb.MAX_SCORE, rz, pb.X, pb.O, pb.E, rz)
     rows_n = n * K
-    d_ref = zeros(len(ref) + 64)
-    d_ref[:len(ref)] = torch.from_numpy(ref).to(dev)
-    sp = pb.seed_params()
-    out = engine.split_segments(sp, engine.chain_classify(sp, engine.seed_chain_candidates(sp, engine.index_build_minimizers(ref, pb.K_MER, pb.W), len(ref), rl, rows)), len(ref))
-    d_ct = d_st = d_ln = None
-    if contigs:
-        d_st, d_ln = torch.from_numpy(starts.view(np.int32)).to(dev), torch.from_numpy(lens.view(np.int32)).to(dev)
-        d_ct = torch.full((rows_n,), -286331154, dtype=torch.int32, device=dev)
-        torch.cuda.synchronize()
-        engine.contig_clip_device(K, rs, flank, len(ref), len(starts), d_st.data_ptr(), d_ln.data_ptr(), n, out["d_read_len"].data_ptr(), out["d_req"].data_ptr(),
-                                  out["d_text_pos"].data_ptr(), out["d_chains"].data_ptr(), out["d_seg_req"].data_ptr(), out["d_seg_text_pos"].data_ptr(),
-                                  out["d_seg"].data_ptr(), d_ct.data_ptr())
+    d_ref = put(ref, dev, 64)
+    out = hs.segment_rows(pb.seed_params(), ref, rl, rows)
+    d_ct, d_st, d_ln = hs.clip_contigs(out, K, rs, flank, len(ref), starts, lens, n) if contigs else (None, None, None)
     ptr = lambda t: None if t is None else t.data_ptr()
     ccap, mcap, rccap, rmcap = rows_n * 64, rows_n * 256, n * 64, n * 256
-    d_sam, d_cigar, d_md, d_cur = zeros(rows_n * 48), zeros((ccap + rccap) * 4), zeros(mcap + rmcap), zeros(8)
-
-    def align(p, count, d_req, d_pat, d_tp):
-        d_res, d_ops = zeros(count * capi.RESULT_DTYPE.itemsize), zeros(count * 2 * p.read_size + 64)
-        sb = lib.aim_scratch_bytes(capi.params_ref(p), count)
-        d_scr = zeros(sb)
-        torch.cuda.synchronize()
-        rc = lib.aim_align_device_ref(capi.params_ref(p), count, d_req.data_ptr(), d_pat.data_ptr(), d_tp.data_ptr(), d_ref.data_ptr(), len(ref), d_res.data_ptr(),
-                                      d_ops.data_ptr(), d_scr.data_ptr(), sb, None)
-        assert rc == 0, lib.aim_last_error()
-        torch.cuda.synchronize()
-        return d_res, d_ops
-    d_res, d_ops = align(params, rows_n, out["d_seg_req"], out["d_seg_patterns"], out["d_seg_text_pos"])
-    engine.sam_device_split(params, rows_n, out["d_seg_req"].data_ptr(), out["d_seg_text_pos"].data_ptr(), None, d_res.data_ptr(), d_ops.data_ptr(), d_ref.data_ptr(),
-                            len(ref), 0, d_sam.data_ptr(), d_cigar.data_ptr(), ccap, d_md.data_ptr(), mcap, d_cur.data_ptr(), out["d_seg"].data_ptr())
-    torch.cuda.synchronize()
+    d_cigar, d_md = zeros((ccap + rccap) * 4, dev), zeros(mcap + rmcap, dev)           # the rescue records go behind the main regions
+    d_res, d_ops = hs.align_rows(params, rows_n, out["d_seg_req"], out["d_seg_patterns"], out["d_seg_text_pos"], d_ref, len(ref))
+    last = hs.sam_rows(params, rows_n, out["d_seg_req"], out["d_seg_text_pos"], d_res, d_ops, d_ref, len(ref), (ccap, mcap), split_seg=out["d_seg"],
+                       into=(d_cigar, d_md, 0, 0))
+    d_sam, sam = last["d_sam"], last["sam"]
     seg = out["d_seg"].cpu().numpy().view(capi.SEGMENT_DTYPE)[:rows_n].copy()
-    sam = d_sam.cpu().numpy().view(capi.SAM_DTYPE)[:rows_n].copy()
     contig = d_ct.cpu().numpy().view(np.uint32).copy() if contigs else None
     pp = pm.Params(pb.MIN_SPAN, pb.MAX_SPAN, pb.UNPAIRED_PENALTY, pm.RESCUE if rescue else 0, rz)
     res_sam = None
     needed = [0, 0]
     if rescue:
-        d_rreq, d_rtp, d_rpat, d_rsam, d_rcur = zeros(16 * n), zeros(8 * n), zeros(n * rz + 64), zeros(48 * n), zeros(8)
+        d_rreq, d_rtp, d_rpat = zeros(16 * n, dev), zeros(8 * n, dev), zeros(n * rz + 64, dev)
         engine.pair_rescue_rows_device(pb.pair_params(n), K, rs, len(ref), n, out["d_read_len"].data_ptr(), out["d_reads"].data_ptr(), out["d_seg"].data_ptr(),
                                        d_sam.data_ptr(), d_rreq.data_ptr(), d_rtp.data_ptr(), d_rpat.data_ptr(), d_contig=ptr(d_ct), n_contigs=len(starts) if contigs else 0,
                                        d_contig_start=ptr(d_st), d_contig_len=ptr(d_ln))
         torch.cuda.synchronize()
         want_req, want_tp, want_rows = pm.rescue_rows(pp, K, rs, len(ref), n, rl, rows, seg, sam, contig, starts, lens)
         assert d_rreq.cpu().numpy()[:16 * n].tobytes() == want_req.tobytes() and d_rtp.cpu().numpy()[:8 * n].tobytes() == want_tp.tobytes()
-        d_rres, d_rops = align(rparams, n, d_rreq, d_rpat, d_rtp)
-        engine.sam_device(rparams, n, d_rreq.data_ptr(), d_rtp.data_ptr(), None, d_rres.data_ptr(), d_rops.data_ptr(), d_ref.data_ptr(), len(ref), 0, d_rsam.data_ptr(),
-                          d_cigar.data_ptr() + 4 * ccap, rccap, d_md.data_ptr() + mcap, rmcap, d_rcur.data_ptr())
-        torch.cuda.synchronize()
-        res_sam = d_rsam.cpu().numpy().view(capi.SAM_DTYPE)[:n].copy()
-        needed = d_rcur.cpu().numpy().view(np.uint32)[:2].tolist()
+        d_rres, d_rops = hs.align_rows(rparams, n, d_rreq, d_rpat, d_rtp, d_ref, len(ref))
+        last = hs.sam_rows(rparams, n, d_rreq, d_rtp, d_rres, d_rops, d_ref, len(ref), (rccap, rmcap), into=(d_cigar, d_md, ccap, mcap))
+        res_sam, needed = last["sam"], last["cur"].tolist()
         empty = want_req["pattern_len"] == 0                      # an empty row comes back unmapped at position 0, as the rule says
         assert (res_sam["flags"][empty] == pm.SAM_UNMAPPED).all() and (res_sam["pos"][empty] == 0).all() and (res_sam["n_cigar"][empty] == 0).all()
     pairs, seg2, sam2, cls2, contig2 = pm.select(pp, K, rs, n, rl, seg, sam, out["class"], contig, res_sam, ccap, mcap)
     off, rec = cg.records(K, n, seg2, sam2, cls2, contig2, starts) if contigs else mm.map_records(K, n, seg2, sam2, cls2)
     rec2, mates = pm.mates(K, n, pairs, seg2, sam2, contig2, starts, off, rec)
-    return {"records": rec2, "rec_offsets": off, "cigar": d_cigar.cpu().numpy().view(np.uint32), "md": d_md.cpu().numpy(), "mates": mates, "pairs": pairs,
+    return {"records": rec2, "rec_offsets": off, "cigar": last["cigar"], "md": last["md"], "mates": mates, "pairs": pairs,
             "rescue_cigar_needed": needed[0], "rescue_md_needed": needed[1]}
 
 
@@ -371,9 +327,8 @@ def check_truth(got, layout, contigs, rescue):
 def end_to_end():
     """The paired batch through aim_mapper_t with pairing against hand_path -- records in canon form, rec_offsets, mates and pairs, byte for
     byte -- and against the truth: one sequence and three contigs, each with and without rescue. Then a mapper on which set_pairing
-    was never called against the hand-driven single-end path of tests/test_mapper_gpu.py over its batch."""
+    was never called against the hand-driven single-end path of tests/hand_stages.py over its batch."""
     import mapper_batch as mb
-    import test_mapper_gpu as tm
     for contigs, rescue in ((False, True), (True, True), (False, False), (True, False)):
         got, layout = map_pairs(contigs, rescue)
         want = hand_path(contigs, rescue)
@@ -387,23 +342,12 @@ def end_to_end():
         check_truth(got, layout, contigs, rescue)
         print("contigs", contigs, "rescue", rescue, "records", len(got["records"]), "proper", int((got["pairs"]["flags"] & 1).sum()), "rescue words", got["rescue_cigar_needed"])
     b = mb.batch()
-    plain = tm.map_alone(mb.mapper_params(len(b["read_len"]), False), b["ref"], b["read_len"], b["rows"])
-    assert "pairs" not in plain and mb.canon(plain) == mb.canon(tm.hand_path(False))
-
-
-PATH_CHILD = '''
-import sys
-import torch
-torch.cuda.init()   # (before the library: the hand-driven path's buffers are torch's)
-sys.path.insert(0, "tests")
-import test_pairs_gpu as t
-t.end_to_end()
-print("PAIRS_END_TO_END_OK")
-'''
+    plain = mb.map_alone(mb.mapper_params(len(b["read_len"]), False), b["ref"], b["read_len"], b["rows"])
+    assert "pairs" not in plain and mb.canon(plain) == mb.canon(hs.single_end(False))
 
 
 def test_mapper_with_pairing_equals_the_stages_by_hand_and_the_truth():
-    p = subprocess.run([sys.executable, "-c", PATH_CHILD], cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=300)
+    p = child.run("test_pairs_gpu", "end_to_end", cuda_first=True, marker="PAIRS_END_TO_END_OK", check=False)
     print(p.stdout[-3000:])
     assert p.returncode == 0 and "PAIRS_END_TO_END_OK" in p.stdout, p.stdout + p.stderr
 

@@ -1,7 +1,6 @@
 """AIM_FLAG_SAM_FIELDS on the GPU. Every record is compared with tests/sam_model.py applied to the result rows, ops rows and text_pos of
 the SAME call without the flag, and every other output of the flagged call (result rows, ops ranges, compact headers and runs, best,
 mates) must equal the flag-less one. Offsets are never compared; the words and bytes they address are."""
-import ctypes as C
 import os
 import re
 import sys
@@ -13,21 +12,11 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sam_model  # noqa: E402
+from gpu_buffers import Hip  # noqa: E402
+from sam_model import HAND_ROWS, make_reference as reference  # noqa: E402
 
 MINUS = 1 << 63
 UINT32_MAX = 0xFFFFFFFF
-
-
-def reference(seed, n=300000):
-    """Random A/C/G/T with a few N runs and lowercase stretches (the MD carries reference bytes verbatim)."""
-    rng = np.random.default_rng([seed, 0x73616D])
-    ref = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=n)].copy()
-    for _ in range(n // 20000):
-        at = int(rng.integers(0, n - 600))
-        ref[at:at + int(rng.integers(1, 12))] = ord("N")
-        at = int(rng.integers(0, n - 600))
-        ref[at:at + int(rng.integers(16, 300))] |= 0x20
-    return ref
 
 
 def same_ranges(res, ops, res0, ops0):
@@ -126,47 +115,11 @@ def both(kw, ms, rs, algo, ref, req, pat, tpos, eqx=False, check=True, **sub):
     return out0, out1, exps, p0
 
 
-class Hip:
-    """The HIP runtime the library already loaded, through ctypes: device buffers for the stateless entry point."""
-
-    def __init__(self):
-        from aim_amd import capi
-        capi.load()
-        path = next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64" in line)
-        self.lib = C.CDLL(path)
-        self.lib.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-        self.lib.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        self.lib.hipFree.argtypes = [C.c_void_p]
-        self.bufs = []
-
-    def up(self, arr, slack=0):
-        a = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
-        a = np.concatenate([a, np.zeros(slack, dtype=np.uint8)]) if slack else a
-        p = C.c_void_p()
-        assert self.lib.hipMalloc(C.byref(p), max(len(a), 4)) == 0
-        self.bufs.append(p)
-        if len(a):
-            assert self.lib.hipMemcpy(p, a.ctypes.data, len(a), 1) == 0
-        return p
-
-    def down(self, p, nbytes):
-        out = np.zeros(nbytes, dtype=np.uint8)
-        assert self.lib.hipDeviceSynchronize() == 0
-        assert self.lib.hipMemcpy(out.ctypes.data, p, nbytes, 2) == 0
-        return out
-
-    def free(self):
-        for p in self.bufs:
-            self.lib.hipFree(p)
-        self.bufs = []
-
-
 def sam_device(params, res, ops, tpos, ref, sel=None, options=0, ccap=1, mcap=1, req=None):
     """aim_sam_device over rows uploaded to the device: (records, words, bytes, cursors). A guard word / byte sits behind each
     capacity."""
     from aim_amd import capi, engine
-    h = Hip()
-    try:
+    with Hip() as h:
         n = len(res)
         d_res, d_ops, d_tp = h.up(res), h.up(ops, 64), h.up(np.asarray(tpos, dtype=np.uint64))
         d_ref = h.up(ref, 16)
@@ -180,8 +133,6 @@ def sam_device(params, res, ops, tpos, ref, sel=None, options=0, ccap=1, mcap=1,
         cg, md = h.down(d_cg, 4 * (ccap + 1)).view(np.uint32), h.down(d_md, mcap + 1)
         assert int(cg[ccap]) == 0x7E7E7E7E and int(md[mcap]) == 0x7E, "written past a capacity"
         return h.down(d_sam, n * 48).view(capi.SAM_DTYPE), cg[:ccap], md[:mcap], h.down(d_cur, 8).view(np.uint32)
-    finally:
-        h.free()
 
 
 def endsfree_batch(seed, n, ref):
@@ -232,9 +183,6 @@ def test_sam_device_equals_the_pipelined_records(wfa_ef):
     exp_sel = [exp[r] if s != UINT32_MAX else (0, 0, 0, [], b"", 4) for r, s in zip(rows, sel)]
     sam, cg, md, _ = sam_device(p0, res[rows], ops[rows], tpos, ref, sel=sel, ccap=nc, mcap=nb)
     assert sam_model.check_records(sam, cg, md, exp_sel) == []
-
-
-HAND_ROWS = [b"IIIDDDII", b"DDDD", b"IDIDDMXMDIID", b"DDIMMXMII", b"MXXMIM", b"MMIIXM", b"DDDDMMMMMMMMXMMMMMDDD", b"M" * 300 + b"I" * 70 + b"XX" + b"D" * 9 + b"M" * 1100 + b"DD"]
 
 
 @pytest.mark.parametrize("wave_min", ["0", "1000000"], ids=["row-per-wavefront", "row-per-lane"])

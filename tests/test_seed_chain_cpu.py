@@ -15,9 +15,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "aim_hip.h")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from chain_model import strand_stats  # noqa: E402
 
 READ_SIZE = 128
-# (k, stride, w, max_occ, band, flank, min_votes, K): the rows of tests/test_seed_chain_gpu.py at read_size 128
+# (k, stride, w, max_occ, band, flank, min_votes, K): the rows of tests/pipeline_batches.py at read_size 128
 ROWS = [(11, 1, None, 8, 8, 8, 2, 4), (8, 1, None, 64, 48, 16, 3, 16), (14, 3, None, 1, 16, 8, 1, 8), (11, 4, None, 2, 0, 0, 1, 1),
         (11, 1, 5, 8, 32, 8, 2, 4), (13, 1, 10, 8, 32, 8, 2, 4), (8, 1, 2, 64, 48, 16, 3, 16)]
 
@@ -191,37 +192,6 @@ def test_model_properties(row):
         assert (got[nc:].view(np.uint8) == 0).all() and (got["score"][:nc] >= k).all() and (np.diff(got["score"][:nc].astype(np.int64)) <= 0).all()
         assert (got["q_lo"][:nc] + k <= got["q_hi"][:nc]).all() and (got["q_hi"][:nc] <= rl[r]).all()
         assert (votes[r * K:(r + 1) * K] == got["score"]).all()
-
-
-def branching(pred):
-    """Anchors chosen as the predecessor of two or more successors."""
-    return int((np.bincount(pred[pred >= 0]) >= 2).sum()) if (pred >= 0).any() else 0
-
-
-def tied(a, f, pred, k, band):
-    """Anchors whose best candidate score is reached by more than one admissible predecessor."""
-    import chain_model as cm
-    n_tied = 0
-    for i in np.nonzero(pred >= 0)[0]:
-        hits = 0
-        for j in range(max(0, i - cm.LOOKBACK), i):
-            d_p, d_q = a[i][0] - a[j][0], a[i][1] - a[j][1]
-            if d_p > 0 and d_q > 0 and abs(d_p - d_q) <= band and f[j] + min(d_p, d_q, k) - int(cm.cost(abs(d_p - d_q), k)) == f[i]:
-                hits += 1
-        n_tied += hits > 1
-    return n_tied
-
-
-def strand_stats(d, k, band, with_ties):
-    """What one strand's (anchors, f, pred) holds: branching anchors, links with g > 0, trees whose end is not their last anchor, and
-    (where asked: the count is quadratic) anchors with tied best predecessors."""
-    import chain_model as cm
-    a, f, pred = d
-    diag = np.array([p - j for p, j in a], dtype=np.int64)
-    linked = np.nonzero(pred >= 0)[0]
-    root, depth, ends = cm.trees(f, pred)
-    return dict(branching=branching(pred), gap_links=int((diag[linked] != diag[pred[linked]]).sum()),
-                end_not_last=sum(1 for t, e in ends.items() if e != np.nonzero(root == t)[0].max()), ties=tied(a, f, pred, k, band) if with_ties else 0)
 
 
 def test_batches_hold_what_can_go_wrong():

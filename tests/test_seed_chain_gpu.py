@@ -5,7 +5,6 @@ idx_base that wraps, windows clamped at both ends of the reference, any CU count
 kernel's buffers go straight into aim_align_device_groups, and the chained window is the one the read aligns to within the cost of
 its edits."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,81 +12,33 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import child  # noqa: E402
+from gpu_buffers import Hip  # noqa: E402
+from pipeline_batches import (FULL, LONG, LONG_DEL, LONG_EDITS, LONG_SIZE, MINIMIZER, READ_SIZE, case_id, edge_reads, expected, long_reads,  # noqa: E402
+                              reference, short_reads)
 
-READ_SIZE = 128
-# (k, stride, w, max_occ, band, flank, min_votes, K); w = None: the full index at that stride
-FULL = [(11, 1, None, 8, 8, 8, 2, 4), (8, 1, None, 64, 48, 16, 3, 16), (14, 3, None, 1, 16, 8, 1, 8), (11, 4, None, 2, 0, 0, 1, 1)]
-MINIMIZER = [(11, 1, 5, 8, 32, 8, 2, 4), (13, 1, 10, 8, 32, 8, 2, 4),
-             (8, 1, 2, 64, 48, 16, 3, 16)]   # minimizer strands that overflow the 1 024 kept hits (the reads from inside the tandem repeat)
-LONG = (11, 1, 10, 8, 96, 16, 2, 4)          # the long reads' row, at read_size 1 024
-LONG_SIZE, LONG_L, LONG_DEL, LONG_EDITS = 1024, 800, 60, 80
 NAMES = ("requests", "text_pos", "votes", "seed", "chains")
-
-_CACHE = {}
-
-
-def cached(key, make):
-    if key not in _CACHE:
-        _CACHE[key] = make()
-    return _CACHE[key]
-
-
-def case_id(c):
-    return "k%d-s%d-w%s-occ%d-b%d-f%d-v%d-K%d" % c
-
-
-def reference():
-    import seed_model as m
-    return cached("ref", m.make_reference)
-
-
-def short_reads():
-    """seed_model's 256 reads in rows of 128."""
-    import seed_model as m
-    return cached("short", lambda: m.make_reads(reference(), 256, READ_SIZE))
-
-
-def model_index(k, w):
-    import minimizer_model as mm
-    import seed_model as m
-    return cached(("model index", k, w), lambda: m.build_index(reference(), k) if w is None else mm.build_index(reference(), k, w))
-
-
-def expected(case, rows, rl, key, read_size=READ_SIZE, idx_base=0, ref=None, index=None):
-    """The model's output for a parameter row over the batch `key`, computed once."""
-    import chain_model as cm
-    k, stride, w, max_occ, band, flank, min_votes, K = case
-    ref = reference() if ref is None else ref
-    return cached(("expected", case, key, read_size, idx_base),
-                  lambda: cm.seed_chain(rows, rl, index or model_index(k, w), len(ref), k, stride, w, max_occ, band, flank, min_votes, K, read_size,
-                                        idx_base=idx_base))
 
 
 def run_chain(case, rows, rl, read_size=READ_SIZE, idx_base=0, ref=None, chains=True):
     """aim_seed_chain_device over buffers uploaded through the HIP runtime the library loaded, every output prefilled with 0xEE; the
     index is the library's own host build. chains=False passes d_chains = NULL and returns four arrays."""
-    from test_sam_fields_gpu import Hip
     from aim_amd import capi, engine
     k, stride, w, max_occ, band, flank, min_votes, K = case
     ref = reference() if ref is None else ref
     sp = engine.seed_params(k, read_size, stride=stride, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K, idx_base=idx_base, w=w)
     bucket, pos = engine.build_index(ref, k, threads=4) if w is None else engine.index_build_minimizers(ref, k, w, threads=4)
     n = len(rl)
-    h = Hip()
-    try:
+    with Hip() as h:
         d_b, d_p = h.up(bucket), h.up(pos)
         d_rl, d_rows = h.up(np.ascontiguousarray(rl, dtype=np.int32)), h.up(np.ascontiguousarray(rows), 64)
-        fill = lambda nbytes: h.up(np.full(nbytes, 0xEE, dtype=np.uint8))
-        d_req, d_tp, d_v, d_s = fill(n * K * 16), fill(n * K * 8), fill(n * K * 4), fill(n * 16)
-        d_c = fill(n * K * 16) if chains else None
+        d_req, d_tp, d_v, d_s = h.filled(n * K * 16), h.filled(n * K * 8), h.filled(n * K * 4), h.filled(n * 16)
+        d_c = h.filled(n * K * 16) if chains else None
         engine.seed_chain_device(sp, n, d_rl, d_rows, d_b, d_p, len(ref), d_req, d_tp, d_v, d_s, d_c)
         out = (h.down(d_req, n * K * 16).view(capi.REQUEST_DTYPE), h.down(d_tp, n * K * 8).view(np.uint64),
                h.down(d_v, n * K * 4).view(np.uint32), h.down(d_s, n * 16).view(capi.SEED_DTYPE))
         return out + ((h.down(d_c, n * K * 16).view(capi.CHAIN_DTYPE),) if chains else ())
-    finally:
-        h.free()
 
 
 def assert_equal(got, want):
@@ -108,31 +59,6 @@ def test_equals_model(case):
     assert (want[3]["n_cands"] < K).any() or K == 1                                       # empty slots exist
     assert (want[4]["n_anchors"] > 1).any() and (want[4]["score"] > case[0]).any()
     assert_equal(run_chain(case, rows, rl), want)
-
-
-def long_reads():
-    """64 reads of about 800 bases in rows of 1 024: 80 edits each, every second one with 60 reference bases deleted in the middle,
-    every third from the minus strand; all but every 16th drawn clear of the planted copies, the N run, the lower-case bases and
-    the tandem repeat. Returns (rows, read_len, true_pos, true_span, strand, clear, with_deletion)."""
-    def make():
-        import seed_model as m
-        ref = reference()
-        rng = np.random.default_rng(2024)
-        n = 64
-        rows, rl = np.zeros((n, LONG_SIZE), dtype=np.uint8), np.zeros(n, dtype=np.int32)
-        pos, span, strand = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
-        clear, deleted = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
-        for r in range(n):
-            deleted[r], clear[r], strand[r] = r % 2 == 1, r % 16 != 5, r % 3 == 1
-            span[r] = LONG_L + (LONG_DEL if deleted[r] else 0)
-            p = m.clean_position(rng, int(span[r])) if clear[r] else int(rng.integers(0, len(ref) - span[r]))
-            h = LONG_L // 2
-            base = np.concatenate([ref[p:p + h], ref[p + h + LONG_DEL:p + span[r]]]) if deleted[r] else ref[p:p + LONG_L]
-            read = m.edit(rng, base, LONG_EDITS)[:LONG_SIZE]
-            read = m.revcomp(read) if strand[r] else read
-            rows[r, :len(read)], rl[r], pos[r] = read, len(read), p
-        return rows, rl, pos, span, strand, clear, deleted
-    return cached("long", make)
 
 
 def test_long_reads_equal_model():
@@ -191,7 +117,6 @@ def test_idx_base_and_wraparound():
 
 def test_window_edges():
     """flank 25 reaches past both ends of the reference: start is clamped at 0 and end at ref_len exactly as the model says."""
-    from test_seed_gpu import edge_reads
     ref = reference()
     rows, rl, starts = edge_reads()
     flank = 25
@@ -209,13 +134,6 @@ def test_window_edges():
     assert_equal(run_chain(case, rows, rl), want)
 
 
-KNOB_CHILD = '''
-import sys
-import numpy as np
-sys.path.insert(0, "tests")
-import test_seed_chain_gpu as t
-np.savez(sys.argv[1], **t.knob_batch())
-'''
 KNOB_CASES = (FULL[0], FULL[1], MINIMIZER[0])
 
 
@@ -234,8 +152,7 @@ def test_grid_and_poison_identical(tmp_path, env):
     """The same bytes -- the model's -- at AIM_CHIP_CUS 1 and 256 and under the three AIM_DEBUG_POISON_* knobs."""
     rows, rl = short_reads()[:2]
     f = str(tmp_path / "k.npz")
-    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    child.run("test_seed_chain_gpu", "knob_batch", npz=f, env=env)
     out = np.load(f)
     for i, case in enumerate(KNOB_CASES):
         for name, want in zip(NAMES, expected(case, rows, rl, "short")):
@@ -258,20 +175,9 @@ def test_long_reads_are_well_placed_by_the_model():
     assert well_placed().sum() >= 56
 
 
-CHAIN_CHILD = '''
-import sys
-import torch
-torch.cuda.init()   # (before the library: the device buffers are torch's)
-sys.path.insert(0, "tests")
-import test_seed_chain_gpu as t
-t.chain_on_device()
-print("SEED_CHAIN_ON_DEVICE_OK")
-'''
-
-
 def test_chain_on_device():
-    p = subprocess.run([sys.executable, "-c", CHAIN_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "SEED_CHAIN_ON_DEVICE_OK" in p.stdout, p.stdout + p.stderr
+    p = child.run("test_seed_chain_gpu", "chain_on_device", cuda_first=True, marker="SEED_CHAIN_ON_DEVICE_OK")
+    assert "SEED_CHAIN_ON_DEVICE_OK" in p.stdout, p.stdout + p.stderr
 
 
 def chain_on_device():

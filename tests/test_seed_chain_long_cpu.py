@@ -157,7 +157,7 @@ def test_the_local_selection_is_the_window_rule():
 def test_batches_hold_what_they_are_meant_to_hold():
     """Counted on the model: the kernel is compared with it on these batches, so the batches have to contain the cases."""
     import chain_long_batches as lb
-    from test_seed_chain_cpu import strand_stats, tied
+    from chain_model import strand_stats, tied
     # B: more than 1 024 anchors on the true strand, none truncated, offsets beyond 12 bits, all 8 well placed with a tight window
     b, want = lb.batch_b(), lb.expected(lb.CASE_B, lb.batch_b(), "B")
     true_hits = want[3]["n_hits"][np.arange(8), b["strand"]]

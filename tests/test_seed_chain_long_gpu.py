@@ -6,7 +6,6 @@ batch (A: the same bytes as aim_seed_chain_device), more than 1 024 anchors and 
 w = 1 (F), read lengths around the tile seams with N runs across them (G), d_chains = NULL, an idx_base that wraps and windows clamped
 at both ends of the reference (H), any CU count and poison knob (I), and the chain on the device into aim_align_device_groups (J)."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,8 +13,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import child  # noqa: E402
+from gpu_buffers import Hip  # noqa: E402
 
 NAMES = ("requests", "text_pos", "votes", "seed", "chains")
 _STATE = {"failed": False}
@@ -36,21 +36,18 @@ def run_long(case, rows, rl, ref, idx_base=0, chains=True, old=False):
     if _STATE["failed"]:
         pytest.fail("an earlier GPU step of this module failed: nothing more is started")
     _STATE["failed"] = True
-    from test_sam_fields_gpu import Hip
     from aim_amd import capi, engine
     k, w, max_occ, band, flank, min_votes, K, H, read_size = case
     sp = engine.seed_params(k, read_size, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K, idx_base=idx_base, w=w,
                             long_reads=True)
     bucket, pos = engine.index_build_minimizers(ref, k, w, threads=4)
     n = len(rl)
-    h = Hip()
-    try:
+    with Hip() as h:
         d_b, d_p = h.up(bucket), h.up(pos)
         d_rl, d_rows = h.up(np.ascontiguousarray(rl, dtype=np.int32)), h.up(np.ascontiguousarray(rows), 64)
-        fill = lambda nbytes: h.up(np.full(nbytes, 0xEE, dtype=np.uint8))
 
         def outputs():
-            return [fill(n * K * 16), fill(n * K * 8), fill(n * K * 4), fill(n * 16), fill(n * K * 16) if chains else None]
+            return [h.filled(n * K * 16), h.filled(n * K * 8), h.filled(n * K * 4), h.filled(n * 16), h.filled(n * K * 16) if chains else None]
 
         def down(d):
             out = (h.down(d[0], n * K * 16).view(capi.REQUEST_DTYPE), h.down(d[1], n * K * 8).view(np.uint64),
@@ -65,8 +62,6 @@ def run_long(case, rows, rl, ref, idx_base=0, chains=True, old=False):
             got = (got, down(d2))
         _STATE["failed"] = False
         return got
-    finally:
-        h.free()
 
 
 def assert_equal(got, want):
@@ -87,7 +82,7 @@ def test_a_same_bytes_as_seed_chain_device(row):
     import chain_long_model as clm
     import minimizer_model as mm
     import seed_model as m
-    import test_seed_chain_gpu as old
+    import pipeline_batches as old
     k, stride, w, max_occ, band, flank, min_votes, K = old.MINIMIZER[row]
     ref = old.reference()
     rows, rl = old.short_reads()[:2]
@@ -184,15 +179,6 @@ def test_h_window_edges():
 
 
 # ---- I: grid and poison ---------------------------------------------------------------------------------------------------------
-KNOB_CHILD = '''
-import sys
-import numpy as np
-sys.path.insert(0, "tests")
-import test_seed_chain_long_gpu as t
-np.savez(sys.argv[1], **t.knob_batch())
-'''
-
-
 def knob_batch():
     import chain_long_batches as lb
     out = {}
@@ -210,7 +196,7 @@ def test_i_grid_and_poison_identical(tmp_path, env):
     if _STATE["failed"]:
         pytest.fail("an earlier GPU step of this module failed: nothing more is started")
     f = str(tmp_path / "k.npz")
-    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
+    p = child.run("test_seed_chain_long_gpu", "knob_batch", npz=f, env=env, check=False)
     if p.returncode != 0:
         _STATE["failed"] = True
     assert p.returncode == 0, p.stdout + p.stderr
@@ -221,21 +207,10 @@ def test_i_grid_and_poison_identical(tmp_path, env):
 
 
 # ---- J: the chain on the device -------------------------------------------------------------------------------------------------
-CHAIN_CHILD = '''
-import sys
-import torch
-torch.cuda.init()   # (before the library: the device buffers are torch's)
-sys.path.insert(0, "tests")
-import test_seed_chain_long_gpu as t
-t.chain_on_device()
-print("SEED_CHAIN_LONG_ON_DEVICE_OK")
-'''
-
-
 def test_j_chain_on_device():
     if _STATE["failed"]:
         pytest.fail("an earlier GPU step of this module failed: nothing more is started")
-    p = subprocess.run([sys.executable, "-c", CHAIN_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    p = child.run("test_seed_chain_long_gpu", "chain_on_device", cuda_first=True, marker="SEED_CHAIN_LONG_ON_DEVICE_OK", check=False)
     if p.returncode != 0:
         _STATE["failed"] = True
     assert p.returncode == 0 and "SEED_CHAIN_LONG_ON_DEVICE_OK" in p.stdout, p.stdout + p.stderr

@@ -4,7 +4,6 @@ that overflows AIM_SEED_MAX_HITS, windows clamped at both ends of the reference,
 the kernel's device buffers go straight into aim_align_device_groups."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,8 +11,10 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import child  # noqa: E402
+from gpu_buffers import Hip  # noqa: E402
+from pipeline_batches import edge_reads  # noqa: E402
 
 READ_SIZE = 128
 # (k, stride, max_occ, band, flank, min_votes, K)
@@ -54,24 +55,19 @@ def expected(case, rows=None, rl=None, key=None, idx_base=0):
 
 def run_seed(case, rows, rl, idx_base=0):
     """aim_seed_device over buffers uploaded through the HIP runtime the library loaded; the index is the library's own build."""
-    from test_sam_fields_gpu import Hip
     from aim_amd import capi, engine
     d = data()
     k, stride, max_occ, band, flank, min_votes, K = case
     sp = engine.seed_params(k, READ_SIZE, stride=stride, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K, idx_base=idx_base)
     bucket, pos = engine.build_index(d["ref"], k, threads=4)
     n = len(rl)
-    h = Hip()
-    try:
+    with Hip() as h:
         d_b, d_p = h.up(bucket), h.up(pos)
         d_rl, d_rows = h.up(np.ascontiguousarray(rl, dtype=np.int32)), h.up(rows, 64)
-        d_req, d_tp = h.up(np.full(n * K * 16, 0xEE, dtype=np.uint8)), h.up(np.full(n * K * 8, 0xEE, dtype=np.uint8))
-        d_v, d_s = h.up(np.full(n * K * 4, 0xEE, dtype=np.uint8)), h.up(np.full(n * 16, 0xEE, dtype=np.uint8))
+        d_req, d_tp, d_v, d_s = h.filled(n * K * 16), h.filled(n * K * 8), h.filled(n * K * 4), h.filled(n * 16)
         engine.seed_device(sp, n, d_rl, d_rows, d_b, d_p, len(d["ref"]), d_req, d_tp, d_v, d_s)
         return (h.down(d_req, n * K * 16).view(capi.REQUEST_DTYPE), h.down(d_tp, n * K * 8).view(np.uint64),
                 h.down(d_v, n * K * 4).view(np.uint32), h.down(d_s, n * 16).view(capi.SEED_DTYPE))
-    finally:
-        h.free()
 
 
 def assert_equal(got, want):
@@ -103,18 +99,6 @@ def test_idx_base_and_wraparound():
     assert_equal(run_seed(case, d["rows"][:32], d["rl"][:32], idx_base=base), want)
 
 
-def edge_reads():
-    """Reads of 100 bases from the first and last 20 positions of the reference, both strands."""
-    import seed_model as m
-    ref = data()["ref"]
-    starts = list(range(0, 20)) + list(range(len(ref) - 100 - 19, len(ref) - 100 + 1))
-    rows = np.zeros((2 * len(starts), READ_SIZE), dtype=np.uint8)
-    for i, p in enumerate(starts):
-        rows[2 * i, :100] = ref[p:p + 100]
-        rows[2 * i + 1, :100] = m.revcomp(ref[p:p + 100])
-    return rows, np.full(len(rows), 100, dtype=np.int32), np.repeat(starts, 2)
-
-
 def test_window_edges():
     """flank 25 reaches past both ends of the reference: start is clamped at 0 and end at ref_len exactly as the model says, and
     aim_ref_windows_check accepts every slot (the empty ones too)."""
@@ -139,15 +123,6 @@ def test_window_edges():
     assert rc == capi.AIM_OK, capi.load().aim_last_error()
 
 
-KNOB_CHILD = '''
-import sys
-import numpy as np
-sys.path.insert(0, "tests")
-import test_seed_gpu as t
-np.savez(sys.argv[1], **t.knob_batch())
-'''
-
-
 def knob_batch():
     d = data()
     out = {}
@@ -162,8 +137,7 @@ def knob_batch():
 def test_grid_and_poison_identical(tmp_path, env):
     """The same bytes -- the model's -- at AIM_CHIP_CUS 1 and 256 and under the three AIM_DEBUG_POISON_* knobs."""
     f = str(tmp_path / "k.npz")
-    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, **env), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    child.run("test_seed_gpu", "knob_batch", npz=f, env=env)
     out = np.load(f)
     for i in (0, 2):
         req, tpos, votes, seed = expected(CASES[i])
@@ -171,20 +145,9 @@ def test_grid_and_poison_identical(tmp_path, env):
             assert out[key].tobytes() == want.tobytes(), (key, env)
 
 
-CHAIN_CHILD = '''
-import sys
-import torch
-torch.cuda.init()   # (before the library: the device buffers are torch's)
-sys.path.insert(0, "tests")
-import test_seed_gpu as t
-t.chain_on_device()
-print("CHAIN_ON_DEVICE_OK")
-'''
-
-
 def test_chain_on_device():
-    p = subprocess.run([sys.executable, "-c", CHAIN_CHILD], cwd=ROOT, capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "CHAIN_ON_DEVICE_OK" in p.stdout, p.stdout + p.stderr
+    p = child.run("test_seed_gpu", "chain_on_device", cuda_first=True, marker="CHAIN_ON_DEVICE_OK")
+    assert "CHAIN_ON_DEVICE_OK" in p.stdout, p.stdout + p.stderr
 
 
 def chain_on_device():

@@ -309,7 +309,7 @@ def test_chimeric_reads_give_two_segments_each():
     breakpoint by chance), and none is loose."""
     import chain_class_model as ccm
     import split_model as sm
-    from test_chain_class_cpu import model_chains
+    from pipeline_batches import model_chains
     rows, rl, halves = sm.chimeric()
     k, stride, w, max_occ, band, flank, min_votes, K = ccm.CHIMERIC_ROW
     req, tpos, votes, seeds, chains = model_chains("chimeric", ccm.CHIMERIC_ROW, rows, rl, ccm.CHIMERIC_SIZE)

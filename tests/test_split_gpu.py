@@ -6,7 +6,6 @@ poison knobs, and the whole path chain -> classify -> split -> align -> SAM reco
 mappings of the record kernels; aim_sam_device_split on hand-made rows and segments on both mappings: clips that merge with a peeled S,
 d_sel with UINT32_MAX, valid segments on unmapped and over-cap rows, and the overflow rule with the added words."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,21 +13,18 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import child  # noqa: E402
+import hand_stages as hs  # noqa: E402
+from gpu_buffers import Hip, cached, put  # noqa: E402
+from hand_stages import chain_classify_split  # noqa: E402
+from pipeline_batches import FULL, READ_SIZE, chimeric_expected, expected, reference, short_reads  # noqa: E402
+from sam_model import HAND_ROWS, make_reference  # noqa: E402
 
 KS = (1, 4, 8, 16)
 N_READS = (1, 65, 4099)             # below, across and beyond one workgroup; never a multiple of the reads per wavefront
 READ_SIZES = (104, 1024)            # 16 lanes per read, 64 lanes per read
 OUT = ("seg_req", "seg_text_pos", "seg_patterns", "seg")
-
-_CACHE = {}
-
-
-def cached(key, make):
-    if key not in _CACHE:
-        _CACHE[key] = make()
-    return _CACHE[key]
 
 
 def synthetic(K, rs, n=max(N_READS)):
@@ -44,8 +40,7 @@ def run_split(h, K, read_size, flank, ref_len, d):
     """aim_split_segments_device over uploaded arrays, every output prefilled with 0xEE: (requests, text_pos, patterns, segments)."""
     from aim_amd import capi, engine
     n = len(d["read_len"])
-    fill = lambda nbytes: h.up(np.full(nbytes, 0xEE, dtype=np.uint8))
-    d_req, d_tp, d_pat, d_seg = fill(n * K * 16), fill(n * K * 8), fill(n * K * read_size + 64), fill(n * K * 8)
+    d_req, d_tp, d_pat, d_seg = h.filled(n * K * 16), h.filled(n * K * 8), h.filled(n * K * read_size + 64), h.filled(n * K * 8)
     engine.split_segments_device(K, read_size, flank, ref_len, n, h.up(np.ascontiguousarray(d["read_len"], dtype=np.int32)), h.up(d["reads"], 64),
                                  h.up(d["req"]), h.up(d["text_pos"]), h.up(d["seed"]), h.up(d["chains"]), h.up(d["cls"]), d_req, d_tp, d_pat, d_seg)
     pat = h.down(d_pat, n * K * read_size + 64)
@@ -66,83 +61,24 @@ def same(got, want, n_slots=None):
 @pytest.mark.parametrize("K", KS)
 def test_segments_equal_model(K, rs):
     import split_model as sm
-    from test_sam_fields_gpu import Hip
     d, want = synthetic(K, rs)
     fl = want[3]["flags"]
     assert (fl & sm.VALID).any() and (fl == 0).any() and (fl & sm.LOOSE).any() and ((fl & sm.VALID != 0) & (fl & 12 == 0)).any() == (K > 2)
-    h = Hip()
-    try:
+    with Hip() as h:
         for n in N_READS:
             same(run_split(h, K, rs, sm.SYN_FLANK, sm.SYN_REF_LEN, sm.prefix(d, n, K)), want, n * K)
             h.free()
-    finally:
-        h.free()
 
 
 def test_one_read_in_a_row_of_65528():
     """The largest row: one read, K = 4, cut into shares that groups of their own walk (parts = 16 at this size)."""
     import split_model as sm
-    from test_sam_fields_gpu import Hip
     d, want = synthetic(4, 65528, n=1)
     d2, want2 = synthetic(16, 65528, n=3)
     assert (want[3]["flags"] & sm.VALID).any() and (want2[3]["flags"] & sm.VALID).sum() >= 3
-    h = Hip()
-    try:
+    with Hip() as h:
         same(run_split(h, 4, 65528, sm.SYN_FLANK, sm.SYN_REF_LEN, d), want)
         same(run_split(h, 16, 65528, sm.SYN_FLANK, sm.SYN_REF_LEN, d2), want2)
-    finally:
-        h.free()
-
-
-def chain_classify_split(case, rows, rl, read_size, max_hits=None):
-    """aim_seed_chain_device (max_hits: aim_seed_chain_long_device), aim_chain_classify_device and aim_split_segments_device on buffers
-    that never leave the device in between. Returns (requests, text_pos, seed, chains, class) and the four segment outputs."""
-    from test_sam_fields_gpu import Hip
-    from test_seed_chain_gpu import reference
-    from aim_amd import capi, engine
-    k, stride, w, max_occ, band, flank, min_votes, K = case
-    ref = reference()
-    sp = engine.seed_params(k, read_size, stride=stride, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K, w=w,
-                            long_reads=max_hits is not None)
-    bucket, pos = engine.build_index(ref, k, threads=4) if w is None else engine.index_build_minimizers(ref, k, w, threads=4)
-    n = len(rl)
-    h = Hip()
-    try:
-        d_rl, d_rows = h.up(np.ascontiguousarray(rl, dtype=np.int32)), h.up(np.ascontiguousarray(rows), 64)
-        fill = lambda nbytes: h.up(np.full(nbytes, 0xEE, dtype=np.uint8))
-        d_req, d_tp, d_v, d_s, d_c, d_cls = fill(n * K * 16), fill(n * K * 8), fill(n * K * 4), fill(n * 16), fill(n * K * 16), fill(n * K * 8)
-        s_req, s_tp, s_pat, s_seg = fill(n * K * 16), fill(n * K * 8), fill(n * K * read_size + 64), fill(n * K * 8)
-        args = (n, d_rl, d_rows, h.up(bucket), h.up(pos), len(ref), d_req, d_tp, d_v, d_s, d_c)
-        if max_hits is None:
-            engine.seed_chain_device(sp, *args)
-        else:
-            engine.seed_chain_long_device(sp, max_hits, *args)
-        engine.chain_classify_device(K, read_size, 128, n, d_rl, d_tp, d_s, d_c, d_cls)
-        engine.split_segments_device(K, read_size, flank, len(ref), n, d_rl, d_rows, d_req, d_tp, d_s, d_c, d_cls, s_req, s_tp, s_pat, s_seg)
-        chain = (h.down(d_req, n * K * 16).view(capi.REQUEST_DTYPE), h.down(d_tp, n * K * 8).view(np.uint64), h.down(d_s, n * 16).view(capi.SEED_DTYPE),
-                 h.down(d_c, n * K * 16).view(capi.CHAIN_DTYPE), h.down(d_cls, n * K * 8).view(capi.CHAIN_CLASS_DTYPE))
-        seg = (h.down(s_req, n * K * 16).view(capi.REQUEST_DTYPE), h.down(s_tp, n * K * 8).view(np.uint64),
-               h.down(s_pat, n * K * read_size).reshape(n * K, read_size), h.down(s_seg, n * K * 8).view(capi.SEGMENT_DTYPE))
-        return chain, seg
-    finally:
-        h.free()
-
-
-def chimeric_expected():
-    """(rows, read_len, halves, the chain model's outputs, the class model's rows, the split model's outputs) for the chimeric reads."""
-    import chain_class_model as ccm
-    import split_model as sm
-    from test_seed_chain_gpu import expected, reference
-
-    def make():
-        ref = reference()
-        rows, rl, halves = sm.chimeric(ref)
-        K, flank = ccm.CHIMERIC_ROW[7], ccm.CHIMERIC_ROW[5]
-        req, tpos, votes, seeds, chains = expected(ccm.CHIMERIC_ROW, rows, rl, "chimeric", read_size=ccm.CHIMERIC_SIZE)
-        cls = ccm.classify(K, ccm.CHIMERIC_SIZE, 128, rl, tpos, seeds, chains)
-        segs = sm.segments(K, ccm.CHIMERIC_SIZE, flank, len(ref), rl, rows, req, tpos, seeds, chains, cls)
-        return rows, rl, halves, (req, tpos, seeds, chains), cls, segs
-    return cached("chimeric", make)
 
 
 @pytest.mark.parametrize("max_hits", (None, 1024), ids=("seed_chain_device", "seed_chain_long_device"))
@@ -163,7 +99,6 @@ def test_single_primary_identity():
     row, byte for byte; and the whole output equals the model."""
     import chain_class_model as ccm
     import split_model as sm
-    from test_seed_chain_gpu import FULL, READ_SIZE, expected, reference, short_reads
     rows, rl = short_reads()[:2]
     case = FULL[0]
     K, flank = case[7], case[5]
@@ -181,13 +116,6 @@ def test_single_primary_identity():
         assert tuple(s_seg[slot]) == (0, rl[r], rl[r], sm.VALID | sm.LEFT_OPEN | sm.RIGHT_OPEN, 0)
 
 
-KNOB_CHILD = '''
-import sys
-import numpy as np
-sys.path.insert(0, "tests")
-import test_split_gpu as t
-np.savez(sys.argv[1], **t.knob_batch())
-'''
 KNOB_CASES = ((4, 104), (16, 1024), (4, 65528))
 
 
@@ -197,17 +125,13 @@ def knob_n(rs):
 
 def knob_batch():
     import split_model as sm
-    from test_sam_fields_gpu import Hip
     out = {}
-    h = Hip()
-    try:
+    with Hip() as h:
         for K, rs in KNOB_CASES:
             d, _ = synthetic(K, rs, n=knob_n(rs))
             for name, arr in zip(OUT, run_split(h, K, rs, sm.SYN_FLANK, sm.SYN_REF_LEN, d)):
                 out["%s_%d_%d" % (name, K, rs)] = arr.view(np.uint8)
             h.free()
-    finally:
-        h.free()
     return out
 
 
@@ -217,9 +141,7 @@ def test_grid_and_poison_identical(tmp_path, env):
     """The same bytes -- the model's -- at AIM_CHIP_CUS 1 (eight workgroups walk the batch) and 256 and under the three
     AIM_DEBUG_POISON_* knobs, on both lane mappings and on rows cut into shares."""
     f = str(tmp_path / "k.npz")
-    p = subprocess.run([sys.executable, "-c", KNOB_CHILD, f], cwd=ROOT, env=dict(os.environ, AIM_PLAN_DEBUG="1", **env), capture_output=True, text=True,
-                       timeout=300)
-    assert p.returncode == 0, p.stdout + p.stderr
+    p = child.run("test_split_gpu", "knob_batch", npz=f, env=dict(env, AIM_PLAN_DEBUG="1"))
     grid = 8 if env["AIM_CHIP_CUS"] == "1" else -(-4099 // 16)
     assert "[aim plan] split_segments_kernel grid=%d block=256 lanes=16 parts=1 reads=4099 K=4 read_size=104" % grid in p.stderr, p.stderr
     assert "lanes=64 parts=2 reads=4099 K=16 read_size=1024" in p.stderr and "lanes=64 parts=16 reads=3 K=4 read_size=65528" in p.stderr, p.stderr
@@ -230,26 +152,11 @@ def test_grid_and_poison_identical(tmp_path, env):
             assert out["%s_%d_%d" % (name, K, rs)].tobytes() == w.tobytes(), (name, K, rs, env)
 
 
-PATH_CHILD = '''
-import sys
-import torch
-torch.cuda.init()   # (before the library: the device buffers are torch's)
-sys.path.insert(0, "tests")
-import test_split_gpu as t
-t.whole_path()
-print("SPLIT_WHOLE_PATH_OK")
-'''
-
-
 @pytest.mark.parametrize("wave_min,kernel", [(None, "sam_lane_kernel"), ("0", "sam_wave_kernel")], ids=["default-row-per-lane", "row-per-wavefront"])
 def test_whole_path(wave_min, kernel):
     """Once as a caller gets it (rows of 1 024 take the lane mapping) and once with AIM_SAM_WAVE_MIN = 0, so that both record calls take
     the wave mapping: sam_wave_split_kernel."""
-    env = dict(os.environ)
-    env.pop("AIM_SAM_WAVE_MIN", None)
-    if wave_min is not None:
-        env["AIM_SAM_WAVE_MIN"] = wave_min
-    p = subprocess.run([sys.executable, "-c", PATH_CHILD], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    p = child.run("test_split_gpu", "whole_path", cuda_first=True, marker="SPLIT_WHOLE_PATH_OK", env={"AIM_SAM_WAVE_MIN": wave_min}, check=False)
     print(p.stdout[-3000:])
     assert p.returncode == 0 and "SPLIT_WHOLE_PATH_OK" in p.stdout and "record mapping %s\n" % kernel in p.stdout, p.stdout + p.stderr
 
@@ -266,7 +173,6 @@ def whole_path():
     import torch
     import chain_class_model as ccm
     import split_model as sm
-    from test_seed_chain_gpu import reference
     from aim_amd import capi, engine
     lib = capi.load()
     ref = reference()
@@ -274,7 +180,7 @@ def whole_path():
     k, stride, w, max_occ, band, flank, min_votes, K = ccm.CHIMERIC_ROW
     rs, n = ccm.CHIMERIC_SIZE, len(rl)
     sp = engine.seed_params(k, rs, stride=stride, max_occ=max_occ, band=band, flank=flank, min_votes=min_votes, max_cands=K, w=w)
-    out = engine.split_segments(sp, engine.chain_classify(sp, engine.seed_chain_candidates(sp, engine.index_build_minimizers(ref, k, w), len(ref), rl, rows)), len(ref))
+    out = hs.segment_rows(sp, ref, rl, rows)
     assert out["chains"].tobytes() == m_chains.tobytes() and out["class"].tobytes() == m_cls.tobytes()
     same((out["seg_req"], out["seg_text_pos"], out["seg_patterns"], out["seg"]), want)
     seg = out["seg"]
@@ -282,31 +188,15 @@ def whole_path():
     bound = ccm.CHIMERIC_EDITS * max(x, o + e)
     max_score = bound + 16
     dev = torch.device("cuda:0")
-    params = engine.make_params("wfa", max_score, rs, mismatch=x, gap_o=o, gap_e=e, backtrace=True, ref_texts=True, ends_free=(0, 0, 2 * flank, 2 * flank))
+    params = hs.wfa_params(max_score, rs, x, o, e, 2 * flank)
     rows_n = n * K
-    d_ref = torch.zeros(len(ref) + 64, dtype=torch.uint8, device=dev)
-    d_ref[:len(ref)] = torch.from_numpy(ref).to(dev)
-    d_res = torch.zeros(rows_n * capi.RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_ops = torch.zeros(rows_n * 2 * rs + 64, dtype=torch.uint8, device=dev)
-    sb = lib.aim_scratch_bytes(capi.params_ref(params), rows_n)
-    d_scr = torch.zeros(max(sb, 16), dtype=torch.uint8, device=dev)
+    d_ref = put(ref, dev, 64)
     ccap, mcap = rows_n * 64, rows_n * 256
-    bufs = []
-    for _ in range(2):
-        bufs.append((torch.zeros(rows_n * 48, dtype=torch.uint8, device=dev), torch.zeros(ccap * 4, dtype=torch.uint8, device=dev),
-                     torch.zeros(mcap, dtype=torch.uint8, device=dev), torch.zeros(8, dtype=torch.uint8, device=dev)))
-    torch.cuda.synchronize()
-    rc = lib.aim_align_device_ref(capi.params_ref(params), rows_n, out["d_seg_req"].data_ptr(), out["d_seg_patterns"].data_ptr(), out["d_seg_text_pos"].data_ptr(),
-                                  d_ref.data_ptr(), len(ref), d_res.data_ptr(), d_ops.data_ptr(), d_scr.data_ptr(), sb, None)
-    assert rc == 0, lib.aim_last_error()
+    d_res, d_ops = hs.align_rows(params, rows_n, out["d_seg_req"], out["d_seg_patterns"], out["d_seg_text_pos"], d_ref, len(ref))
     print("record mapping", engine.sam_kernel_name(params))
-    common = (params, rows_n, out["d_seg_req"].data_ptr(), out["d_seg_text_pos"].data_ptr(), None, d_res.data_ptr(), d_ops.data_ptr(), d_ref.data_ptr(), len(ref), 0)
-    engine.sam_device(*common, bufs[0][0].data_ptr(), bufs[0][1].data_ptr(), ccap, bufs[0][2].data_ptr(), mcap, bufs[0][3].data_ptr())
-    engine.sam_device_split(*common, bufs[1][0].data_ptr(), bufs[1][1].data_ptr(), ccap, bufs[1][2].data_ptr(), mcap, bufs[1][3].data_ptr(), out["d_seg"].data_ptr())
-    torch.cuda.synchronize()
-    down = lambda b: (b[0].cpu().numpy().view(capi.SAM_DTYPE), b[1].cpu().numpy().view(np.uint32), b[2].cpu().numpy(), b[3].cpu().numpy().view(np.uint32))
-    plain, p_cg, p_md, p_cur = down(bufs[0])
-    split, s_cg, s_md, s_cur = down(bufs[1])
+    common = (params, rows_n, out["d_seg_req"], out["d_seg_text_pos"], d_res, d_ops, d_ref, len(ref), (ccap, mcap))
+    p, s = hs.sam_rows(*common), hs.sam_rows(*common, split_seg=out["d_seg"])
+    (plain, p_cg, p_md, p_cur), (split, s_cg, s_md, s_cur) = ((r["sam"], r["cigar"], r["md"], r["cur"]) for r in (p, s))
     assert p_cur[0] <= ccap and p_cur[1] <= mcap and s_cur[0] <= ccap and s_cur[1] == p_cur[1]
     want_rec, want_words = sm.sam_split(plain, p_cg, seg, out["seg_text_pos"])
     sm.check_split_records(split, s_cg, s_md, want_rec, want_words, plain, p_md)
@@ -339,7 +229,7 @@ def whole_path():
     print("ref spans", spans)
     # for contrast: the whole read against every candidate window, one winner per read
     gparams = engine.make_params("wfa", max_score, rs, mismatch=x, gap_o=o, gap_e=e, read_groups=True, ref_texts=True, ends_free=(0, 0, 2 * flank, 2 * flank))
-    d_off = torch.from_numpy(engine.seed_groups_offsets(n, K).view(np.uint8).copy()).to(dev)
+    d_off = put(engine.seed_groups_offsets(n, K), dev)
     d_gres = torch.zeros(n * capi.RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
     d_best = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
     gsb = lib.aim_scratch_bytes(capi.params_ref(gparams), rows_n)
@@ -359,10 +249,8 @@ HAND_RS, HAND_CAP = 1024, 5000
 def sam_both(params, res, ops, tpos, ref, seg, sel=None, options=0, ccap=1, mcap=1, split_ccap=None):
     """aim_sam_device and aim_sam_device_split over the same uploaded rows: two tuples (records, words, bytes, cursors). A guard word /
     byte sits behind each capacity. split_ccap: another CIGAR capacity for the split call."""
-    from test_sam_fields_gpu import Hip
     from aim_amd import capi, engine
-    h = Hip()
-    try:
+    with Hip() as h:
         n = len(res)
         d_res, d_ops, d_tp, d_ref = h.up(res), h.up(ops, 64), h.up(np.asarray(tpos, dtype=np.uint64)), h.up(ref, 16)
         d_req = h.up(np.zeros(max(len(tpos), 1), dtype=capi.REQUEST_DTYPE))
@@ -382,17 +270,14 @@ def sam_both(params, res, ops, tpos, ref, seg, sel=None, options=0, ccap=1, mcap
             assert int(cg[cc]) == 0x7E7E7E7E and int(md[mcap]) == 0x7E, "written past a capacity"
             out.append((h.down(d_sam, n * 48).view(capi.SAM_DTYPE), cg[:cc], md[:mcap], h.down(d_cur, 8).view(np.uint32)))
         return out
-    finally:
-        h.free()
 
 
 def hand_rows():
-    """test_sam_fields_gpu's hand-made ops rows on both strands at every begin_offset mod 4, every one also as a row over the WFA cap;
+    """sam_model's hand-made ops rows on both strands at every begin_offset mod 4, every one also as a row over the WFA cap;
     one candidate (text_pos, segment) per row plus four spare ones. The segments cycle through: clips at both ends, a lead only, a trail
     only, no clip at all, no segment (flags 0), and supplementary or not. Rows of gaps only give valid segments on unmapped rows; rows
     that begin or end with D give clips that merge with the peeled S."""
     import split_model as sm
-    from test_sam_fields_gpu import HAND_ROWS
     from aim_amd import capi
     rs = HAND_RS
     rows = [(o, strand, shift, over) for o in HAND_ROWS for strand in (0, 1) for shift in (0, 1, 2, 3) for over in ((False, True) if shift == 0 else (False,))]
@@ -421,10 +306,9 @@ def test_hand_made_rows_and_segments_on_both_mappings(wave_min, monkeypatch):
     """Split records equal sam_split of the plain records, with and without EQX, with d_sel NULL and with a d_sel that reverses the
     rows, points some at the spare candidates and gives every ninth row UINT32_MAX."""
     import split_model as sm
-    from test_sam_fields_gpu import reference
     from aim_amd import capi, engine
     monkeypatch.setenv("AIM_SAM_WAVE_MIN", wave_min)
-    ref = reference(3, 40000)
+    ref = make_reference(3, 40000)
     res, ops, tpos, seg = hand_rows()
     n = len(res)
     p = engine.make_params("wfa", HAND_CAP, HAND_RS, backtrace=True, ref_texts=True)
@@ -470,10 +354,9 @@ def test_cigar_capacity_below_the_need_with_the_added_words(wave_min, short, mon
     report the split need, the rows marked AIM_SAM_OVERFLOW have n_cigar = md_len = 0 and every other field right, their removal makes
     the rest fit, every other row is right and nothing is written past the capacity."""
     import split_model as sm
-    from test_sam_fields_gpu import reference
     from aim_amd import engine
     monkeypatch.setenv("AIM_SAM_WAVE_MIN", wave_min)
-    ref = reference(3, 40000)
+    ref = make_reference(3, 40000)
     res, ops, tpos, seg = hand_rows()
     none = seg["flags"] == 0                                    # every row gets a segment here, so that clips only add words
     seg[none] = (5, 505, 515, sm.VALID, 0)
