@@ -68,6 +68,9 @@ SEG_CONTIG_CLIPPED = 0x80         # aim_segment_t.flags, from aim_contig_clip_de
 FEATURE_PAIRED = 0x200000         # aim_features(): aim_pair_rescue_rows_device / aim_pair_select_device / aim_map_mates_device / aim_mapper_set_pairing exist
 PAIR_RESCUE = 0x1                 # aim_map_pair_params_t.options: try the mate rescue
 PAIR_PROPER, PAIR_RESCUE_TRIED_A, PAIR_RESCUE_TRIED_B, PAIR_RESCUED_A, PAIR_RESCUED_B = 0x1, 0x2, 0x4, 0x8, 0x10   # aim_map_pair_t.flags
+FEATURE_PAIR_ESTIMATE = 0x400000  # aim_features(): aim_pair_estimate_device / the _est entry points / aim_mapper_set_pairing_estimated exist (rule 15c)
+PAIR_EST_MAX_HIST = 8192          # aim_pair_est_params_t.hist_size: 64..this, a multiple of 64
+PAIR_EST_FALLBACK, PAIR_EST_CLAMPED, PAIR_EST_FLOORED = 0x1, 0x2, 0x4   # aim_pair_estimate_t.flags
 
 
 def CONTIG_SPACER(band):
@@ -214,6 +217,22 @@ MAP_MATE_DTYPE = np.dtype([("mate_pos", "<u8"), ("tlen", "<i4"), ("mate_contig",
 assert C.sizeof(MapPairParams) == 40 and C.sizeof(MapperPairsOut) == 40 and MAP_PAIR_DTYPE.itemsize == 32 and MAP_MATE_DTYPE.itemsize == 16
 
 
+class PairEstParams(C.Structure):
+    """aim_pair_est_params_t"""
+    _fields_ = [("hist_size", C.c_uint32), ("min_samples", C.c_uint32), ("min_mapq", C.c_uint32), ("min_slack", C.c_uint32)]
+
+
+class PairEstimate(C.Structure):
+    """aim_pair_estimate_t"""
+    _fields_ = [("min_span", C.c_int64), ("max_span", C.c_int64), ("n_samples", C.c_uint32), ("n_beyond", C.c_uint32), ("p25", C.c_uint32), ("p50", C.c_uint32),
+                ("p75", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+PAIR_ESTIMATE_DTYPE = np.dtype([("min_span", "<i8"), ("max_span", "<i8"), ("n_samples", "<u4"), ("n_beyond", "<u4"), ("p25", "<u4"), ("p50", "<u4"), ("p75", "<u4"),
+                                ("flags", "<u4"), ("pad", "<u4", (2,))])   # aim_pair_estimate_t
+assert C.sizeof(PairEstParams) == 16 and C.sizeof(PairEstimate) == 48 and PAIR_ESTIMATE_DTYPE.itemsize == 48
+
+
 class BatchIO(C.Structure):
     """aim_batch_io_t"""
     _fields_ = [("n_pairs", C.c_uint32), ("requests", C.c_void_p), ("patterns", C.c_void_p), ("texts", C.c_void_p),
@@ -348,6 +367,13 @@ SYMBOLS = {
     "aim_mapper_pairing_device_bytes": (C.c_int, [C.POINTER(MapperParams), C.POINTER(MapPairParams), C.POINTER(C.c_uint64)]),
     "aim_mapper_set_pairing": (C.c_int, [_VP, C.POINTER(MapPairParams)]),
     "aim_mapper_pairs": (C.c_int, [_VP, _U32, C.POINTER(MapperPairsOut)]),
+    "aim_pair_estimate_scratch": (C.c_size_t, [_U32]),
+    "aim_pair_estimate_device": (C.c_int, [C.POINTER(MapPairParams), C.POINTER(PairEstParams), _U32, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "aim_pair_rescue_rows_device_est": (C.c_int, [C.POINTER(MapPairParams), _U32, _U32, C.c_uint64, _U32, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "aim_pair_select_device_est": (C.c_int, [C.POINTER(MapPairParams), _U32, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _VP, _VP, _VP]),
+    "aim_pair_estimate_kernel_names": (C.c_char_p, []),
+    "aim_mapper_set_pairing_estimated": (C.c_int, [_VP, C.POINTER(MapPairParams), C.POINTER(PairEstParams)]),
+    "aim_mapper_pair_estimate": (C.c_int, [_VP, _U32, C.POINTER(PairEstimate)]),
 }
 
 _lib = None

@@ -42,6 +42,8 @@ int check_extend_params(const char *fn, const aim_extend_params_t *p);
 // Rule 14c's refusals of its aim_map_pair_params_t against K, read_size and n_reads, in the header's order, under the name `fn`
 // (capi_pair.hip). The rescue_size bounds are checked with AIM_PAIR_RESCUE, or always when `rescue_always`.
 int check_pair_params(const char *fn, const aim_map_pair_params_t *pp, uint32_t K, uint32_t read_size, uint32_t n_reads, bool rescue_always);
+// Rule 15c's refusals of its aim_pair_est_params_t, in the header's order, under the name `fn` (capi_pair.hip).
+int check_pair_est_params(const char *fn, const aim_pair_est_params_t *ep);
 
 // The refusals the pipeline's entry points share: one copy of each bound and of its message; `fn` names the entry point. Each is true when
 // its bound holds and otherwise leaves its message in aim_last_error(). An entry point joins them with && in its own order -- the order its

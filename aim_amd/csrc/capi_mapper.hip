@@ -130,7 +130,9 @@ uint32_t mapper_spacer(const aim_mapper_params_t &p) { return AIM_CONTIG_SPACER(
 enum Buf { B_READS, B_READ_LEN, B_REQ, B_TEXT_POS, B_VOTES, B_SEED, B_CHAINS, B_CLASS, B_SEG_REQ, B_SEG_TEXT_POS, B_SEG_PATTERNS, B_SEG, B_EXT,
            B_RESULTS, B_OPS, B_SCRATCH, B_SAM, B_CIGAR, B_MD, B_OFFSETS, B_RECORDS, B_MAP_SCRATCH, B_CONTIG,
            // rule 14c, after aim_mapper_set_pairing alone (the B_RES_* only with AIM_PAIR_RESCUE): a mapper without it keeps its layout
-           B_PAIRS, B_MATES, B_RES_CURSORS, B_RES_REQ, B_RES_TEXT_POS, B_RES_PATTERNS, B_RES_RESULTS, B_RES_OPS, B_RES_SCRATCH, B_RES_SAM, B_COUNT };
+           B_PAIRS, B_MATES, B_RES_CURSORS, B_RES_REQ, B_RES_TEXT_POS, B_RES_PATTERNS, B_RES_RESULTS, B_RES_OPS, B_RES_SCRATCH, B_RES_SAM,
+           // rule 15c, after aim_mapper_set_pairing_estimated alone: the estimate and its histogram
+           B_EST, B_EST_SCRATCH, B_COUNT };
 
 struct SlotLayout {
     uint64_t at[B_COUNT], bytes[B_COUNT], total;
@@ -138,7 +140,8 @@ struct SlotLayout {
 
 inline uint64_t up256(uint64_t x) { return (x + 255u) & ~255ull; }
 
-SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch, bool contigs, const aim_map_pair_params_t *pp = nullptr, size_t rescue_scratch = 0)
+SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch, bool contigs, const aim_map_pair_params_t *pp = nullptr, size_t rescue_scratch = 0,
+                       const aim_pair_est_params_t *ep = nullptr)
 {
     const uint64_t N = p.max_reads, K = (uint64_t)p.seed.max_cands, rs = (uint64_t)p.seed.read_size, S = N * K;
     SlotLayout L;
@@ -162,10 +165,13 @@ SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch, bool 
             b[B_RES_OPS] = N * 2 * rz + 64; b[B_RES_SCRATCH] = rescue_scratch; b[B_RES_SAM] = sizeof(aim_sam_t) * N;
         }
     }
+    if (pp && ep) {                      // rule 15c
+        b[B_EST] = sizeof(aim_pair_estimate_t); b[B_EST_SCRATCH] = aim_pair_estimate_scratch(ep->hist_size);
+    }
     uint64_t at = 0;
     for (int i = 0; i < B_COUNT; ++i) {
         L.at[i] = at;
-        if (i >= B_CONTIG && !b[i]) continue;   // the buffers of rules 13c and 14c exist only where the rule runs
+        if (i >= B_CONTIG && !b[i]) continue;   // the buffers of rules 13c, 14c and 15c exist only where the rule runs
         at += up256(std::max<uint64_t>(b[i], 4));
     }
     L.total = at;
@@ -190,6 +196,7 @@ struct MapperSlot {
     uint32_t *h_res_head = nullptr;      // {rescue CIGAR words, rescue MD bytes}
     bool waited = false;
     aim_mapper_pairs_out_t po = {};
+    aim_pair_estimate_t *h_est = nullptr;   // rule 15c (aim_mapper_set_pairing_estimated): pinned; the last batch waited for
 };
 
 }  // namespace
@@ -210,6 +217,8 @@ struct aim_mapper {
     aim_map_pair_params_t pp = {};
     aim_endsfree_params_t rap = {};      // the rescue alignment
     size_t rescue_scratch = 0;
+    bool estimated = false;              // rule 15c: ... through aim_mapper_set_pairing_estimated
+    aim_pair_est_params_t ep = {};
 };
 
 namespace {
@@ -223,7 +232,7 @@ void release(aim_mapper *m)
         if (s.stream) (void)hipStreamSynchronize(s.stream);
         if (s.dev) (void)hipFree(s.dev);
         for (void *h : {(void *)s.h_reads, (void *)s.h_read_len, (void *)s.h_records, (void *)s.h_offsets, (void *)s.h_cigar, (void *)s.h_md, (void *)s.h_head,
-                        (void *)s.h_mates, (void *)s.h_pairs, (void *)s.h_res_head})
+                        (void *)s.h_mates, (void *)s.h_pairs, (void *)s.h_res_head, (void *)s.h_est})
             if (h) (void)hipHostFree(h);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
@@ -342,7 +351,8 @@ int map_records(const char *fn, bool contigs, uint32_t K, uint32_t n_reads, cons
 }
 
 // Rule 14c's stages between aim_sam_device_split and the record kernel, on the slot's buffers: the rescue rows, their alignment and
-// their records behind the main CIGAR / MD regions (the three with AIM_PAIR_RESCUE alone), then select / apply.
+// their records behind the main CIGAR / MD regions (the three with AIM_PAIR_RESCUE alone), then select / apply. With rule 15c the
+// estimate comes first, and the two kernels of rule 14c read their bounds from it.
 int submit_pairing(aim_mapper *m, MapperSlot &s, uint32_t n_reads, hipStream_t st)
 {
     const aim_mapper_params_t &p = m->p;
@@ -353,13 +363,20 @@ int submit_pairing(aim_mapper *m, MapperSlot &s, uint32_t n_reads, hipStream_t s
     aim_segment_t *d_seg = at<aim_segment_t>(m, s, B_SEG);
     aim_sam_t *d_sam = at<aim_sam_t>(m, s, B_SAM), *d_res_sam = rescue ? at<aim_sam_t>(m, s, B_RES_SAM) : nullptr;
     uint32_t *d_contig = n_contigs ? at<uint32_t>(m, s, B_CONTIG) : nullptr, *d_res_cursors = at<uint32_t>(m, s, B_RES_CURSORS);
+    aim_chain_class_t *d_cls = at<aim_chain_class_t>(m, s, B_CLASS);
+    aim_pair_estimate_t *d_est = m->estimated ? at<aim_pair_estimate_t>(m, s, B_EST) : nullptr;
     int rc = AIM_OK;
+    if (m->estimated)
+        rc = aim_pair_estimate_device(&pp, &m->ep, K, rs, n_reads, d_seg, d_sam, d_cls, d_contig, d_est, at<void>(m, s, B_EST_SCRATCH), (size_t)m->L.bytes[B_EST_SCRATCH], st);
+    if (rc) return rc;
     if (rescue) {
         void *d_req = at<void>(m, s, B_RES_REQ), *d_res = at<void>(m, s, B_RES_RESULTS);
         uint64_t *d_tp = at<uint64_t>(m, s, B_RES_TEXT_POS);
         char *d_pat = at<char>(m, s, B_RES_PATTERNS), *d_ops = at<char>(m, s, B_RES_OPS);
-        rc = aim_pair_rescue_rows_device(&pp, K, rs, m->ref_len, n_contigs, m->d_contig_start, m->d_contig_len, n_reads, d_rl, at<char>(m, s, B_READS), d_seg, d_sam,
-                                         d_contig, d_req, d_tp, d_pat, st);
+        rc = m->estimated ? aim_pair_rescue_rows_device_est(&pp, K, rs, m->ref_len, n_contigs, m->d_contig_start, m->d_contig_len, n_reads, d_rl, at<char>(m, s, B_READS),
+                                                            d_seg, d_sam, d_contig, d_req, d_tp, d_pat, d_est, st)
+                          : aim_pair_rescue_rows_device(&pp, K, rs, m->ref_len, n_contigs, m->d_contig_start, m->d_contig_len, n_reads, d_rl, at<char>(m, s, B_READS), d_seg, d_sam,
+                                                        d_contig, d_req, d_tp, d_pat, st);
         if (!rc) rc = aim_align_device_ref(&m->rap.base, n_reads, d_req, d_pat, d_tp, m->d_ref, m->ref_len, d_res, d_ops, at<void>(m, s, B_RES_SCRATCH), m->rescue_scratch, st);
         if (!rc)
             rc = aim_sam_device(&m->rap.base, n_reads, d_req, d_tp, nullptr, d_res, d_ops, m->d_ref, m->ref_len, p.sam_options, d_res_sam,
@@ -368,8 +385,9 @@ int submit_pairing(aim_mapper *m, MapperSlot &s, uint32_t n_reads, hipStream_t s
         HIP_TRY(hipMemsetAsync(d_res_cursors, 0, 8, st));
     }
     if (!rc)
-        rc = aim_pair_select_device(&pp, K, rs, n_reads, d_rl, d_seg, d_sam, at<aim_chain_class_t>(m, s, B_CLASS), d_contig, d_res_sam, p.cigar_cap, p.md_cap,
-                                    at<aim_map_pair_t>(m, s, B_PAIRS), st);
+        rc = m->estimated ? aim_pair_select_device_est(&pp, K, rs, n_reads, d_rl, d_seg, d_sam, d_cls, d_contig, d_res_sam, p.cigar_cap, p.md_cap,
+                                                       at<aim_map_pair_t>(m, s, B_PAIRS), d_est, st)
+                          : aim_pair_select_device(&pp, K, rs, n_reads, d_rl, d_seg, d_sam, d_cls, d_contig, d_res_sam, p.cigar_cap, p.md_cap, at<aim_map_pair_t>(m, s, B_PAIRS), st);
     return rc;
 }
 
@@ -631,12 +649,17 @@ int aim_mapper_wait(aim_mapper_t *m, uint32_t slot, aim_mapper_out_t *out)
     out->n_reads = s.n_reads;
     out->records = s.h_records; out->rec_offsets = s.h_offsets; out->cigar = s.h_cigar; out->md = s.h_md;
     s.h_offsets[0] = 0;
+    if (m->estimated) {                  // an empty batch: the fallback, every count 0
+        memset(s.h_est, 0, sizeof *s.h_est);
+        s.h_est->min_span = m->pp.min_span; s.h_est->max_span = m->pp.max_span; s.h_est->flags = AIM_PAIR_EST_FALLBACK;
+    }
     if (!s.n_reads) return AIM_OK;
     HIP_TRY(hipSetDevice(m->device));
     const uint32_t *d_off = at<uint32_t>(m, s, B_OFFSETS);
     // one small copy first: rec_offsets[n_reads] and the two cursors behind it; it says how much of everything else is in use
     HIP_TRY(hipMemcpyAsync(s.h_head, d_off + s.n_reads, 12, hipMemcpyDeviceToHost, s.stream));
     if (m->paired) HIP_TRY(hipMemcpyAsync(s.h_res_head, at<char>(m, s, B_RES_CURSORS), 8, hipMemcpyDeviceToHost, s.stream));   // the rescue regions' own cursor pair
+    if (m->estimated) HIP_TRY(hipMemcpyAsync(s.h_est, at<char>(m, s, B_EST), sizeof(aim_pair_estimate_t), hipMemcpyDeviceToHost, s.stream));   // rule 15c's 48 bytes
     HIP_TRY(hipStreamSynchronize(s.stream));
     out->n_records = s.h_head[0];
     out->cigar_needed = s.h_head[1]; out->md_needed = s.h_head[2];
@@ -678,11 +701,17 @@ int aim_mapper_pairing_device_bytes(const aim_mapper_params_t *params, const aim
     return AIM_OK;
 }
 
-int aim_mapper_set_pairing(aim_mapper_t *m, const aim_map_pair_params_t *pp)
+}  // extern "C"
+
+namespace {
+
+// aim_mapper_set_pairing and, with `estimate`, aim_mapper_set_pairing_estimated: the first's refusals, then ep's
+int set_pairing(const char *fn, aim_mapper *m, const aim_map_pair_params_t *pp, bool estimate, const aim_pair_est_params_t *ep)
 {
-    const char *fn = "aim_mapper_set_pairing";
     if (!m) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
     if (const int rc = check_pairing(fn, m->p, pp)) return rc;
+    if (estimate)
+        if (const int rc = check_pair_est_params(fn, ep)) return rc;
     if (m->paired) return fail(AIM_ESTATE, "%s: pairing is already set", fn);
     for (uint32_t i = 0; i < m->p.slots; ++i)
         if (m->slot[i].in_flight) return fail(AIM_ESTATE, "%s: slot %u is in flight (aim_mapper_wait first)", fn, i);
@@ -695,11 +724,11 @@ int aim_mapper_set_pairing(aim_mapper_t *m, const aim_map_pair_params_t *pp)
         rsb = aim_scratch_bytes(&rap.base, p.max_reads);
         if (!rsb) return under(fn, AIM_ENOMEM);
     }
-    const SlotLayout L = slot_layout(p, m->align_scratch, !m->starts.empty(), pp, rsb);
+    const SlotLayout L = slot_layout(p, m->align_scratch, !m->starts.empty(), pp, rsb, estimate ? ep : nullptr);
     // Each slot moves to buffers of the new layout; nothing is in flight and no slot keeps state between batches. The new buffers come
     // first, so a failure leaves the mapper as it was.
     char *dev[AIM_MAPPER_MAX_SLOTS] = {};
-    void *host[AIM_MAPPER_MAX_SLOTS][5] = {};
+    void *host[AIM_MAPPER_MAX_SLOTS][6] = {};
     int rc = AIM_OK;
     auto make = [&]() -> int {
         for (uint32_t i = 0; i < p.slots; ++i) {
@@ -709,6 +738,8 @@ int aim_mapper_set_pairing(aim_mapper_t *m, const aim_map_pair_params_t *pp)
                                        sizeof(aim_map_pair_t) * ((N + 1) / 2), 16};
             for (int j = 0; j < 5; ++j)
                 if (const int r = pinned(&host[i][j], sizes[j])) return r;
+            if (estimate)
+                if (const int r = pinned(&host[i][5], sizeof(aim_pair_estimate_t))) return r;
         }
         HIP_TRY(hipDeviceSynchronize());
         return AIM_OK;
@@ -730,13 +761,43 @@ int aim_mapper_set_pairing(aim_mapper_t *m, const aim_map_pair_params_t *pp)
         s.dev = dev[i];
         s.h_cigar = static_cast<uint32_t *>(host[i][0]); s.h_md = static_cast<char *>(host[i][1]);
         s.h_mates = static_cast<aim_map_mate_t *>(host[i][2]); s.h_pairs = static_cast<aim_map_pair_t *>(host[i][3]); s.h_res_head = static_cast<uint32_t *>(host[i][4]);
+        s.h_est = static_cast<aim_pair_estimate_t *>(host[i][5]);
         s.waited = false;
     }
     m->L = L;
+    if (estimate) {
+        m->estimated = true;
+        m->ep = *ep;
+    }
     m->pp = *pp;
     m->rap = rap;
     m->rescue_scratch = rsb;
     m->paired = true;
+    return AIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int aim_mapper_set_pairing(aim_mapper_t *m, const aim_map_pair_params_t *pp) { return set_pairing("aim_mapper_set_pairing", m, pp, false, nullptr); }
+
+// rule 15c (AIM_FEATURE_PAIR_ESTIMATE): pairing with the span bounds estimated per batch on the device
+int aim_mapper_set_pairing_estimated(aim_mapper_t *m, const aim_map_pair_params_t *pp, const aim_pair_est_params_t *ep)
+{
+    return set_pairing("aim_mapper_set_pairing_estimated", m, pp, true, ep);
+}
+
+int aim_mapper_pair_estimate(aim_mapper_t *m, uint32_t slot, aim_pair_estimate_t *out)
+{
+    const char *fn = "aim_mapper_pair_estimate";
+    if (!m) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
+    if (slot >= m->p.slots) return fail(AIM_EINVAL, "%s: slot %u is outside 0..%u", fn, slot, m->p.slots - 1);
+    if (!out) return fail(AIM_EINVAL, "%s: out is NULL", fn);
+    if (!m->estimated) return fail(AIM_ESTATE, "%s: aim_mapper_set_pairing_estimated was not called", fn);
+    const MapperSlot &s = m->slot[slot];
+    if (s.in_flight || !s.waited) return fail(AIM_ESTATE, "%s: slot %u has no batch waited for (aim_mapper_wait first)", fn, slot);
+    *out = *s.h_est;
     return AIM_OK;
 }
 

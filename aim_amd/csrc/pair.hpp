@@ -7,6 +7,8 @@
 //   * pair_select_kernel: per read pair, the proper combination of lowest cost over the mapped slots and the mapped rescue rows (index
 //     K), against the unpaired cost -> aim_map_pair_t; where a rescue row is in the winning combination it is folded into the read's
 //     slot 0 in place (apply), so rules 12c / 13c run unchanged behind it.
+//   * pair_rescue_rows_est_kernel, pair_select_est_kernel: the same two bodies with min_span / max_span loaded from the aim_pair_estimate_t
+//     of rule 15c (pair_estimate.hpp) in device memory instead of taken from the arguments.
 //   * map_mates_kernel: behind the record kernel, one record per lane: the paired SAM flag bits into the record and aim_map_mate_t.
 //
 // The first two give a read pair G = 4, 8 or 16 consecutive lanes by K (chain_class_lanes), with candidate i of BOTH reads in lane i
@@ -191,131 +193,31 @@ __device__ __forceinline__ uint32_t pair_read_len(const PairArgs &a, bool live, 
 }
 
 // G: lanes per read pair, 4, 8 or 16 and at least K (workgroup-uniform, like every loop bound below: every lane takes every exchange).
+// The body is pair_rescue_rows_body.inc: one text for this kernel and its rule-15c twin.
 __global__ __launch_bounds__(kPairThreads) void pair_rescue_rows_kernel(PairArgs a, uint32_t G)
 {
-    const uint32_t kPairs = kPairThreads / G;
-    const uint32_t cand = threadIdx.x & (G - 1u);
-    const uint32_t base = (threadIdx.x & (uint32_t)(kWave - 1)) & ~(G - 1u);
-    const uint32_t gm = (1u << G) - 1u;
-    const uint32_t n_mates = a.n_reads / 2u, n_blocks = (n_mates + kPairs - 1u) / kPairs;   // (slots, reads and pairs are 32-bit: n_reads * (K + 1) < 2^32)
-    for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-        const uint32_t m = blk * kPairs + threadIdx.x / G;
-        const bool pair_live = m < n_mates, live = pair_live && cand < a.K;
-        const PairCand A = pair_load_slot(a, live, 2u * m * a.K + cand), B = pair_load_slot(a, live, (2u * m + 1u) * a.K + cand);
-        const uint32_t mask_a = (uint32_t)(__ballot(A.fl & 1u) >> base) & gm, mask_b = (uint32_t)(__ballot(B.fl & 1u) >> base) & gm;
-        const bool none_proper = !((uint32_t)(__ballot(pair_mapped_row(a, A, B, cand, G).cnt != 0u) >> base) & gm);
-        // (`side ? A : B` selects a six-register candidate. The compiler unrolls these two rounds, so each is a plain use of A or of B and
-        // the kernel stays at 36 VGPRs; nothing in the language promises that. tests/test_pairs_cpu.py holds the code object to kPairMaxVgpr
-        // and to no scratch: if a compiler keeps the loop and the count moves, write the two rounds out.)
-        for (uint32_t side = 0; side < 2u; ++side) {                        // side: the read b of the row; its mate is the anchor's read
-            const uint32_t b = 2u * m + side;
-            const uint32_t mask = side ? mask_a : mask_b;                    // the mate's mapped slots
-            const PairCand anchor = pair_bcast(side ? A : B, mask ? (uint32_t)__ffs(mask) - 1u : 0u, G);
-            const uint32_t L = pair_read_len(a, pair_live, b);
-            int64_t lo = 0, hi = 0;
-            if ((a.options & AIM_PAIR_RESCUE) && mask && none_proper && L) {   // the rescue is tried
-                int64_t c_lo = 0, c_hi = a.ref_len;
-                if (a.contig && anchor.contig < a.n_contigs) {               // (no load outside the table)
-                    c_lo = a.contig_start[anchor.contig];
-                    c_hi = c_lo + a.contig_len[anchor.contig];
-                }
-                const int64_t P = (int64_t)((uint64_t)anchor.pos_hi << 32 | anchor.pos_lo);
-                if (anchor.fl & 2u) {
-                    const int64_t E = P + anchor.span;
-                    lo = max(E - a.max_span, c_lo);
-                    hi = min(E - a.min_span + L, c_hi);
-                } else {
-                    lo = max(P + a.min_span - L, c_lo);
-                    hi = min(P + a.max_span, c_hi);
-                }
-            }
-            const bool row = hi - lo >= (int64_t)L && L;                     // else the empty row: lengths 0, text_pos 0
-            if (pair_live && cand == 0) {
-                const uint64_t tp = row ? ((uint64_t)lo | ((anchor.fl & 2u) ? 0ull : AIM_REF_MINUS_STRAND)) : 0ull;
-                reinterpret_cast<uint4 *>(a.res_req)[b] = make_uint4(row ? L : 0u, row ? (uint32_t)(hi - lo) : 0u, 0u, b);
-                reinterpret_cast<uint2 *>(a.res_text_pos)[b] = make_uint2((uint32_t)tp, (uint32_t)(tp >> 32));
-            }
-            if (row) {                                                       // the read as given, at the stride of the rescue alignment
-                const uint2 *src = reinterpret_cast<const uint2 *>(a.reads + (uint64_t)b * a.read_size);
-                uint2 *dst = reinterpret_cast<uint2 *>(a.res_patterns + (uint64_t)b * a.rescue_size);
-                for (uint32_t w = cand; w < a.read_size / 8u; w += G) dst[w] = src[w];
-            }
-        }
-    }
+#include "pair_rescue_rows_body.inc"
 }
 
+// Rule 15c: the bounds are the estimate's, which the kernel in front of this one on the stream wrote (two uniform 64-bit loads).
+__global__ __launch_bounds__(kPairThreads) void pair_rescue_rows_est_kernel(PairArgs a, uint32_t G, const aim_pair_estimate_t *est)
+{
+    a.min_span = est->min_span;
+    a.max_span = est->max_span;
+#include "pair_rescue_rows_body.inc"
+}
+
+// (the body: pair_select_body.inc, shared with the rule-15c twin below)
 __global__ __launch_bounds__(kPairThreads) void pair_select_kernel(PairArgs a, uint32_t G)
 {
-    const uint32_t kPairs = kPairThreads / G;
-    const uint32_t cand = threadIdx.x & (G - 1u);
-    const uint32_t base = (threadIdx.x & (uint32_t)(kWave - 1)) & ~(G - 1u);
-    const uint32_t gm = (1u << G) - 1u, K = a.K;
-    const uint32_t n_mates = a.n_reads / 2u, n_blocks = (n_mates + kPairs - 1u) / kPairs;
-    for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-        const uint32_t m = blk * kPairs + threadIdx.x / G;
-        const bool pair_live = m < n_mates, live = pair_live && cand < K;
-        const uint32_t ra = 2u * m, rb = ra + 1u;
-        const PairCand A = pair_load_slot(a, live, ra * K + cand), B = pair_load_slot(a, live, rb * K + cand);
-        const uint32_t mask_a = (uint32_t)(__ballot(A.fl & 1u) >> base) & gm, mask_b = (uint32_t)(__ballot(B.fl & 1u) >> base) & gm;
-        const uint32_t rep_a = mask_a ? (uint32_t)__ffs(mask_a) - 1u : 0u, rep_b = mask_b ? (uint32_t)__ffs(mask_b) - 1u : 0u;
-        PairSel v = pair_mapped_row(a, A, B, cand, G);
-        // of the two representatives -- the anchors of the rescue -- what the choice needs: the contig and the score
-        const uint32_t contig_a = (uint32_t)__shfl((int)A.contig, (int)rep_a, (int)G), contig_b = (uint32_t)__shfl((int)B.contig, (int)rep_b, (int)G);
-        const int score_a = __shfl(A.score, (int)rep_a, (int)G), score_b = __shfl(B.score, (int)rep_b, (int)G);
-        // the rescue rows: tried as pair_rescue_rows_kernel decides it, usable when the row came back mapped; its contig is its anchor's
-        const bool rescue = (a.options & AIM_PAIR_RESCUE) && !((uint32_t)(__ballot(v.cnt != 0u) >> base) & gm);
-        const bool tried_a = rescue && mask_b && pair_read_len(a, pair_live, ra), tried_b = rescue && mask_a && pair_read_len(a, pair_live, rb);
-#pragma unroll 1   // (one copy of the 64-bit arithmetic: unrolled, the kernel needs 68 VGPRs)
-        for (uint32_t side = 0; side < 2u; ++side) {                           // (i, K) with read 2m + 1's row, then (K, j) with read 2m's; (K, K) is excluded
-            const PairCand R = pair_load(a.res_sam, side ? tried_a : tried_b, side ? ra : rb, true, side ? contig_b : contig_a);
-            v = pair_add(a, v, side ? B : A, R, side ? K : cand, side ? cand : K);
-        }
-        v = pair_butterfly(v, G);
-        const uint32_t vi = v.ij >> 8, vj = v.ij & 0xffu;
-        const bool both = mask_a && mask_b;
-        const int unpaired = pair_clamp((int64_t)score_a + score_b + a.unpaired_penalty);
-        const bool take = v.cnt && (!both || v.cost <= unpaired);              // (a tie goes to the proper combination)
-        if (pair_live && cand == 0) {
-            uint4 lo = make_uint4(mask_a ? ra * K + rep_a : UINT_MAX, mask_b ? rb * K + rep_b : UINT_MAX, (uint32_t)INT_MAX, (uint32_t)INT_MAX);
-            uint4 hi = make_uint4(0u, (tried_a ? AIM_PAIR_RESCUE_TRIED_A : 0u) | (tried_b ? AIM_PAIR_RESCUE_TRIED_B : 0u), 0u, 0u);
-            if (take) {
-                lo = make_uint4(ra * K + vi, rb * K + vj, (uint32_t)v.cost, (uint32_t)v.sec);
-                hi.x = v.cnt;
-                hi.y |= AIM_PAIR_PROPER | (vi == K ? AIM_PAIR_RESCUED_A : 0u) | (vj == K ? AIM_PAIR_RESCUED_B : 0u);
-                hi.z = v.span_lo;
-                hi.w = v.span_hi;
-            } else if (both) {
-                lo.z = (uint32_t)unpaired;
-                lo.w = (uint32_t)(v.cnt ? v.cost : INT_MAX);
-            }
-            uint4 *out = reinterpret_cast<uint4 *>(a.pairs + m);
-            out[0] = lo;
-            out[1] = hi;
-        }
-        // apply: the rescue row of the winning combination becomes slot 0 of its read, the read's other slots lose AIM_SEG_VALID
-        if (take && live && (vi == K || vj == K)) {
-            const bool b_side = vj == K;
-            const uint32_t r = b_side ? rb : ra;
-            const uint64_t slot = (uint64_t)r * K + cand;
-            if (cand == 0) {
-                const uint4 *row = reinterpret_cast<const uint4 *>(a.res_sam) + (uint64_t)r * 3u;
-                const uint4 w0 = row[0], w1 = row[1], w2 = row[2];
-                uint4 *dst = reinterpret_cast<uint4 *>(a.sam) + slot * 3u;
-                dst[0] = w0;
-                dst[1] = make_uint4(w1.x, w1.y, w1.z + a.cigar_base, w1.w);    // cigar_offset
-                dst[2] = make_uint4(w2.x + a.md_base, w2.y, w2.z, w2.w);       // md_offset
-                const uint32_t L = pair_read_len(a, true, r);
-                reinterpret_cast<uint2 *>(a.seg)[slot] = make_uint2(L << 16, L | (AIM_SEG_VALID | AIM_SEG_LEFT_OPEN | AIM_SEG_RIGHT_OPEN) << 16);
-                const uint64_t anchor_slot = b_side ? ra * K + rep_a : rb * K + rep_b;
-                if (a.contig) a.contig[slot] = b_side ? contig_a : contig_b;
-                uint32_t *c1 = reinterpret_cast<uint32_t *>(a.cls) + slot * 2u + 1u;
-                *c1 = (*c1 & ~0x00ff0000u) | (reinterpret_cast<const uint32_t *>(a.cls)[anchor_slot * 2u + 1u] & 0x00ff0000u);   // the mapq byte
-            } else {
-                uint32_t *s1 = reinterpret_cast<uint32_t *>(a.seg) + slot * 2u + 1u;
-                *s1 &= ~(AIM_SEG_VALID << 16);
-            }
-        }
-    }
+#include "pair_select_body.inc"
+}
+
+__global__ __launch_bounds__(kPairThreads) void pair_select_est_kernel(PairArgs a, uint32_t G, const aim_pair_estimate_t *est)
+{
+    a.min_span = est->min_span;
+    a.max_span = est->max_span;
+#include "pair_select_body.inc"
 }
 
 // One record per lane. The mate's mapped slots come from the slot arrays (as apply left them), never from other lanes' records.
@@ -375,6 +277,16 @@ void pair_select_launch(const PairArgs &a, uint32_t lanes, uint32_t grid, hipStr
     hipLaunchKernelGGL(pair_select_kernel, dim3(grid), dim3(kPairThreads), 0, s, a, lanes);
 }
 
+void pair_rescue_rows_est_launch(const PairArgs &a, uint32_t lanes, uint32_t grid, const aim_pair_estimate_t *est, hipStream_t s)
+{
+    hipLaunchKernelGGL(pair_rescue_rows_est_kernel, dim3(grid), dim3(kPairThreads), 0, s, a, lanes, est);
+}
+
+void pair_select_est_launch(const PairArgs &a, uint32_t lanes, uint32_t grid, const aim_pair_estimate_t *est, hipStream_t s)
+{
+    hipLaunchKernelGGL(pair_select_est_kernel, dim3(grid), dim3(kPairThreads), 0, s, a, lanes, est);
+}
+
 void map_mates_launch(const MatesArgs &a, uint32_t grid, hipStream_t s)
 {
     hipLaunchKernelGGL(map_mates_kernel, dim3(grid), dim3(kPairThreads), 0, s, a);
@@ -382,6 +294,8 @@ void map_mates_launch(const MatesArgs &a, uint32_t grid, hipStream_t s)
 #else
 void pair_rescue_rows_launch(const PairArgs &a, uint32_t lanes, uint32_t grid, hipStream_t s);
 void pair_select_launch(const PairArgs &a, uint32_t lanes, uint32_t grid, hipStream_t s);
+void pair_rescue_rows_est_launch(const PairArgs &a, uint32_t lanes, uint32_t grid, const aim_pair_estimate_t *est, hipStream_t s);
+void pair_select_est_launch(const PairArgs &a, uint32_t lanes, uint32_t grid, const aim_pair_estimate_t *est, hipStream_t s);
 void map_mates_launch(const MatesArgs &a, uint32_t grid, hipStream_t s);
 #endif
 

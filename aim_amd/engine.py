@@ -789,6 +789,43 @@ def map_mates_device(K, n_reads, d_pairs, d_seg, d_sam, d_rec_offsets, d_records
                                                 d_mates, stream))
 
 
+def pair_estimate_params(hist_size=2048, min_samples=64, min_mapq=20, min_slack=16):
+    """aim_pair_est_params_t (rule 15c): the histogram's bins of one base (64..8192, a multiple of 64), the binned samples below which the
+    estimate falls back to pair_params' own bounds, the MAPQ either mate of a sample needs, and the floor of the spread 3 * IQR."""
+    return capi.PairEstParams(int(hist_size), int(min_samples), int(min_mapq), int(min_slack))
+
+
+def pair_estimate_scratch(hist_size):
+    """aim_pair_estimate_scratch: the bytes of d_scratch pair_estimate_device wants."""
+    return int(capi.load().aim_pair_estimate_scratch(int(hist_size)))
+
+
+def estimate_dict(e):
+    """An aim_pair_estimate_t (capi.PairEstimate, or one item of capi.PAIR_ESTIMATE_DTYPE) as a dict of Python integers."""
+    names = ("min_span", "max_span", "n_samples", "n_beyond", "p25", "p50", "p75", "flags")
+    return {k: int(getattr(e, k) if isinstance(e, capi.PairEstimate) else e[k]) for k in names}
+
+
+def pair_estimate_device(pp, ep, K, read_size, n_reads, d_seg, d_sam, d_class, d_est, d_scratch, scratch_bytes, d_contig=None, stream=None):
+    """aim_pair_estimate_device on device pointers: rule 15c's span bounds of the batch, from the slot arrays behind sam_device_split, into
+    the 48 bytes at d_est (capi.PAIR_ESTIMATE_DTYPE). d_scratch may hold anything. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_pair_estimate_device(C.byref(pp), C.byref(ep), int(K), int(read_size), int(n_reads), d_seg, d_sam, d_class, d_contig, d_est, d_scratch,
+                                                    int(scratch_bytes), stream))
+
+
+def pair_rescue_rows_device_est(pp, K, read_size, ref_len, n_reads, d_read_len, d_reads, d_seg, d_sam, d_res_requests, d_res_text_pos, d_res_patterns, d_est,
+                                d_contig=None, n_contigs=0, d_contig_start=None, d_contig_len=None, stream=None):
+    """aim_pair_rescue_rows_device_est: pair_rescue_rows_device with min_span / max_span read from d_est on the device (rule 15c)."""
+    capi.check(capi.load().aim_pair_rescue_rows_device_est(C.byref(pp), int(K), int(read_size), int(ref_len), int(n_contigs), d_contig_start, d_contig_len, int(n_reads),
+                                                           d_read_len, d_reads, d_seg, d_sam, d_contig, d_res_requests, d_res_text_pos, d_res_patterns, d_est, stream))
+
+
+def pair_select_device_est(pp, K, read_size, n_reads, d_read_len, d_seg, d_sam, d_class, d_res_sam, cigar_base, md_base, d_pairs, d_est, d_contig=None, stream=None):
+    """aim_pair_select_device_est: pair_select_device with min_span / max_span read from d_est on the device (rule 15c)."""
+    capi.check(capi.load().aim_pair_select_device_est(C.byref(pp), int(K), int(read_size), int(n_reads), d_read_len, d_seg, d_sam, d_class, d_contig, d_res_sam,
+                                                      int(cigar_base), int(md_base), d_pairs, d_est, stream))
+
+
 def mapper_pairing_device_bytes(mp, pp):
     """aim_mapper_pairing_device_bytes: the device memory Mapper.set_pairing adds, over all slots."""
     b = C.c_uint64()
@@ -827,13 +864,16 @@ class Mapper:
     """aim_mapper_t: the reference, its minimizer index and per-slot buffers and streams on one device. submit(slot, read_len, reads)
     copies a batch in and enqueues every stage; wait(slot) returns a dict of numpy views of the slot's pinned buffers -- "records"
     (capi.MAP_RECORD_DTYPE), "rec_offsets" (uint32[n_reads + 1]), "cigar" (uint32 words) and "md" (uint8) -- which stay valid until the
-    slot's next submit, plus "cigar_needed" / "md_needed". After set_pairing(pp) (rule 14c) reads 2m and 2m + 1 are mates: wait's dict
+    slot's next submit, plus "cigar_needed" / "md_needed". set_pairing(pp, estimate=pair_estimate_params(...)) (rule 15c) estimates the
+    span bounds per batch on the device, pp's own being the fallback; wait's dict then has "pair_estimate", what pair_estimate(slot)
+    returns. After set_pairing(pp) (rule 14c) reads 2m and 2m + 1 are mates: wait's dict
     gains what pairs(slot) returns, and where a rescue wrote something "cigar" / "md" reach to the end of the rescue region (which starts
     at cigar_cap / md_cap), so that a rescued record's cigar_offset / md_offset index them like any other. Such a widened view spans the
     gap between the main range's end (cigar_needed / md_needed, at most the capacity) and the region's start: that gap is never copied
     and holds whatever the pinned buffer held -- index the arrays by a record's offsets, do not hash or compare them whole. "rescue_cigar"
     and "rescue_md" are the rescue ranges alone, as views of their own."""
     pairing = None
+    estimate = None
 
     def __init__(self, mp, reference, device=0):
         self.lib = capi.load()
@@ -874,10 +914,22 @@ class Mapper:
     def __exit__(self, *exc):
         self.close()
 
-    def set_pairing(self, pp):
-        """aim_mapper_set_pairing: once, while no slot is in flight."""
-        capi.check(self.lib.aim_mapper_set_pairing(self.handle, C.byref(pp)))
+    def set_pairing(self, pp, estimate=None):
+        """aim_mapper_set_pairing: once, while no slot is in flight. estimate: pair_estimate_params() for aim_mapper_set_pairing_estimated
+        (rule 15c) -- the span bounds come from each batch, pp.min_span / pp.max_span are the fallback."""
+        if estimate is None:
+            capi.check(self.lib.aim_mapper_set_pairing(self.handle, C.byref(pp)))
+        else:
+            capi.check(self.lib.aim_mapper_set_pairing_estimated(self.handle, C.byref(pp), C.byref(estimate)))
         self.pairing = pp
+        self.estimate = estimate
+
+    def pair_estimate(self, slot):
+        """aim_mapper_pair_estimate after wait(slot): the estimate of the slot's last batch as a dict -- "min_span", "max_span", "n_samples",
+        "n_beyond", "p25", "p50", "p75" and "flags" (capi.PAIR_EST_*)."""
+        e = capi.PairEstimate()
+        capi.check(self.lib.aim_mapper_pair_estimate(self.handle, int(slot), C.byref(e)))
+        return estimate_dict(e)
 
     def pairs(self, slot):
         """aim_mapper_pairs after wait(slot): "mates" (capi.MAP_MATE_DTYPE per record), "pairs" (capi.MAP_PAIR_DTYPE per read pair) and the
@@ -911,6 +963,8 @@ class Mapper:
                 res["md"] = view(out.md, self.params.md_cap + res["rescue_md_bytes"], np.uint8)
             res["rescue_cigar"] = res["cigar"][self.params.cigar_cap:] if res["rescue_cigar_words"] else np.zeros(0, dtype=np.uint32)
             res["rescue_md"] = res["md"][self.params.md_cap:] if res["rescue_md_bytes"] else np.zeros(0, dtype=np.uint8)
+            if self.estimate is not None:
+                res["pair_estimate"] = self.pair_estimate(slot)
         return res
 
 

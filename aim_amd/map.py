@@ -112,6 +112,12 @@ def parser():
     ap.add_argument("--unpaired-penalty", type=int, default=17, help="paired-end: what the two best single placements pay against a proper pair")
     ap.add_argument("--rescue-size", type=int, default=None, help="paired-end: row size of the rescue alignment (default: max_span - min_span + read_size, rounded up to 8)")
     ap.add_argument("--no-rescue", action="store_true", help="paired-end: pair what was mapped, rescue nothing")
+    ap.add_argument("--estimate-span", action="store_true",
+                    help="paired-end: estimate the span bounds from each batch on the device (rule 15c); --min-span / --max-span are the fallback and size --rescue-size")
+    ap.add_argument("--est-hist-size", type=int, default=2048, help="--estimate-span: bins of one base, a multiple of 64 in 64..8192")
+    ap.add_argument("--est-min-samples", type=int, default=64, help="--estimate-span: fewer sampled pairs in a batch give the fallback")
+    ap.add_argument("--est-min-mapq", type=int, default=20, help="--estimate-span: the MAPQ either mate of a sample needs")
+    ap.add_argument("--est-min-slack", type=int, default=16, help="--estimate-span: a floor for the spread, 3 * IQR")
     ap.add_argument("-o", "--out", required=True)
     ap.add_argument("--contigs", action="store_true", help="map against every sequence of a multi-sequence FASTA (a contig table)")
     ap.add_argument("--device", type=int, default=0)
@@ -195,7 +201,9 @@ def main(argv=None):
             try:
                 m.set_pairing(engine.pair_params(args.min_span, args.max_span, args.unpaired_penalty, rescue=not args.no_rescue,
                                                  rescue_size=args.rescue_size if args.rescue_size is not None else engine.round_up_8(max(span, read_size)),
-                                                 rescue_cigar_cap=args.batch * 64, rescue_md_cap=args.batch * 256))
+                                                 rescue_cigar_cap=args.batch * 64, rescue_md_cap=args.batch * 256),
+                              estimate=engine.pair_estimate_params(args.est_hist_size, args.est_min_samples, args.est_min_mapq, args.est_min_slack)
+                              if args.estimate_span else None)
             except capi.AimError as e:
                 print("aim_amd.map: %s" % e, file=sys.stderr)
                 return 2
@@ -209,6 +217,10 @@ def main(argv=None):
             if out["cigar_needed"] > mp.cigar_cap or out["md_needed"] > mp.md_cap:
                 print("aim_amd.map: a batch needed %d CIGAR words and %d MD bytes: records over --cigar-cap %d / --md-cap %d have no CIGAR" %
                       (out["cigar_needed"], out["md_needed"], mp.cigar_cap, mp.md_cap), file=sys.stderr)
+            if "pair_estimate" in out:
+                e = out["pair_estimate"]
+                print("aim_amd.map: span estimate p25=%d p50=%d p75=%d bounds=%d..%d samples=%d beyond=%d flags=0x%x" %
+                      (e["p25"], e["p50"], e["p75"], e["min_span"], e["max_span"], e["n_samples"], e["n_beyond"], e["flags"]), file=sys.stderr)
             n_lines += samout.write(fh, out, names, rows, rl, rname, quals)
         for b, lo in enumerate(range(0, len(reads), args.batch)):
             part = reads[lo:lo + args.batch]

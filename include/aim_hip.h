@@ -350,6 +350,7 @@ int aim_abi_version(void);
 #define AIM_FEATURE_MAPPER 0x80000u /* rule 12c and the mapper object: aim_map_records_device / aim_mapper_create / aim_mapper_submit / aim_mapper_wait exist */
 #define AIM_FEATURE_CONTIGS 0x100000u /* rule 13c, references of several sequences: aim_contigs_layout / aim_contig_clip_device / aim_map_records_contigs_device / aim_mapper_create_contigs exist */
 #define AIM_FEATURE_PAIRED 0x200000u /* rule 14c, paired-end reads: aim_pair_rescue_rows_device / aim_pair_select_device / aim_map_mates_device / aim_mapper_set_pairing / aim_mapper_pairs exist */
+#define AIM_FEATURE_PAIR_ESTIMATE 0x400000u /* rule 15c, the span bounds of rule 14c estimated from the batch: aim_pair_estimate_device / aim_pair_rescue_rows_device_est / aim_pair_select_device_est / aim_mapper_set_pairing_estimated / aim_mapper_pair_estimate exist */
 uint32_t aim_features(void);
 const char *aim_last_error(void);
 /* Number of usable gfx950 devices (0 and AIM_ENODEV when there is none). */
@@ -1340,7 +1341,7 @@ int aim_mapper_contigs(const aim_mapper_t *mapper, uint32_t *n_contigs, const ui
  *       AIM_SAM_OVERFLOW on the rescued records and rescue_*_needed above rescue_*_words / _bytes.
  *       A mapper on which aim_mapper_set_pairing was never called gives the bytes it always gave.
  * aim_pair_kernel_names: "pair_rescue_rows_kernel,pair_select_kernel,map_mates_kernel".
- * Not in this version: a pair MAPQ, insert-size estimation from the data, rescue against anchors other than the representative,
+ * Not in this version: a pair MAPQ (the span bounds estimated from the data: rule 15c below), rescue against anchors other than the representative,
  * keeping a rescued read's discordant placement as a secondary line, mates that overlap so far that pos_r < pos_f, pairing inside
  * aim_set_submit or host.c, AIM_FLAG_TOP_HITS rows. Check aim_features() & AIM_FEATURE_PAIRED first. */
 #define AIM_PAIR_RESCUE 0x1u            /* aim_map_pair_params_t.options: try the mate rescue */
@@ -1394,6 +1395,86 @@ const char *aim_pair_kernel_names(void);
 int aim_mapper_pairing_device_bytes(const aim_mapper_params_t *params, const aim_map_pair_params_t *pp, uint64_t *bytes);
 int aim_mapper_set_pairing(aim_mapper_t *mapper, const aim_map_pair_params_t *pp);
 int aim_mapper_pairs(aim_mapper_t *mapper, uint32_t slot, aim_mapper_pairs_out_t *out);
+
+/* ---- the span bounds of rule 14c estimated from the batch (AIM_FEATURE_PAIR_ESTIMATE) ---------------------------------------------
+ * min_span and max_span decide what rule 14c calls proper, which mates it rescues and where; a caller who does not know the library's
+ * fragment lengths has to guess them. Most read pairs of a batch place both mates uniquely, and their spans are the fragment lengths.
+ * Rule 15c reads them off the slot arrays as they stand after aim_sam_device_split -- d_seg, d_sam, d_class and d_contig (NULL for one
+ * sequence), in front of aim_pair_rescue_rows_device -- and leaves the bounds in device memory, where the two kernels of rule 14c read
+ * them: no round trip through the host, and nothing is carried from one batch to the next. All arithmetic is signed 64-bit and
+ * integer only; the result is deterministic and independent of the grid and of the AIM_DEBUG_POISON_* knobs.
+ *   15c. Sample. Read pair m = (2m, 2m + 1) is a SAMPLE when each of the two reads has exactly one mapped slot (rule 12c's: the read
+ *       is neither unmapped nor split), d_class[slot].mapq >= min_mapq for both, the two slots lie on the same contig (d_contig equal,
+ *       when given), they differ in AIM_SAM_REVERSE and, with f the forward and r the reverse record, pos_f <= pos_r. Its value is
+ *       rule 14c's span, pos_r + ref_span_r - pos_f. A sample with span < hist_size is binned at its span and n_samples counts these;
+ *       a sample with span >= hist_size counts in n_beyond and is otherwise ignored.
+ *       Quartiles. cum(s) is the number of binned samples with span <= s. p_q is the smallest s with 4 * cum(s) >= q * n_samples, for
+ *       q = 1, 2, 3: p25, p50, p75. All three are 0 when n_samples == 0.
+ *       Bounds. IQR = p75 - p25, slack = max(3 * IQR, min_slack), lo = max(p25 - slack, 0), hi = p75 + slack.
+ *         AIM_PAIR_EST_FLOORED: the max(.., 0) in lo = max(p25 - slack, 0) changed lo.
+ *         AIM_PAIR_EST_CLAMPED: with AIM_PAIR_RESCUE and W = rescue_size - read_size, when hi - lo > W: lo = max(p50 - W / 2, 0) and
+ *           hi = lo + W. This keeps rule 14c's invariant hi - lo + read_size <= rescue_size for bounds the host never sees.
+ *         AIM_PAIR_EST_FALLBACK: when n_samples < min_samples, lo = pp->min_span and hi = pp->max_span, and no other flag is set.
+ *       Output. aim_pair_estimate_t in device memory, 48 bytes, 16-byte aligned: min_span = lo, max_span = hi, the counts, the
+ *       quartiles, the flags, and two pad words of 0.
+ *       Use. aim_pair_rescue_rows_device_est and aim_pair_select_device_est are aim_pair_rescue_rows_device and aim_pair_select_device
+ *       of rule 14c word for word, with min_span and max_span read from d_est by the kernel. pp's own bounds are the fallback alone and
+ *       still have to pass rule 14c's checks; d_est is 16-byte aligned and may be NULL only with n_reads = 0.
+ *   aim_pair_estimate_device enqueues on hip_stream, allocating nothing: the clear of d_scratch (so the scratch may hold anything),
+ *       pair_span_hist_kernel and pair_span_bounds_kernel (csrc/pair_estimate.hpp). The first gives a read pair 4, 8 or 16 lanes by K
+ *       like rule 14c's kernels and counts into a histogram in LDS of its workgroup (4 * (hist_size + 1) bytes), whose non-zero bins
+ *       it adds to the one in d_scratch; those integer adds are the only atomics, and a sum does not depend on the order of its terms.
+ *       The second is one workgroup. aim_pair_estimate_scratch(hist_size) = 4 * hist_size + 16 bytes. n_reads = 0 writes the fallback
+ *       estimate with every count 0 (into a d_est that is not NULL; the other buffers may be NULL then).
+ *       AIM_EINVAL under the entry point's name, before any device query: every check of rule 14c on pp, K, read_size and n_reads; a
+ *       NULL aim_pair_est_params_t; hist_size outside 64..AIM_PAIR_EST_MAX_HIST or not a multiple of 64; min_samples 0; min_mapq above
+ *       60; a NULL buffer with n_reads > 0; a d_est that is not 16-byte aligned (d_sam 16, d_seg and d_class 8, d_scratch 4);
+ *       scratch_bytes below aim_pair_estimate_scratch(hist_size).
+ *   Mapper. aim_mapper_set_pairing_estimated(m, &pp, &ep) is aim_mapper_set_pairing plus the estimate: the same state rules, its
+ *       refusals followed by ep's. Per slot it allocates, on the device, up256(48) + up256(aim_pair_estimate_scratch(hist_size)) bytes
+ *       more than aim_mapper_pairing_device_bytes reports per slot (up256: rounded up to a multiple of 256); that function is unchanged.
+ *       aim_mapper_submit enqueues the estimate behind aim_sam_device_split and calls the _est variants in place of rule 14c's two;
+ *       aim_mapper_wait copies the 48 bytes together with its first small copy. aim_mapper_pair_estimate(m, slot, &e) gives the
+ *       estimate of the last batch waited for on the slot (for an empty batch: the fallback with every count 0); AIM_ESTATE before the
+ *       first wait, while the slot is in flight, and on a mapper without estimation. A mapper paired with aim_mapper_set_pairing, or not
+ *       paired at all, keeps its buffers and every byte it gave before.
+ * aim_pair_estimate_kernel_names: "pair_span_hist_kernel,pair_span_bounds_kernel,pair_rescue_rows_est_kernel,pair_select_est_kernel".
+ * Not in this version: a pair MAPQ, orientations other than forward / reverse, bins wider than one base or spans of
+ * AIM_PAIR_EST_MAX_HIST and more, an estimate carried across batches, compaction of the rescue rows. Check aim_features() &
+ * AIM_FEATURE_PAIR_ESTIMATE first. */
+#define AIM_PAIR_EST_MAX_HIST 8192u
+#define AIM_PAIR_EST_FALLBACK 0x1u      /* aim_pair_estimate_t.flags */
+#define AIM_PAIR_EST_CLAMPED 0x2u
+#define AIM_PAIR_EST_FLOORED 0x4u
+typedef struct aim_pair_est_params {
+    uint32_t hist_size;            /* bins of one base: 64..AIM_PAIR_EST_MAX_HIST, a multiple of 64 */
+    uint32_t min_samples;          /* >= 1: fewer binned samples give the fallback */
+    uint32_t min_mapq;             /* 0..60 */
+    uint32_t min_slack;            /* a floor for the spread 3 * IQR */
+} aim_pair_est_params_t; /* 16 B */
+typedef struct aim_pair_estimate {
+    int64_t min_span, max_span;    /* lo and hi */
+    uint32_t n_samples, n_beyond, p25, p50, p75;
+    uint32_t flags;                /* AIM_PAIR_EST_* */
+    uint32_t pad[2];               /* 0 */
+} aim_pair_estimate_t; /* 48 B, 16-byte aligned in device memory */
+size_t aim_pair_estimate_scratch(uint32_t hist_size);   /* 4 * hist_size + 16 */
+int aim_pair_estimate_device(const aim_map_pair_params_t *pp, const aim_pair_est_params_t *ep, uint32_t K, uint32_t read_size, uint32_t n_reads,
+                             const aim_segment_t *d_seg, const aim_sam_t *d_sam, const aim_chain_class_t *d_class, const uint32_t *d_contig_or_null,
+                             aim_pair_estimate_t *d_est, void *d_scratch, size_t scratch_bytes, void *hip_stream);
+int aim_pair_rescue_rows_device_est(const aim_map_pair_params_t *pp, uint32_t K, uint32_t read_size, uint64_t ref_len, uint32_t n_contigs,
+                                    const uint32_t *d_contig_start, const uint32_t *d_contig_len, uint32_t n_reads, const int32_t *d_read_len,
+                                    const char *d_reads, const aim_segment_t *d_seg, const aim_sam_t *d_sam, const uint32_t *d_contig_or_null,
+                                    void *d_res_requests, uint64_t *d_res_text_pos, char *d_res_patterns, const aim_pair_estimate_t *d_est,
+                                    void *hip_stream);
+int aim_pair_select_device_est(const aim_map_pair_params_t *pp, uint32_t K, uint32_t read_size, uint32_t n_reads, const int32_t *d_read_len,
+                               aim_segment_t *d_seg, aim_sam_t *d_sam, aim_chain_class_t *d_class, uint32_t *d_contig_or_null,
+                               const aim_sam_t *d_res_sam, uint32_t cigar_base, uint32_t md_base, aim_map_pair_t *d_pairs,
+                               const aim_pair_estimate_t *d_est, void *hip_stream);
+/* Comma-separated rocprofv3 kernel-trace name prefixes of the four kernels rule 15c adds. */
+const char *aim_pair_estimate_kernel_names(void);
+int aim_mapper_set_pairing_estimated(aim_mapper_t *mapper, const aim_map_pair_params_t *pp, const aim_pair_est_params_t *ep);
+int aim_mapper_pair_estimate(aim_mapper_t *mapper, uint32_t slot, aim_pair_estimate_t *out);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
