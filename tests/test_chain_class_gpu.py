@@ -17,7 +17,7 @@ from gpu_buffers import Hip, cached  # noqa: E402
 from hand_stages import chain_then_classify  # noqa: E402
 from pipeline_batches import READ_SIZE, expected, reference, short_reads  # noqa: E402
 
-KS = (1, 2, 3, 4, 5, 8, 16)
+KS = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16)  # 7, 9, 15: a group of 8 one lane short, just past it, and a group of 16 one lane short
 MASKS = (1, 128, 256)
 N_READS = (1, 5, 67, 4099)          # below, across and beyond one workgroup; never a multiple of the reads per wavefront
 SHORT_ROWS = [(11, 1, None, 8, 8, 8, 2, 4), (11, 1, 5, 8, 32, 8, 2, 4), (13, 1, 10, 8, 32, 8, 2, 4)]
@@ -82,7 +82,7 @@ def mapq_batch(K, n):
 
 @pytest.mark.parametrize("with_mates", (False, True), ids=("reads", "mates"))
 @pytest.mark.parametrize("score_unit", (1, 3, 4))
-@pytest.mark.parametrize("K", (1, 4, 16))
+@pytest.mark.parametrize("K", (1, 2, 4, 7, 8, 9, 16))
 def test_read_mapq_equals_model(K, score_unit, with_mates):
     import chain_class_model as ccm
     with Hip() as h:

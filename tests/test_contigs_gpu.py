@@ -1,6 +1,7 @@
 """References of several sequences on the GPU. aim_contig_clip_device on synthetic slot tables against rule 13c's numpy model, every byte
 of the four buffers, for each K, batch size and contig count below, on a small and a large grid and under the poison knobs;
-aim_map_records_contigs_device on the same tables; Mapper.from_contigs end to end on the shared batch cut into three contigs
+aim_map_records_contigs_device on the same tables, under the knobs too, and on the tables of K = 3 padded with empty slots to every group
+width (tests/slot_padding.py); Mapper.from_contigs end to end on the shared batch cut into three contigs
 (tests/contig_model.py) with five reads planted on the contig edges, against the stages driven by hand and against the one-sequence
 mapper on the concatenation; two slots and a reused slot; and python -m aim_amd.map --contigs."""
 import json
@@ -20,7 +21,7 @@ import child  # noqa: E402
 import hand_stages as hs  # noqa: E402
 from gpu_buffers import Hip, copy_out, put  # noqa: E402
 
-KS = (1, 4, 16)
+KS = (1, 2, 3, 4, 6, 7, 8, 9, 15, 16)  # the three group widths of the record kernel full (4, 8, 16), one lane short, just past the width before, and 2
 N_READS = (1, 65, 2100)
 N_CONTIGS = (1, 2, 3, 1024, 1025, 5000)          # 1 024 | 1 025: the sampled table's step goes from 1 to 2; 5 000: step 8
 # every contig count at 65 reads; the ends of the range at the other two sizes (one lane of work, and 33 workgroups of it)
@@ -67,7 +68,8 @@ def test_clip_equals_model(K):
                 h.free()
 
 
-KNOB_CASES = ((4, 2100, 5000), (16, 65, 1025), (1, 2100, 3), (4, 65, 1024))
+KNOB_CASES = ((4, 2100, 5000), (16, 65, 1025), (1, 2100, 3), (4, 65, 1024), (6, 2100, 5000), (9, 65, 1025))
+RECORD_KNOB_CASES = ((6, 2100, 1025), (9, 65, 3))      # the record kernel in groups of 8 lanes, and of 16 that K does not fill
 
 
 def knob_batch():
@@ -76,6 +78,12 @@ def knob_batch():
         for i, (K, n, nc) in enumerate(KNOB_CASES):
             for j, g in enumerate(run_clip(h, K, n, nc)):
                 out["c%d_%d" % (i, j)] = g
+            h.free()
+        for i, (K, n, nc) in enumerate(RECORD_KNOB_CASES):
+            got = run_contig_records(h, K, n, nc)
+            for j, g in enumerate(got[0]):
+                out["rc%d_%d" % (i, j)] = g
+            out["off_%d" % i], out["rec_%d" % i] = got[1:]
             h.free()
     return out
 
@@ -91,41 +99,97 @@ def test_grid_and_poison_identical(tmp_path, env):
     assert "[aim plan] contig_clip_kernel grid=%d block=256 contigs=5000 step=8 slots=8400" % grid in p.stderr, p.stderr
     assert "[aim plan] contig_clip_kernel grid=5 block=256 contigs=1025 step=2 slots=1040" in p.stderr, p.stderr
     assert "block=256 contigs=3 step=1 slots=2100" in p.stderr and "[aim plan] contig_clip_kernel grid=2 block=256 contigs=1024 step=1 slots=260" in p.stderr, p.stderr
+    # the record kernel in groups of 8 lanes, and of 16 with K = 9: the launcher's own rule, ceil(reads / (256 / lanes)) under the
+    # resident grid of 8 workgroups per compute unit
+    line = "[aim plan] map_count_kernel grid=%d block=256 lanes=%d reads=%d K=%d; scan parts=%d per_part=1024; map_records_contig_kernel grid=%d block=256"
+    for lanes, n, K, parts in ((8, 2100, 6, 3), (16, 65, 9, 1)):
+        g = min(8 * int(env["AIM_CHIP_CUS"]), -(-n // (256 // lanes)))
+        assert line % (g, lanes, n, K, parts, g) in p.stderr, p.stderr
+    assert "block=256 contigs=5000 step=8 slots=12600" in p.stderr and "contig_clip_kernel grid=3 block=256 contigs=1025 step=2 slots=585" in p.stderr, p.stderr
     out = np.load(f)
     for i, (K, n, nc) in enumerate(KNOB_CASES):
         check_clip(K, n, nc, [out["c%d_%d" % (i, j)] for j in range(4)])
+    for i, (K, n, nc) in enumerate(RECORD_KNOB_CASES):
+        check_contig_records(K, n, nc, [out["rc%d_%d" % (i, j)] for j in range(4)], out["off_%d" % i], out["rec_%d" % i])
+
+
+def run_contig_records(h, K, n, nc):
+    """The clip over map_records_model's slot tables (their aim_segment_t flags drive the clip's synthetic slots), then
+    aim_map_records_contigs_device with d_contig straight from the clip on the device: (the clip's four buffers, rec_offsets, records)
+    as bytes, guards included."""
+    import map_records_model as mm
+    from aim_amd import engine
+    seg, sam, cls = mm.synthetic_tables(11, K, n)
+    got, (d_sg, d_ct, d_st) = run_clip(h, K, n, nc, seg_flags=seg["flags"], keep=True)
+    d_off, d_rec = h.filled(4 * (n + 1) + GUARD), h.filled(64 * n * K + GUARD)
+    sb = engine.map_records_scratch(n)
+    engine.map_records_contigs_device(K, n, d_sg, h.up(sam), h.up(cls), d_ct, nc, d_st, d_off, d_rec, h.filled(sb), sb)
+    return got, h.down(d_off, 4 * (n + 1) + GUARD), h.down(d_rec, 64 * n * K + GUARD)
+
+
+def check_records(case, n, off_b, rec_b, want_off, want):
+    import map_records_model as mm
+    assert off_b[:4 * (n + 1)].tobytes() == want_off.tobytes() and (off_b[4 * (n + 1):] == 0xEE).all(), case
+    total = int(want_off[n])
+    g = rec_b[:64 * total].view(mm.RECORD_DTYPE)
+    if g.tobytes() != want.tobytes():
+        bad = np.nonzero((g.view(np.uint8).reshape(total, 64) != want.view(np.uint8).reshape(total, 64)).any(axis=1))[0]
+        raise AssertionError((case, bad[:8].tolist(), g[bad[0]], want[bad[0]]))
+    assert (rec_b[64 * total:] == 0xEE).all(), "written past the records"
+
+
+def check_contig_records(K, n, nc, clip_bytes, off_b, rec_b):
+    import contig_model as cg
+    import map_records_model as mm
+    seg, sam, cls = mm.synthetic_tables(11, K, n)
+    check_clip(K, n, nc, clip_bytes, seg_flags=seg["flags"])
+    lens, starts, ref_len, d, o = cg.synthetic_clip(SEED, K, n, nc, seg["flags"])
+    want_off, want = cg.records(K, n, o["seg"], sam, cls, o["contig"], starts)
+    check_records((K, n, nc), n, off_b, rec_b, want_off, want)
+    assert (want["sam"]["pad"] == cg.NONE).any() or n == 1
 
 
 @pytest.mark.parametrize("K", KS)
 def test_contig_records_equal_model(K):
     """map_records_model's slot tables, their aim_segment_t flags driving the clip's synthetic slots, d_contig straight from the clip on
     the device: offsets and records equal the model byte for byte; n_reads = 0 writes rec_offsets[0] alone."""
-    import contig_model as cg
-    import map_records_model as mm
     from aim_amd import engine
     with Hip() as h:
         for n, nc in ((1, 1), (65, 3), (2100, 1025)):
-            seg, sam, cls = mm.synthetic_tables(11, K, n)
-            got, (d_sg, d_ct, d_st) = run_clip(h, K, n, nc, seg_flags=seg["flags"], keep=True)
-            check_clip(K, n, nc, got, seg_flags=seg["flags"])
-            lens, starts, ref_len, d, o = cg.synthetic_clip(SEED, K, n, nc, seg["flags"])
-            d_off, d_rec = h.filled(4 * (n + 1) + GUARD), h.filled(64 * n * K + GUARD)
-            sb = engine.map_records_scratch(n)
-            engine.map_records_contigs_device(K, n, d_sg, h.up(sam), h.up(cls), d_ct, nc, d_st, d_off, d_rec, h.filled(sb), sb)
-            off_b, rec_b = h.down(d_off, 4 * (n + 1) + GUARD), h.down(d_rec, 64 * n * K + GUARD)
-            want_off, want = cg.records(K, n, o["seg"], sam, cls, o["contig"], starts)
-            assert off_b[:4 * (n + 1)].tobytes() == want_off.tobytes() and (off_b[4 * (n + 1):] == 0xEE).all(), (K, n)
-            total = int(want_off[n])
-            g = rec_b[:64 * total].view(mm.RECORD_DTYPE)
-            if g.tobytes() != want.tobytes():
-                bad = np.nonzero((g.view(np.uint8).reshape(total, 64) != want.view(np.uint8).reshape(total, 64)).any(axis=1))[0]
-                raise AssertionError((K, n, nc, bad[:8].tolist(), g[bad[0]], want[bad[0]]))
-            assert (rec_b[64 * total:] == 0xEE).all(), "written past the records"
-            assert (want["sam"]["pad"] == cg.NONE).any() or n == 1
+            check_contig_records(K, n, nc, *run_contig_records(h, K, n, nc))
             h.free()
         d_off = h.filled(8)
         engine.map_records_contigs_device(K, 0, None, None, None, None, 1, None, d_off, None, None, 0)
         assert h.down(d_off, 8).tolist() == [0, 0, 0, 0, 0xEE, 0xEE, 0xEE, 0xEE]
+
+
+def test_empty_slots_change_nothing_in_the_contig_records():
+    """tests/slot_padding.py on the device: the clipped tables of K = 3 with every read padded to 4, 8 and 16 slots (d_contig of an empty
+    slot: the read's slot 0) -- the same reads in groups of 4, 8 and 16 lanes -- give rec_offsets and, `slot` renamed, every record byte
+    of K = 3, which are the model's."""
+    import contig_model as cg
+    import map_records_model as mm
+    import slot_padding as sp
+    from aim_amd import engine
+    K, n, nc = 3, N_READS[1], 3
+    seg, sam, cls = mm.synthetic_tables(11, K, n)
+    lens, starts, ref_len, d, o = cg.synthetic_clip(SEED, K, n, nc, seg["flags"])
+    want_off, want = cg.records(K, n, o["seg"], sam, cls, o["contig"], starts)
+    assert (want["sam"]["pad"] == cg.NONE).any() and (want["sam"]["pad"] == 2).any() and int(want_off[n]) > n
+    with Hip() as h:
+        for K2 in (3, 4, 8, 16):
+            d_off, d_rec = h.filled(4 * (n + 1) + GUARD), h.filled(64 * n * K2 + GUARD)
+            sb = engine.map_records_scratch(n)
+            engine.map_records_contigs_device(K2, n, h.up(sp.pad(o["seg"], K, K2, n)), h.up(sp.pad(sam, K, K2, n)), h.up(sp.pad(cls, K, K2, n)),
+                                              h.up(sp.pad(o["contig"], K, K2, n, from_slot0=True)), nc, h.up(starts), d_off, d_rec, h.filled(sb), sb)
+            off_b, rec_b = h.down(d_off, 4 * (n + 1) + GUARD), h.down(d_rec, 64 * n * K2 + GUARD)
+            h.free()
+            if K2 == K:
+                check_records((K, n, nc), n, off_b, rec_b, want_off, want)
+                off3, rec3 = off_b, rec_b[:64 * int(want_off[n])].view(mm.RECORD_DTYPE)
+            assert off_b.tobytes() == off3.tobytes(), K2
+            assert rec_b[:64 * len(rec3)].tobytes() == sp.records_renamed(rec3, K, K2).tobytes(), K2
+            assert (rec_b[64 * len(rec3):] == 0xEE).all(), "written past the records"
 
 
 # ---- the mapper end to end -----------------------------------------------------------------------------------------------------------

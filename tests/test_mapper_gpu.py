@@ -1,5 +1,6 @@
 """The mapper on the GPU. aim_map_records_device on synthetic slot tables against rule 12c's numpy model, every output byte, for each K
-and batch size below, on a small and a large grid and under the poison knobs; aim_mapper_t end to end on the shared batch
+and batch size below, on a small and a large grid and under the poison knobs, and the tables of K = 3 padded with empty slots to every
+group width against themselves (tests/slot_padding.py); aim_mapper_t end to end on the shared batch
 (tests/mapper_batch.py: chimeric, unbroken and random reads) against the same stages driven by hand through the engine helpers plus the
 record model, with and without the segment extension; two slots, a reused slot, an empty batch and capacities set too small; and
 python -m aim_amd.map against samout over the mapper's own records."""
@@ -19,7 +20,7 @@ from gpu_buffers import Hip  # noqa: E402
 from hand_stages import single_end as hand_path  # noqa: E402
 from mapper_batch import map_alone  # noqa: E402
 
-KS = (1, 4, 16)
+KS = (1, 2, 3, 4, 6, 7, 8, 9, 15, 16)  # the three group widths full (4, 8, 16), one lane short, just past the width before, and 2
 N_READS = (1, 65, 2100)             # one group, across a wavefront, and 2 101 scan entries: three scan parts of 1 024
 GUARD = 64
 
@@ -70,7 +71,7 @@ def test_map_records_equal_model(K):
         assert h.down(d_off, 8).tolist() == [0, 0, 0, 0, 0xEE, 0xEE, 0xEE, 0xEE]
 
 
-KNOB_CASES = ((4, 2100), (16, 65), (1, 2100))
+KNOB_CASES = ((4, 2100), (16, 65), (1, 2100), (6, 2100), (9, 65))      # the last two: 8 lanes per read, and 16 that K does not fill
 
 
 def knob_batch():
@@ -93,9 +94,35 @@ def test_grid_and_poison_identical(tmp_path, env):
     line = "[aim plan] map_count_kernel grid=%d block=256 lanes=4 reads=2100 K=4; scan parts=3 per_part=1024; map_records_kernel grid=%d block=256"
     assert line % (grid, grid) in p.stderr, p.stderr
     assert "lanes=16 reads=65 K=16; scan parts=1 per_part=1024" in p.stderr, p.stderr
+    # the 8-lane path ran, and a 16-lane group of 9: the launcher's own rule, ceil(reads / (256 / lanes)) under the resident grid of
+    # 8 workgroups per compute unit
+    line = "[aim plan] map_count_kernel grid=%d block=256 lanes=%d reads=%d K=%d; scan parts=%d per_part=1024; map_records_kernel grid=%d block=256"
+    for lanes, n, K, parts in ((8, 2100, 6, 3), (16, 65, 9, 1)):
+        g = min(8 * int(env["AIM_CHIP_CUS"]), -(-n // (256 // lanes)))
+        assert line % (g, lanes, n, K, parts, g) in p.stderr, p.stderr
     out = np.load(f)
     for i, (K, n) in enumerate(KNOB_CASES):
         check_against_model(K, n, out["off_%d" % i], out["rec_%d" % i])
+
+
+def test_empty_slots_change_nothing():
+    """tests/slot_padding.py on the device: the tables of K = 3 with every read padded to 4, 8 and 16 slots -- the same reads in groups
+    of 4, 8 and 16 lanes -- give rec_offsets and, `slot` renamed, every record byte of K = 3, which are the model's."""
+    import map_records_model as mm
+    import slot_padding as sp
+    K, n = 3, N_READS[1]
+    seg, sam, cls = tables(K, n)
+    with Hip() as h:
+        off3, rec3 = run_map_records(h, K, n, seg, sam, cls)
+        check_against_model(K, n, off3, rec3)
+        total = int(off3[:4 * (n + 1)].view(np.uint32)[n])
+        assert total > n
+        for K2 in (4, 8, 16):
+            off, rec = run_map_records(h, K2, n, sp.pad(seg, K, K2, n), sp.pad(sam, K, K2, n), sp.pad(cls, K, K2, n))
+            h.free()
+            assert off[:4 * (n + 1)].tobytes() == off3[:4 * (n + 1)].tobytes() and (off[4 * (n + 1):] == 0xEE).all(), K2
+            assert rec[:64 * total].tobytes() == sp.records_renamed(rec3[:64 * total].view(mm.RECORD_DTYPE), K, K2).tobytes(), K2
+            assert (rec[64 * total:] == 0xEE).all(), "written past the records"
 
 
 # ---- the mapper end to end ---------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Rule 15c on the GPU. aim_pair_estimate_device and the _est twins of rule 14c's two kernels on synthetic slot tables against the Python
 models (tests/pair_estimate_model.py, tests/pair_model.py), every output byte, for each K, batch size and histogram size below, with and
-without d_contig, on a small and a large grid and under the poison knobs; then aim_mapper_t with estimation on the shared batch
+without d_contig, on a small and a large grid and under the poison knobs, and the tables of K = 3 padded with empty slots to every group
+width against themselves (tests/slot_padding.py); then aim_mapper_t with estimation on the shared batch
 (tests/pair_est_batch.py) against the stages driven by hand, against the true fragment lengths and against plain set_pairing with the
 fallback bounds; and the command line's --estimate-span."""
 import functools
@@ -20,7 +21,7 @@ import child  # noqa: E402
 import hand_stages as hs  # noqa: E402
 from gpu_buffers import Hip, copy_out, put, zeros  # noqa: E402
 
-KS = (1, 4, 16)
+KS = (1, 2, 3, 4, 6, 7, 8, 9, 15, 16)  # the three group widths full (4, 8, 16), one lane short, just past the width before, and 2
 N_READS = (2, 130, 4100)            # one group, across wavefronts, and more read pairs than one workgroup of any K holds
 GUARD = 64
 CIGAR_BASE, MD_BASE = 1000, 70000
@@ -148,7 +149,8 @@ def test_stages_equal_model(K, contigs):
         engine.pair_select_device_est(pp, K, pm.READ_SIZE, 0, None, None, None, None, None, 0, 0, None, None)
 
 
-KNOB_CASES = ((4, 4100, True, EST_SETS[2]), (16, 130, False, EST_SETS[3]), (1, 4100, False, EST_SETS[0]), (4, 4100, False, EST_SETS[1]))
+KNOB_CASES = ((4, 4100, True, EST_SETS[2]), (16, 130, False, EST_SETS[3]), (1, 4100, False, EST_SETS[0]), (4, 4100, False, EST_SETS[1]),
+              (6, 4100, True, EST_SETS[2]), (9, 130, False, EST_SETS[3]))      # the last two: 8 lanes per read pair, and 16 that K does not fill
 
 
 def knob_batch():
@@ -173,9 +175,52 @@ def test_grid_and_poison_identical(tmp_path, env):
     assert "[aim plan] pair_rescue_rows_est_kernel grid=%d block=256 lanes=4 reads=4100 K=4 rescue_size=512" % grid in p.stderr, p.stderr
     assert "[aim plan] pair_select_est_kernel grid=%d block=256 lanes=4 reads=4100 K=4 rescue=1" % grid in p.stderr, p.stderr
     assert "pair_span_hist_kernel grid=2 block=256 lanes=16 reads=130 K=16 hist_size=8192 lds=32772" in p.stderr, p.stderr
+    # the 8-lane path ran, and a 16-lane group of 9: the launchers' own rule, ceil(read pairs / (256 / lanes)) blocks under the resident
+    # grid of 8 workgroups per compute unit, a workgroup of the histogram kernel walking four blocks at least
+    resident = 8 * int(env["AIM_CHIP_CUS"])
+    for lanes, n, K, hist_size in ((8, 4100, 6, 1024), (16, 130, 9, 8192)):
+        blocks = -(-(n // 2) // (256 // lanes))
+        g, hg = min(resident, blocks), min(resident, -(-blocks // 4))
+        assert "[aim plan] pair_span_hist_kernel grid=%d block=256 lanes=%d reads=%d K=%d hist_size=%d lds=%d; pair_span_bounds_kernel grid=1 block=256" % (
+            hg, lanes, n, K, hist_size, 4 * (hist_size + 1)) in p.stderr, p.stderr
+        assert "[aim plan] pair_rescue_rows_est_kernel grid=%d block=256 lanes=%d reads=%d K=%d rescue_size=512" % (g, lanes, n, K) in p.stderr, p.stderr
+        assert "[aim plan] pair_select_est_kernel grid=%d block=256 lanes=%d reads=%d K=%d rescue=1" % (g, lanes, n, K) in p.stderr, p.stderr
     out = np.load(f)
     for i, (K, n, contigs, est_set) in enumerate(KNOB_CASES):
         check_against_model(K, n, contigs, est_set, {k[:-2]: out[k] for k in out.files if k.endswith("_%d" % i)})
+
+
+@pytest.mark.parametrize("contigs", (False, True), ids=("one-seq", "contigs"))
+def test_empty_slots_change_nothing(contigs):
+    """tests/slot_padding.py on the device: the tables of K = 3 with every read padded to 4, 8 and 16 slots -- the same read pairs in
+    groups of 4, 8 and 16 lanes -- give the 48 bytes of the estimate of K = 3 under every EST_SETS row, and behind it every byte of the
+    _est twins' outputs, slot numbers renamed. Those of K = 3 are the models'."""
+    import pair_model as pm
+    import slot_padding as sp
+    K, n = 3, N_READS[1]
+    t = tables(K, n, contigs)
+    samples = 0
+    with Hip() as h:
+        for est_set in EST_SETS:
+            a = run_stages(h, K, n, t, est_set)
+            h.free()
+            samples += int(check_against_model(K, n, contigs, est_set, a)["n_samples"])
+            for K2 in (4, 8, 16):
+                case = (K, K2, n, contigs, est_set)
+                t2 = sp.pad_tables(t, K, K2, n)
+                b = run_stages(h, K2, n, t2, est_set)
+                h.free()
+                for k in ("est_first", "est", "est_after", "scr_guard", "req", "tpos", "pat"):
+                    same(k, b[k], a[k], 1, case)
+                npairs = 32 * (n // 2)
+                same("pairs", b["pairs"][:npairs], sp.pairs_renamed(a["pairs"][:npairs].view(pm.PAIR_DTYPE), K, K2), 32, case)
+                assert (b["pairs"][npairs:] == 0xEE).all(), case
+                for k, dt in (("seg", pm.SEG_DTYPE), ("sam", pm.SAM_DTYPE), ("cls", pm.CLASS_DTYPE), ("contig", np.dtype("<u4"))):
+                    if k in a:
+                        own, rest = sp.unpad(b[k].view(dt), K, K2, n)
+                        same(k, own, a[k], dt.itemsize, case)
+                        same(k + " of the empty slots", rest, sp.unpad(t2[k], K, K2, n)[1], dt.itemsize, case)
+    assert samples
 
 
 # ---- the mapper with estimation -------------------------------------------------------------------------------------------------------

@@ -1,10 +1,12 @@
 """Rule 14c on the GPU. aim_pair_rescue_rows_device, aim_pair_select_device (apply included) and aim_map_mates_device on synthetic slot
 tables against the numpy model (tests/pair_model.py), every output byte -- the rescue rows and the pattern rows, aim_map_pair_t, the
 rewritten slot arrays, aim_map_mate_t and the records -- for each K and batch size below, with and without d_contig, on a small and a
-large grid and under the poison knobs; then aim_mapper_t with pairing on the shared paired batch (tests/pair_batch.py) against the
+large grid and under the poison knobs, and the tables of K = 3 padded with empty slots to every group width against themselves
+(tests/slot_padding.py); then aim_mapper_t with pairing on the shared paired batch (tests/pair_batch.py) against the
 stages driven by hand and against the truth; and a mapper without pairing against the bytes it always gave."""
 import functools
 import os
+import re
 import subprocess
 import sys
 
@@ -19,7 +21,7 @@ import child  # noqa: E402
 import hand_stages as hs  # noqa: E402
 from gpu_buffers import Hip, copy_out, put, zeros  # noqa: E402
 
-KS = (1, 4, 16)
+KS = (1, 2, 3, 4, 6, 7, 8, 9, 15, 16)  # the three group widths full (4, 8, 16), one lane short, just past the width before, and 2
 N_READS = (2, 130, 4100)            # one group, across wavefronts, and more read pairs than one workgroup of any K holds
 GUARD = 64
 CIGAR_BASE, MD_BASE = 1000, 70000
@@ -147,7 +149,7 @@ def test_stages_equal_model(K, contigs):
         engine.map_mates_device(K, 0, None, None, None, None, None, None)
 
 
-KNOB_CASES = ((4, 4100, True), (16, 130, False), (1, 4100, False))
+KNOB_CASES = ((4, 4100, True), (16, 130, False), (1, 4100, False), (6, 4100, True), (9, 130, False))     # the last two: 8 lanes, and 16 that K does not fill
 
 
 def knob_batch():
@@ -172,9 +174,63 @@ def test_grid_and_poison_identical(tmp_path, env):
     assert "[aim plan] pair_select_kernel grid=%d block=256 lanes=4 reads=4100 K=4 rescue=1" % grid in p.stderr, p.stderr
     assert "[aim plan] map_mates_kernel grid=%d block=256 reads=4100 K=4" % mgrid in p.stderr, p.stderr
     assert "pair_select_kernel grid=5 block=256 lanes=16 reads=130 K=16" in p.stderr, p.stderr
+    # the 8-lane path ran, and a 16-lane group of 9: the launchers' own rule, ceil(read pairs / (256 / lanes)) under the resident grid
+    # of 8 workgroups per compute unit (the record kernels: ceil(reads / (256 / lanes)))
+    resident = 8 * int(env["AIM_CHIP_CUS"])
+    for lanes, n, K, records in ((8, 4100, 6, "map_records_contig_kernel"), (16, 130, 9, "map_records_kernel")):
+        g, rg = min(resident, -(-(n // 2) // (256 // lanes))), min(resident, -(-n // (256 // lanes)))
+        assert "[aim plan] pair_rescue_rows_kernel grid=%d block=256 lanes=%d reads=%d K=%d rescue_size=512" % (g, lanes, n, K) in p.stderr, p.stderr
+        assert "[aim plan] pair_select_kernel grid=%d block=256 lanes=%d reads=%d K=%d rescue=1" % (g, lanes, n, K) in p.stderr, p.stderr
+        assert re.search(r"\[aim plan\] map_count_kernel grid=%d block=256 lanes=%d reads=%d K=%d; scan parts=\d+ per_part=\d+; %s grid=%d block=256"
+                         % (rg, lanes, n, K, records, rg), p.stderr), p.stderr
     out = np.load(f)
     for i, (K, n, contigs) in enumerate(KNOB_CASES):
         check_against_model(K, n, contigs, {k[:-2]: out[k] for k in out.files if k.endswith("_%d" % i)})
+
+
+def same_after_renaming(K, K2, n, t2, a, b):
+    """run_stages' bytes b over the tables t2 -- those of K padded to K2 slots per read (tests/slot_padding.py) -- against a, the bytes
+    over the tables themselves: what is per read is the same, slot numbers are renamed, apply leaves the empty slots as they were."""
+    import pair_model as pm
+    import slot_padding as sp
+    case = (K, K2, n)
+    for k in ("req", "tpos", "pat", "off"):                        # (the rescue rows run with rescue alone)
+        if k in a:
+            same(k, b[k], a[k], 1, case)
+    npairs = 32 * (n // 2)
+    same("pairs", b["pairs"][:npairs], sp.pairs_renamed(a["pairs"][:npairs].view(pm.PAIR_DTYPE), K, K2), 32, case)
+    assert (b["pairs"][npairs:] == 0xEE).all(), case
+    for k, dt in (("seg", pm.SEG_DTYPE), ("sam", pm.SAM_DTYPE), ("cls", pm.CLASS_DTYPE), ("contig", np.dtype("<u4"))):
+        if k in a:
+            own, rest = sp.unpad(b[k].view(dt), K, K2, n)
+            same(k, own, a[k], dt.itemsize, case)
+            same(k + " of the empty slots", rest, sp.unpad(t2[k], K, K2, n)[1], dt.itemsize, case)
+    total = int(a["off"].view(np.uint32)[n])
+    for k in ("rec_before", "rec"):
+        same(k, b[k][:64 * total], sp.records_renamed(a[k][:64 * total].view(pm.RECORD_DTYPE), K, K2), 64, case)
+    same("mates", b["mates"][:16 * total], a["mates"][:16 * total], 16, case)
+    assert (b["rec"][64 * n * K2:] == 0xEE).all() and (b["mates"][16 * total:] == 0xEE).all(), case
+
+
+@pytest.mark.parametrize("contigs", (False, True), ids=("one-seq", "contigs"))
+def test_empty_slots_change_nothing(contigs):
+    """tests/slot_padding.py on the device: the tables of K = 3 with every read padded to 4, 8 and 16 slots -- the same read pairs in
+    groups of 4, 8 and 16 lanes -- through the rescue rows, select / apply, the records and the mates, with and without rescue: every
+    byte of K = 3, slot numbers renamed. Those of K = 3 are the model's."""
+    import pair_model as pm
+    import slot_padding as sp
+    K, n = 3, N_READS[1]
+    t = tables(K, n, contigs)
+    with Hip() as h:
+        for rescue in (True, False):
+            a = run_stages(h, K, n, t, rescue=rescue)
+            h.free()
+            f = check_against_model(K, n, contigs, a, rescue=rescue)["flags"]
+            assert (f & pm.PROPER).any() and bool((f & (pm.RESCUED_A | pm.RESCUED_B)).any()) == rescue
+            for K2 in (4, 8, 16):
+                t2 = sp.pad_tables(t, K, K2, n)
+                same_after_renaming(K, K2, n, t2, a, run_stages(h, K2, n, t2, rescue=rescue))
+                h.free()
 
 
 # ---- the mapper with pairing ---------------------------------------------------------------------------------------------------------

@@ -21,7 +21,7 @@ from hand_stages import chain_classify_split  # noqa: E402
 from pipeline_batches import FULL, READ_SIZE, chimeric_expected, expected, reference, short_reads  # noqa: E402
 from sam_model import HAND_ROWS, make_reference  # noqa: E402
 
-KS = (1, 4, 8, 16)
+KS = (1, 3, 4, 5, 8, 11, 16)       # (lanes follow the row size here, but lanes i < K carry the decision: 3, 5 and 11 leave the group of a K unfilled)
 N_READS = (1, 65, 4099)             # below, across and beyond one workgroup; never a multiple of the reads per wavefront
 READ_SIZES = (104, 1024)            # 16 lanes per read, 64 lanes per read
 OUT = ("seg_req", "seg_text_pos", "seg_patterns", "seg")
