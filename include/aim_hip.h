@@ -763,7 +763,9 @@ const char *aim_minimizer_kernel_names(void);
  * d_read_len[n_reads], the index of a reference of ref_len bytes, and the outputs of the rule above: d_requests
  * (aim_request_t[n_reads * K]), d_text_pos, d_votes (each [n_reads * K]) and d_seed[n_reads]. The call only enqueues work on
  * hip_stream and needs no scratch: everything per read lives in LDS. A read_len outside 0..read_size is clamped; index entries that
- * point outside the arrays aim_index_sizes describes make a seed count as absent, never a fault. AIM_EINVAL with a message naming the
+ * point outside the arrays aim_index_sizes describes make a seed count as absent, never a fault: a code c whose entries fail
+ * bucket[c] <= bucket[c + 1] <= pos_capacity has no positions, and every other code has pos[bucket[c] .. bucket[c + 1]) as it
+ * stands, in the array's order. AIM_EINVAL with a message naming the
  * field for every bound of aim_seed_params_t, for ref_len, and for n_reads * K >= 2^32. With options = AIM_SEED_OPT_MINIMIZERS(w) the
  * kernel is seed_minimizer_kernel and d_bucket / d_pos must be a minimizer index of the same (k, w). */
 int aim_seed_device(const aim_seed_params_t *sp, uint32_t n_reads, const int32_t *d_read_len, const char *d_reads,
