@@ -12,8 +12,9 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sam_model  # noqa: E402
-from gpu_buffers import Hip  # noqa: E402
+from gpu_buffers import Hip  # noqa: E402,F401  (other test modules reach it as S.Hip)
 from sam_model import HAND_ROWS, make_reference as reference  # noqa: E402
+from sam_rows import sam_device  # noqa: E402
 
 MINUS = 1 << 63
 UINT32_MAX = 0xFFFFFFFF
@@ -113,26 +114,6 @@ def both(kw, ms, rs, algo, ref, req, pat, tpos, eqx=False, check=True, **sub):
         assert np.array_equal(o1["sam"]["status"], o0["res"]["status"].astype(np.uint16))
         assert sam_model.check_records(o1["sam"], o1["sam_cigar"], o1["sam_md"], exp) == []
     return out0, out1, exps, p0
-
-
-def sam_device(params, res, ops, tpos, ref, sel=None, options=0, ccap=1, mcap=1, req=None):
-    """aim_sam_device over rows uploaded to the device: (records, words, bytes, cursors). A guard word / byte sits behind each
-    capacity."""
-    from aim_amd import capi, engine
-    with Hip() as h:
-        n = len(res)
-        d_res, d_ops, d_tp = h.up(res), h.up(ops, 64), h.up(np.asarray(tpos, dtype=np.uint64))
-        d_ref = h.up(ref, 16)
-        d_req = h.up(req if req is not None else np.zeros(max(len(tpos), 1), dtype=capi.REQUEST_DTYPE))
-        d_sel = None if sel is None else h.up(np.asarray(sel, dtype=np.uint32))
-        d_sam = h.up(np.zeros(n * 48, dtype=np.uint8))
-        d_cg = h.up(np.full(ccap + 1, 0x7E7E7E7E, dtype=np.uint32))
-        d_md = h.up(np.full(mcap + 1, 0x7E, dtype=np.uint8))
-        d_cur = h.up(np.full(2, 0xFFFFFFFF, dtype=np.uint32))
-        engine.sam_device(params, n, d_req, d_tp, d_sel, d_res, d_ops, d_ref, len(ref), options, d_sam, d_cg, ccap, d_md, mcap, d_cur, None)
-        cg, md = h.down(d_cg, 4 * (ccap + 1)).view(np.uint32), h.down(d_md, mcap + 1)
-        assert int(cg[ccap]) == 0x7E7E7E7E and int(md[mcap]) == 0x7E, "written past a capacity"
-        return h.down(d_sam, n * 48).view(capi.SAM_DTYPE), cg[:ccap], md[:mcap], h.down(d_cur, 8).view(np.uint32)
 
 
 def endsfree_batch(seed, n, ref):

@@ -20,6 +20,7 @@ from gpu_buffers import Hip, cached, put  # noqa: E402
 from hand_stages import chain_classify_split  # noqa: E402
 from pipeline_batches import FULL, READ_SIZE, chimeric_expected, expected, reference, short_reads  # noqa: E402
 from sam_model import HAND_ROWS, make_reference  # noqa: E402
+from sam_rows import sam_both  # noqa: E402
 
 KS = (1, 3, 4, 5, 8, 11, 16)       # (lanes follow the row size here, but lanes i < K carry the decision: 3, 5 and 11 leave the group of a K unfilled)
 N_READS = (1, 65, 4099)             # below, across and beyond one workgroup; never a multiple of the reads per wavefront
@@ -244,32 +245,6 @@ def whole_path():
 
 # ---- aim_sam_device_split on hand-made rows ---------------------------------------------------------------------------------------
 HAND_RS, HAND_CAP = 1024, 5000
-
-
-def sam_both(params, res, ops, tpos, ref, seg, sel=None, options=0, ccap=1, mcap=1, split_ccap=None):
-    """aim_sam_device and aim_sam_device_split over the same uploaded rows: two tuples (records, words, bytes, cursors). A guard word /
-    byte sits behind each capacity. split_ccap: another CIGAR capacity for the split call."""
-    from aim_amd import capi, engine
-    with Hip() as h:
-        n = len(res)
-        d_res, d_ops, d_tp, d_ref = h.up(res), h.up(ops, 64), h.up(np.asarray(tpos, dtype=np.uint64)), h.up(ref, 16)
-        d_req = h.up(np.zeros(max(len(tpos), 1), dtype=capi.REQUEST_DTYPE))
-        d_sel = None if sel is None else h.up(np.asarray(sel, dtype=np.uint32))
-        d_seg = h.up(seg)
-        out = []
-        for split in (False, True):
-            cc = split_ccap if split and split_ccap is not None else ccap
-            d_sam, d_cg, d_md = h.up(np.zeros(n * 48, dtype=np.uint8)), h.up(np.full(cc + 1, 0x7E7E7E7E, dtype=np.uint32)), h.up(np.full(mcap + 1, 0x7E, dtype=np.uint8))
-            d_cur = h.up(np.full(2, 0xFFFFFFFF, dtype=np.uint32))
-            args = (params, n, d_req, d_tp, d_sel, d_res, d_ops, d_ref, len(ref), options, d_sam, d_cg, cc, d_md, mcap, d_cur)
-            if split:
-                engine.sam_device_split(*args, d_seg, None)
-            else:
-                engine.sam_device(*args, None)
-            cg, md = h.down(d_cg, 4 * (cc + 1)).view(np.uint32), h.down(d_md, mcap + 1)
-            assert int(cg[cc]) == 0x7E7E7E7E and int(md[mcap]) == 0x7E, "written past a capacity"
-            out.append((h.down(d_sam, n * 48).view(capi.SAM_DTYPE), cg[:cc], md[:mcap], h.down(d_cur, 8).view(np.uint32)))
-        return out
 
 
 def hand_rows():
