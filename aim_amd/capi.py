@@ -71,6 +71,11 @@ PAIR_PROPER, PAIR_RESCUE_TRIED_A, PAIR_RESCUE_TRIED_B, PAIR_RESCUED_A, PAIR_RESC
 FEATURE_PAIR_ESTIMATE = 0x400000  # aim_features(): aim_pair_estimate_device / the _est entry points / aim_mapper_set_pairing_estimated exist (rule 15c)
 PAIR_EST_MAX_HIST = 8192          # aim_pair_est_params_t.hist_size: 64..this, a multiple of 64
 PAIR_EST_FALLBACK, PAIR_EST_CLAMPED, PAIR_EST_FLOORED = 0x1, 0x2, 0x4   # aim_pair_estimate_t.flags
+FEATURE_SECONDARY = 0x800000      # aim_features(): aim_secondary_rows_device / aim_secondary_select_device / aim_map_records_secondary_device / aim_mapper_set_secondary exist (rule 16c)
+SEC_MAX = 15                      # max_sec is 1..SEC_MAX
+SEC_RECORDS = 0x1                 # aim_map_sec_params_t.options: the other mapped members of a locus as SAM_SECONDARY records
+SAM_SECONDARY = 0x100             # aim_sam_t.flags, from aim_map_records_secondary_device
+SEC_SWAPPED, SEC_COMPLETE = 0x1, 0x2   # aim_sec_slot_t.flags / aim_map_sec_t.flags; aim_sec_slot_t.flags >> 4 is n_members - 1
 
 
 def CONTIG_SPACER(band):
@@ -233,6 +238,22 @@ PAIR_ESTIMATE_DTYPE = np.dtype([("min_span", "<i8"), ("max_span", "<i8"), ("n_sa
 assert C.sizeof(PairEstParams) == 16 and C.sizeof(PairEstimate) == 48 and PAIR_ESTIMATE_DTYPE.itemsize == 48
 
 
+class MapSecParams(C.Structure):
+    """aim_map_sec_params_t"""
+    _fields_ = [("max_sec", C.c_uint32), ("options", C.c_uint32)]
+
+
+class MapperSecondaryOut(C.Structure):
+    """aim_mapper_secondary_out_t"""
+    _fields_ = [("n_records", C.c_uint32), ("pad", C.c_uint32), ("sec", C.c_void_p)]
+
+
+SEC_SLOT_DTYPE = np.dtype([("role", "u1"), ("family", "u1"), ("mapq", "u1"), ("aln_mapq", "u1"), ("n_tied", "u1"), ("flags", "u1"), ("gap", "<u2")])   # aim_sec_slot_t
+MAP_SEC_DTYPE = np.dtype([("family_slot", "<u4"), ("second_score", "<i4"), ("aln_mapq", "u1"), ("chain_mapq", "u1"), ("n_members", "u1"), ("n_tied", "u1"),
+                          ("flags", "<u4")])   # aim_map_sec_t
+assert C.sizeof(MapSecParams) == 8 and C.sizeof(MapperSecondaryOut) == 16 and SEC_SLOT_DTYPE.itemsize == 8 and MAP_SEC_DTYPE.itemsize == 16
+
+
 class BatchIO(C.Structure):
     """aim_batch_io_t"""
     _fields_ = [("n_pairs", C.c_uint32), ("requests", C.c_void_p), ("patterns", C.c_void_p), ("texts", C.c_void_p),
@@ -374,6 +395,13 @@ SYMBOLS = {
     "aim_pair_estimate_kernel_names": (C.c_char_p, []),
     "aim_mapper_set_pairing_estimated": (C.c_int, [_VP, C.POINTER(MapPairParams), C.POINTER(PairEstParams)]),
     "aim_mapper_pair_estimate": (C.c_int, [_VP, _U32, C.POINTER(PairEstimate)]),
+    "aim_secondary_rows_device": (C.c_int, [_U32, _U32, _I32, C.c_uint64, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _VP]),
+    "aim_secondary_select_device": (C.c_int, [_U32, _U32, _VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP]),
+    "aim_map_records_secondary_device": (C.c_int, [_U32, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "aim_secondary_kernel_names": (C.c_char_p, []),
+    "aim_mapper_secondary_device_bytes": (C.c_int, [C.POINTER(MapperParams), C.POINTER(MapSecParams), C.POINTER(C.c_uint64)]),
+    "aim_mapper_set_secondary": (C.c_int, [_VP, C.POINTER(MapSecParams)]),
+    "aim_mapper_secondary": (C.c_int, [_VP, _U32, C.POINTER(MapperSecondaryOut)]),
 }
 
 _lib = None

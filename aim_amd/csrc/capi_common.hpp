@@ -2,7 +2,7 @@
 // launches, and the stateless alignment entry points), capi_groups.hip (the read-groups path: AIM_FLAG_READ_GROUPS, MATE_PAIRS and
 // TOP_HITS) -- these three share the device set and launch() through capi_set.hpp --,
 // capi_plan.hip (the launch planner; its types and entry points are in plan.hpp), capi_pipeline.hip (index, seeding, classes and MAPQ,
-// split, extension), capi_mapper.hip (the record list and aim_mapper_t), capi_pair.hip (rule 14c's stateless entry points) and capi_host.hip (host-side formatters and
+// split, extension), capi_mapper.hip (the record list and aim_mapper_t), capi_pair.hip (rule 14c's stateless entry points), capi_secondary.hip (rule 16c's) and capi_host.hip (host-side formatters and
 // generators). None of
 // them compiles a kernel: each kernel family's tu_*.hip does, and these units call its launchers. Internal, not installed.
 // Every function declared here has ONE definition, next to the state it owns: fail() in aim_capi.hip, where it writes the thread-local

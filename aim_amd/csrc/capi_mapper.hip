@@ -3,6 +3,8 @@
 // index and per-slot buffers and streams and runs the stages of capi_pipeline.hip and aim_capi.hip through their public entry points.
 // Rule 13c (AIM_FEATURE_CONTIGS) lives here too: the contig layout, aim_contig_clip_device (kernel in contig.hpp),
 // aim_map_records_contigs_device and the mapper of a reference of several sequences.
+// Rule 16c's mapper side (AIM_FEATURE_SECONDARY: aim_mapper_set_secondary, aim_mapper_secondary) is here as well; its stateless entry points
+// are in capi_secondary.hip.
 // Host code only. What this unit shares with the others is in capi_common.hpp.
 #include <algorithm>
 #include <cstdio>
@@ -14,6 +16,7 @@
 #include "contig.hpp"
 #include "index.hpp"
 #include "mapper.hpp"
+#include "secondary.hpp"
 
 using namespace aim::capi;
 
@@ -67,6 +70,15 @@ int check_pairing(const char *fn, const aim_mapper_params_t &p, const aim_map_pa
     }
     if ((uint64_t)p.cigar_cap + pp->rescue_cigar_cap >= (1ull << 32) || (uint64_t)p.md_cap + pp->rescue_md_cap >= (1ull << 32))
         return fail(AIM_EINVAL, "%s: cigar_cap + rescue_cigar_cap and md_cap + rescue_md_cap must stay below 2^32", fn);
+    return AIM_OK;
+}
+
+// The refusals of rule 16c's aim_map_sec_params_t, under the name `fn`; no device is asked anything.
+int check_secondary(const char *fn, const aim_map_sec_params_t *sp)
+{
+    if (!sp) return fail(AIM_EINVAL, "%s: params is NULL", fn);
+    if (sp->max_sec < 1 || sp->max_sec > AIM_SEC_MAX) return fail(AIM_EINVAL, "%s: max_sec %u is outside 1..%u", fn, sp->max_sec, AIM_SEC_MAX);
+    if (sp->options & ~AIM_SEC_RECORDS) return fail(AIM_EINVAL, "%s: unknown options 0x%x", fn, sp->options);
     return AIM_OK;
 }
 
@@ -132,7 +144,9 @@ enum Buf { B_READS, B_READ_LEN, B_REQ, B_TEXT_POS, B_VOTES, B_SEED, B_CHAINS, B_
            // rule 14c, after aim_mapper_set_pairing alone (the B_RES_* only with AIM_PAIR_RESCUE): a mapper without it keeps its layout
            B_PAIRS, B_MATES, B_RES_CURSORS, B_RES_REQ, B_RES_TEXT_POS, B_RES_PATTERNS, B_RES_RESULTS, B_RES_OPS, B_RES_SCRATCH, B_RES_SAM,
            // rule 15c, after aim_mapper_set_pairing_estimated alone: the estimate and its histogram
-           B_EST, B_EST_SCRATCH, B_COUNT };
+           B_EST, B_EST_SCRATCH,
+           // rule 16c, after aim_mapper_set_secondary alone: aim_sec_slot_t per slot and aim_map_sec_t per record
+           B_SEC, B_SEC_RECORDS, B_COUNT };
 
 struct SlotLayout {
     uint64_t at[B_COUNT], bytes[B_COUNT], total;
@@ -141,7 +155,7 @@ struct SlotLayout {
 inline uint64_t up256(uint64_t x) { return (x + 255u) & ~255ull; }
 
 SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch, bool contigs, const aim_map_pair_params_t *pp = nullptr, size_t rescue_scratch = 0,
-                       const aim_pair_est_params_t *ep = nullptr)
+                       const aim_pair_est_params_t *ep = nullptr, bool secondary = false)
 {
     const uint64_t N = p.max_reads, K = (uint64_t)p.seed.max_cands, rs = (uint64_t)p.seed.read_size, S = N * K;
     SlotLayout L;
@@ -168,10 +182,13 @@ SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch, bool 
     if (pp && ep) {                      // rule 15c
         b[B_EST] = sizeof(aim_pair_estimate_t); b[B_EST_SCRATCH] = aim_pair_estimate_scratch(ep->hist_size);
     }
+    if (secondary) {                     // rule 16c
+        b[B_SEC] = sizeof(aim_sec_slot_t) * S; b[B_SEC_RECORDS] = sizeof(aim_map_sec_t) * S;
+    }
     uint64_t at = 0;
     for (int i = 0; i < B_COUNT; ++i) {
         L.at[i] = at;
-        if (i >= B_CONTIG && !b[i]) continue;   // the buffers of rules 13c, 14c and 15c exist only where the rule runs
+        if (i >= B_CONTIG && !b[i]) continue;   // the buffers of rules 13c to 16c exist only where the rule runs
         at += up256(std::max<uint64_t>(b[i], 4));
     }
     L.total = at;
@@ -197,6 +214,8 @@ struct MapperSlot {
     bool waited = false;
     aim_mapper_pairs_out_t po = {};
     aim_pair_estimate_t *h_est = nullptr;   // rule 15c (aim_mapper_set_pairing_estimated): pinned; the last batch waited for
+    aim_map_sec_t *h_sec = nullptr;      // rule 16c (aim_mapper_set_secondary): pinned; the view of aim_mapper_secondary
+    uint32_t n_records = 0;              // ... and how many of them the last wait copied
 };
 
 }  // namespace
@@ -219,6 +238,8 @@ struct aim_mapper {
     size_t rescue_scratch = 0;
     bool estimated = false;              // rule 15c: ... through aim_mapper_set_pairing_estimated
     aim_pair_est_params_t ep = {};
+    bool secondary = false;              // rule 16c: aim_mapper_set_secondary was called
+    aim_map_sec_params_t sc = {};
 };
 
 namespace {
@@ -232,7 +253,7 @@ void release(aim_mapper *m)
         if (s.stream) (void)hipStreamSynchronize(s.stream);
         if (s.dev) (void)hipFree(s.dev);
         for (void *h : {(void *)s.h_reads, (void *)s.h_read_len, (void *)s.h_records, (void *)s.h_offsets, (void *)s.h_cigar, (void *)s.h_md, (void *)s.h_head,
-                        (void *)s.h_mates, (void *)s.h_pairs, (void *)s.h_res_head, (void *)s.h_est})
+                        (void *)s.h_mates, (void *)s.h_pairs, (void *)s.h_res_head, (void *)s.h_est, (void *)s.h_sec})
             if (h) (void)hipHostFree(h);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
@@ -608,6 +629,9 @@ int aim_mapper_submit(aim_mapper_t *m, uint32_t slot, uint32_t n_reads, const in
     if (!rc && (p.options & AIM_MAP_EXTEND))
         rc = aim_extend_segments_device(&p.extend, K, rs, m->ref_len, n_reads, d_rl, d_reads, m->d_ref, d_seg_req, d_seg_tp, d_seg_pat, d_seg,
                                         at<aim_extend_t>(m, s, B_EXT), st);
+    if (!rc && m->secondary)             // rule 16c, part 1: rows for the secondaries, where the split left empty slots
+        rc = aim_secondary_rows_device(K, rs, flank, m->ref_len, n_reads, d_rl, d_reads, d_req, d_tp, d_seed, d_chains, d_cls, d_seg_req, d_seg_tp, d_seg_pat, d_seg,
+                                       m->sc.max_sec, st);
     const uint32_t n_contigs = (uint32_t)m->starts.size();
     uint32_t *d_contig = at<uint32_t>(m, s, B_CONTIG);
     if (!rc && n_contigs)
@@ -618,7 +642,13 @@ int aim_mapper_submit(aim_mapper_t *m, uint32_t slot, uint32_t n_reads, const in
         rc = aim_sam_device_split(&m->ap.base, rows, d_seg_req, d_seg_tp, nullptr, d_res, d_ops, m->d_ref, m->ref_len, p.sam_options, d_sam, at<uint32_t>(m, s, B_CIGAR),
                                   p.cigar_cap, at<char>(m, s, B_MD), p.md_cap, d_cursors, d_seg, st);
     if (!rc && m->paired) rc = submit_pairing(m, s, n_reads, st);   // rule 14c in front of the record kernel: rescue, select / apply
-    if (!rc)
+    if (!rc && m->secondary) {           // ... part 2: one winner per locus; part 3: the records over loci
+        rc = aim_secondary_select_device(K, n_reads, d_seg, d_sam, d_cls, d_chains, p.max_score, p.mismatch, at<aim_sec_slot_t>(m, s, B_SEC), st);
+        if (!rc)
+            rc = aim_map_records_secondary_device(K, n_reads, m->sc.options, d_seg, d_sam, d_cls, at<aim_sec_slot_t>(m, s, B_SEC), n_contigs ? d_contig : nullptr, n_contigs,
+                                                  n_contigs ? m->d_contig_start : nullptr, d_off, at<aim_map_record_t>(m, s, B_RECORDS),
+                                                  at<aim_map_sec_t>(m, s, B_SEC_RECORDS), at<void>(m, s, B_MAP_SCRATCH), kMapScratch, st);
+    } else if (!rc)
         rc = n_contigs ? aim_map_records_contigs_device(K, n_reads, d_seg, d_sam, d_cls, d_contig, n_contigs, m->d_contig_start, d_off,
                                                         at<aim_map_record_t>(m, s, B_RECORDS), at<void>(m, s, B_MAP_SCRATCH), kMapScratch, st)
                        : aim_map_records_device(K, n_reads, d_seg, d_sam, d_cls, d_off, at<aim_map_record_t>(m, s, B_RECORDS), at<void>(m, s, B_MAP_SCRATCH), kMapScratch, st);
@@ -649,6 +679,7 @@ int aim_mapper_wait(aim_mapper_t *m, uint32_t slot, aim_mapper_out_t *out)
     out->n_reads = s.n_reads;
     out->records = s.h_records; out->rec_offsets = s.h_offsets; out->cigar = s.h_cigar; out->md = s.h_md;
     s.h_offsets[0] = 0;
+    s.n_records = 0;
     if (m->estimated) {                  // an empty batch: the fallback, every count 0
         memset(s.h_est, 0, sizeof *s.h_est);
         s.h_est->min_span = m->pp.min_span; s.h_est->max_span = m->pp.max_span; s.h_est->flags = AIM_PAIR_EST_FALLBACK;
@@ -668,6 +699,10 @@ int aim_mapper_wait(aim_mapper_t *m, uint32_t slot, aim_mapper_out_t *out)
     HIP_TRY(hipMemcpyAsync(s.h_offsets, d_off, 4ull * (s.n_reads + 1u), hipMemcpyDeviceToHost, s.stream));
     if (out->cigar_words) HIP_TRY(hipMemcpyAsync(s.h_cigar, at<char>(m, s, B_CIGAR), 4ull * out->cigar_words, hipMemcpyDeviceToHost, s.stream));
     if (out->md_bytes) HIP_TRY(hipMemcpyAsync(s.h_md, at<char>(m, s, B_MD), out->md_bytes, hipMemcpyDeviceToHost, s.stream));
+    if (m->secondary) {                  // rule 16c: the array parallel to the records
+        s.n_records = out->n_records;
+        HIP_TRY(hipMemcpyAsync(s.h_sec, at<char>(m, s, B_SEC_RECORDS), sizeof(aim_map_sec_t) * (size_t)out->n_records, hipMemcpyDeviceToHost, s.stream));
+    }
     if (m->paired) {                     // rule 14c: the second range of either buffer, the mate fields and the pairs
         aim_mapper_pairs_out_t &po = s.po;
         po.n_pairs = s.n_reads / 2u; po.n_records = out->n_records;
@@ -712,6 +747,7 @@ int set_pairing(const char *fn, aim_mapper *m, const aim_map_pair_params_t *pp, 
     if (const int rc = check_pairing(fn, m->p, pp)) return rc;
     if (estimate)
         if (const int rc = check_pair_est_params(fn, ep)) return rc;
+    if (m->secondary) return fail(AIM_EINVAL, "%s: the mapper aligns secondaries (aim_mapper_set_secondary): pairing together with them is not in this version", fn);
     if (m->paired) return fail(AIM_ESTATE, "%s: pairing is already set", fn);
     for (uint32_t i = 0; i < m->p.slots; ++i)
         if (m->slot[i].in_flight) return fail(AIM_ESTATE, "%s: slot %u is in flight (aim_mapper_wait first)", fn, i);
@@ -811,6 +847,81 @@ int aim_mapper_pairs(aim_mapper_t *m, uint32_t slot, aim_mapper_pairs_out_t *out
     const MapperSlot &s = m->slot[slot];
     if (s.in_flight || !s.waited) return fail(AIM_ESTATE, "%s: slot %u has no batch waited for (aim_mapper_wait first)", fn, slot);
     *out = s.po;
+    return AIM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// aligned secondaries (AIM_FEATURE_SECONDARY; rule 16c in aim_hip.h, the kernels in secondary.hpp, the stateless entry points in
+// capi_secondary.hip)
+// ---------------------------------------------------------------------------
+int aim_mapper_secondary_device_bytes(const aim_mapper_params_t *params, const aim_map_sec_params_t *sp, uint64_t *bytes)
+{
+    const char *fn = "aim_mapper_secondary_device_bytes";
+    if (const int rc = check_mapper_params(fn, params, 0)) return rc;
+    if (const int rc = check_secondary(fn, sp)) return rc;
+    if (!bytes) return fail(AIM_EINVAL, "%s: bytes is NULL", fn);
+    // (the difference does not depend on the alignment's scratch, nor on the kind of mapper)
+    *bytes = (uint64_t)params->slots * (slot_layout(*params, 0, false, nullptr, 0, nullptr, true).total - slot_layout(*params, 0, false).total);
+    return AIM_OK;
+}
+
+int aim_mapper_set_secondary(aim_mapper_t *m, const aim_map_sec_params_t *sp)
+{
+    const char *fn = "aim_mapper_set_secondary";
+    if (const int rc = check_secondary(fn, sp)) return rc;
+    if (!m) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
+    if (m->secondary) return fail(AIM_EINVAL, "%s: secondaries are already set", fn);
+    for (uint32_t i = 0; i < m->p.slots; ++i)
+        if (m->slot[i].in_flight) return fail(AIM_EINVAL, "%s: slot %u is in flight (aim_mapper_wait first)", fn, i);
+    if (m->paired) return fail(AIM_EINVAL, "%s: the mapper is paired (aim_mapper_set_pairing): pairing together with secondaries is not in this version", fn);
+    HIP_TRY(hipSetDevice(m->device));
+    const aim_mapper_params_t &p = m->p;
+    const SlotLayout L = slot_layout(p, m->align_scratch, !m->starts.empty(), nullptr, 0, nullptr, true);
+    // As in aim_mapper_set_pairing: each slot moves to buffers of the new layout, the new buffers come first, a failure leaves the mapper as it was.
+    char *dev[AIM_MAPPER_MAX_SLOTS] = {};
+    aim_map_sec_t *host[AIM_MAPPER_MAX_SLOTS] = {};
+    auto make = [&]() -> int {
+        for (uint32_t i = 0; i < p.slots; ++i) {
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dev[i]), (size_t)L.total));
+            HIP_TRY(hipMemset(dev[i], 0, (size_t)L.total));
+            if (const int r = pinned(&host[i], sizeof(aim_map_sec_t) * (uint64_t)p.max_reads * (uint64_t)p.seed.max_cands)) return r;
+        }
+        HIP_TRY(hipDeviceSynchronize());
+        return AIM_OK;
+    };
+    if (const int rc = make()) {
+        const std::string was = aim_last_error();
+        for (uint32_t i = 0; i < p.slots; ++i) {
+            if (dev[i]) (void)hipFree(dev[i]);
+            if (host[i]) (void)hipHostFree(host[i]);
+        }
+        return fail(rc, "%s: %s", fn, was.c_str());
+    }
+    for (uint32_t i = 0; i < p.slots; ++i) {
+        MapperSlot &s = m->slot[i];
+        (void)hipFree(s.dev);
+        s.dev = dev[i];
+        s.h_sec = host[i];
+        s.waited = false;
+    }
+    m->L = L;
+    m->sc = *sp;
+    m->secondary = true;
+    return AIM_OK;
+}
+
+int aim_mapper_secondary(aim_mapper_t *m, uint32_t slot, aim_mapper_secondary_out_t *out)
+{
+    const char *fn = "aim_mapper_secondary";
+    if (!m) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
+    if (slot >= m->p.slots) return fail(AIM_EINVAL, "%s: slot %u is outside 0..%u", fn, slot, m->p.slots - 1);
+    if (!out) return fail(AIM_EINVAL, "%s: out is NULL", fn);
+    if (!m->secondary) return fail(AIM_ESTATE, "%s: aim_mapper_set_secondary was not called", fn);
+    const MapperSlot &s = m->slot[slot];
+    if (s.in_flight || !s.waited) return fail(AIM_ESTATE, "%s: slot %u has no batch waited for (aim_mapper_wait first)", fn, slot);
+    out->n_records = s.n_records;
+    out->pad = 0;
+    out->sec = s.h_sec;
     return AIM_OK;
 }
 

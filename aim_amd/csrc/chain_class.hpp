@@ -51,6 +51,18 @@ struct ReadMapqArgs {
 // Lanes per read: the smallest of 4, 8, 16 that holds K candidates.
 constexpr uint32_t chain_class_lanes(uint32_t K) { return K <= 4 ? 4u : K <= 8 ? 8u : 16u; }
 
+// min(60, num / den) for den >= 1 without a 64-bit division: below 60 the quotient comes from a float estimate, which is off by one at
+// the most (num < 2^38, den < 2^32; 24 bits of mantissa against a quotient below 2^6), and two exact products put it right.
+__device__ __forceinline__ uint32_t quot60(uint64_t num, uint64_t den)
+{
+    if (num >= 60u * den) return 60u;
+    uint32_t q = min((uint32_t)((float)num / (float)den), 59u);
+    while ((uint64_t)q * den > num) --q;
+    while ((uint64_t)(q + 1u) * den <= num) ++q;
+    return q;
+}
+// (above the unit guard: secondary.hpp's rule 16c takes the same quotient)
+
 #ifdef AIM_TU_CHAIN_CLASS   // the kernels live in tu_chain_class.hip alone; capi_pipeline.hip sees the arguments and the launchers
 
 // Both 8-byte rows as the two dwords they are stored as: one dwordx2 store per row instead of a dword and four bytes.
@@ -62,17 +74,6 @@ static_assert(sizeof(aim_chain_class_t) == 8 && sizeof(aim_read_mapq_t) == 8 && 
 __device__ __forceinline__ uint32_t class_parent(const ClassWords &c) { return c.w1 & 0xffu; }
 __device__ __forceinline__ uint32_t class_flags(const ClassWords &c) { return (c.w1 >> 8) & 0xffu; }
 __device__ __forceinline__ uint32_t class_mapq(const ClassWords &c) { return (c.w1 >> 16) & 0xffu; }
-
-// min(60, num / den) for den >= 1 without a 64-bit division: below 60 the quotient comes from a float estimate, which is off by one at
-// the most (num < 2^38, den < 2^32; 24 bits of mantissa against a quotient below 2^6), and two exact products put it right.
-__device__ __forceinline__ uint32_t quot60(uint64_t num, uint64_t den)
-{
-    if (num >= 60u * den) return 60u;
-    uint32_t q = min((uint32_t)((float)num / (float)den), 59u);
-    while ((uint64_t)q * den > num) --q;
-    while ((uint64_t)(q + 1u) * den <= num) ++q;
-    return q;
-}
 
 // G: lanes per read, 4, 8 or 16 and at least K (workgroup-uniform, like every loop bound below: every lane takes every shuffle).
 __global__ __launch_bounds__(kChainClassThreads) void chain_class_kernel(ChainClassArgs a, uint32_t G)

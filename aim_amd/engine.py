@@ -833,6 +833,43 @@ def mapper_pairing_device_bytes(mp, pp):
     return b.value
 
 
+def secondary_params(max_sec=capi.SEC_MAX, records=True):
+    """aim_map_sec_params_t (rule 16c): how many secondaries of a locus are aligned next to its primary (1..capi.SEC_MAX, in candidate
+    order), and whether the mapped members that lost come back as SAM secondary records (0x100) behind the read's locus records."""
+    return capi.MapSecParams(int(max_sec), capi.SEC_RECORDS if records else 0)
+
+
+def secondary_rows_device(K, read_size, flank, ref_len, n_reads, d_read_len, d_reads, d_requests, d_text_pos, d_seed, d_chains, d_class, d_seg_requests,
+                          d_seg_text_pos, d_seg_patterns, d_seg, max_sec, stream=None):
+    """aim_secondary_rows_device on device pointers (integers, e.g. torch's data_ptr(); None = NULL): rule 16c part 1 over the four outputs
+    of split_segments_device / extend_segments_device, in place -- a secondary whose parent has a segment gets a row over the parent's
+    read interval; every other slot keeps every byte. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_secondary_rows_device(int(K), int(read_size), int(flank), int(ref_len), int(n_reads), d_read_len, d_reads, d_requests, d_text_pos,
+                                                     d_seed, d_chains, d_class, d_seg_requests, d_seg_text_pos, d_seg_patterns, d_seg, int(max_sec), stream))
+
+
+def secondary_select_device(K, n_reads, d_seg, d_sam, d_class, d_chains, max_score, score_unit, d_sec, stream=None):
+    """aim_secondary_select_device: rule 16c part 2 behind sam_device_split -- one capi.SEC_SLOT_DTYPE per slot in d_sec: the winner of
+    each locus by alignment score, its MAPQ from the runner-up, and who becomes a secondary record. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_secondary_select_device(int(K), int(n_reads), d_seg, d_sam, d_class, d_chains, int(max_score), int(score_unit), d_sec, stream))
+
+
+def map_records_secondary_device(K, n_reads, options, d_seg, d_sam, d_class, d_sec, d_rec_offsets, d_records, d_sec_records, d_scratch, scratch_bytes,
+                                 d_contig=None, n_contigs=0, d_contig_start=None, stream=None):
+    """aim_map_records_secondary_device: rule 16c part 3 -- map_records_device over loci, keyed on d_sec: d_rec_offsets, the dense
+    aim_map_record_t list and one capi.MAP_SEC_DTYPE per record in d_sec_records (room for n_reads * K each). options: capi.SEC_RECORDS.
+    d_contig (with the contig table) for a reference of several sequences. Only enqueues work on `stream`."""
+    capi.check(capi.load().aim_map_records_secondary_device(int(K), int(n_reads), int(options), d_seg, d_sam, d_class, d_sec, d_contig, int(n_contigs), d_contig_start,
+                                                            d_rec_offsets, d_records, d_sec_records, d_scratch, int(scratch_bytes), stream))
+
+
+def mapper_secondary_device_bytes(mp, sc):
+    """aim_mapper_secondary_device_bytes: the device memory Mapper.set_secondary adds, over all slots."""
+    b = C.c_uint64()
+    capi.check(capi.load().aim_mapper_secondary_device_bytes(C.byref(mp), C.byref(sc), C.byref(b)))
+    return b.value
+
+
 def mapper_params(sp, max_reads, max_score, mismatch=3, gap_o=4, gap_e=1, match=0, max_hits=0, mask_q8=capi.CHAIN_MASK_DEFAULT, extend=None, sam_options=0,
                   slots=2, cigar_cap=None, md_cap=None):
     """aim_mapper_params_t from the seed parameters of seed_params(..., w=...) (K is sp.max_cands, read_size sp.read_size), the batch
@@ -874,6 +911,7 @@ class Mapper:
     and "rescue_md" are the rescue ranges alone, as views of their own."""
     pairing = None
     estimate = None
+    secondaries = None
 
     def __init__(self, mp, reference, device=0):
         self.lib = capi.load()
@@ -924,6 +962,19 @@ class Mapper:
         self.pairing = pp
         self.estimate = estimate
 
+    def set_secondary(self, sc=None):
+        """aim_mapper_set_secondary (rule 16c): once, while no slot is in flight. sc: secondary_params() (None = its defaults). wait's dict
+        then has "sec" (capi.MAP_SEC_DTYPE per record), what secondary(slot) returns; records may carry capi.SAM_SECONDARY."""
+        sc = secondary_params() if sc is None else sc
+        capi.check(self.lib.aim_mapper_set_secondary(self.handle, C.byref(sc)))
+        self.secondaries = sc
+
+    def secondary(self, slot):
+        """aim_mapper_secondary after wait(slot): a view of the capi.MAP_SEC_DTYPE array parallel to "records"."""
+        so = capi.MapperSecondaryOut()
+        capi.check(self.lib.aim_mapper_secondary(self.handle, int(slot), C.byref(so)))
+        return _view(so.sec, so.n_records, capi.MAP_SEC_DTYPE)
+
     def pair_estimate(self, slot):
         """aim_mapper_pair_estimate after wait(slot): the estimate of the slot's last batch as a dict -- "min_span", "max_span", "n_samples",
         "n_beyond", "p25", "p50", "p75" and "flags" (capi.PAIR_EST_*)."""
@@ -965,6 +1016,8 @@ class Mapper:
             res["rescue_md"] = res["md"][self.params.md_cap:] if res["rescue_md_bytes"] else np.zeros(0, dtype=np.uint8)
             if self.estimate is not None:
                 res["pair_estimate"] = self.pair_estimate(slot)
+        if self.secondaries is not None:
+            res["sec"] = self.secondary(slot)
         return res
 
 

@@ -145,6 +145,9 @@ def parser():
     ap.add_argument("--gap-o", type=int, default=4)
     ap.add_argument("--gap-e", type=int, default=1)
     ap.add_argument("--max-score", type=int, default=None, help="WFA cost cap of a segment (default: max(32, read_size / 10))")
+    ap.add_argument("--secondary", type=int, default=0, metavar="N",
+                    help="align up to N secondaries of every locus next to its primary (rule 16c, 1..15): the best copy by alignment, MAPQ from the runner-up")
+    ap.add_argument("--no-secondary-lines", action="store_true", help="--secondary: do not write the copies that lost as 0x100 lines")
     ap.add_argument("--eqx", action="store_true", help="'=' and 'X' instead of 'M'")
     ap.add_argument("--cigar-cap", type=int, default=None)
     ap.add_argument("--md-cap", type=int, default=None)
@@ -204,6 +207,15 @@ def main(argv=None):
                                                  rescue_cigar_cap=args.batch * 64, rescue_md_cap=args.batch * 256),
                               estimate=engine.pair_estimate_params(args.est_hist_size, args.est_min_samples, args.est_min_mapq, args.est_min_slack)
                               if args.estimate_span else None)
+            except capi.AimError as e:
+                print("aim_amd.map: %s" % e, file=sys.stderr)
+                return 2
+        if args.secondary:
+            if args.reads2:
+                print("aim_amd.map: --secondary together with --reads2 is not in this version", file=sys.stderr)
+                return 2
+            try:
+                m.set_secondary(engine.secondary_params(args.secondary, records=not args.no_secondary_lines))
             except capi.AimError as e:
                 print("aim_amd.map: %s" % e, file=sys.stderr)
                 return 2

@@ -9,7 +9,12 @@ alignment. MAPQ is the record's own: the chain MAPQ of rule 8c, this project's f
 A result of a mapper with pairing (rule 14c: `out` carries "mates", one aim_map_mate_t per record) gives paired lines: FLAG is the
 record's own, which already holds 0x1 / 0x2 / 0x8 / 0x20 / 0x40 / 0x80; RNEXT is `=` on the record's own contig, PNEXT 1-based and TLEN
 signed, all from the mate fields; an unmapped read whose mate is mapped is written at its mate's RNAME and POS, as the SAM
-specification recommends; with both reads unmapped RNAME / RNEXT are `*` and the positions 0. SA is written as before."""
+specification recommends; with both reads unmapped RNAME / RNEXT are `*` and the positions 0. SA is written as before.
+
+A result of a mapper with secondaries (rule 16c: `out` carries "sec", one aim_map_sec_t per record) marks every mapped line: `tp:A:P`
+on a locus record, `tp:A:S` on a secondary record (FLAG 0x100). A secondary line has SEQ and QUAL `*`, as the SAM specification allows
+for secondary alignments, MAPQ 0 and no SA tag, and the SA tags of the other lines list non-secondary records only. MAPQ of a locus
+record is rule 16c's: from the alignment scores of the locus' copies, capped by the chain's anchors."""
 import numpy as np
 
 from . import capi, engine
@@ -57,6 +62,7 @@ def record_lines(out, names, reads, read_len, rname, quals=None):
     Mapper.from_contigs, whose pad says which contig pos is local to; an SA entry carries its own record's contig."""
     recs, off, cigar, md = out["records"], out["rec_offsets"], out["cigar"], np.asarray(out["md"], dtype=np.uint8)
     mates = out.get("mates") if isinstance(out, dict) else None
+    with_sec = isinstance(out, dict) and out.get("sec") is not None
     contig_name = lambda c: rname if isinstance(rname, str) else rname[int(c)]
     lines = []
     for r in range(len(off) - 1):
@@ -65,7 +71,7 @@ def record_lines(out, names, reads, read_len, rname, quals=None):
         seq = bytes(reads[r][:L]) if isinstance(reads[r], (bytes, bytearray)) else np.asarray(reads[r], dtype=np.uint8)[:L].tobytes()
         qual = quals[r] if quals is not None and quals[r] is not None else None
         # in an SA tag the non-supplementary line comes first, then the others in rank order
-        sa_order = sorted(range(len(group)), key=lambda j: (bool(int(group[j]["sam"]["flags"]) & capi.SAM_SUPPLEMENTARY), int(group[j]["rank"])))
+        sa_order = sorted((j for j in range(len(group)) if not int(group[j]["sam"]["flags"]) & capi.SAM_SECONDARY), key=lambda j: (bool(int(group[j]["sam"]["flags"]) & capi.SAM_SUPPLEMENTARY), int(group[j]["rank"])))
         for j, rec in enumerate(group):
             s = rec["sam"]
             flags = int(s["flags"])
@@ -81,13 +87,17 @@ def record_lines(out, names, reads, read_len, rname, quals=None):
                 lines.append("\t".join([names[r], str(flags) if mates is not None else "4"] + place + ["0", "*", rnext, pnext, "0", seq.decode("latin-1") or "*", qual or "*"]))
                 continue
             rev = bool(flags & capi.SAM_REVERSE)
+            secondary = bool(flags & capi.SAM_SECONDARY)   # rule 16c: another copy of a locus -- no bases, no qualities, no SA
             fields = [names[r], str(flags), _rname(rname, rec), str(int(s["pos"]) + 1), str(int(rec["mapq"])), _cigar(rec, cigar), rnext, pnext, tlen,
-                      (revcomp(seq) if rev else seq).decode("latin-1") or "*", (qual[::-1] if rev else qual) if qual else "*", "NM:i:%d" % int(s["nm"])]
+                      "*" if secondary else (revcomp(seq) if rev else seq).decode("latin-1") or "*",
+                      "*" if secondary or not qual else (qual[::-1] if rev else qual), "NM:i:%d" % int(s["nm"])]
             if int(s["md_len"]) and not int(s["status"]) & capi.SAM_OVERFLOW:
                 o = int(s["md_offset"])
                 fields.append("MD:Z:" + md[o:o + int(s["md_len"])].tobytes().decode("latin-1"))
             fields.append("AS:i:%d" % -int(s["score"]))
-            if len(group) > 1:
+            if with_sec or secondary:
+                fields.append("tp:A:S" if secondary else "tp:A:P")
+            if len(sa_order) > 1 and not secondary:
                 fields.append("SA:Z:" + "".join(_sa(rname, group[k], cigar) for k in sa_order if k != j))
             lines.append("\t".join(fields))
     return lines

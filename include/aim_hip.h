@@ -1142,7 +1142,7 @@ const char *aim_extend_kernel_names(void);
  * Not in this version: a mapper stage inside aim_set_submit or host.c, more than one device per mapper
  * (references of more than one sequence: rule 13c and aim_mapper_create_contigs below; paired-end reads: rule 14c and
  * aim_mapper_set_pairing below), hard clips, trimming the overlap of neighbouring segments, packed
- * read rows, MAPQ from alignment runner-ups. The SA tag is text and is written on the host (aim_amd/samout.py) from the records of a
+ * read rows (MAPQ from alignment runner-ups and secondary records: rule 16c and aim_mapper_set_secondary below). The SA tag is text and is written on the host (aim_amd/samout.py) from the records of a
  * read. Check aim_features() & AIM_FEATURE_MAPPER first. */
 typedef struct aim_map_record {
     aim_sam_t sam;                 /* the slot's row; flags with rule 12c's supplementary bit */
@@ -1477,6 +1477,140 @@ int aim_pair_select_device_est(const aim_map_pair_params_t *pp, uint32_t K, uint
 const char *aim_pair_estimate_kernel_names(void);
 int aim_mapper_set_pairing_estimated(aim_mapper_t *mapper, const aim_map_pair_params_t *pp, const aim_pair_est_params_t *ep);
 int aim_mapper_pair_estimate(aim_mapper_t *mapper, uint32_t slot, aim_pair_estimate_t *out);
+
+/* ---- aligned secondaries (AIM_FEATURE_SECONDARY): the best copy of a repeat by alignment, MAPQ from the runner-up, 0x100 records ----
+ * Rules 8c, 10c and 12c decide from the chains alone which copy of a repeat a read belongs to: the primary of a locus is the chain of
+ * highest score (the lowest position among equals), only primaries get a row, and the record carries the chain MAPQ. A read from a
+ * diverged repeat whose chains tie therefore comes back on whichever copy lies first, with MAPQ 0. Rule 16c aligns the secondaries of
+ * a locus over the same read interval as their primary, lets the alignment scores choose the locus' one record, derives its MAPQ from
+ * the runner-up, and can report the other copies as SAM secondary records. The sequence is
+ *     chain -> aim_chain_classify_device -> aim_split_segments_device -> [aim_extend_segments_device] -> aim_secondary_rows_device ->
+ *     [aim_contig_clip_device] -> aim_align_device_ref -> aim_sam_device_split -> aim_secondary_select_device ->
+ *     aim_map_records_secondary_device.
+ * All n_reads * K slot rows go through the alignment anyway, so there is no new alignment launch and no new row buffer: a secondary's
+ * row takes the place of rule 7's empty slot. Arithmetic is signed 64-bit unless stated; every byte is deterministic and independent of
+ * the grid and of the AIM_DEBUG_POISON_* knobs. A mapper that does not switch the rule on gives the bytes it always gave.
+ *   16c, part 1: rows for secondaries (aim_secondary_rows_device). Works in place on the four segment buffers, behind
+ *       aim_split_segments_device and, where it runs, aim_extend_segments_device. For read r: n = min(d_seed[r].n_cands, K), L =
+ *       d_read_len[r] clamped to 0..read_size. Candidate i < n is a secondary when d_class[slot].flags & (AIM_CHAIN_PRIMARY |
+ *       AIM_CHAIN_SECONDARY) is AIM_CHAIN_SECONDARY alone, its parent is j = d_class[slot].parent (rule 8c), and t is its index among
+ *       the secondaries of the read with the same parent, in candidate order. It gets a row when all of these hold: t < max_sec;
+ *       j < n and candidate j carries AIM_CHAIN_PRIMARY alone of the two flags; d_seg[r * K + j] has AIM_SEG_VALID and is well-formed
+ *       (q_begin <= q_end <= L); rule 10c's p_lo of candidate i is recoverable -- the same recovery, from the candidate's own
+ *       d_requests / d_text_pos / d_chains. Every other slot keeps every byte of the four buffers.
+ *       Interval. [qa, qb) = the parent segment's (q_begin, q_end) as they stand: an extension has already acted.
+ *       Window. The interval projected along the secondary chain's end diagonals, the flank on both sides. With c = d_chains[slot],
+ *       s = d_text_pos[slot] >> 63, p_hi = p_lo + c.ref_span and [u, v) = s ? [L - qb, L - qa) : [qa, qb):
+ *       lo = p_lo + (u - c.q_lo) - flank, hi = p_hi + (v - c.q_hi) + flank, seg_start = min(max(lo, 0), ref_len),
+ *       seg_end = max(seg_start, min(max(hi, 0), ref_len)), text_len = min(seg_end - seg_start, read_size).
+ *       Outputs. d_seg_requests[slot] = {qb - qa, text_len, 0, d_requests[slot].idx}; d_seg_text_pos[slot] = seg_start | s << 63; the
+ *       pattern row is read[qa, qb) as given, then zero bytes up to read_size; d_seg[slot] = {qa, qb, L, the parent's flags &
+ *       (AIM_SEG_VALID | AIM_SEG_SUPPLEMENTARY | AIM_SEG_LEFT_OPEN | AIM_SEG_RIGHT_OPEN), cand = i}. A secondary segment needs no flag
+ *       of its own: it is a VALID slot whose d_class entry says SECONDARY.
+ *       Identity. Where the parent's interval is the whole read ([0, L): one primary, no extension) the row's request and text_pos
+ *       equal the chain kernel's own slot byte for byte: lo and hi above are rule 6c's.
+ *   16c, part 2: one winner per locus (aim_secondary_select_device), behind aim_sam_device_split. Slot r * K + i is valid when
+ *       d_seg[slot].flags has AIM_SEG_VALID, mapped as in rule 12c, and OK when d_sam[slot].status without AIM_SAM_OVERFLOW is
+ *       AIM_PAIR_OK. Primary and secondary are read from d_class as in part 1 (an empty slot is neither).
+ *       Family of primary j: j itself and the valid secondaries whose parent is j. n_members is their number.
+ *       Counted score. e_i = d_sam[slot].score for a mapped slot and max_score + 1 otherwise: a WFA row over the cap counts with
+ *       MAX_SCORE + 1, a lower bound of its cost, as in rule 9c.
+ *       Winner. The mapped member of lowest (score, i); b is its score. A family without a mapped member has no winner, and all its
+ *       slots get 8 zero bytes.
+ *       Runner-up. s2 = the lowest e among the other members that are valid and OK; INT32_MAX when there is none.
+ *       n_tied = 1 + the number of those members with e == b.
+ *       aln_mapq: rule 9c's formula -- 0 when n_tied > 1, 60 without a runner-up, otherwise min(60, 6 * max(s2 - b, 0) / score_unit).
+ *       anchor_cap = 6 * min(the winner's d_chains n_anchors, 10), and 0 where that chain's score is 0 (rule 8c's f1 = 0).
+ *       complete: n_members - 1 == d_class[r * K + j].n_sub -- every secondary the classification counted got a row.
+ *       mapq = min(aln_mapq, anchor_cap) when complete, min(aln_mapq, anchor_cap, d_class[r * K + j].mapq) otherwise. A primary
+ *       without secondaries thereby keeps exactly the byte rule 12c gives it: 6 * m with f2 = 0.
+ *       aim_sec_slot_t of a family with a winner: role = 1 (the locus record) in the winner's slot, 2 (a secondary record) in the slot
+ *       of every other mapped member; family = j; mapq in the winner's slot and 0 in the others; aln_mapq and n_tied; flags =
+ *       AIM_SEC_SWAPPED (the winner is not j) | AIM_SEC_COMPLETE | (n_members - 1) << 4; gap = min(max(s2 - b, 0), 65534), or 65535
+ *       without a runner-up: the second score relative to b in 16 bits, which saturates far above anything aln_mapq tells apart.
+ *       Every other slot is 8 zero bytes.
+ *   16c, part 3: records (aim_map_records_secondary_device). Rule 12c over loci instead of slots.
+ *       Locus records. A family with a winner contributes the winner's row. The locus records of a read are sorted by (q_begin of the
+ *       winner's segment, j); rank is the position in that order. The family of lowest j that has a winner is the line without
+ *       AIM_SAM_SUPPLEMENTARY, the others gain it. The record's mapq is part 2's.
+ *       Secondary records, with AIM_SEC_RECORDS in options: every slot of role 2 (a primary that lost among them) follows behind the
+ *       read's locus records, ordered by (the rank of its family's locus record, score, i); such a record carries AIM_SAM_SECONDARY,
+ *       has AIM_SAM_SUPPLEMENTARY cleared and mapq 0. Without the option they are dropped.
+ *       c_r is the number of records of read r, or 1 when it has none: that read gets rule 12c's single unmapped record.
+ *       d_rec_offsets (the same three-launch scan), read, q_begin, q_end, seg_flags, n_records and slot are rule 12c's.
+ *       aim_map_sec_t, one per record, parallel to d_records: family_slot = r * K + j; second_score = b + gap saturated at
+ *       INT32_MAX - 1, or INT32_MAX without a runner-up; aln_mapq; chain_mapq = d_class[family_slot].mapq; n_members; n_tied; flags =
+ *       AIM_SEC_SWAPPED | AIM_SEC_COMPLETE as in part 2. The unmapped record's is {r * K, INT32_MAX, zeros}.
+ *       Contigs. With d_contig (NULL: a reference of one sequence) every mapped record gets rule 13c's change -- sam.pos local to
+ *       d_contig[slot], sam.pad the contig -- and the unmapped record sam.pad = AIM_CONTIG_NONE. One record kernel serves both.
+ *   Kernels (csrc/secondary.hpp): secondary_rows_kernel, secondary_select_kernel, map_count_sec_kernel, map_records_sec_kernel. A read
+ *       gets 4, 8 or 16 lanes by K as in chain_class_kernel; no LDS, no scratch memory, no atomics, vector stores only. The calls only
+ *       enqueue work on hip_stream. d_sec is 8-byte aligned, d_sec_records, d_sam and d_records 16-byte.
+ *   AIM_EINVAL with a message under the entry point's name, before any device query: aim_secondary_rows_device refuses what
+ *       aim_split_segments_device refuses and, behind those bounds and before the NULL-buffer check, a max_sec outside 1..AIM_SEC_MAX;
+ *       aim_secondary_select_device a K outside 1..AIM_SEED_MAX_CANDS, n_reads * K >= 2^32, max_score outside 0..INT32_MAX - 1,
+ *       score_unit < 1 and a NULL device buffer with n_reads > 0; aim_map_records_secondary_device what aim_map_records_device
+ *       refuses (d_sec_records aligned like d_records), unknown option bits, and with d_contig an n_contigs outside 1..AIM_CONTIG_MAX
+ *       or a NULL d_contig_start.
+ *   Mapper. aim_mapper_set_secondary(m, params) is called once, while no slot is in flight (like aim_mapper_set_pairing: before the first
+ *       submit, or after every submitted batch was waited for); it allocates d_sec and the per-record array
+ *       in every slot (aim_mapper_secondary_device_bytes says how much over all slots). aim_mapper_submit then runs the three stages
+ *       at the places named above with score_unit = mismatch and the mapper's max_score, aim_mapper_wait copies the extra array, and
+ *       aim_mapper_secondary(m, slot, &out) returns a view of the aim_map_sec_t[n_records] of the last wait on the slot (AIM_ESTATE
+ *       before the first wait, while the slot is in flight and on a mapper without secondaries). Refusals, AIM_EINVAL under the entry
+ *       point's name before any device query, in this order: a NULL params, max_sec outside 1..AIM_SEC_MAX, unknown option bits, a
+ *       NULL mapper, a second call, a slot in flight, a paired mapper -- and likewise the two pairing setters on a mapper with
+ *       secondaries: rule 14c rewrites the slot arrays, and combining the two is a follow-up.
+ * aim_secondary_kernel_names: "secondary_rows_kernel,secondary_select_kernel,map_count_sec_kernel,map_records_sec_kernel".
+ * Not in this version: pairing together with secondaries, secondaries beyond the kept K, a pair MAPQ, AIM_FLAG_TOP_HITS rows, the
+ * voting kernel's clusters, hard clips, trimming overlapping neighbour segments, a stage inside aim_set_submit or host.c. Check
+ * aim_features() & AIM_FEATURE_SECONDARY first. */
+#define AIM_FEATURE_SECONDARY 0x800000u /* rule 16c: aim_secondary_rows_device / aim_secondary_select_device / aim_map_records_secondary_device / aim_mapper_set_secondary / aim_mapper_secondary exist */
+#define AIM_SEC_MAX 15u                 /* max_sec is 1..AIM_SEC_MAX */
+#define AIM_SEC_RECORDS 0x1u            /* options: the other mapped members of a locus as AIM_SAM_SECONDARY records */
+#define AIM_SAM_SECONDARY 0x100u        /* aim_sam_t.flags, from aim_map_records_secondary_device alone */
+#define AIM_SEC_SWAPPED 0x1u            /* aim_sec_slot_t.flags / aim_map_sec_t.flags: the winner is not the chain's primary */
+#define AIM_SEC_COMPLETE 0x2u           /* ... every secondary rule 8c counted under the primary was aligned */
+#define AIM_SEC_MEMBERS(flags) ((((uint32_t)(flags)) >> 4) + 1u) /* n_members from aim_sec_slot_t.flags */
+typedef struct aim_sec_slot {
+    uint8_t role;                  /* 0: none, 1: the locus record, 2: a secondary record */
+    uint8_t family;                /* j */
+    uint8_t mapq, aln_mapq, n_tied;
+    uint8_t flags;                 /* AIM_SEC_SWAPPED | AIM_SEC_COMPLETE | (n_members - 1) << 4 */
+    uint16_t gap;                  /* min(max(s2 - b, 0), 65534); 65535: no runner-up */
+} aim_sec_slot_t;      /* 8 B per slot */
+typedef struct aim_map_sec {
+    uint32_t family_slot;          /* r * K + j */
+    int32_t second_score;          /* INT32_MAX: none */
+    uint8_t aln_mapq, chain_mapq, n_members, n_tied;
+    uint32_t flags;                /* AIM_SEC_SWAPPED | AIM_SEC_COMPLETE */
+} aim_map_sec_t;       /* 16 B per record */
+typedef struct aim_map_sec_params {
+    uint32_t max_sec;              /* 1..AIM_SEC_MAX */
+    uint32_t options;              /* AIM_SEC_RECORDS */
+} aim_map_sec_params_t;
+typedef struct aim_mapper_secondary_out {
+    uint32_t n_records, pad;
+    const aim_map_sec_t *sec;      /* [n_records], parallel to aim_mapper_out_t.records */
+} aim_mapper_secondary_out_t;
+int aim_secondary_rows_device(uint32_t K, uint32_t read_size, int32_t flank, uint64_t ref_len, uint32_t n_reads, const int32_t *d_read_len,
+                              const char *d_reads, const void *d_requests /* aim_request_t[n_reads * K] */, const uint64_t *d_text_pos,
+                              const aim_seed_t *d_seed, const aim_chain_t *d_chains, const aim_chain_class_t *d_class,
+                              void *d_seg_requests /* in/out */, uint64_t *d_seg_text_pos /* in/out */, char *d_seg_patterns /* in/out */,
+                              aim_segment_t *d_seg /* in/out */, uint32_t max_sec, void *hip_stream);
+int aim_secondary_select_device(uint32_t K, uint32_t n_reads, const aim_segment_t *d_seg, const aim_sam_t *d_sam, const aim_chain_class_t *d_class,
+                                const aim_chain_t *d_chains, int32_t max_score, int32_t score_unit, aim_sec_slot_t *d_sec /* [n_reads * K] */,
+                                void *hip_stream);
+int aim_map_records_secondary_device(uint32_t K, uint32_t n_reads, uint32_t options, const aim_segment_t *d_seg, const aim_sam_t *d_sam,
+                                     const aim_chain_class_t *d_class, const aim_sec_slot_t *d_sec, const uint32_t *d_contig_or_null,
+                                     uint32_t n_contigs, const uint32_t *d_contig_start_or_null, uint32_t *d_rec_offsets /* [n_reads + 1] */,
+                                     aim_map_record_t *d_records /* [n_reads * K] */, aim_map_sec_t *d_sec_records /* [n_reads * K] */,
+                                     void *d_scratch, size_t scratch_bytes, void *hip_stream);
+/* Comma-separated rocprofv3 kernel-trace name prefixes of the four kernels rule 16c adds. */
+const char *aim_secondary_kernel_names(void);
+int aim_mapper_secondary_device_bytes(const aim_mapper_params_t *params, const aim_map_sec_params_t *sp, uint64_t *bytes);
+int aim_mapper_set_secondary(aim_mapper_t *mapper, const aim_map_sec_params_t *sp);
+int aim_mapper_secondary(aim_mapper_t *mapper, uint32_t slot, aim_mapper_secondary_out_t *out);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
