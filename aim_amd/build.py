@@ -8,7 +8,7 @@
 
 The library is several translation units -- the C-ABI in aim_capi.hip (device sets, slots, submit and wait), capi_launch.hip (a plan
 into kernel launches, the stateless alignment entry points), capi_groups.hip (the read-groups path: READ_GROUPS, MATE_PAIRS, TOP_HITS),
-capi_plan.hip (the launch planner), capi_pipeline.hip (index, seeding, classes, split, extension), capi_mapper.hip (the record list and the mapper object), capi_pair.hip (paired-end reads: the entry points of rules 14c and 15c), capi_secondary.hip (aligned secondaries: the entry points of rule 16c) and capi_host.hip (host-side helpers), all
+capi_plan.hip (the launch planner), capi_pipeline.hip (index, seeding, classes, split, extension), capi_mapper.hip (the record list and the mapper object), capi_pair.hip (paired-end reads: the entry points of rules 14c and 15c), capi_secondary.hip (aligned secondaries: the entry points of rule 16c), capi_pair_secondary.hip (pairing over them: the entry points of rule 17c) and capi_host.hip (host-side helpers), all
 of them host code only, and one tu_*.hip per kernel family, each of which instantiates the kernels of ONE header (tu_groups.hip: of
 groups.hpp, hits.hpp and mates.hpp) -- compiled in parallel (MAX_JOBS at a time when it is set) into build/obj/ and linked
 once: a full rebuild takes as long as the slowest family instead of the sum, and editing one kernel header recompiles only

@@ -76,6 +76,7 @@ SEC_MAX = 15                      # max_sec is 1..SEC_MAX
 SEC_RECORDS = 0x1                 # aim_map_sec_params_t.options: the other mapped members of a locus as SAM_SECONDARY records
 SAM_SECONDARY = 0x100             # aim_sam_t.flags, from aim_map_records_secondary_device
 SEC_SWAPPED, SEC_COMPLETE = 0x1, 0x2   # aim_sec_slot_t.flags / aim_map_sec_t.flags; aim_sec_slot_t.flags >> 4 is n_members - 1
+FEATURE_PAIR_SECONDARY = 0x1000000  # aim_features(): aim_pair_rescue_rows_secondary_device / aim_pair_select_secondary_device / aim_map_mates_secondary_device exist (rule 17c)
 
 
 def CONTIG_SPACER(band):
@@ -252,6 +253,8 @@ SEC_SLOT_DTYPE = np.dtype([("role", "u1"), ("family", "u1"), ("mapq", "u1"), ("a
 MAP_SEC_DTYPE = np.dtype([("family_slot", "<u4"), ("second_score", "<i4"), ("aln_mapq", "u1"), ("chain_mapq", "u1"), ("n_members", "u1"), ("n_tied", "u1"),
                           ("flags", "<u4")])   # aim_map_sec_t
 assert C.sizeof(MapSecParams) == 8 and C.sizeof(MapperSecondaryOut) == 16 and SEC_SLOT_DTYPE.itemsize == 8 and MAP_SEC_DTYPE.itemsize == 16
+MAP_PAIR_MAPQ_DTYPE = np.dtype([("alt_sum", "<i4", (2,)), ("mapq", "u1", (2,)), ("pair_mapq", "u1", (2,)), ("own_mapq", "u1", (2,)), ("tied", "u1", (2,))])   # aim_map_pair_mapq_t
+assert MAP_PAIR_MAPQ_DTYPE.itemsize == 16
 
 
 class BatchIO(C.Structure):
@@ -402,6 +405,14 @@ SYMBOLS = {
     "aim_mapper_secondary_device_bytes": (C.c_int, [C.POINTER(MapperParams), C.POINTER(MapSecParams), C.POINTER(C.c_uint64)]),
     "aim_mapper_set_secondary": (C.c_int, [_VP, C.POINTER(MapSecParams)]),
     "aim_mapper_secondary": (C.c_int, [_VP, _U32, C.POINTER(MapperSecondaryOut)]),
+    "aim_pair_rescue_rows_secondary_device": (C.c_int, [C.POINTER(MapPairParams), _U32, _U32, C.c_uint64, _U32, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                                        _VP]),
+    "aim_pair_select_secondary_device": (C.c_int, [C.POINTER(MapPairParams), _U32, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _U32, _U32, _VP, _VP, _VP, _VP]),
+    "aim_map_mates_secondary_device": (C.c_int, [_U32, _U32, _VP, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP]),
+    "aim_pair_secondary_kernel_names": (C.c_char_p, []),
+    "aim_mapper_pairing_secondary_device_bytes": (C.c_int, [C.POINTER(MapperParams), C.POINTER(MapPairParams), C.POINTER(MapSecParams), C.POINTER(C.c_uint64)]),
+    "aim_mapper_set_pairing_secondary": (C.c_int, [_VP, C.POINTER(MapPairParams), C.POINTER(PairEstParams), C.POINTER(MapSecParams)]),
+    "aim_mapper_pair_mapq": (C.c_int, [_VP, _U32, C.POINTER(_VP)]),
 }
 
 _lib = None

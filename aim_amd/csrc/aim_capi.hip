@@ -514,7 +514,7 @@ uint32_t aim_features(void)
     return AIM_FEATURE_ENDSFREE | AIM_FEATURE_AFFINE2P | AIM_FEATURE_LINEAR | AIM_FEATURE_WFA_W32 | AIM_FEATURE_WFA_BIDIR | AIM_FEATURE_REF_TEXTS |
            AIM_FEATURE_READ_GROUPS | AIM_FEATURE_WFA_ESCALATE | AIM_FEATURE_MATE_PAIRS | AIM_FEATURE_SAM_FIELDS | AIM_FEATURE_TOP_HITS | AIM_FEATURE_SEED |
            AIM_FEATURE_INDEX_DEVICE | AIM_FEATURE_MINIMIZERS | AIM_FEATURE_SEED_CHAIN | AIM_FEATURE_SEED_CHAIN_LONG | AIM_FEATURE_CHAIN_CLASS | AIM_FEATURE_SPLIT | AIM_FEATURE_EXTEND |
-           AIM_FEATURE_MAPPER | AIM_FEATURE_CONTIGS | AIM_FEATURE_PAIRED | AIM_FEATURE_PAIR_ESTIMATE | AIM_FEATURE_SECONDARY;
+           AIM_FEATURE_MAPPER | AIM_FEATURE_CONTIGS | AIM_FEATURE_PAIRED | AIM_FEATURE_PAIR_ESTIMATE | AIM_FEATURE_SECONDARY | AIM_FEATURE_PAIR_SECONDARY;
 }
 const char *aim_last_error(void) { return g_err; }
 

@@ -2,7 +2,7 @@
 // launches, and the stateless alignment entry points), capi_groups.hip (the read-groups path: AIM_FLAG_READ_GROUPS, MATE_PAIRS and
 // TOP_HITS) -- these three share the device set and launch() through capi_set.hpp --,
 // capi_plan.hip (the launch planner; its types and entry points are in plan.hpp), capi_pipeline.hip (index, seeding, classes and MAPQ,
-// split, extension), capi_mapper.hip (the record list and aim_mapper_t), capi_pair.hip (rule 14c's stateless entry points), capi_secondary.hip (rule 16c's) and capi_host.hip (host-side formatters and
+// split, extension), capi_mapper.hip (the record list and aim_mapper_t), capi_pair.hip (rule 14c's stateless entry points), capi_secondary.hip (rule 16c's), capi_pair_secondary.hip (rule 17c's) and capi_host.hip (host-side formatters and
 // generators). None of
 // them compiles a kernel: each kernel family's tu_*.hip does, and these units call its launchers. Internal, not installed.
 // Every function declared here has ONE definition, next to the state it owns: fail() in aim_capi.hip, where it writes the thread-local
@@ -69,6 +69,17 @@ inline bool ref_len_ok(const char *fn, uint64_t ref_len, bool say_why)
 }
 // (an empty batch may come with NULL buffers)
 inline bool buffers_ok(const char *fn, uint32_t n_reads, bool all_set) { return !n_reads || all_set || refuse("%s: null device buffer", fn); }
+// a buffer against its alignment; the message names it
+inline bool aligned_ok(const char *fn, const void *p, uintptr_t align, const char *name)
+{
+    return !((uintptr_t)p & (align - 1u)) || refuse("%s: %s must be %u-byte aligned", fn, name, (unsigned)align);
+}
+// d_contig comes with a contig table of 1..AIM_CONTIG_MAX entries (rules 14c and 17c)
+inline bool contigs_ok(const char *fn, bool contigs, uint32_t n_contigs, bool tables)
+{
+    return !contigs || (((n_contigs >= 1 && n_contigs <= AIM_CONTIG_MAX) || refuse("%s: n_contigs %u is outside 1..%u", fn, n_contigs, AIM_CONTIG_MAX)) &&
+                        (tables || refuse("%s: d_contig is given without its contig table", fn)));
+}
 // AIM_DEBUG_POISON_LDS as the kernels take it (dbg_poison_lds): 0x100 | byte, or 0 for "leave LDS as it is"
 inline uint32_t poison_lds_word(const aim::Knobs &kn) { return kn.poison_lds >= 0 ? (0x100u | (uint32_t)(kn.poison_lds & 0xff)) : 0u; }
 // The KArgs of a batch-I/O kernel: the params, the pair count and the requests; every other member zero

@@ -146,7 +146,9 @@ enum Buf { B_READS, B_READ_LEN, B_REQ, B_TEXT_POS, B_VOTES, B_SEED, B_CHAINS, B_
            // rule 15c, after aim_mapper_set_pairing_estimated alone: the estimate and its histogram
            B_EST, B_EST_SCRATCH,
            // rule 16c, after aim_mapper_set_secondary alone: aim_sec_slot_t per slot and aim_map_sec_t per record
-           B_SEC, B_SEC_RECORDS, B_COUNT };
+           B_SEC, B_SEC_RECORDS,
+           // rule 17c, after aim_mapper_set_pairing_secondary alone: aim_map_pair_mapq_t per read pair
+           B_PAIR_MAPQ, B_COUNT };
 
 struct SlotLayout {
     uint64_t at[B_COUNT], bytes[B_COUNT], total;
@@ -185,10 +187,11 @@ SlotLayout slot_layout(const aim_mapper_params_t &p, size_t align_scratch, bool 
     if (secondary) {                     // rule 16c
         b[B_SEC] = sizeof(aim_sec_slot_t) * S; b[B_SEC_RECORDS] = sizeof(aim_map_sec_t) * S;
     }
+    if (pp && secondary) b[B_PAIR_MAPQ] = sizeof(aim_map_pair_mapq_t) * ((N + 1) / 2);   // rule 17c
     uint64_t at = 0;
     for (int i = 0; i < B_COUNT; ++i) {
         L.at[i] = at;
-        if (i >= B_CONTIG && !b[i]) continue;   // the buffers of rules 13c to 16c exist only where the rule runs
+        if (i >= B_CONTIG && !b[i]) continue;   // the buffers of rules 13c to 17c exist only where the rule runs
         at += up256(std::max<uint64_t>(b[i], 4));
     }
     L.total = at;
@@ -216,6 +219,7 @@ struct MapperSlot {
     aim_pair_estimate_t *h_est = nullptr;   // rule 15c (aim_mapper_set_pairing_estimated): pinned; the last batch waited for
     aim_map_sec_t *h_sec = nullptr;      // rule 16c (aim_mapper_set_secondary): pinned; the view of aim_mapper_secondary
     uint32_t n_records = 0;              // ... and how many of them the last wait copied
+    aim_map_pair_mapq_t *h_pair_mapq = nullptr;   // rule 17c (aim_mapper_set_pairing_secondary): pinned; the view of aim_mapper_pair_mapq
 };
 
 }  // namespace
@@ -240,6 +244,7 @@ struct aim_mapper {
     aim_pair_est_params_t ep = {};
     bool secondary = false;              // rule 16c: aim_mapper_set_secondary was called
     aim_map_sec_params_t sc = {};
+    bool combined = false;               // rule 17c: paired and secondary through aim_mapper_set_pairing_secondary
 };
 
 namespace {
@@ -253,7 +258,7 @@ void release(aim_mapper *m)
         if (s.stream) (void)hipStreamSynchronize(s.stream);
         if (s.dev) (void)hipFree(s.dev);
         for (void *h : {(void *)s.h_reads, (void *)s.h_read_len, (void *)s.h_records, (void *)s.h_offsets, (void *)s.h_cigar, (void *)s.h_md, (void *)s.h_head,
-                        (void *)s.h_mates, (void *)s.h_pairs, (void *)s.h_res_head, (void *)s.h_est, (void *)s.h_sec})
+                        (void *)s.h_mates, (void *)s.h_pairs, (void *)s.h_res_head, (void *)s.h_est, (void *)s.h_sec, (void *)s.h_pair_mapq})
             if (h) (void)hipHostFree(h);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
@@ -386,6 +391,7 @@ int submit_pairing(aim_mapper *m, MapperSlot &s, uint32_t n_reads, hipStream_t s
     uint32_t *d_contig = n_contigs ? at<uint32_t>(m, s, B_CONTIG) : nullptr, *d_res_cursors = at<uint32_t>(m, s, B_RES_CURSORS);
     aim_chain_class_t *d_cls = at<aim_chain_class_t>(m, s, B_CLASS);
     aim_pair_estimate_t *d_est = m->estimated ? at<aim_pair_estimate_t>(m, s, B_EST) : nullptr;
+    aim_sec_slot_t *d_sec = m->combined ? at<aim_sec_slot_t>(m, s, B_SEC) : nullptr;   // rule 17c
     int rc = AIM_OK;
     if (m->estimated)
         rc = aim_pair_estimate_device(&pp, &m->ep, K, rs, n_reads, d_seg, d_sam, d_cls, d_contig, d_est, at<void>(m, s, B_EST_SCRATCH), (size_t)m->L.bytes[B_EST_SCRATCH], st);
@@ -394,10 +400,13 @@ int submit_pairing(aim_mapper *m, MapperSlot &s, uint32_t n_reads, hipStream_t s
         void *d_req = at<void>(m, s, B_RES_REQ), *d_res = at<void>(m, s, B_RES_RESULTS);
         uint64_t *d_tp = at<uint64_t>(m, s, B_RES_TEXT_POS);
         char *d_pat = at<char>(m, s, B_RES_PATTERNS), *d_ops = at<char>(m, s, B_RES_OPS);
-        rc = m->estimated ? aim_pair_rescue_rows_device_est(&pp, K, rs, m->ref_len, n_contigs, m->d_contig_start, m->d_contig_len, n_reads, d_rl, at<char>(m, s, B_READS),
-                                                            d_seg, d_sam, d_contig, d_req, d_tp, d_pat, d_est, st)
-                          : aim_pair_rescue_rows_device(&pp, K, rs, m->ref_len, n_contigs, m->d_contig_start, m->d_contig_len, n_reads, d_rl, at<char>(m, s, B_READS), d_seg, d_sam,
-                                                        d_contig, d_req, d_tp, d_pat, st);
+        // (rule 17c: the slots d_sec gave a role, anchored at the representative; its d_est may be NULL)
+        rc = m->combined    ? aim_pair_rescue_rows_secondary_device(&pp, K, rs, m->ref_len, n_contigs, m->d_contig_start, m->d_contig_len, n_reads, d_rl,
+                                                                    at<char>(m, s, B_READS), d_seg, d_sam, d_contig, d_sec, d_req, d_tp, d_pat, d_est, st)
+             : m->estimated ? aim_pair_rescue_rows_device_est(&pp, K, rs, m->ref_len, n_contigs, m->d_contig_start, m->d_contig_len, n_reads, d_rl, at<char>(m, s, B_READS),
+                                                              d_seg, d_sam, d_contig, d_req, d_tp, d_pat, d_est, st)
+                            : aim_pair_rescue_rows_device(&pp, K, rs, m->ref_len, n_contigs, m->d_contig_start, m->d_contig_len, n_reads, d_rl, at<char>(m, s, B_READS), d_seg,
+                                                          d_sam, d_contig, d_req, d_tp, d_pat, st);
         if (!rc) rc = aim_align_device_ref(&m->rap.base, n_reads, d_req, d_pat, d_tp, m->d_ref, m->ref_len, d_res, d_ops, at<void>(m, s, B_RES_SCRATCH), m->rescue_scratch, st);
         if (!rc)
             rc = aim_sam_device(&m->rap.base, n_reads, d_req, d_tp, nullptr, d_res, d_ops, m->d_ref, m->ref_len, p.sam_options, d_res_sam,
@@ -405,10 +414,12 @@ int submit_pairing(aim_mapper *m, MapperSlot &s, uint32_t n_reads, hipStream_t s
     } else {
         HIP_TRY(hipMemsetAsync(d_res_cursors, 0, 8, st));
     }
+    aim_map_pair_t *d_pairs = at<aim_map_pair_t>(m, s, B_PAIRS);
     if (!rc)
-        rc = m->estimated ? aim_pair_select_device_est(&pp, K, rs, n_reads, d_rl, d_seg, d_sam, d_cls, d_contig, d_res_sam, p.cigar_cap, p.md_cap,
-                                                       at<aim_map_pair_t>(m, s, B_PAIRS), d_est, st)
-                          : aim_pair_select_device(&pp, K, rs, n_reads, d_rl, d_seg, d_sam, d_cls, d_contig, d_res_sam, p.cigar_cap, p.md_cap, at<aim_map_pair_t>(m, s, B_PAIRS), st);
+        rc = m->combined    ? aim_pair_select_secondary_device(&pp, K, rs, n_reads, d_rl, d_seg, d_sam, d_cls, d_contig, d_sec, at<aim_chain_t>(m, s, B_CHAINS), p.mismatch,
+                                                               d_res_sam, p.cigar_cap, p.md_cap, d_pairs, at<aim_map_pair_mapq_t>(m, s, B_PAIR_MAPQ), d_est, st)
+             : m->estimated ? aim_pair_select_device_est(&pp, K, rs, n_reads, d_rl, d_seg, d_sam, d_cls, d_contig, d_res_sam, p.cigar_cap, p.md_cap, d_pairs, d_est, st)
+                            : aim_pair_select_device(&pp, K, rs, n_reads, d_rl, d_seg, d_sam, d_cls, d_contig, d_res_sam, p.cigar_cap, p.md_cap, d_pairs, st);
     return rc;
 }
 
@@ -641,9 +652,12 @@ int aim_mapper_submit(aim_mapper_t *m, uint32_t slot, uint32_t n_reads, const in
     if (!rc)
         rc = aim_sam_device_split(&m->ap.base, rows, d_seg_req, d_seg_tp, nullptr, d_res, d_ops, m->d_ref, m->ref_len, p.sam_options, d_sam, at<uint32_t>(m, s, B_CIGAR),
                                   p.cigar_cap, at<char>(m, s, B_MD), p.md_cap, d_cursors, d_seg, st);
+    if (!rc && m->combined)              // rule 17c: part 2 of rule 16c moves in front of the pairing, which reads and rewrites its d_sec
+        rc = aim_secondary_select_device(K, n_reads, d_seg, d_sam, d_cls, d_chains, p.max_score, p.mismatch, at<aim_sec_slot_t>(m, s, B_SEC), st);
     if (!rc && m->paired) rc = submit_pairing(m, s, n_reads, st);   // rule 14c in front of the record kernel: rescue, select / apply
     if (!rc && m->secondary) {           // ... part 2: one winner per locus; part 3: the records over loci
-        rc = aim_secondary_select_device(K, n_reads, d_seg, d_sam, d_cls, d_chains, p.max_score, p.mismatch, at<aim_sec_slot_t>(m, s, B_SEC), st);
+        if (!m->combined)
+            rc = aim_secondary_select_device(K, n_reads, d_seg, d_sam, d_cls, d_chains, p.max_score, p.mismatch, at<aim_sec_slot_t>(m, s, B_SEC), st);
         if (!rc)
             rc = aim_map_records_secondary_device(K, n_reads, m->sc.options, d_seg, d_sam, d_cls, at<aim_sec_slot_t>(m, s, B_SEC), n_contigs ? d_contig : nullptr, n_contigs,
                                                   n_contigs ? m->d_contig_start : nullptr, d_off, at<aim_map_record_t>(m, s, B_RECORDS),
@@ -652,7 +666,10 @@ int aim_mapper_submit(aim_mapper_t *m, uint32_t slot, uint32_t n_reads, const in
         rc = n_contigs ? aim_map_records_contigs_device(K, n_reads, d_seg, d_sam, d_cls, d_contig, n_contigs, m->d_contig_start, d_off,
                                                         at<aim_map_record_t>(m, s, B_RECORDS), at<void>(m, s, B_MAP_SCRATCH), kMapScratch, st)
                        : aim_map_records_device(K, n_reads, d_seg, d_sam, d_cls, d_off, at<aim_map_record_t>(m, s, B_RECORDS), at<void>(m, s, B_MAP_SCRATCH), kMapScratch, st);
-    if (!rc && m->paired)                // ... and behind it: the mate fields
+    if (!rc && m->combined)              // ... and behind it: the mate fields, the representative from d_sec
+        rc = aim_map_mates_secondary_device(K, n_reads, at<aim_map_pair_t>(m, s, B_PAIRS), d_seg, d_sam, at<aim_sec_slot_t>(m, s, B_SEC), n_contigs ? d_contig : nullptr,
+                                            n_contigs, m->d_contig_start, d_off, at<aim_map_record_t>(m, s, B_RECORDS), at<aim_map_mate_t>(m, s, B_MATES), st);
+    else if (!rc && m->paired)           // ... and behind it: the mate fields
         rc = aim_map_mates_device(K, n_reads, at<aim_map_pair_t>(m, s, B_PAIRS), d_seg, d_sam, n_contigs ? d_contig : nullptr, n_contigs, m->d_contig_start, d_off,
                                   at<aim_map_record_t>(m, s, B_RECORDS), at<aim_map_mate_t>(m, s, B_MATES), st);
     if (rc) {
@@ -713,6 +730,8 @@ int aim_mapper_wait(aim_mapper_t *m, uint32_t slot, aim_mapper_out_t *out)
         if (po.rescue_md_bytes) HIP_TRY(hipMemcpyAsync(s.h_md + m->p.md_cap, at<char>(m, s, B_MD) + m->p.md_cap, po.rescue_md_bytes, hipMemcpyDeviceToHost, s.stream));
         HIP_TRY(hipMemcpyAsync(s.h_mates, at<char>(m, s, B_MATES), sizeof(aim_map_mate_t) * (size_t)po.n_records, hipMemcpyDeviceToHost, s.stream));
         HIP_TRY(hipMemcpyAsync(s.h_pairs, at<char>(m, s, B_PAIRS), sizeof(aim_map_pair_t) * (size_t)po.n_pairs, hipMemcpyDeviceToHost, s.stream));
+        if (m->combined)                 // rule 17c: one aim_map_pair_mapq_t per pair
+            HIP_TRY(hipMemcpyAsync(s.h_pair_mapq, at<char>(m, s, B_PAIR_MAPQ), sizeof(aim_map_pair_mapq_t) * (size_t)po.n_pairs, hipMemcpyDeviceToHost, s.stream));
     }
     HIP_TRY(hipStreamSynchronize(s.stream));
     return AIM_OK;
@@ -736,19 +755,56 @@ int aim_mapper_pairing_device_bytes(const aim_mapper_params_t *params, const aim
     return AIM_OK;
 }
 
+// rule 17c: what aim_mapper_set_pairing_secondary adds over all slots (without the estimate's buffers, as aim_mapper_pairing_device_bytes)
+int aim_mapper_pairing_secondary_device_bytes(const aim_mapper_params_t *params, const aim_map_pair_params_t *pp, const aim_map_sec_params_t *sp, uint64_t *bytes)
+{
+    const char *fn = "aim_mapper_pairing_secondary_device_bytes";
+    if (const int rc = check_mapper_params(fn, params, 0)) return rc;
+    if (const int rc = check_pairing(fn, *params, pp)) return rc;
+    if (const int rc = check_secondary(fn, sp)) return rc;
+    if (!bytes) return fail(AIM_EINVAL, "%s: bytes is NULL", fn);
+    const aim_endsfree_params_t ap = align_params(*params), rap = rescue_params(*params, *pp);
+    const size_t as = aim_scratch_bytes(&ap.base, (uint32_t)((uint64_t)params->max_reads * (uint64_t)params->seed.max_cands));
+    const size_t rsb = (pp->options & AIM_PAIR_RESCUE) ? aim_scratch_bytes(&rap.base, params->max_reads) : 0;
+    if (!as || ((pp->options & AIM_PAIR_RESCUE) && !rsb)) return under(fn, AIM_ENOMEM);
+    *bytes = (uint64_t)params->slots * (slot_layout(*params, as, false, pp, rsb, nullptr, true).total - slot_layout(*params, as, false).total);
+    return AIM_OK;
+}
+
 }  // extern "C"
 
 namespace {
 
-// aim_mapper_set_pairing and, with `estimate`, aim_mapper_set_pairing_estimated: the first's refusals, then ep's
-int set_pairing(const char *fn, aim_mapper *m, const aim_map_pair_params_t *pp, bool estimate, const aim_pair_est_params_t *ep)
+// What the two setters of rules 14c / 15c refuse of the mapper's state: one the new setter has touched, one with secondaries, a second call.
+int state_for_pairing(const char *fn, const aim_mapper *m)
+{
+    if (m->combined) return fail(AIM_EINVAL, "%s: the mapper pairs over secondaries (aim_mapper_set_pairing_secondary): it is paired already", fn);
+    if (m->secondary) return fail(AIM_EINVAL, "%s: the mapper aligns secondaries (aim_mapper_set_secondary): aim_mapper_set_pairing_secondary switches both on, in one call on a fresh mapper", fn);
+    if (m->paired) return fail(AIM_ESTATE, "%s: pairing is already set", fn);
+    return AIM_OK;
+}
+
+// ... and the setter of rule 17c: a second call of its own, and a mapper any of the three earlier setters has touched.
+int state_for_pairing_secondary(const char *fn, const aim_mapper *m)
+{
+    if (m->combined) return fail(AIM_ESTATE, "%s: pairing over secondaries is already set", fn);
+    if (m->paired) return fail(AIM_EINVAL, "%s: the mapper is paired (aim_mapper_set_pairing): call this setter on a mapper no other setter has touched", fn);
+    if (m->secondary) return fail(AIM_EINVAL, "%s: the mapper aligns secondaries (aim_mapper_set_secondary): call this setter on a mapper no other setter has touched", fn);
+    return AIM_OK;
+}
+
+// aim_mapper_set_pairing and, with `estimate`, aim_mapper_set_pairing_estimated: the first's refusals, then ep's; with `sp`,
+// aim_mapper_set_pairing_secondary (rule 17c): check_pairing, ep's rules where ep is given, check_secondary, then the mapper's state
+int set_pairing(const char *fn, aim_mapper *m, const aim_map_pair_params_t *pp, bool estimate, const aim_pair_est_params_t *ep, const aim_map_sec_params_t *sp = nullptr,
+                bool combined = false)
 {
     if (!m) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
     if (const int rc = check_pairing(fn, m->p, pp)) return rc;
     if (estimate)
         if (const int rc = check_pair_est_params(fn, ep)) return rc;
-    if (m->secondary) return fail(AIM_EINVAL, "%s: the mapper aligns secondaries (aim_mapper_set_secondary): pairing together with them is not in this version", fn);
-    if (m->paired) return fail(AIM_ESTATE, "%s: pairing is already set", fn);
+    if (combined)
+        if (const int rc = check_secondary(fn, sp)) return rc;
+    if (const int rc = combined ? state_for_pairing_secondary(fn, m) : state_for_pairing(fn, m)) return rc;
     for (uint32_t i = 0; i < m->p.slots; ++i)
         if (m->slot[i].in_flight) return fail(AIM_ESTATE, "%s: slot %u is in flight (aim_mapper_wait first)", fn, i);
     HIP_TRY(hipSetDevice(m->device));
@@ -760,11 +816,11 @@ int set_pairing(const char *fn, aim_mapper *m, const aim_map_pair_params_t *pp, 
         rsb = aim_scratch_bytes(&rap.base, p.max_reads);
         if (!rsb) return under(fn, AIM_ENOMEM);
     }
-    const SlotLayout L = slot_layout(p, m->align_scratch, !m->starts.empty(), pp, rsb, estimate ? ep : nullptr);
+    const SlotLayout L = slot_layout(p, m->align_scratch, !m->starts.empty(), pp, rsb, estimate ? ep : nullptr, combined);
     // Each slot moves to buffers of the new layout; nothing is in flight and no slot keeps state between batches. The new buffers come
     // first, so a failure leaves the mapper as it was.
     char *dev[AIM_MAPPER_MAX_SLOTS] = {};
-    void *host[AIM_MAPPER_MAX_SLOTS][6] = {};
+    void *host[AIM_MAPPER_MAX_SLOTS][8] = {};
     int rc = AIM_OK;
     auto make = [&]() -> int {
         for (uint32_t i = 0; i < p.slots; ++i) {
@@ -776,6 +832,10 @@ int set_pairing(const char *fn, aim_mapper *m, const aim_map_pair_params_t *pp, 
                 if (const int r = pinned(&host[i][j], sizes[j])) return r;
             if (estimate)
                 if (const int r = pinned(&host[i][5], sizeof(aim_pair_estimate_t))) return r;
+            if (combined) {
+                if (const int r = pinned(&host[i][6], sizeof(aim_map_sec_t) * N * K)) return r;
+                if (const int r = pinned(&host[i][7], sizeof(aim_map_pair_mapq_t) * ((N + 1) / 2))) return r;
+            }
         }
         HIP_TRY(hipDeviceSynchronize());
         return AIM_OK;
@@ -798,6 +858,10 @@ int set_pairing(const char *fn, aim_mapper *m, const aim_map_pair_params_t *pp, 
         s.h_cigar = static_cast<uint32_t *>(host[i][0]); s.h_md = static_cast<char *>(host[i][1]);
         s.h_mates = static_cast<aim_map_mate_t *>(host[i][2]); s.h_pairs = static_cast<aim_map_pair_t *>(host[i][3]); s.h_res_head = static_cast<uint32_t *>(host[i][4]);
         s.h_est = static_cast<aim_pair_estimate_t *>(host[i][5]);
+        if (combined) {
+            s.h_sec = static_cast<aim_map_sec_t *>(host[i][6]);
+            s.h_pair_mapq = static_cast<aim_map_pair_mapq_t *>(host[i][7]);
+        }
         s.waited = false;
     }
     m->L = L;
@@ -809,6 +873,11 @@ int set_pairing(const char *fn, aim_mapper *m, const aim_map_pair_params_t *pp, 
     m->rap = rap;
     m->rescue_scratch = rsb;
     m->paired = true;
+    if (combined) {
+        m->sc = *sp;
+        m->secondary = true;
+        m->combined = true;
+    }
     return AIM_OK;
 }
 
@@ -822,6 +891,25 @@ int aim_mapper_set_pairing(aim_mapper_t *m, const aim_map_pair_params_t *pp) { r
 int aim_mapper_set_pairing_estimated(aim_mapper_t *m, const aim_map_pair_params_t *pp, const aim_pair_est_params_t *ep)
 {
     return set_pairing("aim_mapper_set_pairing_estimated", m, pp, true, ep);
+}
+
+// rule 17c (AIM_FEATURE_PAIR_SECONDARY): pairing, the estimate when ep is given, and secondaries in one call
+int aim_mapper_set_pairing_secondary(aim_mapper_t *m, const aim_map_pair_params_t *pp, const aim_pair_est_params_t *ep, const aim_map_sec_params_t *sp)
+{
+    return set_pairing("aim_mapper_set_pairing_secondary", m, pp, ep != nullptr, ep, sp, true);
+}
+
+int aim_mapper_pair_mapq(aim_mapper_t *m, uint32_t slot, const aim_map_pair_mapq_t **out)
+{
+    const char *fn = "aim_mapper_pair_mapq";
+    if (!m) return fail(AIM_EINVAL, "%s: mapper is NULL", fn);
+    if (slot >= m->p.slots) return fail(AIM_EINVAL, "%s: slot %u is outside 0..%u", fn, slot, m->p.slots - 1);
+    if (!out) return fail(AIM_EINVAL, "%s: out is NULL", fn);
+    if (!m->combined) return fail(AIM_ESTATE, "%s: aim_mapper_set_pairing_secondary was not called", fn);
+    const MapperSlot &s = m->slot[slot];
+    if (s.in_flight || !s.waited) return fail(AIM_ESTATE, "%s: slot %u has no batch waited for (aim_mapper_wait first)", fn, slot);
+    *out = s.h_pair_mapq;                // [aim_mapper_pairs' n_pairs]
+    return AIM_OK;
 }
 
 int aim_mapper_pair_estimate(aim_mapper_t *m, uint32_t slot, aim_pair_estimate_t *out)
@@ -873,7 +961,7 @@ int aim_mapper_set_secondary(aim_mapper_t *m, const aim_map_sec_params_t *sp)
     if (m->secondary) return fail(AIM_EINVAL, "%s: secondaries are already set", fn);
     for (uint32_t i = 0; i < m->p.slots; ++i)
         if (m->slot[i].in_flight) return fail(AIM_EINVAL, "%s: slot %u is in flight (aim_mapper_wait first)", fn, i);
-    if (m->paired) return fail(AIM_EINVAL, "%s: the mapper is paired (aim_mapper_set_pairing): pairing together with secondaries is not in this version", fn);
+    if (m->paired) return fail(AIM_EINVAL, "%s: the mapper is paired (aim_mapper_set_pairing): aim_mapper_set_pairing_secondary switches both on, in one call on a fresh mapper", fn);
     HIP_TRY(hipSetDevice(m->device));
     const aim_mapper_params_t &p = m->p;
     const SlotLayout L = slot_layout(p, m->align_scratch, !m->starts.empty(), nullptr, 0, nullptr, true);

@@ -48,26 +48,7 @@ int check_pair_est_params(const char *fn, const aim_pair_est_params_t *ep)
 }  // namespace capi
 }  // namespace aim
 
-namespace {
-
-// a buffer against its alignment; the message names it
-bool aligned_ok(const char *fn, const void *p, uintptr_t align, const char *name)
-{
-    return !((uintptr_t)p & (align - 1u)) || refuse("%s: %s must be %u-byte aligned", fn, name, (unsigned)align);
-}
-
-bool contigs_ok(const char *fn, bool contigs, uint32_t n_contigs, bool tables)
-{
-    return !contigs || (((n_contigs >= 1 && n_contigs <= AIM_CONTIG_MAX) || refuse("%s: n_contigs %u is outside 1..%u", fn, n_contigs, AIM_CONTIG_MAX)) &&
-                        (tables || refuse("%s: d_contig is given without its contig table", fn)));
-}
-
-uint32_t pair_grid(const aim::Knobs &kn, uint64_t units, uint32_t per_block)
-{
-    return (uint32_t)std::min<uint64_t>(aim::resident_grid(kn, aim::kPairPerCu), (units + per_block - 1u) / per_block);
-}
-
-}  // namespace
+using aim::pair_grid;
 
 extern "C" {
 

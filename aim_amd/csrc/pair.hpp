@@ -66,7 +66,15 @@ struct MatesArgs {
     aim_map_mate_t *mates;
 };
 
-#ifdef AIM_TU_PAIR   // the kernels live in tu_pair.hip alone; capi_pair.hip sees the arguments and the launchers
+// The grid of a kernel that walks `units` items, per_block to a workgroup: what is resident at the most.
+inline uint32_t pair_grid(const Knobs &kn, uint64_t units, uint32_t per_block)
+{
+    const uint64_t blocks = (units + per_block - 1u) / per_block;
+    return (uint32_t)(blocks < resident_grid(kn, kPairPerCu) ? blocks : resident_grid(kn, kPairPerCu));
+}
+
+// The device helpers: what tu_pair.hip's kernels and those of rule 17c (pair_secondary.hpp in tu_pair_secondary.hip) share.
+#if defined(AIM_TU_PAIR) || defined(AIM_TU_PAIR_SECONDARY)
 
 static_assert(sizeof(aim_sam_t) == 48 && sizeof(aim_map_record_t) == 64 && sizeof(aim_segment_t) == 8 && sizeof(aim_chain_class_t) == 8 &&
                   sizeof(aim_map_pair_t) == 32 && sizeof(aim_map_mate_t) == 16 && sizeof(aim_request_t) == 16,
@@ -191,6 +199,10 @@ __device__ __forceinline__ uint32_t pair_read_len(const PairArgs &a, bool live, 
 {
     return live ? (uint32_t)min(max(a.read_len[r], 0), (int)a.read_size) : 0u;
 }
+
+#endif
+
+#ifdef AIM_TU_PAIR   // the kernels live in tu_pair.hip alone; capi_pair.hip sees the arguments and the launchers
 
 // G: lanes per read pair, 4, 8 or 16 and at least K (workgroup-uniform, like every loop bound below: every lane takes every exchange).
 // The body is pair_rescue_rows_body.inc: one text for this kernel and its rule-15c twin.

@@ -863,6 +863,39 @@ def map_records_secondary_device(K, n_reads, options, d_seg, d_sam, d_class, d_s
                                                             d_rec_offsets, d_records, d_sec_records, d_scratch, int(scratch_bytes), stream))
 
 
+def pair_rescue_rows_secondary_device(pp, K, read_size, ref_len, n_reads, d_read_len, d_reads, d_seg, d_sam, d_sec, d_res_requests, d_res_text_pos, d_res_patterns,
+                                      d_est=None, d_contig=None, n_contigs=0, d_contig_start=None, d_contig_len=None, stream=None):
+    """aim_pair_rescue_rows_secondary_device (rule 17c): pair_rescue_rows_device over the slots d_sec -- secondary_select_device's output --
+    gave a role, anchored at the mate's representative. d_est (capi.PAIR_ESTIMATE_DTYPE on the device) replaces pp's span bounds."""
+    capi.check(capi.load().aim_pair_rescue_rows_secondary_device(C.byref(pp), int(K), int(read_size), int(ref_len), int(n_contigs), d_contig_start, d_contig_len,
+                                                                 int(n_reads), d_read_len, d_reads, d_seg, d_sam, d_contig, d_sec, d_res_requests, d_res_text_pos,
+                                                                 d_res_patterns, d_est, stream))
+
+
+def pair_select_secondary_device(pp, K, read_size, n_reads, d_read_len, d_seg, d_sam, d_class, d_sec, d_chains, score_unit, d_res_sam, cigar_base, md_base, d_pairs,
+                                 d_pair_mapq, d_est=None, d_contig=None, stream=None):
+    """aim_pair_select_secondary_device (rule 17c): rule 14c's choice over primaries and aligned secondaries -> d_pairs, the MAPQ of both
+    reads from the pair's runner-up -> d_pair_mapq (capi.MAP_PAIR_MAPQ_DTYPE per pair), and apply: the chosen slots' MAPQ and roles into
+    d_sec, a chosen rescue row into the slot arrays. Only enqueues work."""
+    capi.check(capi.load().aim_pair_select_secondary_device(C.byref(pp), int(K), int(read_size), int(n_reads), d_read_len, d_seg, d_sam, d_class, d_contig, d_sec,
+                                                            d_chains, int(score_unit), d_res_sam, int(cigar_base), int(md_base), d_pairs, d_pair_mapq, d_est, stream))
+
+
+def map_mates_secondary_device(K, n_reads, d_pairs, d_seg, d_sam, d_sec, d_rec_offsets, d_records, d_mates, d_contig=None, n_contigs=0, d_contig_start=None,
+                               stream=None):
+    """aim_map_mates_secondary_device, behind map_records_secondary_device: map_mates_device with the mate's representative read from
+    d_sec; 0x100 records get mate fields, never 0x2. Only enqueues work."""
+    capi.check(capi.load().aim_map_mates_secondary_device(int(K), int(n_reads), d_pairs, d_seg, d_sam, d_sec, d_contig, int(n_contigs), d_contig_start, d_rec_offsets,
+                                                          d_records, d_mates, stream))
+
+
+def mapper_pairing_secondary_device_bytes(mp, pp, sc):
+    """aim_mapper_pairing_secondary_device_bytes: the device memory Mapper.set_pairing_secondary adds, over all slots (without an estimate's)."""
+    b = C.c_uint64()
+    capi.check(capi.load().aim_mapper_pairing_secondary_device_bytes(C.byref(mp), C.byref(pp), C.byref(sc), C.byref(b)))
+    return b.value
+
+
 def mapper_secondary_device_bytes(mp, sc):
     """aim_mapper_secondary_device_bytes: the device memory Mapper.set_secondary adds, over all slots."""
     b = C.c_uint64()
@@ -912,6 +945,7 @@ class Mapper:
     pairing = None
     estimate = None
     secondaries = None
+    combined = False
 
     def __init__(self, mp, reference, device=0):
         self.lib = capi.load()
@@ -969,6 +1003,21 @@ class Mapper:
         capi.check(self.lib.aim_mapper_set_secondary(self.handle, C.byref(sc)))
         self.secondaries = sc
 
+    def set_pairing_secondary(self, pp, sc=None, estimate=None):
+        """aim_mapper_set_pairing_secondary (rule 17c): pairing, the estimate when pair_estimate_params() is given, and secondaries in one
+        call on a mapper no other setter has touched. wait's dict then has everything set_pairing and set_secondary add plus "pair_mapq"
+        (capi.MAP_PAIR_MAPQ_DTYPE per read pair): the MAPQ of both reads from the pair's runner-up."""
+        sc = secondary_params() if sc is None else sc
+        capi.check(self.lib.aim_mapper_set_pairing_secondary(self.handle, C.byref(pp), C.byref(estimate) if estimate is not None else None, C.byref(sc)))
+        self.pairing, self.estimate, self.secondaries, self.combined = pp, estimate, sc, True
+
+    def pair_mapq(self, slot):
+        """aim_mapper_pair_mapq after wait(slot): a view of the capi.MAP_PAIR_MAPQ_DTYPE array parallel to "pairs"."""
+        po, v = capi.MapperPairsOut(), C.c_void_p()
+        capi.check(self.lib.aim_mapper_pair_mapq(self.handle, int(slot), C.byref(v)))
+        capi.check(self.lib.aim_mapper_pairs(self.handle, int(slot), C.byref(po)))
+        return _view(v.value, po.n_pairs, capi.MAP_PAIR_MAPQ_DTYPE)
+
     def secondary(self, slot):
         """aim_mapper_secondary after wait(slot): a view of the capi.MAP_SEC_DTYPE array parallel to "records"."""
         so = capi.MapperSecondaryOut()
@@ -1018,6 +1067,8 @@ class Mapper:
                 res["pair_estimate"] = self.pair_estimate(slot)
         if self.secondaries is not None:
             res["sec"] = self.secondary(slot)
+        if self.combined:
+            res["pair_mapq"] = self.pair_mapq(slot)
         return res
 
 

@@ -201,19 +201,19 @@ def main(argv=None):
     with open(args.out, "w") as fh, make(mp, ref, device=args.device) as m:
         if args.reads2:
             span = args.max_span - args.min_span + read_size
+            pp = engine.pair_params(args.min_span, args.max_span, args.unpaired_penalty, rescue=not args.no_rescue,
+                                    rescue_size=args.rescue_size if args.rescue_size is not None else engine.round_up_8(max(span, read_size)),
+                                    rescue_cigar_cap=args.batch * 64, rescue_md_cap=args.batch * 256)
+            est = engine.pair_estimate_params(args.est_hist_size, args.est_min_samples, args.est_min_mapq, args.est_min_slack) if args.estimate_span else None
             try:
-                m.set_pairing(engine.pair_params(args.min_span, args.max_span, args.unpaired_penalty, rescue=not args.no_rescue,
-                                                 rescue_size=args.rescue_size if args.rescue_size is not None else engine.round_up_8(max(span, read_size)),
-                                                 rescue_cigar_cap=args.batch * 64, rescue_md_cap=args.batch * 256),
-                              estimate=engine.pair_estimate_params(args.est_hist_size, args.est_min_samples, args.est_min_mapq, args.est_min_slack)
-                              if args.estimate_span else None)
+                if args.secondary:                    # rule 17c: pairing over the aligned secondaries, MAPQ from the pair's runner-up
+                    m.set_pairing_secondary(pp, engine.secondary_params(args.secondary, records=not args.no_secondary_lines), estimate=est)
+                else:
+                    m.set_pairing(pp, estimate=est)
             except capi.AimError as e:
                 print("aim_amd.map: %s" % e, file=sys.stderr)
                 return 2
-        if args.secondary:
-            if args.reads2:
-                print("aim_amd.map: --secondary together with --reads2 is not in this version", file=sys.stderr)
-                return 2
+        elif args.secondary:
             try:
                 m.set_secondary(engine.secondary_params(args.secondary, records=not args.no_secondary_lines))
             except capi.AimError as e:

@@ -14,7 +14,11 @@ specification recommends; with both reads unmapped RNAME / RNEXT are `*` and the
 A result of a mapper with secondaries (rule 16c: `out` carries "sec", one aim_map_sec_t per record) marks every mapped line: `tp:A:P`
 on a locus record, `tp:A:S` on a secondary record (FLAG 0x100). A secondary line has SEQ and QUAL `*`, as the SAM specification allows
 for secondary alignments, MAPQ 0 and no SA tag, and the SA tags of the other lines list non-secondary records only. MAPQ of a locus
-record is rule 16c's: from the alignment scores of the locus' copies, capped by the chain's anchors."""
+record is rule 16c's: from the alignment scores of the locus' copies, capped by the chain's anchors.
+
+A result of a mapper with both (rule 17c, Mapper.set_pairing_secondary) carries "mates" and "sec": paired lines with `tp:A:P` /
+`tp:A:S`. A `0x100` line gets the mate fields of any line -- 0x1, 0x40 / 0x80, 0x8 / 0x20, RNEXT and PNEXT -- never 0x2, TLEN 0, and
+`*` for SEQ and QUAL. MAPQ of the two chosen records of a proper pair is rule 17c's, from the pair's runner-up."""
 import numpy as np
 
 from . import capi, engine

@@ -1343,7 +1343,7 @@ int aim_mapper_contigs(const aim_mapper_t *mapper, uint32_t *n_contigs, const ui
  *       AIM_SAM_OVERFLOW on the rescued records and rescue_*_needed above rescue_*_words / _bytes.
  *       A mapper on which aim_mapper_set_pairing was never called gives the bytes it always gave.
  * aim_pair_kernel_names: "pair_rescue_rows_kernel,pair_select_kernel,map_mates_kernel".
- * Not in this version: a pair MAPQ (the span bounds estimated from the data: rule 15c below), rescue against anchors other than the representative,
+ * Not in this version (a pair MAPQ: rule 17c below; the span bounds estimated from the data: rule 15c below): rescue against anchors other than the representative,
  * keeping a rescued read's discordant placement as a secondary line, mates that overlap so far that pos_r < pos_f, pairing inside
  * aim_set_submit or host.c, AIM_FLAG_TOP_HITS rows. Check aim_features() & AIM_FEATURE_PAIRED first. */
 #define AIM_PAIR_RESCUE 0x1u            /* aim_map_pair_params_t.options: try the mate rescue */
@@ -1560,9 +1560,9 @@ int aim_mapper_pair_estimate(aim_mapper_t *mapper, uint32_t slot, aim_pair_estim
  *       before the first wait, while the slot is in flight and on a mapper without secondaries). Refusals, AIM_EINVAL under the entry
  *       point's name before any device query, in this order: a NULL params, max_sec outside 1..AIM_SEC_MAX, unknown option bits, a
  *       NULL mapper, a second call, a slot in flight, a paired mapper -- and likewise the two pairing setters on a mapper with
- *       secondaries: rule 14c rewrites the slot arrays, and combining the two is a follow-up.
+ *       secondaries: rule 14c rewrites the slot arrays; aim_mapper_set_pairing_secondary (rule 17c) switches both on in one call.
  * aim_secondary_kernel_names: "secondary_rows_kernel,secondary_select_kernel,map_count_sec_kernel,map_records_sec_kernel".
- * Not in this version: pairing together with secondaries, secondaries beyond the kept K, a pair MAPQ, AIM_FLAG_TOP_HITS rows, the
+ * Not in this version (pairing together with secondaries and a pair MAPQ: rule 17c below): secondaries beyond the kept K, AIM_FLAG_TOP_HITS rows, the
  * voting kernel's clusters, hard clips, trimming overlapping neighbour segments, a stage inside aim_set_submit or host.c. Check
  * aim_features() & AIM_FEATURE_SECONDARY first. */
 #define AIM_FEATURE_SECONDARY 0x800000u /* rule 16c: aim_secondary_rows_device / aim_secondary_select_device / aim_map_records_secondary_device / aim_mapper_set_secondary / aim_mapper_secondary exist */
@@ -1611,6 +1611,104 @@ const char *aim_secondary_kernel_names(void);
 int aim_mapper_secondary_device_bytes(const aim_mapper_params_t *params, const aim_map_sec_params_t *sp, uint64_t *bytes);
 int aim_mapper_set_secondary(aim_mapper_t *mapper, const aim_map_sec_params_t *sp);
 int aim_mapper_secondary(aim_mapper_t *mapper, uint32_t slot, aim_mapper_secondary_out_t *out);
+
+/* ---- pairing over aligned secondaries, a MAPQ per read from the pair's runner-up (AIM_FEATURE_PAIR_SECONDARY) ----------------------
+ * Rule 16c lets the alignment choose the copy of a repeat a read belongs to, rule 14c lets the mate choose -- but over the primaries
+ * alone, so it reaches the right copy only through a rescue alignment, and almost never sees a second proper combination. Rule 17c is
+ * rule 14c over every slot rule 16c aligned: the copy next to the mate is already a slot, and the runner-up among the combinations is
+ * what a paired-end MAPQ is made from. The sequence is rule 16c's up to aim_secondary_select_device, which now runs in front of the
+ * pairing; then [aim_pair_estimate_device, unchanged] -> aim_pair_rescue_rows_secondary_device -> the alignment and the records of the
+ * rescue rows (rule 14c's calls, unchanged) -> aim_pair_select_secondary_device -> aim_map_records_secondary_device (unchanged) ->
+ * aim_map_mates_secondary_device. Rule 17c reads d_sec as part 2 of rule 16c wrote it and rewrites it. Arithmetic is signed 64-bit;
+ * everything is deterministic and independent of the grid and of the AIM_DEBUG_POISON_* knobs.
+ *   17c. A slot TAKES PART when it is mapped (rule 12c) and d_sec[slot].role is not 0; part 2 of rule 16c gives a role to every mapped
+ *       slot the pipeline produces, a secondary that got a row under part 1 included. The REPRESENTATIVE of read r is the slot of role 1
+ *       in the family of lowest j that has a winner: the record part 3 leaves without AIM_SAM_SUPPLEMENTARY. (Not rule 12c's lowest
+ *       mapped slot: a family's winner may be a secondary.) Where rule 14c says "read r has a mapped slot", rule 17c says "read r has
+ *       a representative". Proper combination, span and cost are rule 14c's, over the slots that take part plus index K for a usable
+ *       rescue row; primaries, supplementary primaries and secondaries count alike; (K, K) is excluded.
+ *       Bounds. min_span and max_span are pp's, or those of the aim_pair_estimate_t at d_est when d_est is not NULL (rule 15c; pp's
+ *       own still have to pass rule 14c's checks). One kernel serves both cases.
+ *       Rescue rows (aim_pair_rescue_rows_secondary_device). Rule 14c's text with the representative as the anchor: tried when options
+ *       has AIM_PAIR_RESCUE, the mate has a representative, no proper combination exists among the slots that take part -- a copy
+ *       that already fits the mate costs no rescue -- and L > 0. Windows, empty rows, pattern rows and the contig clip are rule 14c's.
+ *       Choice (aim_pair_select_secondary_device). Rule 14c's: lowest cost, ties to the lowest i and then the lowest j; n_best and
+ *       second_sum as there. The unpaired cost is score(rep_a) + score(rep_b) + unpaired_penalty, clamped alike, and exists when both
+ *       reads have a representative. The proper combination is taken when there is no unpaired cost or its cost is no higher.
+ *       aim_map_pair_t keeps its layout and its meaning (not taken: slot[] = the representatives). On slot arrays in which no secondary
+ *       has a row every aim_map_pair_t equals rule 14c's byte for byte.
+ *       Pair MAPQ, for a taken combination (vi, vj) of cost c, for read a = 2m (read b alike with j, vj): alt_a is the lower of the
+ *       lowest cost among the proper combinations with i != vi and, where it exists and a's representative is not slot vi, the
+ *       unpaired cost; INT32_MAX with neither. tied_a is the number of proper combinations with i != vi and cost c. pair_mapq_a is 0
+ *       when tied_a > 0, 60 when alt_a is INT32_MAX, otherwise min(60, 6 * max(alt_a - c, 0) / score_unit). own_a is
+ *       d_sec[slot].mapq when the chosen slot has role 1 (before apply), 0 for a role-2 slot and for a rescue row.
+ *       mapq_a = min(max(own_a, min(pair_mapq_a, own_a + 40)), cap_a), where cap_a is rule 16c's anchor_cap of the chosen slot's own
+ *       chain (d_chains) and, for a rescue row, the mate's mapq, computed first. So a unique mate keeps its 60 while its partner in a
+ *       tied repeat gets 0, and a read that pairing moved off its alignment winner gets 6 * (unpaired_penalty - score difference) /
+ *       score_unit. aim_map_pair_mapq_t[m] holds alt, mapq, pair_mapq, own_mapq and tied (saturating at 255) of both reads; for a
+ *       combination that is not taken, zeros with alt_sum INT32_MAX.
+ *       Apply (inside aim_pair_select_secondary_device). Not taken: no byte of d_sec or of the slot arrays changes. A chosen slot of
+ *       role 1: its d_sec.mapq becomes mapq_a. A chosen slot of role 2: it and its family's role-1 slot exchange roles -- the promoted
+ *       slot gets role 1, mapq_a, aln_mapq 0, gap 0 and AIM_SEC_SWAPPED exactly when it is not the family's j; the demoted slot gets
+ *       role 2 and mapq 0, and thereby becomes the 0x100 record under AIM_SEC_RECORDS; every other byte of the family stays. A chosen
+ *       rescue row of read b: rule 14c's apply to d_sam, d_seg and d_contig; the mapq byte of d_class[b * K] becomes that of
+ *       d_class[the anchor's family slot], which is what part 3 reports as chain_mapq; d_sec[b * K] becomes {role 1, family 0, mapq_b,
+ *       aln_mapq 0, n_tied 1, AIM_SEC_COMPLETE, gap 65535} and the read's other d_sec entries 8 zero bytes.
+ *       Mate fields (aim_map_mates_secondary_device), behind aim_map_records_secondary_device. Rule 14c's, with the mate's reference
+ *       record its chosen slot if the pair is proper, else its representative, read from d_sec as apply left it; "the mate has no
+ *       mapped slot" reads "the mate has no slot of role 1". AIM_SAM_SECONDARY records get 0x1, 0x40 / 0x80, 0x8 / 0x20 and the mate's
+ *       position like any record; they never get 0x2, and their tlen is 0.
+ *   Kernels (csrc/pair_secondary.hpp): pair_sec_rescue_rows_kernel, pair_sec_select_kernel, map_mates_sec_kernel. A read pair gets 4, 8
+ *       or 16 lanes by K as in rule 14c, candidate i of both reads with its d_sec entries in lane i; the per-read alternatives come from
+ *       a second pass of K broadcasts. No LDS, no scratch memory, no atomics. The calls only enqueue work on hip_stream.
+ *       AIM_EINVAL under the entry point's name, before any device query: everything the rule-14c counterpart refuses, in its order;
+ *       aim_pair_select_secondary_device a score_unit < 1, in front of the NULL-buffer check; a NULL d_sec, d_chains or d_pair_mapq
+ *       with n_reads > 0; d_sec or d_chains not 8-byte aligned, d_pair_mapq or a given d_est not 16-byte aligned.
+ * aim_pair_secondary_kernel_names: "pair_sec_rescue_rows_kernel,pair_sec_select_kernel,map_mates_sec_kernel".
+ *   Precondition. d_sec is what aim_secondary_select_device wrote for these slot arrays: a slot with a role is mapped, and a role-2 slot
+ *       has a role-1 slot in its family. The kernels stay inside the read's slots for any d_sec, but their bytes are defined for such a one only.
+ *   Mapper. aim_mapper_set_pairing_secondary(m, &pp, ep_or_null, &sp) switches on pairing, the estimate when ep is given, and
+ *       secondaries in one call, with the state rules of aim_mapper_set_pairing. Refusals, AIM_EINVAL under its name before any device
+ *       query, in this order: a NULL mapper, aim_mapper_set_pairing's of pp, ep's rules (rule 15c) when ep is given, rule 16c's of sp;
+ *       then a mapper any of the three earlier setters has touched (AIM_ESTATE for a second call of its own, and for a slot in flight).
+ *       The earlier setters refuse a mapper this one has touched. It allocates what aim_mapper_set_pairing[_estimated] and
+ *       aim_mapper_set_secondary allocate plus one aim_map_pair_mapq_t per read pair and slot;
+ *       aim_mapper_pairing_secondary_device_bytes reports the sum without the estimate's buffers. aim_mapper_submit runs the
+ *       sequence above with score_unit = mismatch; aim_mapper_wait copies aim_map_pair_mapq_t[n_reads / 2] as well. aim_mapper_pairs,
+ *       aim_mapper_secondary and aim_mapper_pair_estimate work as on the mappers of their own setters; aim_mapper_pair_mapq(m, slot,
+ *       &view) gives the aim_map_pair_mapq_t[n_pairs] of the last batch waited for on the slot, with aim_mapper_pairs' state rules.
+ *       A mapper set up by an earlier setter, or by none, keeps its buffers and every byte it gave.
+ * Not in this version: rescue against anchors other than the representative; a
+ * rescued read's discordant placement as a secondary line; a pair MAPQ on a mapper paired without secondaries; compaction of the rescue
+ * rows; pairing inside aim_set_submit or host.c. Check aim_features() & AIM_FEATURE_PAIR_SECONDARY first. */
+#define AIM_FEATURE_PAIR_SECONDARY 0x1000000u /* rule 17c: aim_pair_rescue_rows_secondary_device / aim_pair_select_secondary_device / aim_map_mates_secondary_device / aim_mapper_set_pairing_secondary / aim_mapper_pair_mapq exist */
+typedef struct aim_map_pair_mapq {  /* 16 B, one per read pair m; [0]: read 2m, [1]: read 2m + 1 */
+    int32_t alt_sum[2];            /* lowest cost of what places the read elsewhere; INT32_MAX: nothing does, or not taken */
+    uint8_t mapq[2];               /* what apply wrote into d_sec of the chosen slot */
+    uint8_t pair_mapq[2];          /* from alt_sum and tied alone */
+    uint8_t own_mapq[2];           /* the chosen slot's MAPQ before apply; 0 for a role-2 slot and a rescue row */
+    uint8_t tied[2];               /* combinations that place the read elsewhere at the taken cost, saturating at 255 */
+} aim_map_pair_mapq_t;
+int aim_pair_rescue_rows_secondary_device(const aim_map_pair_params_t *pp, uint32_t K, uint32_t read_size, uint64_t ref_len, uint32_t n_contigs,
+                                          const uint32_t *d_contig_start, const uint32_t *d_contig_len, uint32_t n_reads, const int32_t *d_read_len,
+                                          const char *d_reads, const aim_segment_t *d_seg, const aim_sam_t *d_sam, const uint32_t *d_contig_or_null,
+                                          const aim_sec_slot_t *d_sec, void *d_res_requests, uint64_t *d_res_text_pos, char *d_res_patterns,
+                                          const aim_pair_estimate_t *d_est_or_null, void *hip_stream);
+int aim_pair_select_secondary_device(const aim_map_pair_params_t *pp, uint32_t K, uint32_t read_size, uint32_t n_reads, const int32_t *d_read_len,
+                                     aim_segment_t *d_seg, aim_sam_t *d_sam, aim_chain_class_t *d_class, uint32_t *d_contig_or_null,
+                                     aim_sec_slot_t *d_sec /* in/out */, const aim_chain_t *d_chains, int32_t score_unit,
+                                     const aim_sam_t *d_res_sam /* [n_reads]; may be NULL without AIM_PAIR_RESCUE */, uint32_t cigar_base, uint32_t md_base,
+                                     aim_map_pair_t *d_pairs /* [n_reads / 2] */, aim_map_pair_mapq_t *d_pair_mapq /* [n_reads / 2] */,
+                                     const aim_pair_estimate_t *d_est_or_null, void *hip_stream);
+int aim_map_mates_secondary_device(uint32_t K, uint32_t n_reads, const aim_map_pair_t *d_pairs, const aim_segment_t *d_seg, const aim_sam_t *d_sam,
+                                   const aim_sec_slot_t *d_sec, const uint32_t *d_contig_or_null, uint32_t n_contigs, const uint32_t *d_contig_start,
+                                   const uint32_t *d_rec_offsets, aim_map_record_t *d_records, aim_map_mate_t *d_mates /* [n_reads * K] */,
+                                   void *hip_stream);
+/* Comma-separated rocprofv3 kernel-trace name prefixes of the three kernels rule 17c adds. */
+const char *aim_pair_secondary_kernel_names(void);
+int aim_mapper_pairing_secondary_device_bytes(const aim_mapper_params_t *params, const aim_map_pair_params_t *pp, const aim_map_sec_params_t *sp, uint64_t *bytes);
+int aim_mapper_set_pairing_secondary(aim_mapper_t *mapper, const aim_map_pair_params_t *pp, const aim_pair_est_params_t *ep_or_null, const aim_map_sec_params_t *sp);
+int aim_mapper_pair_mapq(aim_mapper_t *mapper, uint32_t slot, const aim_map_pair_mapq_t **out /* [n_pairs of aim_mapper_pairs] */);
 /* The plan aim_align_device would follow for (params, n_pairs) in this process right now, as one line (see
  * aim_set_plan_describe).  The stateless entry points read the AIM_* switches at every call. */
 int aim_plan_describe(const aim_params_t *params, uint32_t n_pairs, char *out, size_t cap);
